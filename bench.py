@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the AdaIN hot path on MI355X (BASELINE.json metric: stylised Mpixels/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--dump-outputs DIR]
 N > 1: one process per GPU.  Either launched by ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``, or
 typed bare (``python bench.py --gpus N``): the bare process then starts N fresh rank processes itself BEFORE anything touches a
 GPU (subprocesses, never an exec), hands rank 0's JSON line through, and exits with the worst child's status.
@@ -642,6 +642,38 @@ def cpu_baseline(step, gpu_out, job_frames=None, job_depth=None):
     }, psnr, rel
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: float32 bytes written at most, all arrays together
+
+
+def capture_outputs(arrays):
+    """``--dump-outputs``: ``arrays`` = {name: tensor} that the timed path returned in its last step -> {name: (float32 numpy array,
+    description)} on the host, taken straight after the timed region (later legs reuse the step's buffers).  Arrays holding more than
+    DUMP_BUDGET_BYTES as float32 in all are each cut to the same share of their elements: a seeded sample of flat indices
+    (``numpy.random.default_rng(0).choice(n, k, replace=False)``, ascending), identical from run to run for the same arguments."""
+    total = 4 * sum(int(t.numel()) for t in arrays.values())
+    out = {}
+    for name, t in arrays.items():
+        n = int(t.numel())
+        desc = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")}
+        if total > DUMP_BUDGET_BYTES:
+            k = max(1, n * DUMP_BUDGET_BYTES // total)
+            idx = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+            desc["sample"] = f"{k} of {n} elements: flat indices numpy.random.default_rng(0).choice({n}, {k}, replace=False), ascending"
+        else:
+            a = t.float().cpu().numpy()
+        out[name] = (a, desc)
+    return out
+
+
+def write_outputs(directory, captured):
+    """Writes ``capture_outputs``'s arrays as ``directory/<name>.npy``; returns what the JSON line says about them."""
+    os.makedirs(directory, exist_ok=True)
+    for name, (a, _) in captured.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {"dir": os.path.abspath(directory), "arrays": {name: desc for name, (_, desc) in captured.items()}}
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -680,7 +712,14 @@ def parse_args():
     ap.add_argument("--layers", action="store_true", help="also print the per-layer table to stderr")
     ap.add_argument("--rehearse", action="store_true",
                     help="single-GPU rehearsal of the multi-rank path: ranks may share a GPU and the gather may run over gloo (labelled in the JSON)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the timed path returned in its last step as DIR/<name>.npy (float32; "
+                         f"a fixed seeded sample of the elements when the arrays hold more than {DUMP_BUDGET_BYTES >> 20} MB in all)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must be at least 0")
     if args.job and args.config not in (4, 5):
         ap.error("--job runs the video job (--config 4) or the guide-view job (--config 5)")
     if args.depth and args.config != 4:
@@ -839,6 +878,7 @@ def main_job(args, ctx):
     telemetry.window("timed_region", info["t0"], info["t1"])
     if rank == 0:
         assert res is not None and res.shape == (n_total, h, w, 3), (None if res is None else res.shape)
+    dumped = capture_outputs({"output_u8": res}) if args.dump_outputs and rank == 0 else None     # the last job's gathered frames
     first_u8 = res[:2].clone() if rank == 0 else None
     per_rank = [None] * world
     mine = {k: round(float(info[k]), 4) for k in ("compute_s", "gather_s", "enqueue_s", "fetch_s", "host_cpu_s", "process_cpu_s")}
@@ -918,6 +958,8 @@ def main_job(args, ctx):
         if args.layers and layers:
             for i, L in enumerate(layers):
                 print(f"layer {i:2d}: {L['gflop']:8.2f} GF  {L['ms']:8.4f} ms  {L['tflops']:7.2f} TF/s", file=sys.stderr)
+        if dumped is not None:
+            result["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
         emit(result)
     ctx.finish(rank0_done=True)
 
@@ -934,7 +976,7 @@ def main_per_call(args, ctx):
 
     from applied_image_processing_amd.AdaIN import test as T
 
-    mode, n = args.per_call, max(4, args.steps)
+    mode, n = args.per_call, args.steps
     T.set_latency_schedule(args.schedule == "latency")
     h, w = ((270, 480) if mode == "video" else (800, 800)) if not args.size else (args.size, args.size)     # the callers' own shapes
     csize = 256 if mode == "video" else 512
@@ -989,6 +1031,8 @@ def main_per_call(args, ctx):
     gpu_ms = T._stage_timer.gpu_ms() / n
     same = all(open(a, "rb").read() == open(b, "rb").read() for a, b in zip(cached, plain))
     ch, cw = Image.open(cached[0]).size[::-1]
+    # the caller of the timed (cached) loop receives a JPEG file per call: the last call's, decoded
+    dumped = capture_outputs({"output_u8": torch.from_numpy(np.asarray(Image.open(cached[-1]).convert("RGB")))}) if args.dump_outputs else None
     result = {"metric": f"adain_inference calls/s, the reference's {'video' if mode == 'video' else 'guide-view'} caller loop unchanged "
                         "(file / PIL in, stylised JPEG file out)", "value": round(n / dt, 2), "unit": "calls/s", "n_gpus": 1, "steps": n,
               "warmup": args.warmup, "ms_per_step": round(dt * 1e3 / n, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -1027,6 +1071,8 @@ def main_per_call(args, ctx):
     import shutil
 
     shutil.rmtree(root, ignore_errors=True)
+    if dumped is not None:
+        result["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
     emit(result)
     ctx.finish()
 
@@ -1098,6 +1144,18 @@ def main():
     if use_dist and rank == 0:
         expect = n_job * (args.steps if args.gather == "end" else 1)
         assert gathered is not None and gathered.shape[0] == expect, (None if gathered is None else gathered.shape, expect)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's float frames (rank 0's) and, where the path quantises, its uint8 frames: with more than one rank the
+        # gathered frames of every rank (mode "end" gathers rank r's K steps as one block: the last step is the end of each block)
+        arrays = {"output": out}
+        if use_dist:
+            n_end = args.steps * args.batch
+            arrays["output_u8"] = (torch.cat([gathered[r * n_end + n_end - args.batch:(r + 1) * n_end] for r in range(world)])
+                                   if args.gather == "end" else gathered)
+        elif need_u8:
+            arrays["output_u8"] = step.u8
+        dumped = capture_outputs(arrays)
     del gathered
 
     # one isolated gather of one step's frames (nothing else in flight) for the transport's own cost
@@ -1201,6 +1259,8 @@ def main():
         # where this process's wall time went: the K timed steps are a fraction of a second of a run dominated by set-up and the CPU
         # baseline, so a utilisation sampler beside the whole run sees a mostly idle GPU
         result["run_phases_s"] = phases
+        if dumped is not None:
+            result["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
         emit(result)
     ctx.finish(rank0_done=True)           # (the other ranks wait on the store key since the per-rank table)
 

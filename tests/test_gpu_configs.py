@@ -280,12 +280,13 @@ def test_bench_front_door_starts_its_own_ranks():
     the line shows what the transport saw.  Without ``--rehearse`` two ranks on one GPU are refused with a clear message."""
     import json
 
-    r = _bench(["--gpus", "2", "--rehearse", "--no-cpu", "--no-secondary", "--steps", "3", "--warmup", "1", "--size", "256"])
+    # 40 steps: the telemetry samples every 10 ms, and 3 steps of a 256 x 256 frame (about 7 ms) can fall between two samples
+    r = _bench(["--gpus", "2", "--rehearse", "--no-cpu", "--no-secondary", "--steps", "40", "--warmup", "1", "--size", "256"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["rehearsal"]["ranks_share_a_gpu"]
+    assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["rehearsal"]["ranks_share_a_gpu"] and d["steps"] == 40
     assert d["gather"]["mode"] == "end" and d["gather"]["gathers_in_timed_region"] == 1
     assert d["ranks"]["world"] == 2 and d["ranks"]["allreduce_of_ones"] == 2 and len(d["ranks"]["devices"]) == 2
     assert d["ranks"]["launcher"] == "bench.py self-launch" and len({x["pid"] for x in d["ranks"]["devices"]}) == 2
@@ -301,3 +302,27 @@ def test_bench_front_door_starts_its_own_ranks():
     if __import__("torch").cuda.device_count() < 2:
         r = _bench(["--gpus", "2", "--no-cpu", "--steps", "3"], timeout=120)
         assert r.returncode != 0 and "2 ranks, one per GPU" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_are_the_last_steps_and_repeat(tmp_path):
+    """``bench.py --dump-outputs DIR``: the line counts exactly ``--steps`` timed steps and ``ms_per_step``, and DIR holds the last
+    step's float32 frame; the inputs are seeded, so runs with other step counts write the same bits (the forward is bitwise
+    repeatable).  Config 4 also dumps its uint8 frames, which are the float frame quantised."""
+    import json
+    import os
+
+    got = {}
+    for steps, cfg in ((2, 2), (5, 2), (3, 4)):
+        d = tmp_path / f"s{steps}_c{cfg}"
+        r = _bench(["--no-cpu", "--no-secondary", "--sustain", "0", "--config", str(cfg), "--size", "256", "--steps", str(steps), "--warmup", "1",
+                    "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and set(line["dumped_outputs"]["arrays"]) == ({"output"} if cfg == 2 else {"output", "output_u8"})
+        got[steps] = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert got[steps]["output"].dtype == np.float32 and got[steps]["output"].shape == (1, 3, 256, 256)
+        assert np.isfinite(got[steps]["output"]).all()
+    assert np.array_equal(got[2]["output"], got[5]["output"])
+    u8 = got[3]["output_u8"]
+    assert u8.dtype == np.float32 and u8.shape == (1, 256, 256, 3) and u8.min() >= 0 and u8.max() <= 255 and np.array_equal(u8, np.round(u8))
+    assert np.abs(u8 - np.clip(got[3]["output"], 0, 1).transpose(0, 2, 3, 1) * 255).max() <= 1.0

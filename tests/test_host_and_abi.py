@@ -284,6 +284,41 @@ def test_bench_launcher_stops_every_rank_when_one_fails_or_hangs(tmp_path):
     assert r.returncode == 124 and "did not finish within 3 s" in r.stderr and time.time() - t0 < 40, (r.returncode, r.stderr[-500:])
 
 
+def test_bench_dump_outputs_whole_or_seeded_sample(tmp_path):
+    """``bench.py --dump-outputs`` (CPU tensors stand in for the device's): arrays within the 64 MB budget are written whole as
+    float32 in their own shape; larger ones are cut to a seeded sample of ascending flat indices that is identical from call to
+    call and stays within the budget, each array keeping its share.  Run in a child: importing bench sets process environment."""
+    import subprocess
+    import sys
+
+    prog = tmp_path / "dump.py"
+    prog.write_text(
+        "import os, sys\n"
+        f"sys.path.insert(0, {ROOT!r})\n"
+        "import numpy as np, torch\n"
+        "import bench\n"
+        f"d = {str(tmp_path / 'out')!r}\n"
+        "small = {'output': torch.linspace(0, 1, 48).reshape(1, 3, 4, 4), 'output_u8': torch.arange(36, dtype=torch.uint8).reshape(1, 2, 6, 3)}\n"
+        "info = bench.write_outputs(d, bench.capture_outputs(small))\n"
+        "assert sorted(os.listdir(d)) == ['output.npy', 'output_u8.npy'] and info['arrays']['output_u8']['dtype'] == 'uint8'\n"
+        "for k, t in small.items():\n"
+        "    a = np.load(os.path.join(d, k + '.npy'))\n"
+        "    assert a.dtype == np.float32 and a.shape == tuple(t.shape) and np.array_equal(a, t.float().numpy())\n"
+        "g = torch.Generator().manual_seed(1)\n"
+        "big = {'output': torch.rand(2_000_000, generator=g), 'output_u8': torch.randint(0, 256, (20_000_000,), dtype=torch.uint8, generator=g)}\n"
+        "c1, c2 = bench.capture_outputs(big), bench.capture_outputs(big)\n"
+        "assert sum(a.nbytes for a, _ in c1.values()) <= bench.DUMP_BUDGET_BYTES\n"
+        "for k, t in big.items():\n"
+        "    a, desc = c1[k]\n"
+        "    assert a.dtype == np.float32 and np.array_equal(a, c2[k][0]) and 'sample' in desc\n"
+        "    n = t.numel(); want = n * bench.DUMP_BUDGET_BYTES // (4 * 22_000_000)\n"
+        "    idx = np.sort(np.random.default_rng(0).choice(n, want, replace=False))\n"
+        "    assert a.shape == (want,) and np.array_equal(a, t.numpy()[idx].astype(np.float32))\n")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, str(prog)], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
 @pytest.mark.parametrize("header", ["adain_hip.h", "adain_hip_diag.h"])
 def test_headers_are_plain_c_and_cxx(tmp_path, header):
     """The boundary is a C ABI: both headers compile on their own as strict C99 and as C++17 (no torch, no HIP types in any signature)."""
