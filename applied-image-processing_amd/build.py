@@ -14,7 +14,7 @@ LIB = os.path.join(PKG, "libadain_hip.so")
 DIAG_LIB = os.path.join(PKG, "libadain_hip_diag.so")     # -DADAIN_DIAG: env tuning switches, stamp / timing-only kernels (tools/ only)
 # Both libraries are these sources; the diagnostic one adds -DADAIN_DIAG (environment tuning switches, stamp / timing-only variants of
 # the F(4,3) x F(2,3) kernel).  The direct implicit-GEMM and F(2x2,3x3) families of rounds 1-2 were retired in round 6 (git history).
-SOURCES = ["conv_edge.hip", "conv_wino4.hip", "stats.hip", "pixel.hip", "resample.hip", "api.hip"]
+SOURCES = ["conv_edge.hip", "conv_wino4.hip", "stats.hip", "pixel.hip", "resample.hip", "flow.hip", "api.hip"]
 DIAG_SOURCES = []
 # -fvisibility=hidden: the shared library exports the C ABI of include/adain_hip.h (ADAIN_API) and nothing else
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]

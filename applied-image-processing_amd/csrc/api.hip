@@ -542,6 +542,27 @@ int adain_warp_blend_u8(const uint8_t* cur, const uint8_t* prev, const float* fl
     if (!cur || !prev || !flow || !out) { set_error("warp_blend_u8: null pointer"); return ADAIN_EINVAL; }
     return launch_warp_blend_u8(cur, prev, flow, out, h, w, c, alpha, one_minus_alpha, (hipStream_t)stream);
 }
+int adain_flow_gray_u8(const uint8_t* rgb_u8, int n, int hi, int wi, uint8_t* gray_u8, int ho, int wo, adain_stream_t stream) {
+    if (!rgb_u8 || !gray_u8) { set_error("flow_gray_u8: null pointer"); return ADAIN_EINVAL; }
+    return launch_flow_gray_u8(rgb_u8, n, hi, wi, gray_u8, ho, wo, (hipStream_t)stream);
+}
+int adain_farneback_levels(int h, int w, double pyr_scale, int levels, int* out_levels, int* sizes_wh, int* ksizes, double* sigmas) {
+    return farneback_levels(h, w, pyr_scale, levels, out_levels, sizes_wh, ksizes, sigmas);
+}
+size_t adain_farneback_pyramid_bytes(int h, int w, double pyr_scale, int levels) { return farneback_pyramid_bytes(h, w, pyr_scale, levels); }
+size_t adain_farneback_workspace_bytes(int h, int w) { return farneback_workspace_bytes(h, w); }
+int adain_farneback_expand(const uint8_t* gray_u8, int h, int w, double pyr_scale, int levels, int poly_n, double poly_sigma, float* pyramid,
+                           void* workspace, size_t workspace_bytes, adain_stream_t stream) {
+    if (!gray_u8 || !pyramid) { set_error("farneback_expand: null pointer"); return ADAIN_EINVAL; }
+    return launch_farneback_expand(gray_u8, h, w, pyr_scale, levels, poly_n, poly_sigma, pyramid, workspace, workspace_bytes,
+                                   (hipStream_t)stream);
+}
+int adain_farneback_flow(const float* pyr_prev, const float* pyr_next, int h, int w, double pyr_scale, int levels, int winsize, int iterations,
+                         int flags, float* flow_out, void* workspace, size_t workspace_bytes, adain_stream_t stream) {
+    if (!pyr_prev || !pyr_next || !flow_out) { set_error("farneback_flow: null pointer"); return ADAIN_EINVAL; }
+    return launch_farneback_flow(pyr_prev, pyr_next, h, w, pyr_scale, levels, winsize, iterations, flags, flow_out, workspace,
+                                 workspace_bytes, (hipStream_t)stream);
+}
 int adain_resize_area_u8(const uint8_t* in, uint8_t* out, int n, int hi, int wi, int c, int ho, int wo, adain_stream_t stream) {
     if (!in || !out) { set_error("resize_area_u8: null pointer"); return ADAIN_EINVAL; }
     return launch_resize_area_u8(in, out, n, hi, wi, c, ho, wo, (hipStream_t)stream);

@@ -146,6 +146,16 @@ size_t resize_pil_workspace_bytes(int hi, int wi, int ho, int wo);
 int launch_resize_pil_bilinear_u8(const uint8_t* in, int pixel_bytes, int n, int hi, int wi, uint8_t* out, int ho, int wo, int y0, int x0, int ch,
                                   int cw, void* workspace, size_t ws_bytes, hipStream_t s);
 
+// flow.hip: Farneback dense optical flow (OpenCV's calcOpticalFlowFarneback, flags 0) and the video callers' frame preparation
+int launch_flow_gray_u8(const uint8_t* rgb, int n, int hi, int wi, uint8_t* gray, int ho, int wo, hipStream_t s);
+int farneback_levels(int h, int w, double pyr_scale, int levels, int* out_levels, int* sizes_wh, int* ksizes, double* sigmas);
+size_t farneback_pyramid_bytes(int h, int w, double pyr_scale, int levels);
+size_t farneback_workspace_bytes(int h, int w);
+int launch_farneback_expand(const uint8_t* gray, int h, int w, double pyr_scale, int levels, int poly_n, double poly_sigma,
+                            float* pyramid, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_farneback_flow(const float* pyr_prev, const float* pyr_next, int h, int w, double pyr_scale, int levels, int winsize,
+                          int iterations, int flags, float* flow_out, void* ws, size_t ws_bytes, hipStream_t s);
+
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

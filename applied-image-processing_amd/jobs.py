@@ -818,8 +818,8 @@ def video_style_transfer_sharded(engine, frames, styles, *, flows=None, target_r
     given, which is how the reference runs it: ``use_depth=True``, offset 0.30, prominence 20), ``cv2.resize(...,
     target_resolution, INTER_AREA)`` of every stylised frame on its own rank (:352-353; ``target_resolution`` =
     (width, height)), ONE gather, then on ``dst`` the recurrence ``frame_i = blend(frame_i, warp(result_{i-1}, flow_{i-1}),
-    blend_alpha)`` (:355-368) over ``flows`` [n-1,2,H,W] (prev -> current, estimated by the caller: the optical-flow
-    estimator is OpenCV's and stays outside).  Returns ``(frames_u8 on dst | None, info)``."""
+    blend_alpha)`` (:355-368) over ``flows`` [n-1,2,H,W] (prev -> current at the target resolution: ``flow.FlowSequence().batch``
+    computes the reference's Farneback flows on the device, or the caller brings its own).  Returns ``(frames_u8 on dst | None, info)``."""
     n = len(frames)
     style_list = list(styles) if isinstance(styles, (list, tuple)) else [styles]
     post = out_hw = None

@@ -59,6 +59,15 @@ SIGNATURES = {
     "adain_u8_to_f32": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_warp_blend_u8": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_void_p]),
     "adain_resize_area_u8": (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 6 + [_c_void_p]),
+    "adain_flow_gray_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_void_p]),
+    "adain_farneback_levels": (_c_int, [_c_int, _c_int, ctypes.c_double, _c_int, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
+                                        ctypes.POINTER(_c_int), ctypes.POINTER(ctypes.c_double)]),
+    "adain_farneback_pyramid_bytes": (_c_size_t, [_c_int, _c_int, ctypes.c_double, _c_int]),
+    "adain_farneback_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
+    "adain_farneback_expand": (_c_int, [_c_void_p, _c_int, _c_int, ctypes.c_double, _c_int, _c_int, ctypes.c_double, _c_void_p, _c_void_p,
+                                        _c_size_t, _c_void_p]),
+    "adain_farneback_flow": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, ctypes.c_double, _c_int, _c_int, _c_int, _c_int, _c_void_p,
+                                      _c_void_p, _c_size_t, _c_void_p]),
     "adain_resize_pil_bilinear_u8_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "adain_resize_pil_bilinear_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p]),
     "adain_stylize_u8_workspace_bytes": (_c_size_t, [_c_int] * 9),

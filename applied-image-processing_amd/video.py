@@ -16,7 +16,10 @@ What stays with the caller, because the reference gets it from libraries this pa
     MiDaS through torch.hub per frame) — or pass ``depth_maps=``;
   * the optical flow: ``set_flow_provider(fn)`` with ``fn(prev_frame_path, frame_path, target_resolution, method) ->
     [2,H,W] float32`` (x then y displacement at the target resolution, what ``estimate_optical_flow`` returns for the two
-    resized frames, :75-86, :322-358) — OpenCV's Farnebäck / DualTV-L1 estimators are the caller's.
+    resized frames, :75-86, :322-358).  ``set_flow_provider(device_flow_provider)`` plugs in the package's own Farnebäck
+    estimator (flow.py, csrc/flow.hip: the reference's ``cv2.calcOpticalFlowFarneback(..., 0.5, 5, 15, 3, 7, 1.5, 0)`` on the
+    device); with it installed the rank-0 recurrence expands every frame once (flow.FlowSequence) instead of twice per pair.
+    DualTV-L1 is not built in: that method stays with a caller's provider.
 One deliberate difference: the reference writes every stylised frame as a JPEG into a temporary directory and reads it back
 (:261-273); here the uint8 frames stay in memory unless ``intermediate_jpeg=True`` re-creates that lossy round trip.
 """
@@ -47,6 +50,29 @@ def estimate_optical_flow(prev_frame_path, frame_path, target_resolution, method
                            "DualTV-L1 estimators here, which this package does not depend on)")
     f = _flow_provider(prev_frame_path, frame_path, target_resolution, method)
     return torch.as_tensor(np.asarray(f) if not isinstance(f, torch.Tensor) else f, dtype=torch.float32)
+
+
+def _decode_gray(path, target_resolution, device):
+    """cv2.imread + cv2.resize(target_resolution) + COLOR_RGB2GRAY of the reference (video/utils.py:75-77, :330-332), on the
+    device (flow.frames_to_gray).  Decoded with PIL, which does not apply the EXIF orientation cv2.imread applies (unpinned)."""
+    from . import flow as fl
+
+    rgb = torch.from_numpy(np.array(Image.open(path).convert("RGB"))).to(device)
+    return fl.frames_to_gray(rgb, target_resolution)
+
+
+def device_flow_provider(prev_frame_path, frame_path, target_resolution, method="farneback"):
+    """A flow provider (``set_flow_provider``) that runs the reference's Farnebäck call on the current GPU: both frames decoded,
+    resized and converted as the reference does, then ``cv2.calcOpticalFlowFarneback(prev, cur, None, 0.5, 5, 15, 3, 7, 1.5, 0)``
+    (flow.calc_optical_flow_farneback) -> [2,H,W] float32 on the device."""
+    from . import flow as fl
+
+    if method != "farneback":
+        raise ValueError(f"device_flow_provider: optical-flow method {method!r} is not built in (DualTV-L1 is not; use 'farneback' or "
+                         "install a provider of your own)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    prev, cur = _decode_gray(prev_frame_path, target_resolution, dev), _decode_gray(frame_path, target_resolution, dev)
+    return fl.calc_optical_flow_farneback(prev, cur, None, 0.5, 5, 15, 3, 7, 1.5, 0).permute(2, 0, 1).contiguous()
 
 
 def normalize_image(image):
@@ -141,12 +167,27 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
         try:
             n, h, w, _ = frames_u8.shape
             prev = None
+            seq = None
+            if _flow_provider is device_flow_provider and n > 1:
+                # the package's own estimator: every frame decoded and expanded ONCE (the pair path does both twice per pair);
+                # the same bits as device_flow_provider per pair
+                from . import flow as fl
+
+                if flow_method != "farneback":
+                    device_flow_provider(None, None, None, flow_method)       # raises: the method is not built in
+                seq = fl.FlowSequence(0.5, 5, 15, 3, 7, 1.5, 0)
+                with torch.cuda.device(frames_u8.device):
+                    seq.push(_decode_gray(os.path.join(content_dir, names[0]), (w, h), frames_u8.device))
             for i, name in enumerate(names):
                 if cancel_flag is not None and cancel_flag.is_set():
                     print("Stopping style transfer...")
                     break
                 cur = frames_u8[i]
-                if prev is not None:
+                if prev is not None and seq is not None:
+                    with torch.cuda.device(cur.device):
+                        flow = seq.push(_decode_gray(os.path.join(content_dir, name), (w, h), cur.device))
+                    cur = engine.warp_blend_u8(cur.contiguous(), prev, flow, alpha)
+                elif prev is not None:
                     flow = estimate_optical_flow(os.path.join(content_dir, names[i - 1]), os.path.join(content_dir, name), (w, h), flow_method)
                     cur = engine.warp_blend_u8(cur.contiguous(), prev, flow.to(cur.device), alpha)
                 sink.write(cur.unsqueeze(0), [os.path.join(output_dir, name)])

@@ -165,7 +165,8 @@ ADAIN_API int adain_u8_to_f32(const uint8_t* in_nhwc, float* out_nchw, int n, in
  * HWC uint8 frames [h][w][c]; flow [2][h][w] (x then y displacement, as estimate_optical_flow returns it,
  * video/utils.py:75-86).  out = u8(clip((alpha*cur/255 + one_minus_alpha*warp(prev)/255)*255, 0, 255)), warp =
  * cv2.remap(INTER_LINEAR, BORDER_REFLECT) in OpenCV's uint8 fixed point (map rounded to 1/32 px, 2^15-scaled weights,
- * (sum + 2^14) >> 15).  The optical-flow estimate itself stays with the caller (OpenCV). */
+ * (sum + 2^14) >> 15).  The flow can come from adain_farneback_flow below (the reference's Farneback estimator on the device) or
+ * from the caller. */
 ADAIN_API int adain_warp_blend_u8(const uint8_t* cur_u8, const uint8_t* prev_u8, const float* flow, uint8_t* out_u8, int h, int w,
                         int c, float alpha, float one_minus_alpha, adain_stream_t stream);
 
@@ -177,6 +178,36 @@ ADAIN_API int adain_warp_blend_u8(const uint8_t* cur_u8, const uint8_t* prev_u8,
  * pixels). */
 ADAIN_API int adain_resize_area_u8(const uint8_t* in_u8, uint8_t* out_u8, int n, int hi, int wi, int c, int ho, int wo,
                          adain_stream_t stream);
+
+/* ---- dense optical flow: cv2.calcOpticalFlowFarneback(prev, next, None, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma,
+ * 0) of OpenCV 4.x's CPU implementation (reference video/utils.py:75-86 runs it with 0.5, 5, 15, 3, 7, 1.5, 0) --------------------
+ * The rules (level schedule, Gaussian level images, polynomial expansion, matrix update, box-blur flow update, flow upscale) are
+ * restated at the top of csrc/flow.hip and in NumPy in tests/farneback_ref.py; parity with cv2 itself is not pinned.
+ *
+ * adain_flow_gray_u8: the callers' frame preparation, n packed RGB frames [n][hi][wi][3] (PIL's channel order) -> gray [n][ho][wo]:
+ *   cv2.resize(frame, (wo, ho)) on the BGR frame cv2.imread gives (uint8 INTER_LINEAR: 2048-scaled taps, VResizeLinear's fixed-point
+ *   combine; an exact 2x shrink is INTER_AREA's (a+b+c+d+2)>>2, an equal size a copy), then cv2.COLOR_RGB2GRAY applied to that BGR
+ *   data: gray = (4899 B + 9617 G + 1868 R + 8192) >> 14.
+ * adain_farneback_levels (host only): the pyramid schedule of an h x w frame: *out_levels = the effective `levels` L (L + 1 pyramid
+ *   levels); sizes_wh[2k], [2k+1] = width, height of level k (k = 0: full size ... L: coarsest), ksizes[k] / sigmas[k] = its Gaussian.
+ *   Each output may be NULL; the arrays need room for levels + 1 entries (pairs) of the REQUESTED levels.
+ * adain_farneback_expand: a frame's pyramid (gray uint8 [h][w] -> `pyramid`, adain_farneback_pyramid_bytes): per level k the level
+ *   image [h_k][w_k] then its polynomial expansion R [h_k][w_k][5] (OpenCV's channel order y, x, yy, xx, xy), each float block
+ *   256-byte aligned, levels in order k = 0, 1, ...  It depends on the frame only: a clip of N frames needs N expansions, each
+ *   used as `next` of one pair and `prev` of the following one.
+ * adain_farneback_flow: the flow from pyr_prev's frame to pyr_next's (both expanded with the same h, w, pyr_scale, levels) ->
+ *   flow_out [2][h][w] (x then y displacement, the layout adain_warp_blend_u8 consumes).
+ * One workspace (adain_farneback_workspace_bytes) serves both calls; calls that share it must be ordered (one stream).
+ * Refused with ADAIN_EINVAL: flags != 0 (OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN are not built), pyr_scale outside
+ * (0, 1), poly_n not 5 or 7, winsize outside [2, 63], iterations < 1, levels < 0. */
+ADAIN_API int adain_flow_gray_u8(const uint8_t* rgb_u8, int n, int hi, int wi, uint8_t* gray_u8, int ho, int wo, adain_stream_t stream);
+ADAIN_API int adain_farneback_levels(int h, int w, double pyr_scale, int levels, int* out_levels, int* sizes_wh, int* ksizes, double* sigmas);
+ADAIN_API size_t adain_farneback_pyramid_bytes(int h, int w, double pyr_scale, int levels);
+ADAIN_API size_t adain_farneback_workspace_bytes(int h, int w);
+ADAIN_API int adain_farneback_expand(const uint8_t* gray_u8, int h, int w, double pyr_scale, int levels, int poly_n, double poly_sigma,
+                                     float* pyramid, void* workspace, size_t workspace_bytes, adain_stream_t stream);
+ADAIN_API int adain_farneback_flow(const float* pyr_prev, const float* pyr_next, int h, int w, double pyr_scale, int levels, int winsize,
+                                   int iterations, int flags, float* flow_out, void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
 /* ---- test_transform's Resize [+ CenterCrop] on the device (test.py:16-24, applied at :190-204; video/utils.py:341-350) --------
  * PIL.Image.resize((wo, ho), BILINEAR) of uint8 RGB images, bit for bit (Pillow's ImagingResample: separable triangle filter whose
