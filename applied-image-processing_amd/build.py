@@ -11,11 +11,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 INC = os.path.join(os.path.dirname(PKG), "include")
 LIB = os.path.join(PKG, "libadain_hip.so")
-DIAG_LIB = os.path.join(PKG, "libadain_hip_diag.so")     # -DADAIN_DIAG: env tuning switches, stamp / timing-only kernels (tools/ only)
-# Both libraries are these sources; the diagnostic one adds -DADAIN_DIAG (environment tuning switches, stamp / timing-only variants of
-# the F(4,3) x F(2,3) kernel).  The direct implicit-GEMM and F(2x2,3x3) families of rounds 1-2 were retired in round 6 (git history).
+# The direct implicit-GEMM and F(2x2,3x3) families of rounds 1-2 were retired in round 6 (git history).
 SOURCES = ["conv_edge.hip", "conv_wino4.hip", "stats.hip", "pixel.hip", "resample.hip", "flow.hip", "api.hip"]
-DIAG_SOURCES = []
 # -fvisibility=hidden: the shared library exports the C ABI of include/adain_hip.h (ADAIN_API) and nothing else
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # The MFMA kernels carry their fp32 vector-ALU work (input transform, epilogues) next to the matrix instructions, where
@@ -39,25 +36,20 @@ def _newer(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=False, diag=False):
-    """Builds the product library; ``diag=True`` builds ``libadain_hip_diag.so`` instead (the same sources with -DADAIN_DIAG:
-    environment tuning switches, stamp / timing-only variants used by tools/).  A process loads it explicitly
-    with ``runtime.use_library(runtime.DIAG_LIB_PATH)`` - nothing in the environment selects it."""
-    objdir = os.path.join(PKG, "build_diag" if diag else "build")
+def build(force=False, verbose=False):
+    """Builds the library and returns its path."""
+    objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
-    lib = DIAG_LIB if diag else LIB
-    flags = FLAGS + (["-DADAIN_DIAG"] if diag else []) + os.environ.get("ADAIN_EXTRA_HIPCC_FLAGS", "").split()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(INC, "adain_hip.h"),
-               os.path.join(INC, "adain_hip_diag.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(INC, "adain_hip.h")]
     hipcc = _hipcc()
     jobs = []
     objs = []
-    for src in SOURCES + (DIAG_SOURCES if diag else []):
+    for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
         if force or _newer(o, [s] + headers):
-            jobs.append([hipcc] + flags + EXTRA_FLAGS.get(src, []) + ["-I", INC, "-c", s, "-o", o])
+            jobs.append([hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-I", INC, "-c", s, "-o", o])
 
     def run(cmd):
         if verbose:
@@ -71,14 +63,10 @@ def build(force=False, verbose=False, diag=False):
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(run, jobs))
-    if force or jobs or _newer(lib, objs):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
-    return lib
+    if force or jobs or _newer(LIB, objs):
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs)
+    return LIB
 
 
 if __name__ == "__main__":
-    if "--all" in sys.argv:
-        print(build(force="--force" in sys.argv, verbose=True))
-        print(build(force="--force" in sys.argv, verbose=True, diag=True))
-    else:
-        print(build(force="--force" in sys.argv, verbose=True, diag="--diag" in sys.argv))
+    print(build(force="--force" in sys.argv, verbose=True))

@@ -4,9 +4,6 @@
 #include <stdlib.h>
 
 #include "../../include/adain_hip.h"
-#ifdef ADAIN_DIAG
-#include "../../include/adain_hip_diag.h"
-#endif
 #include "common.h"
 
 namespace adain {
@@ -39,8 +36,8 @@ static size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 constexpr size_t FIRST_W = 2 * 14 * 64, FIRST_B = 64, LAST_W = 8 * 64 * 4, LAST_B = 3;
 
 // The generic 3x3 layers run - and the library only contains - the Winograd F(4,3) x F(2,3) kernels (csrc/conv_wino4.hip).  The direct
-// implicit GEMM and the F(2x2,3x3) families of rounds 1-2 were A/B baselines in the diagnostic build until round 6 and are retired
-// (git history; docs/HISTORY.md has their numbers).
+// implicit GEMM and the F(2x2,3x3) families of rounds 1-2 were A/B baselines until round 6 and are retired (git history;
+// docs/HISTORY.md has their numbers).
 static size_t form_floats(int cin, int cout) { return (size_t)cin * cout * 24; }
 
 // packed layout: [first w][first b] then per generic layer [w in the form the schedules launch][b], every block 256-B
@@ -220,34 +217,26 @@ size_t adain_encode_multi_workspace_bytes(int count, const int* n, const int* h,
 // batch, as they always did.  Results do not depend on the split.
 constexpr double BIG_LAYER_ROUNDS = 6.0;
 constexpr int BIG_FRAME_WIDTH = 1600;
-static double big_layer_rounds() {           // (diagnostic build: ADAIN_BIG_ROUNDS_X10, e.g. 10000000 = never frame by frame)
-    static const int v = tune_env("ADAIN_BIG_ROUNDS_X10", (int)(BIG_LAYER_ROUNDS * 10));
-    return v / 10.0;
-}
-static int big_frame_width() {               // (diagnostic build: ADAIN_BIG_FRAME_WIDTH, 0 = any width)
-    static const int v = tune_env("ADAIN_BIG_FRAME_WIDTH", BIG_FRAME_WIDTH);
-    return v;
-}
 
 // encoder: number of leading generic layers (0..7) run frame by frame = index after the LAST big layer.  conv4_1 (layer 7) is never
 // part of the prefix: it writes the caller's feature tensors, not the ping-pong buffers the frame-major pass works in, so it always
 // runs over the whole batch in the layer-major loop behind (a 1440 x 2560 frame's conv4_1 is 7.2 rounds and would count as big).
 static int enc_frame_major_layers(int n, int h, int w) {
-    if (n < 2 || w < big_frame_width()) return 0;
+    if (n < 2 || w < BIG_FRAME_WIDTH) return 0;
     int k = 0, ch = h, cw = w;
     for (int l = 0; l < 7; ++l) {
-        if (wino4_rounds_per_image(ch, cw, ENC[l].cout) >= big_layer_rounds()) k = l + 1;
+        if (wino4_rounds_per_image(ch, cw, ENC[l].cout) >= BIG_LAYER_ROUNDS) k = l + 1;
         if (ENC[l].pool) { ch = (ch + 1) / 2; cw = (cw + 1) / 2; }
     }
     return k;
 }
 // decoder: number of leading layers (0..8) run over the whole batch = index of the FIRST big layer (8: none is big)
 static int dec_batched_layers(int n, int hc, int wc) {
-    if (n < 2 || 8 * wc < big_frame_width()) return 8;
+    if (n < 2 || 8 * wc < BIG_FRAME_WIDTH) return 8;
     int ch = hc, cw = wc;
     for (int l = 0; l < 8; ++l) {
         if (DEC[l].src == SRC_UP2X) { ch *= 2; cw *= 2; }
-        if (wino4_rounds_per_image(ch, cw, DEC[l].cout) >= big_layer_rounds()) return l;
+        if (wino4_rounds_per_image(ch, cw, DEC[l].cout) >= BIG_LAYER_ROUNDS) return l;
     }
     return 8;
 }
@@ -714,8 +703,6 @@ int adain_stylize_u8(const uint8_t* frames, int n, int h, int w, const float* en
     return launch_quantize_u8(comp, out_u8, n, 3, h, w, s);
 }
 
-static unsigned long long* g_conv_dbg = nullptr;     // stamp buffer of the diagnostic kernels; always null in the product library
-
 size_t adain_conv3x3_wino4_packed_floats(int cin, int cout) { return (size_t)cin * cout * 24; }
 
 int adain_conv3x3_wino4_pack(const float* w, float* packed, int cin, int cout, adain_stream_t stream) {
@@ -733,7 +720,6 @@ int adain_conv3x3_wino(const float* in, float* out, const float* packed_w, const
         set_error("conv3x3_wino: form %d is retired (rounds 1-2: F(2x2,3x3) forms 1-4); this library runs form 5, F(4,3) x F(2,3)", mh);
         return ADAIN_EINVAL;
     }
-    a.dbg = g_conv_dbg;     // diagnostic builds only (tools/wino4_probe.py sets it)
     return launch_conv3x3_wino4(a, src_mode, (hipStream_t)stream);
 }
 
@@ -749,11 +735,5 @@ int adain_conv3x3_wino4_split(const float* in, float* out, const float* packed_w
     a.n = n; a.H = h; a.W = w; a.Hs = hs; a.Ws = ws; a.cin = cin; a.cout = cout; a.relu = relu; a.pool_out = pool_out ? 1 : 0;
     return launch_conv3x3_wino4(a, src_mode, (hipStream_t)stream, SplitWs{(float*)workspace, workspace ? ws_bytes / sizeof(float) : 0});
 }
-
-#ifdef ADAIN_DIAG
-/* ---- diagnostic library only (include/adain_hip_diag.h) -------------------------------------------------------------------- */
-int adain_debug_set_conv_stamp_buffer(void* p) { g_conv_dbg = (unsigned long long*)p; return 0; }
-
-#endif
 
 }  // extern "C"

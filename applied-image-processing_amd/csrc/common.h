@@ -27,9 +27,7 @@ struct ConvArgs {
     int cin, cout;
     int relu;
     int pool_out;       // 1: write only MaxPool2d(2,2,ceil_mode=True)(output), [n][ceil(H/2)][ceil(W/2)][cout]
-    int xcd_order;      // 1: XCD-aware block -> tile order (speed only)
     int tiles_x, tiles_y;
-    unsigned long long* dbg;   // diagnostic builds only (clock stamps); nullptr in production
     // cin split of the F(4,3) x F(2,3) one-tile form (set by launch_conv3x3_wino4 only): workgroups per (tile, channel tile),
     // input channels per workgroup, floats between the partial-sum slabs that `out` then points at
     int ksplit, cin_sub;
@@ -55,22 +53,8 @@ constexpr int MAX_CONV_SEGS = 4;
 struct ConvSegs {
     int count;
     int ctg;            // channel tiles per group of the persistent walk (divides cout / 32): see conv3x3_wino4_kernel
-    int stagger;        // start delay of the second half of the persistent grid in units of 64 cycles
-    int pad_;
     ConvSeg s[MAX_CONV_SEGS];
 };
-
-// Tuning and diagnostic switches exist only in the diagnostic build (-DADAIN_DIAG: libadain_hip_diag.so, loaded by tools/
-// through ADAIN_HIP_LIB): the product library takes no behaviour from the environment and holds no timing-only kernels.
-inline int tune_env(const char* name, int dflt) {
-#ifdef ADAIN_DIAG
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
 
 // thread-local error text for adain_last_error()
 void set_error(const char* fmt, ...);

@@ -92,13 +92,7 @@ constexpr int CF_OSTR = 68;      // floats per pixel of the row buffer: b128 wri
 //   * the weights are consumed before the loop (their waits used to sit at their first use INSIDE it, where in every later tile
 //     they waited for the previous tile's stores to be acknowledged).
 constexpr int CF_HBUF = 1024;    // floats per halo image slot (3 planes x 340 = 1020)
-// CFD (diagnostic library only, ADAIN_CF_DIAG; timing-only, wrong results by construction): 1 = no global stores, 2 = no MFMAs,
-// 3 = neither (round 5's ablations, tools/probes/cf_diag_ab.sh: 75.7 / 56.7 / 63.1 / 31.0 us at 1024 x 1024).
-// DEEP (round 6, the review's last structural A/B; diagnostic library, ADAIN_CF_DEEP=1): the halo loads run TWO tiles ahead - tile t
-// starts by writing tile t+1's halo (loaded during tile t-1, long arrived) into the other LDS image and then requests tile t+2's,
-// so a load has a whole tile period to arrive instead of one matrix phase; the stores are then unconditional (rows below the image
-// get an empty descriptor) so that the compiler's wait for those loads can leave the 16 younger stores in flight.
-template <bool U8, int CFD = 0, bool DEEP = false>
+template <bool U8>
 __global__ __launch_bounds__(256, 3) void conv_first_kernel(const void* __restrict__ img_any,
                                                             float* __restrict__ out, const float* __restrict__ wpk,
                                                             const float* __restrict__ bias, int H, int W, int tiles_x,
@@ -139,20 +133,14 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const void* __restri
                              __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src, voff, soff + 2 * pb, 0)), 0.f};
             }
         };
-        // DEEP: the second pixel's load is issued by EVERY thread (threads without one aim past the descriptor: the hardware returns 0
-        // without touching memory) - a load under a lane mask becomes a merge with the register's old value, and for a value that is
-        // carried over the loop's back edge the compiler then loads into a scratch register and waits for it at once
-        constexpr int CF_OOB = 0x7ffffff0;
         if (interior) {
             const int soff = ((ty0 - 1) * W + tx0 - 1) * EB;
             h0 = fetch(rel0, soff);
-            if constexpr (DEEP) h1 = fetch(second ? rel1 : CF_OOB, soff);
-            else if (second) h1 = fetch(rel1, soff);
+            if (second) h1 = fetch(rel1, soff);
         } else {
             auto at = [&](int hy, int hx) { return (reflect1(ty0 + hy - 1, H) * W + reflect1(tx0 + hx - 1, W)) * EB; };
             h0 = fetch(at(hy0, hx0), 0);
-            if constexpr (DEEP) h1 = fetch(second ? at(hy1, hx1) : CF_OOB, 0);
-            else if (second) h1 = fetch(at(hy1, hx1), 0);
+            if (second) h1 = fetch(at(hy1, hx1), 0);
         }
     };
     // halo registers -> LDS image `buf` (planar [r | g | b][10][34]: the K reads walk consecutive floats)
@@ -172,10 +160,6 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const void* __restri
     int t = blockIdx.x;
     if (t >= ntiles) return;
     halo_load(t);
-    if constexpr (DEEP) {        // tile t's halo to image 0 now; the registers then carry tile t + stride's
-        halo_to_lds(smem_all);
-        if (t + (int)gridDim.x < ntiles) halo_load(t + gridDim.x);
-    }
     // this lane's 2 x 14 weights (A operand; K index e = 2 g + lh) and the LDS index of halo element e = (tap, channel) for this
     // lane's pixel column in the wave's first row: held in registers over the tile walk
     float wf[2][14];
@@ -191,7 +175,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const void* __restri
     for (int g = 0; g < 14; ++g)
 #pragma unroll
         for (int c = 0; c < 2; ++c) asm volatile("" ::"v"(wf[c][g]));       // arrived BEFORE the loop (see above)
-    if constexpr (!DEEP) halo_to_lds(smem_all);
+    halo_to_lds(smem_all);
     float* const st = smem_all + 2 * CF_HBUF + wave * (32 * CF_OSTR);        // this wave's row buffer
     // per-lane constants of the epilogue: where this lane's four channels of pixel li go in the row buffer, which 16 bytes of the
     // row buffer it reads back (pixel 4 k + lane / 16, quad lane % 16) and where those go in the output row
@@ -206,13 +190,7 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const void* __restri
         const int tx0 = (pt % tiles_x) * 32, ty0 = (pt / tiles_x) * 8;
         __syncthreads();                                 // halo image `par` is complete (and image 1 - par is free, see above)
         const int tn = t + gridDim.x;
-        if constexpr (DEEP) {
-            // the registers hold tile tn's halo since the previous tile: into the free image, then the request for the tile after it
-            if (tn < ntiles) halo_to_lds(smem_all + (1 - par) * CF_HBUF);
-            if (tn + (int)gridDim.x < ntiles) halo_load(tn + gridDim.x);
-        } else {
-            if (tn < ntiles) halo_load(tn);              // in flight during this tile's MFMAs
-        }
+        if (tn < ntiles) halo_load(tn);                  // in flight during this tile's MFMAs
 
         f32x16 acc[2][2];      // [channel tile][row of this wave]
 #pragma unroll
@@ -232,15 +210,11 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const void* __restri
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    if constexpr (CFD == 2 || CFD == 3) acc[c][m][g & 15] += wf[c][g] * xf[m];      // timing-only: operands kept alive, no MFMA
-                    else acc[c][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[c][g], xf[m], acc[c][m], 0, 0, 0);
-                }
+                for (int m = 0; m < 2; ++m) acc[c][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[c][g], xf[m], acc[c][m], 0, 0, 0);
         }
         // the next tile's halo goes to the OTHER LDS image here, before this tile's stores are issued (loads and stores share one
         // in-flight counter on gfx9: consumed later, the prefetched loads would wait for every store issued in between)
-        if constexpr (!DEEP)
-            if (tn < ntiles) halo_to_lds(smem_all + (1 - par) * CF_HBUF);
+        if (tn < ntiles) halo_to_lds(smem_all + (1 - par) * CF_HBUF);
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const int y = ty0 + wave * 2 + m;            // wave-uniform
@@ -260,17 +234,15 @@ __global__ __launch_bounds__(256, 3) void conv_first_kernel(const void* __restri
                     }
                     *(f32x4*)(st_w + 32 * c + 8 * q) = v;
                 }
-            if (DEEP || y < H) {
+            if (y < H) {
                 // this output row from the tile's first pixel to the END OF THE ROW: pixels right of the image fall outside the
                 // descriptor and are dropped by the hardware; the row buffer is private to the wave and LDS operations of one wave
-                // complete in order: no barrier.  (DEEP: a row below the image gets an EMPTY descriptor instead of a branch.)
-                const bool row_ok = y < H;
-                const rsrc_t dst = make_rsrc(out + (((size_t)img * H + (row_ok ? y : 0)) * W + tx0) * 64, row_ok ? (unsigned)(W - tx0) * 256u : 0u);
+                // complete in order: no barrier
+                const rsrc_t dst = make_rsrc(out + (((size_t)img * H + y) * W + tx0) * 64, (unsigned)(W - tx0) * 256u);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const f32x4 v = *(const f32x4*)(st_r + 4 * k * CF_OSTR);
-                    if constexpr (CFD == 1 || CFD == 3) asm volatile("" ::"v"(v));        // timing-only: no global stores
-                    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), dst, vo + k * 1024, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), dst, vo + k * 1024, 0, 0);
                 }
             }
         }
@@ -299,11 +271,10 @@ __device__ __forceinline__ void static_for(F&& f) {
     [&]<int... I>(std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, N>{});
 }
 
-// CLD (diagnostic library only, ADAIN_CL_DIAG): 1 = no MFMAs (memory side alone: 60-63 us at 1024 x 1024), 2 = every load of a
-// group from one address (matrix side alone: 57 us), 4 = tiles in launch order (no XCD ranges: 68 us); product: 63-65 us.
-// TH = tile height: 16 (612 halo pixels = 20 groups of 32, 5 per wave; T = 69 KB: two workgroups per CU; the product) or 12
-// (476 pixels = 15 groups, the fourth wave takes 3; T = 52 KB: three workgroups per CU; diagnostic library, ADAIN_CL_TH=12:
-// 64.3-64.5 us against 64.5-65.5 on the same box - the third workgroup buys nothing here, unlike in conv_first).
+// Tile height CL_TH = 16: 612 halo pixels = 20 groups of 32, 5 per wave; T = 69 KB: two workgroups per CU.  (A 12-row tile with
+// three workgroups per CU measured the same - 64.3-64.5 us against 64.5-65.5 on the same box - the third workgroup buys nothing here,
+// unlike in conv_first.)
+constexpr int CL_TH = 16;
 // U8OUT (round 6): the image leaves as what torchvision's save_image makes of it (reference test.py:243-244) - x * 255 + 0.5, clamped to
 // [0, 255], truncated, uint8 HWC [n][H][W][3] - straight from the registers that hold the float pixel: adain_quantize_u8's arithmetic
 // operation for operation (the multiply and the add round separately: __fmul_rn / __fadd_rn, this file is compiled with contraction
@@ -314,11 +285,11 @@ __device__ __forceinline__ unsigned cl_quant1(float x) {
     v = fminf(fmaxf(v, 0.f), 255.f);
     return (unsigned)v;
 }
-template <int CLD, int TH, bool U8OUT = false>
-__global__ __launch_bounds__(256, TH == 12 ? 3 : 2) void conv_last_kernel(const float* __restrict__ in, void* __restrict__ out_any,
-                                                                          const float* __restrict__ wpk, const float* __restrict__ bias,
-                                                                          int H, int W, int tiles_x, int tiles_y) {
-    constexpr int NPX = (TH + 2) * HW_, NGRP = (NPX + 31) / 32, GPW = (NGRP + 3) / 4, SLOTS = NGRP * 32;
+template <bool U8OUT>
+__global__ __launch_bounds__(256, 2) void conv_last_kernel(const float* __restrict__ in, void* __restrict__ out_any,
+                                                           const float* __restrict__ wpk, const float* __restrict__ bias,
+                                                           int H, int W, int tiles_x, int tiles_y) {
+    constexpr int NPX = (CL_TH + 2) * HW_, NGRP = (NPX + 31) / 32, GPW = (NGRP + 3) / 4, SLOTS = NGRP * 32;
     __shared__ float T[27 * SLOTS];                                          // [n'][pixel slot]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -327,10 +298,10 @@ __global__ __launch_bounds__(256, TH == 12 ? 3 : 2) void conv_last_kernel(const 
     // the workgroups of one XCD (blockIdx % 8) take a contiguous range of the tile list: the halo rows and columns that
     // neighbouring tiles share are re-read from that XCD's L2 (speed only)
     int lid = blockIdx.x;
-    if (CLD != 4 && (gridDim.x & 7) == 0) lid = (lid & 7) * (gridDim.x >> 3) + (lid >> 3);
+    if ((gridDim.x & 7) == 0) lid = (lid & 7) * (gridDim.x >> 3) + (lid >> 3);
     const int pt = lid % tiles, img = lid / tiles;
-    const int tx0 = (pt % tiles_x) * TW, ty0 = (pt / tiles_x) * TH;
-    // the source descriptor starts at the first row the tile's halo can touch: offsets stay inside TH + 2 rows
+    const int tx0 = (pt % tiles_x) * TW, ty0 = (pt / tiles_x) * CL_TH;
+    // the source descriptor starts at the first row the tile's halo can touch: offsets stay inside CL_TH + 2 rows
     const int srow0 = max(ty0 - 1, 0);
     const size_t sleft = (size_t)(H - srow0) * W * 256;
     const rsrc_t src = make_rsrc(in + ((size_t)img * H + srow0) * W * 64, sleft < 0x7ffffff0ull ? (unsigned)sleft : 0x7ffffff0u);
@@ -347,7 +318,7 @@ __global__ __launch_bounds__(256, TH == 12 ? 3 : 2) void conv_last_kernel(const 
         const int y = reflect1(ty0 + hy - 1, H), x = reflect1(tx0 + hx - 1, W);
         const int off = ((y - srow0) * W + x) * 256 + lh * 16;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) bx[g % RB][j] = buf_load4(src, off, CLD == 2 ? 0 : j * 32);
+        for (int j = 0; j < 8; ++j) bx[g % RB][j] = buf_load4(src, off, j * 32);
     };
     f32x4 wq[8];
 #pragma unroll
@@ -367,10 +338,7 @@ __global__ __launch_bounds__(256, TH == 12 ? 3 : 2) void conv_last_kernel(const 
 #pragma unroll
             for (int j = 0; j < 8; ++j)
 #pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    if constexpr (CLD == 1) acc[(j * 4 + s) & 15] += wq[j][s] * bx[g % RB][j][s];
-                    else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wq[j][s], bx[g % RB][j][s], acc, 0, 0, 0);
-                }
+                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wq[j][s], bx[g % RB][j][s], acc, 0, 0, 0);
             // D[row n' = (r & 3) + 8 (r >> 2) + 4 lh][column = this lane's pixel] -> plane n' of T: a store instruction writes 32
             // consecutive floats per lane half, and the shifted sum below reads consecutive floats too (no bank conflicts either way)
             float* rec = T + (lh * 4) * SLOTS + (4 * g + wave) * 32 + px;
@@ -388,7 +356,7 @@ __global__ __launch_bounds__(256, TH == 12 ? 3 : 2) void conv_last_kernel(const 
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int yy = oy + 8 * r;
-        if (yy >= TH) break;
+        if (yy >= CL_TH) break;
         float o0 = b0, o1 = b1, o2 = b2;
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy)
@@ -411,8 +379,8 @@ __global__ __launch_bounds__(256, TH == 12 ? 3 : 2) void conv_last_kernel(const 
         }
         if constexpr (U8OUT) {
             // this lane's pixel as 24 bits, then lane 4 q gathers the pixels of lanes 4 q .. 4 q + 3 (the same output row: a row is 32
-            // lanes) into three dwords; W is a multiple of 8 (the decoder's output is 8 hc x 8 wc) and the launcher checked the base
-            // pointer's alignment, so the 12 bytes sit on a dword boundary and a group of four pixels is inside the row or outside it
+            // lanes) into three dwords; the launcher checked W % 4 == 0 and a 4-byte aligned base pointer, so (x a multiple of 4) the
+            // 12 bytes sit on a dword boundary and a group of four pixels is inside the row or outside it
             const unsigned w0 = cl_quant1(o0) | (cl_quant1(o1) << 8) | (cl_quant1(o2) << 16);
             const unsigned w1 = __shfl_down(w0, 1), w2 = __shfl_down(w0, 2), w3 = __shfl_down(w0, 3);
             if ((ox & 3) == 0 && y < H && x < W) {
@@ -451,30 +419,8 @@ int launch_conv_first(const void* img, int u8, float* out, const float* packed, 
     if (ntiles > 0x7fffffffLL) { set_error("conv_first: bad grid"); return -1; }
     const int cus = device_cu_count();
     if (cus <= 0) { set_error("conv_first: device query failed"); return -1; }
-    long long per_cu = 3;                                                  // 3 workgroups per CU walk the tiles (same box: 2: 85 us, 3: 80, 4: 90)
-#ifdef ADAIN_DIAG
-    static const int wgs_env = tune_env("ADAIN_CF_WGS", 3);
-    per_cu = wgs_env;
-#endif
+    const long long per_cu = 3;                                            // 3 workgroups per CU walk the tiles (same box: 2: 85 us, 3: 80, 4: 90)
     const long long grid = ntiles < per_cu * cus ? ntiles : per_cu * cus;
-#ifdef ADAIN_DIAG
-    // timing-only ablations and the two-tiles-ahead variant (tools/probes/cf_diag_ab.sh; float entry only for the ablations)
-    static const int cfd = tune_env("ADAIN_CF_DIAG", 0), deep = tune_env("ADAIN_CF_DEEP", 0);
-#define CF_LAUNCH(...) hipLaunchKernelGGL((conv_first_kernel<__VA_ARGS__>), dim3((unsigned)grid), dim3(256), 0, s, img, out, packed, bias, H, W, tx, ty, (int)ntiles)
-    if (deep) {
-        if (u8) CF_LAUNCH(true, 0, true);
-        else if (cfd == 3) CF_LAUNCH(false, 3, true);
-        else CF_LAUNCH(false, 0, true);
-        return check_launch("conv_first(deep)");
-    }
-    if (!u8 && cfd >= 1 && cfd <= 3) {
-        if (cfd == 1) CF_LAUNCH(false, 1);
-        else if (cfd == 2) CF_LAUNCH(false, 2);
-        else CF_LAUNCH(false, 3);
-        return check_launch("conv_first(diag)");
-    }
-#undef CF_LAUNCH
-#endif
     if (u8) hipLaunchKernelGGL(conv_first_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, img, out, packed, bias, H, W, tx, ty, (int)ntiles);
     else hipLaunchKernelGGL(conv_first_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, img, out, packed, bias, H, W, tx, ty, (int)ntiles);
     return check_launch("conv_first");
@@ -485,25 +431,12 @@ int launch_conv_last(const float* in, float* out_f32, const float* packed, const
     void* const out = out_u8 ? (void*)out_u8 : (void*)out_f32;
     if (H < 2 || W < 2 || n < 1) { set_error("conv_last: H, W must be >= 2, got %dx%d", H, W); return -1; }
     if ((size_t)W * 256 * 18 >= 0x7ffffff0ULL) { set_error("conv_last: eighteen 64-channel rows of width %d reach 2 GiB", W); return -1; }
-    int th = 16;
-#ifdef ADAIN_DIAG
-    static const int th_env = tune_env("ADAIN_CL_TH", 16);
-    th = th_env == 12 ? 12 : 16;
-#endif
-    const int tx = (W + TW - 1) / TW, ty = (H + th - 1) / th;
+    const int tx = (W + TW - 1) / TW, ty = (H + CL_TH - 1) / CL_TH;
     if ((long long)tx * ty * n > 0x7fffffffLL) { set_error("conv_last: bad grid"); return -1; }
     const dim3 grid((unsigned)(tx * ty * n));
-#ifdef ADAIN_DIAG
-    static const int cld = tune_env("ADAIN_CL_DIAG", 0);
-    if (cld == 1) hipLaunchKernelGGL((conv_last_kernel<1, 16>), grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
-    else if (cld == 2) hipLaunchKernelGGL((conv_last_kernel<2, 16>), grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
-    else if (cld == 4) hipLaunchKernelGGL((conv_last_kernel<4, 16>), grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
-    else if (th == 12) hipLaunchKernelGGL((conv_last_kernel<0, 12>), grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
-    else
-#endif
     if (out_u8 && ((W & 3) || ((uintptr_t)out_u8 & 3))) { set_error("conv_last: the uint8 form needs W %% 4 == 0 and a 4-byte aligned image"); return -1; }
-    if (out_u8) hipLaunchKernelGGL((conv_last_kernel<0, 16, true>), grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
-    else hipLaunchKernelGGL((conv_last_kernel<0, 16>), grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
+    if (out_u8) hipLaunchKernelGGL(conv_last_kernel<true>, grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
+    else hipLaunchKernelGGL(conv_last_kernel<false>, grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
     return check_launch("conv_last");
 }
 

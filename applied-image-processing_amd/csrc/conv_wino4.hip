@@ -33,10 +33,6 @@
 namespace adain {
 
 namespace {
-#ifndef W4_GROUP
-#define W4_GROUP 1                           // 1: one MFMA per scheduling region (default); 8: eight MFMAs back to back, then their work
-#endif
-static_assert(W4_GROUP == 1 || W4_GROUP == 8, "the burst schedule is laid out for groups of 8 (one pair of row positions)");
 constexpr int W4_KR = 16;                    // channels per raw stage = 2 chunks of 8
 constexpr int W4_RSTR = W4_KR + 4;           // floats per halo pixel (80 B = 5 quads: an odd number of 16-byte bank quads)
 constexpr int W4_RITEMS = 6;                 // staging items per thread: at most 340 halo pixels x 4 quads over 256 threads
@@ -119,18 +115,8 @@ __global__ void pack_wino4_kernel(const float* __restrict__ w, float* __restrict
     }
 }
 
-// DIAG (not the product path; selected by ADAIN_W4_DIAG when a stamp buffer is set, tools/wino4_probe.py, tools/wino4_phase_probe.py,
-// tools/probes/diag_ab.py):
-//   1 = a shader-clock stamp per 8-MFMA double step of the first 32 workgroups, 2 = the same with LDS padded to one workgroup per
-//   CU, 3 = four s_memrealtime phase stamps per wave (entry, main-loop start / end, exit);
-//   timing-only ablations of the one-tile form (wrong results by construction; A/B against the product kernel, two workgroups
-//   per CU, 256->256 at 256^2 / 64->64 at 1024^2): 5 = no input transform at all (+16 %), 6 = no patch reads, arithmetic on stale
-//   registers (+16 %: the LDS reads are the transform's whole cost), 9 = ds_read_b32 instead of b128 (+5 %), 7 = no stage
-//   barrier (+2 %), 8 = no halo loads or stores (+8 / +10 %), 10 = no halo loads (+5 / +8 %), 11 = no halo stores (+3 %),
-//   12 = (correct results) 12-slot weight ring, a whole chunk ahead (+1 %); 13 = no weight loads in the main loop, 14 = no vector-memory
-//   loads at all in the main loop (round 2: prices the CU's vector-memory path); a build that sent the halo straight to LDS
-//   (`buffer_load ... lds`, wrong image layout, no staging registers or ds_writes; since removed) measured +3 %.  In a bare MFMA loop neither LDS reads nor streaming
-//   weight loads cost the matrix pipe anything (tools/probes/mfma_chain_probe.hip), so these are waits, not port conflicts.
+// The stamp and timing-only ablation variants that measured this kernel (what its data movement costs, where its steps wait) are
+// retired; docs/HISTORY.md keeps their numbers.
 // PERSIST: a workgroup walks a list of tiles (grid = 2 per CU; XCD x owns a contiguous range of the tile list, channel tile
 // fastest) instead of one: the next tile's first halo stage is loaded during the current tile's last stages and its first
 // weight fragments replace the ring's run-off loads, so a tile starts with an LDS write + barrier + transform instead of a cold
@@ -146,26 +132,16 @@ __global__ void pack_wino4_kernel(const float* __restrict__ w, float* __restrict
 // content launch's list.  A tile's geometry (H, W, pointers) comes from its segment's descriptor, re-read from the kernel
 // arguments at the two places that need it (the next tile's halo offsets, the epilogue's stores).
 // BIG: per-tile buffer descriptors (any image size); the default form keeps one descriptor per image (tensors below 2 GiB)
-template <int MODE, int DIAG = 0, bool PERSIST = false, bool BIG = false, int GEO = 0>
-__global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(ConvArgs a, ConvSegs m, int items, int prio_mode) {
+template <int MODE, bool PERSIST = false, bool BIG = false, int GEO = 0>
+__global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvSegs m, int items) {
     using G = W4G<GEO>;
     constexpr int W4_HALO_W = G::HALO_W, W4_HALO_H = G::HALO_H, W4_HALO = G::HALO, W4_PROW = G::PROW, W4_PLANE = G::PLANE,
                   W4_TAIL = G::TAIL, TILE_W = G::TILE_W, TILE_H = G::TILE_H, TCL = G::TCOLS_LOG, TCM = (1 << G::TCOLS_LOG) - 1;
-    __shared__ __attribute__((aligned(16))) float smem[DIAG == 2 ? W4_PEX + 8192 : (DIAG == 1 ? W4_PEX + 1024 : W4_PEX)];
+    __shared__ __attribute__((aligned(16))) float smem[W4_PEX];
     float* const Rs = smem;
-    unsigned* const steplog = (unsigned*)(smem + W4_PEX);     // DIAG 1, 2: [wave][96] low words of s_memtime
-    int nlog = 0;
-    unsigned long long phase[4] = {0, 0, 0, 0};
-    unsigned long long tpx[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // DIAG 4
-    if constexpr (DIAG == 3) phase[0] = __builtin_amdgcn_s_memrealtime();
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-#ifdef W4_AGPR_ACC
-    // an inline-asm AGPR operand makes the compiler select the MFMAs' AGPR-destination form: the 96 accumulator registers then
-    // live in the accumulator half of the register file (experiment: -DW4_AGPR_ACC)
-    { float agpr_hint = 1.0f; asm volatile("; agpr hint %0" ::"a"(agpr_hint)); }
-#endif
     const int wj = __builtin_amdgcn_readfirstlane(tid >> 6);      // transform column of this wave
     // the one lane constant kept live through the main loop; other lane-derived addresses are rebuilt from an opaque copy
     const int wvo = lane * 16;
@@ -203,7 +179,7 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
         lid = item - m.s[seg].item0;
         gH = m.s[seg].H; gW = m.s[seg].W; gWs = m.s[seg].Ws; gtx = m.s[seg].tiles_x;
         tiles = gtx * m.s[seg].tiles_y;
-    } else if (a.xcd_order && (gridDim.x & 7) == 0) {
+    } else if ((gridDim.x & 7) == 0) {
         lid = (lid & 7) * (gridDim.x >> 3) + (lid >> 3);
     }
     // Persistent walk: inside a segment the items are ordered (channel-tile GROUP, image, pixel tile, channel tile in the group),
@@ -223,11 +199,7 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
     };
     if constexpr (PERSIST) {
         decode(lid, tiles, m.s[seg].n, ct, pt, img);
-    } else if (a.xcd_order == 2) {          // pixel tile fastest: the workgroups resident on an XCD share one or two channel tiles' weights
-        pt = lid % tiles; lid /= tiles;
-        ct = lid % nct;
-        img = lid / nct;
-    } else {                         // channel tile fastest: they share halos
+    } else {                         // channel tile fastest: the workgroups resident on an XCD share halos
         ct = lid % nct; lid /= nct;
         if (a.ksplit > 1) { ks = lid % a.ksplit; lid /= a.ksplit; }      // CIN SPLIT: then the cin ranges of one (pixel tile, channel tile)
         pt = lid % tiles;
@@ -331,12 +303,10 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
     };
 
     // ---- weights: one b128 fragment per step (row position r), ring slot = r, loaded 5 steps ahead ---------------------------
-    // RING12 (experiment, DIAG 12): two chunks of weight slots - a chunk's six fragments are requested during the previous chunk
-    constexpr bool RING12 = DIAG == 12;
-    f32x4 bq[RING12 ? 12 : 6];
+    f32x4 bq[6];
     int wso = ((ct * 4 + wj) * nch + (PERSIST ? 0 : ks * (a.cin_sub >> 3))) * 6144;
 #pragma unroll
-    for (int r = 0; r < (RING12 ? 6 : 4); ++r) bq[r] = buf_load4(wsr, wvo, wso + r * 1024);
+    for (int r = 0; r < 4; ++r) bq[r] = buf_load4(wsr, wvo, wso + r * 1024);
 
     f32x16 acc[6];
     if constexpr (!PERSIST) {       // the persistent form starts every tile with MFMAs on a zero C operand
@@ -374,7 +344,6 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
         }
     }
     __syncthreads();
-    if constexpr (DIAG == 4) tpx[3] = __builtin_amdgcn_s_memtime();
     {
         const int le = lane_now(), q8 = le & 7, tt = le >> 3;
         const int tl = wj * 8 + tt;
@@ -404,7 +373,6 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
         if constexpr (PERSIST) {
             __syncthreads();                               // every wave has its P values: the LDS image is free again
             raw_store(Rs);                                 // the next tile's first halo stage (loaded during this tile)
-            if constexpr (DIAG == 4) tpx[4] = __builtin_amdgcn_s_memtime();
         }
 #pragma unroll
         for (int ap = 0; ap < 4; ++ap) {
@@ -483,7 +451,6 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
             xaddr = (4 * (li >> TCL)) * W4_PROW + (li & TCM) * W4_RSTR + 4 * lh;
             asm volatile("" : "+v"(xaddr));
         }
-        auto xf_addr = [&]() {};
         // patch pixel (row a, column c of the 6 x 4 patch) relative to xaddr: plane c & 1, plane column + (c >> 1)
         auto poff = [=](int a, int c) { return (c & 1) * W4_PLANE + a * W4_PROW + (c >> 1) * W4_RSTR; };
         auto xf_read3 = [&](const float* rb, int a0) {
@@ -496,10 +463,7 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
         // one patch read (read index i = 0..5 of rows a0..a0+2: i / 2 = row, i & 1 = column cA / cB)
         auto xf_read1 = [&](const float* rb, int a0, auto II) {
             constexpr int i = decltype(II)::value, k = i / 2;
-            if constexpr (DIAG == 9) {      // timing-only: the same number of LDS instructions, a quarter of the bytes
-                if constexpr ((i & 1) == 0) dA[k][0] = *(const float*)(rb + xaddr + poff(a0 + k, cA));
-                else dB[k][0] = *(const float*)(rb + xaddr + poff(a0 + k, cB));
-            } else if constexpr ((i & 1) == 0) dA[k] = *(const f32x4*)(rb + xaddr + poff(a0 + k, cA));
+            if constexpr ((i & 1) == 0) dA[k] = *(const f32x4*)(rb + xaddr + poff(a0 + k, cA));
             else dB[k] = *(const f32x4*)(rb + xaddr + poff(a0 + k, cB));
         };
 
@@ -509,45 +473,30 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
         // 412 cycles per 4 instead of 256 + issue overheads), and left to itself the scheduler builds exactly those chains.
         // XF: transform the next chunk's patches meanwhile; ST: the last third also writes the staged halo registers to LDS;
         // LD: the halo loads two stages ahead.  Weight ring: slot = row position, refilled as soon as its MFMAs have issued.
-        auto chunk = [&](const float* nsrc, auto XFC, auto STC, auto LDC, int raw_soff, float* store_to, int wnext, auto PARC,
-                         auto FIRSTC) {
+        auto chunk = [&](const float* nsrc, auto XFC, auto STC, auto LDC, int raw_soff, float* store_to, int wnext, auto FIRSTC) {
             constexpr bool do_xf = decltype(XFC)::value, st = decltype(STC)::value, ld = decltype(LDC)::value;
             // FIRST: the tile's first chunk - every accumulator's first MFMA takes a zero C operand (an inline constant) instead of
             // a cleared register: no 96 v_mov per tile (vector instructions cost this kernel matrix-pipe time)
             constexpr bool first = decltype(FIRSTC)::value;
-            constexpr int par = RING12 ? decltype(PARC)::value : 0;
-            // Schedule: GRP == 1 (default) = one MFMA per scheduling region followed by its share of the chunk's other work;
-            // GRP == 8 (-DW4_GROUP=8) = the eight MFMAs of a pair of row positions back to back, then their regions' work in one
-            // burst.  A plain fp32 vector instruction takes matrix-pipe time on gfx950 (tools/probes/mfma_valu_probe.hip: a bare
-            // stream of fp32 MFMAs with 5 v_fma_f32 each reaches 113-119 TFLOP/s alternating 1 : 5 and 126-129 in bursts of 4 : 20 or
-            // more), but in this kernel the burst form measured 0.6 % SLOWER (3.64 vs 3.62 ms per config-2 step): what counts is
-            // the NUMBER of vector instructions per MFMA (see `sa`, `xaddr`), not their placement.
-            constexpr int GRP = W4_GROUP;
+            // A plain fp32 vector instruction takes matrix-pipe time on gfx950 (tools/probes/mfma_valu_probe.hip: a bare stream of fp32
+            // MFMAs with 5 v_fma_f32 each reaches 113-119 TFLOP/s alternating 1 : 5 and 126-129 in bursts of 4 : 20 or more), but in this
+            // kernel a burst schedule (the eight MFMAs of a pair of row positions back to back, then their regions' work) measured 0.6 %
+            // SLOWER (3.64 vs 3.62 ms per config-2 step): what counts is the NUMBER of vector instructions per MFMA (see `sa`, `xaddr`),
+            // not their placement.
             auto mf = [&](auto HH) {
                 constexpr int h = decltype(HH)::value, m = h / 2, b = h & 1, d = m / 4, sidx = m & 3, r = 2 * d + b;
-                if constexpr ((DIAG == 1 || DIAG == 2) && (h % 8) == 0) {
-                    const unsigned tnow = (unsigned)__builtin_amdgcn_s_memtime();
-                    if (lane_now() == 0 && nlog < 96) steplog[WJ * 96 + nlog] = tnow;
-                    ++nlog;
-                }
                 if constexpr (first && sidx == 0) {
                     constexpr f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    acc[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[6 * par + r][sidx], aq[r][sidx], zero, 0, 0, 0);
+                    acc[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[r][sidx], aq[r][sidx], zero, 0, 0, 0);
                 } else {
-                    acc[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[6 * par + r][sidx], aq[r][sidx], acc[r], 0, 0, 0);
+                    acc[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[r][sidx], aq[r][sidx], acc[r], 0, 0, 0);
                 }
             };
-            // region (1 MFMA : work) schedule, and the burst schedule's regions for the same pieces of work
-            constexpr int H_COLS0 = GRP == 1 ? 10 : 8, H_READ1 = GRP == 1 ? 11 : 9, H_COLS3 = GRP == 1 ? 20 : 16, H_ROWS = GRP == 1 ? 21 : 17;
             auto work = [&](auto HH) {
                 constexpr int h = decltype(HH)::value;          // 0..23: mini-step m = h / 2 (d = m / 4, s = m % 4), b = second MFMA
                 constexpr int m = h / 2, b = h & 1;
                 // ---- weight ring: (this chunk) slots 4, 5 at mini-steps 0, 1; (next chunk) slots 0, 1 at 4, 5; slots 2, 3 at 8, 9 ----
-                if constexpr (DIAG == 13 || DIAG == 14) {
-                    // timing-only: no weight loads in the main loop (the ring keeps its first fragments)
-                } else if constexpr (RING12) {
-                    if constexpr (b == 0 && m < 6) bq[6 * (1 - par) + m] = buf_load4(wsr, wvo, wnext + m * 1024);
-                } else if constexpr (b == 0) {
+                if constexpr (b == 0) {
                     if constexpr (m == 0) bq[4] = buf_load4(wsr, wvo, wso + 4 * 1024);
                     if constexpr (m == 1) bq[5] = buf_load4(wsr, wvo, wso + 5 * 1024);
                     if constexpr (m == 4) bq[0] = buf_load4(wsr, wvo, wnext);
@@ -556,100 +505,64 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
                     if constexpr (m == 9) bq[3] = buf_load4(wsr, wvo, wnext + 3 * 1024);
                 }
                 // ---- halo loads two stages ahead, in the first two thirds of the chunk (regions 5, 7, 9, 11, 13, 15) ----
-                if constexpr (ld && DIAG != 10 && DIAG != 14 && b == 1 && h >= 5 && h <= 15) {      // DIAG 10: timing-only, no halo loads (stale stores)
+                if constexpr (ld && b == 1 && h >= 5 && h <= 15) {
                     constexpr int k = (h - 5) / 2;
                     rawreg[k] = buf_load4(src, roff[k], tbase + raw_soff);
                 }
                 // ---- input transform of the next chunk ----
-                if constexpr (do_xf && DIAG != 5) {
-                    if constexpr (h == 0) xf_addr();
-                    if constexpr (h >= 1 && h <= 6 && DIAG != 6) xf_read1(nsrc, 0, std::integral_constant<int, h - 1>{});
-                    if constexpr (h == H_COLS0) xf_cols(0);
-                    if constexpr (h >= H_READ1 && h <= H_READ1 + 5 && DIAG != 6) xf_read1(nsrc, 3, std::integral_constant<int, h - H_READ1>{});
-                    if constexpr (h == H_COLS3) xf_cols(3);
-                    if constexpr (h == H_ROWS) { aq[0] = 4.f * f[0] + (f[4] - 5.f * f[2]); t1 = f[4] - 4.f * f[2]; t2 = f[3] - 4.f * f[1]; }   // fragments 0..3: dead since region 15
-                    if constexpr (h == H_ROWS + 1) { aq[1] = t1 + t2; aq[2] = t1 - t2; t3 = f[4] - f[2]; d31 = f[3] - f[1]; }
-                    if constexpr (h == H_ROWS + 2) { aq[3] = t3 + 2.f * d31; o4 = t3 - 2.f * d31; o5 = 4.f * f[1] + (f[5] - 5.f * f[3]); }
+                if constexpr (do_xf) {
+                    if constexpr (h >= 1 && h <= 6) xf_read1(nsrc, 0, std::integral_constant<int, h - 1>{});
+                    if constexpr (h == 10) xf_cols(0);
+                    if constexpr (h >= 11 && h <= 16) xf_read1(nsrc, 3, std::integral_constant<int, h - 11>{});
+                    if constexpr (h == 20) xf_cols(3);
+                    if constexpr (h == 21) { aq[0] = 4.f * f[0] + (f[4] - 5.f * f[2]); t1 = f[4] - 4.f * f[2]; t2 = f[3] - 4.f * f[1]; }   // fragments 0..3: dead since region 15
+                    if constexpr (h == 22) { aq[1] = t1 + t2; aq[2] = t1 - t2; t3 = f[4] - f[2]; d31 = f[3] - f[1]; }
+                    if constexpr (h == 23) { aq[3] = t3 + 2.f * d31; o4 = t3 - 2.f * d31; o5 = 4.f * f[1] + (f[5] - 5.f * f[3]); }
                 }
                 // ---- halo store of the stage loaded one stage ago ----
-                if constexpr (st && DIAG != 8 && DIAG != 11) {
-                    if constexpr (h >= 17 && h <= 22) *(f32x4*)((char*)store_to + sa[h - 17]) = rawreg[h - 17];
-                }
-                if constexpr (st && DIAG == 11) {      // timing-only: halo loads kept alive without the LDS stores
-                    if constexpr (h >= 17 && h <= 22) asm volatile("" ::"v"(rawreg[h - 17]));
-                }
+                if constexpr (st && h >= 17 && h <= 22) *(f32x4*)((char*)store_to + sa[h - 17]) = rawreg[h - 17];
                 if constexpr (do_xf && h == 23) { aq[4] = o4; aq[5] = o5; }
             };
-            auto group = [&](auto GG) {
-                constexpr int g0 = decltype(GG)::value * GRP;
-                [&]<int... I>(std::integer_sequence<int, I...>) { (mf(std::integral_constant<int, g0 + I>{}), ...); }(std::make_integer_sequence<int, GRP>{});
-                if constexpr (GRP > 1) __builtin_amdgcn_sched_barrier(0);
-                [&]<int... I>(std::integer_sequence<int, I...>) { (work(std::integral_constant<int, g0 + I>{}), ...); }(std::make_integer_sequence<int, GRP>{});
-                if constexpr (GRP == 1) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);       // the MFMA first, everything else behind it
+            auto region = [&](auto HH) {
+                mf(HH);
+                work(HH);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);       // the MFMA first, everything else behind it
                 __builtin_amdgcn_sched_barrier(0);
             };
-            [&]<int... G>(std::integer_sequence<int, G...>) { (group(std::integral_constant<int, G>{}), ...); }(std::make_integer_sequence<int, 24 / GRP>{});
+            [&]<int... H>(std::integer_sequence<int, H...>) { (region(std::integral_constant<int, H>{}), ...); }(std::make_integer_sequence<int, 24>{});
             wso += 6144;
         };
         constexpr std::true_type T{};
         constexpr std::false_type F{};
-        constexpr std::integral_constant<int, 0> P0{};
-        constexpr std::integral_constant<int, 1> P1{};
 
         // ---- prologue --------------------------------------------------------------------------------------------------------------
         raw_load(0);
-        if constexpr (PERSIST) {
-            // STAGGER: the two workgroups of a CU start together and run tiles of equal length, so their epilogues (no MFMAs for
-            // ~10 k cycles) tend to coincide and the matrix pipe idles (tools/wino4_persist_probe.py: 17 % of the time at cin = 64).
-            // The second-dispatched half of the grid starts m.stagger x 1024 cycles late, once, while its first loads are in flight.
-            if ((int)(blockIdx.x >> 3) >= (stride >> 1))
-                for (int k = 0; k < m.stagger; ++k) __builtin_amdgcn_s_sleep(16);
-        }
         raw_store(Rs);
         __syncthreads();
         raw_load(W4_KR * 4);                                // stages past the end read neighbouring data or zeros, never consumed
-        xf_addr();
         xf_read3(Rs, 0); xf_cols(0);
         xf_read3(Rs, 3); xf_cols(3);
         rows_012(aq); rows_34(aq); rows_5();
         aq[4] = o4; aq[5] = o5;
-        if constexpr (DIAG == 3) phase[1] = __builtin_amdgcn_s_memrealtime();
 
         if constexpr (!PERSIST) {
             // stages in pairs (even stage: reads buffer 0, fills buffer 1; odd stage: the reverse): every LDS address of the loop is a
             // register + an immediate (see the persistent form); the last pair is its first half when nst is even
             for (int s = 0; s + 1 < nst; s += 2) {
-                chunk(Rs + 8, T, T, F, 0, Rs + W4_RBUF, wso + 6144, P0, F);        // channels 0..7; prepares 8..15; writes the next stage's halo
-                if constexpr (DIAG != 7) __syncthreads();
-                chunk(Rs + W4_RBUF, T, F, T, (s + 2) * W4_KR * 4, nullptr, wso + 6144, P1, F);      // channels 8..15; prepares the next stage; loads two stages ahead
+                chunk(Rs + 8, T, T, F, 0, Rs + W4_RBUF, wso + 6144, F);        // channels 0..7; prepares 8..15; writes the next stage's halo
+                __syncthreads();
+                chunk(Rs + W4_RBUF, T, F, T, (s + 2) * W4_KR * 4, nullptr, wso + 6144, F);      // channels 8..15; prepares the next stage; loads two stages ahead
                 if (s + 2 < nst) {
-                    chunk(Rs + W4_RBUF + 8, T, T, F, 0, Rs, wso + 6144, P0, F);
-                    if constexpr (DIAG != 7) __syncthreads();
-                    chunk(Rs, T, F, T, (s + 3) * W4_KR * 4, nullptr, wso + 6144, P1, F);
+                    chunk(Rs + W4_RBUF + 8, T, T, F, 0, Rs, wso + 6144, F);
+                    __syncthreads();
+                    chunk(Rs, T, F, T, (s + 3) * W4_KR * 4, nullptr, wso + 6144, F);
                 }
             }
-            chunk(Rs + ((nst - 1) & 1) * W4_RBUF + 8, T, F, F, 0, nullptr, wso + 6144, P0, F);
-            chunk(Rs, F, F, F, 0, nullptr, wso + 6144, P1, F);
-            if constexpr (DIAG == 3) phase[2] = __builtin_amdgcn_s_memrealtime();
+            chunk(Rs + ((nst - 1) & 1) * W4_RBUF + 8, T, F, F, 0, nullptr, wso + 6144, F);
+            chunk(Rs, F, F, F, 0, nullptr, wso + 6144, F);
         } else {
             int ntile = 0;
-            // DIAG 4: shader-clock stamps of the persistent form: 0 tile start, 1 main-loop end, 2 after the barrier in front of
-            // the epilogue, 3 P values written + barrier, 4 P values read + barrier + next halo stored, 5 outputs stored,
-            // 6 accumulators cleared + barrier, 7 next tile's first transform done
-            auto tile_stamp = [&]() {
-                if constexpr (DIAG == 4) {
-                    tpx[7] = __builtin_amdgcn_s_memtime();
-                    if (a.dbg && lane_now() == 0 && ntile <= 32) {
-                        unsigned long long* d = a.dbg + (((size_t)blockIdx.x * 4 + WJ) * 32 + (ntile - 1)) * 8;
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) d[q] = tpx[q];
-                        if (ntile == 1 && WJ == 0) a.dbg[(size_t)gridDim.x * 1024 + blockIdx.x] =
-                            ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-                    }
-                }
-            };
             for (;;) {
-                if constexpr (DIAG == 4) tpx[0] = __builtin_amdgcn_s_memtime();
                 // the tile after this one (or this one again when the list is exhausted: its loads are then never consumed)
                 const int nitem = item + stride < hi ? item + stride : item;
                 const int nseg = seg_of(nitem);
@@ -658,12 +571,9 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
                 decode(nli, ntiles, m.s[nseg].n, nct_, npt, nimg);
                 const int ntx0 = (npt % ngtx) * TILE_W, nty0 = (npt / ngtx) * TILE_H;
                 const int wso_next = ((nct_ * 4 + wj) * nch) * 6144;
-                if (prio_mode & 1) {
-                    if ((ntile + (int)((blockIdx.x >> 3) >= (stride >> 1))) & 1) __builtin_amdgcn_s_setprio(1);
-                    else __builtin_amdgcn_s_setprio(0);
-                } else if (prio_mode & 2) {
-                    __builtin_amdgcn_s_setprio(0);
-                }
+                // wave priority alternating per tile, in opposite phase for the two halves of the grid (see PERSIST above)
+                if ((ntile + (int)((blockIdx.x >> 3) >= (stride >> 1))) & 1) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
                 ++ntile;
                 // The halo loads run two stages ahead, and the staging offsets (six vector registers, the scalar tile base, the source
                 // descriptor) switch to the next tile at ONE straight-line point: behind the stage loop, in front of the tile's last two
@@ -678,46 +588,39 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
                     src = src_of(m.s[nseg].in, m.s[nseg].Hs, m.s[nseg].Ws, nimg, nty0);
                 };
                 {   // stage 0, peeled: its first chunk starts the tile's accumulators (FIRST)
-                    chunk(Rs + 8, T, T, F, 0, Rs + W4_RBUF, wso + 6144, P0, T);
+                    chunk(Rs + 8, T, T, F, 0, Rs + W4_RBUF, wso + 6144, T);
                     __syncthreads();
-                    chunk(Rs + W4_RBUF, T, F, T, min(2, nst - 1) * W4_KR * 4, nullptr, wso + 6144, P1, F);
+                    chunk(Rs + W4_RBUF, T, F, T, min(2, nst - 1) * W4_KR * 4, nullptr, wso + 6144, F);
                 }
                 // stages 1 .. nst-2 in pairs (odd stage: reads buffer 1, fills buffer 0; even stage: the reverse), so that every LDS
                 // address of the loop is a register + an immediate: with the buffer a run-time value the loop spent 8 vector
                 // instructions per stage on `base + offset` (of 152; every one costs matrix-pipe time).  cin a multiple of 32 gives
                 // whole pairs; otherwise the last pair is its first half.
                 for (int s = 1; s + 1 < nst; s += 2) {
-                    chunk(Rs + W4_RBUF + 8, T, T, F, 0, Rs, wso + 6144, P0, F);
+                    chunk(Rs + W4_RBUF + 8, T, T, F, 0, Rs, wso + 6144, F);
                     __syncthreads();
-                    chunk(Rs, T, F, T, min(s + 2, nst - 1) * W4_KR * 4, nullptr, wso + 6144, P1, F);
+                    chunk(Rs, T, F, T, min(s + 2, nst - 1) * W4_KR * 4, nullptr, wso + 6144, F);
                     if (s + 2 < nst) {
-                        chunk(Rs + 8, T, T, F, 0, Rs + W4_RBUF, wso + 6144, P0, F);
+                        chunk(Rs + 8, T, T, F, 0, Rs + W4_RBUF, wso + 6144, F);
                         __syncthreads();
-                        chunk(Rs + W4_RBUF, T, F, T, min(s + 3, nst - 1) * W4_KR * 4, nullptr, wso + 6144, P1, F);
+                        chunk(Rs + W4_RBUF, T, F, T, min(s + 3, nst - 1) * W4_KR * 4, nullptr, wso + 6144, F);
                     }
                 }
                 next_halo();
-                chunk(Rs + ((nst - 1) & 1) * W4_RBUF + 8, T, F, T, 0, nullptr, wso + 6144, P0, F);      // + the next tile's first halo stage
-                chunk(Rs, F, F, F, 0, nullptr, wso_next, P1, F);      // the ring's look-ahead continues in the next tile's weights
+                chunk(Rs + ((nst - 1) & 1) * W4_RBUF + 8, T, F, T, 0, nullptr, wso + 6144, F);      // + the next tile's first halo stage
+                chunk(Rs, F, F, F, 0, nullptr, wso_next, F);      // the ring's look-ahead continues in the next tile's weights
                 wso = wso_next;
-                if constexpr (DIAG == 4) tpx[1] = __builtin_amdgcn_s_memtime();
-                if (prio_mode & 2) __builtin_amdgcn_s_setprio(3);      // experiment: the MFMA-free phase of a tile at top priority
                 __syncthreads();
-                if constexpr (DIAG == 4) tpx[2] = __builtin_amdgcn_s_memtime();
                 epilogue();                                     // of (ct, img, tx0, ty0); also writes the next tile's first halo stage
-                if constexpr (DIAG == 4) tpx[5] = __builtin_amdgcn_s_memtime();
-                if (item + stride >= hi) { tpx[6] = tpx[5]; tile_stamp(); break; }
+                if (item + stride >= hi) break;
                 item += stride;
                 ct = nct_; img = nimg; tx0 = ntx0; ty0 = nty0; seg = nseg;
                 __syncthreads();                                // (the accumulators are not cleared: see FIRST)
-                if constexpr (DIAG == 4) tpx[6] = __builtin_amdgcn_s_memtime();
                 raw_load(W4_KR * 4);
-                xf_addr();
                 xf_read3(Rs, 0); xf_cols(0);
                 xf_read3(Rs, 3); xf_cols(3);
                 rows_012(aq); rows_34(aq); rows_5();
                 aq[4] = o4; aq[5] = o5;
-                tile_stamp();
             }
         }
     };
@@ -727,23 +630,7 @@ __global__ __launch_bounds__(256, DIAG == 2 ? 1 : 2) void conv3x3_wino4_kernel(C
     else main_loop(std::integral_constant<int, 3>{});
     if constexpr (PERSIST) return;
     __syncthreads();
-    if constexpr (DIAG == 1 || DIAG == 2) {
-        if (a.dbg && blockIdx.x < 32) {
-            unsigned* d32 = (unsigned*)a.dbg + blockIdx.x * 384;
-            for (int i = tid; i < 384; i += 256) d32[i] = steplog[i];
-        }
-        __syncthreads();
-    }
     epilogue();
-    if constexpr (DIAG == 3) {
-        phase[3] = __builtin_amdgcn_s_memrealtime();
-        if (a.dbg && lane_now() == 0) {     // [block][wave][4 stamps], then [block] hardware ids
-            unsigned long long* d = a.dbg + ((size_t)blockIdx.x * 4 + wj) * 4;
-            d[0] = phase[0]; d[1] = phase[1]; d[2] = phase[2]; d[3] = phase[3];
-            if (wj == 0) a.dbg[(size_t)gridDim.x * 16 + blockIdx.x] =
-                ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-        }
-    }
 }
 
 // Second half of a cin-split layer: out = [pool](relu(slab 0 + slab 1 + ... + bias)), the slabs added in that fixed order (bitwise
@@ -827,15 +714,10 @@ static int check_wino4_shape(const ConvArgs& a, int src_mode) {
 // Channel tiles per group of the persistent walk: the largest divisor of cout / 32 whose transformed weights (cin x 32 G x 24
 // floats) fit W4_L2_WEIGHT_BYTES of an XCD's 4 MB L2 (the rest is left to the halos and outputs streaming through).
 constexpr size_t W4_L2_WEIGHT_BYTES = 3u << 20;
-constexpr int W4_STAGGER = 0;       // start delay of the second half of the persistent grid (x 1024 cycles); see the kernel
 static int walk_group(int cin, int cout) {
     const int nct = cout / 32;
-    static const int force = tune_env("ADAIN_W4_CTG", 0);       // diagnostic build: 0 = automatic, -1 = all channel tiles, > 0 = that many
-    if (force < 0) return nct;
     int g = nct;
-    if (force > 0) g = force < nct ? force : nct;
-    else
-        while (g > 1 && (size_t)cin * 32 * g * 96 > W4_L2_WEIGHT_BYTES) --g;
+    while (g > 1 && (size_t)cin * 32 * g * 96 > W4_L2_WEIGHT_BYTES) --g;
     while (nct % g) --g;
     return g;
 }
@@ -843,13 +725,7 @@ static int walk_group(int cin, int cout) {
 static long long persistent_grid() {
     const int cus = device_cu_count();
     if (cus <= 0) return 0;
-    long long pgrid = 2LL * cus;
-#ifdef ADAIN_DIAG
-    // timing experiment (tools/probes/one_wave_probe.py): ADAIN_W4_WGS=1 leaves one workgroup per CU = ONE wave per SIMD, nothing
-    // beside a wave's stalls and a tile's epilogue - what a split with more accumulators per wave would have to live with
-    static const int wgs = tune_env("ADAIN_W4_WGS", 2);
-    pgrid = (long long)(wgs == 1 ? 1 : 2) * cus;
-#endif
+    const long long pgrid = 2LL * cus;
     return pgrid - pgrid % 8;
 }
 
@@ -861,8 +737,6 @@ static long long geo_tiles(int geo, int n, int H, int W) {
     return (long long)n * ((H + tile_h(geo) - 1) / tile_h(geo)) * ((W + tile_w(geo) - 1) / tile_w(geo));
 }
 static int pick_geo(const ConvSeg* segs, int count) {
-    static const int force = tune_env("ADAIN_W4_GEO", -1);      // diagnostic build: -1 = automatic, 0 / 1 = that geometry
-    if (force == 0 || force == 1) return force;
     long long t0 = 0, t1 = 0;
     for (int i = 0; i < count; ++i) {
         t0 += geo_tiles(0, segs[i].n, segs[i].H, segs[i].W);
@@ -884,33 +758,21 @@ double wino4_rounds_per_image(int H, int W, int cout) {
 }
 
 template <int MODE, bool PERSIST, bool BIG>
-static void w4_launch_geo(int geo, dim3 grid, hipStream_t s, const ConvArgs& a, const ConvSegs& m, int items, int prio) {
+static void w4_launch_geo(int geo, dim3 grid, hipStream_t s, const ConvArgs& a, const ConvSegs& m, int items) {
     if constexpr (!BIG) {       // (per-tile descriptors - tensors of 2 GiB and more - exist for the default geometry only: see pick_geo's callers)
-        if (geo) { hipLaunchKernelGGL((conv3x3_wino4_kernel<MODE, 0, PERSIST, BIG, 1>), grid, dim3(256), 0, s, a, m, items, prio); return; }
+        if (geo) { hipLaunchKernelGGL((conv3x3_wino4_kernel<MODE, PERSIST, BIG, 1>), grid, dim3(256), 0, s, a, m, items); return; }
     }
-    hipLaunchKernelGGL((conv3x3_wino4_kernel<MODE, 0, PERSIST, BIG, 0>), grid, dim3(256), 0, s, a, m, items, prio);
+    hipLaunchKernelGGL((conv3x3_wino4_kernel<MODE, PERSIST, BIG, 0>), grid, dim3(256), 0, s, a, m, items);
 }
 static void w4_launch(int src_mode, bool persist, bool big, int geo, dim3 grid, hipStream_t s, const ConvArgs& a, const ConvSegs& m,
-                      int items, int prio) {
+                      int items) {
     const bool up = src_mode == SRC_UP2X;
-#ifdef ADAIN_DIAG
-    // timing-only ablations of the PERSISTENT form inside whole passes (wrong results by construction; bench.py --diag-lib with
-    // ADAIN_W4_PDIAG = 8: no halo loads or stores in the main loop, 10: no halo loads, 11: no halo stores): what the halo staging
-    // costs the step, i.e. the most a direct-to-LDS staging (`buffer_load ... lds`) could win
-    static const int pdiag = tune_env("ADAIN_W4_PDIAG", 0);
-    if (persist && !big && geo == 0 && (pdiag == 8 || pdiag == 10 || pdiag == 11)) {
-#define W4_PDIAG_CASE(D) if (pdiag == D) { if (up) hipLaunchKernelGGL((conv3x3_wino4_kernel<SRC_UP2X, D, true>), grid, dim3(256), 0, s, a, m, items, prio); \
-                                           else hipLaunchKernelGGL((conv3x3_wino4_kernel<SRC_DIRECT, D, true>), grid, dim3(256), 0, s, a, m, items, prio); return; }
-        W4_PDIAG_CASE(8) W4_PDIAG_CASE(10) W4_PDIAG_CASE(11)
-#undef W4_PDIAG_CASE
-    }
-#endif
     if (persist) {
-        if (big) up ? w4_launch_geo<SRC_UP2X, true, true>(geo, grid, s, a, m, items, prio) : w4_launch_geo<SRC_DIRECT, true, true>(geo, grid, s, a, m, items, prio);
-        else up ? w4_launch_geo<SRC_UP2X, true, false>(geo, grid, s, a, m, items, prio) : w4_launch_geo<SRC_DIRECT, true, false>(geo, grid, s, a, m, items, prio);
+        if (big) up ? w4_launch_geo<SRC_UP2X, true, true>(geo, grid, s, a, m, items) : w4_launch_geo<SRC_DIRECT, true, true>(geo, grid, s, a, m, items);
+        else up ? w4_launch_geo<SRC_UP2X, true, false>(geo, grid, s, a, m, items) : w4_launch_geo<SRC_DIRECT, true, false>(geo, grid, s, a, m, items);
     } else {
-        if (big) up ? w4_launch_geo<SRC_UP2X, false, true>(geo, grid, s, a, m, items, prio) : w4_launch_geo<SRC_DIRECT, false, true>(geo, grid, s, a, m, items, prio);
-        else up ? w4_launch_geo<SRC_UP2X, false, false>(geo, grid, s, a, m, items, prio) : w4_launch_geo<SRC_DIRECT, false, false>(geo, grid, s, a, m, items, prio);
+        if (big) up ? w4_launch_geo<SRC_UP2X, false, true>(geo, grid, s, a, m, items) : w4_launch_geo<SRC_DIRECT, false, true>(geo, grid, s, a, m, items);
+        else up ? w4_launch_geo<SRC_UP2X, false, false>(geo, grid, s, a, m, items) : w4_launch_geo<SRC_DIRECT, false, false>(geo, grid, s, a, m, items);
     }
 }
 
@@ -945,57 +807,32 @@ int launch_conv3x3_wino4(const ConvArgs& a0, int src_mode, hipStream_t s, SplitW
     m.count = 1;
     m.s[0] = ConvSeg{a.in, a.out, a.n, a.H, a.W, a.Hs, a.Ws, 0, 0, 0};
     const bool big = wino4_big(a);
-    const int geo = (a.dbg || big) ? 0 : pick_geo(m.s, 1);      // the stamp / timing-only and the >= 2 GiB builds exist for the default geometry
+    const int geo = big ? 0 : pick_geo(m.s, 1);      // the >= 2 GiB build exists for the default geometry
     a.tiles_x = (a.W + tile_w(geo) - 1) / tile_w(geo);
     a.tiles_y = (a.H + tile_h(geo) - 1) / tile_h(geo);
     m.s[0].tiles_x = a.tiles_x; m.s[0].tiles_y = a.tiles_y;
     const long long blocks = (long long)a.tiles_x * a.tiles_y * (a.cout / 32) * a.n;
     if (blocks <= 0 || blocks > 0x7fffffffLL) { set_error("conv3x3_wino4: bad grid %lld", blocks); return -1; }
-    static const int order_env = tune_env("ADAIN_W4_ORDER", 1);
-    a.xcd_order = order_env;
     const dim3 g((unsigned)blocks);
-    // persistent form (default) whenever the launch has at least two tiles per resident workgroup; ADAIN_W4_PERSIST = largest
-    // cin it is used for (0 = never: one tile per workgroup).  +2-3 % on most layer shapes, +1.1 % on the config-2 step.
-    static const int persist_env = tune_env("ADAIN_W4_PERSIST", 1 << 20);
-    static const int prio_env = tune_env("ADAIN_W4_PRIO", 1);
+    // persistent form whenever the launch has at least two tiles per resident workgroup (and cin is at most 2^20): +2-3 % on most
+    // layer shapes, +1.1 % on the config-2 step
     const long long pgrid = persistent_grid();
     if (pgrid <= 0) { set_error("conv3x3_wino4: device query failed"); return -1; }
-    const bool persist_ok = a.cin <= persist_env && a.cin >= 2 * W4_KR && pgrid >= 8 && blocks >= 2 * pgrid;
-    const bool persist = !a.dbg && persist_ok;
+    const bool persist = a.cin <= (1 << 20) && a.cin >= 2 * W4_KR && pgrid >= 8 && blocks >= 2 * pgrid;
     const int items = (int)blocks;
     m.ctg = walk_group(a.cin, a.cout);
-    m.stagger = tune_env("ADAIN_W4_STAGGER", W4_STAGGER);
     if (persist) {
-        w4_launch(src_mode, true, big, geo, dim3((unsigned)pgrid), s, a, m, items, prio_env);
+        w4_launch(src_mode, true, big, geo, dim3((unsigned)pgrid), s, a, m, items);
         return check_launch("conv3x3_wino4");
     }
-#ifdef ADAIN_DIAG
-    // timing / stamp builds of the one-tile form (tools/ only: libadain_hip_diag.so); selected by ADAIN_W4_DIAG when a stamp
-    // buffer is set
-    static const int diag_env = tune_env("ADAIN_W4_DIAG", 0);
-    if (a.dbg && diag_env == 4 && persist_ok && src_mode == SRC_DIRECT) {      // per-tile phase stamps of the persistent form
-        hipLaunchKernelGGL((conv3x3_wino4_kernel<SRC_DIRECT, 4, true>), dim3((unsigned)pgrid), dim3(256), 0, s, a, m, items, prio_env);
-        return check_launch("conv3x3_wino4(diag)");
-    }
-    if (a.dbg && src_mode == SRC_DIRECT) {
-        switch (diag_env) {
-#define W4_DIAG_CASE(D) case D: hipLaunchKernelGGL((conv3x3_wino4_kernel<SRC_DIRECT, D>), g, dim3(256), 0, s, a, m, items, 0); break;
-            W4_DIAG_CASE(2) W4_DIAG_CASE(3) W4_DIAG_CASE(5) W4_DIAG_CASE(6) W4_DIAG_CASE(7) W4_DIAG_CASE(8) W4_DIAG_CASE(9)
-            W4_DIAG_CASE(10) W4_DIAG_CASE(11) W4_DIAG_CASE(12) W4_DIAG_CASE(13) W4_DIAG_CASE(14)
-#undef W4_DIAG_CASE
-            default: hipLaunchKernelGGL((conv3x3_wino4_kernel<SRC_DIRECT, 1>), g, dim3(256), 0, s, a, m, items, 0);
-        }
-        return check_launch("conv3x3_wino4(diag)");
-    }
-#endif
-    const int S = (split.slab && !big && !a.dbg) ? wino4_ksplit(blocks, a.cin) : 1;
+    const int S = (split.slab && !big) ? wino4_ksplit(blocks, a.cin) : 1;
     if (S > 1) {
         const size_t slab = (size_t)a.n * a.H * a.W * a.cout;
         if (split.floats < (size_t)S * slab) { set_error("conv3x3_wino4: split workspace too small (%zu < %zu floats)", split.floats, (size_t)S * slab); return -1; }
         ConvArgs p = a;                  // first half: S workgroups per (tile, channel tile), partial sums into the slabs
         p.ksplit = S; p.cin_sub = a.cin / S; p.slab_stride = slab;
-        p.out = split.slab; p.relu = 0; p.pool_out = 0; p.xcd_order = 1;
-        w4_launch(src_mode, false, false, geo, dim3((unsigned)(blocks * S)), s, p, m, items * S, 0);
+        p.out = split.slab; p.relu = 0; p.pool_out = 0;
+        w4_launch(src_mode, false, false, geo, dim3((unsigned)(blocks * S)), s, p, m, items * S);
         if (int r = check_launch("conv3x3_wino4(split)")) return r;
         const int Ho = a.pool_out ? (a.H + 1) / 2 : a.H, Wo = a.pool_out ? (a.W + 1) / 2 : a.W;
         const size_t total = (size_t)a.n * Ho * Wo * (a.cout / 4);
@@ -1004,7 +841,7 @@ int launch_conv3x3_wino4(const ConvArgs& a0, int src_mode, hipStream_t s, SplitW
                            a.n, a.H, a.W, a.cout);
         return check_launch("conv3x3_wino4(combine)");
     }
-    w4_launch(src_mode, false, big, geo, g, s, a, m, items, 0);
+    w4_launch(src_mode, false, big, geo, g, s, a, m, items);
     return check_launch("conv3x3_wino4");
 }
 
@@ -1013,7 +850,6 @@ int launch_conv3x3_wino4_multi(const ConvArgs& layer, const ConvSeg* segs, int c
     ConvSegs m{};
     m.count = count;
     m.ctg = walk_group(layer.cin, layer.cout);
-    m.stagger = tune_env("ADAIN_W4_STAGGER", W4_STAGGER);
     long long total = 0;
     bool big = false;
     ConvArgs a = layer;
@@ -1035,11 +871,9 @@ int launch_conv3x3_wino4_multi(const ConvArgs& layer, const ConvSeg* segs, int c
         total += (long long)m.s[i].tiles_x * m.s[i].tiles_y * (a.cout / 32) * a.n;
         if (total > 0x7fffffffLL) { set_error("conv3x3_wino4_multi: too many tiles"); return -1; }
     }
-    static const int merge_env = tune_env("ADAIN_W4_MERGE", 1);
-    static const int prio_env = tune_env("ADAIN_W4_PRIO", 1);
     const long long pgrid = persistent_grid();
     if (pgrid <= 0) { set_error("conv3x3_wino4: device query failed"); return -1; }
-    if (count == 1 || !merge_env || a.cin < 2 * W4_KR || pgrid < 8 || total < 2 * pgrid) {
+    if (count == 1 || a.cin < 2 * W4_KR || pgrid < 8 || total < 2 * pgrid) {
         // not enough work for a shared persistent list (or a single segment): one launch per segment
         for (int i = 0; i < count; ++i) {
             a.in = segs[i].in; a.out = segs[i].out; a.n = segs[i].n;
@@ -1051,9 +885,7 @@ int launch_conv3x3_wino4_multi(const ConvArgs& layer, const ConvSeg* segs, int c
     // the kernel reads its geometry from the segments; the ConvArgs copy carries the layer (weights, bias, cin, cout, flags)
     a.in = m.s[0].in; a.out = m.s[0].out; a.n = m.s[0].n; a.H = m.s[0].H; a.W = m.s[0].W; a.Hs = m.s[0].Hs; a.Ws = m.s[0].Ws;
     a.tiles_x = m.s[0].tiles_x; a.tiles_y = m.s[0].tiles_y;
-    a.xcd_order = 1;
-    a.dbg = nullptr;
-    w4_launch(src_mode, true, big, geo, dim3((unsigned)pgrid), s, a, m, (int)total, prio_env);
+    w4_launch(src_mode, true, big, geo, dim3((unsigned)pgrid), s, a, m, (int)total);
     return check_launch("conv3x3_wino4(multi)");
 }
 

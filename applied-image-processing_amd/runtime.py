@@ -12,10 +12,9 @@ import threading
 import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
-# The product library.  Nothing in the environment can swap it: the diagnostic build (libadain_hip_diag.so, build.py --diag) is
-# loaded only by an explicit ``use_library(DIAG_LIB_PATH)`` call (tools/_diag.py).
+# The product library.  Nothing in the environment can swap it: another build is loaded only by an explicit ``use_library(path)``
+# call (bench.py --lib: same-box A/B runs).
 LIB_PATH = os.path.join(_PKG, "libadain_hip.so")
-DIAG_LIB_PATH = os.path.join(_PKG, "libadain_hip_diag.so")
 
 SRC_DIRECT, SRC_UP2X, SRC_POOL2 = 0, 1, 2
 SCHEDULE_BATCH, SCHEDULE_LATENCY = 0, 1      # ADAIN_SCHEDULE_*: see adain_set_schedule in include/adain_hip.h
@@ -84,11 +83,6 @@ SIGNATURES = {
     "adain_conv3x3_wino4_split": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p] + [_c_int] * 10 + [_c_void_p, _c_size_t, _c_void_p]),
 }
 
-# entry points of include/adain_hip_diag.h: exported by the diagnostic library only
-DIAG_SIGNATURES = {
-    "adain_debug_set_conv_stamp_buffer": (_c_int, [_c_void_p]),
-}
-
 _lib = None
 _lock = threading.Lock()
 
@@ -109,10 +103,7 @@ def lib():
                         "(there is no CPU / PyTorch fallback for the AdaIN path)"
                     )
                 l = ctypes.CDLL(LIB_PATH)
-                sigs = dict(SIGNATURES)
-                if hasattr(l, "adain_debug_set_conv_stamp_buffer"):      # the diagnostic build: both headers
-                    sigs.update(DIAG_SIGNATURES)
-                for name, (res, args) in sigs.items():
+                for name, (res, args) in SIGNATURES.items():
                     f = getattr(l, name)
                     f.restype, f.argtypes = res, args
                 if l.adain_abi_version() != ABI_VERSION:
@@ -123,16 +114,12 @@ def lib():
 
 
 def use_library(path):
-    """Switches the process to another build of the library (the diagnostic build, ``DIAG_LIB_PATH``; ``LIB_PATH`` switches
-    back).  Only tools/ call this: the product path always runs ``LIB_PATH``."""
+    """Switches the process to another build of the library (bench.py --lib: a same-box A/B against another build of the
+    product library).  The product path always runs ``LIB_PATH``."""
     global _lib, LIB_PATH
     with _lock:
         _lib, LIB_PATH = None, path
     return lib()
-
-
-def is_diag():
-    return hasattr(lib(), "adain_debug_set_conv_stamp_buffer")
 
 
 ABI_CALLS = [0]          # compute calls made through the C ABI by this process (jobs report it per frame)

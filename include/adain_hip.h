@@ -26,8 +26,8 @@
 extern "C" {
 #endif
 
-/* 2: adain_encode_u8, adain_u8_to_f32 and adain_stylize_u8* added; the direct / F(2x2,3x3) single-layer entry points moved to
- * the diagnostic library (include/adain_hip_diag.h); adain_conv3x3_wino accepts form 5 only.  Version 1 was never frozen.
+/* 2: adain_encode_u8, adain_u8_to_f32 and adain_stylize_u8* added; the direct / F(2x2,3x3) single-layer entry points removed;
+ * adain_conv3x3_wino accepts form 5 only.  Version 1 was never frozen.
  * 3: adain_encode_relu1_1 and the uint8 Pillow-exact resize (adain_resize_pil_bilinear_u8*) added; nothing removed or changed.
  * 4: adain_set_schedule / adain_get_schedule and adain_conv3x3_wino4_split* added; the encoder / decoder / stylize workspaces grow by
  *    the partial-sum slabs of the latency schedule (at most 8 MB; callers that size them with the *_bytes queries need no change). */
@@ -267,7 +267,7 @@ ADAIN_API int adain_nchw_to_nhwc(const float* in, float* out, int n, int c, int 
  * epilogue (pool_out != 0: out is [n][ceil(h/2)][ceil(w/2)][cout]).  (h, w) = conv output size before any output pool;
  * (hs, ws) = source size.  Weights packed by adain_conv3x3_wino4_pack, 24 floats per (cin, cout) pair; cin % 16 == 0,
  * cout % 32 == 0; persistent kernel when the launch has >= 2 tiles per resident workgroup.  `form` must be 5 (the other forms -
- * F(2x2,3x3) and the direct implicit GEMM - live in the diagnostic library only, include/adain_hip_diag.h). */
+ * F(2x2,3x3) and the direct implicit GEMM - are retired). */
 ADAIN_API size_t adain_conv3x3_wino4_packed_floats(int cin, int cout);
 ADAIN_API int adain_conv3x3_wino4_pack(const float* w_oihw, float* packed, int cin, int cout, adain_stream_t stream);
 ADAIN_API int adain_conv3x3_wino(const float* in_nhwc, float* out_nhwc, const float* packed_w, const float* bias, int n, int h,

@@ -80,21 +80,20 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert lib.adain_encode_workspace_bytes(1, 1024, 1024) == (64 + 16) * 1024 * 1024 * 4   # A: conv1_1 out, B: pooled conv1_2 out
 
 
-def test_diagnostic_library_exports_both_headers(diag_lib):
-    both = sorted(set(_declared("adain_hip.h")) | set(_declared("adain_hip_diag.h")))
-    assert _exported_functions(diag_lib.LIB_PATH) == both
-    assert sorted(set(diag_lib.SIGNATURES) | set(diag_lib.DIAG_SIGNATURES)) == both
-    assert diag_lib.is_diag() and diag_lib.lib().adain_abi_version() == 4
-
-
-def test_product_library_ignores_the_environment(monkeypatch):
-    """ADAIN_HIP_LIB (round 2's switch) no longer redirects the product runtime; the retired kernel families say so."""
+def test_product_library_reads_no_environment(monkeypatch):
+    """ADAIN_HIP_LIB (round 2's switch) no longer redirects the product runtime; the retired kernel families say so.  The product
+    library reads no environment at all (no getenv import) and exports no debug entry point."""
     import importlib
+    import subprocess
 
     monkeypatch.setenv("ADAIN_HIP_LIB", "/nonexistent/libother.so")
     fresh = importlib.reload(rt)
     try:
-        assert fresh.LIB_PATH.endswith("libadain_hip.so") and not fresh.is_diag()
+        assert fresh.LIB_PATH.endswith("libadain_hip.so")
+        fresh.lib()
+        assert not [f for f in _exported_functions(fresh.LIB_PATH) if f.startswith("adain_debug_")]
+        undefined = subprocess.run(["nm", "-D", "--undefined-only", fresh.LIB_PATH], capture_output=True, text=True, check=True).stdout
+        assert "getenv" not in [ln.split()[-1].split("@")[0] for ln in undefined.splitlines() if ln.split()]
         with pytest.raises(fresh.AdainHipError, match="retired"):
             fresh.conv3x3_wino_pack(torch.zeros(64, 64, 3, 3), 3)
         assert not hasattr(fresh, "conv3x3_pack") and not hasattr(fresh, "conv3x3")
@@ -319,9 +318,9 @@ def test_bench_dump_outputs_whole_or_seeded_sample(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
 
 
-@pytest.mark.parametrize("header", ["adain_hip.h", "adain_hip_diag.h"])
+@pytest.mark.parametrize("header", ["adain_hip.h"])
 def test_headers_are_plain_c_and_cxx(tmp_path, header):
-    """The boundary is a C ABI: both headers compile on their own as strict C99 and as C++17 (no torch, no HIP types in any signature)."""
+    """The boundary is a C ABI: the header compiles on its own as strict C99 and as C++17 (no torch, no HIP types in any signature)."""
     import shutil
     import subprocess
 

@@ -136,7 +136,7 @@ w = {cfg: (counters(f"prof_{ptag}_cfg{cfg}_waits"), counters(f"prof_{ptag}_cfg{c
 rows = []
 for cfg, (wa, tc) in w.items():
     for k in sorted(wa):
-        if "conv3x3_wino4_kernel<0, 0, true" in k and k in tc:
+        if "conv3x3_wino4_kernel<0, true" in k and k in tc:
             a, t = wa[k], tc[k]
             rows.append(f"| {cfg} | `{k}` | {a['SQ_WAVE_CYCLES'][0]} | {a['SQ_WAIT_ANY'][1] / a['SQ_WAVE_CYCLES'][1]:.4f} | "
                         f"{a['SQ_WAIT_INST_ANY'][1] / a['SQ_WAVE_CYCLES'][1]:.4f} | {t['TCC_HIT_sum'][1] / (t['TCC_HIT_sum'][1] + t['TCC_MISS_sum'][1]):.4f} | "
