@@ -552,6 +552,25 @@ int adain_farneback_flow(const float* pyr_prev, const float* pyr_next, int h, in
     return launch_farneback_flow(pyr_prev, pyr_next, h, w, pyr_scale, levels, winsize, iterations, flags, flow_out, workspace,
                                  workspace_bytes, (hipStream_t)stream);
 }
+int adain_tvl1_scales(int h, int w, const adain_tvl1_params* params, int* out_nscales, int* sizes_wh) {
+    return tvl1_scales(h, w, params, out_nscales, sizes_wh);
+}
+size_t adain_tvl1_frame_bytes(int h, int w, const adain_tvl1_params* params) { return tvl1_frame_bytes(h, w, params); }
+int adain_tvl1_prepare(const uint8_t* gray_u8, int n, int h, int w, const adain_tvl1_params* params, float* prepared,
+                       adain_stream_t stream) {
+    if (!gray_u8 || !prepared) { set_error("tvl1_prepare: null pointer"); return ADAIN_EINVAL; }
+    return launch_tvl1_prepare(gray_u8, n, h, w, params, prepared, (hipStream_t)stream);
+}
+size_t adain_tvl1_workspace_bytes(int h, int w, int npairs, const adain_tvl1_params* params) {
+    return tvl1_workspace_bytes(h, w, npairs, params);
+}
+int adain_tvl1_flow(const float* const* prev_frames, const float* const* next_frames, int npairs, int h, int w,
+                    const adain_tvl1_params* params, float* flows_out, int* iters_out, void* workspace, size_t workspace_bytes,
+                    adain_stream_t stream) {
+    if (!prev_frames || !next_frames || !flows_out) { set_error("tvl1_flow: null pointer"); return ADAIN_EINVAL; }
+    return launch_tvl1_flow(prev_frames, next_frames, npairs, h, w, params, flows_out, iters_out, workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
 int adain_resize_area_u8(const uint8_t* in, uint8_t* out, int n, int hi, int wi, int c, int ho, int wo, adain_stream_t stream) {
     if (!in || !out) { set_error("resize_area_u8: null pointer"); return ADAIN_EINVAL; }
     return launch_resize_area_u8(in, out, n, hi, wi, c, ho, wo, (hipStream_t)stream);

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+struct adain_tvl1_params;   // include/adain_hip.h
+
 namespace adain {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -139,6 +141,14 @@ int launch_farneback_expand(const uint8_t* gray, int h, int w, double pyr_scale,
                             float* pyramid, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_farneback_flow(const float* pyr_prev, const float* pyr_next, int h, int w, double pyr_scale, int levels, int winsize,
                           int iterations, int flags, float* flow_out, void* ws, size_t ws_bytes, hipStream_t s);
+
+// tvl1.hip: Dual TV-L1 dense optical flow (OpenCV's contrib DualTVL1OpticalFlow, CPU path)
+int tvl1_scales(int h, int w, const ::adain_tvl1_params* p, int* out_nscales, int* sizes_wh);
+size_t tvl1_frame_bytes(int h, int w, const ::adain_tvl1_params* p);
+size_t tvl1_workspace_bytes(int h, int w, int npairs, const ::adain_tvl1_params* p);
+int launch_tvl1_prepare(const uint8_t* gray, int n, int h, int w, const ::adain_tvl1_params* p, float* prep, hipStream_t s);
+int launch_tvl1_flow(const float* const* prev, const float* const* next, int npairs, int h, int w, const ::adain_tvl1_params* p, float* flows, int* iters,
+                     void* ws, size_t ws_bytes, hipStream_t s);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -180,3 +180,7 @@ class FlowSequence:
         for i, g in enumerate(grays):
             self.push(g, out=out[i - 1] if i > 0 else None)
         return out
+
+
+# Dual TV-L1, the reference's other method (tvl1.py, csrc/tvl1.hip)
+from .tvl1 import DualTVL1OpticalFlow, DualTVL1OpticalFlow_create, TVL1, TVL1Sequence  # noqa: E402,F401

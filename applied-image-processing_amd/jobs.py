@@ -819,7 +819,7 @@ def video_style_transfer_sharded(engine, frames, styles, *, flows=None, target_r
     target_resolution, INTER_AREA)`` of every stylised frame on its own rank (:352-353; ``target_resolution`` =
     (width, height)), ONE gather, then on ``dst`` the recurrence ``frame_i = blend(frame_i, warp(result_{i-1}, flow_{i-1}),
     blend_alpha)`` (:355-368) over ``flows`` [n-1,2,H,W] (prev -> current at the target resolution: ``flow.FlowSequence().batch``
-    computes the reference's Farneback flows on the device, or the caller brings its own).  Returns ``(frames_u8 on dst | None, info)``."""
+    computes the reference's Farneback flows on the device, ``tvl1.TVL1Sequence().batch`` its Dual TV-L1 flows, or the caller brings its own).  Returns ``(frames_u8 on dst | None, info)``."""
     n = len(frames)
     style_list = list(styles) if isinstance(styles, (list, tuple)) else [styles]
     post = out_hw = None

@@ -67,6 +67,12 @@ SIGNATURES = {
                                         _c_size_t, _c_void_p]),
     "adain_farneback_flow": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, ctypes.c_double, _c_int, _c_int, _c_int, _c_int, _c_void_p,
                                       _c_void_p, _c_size_t, _c_void_p]),
+    "adain_tvl1_scales": (_c_int, [_c_int, _c_int, _c_void_p, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
+    "adain_tvl1_frame_bytes": (_c_size_t, [_c_int, _c_int, _c_void_p]),
+    "adain_tvl1_prepare": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "adain_tvl1_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_void_p]),
+    "adain_tvl1_flow": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t,
+                                 _c_void_p]),
     "adain_resize_pil_bilinear_u8_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "adain_resize_pil_bilinear_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p]),
     "adain_stylize_u8_workspace_bytes": (_c_size_t, [_c_int] * 9),

@@ -19,7 +19,10 @@ What stays with the caller, because the reference gets it from libraries this pa
     resized frames, :75-86, :322-358).  ``set_flow_provider(device_flow_provider)`` plugs in the package's own Farnebäck
     estimator (flow.py, csrc/flow.hip: the reference's ``cv2.calcOpticalFlowFarneback(..., 0.5, 5, 15, 3, 7, 1.5, 0)`` on the
     device); with it installed the rank-0 recurrence expands every frame once (flow.FlowSequence) instead of twice per pair.
-    DualTV-L1 is not built in: that method stays with a caller's provider.
+    ``set_flow_provider(device_flow_provider_all)`` accepts both of the reference's method names: ``'farneback'`` as above and
+    ``'dualtvl1'``, the package's Dual TV-L1 (tvl1.py, csrc/tvl1.hip: ``cv2.optflow.DualTVL1OpticalFlow_create().calc(prev, next,
+    None)`` on the device); with it installed and ``'dualtvl1'`` rank 0 computes the clip's n-1 flows before the recurrence
+    (tvl1.TVL1Sequence.batch: each frame prepared once, many pairs per launch).
 One deliberate difference: the reference writes every stylised frame as a JPEG into a temporary directory and reads it back
 (:261-273); here the uint8 frames stay in memory unless ``intermediate_jpeg=True`` re-creates that lossy round trip.
 """
@@ -75,6 +78,22 @@ def device_flow_provider(prev_frame_path, frame_path, target_resolution, method=
     return fl.calc_optical_flow_farneback(prev, cur, None, 0.5, 5, 15, 3, 7, 1.5, 0).permute(2, 0, 1).contiguous()
 
 
+def device_flow_provider_all(prev_frame_path, frame_path, target_resolution, method="farneback"):
+    """A flow provider (``set_flow_provider``) for both of the reference's methods on the current GPU: ``'farneback'`` is exactly
+    ``device_flow_provider``; ``'dualtvl1'`` decodes, resizes and converts both frames the same way and runs
+    ``cv2.optflow.DualTVL1OpticalFlow_create().calc(prev, cur, None)`` (tvl1.DualTVL1OpticalFlow_create) -> [2,H,W] float32 on the
+    device.  Any other name raises ValueError (the reference would fail with an unbound local there)."""
+    if method == "farneback":
+        return device_flow_provider(prev_frame_path, frame_path, target_resolution, method)
+    if method != "dualtvl1":
+        raise ValueError(f"device_flow_provider_all: unknown optical-flow method {method!r} (use 'farneback' or 'dualtvl1')")
+    from . import tvl1
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    prev, cur = _decode_gray(prev_frame_path, target_resolution, dev), _decode_gray(frame_path, target_resolution, dev)
+    return tvl1.DualTVL1OpticalFlow_create().calc(prev, cur, None).permute(2, 0, 1).contiguous()
+
+
 def normalize_image(image):
     """uint8 -> float32 in [0,1] before blending (video/utils.py:217-221)."""
     return image.astype(np.float32) / 255.0 if image.dtype == np.uint8 else image
@@ -110,14 +129,20 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
     dev = engine.device if engine is not None else (torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None)
     # Everything that can stop the job is settled BEFORE any rank starts computing, with one status word, so that no rank is
     # ever left waiting in a collective for a peer that has returned or raised: cancellation (the flag is a per-process Event),
-    # and the optical-flow provider the rank-0 recurrence will need from the second frame on.
+    # and the optical-flow provider the rank-0 recurrence will need from the second frame on (device_flow_provider_all: and a
+    # method name it knows).
     cancelled = cancel_flag is not None and cancel_flag.is_set()
     need_flow = rank == 0 and len(names) > 1 and _flow_provider is None
-    go = sh.agree_min(0 if need_flow else 1 if cancelled else 2, group, dev)
+    bad_method = (rank == 0 and len(names) > 1 and _flow_provider is device_flow_provider_all
+                  and flow_method not in ("farneback", "dualtvl1"))
+    go = sh.agree_min(0 if need_flow or bad_method else 1 if cancelled else 2, group, dev)
     if go == 0:
         if need_flow:
             estimate_optical_flow(None, None, None)            # raises the "no optical-flow provider" error
-        raise RuntimeError("video style transfer: rank 0 has no optical-flow provider (video.set_flow_provider)")
+        if bad_method:
+            device_flow_provider_all(None, None, None, flow_method)     # raises: unknown method
+        raise RuntimeError("video style transfer: rank 0 has no optical-flow provider (video.set_flow_provider) or does not "
+                           f"know the method {flow_method!r}")
     if go == 1:                                                # cancelled on some rank: every rank stops, as the reference loop does
         print("Stopping style transfer...")
         return None
@@ -168,7 +193,17 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
             n, h, w, _ = frames_u8.shape
             prev = None
             seq = None
-            if _flow_provider is device_flow_provider and n > 1:
+            tv_flows = None
+            own_tvl1 = _flow_provider is device_flow_provider_all and flow_method == "dualtvl1"
+            if own_tvl1 and n > 1:
+                # the package's Dual TV-L1: all n-1 flows before the recurrence, each frame prepared once, up to max_pairs pairs per
+                # call (chunks); the same bits as device_flow_provider_all per pair
+                from . import tvl1
+
+                with torch.cuda.device(frames_u8.device):
+                    grays = [_decode_gray(os.path.join(content_dir, nm), (w, h), frames_u8.device) for nm in names]
+                    tv_flows = tvl1.TVL1Sequence().batch(grays, cancel=cancel_flag)
+            elif _flow_provider in (device_flow_provider, device_flow_provider_all) and n > 1:
                 # the package's own estimator: every frame decoded and expanded ONCE (the pair path does both twice per pair);
                 # the same bits as device_flow_provider per pair
                 from . import flow as fl
@@ -183,7 +218,9 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
                     print("Stopping style transfer...")
                     break
                 cur = frames_u8[i]
-                if prev is not None and seq is not None:
+                if prev is not None and tv_flows is not None:
+                    cur = engine.warp_blend_u8(cur.contiguous(), prev, tv_flows[i - 1], alpha)
+                elif prev is not None and seq is not None:
                     with torch.cuda.device(cur.device):
                         flow = seq.push(_decode_gray(os.path.join(content_dir, name), (w, h), cur.device))
                     cur = engine.warp_blend_u8(cur.contiguous(), prev, flow, alpha)

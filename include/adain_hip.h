@@ -209,6 +209,48 @@ ADAIN_API int adain_farneback_expand(const uint8_t* gray_u8, int h, int w, doubl
 ADAIN_API int adain_farneback_flow(const float* pyr_prev, const float* pyr_next, int h, int w, double pyr_scale, int levels, int winsize,
                                    int iterations, int flags, float* flow_out, void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
+/* ---- dense optical flow: cv2.optflow.DualTVL1OpticalFlow_create(...).calc(I0, I1, None) of OpenCV 4.x's contrib CPU implementation
+ * (reference video/utils.py:75-86 runs it with the defaults below; its driver picks it, :416) ------------------------------------------
+ * The rules (scales, centred gradient, cubic remap, thresholding, dual updates, median, stop rule) are restated at the top of
+ * csrc/tvl1.hip and in NumPy in tests/tvl1_ref.py; parity with cv2 itself is not pinned.  The fields keep create()'s names; its
+ * defaults: tau 0.25, lambda 0.15, theta 0.3, nscales 5, warps 5, epsilon 0.01, innerIterations 30, outerIterations 10, scaleStep 0.8,
+ * gamma 0, medianFiltering 5, useInitialFlow 0.
+ *
+ * adain_tvl1_scales (host only): the effective scale count (*out_nscales) and sizes_wh[2s], [2s+1] = width, height of scale s (s = 0:
+ *   full size); sizes_wh needs room for params->nscales pairs.  Either output may be NULL.
+ * adain_tvl1_frame_bytes: the size of one prepared frame (per scale, float4 (I, I_x, I_y, 0) per pixel, 256-byte aligned blocks).
+ * adain_tvl1_prepare: n gray frames [n][h][w] -> n prepared frames, frame_bytes apart.  A frame's preparation depends on the frame
+ *   only: a clip prepares each frame once and uses it as I1 of one pair and I0 of the next.
+ * adain_tvl1_flow: npairs flows at once.  prev_frames / next_frames are DEVICE arrays of npairs pointers to prepared frames (I0 and
+ *   I1 of each pair, all prepared with the same h, w and params; one frame may appear in several pairs); flows_out [npairs][2][h][w] (x then y, the layout adain_warp_blend_u8 consumes);
+ *   iters_out, if not NULL, a device int array [npairs][nscales][warps] (effective nscales, scale 0 = full size) that receives the
+ *   number of inner steps each (scale, warp) executed.  A pair's result does not depend on the batch it runs in.  The frames and
+ *   flows_out must be 16-byte aligned (adain_tvl1_prepare's frames at 256-byte aligned addresses are).  Unlike every other call of
+ *   this header, adain_tvl1_flow makes the host wait on `stream`: after every outer pass but the last of each warp it copies back how
+ *   many pairs have met the stop rule, waits for that copy (hipStreamSynchronize), and skips the remaining launches of the warp when
+ *   all have.  So it cannot be captured into a hipGraph.  It returns with the launches after the last such wait (at least the last
+ *   outer pass of the finest scale's last warp and the store of the flows) still enqueued: order readers of flows_out / iters_out
+ *   on `stream` as for any other call.
+ * The workspace (adain_tvl1_workspace_bytes) serves one call at a time.  Refused with ADAIN_EINVAL before anything is launched: gamma != 0,
+ * useInitialFlow != 0, medianFiltering other than <= 1 (off), 3 or 5, nscales < 1, negative warps / iterations, scaleStep outside (0, 1],
+ * frames smaller than 3 x 3, more than 64 scales.  The size queries return 0 for refused parameters. */
+typedef struct adain_tvl1_params {
+    double tau, lambda, theta;
+    int nscales, warps;
+    double epsilon;
+    int innerIterations, outerIterations;
+    double scaleStep, gamma;
+    int medianFiltering, useInitialFlow;
+} adain_tvl1_params;
+ADAIN_API int adain_tvl1_scales(int h, int w, const adain_tvl1_params* params, int* out_nscales, int* sizes_wh);
+ADAIN_API size_t adain_tvl1_frame_bytes(int h, int w, const adain_tvl1_params* params);
+ADAIN_API int adain_tvl1_prepare(const uint8_t* gray_u8, int n, int h, int w, const adain_tvl1_params* params, float* prepared,
+                                 adain_stream_t stream);
+ADAIN_API size_t adain_tvl1_workspace_bytes(int h, int w, int npairs, const adain_tvl1_params* params);
+ADAIN_API int adain_tvl1_flow(const float* const* prev_frames, const float* const* next_frames, int npairs, int h, int w,
+                              const adain_tvl1_params* params, float* flows_out, int* iters_out, void* workspace, size_t workspace_bytes,
+                              adain_stream_t stream);
+
 /* ---- test_transform's Resize [+ CenterCrop] on the device (test.py:16-24, applied at :190-204; video/utils.py:341-350) --------
  * PIL.Image.resize((wo, ho), BILINEAR) of uint8 RGB images, bit for bit (Pillow's ImagingResample: separable triangle filter whose
  * support grows with the shrink factor, double-precision taps converted to 22-bit fixed point, a horizontal pass into a uint8
