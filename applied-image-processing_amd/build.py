@@ -41,7 +41,7 @@ def build(force=False, verbose=False):
     """Builds the library and returns its path."""
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_utils.h"), os.path.join(INC, "adain_hip.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "device_utils.h", "cv_resize.h")] + [os.path.join(INC, "adain_hip.h")]
     hipcc = _hipcc()
     jobs = []
     objs = []

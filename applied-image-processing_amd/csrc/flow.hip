@@ -30,6 +30,7 @@
 // dependent order: the same inputs give the same bits.
 #include "../../include/adain_hip.h"
 #include "common.h"
+#include "cv_resize.h"
 
 namespace adain {
 
@@ -40,8 +41,6 @@ constexpr int FB_MAX_HALF_WIN = 31;   // winsize <= 63
 
 struct FbTaps { float t[FB_MAX_TAPS]; };
 struct FbPoly { float g[FB_MAX_POLY_N + 1], xg[FB_MAX_POLY_N + 1], xxg[FB_MAX_POLY_N + 1]; double ig11, ig03, ig33, ig55; };
-
-static size_t align64f(size_t floats) { return (floats + 63) & ~(size_t)63; }
 
 struct FbLevel { int w, h, ksize; double scale, sigma; size_t img_off, r_off; };   // offsets in floats into the pyramid
 
@@ -134,39 +133,6 @@ __device__ __forceinline__ int reflect101(int p, int n) {
     return p < n ? p : period - p;
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// cv::resize's choice for a (ssize -> dsize) pair: 0 copy, 1 2x2 mean (INTER_AREA's fast path at an exact 2x shrink), 2 linear
-static int resize_mode(int hi, int wi, int ho, int wo, double* sx, double* sy) {
-    *sx = 1. / ((double)wo / wi);
-    *sy = 1. / ((double)ho / hi);
-    if (ho == hi && wo == wi) return 0;
-    const int ix = (int)nearbyint(*sx), iy = (int)nearbyint(*sy);
-    const bool fast = fabs(*sx - ix) < 2.220446049250313e-16 && fabs(*sy - iy) < 2.220446049250313e-16;
-    return fast && ix == 2 && iy == 2 ? 1 : 2;
-}
-
-// INTER_LINEAR source index and fraction of one output index (resize.cpp's coefficient loop): clamp = x axis rule (fraction 0
-// at both ends); the y axis keeps its fraction and clamps the rows
-struct LinTap { int s0, s1; float f; };
-__device__ __forceinline__ LinTap lin_tap(int d, int ssize, double scale, bool xaxis) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    LinTap t;
-    if (xaxis) {
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
-        t.s0 = s;
-        t.s1 = min(s + 1, ssize - 1);
-    } else {
-        t.s0 = clampi(s, 0, ssize - 1);
-        t.s1 = clampi(s + 1, 0, ssize - 1);
-    }
-    t.f = f;
-    return t;
-}
-
 // ---- frame preparation: cv2.resize(bgr, (wo, ho)) [uint8 INTER_LINEAR fixed point] + cv2.COLOR_RGB2GRAY on BGR data ----------
 // in: PIL's RGB order [n][hi][wi][3]; gray = (4899 B + 9617 G + 1868 R + 8192) >> 14 of the resized channels
 __global__ __launch_bounds__(256) void fb_gray_kernel(const uint8_t* __restrict__ rgb, int hi, int wi, uint8_t* __restrict__ gray, int ho,
@@ -223,21 +189,8 @@ __global__ __launch_bounds__(256) void fb_level_image_kernel(const float* __rest
                                                              double scale_y) {
     const int dx = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
     if (dx >= lw || dy >= lh) return;
-    float v;
-    if (mode == 0) {
-        v = col_blur(tmp, h, w, ks, taps, dy, dx);
-    } else if (mode == 1) {
-        const float a = col_blur(tmp, h, w, ks, taps, 2 * dy, 2 * dx), b = col_blur(tmp, h, w, ks, taps, 2 * dy, 2 * dx + 1);
-        const float c = col_blur(tmp, h, w, ks, taps, 2 * dy + 1, 2 * dx), d = col_blur(tmp, h, w, ks, taps, 2 * dy + 1, 2 * dx + 1);
-        v = (((a + b) + c) + d) * 0.25f;
-    } else {
-        const LinTap tx = lin_tap(dx, w, scale_x, true), ty = lin_tap(dy, h, scale_y, false);
-        const float a0 = 1.f - tx.f, a1 = tx.f, b0 = 1.f - ty.f, b1 = ty.f;
-        const float h0 = col_blur(tmp, h, w, ks, taps, ty.s0, tx.s0) * a0 + col_blur(tmp, h, w, ks, taps, ty.s0, tx.s1) * a1;
-        const float h1 = col_blur(tmp, h, w, ks, taps, ty.s1, tx.s0) * a0 + col_blur(tmp, h, w, ks, taps, ty.s1, tx.s1) * a1;
-        v = h0 * b0 + h1 * b1;
-    }
-    img[(size_t)dy * lw + dx] = v;
+    auto at = [&](int yy, int xx) { return col_blur(tmp, h, w, ks, taps, yy, xx); };
+    img[(size_t)dy * lw + dx] = resample(at, h, w, dx, dy, mode, scale_x, scale_y);
 }
 
 // ---- polynomial expansion of one level: a 64 x 8 output tile, its (8 + 2n) x (64 + 2n) source window in LDS ---------------------
@@ -354,6 +307,8 @@ __global__ __launch_bounds__(256) void fb_update_kernel(const float* __restrict_
             fl[0] = pflow[(size_t)y * pw + x];
             fl[1] = pflow[plane + (size_t)y * pw + x];
         } else {                          // the finer level is never an exact 2x SHRINK of the coarser one: linear
+            // cv_resize.h's linear arm with the taps shared by both components, written out: under this file's default FMA
+            // contraction, resample() per component compiles to other fused multiply-adds and changes the flow's last bits
             const LinTap tx = lin_tap(x, pw, scale_x, true), ty = lin_tap(y, ph, scale_y, false);
             const float a0 = 1.f - tx.f, a1 = tx.f, b0 = 1.f - ty.f, b1 = ty.f;
 #pragma unroll
@@ -429,8 +384,8 @@ int launch_flow_gray_u8(const uint8_t* rgb, int n, int hi, int wi, uint8_t* gray
         if (n < 1 || n > 65535) set_error("flow_gray_u8: bad frame count %d", n);
         return ADAIN_EINVAL;
     }
-    double sx, sy;
-    const int mode = resize_mode(hi, wi, ho, wo, &sx, &sy);
+    const double sx = 1. / ((double)wo / wi), sy = 1. / ((double)ho / hi);
+    const int mode = resize_mode(hi, wi, ho, wo, sx, sy);
     hipLaunchKernelGGL(fb_gray_kernel, dim3((wo + 63) / 64, (ho + 3) / 4, n), dim3(64, 4), 0, s, rgb, hi, wi, gray, ho, wo, mode, sx, sy);
     return check_launch("flow_gray_u8");
 }
@@ -495,8 +450,8 @@ int launch_farneback_expand(const uint8_t* gray, int h, int w, double pyr_scale,
         fb_gauss_taps(l.ksize, l.sigma, T);
         hipLaunchKernelGGL(fb_blur_rows_kernel, dim3((w + 255) / 256, h), dim3(256), (256 + l.ksize - 1) * sizeof(float), s, gray, h, w,
                            l.ksize, T, tmp);
-        double sx, sy;
-        const int mode = resize_mode(h, w, l.h, l.w, &sx, &sy);
+        const double sx = 1. / ((double)l.w / w), sy = 1. / ((double)l.h / h);
+        const int mode = resize_mode(h, w, l.h, l.w, sx, sy);
         float* img = pyramid + l.img_off;
         hipLaunchKernelGGL(fb_level_image_kernel, dim3((l.w + 63) / 64, (l.h + 3) / 4), dim3(64, 4), 0, s, tmp, h, w, l.ksize, T, img,
                            l.h, l.w, mode, sx, sy);
@@ -536,8 +491,8 @@ int launch_farneback_flow(const float* pyr_prev, const float* pyr_next, int h, i
         const float* R0 = pyr_prev + l.r_off;
         const float* R1 = pyr_next + l.r_off;
         float* fl = i == 0 ? flow_out : Fb[i & 1];
-        double sx = 0, sy = 0;
-        const int mode = prev_flow ? resize_mode(ph, pw, l.h, l.w, &sx, &sy) : 0;
+        const double sx = prev_flow ? 1. / ((double)l.w / pw) : 0, sy = prev_flow ? 1. / ((double)l.h / ph) : 0;
+        const int mode = prev_flow ? resize_mode(ph, pw, l.h, l.w, sx, sy) : 0;
         hipLaunchKernelGGL(fb_update_kernel, dim3((l.w + 63) / 64, (l.h + 3) / 4), dim3(64, 4), 0, s, R0, R1, l.w, l.h, prev_flow, ph, pw,
                            mode, sx, sy, inv_pyr, Mb[0]);
         for (int it = 0; it < iterations; ++it) {

@@ -10,9 +10,9 @@
 //             <= 1 (off), 3 or 5 (medianBlur on float data), nscales < 1, negative warps / iterations, scaleStep outside (0, 1].
 //   input     uint8 gray [H][W] -> float32, values 0..255 (convertTo with scale 1).
 //   scales    level s = resize(level s-1, Size(), scaleStep, scaleStep, INTER_LINEAR): size cvRound(w*scaleStep) x cvRound(h*scaleStep)
-//             (half to even), source coordinates with scale 1/scaleStep (not the size ratio); the float INTER_LINEAR of flow.hip
-//             (fx = (float)((dx+0.5)*scale - 0.5), clamped x taps, clamped rows with their weights kept; an equal size is a copy, an
-//             exact 2x shrink INTER_AREA's 2x2 mean).  The first level with fewer than 16 columns or rows ends the list (discarded).
+//             (half to even), source coordinates with scale 1/scaleStep (not the size ratio); the float INTER_LINEAR of cv_resize.h
+//             (an equal size is a copy, an exact 2x shrink INTER_AREA's 2x2 mean over the source pixels inside the image).  The
+//             first level with fewer than 16 columns or rows ends the list (discarded).
 //   gradient  I1x, I1y = centred differences 0.5f*(next - previous), one-sided 0.5f*(x1 - x0) on the first / last row and column.
 //   per scale coarsest: u = 0; finer: u = resize(u_coarser, this size, INTER_LINEAR with the size ratio) * (float)(1/scaleStep);
 //             p11 = p12 = p21 = p22 = 0; scaledEpsilon = (float)(epsilon^2 * w*h); l_t = (float)(lambda*theta); taut = (float)(tau/theta).
@@ -41,6 +41,7 @@
 // reads how many pairs are done and skips the rest of the warp when all are.
 #include "../../include/adain_hip.h"
 #include "common.h"
+#include "cv_resize.h"
 
 #include <float.h>
 #include <math.h>
@@ -49,8 +50,6 @@ namespace adain {
 
 constexpr int TV_MAX_SCALES = 64;
 constexpr int TV_MIN_SIZE = 16;
-
-static size_t tv_align(size_t floats) { return (floats + 63) & ~(size_t)63; }
 
 struct TvScale { int w, h; size_t off; };   // off: floats into a prepared frame, float4 (img, I_x, I_y, 0) per pixel
 
@@ -70,7 +69,7 @@ static int tv_schedule(int h, int w, int nscales, double step, TvScale* S, size_
     size_t off = 0;
     for (int s = 0; s < n; ++s) {
         S[s].off = off;
-        off += tv_align((size_t)S[s].w * S[s].h * 4);
+        off += align64f((size_t)S[s].w * S[s].h * 4);
     }
     if (frame_floats) *frame_floats = off;
     return n;
@@ -102,56 +101,6 @@ static bool tv_check(const adain_tvl1_params* p, int h, int w, const char* what)
     return true;
 }
 
-__device__ __forceinline__ int tv_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// the float INTER_LINEAR of cv::resize (the same rule as flow.hip's lin_tap)
-struct TvTap { int s0, s1; float f; };
-__device__ __forceinline__ TvTap tv_lin_tap(int d, int ssize, double scale, bool xaxis) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    TvTap t;
-    if (xaxis) {
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
-        t.s0 = s;
-        t.s1 = min(s + 1, ssize - 1);
-    } else {
-        t.s0 = tv_clampi(s, 0, ssize - 1);
-        t.s1 = tv_clampi(s + 1, 0, ssize - 1);
-    }
-    t.f = f;
-    return t;
-}
-
-// mode: 0 copy, 1 2x2 mean (INTER_AREA's fast path: the source pixels inside the image, averaged), 2 linear.  `at(y, x)` reads the source.
-template <class F>
-__device__ __forceinline__ float tv_resample(F at, int sh, int sw, int x, int y, int mode, double sx, double sy) {
-    if (mode == 0) return at(y, x);
-    if (mode == 1) {
-        const int x0 = 2 * x, y0 = 2 * y;
-        if (x0 + 1 < sw && y0 + 1 < sh) return (((at(y0, x0) + at(y0, x0 + 1)) + at(y0 + 1, x0)) + at(y0 + 1, x0 + 1)) * 0.25f;
-        float sum = 0.f;
-        int cnt = 0;
-        for (int yy = y0; yy < y0 + 2 && yy < sh; ++yy)
-            for (int xx = x0; xx < x0 + 2 && xx < sw; ++xx) { sum += at(yy, xx); ++cnt; }
-        return cnt ? sum / (float)cnt : 0.f;
-    }
-    const TvTap tx = tv_lin_tap(x, sw, sx, true), ty = tv_lin_tap(y, sh, sy, false);
-    const float a0 = 1.f - tx.f, a1 = tx.f, b0 = 1.f - ty.f, b1 = ty.f;
-    const float h0 = at(ty.s0, tx.s0) * a0 + at(ty.s0, tx.s1) * a1;
-    const float h1 = at(ty.s1, tx.s0) * a0 + at(ty.s1, tx.s1) * a1;
-    return h0 * b0 + h1 * b1;
-}
-
-// cv::resize's choice for (ssize -> dsize) with the source-per-destination scales sx, sy
-static int tv_resize_mode(int hi, int wi, int ho, int wo, double sx, double sy) {
-    if (ho == hi && wo == wi) return 0;
-    const int ix = (int)nearbyint(sx), iy = (int)nearbyint(sy);
-    const bool fast = fabs(sx - ix) < 2.220446049250313e-16 && fabs(sy - iy) < 2.220446049250313e-16;
-    return fast && ix == 2 && iy == 2 ? 1 : 2;
-}
-
 // ---- frame preparation ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tv_to_float_kernel(const uint8_t* __restrict__ gray, int h, int w, float* __restrict__ prep,
                                                           size_t frame_floats) {
@@ -167,7 +116,7 @@ __global__ __launch_bounds__(256) void tv_scale_kernel(float* __restrict__ prep,
     float* f = prep + (size_t)blockIdx.z * frame_floats;
     const float* src = f + src_off;
     auto at = [&](int yy, int xx) { return src[((size_t)yy * sw + xx) * 4]; };
-    f[dst_off + ((size_t)y * dw + x) * 4] = tv_resample(at, sh, sw, x, y, mode, sx, sy);
+    f[dst_off + ((size_t)y * dw + x) * 4] = resample(at, sh, sw, x, y, mode, sx, sy);
 }
 
 __global__ __launch_bounds__(256) void tv_gradient_kernel(float* __restrict__ prep, size_t frame_floats, size_t off, int h, int w) {
@@ -241,8 +190,8 @@ __global__ __launch_bounds__(256) void tv_init_kernel(TvArgs a, const float* __r
         const float* c1 = c0 + (size_t)ch * cw;
         auto at0 = [&](int yy, int xx) { return c0[(size_t)yy * cw + xx]; };
         auto at1 = [&](int yy, int xx) { return c1[(size_t)yy * cw + xx]; };
-        u.x = tv_resample(at0, ch, cw, x, y, mode, sx, sy) * inv_step;
-        u.y = tv_resample(at1, ch, cw, x, y, mode, sx, sy) * inv_step;
+        u.x = resample(at0, ch, cw, x, y, mode, sx, sy) * inv_step;
+        u.y = resample(at1, ch, cw, x, y, mode, sx, sy) * inv_step;
     }
     const size_t i = (size_t)y * a.w + x;
     b.U(0)[i] = u;
@@ -323,7 +272,7 @@ __device__ __forceinline__ float tv_median(const float2* __restrict__ U, int h, 
     for (int dy = 0; dy < K; ++dy)
 #pragma unroll
         for (int dx = 0; dx < K; ++dx) {
-            const float2 q = U[(size_t)tv_clampi(y + dy - R, 0, h - 1) * w + tv_clampi(x + dx - R, 0, w - 1)];
+            const float2 q = U[(size_t)clampi(y + dy - R, 0, h - 1) * w + clampi(x + dx - R, 0, w - 1)];
             v[dy * K + dx] = c == 0 ? q.x : q.y;
         }
 #pragma unroll
@@ -552,7 +501,7 @@ static int tv_nblk(int h, int w) { return ((w + ST_TX - 1) / ST_TX) * ((h + ST_T
 
 size_t tvl1_workspace_bytes(int h, int w, int npairs, const adain_tvl1_params* p) {
     if (!tv_check(p, h, w, "tvl1_workspace_bytes") || npairs < 1 || npairs > 65535) return 0;
-    const size_t plane = tv_align((size_t)h * w);
+    const size_t plane = align64f((size_t)h * w);
     const size_t part = (((size_t)npairs * tv_nblk(h, w) * sizeof(double)) + 255) & ~(size_t)255;
     return tv_state_bytes(npairs) + part + (size_t)npairs * 16 * plane * sizeof(float);
 }
@@ -569,7 +518,7 @@ int launch_tvl1_prepare(const uint8_t* gray, int n, int h, int w, const adain_tv
         const TvScale& c = S[k];
         if (k > 0) {
             const double sc = 1. / p->scaleStep;
-            const int mode = tv_resize_mode(S[k - 1].h, S[k - 1].w, c.h, c.w, sc, sc);
+            const int mode = resize_mode(S[k - 1].h, S[k - 1].w, c.h, c.w, sc, sc);
             hipLaunchKernelGGL(tv_scale_kernel, dim3((c.w + 63) / 64, (c.h + 3) / 4, n), blk, 0, s, prep, ff, S[k - 1].off, S[k - 1].h,
                                S[k - 1].w, c.off, c.h, c.w, mode, sc, sc);
         }
@@ -587,7 +536,7 @@ int launch_tvl1_flow(const float* const* prev, const float* const* next, int npa
     TvScale S[TV_MAX_SCALES];
     size_t ff = 0;
     const int ns = tv_schedule(h, w, p->nscales, p->scaleStep, S, &ff);
-    const size_t plane = tv_align((size_t)h * w);
+    const size_t plane = align64f((size_t)h * w);
     const size_t sb = tv_state_bytes(npairs);
     const size_t part = (((size_t)npairs * tv_nblk(h, w) * sizeof(double)) + 255) & ~(size_t)255;
     char* base = (char*)ws;
@@ -627,7 +576,7 @@ int launch_tvl1_flow(const float* const* prev, const float* const* next, int npa
             ch = S[k + 1].h;
             sx = 1. / ((double)c.w / cw);
             sy = 1. / ((double)c.h / ch);
-            mode = tv_resize_mode(ch, cw, c.h, c.w, sx, sy);
+            mode = resize_mode(ch, cw, c.h, c.w, sx, sy);
         }
         hipLaunchKernelGGL(tv_init_kernel, pix, blk, 0, s, a, flows, out_stride, ch, cw, mode, sx, sy, inv_step);
         for (int wi = 0; wi < p->warps; ++wi) {

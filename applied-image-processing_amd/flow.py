@@ -110,12 +110,11 @@ class Farneback:
     def flow(self, pyr_prev, pyr_next, out=None):
         dev = pyr_prev.device
         for p in (pyr_prev, pyr_next):
-            if not p.is_cuda or p.dtype != torch.uint8 or p.numel() < self.pyr_bytes or not p.is_contiguous():
-                raise rt.AdainHipError("farneback: pyramids must be contiguous uint8 device buffers made by expand()")
+            rt._check_buffer(p, "farneback: each pyramid (made by expand())", torch.uint8, dev, min_numel=self.pyr_bytes)
         if out is None:
             out = torch.empty((2, self.h, self.w), dtype=torch.float32, device=dev)
-        elif (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (2, self.h, self.w) or not out.is_contiguous()):
-            raise rt.AdainHipError(f"farneback: out must be a contiguous float32 [2,{self.h},{self.w}] device tensor")
+        else:
+            rt._check_buffer(out, "farneback: out", torch.float32, dev, shape=(2, self.h, self.w))
         ws = rt.workspace(dev, "farneback", self.ws_bytes)
         with torch.cuda.device(dev):
             rt._check(rt.lib().adain_farneback_flow(pyr_prev.data_ptr(), pyr_next.data_ptr(), self.h, self.w, self.pyr_scale, self.levels,

@@ -178,6 +178,22 @@ def _dev(t, name, dtype=torch.float32):
     return t.contiguous()
 
 
+def _check_buffer(t, name, dtype, device, shape=None, numel=None, min_numel=None, align=None, distinct=()):
+    """Refuses a caller-supplied buffer that a kernel could not be handed as it is: not a contiguous ``dtype`` GPU tensor on
+    ``device``, not of ``shape`` / ``numel`` / at least ``min_numel`` elements, not ``align``-byte aligned, or starting where one
+    of the ``distinct`` inputs starts.  AdainHipError("<name> must be ...") before anything is launched."""
+    ok = (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == dtype and t.is_contiguous()
+          and (shape is None or tuple(t.shape) == tuple(shape)) and (numel is None or t.numel() == numel)
+          and (min_numel is None or t.numel() >= min_numel) and (align is None or t.data_ptr() % align == 0)
+          and t.data_ptr() not in [d.data_ptr() for d in distinct])
+    if not ok:
+        size = (f"[{','.join(map(str, shape))}]" if shape is not None else f"{numel}-element" if numel is not None
+                else f"at least {min_numel}-element" if min_numel is not None else "")
+        raise AdainHipError(f"{name} must be a contiguous{f', {align}-byte aligned' if align else ''} {str(dtype)[6:]} {size} tensor "
+                            f"on {device if device.type == 'cuda' else 'a GPU'}{', distinct from its inputs' if distinct else ''}")
+    return t
+
+
 def _ptr_array(tensors):
     arr = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
     return ctypes.cast(arr, _PP), arr
@@ -448,9 +464,8 @@ def quantize_u8(img, out=None):
     n, c, h, w = img.shape
     if out is None:
         out = torch.empty((n, h, w, c), dtype=torch.uint8, device=img.device)
-    elif (not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, c) or not out.is_contiguous()
-          or out.device != img.device):
-        raise AdainHipError(f"quantize_u8: out must be a contiguous uint8 {(n, h, w, c)} tensor on {img.device}")
+    else:
+        _check_buffer(out, "quantize_u8: out", torch.uint8, img.device, shape=(n, h, w, c))
     with torch.cuda.device(img.device):
         _check(lib().adain_quantize_u8(img.data_ptr(), out.data_ptr(), n, c, h, w, _stream()), "adain_quantize_u8")
     return out
@@ -496,8 +511,8 @@ def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, dept
     shape = (n, oh.value, ow.value, 3)
     if out is None:
         out = torch.empty(shape, dtype=torch.uint8, device=dev)
-    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
-        raise AdainHipError(f"stylize_u8: out must be a contiguous uint8 {shape} tensor on {dev}")
+    else:
+        _check_buffer(out, "stylize_u8: out", torch.uint8, dev, shape=shape)
     nbytes = L.adain_stylize_u8_workspace_bytes(n, h, w, int(depth_maps is not None), mn, mc, mh, mw, m_float)
     ws = workspace(dev, "stylize", nbytes)
     with torch.cuda.device(dev):
@@ -528,9 +543,8 @@ def warp_blend_u8(cur, prev, flow, alpha, out=None):
         raise AdainHipError("warp_blend_u8: shape mismatch")
     if out is None:
         out = torch.empty_like(cur)
-    elif (not out.is_cuda or out.dtype != torch.uint8 or out.shape != cur.shape or not out.is_contiguous() or out.device != cur.device
-          or out.data_ptr() in (cur.data_ptr(), prev.data_ptr())):
-        raise AdainHipError(f"warp_blend_u8: out must be a contiguous uint8 {tuple(cur.shape)} tensor on {cur.device}, distinct from cur and prev")
+    else:
+        _check_buffer(out, "warp_blend_u8: out", torch.uint8, cur.device, shape=cur.shape, distinct=(cur, prev))
     with torch.cuda.device(cur.device):
         _check(lib().adain_warp_blend_u8(cur.data_ptr(), prev.data_ptr(), flow.data_ptr(), out.data_ptr(), h, w, c, float(alpha),
                                          float(1 - alpha), _stream()), "adain_warp_blend_u8")
@@ -570,8 +584,8 @@ def resize_pil_bilinear_u8(frames, size, crop=None, out=None):
     y0, x0, ch, cw = (0, 0, ho, wo) if crop is None else [int(v) for v in crop]
     if out is None:
         out = torch.empty((n, max(ch, 0), max(cw, 0), 3), dtype=torch.uint8, device=x.device)
-    elif tuple(out.shape) != (n, ch, cw, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device:
-        raise AdainHipError(f"resize_pil_bilinear_u8: out must be a contiguous uint8 [{n},{ch},{cw},3] on {x.device}")
+    else:
+        _check_buffer(out, "resize_pil_bilinear_u8: out", torch.uint8, x.device, shape=(n, ch, cw, 3))
     # the tap tables live in the stream's workspace between the call's two launches: calls from several threads (the job feeders'
     # fetch pool) on one stream must not interleave
     with _pil_lock, torch.cuda.device(x.device):

@@ -85,10 +85,8 @@ class TVL1:
         n = g.shape[0]
         if out is None:
             out = torch.empty((n, self.frame_floats), dtype=torch.float32, device=g.device)
-        elif (not out.is_cuda or out.device != g.device or out.dtype != torch.float32 or not out.is_contiguous() or
-              out.numel() != n * self.frame_floats or out.data_ptr() % 256):
-            raise rt.AdainHipError(f"tvl1: out must be a contiguous, 256-byte aligned float32 buffer of {n} x {self.frame_floats} on "
-                                   f"{g.device}")
+        else:
+            rt._check_buffer(out, "tvl1: out", torch.float32, g.device, numel=n * self.frame_floats, align=256)
         with torch.cuda.device(g.device):
             rt._check(rt.lib().adain_tvl1_prepare(g.data_ptr(), n, self.h, self.w, ctypes.addressof(self.P), out.data_ptr(), rt._stream()),
                       "adain_tvl1_prepare")
@@ -114,18 +112,14 @@ class TVL1:
         dev = prev_list[0].device
         for t in list(prev_list) + list(next_list):
             # prepare() writes each frame 256-byte aligned; the kernels read it as float4 at 256-byte aligned scale offsets
-            if (not t.is_cuda or t.device != dev or t.dtype != torch.float32 or t.numel() < self.frame_floats or not t.is_contiguous()
-                    or t.data_ptr() % 256):
-                raise rt.AdainHipError("tvl1: prepared frames must be contiguous, 256-byte aligned float32 buffers made by prepare(), "
-                                       "all on one device")
+            rt._check_buffer(t, "tvl1: each of the prepared frames (made by prepare())", torch.float32, dev, min_numel=self.frame_floats,
+                             align=256)
         if out is None:
             out = torch.empty((n, 2, self.h, self.w), dtype=torch.float32, device=dev)
-        elif (not out.is_cuda or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (n, 2, self.h, self.w) or
-              not out.is_contiguous()):
-            raise rt.AdainHipError(f"tvl1: out must be a contiguous float32 [{n},2,{self.h},{self.w}] tensor on {dev}")
-        if iters_out is not None and (not iters_out.is_cuda or iters_out.device != dev or iters_out.dtype != torch.int32 or
-                                      not iters_out.is_contiguous() or tuple(iters_out.shape) != (n, len(self.scales), self.P.warps)):
-            raise rt.AdainHipError(f"tvl1: iters_out must be a contiguous int32 [{n},{len(self.scales)},{self.P.warps}] tensor on {dev}")
+        else:
+            rt._check_buffer(out, "tvl1: out", torch.float32, dev, shape=(n, 2, self.h, self.w))
+        if iters_out is not None:
+            rt._check_buffer(iters_out, "tvl1: iters_out", torch.int32, dev, shape=(n, len(self.scales), self.P.warps))
         ptrs = torch.tensor([t.data_ptr() for t in prev_list] + [t.data_ptr() for t in next_list], dtype=torch.int64).to(dev)
         nbytes = self.workspace_bytes(n)
         ws = rt.workspace(dev, "tvl1", nbytes)
@@ -219,9 +213,8 @@ class TVL1Sequence:
         m = max(1, min(m, n - 1))
         if out is None:
             out = torch.empty((n - 1, 2, h, w), dtype=torch.float32, device=grays[0].device)
-        elif (not out.is_cuda or out.device != grays[0].device or out.dtype != torch.float32 or tuple(out.shape) != (n - 1, 2, h, w)
-              or not out.is_contiguous()):
-            raise rt.AdainHipError(f"TVL1Sequence.batch: out must be a contiguous float32 [{n - 1},2,{h},{w}] tensor on {grays[0].device}")
+        else:
+            rt._check_buffer(out, "TVL1Sequence.batch: out", torch.float32, grays[0].device, shape=(n - 1, 2, h, w))
         ring = torch.empty((m + 1, tv.frame_floats), dtype=torch.float32, device=grays[0].device)
 
         def prepare(a, b):                  # frames a..b-1 into their slots, in contiguous runs of the ring

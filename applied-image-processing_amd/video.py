@@ -22,7 +22,8 @@ What stays with the caller, because the reference gets it from libraries this pa
     ``set_flow_provider(device_flow_provider_all)`` accepts both of the reference's method names: ``'farneback'`` as above and
     ``'dualtvl1'``, the package's Dual TV-L1 (tvl1.py, csrc/tvl1.hip: ``cv2.optflow.DualTVL1OpticalFlow_create().calc(prev, next,
     None)`` on the device); with it installed and ``'dualtvl1'`` rank 0 computes the clip's n-1 flows before the recurrence
-    (tvl1.TVL1Sequence.batch: each frame prepared once, many pairs per launch).
+    (tvl1.TVL1Sequence.batch: each frame prepared once, many pairs per launch).  With either installed, a method it does not
+    serve is refused before any frame is stylised.
 One deliberate difference: the reference writes every stylised frame as a JPEG into a temporary directory and reads it back
 (:261-273); here the uint8 frames stay in memory unless ``intermediate_jpeg=True`` re-creates that lossy round trip.
 """
@@ -94,6 +95,38 @@ def device_flow_provider_all(prev_frame_path, frame_path, target_resolution, met
     return tvl1.DualTVL1OpticalFlow_create().calc(prev, cur, None).permute(2, 0, 1).contiguous()
 
 
+# The package's own providers (by identity: a wrapper of one is an ordinary provider) and the methods each serves.  With one of them
+# installed, rank 0 refuses any other method before stylising and runs the served method's sequence path (_flow_source).
+_OWN_METHODS = {id(device_flow_provider): ("farneback",), id(device_flow_provider_all): ("farneback", "dualtvl1")}
+
+
+def _flow_source(content_dir, names, flow_method, size, device, cancel_flag):
+    """The recurrence's flows: ``f(i)`` is the [2,H,W] device flow frame i-1 -> frame i, called for i = 1, 2, ... in order.  The
+    package's own estimators decode and prepare every frame once, with the same bits as their providers per pair; any other
+    provider is called per pair."""
+    path = lambda k: os.path.join(content_dir, names[k])
+    if flow_method not in _OWN_METHODS.get(id(_flow_provider), ()):
+        return lambda i: estimate_optical_flow(path(i - 1), path(i), size, flow_method).to(device)
+    gray = lambda k: _decode_gray(path(k), size, device)
+    with torch.cuda.device(device):
+        if flow_method == "dualtvl1":
+            # all n-1 flows before the recurrence, up to max_pairs pairs per call (chunks); None when cancelled
+            from . import tvl1
+
+            flows = tvl1.TVL1Sequence().batch([gray(k) for k in range(len(names))], cancel=cancel_flag)
+            return lambda i: flows[i - 1]
+        # Farneback: one pyramid per frame, streamed (never n-1 flows at once)
+        from . import flow as fl
+
+        seq = fl.FlowSequence(0.5, 5, 15, 3, 7, 1.5, 0)
+        seq.push(gray(0))
+
+    def push(i):
+        with torch.cuda.device(device):
+            return seq.push(gray(i))
+    return push
+
+
 def normalize_image(image):
     """uint8 -> float32 in [0,1] before blending (video/utils.py:217-221)."""
     return image.astype(np.float32) / 255.0 if image.dtype == np.uint8 else image
@@ -129,18 +162,18 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
     dev = engine.device if engine is not None else (torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None)
     # Everything that can stop the job is settled BEFORE any rank starts computing, with one status word, so that no rank is
     # ever left waiting in a collective for a peer that has returned or raised: cancellation (the flag is a per-process Event),
-    # and the optical-flow provider the rank-0 recurrence will need from the second frame on (device_flow_provider_all: and a
-    # method name it knows).
+    # and the optical-flow provider the rank-0 recurrence will need from the second frame on (one of the package's own: and a
+    # method it serves).
     cancelled = cancel_flag is not None and cancel_flag.is_set()
     need_flow = rank == 0 and len(names) > 1 and _flow_provider is None
-    bad_method = (rank == 0 and len(names) > 1 and _flow_provider is device_flow_provider_all
-                  and flow_method not in ("farneback", "dualtvl1"))
+    own = _OWN_METHODS.get(id(_flow_provider))
+    bad_method = rank == 0 and len(names) > 1 and own is not None and flow_method not in own
     go = sh.agree_min(0 if need_flow or bad_method else 1 if cancelled else 2, group, dev)
     if go == 0:
         if need_flow:
             estimate_optical_flow(None, None, None)            # raises the "no optical-flow provider" error
         if bad_method:
-            device_flow_provider_all(None, None, None, flow_method)     # raises: unknown method
+            _flow_provider(None, None, None, flow_method)      # raises the provider's own refusal of the method
         raise RuntimeError("video style transfer: rank 0 has no optical-flow provider (video.set_flow_provider) or does not "
                            f"know the method {flow_method!r}")
     if go == 1:                                                # cancelled on some rank: every rank stops, as the reference loop does
@@ -192,41 +225,14 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
         try:
             n, h, w, _ = frames_u8.shape
             prev = None
-            seq = None
-            tv_flows = None
-            own_tvl1 = _flow_provider is device_flow_provider_all and flow_method == "dualtvl1"
-            if own_tvl1 and n > 1:
-                # the package's Dual TV-L1: all n-1 flows before the recurrence, each frame prepared once, up to max_pairs pairs per
-                # call (chunks); the same bits as device_flow_provider_all per pair
-                from . import tvl1
-
-                with torch.cuda.device(frames_u8.device):
-                    grays = [_decode_gray(os.path.join(content_dir, nm), (w, h), frames_u8.device) for nm in names]
-                    tv_flows = tvl1.TVL1Sequence().batch(grays, cancel=cancel_flag)
-            elif _flow_provider in (device_flow_provider, device_flow_provider_all) and n > 1:
-                # the package's own estimator: every frame decoded and expanded ONCE (the pair path does both twice per pair);
-                # the same bits as device_flow_provider per pair
-                from . import flow as fl
-
-                if flow_method != "farneback":
-                    device_flow_provider(None, None, None, flow_method)       # raises: the method is not built in
-                seq = fl.FlowSequence(0.5, 5, 15, 3, 7, 1.5, 0)
-                with torch.cuda.device(frames_u8.device):
-                    seq.push(_decode_gray(os.path.join(content_dir, names[0]), (w, h), frames_u8.device))
+            flow_of = _flow_source(content_dir, names, flow_method, (w, h), frames_u8.device, cancel_flag) if n > 1 else None
             for i, name in enumerate(names):
                 if cancel_flag is not None and cancel_flag.is_set():
                     print("Stopping style transfer...")
                     break
                 cur = frames_u8[i]
-                if prev is not None and tv_flows is not None:
-                    cur = engine.warp_blend_u8(cur.contiguous(), prev, tv_flows[i - 1], alpha)
-                elif prev is not None and seq is not None:
-                    with torch.cuda.device(cur.device):
-                        flow = seq.push(_decode_gray(os.path.join(content_dir, name), (w, h), cur.device))
-                    cur = engine.warp_blend_u8(cur.contiguous(), prev, flow, alpha)
-                elif prev is not None:
-                    flow = estimate_optical_flow(os.path.join(content_dir, names[i - 1]), os.path.join(content_dir, name), (w, h), flow_method)
-                    cur = engine.warp_blend_u8(cur.contiguous(), prev, flow.to(cur.device), alpha)
+                if prev is not None:
+                    cur = engine.warp_blend_u8(cur.contiguous(), prev, flow_of(i), alpha)
                 sink.write(cur.unsqueeze(0), [os.path.join(output_dir, name)])
                 print(f"Stylized and saved: {os.path.join(output_dir, name)}")
                 prev = cur

@@ -92,13 +92,19 @@ def gaussian_blur(img, ks, sigma, dtype):
     return out
 
 
-def _resize_mode(hi, wi, ho, wo):
-    sx, sy = 1.0 / (wo / wi), 1.0 / (ho / hi)
+def resize_mode(hi, wi, ho, wo, sx, sy):
+    """cv::resize's choice for (hi, wi) -> (ho, wo) with the source-per-destination scales sx, sy (csrc/cv_resize.h): 0 copy,
+    1 INTER_AREA's 2x2 mean at an exact 2x shrink, 2 linear."""
     if (ho, wo) == (hi, wi):
-        return 0, sx, sy
+        return 0
     ix, iy = cv_round(sx), cv_round(sy)
     fast = abs(sx - ix) < 2.220446049250313e-16 and abs(sy - iy) < 2.220446049250313e-16
-    return (1 if fast and ix == 2 and iy == 2 else 2), sx, sy
+    return 1 if fast and ix == 2 and iy == 2 else 2
+
+
+def _resize_mode(hi, wi, ho, wo):
+    sx, sy = 1.0 / (wo / wi), 1.0 / (ho / hi)
+    return resize_mode(hi, wi, ho, wo, sx, sy), sx, sy
 
 
 def _lin_taps(dsize, ssize, scale, xaxis):

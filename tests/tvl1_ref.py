@@ -50,10 +50,10 @@ def resize(src, wo, ho, sx, sy, dtype):
     mean, over the source pixels inside the image, at an exact 2x)."""
     hi, wi = src.shape
     s = src.astype(dtype)
-    if (hi, wi) == (ho, wo):
+    mode = F.resize_mode(hi, wi, ho, wo, sx, sy)
+    if mode == 0:
         return s.copy()
-    ix, iy = F.cv_round(sx), F.cv_round(sy)
-    if abs(sx - ix) < 2.220446049250313e-16 and abs(sy - iy) < 2.220446049250313e-16 and ix == 2 and iy == 2:
+    if mode == 1:
         out = np.zeros((ho, wo), dtype)
         for y in range(ho):
             for x in range(wo):
