@@ -39,6 +39,8 @@ constexpr size_t FIRST_W = 2 * 14 * 64, FIRST_B = 64, LAST_W = 8 * 64 * 4, LAST_
 // implicit GEMM and the F(2x2,3x3) families of rounds 1-2 were A/B baselines until round 6 and are retired (git history;
 // docs/HISTORY.md has their numbers).
 static size_t form_floats(int cin, int cout) { return (size_t)cin * cout * 24; }
+// the decoder's up layers run as four phase convolutions of the source (conv_wino4.hip, W4P): their own 4 x 24 floats per pair
+static size_t dec_form_floats(int i) { return form_floats(DEC[i].cin, DEC[i].cout) * (DEC[i].src == SRC_UP2X ? 4 : 1); }
 
 // packed layout: [first w][first b] then per generic layer [w in the form the schedules launch][b], every block 256-B
 // aligned: 75 MB for the two networks in the F(4,3) x F(2,3) form (only that form is packed and kept).
@@ -63,7 +65,7 @@ static Offsets dec_offsets() {
     size_t o = 0;
     for (int i = 0; i < 8; ++i) {
         f.w[i] = o;
-        o += align64(form_floats(DEC[i].cin, DEC[i].cout));
+        o += align64(dec_form_floats(i));
         f.b[i] = o;
         o += align64(DEC[i].cout);
     }
@@ -81,6 +83,13 @@ static int launch_layer(ConvArgs& a, const float* packed, const Offsets& f, int 
     a.bias = packed + f.b[i];
     a.wpk = packed + f.w[i];
     return launch_conv3x3_wino4(a, src, s, split);
+}
+// decoder layer i: the up layers in their polyphase form (never split along cin), the others as launch_layer
+static int launch_dec_layer(ConvArgs& a, const float* packed, const Offsets& f, int i, hipStream_t s, SplitWs split = SplitWs{nullptr, 0}) {
+    if (DEC[i].src != SRC_UP2X) return launch_layer(a, packed, f, i, DEC[i].src, s, split);
+    a.bias = packed + f.b[i];
+    a.wpk = packed + f.w[i];
+    return launch_conv3x3_up2x_poly(a, s);
 }
 
 static int copy_bias(const float* src, float* dst, int n, hipStream_t s) {
@@ -134,7 +143,8 @@ int adain_decoder_pack(const float* const* w, const float* const* b, float* pack
     hipStream_t s = (hipStream_t)stream;
     const Offsets f = dec_offsets();
     for (int i = 0; i < 8; ++i) {
-        RET_IF(pack_layer(w[i], packed + f.w[i], DEC[i].cin, DEC[i].cout, s));
+        if (DEC[i].src == SRC_UP2X) RET_IF(launch_pack_up2x_poly(w[i], packed + f.w[i], DEC[i].cin, DEC[i].cout, s));
+        else RET_IF(pack_layer(w[i], packed + f.w[i], DEC[i].cin, DEC[i].cout, s));
         RET_IF(copy_bias(b[i], packed + f.b[i], DEC[i].cout, s));
     }
     RET_IF(launch_pack_conv_last(w[8], packed + f.last_w, s));
@@ -434,7 +444,7 @@ static int decode_impl(const float* feat, float* image, uint8_t* image_u8, const
         a.H = ch; a.W = cw;
         a.cin = DEC[i].cin; a.cout = DEC[i].cout;
         a.relu = 1;
-        RET_IF(launch_layer(a, packed, f, i, DEC[i].src, s, split));
+        RET_IF(launch_dec_layer(a, packed, f, i, s, split));
         record(ev, i + 1, s);
         cur = a.out;
     }
@@ -450,7 +460,6 @@ static int decode_impl(const float* feat, float* image, uint8_t* image_u8, const
         for (int i = batched; i < 8; ++i) {
             ConvArgs a{};
             a.cin = DEC[i].cin; a.cout = DEC[i].cout; a.relu = 1;
-            a.bias = packed + f.b[i]; a.wpk = packed + f.w[i];
             a.in = c + (size_t)img * ch * cw * DEC[i].cin;
             a.n = 1;
             a.Hs = ch; a.Ws = cw;
@@ -458,7 +467,7 @@ static int decode_impl(const float* feat, float* image, uint8_t* image_u8, const
             a.H = ch; a.W = cw;
             float* out = (i & 1) ? bufB : bufA;
             a.out = out + (size_t)img * ch * cw * DEC[i].cout;
-            RET_IF(launch_conv3x3_wino4(a, DEC[i].src, s));
+            RET_IF(launch_dec_layer(a, packed, f, i, s));
             c = out;
         }
         RET_IF(launch_conv_last(c + (size_t)img * ch * cw * 64, image ? image + (size_t)img * 3 * ch * cw : nullptr, packed + f.last_w, packed + f.last_b,
@@ -744,6 +753,22 @@ int adain_conv3x3_wino(const float* in, float* out, const float* packed_w, const
 
 size_t adain_conv3x3_wino4_split_workspace_bytes(int n, int h, int w, int cin, int cout) {
     return wino4_split_floats(n, h, w, cin, cout) * sizeof(float);
+}
+
+size_t adain_conv3x3_up2x_poly_packed_floats(int cin, int cout) { return (size_t)cin * cout * 96; }
+
+int adain_conv3x3_up2x_poly_pack(const float* w, float* packed, int cin, int cout, adain_stream_t stream) {
+    if (!w || !packed) { set_error("conv3x3_up2x_poly_pack: null pointer"); return ADAIN_EINVAL; }
+    return launch_pack_up2x_poly(w, packed, cin, cout, (hipStream_t)stream);
+}
+
+int adain_conv3x3_up2x_poly(const float* in, float* out, const float* packed_w, const float* bias, int n, int hs, int ws, int cin, int cout,
+                            int relu, adain_stream_t stream) {
+    if (!in || !out || !packed_w || !bias) { set_error("conv3x3_up2x_poly: null pointer"); return ADAIN_EINVAL; }
+    ConvArgs a{};
+    a.in = in; a.out = out; a.wpk = packed_w; a.bias = bias;
+    a.n = n; a.Hs = hs; a.Ws = ws; a.H = 2 * hs; a.W = 2 * ws; a.cin = cin; a.cout = cout; a.relu = relu;
+    return launch_conv3x3_up2x_poly(a, (hipStream_t)stream);
 }
 
 int adain_conv3x3_wino4_split(const float* in, float* out, const float* packed_w, const float* bias, int n, int h, int w, int hs, int ws,

@@ -70,10 +70,39 @@ struct W4G {
     static_assert(GEO != 0 || (PROW / 4) % 16 == 8, "bank layout (2 x 16 tiles)");
     static_assert(GEO != 1 || (PROW / 4) % 4 == 2, "bank layout (4 x 8 tiles)");
     static_assert(HALO * 4 <= W4_RITEMS * 256, "staging items");
+    static constexpr int RITEMS = W4_RITEMS, RBUF = 8192, CH1 = 8;      // staging items per thread; floats per halo buffer; chunk 1
 };
-constexpr int W4_RBUF = 8192;                          // 2 planes + tail, rounded: two buffers = the exchange area
+// UP2X_POLY: a nearest-2x upsample + reflection pad + 3x3 conv is, per output phase (py, px) = pixels (2y + py, 2x + px), a 2 x 2
+// convolution of the SOURCE map with a clamp pad (up[-1] reflects to up[1] = src[0], up[2W] to src[W-1]); along one axis the even
+// phase applies (w0, w1 + w2) to src[i-1], src[i], the odd phase (w0 + w1, w2) to src[i], src[i+1].  F(5,2) uses the points of F(4,3)
+// and F(3,2) those of F(2,3), so the input transform - patch 6 x 4, 24 positions, one column per wave - is the kernel's own.  A tile
+// keeps 4 of the 5 rows F(5,2) yields (the fifth is the next tile's first; A5^T's rows 0-3 are A4^T's without the inf column, whose
+// position then feeds nothing kept): 4 x 3 outputs of one phase instead of 4 x 2, 24 / 12 = 2 multiplies per output instead of 3.
+// Tiles of 4 rows keep every tile boundary where the 3x3 kernel has one (multiples of 16 output rows): a frame and a band cut from it
+// on such rows compute the rows they share with the same arithmetic (5-row tiles, 1.6 multiplies, would not: test_gpu_parity's
+// 4k-frame bands).  An item is (tile group, channel tile, phase): the phase is folded into a VIRTUAL channel tile 4 ct + phase
+// (weights [cout/32][phase][j][cin/8][r][lane][4]).  Two halo buffers = 65,664 B per workgroup.
+// Tile group: 4 x 8 tiles = 16 x 24 outputs of the phase grid from an 18 x 25 source halo.  LDS image without per-pixel padding (the
+// 80-byte pixels of W4G would leave no room for a second workgroup): halo pixel (hy, hx), channel quad q at quad
+//   hy * 114 + q * 27 + (hx % 3) * 9 + hx / 3
+// so that a patch column c of the lanes' patches (3 pixels apart) sits in one column-mod-3 sub-row at consecutive quads: lane
+// (tile row tr = li >> 3, column tc = li & 7) reads quad 4 tr * 114 + tc + const; 456 = 8 (mod 16), so the four tile rows of a
+// ds_read_b128 lane group ({0-3,12-15,20-27}: tr 0 / 3 columns 0-3, tr 1 / 2 columns 4-7) land on quads {0-3}, {8-11}, {12-15},
+// {4-7} (mod 16) and those of the complement on {4-7}, {8-11}, {0-3}, {12-15}: all 16, conflict-free.  Staging stores hit at most
+// 2-way on one bank per 8-lane group, which a ds_write_b128 absorbs (its transfer, not the LDS array, sets its cycles).
+struct W4P {
+    static constexpr int TCOLS_LOG = 3;
+    static constexpr int TSTEP = 4;                                // output rows per tile (of the 5 F(5,2) yields)
+    static constexpr int TILE_H = 4 * TSTEP, TILE_W = 24, HALO_H = TILE_H + 2, HALO_W = 25, HALO = HALO_H * HALO_W;
+    static constexpr int RQ = 114, QQ = 27, SQ = 9;                // quads per halo row, per channel quad, per sub-row
+    static constexpr int PROW = 4 * RQ, PLANE = 0, TAIL = 0;
+    static constexpr int RITEMS = 8, RBUF = HALO_H * RQ * 4, CH1 = 2 * QQ * 4;
+    static_assert(4 * QQ <= RQ && 3 * SQ <= QQ, "row layout");
+    static_assert((TSTEP * RQ) % 16 == 8, "bank layout: tile rows 1 / 2 / 3 shifted by 8 / 0 / 8 quads against the column blocks");
+    static_assert(HALO * 4 <= RITEMS * 256 && 2 * RBUF * 4 <= 80 * 1024, "LDS layout");
+};
 constexpr int W4_PEX = 4 * 4 * 32 * 32;                // [column j][a][tile][32 channels] floats = 64 KiB
-static_assert(2 * W4_RBUF <= W4_PEX, "LDS layout");
+static_assert(2 * W4G<0>::RBUF <= W4_PEX && 2 * W4G<1>::RBUF <= W4_PEX, "LDS layout");
 
 // 128-bit buffer store.  The scalar offset operand is deliberately NOT exposed (always the literal 0): with an SGPR soffset LLVM
 // models no hazard between a >64-bit MUBUF store and a following VALU write of its data registers and emits none of the wait states
@@ -115,6 +144,44 @@ __global__ void pack_wino4_kernel(const float* __restrict__ w, float* __restrict
     }
 }
 
+// UP2X_POLY: OIHW [cout][cin][3][3] -> per phase (py, px) the folded 2 x 2 filter h = F_py g F_px^T (even phase (w0, w1 + w2), odd
+// phase (w0 + w1, w2) along each axis), then U = G5 h G3^T, packed as [cout/32][phase 2 py + px][j 4][cin/8][r 6][lane 64][s 4]
+// (pack_wino4_kernel's layout with the phase beside the channel tile: the kernel streams it as virtual channel tile 4 ct + phase).
+// Folded and transformed in double, rounded once.
+__global__ void pack_up2x_poly_kernel(const float* __restrict__ w, float* __restrict__ p, int cin, int cout) {
+    const double G3[4][2] = {{1., 0.}, {0.5, 0.5}, {0.5, -0.5}, {0., -1.}};
+    const double G5[6][2] = {{0.25, 0.}, {-1. / 6, -1. / 6}, {-1. / 6, 1. / 6}, {1. / 24, 1. / 12}, {1. / 24, -1. / 12}, {0., 1.}};
+    const size_t total = (size_t)cin * cout * 96;
+    const int nch = cin / 8;
+    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        size_t t = idx;
+        const int s = t & 3; t >>= 2;
+        const int lane = t & 63; t >>= 6;
+        const int r = t % 6; t /= 6;
+        const int chunk = t % nch; t /= nch;
+        const int j = t & 3; t >>= 2;
+        const int ph = t & 3; t >>= 2;
+        const int ct = (int)t, py = ph >> 1, px = ph & 1;
+        // fold: tap a of 2 takes taps {0} / {1, 2} of 3 (even phase) or {0, 1} / {2} (odd phase)
+        auto fold = [](int odd, int a, int t3) { return (double)(odd ? (a ? t3 == 2 : t3 < 2) : (a ? t3 > 0 : t3 == 0)); };
+        const int co = ct * 32 + (lane & 31), ci = chunk * 8 + 4 * (lane >> 5) + s;
+        const float* g = w + ((size_t)co * cin + ci) * 9;
+        double u = 0.;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                double h = 0.;
+#pragma unroll
+                for (int ty = 0; ty < 3; ++ty)
+#pragma unroll
+                    for (int tx = 0; tx < 3; ++tx) h += fold(py, a, ty) * fold(px, b, tx) * (double)g[ty * 3 + tx];
+                u += G5[r][a] * h * G3[j][b];
+            }
+        p[idx] = (float)u;
+    }
+}
+
 // The stamp and timing-only ablation variants that measured this kernel (what its data movement costs, where its steps wait) are
 // retired; docs/HISTORY.md keeps their numbers.
 // PERSIST: a workgroup walks a list of tiles (grid = 2 per CU; XCD x owns a contiguous range of the tile list, channel tile
@@ -134,10 +201,12 @@ __global__ void pack_wino4_kernel(const float* __restrict__ w, float* __restrict
 // BIG: per-tile buffer descriptors (any image size); the default form keeps one descriptor per image (tensors below 2 GiB)
 template <int MODE, bool PERSIST = false, bool BIG = false, int GEO = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvSegs m, int items) {
-    using G = W4G<GEO>;
+    constexpr bool POLY = MODE == SRC_UP2X_POLY;      // UP2X_POLY: see W4P
+    using G = std::conditional_t<POLY, W4P, W4G<GEO>>;
     constexpr int W4_HALO_W = G::HALO_W, W4_HALO_H = G::HALO_H, W4_HALO = G::HALO, W4_PROW = G::PROW, W4_PLANE = G::PLANE,
                   W4_TAIL = G::TAIL, TILE_W = G::TILE_W, TILE_H = G::TILE_H, TCL = G::TCOLS_LOG, TCM = (1 << G::TCOLS_LOG) - 1;
-    __shared__ __attribute__((aligned(16))) float smem[W4_PEX];
+    constexpr int RI = G::RITEMS, W4_RBUF = G::RBUF, CH1 = G::CH1;
+    __shared__ __attribute__((aligned(16))) float smem[POLY ? 2 * W4P::RBUF : W4_PEX];
     float* const Rs = smem;
 
     const int tid = threadIdx.x;
@@ -153,7 +222,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
 
     // block -> (channel tile fastest, pixel tile, image) inside a contiguous per-XCD range (halo reuse in L2)
     int tiles = a.tiles_x * a.tiles_y;
-    const int nct = a.cout / 32;
+    const int nct = (POLY ? 4 : 1) * (a.cout / 32);   // POLY: virtual channel tiles 4 ct + phase
     int lid = blockIdx.x, ct, pt, img;
     // geometry of the tile being computed (gH, gW: conv output size; gWs: source row length) and of its tensors
     int gH = a.H, gW = a.W, gWs = a.Ws, gtx = a.tiles_x;
@@ -216,7 +285,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
     auto src_row0 = [&](int y0) {
         if constexpr (!BIG) return 0;
         const int r = max(y0 - 1, 0);                  // reflection never reaches above this row (row -1 maps to row 1)
-        return MODE == SRC_UP2X ? r >> 1 : r;
+        return MODE == SRC_UP2X ? r >> 1 : r;          // (POLY: y0 is a source row; the window starts at y0 - 1 + py, clamped)
     };
     auto src_of = [&](const float* base, int Hs, int Ws, int im, int y0) {
         if constexpr (!BIG) {
@@ -230,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
         }
     };
     rsrc_t src = PERSIST ? src_of(m.s[seg].in, m.s[seg].Hs, m.s[seg].Ws, img, ty0) : src_of(a.in, a.Hs, a.Ws, img, ty0);
-    const rsrc_t wsr = make_rsrc(a.wpk, (unsigned)a.cin * a.cout * 96u);
+    const rsrc_t wsr = make_rsrc(a.wpk, (unsigned)a.cin * a.cout * (POLY ? 384u : 96u));
 
     // ---- raw halo staging: 340 pixels x 4 quads over 256 threads x 6 items ---------------------------------------------------
     // Per-lane byte offsets of the six staging items + a per-tile SCALAR base (the buffer load's soffset operand).  A tile whose
@@ -240,16 +309,45 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
     // tile, 78 vector instructions of the ~560 a tile spends outside its main loop (they cost matrix-pipe time: DESIGN.md 4).
     // Tile origins are multiples of 8 / 32, so the nearest-2x source index splits the same way: (x0 + hx - 1) >> 1 =
     // (x0 / 2 - 1) + ((hx + 1) >> 1).  Tiles at the image border take the general path (reflection, base 0).
-    int roff[W4_RITEMS];
+    int roff[RI];
     int tbase = 0, roff_seg = -1;
-    auto halo_offsets = [&](int x0, int y0, int H, int W, int Ws, int sg) {
+    auto halo_offsets = [&](int x0, int y0, int H, int W, int Ws, int sg, int vct) {
         const int t = PERSIST ? (lane_now() | (wj << 6)) : tid;        // persistent: recomputed per tile, nothing hoisted
+        if constexpr (POLY) {           // window of phase (py, px) = vct & 3 at source (y0 - 1 + py, x0 - 1 + px), clamped
+            const int Hs = H >> 1, wy = y0 - 1 + ((vct >> 1) & 1), wx = x0 - 1 + (vct & 1);
+            const int r0 = src_row0(y0);
+            if (PERSIST && wy >= 0 && wy + W4_HALO_H <= Hs && wx >= 0 && wx + W4_HALO_W <= Ws) {
+                if (roff_seg != sg) {
+#pragma unroll
+                    for (int k = 0; k < RI; ++k) {
+                        const int idx = t + k * 256;
+                        const int hp = min(idx >> 2, W4_HALO - 1), q = idx & 3;
+                        const int hy = hp / W4_HALO_W, hx = hp - hy * W4_HALO_W;
+                        roff[k] = ((hy * Ws + hx) * a.cin + q * 4) * 4;
+                    }
+                    roff_seg = sg;
+                }
+                tbase = (((wy - r0) * Ws + wx) * a.cin) * 4;
+            } else {
+#pragma unroll
+                for (int k = 0; k < RI; ++k) {
+                    const int idx = t + k * 256;
+                    const int hp = min(idx >> 2, W4_HALO - 1), q = idx & 3;
+                    const int hy = hp / W4_HALO_W, hx = hp - hy * W4_HALO_W;
+                    const int y = min(max(wy + hy, 0), Hs - 1) - r0, x = min(max(wx + hx, 0), Ws - 1);
+                    roff[k] = ((y * Ws + x) * a.cin + q * 4) * 4;
+                }
+                roff_seg = -1;
+                tbase = 0;
+            }
+            return;
+        }
         const bool interior = PERSIST && y0 >= 1 && y0 + W4_HALO_H - 1 <= H && x0 >= 1 && x0 + W4_HALO_W - 1 <= W;
         [[maybe_unused]] const int r0 = src_row0(y0);  // BIG: rows are counted from the tile's source descriptor
         if (interior) {
             if (roff_seg != sg) {
 #pragma unroll
-                for (int k = 0; k < W4_RITEMS; ++k) {
+                for (int k = 0; k < RI; ++k) {
                     const int idx = t + k * 256;
                     const int hp = min(idx >> 2, W4_HALO - 1), q = idx & 3;
                     const int hy = hp / W4_HALO_W, hx = hp - hy * W4_HALO_W;
@@ -263,7 +361,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
             tbase = ((by * Ws + bx) * a.cin) * 4;
         } else {
 #pragma unroll
-            for (int k = 0; k < W4_RITEMS; ++k) {
+            for (int k = 0; k < RI; ++k) {
                 const int idx = t + k * 256;
                 const int hp = min(idx >> 2, W4_HALO - 1), q = idx & 3;
                 const int hy = hp / W4_HALO_W, hx = hp - hy * W4_HALO_W;
@@ -276,30 +374,35 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
             tbase = PERSIST ? 0 : ks * a.cin_sub * 4;       // first channel of this workgroup's cin range
         }
     };
-    halo_offsets(tx0, ty0, gH, gW, gWs, seg);
-    f32x4 rawreg[W4_RITEMS];
+    halo_offsets(tx0, ty0, gH, gW, gWs, seg, ct);
+    f32x4 rawreg[RI];
     auto raw_load = [&](int soff) {
 #pragma unroll
-        for (int k = 0; k < W4_RITEMS; ++k) rawreg[k] = buf_load4(src, roff[k], tbase + soff);
+        for (int k = 0; k < RI; ++k) rawreg[k] = buf_load4(src, roff[k], tbase + soff);
     };
     // LDS address (in BYTES from the start of a halo buffer) of staging item k of this thread: pixel (t >> 2) + 64 k of the halo,
     // quad t & 3; depends on the thread only, computed once.  Bytes, so that a store into a buffer whose place is known at compile
     // time is the register + an immediate offset (the persistent form's stage loop: no address arithmetic at all).
-    int sa[W4_RITEMS];
+    int sa[RI];
     {
         const int t = tid;
 #pragma unroll
-        for (int k = 0; k < W4_RITEMS; ++k) {
+        for (int k = 0; k < RI; ++k) {
             const int hp = (t >> 2) + 64 * k, q = t & 3;
             const int hy = hp / W4_HALO_W, hx = hp - hy * W4_HALO_W;
-            sa[k] = 4 * (hp < W4_HALO ? (hx & 1) * W4_PLANE + hy * W4_PROW + (hx >> 1) * W4_RSTR + q * 4
-                                      : W4_TAIL + (hp - W4_HALO) * W4_RSTR + q * 4);
+            if constexpr (POLY) {       // items past the halo repeat its last pixel (the same bytes to the same place)
+                const int hc = min(hp, W4_HALO - 1), cy = hc / W4_HALO_W, cx = hc - cy * W4_HALO_W;
+                sa[k] = 16 * (cy * W4P::RQ + q * W4P::QQ + (cx % 3) * W4P::SQ + cx / 3);
+            } else {
+                sa[k] = 4 * (hp < W4_HALO ? (hx & 1) * W4_PLANE + hy * W4_PROW + (hx >> 1) * W4_RSTR + q * 4
+                                          : W4_TAIL + (hp - W4_HALO) * W4_RSTR + q * 4);
+            }
             asm volatile("" : "+v"(sa[k]));      // held in a register: left alone the compiler recomputes it (8 vector
         }                                        // instructions per item and stage, and every one of them costs matrix-pipe time)
     }
     auto raw_store = [&](float* buf) {
 #pragma unroll
-        for (int k = 0; k < W4_RITEMS; ++k) *(f32x4*)((char*)buf + sa[k]) = rawreg[k];
+        for (int k = 0; k < RI; ++k) *(f32x4*)((char*)buf + sa[k]) = rawreg[k];
     };
 
     // ---- weights: one b128 fragment per step (row position r), ring slot = r, loaded 5 steps ahead ---------------------------
@@ -326,6 +429,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
             f32x4 P0, P1, P2, P3;
+            const int slot = ((2 * rq + lh) ^ sw) << 2;    // channel quad of the 32, XOR-swizzled: conflict-free both ways
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int k = rq * 4 + e;
@@ -334,9 +438,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
                 P0[e] = acc[0][k] + s1 + s2;               // A4^T = (1,1,1,1,1,0) (0,1,-1,2,-2,0) (0,1,1,4,4,0) (0,1,-1,8,-8,1)
                 P1[e] = d1 + 2.f * d2;
                 P2[e] = s1 + 4.f * s2;
-                P3[e] = d1 + 8.f * d2 + acc[5][k];
+                P3[e] = d1 + 8.f * d2 + (POLY ? 0.f : acc[5][k]);      // POLY: rows 0-3 of A5^T (no inf column)
             }
-            const int slot = ((2 * rq + lh) ^ sw) << 2;    // channel quad of the 32, XOR-swizzled: conflict-free both ways
             *(f32x4*)(Pw + slot) = P0;
             *(f32x4*)(Pw + 1 * 32 * 32 + slot) = P1;
             *(f32x4*)(Pw + 2 * 32 * 32 + slot) = P2;
@@ -344,7 +447,46 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
         }
     }
     __syncthreads();
-    {
+    if constexpr (POLY) {
+        const int le = lane_now(), q8 = le & 7, tt = le >> 3;
+        const int tl = wj * 8 + tt;
+        const float* Pr = smem + tl * 32 + ((q8 ^ ((tl >> 1) & 7)) << 2);
+        const int ctr = ct >> 2, py = (ct >> 1) & 1, px = ct & 1;       // real channel tile, phase
+        const f32x4 bias4 = *(const f32x4*)(a.bias + ctr * 32 + 4 * q8);
+        const int eH = PERSIST ? m.s[seg].H : a.H, eW = PERSIST ? m.s[seg].W : a.W, pH = eH >> 1, pW = eW >> 1;
+        float* const eout = PERSIST ? m.s[seg].out : a.out;
+        rsrc_t dst;
+        if constexpr (!BIG) dst = make_rsrc(eout + (size_t)img * eH * eW * a.cout, (unsigned)(eH * eW * a.cout) * 4u);
+        else dst = make_rsrc(eout + ((size_t)img * eH + 2 * ty0) * eW * a.cout, 0x7ffffff0u);      // stores masked per lane
+        const int gy = ty0 + W4P::TSTEP * (tl >> TCL), gx = tx0 + 3 * (tl & TCM);     // the tile's first output in the phase grid
+        const int ry = (BIG ? 2 * W4P::TSTEP * (tl >> TCL) : 2 * gy) + py, ox = 2 * gx + px;
+        const int cbyte = (ctr * 32 + 4 * q8) * 4;
+        const float relu_lo = a.relu ? 0.f : -__builtin_inff();
+        f32x4 P[4][4];
+#pragma unroll
+        for (int ap = 0; ap < 4; ++ap)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) P[ap][j] = *(const f32x4*)(Pr + (j * 4 + ap) * (32 * 32));
+        if constexpr (PERSIST) {
+            __syncthreads();                               // every wave has its P values: the LDS image is free again
+            raw_store(Rs);                                 // the next tile's first halo stage (loaded during this tile)
+        }
+#pragma unroll
+        for (int ap = 0; ap < 4; ++ap) {
+            f32x4 y[3];
+            y[0] = P[ap][0] + P[ap][1] + P[ap][2] + bias4;          // A3 = columns (1,1,1,0), (0,1,-1,0), (0,1,1,1)
+            y[1] = P[ap][1] - P[ap][2] + bias4;
+            y[2] = P[ap][1] + P[ap][2] + P[ap][3] + bias4;
+            const int off = (((ry + 2 * ap) * eW + ox) * a.cout) * 4 + cbyte;
+            const bool rowok = gy + ap < pH;
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[b][e] = __builtin_amdgcn_fmed3f(y[b][e], relu_lo, __builtin_inff());
+                buf_store4(dst, y[b], (rowok && gx + b < pW) ? off + b * 2 * a.cout * 4 : 0x7fffffff);
+            }
+        }
+    } else {
         const int le = lane_now(), q8 = le & 7, tt = le >> 3;
         const int tl = wj * 8 + tt;
         const float* Pr = smem + tl * 32 + ((q8 ^ ((tl >> 1) & 7)) << 2);
@@ -448,11 +590,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
         int xaddr = 0;          // this lane's patch origin in the halo image (floats): computed once, held in a register
         {
             const int li = lane & 31, lh = lane >> 5;
-            xaddr = (4 * (li >> TCL)) * W4_PROW + (li & TCM) * W4_RSTR + 4 * lh;
+            if constexpr (POLY) xaddr = 4 * (W4P::TSTEP * (li >> TCL) * W4P::RQ + (li & TCM) + lh * W4P::QQ);
+            else xaddr = (4 * (li >> TCL)) * W4_PROW + (li & TCM) * W4_RSTR + 4 * lh;
             asm volatile("" : "+v"(xaddr));
         }
         // patch pixel (row a, column c of the 6 x 4 patch) relative to xaddr: plane c & 1, plane column + (c >> 1)
-        auto poff = [=](int a, int c) { return (c & 1) * W4_PLANE + a * W4_PROW + (c >> 1) * W4_RSTR; };
+        auto poff = [=](int a, int c) {
+            if constexpr (POLY) return 4 * (a * W4P::RQ + (c % 3) * W4P::SQ + c / 3);
+            else return (c & 1) * W4_PLANE + a * W4_PROW + (c >> 1) * W4_RSTR;
+        };
         auto xf_read3 = [&](const float* rb, int a0) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -504,8 +650,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
                     if constexpr (m == 8) bq[2] = buf_load4(wsr, wvo, wnext + 2 * 1024);
                     if constexpr (m == 9) bq[3] = buf_load4(wsr, wvo, wnext + 3 * 1024);
                 }
-                // ---- halo loads two stages ahead, in the first two thirds of the chunk (regions 5, 7, 9, 11, 13, 15) ----
-                if constexpr (ld && b == 1 && h >= 5 && h <= 15) {
+                // ---- halo loads two stages ahead, in the odd regions from 5 (5..15; POLY's nine items 5..21) ----
+                if constexpr (ld && b == 1 && h >= 5 && h < 5 + 2 * RI) {
                     constexpr int k = (h - 5) / 2;
                     rawreg[k] = buf_load4(src, roff[k], tbase + raw_soff);
                 }
@@ -520,7 +666,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
                     if constexpr (h == 23) { aq[3] = t3 + 2.f * d31; o4 = t3 - 2.f * d31; o5 = 4.f * f[1] + (f[5] - 5.f * f[3]); }
                 }
                 // ---- halo store of the stage loaded one stage ago ----
-                if constexpr (st && h >= 17 && h <= 22) *(f32x4*)((char*)store_to + sa[h - 17]) = rawreg[h - 17];
+                if constexpr (st && h >= 23 - RI && h <= 22) *(f32x4*)((char*)store_to + sa[h - (23 - RI)]) = rawreg[h - (23 - RI)];
                 if constexpr (do_xf && h == 23) { aq[4] = o4; aq[5] = o5; }
             };
             auto region = [&](auto HH) {
@@ -549,16 +695,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
             // stages in pairs (even stage: reads buffer 0, fills buffer 1; odd stage: the reverse): every LDS address of the loop is a
             // register + an immediate (see the persistent form); the last pair is its first half when nst is even
             for (int s = 0; s + 1 < nst; s += 2) {
-                chunk(Rs + 8, T, T, F, 0, Rs + W4_RBUF, wso + 6144, F);        // channels 0..7; prepares 8..15; writes the next stage's halo
+                chunk(Rs + CH1, T, T, F, 0, Rs + W4_RBUF, wso + 6144, F);        // channels 0..7; prepares 8..15; writes the next stage's halo
                 __syncthreads();
                 chunk(Rs + W4_RBUF, T, F, T, (s + 2) * W4_KR * 4, nullptr, wso + 6144, F);      // channels 8..15; prepares the next stage; loads two stages ahead
                 if (s + 2 < nst) {
-                    chunk(Rs + W4_RBUF + 8, T, T, F, 0, Rs, wso + 6144, F);
+                    chunk(Rs + W4_RBUF + CH1, T, T, F, 0, Rs, wso + 6144, F);
                     __syncthreads();
                     chunk(Rs, T, F, T, (s + 3) * W4_KR * 4, nullptr, wso + 6144, F);
                 }
             }
-            chunk(Rs + ((nst - 1) & 1) * W4_RBUF + 8, T, F, F, 0, nullptr, wso + 6144, F);
+            chunk(Rs + ((nst - 1) & 1) * W4_RBUF + CH1, T, F, F, 0, nullptr, wso + 6144, F);
             chunk(Rs, F, F, F, 0, nullptr, wso + 6144, F);
         } else {
             int ntile = 0;
@@ -584,11 +730,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
                 // inlined copies of the offset code.  The price: the stage that has nothing left to request re-requests the tile's
                 // last stage (six loads per thread and tile that hit in L1 / L2 and are never stored).
                 auto next_halo = [&]() {
-                    halo_offsets(ntx0, nty0, m.s[nseg].H, m.s[nseg].W, m.s[nseg].Ws, nseg);
+                    halo_offsets(ntx0, nty0, m.s[nseg].H, m.s[nseg].W, m.s[nseg].Ws, nseg, nct_);
                     src = src_of(m.s[nseg].in, m.s[nseg].Hs, m.s[nseg].Ws, nimg, nty0);
                 };
                 {   // stage 0, peeled: its first chunk starts the tile's accumulators (FIRST)
-                    chunk(Rs + 8, T, T, F, 0, Rs + W4_RBUF, wso + 6144, T);
+                    chunk(Rs + CH1, T, T, F, 0, Rs + W4_RBUF, wso + 6144, T);
                     __syncthreads();
                     chunk(Rs + W4_RBUF, T, F, T, min(2, nst - 1) * W4_KR * 4, nullptr, wso + 6144, F);
                 }
@@ -597,17 +743,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino4_kernel(ConvArgs a, ConvS
                 // instructions per stage on `base + offset` (of 152; every one costs matrix-pipe time).  cin a multiple of 32 gives
                 // whole pairs; otherwise the last pair is its first half.
                 for (int s = 1; s + 1 < nst; s += 2) {
-                    chunk(Rs + W4_RBUF + 8, T, T, F, 0, Rs, wso + 6144, F);
+                    chunk(Rs + W4_RBUF + CH1, T, T, F, 0, Rs, wso + 6144, F);
                     __syncthreads();
                     chunk(Rs, T, F, T, min(s + 2, nst - 1) * W4_KR * 4, nullptr, wso + 6144, F);
                     if (s + 2 < nst) {
-                        chunk(Rs + 8, T, T, F, 0, Rs + W4_RBUF, wso + 6144, F);
+                        chunk(Rs + CH1, T, T, F, 0, Rs + W4_RBUF, wso + 6144, F);
                         __syncthreads();
                         chunk(Rs + W4_RBUF, T, F, T, min(s + 3, nst - 1) * W4_KR * 4, nullptr, wso + 6144, F);
                     }
                 }
                 next_halo();
-                chunk(Rs + ((nst - 1) & 1) * W4_RBUF + 8, T, F, T, 0, nullptr, wso + 6144, F);      // + the next tile's first halo stage
+                chunk(Rs + ((nst - 1) & 1) * W4_RBUF + CH1, T, F, T, 0, nullptr, wso + 6144, F);      // + the next tile's first halo stage
                 chunk(Rs, F, F, F, 0, nullptr, wso_next, F);      // the ring's look-ahead continues in the next tile's weights
                 wso = wso_next;
                 __syncthreads();
@@ -681,6 +827,14 @@ int launch_pack_wino4(const float* w, float* p, int cin, int cout, hipStream_t s
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(pack_wino4_kernel, dim3(blocks), dim3(256), 0, s, w, p, cin, cout);
     return check_launch("pack_wino4");
+}
+
+int launch_pack_up2x_poly(const float* w, float* p, int cin, int cout, hipStream_t s) {
+    if (cin % 8 || cout % 32 || cin < 8 || cout < 32) { set_error("pack_up2x_poly: cin %% 8 or cout %% 32 != 0 (%d, %d)", cin, cout); return -1; }
+    const size_t total = (size_t)cin * cout * 96;
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(pack_up2x_poly_kernel, dim3(blocks), dim3(256), 0, s, w, p, cin, cout);
+    return check_launch("pack_up2x_poly");
 }
 
 // a per-image source or output tensor of 2 GiB or more needs the per-tile descriptors (BIG instantiations)
@@ -889,4 +1043,41 @@ int launch_conv3x3_wino4_multi(const ConvArgs& layer, const ConvSeg* segs, int c
     return check_launch("conv3x3_wino4(multi)");
 }
 
+}  // namespace adain
+
+namespace adain {
+// The decoder's up layers (nearest 2x upsample + reflection pad + 3x3 conv) as four phase convolutions of the source (W4P): weights
+// from launch_pack_up2x_poly; (a.H, a.W) = 2 (a.Hs, a.Ws).  Never split along cin (the latency schedule runs these layers whole).
+int launch_conv3x3_up2x_poly(const ConvArgs& a0, hipStream_t s) {
+    ConvArgs a = a0;
+    a.ksplit = 1; a.cin_sub = a.cin; a.slab_stride = 0;
+    if (a.cin % W4_KR || a.cin < W4_KR) { set_error("conv3x3_up2x_poly: cin %d not a multiple of 16", a.cin); return -1; }
+    if (a.cout % 32 || a.cout < 32) { set_error("conv3x3_up2x_poly: cout %d not a multiple of 32", a.cout); return -1; }
+    if (a.n < 1 || a.Hs < 1 || a.Ws < 1 || a.H != 2 * a.Hs || a.W != 2 * a.Ws) {
+        set_error("conv3x3_up2x_poly: needs n >= 1, a source of at least 1x1 and H == 2 Hs, W == 2 Ws (got %d: %dx%d -> %dx%d)", a.n, a.Hs, a.Ws, a.H, a.W);
+        return -1;
+    }
+    if (a.pool_out) { set_error("conv3x3_up2x_poly: no fused output pool"); return -1; }
+    // per-tile descriptors address a band of 19 source / 32 output rows with 32-bit offsets
+    if ((size_t)a.Ws * a.cin * 4 * 19 >= 0x7ffffff0ULL || (size_t)a.W * a.cout * 4 * 32 >= 0x7ffffff0ULL) {
+        set_error("conv3x3_up2x_poly: a band of 19 source or 32 output rows reaches 2 GiB");
+        return -1;
+    }
+    if ((size_t)a.cin * a.cout * 384 >= 0xffffffffULL) { set_error("conv3x3_up2x_poly: packed weights must stay below 4 GiB"); return -1; }
+    const bool big = wino4_big(a);
+    a.tiles_x = (a.Ws + W4P::TILE_W - 1) / W4P::TILE_W;
+    a.tiles_y = (a.Hs + W4P::TILE_H - 1) / W4P::TILE_H;
+    ConvSegs m{};
+    m.count = 1;
+    m.s[0] = ConvSeg{a.in, a.out, a.n, a.H, a.W, a.Hs, a.Ws, a.tiles_x, a.tiles_y, 0};
+    m.ctg = walk_group(a.cin, 4 * a.cout);           // virtual channel tiles 4 ct + phase: the phases of a channel tile share halos
+    const long long blocks = (long long)a.tiles_x * a.tiles_y * (4 * a.cout / 32) * a.n;
+    if (blocks <= 0 || blocks > 0x7fffffffLL) { set_error("conv3x3_up2x_poly: bad grid %lld", blocks); return -1; }
+    // One tile per workgroup: the persistent form's loop-carried next-tile state does not fit beside nine staging items per thread
+    // (the build spills; the one-tile form holds 246 registers and no scratch).
+    const dim3 g((unsigned)blocks);
+    if (big) hipLaunchKernelGGL((conv3x3_wino4_kernel<SRC_UP2X_POLY, false, true>), g, dim3(256), 0, s, a, m, (int)blocks);
+    else hipLaunchKernelGGL((conv3x3_wino4_kernel<SRC_UP2X_POLY, false, false>), g, dim3(256), 0, s, a, m, (int)blocks);
+    return check_launch("conv3x3_up2x_poly");
+}
 }  // namespace adain

@@ -86,6 +86,9 @@ SIGNATURES = {
     "adain_conv3x3_wino4_pack": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p]),
     "adain_conv3x3_wino": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p] + [_c_int] * 11 + [_c_void_p]),
     "adain_conv3x3_wino4_split_workspace_bytes": (_c_size_t, [_c_int] * 5),
+    "adain_conv3x3_up2x_poly_packed_floats": (_c_size_t, [_c_int, _c_int]),
+    "adain_conv3x3_up2x_poly_pack": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p]),
+    "adain_conv3x3_up2x_poly": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p] + [_c_int] * 6 + [_c_void_p]),
     "adain_conv3x3_wino4_split": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p] + [_c_int] * 10 + [_c_void_p, _c_size_t, _c_void_p]),
 }
 
@@ -637,6 +640,29 @@ def conv3x3_wino(x_nhwc, packed_w, bias, cout, src_mode=SRC_DIRECT, relu=True, p
     with torch.cuda.device(x.device):
         _check(lib().adain_conv3x3_wino(x.data_ptr(), out.data_ptr(), packed_w.data_ptr(), bias.data_ptr(), n, h, w, hs, ws_, cin, cout,
                                         src_mode, int(relu), int(pool_out), int(m_tiles), _stream()), "adain_conv3x3_wino")
+    return out
+
+
+def conv3x3_up2x_poly_pack(w_oihw):
+    """Packed weights of the polyphase up layer (adain_conv3x3_up2x_poly_pack): per output phase the folded 2 x 2 filter in
+    Winograd F(5,2) x F(3,2), 96 floats per (cin, cout) pair."""
+    w = _dev(w_oihw, "weight")
+    cout, cin = w.shape[:2]
+    packed = torch.empty(lib().adain_conv3x3_up2x_poly_packed_floats(cin, cout), dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(lib().adain_conv3x3_up2x_poly_pack(w.data_ptr(), packed.data_ptr(), cin, cout, _stream()), "adain_conv3x3_up2x_poly_pack")
+    return packed
+
+
+def conv3x3_up2x_poly(x_nhwc, packed_w, bias, cout, relu=True):
+    """The decoder's up layer as the schedules run it: nearest 2x upsample + ReflectionPad2d(1) + Conv2d [+ ReLU] on NHWC, as four
+    phase convolutions of the source (weights packed by conv3x3_up2x_poly_pack)."""
+    x = _dev(x_nhwc, "x")
+    n, hs, ws_, cin = x.shape
+    out = torch.empty((n, 2 * hs, 2 * ws_, cout), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().adain_conv3x3_up2x_poly(x.data_ptr(), out.data_ptr(), packed_w.data_ptr(), bias.data_ptr(), n, hs, ws_, cin, cout,
+                                             int(relu), _stream()), "adain_conv3x3_up2x_poly")
     return out
 
 

@@ -325,6 +325,15 @@ ADAIN_API int adain_conv3x3_wino4_split(const float* in_nhwc, float* out_nhwc, c
                               int w, int hs, int ws, int cin, int cout, int src_mode, int relu, int pool_out, void* workspace,
                               size_t workspace_bytes, adain_stream_t stream);
 
+/* The decoder's up layers as the schedules run them: nearest-2x upsample + ReflectionPad2d(1) + Conv2d(cin, cout, 3) [+ ReLU] on NHWC,
+ * computed as four 2 x 2 phase convolutions of the source (pixels (2y + py, 2x + px)) in Winograd F(5,2) x F(3,2), 4 of the 5 rows
+ * kept: 2 multiplies per output instead of 3.  in: [n][hs][ws][cin]; out: [n][2 hs][2 ws][cout].  Weights packed by adain_conv3x3_up2x_poly_pack, 96 floats per
+ * (cin, cout) pair; cin % 16 == 0, cout % 32 == 0, hs, ws >= 1.  For unit tests and profiling. */
+ADAIN_API size_t adain_conv3x3_up2x_poly_packed_floats(int cin, int cout);
+ADAIN_API int adain_conv3x3_up2x_poly_pack(const float* w_oihw, float* packed, int cin, int cout, adain_stream_t stream);
+ADAIN_API int adain_conv3x3_up2x_poly(const float* in_nhwc, float* out_nhwc, const float* packed_w, const float* bias, int n, int hs,
+                                      int ws, int cin, int cout, int relu, adain_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
