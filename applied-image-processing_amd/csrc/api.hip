@@ -21,16 +21,17 @@ void set_error(const char* fmt, ...) {
 
 // Layer tables.  Encoder = net.vgg[:31] (reference net.py:38-69): conv0+conv1_1 folded ("first"), then
 // 8 generic 3x3 convs; the ceil-mode max-pools in front of conv2_1, conv3_1, conv4_1 are fused into those
-// convs' gathers.  Decoder = net.decoder (net.py:6-36): 8 generic convs (the nearest-2x upsamples in front
-// of the 2nd, 6th and 8th are fused into their gathers) + the 64->3 "last" conv.
+// convs' producers.  Decoder = net.decoder (net.py:6-36): 8 generic convs (the nearest-2x upsamples in front
+// of the 2nd, 6th and 8th are fused into them) + the 64->3 "last" conv.
 // `pool` = the layer's output feeds a max-pool: the pool is fused into this layer's EPILOGUE (only the pooled
-// tensor is written), so the next conv reads it directly.  (The consumer-side form, SRC_POOL2, stays available
-// through adain_conv3x3.)
-struct Layer { int cin, cout, src, pool; };
-static const Layer ENC[8] = {{64, 64, SRC_DIRECT, 1},   {64, 128, SRC_DIRECT, 0},  {128, 128, SRC_DIRECT, 1}, {128, 256, SRC_DIRECT, 0},
-                             {256, 256, SRC_DIRECT, 0}, {256, 256, SRC_DIRECT, 0}, {256, 256, SRC_DIRECT, 1}, {256, 512, SRC_DIRECT, 0}};
-static const Layer DEC[8] = {{512, 256, SRC_DIRECT, 0}, {256, 256, SRC_UP2X, 0},   {256, 256, SRC_DIRECT, 0}, {256, 256, SRC_DIRECT, 0},
-                             {256, 128, SRC_DIRECT, 0}, {128, 128, SRC_UP2X, 0},   {128, 64, SRC_DIRECT, 0},  {64, 64, SRC_UP2X, 0}};
+// tensor is written), so the next conv reads it directly.  `up` = the layer reads the nearest-2x upsample of its
+// source: it runs as four phase convolutions of the source (conv_wino4.hip, W4P) with their own 4 x 24 floats per
+// weight pair.
+struct Layer { int cin, cout, pool, up; };
+static const Layer ENC[8] = {{64, 64, 1, 0},   {64, 128, 0, 0},  {128, 128, 1, 0}, {128, 256, 0, 0},
+                             {256, 256, 0, 0}, {256, 256, 0, 0}, {256, 256, 1, 0}, {256, 512, 0, 0}};
+static const Layer DEC[8] = {{512, 256, 0, 0}, {256, 256, 0, 1}, {256, 256, 0, 0}, {256, 256, 0, 0},
+                             {256, 128, 0, 0}, {128, 128, 0, 1}, {128, 64, 0, 0},  {64, 64, 0, 1}};
 
 static size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 constexpr size_t FIRST_W = 2 * 14 * 64, FIRST_B = 64, LAST_W = 8 * 64 * 4, LAST_B = 3;
@@ -38,58 +39,33 @@ constexpr size_t FIRST_W = 2 * 14 * 64, FIRST_B = 64, LAST_W = 8 * 64 * 4, LAST_
 // The generic 3x3 layers run - and the library only contains - the Winograd F(4,3) x F(2,3) kernels (csrc/conv_wino4.hip).  The direct
 // implicit GEMM and the F(2x2,3x3) families of rounds 1-2 were A/B baselines until round 6 and are retired (git history;
 // docs/HISTORY.md has their numbers).
-static size_t form_floats(int cin, int cout) { return (size_t)cin * cout * 24; }
-// the decoder's up layers run as four phase convolutions of the source (conv_wino4.hip, W4P): their own 4 x 24 floats per pair
-static size_t dec_form_floats(int i) { return form_floats(DEC[i].cin, DEC[i].cout) * (DEC[i].src == SRC_UP2X ? 4 : 1); }
+static size_t form_floats(const Layer& l) { return (size_t)l.cin * l.cout * 24 * (l.up ? 4 : 1); }
 
-// packed layout: [first w][first b] then per generic layer [w in the form the schedules launch][b], every block 256-B
-// aligned: 75 MB for the two networks in the F(4,3) x F(2,3) form (only that form is packed and kept).
+// packed layout: [first w][first b] (encoder) then per generic layer [w in the form the schedules launch][b], then [last w][last b]
+// (decoder), every block 256-B aligned: 75 MB for the two networks in the F(4,3) x F(2,3) form (only that form is packed and kept).
 struct Offsets { size_t w[8], b[8], first_b, last_w, last_b, total; };
-static Offsets enc_offsets() {
+static Offsets offsets(const Layer* L) {
     Offsets f{};
     size_t o = 0;
-    o += align64(FIRST_W);
-    f.first_b = o;
-    o += align64(FIRST_B);
+    if (L == ENC) {
+        o += align64(FIRST_W);
+        f.first_b = o;
+        o += align64(FIRST_B);
+    }
     for (int i = 0; i < 8; ++i) {
         f.w[i] = o;
-        o += align64(form_floats(ENC[i].cin, ENC[i].cout));
+        o += align64(form_floats(L[i]));
         f.b[i] = o;
-        o += align64(ENC[i].cout);
+        o += align64(L[i].cout);
+    }
+    if (L == DEC) {
+        f.last_w = o;
+        o += align64(LAST_W);
+        f.last_b = o;
+        o += align64(LAST_B);
     }
     f.total = o;
     return f;
-}
-static Offsets dec_offsets() {
-    Offsets f{};
-    size_t o = 0;
-    for (int i = 0; i < 8; ++i) {
-        f.w[i] = o;
-        o += align64(dec_form_floats(i));
-        f.b[i] = o;
-        o += align64(DEC[i].cout);
-    }
-    f.last_w = o;
-    o += align64(LAST_W);
-    f.last_b = o;
-    o += align64(LAST_B);
-    f.total = o;
-    return f;
-}
-
-static int pack_layer(const float* w, float* dst, int cin, int cout, hipStream_t s) { return launch_pack_wino4(w, dst, cin, cout, s); }
-
-static int launch_layer(ConvArgs& a, const float* packed, const Offsets& f, int i, int src, hipStream_t s, SplitWs split = SplitWs{nullptr, 0}) {
-    a.bias = packed + f.b[i];
-    a.wpk = packed + f.w[i];
-    return launch_conv3x3_wino4(a, src, s, split);
-}
-// decoder layer i: the up layers in their polyphase form (never split along cin), the others as launch_layer
-static int launch_dec_layer(ConvArgs& a, const float* packed, const Offsets& f, int i, hipStream_t s, SplitWs split = SplitWs{nullptr, 0}) {
-    if (DEC[i].src != SRC_UP2X) return launch_layer(a, packed, f, i, DEC[i].src, s, split);
-    a.bias = packed + f.b[i];
-    a.wpk = packed + f.w[i];
-    return launch_conv3x3_up2x_poly(a, s);
 }
 
 static int copy_bias(const float* src, float* dst, int n, hipStream_t s) {
@@ -104,11 +80,20 @@ static void record(void* const* ev, int i, hipStream_t s) {
     if (ev && ev[i]) (void)hipEventRecord((hipEvent_t)ev[i], s);
 }
 
+#define RET_IF(x) do { int _r = (x); if (_r) return _r; } while (0)
+
+// the 8 generic layers' weights (w[i], b[i]) into their blocks of a packed network
+static int pack_generic(const Layer* L, const float* const* w, const float* const* b, float* packed, const Offsets& f, hipStream_t s) {
+    for (int i = 0; i < 8; ++i) {
+        RET_IF((L[i].up ? launch_pack_up2x_poly : launch_pack_wino4)(w[i], packed + f.w[i], L[i].cin, L[i].cout, s));
+        RET_IF(copy_bias(b[i], packed + f.b[i], L[i].cout, s));
+    }
+    return 0;
+}
+
 }  // namespace adain
 
 using namespace adain;
-
-#define RET_IF(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 extern "C" {
 
@@ -123,33 +108,24 @@ int adain_set_schedule(int schedule) {
 }
 int adain_get_schedule(void) { return g_schedule; }
 
-size_t adain_encoder_packed_floats(void) { return enc_offsets().total; }
-size_t adain_decoder_packed_floats(void) { return dec_offsets().total; }
+size_t adain_encoder_packed_floats(void) { return offsets(ENC).total; }
+size_t adain_decoder_packed_floats(void) { return offsets(DEC).total; }
 
 int adain_encoder_pack(const float* const* w, const float* const* b, float* packed, adain_stream_t stream) {
     if (!w || !b || !packed) { set_error("encoder_pack: null pointer"); return ADAIN_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    const Offsets f = enc_offsets();
+    const Offsets f = offsets(ENC);
     RET_IF(launch_pack_conv_first(w[0], b[0], w[1], b[1], packed, packed + f.first_b, s));
-    for (int i = 0; i < 8; ++i) {
-        RET_IF(pack_layer(w[i + 2], packed + f.w[i], ENC[i].cin, ENC[i].cout, s));
-        RET_IF(copy_bias(b[i + 2], packed + f.b[i], ENC[i].cout, s));
-    }
-    return 0;
+    return pack_generic(ENC, w + 2, b + 2, packed, f, s);
 }
 
 int adain_decoder_pack(const float* const* w, const float* const* b, float* packed, adain_stream_t stream) {
     if (!w || !b || !packed) { set_error("decoder_pack: null pointer"); return ADAIN_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    const Offsets f = dec_offsets();
-    for (int i = 0; i < 8; ++i) {
-        if (DEC[i].src == SRC_UP2X) RET_IF(launch_pack_up2x_poly(w[i], packed + f.w[i], DEC[i].cin, DEC[i].cout, s));
-        else RET_IF(pack_layer(w[i], packed + f.w[i], DEC[i].cin, DEC[i].cout, s));
-        RET_IF(copy_bias(b[i], packed + f.b[i], DEC[i].cout, s));
-    }
+    const Offsets f = offsets(DEC);
+    RET_IF(pack_generic(DEC, w, b, packed, f, s));
     RET_IF(launch_pack_conv_last(w[8], packed + f.last_w, s));
-    RET_IF(copy_bias(b[8], packed + f.last_b, 3, s));
-    return 0;
+    return copy_bias(b[8], packed + f.last_b, 3, s);
 }
 
 void adain_encoded_size(int h, int w, int* hc, int* wc) {
@@ -158,53 +134,96 @@ void adain_encoded_size(int h, int w, int* hc, int* wc) {
     if (wc) *wc = w;
 }
 
-// Ping-pong activation buffers of the encoder: A takes conv1_1's output and then every second layer, B the
-// others; sizes are the maxima over the schedule (ceil-mode pooling makes odd sizes non-monotonic).
-static void enc_buf_sizes(int n, int h, int w, size_t* a_floats, size_t* b_floats) {
-    size_t mx[2] = {(size_t)n * h * w * 64, 0};
-    int cur = 0, ch = h, cw = w;
-    for (int i = 0; i < 7; ++i) {   // layer 7 writes the caller's feature buffer
-        const int oh = ENC[i].pool ? (ch + 1) / 2 : ch, ow = ENC[i].pool ? (cw + 1) / 2 : cw;
-        const size_t sz = (size_t)n * oh * ow * ENC[i].cout;
-        cur ^= 1;
-        if (sz > mx[cur]) mx[cur] = sz;
-        ch = oh; cw = ow;
-    }
-    *a_floats = align64(mx[0]);
-    *b_floats = align64(mx[1]);
-}
-static size_t enc_buf_a(int n, int h, int w) { size_t a, b; enc_buf_sizes(n, h, w, &a, &b); return a; }
-static size_t enc_buf_b(int n, int h, int w) { size_t a, b; enc_buf_sizes(n, h, w, &a, &b); return b; }
-// Third block of an encoder / decoder workspace: the partial-sum slabs of the layers that ADAIN_SCHEDULE_LATENCY would split along
-// cin (conv_wino4.hip: only launches with fewer tiles than compute units - single frames of the 256 class; at most 8 MB).  Always
-// part of the workspace, whatever the calling thread's schedule is when it asks for the size.
-static size_t enc_slab_floats(int n, int h, int w) {
-    size_t mx = 0;
-    int ch = h, cw = w;
+// ---- one network over one call: the plan every size, buffer and launch of its schedules is read from ----------------------------------
+// Per generic layer l: the source size (Hs, Ws), the conv size (H, W: twice the source for an up layer), the stored output size (Ho, Wo:
+// halved, ceil mode, where the layer pools), the output floats per image, and the ping-pong buffer the layer writes - the one its input
+// is not in.  The encoder's input is conv_first's 64-channel output in buffer A and its conv4_1 (layer 7) writes the caller's feature
+// tensor; the decoder's input is the caller's feature tensor.  The workspace is [A][B][slabs]: A and B hold the maxima over the layers
+// that write them (ceil-mode pooling makes odd sizes non-monotonic), the slabs take the partial sums of the layers that
+// ADAIN_SCHEDULE_LATENCY would split along cin (conv_wino4.hip: only launches with fewer tiles than compute units - single frames of the
+// 256 class; at most 8 MB).  The slabs are always part of the workspace, whatever the calling thread's schedule is when it asks for the size.
+constexpr int BUF_A = 0, BUF_B = 1, CALLER = -1;     // NetPlan::in_buf, NetPlan::buf: a ping-pong buffer or a tensor of the caller
+struct NetPlan {
+    const Layer* L;
+    int n;
+    int Hs[8], Ws[8], H[8], W[8], Ho[8], Wo[8];
+    size_t out_img[8];                                 // output floats per image
+    int buf[8];
+    int in_buf;                                        // where layer 0's input is
+    size_t buf_floats[2], slab_floats;                 // 64-float aligned
+    // the call's tensors (place()): the two buffers, the slab workspace, the caller's input / output tensor
+    float* bufs[2];
+    float* slab;
+    const float* in;
+    float* out;
+};
+static NetPlan net_plan(const Layer* L, int n, int h, int w) {
+    NetPlan p{};
+    p.L = L;
+    p.n = n;
+    p.in_buf = L == ENC ? BUF_A : CALLER;
+    size_t mx[2] = {0, 0}, slab = 0;
+    if (p.in_buf == BUF_A) mx[BUF_A] = (size_t)n * h * w * L[0].cin;
+    int in_buf = p.in_buf;
     for (int l = 0; l < 8; ++l) {
-        const size_t f = wino4_split_floats(n, ch, cw, ENC[l].cin, ENC[l].cout);
-        if (f > mx) mx = f;
-        if (ENC[l].pool) { ch = (ch + 1) / 2; cw = (cw + 1) / 2; }
+        p.Hs[l] = h; p.Ws[l] = w;
+        p.H[l] = L[l].up ? 2 * h : h; p.W[l] = L[l].up ? 2 * w : w;
+        p.Ho[l] = L[l].pool ? (p.H[l] + 1) / 2 : p.H[l]; p.Wo[l] = L[l].pool ? (p.W[l] + 1) / 2 : p.W[l];
+        p.out_img[l] = (size_t)p.Ho[l] * p.Wo[l] * L[l].cout;
+        p.buf[l] = (L == ENC && l == 7) ? CALLER : (in_buf == BUF_A ? BUF_B : BUF_A);
+        if (p.buf[l] >= 0 && (size_t)n * p.out_img[l] > mx[p.buf[l]]) mx[p.buf[l]] = (size_t)n * p.out_img[l];
+        const size_t f = wino4_split_floats(n, p.H[l], p.W[l], L[l].cin, L[l].cout);
+        if (f > slab) slab = f;
+        in_buf = p.buf[l];
+        h = p.Ho[l]; w = p.Wo[l];
     }
-    return align64(mx);
+    p.buf_floats[BUF_A] = align64(mx[BUF_A]);
+    p.buf_floats[BUF_B] = align64(mx[BUF_B]);
+    p.slab_floats = align64(slab);
+    return p;
 }
-static size_t dec_slab_floats(int n, int hc, int wc) {
-    size_t mx = 0;
-    int ch = hc, cw = wc;
-    for (int l = 0; l < 8; ++l) {
-        if (DEC[l].src == SRC_UP2X) { ch *= 2; cw *= 2; }
-        const size_t f = wino4_split_floats(n, ch, cw, DEC[l].cin, DEC[l].cout);
-        if (f > mx) mx = f;
+static size_t workspace_floats(const NetPlan& p) { return p.buf_floats[BUF_A] + p.buf_floats[BUF_B] + p.slab_floats; }
+// carves the plan's workspace from ws; in / out: the caller's tensors the network reads / writes in place of a buffer
+static void place(NetPlan& p, float* ws, const float* in, float* out) {
+    p.bufs[BUF_A] = ws;
+    p.bufs[BUF_B] = ws + p.buf_floats[BUF_A];
+    p.slab = p.bufs[BUF_B] + p.buf_floats[BUF_B];
+    p.in = in;
+    p.out = out;
+}
+static SplitWs split_ws(const NetPlan& p) {
+    return (g_schedule == ADAIN_SCHEDULE_LATENCY && p.slab_floats) ? SplitWs{p.slab, p.slab_floats} : SplitWs{nullptr, 0};
+}
+
+// floats per image of layer l's source
+static size_t src_img(const NetPlan& p, int l) { return (size_t)p.Hs[l] * p.Ws[l] * p.L[l].cin; }
+// layer l of a placed plan over images [i0, i0 + k): source and output at i0 x their per-image sizes
+static ConvArgs layer_args(const NetPlan& p, int l, int i0, int k, const float* packed, const Offsets& f) {
+    const Layer& L = p.L[l];
+    const int src = l ? p.buf[l - 1] : p.in_buf;
+    ConvArgs a{};
+    a.cin = L.cin; a.cout = L.cout; a.relu = 1; a.pool_out = L.pool;
+    a.bias = packed + f.b[l]; a.wpk = packed + f.w[l];
+    a.in = (src < 0 ? p.in : p.bufs[src]) + (size_t)i0 * src_img(p, l);
+    a.out = (p.buf[l] < 0 ? p.out : p.bufs[p.buf[l]]) + (size_t)i0 * p.out_img[l];
+    a.n = k; a.H = p.H[l]; a.W = p.W[l]; a.Hs = p.Hs[l]; a.Ws = p.Ws[l];
+    return a;
+}
+// layers [l0, l1) over images [i0, i0 + k); ev[l] (if given) is recorded after layer l.  Up layers run in their polyphase form, which
+// is never split along cin.
+static int run_layers(const NetPlan& p, int l0, int l1, int i0, int k, const float* packed, const Offsets& f, SplitWs split, void* const* ev,
+                      hipStream_t s) {
+    for (int l = l0; l < l1; ++l) {
+        const ConvArgs a = layer_args(p, l, i0, k, packed, f);
+        RET_IF(p.L[l].up ? launch_conv3x3_up2x_poly(a, s) : launch_conv3x3_wino4(a, SRC_DIRECT, s, split));
+        record(ev, l, s);
     }
-    return align64(mx);
-}
-static SplitWs split_ws(float* slab, size_t floats) {
-    return (g_schedule == ADAIN_SCHEDULE_LATENCY && floats) ? SplitWs{slab, floats} : SplitWs{nullptr, 0};
+    return 0;
 }
 
 size_t adain_encode_workspace_bytes(int n, int h, int w) {
     if (n < 1 || h < 1 || w < 1) return 0;
-    return (enc_buf_a(n, h, w) + enc_buf_b(n, h, w) + enc_slab_floats(n, h, w)) * sizeof(float);
+    return workspace_floats(net_plan(ENC, n, h, w)) * sizeof(float);
 }
 
 size_t adain_encode_multi_workspace_bytes(int count, const int* n, const int* h, const int* w) {
@@ -212,6 +231,11 @@ size_t adain_encode_multi_workspace_bytes(int count, const int* n, const int* h,
     size_t total = 0;
     for (int i = 0; i < count; ++i) total += adain_encode_workspace_bytes(n[i], h[i], w[i]);
     return total;
+}
+
+size_t adain_decode_workspace_bytes(int n, int hc, int wc) {
+    if (n < 1 || hc < 1 || wc < 1) return 0;
+    return workspace_floats(net_plan(DEC, n, hc, wc)) * sizeof(float);
 }
 
 // ---- batches of WIDE frames: which layers run frame by frame -----------------------------------------------------------------------
@@ -227,96 +251,40 @@ size_t adain_encode_multi_workspace_bytes(int count, const int* n, const int* h,
 // batch, as they always did.  Results do not depend on the split.
 constexpr double BIG_LAYER_ROUNDS = 6.0;
 constexpr int BIG_FRAME_WIDTH = 1600;
+static bool big_layer(const NetPlan& p, int l) { return wino4_rounds_per_image(p.H[l], p.W[l], p.L[l].cout) >= BIG_LAYER_ROUNDS; }
 
 // encoder: number of leading generic layers (0..7) run frame by frame = index after the LAST big layer.  conv4_1 (layer 7) is never
 // part of the prefix: it writes the caller's feature tensors, not the ping-pong buffers the frame-major pass works in, so it always
 // runs over the whole batch in the layer-major loop behind (a 1440 x 2560 frame's conv4_1 is 7.2 rounds and would count as big).
-static int enc_frame_major_layers(int n, int h, int w) {
-    if (n < 2 || w < BIG_FRAME_WIDTH) return 0;
-    int k = 0, ch = h, cw = w;
-    for (int l = 0; l < 7; ++l) {
-        if (wino4_rounds_per_image(ch, cw, ENC[l].cout) >= BIG_LAYER_ROUNDS) k = l + 1;
-        if (ENC[l].pool) { ch = (ch + 1) / 2; cw = (cw + 1) / 2; }
-    }
+static int enc_frame_major_layers(const NetPlan& p) {
+    if (p.n < 2 || p.Ws[0] < BIG_FRAME_WIDTH) return 0;
+    int k = 0;
+    for (int l = 0; l < 7; ++l)
+        if (big_layer(p, l)) k = l + 1;
     return k;
 }
 // decoder: number of leading layers (0..8) run over the whole batch = index of the FIRST big layer (8: none is big)
-static int dec_batched_layers(int n, int hc, int wc) {
-    if (n < 2 || 8 * wc < BIG_FRAME_WIDTH) return 8;
-    int ch = hc, cw = wc;
-    for (int l = 0; l < 8; ++l) {
-        if (DEC[l].src == SRC_UP2X) { ch *= 2; cw *= 2; }
-        if (wino4_rounds_per_image(ch, cw, DEC[l].cout) >= BIG_LAYER_ROUNDS) return l;
-    }
+static int dec_batched_layers(const NetPlan& p) {
+    if (p.n < 2 || p.W[7] < BIG_FRAME_WIDTH) return 8;           // W[7]: the width of the decoded frames
+    for (int l = 0; l < 8; ++l)
+        if (big_layer(p, l)) return l;
     return 8;
 }
 
-// The frame-major pass shares the layer-major schedule's two ping-pong buffers (image i's tensor of a layer sits at i x that layer's
-// per-image size, where the batched layers behind expect it), so an image processed later must never write over the LAST
-// frame-major tensor of an image processed earlier.  With VGG's sizes it never does (later tensors of the same buffer are
-// larger and start further out); this replays the offsets and says so for the case at hand - if not, the schedule stays layer-major.
-static bool enc_frame_major_is_safe(int n, int h, int w, int k) {
-    if (k < 1) return false;
-    size_t size[8];                    // per-image floats of layer l's output
-    int ch = h, cw = w;
-    for (int l = 0; l < k; ++l) {
-        if (ENC[l].pool) { ch = (ch + 1) / 2; cw = (cw + 1) / 2; }
-        size[l] = (size_t)ch * cw * ENC[l].cout;
-    }
-    const int last_buf = (k - 1) & 1 ? 0 : 1;          // layer l writes buffer B (1) for even l, A (0) for odd l
-    const size_t keep = size[k - 1];
-    // image j writes layer l's tensor at j * size[l]; the kept tensors of images 0 .. j-1 occupy [0, j * keep) of last_buf: safe iff
-    // every earlier tensor of that buffer is at least as large per image (j cancels)
-    if (n < 2) return true;
-    if (last_buf == 0 && (size_t)h * w * 64 < keep) return false;                 // conv_first -> buffer A
-    for (int l = 0; l + 1 < k; ++l)
-        if (((l & 1) ? 0 : 1) == last_buf && size[l] < keep) return false;
+// The frame-by-frame passes share the batched schedule's two ping-pong buffers (image i's tensor of a layer sits at i x that layer's
+// per-image size, where the batched layers expect it).  A pass runs layers [first, last) for one image after the other (first == -1:
+// conv_first's output, the encoder's input, too), and tensor `keep` of every image must survive the passes of the images behind it:
+// the encoder keeps the LAST frame-major tensor of the images processed earlier, the decoder - images processed LAST to FIRST - the
+// batched layers' output of the images still waiting.  When image j runs, those tensors occupy [0, j x keep's size) of keep's buffer
+// and image j writes tensor t at j x t's size: safe iff every tensor of the pass in that buffer is at least as large per image (j
+// cancels).  With VGG's sizes it always is (later tensors of the same buffer are larger and start further out); this replays the
+// offsets and says so for the case at hand - if not, every layer runs over the whole batch.
+static bool frame_pass_is_safe(const NetPlan& p, int first, int last, int keep) {
+    const size_t kept = p.out_img[keep];
+    if (first < 0 && p.in_buf == p.buf[keep] && src_img(p, 0) < kept) return false;
+    for (int l = first < 0 ? 0 : first; l < last; ++l)
+        if (p.buf[l] == p.buf[keep] && p.out_img[l] < kept) return false;
     return true;
-}
-// decoder, images processed LAST to FIRST: image j's writes into the buffer that holds the batched layers' output must stay behind
-// the tensors of the images still waiting, [0, j x that tensor's size)
-static bool dec_frame_major_is_safe(int n, int hc, int wc, int batched) {
-    if (batched < 1 || batched > 7) return true;       // 0: the input is the caller's feature tensor; 8: nothing runs frame by frame
-    size_t size[8];
-    int ch = hc, cw = wc;
-    for (int l = 0; l < 8; ++l) {
-        if (DEC[l].src == SRC_UP2X) { ch *= 2; cw *= 2; }
-        size[l] = (size_t)ch * cw * DEC[l].cout;
-    }
-    const int in_buf = (batched - 1) & 1;               // layer l writes buffer B (1) for odd l, A (0) for even l
-    for (int l = batched; l < 8; ++l)
-        if ((l & 1) == in_buf && size[l] < size[batched - 1]) return false;
-    (void)n;
-    return true;
-}
-
-// one batch of n images [n][h][w]: the frame-major part of the encoder (conv_first + the first k generic layers, image by image),
-// leaving layer k - 1's output for all images contiguous in *cur_out (dims *ch_out x *cw_out) exactly where the layer-major
-// schedule would have put it
-static int encode_frame_major(const void* images, int u8, int n, int h, int w, int k, const float* packed, const Offsets& f, float* bufA,
-                              float* bufB, const float** cur_out, int* ch_out, int* cw_out, hipStream_t s) {
-    const size_t img_stride = (size_t)h * w * 3 * (u8 ? 1 : 4);      // bytes per source image
-    int ch = h, cw = w;
-    const float* cur = bufA;
-    for (int i = 0; i < n; ++i) {
-        RET_IF(launch_conv_first((const char*)images + (size_t)i * img_stride, u8, bufA + (size_t)i * h * w * 64, packed, packed + f.first_b, 1, h, w, s));
-        cur = bufA;
-        ch = h; cw = w;
-        for (int l = 0; l < k; ++l) {
-            float* out = cur == bufA ? bufB : bufA;
-            const int oh = ENC[l].pool ? (ch + 1) / 2 : ch, ow = ENC[l].pool ? (cw + 1) / 2 : cw;
-            ConvArgs a{};
-            a.cin = ENC[l].cin; a.cout = ENC[l].cout; a.relu = 1; a.pool_out = ENC[l].pool;
-            a.bias = packed + f.b[l]; a.wpk = packed + f.w[l];
-            a.in = cur + (size_t)i * ch * cw * ENC[l].cin;
-            a.out = out + (size_t)i * oh * ow * ENC[l].cout;
-            a.n = 1; a.H = a.Hs = ch; a.W = a.Ws = cw;
-            RET_IF(launch_conv3x3_wino4(a, ENC[l].src, s));
-            cur = out; ch = oh; cw = ow;
-        }
-    }
-    *cur_out = cur; *ch_out = ch; *cw_out = cw;
-    return 0;
 }
 
 // images[i]: NCHW float, or (u8 != 0) HWC uint8 converted as ToTensor does inside the first layer's kernel
@@ -334,51 +302,42 @@ static int encode_impl(int count, const void* const* images, int u8, float* cons
     }
     if (ws_bytes < adain_encode_multi_workspace_bytes(count, n, h, w)) { set_error("encode: workspace too small"); return ADAIN_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    const Offsets f = enc_offsets();
-    float* bufA[MAX_CONV_SEGS];
-    float* bufB[MAX_CONV_SEGS];
+    const Offsets f = offsets(ENC);
+    NetPlan p[MAX_CONV_SEGS];
     SplitWs split[MAX_CONV_SEGS];
-    const float* cur[MAX_CONV_SEGS];
-    int ch[MAX_CONV_SEGS], cw[MAX_CONV_SEGS];
     float* base = (float*)workspace;
-    record(ev, 0, s);
-    // a batch of large frames (one tensor pair, no per-layer events wanted): its big layers frame by frame, see above
-    int frame_major = (count == 1 && !ev) ? enc_frame_major_layers(n[0], h[0], w[0]) : 0;
-    if (frame_major && !enc_frame_major_is_safe(n[0], h[0], w[0], frame_major)) frame_major = 0;
     for (int i = 0; i < count; ++i) {
-        bufA[i] = base;
-        bufB[i] = base + enc_buf_a(n[i], h[i], w[i]);
-        base = bufB[i] + enc_buf_b(n[i], h[i], w[i]);
-        split[i] = split_ws(base, enc_slab_floats(n[i], h[i], w[i]));
-        base += enc_slab_floats(n[i], h[i], w[i]);
-        if (frame_major) {
-            RET_IF(encode_frame_major(images[i], u8, n[i], h[i], w[i], frame_major, packed, f, bufA[i], bufB[i], &cur[i], &ch[i], &cw[i], s));
-            continue;
+        p[i] = net_plan(ENC, n[i], h[i], w[i]);
+        place(p[i], base, nullptr, feats[i]);
+        base += workspace_floats(p[i]);
+        split[i] = split_ws(p[i]);
+    }
+    record(ev, 0, s);
+    // a batch of large frames (one tensor pair, no per-layer events wanted): conv_first and its big layers frame by frame, see above,
+    // leaving every image's tensors where the layer-major loop behind expects them
+    int frame_major = (count == 1 && !ev) ? enc_frame_major_layers(p[0]) : 0;
+    if (frame_major && !frame_pass_is_safe(p[0], -1, frame_major, frame_major - 1)) frame_major = 0;
+    if (frame_major) {
+        const size_t img_bytes = (size_t)h[0] * w[0] * 3 * (u8 ? 1 : 4);
+        for (int j = 0; j < n[0]; ++j) {
+            RET_IF(launch_conv_first((const char*)images[0] + j * img_bytes, u8, p[0].bufs[BUF_A] + j * src_img(p[0], 0), packed, packed + f.first_b,
+                                     1, h[0], w[0], s));
+            RET_IF(run_layers(p[0], 0, frame_major, j, 1, packed, f, SplitWs{nullptr, 0}, nullptr, s));
         }
-        RET_IF(launch_conv_first(images[i], u8, bufA[i], packed, packed + f.first_b, n[i], h[i], w[i], s));
-        cur[i] = bufA[i];
-        ch[i] = h[i]; cw[i] = w[i];
+    } else {
+        for (int i = 0; i < count; ++i)
+            RET_IF(launch_conv_first(images[i], u8, p[i].bufs[BUF_A], packed, packed + f.first_b, n[i], h[i], w[i], s));
     }
     record(ev, 1, s);
     for (int l = frame_major; l < 8; ++l) {
-        ConvArgs a{};
-        a.cin = ENC[l].cin; a.cout = ENC[l].cout;
-        a.relu = 1;
-        a.pool_out = ENC[l].pool;
+        // one launch for every batch: the persistent kernel's tile list runs over all of them (csrc/conv_wino4.hip, SEGMENTS)
         ConvSeg segs[MAX_CONV_SEGS];
         for (int i = 0; i < count; ++i) {
-            float* out = (l == 7) ? feats[i] : (cur[i] == bufA[i] ? bufB[i] : bufA[i]);
-            segs[i] = ConvSeg{cur[i], out, n[i], ch[i], cw[i], ch[i], cw[i], 0, 0, 0};
+            const ConvArgs a = layer_args(p[i], l, 0, n[i], packed, f);
+            segs[i] = ConvSeg{a.in, a.out, a.n, a.H, a.W, a.Hs, a.Ws, 0, 0, 0};
         }
-        // one launch for every batch: the persistent kernel's tile list runs over all of them (csrc/conv_wino4.hip, SEGMENTS)
-        a.bias = packed + f.b[l];
-        a.wpk = packed + f.w[l];
-        RET_IF(launch_conv3x3_wino4_multi(a, segs, count, ENC[l].src, s, split));
+        RET_IF(launch_conv3x3_wino4_multi(layer_args(p[0], l, 0, n[0], packed, f), segs, count, SRC_DIRECT, s, split));
         record(ev, l + 2, s);
-        for (int i = 0; i < count; ++i) {
-            cur[i] = segs[i].out;
-            if (ENC[l].pool) { ch[i] = (ch[i] + 1) / 2; cw[i] = (cw[i] + 1) / 2; }
-        }
     }
     return 0;
 }
@@ -405,13 +364,8 @@ int adain_encode_u8(const uint8_t* image, float* feat, const float* packed, void
 int adain_encode_relu1_1(const void* image, int is_u8, float* relu1_1, const float* packed, int n, int h, int w, adain_stream_t stream) {
     if (!image || !relu1_1 || !packed) { set_error("encode_relu1_1: null pointer"); return ADAIN_EINVAL; }
     if (n < 1 || h < 2 || w < 2) { set_error("encode_relu1_1: image %dx%d too small (the reflection pad needs h, w >= 2)", h, w); return ADAIN_EINVAL; }
-    const Offsets f = enc_offsets();
+    const Offsets f = offsets(ENC);
     return launch_conv_first(image, is_u8 ? 1 : 0, relu1_1, packed, packed + f.first_b, n, h, w, (hipStream_t)stream);
-}
-
-size_t adain_decode_workspace_bytes(int n, int hc, int wc) {
-    if (n < 1 || hc < 1 || wc < 1) return 0;
-    return (align64((size_t)n * hc * wc * 1024) + align64((size_t)n * hc * wc * 4096) + dec_slab_floats(n, hc, wc)) * sizeof(float);
 }
 
 // image_u8 != nullptr: the last layer writes save_image's uint8 HWC frames itself (adain_stylize_u8 without a mask: the bytes of
@@ -422,56 +376,26 @@ static int decode_impl(const float* feat, float* image, uint8_t* image_u8, const
     if (n < 1 || hc < 2 || wc < 2) { set_error("decode: feature map %dx%d too small (needs >= 2x2)", hc, wc); return ADAIN_EINVAL; }
     if (ws_bytes < adain_decode_workspace_bytes(n, hc, wc)) { set_error("decode: workspace too small"); return ADAIN_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    const Offsets f = dec_offsets();
-    // buffer A (1024*hc*wc floats per image) takes the outputs of layers 0,2,4,6; buffer B (4096*hc*wc) of 1,3,5,7
-    float* bufA = (float*)workspace;
-    float* bufB = bufA + align64((size_t)n * hc * wc * 1024);
-    const SplitWs split = split_ws(bufB + align64((size_t)n * hc * wc * 4096), dec_slab_floats(n, hc, wc));
-    const float* cur = feat;
-    int ch = hc, cw = wc;
+    const Offsets f = offsets(DEC);
+    NetPlan p = net_plan(DEC, n, hc, wc);
+    place(p, (float*)workspace, feat, nullptr);
     record(ev, 0, s);
     // a batch of large frames: the leading small layers over the whole batch, then everything from the first big layer to the
-    // image frame by frame (see enc_frame_major_layers)
-    int batched = !ev ? dec_batched_layers(n, hc, wc) : 8;
-    if (!dec_frame_major_is_safe(n, hc, wc, batched)) batched = 8;
-    for (int i = 0; i < batched; ++i) {
-        ConvArgs a{};
-        a.in = cur;
-        a.out = (i & 1) ? bufB : bufA;
-        a.n = n;
-        a.Hs = ch; a.Ws = cw;
-        if (DEC[i].src == SRC_UP2X) { ch *= 2; cw *= 2; }
-        a.H = ch; a.W = cw;
-        a.cin = DEC[i].cin; a.cout = DEC[i].cout;
-        a.relu = 1;
-        RET_IF(launch_dec_layer(a, packed, f, i, s, split));
-        record(ev, i + 1, s);
-        cur = a.out;
-    }
+    // image frame by frame, images last to first (see enc_frame_major_layers, frame_pass_is_safe)
+    int batched = !ev ? dec_batched_layers(p) : 8;
+    if (batched > 0 && batched < 8 && !frame_pass_is_safe(p, batched, 8, batched - 1)) batched = 8;
+    RET_IF(run_layers(p, 0, batched, 0, n, packed, f, split_ws(p), ev ? ev + 1 : nullptr, s));
+    const float* last = p.bufs[p.buf[7]];
+    const int H = p.H[7], W = p.W[7];
     if (batched == 8) {
-        RET_IF(launch_conv_last(cur, image, packed + f.last_w, packed + f.last_b, n, ch, cw, s, image_u8));
+        RET_IF(launch_conv_last(last, image, packed + f.last_w, packed + f.last_b, n, H, W, s, image_u8));
         record(ev, 9, s);
         return 0;
     }
-    const int ch0 = ch, cw0 = cw;                                   // size of layer `batched`'s source, per image
-    for (int img = n - 1; img >= 0; --img) {                        // last to first: see dec_frame_major_is_safe
-        const float* c = cur;
-        ch = ch0; cw = cw0;
-        for (int i = batched; i < 8; ++i) {
-            ConvArgs a{};
-            a.cin = DEC[i].cin; a.cout = DEC[i].cout; a.relu = 1;
-            a.in = c + (size_t)img * ch * cw * DEC[i].cin;
-            a.n = 1;
-            a.Hs = ch; a.Ws = cw;
-            if (DEC[i].src == SRC_UP2X) { ch *= 2; cw *= 2; }
-            a.H = ch; a.W = cw;
-            float* out = (i & 1) ? bufB : bufA;
-            a.out = out + (size_t)img * ch * cw * DEC[i].cout;
-            RET_IF(launch_dec_layer(a, packed, f, i, s));
-            c = out;
-        }
-        RET_IF(launch_conv_last(c + (size_t)img * ch * cw * 64, image ? image + (size_t)img * 3 * ch * cw : nullptr, packed + f.last_w, packed + f.last_b,
-                                1, ch, cw, s, image_u8 ? image_u8 + (size_t)img * 3 * ch * cw : nullptr));
+    for (int img = n - 1; img >= 0; --img) {
+        RET_IF(run_layers(p, batched, 8, img, 1, packed, f, SplitWs{nullptr, 0}, nullptr, s));
+        RET_IF(launch_conv_last(last + (size_t)img * p.out_img[7], image ? image + (size_t)img * 3 * H * W : nullptr, packed + f.last_w,
+                                packed + f.last_b, 1, H, W, s, image_u8 ? image_u8 + (size_t)img * 3 * H * W : nullptr));
     }
     return 0;
 }

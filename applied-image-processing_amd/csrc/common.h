@@ -13,10 +13,11 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 // Source-gather modes of the 3x3 convolution's input (fused into the LDS staging):
-//   DIRECT : conceptual input == source tensor
-//   UP2X   : conceptual input == nearest 2x upsample of the source   (decoder, net.py:10,23,30)
-//   POOL2  : conceptual input == MaxPool2d(2,2,ceil_mode=True) of the source (encoder, net.py:46,53,66) - the schedules fuse the pool into
-//            the PRODUCER's epilogue instead (ConvArgs::pool_out); the consumer-side form went with the direct kernels (docs/HISTORY.md)
+//   DIRECT   : conceptual input == source tensor
+//   UP2X     : conceptual input == nearest 2x upsample of the source, gathered (adain_conv3x3_wino; net.py:10,23,30)
+//   POOL2    : conceptual input == MaxPool2d(2,2,ceil_mode=True) of the source (net.py:46,53,66).  No launcher takes it
+//              (check_wino4_shape refuses it): the encoder fuses its pools into the PRODUCER's epilogue (ConvArgs::pool_out).
+//              The value stays, as ADAIN_SRC_POOL2 does in the public header.
 //   UP2X_POLY: UP2X computed as four 2x2 phase convolutions of the source (conv_wino4.hip, W4P; the decoder's up layers)
 enum SrcMode { SRC_DIRECT = 0, SRC_UP2X = 1, SRC_POOL2 = 2, SRC_UP2X_POLY = 3 };
 
@@ -91,10 +92,11 @@ int launch_conv3x3_wino4_multi(const ConvArgs& layer, const ConvSeg* segs, int c
                                const SplitWs* split = nullptr);
 // floats of slab workspace a launch of this layer over n images of H x W (conv output size) needs to be split; 0: it would not be
 size_t wino4_split_floats(int n, int H, int W, int cin, int cout);
+// persistent-grid rounds one image of a layer is worth (the schedules of api.hip)
 double wino4_rounds_per_image(int H, int W, int cout);
 // the nearest-2x-upsample layer as four phase convolutions of the source (4 x 24 floats per (cin, cout) pair; see W4P)
 int launch_pack_up2x_poly(const float* w_oihw, float* packed, int cin, int cout, hipStream_t s);
-int launch_conv3x3_up2x_poly(const ConvArgs& a, hipStream_t s);      // persistent-grid rounds one image of a layer is worth (schedules, api.hip)
+int launch_conv3x3_up2x_poly(const ConvArgs& a, hipStream_t s);
 // img: NCHW float [n][3][H][W], or (u8 != 0) HWC uint8 [n][H][W][3] converted as ToTensor does (v / 255)
 int launch_conv_first(const void* img, int u8, float* out_nhwc, const float* packed, const float* bias, int n, int H,
                       int W, hipStream_t s);

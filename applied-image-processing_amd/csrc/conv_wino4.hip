@@ -911,23 +911,18 @@ double wino4_rounds_per_image(int H, int W, int cout) {
     return (double)geo_tiles(geo, 1, H, W) * (cout / 32) / (double)pgrid;
 }
 
-template <int MODE, bool PERSIST, bool BIG>
-static void w4_launch_geo(int geo, dim3 grid, hipStream_t s, const ConvArgs& a, const ConvSegs& m, int items) {
-    if constexpr (!BIG) {       // (per-tile descriptors - tensors of 2 GiB and more - exist for the default geometry only: see pick_geo's callers)
-        if (geo) { hipLaunchKernelGGL((conv3x3_wino4_kernel<MODE, PERSIST, BIG, 1>), grid, dim3(256), 0, s, a, m, items); return; }
-    }
-    hipLaunchKernelGGL((conv3x3_wino4_kernel<MODE, PERSIST, BIG, 0>), grid, dim3(256), 0, s, a, m, items);
+// The 12 instantiations the generic layers launch: source mode DIRECT or UP2X, persistent or one-tile, and geometry 0, 1 or (BIG: per-tile
+// descriptors for tensors of 2 GiB and more) 0 - the BIG build exists for the default geometry only (see w4_list).
+template <int MODE, bool PERSIST>
+static void w4_launch_mode(bool big, int geo, dim3 grid, hipStream_t s, const ConvArgs& a, const ConvSegs& m, int items) {
+    if (big) hipLaunchKernelGGL((conv3x3_wino4_kernel<MODE, PERSIST, true, 0>), grid, dim3(256), 0, s, a, m, items);
+    else if (geo) hipLaunchKernelGGL((conv3x3_wino4_kernel<MODE, PERSIST, false, 1>), grid, dim3(256), 0, s, a, m, items);
+    else hipLaunchKernelGGL((conv3x3_wino4_kernel<MODE, PERSIST, false, 0>), grid, dim3(256), 0, s, a, m, items);
 }
-static void w4_launch(int src_mode, bool persist, bool big, int geo, dim3 grid, hipStream_t s, const ConvArgs& a, const ConvSegs& m,
-                      int items) {
-    const bool up = src_mode == SRC_UP2X;
-    if (persist) {
-        if (big) up ? w4_launch_geo<SRC_UP2X, true, true>(geo, grid, s, a, m, items) : w4_launch_geo<SRC_DIRECT, true, true>(geo, grid, s, a, m, items);
-        else up ? w4_launch_geo<SRC_UP2X, true, false>(geo, grid, s, a, m, items) : w4_launch_geo<SRC_DIRECT, true, false>(geo, grid, s, a, m, items);
-    } else {
-        if (big) up ? w4_launch_geo<SRC_UP2X, false, true>(geo, grid, s, a, m, items) : w4_launch_geo<SRC_DIRECT, false, true>(geo, grid, s, a, m, items);
-        else up ? w4_launch_geo<SRC_UP2X, false, false>(geo, grid, s, a, m, items) : w4_launch_geo<SRC_DIRECT, false, false>(geo, grid, s, a, m, items);
-    }
+template <bool PERSIST>
+static void w4_launch(int src_mode, bool big, int geo, dim3 grid, hipStream_t s, const ConvArgs& a, const ConvSegs& m, int items) {
+    if (src_mode == SRC_UP2X) w4_launch_mode<SRC_UP2X, PERSIST>(big, geo, grid, s, a, m, items);
+    else w4_launch_mode<SRC_DIRECT, PERSIST>(big, geo, grid, s, a, m, items);
 }
 
 // Cin split of a small launch.  A one-tile workgroup walks its whole cin loop alone (about 1.5 us per 16 channels, 8 us of launch,
@@ -953,40 +948,74 @@ size_t wino4_split_floats(int n, int H, int W, int cin, int cout) {
     return S > 1 ? (size_t)S * n * H * W * cout : 0;
 }
 
+// The tile list of one launch of a layer over `count` segments: every segment's shape checked (ConvArgs `layer` with the segment's
+// sizes), one tile geometry for all of them - the one with fewer tiles over all segments, or the default when any tensor reaches
+// 2 GiB (the BIG build exists for that geometry only) - and each segment's tiles and first item.  `a` = `layer` with segment 0's
+// geometry; `items` = tiles x channel tiles over all segments.
+struct W4List {
+    ConvArgs a;
+    ConvSegs m;
+    bool big;
+    int geo;
+    long long items;
+};
+static void set_seg(ConvArgs& a, const ConvSeg& g) {
+    a.in = g.in; a.out = g.out; a.n = g.n; a.H = g.H; a.W = g.W; a.Hs = g.Hs; a.Ws = g.Ws;
+}
+static int w4_list(const ConvArgs& layer, const ConvSeg* segs, int count, int src_mode, W4List& t) {
+    t.a = layer;
+    t.m = ConvSegs{};
+    t.m.count = count;
+    t.m.ctg = walk_group(layer.cin, layer.cout);
+    t.big = false;
+    for (int i = 0; i < count; ++i) {
+        set_seg(t.a, segs[i]);
+        if (check_wino4_shape(t.a, src_mode)) return -1;
+        t.big = t.big || wino4_big(t.a);
+    }
+    t.geo = t.big ? 0 : pick_geo(segs, count);
+    t.items = 0;
+    for (int i = 0; i < count; ++i) {
+        ConvSeg& g = t.m.s[i];
+        g = segs[i];
+        g.tiles_x = (g.W + tile_w(t.geo) - 1) / tile_w(t.geo);
+        g.tiles_y = (g.H + tile_h(t.geo) - 1) / tile_h(t.geo);
+        g.item0 = (int)t.items;
+        t.items += (long long)g.tiles_x * g.tiles_y * (layer.cout / 32) * g.n;
+    }
+    set_seg(t.a, t.m.s[0]);
+    t.a.tiles_x = t.m.s[0].tiles_x;
+    t.a.tiles_y = t.m.s[0].tiles_y;
+    return 0;
+}
+
 int launch_conv3x3_wino4(const ConvArgs& a0, int src_mode, hipStream_t s, SplitWs split) {
-    ConvArgs a = a0;
-    a.ksplit = 1; a.cin_sub = a.cin; a.slab_stride = 0;
-    if (check_wino4_shape(a, src_mode)) return -1;
-    ConvSegs m{};
-    m.count = 1;
-    m.s[0] = ConvSeg{a.in, a.out, a.n, a.H, a.W, a.Hs, a.Ws, 0, 0, 0};
-    const bool big = wino4_big(a);
-    const int geo = big ? 0 : pick_geo(m.s, 1);      // the >= 2 GiB build exists for the default geometry
-    a.tiles_x = (a.W + tile_w(geo) - 1) / tile_w(geo);
-    a.tiles_y = (a.H + tile_h(geo) - 1) / tile_h(geo);
-    m.s[0].tiles_x = a.tiles_x; m.s[0].tiles_y = a.tiles_y;
-    const long long blocks = (long long)a.tiles_x * a.tiles_y * (a.cout / 32) * a.n;
+    ConvArgs layer = a0;
+    layer.ksplit = 1; layer.cin_sub = layer.cin; layer.slab_stride = 0;
+    const ConvSeg seg{layer.in, layer.out, layer.n, layer.H, layer.W, layer.Hs, layer.Ws, 0, 0, 0};
+    W4List t;
+    if (w4_list(layer, &seg, 1, src_mode, t)) return -1;
+    const ConvArgs& a = t.a;
+    const long long blocks = t.items;
     if (blocks <= 0 || blocks > 0x7fffffffLL) { set_error("conv3x3_wino4: bad grid %lld", blocks); return -1; }
-    const dim3 g((unsigned)blocks);
     // persistent form whenever the launch has at least two tiles per resident workgroup (and cin is at most 2^20): +2-3 % on most
     // layer shapes, +1.1 % on the config-2 step
     const long long pgrid = persistent_grid();
     if (pgrid <= 0) { set_error("conv3x3_wino4: device query failed"); return -1; }
     const bool persist = a.cin <= (1 << 20) && a.cin >= 2 * W4_KR && pgrid >= 8 && blocks >= 2 * pgrid;
     const int items = (int)blocks;
-    m.ctg = walk_group(a.cin, a.cout);
     if (persist) {
-        w4_launch(src_mode, true, big, geo, dim3((unsigned)pgrid), s, a, m, items);
+        w4_launch<true>(src_mode, t.big, t.geo, dim3((unsigned)pgrid), s, a, t.m, items);
         return check_launch("conv3x3_wino4");
     }
-    const int S = (split.slab && !big) ? wino4_ksplit(blocks, a.cin) : 1;
+    const int S = (split.slab && !t.big) ? wino4_ksplit(blocks, a.cin) : 1;
     if (S > 1) {
         const size_t slab = (size_t)a.n * a.H * a.W * a.cout;
         if (split.floats < (size_t)S * slab) { set_error("conv3x3_wino4: split workspace too small (%zu < %zu floats)", split.floats, (size_t)S * slab); return -1; }
         ConvArgs p = a;                  // first half: S workgroups per (tile, channel tile), partial sums into the slabs
         p.ksplit = S; p.cin_sub = a.cin / S; p.slab_stride = slab;
         p.out = split.slab; p.relu = 0; p.pool_out = 0;
-        w4_launch(src_mode, false, false, geo, dim3((unsigned)(blocks * S)), s, p, m, items * S);
+        w4_launch<false>(src_mode, false, t.geo, dim3((unsigned)(blocks * S)), s, p, t.m, items * S);
         if (int r = check_launch("conv3x3_wino4(split)")) return r;
         const int Ho = a.pool_out ? (a.H + 1) / 2 : a.H, Wo = a.pool_out ? (a.W + 1) / 2 : a.W;
         const size_t total = (size_t)a.n * Ho * Wo * (a.cout / 4);
@@ -995,51 +1024,30 @@ int launch_conv3x3_wino4(const ConvArgs& a0, int src_mode, hipStream_t s, SplitW
                            a.n, a.H, a.W, a.cout);
         return check_launch("conv3x3_wino4(combine)");
     }
-    w4_launch(src_mode, false, big, geo, g, s, a, m, items);
+    w4_launch<false>(src_mode, t.big, t.geo, dim3((unsigned)blocks), s, a, t.m, items);
     return check_launch("conv3x3_wino4");
 }
 
 int launch_conv3x3_wino4_multi(const ConvArgs& layer, const ConvSeg* segs, int count, int src_mode, hipStream_t s, const SplitWs* split) {
     if (count < 1 || count > MAX_CONV_SEGS) { set_error("conv3x3_wino4_multi: 1..%d segments, got %d", MAX_CONV_SEGS, count); return -1; }
-    ConvSegs m{};
-    m.count = count;
-    m.ctg = walk_group(layer.cin, layer.cout);
-    long long total = 0;
-    bool big = false;
-    ConvArgs a = layer;
-    for (int i = 0; i < count; ++i) {
-        a.n = segs[i].n; a.H = segs[i].H; a.W = segs[i].W; a.Hs = segs[i].Hs; a.Ws = segs[i].Ws;
-        big = big || wino4_big(a);
-    }
-    const int geo = big ? 0 : pick_geo(segs, count);             // one geometry per launch: the one with fewer tiles over all segments
-    for (int i = 0; i < count; ++i) {
-        a.in = segs[i].in; a.out = segs[i].out; a.n = segs[i].n;
-        a.H = segs[i].H; a.W = segs[i].W; a.Hs = segs[i].Hs; a.Ws = segs[i].Ws;
-        if (!a.in || !a.out) { set_error("conv3x3_wino4_multi: null pointer in segment %d", i); return -1; }
-        if (check_wino4_shape(a, src_mode)) return -1;
-        big = big || wino4_big(a);
-        m.s[i] = segs[i];
-        m.s[i].tiles_x = (a.W + tile_w(geo) - 1) / tile_w(geo);
-        m.s[i].tiles_y = (a.H + tile_h(geo) - 1) / tile_h(geo);
-        m.s[i].item0 = (int)total;
-        total += (long long)m.s[i].tiles_x * m.s[i].tiles_y * (a.cout / 32) * a.n;
-        if (total > 0x7fffffffLL) { set_error("conv3x3_wino4_multi: too many tiles"); return -1; }
-    }
+    for (int i = 0; i < count; ++i)
+        if (!segs[i].in || !segs[i].out) { set_error("conv3x3_wino4_multi: null pointer in segment %d", i); return -1; }
+    W4List t;
+    if (w4_list(layer, segs, count, src_mode, t)) return -1;
+    if (t.items > 0x7fffffffLL) { set_error("conv3x3_wino4_multi: too many tiles"); return -1; }
     const long long pgrid = persistent_grid();
     if (pgrid <= 0) { set_error("conv3x3_wino4: device query failed"); return -1; }
-    if (count == 1 || a.cin < 2 * W4_KR || pgrid < 8 || total < 2 * pgrid) {
+    if (count == 1 || layer.cin < 2 * W4_KR || pgrid < 8 || t.items < 2 * pgrid) {
         // not enough work for a shared persistent list (or a single segment): one launch per segment
+        ConvArgs a = layer;
         for (int i = 0; i < count; ++i) {
-            a.in = segs[i].in; a.out = segs[i].out; a.n = segs[i].n;
-            a.H = segs[i].H; a.W = segs[i].W; a.Hs = segs[i].Hs; a.Ws = segs[i].Ws;
+            set_seg(a, segs[i]);
             if (int r = launch_conv3x3_wino4(a, src_mode, s, split ? split[i] : SplitWs{nullptr, 0})) return r;
         }
         return 0;
     }
     // the kernel reads its geometry from the segments; the ConvArgs copy carries the layer (weights, bias, cin, cout, flags)
-    a.in = m.s[0].in; a.out = m.s[0].out; a.n = m.s[0].n; a.H = m.s[0].H; a.W = m.s[0].W; a.Hs = m.s[0].Hs; a.Ws = m.s[0].Ws;
-    a.tiles_x = m.s[0].tiles_x; a.tiles_y = m.s[0].tiles_y;
-    w4_launch(src_mode, true, big, geo, dim3((unsigned)pgrid), s, a, m, (int)total);
+    w4_launch<true>(src_mode, t.big, t.geo, dim3((unsigned)pgrid), s, t.a, t.m, (int)t.items);
     return check_launch("conv3x3_wino4(multi)");
 }
 

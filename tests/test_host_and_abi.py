@@ -80,6 +80,58 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert lib.adain_encode_workspace_bytes(1, 1024, 1024) == (64 + 16) * 1024 * 1024 * 4   # A: conv1_1 out, B: pooled conv1_2 out
 
 
+def _conv_workspace_bytes(lib, net, n, h, w):
+    """An encoder (image h x w) or decoder (feature map h x w) workspace restated from the layer plans, as (ping-pong bytes, slab
+    bytes): the two ping-pong buffers - each generic layer writes the one its input is not in; the encoder's input is conv_first's
+    64-channel output in A and its last layer writes the caller's features, the decoder's input is the caller's features - at their
+    largest over the layers, then the cin-split slabs of the largest layer.  Every block 64-float aligned."""
+    def a64(nbytes):
+        return (nbytes // 4 + 63) // 64 * 64 * 4
+
+    enc = net == "encoder"
+    layers = arch.encoder_plan()[2:] if enc else arch.decoder_plan()[:-1]      # the 8 generic 3x3 layers
+    assert len(layers) == 8
+    peak, buf, slab = [n * h * w * 64 * 4 if enc else 0, 0], 0 if enc else None, 0
+    for i, L in enumerate(layers):
+        if L["src"] == "up":
+            h, w = 2 * h, 2 * w
+        slab = max(slab, lib.adain_conv3x3_wino4_split_workspace_bytes(n, h, w, L["cin"], L["cout"]))
+        if i + 1 < 8 and layers[i + 1]["src"] == "pool":       # the pool in front of the next layer: fused into this layer's output
+            h, w = (h + 1) // 2, (w + 1) // 2
+        if enc and i == 7:
+            break
+        buf = 1 if buf == 0 else 0
+        peak[buf] = max(peak[buf], n * h * w * L["cout"] * 4)
+    return a64(peak[0]) + a64(peak[1]), a64(slab)
+
+
+@pytest.mark.parametrize("device", [False, pytest.param(True, marks=pytest.mark.gpu)])
+def test_conv_workspaces_follow_the_layer_plans(device):
+    """adain_encode_workspace_bytes, adain_decode_workspace_bytes and adain_encode_multi_workspace_bytes against the layout restated
+    from arch's layer plans, over batches, odd and even sides and wide frames.  The slab term needs a device (0 without one)."""
+    lib = _lib_built()
+    if device:
+        torch.zeros(1, device="cuda")
+    sides = [9, 10, 15, 16, 31, 45, 64, 67, 100, 256, 263, 513]
+    shapes = [(h, w) for h in sides for w in sides] + [(1080, 1920), (264, 1720), (2160, 3840), (1200, 1600), (720, 1280)]
+    with_slab = 0
+    for n in range(1, 5):
+        for h, w in shapes:
+            bufs, slab = _conv_workspace_bytes(lib, "encoder", n, h, w)
+            assert lib.adain_encode_workspace_bytes(n, h, w) == bufs + slab, (n, h, w)
+            with_slab += slab > 0
+            hc, wc = arch.encoded_size(h, w)
+            bufs, slab = _conv_workspace_bytes(lib, "decoder", n, hc, wc)
+            assert lib.adain_decode_workspace_bytes(n, hc, wc) == bufs + slab, (n, hc, wc)
+            with_slab += slab > 0
+    batches = [(1, 256, 256), (2, 1080, 1920), (3, 33, 47), (4, 264, 1720)]
+    for k in range(1, 5):
+        ns, hs, ws = ((ctypes.c_int * k)(*[b[j] for b in batches[:k]]) for j in range(3))
+        assert lib.adain_encode_multi_workspace_bytes(k, ns, hs, ws) == sum(sum(_conv_workspace_bytes(lib, "encoder", *b)) for b in batches[:k])
+    if device:
+        assert with_slab, "no shape of the grid has a cin-split slab on this device"
+
+
 def test_product_library_reads_no_environment(monkeypatch):
     """ADAIN_HIP_LIB (round 2's switch) no longer redirects the product runtime; the retired kernel families say so.  The product
     library reads no environment at all (no getenv import) and exports no debug entry point."""
