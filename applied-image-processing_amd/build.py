@@ -12,15 +12,16 @@ CSRC = os.path.join(PKG, "csrc")
 INC = os.path.join(os.path.dirname(PKG), "include")
 LIB = os.path.join(PKG, "libadain_hip.so")
 # The direct implicit-GEMM and F(2x2,3x3) families of rounds 1-2 were retired in round 6 (git history).
-SOURCES = ["conv_edge.hip", "conv_wino4.hip", "stats.hip", "pixel.hip", "resample.hip", "flow.hip", "tvl1.hip", "api.hip"]
+SOURCES = ["conv_edge.hip", "conv_wino4.hip", "stats.hip", "pixel.hip", "resample.hip", "flow.hip", "tvl1.hip", "colour.hip", "api.hip"]
 # -fvisibility=hidden: the shared library exports the C ABI of include/adain_hip.h (ADAIN_API) and nothing else
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # The MFMA kernels carry their fp32 vector-ALU work (input transform, epilogues) next to the matrix instructions, where
 # v_pk_add_f32 / v_pk_fma_f32 issue far slower than the plain forms (MI355X_MICROARCH.md, "price of one filler beside
 # MFMAs"): keep hipcc from packing f32 pairs in those files.  Measured on the Winograd kernel: +7 %.
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-# tvl1.hip keeps OpenCV's float operations one by one (no FMA contraction), as its NumPy restatement does
-EXTRA_FLAGS = {"conv_wino4.hip": NO_PACKED_F32, "tvl1.hip": ["-ffp-contract=off"]}
+# tvl1.hip keeps OpenCV's float operations one by one (no FMA contraction), as its NumPy restatement does; colour.hip keeps numpy's
+# float64 operations apart the same way, so that equal colours run one instruction sequence and project to equal keys
+EXTRA_FLAGS = {"conv_wino4.hip": NO_PACKED_F32, "tvl1.hip": ["-ffp-contract=off"], "colour.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

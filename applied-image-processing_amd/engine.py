@@ -136,6 +136,16 @@ class AdaINEngine:
         """One step of the video recurrence: blend(cur, warp(prev, flow), alpha) on uint8 HWC frames (video/utils.py:89-105, :223-229)."""
         return rt.warp_blend_u8(cur, prev, flow, alpha)
 
+    def colour_transfer_u8(self, fg, bg, out=None):
+        """The localized pipeline's foreground colour transfer (localized_style_transfer.py:128-168) on uint8 HWC images -> (adjusted
+        foreground, device record); see ``runtime.colour_transfer_u8``."""
+        return rt.colour_transfer_u8(fg, bg, out)
+
+    def localized_combine_u8(self, content, stylised, mask, out=None):
+        """The localized pipeline's composite with the colour transfer inside (:232-238): content, stylised uint8 [h,w,3], {0,1} background
+        mask uint8 [h,w] -> (final uint8 image, device record)."""
+        return rt.localized_combine_u8(content, stylised, mask, out)
+
     def temporal_blend(self, frames_u8, flows, alpha=0.7):
         return temporal_blend(frames_u8, flows, alpha)
 

@@ -5,7 +5,9 @@ stylised background in Reinhard's l-alpha-beta space along each region's first p
 composited (:232-243).
 
 The AdaIN call runs on the MI355X kernels; everything after it is the reference's host-side numpy arithmetic on two uint8
-images, restated here with the same names, argument meaning and return types.  Two dependencies of the reference are not
+images, restated here with the same names, argument meaning and return types.  That host form is the default.  The same arithmetic
+runs on the device (csrc/colour.hip, float64 throughout) through ``color_transfer_foreground_device`` / ``combine_localized_device``
+and ``run_localized_style_transfer(colour_on_device=True)``.  Two dependencies of the reference are not
 needed: scikit-learn's ``PCA(n_components=1)`` is restated in numpy (covariance eigen-decomposition with scikit-learn >= 1.5's
 deterministic sign convention) and the DeepLabV3 background segmentation (:171-188, a network download) is a pluggable
 provider (``set_mask_provider``) or a precomputed ``background_mask``.
@@ -151,11 +153,104 @@ def combine_localized(content_np, stylized_np, background_mask):
     return (adjusted * fg_mask[..., None] + background).astype(np.uint8)
 
 
+# ---- the same arithmetic on the device (csrc/colour.hip through runtime.colour_transfer_u8 / localized_combine_u8) --------------------
+def _u8_image(x, name, shape=None):
+    """Refuses, before any device is touched, what the kernels could not take: anything but a uint8 [H,W,3] numpy array or torch
+    tensor (of ``shape`` when given)."""
+    ok = (hasattr(x, "shape") and hasattr(x, "dtype") and len(x.shape) == 3 and x.shape[2] == 3 and str(x.dtype).endswith("uint8")
+          and (shape is None or tuple(x.shape) == tuple(shape)))
+    if not ok:
+        want = f"[{','.join(map(str, shape))}]" if shape is not None else "[H,W,3]"
+        raise ValueError(f"{name} must be a uint8 {want} numpy array or torch tensor, got "
+                         f"{getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
+
+
+def _to_device(x, device):
+    import torch
+
+    if isinstance(x, torch.Tensor):
+        return x.to(device).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(x)).to(device)
+
+
+def _device_of(device, *arrays):
+    import torch
+
+    if device is not None:
+        return torch.device(device)
+    for a in arrays:
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            return a.device
+    if not torch.cuda.is_available():
+        from .runtime import AdainHipError
+
+        raise AdainHipError("the device colour transfer needs a GPU (the host form is color_transfer_foreground / combine_localized)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _finish(out, record, like, return_record):
+    """Reads the device record (one fixed-size copy), prints the reference's warnings (:141-147), refuses a one-pixel region and
+    hands the result back as ``like``'s type."""
+    import torch
+
+    from . import runtime as rt
+
+    rec = rt.colour_record(record)
+    if rec["status"] & rt.COLOUR_FG_EMPTY:
+        print("Warning: No foreground pixels found.")
+    elif rec["status"] & rt.COLOUR_BG_EMPTY:
+        print("Warning: No background pixels found for color transfer.")
+    elif rec["status"]:
+        which = "foreground" if rec["status"] & rt.COLOUR_FG_SINGLE else "background"
+        raise ValueError(f"the {which} region has one pixel: PCA needs at least two (the reference divides by zero here)")
+    if not isinstance(like, torch.Tensor):
+        out = out.cpu().numpy()
+    elif not like.is_cuda:
+        out = out.cpu()
+    return (out, rec) if return_record else out
+
+
+def color_transfer_foreground_device(foreground_img, background_img, device=None, return_record=False):
+    """``color_transfer_foreground`` on the device: uint8 [H,W,3] numpy arrays or torch tensors in, the same type out (a torch CUDA
+    tensor stays on its device).  Same warnings for empty regions; ValueError for a one-pixel region.  ``return_record``: also the
+    fitted PCAs as ``runtime.colour_record`` gives them (``fg`` / ``bg``: ``n``, ``mean``, ``component``)."""
+    _u8_image(foreground_img, "foreground_img")
+    _u8_image(background_img, "background_img", foreground_img.shape)
+    from . import runtime as rt
+
+    dev = _device_of(device, foreground_img, background_img)
+    out, record = rt.colour_transfer_u8(_to_device(foreground_img, dev), _to_device(background_img, dev))
+    return _finish(out, record, foreground_img, return_record)
+
+
+def combine_localized_device(content_np, stylized_np, background_mask, device=None, return_record=False):
+    """``combine_localized`` on the device, the masked images never materialised: content uint8 [H,W,3], stylised uint8 (nearest-resized
+    to the mask on the host when sizes differ, :223-230), ``background_mask`` [H,W] holding 0 and 1 only."""
+    import torch
+
+    m = background_mask
+    host_mask = m.cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
+    if host_mask.ndim != 2 or host_mask.dtype.kind not in "bui" or ((host_mask != 0) & (host_mask != 1)).any():
+        raise ValueError(f"background_mask must be an integer [H,W] array of 0 and 1, got {host_mask.dtype} {host_mask.shape}")
+    _u8_image(content_np, "content_np", host_mask.shape + (3,))
+    _u8_image(stylized_np, "stylized_np")
+    if tuple(stylized_np.shape[:2]) != host_mask.shape:
+        sty = stylized_np.cpu().numpy() if isinstance(stylized_np, torch.Tensor) else stylized_np
+        stylized_np = np.array(Image.fromarray(sty).resize((host_mask.shape[1], host_mask.shape[0]), Image.NEAREST))
+    from . import runtime as rt
+
+    dev = _device_of(device, content_np, stylized_np)
+    mask = m.to(dev, torch.uint8) if isinstance(m, torch.Tensor) else _to_device(host_mask.astype(np.uint8), dev)
+    out, record = rt.localized_combine_u8(_to_device(content_np, dev), _to_device(stylized_np, dev), mask.contiguous())
+    return _finish(out, record, content_np, return_record)
+
+
 def run_localized_style_transfer(content_img_path, style_img_path, output_path="../output", file_name="test", use_depth=False,
-                                 depth_offset=0.5, depth_prominence=20, background_mask=None, **adain_kwargs):
+                                 depth_offset=0.5, depth_prominence=20, background_mask=None, *, colour_on_device=False, **adain_kwargs):
     """Same parameters and return value (the saved file's path, a str) as the reference (:191-245) plus ``background_mask``
     ([1,H,W] uint8) to bypass the mask provider; extra keyword arguments go to ``adain_inference`` (checkpoint paths,
-    ``depth_map=`` ...)."""
+    ``depth_map=`` ...).  ``colour_on_device`` (keyword only, default off): the colour transfer and the composite run on the device
+    (``combine_localized_device``) instead of in numpy; file names, the JPEG save and the return value do not change."""
     from .AdaIN.test import adain_inference
 
     content_img = Image.open(content_img_path).convert("RGB")
@@ -167,7 +262,7 @@ def run_localized_style_transfer(content_img_path, style_img_path, output_path="
                                     output=output_path, file_name=file_name, use_depth=use_depth, depth_offset=depth_offset,
                                     depth_prominence=depth_prominence, alpha=1, **adain_kwargs)
     stylized_np = np.array(Image.open(stylized_path).convert("RGB"))
-    combined = combine_localized(content_np, stylized_np, background_mask[0])
+    combined = (combine_localized_device if colour_on_device else combine_localized)(content_np, stylized_np, background_mask[0])
     Path(output_path).mkdir(exist_ok=True, parents=True)
     save_path = f"{output_path}/localized_style_transfer_result.jpg"
     Image.fromarray(combined).save(save_path)

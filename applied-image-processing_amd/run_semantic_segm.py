@@ -7,7 +7,7 @@ It calls ``localized.run_localized_style_transfer`` (reference Style_3DGS/locali
 ``adain_inference(content_mask=..., alpha=1)`` on the MI355X kernels -> Reinhard / PCA / CDF colour transfer of the foreground ->
 composite.  Extra flags make it usable offline (the reference downloads DeepLabV3 and MiDaS at run time): ``--mask_npy`` takes a
 precomputed background mask ([1,H,W] or [H,W], 1 = background), ``--depth_npy`` a proximity map, ``--vgg`` / ``--decoder`` the
-checkpoint paths.  Without ``--mask_npy`` a provider must have been registered (``localized.set_mask_provider``).
+checkpoint paths, ``--colour_on_device`` moves the colour transfer and the composite to the GPU.  Without ``--mask_npy`` a provider must have been registered (``localized.set_mask_provider``).
 """
 import argparse
 
@@ -29,6 +29,7 @@ _EXTRA_FLAGS = (
     ("--depth_npy", dict(type=str, default=None, help=".npy proximity map [H0,W0]; replaces the MiDaS estimate")),
     ("--vgg", dict(type=str, default="Style_3DGS/AdaIN/models/vgg_normalised.pth", help="encoder state_dict")),
     ("--decoder", dict(type=str, default="Style_3DGS/AdaIN/models/decoder.pth", help="decoder state_dict")),
+    ("--colour_on_device", dict(action="store_true", help="run the foreground colour transfer and the composite on the GPU instead of in numpy")),
 )
 
 
@@ -45,7 +46,7 @@ def main(argv=None):
     if ns.depth_npy:
         extra["depth_map"] = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
     return run_localized_style_transfer(content_img_path=ns.content, style_img_path=ns.style, output_path=ns.output, file_name=ns.file_name,
-                                        use_depth=ns.use_depth, background_mask=mask, **extra)
+                                        use_depth=ns.use_depth, background_mask=mask, colour_on_device=ns.colour_on_device, **extra)
 
 
 if __name__ == "__main__":

@@ -73,6 +73,9 @@ SIGNATURES = {
     "adain_tvl1_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_void_p]),
     "adain_tvl1_flow": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t,
                                  _c_void_p]),
+    "adain_colour_transfer_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
+    "adain_colour_transfer_u8": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "adain_localized_combine_u8": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p]),
     "adain_resize_pil_bilinear_u8_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "adain_resize_pil_bilinear_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p]),
     "adain_stylize_u8_workspace_bytes": (_c_size_t, [_c_int] * 9),
@@ -552,6 +555,67 @@ def warp_blend_u8(cur, prev, flow, alpha, out=None):
         _check(lib().adain_warp_blend_u8(cur.data_ptr(), prev.data_ptr(), flow.data_ptr(), out.data_ptr(), h, w, c, float(alpha),
                                          float(1 - alpha), _stream()), "adain_warp_blend_u8")
     return out
+
+
+# --- the localized pipeline's colour transfer (adain_colour_transfer_u8 / adain_localized_combine_u8) ---------------------------
+COLOUR_FG_EMPTY, COLOUR_BG_EMPTY, COLOUR_FG_SINGLE, COLOUR_BG_SINGLE = 1, 2, 4, 8      # ADAIN_COLOUR_*: adain_colour_record.status
+
+
+class _ColourRegion(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int64), ("mean", ctypes.c_double * 3), ("component", ctypes.c_double * 3), ("explained_variance", ctypes.c_double)]
+
+
+class _ColourRecord(ctypes.Structure):        # adain_colour_record of include/adain_hip.h
+    _fields_ = [("fg", _ColourRegion), ("bg", _ColourRegion), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+COLOUR_RECORD_BYTES = ctypes.sizeof(_ColourRecord)
+
+
+def colour_record(record):
+    """The device record a colour call returned (uint8 [COLOUR_RECORD_BYTES]) as a dict: ``status`` and per region (``fg``, ``bg``)
+    ``n``, ``mean``, ``component``, ``explained_variance``.  One fixed-size copy to the host, which waits for the call's stream."""
+    raw = _ColourRecord.from_buffer_copy(record.cpu().numpy().tobytes())
+    region = lambda r: dict(n=int(r.n), mean=list(r.mean), component=list(r.component), explained_variance=float(r.explained_variance))
+    return dict(status=int(raw.status), fg=region(raw.fg), bg=region(raw.bg))
+
+
+def _colour_call(name, fn, images, out):
+    h, w, c = images[0].shape
+    dev = images[0].device
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+    else:
+        _check_buffer(out, f"{name}: out", torch.uint8, dev, shape=(h, w, 3), distinct=images)
+    with torch.cuda.device(dev):
+        nbytes = lib().adain_colour_transfer_workspace_bytes(h, w)
+        if nbytes == 0:
+            raise AdainHipError(f"{name}: unsupported size {h} x {w}")
+        ws = workspace(dev, "colour", nbytes)
+        _check(fn(*[t.data_ptr() for t in images], out.data_ptr(), h, w, ws.data_ptr(), _stream()), f"adain_{name}")
+        record = ws[:COLOUR_RECORD_BYTES].clone()        # the workspace is the stream's: the next call overwrites it
+    return out, record
+
+
+def colour_transfer_u8(fg, bg, out=None):
+    """color_transfer_foreground (Style_3DGS/localized_style_transfer.py:128-168) on the device: fg, bg uint8 [h,w,3] -> (adjusted
+    foreground uint8 [h,w,3], device record for ``colour_record``).  Nothing is copied to the host: an empty or one-pixel region leaves
+    a copy of ``fg`` and a non-zero status in the record."""
+    fg, bg = _dev(fg, "fg", torch.uint8), _dev(bg, "bg", torch.uint8)
+    if fg.dim() != 3 or fg.shape[2] != 3 or bg.shape != fg.shape or bg.device != fg.device:
+        raise AdainHipError(f"colour_transfer_u8: expected two uint8 [h,w,3] images of one size on one device, got {tuple(fg.shape)} and {tuple(bg.shape)}")
+    return _colour_call("colour_transfer_u8", lib().adain_colour_transfer_u8, (fg, bg), out)
+
+
+def localized_combine_u8(content, stylised, mask, out=None):
+    """The composite of run_localized_style_transfer (:232-238) with the colour transfer inside: content, stylised uint8 [h,w,3], mask
+    uint8 [h,w] holding 0 and 1 only (1 = background; NOT checked here, that would wait for the device) -> (uint8 [h,w,3], record)."""
+    content, stylised, mask = _dev(content, "content", torch.uint8), _dev(stylised, "stylised", torch.uint8), _dev(mask, "mask", torch.uint8)
+    if (content.dim() != 3 or content.shape[2] != 3 or stylised.shape != content.shape or tuple(mask.shape) != tuple(content.shape[:2])
+            or stylised.device != content.device or mask.device != content.device):
+        raise AdainHipError(f"localized_combine_u8: expected uint8 [h,w,3], [h,w,3] and [h,w] on one device, got {tuple(content.shape)}, "
+                            f"{tuple(stylised.shape)} and {tuple(mask.shape)}")
+    return _colour_call("localized_combine_u8", lib().adain_localized_combine_u8, (content, stylised, mask), out)
 
 
 def resize_area_u8(frames, dsize):

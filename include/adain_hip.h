@@ -251,6 +251,45 @@ ADAIN_API int adain_tvl1_flow(const float* const* prev_frames, const float* cons
                               const adain_tvl1_params* params, float* flows_out, int* iters_out, void* workspace, size_t workspace_bytes,
                               adain_stream_t stream);
 
+/* ---- the localized pipeline's foreground colour transfer (Style_3DGS/localized_style_transfer.py:128-168) and the composite around it
+ * (:232-238), which the reference computes in numpy on the host --------------------------------------------------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * fg, bg, out: uint8 HWC [h][w][3] of one size.  A region is the set of pixels whose channels do not sum to zero.  Both regions go
+ * to Reinhard's l-alpha-beta space, each is projected on its first principal axis (scikit-learn's PCA(n_components=1), >= 1.5 sign
+ * rule), the foreground projections are CDF-matched to the background's (np.sort, np.linspace, np.interp restated: csrc/colour.hip
+ * lists the rules) and mapped back through the foreground's axis; pixels outside the foreground region are copied.  float64
+ * throughout, partial sums in a fixed order: the same inputs give the same bytes on every run, stream and device size.
+ * adain_localized_combine_u8: the same with foreground = content * (1 - m) and background = stylised * m built on the fly from the
+ *   {0,1} background mask [h][w] (bytes other than 0 and 1 are the caller's to refuse), and out = adjusted * (1 - m) + background.
+ * The workspace (adain_colour_transfer_workspace_bytes; 0 for a refused size or when the process has no device to size the sort
+ * for; at least 8-byte aligned; both calls take the same) is
+ * not passed with a size: it must hold what the query returns.  It starts with an adain_colour_record that the call fills on the
+ * device and that stays valid until the workspace is used again.  The calls enqueue 5 kernels and two rocprim radix sorts, allocate
+ * nothing, copy nothing to the host and do not wait for the stream - so they CANNOT know the region sizes: an empty region (the
+ * reference returns a copy of the foreground, :141-147) or a region of ONE pixel (the reference divides by zero there; no NaNs
+ * are reproduced) leaves `out` a copy of the foreground (combine: the plain composite) and says so in `status`; a caller that wants
+ * an error for it reads the record after the stream has got there. */
+#define ADAIN_COLOUR_FG_EMPTY 1  /* status bits */
+#define ADAIN_COLOUR_BG_EMPTY 2
+#define ADAIN_COLOUR_FG_SINGLE 4 /* a region of exactly one pixel: no covariance */
+#define ADAIN_COLOUR_BG_SINGLE 8
+typedef struct adain_colour_region {
+    int64_t n;                 /* pixels in the region */
+    double mean[3];            /* PCA.mean_ (l, alpha, beta) */
+    double component[3];       /* PCA.components_[0]; zeros when n < 2 */
+    double explained_variance; /* PCA.explained_variance_[0] */
+} adain_colour_region;
+typedef struct adain_colour_record {
+    adain_colour_region fg, bg;
+    int32_t status; /* 0: the transfer ran; otherwise ADAIN_COLOUR_* bits and `out` holds no transfer */
+    int32_t reserved;
+} adain_colour_record;
+ADAIN_API size_t adain_colour_transfer_workspace_bytes(int h, int w);
+ADAIN_API int adain_colour_transfer_u8(const uint8_t* fg_u8, const uint8_t* bg_u8, uint8_t* out_u8, int h, int w, void* workspace,
+                                       adain_stream_t stream);
+ADAIN_API int adain_localized_combine_u8(const uint8_t* content_u8, const uint8_t* stylised_u8, const uint8_t* mask_u8, uint8_t* out_u8, int h,
+                                         int w, void* workspace, adain_stream_t stream);
+
 /* ---- test_transform's Resize [+ CenterCrop] on the device (test.py:16-24, applied at :190-204; video/utils.py:341-350) --------
  * PIL.Image.resize((wo, ho), BILINEAR) of uint8 RGB images, bit for bit (Pillow's ImagingResample: separable triangle filter whose
  * support grows with the shrink factor, double-precision taps converted to 22-bit fixed point, a horizontal pass into a uint8
