@@ -68,8 +68,12 @@ static Offsets offsets(const Layer* L) {
     return f;
 }
 
+// a bias into its block of a packed network; the block's padding (the decoder's last bias: 3 floats of 64) is zeroed, so that a pack
+// writes every float the *_packed_floats query counts and the caller's buffer needs no preparation
 static int copy_bias(const float* src, float* dst, int n, hipStream_t s) {
-    if (hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
+    const size_t pad = align64((size_t)n) - (size_t)n;
+    if (hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        (pad && hipMemsetAsync(dst + n, 0, pad * sizeof(float), s) != hipSuccess)) {
         set_error("bias copy failed: %s", hipGetErrorString(hipGetLastError()));
         return ADAIN_ELAUNCH;
     }

@@ -234,7 +234,7 @@ def pack_encoder(state_dict, device):
     """state_dict with reference keys ("0.weight", "2.weight", ... ) -> packed device buffer."""
     ws = [_dev(state_dict[f"{k}.weight"].to(device=device, dtype=torch.float32), "weight") for k in ENC_KEYS]
     bs = [_dev(state_dict[f"{k}.bias"].to(device=device, dtype=torch.float32), "bias") for k in ENC_KEYS]
-    packed = torch.zeros(lib().adain_encoder_packed_floats(), dtype=torch.float32, device=device)
+    packed = torch.empty(lib().adain_encoder_packed_floats(), dtype=torch.float32, device=device)
     wp, _k1 = _ptr_array(ws)
     bp, _k2 = _ptr_array(bs)
     with torch.cuda.device(device):
@@ -246,7 +246,7 @@ def pack_encoder(state_dict, device):
 def pack_decoder(state_dict, device):
     ws = [_dev(state_dict[f"{k}.weight"].to(device=device, dtype=torch.float32), "weight") for k in DEC_KEYS]
     bs = [_dev(state_dict[f"{k}.bias"].to(device=device, dtype=torch.float32), "bias") for k in DEC_KEYS]
-    packed = torch.zeros(lib().adain_decoder_packed_floats(), dtype=torch.float32, device=device)
+    packed = torch.empty(lib().adain_decoder_packed_floats(), dtype=torch.float32, device=device)
     wp, _k1 = _ptr_array(ws)
     bp, _k2 = _ptr_array(bs)
     with torch.cuda.device(device):

@@ -69,7 +69,8 @@ ADAIN_API int adain_get_schedule(void);
 /* ---- weights: pack a reference state_dict once (net.vgg / net.decoder, net.py:6-92) ----------------
  * w[i] / b[i] are the OIHW weight and bias tensors of the i-th conv in module order
  * (encoder: state_dict keys 0,2,5,9,12,16,19,22,25,29 ; decoder: 1,5,8,11,14,18,21,25,28).
- * `packed` receives MFMA-fragment-ordered weights + biases; its size is the *_floats query. */
+ * `packed` receives MFMA-fragment-ordered weights + biases; its size is the *_floats query.  A pack writes every float of it (the
+ * padding between its 256-byte aligned blocks included): the buffer needs no preparation by the caller. */
 ADAIN_API size_t adain_encoder_packed_floats(void);
 ADAIN_API size_t adain_decoder_packed_floats(void);
 ADAIN_API int adain_encoder_pack(const float* const* w_host_array_of_dev_ptrs, const float* const* b_host_array_of_dev_ptrs,
@@ -193,7 +194,8 @@ ADAIN_API int adain_resize_area_u8(const uint8_t* in_u8, uint8_t* out_u8, int n,
  *   Each output may be NULL; the arrays need room for levels + 1 entries (pairs) of the REQUESTED levels.
  * adain_farneback_expand: a frame's pyramid (gray uint8 [h][w] -> `pyramid`, adain_farneback_pyramid_bytes): per level k the level
  *   image [h_k][w_k] then its polynomial expansion R [h_k][w_k][5] (OpenCV's channel order y, x, yy, xx, xy), each float block
- *   256-byte aligned, levels in order k = 0, 1, ...  It depends on the frame only: a clip of N frames needs N expansions, each
+ *   256-byte aligned, levels in order k = 0, 1, ...  The padding behind a block (up to its 256-byte boundary, counted in
+ *   adain_farneback_pyramid_bytes) is not part of the result: no call writes or reads it.  It depends on the frame only: a clip of N frames needs N expansions, each
  *   used as `next` of one pair and `prev` of the following one.
  * adain_farneback_flow: the flow from pyr_prev's frame to pyr_next's (both expanded with the same h, w, pyr_scale, levels) ->
  *   flow_out [2][h][w] (x then y displacement, the layout adain_warp_blend_u8 consumes).
@@ -218,7 +220,8 @@ ADAIN_API int adain_farneback_flow(const float* pyr_prev, const float* pyr_next,
  *
  * adain_tvl1_scales (host only): the effective scale count (*out_nscales) and sizes_wh[2s], [2s+1] = width, height of scale s (s = 0:
  *   full size); sizes_wh needs room for params->nscales pairs.  Either output may be NULL.
- * adain_tvl1_frame_bytes: the size of one prepared frame (per scale, float4 (I, I_x, I_y, 0) per pixel, 256-byte aligned blocks).
+ * adain_tvl1_frame_bytes: the size of one prepared frame (per scale, float4 (I, I_x, I_y, 0) per pixel, 256-byte aligned blocks; the
+ *   padding behind a block is counted in the size and is not part of the result: no call writes or reads it).
  * adain_tvl1_prepare: n gray frames [n][h][w] -> n prepared frames, frame_bytes apart.  A frame's preparation depends on the frame
  *   only: a clip prepares each frame once and uses it as I1 of one pair and I0 of the next.
  * adain_tvl1_flow: npairs flows at once.  prev_frames / next_frames are DEVICE arrays of npairs pointers to prepared frames (I0 and
