@@ -51,13 +51,7 @@ def style_schedule(n_frames, n_styles):
     return out
 
 
-def _rank_world(group):
-    return sh.rank_world(group)
-
-
-def host_barrier(group=None, device=None):
-    """Host-side rendezvous of the ranks (see ``sharding.host_barrier``)."""
-    sh.host_barrier(group, device)
+host_barrier = sh.host_barrier
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -118,6 +112,13 @@ def sleep_wait(event, period=2e-4):
         time.sleep(period)
 
 
+def _event(device, stream=None):
+    """A HIP event recorded now on ``stream`` (default: the current stream of ``device``)."""
+    e = torch.cuda.Event()
+    e.record(stream if stream is not None else torch.cuda.current_stream(device))
+    return e
+
+
 class _Batch:
     __slots__ = ("i", "j", "content", "depth", "mask", "ready", "slot")
 
@@ -172,13 +173,13 @@ class FrameFeeder:
 
     # ---- worker thread ----------------------------------------------------------------------------------------------------------
     def _cut(self):
-        """Yields (i, j, frames-or-block, kind) for consecutive sub-batches of [lo, hi)."""
+        """Yields (i, j, frames-or-block) for consecutive sub-batches of [lo, hi)."""
         k, carry = self.lo, None
         block = getattr(self.frames, "block", None)
         ahead, nxt = [], self.lo               # futures of frames nxt - len(ahead) .. nxt - 1, fetched by the pool in index order
 
         def fetch(idx):
-            return as_frame(self.frames[idx])
+            return as_frame(self.frames[idx])[0]
 
         def get(idx):
             nonlocal nxt
@@ -187,37 +188,34 @@ class FrameFeeder:
                 nxt += 1
             return ahead.pop(0).result()
 
-        def size_of(t, kd):
-            return (t.shape[-3], t.shape[-2]) if kd == "u8" else (t.shape[-2], t.shape[-1])
+        def size_of(t):                        # decoded frames are uint8 [.., h, w, 3], transformed ones float [.., 3, h, w]
+            return (t.shape[-3], t.shape[-2]) if t.dtype == torch.uint8 else (t.shape[-2], t.shape[-1])
 
         while k < self.hi:
             i = k
             if block is not None:
                 limit = self.sub_batch
                 if self.auto:
-                    one = block(i, i + 1)
-                    limit = auto_sub_batch(*size_of(one, "u8" if one.dtype == torch.uint8 else "f32"))
+                    limit = auto_sub_batch(*size_of(block(i, i + 1)))
                 j = i + 1
                 while j < self.hi and j - i < limit and self.style_of[j] == self.style_of[i] and j not in self.cuts:
                     j += 1
-                t = block(i, j)
-                yield i, j, t, ("u8" if t.dtype == torch.uint8 else "f32")
+                yield i, j, block(i, j)
                 k = j
                 continue
-            items, kind = [], None
+            items = []
             limit = self.sub_batch
             while k < self.hi and len(items) < limit and self.style_of[k] == self.style_of[i] and not (items and k in self.cuts):
-                fr, kd = carry if carry is not None else get(k)
+                fr = carry if carry is not None else get(k)
                 carry = None
                 if not items and self.auto:
-                    limit = auto_sub_batch(*size_of(fr, kd))
-                if items and (kd != kind or fr.shape != items[0].shape or fr.device != items[0].device):
-                    carry = (fr, kd)          # another size / kind: it opens the next sub-batch
+                    limit = auto_sub_batch(*size_of(fr))
+                if items and (fr.dtype != items[0].dtype or fr.shape != items[0].shape or fr.device != items[0].device):
+                    carry = fr                # another size / kind: it opens the next sub-batch
                     break
                 items.append(fr)
-                kind = kd
                 k += 1
-            yield i, k, items, kind
+            yield i, k, items
 
     def _upload(self, host):
         """A one-off upload (shapes that do not fit the slot buffers): pinned copy + asynchronous H2D on the copy stream."""
@@ -279,8 +277,9 @@ class FrameFeeder:
         try:
             if self.cuda:
                 torch.cuda.set_device(self.device)
+            stage = self._stage_device if self.cuda else self._stage_host
             b = 0
-            for i, j, items, kind in self._cut():
+            for i, j, items in self._cut():
                 if self.stop.is_set():
                     return
                 t0 = time.perf_counter()
@@ -288,74 +287,73 @@ class FrameFeeder:
                 t1 = time.perf_counter()
                 self.fetch_s += t1 - t0
                 self.free.acquire()
-                t2 = time.perf_counter()
-                self.stats["wait_slot_s"] += t2 - t1
+                self.stats["wait_slot_s"] += time.perf_counter() - t1
                 self.stats["batches"] += 1
                 if self.stop.is_set():
                     return
-                s = b % self.nslots
+                self.q.put(stage(b % self.nslots, i, j, items, depth, mask))
                 b += 1
-                ready = None
-                if not self.cuda:
-                    content = items if isinstance(items, torch.Tensor) else torch.stack(items)
-                    if mask is not None and all(m.shape == mask[0].shape for m in mask):
-                        mask = torch.stack(mask)
-                else:
-                    if self.h2d_done[s] is not None:
-                        sleep_wait(self.h2d_done[s])                     # the slot's previous uploads have left its pinned buffers
-                    t3 = time.perf_counter()
-                    self.stats["wait_h2d_s"] += t3 - t2
-                    # device tensors handed over by the stores (a mask or depth map computed lazily in __getitem__, a frame
-                    # made on the GPU) were produced on the fetching threads' current stream, not on the copy stream: whatever
-                    # reads them below - and the consumer, through `ready` - is ordered behind an event recorded there now
-                    on_device = ((isinstance(items, torch.Tensor) and items.is_cuda) or (isinstance(items, list) and items and items[0].is_cuda)
-                                 or any(t.is_cuda for t in (depth or [])) or any(t.is_cuda for t in (mask or [])))
-                    fetched = None
-                    if on_device:
-                        fetched = torch.cuda.Event()
-                        fetched.record(torch.cuda.current_stream(self.device))
-                    with torch.cuda.stream(self.copy_stream):
-                        if self.consumed[s] is not None:
-                            self.copy_stream.wait_event(self.consumed[s])      # the kernels that read this slot have finished
-                        staged = False                                       # something was copied out of the slot's pinned buffers
-                        ordered = fetched is not None                        # `ready` must carry an ordering on to the consumer
-                        if fetched is not None:
-                            self.copy_stream.wait_event(fetched)
-                        if isinstance(items, torch.Tensor):              # a ready block (device-resident store)
-                            content = items
-                        elif items[0].is_cuda:
-                            content = None                               # stacked by the consumer on its own stream
-                        else:
-                            content = self._stage(s, "content", items)
-                            staged = True
-                        if depth is not None and not all(d.is_cuda for d in depth):
-                            if self._uniform(depth):
-                                dd = self._stage(s, "depth", depth)
-                                depth = [dd[k] for k in range(len(depth))]
-                            else:
-                                depth = [d if d.is_cuda else self._upload(d) for d in depth]
-                            staged = True
-                        if mask is not None:
-                            if all(m.is_cuda for m in mask):
-                                mask = torch.stack(mask)
-                                mask.record_stream(self.compute_stream)
-                            elif self._uniform(mask):
-                                mask = self._stage(s, "mask", mask)
-                            else:                                        # masks of several sizes: one upload each, composited per frame
-                                mask = [m if m.is_cuda else self._upload(m) for m in mask]
-                            staged = True
-                        if staged or ordered:
-                            ready = torch.cuda.Event()
-                            ready.record(self.copy_stream)
-                            if staged:                                       # only pinned buffers need the host to wait before reuse
-                                self.h2d_done[s] = ready
-                    self.stats["stage_s"] += time.perf_counter() - t3
-                    if content is None:
-                        content = items                                  # list of device tensors
-                self.q.put(_Batch(i, j, content, depth, mask, ready, s))
             self.q.put(None)
         except BaseException as e:                                       # re-raised by the consumer
             self.q.put(e)
+
+    def _stage_host(self, s, i, j, items, depth, mask):
+        """The CPU stand-in: the sub-batch as stacked host tensors, no slot buffers and no streams."""
+        content = items if isinstance(items, torch.Tensor) else torch.stack(items)
+        if mask is not None and all(m.shape == mask[0].shape for m in mask):
+            mask = torch.stack(mask)
+        return _Batch(i, j, content, depth, mask, None, s)
+
+    def _to_device(self, s, name, ts):
+        """The tensors ``ts`` (one per frame) of slot ``s`` on their way up, on the copy stream: host tensors of one shape and
+        dtype -> the slot's buffer ``name`` (a device view [len(ts), ...]), other host tensors -> one upload each (a list).
+        Returns them and True - or, if all of them already are on the device, ``ts`` as it is and False: nothing left pinned
+        memory, and it is the consumer that tells the allocator who reads them (``__iter__``)."""
+        if all(t.is_cuda for t in ts):
+            return ts, False
+        if self._uniform(ts):
+            return self._stage(s, name, ts), True
+        return [t if t.is_cuda else self._upload(t) for t in ts], True
+
+    def _stage_device(self, s, i, j, items, depth, mask):
+        """Sub-batch i..j-1 into slot ``s``: its frames, proximity maps and masks uploaded on the copy stream, ordered behind
+        the slot's previous use and ahead of the consumer (``ready``)."""
+        t2 = time.perf_counter()
+        if self.h2d_done[s] is not None:
+            sleep_wait(self.h2d_done[s])                     # the slot's previous uploads have left its pinned buffers
+        t3 = time.perf_counter()
+        self.stats["wait_h2d_s"] += t3 - t2
+        # device tensors handed over by the stores (a mask or depth map computed lazily in __getitem__, a frame made on the GPU)
+        # were produced on the fetching threads' current stream, not on the copy stream: whatever reads them below - and the
+        # consumer, through `ready` - is ordered behind an event recorded there now
+        groups = [items if isinstance(items, list) else [items], depth or [], mask or []]
+        fetched = _event(self.device) if any(t.is_cuda for g in groups for t in g) else None
+        staged = False                                       # something was copied out of the slot's pinned buffers
+        with torch.cuda.stream(self.copy_stream):
+            if self.consumed[s] is not None:
+                self.copy_stream.wait_event(self.consumed[s])      # the kernels that read this slot have finished
+            if fetched is not None:
+                self.copy_stream.wait_event(fetched)
+            if isinstance(items, list):                      # (else a ready block of a device-resident store; a list of device
+                items, staged = self._to_device(s, "content", items)         # tensors is stacked by the consumer on its own stream)
+            if depth is not None:
+                depth, up = self._to_device(s, "depth", depth)
+                staged |= up
+                if isinstance(depth, torch.Tensor):
+                    depth = [depth[k] for k in range(j - i)]
+            if mask is not None:
+                mask, up = self._to_device(s, "mask", mask)  # (a list: masks of several sizes, composited per frame)
+                staged |= up
+                if not up:
+                    mask = torch.stack(mask)
+                    mask.record_stream(self.compute_stream)
+            ready = None
+            if staged or fetched is not None:                # `ready` carries the uploads' and `fetched`'s order on to the consumer
+                ready = _event(self.device, self.copy_stream)
+                if staged:                                   # only pinned buffers need the host to wait before reuse
+                    self.h2d_done[s] = ready
+        self.stats["stage_s"] += time.perf_counter() - t3
+        return _Batch(i, j, items, depth, mask, ready, s)
 
     # ---- consumer ---------------------------------------------------------------------------------------------------------------
     def __iter__(self):
@@ -385,9 +383,7 @@ class FrameFeeder:
     def release(self, batch):
         """The consumer has enqueued the last kernel that reads ``batch``'s slot."""
         if self.cuda and batch.slot is not None:
-            e = torch.cuda.Event()
-            e.record(torch.cuda.current_stream(self.device))
-            self.consumed[batch.slot] = e
+            self.consumed[batch.slot] = _event(self.device)
         self.free.release()
 
     def close(self):
@@ -410,23 +406,22 @@ class HostCopier:
             self.stream = torch.cuda.Stream(self.device)
 
     def copy(self, dst_host, src):
-        """dst_host.copy_(src) once the work enqueued so far on the current stream has finished."""
+        """dst_host.copy_(src) once the work enqueued so far on the current stream has finished.  Returns the event recorded
+        behind the copy (None on a CPU device: the copy is done)."""
         self.bytes += src.numel() * src.element_size()
         if not self.cuda:
             dst_host.copy_(src)
-            return
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream(self.device))
+            return None
+        ready = _event(self.device)
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(ready)
             dst_host.copy_(src, non_blocking=True)
             src.record_stream(self.stream)
+            return _event(self.device, self.stream)
 
     def finish(self):
         if self.cuda:
-            done = torch.cuda.Event()
-            done.record(self.stream)
-            sleep_wait(done)
+            sleep_wait(_event(self.device, self.stream))
 
 
 class FileSink:
@@ -435,11 +430,9 @@ class FileSink:
     kernels are already running.  ``close()`` waits for every file and re-raises the first error."""
 
     def __init__(self, device, workers=4, max_in_flight=None):
-        self.device = torch.device(device)
-        self.cuda = self.device.type == "cuda"
+        self.copier = HostCopier(device)
         self.pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="adain-file-sink")
         self.futures = []
-        self.d2h_bytes = 0
         # back-pressure: at most `max_in_flight` blocks (default 2 per writer) sit in pinned memory waiting for their encoder;
         # write() blocks when the writers fall behind instead of pinning the whole job.  The pinned buffers are reused.
         self.max_in_flight = max(1, int(max_in_flight if max_in_flight is not None else 2 * workers))
@@ -447,8 +440,10 @@ class FileSink:
         self.spare = {}                    # block shape -> idle pinned buffers
         self.spare_lock = threading.Lock()
         self.wait_s = 0.0                  # time write() spent blocked on the writers
-        if self.cuda:
-            self.stream = torch.cuda.Stream(self.device)
+
+    @property
+    def d2h_bytes(self):
+        return self.copier.bytes
 
     def _pinned(self, shape):
         with self.spare_lock:
@@ -469,20 +464,11 @@ class FileSink:
         self.slots.acquire()
         self.wait_s += time.perf_counter() - t0
         shape = tuple(u8_block.shape)
-        if not self.cuda:
+        if not self.copier.cuda:
             host, done = u8_block, None
         else:
-            cur = torch.cuda.current_stream(self.device)
-            ready = torch.cuda.Event()
-            ready.record(cur)
             host = self._pinned(shape)
-            with torch.cuda.stream(self.stream):
-                self.stream.wait_event(ready)
-                host.copy_(u8_block, non_blocking=True)
-                u8_block.record_stream(self.stream)
-                done = torch.cuda.Event()
-                done.record(self.stream)
-            self.d2h_bytes += u8_block.numel()
+            done = self.copier.copy(host, u8_block)
 
         def job():
             try:
@@ -523,9 +509,146 @@ def _elapsed(engine, a, b):
     return f(a, b) if f is not None else b - a
 
 
+def _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence):
+    """One sub-batch of the feeder on the engine -> the finished uint8 frames [k,H,W,3]."""
+    content, dev = batch.content, engine.device
+    one_call = getattr(engine, "stylize_u8", None)
+    if (one_call is not None and content.dtype == torch.uint8 and content.dim() == 4 and content.shape[-1] == 3
+            and not isinstance(batch.mask, list)):
+        # decoded RGB frames with (at most) one mask tensor for the sub-batch: the whole chain in one C-ABI call
+        return one_call(content, alpha=alpha, depth_maps=batch.depth, offset=depth_offset, prominence=depth_prominence, masks=batch.mask)
+    if batch.depth is not None:
+        out = engine.stylize_depth(content, [d.to(dev, torch.float32) for d in batch.depth], depth_offset, depth_prominence)
+    else:
+        out = engine.stylize(content, alpha)
+    if isinstance(batch.mask, list):           # masks of different sizes inside one sub-batch: composite frame by frame
+        out = torch.cat([engine.composite(content[k:k + 1], out[k:k + 1], m.to(dev).float().unsqueeze(0))
+                         for k, m in enumerate(batch.mask)])
+    elif batch.mask is not None:
+        out = engine.composite(content, out, batch.mask.to(dev).float())
+    return engine.to_u8(out)
+
+
+def _cat_blocks(blocks, geom, device):
+    """The uint8 blocks as one [k,H,W,C] tensor; without blocks, an empty one of the frame geometry ``geom`` = (H, W, C)."""
+    if blocks:
+        return torch.cat(blocks) if len(blocks) > 1 else blocks[0]
+    return torch.empty((0,) + tuple(geom), dtype=torch.uint8, device=device)
+
+
+class _BlockGather:
+    """The collectives of one job, the same sequence on every rank whatever happens to its block: pieces 0 .. k-2 of the
+    block as soon as they are finished (``add``), then - ``finish`` - the status word and the last piece.  A single piece
+    (k = 1) is the job's one gather after the status word.  The finished frames arrive on ``dst`` in frame order and, piece
+    by piece, in ``host_out``."""
+
+    def __init__(self, n, rank, world, dst, group, device, chunks, out_hw, info, copier=None, host_out=None):
+        self.n, self.rank, self.world, self.dst, self.group, self.device = n, rank, world, dst, group, device
+        self.chunks, self.out_hw, self.info, self.copier, self.host_out = chunks, out_hw, info, copier, host_out
+        # pieces issued before the status word take the frame geometry from the caller
+        self.piece_geom = tuple(out_hw) + (3,) if chunks > 1 else None
+        self.first = [sh.shard_range(n, world, r)[0] for r in range(world)]
+        # piece c of rank r = frames [first[r] + a, first[r] + b) with (a, b) = bounds[r][c]
+        self.bounds = [sh.chunk_bounds(count, chunks) for count in sh.shard_counts(n, world)]
+        self.blocks, self.shapes = [], set()   # finished sub-batches (i, j, u8) of this rank, their frame shapes
+        self.issued = 0                        # pieces of this rank that have joined their gather
+        self.pending, self.landed = [], []     # (piece, counts, finish closure) in flight; (first frame, rows) arrived on dst
+
+    def cuts(self):
+        """The frame indices at which a sub-batch of this rank must end: the borders of its pieces."""
+        return [self.first[self.rank] + b for (_, b) in self.bounds[self.rank]]
+
+    def add(self, i, j, u8):
+        """Sub-batch (frames i..j-1) is finished: every in-loop piece that is now complete joins its gather."""
+        self.blocks.append((i, j, u8))
+        self.shapes.add(tuple(u8.shape[1:]))
+        if self.chunks > 1 and tuple(u8.shape[1:3]) != tuple(self.out_hw):
+            raise ValueError(f"stylize_frames_sharded: out_hw {tuple(self.out_hw)} but a finished frame is {tuple(u8.shape[1:3])}")
+        while self.issued < self.chunks - 1 and self.first[self.rank] + self.bounds[self.rank][self.issued][1] <= j:
+            self._issue(self.piece_geom)
+
+    def _issue(self, geom, zeros=False):
+        """The next piece of this rank's block joins its gather; ``zeros``: this rank has failed - it still takes part, with a
+        zero-filled block of the agreed geometry, so that its peers (already inside the collective) are not left waiting; the
+        status word after the last in-loop piece then raises on every rank."""
+        c = self.issued
+        self.issued += 1
+        lo = self.first[self.rank]
+        a, b = self.bounds[self.rank][c]
+        if zeros:
+            local = torch.zeros((b - a,) + geom, dtype=torch.uint8, device=self.device)
+        else:
+            local = _cat_blocks([u8 for (i, j, u8) in self.blocks if lo + a <= i and j <= lo + b], geom, self.device)
+        cnts = [bd[c][1] - bd[c][0] for bd in self.bounds]
+        self.info["gathers"] += 1
+        self._land()                       # the previous piece has long arrived: hand it on before queueing the next
+        self.pending.append((c, cnts, sh.gather_frames(local, self.n, dst=self.dst, group=self.group, async_op=True, counts=cnts)))
+
+    def _land(self):
+        """Waits (on the stream) for the gathered pieces issued so far and files them on dst: into the job's result and, piece
+        by piece, into ``host_out``."""
+        while self.pending:
+            c, cnts, fin = self.pending.pop(0)
+            got = fin()
+            if self.rank != self.dst:
+                continue
+            # rank r's rows of the piece belong at frame first[r] + a; a job's only piece is the job in frame order: one run
+            runs = [(0, self.n)] if self.chunks == 1 else [(self.first[r] + self.bounds[r][c][0], cnts[r]) for r in range(self.world)]
+            at = 0
+            for frame, k in runs:
+                if k:
+                    self.landed.append((frame, got[at:at + k]))
+                    if self.copier is not None:
+                        self.copier.copy(self.host_out[frame:frame + k], got[at:at + k])
+                at += k
+
+    def _drain(self):
+        """An abandoned job: the pieces already issued are complete collectives (every rank took part) - wait for them so that
+        nothing of this job is left in flight on the communicator, and drop the data."""
+        while self.pending:
+            try:
+                self.pending.pop(0)[2]()
+            except Exception:
+                pass
+
+    def finish(self, err):
+        """The block is over, ``err`` = what ended it early (or None).  Returns the job's frames [n,H,W,C] on ``dst`` (None on
+        the other ranks) - or raises, on EVERY rank, if any rank failed or the frames do not share one size."""
+        # every rank issues every in-loop piece, whatever happened to its block: the collective sequence stays identical
+        # (pieces 0 .. k-2, status word, last piece); a failed rank sends zeros and the status word raises everywhere
+        try:
+            while self.issued < self.chunks - 1:
+                self._issue(self.piece_geom, zeros=err is not None)
+        except Exception as e:
+            err = err or e
+        ok, geom, uniform = sh.agree_geometry(err is None, self.shapes, self.group, self.device)
+        if err is not None or not ok:
+            self._drain()
+        if err is not None:
+            raise err
+        if not ok:
+            raise RuntimeError("stylize_frames_sharded: another rank failed; job abandoned before the gather")
+        if not uniform:
+            raise ValueError("stylize_frames_sharded: the gather needs one frame size on every rank")
+        if geom is not None and self.out_hw is not None and tuple(self.out_hw) != tuple(geom[:2]):
+            raise ValueError(f"stylize_frames_sharded: out_hw {tuple(self.out_hw)} but the finished frames are {tuple(geom[:2])}")
+        if geom is None:                       # an empty job: nothing to gather anywhere
+            return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=self.device) if self.rank == self.dst else None
+        self._issue(self.piece_geom or geom)   # (a job's only piece: a rank with an empty block learns the geometry from the status word)
+        self._land()
+        if self.rank != self.dst:
+            return None
+        if len(self.landed) == 1:              # one run holds every frame: it is the result
+            return self.landed[0][1]
+        out = torch.empty((self.n,) + tuple(geom), dtype=torch.uint8, device=self.device)
+        for frame, rows in self.landed:
+            out[frame:frame + rows.shape[0]].copy_(rows)
+        return out
+
+
 def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, depth_maps=None, depth_offset=0.15,
                            depth_prominence=20, masks=None, post=None, sub_batch=None, group=None, dst=0, gather=True,
-                           require_transport=None, style_cache=None, out_hw=None, gather_chunks=1, agree=True, sink=None,
+                           require_transport=None, style_cache=None, out_hw=None, gather_chunks=1, sink=None,
                            prefetch=4, host_out=None, fetch_workers=4):
     """Stylises ``frames`` (a sequence indexed lazily: a rank only ever touches its own block; an element is a decoded
     frame uint8 [h,w,3] / RGB PIL image, or a float tensor [3,h,w] in [0,1]) and returns ``(frames_u8, info)``: the uint8
@@ -545,8 +668,7 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
                     (frame-local work such as the INTER_AREA resize, so the gather moves the small frames).
     sink            optional ``f(i, j, u8_block)`` called with every finished sub-batch (frames i..j-1) on the owning rank.
     require_transport   e.g. "rccl": raise before any work if the gather would use another transport.
-    out_hw          (H, W) of a finished frame, if the caller knows it: lets ``agree=False`` jobs and chunked gathers run with
-                    ranks whose block is empty.
+    out_hw          (H, W) of a finished frame, if the caller knows it: lets chunked gathers run with ranks whose block is empty.
     gather_chunks   1: ONE gather when every rank has finished (after the status word: an error anywhere raises everywhere).
                     k > 1 (needs ``out_hw``: ValueError without it): the block is gathered in k pieces, pieces 0 .. k-2
                     issued asynchronously as soon as they are finished so that they overlap the rest of the compute, then the
@@ -556,11 +678,10 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
     host_out        a (pinned) uint8 host tensor [n,H,W,3]: finished frames are also copied into it, asynchronously on a copy
                     stream as they become available — per sub-batch on a single rank (or with ``gather=False``: every rank fills
                     the rows of its own block), per gathered piece on ``dst`` otherwise — and are all there when the call returns.
-    agree           False skips the per-job status word (per-step benchmark mode: every rank must have frames or ``out_hw``).
 
     The gather needs one frame size over the whole job; with ``gather=False`` sizes may differ from frame to frame (a
     sub-batch ends where the size changes).  Nothing in the frame loop synchronises the device or communicates."""
-    rank, world = _rank_world(group)
+    rank, world = sh.rank_world(group)
     n = len(frames)
     lo, hi = sh.shard_range(n, world, rank)
     style_list = list(styles) if isinstance(styles, (list, tuple)) else [styles]
@@ -569,79 +690,33 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
     if len(style_of) != n:
         raise ValueError("style_of needs one style index per frame")
     dev = engine.device
+    on_gpu = dev.type == "cuda"
     gathering = gather and world > 1
-    transport = None
     if int(gather_chunks) > 1 and out_hw is None:
         # Pieces are issued inside the frame loop, BEFORE the status word: a rank that fails must still take part in every one of
         # them (with zero-filled blocks), so it has to know what a finished frame looks like without having finished one.  Asking
         # for pieces without out_hw is an error, decided from the arguments alone: the same on every rank and for every world size
         # (round 4 silently ran such a job with one end gather: no overlap and no signal).
         raise ValueError("gather_chunks > 1 needs out_hw (the size of a finished frame): pieces are gathered before the ranks agree")
-    chunks = max(1, int(gather_chunks)) if gathering else 1
-    if gathering:
-        transport = sh.device_transport(torch.empty(0, dtype=torch.uint8, device=dev), group)
-        if require_transport and transport != require_transport:
-            raise RuntimeError(f"final gather would run over {transport!r}, not {require_transport!r}")
-        if not agree and n < world and out_hw is None:        # the same decision on every rank
-            raise ValueError("a job with fewer frames than ranks needs out_hw for unagreed gathers")
-    counts = sh.shard_counts(n, world)
-    # chunk c of rank r = frames [lo_r + a, lo_r + b) with (a, b) = chunk_bounds(counts[r], chunks)[c]
-    my_chunks = sh.chunk_bounds(hi - lo, chunks)
+    transport = sh.device_transport(torch.empty(0, dtype=torch.uint8, device=dev), group) if gathering else None
+    if gathering and require_transport and transport != require_transport:
+        raise RuntimeError(f"final gather would run over {transport!r}, not {require_transport!r}")
 
     info = {"rank": rank, "world": world, "shard": (lo, hi), "transport": transport, "gathers": 0}
     t_host0 = time.perf_counter()
     cpu0_thread, cpu0_proc = time.thread_time(), time.process_time()
     abi0 = getattr(engine, "abi_calls", lambda: 0)()
     m0 = _mark(engine)
-    blocks, shapes = [], set()             # finished sub-batches (i, j, u8) of this rank, their frame shapes
-    pending, landed = [], []               # chunked gather: (chunk, counts, finish closure) in flight; (first frame, block) arrived on dst
-    next_chunk = 0
-    err = None
     copier = HostCopier(dev) if host_out is not None else None
+    gathered = _BlockGather(n, rank, world, dst, group, dev, max(1, int(gather_chunks)), out_hw, info, copier, host_out) if gathering else None
     feeder = FrameFeeder(frames, lo, hi, style_of, sub_batch, dev, depth_maps, masks, depth=prefetch,
-                         cuts=[lo + b for (_, b) in my_chunks] if chunks > 1 else (), workers=fetch_workers)
-
-    def chunk_ready(c, done_upto):
-        return lo + my_chunks[c][1] <= done_upto
-
-    def issue_chunk(c, zeros=False):
-        """Piece c of this rank's block joins the gather; ``zeros``: this rank has failed - it still takes part, with a zero-filled
-        block of the agreed geometry, so that its peers (already inside the collective) are not left waiting; the status word
-        after the last in-loop piece then raises on every rank."""
-        a, b = my_chunks[c]
-        part = [] if zeros else [u8 for (i, j, u8) in blocks if lo + a <= i and j <= lo + b]
-        if part:
-            local_c = torch.cat(part) if len(part) > 1 else part[0]
-        else:
-            local_c = torch.zeros((b - a if zeros else 0,) + tuple(out_hw) + (3,), dtype=torch.uint8, device=dev)
-        cnts = [sh.chunk_bounds(cr, chunks)[c][1] - sh.chunk_bounds(cr, chunks)[c][0] for cr in counts]
-        info["gathers"] += 1
-        land_pending()                     # the previous piece has long arrived: hand it on before queueing the next
-        pending.append((c, cnts, sh.gather_frames(local_c, n, dst=dst, group=group, async_op=True, counts=cnts)))
-
-    def land_pending():
-        """Waits (on the stream) for the gathered pieces issued so far and files them on dst: into the job's result and, piece
-        by piece, into ``host_out``."""
-        while pending:
-            c, cnts, fin = pending.pop(0)
-            got = fin()
-            if rank != dst:
-                continue
-            at = 0
-            for r in range(world):
-                r_lo = sh.shard_range(n, world, r)[0]
-                a = sh.chunk_bounds(counts[r], chunks)[c][0]
-                if cnts[r]:
-                    landed.append((r_lo + a, got[at:at + cnts[r]]))
-                    if copier is not None:
-                        copier.copy(host_out[r_lo + a:r_lo + a + cnts[r]], got[at:at + cnts[r]])
-                at += cnts[r]
-
+                         cuts=gathered.cuts() if gathering else (), workers=fetch_workers)
+    blocks = []                            # without a gather: the finished sub-batches of this rank that the caller gets
     # At most MAX_QUEUED_BATCHES sub-batches are queued on the device beyond the one that is running: enough that the GPU never
     # waits for the host (a sub-batch is about three megapixels: >= 5 ms of kernels), few enough that this thread sleeps in
     # sleep_wait instead of spinning inside hipLaunchKernel on a full HIP queue.
     queued = []
-    on_gpu = dev.type == "cuda"
+    err = None
     try:
         cur_style = None
         stats = style_cache if style_cache is not None else {}
@@ -654,44 +729,21 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
                 if cur_style not in stats:
                     stats[cur_style] = engine.set_style(style_list[cur_style]).style_stats()
                 engine.use_style_stats(stats[cur_style])
-            content = batch.content
-            one_call = getattr(engine, "stylize_u8", None)
-            if (one_call is not None and content.dtype == torch.uint8 and content.dim() == 4 and content.shape[-1] == 3
-                    and not isinstance(batch.mask, list)):
-                # decoded RGB frames with (at most) one mask tensor for the sub-batch: the whole chain in one C-ABI call
-                u8 = one_call(content, alpha=alpha, depth_maps=batch.depth, offset=depth_offset, prominence=depth_prominence, masks=batch.mask)
-                out = None
-            elif batch.depth is not None:
-                out = engine.stylize_depth(content, [d.to(dev, torch.float32) for d in batch.depth], depth_offset, depth_prominence)
-            else:
-                out = engine.stylize(content, alpha)
-            if out is not None:
-                if isinstance(batch.mask, list):       # masks of different sizes inside one sub-batch: composite frame by frame
-                    out = torch.cat([engine.composite(content[k:k + 1], out[k:k + 1], m.to(dev).float().unsqueeze(0))
-                                     for k, m in enumerate(batch.mask)])
-                elif batch.mask is not None:
-                    out = engine.composite(content, out, batch.mask.to(dev).float())
-                u8 = engine.to_u8(out)
+            u8 = _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence)
             feeder.release(batch)
             if on_gpu:
-                e = torch.cuda.Event()
-                e.record(torch.cuda.current_stream(dev))
-                queued.append(e)
+                queued.append(_event(dev))
             if post is not None:
                 u8 = post(u8)
-            shapes.add(tuple(u8.shape[1:]))
             if sink is not None:
                 sink(i, j, u8)
-            if copier is not None and not gathering:
-                copier.copy(host_out[i:j], u8)
-            if gather or sink is None:
-                blocks.append((i, j, u8))
-            if chunks > 1:
-                if tuple(u8.shape[1:3]) != tuple(out_hw):
-                    raise ValueError(f"stylize_frames_sharded: out_hw {tuple(out_hw)} but a finished frame is {tuple(u8.shape[1:3])}")
-                while next_chunk < chunks - 1 and chunk_ready(next_chunk, j):
-                    issue_chunk(next_chunk)
-                    next_chunk += 1
+            if gathering:
+                gathered.add(i, j, u8)
+            else:
+                if copier is not None:
+                    copier.copy(host_out[i:j], u8)
+                if gather or sink is None:
+                    blocks.append(u8)
     except Exception as e:                 # agreed on below: every rank raises, none is left waiting in the gather
         err = e
     finally:
@@ -701,15 +753,6 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
             engine.synchronize()
         except Exception:
             pass
-    if chunks > 1:
-        # every rank issues every in-loop piece, whatever happened to its block: the collective sequence stays identical
-        # (pieces 0 .. k-2, status word, last piece); a failed rank sends zeros and the status word raises everywhere
-        try:
-            while next_chunk < chunks - 1:
-                issue_chunk(next_chunk, zeros=err is not None)
-                next_chunk += 1
-        except Exception as e:
-            err = err or e
     info["h2d_bytes"] = feeder.h2d_bytes
     info["fetch_s"] = feeder.fetch_s
     info["feeder"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in feeder.stats.items()}
@@ -722,91 +765,26 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
     info["process_cpu_s"] = time.process_time() - cpu0_proc
     info["abi_calls"] = getattr(engine, "abi_calls", lambda: 0)() - abi0
 
-    def finish_times(m2=None):
-        if on_gpu:                          # sleep until the device has finished this job's work, then the (now immediate) synchronisations
-            e = torch.cuda.Event()
-            e.record(torch.cuda.current_stream(dev))
-            sleep_wait(e)
-        if copier is not None:
-            copier.finish()
-            info["d2h_bytes"] = copier.bytes
-        engine.synchronize()
-        info["compute_s"] = _elapsed(engine, m0, m1)
-        info["gather_s"] = _elapsed(engine, m1, m2) if m2 is not None else 0.0
-
-    if not gathering:
-        if err is not None:
-            raise err
-        finish_times()
-        if sink is not None and not gather:
-            return None, info
-        if len(shapes) > 1:
+    out = m2 = None
+    if gathering:
+        out = gathered.finish(err)         # the job's status word, then its (last) gather; raises on every rank if one failed
+        m2 = _mark(engine)
+    elif err is not None:
+        raise err
+    if on_gpu:                             # sleep until the device has finished this job's work, then the (now immediate) synchronisations
+        sleep_wait(_event(dev))
+    if copier is not None:
+        copier.finish()
+        info["d2h_bytes"] = copier.bytes
+    engine.synchronize()
+    info["compute_s"] = _elapsed(engine, m0, m1)
+    info["gather_s"] = _elapsed(engine, m1, m2) if m2 is not None else 0.0
+    if not gathering and (gather or sink is None):       # the local block(s) - unless a sink took them
+        if len({tuple(u8.shape[1:]) for u8 in blocks}) > 1:
             if gather:
                 raise ValueError("stylize_frames_sharded: the gather needs one frame size over the whole job")
-            return [u8 for (_, _, u8) in blocks], info
-        if blocks:
-            local = torch.cat([u8 for (_, _, u8) in blocks]) if len(blocks) > 1 else blocks[0][2]
-        else:
-            geom = tuple(out_hw) + (3,) if out_hw is not None else (0, 0, 3)
-            local = torch.empty((0,) + geom, dtype=torch.uint8, device=dev)
-        return local, info
-
-    # ---- the job's status word, then its gather ------------------------------------------------------------------------------------
-    geom = next(iter(shapes)) if len(shapes) == 1 else None
-    def drop_pending():
-        """An abandoned chunked job: the pieces already issued are complete collectives (every rank took part) - wait for them
-        so that nothing of this job is left in flight on the communicator, and drop the data."""
-        while pending:
-            try:
-                pending.pop(0)[2]()
-            except Exception:
-                pass
-
-    if agree:
-        ok, geom_all, uniform = sh.agree_geometry(err is None, shapes, group, dev)
-        if err is not None or not ok:
-            drop_pending()
-        if err is not None:
-            raise err
-        if not ok:
-            raise RuntimeError("stylize_frames_sharded: another rank failed; job abandoned before the gather")
-        if not uniform:
-            raise ValueError("stylize_frames_sharded: the gather needs one frame size on every rank")
-        if geom_all is not None and out_hw is not None and tuple(out_hw) != tuple(geom_all[:2]):
-            raise ValueError(f"stylize_frames_sharded: out_hw {tuple(out_hw)} but the finished frames are {tuple(geom_all[:2])}")
-        geom = geom_all
-    else:
-        if err is not None:
-            drop_pending()
-            raise err
-        if len(shapes) > 1:
-            raise ValueError("stylize_frames_sharded: the gather needs one frame size over the whole job")
-        if geom is None and out_hw is not None:
-            geom = tuple(out_hw) + (3,)
-    if geom is None:                       # an empty job: nothing to gather anywhere
-        finish_times()
-        return (torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=dev) if rank == dst else None), info
-    if chunks == 1:
-        if blocks:
-            local = torch.cat([u8 for (_, _, u8) in blocks]) if len(blocks) > 1 else blocks[0][2]
-        else:
-            local = torch.empty((0,) + tuple(geom), dtype=torch.uint8, device=dev)
-        info["gathers"] += 1
-        out = sh.gather_frames(local, n, dst=dst, group=group)
-        if copier is not None and rank == dst:
-            copier.copy(host_out, out)
-    else:
-        while next_chunk < chunks:
-            issue_chunk(next_chunk)
-            next_chunk += 1
-        land_pending()
-        out = None
-        if rank == dst:
-            out = torch.empty((n,) + tuple(geom), dtype=torch.uint8, device=dev)
-            for first, blk in landed:
-                out[first:first + blk.shape[0]].copy_(blk)
-    m2 = _mark(engine)
-    finish_times(m2)
+            return blocks, info
+        out = _cat_blocks(blocks, tuple(out_hw) + (3,) if out_hw is not None else (0, 0, 3), dev)
     return out, info
 
 
@@ -855,7 +833,7 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
 
     if write not in ("dst", "local"):
         raise ValueError("write must be 'dst' or 'local'")
-    rank, world = _rank_world(group)
+    rank, world = sh.rank_world(group)
     out_dir = Path(output_dir)
     out_dir.mkdir(exist_ok=True, parents=True)
     tf = test_transform_u8(content_size, crop)
@@ -916,6 +894,17 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
 # ---------------------------------------------------------------------------------------------------------------------------------
 # timed job loop (bench.py --job; driven on CPU by tests/test_distributed_gloo.py)
 # ---------------------------------------------------------------------------------------------------------------------------------
+def _max_over_ranks(dt, group, device="cuda"):
+    """The largest ``dt`` of the ranks: on the host when the group has a CPU backend, else on ``device`` (default: the current one)."""
+    if sh.dist_on() and dist.get_world_size(group) > 1:
+        t = torch.tensor([dt], dtype=torch.float64)
+        if "cpu" not in sh.backend_table(group):
+            t = t.to(device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+        dt = float(t.item())
+    return dt
+
+
 def run_timed_jobs(job, steps, warmup, *, barrier, group=None):
     """bench.py's contract around whole jobs: ``warmup`` untimed jobs, ``barrier()``, EXACTLY ``steps`` jobs, ``barrier()``;
     returns (seconds as the MAX over the ranks, the last job's result, per-rank info of the last job).  ``job()`` runs one
@@ -932,13 +921,7 @@ def run_timed_jobs(job, steps, warmup, *, barrier, group=None):
     dt = time.perf_counter() - t0
     if isinstance(info, dict):
         info["t0"], info["t1"] = t0, t0 + dt          # host clock at both ends of the timed region (bench.py's telemetry window)
-    if sh.dist_on() and dist.get_world_size(group) > 1:
-        t = torch.tensor([dt], dtype=torch.float64)
-        if "cpu" not in sh.backend_table(group):
-            t = t.to(info["device"]) if info and "device" in info else t.cuda()
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
-        dt = float(t.item())
-    return dt, res, info
+    return _max_over_ranks(dt, group), res, info
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -971,7 +954,7 @@ def run_timed_steps(step, steps, warmup, *, barrier, block_shape, device, mode="
         raise ValueError(f"gather mode must be one of {GATHER_MODES}, got {mode!r}")
     if steps < 1 or warmup < 0:
         raise ValueError(f"run_timed_steps: steps must be >= 1 and warmup >= 0, got {steps} / {warmup}")
-    rank, world = _rank_world(group)
+    rank, world = sh.rank_world(group)
     gathering = bool(gather) and sh.dist_on()
     b = int(block_shape[0])
     frame = tuple(int(v) for v in block_shape[1:])
@@ -1037,10 +1020,4 @@ def run_timed_steps(step, steps, warmup, *, barrier, block_shape, device, mode="
     info["compute_ms"] = elapsed(m0, m1) * 1e3
     info["gather_ms"] = elapsed(m1, m2) * 1e3
     info["local_s"] = dt
-    if sh.dist_on() and dist.get_world_size(group) > 1:
-        t = torch.tensor([dt], dtype=torch.float64)
-        if "cpu" not in sh.backend_table(group):
-            t = t.to(device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
-        dt = float(t.item())
-    return dt, got[0], info
+    return _max_over_ranks(dt, group, device), got[0], info
