@@ -165,6 +165,11 @@ def save_image(tensor, path):
     The quantisation runs on the GPU (adain_quantize_u8)."""
     if tensor.dim() == 3:
         tensor = tensor.unsqueeze(0)
+    if _device_jpeg_on and _is_jpeg_path(path) and tensor.shape[1] in (1, 3):
+        data, = rt.jpeg_files(*rt.jpeg_encode_u8(rt.quantize_u8(tensor.float()[:1])))
+        with open(str(path), "wb") as f:
+            f.write(data)
+        return
     u8 = rt.quantize_u8(tensor.float()[:1])[0].cpu().numpy()
     Image.fromarray(u8[:, :, 0] if u8.shape[2] == 1 else u8).save(str(path))
 
@@ -248,6 +253,22 @@ def set_latency_schedule(enabled):
     global _latency_schedule_on
     prev, _latency_schedule_on = _latency_schedule_on, bool(enabled)
     return prev
+
+
+_device_jpeg_on = False
+
+
+def set_device_jpeg(enabled):
+    """True: ``adain_inference`` (the cached per-call path and ``save_image``) encodes a ``.jpg`` / ``.jpeg`` output on the device
+    (adain_jpeg_encode_u8: the bytes Pillow's default save writes) and brings over the file instead of the raw frame; any other
+    extension is saved by PIL as before.  Default False.  Returns the previous setting."""
+    global _device_jpeg_on
+    prev, _device_jpeg_on = _device_jpeg_on, bool(enabled)
+    return prev
+
+
+def _is_jpeg_path(path):
+    return str(path).lower().endswith((".jpg", ".jpeg"))
 
 
 def _with_schedule(fn):
@@ -620,6 +641,17 @@ def _one_call(frame, stats, enc, dec, device, alpha, use_depth, depth_map, pil_c
     if T.on:
         e1.record()
         T.events.append((e0, e1))
+    if _device_jpeg_on and _is_jpeg_path(target):
+        encoded = rt.jpeg_encode_u8(u8)
+        T("launch (one C-ABI call)", t0)
+        t0 = time.perf_counter()
+        data, = rt.jpeg_files(*encoded)
+        T("wait for the kernels + download", t0)
+        t0 = time.perf_counter()
+        with open(str(target), "wb") as f:
+            f.write(data)
+        T("encode + write the file", t0)
+        return
     T("launch (one C-ABI call)", t0)
     t0 = time.perf_counter()
     arr = u8[0].cpu().numpy()

@@ -521,6 +521,19 @@ int adain_resize_pil_bilinear_u8(const uint8_t* in, int pixel_bytes, int n, int 
                                          (hipStream_t)stream);
 }
 
+int adain_jpeg_encode_u8_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes) {
+    return jpeg_encode_bytes(n, h, w, c, out_stride, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
+                         size_t workspace_bytes, adain_stream_t stream) {
+    if (!src || !out || !lengths || !workspace) { set_error("jpeg_encode_u8: null pointer"); return ADAIN_EINVAL; }
+    size_t need_stride = 0, need_ws = 0;
+    if (jpeg_encode_bytes(n, h, w, c, &need_stride, &need_ws)) return ADAIN_EINVAL;
+    if (workspace_bytes < need_ws) { set_error("jpeg_encode_u8: workspace too small (%zu < %zu bytes)", workspace_bytes, need_ws); return ADAIN_EINVAL; }
+    const int rc = launch_jpeg_encode_u8(src, n, h, w, c, quality, out, out_stride, lengths, workspace, (hipStream_t)stream);
+    return rc == -1 ? ADAIN_EINVAL : rc;
+}
+
 int adain_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, adain_stream_t stream) {
     if (!in || !out) { set_error("nhwc_to_nchw: null pointer"); return ADAIN_EINVAL; }
     return launch_nhwc_to_nchw(in, out, n, c, hw, (hipStream_t)stream);

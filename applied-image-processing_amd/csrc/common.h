@@ -156,6 +156,11 @@ int launch_tvl1_prepare(const uint8_t* gray, int n, int h, int w, const ::adain_
 int launch_tvl1_flow(const float* const* prev, const float* const* next, int npairs, int h, int w, const ::adain_tvl1_params* p, float* flows, int* iters,
                      void* ws, size_t ws_bytes, hipStream_t s);
 
+// jpeg.hip: baseline JPEG files, byte for byte Pillow's default save (the rules: top of jpeg.hip, tests/jpeg_ref.py)
+int jpeg_encode_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes);
+int launch_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
+                          hipStream_t s);
+
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -1,0 +1,613 @@
+// Baseline JPEG encoder on the device: the file Pillow's default Image.save(f, format="JPEG") writes, byte for byte (libjpeg's
+// integer "islow" DCT, h2v2 chroma, the Annex K quantisation tables scaled by the quality, the Annex K Huffman tables, a JFIF 1.01
+// header).  All arithmetic is int32 / uint64; no floating point; a frame's bytes do not depend on the batch it is in.
+// tests/jpeg_ref.py restates the same rules in NumPy and tests/test_jpeg_host.py holds that restatement to Pillow on the host.
+//
+// The rules
+//   header   FFD8; APP0 "JFIF\0" 1.01, units 0, density 1 x 1, no thumbnail; one DQT per table (8 bit, zigzag order; 0 luma, 1 chroma);
+//            SOF0 (precision 8, h, w, components (1, 0x22, 0) (2, 0x11, 1) (3, 0x11, 1)); DHT DC0, AC0, DC1, AC1; SOS (1, 0x00)
+//            (2, 0x11) (3, 0x11), Ss 0, Se 63, Ah/Al 0.  No DRI.  623 bytes for RGB.  Greyscale: one DQT, component (1, 0x11, 0), DHT
+//            DC0 and AC0, a one-component SOS: 328 bytes.
+//   tables   q = clamp((base * s + 50) / 100, 1, 255) with s = 5000 / quality below 50 and 200 - 2 quality from 50 up.
+//   colour   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16; Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16;
+//            Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+//   padding  luma: edge replication to whole 8 x 8 blocks.  Chroma: the full-resolution planes are replicated to whole MCU columns and
+//            to an EVEN number of rows only, downsampled as (a + b + c + d + bias) >> 2 with bias 1 on even output columns and 2 on odd
+//            ones, and the downsampled rows are then replicated to whole blocks (replicating full-resolution rows further down and
+//            downsampling those gives other bottom rows when the height is even).
+//   dummies  the luma blocks of an MCU that lie outside the ceil(h/8) x ceil(w/8) block grid: all AC zero, the DC of the block before
+//            them in the MCU, so their DC difference is 0.
+//   DCT      jfdctint: CONST_BITS 13, PASS1_BITS 2, rows then columns, output scaled by 8.
+//   quantise sign(c) * ((|c| + (8q >> 1)) / (8q)).
+//   entropy  scan order Y00 Y01 Y10 Y11 Cb Cr per 16 x 16 MCU (greyscale: the blocks row-major); DC prediction per component over the
+//            whole scan; category = bit_length(|v|); a negative value puts v - 1 in the low bits; runs above 15 emit ZRL (0xF0);
+//            trailing zeros emit EOB; the last byte is padded with 1-bits; a 0x00 follows every 0xFF.
+//
+// The stages (8 launches per call, every one over all n frames)
+//   transform  one workgroup per 8 MCUs (greyscale: 32 blocks): the strip goes through LDS with coalesced byte loads, colour conversion
+//              and chroma downsample into per-block planes, the two DCT passes with one lane per row / column, quantisation, and the
+//              zigzag-ordered int16 coefficients leave as one contiguous store
+//   count      one wave64 per block, one lane per coefficient: __ballot gives the non-zero mask, the runs come from bit operations
+//   scan       exclusive scan of the blocks' bit counts per frame (64-bit offsets)
+//   zero       the words of the bit stream the frame will use
+//   emit       each lane ORs its ZRLs, code and value bits into the big-endian bit stream at block offset + in-block prefix; the bits of
+//              different lanes are disjoint, so atomicOr on 32-bit words is order-independent
+//   ffcount / scan / scatter   0xFF bytes per 1024-byte chunk, their scan, and the copy behind the header with a 0x00 after each 0xFF;
+//              the scatter also writes the header, FFD9 and lengths[i]
+#include "common.h"
+
+namespace adain {
+namespace {
+
+constexpr int MCUS_PER_WG = 8;          // RGB: 8 MCUs = 128 x 16 pixels = 48 blocks, 384 threads (one per block row)
+constexpr int GREY_PER_WG = 32;         // L: 32 blocks = 256 x 8 pixels, 256 threads
+constexpr int CHUNK = 1024;             // bytes of entropy-coded data per workgroup pass of the stuffing kernels (one word per thread)
+constexpr int SCAN_THREADS = 1024;
+constexpr int STREAM_GRID = 64;         // workgroups per frame of the grid-stride kernels (zero, ffcount, scatter)
+
+struct Huff {
+    uint16_t dc_code[2][12];
+    uint8_t dc_len[2][12];
+    uint16_t ac_code[2][256];
+    uint8_t ac_len[2][256];
+};
+struct Tables {
+    uint8_t zigzag[64];      // zigzag position -> natural index
+    uint8_t zpos[64];        // natural index -> zigzag position
+    uint8_t qbase[2][64];    // Annex K.1, natural order
+    Huff huff;
+    uint8_t hdr[2][640];     // [0]: greyscale, [1]: RGB; the DQT entries and SOF0's size are left 0
+    int hdr_len[2], dqt[2][2], sof_hw[2];       // offsets of the 64 DQT entries per table and of SOF0's height
+    int max_block_bits;
+};
+
+constexpr uint8_t DC_BITS[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+constexpr uint8_t AC_BITS[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+constexpr uint8_t AC_VALS[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+     0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+     0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+     0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+     0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+     0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+     0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+     0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+     0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+     0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+     0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+     0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa}};
+
+constexpr Tables make_tables() {
+    Tables t{};
+    const uint8_t zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                            35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    const uint8_t ql[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58,  60,  55, 14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                            18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+    const uint8_t qc[32] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99};
+    for (int i = 0; i < 64; ++i) {
+        t.zigzag[i] = zz[i];
+        t.zpos[zz[i]] = (uint8_t)i;
+        t.qbase[0][i] = ql[i];
+        t.qbase[1][i] = i < 32 ? qc[i] : 99;
+    }
+    for (int k = 0; k < 2; ++k) {
+        int code = 0, at = 0;
+        for (int len = 1; len <= 16; ++len) {
+            for (int i = 0; i < DC_BITS[k][len - 1]; ++i, ++at, ++code) { t.huff.dc_code[k][at] = (uint16_t)code; t.huff.dc_len[k][at] = (uint8_t)len; }
+            code <<= 1;
+        }
+        code = 0, at = 0;
+        for (int len = 1; len <= 16; ++len) {
+            for (int i = 0; i < AC_BITS[k][len - 1]; ++i, ++at, ++code) { t.huff.ac_code[k][AC_VALS[k][at]] = (uint16_t)code; t.huff.ac_len[k][AC_VALS[k][at]] = (uint8_t)len; }
+            code <<= 1;
+        }
+    }
+    // the most bits one block can emit: an 11-bit DC difference and 63 AC coefficients of 10 bits, each with the longest code of its kind
+    int dc = 0, ac = 0;
+    for (int k = 0; k < 2; ++k) {
+        for (int s = 0; s < 12; ++s) dc = t.huff.dc_len[k][s] + s > dc ? t.huff.dc_len[k][s] + s : dc;
+        for (int r = 0; r < 16; ++r)
+            for (int s = 1; s <= 10; ++s) ac = t.huff.ac_len[k][r * 16 + s] + s > ac ? t.huff.ac_len[k][r * 16 + s] + s : ac;
+    }
+    t.max_block_bits = dc + 63 * ac;
+    for (int rgb = 0; rgb < 2; ++rgb) {
+        uint8_t* b = t.hdr[rgb];
+        int n = 0;
+        auto put = [&](int v) { b[n++] = (uint8_t)v; };
+        auto seg = [&](int marker, int payload) { put(0xff); put(marker); put((payload + 2) >> 8); put((payload + 2) & 255); };
+        put(0xff); put(0xd8);
+        seg(0xe0, 14);
+        put('J'); put('F'); put('I'); put('F'); put(0); put(1); put(1); put(0); put(0); put(1); put(0); put(1); put(0); put(0);
+        for (int k = 0; k <= rgb; ++k) {
+            seg(0xdb, 65);
+            put(k);
+            t.dqt[rgb][k] = n;
+            n += 64;
+        }
+        seg(0xc0, rgb ? 15 : 9);
+        put(8);
+        t.sof_hw[rgb] = n;
+        n += 4;
+        put(rgb ? 3 : 1);
+        put(1); put(rgb ? 0x22 : 0x11); put(0);
+        if (rgb) { put(2); put(0x11); put(1); put(3); put(0x11); put(1); }
+        for (int k = 0; k <= rgb; ++k) {
+            seg(0xc4, 1 + 16 + 12);
+            put(k);
+            for (int i = 0; i < 16; ++i) put(DC_BITS[k][i]);
+            for (int i = 0; i < 12; ++i) put(i);
+            seg(0xc4, 1 + 16 + 162);
+            put(0x10 | k);
+            for (int i = 0; i < 16; ++i) put(AC_BITS[k][i]);
+            for (int i = 0; i < 162; ++i) put(AC_VALS[k][i]);
+        }
+        seg(0xda, rgb ? 10 : 6);
+        put(rgb ? 3 : 1);
+        put(1); put(0x00);
+        if (rgb) { put(2); put(0x11); put(3); put(0x11); }
+        put(0); put(63); put(0);
+        t.hdr_len[rgb] = n;
+    }
+    return t;
+}
+
+constexpr Tables HOST_T = make_tables();
+static_assert(HOST_T.hdr_len[1] == 623 && HOST_T.max_block_bits == 1660, "the header and the per-block bound of include/adain_hip.h");
+__constant__ const Tables T = make_tables();
+
+// ---- sizes -----------------------------------------------------------------------------------------------------------------------------
+struct Plan {
+    int c, mw, mh, bw, bh;
+    size_t nblk;                  // blocks per frame in scan order, dummy blocks included
+    size_t max_bytes;             // entropy-coded bytes of a frame before stuffing, at most
+    size_t stream_words;          // words of one frame's bit stream
+    size_t chunks;                // CHUNK-byte pieces of max_bytes
+    size_t out_stride;
+    size_t o_coef, o_bits, o_off, o_total, o_stream, o_ffcnt, o_ffoff, o_fftotal, total;      // workspace offsets (bytes) of the n-frame arrays
+};
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+Plan make_plan(int n, int h, int w, int c) {
+    Plan p{};
+    p.c = c;
+    p.bw = (w + 7) / 8, p.bh = (h + 7) / 8;
+    p.mw = (w + 15) / 16, p.mh = (h + 15) / 16;
+    p.nblk = c == 3 ? (size_t)p.mw * p.mh * 6 : (size_t)p.bw * p.bh;
+    p.max_bytes = (p.nblk * HOST_T.max_block_bits + 7) / 8;
+    p.stream_words = (p.max_bytes + 3) / 4 + 4;
+    p.chunks = (p.max_bytes + CHUNK - 1) / CHUNK;
+    p.out_stride = HOST_T.hdr_len[c == 3] + 2 * p.max_bytes + 2;
+    size_t at = 0, N = (size_t)n;
+    auto take = [&](size_t bytes) { size_t o = at; at = align256(at + bytes); return o; };
+    p.o_coef = take(N * p.nblk * 64 * sizeof(int16_t));
+    p.o_bits = take(N * p.nblk * sizeof(uint32_t));
+    p.o_off = take(N * p.nblk * sizeof(uint64_t));
+    p.o_total = take(N * sizeof(uint64_t));
+    p.o_stream = take(N * p.stream_words * sizeof(uint32_t));
+    p.o_ffcnt = take(N * p.chunks * sizeof(uint32_t));
+    p.o_ffoff = take(N * p.chunks * sizeof(uint32_t));
+    p.o_fftotal = take(N * sizeof(uint32_t));
+    p.total = at;
+    return p;
+}
+
+// ---- transform -------------------------------------------------------------------------------------------------------------------------
+// One pass of jfdctint over 8 values p[0], p[S], ...: the first pass keeps PASS1_BITS of extra precision, the second removes them.
+template <int S, bool FIRST>
+__device__ __forceinline__ void fdct_pass(int* p) {
+    constexpr int N = FIRST ? 11 : 15, R = 1 << (N - 1);
+    const int d0 = p[0], d1 = p[S], d2 = p[2 * S], d3 = p[3 * S], d4 = p[4 * S], d5 = p[5 * S], d6 = p[6 * S], d7 = p[7 * S];
+    int t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4;
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    if (FIRST) {
+        p[0] = (t10 + t11) * 4;
+        p[4 * S] = (t10 - t11) * 4;
+    } else {
+        p[0] = (t10 + t11 + 2) >> 2;
+        p[4 * S] = (t10 - t11 + 2) >> 2;
+    }
+    int z1 = (t12 + t13) * 4433;
+    p[2 * S] = (z1 + t13 * 6270 + R) >> N;
+    p[6 * S] = (z1 - t12 * 15137 + R) >> N;
+    z1 = t4 + t7;
+    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const int z5 = (z3 + z4) * 9633;
+    t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299;
+    z1 *= -7373, z2 *= -20995;
+    z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+    p[7 * S] = (t4 + z1 + z3 + R) >> N;
+    p[5 * S] = (t5 + z2 + z4 + R) >> N;
+    p[3 * S] = (t6 + z2 + z3 + R) >> N;
+    p[S] = (t7 + z1 + z4 + R) >> N;
+}
+
+__device__ __forceinline__ int quant_entry(int table, int natural, int quality) {
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    const int q = (T.qbase[table][natural] * s + 50) / 100;
+    return q < 1 ? 1 : q > 255 ? 255 : q;
+}
+
+// The DCT, quantisation and store shared by both layouts.  samp: NB blocks of level-shifted samples, 8 rows of 9 ints (72 per block: a
+// lane per row, then a lane per column, both free of bank conflicts); q8: 8 q of both tables in natural order; zq: NB x 64 int16.
+// Block j of the workgroup uses table table_of(j) and is all zero when dummy_of(j); the first `count` blocks go to dst.
+template <int NB, class TableOf, class DummyOf>
+__device__ __forceinline__ void dct_quantise_store(int* samp, const int* q8, int16_t* zq, int16_t* dst, int count, TableOf table_of, DummyOf dummy_of) {
+    const int t = threadIdx.x, blk = t >> 3, k = t & 7;
+    if (blk < NB) fdct_pass<1, true>(samp + blk * 72 + k * 9);
+    __syncthreads();
+    if (blk < NB) {
+        int* p = samp + blk * 72 + k;
+        fdct_pass<9, false>(p);
+        const int* q = q8 + table_of(blk) * 64;
+        const bool dummy = dummy_of(blk);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int v = p[r * 9], d = q[r * 8 + k];
+            const int m = (int)(((unsigned)(v < 0 ? -v : v) + (unsigned)(d >> 1)) / (unsigned)d);
+            zq[blk * 64 + T.zpos[r * 8 + k]] = dummy ? (int16_t)0 : (int16_t)(v < 0 ? -m : m);
+        }
+    }
+    __syncthreads();
+    uint32_t* d32 = (uint32_t*)dst;               // block starts are 128-byte aligned in the workspace
+    const uint32_t* s32 = (const uint32_t*)zq;
+    for (int i = t; i < count * 32; i += blockDim.x) d32[i] = s32[i];
+}
+
+__global__ __launch_bounds__(MCUS_PER_WG * 48) void jpeg_transform_rgb_kernel(const uint8_t* __restrict__ src, int h, int w, int quality, int16_t* __restrict__ coef,
+                                                                              int mw, int bw, int bh, size_t nblk) {
+    constexpr int NB = MCUS_PER_WG * 6, PX = MCUS_PER_WG * 16, THREADS = MCUS_PER_WG * 48;
+    __shared__ uint8_t raw[16 * PX * 3];
+    __shared__ int samp[NB * 72];
+    __shared__ int q8[128];
+    __shared__ __attribute__((aligned(16))) int16_t zq[NB * 64];
+    const int t = threadIdx.x, my = blockIdx.y, mx0 = blockIdx.x * MCUS_PER_WG;
+    const uint8_t* img = src + (size_t)blockIdx.z * h * w * 3;
+    if (t < 128) q8[t] = 8 * quant_entry(t >> 6, t & 63, quality);
+    for (int i = t; i < 16 * PX * 3; i += THREADS) {
+        const int r = i / (PX * 3), j = i - r * (PX * 3), px = j / 3, ch = j - px * 3;
+        const int gy = min(my * 16 + r, h - 1), gx = min(mx0 * 16 + px, w - 1);
+        raw[i] = img[((size_t)gy * w + gx) * 3 + ch];
+    }
+    __syncthreads();
+    const int ch2 = (h + 1) >> 1;
+    for (int i = t; i < 16 * PX + 2 * 8 * (PX / 2); i += THREADS) {
+        if (i < 16 * PX) {
+            const int r = i / PX, c = i - r * PX;
+            const uint8_t* p = raw + r * (PX * 3) + c * 3;
+            const int y = (19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 32768) >> 16;
+            samp[((c >> 4) * 6 + ((r >> 3) << 1) + ((c >> 3) & 1)) * 72 + (r & 7) * 9 + (c & 7)] = y - 128;
+        } else {
+            const int j = i - 16 * PX, comp = j / (8 * (PX / 2)), jj = j - comp * (8 * (PX / 2)), crow = jj / (PX / 2), cc = jj - crow * (PX / 2);
+            const int lr = min(my * 8 + crow, ch2 - 1) - my * 8;          // the downsampled ROW is what is replicated below the image
+            int sum = 1 + (cc & 1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint8_t* p = raw + (2 * lr + (k >> 1)) * (PX * 3) + (2 * cc + (k & 1)) * 3;
+                sum += comp == 0 ? (-11059 * p[0] - 21709 * p[1] + 32768 * p[2] + (128 << 16) + 32767) >> 16
+                                 : (32768 * p[0] - 27439 * p[1] - 5329 * p[2] + (128 << 16) + 32767) >> 16;
+            }
+            samp[((cc >> 3) * 6 + 4 + comp) * 72 + crow * 9 + (cc & 7)] = (sum >> 2) - 128;
+        }
+    }
+    __syncthreads();
+    const int count = min(MCUS_PER_WG, mw - mx0) * 6;
+    int16_t* dst = coef + ((size_t)blockIdx.z * nblk + ((size_t)my * mw + mx0) * 6) * 64;
+    dct_quantise_store<NB>(samp, q8, zq, dst, count, [](int j) { return j % 6 >= 4 ? 1 : 0; },
+                           [&](int j) { const int m = j / 6, k = j - m * 6; return k < 4 && !(2 * (mx0 + m) + (k & 1) < bw && 2 * my + (k >> 1) < bh); });
+}
+
+__global__ __launch_bounds__(GREY_PER_WG * 8) void jpeg_transform_grey_kernel(const uint8_t* __restrict__ src, int h, int w, int quality, int16_t* __restrict__ coef,
+                                                                              int bw, size_t nblk) {
+    constexpr int NB = GREY_PER_WG, PX = NB * 8, THREADS = NB * 8;
+    __shared__ int samp[NB * 72];
+    __shared__ int q8[128];
+    __shared__ __attribute__((aligned(16))) int16_t zq[NB * 64];
+    const int t = threadIdx.x, by = blockIdx.y, bx0 = blockIdx.x * NB;
+    const uint8_t* img = src + (size_t)blockIdx.z * h * w;
+    if (t < 128) q8[t] = 8 * quant_entry(t >> 6, t & 63, quality);
+    for (int i = t; i < 8 * PX; i += THREADS) {
+        const int r = i / PX, c = i - r * PX;
+        const int gy = min(by * 8 + r, h - 1), gx = min(bx0 * 8 + c, w - 1);
+        samp[(c >> 3) * 72 + r * 9 + (c & 7)] = (int)img[(size_t)gy * w + gx] - 128;
+    }
+    __syncthreads();
+    int16_t* dst = coef + ((size_t)blockIdx.z * nblk + (size_t)by * bw + bx0) * 64;
+    dct_quantise_store<NB>(samp, q8, zq, dst, min(NB, bw - bx0), [](int) { return 0; }, [](int) { return false; });
+}
+
+// ---- entropy coding: one wave64 per block, one lane per coefficient ------------------------------------------------------------------------
+struct Geometry {
+    int c, mw, bw, bh;
+    size_t nblk;
+};
+
+__device__ __forceinline__ bool luma_is_real(const Geometry& g, int mx, int my, int k) { return 2 * mx + (k & 1) < g.bw && 2 * my + (k >> 1) < g.bh; }
+
+// The DC difference of block b of a frame (wave-uniform).  The predictor of a real luma block is the last real block before it in the
+// scan: the dummy blocks in between carry that block's DC.
+__device__ int dc_difference(const int16_t* __restrict__ coef, size_t b, const Geometry& g, int* table) {
+    *table = 0;
+    if (g.c != 3) return coef[b * 64] - (b ? coef[(b - 1) * 64] : 0);
+    size_t m = b / 6;
+    int k = (int)(b - m * 6);
+    if (k >= 4) {
+        *table = 1;
+        return coef[b * 64] - (m ? coef[((m - 1) * 6 + k) * 64] : 0);
+    }
+    if (!luma_is_real(g, (int)(m % g.mw), (int)(m / g.mw), k)) return 0;
+    const int dc = coef[b * 64];
+    if (k == 0) {
+        if (m == 0) return dc;
+        --m, k = 3;
+    } else {
+        --k;
+    }
+    const int mx = (int)(m % g.mw), my = (int)(m / g.mw);
+    while (!luma_is_real(g, mx, my, k)) --k;      // block 0 of an MCU is always real
+    return dc - coef[(m * 6 + k) * 64];
+}
+
+// What this lane puts into the stream: the ZRLs of its run, its code and its value bits, and the EOB when it is the last coded
+// coefficient of a block that does not end at 63; right-aligned in *pattern.  Returns the number of bits (at most 63; 0: a zero).
+__device__ __forceinline__ int lane_bits(int lane, int v, int table, uint64_t* pattern) {
+    const uint64_t mask = __ballot(v != 0) | 1ull;        // the DC always codes
+    if (!((mask >> lane) & 1)) { *pattern = 0; return 0; }
+    const int a = v < 0 ? -v : v;
+    const int size = 32 - __clz(a);
+    const uint32_t value = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << size) - 1);
+    uint64_t pat = 0;
+    int len = 0;
+    if (lane == 0) {
+        pat = T.huff.dc_code[table][size], len = T.huff.dc_len[table][size];
+    } else {
+        const int prev = 63 - __clzll((long long)(mask & ((1ull << lane) - 1)));
+        const int run = lane - prev - 1;
+        const int zc = T.huff.ac_code[table][0xf0], zl = T.huff.ac_len[table][0xf0];
+        for (int k = 0; k < (run >> 4); ++k) pat = (pat << zl) | zc, len += zl;
+        const int sym = ((run & 15) << 4) | size;
+        const int cl = T.huff.ac_len[table][sym];
+        pat = (pat << cl) | T.huff.ac_code[table][sym], len += cl;
+    }
+    pat = (pat << size) | value, len += size;
+    if (lane < 63 && lane == 63 - __clzll((long long)mask)) {
+        const int el = T.huff.ac_len[table][0];
+        pat = (pat << el) | T.huff.ac_code[table][0], len += el;
+    }
+    *pattern = pat;
+    return len;
+}
+
+__global__ __launch_bounds__(256) void jpeg_count_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ bits, Geometry g, size_t total_blocks) {
+    const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= total_blocks) return;
+    const int lane = threadIdx.x & 63;
+    const size_t f = gw / g.nblk, b = gw - f * g.nblk;
+    const int16_t* fc = coef + f * g.nblk * 64;
+    int table;
+    const int diff = dc_difference(fc, b, g, &table);
+    const int v = lane == 0 ? diff : fc[b * 64 + lane];
+    uint64_t pat;
+    int len = lane_bits(lane, v, table, &pat);
+    for (int d = 32; d >= 1; d >>= 1) len += __shfl_xor(len, d);
+    if (lane == 0) bits[gw] = (uint32_t)len;
+}
+
+__global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restrict__ coef, const uint64_t* __restrict__ off, uint32_t* __restrict__ stream,
+                                                        size_t stream_words, Geometry g, size_t total_blocks) {
+    const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= total_blocks) return;
+    const int lane = threadIdx.x & 63;
+    const size_t f = gw / g.nblk, b = gw - f * g.nblk;
+    const int16_t* fc = coef + f * g.nblk * 64;
+    int table;
+    const int diff = dc_difference(fc, b, g, &table);
+    const int v = lane == 0 ? diff : fc[b * 64 + lane];
+    uint64_t pat;
+    const int len = lane_bits(lane, v, table, &pat);
+    int incl = len;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
+    }
+    if (len == 0) return;
+    const uint64_t pos = off[gw] + (uint64_t)(incl - len);
+    uint32_t* word = stream + f * stream_words + (size_t)(pos >> 5);
+    const int o = (int)(pos & 31);
+    const uint64_t hi = pat << (64 - len);                // left-aligned; the 96-bit window starting at the word is hi >> o
+    const uint32_t w0 = (uint32_t)((hi >> 32) >> o), w1 = (uint32_t)(hi >> o), w2 = o ? (uint32_t)hi << (32 - o) : 0u;
+    // a word is touched only where this lane has bits in it: never beyond the frame's last coded bit
+    if (w0) atomicOr(word, w0);
+    if (w1) atomicOr(word + 1, w1);
+    if (w2) atomicOr(word + 2, w2);
+}
+
+// ---- scans: one workgroup per frame ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ size_t stream_bytes(uint64_t bits) { return (size_t)((bits + 7) >> 3); }
+__device__ __forceinline__ size_t stream_chunks(uint64_t bits) { return (stream_bytes(bits) + CHUNK - 1) / CHUNK; }
+
+// out[i] = in[0] + ... + in[i - 1] over a frame's `count` entries (count_bits != nullptr: the chunks of that many coded bits), the sum to total[frame]
+template <class In, class Out>
+__global__ __launch_bounds__(SCAN_THREADS) void jpeg_scan_kernel(const In* __restrict__ in, Out* __restrict__ out, Out* __restrict__ total, size_t stride, size_t count,
+                                                                 const uint64_t* __restrict__ count_bits) {
+    __shared__ Out part[SCAN_THREADS];
+    const int t = threadIdx.x;
+    const size_t f = blockIdx.x;
+    if (count_bits) count = stream_chunks(count_bits[f]);
+    in += f * stride, out += f * stride;
+    const size_t per = (count + SCAN_THREADS - 1) / SCAN_THREADS;
+    const size_t a = min((size_t)t * per, count), b = min(a + per, count);
+    Out sum = 0;
+    for (size_t i = a; i < b; ++i) sum += in[i];
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < SCAN_THREADS; d <<= 1) {
+        const Out add = t >= d ? part[t - d] : (Out)0;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    Out run = part[t] - sum;
+    for (size_t i = a; i < b; ++i) {
+        const Out v = in[i];
+        out[i] = run;
+        run += v;
+    }
+    if (t == SCAN_THREADS - 1) total[f] = part[t];
+}
+
+__global__ __launch_bounds__(256) void jpeg_zero_kernel(uint32_t* __restrict__ stream, size_t stream_words, const uint64_t* __restrict__ total_bits) {
+    const size_t f = blockIdx.y;
+    const size_t words = (size_t)((total_bits[f] + 31) >> 5) + 2;           // <= stream_words: the plan keeps 4 beyond the bound
+    uint32_t* s = stream + f * stream_words;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) s[i] = 0;
+}
+
+// ---- byte stuffing -------------------------------------------------------------------------------------------------------------------------
+// Word i of a frame's stream as its four bytes in file order (the first in the top byte), the 1-bit padding of the last byte applied;
+// *valid = how many of them are part of the stream.
+__device__ __forceinline__ uint32_t stream_word(const uint32_t* __restrict__ s, size_t i, uint64_t bits, int* valid) {
+    const size_t nbytes = stream_bytes(bits);
+    if (i * 4 >= nbytes) { *valid = 0; return 0; }
+    uint32_t v = s[i];
+    *valid = (int)min((size_t)4, nbytes - i * 4);
+    if (i == (nbytes - 1) >> 2) {
+        const int pad = (int)(nbytes * 8 - bits);
+        v |= ((1u << pad) - 1) << (24 - 8 * (int)((nbytes - 1) & 3));
+    }
+    return v;
+}
+
+__device__ __forceinline__ int count_ff(uint32_t v, int valid) {
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c += (k < valid && ((v >> (24 - 8 * k)) & 255) == 255) ? 1 : 0;
+    return c;
+}
+
+// inclusive sum over the 256 threads of a workgroup; part: 4 ints of LDS
+__device__ __forceinline__ int workgroup_inclusive(int v, int* part) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(v, d);
+        if (lane >= d) v += up;
+    }
+    __syncthreads();                                   // the previous pass has read part
+    if (lane == 63) part[wv] = v;
+    __syncthreads();
+    for (int k = 0; k < wv; ++k) v += part[k];
+    return v;
+}
+
+__global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const uint32_t* __restrict__ stream, size_t stream_words, const uint64_t* __restrict__ total_bits,
+                                                           uint32_t* __restrict__ ffcnt, size_t chunks) {
+    __shared__ int part[4];
+    const size_t f = blockIdx.y;
+    const uint64_t bits = total_bits[f];
+    const uint32_t* s = stream + f * stream_words;
+    for (size_t ck = blockIdx.x; ck < stream_chunks(bits); ck += gridDim.x) {
+        int valid;
+        const uint32_t v = stream_word(s, ck * (CHUNK / 4) + threadIdx.x, bits, &valid);
+        const int incl = workgroup_inclusive(count_ff(v, valid), part);
+        if (threadIdx.x == 255) ffcnt[f * chunks + ck] = (uint32_t)incl;
+    }
+}
+
+__global__ __launch_bounds__(256) void jpeg_scatter_kernel(const uint32_t* __restrict__ stream, size_t stream_words, const uint64_t* __restrict__ total_bits,
+                                                           const uint32_t* __restrict__ ffoff, const uint32_t* __restrict__ fftotal, size_t chunks, int h, int w,
+                                                           int rgb, int quality, uint8_t* __restrict__ out, size_t out_stride, int32_t* __restrict__ lengths) {
+    __shared__ int part[4];
+    const size_t f = blockIdx.y;
+    const uint64_t bits = total_bits[f];
+    const uint32_t* s = stream + f * stream_words;
+    uint8_t* file = out + f * out_stride;
+    const int hdr = T.hdr_len[rgb];
+    if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < hdr; i += 256) {
+            int v = T.hdr[rgb][i];
+            for (int k = 0; k <= rgb; ++k)
+                if (i >= T.dqt[rgb][k] && i < T.dqt[rgb][k] + 64) v = quant_entry(k, T.zigzag[i - T.dqt[rgb][k]], quality);
+            const int j = i - T.sof_hw[rgb];
+            if (j >= 0 && j < 4) v = j == 0 ? h >> 8 : j == 1 ? h & 255 : j == 2 ? w >> 8 : w & 255;
+            file[i] = (uint8_t)v;
+        }
+        if (threadIdx.x == 0) {
+            const size_t end = hdr + stream_bytes(bits) + fftotal[f];
+            file[end] = 0xff, file[end + 1] = 0xd9;
+            lengths[f] = (int32_t)(end + 2);
+        }
+    }
+    for (size_t ck = blockIdx.x; ck < stream_chunks(bits); ck += gridDim.x) {
+        int valid;
+        const uint32_t v = stream_word(s, ck * (CHUNK / 4) + threadIdx.x, bits, &valid);
+        const int c = count_ff(v, valid);
+        const int before = workgroup_inclusive(c, part) - c;
+        uint8_t* d = file + hdr + ck * CHUNK + ffoff[f * chunks + ck] + threadIdx.x * 4 + before;
+        for (int k = 0; k < valid; ++k) {
+            const uint8_t byte = (uint8_t)(v >> (24 - 8 * k));
+            *d++ = byte;
+            if (byte == 255) *d++ = 0;
+        }
+    }
+}
+
+const char* check_shape(int n, int h, int w, int c, int quality) {
+    if (n < 1) return "n < 1";
+    if (c != 1 && c != 3) return "channels other than 1 (L) and 3 (RGB)";
+    if (h < 1 || h > 65535 || w < 1 || w > 65535) return "height or width outside 1..65535";
+    if (quality < 1 || quality > 100) return "quality outside 1..100";
+    return nullptr;
+}
+
+}  // namespace
+
+int jpeg_encode_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes) {
+    const char* bad = check_shape(n, h, w, c, 75);
+    if (!bad && make_plan(n, h, w, c).out_stride > (size_t)INT32_MAX) bad = "a worst-case file beyond 2^31 - 1 bytes (lengths are int32)";
+    if (bad) { set_error("jpeg_encode_u8: %s (n %d, %d x %d x %d)", bad, n, h, w, c); return -1; }
+    const Plan p = make_plan(n, h, w, c);
+    if (out_stride) *out_stride = p.out_stride;
+    if (workspace_bytes) *workspace_bytes = p.total;
+    return 0;
+}
+
+int launch_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
+                          hipStream_t s) {
+    const char* bad = check_shape(n, h, w, c, quality);
+    if (bad) { set_error("jpeg_encode_u8: %s (n %d, %d x %d x %d, quality %d)", bad, n, h, w, c, quality); return -1; }
+    const Plan p = make_plan(n, h, w, c);
+    if (p.out_stride > (size_t)INT32_MAX) { set_error("jpeg_encode_u8: %d x %d x %d: a worst-case file beyond 2^31 - 1 bytes", h, w, c); return -1; }
+    if (out_stride < p.out_stride) { set_error("jpeg_encode_u8: out_stride %zu below the %zu of adain_jpeg_encode_u8_bytes", out_stride, p.out_stride); return -1; }
+    if ((uintptr_t)workspace % 8 || (uintptr_t)lengths % 4) { set_error("jpeg_encode_u8: the workspace must be 8-byte and lengths 4-byte aligned"); return -1; }
+    char* ws = (char*)workspace;
+    int16_t* coef = (int16_t*)(ws + p.o_coef);
+    uint32_t* bits = (uint32_t*)(ws + p.o_bits);
+    uint64_t* off = (uint64_t*)(ws + p.o_off);
+    uint64_t* total = (uint64_t*)(ws + p.o_total);
+    uint32_t* stream = (uint32_t*)(ws + p.o_stream);
+    uint32_t* ffcnt = (uint32_t*)(ws + p.o_ffcnt);
+    uint32_t* ffoff = (uint32_t*)(ws + p.o_ffoff);
+    uint32_t* fftotal = (uint32_t*)(ws + p.o_fftotal);
+    const Geometry g{c, p.mw, p.bw, p.bh, p.nblk};
+    const size_t blocks = (size_t)n * p.nblk;
+    // gridDim.y and .z are limited to 65535: h, w <= 65535 keep the block rows below that; the frames ride in z
+    if (n > 65535 || (blocks + 3) / 4 > 0x7fffffffull) { set_error("jpeg_encode_u8: batch of %d frames too large for one call", n); return -1; }
+    if (c == 3)
+        jpeg_transform_rgb_kernel<<<dim3((p.mw + MCUS_PER_WG - 1) / MCUS_PER_WG, p.mh, n), MCUS_PER_WG * 48, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.bh, p.nblk);
+    else
+        jpeg_transform_grey_kernel<<<dim3((p.bw + GREY_PER_WG - 1) / GREY_PER_WG, p.bh, n), GREY_PER_WG * 8, 0, s>>>(src, h, w, quality, coef, p.bw, p.nblk);
+    jpeg_count_kernel<<<(unsigned)((blocks + 3) / 4), 256, 0, s>>>(coef, bits, g, blocks);
+    jpeg_scan_kernel<uint32_t, uint64_t><<<n, SCAN_THREADS, 0, s>>>(bits, off, total, p.nblk, p.nblk, nullptr);
+    jpeg_zero_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total);
+    jpeg_emit_kernel<<<(unsigned)((blocks + 3) / 4), 256, 0, s>>>(coef, off, stream, p.stream_words, g, blocks);
+    jpeg_ffcount_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffcnt, p.chunks);
+    jpeg_scan_kernel<uint32_t, uint32_t><<<n, SCAN_THREADS, 0, s>>>(ffcnt, ffoff, fftotal, p.chunks, 0, total);
+    jpeg_scatter_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffoff, fftotal, p.chunks, h, w, c == 3, quality, out, out_stride, lengths);
+    return check_launch("jpeg_encode_u8");
+}
+
+}  // namespace adain

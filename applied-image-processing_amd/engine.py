@@ -136,6 +136,11 @@ class AdaINEngine:
         """One step of the video recurrence: blend(cur, warp(prev, flow), alpha) on uint8 HWC frames (video/utils.py:89-105, :223-229)."""
         return rt.warp_blend_u8(cur, prev, flow, alpha)
 
+    def jpeg_encode_u8(self, frames_u8, quality=rt.JPEG_DEFAULT_QUALITY):
+        """The files ``PIL.Image.fromarray(frame).save(f, format="JPEG", quality=quality)`` writes for uint8 frames [n,h,w,3|1] on the
+        device, encoded there (adain_jpeg_encode_u8) -> a list of n ``bytes``; only the files cross to the host."""
+        return rt.jpeg_files(*rt.jpeg_encode_u8(frames_u8, quality))
+
     def colour_transfer_u8(self, fg, bg, out=None):
         """The localized pipeline's foreground colour transfer (localized_style_transfer.py:128-168) on uint8 HWC images -> (adjusted
         foreground, device record); see ``runtime.colour_transfer_u8``."""

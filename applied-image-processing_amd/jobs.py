@@ -427,10 +427,17 @@ class HostCopier:
 class FileSink:
     """Writes finished uint8 frames to image files off the compute path: the device -> host copy of a sub-batch runs on its own
     stream into a pinned buffer, a worker thread waits for it and encodes / saves the files (PIL), so the next sub-batch's
-    kernels are already running.  ``close()`` waits for every file and re-raises the first error."""
+    kernels are already running.  ``close()`` waits for every file and re-raises the first error.  ``jpeg_on_device`` (default off):
+    a block whose paths all end in .jpg / .jpeg is encoded on the compute stream (adain_jpeg_encode_u8: the bytes PIL would write);
+    the copy stream then brings over the lengths and, on a second stream of the sink's own, exactly that many bytes per frame, and the
+    worker only writes them.  (The files do not ride on the lengths' stream: by the time a worker knows its lengths, the launching
+    thread may have queued later blocks' length copies there, each waiting for later kernels.)"""
 
-    def __init__(self, device, workers=4, max_in_flight=None):
+    def __init__(self, device, workers=4, max_in_flight=None, jpeg_on_device=False):
         self.copier = HostCopier(device)
+        self.jpeg_on_device = bool(jpeg_on_device)
+        self.file_stream = torch.cuda.Stream(self.copier.device) if self.jpeg_on_device and self.copier.cuda else None
+        self.file_bytes = 0                # bytes of encoded files the workers copied (under spare_lock)
         self.pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="adain-file-sink")
         self.futures = []
         # back-pressure: at most `max_in_flight` blocks (default 2 per writer) sit in pinned memory waiting for their encoder;
@@ -443,7 +450,8 @@ class FileSink:
 
     @property
     def d2h_bytes(self):
-        return self.copier.bytes
+        with self.spare_lock:
+            return self.copier.bytes + self.file_bytes
 
     def _pinned(self, shape):
         with self.spare_lock:
@@ -458,11 +466,63 @@ class FileSink:
 
         Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr).save(str(path))
 
+    def _encodes(self, u8_block, paths):
+        return (self.jpeg_on_device and self.copier.cuda and u8_block.is_cuda and u8_block.dtype == torch.uint8 and u8_block.dim() == 4
+                and u8_block.shape[3] in (1, 3) and len(paths) > 0 and all(str(p).lower().endswith((".jpg", ".jpeg")) for p in paths))
+
+    def _write_encoded(self, u8_block, paths):
+        """The device-encode form of ``write``: the encode on the current stream, the lengths behind it on the copy stream; the worker
+        waits for them, copies each frame's ``lengths[i]`` bytes into one pinned buffer on the copy stream and writes the files."""
+        from . import runtime as rt
+
+        files, lengths = rt.jpeg_encode_u8(u8_block)
+        k = len(paths)
+        lengths_host = torch.empty((k,), dtype=torch.int32, pin_memory=True)
+        have_lengths = self.copier.copy(lengths_host, lengths)
+        stream = self.file_stream          # the encode has finished once the lengths are here: nothing else to wait for
+
+        def job():
+            host = None
+            try:
+                sleep_wait(have_lengths)
+                sizes = lengths_host.tolist()
+                capacity = 1 << max(12, (sum(sizes) - 1).bit_length())       # pinned buffers are pooled by power-of-two size
+                host = self._pinned((capacity,))
+                with torch.cuda.stream(stream):
+                    at = 0
+                    for i, size in enumerate(sizes):
+                        host[at:at + size].copy_(files[i, :size], non_blocking=True)
+                        at += size
+                    files.record_stream(stream)
+                    done = _event(self.copier.device, stream)
+                with self.spare_lock:
+                    self.file_bytes += at
+                sleep_wait(done)
+                arr = host.numpy()
+                at = 0
+                for size, p in zip(sizes, paths):
+                    with open(str(p), "wb") as f:
+                        f.write(arr[at:at + size].tobytes())
+                    at += size
+            finally:
+                if host is not None:
+                    with self.spare_lock:
+                        self.spare.setdefault(tuple(host.shape), []).append(host)
+                self.slots.release()
+
+        self.futures.append(self.pool.submit(job))
+
     def write(self, u8_block, paths):
         """u8_block [k,h,w,c] on the engine's device (finished on the current stream); paths: k file paths."""
         t0 = time.perf_counter()
         self.slots.acquire()
         self.wait_s += time.perf_counter() - t0
+        if self._encodes(u8_block, paths):
+            try:
+                return self._write_encoded(u8_block.contiguous(), paths)
+            except BaseException:
+                self.slots.release()
+                raise
         shape = tuple(u8_block.shape)
         if not self.copier.cuda:
             host, done = u8_block, None
@@ -818,7 +878,7 @@ def video_style_transfer_sharded(engine, frames, styles, *, flows=None, target_r
 
 def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=None, content_size=512, crop=False, alpha=0.5,
                               depth_maps=None, depth_offset=0.5, depth_prominence=20, save_ext=".jpg", sub_batch=None, group=None,
-                              dst=0, write="dst", require_transport=None, writers=4):
+                              dst=0, write="dst", require_transport=None, writers=4, jpeg_on_device=False):
     """The guide-image precompute of the reference's Style_3DGS/train.py:86-115 over all training views, sharded: every view
     is resized as ``adain_inference(content_size=...)`` resizes it (test.py:190-200), stylised, composited with its mask
     (``gt_image_np > 0``, train.py:97) and saved as ``<output_dir>/<name><save_ext>`` — the reference's naming, so the guide
@@ -826,7 +886,8 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
     writes every file (views must then share one size); ``write="local"``: every rank writes its own block as it is
     finished — nothing is gathered and the views may have any mix of sizes.  The views are decoded / resized on a worker
     thread ahead of the kernels and travel to the device as uint8; the files are encoded and written by ``writers`` threads
-    behind them.  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
+    behind them.  ``jpeg_on_device``: .jpg / .jpeg guides are encoded on the device and only the files cross to the host (FileSink;
+    the same bytes).  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
     from PIL import Image
 
     from .AdaIN.test import device_transform_u8, test_transform_u8
@@ -857,7 +918,7 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
     on_gpu = torch.device(engine.device).type == "cuda"
     names = list(names)
     paths = {nm: out_dir / f"{nm}{save_ext}" for nm in names}
-    sink = FileSink(engine.device, workers=writers)
+    sink = FileSink(engine.device, workers=writers, jpeg_on_device=jpeg_on_device)
     err = None
     info = {}
     try:
@@ -882,6 +943,7 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
         err = err or e
     info["write_s"] = time.perf_counter() - t0
     info["d2h_bytes"] = sink.d2h_bytes
+    info["sink_wait_s"] = sink.wait_s
     # every file exists when any rank returns - or every rank raises
     all_ok = sh.agree(err is None, group, engine.device)
     if err is not None:

@@ -7,13 +7,15 @@ It calls ``localized.run_localized_style_transfer`` (reference Style_3DGS/locali
 ``adain_inference(content_mask=..., alpha=1)`` on the MI355X kernels -> Reinhard / PCA / CDF colour transfer of the foreground ->
 composite.  Extra flags make it usable offline (the reference downloads DeepLabV3 and MiDaS at run time): ``--mask_npy`` takes a
 precomputed background mask ([1,H,W] or [H,W], 1 = background), ``--depth_npy`` a proximity map, ``--vgg`` / ``--decoder`` the
-checkpoint paths, ``--colour_on_device`` moves the colour transfer and the composite to the GPU.  Without ``--mask_npy`` a provider must have been registered (``localized.set_mask_provider``).
+checkpoint paths, ``--colour_on_device`` moves the colour transfer and the composite to the GPU, ``--jpeg_on_device`` the JPEG encode of the intermediate
+stylised file (the same bytes; the final composite is still saved by PIL).  Without ``--mask_npy`` a provider must have been registered (``localized.set_mask_provider``).
 """
 import argparse
 
 import numpy as np
 import torch
 
+from .AdaIN.test import set_device_jpeg
 from .localized import run_localized_style_transfer
 
 # (flag, argparse keyword arguments) - names and defaults as in the reference CLI
@@ -30,6 +32,7 @@ _EXTRA_FLAGS = (
     ("--vgg", dict(type=str, default="Style_3DGS/AdaIN/models/vgg_normalised.pth", help="encoder state_dict")),
     ("--decoder", dict(type=str, default="Style_3DGS/AdaIN/models/decoder.pth", help="decoder state_dict")),
     ("--colour_on_device", dict(action="store_true", help="run the foreground colour transfer and the composite on the GPU instead of in numpy")),
+    ("--jpeg_on_device", dict(action="store_true", help="encode the intermediate stylised JPEG on the GPU instead of in PIL (byte-identical file)")),
 )
 
 
@@ -45,8 +48,12 @@ def main(argv=None):
     extra = dict(vgg_str=ns.vgg, decoder_str=ns.decoder)
     if ns.depth_npy:
         extra["depth_map"] = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
-    return run_localized_style_transfer(content_img_path=ns.content, style_img_path=ns.style, output_path=ns.output, file_name=ns.file_name,
-                                        use_depth=ns.use_depth, background_mask=mask, colour_on_device=ns.colour_on_device, **extra)
+    prev = set_device_jpeg(ns.jpeg_on_device)
+    try:
+        return run_localized_style_transfer(content_img_path=ns.content, style_img_path=ns.style, output_path=ns.output, file_name=ns.file_name,
+                                            use_depth=ns.use_depth, background_mask=mask, colour_on_device=ns.colour_on_device, **extra)
+    finally:
+        set_device_jpeg(prev)
 
 
 if __name__ == "__main__":

@@ -83,6 +83,8 @@ SIGNATURES = {
     "adain_stylize_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_float, _c_float, _PP,
                                   ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), _c_float, _c_float, _c_void_p, _c_int, _c_int, _c_int, _c_int,
                                   _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_jpeg_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
+    "adain_jpeg_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_nhwc_to_nchw": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_nchw_to_nhwc": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_conv3x3_wino4_packed_floats": (_c_size_t, [_c_int, _c_int]),
@@ -660,6 +662,51 @@ def resize_pil_bilinear_u8(frames, size, crop=None, out=None):
         _check(lib().adain_resize_pil_bilinear_u8(x.data_ptr(), pix, n, hi, wi, out.data_ptr(), ho, wo, y0, x0, ch, cw, ws.data_ptr(), ws.numel(),
                                                   _stream()), "adain_resize_pil_bilinear_u8")
     return out
+
+
+# --- output files (adain_jpeg_encode_u8) ---------------------------------------------------------------------------------------------
+JPEG_DEFAULT_QUALITY = 75          # Pillow's
+
+
+def jpeg_encode_sizes(n, h, w, c):
+    """(out_stride, workspace_bytes) of adain_jpeg_encode_u8_bytes: the largest file a frame of this shape can have and the scratch
+    of an n-frame call.  Host only.  AdainHipError for a refused shape."""
+    stride, ws = _c_size_t(), _c_size_t()
+    rc = lib().adain_jpeg_encode_u8_bytes(int(n), int(h), int(w), int(c), ctypes.byref(stride), ctypes.byref(ws))
+    if rc != 0:
+        raise AdainHipError(f"adain_jpeg_encode_u8_bytes failed ({rc}): {lib().adain_last_error().decode()}")
+    return stride.value, ws.value
+
+
+def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY):
+    """Frames uint8 [n,h,w,c] (c = 3: RGB, 1: L; or one frame [h,w,c] / [h,w]) -> (files uint8 [n, stride], lengths int32 [n]), both on the
+    device: row i starts with frame i's JPEG file, ``lengths[i]`` bytes, byte for byte what ``PIL.Image.fromarray(frame).save(f,
+    format="JPEG", quality=quality)`` writes; the rest of the row is not written.  Nothing is copied to the host and nothing waits."""
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise AdainHipError(f"jpeg_encode_u8: quality must be an int in 1..100, got {quality!r}")
+    x = _dev(u8, "frames", torch.uint8)
+    if x.dim() == 2:
+        x = x[None, :, :, None]
+    elif x.dim() == 3:
+        x = x[None]
+    if x.dim() != 4 or x.shape[3] not in (1, 3) or x.shape[0] < 1:
+        raise AdainHipError(f"jpeg_encode_u8: expected uint8 [n,h,w,3|1], [h,w,3|1] or [h,w], got {tuple(u8.shape)}")
+    n, h, w, c = x.shape
+    stride, nbytes = jpeg_encode_sizes(n, h, w, c)
+    out = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
+    lengths = torch.empty((n,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = workspace(x.device, "jpeg", nbytes)
+        _check(lib().adain_jpeg_encode_u8(x.data_ptr(), n, h, w, c, quality, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _stream()), "adain_jpeg_encode_u8")
+    return out, lengths
+
+
+def jpeg_files(out, lengths):
+    """The files of a ``jpeg_encode_u8`` result as a list of ``bytes``: the lengths first, then exactly that many bytes per frame (waits for
+    the device)."""
+    ln = lengths.cpu().tolist()
+    return [out[i, :k].cpu().numpy().tobytes() for i, k in enumerate(ln)]
 
 
 def nhwc_to_nchw(x):

@@ -152,7 +152,7 @@ def _jpeg_roundtrip(u8):
 
 
 def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group):
+         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device=False):
     from . import sharding as sh
     from .engine import AdaINEngine
 
@@ -221,7 +221,7 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
     if rank == 0:
         # the frame-to-frame recurrence (video/utils.py:355-368) on the gathered frames; every frame is written by a worker
         # thread behind an asynchronous device -> host copy while the next frame's warp / blend is already running
-        sink = jobs.FileSink(engine.device)
+        sink = jobs.FileSink(engine.device, jpeg_on_device=jpeg_on_device)
         try:
             n, h, w, _ = frames_u8.shape
             prev = None
@@ -253,21 +253,22 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
 def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
                              cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                              vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth", decoder_str="Style_3DGS/AdaIN/models/decoder.pth",
-                             depth_maps=None, intermediate_jpeg=False, group=None):
+                             depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False):
     """One style for the whole clip (video/utils.py:244-295); keyword-only extras: a ready ``engine``, checkpoint paths,
-    precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group."""
+    precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``jpeg_on_device`` (.jpg / .jpeg frames are
+    encoded on the device: the same files, jobs.FileSink)."""
     return _run(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
-                engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group)
+                engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device)
 
 
 def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
                                    cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                                    vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth",
                                    decoder_str="Style_3DGS/AdaIN/models/decoder.pth", depth_maps=None, intermediate_jpeg=False,
-                                   group=None):
+                                   group=None, jpeg_on_device=False):
     """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372)."""
     style_images = sorted(os.listdir(style_dir))
     if len(style_images) == 0:
         raise ValueError("No style images found in the style directory.")
     return _run(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
-                cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group)
+                cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device)

@@ -340,6 +340,32 @@ ADAIN_API int adain_stylize_u8(const uint8_t* frames_nhwc_u8, int n, int h, int 
                      int mask_is_float, int mask_n, int mask_c, int mask_h, int mask_w, uint8_t* out_u8, void* workspace,
                      size_t workspace_bytes, adain_stream_t stream);
 
+/* ---- the callers' output files: PIL's Image.fromarray(frame).save(path) for a .jpg path (test.py:243-244 through torchvision's
+ * save_image; video/utils.py:352-356 per frame), encoded on the device --------------------------------------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * src: n frames HWC uint8 [n][h][w][c], c = 3 (RGB) or 1 (L) - what adain_stylize_u8, adain_resize_area_u8 and adain_warp_blend_u8
+ * write.  Frame i's file - baseline JPEG, JFIF 1.01 header, 4:2:0 chroma for RGB, libjpeg's integer "islow" DCT, the Annex K
+ * quantisation tables scaled by `quality` (Pillow's default: 75) and the Annex K Huffman tables: byte for byte what Pillow's default
+ * save writes at that quality (established against Pillow 12.2.0 built with libjpeg-turbo; the rules are listed at the top of
+ * csrc/jpeg.hip and restated in NumPy in tests/jpeg_ref.py) - lies contiguously at out + i * out_stride and is lengths[i] bytes long
+ * (int32, device).  Bytes of `out` behind a file are not written.  Integer arithmetic throughout: a frame's bytes do not depend on
+ * the batch, the stream or the device size.
+ * adain_jpeg_encode_u8_bytes (host only): *out_stride = the largest file a frame of this shape can have, whatever its content and
+ *   quality, so that an overflow is impossible, not detected: a block codes its DC difference in at most 11 + 11 bits (the longest DC
+ *   code of category <= 11 plus its bits; 8-bit samples give |DC| <= 1024, so |difference| < 2^11) and each of its 63 AC coefficients
+ *   in at most 16 + 10 bits (the longest AC code plus the bits of |AC| < 2^10, which the orthonormal 8 x 8 DCT of samples in
+ *   [-128, 127] cannot exceed; a ZRL or the EOB replaces coefficients that would cost more), 22 + 63 * 26 = 1660 bits; B blocks in the
+ *   scan (6 per 16 x 16 MCU for RGB, dummy luma blocks included; ceil(h/8) * ceil(w/8) for L) give E = ceil(1660 B / 8) bytes, byte
+ *   stuffing at most doubles them, and header (623 bytes RGB, 328 L) and EOI (2) are added: out_stride = header + 2 E + 2.
+ *   *workspace_bytes = the coefficients, bit counts, offsets and the unstuffed bit stream of n frames.  Either output may be NULL.
+ * Refused with ADAIN_EINVAL before anything is launched: c other than 1 and 3, h or w outside 1..65535, n < 1, quality outside
+ * 1..100, n > 65535 (the frames ride in one grid dimension), an out_stride or workspace_bytes below the query's, a workspace that is
+ * not 8-byte aligned or `lengths` that is not 4-byte aligned, and a shape whose out_stride would exceed 2^31 - 1 (lengths are int32).
+ * 8 kernel launches per call, whatever n. */
+ADAIN_API int adain_jpeg_encode_u8_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes);
+ADAIN_API int adain_jpeg_encode_u8(const uint8_t* src_u8, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride,
+                                   int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream);
+
 /* ---- layout changes at the boundary ([n][c][hw] <-> [n][hw][c]) ------------------------------------------ */
 ADAIN_API int adain_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, adain_stream_t stream);
 ADAIN_API int adain_nchw_to_nhwc(const float* in, float* out, int n, int c, int hw, adain_stream_t stream);

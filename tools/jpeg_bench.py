@@ -1,0 +1,137 @@
+"""Times the device JPEG encoder (csrc/jpeg.hip) against Pillow's on the same machine, at 256 x 456, 1080 x 1920 and 1200 x 1600, on a
+stylised synthetic frame (seed-0 weights) and on uniform noise.  Per frame, median and interquartile range over --reps calls (>= 200)
+after warm-up:
+  kernel_ms  adain_jpeg_encode_u8 on a device-resident frame, HIP events
+  device_ms  wall clock from the device uint8 frame to host ``bytes``: the call, the length read, the copy of exactly that many bytes
+  pillow_ms  Image.fromarray(frame).save(BytesIO, format="JPEG") of the same frame on this machine's CPU, one thread
+and whether the two files are the same bytes.  ``passes_1080p``: device_ms sits below pillow_ms by more than the two interquartile
+ranges combined.  With --job, a 64-view 1200 x 1600 precompute_guides_sharded into a temporary directory with jpeg_on_device off and on:
+wall time, the sink's wait and the bytes that crossed to the host.  Prints one JSON line and, with --out, writes it to a file.
+Usage: python tools/jpeg_bench.py [--reps 200] [--job] [--out profiles/jpeg_bench.json]"""
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import PIL
+import torch
+from PIL import Image
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+import applied_image_processing_amd.runtime as rt  # noqa: E402
+import applied_image_processing_amd.synth as synth  # noqa: E402
+from applied_image_processing_amd import jobs  # noqa: E402
+from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
+from applied_image_processing_amd.telemetry import GpuTelemetry  # noqa: E402
+
+SIZES = [(256, 456), (1080, 1920), (1200, 1600)]
+
+
+def spread(times):
+    q = statistics.quantiles(times, n=4)
+    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
+
+
+def wall_ms(fn, reps, warmup, sync):
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(reps):
+        if sync:
+            torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        times.append((time.perf_counter() - t) * 1e3)
+    return spread(times)
+
+
+def event_ms(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return spread(times)
+
+
+def pillow_bytes(a):
+    f = io.BytesIO()
+    Image.fromarray(a).save(f, format="JPEG")
+    return f.getvalue()
+
+
+def guide_job(engine, on, views, style, sub_batch):
+    names = [f"view_{k:03d}" for k in range(len(views))]
+    with tempfile.TemporaryDirectory() as d:
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        paths, info = jobs.precompute_guides_sharded(engine, views, names, d, style, content_size=0, sub_batch=sub_batch, jpeg_on_device=on)
+        wall = time.perf_counter() - t
+        size = sum(os.path.getsize(p) for p in paths.values())
+    return {"wall_s": round(wall, 3), "sink_wait_s": round(info["sink_wait_s"], 3), "write_s": round(info["write_s"], 3), "d2h_bytes": int(info["d2h_bytes"]),
+            "file_bytes": size}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--job", action="store_true")
+    ap.add_argument("--views", type=int, default=64)
+    ap.add_argument("--out", type=str, default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "jpeg_bench needs a GPU"
+    torch.cuda.set_device(0)
+    torch.set_num_threads(1)
+    reps = max(args.reps, 200)
+    dev = torch.device("cuda:0")
+    engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
+    engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
+    tel = GpuTelemetry(0).start()
+    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
+           "pillow": PIL.__version__, "sizes": {}}
+    for h, w in SIZES:
+        source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
+        frames = {"stylised": engine.stylize_u8(source, alpha=0.5).contiguous(),
+                  "noise": torch.from_numpy(np.random.default_rng(0).integers(0, 256, (1, h, w, 3), dtype=np.uint8)).to(dev)}
+        for kind, x in frames.items():
+            host = x[0].cpu().numpy()
+            t0 = time.perf_counter()
+            kernel = event_ms(lambda: rt.jpeg_encode_u8(x), reps, 20)
+            tel.window(f"kernel_{kind}_{h}x{w}", t0, time.perf_counter())
+            device = wall_ms(lambda: rt.jpeg_files(*rt.jpeg_encode_u8(x)), reps, 5, True)
+            pillow = wall_ms(lambda: pillow_bytes(host), reps, 3, False)
+            data, = rt.jpeg_files(*rt.jpeg_encode_u8(x))
+            res["sizes"][f"{kind}_{h}x{w}"] = {"frame_bytes": int(x.numel()), "file_bytes": len(data), "same_bytes_as_pillow": data == pillow_bytes(host),
+                                               "kernel_ms": kernel, "device_ms": device, "pillow_ms": pillow,
+                                               "pillow_over_device": round(pillow["median"] / device["median"], 2)}
+    res["passes_1080p"] = all(v["device_ms"]["median"] + v["device_ms"]["iqr"] + v["pillow_ms"]["iqr"] < v["pillow_ms"]["median"]
+                              for k, v in res["sizes"].items() if k.endswith("1080x1920"))
+    if args.job:
+        base = [(synth.image(100 + k, 1, 1200, 1600)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8) for k in range(8)]
+        views = [Image.fromarray(np.roll(base[k % 8], 16 * (k // 8), axis=1)) for k in range(args.views)]       # PIL views, as the 3DGS caller holds them
+        style = torch.from_numpy(synth.image(4, 1, 512, 512))
+        guide_job(engine, False, views[:8], style, 4)                     # warm-up: workspaces, pinned buffers, clocks
+        guide_job(engine, True, views[:8], style, 4)
+        res["guide_job_64x1200x1600"] = {"views": len(views), "off": guide_job(engine, False, views, style, 4), "on": guide_job(engine, True, views, style, 4)}
+    res["telemetry"] = tel.stop()          # shader clock and power over each kernel timing window (sysfs reads)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
