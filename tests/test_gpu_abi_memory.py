@@ -31,7 +31,8 @@ Entry point -> cases (every export of the library that launches a kernel; the ho
   adain_flow_gray_u8                     test_flow_gray_u8: copy, exact 2x, general, enlarged
   adain_farneback_expand, _flow          test_farneback: 37 x 61 and 1080p
   adain_tvl1_prepare, adain_tvl1_flow    test_tvl1: two pairs sharing a frame, iters_out present and NULL
-  adain_colour_transfer_u8, adain_localized_combine_u8   test_colour_calls: a case_h case, an empty region, the 1080p block mask"""
+  adain_colour_transfer_u8, adain_localized_combine_u8   test_colour_calls: a case_h case, an empty region, the 1080p block mask,
+                                         1 x 7 with three pixels a region (every array of the workspace far below one 256-byte block)"""
 import ctypes
 
 import pytest
@@ -632,9 +633,12 @@ def _colour_cases():
     h, w = 1080, 1920
     blocks = (rng.random((h // 8, w // 8)) < 0.4).astype(np.uint8)
     yield "1080p", rng.integers(1, 256, (h, w, 3), dtype=np.uint8), rng.integers(1, 256, (h, w, 3), dtype=np.uint8), np.kron(blocks, np.ones((8, 8), np.uint8))
+    import colour_fixtures
+
+    yield ("n3_n3",) + colour_fixtures.combine_fixture("n3_n3")              # hw = 7: key and sort arrays of 56 bytes
 
 
-@pytest.mark.parametrize("which", ["case_h", "empty", "1080p"])
+@pytest.mark.parametrize("which", ["case_h", "empty", "1080p", "n3_n3"])
 def test_colour_calls(rt, which):
     L = rt.lib()
     name, content, stylised, m = next(c for c in _colour_cases() if c[0] == which)
@@ -642,16 +646,17 @@ def test_colour_calls(rt, which):
     h, w = m.shape
     q = L.adain_colour_transfer_workspace_bytes(h, w)
     assert q >= rt.COLOUR_RECORD_BYTES
+    h2, w2 = (h - 8, w) if h > 8 else (h, w - 3)                              # the other shape that used the workspace before
     record = lambda a: {"record": a.bytes("ws")[:rt.COLOUR_RECORD_BYTES].clone()}
     cs = Case(rt).inp("content", content).inp("stylised", stylised).inp("mask", m).ws("ws", q, align=8).out("out", h * w * 3)
     outs = cs.run(lambda a: L.adain_localized_combine_u8(a.ptr("content"), a.ptr("stylised"), a.ptr("mask"), a.ptr("out"), h, w, a.ptr("ws"), S(rt)),
-                  history=lambda a: L.adain_colour_transfer_u8(a.ptr("content"), a.ptr("stylised"), a.ptr("out"), h - 8, w, a.ptr("ws"), S(rt)),
+                  history=lambda a: L.adain_colour_transfer_u8(a.ptr("content"), a.ptr("stylised"), a.ptr("out"), h2, w2, a.ptr("ws"), S(rt)),
                   extra=record)
     out, rec = rt.localized_combine_u8(content, stylised, m)
     same(outs, out=out, record=rec)
     fg, bg = content * (1 - m)[..., None], stylised * m[..., None]
     cs = Case(rt).inp("fg", fg).inp("bg", bg).ws("ws", q, align=8).out("out", h * w * 3)
     outs = cs.run(lambda a: L.adain_colour_transfer_u8(a.ptr("fg"), a.ptr("bg"), a.ptr("out"), h, w, a.ptr("ws"), S(rt)),
-                  history=lambda a: L.adain_colour_transfer_u8(a.ptr("bg"), a.ptr("fg"), a.ptr("out"), h - 8, w, a.ptr("ws"), S(rt)), extra=record)
+                  history=lambda a: L.adain_colour_transfer_u8(a.ptr("bg"), a.ptr("fg"), a.ptr("out"), h2, w2, a.ptr("ws"), S(rt)), extra=record)
     out, rec = rt.colour_transfer_u8(fg, bg)
     same(outs, out=out, record=rec)
