@@ -19,9 +19,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fvisibility=hi
 # v_pk_add_f32 / v_pk_fma_f32 issue far slower than the plain forms (MI355X_MICROARCH.md, "price of one filler beside
 # MFMAs"): keep hipcc from packing f32 pairs in those files.  Measured on the Winograd kernel: +7 %.
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-# tvl1.hip keeps OpenCV's float operations one by one (no FMA contraction), as its NumPy restatement does; colour.hip keeps numpy's
-# float64 operations apart the same way, so that equal colours run one instruction sequence and project to equal keys
-EXTRA_FLAGS = {"conv_wino4.hip": NO_PACKED_F32, "tvl1.hip": ["-ffp-contract=off"], "colour.hip": ["-ffp-contract=off"]}
+# flow.hip and tvl1.hip keep OpenCV's float operations one by one (no FMA contraction), as their NumPy restatements do: with it the
+# Farneback flow is the float32 restatement's bit for bit, without it the fused operations moved ill-conditioned narrow frames by
+# up to 4.5e-5 px; colour.hip keeps numpy's float64 operations apart the same way, so that equal colours run one instruction
+# sequence and project to equal keys
+NO_CONTRACT = ["-ffp-contract=off"]
+EXTRA_FLAGS = {"conv_wino4.hip": NO_PACKED_F32, "flow.hip": NO_CONTRACT, "tvl1.hip": NO_CONTRACT, "colour.hip": NO_CONTRACT}
 
 
 def _hipcc():

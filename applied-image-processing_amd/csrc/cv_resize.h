@@ -4,8 +4,8 @@
 //             pixels inside the image); anything else is linear (2).
 //   linear    fx = (float)((dx+0.5)*scale - 0.5), taps (1-fx, fx); x taps clamped at both ends with fraction 0, rows clamped with
 //             their weights kept.
-// Each file compiles this under its own flags: tvl1.hip with -ffp-contract=off; in flow.hip the compiler may fuse a multiply and an
-// add, and which ones it fuses depends on the surrounding code (flow.hip's fb_update_kernel writes its linear arm out for that).
+// Both files are compiled with -ffp-contract=off: every multiply and add below is rounded on its own, as in OpenCV's CPU build and
+// in the NumPy restatements.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

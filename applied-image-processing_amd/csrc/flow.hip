@@ -27,7 +27,10 @@
 // Kernels: a frame's pyramid (level images + R, adain_farneback_expand) depends on that frame only, so a clip of N frames needs N
 // expansions; the flow (adain_farneback_flow) of a pair runs per level one matrix update (fused with the flow upscale) and
 // `iterations` fused box-blur + solve + matrix-update launches that ping-pong M between two buffers.  No atomics, no data-
-// dependent order: the same inputs give the same bits.
+// dependent order: the same inputs give the same bits.  The file is compiled with -ffp-contract=off: the float operations stay
+// OpenCV's, one by one, and the flow equals the float32 mode of tests/farneback_ref.py bit for bit (fused multiply-adds are no less
+// accurate on average, but on narrow frames, where every pixel solves nearly the same ill-conditioned 2 x 2 system, they moved the
+// flow by up to 4.5e-5 px, more than twice the float32 restatement's own distance from float64 on some fixtures).
 #include "../../include/adain_hip.h"
 #include "common.h"
 #include "cv_resize.h"
@@ -307,8 +310,7 @@ __global__ __launch_bounds__(256) void fb_update_kernel(const float* __restrict_
             fl[0] = pflow[(size_t)y * pw + x];
             fl[1] = pflow[plane + (size_t)y * pw + x];
         } else {                          // the finer level is never an exact 2x SHRINK of the coarser one: linear
-            // cv_resize.h's linear arm with the taps shared by both components, written out: under this file's default FMA
-            // contraction, resample() per component compiles to other fused multiply-adds and changes the flow's last bits
+            // cv_resize.h's linear arm with the taps shared by both components, written out
             const LinTap tx = lin_tap(x, pw, scale_x, true), ty = lin_tap(y, ph, scale_y, false);
             const float a0 = 1.f - tx.f, a1 = tx.f, b0 = 1.f - ty.f, b1 = ty.f;
 #pragma unroll

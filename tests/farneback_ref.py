@@ -16,7 +16,8 @@ smooth.dispatch.cpp); nothing in this project runs cv2, so parity with cv2 itsel
   (OpenCV: float vertical pass, double horizontal accumulation); replicated borders; 5 outputs in OpenCV's order y, x, yy, xx, xy.
 * Matrix update (FarnebackUpdateMatrices): R1 sampled bilinearly at (x+dx, y+dy) when 0 <= floor(x+dx) < w-1 and
   0 <= floor(y+dy) < h-1, OpenCV's "else" branch otherwise; border weights {0.14, 0.14, 0.4472, 0.4472, 0.4472} on the outer 5
-  pixels; outputs G11, G12, G22, h1, h2.
+  pixels, applied where OpenCV's unsigned test holds (border_scale: on frames narrower than 10 that is not "the outer 5");
+  outputs G11, G12, G22, h1, h2.
 * Flow update (FarnebackUpdateFlow_Blur): box sum over 2*(winsize//2)+1 pixels each way, replicated borders, scaled by
   1/winsize^2 (double); idet = 1/(g11 g22 - g12^2 + 1e-3), flow_x = (g11 h2 - g12 h1) idet, flow_y = (g22 h1 - g12 h2) idet; M
   is recomputed from the new flow after every iteration but the last; ``iterations`` rounds per level.
@@ -203,6 +204,31 @@ def poly_exp(img, n, sigma, dtype):
     return out.astype(dtype)
 
 
+def border_scale(h, w):
+    """FarnebackUpdateMatrices' border weight per pixel, float32 [h, w].  OpenCV tests ``(unsigned)(x - 5) >= (unsigned)(width - 10)
+    || (unsigned)(y - 5) >= (unsigned)(height - 10)`` in 32-bit unsigned arithmetic and, where that holds, multiplies by
+    border[x] (x < 5), border[width - x - 1] (x >= width - 5) and the same two factors in y.  For width >= 10 the x test is
+    "x < 5 or x >= width - 5".  Below 10 ``width - 10`` wraps to 2^32 - (10 - width) and the test holds only for
+    max(width - 5, 0) <= x < 5: columns 3, 4 of an 8-wide frame, every column of one at most 5 wide.  A pixel that passes through
+    its row takes the column factors as well, whatever the column test said."""
+    def test(n):
+        i = np.arange(n, dtype=np.int64)
+        return ((i - 5) % (1 << 32)) >= ((n - 10) % (1 << 32))
+
+    def factors(n):
+        lo = np.ones(n, np.float32)
+        hi = np.ones(n, np.float32)
+        i = np.arange(n)
+        lo[i < 5] = BORDER[i[i < 5]]
+        hi[i >= n - 5] = BORDER[(n - i - 1)[i >= n - 5]]
+        return lo, hi
+
+    xl, xh = factors(w)
+    yl, yh = factors(h)
+    scale = ((xl[None, :] * xh[None, :]) * yl[:, None]) * yh[:, None]
+    return np.where(test(w)[None, :] | test(h)[:, None], scale, np.float32(1)).astype(np.float32)
+
+
 def update_matrices(R0, R1, flow, dtype):
     """R0, R1 [h, w, 5]; flow [2, h, w] (x, y) -> M [h, w, 5]."""
     h, w = flow.shape[1:]
@@ -231,17 +257,7 @@ def update_matrices(R0, R1, flow, dtype):
     r2 = r2 + (r4 * dy + r6 * dx)
     r3 = r3 + (r6 * dy + r5 * dx)
 
-    def edge(n):
-        lo = np.ones(n, np.float32)
-        hi = np.ones(n, np.float32)
-        i = np.arange(n)
-        lo[i < 5] = BORDER[i[i < 5]]
-        hi[i >= n - 5] = BORDER[(n - i - 1)[i >= n - 5]]
-        return lo, hi
-
-    xl, xh = edge(w)
-    yl, yh = edge(h)
-    scale = (((xl[None, :] * xh[None, :]) * yl[:, None]) * yh[:, None]).astype(t)
+    scale = border_scale(h, w).astype(t)
     r2, r3, r4, r5, r6 = (v * scale for v in (r2, r3, r4, r5, r6))
     return np.stack([r4 * r4 + r6 * r6, (r4 + r5) * r6, r5 * r5 + r6 * r6, r4 * r2 + r6 * r3, r6 * r2 + r5 * r3], axis=-1).astype(t)
 

@@ -252,7 +252,7 @@ def tvl1_prepared(P0, P1, dtype=np.float64, **params):
                 n_inner = 0
                 while error > eps and n_inner < p["innerIterations"]:
                     error = inner_step(state, C, l_t, theta, taut, dtype)
-                    margins.append(abs(error - eps) / eps)
+                    margins.append(abs(error - eps) / eps if eps > 0 else np.inf)   # epsilon 0: nothing is near the threshold
                     iters[s, wi] += 1
                     n_inner += 1
                 n_outer += 1
