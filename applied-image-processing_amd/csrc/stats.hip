@@ -206,16 +206,24 @@ __global__ __launch_bounds__(256) void adain_blend_kernel(const float* __restric
                 r[k] = t * w1 + v[k] * w2;
             }
         } else {
+            // the launcher asks n*c*hw % 4 == 0, not c*hw % 4 == 0: a quad may run over the end of its first element's image (over
+            // three of them when c*hw == 1), so every element takes its own image, and with it its own style and strength-map rows
+            unsigned ik = img, rk = rem;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const unsigned ch = (rem + k) / (unsigned)hw, pix = (rem + k) - ch * (unsigned)hw;
-                const float mc = c_mean[img * c + ch], sc = c_std[img * c + ch];
-                const float ms = s_mean[simg * c + ch], ss = s_std[simg * c + ch];
+            for (int k = 0; k < 4; ++k, ++rk) {
+                if (rk >= per_img) {
+                    rk -= per_img;
+                    ++ik;
+                }
+                const unsigned sk = style_n == 1 ? 0u : ik;
+                const unsigned ch = rk / (unsigned)hw, pix = rk - ch * (unsigned)hw;
+                const float mc = c_mean[ik * c + ch], sc = c_std[ik * c + ch];
+                const float ms = s_mean[sk * c + ch], ss = s_std[sk * c + ch];
                 const float nrm = (v[k] - mc) / sc;
                 const float t = nrm * ss + ms;
                 float w1 = alpha, w2 = one_minus_alpha;
                 if (pmap) {
-                    const float p = pmap[(pmap_n == 1 ? 0u : img) * (unsigned)hw + pix];
+                    const float p = pmap[(pmap_n == 1 ? 0u : ik) * (unsigned)hw + pix];
                     w1 = 1.0f - p;
                     w2 = p;
                 }

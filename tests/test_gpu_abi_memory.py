@@ -22,7 +22,9 @@ Entry point -> cases (every export of the library that launches a kernel; the ho
   adain_decode                           test_decode: 2 x 2, 5 x 13 batch 2, 1080p, two latency-schedule frames, 276 x 512
   adain_stylize_u8                       test_stylize_u8: no mask (2 sizes), the two fused tails, the general composite, depth maps, mask_n 1 / n,
                                          byte and float masks
-  adain_mean_std                         test_mean_std;  adain_blend_alpha, adain_blend_pmap: test_blend;  adain_strength_map: test_strength_map
+  adain_mean_std                         test_mean_std;  adain_strength_map: test_strength_map
+  adain_blend_alpha, adain_blend_pmap    test_blend: NHWC c = 512 and 12, NCHW 64 x 9 x 11 and 32 x 1 x 1; NCHW planes of 15 and 6 floats (a quad
+                                         of four elements lies across two images) with one style row, whose neighbours are the changing fill
   adain_resize_bilinear, _nearest        test_resize;  adain_mask_composite: test_mask_composite
   adain_quantize_u8, adain_u8_to_f32     test_quantize_u8_and_u8_to_f32: c = 1, 3, 4 x widths 1, 3, 5, 67
   adain_nhwc_to_nchw, adain_nchw_to_nhwc test_layout_changes
@@ -422,7 +424,8 @@ def test_mean_std(rt, nhwc, n, c, h, w):
     same(outs, mean=mean, std=std)
 
 
-@pytest.mark.parametrize("nhwc,n,c,h,w,style_n,pmap_n", [(1, 3, 512, 5, 7, 1, 0), (1, 3, 512, 5, 7, 3, 1), (0, 2, 64, 9, 11, 2, 2), (0, 2, 32, 1, 1, 1, 0)])
+@pytest.mark.parametrize("nhwc,n,c,h,w,style_n,pmap_n", [(1, 3, 512, 5, 7, 1, 0), (1, 3, 512, 5, 7, 3, 1), (0, 2, 64, 9, 11, 2, 2), (0, 2, 32, 1, 1, 1, 0),
+                                                          (0, 4, 3, 1, 5, 1, 4), (0, 2, 3, 1, 2, 1, 0), (1, 3, 12, 1, 5, 1, 3)])
 def test_blend(rt, nhwc, n, c, h, w, style_n, pmap_n):
     L = rt.lib()
     x = randn(n, h, w, c, seed=21) if nhwc else randn(n, c, h, w, seed=21)
