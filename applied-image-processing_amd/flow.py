@@ -64,7 +64,7 @@ def frames_to_gray(frames, dsize=None):
     """The reference's frame preparation on the device: uint8 RGB frames [h,w,3] or [n,h,w,3] (PIL's channel order, as decoded
     here) -> uint8 gray [h,w] / [n,h,w] of ``cv2.cvtColor(cv2.resize(bgr, dsize), cv2.COLOR_RGB2GRAY)`` where ``bgr`` is what
     ``cv2.imread`` gives.  ``dsize`` = (width, height) as in cv2; None keeps the size."""
-    frames = rt._dev(frames, "frames", torch.uint8)
+    frames = rt.device_tensor(frames, "frames", torch.uint8)
     single = frames.dim() == 3
     if single:
         frames = frames.unsqueeze(0)
@@ -73,8 +73,7 @@ def frames_to_gray(frames, dsize=None):
     n, hi, wi, _ = frames.shape
     wo, ho = (wi, hi) if dsize is None else (int(dsize[0]), int(dsize[1]))
     out = torch.empty((n, ho, wo), dtype=torch.uint8, device=frames.device)
-    with torch.cuda.device(frames.device):
-        rt._check(rt.lib().adain_flow_gray_u8(frames.data_ptr(), n, hi, wi, out.data_ptr(), ho, wo, rt._stream()), "adain_flow_gray_u8")
+    rt.call("adain_flow_gray_u8", frames.device, frames.data_ptr(), n, hi, wi, out.data_ptr(), ho, wo)
     return out[0] if single else out
 
 
@@ -92,7 +91,7 @@ class Farneback:
             raise ValueError(f"calcOpticalFlowFarneback: unsupported frame size {self.w} x {self.h}")
 
     def _gray(self, g):
-        g = rt._dev(g, "gray", torch.uint8)
+        g = rt.device_tensor(g, "gray", torch.uint8)
         if tuple(g.shape) != (self.h, self.w):
             raise rt.AdainHipError(f"farneback: expected a uint8 [{self.h},{self.w}] frame, got {tuple(g.shape)}")
         return g
@@ -101,25 +100,21 @@ class Farneback:
         gray = self._gray(gray)
         pyr = out if out is not None else torch.empty(self.pyr_bytes, dtype=torch.uint8, device=gray.device)
         ws = rt.workspace(gray.device, "farneback", self.ws_bytes)
-        with torch.cuda.device(gray.device):
-            rt._check(rt.lib().adain_farneback_expand(gray.data_ptr(), self.h, self.w, self.pyr_scale, self.levels, self.poly_n,
-                                                      self.poly_sigma, pyr.data_ptr(), ws.data_ptr(), ws.numel(), rt._stream()),
-                      "adain_farneback_expand")
+        rt.call("adain_farneback_expand", gray.device, gray.data_ptr(), self.h, self.w, self.pyr_scale, self.levels, self.poly_n,
+                self.poly_sigma, pyr.data_ptr(), ws.data_ptr(), ws.numel())
         return pyr
 
     def flow(self, pyr_prev, pyr_next, out=None):
         dev = pyr_prev.device
         for p in (pyr_prev, pyr_next):
-            rt._check_buffer(p, "farneback: each pyramid (made by expand())", torch.uint8, dev, min_numel=self.pyr_bytes)
+            rt.check_buffer(p, "farneback: each pyramid (made by expand())", torch.uint8, dev, min_numel=self.pyr_bytes)
         if out is None:
             out = torch.empty((2, self.h, self.w), dtype=torch.float32, device=dev)
         else:
-            rt._check_buffer(out, "farneback: out", torch.float32, dev, shape=(2, self.h, self.w))
+            rt.check_buffer(out, "farneback: out", torch.float32, dev, shape=(2, self.h, self.w))
         ws = rt.workspace(dev, "farneback", self.ws_bytes)
-        with torch.cuda.device(dev):
-            rt._check(rt.lib().adain_farneback_flow(pyr_prev.data_ptr(), pyr_next.data_ptr(), self.h, self.w, self.pyr_scale, self.levels,
-                                                    self.winsize, self.iterations, self.flags, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                    rt._stream()), "adain_farneback_flow")
+        rt.call("adain_farneback_flow", dev, pyr_prev.data_ptr(), pyr_next.data_ptr(), self.h, self.w, self.pyr_scale, self.levels,
+                self.winsize, self.iterations, self.flags, out.data_ptr(), ws.data_ptr(), ws.numel())
         return out
 
 

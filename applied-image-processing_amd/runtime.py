@@ -5,6 +5,7 @@ compute call below hands raw device pointers (``tensor.data_ptr()``) and the cur
 hand-written gfx950 kernel.  There is NO fallback: if the shared library is missing or the tensors
 are not on a GPU, these functions raise.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -139,10 +140,14 @@ def use_library(path):
 ABI_CALLS = [0]          # compute calls made through the C ABI by this process (jobs report it per frame)
 
 
+def _failure(what, rc):
+    return AdainHipError(f"{what} failed ({rc}): {lib().adain_last_error().decode()}")
+
+
 def _check(rc, what):
     ABI_CALLS[0] += 1
     if rc != 0:
-        raise AdainHipError(f"{what} failed ({rc}): {lib().adain_last_error().decode()}")
+        raise _failure(what, rc)
 
 
 class schedule:
@@ -166,7 +171,7 @@ def set_schedule(value):
     """Sets the calling thread's schedule; returns the previous one."""
     prev = lib().adain_set_schedule(int(value))
     if prev < 0:
-        raise AdainHipError(f"adain_set_schedule failed ({prev}): {lib().adain_last_error().decode()}")
+        raise _failure("adain_set_schedule", prev)
     return prev
 
 
@@ -178,7 +183,8 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _dev(t, name, dtype=torch.float32):
+def device_tensor(t, name, dtype=torch.float32):
+    """``t`` contiguous, or AdainHipError when it is not a GPU tensor of ``dtype``."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise AdainHipError(f"{name}: expected a GPU tensor (the AdaIN path has no CPU fallback)")
     if t.dtype != dtype:
@@ -186,7 +192,7 @@ def _dev(t, name, dtype=torch.float32):
     return t.contiguous()
 
 
-def _check_buffer(t, name, dtype, device, shape=None, numel=None, min_numel=None, align=None, distinct=()):
+def check_buffer(t, name, dtype, device, shape=None, numel=None, min_numel=None, align=None, distinct=()):
     """Refuses a caller-supplied buffer that a kernel could not be handed as it is: not a contiguous ``dtype`` GPU tensor on
     ``device``, not of ``shape`` / ``numel`` / at least ``min_numel`` elements, not ``align``-byte aligned, or starting where one
     of the ``distinct`` inputs starts.  AdainHipError("<name> must be ...") before anything is launched."""
@@ -227,34 +233,62 @@ def free_workspaces():
     _ws.clear()
 
 
+# --- the call path -----------------------------------------------------------------------------------------------
+# THE RULE: a library function whose answer depends on the device that is current on the calling thread is called only inside
+# call() or scratch(), which make the tensors' device current first.  Those functions are every launch (whatever takes a stream)
+# and the five size queries that count the device's compute units for the cin split: adain_encode_workspace_bytes,
+# adain_encode_multi_workspace_bytes, adain_decode_workspace_bytes, adain_stylize_u8_workspace_bytes and
+# adain_conv3x3_wino4_split_workspace_bytes.  Asked elsewhere, such a query sizes the slabs for another device's compute units
+# (the launch then refuses them as too small, with the layers before it already queued) and opens a HIP context on a GPU the
+# caller never meant to touch.
+def _launch(name, *args):
+    """``lib().<name>(*args, stream)`` on the device that is current, with its current stream: counted in ABI_CALLS,
+    AdainHipError("<name> failed (<rc>): <last error>") on a non-zero return."""
+    _check(getattr(lib(), name)(*args, _stream()), name)
+
+
+def call(name, device, *args):
+    """One compute call of the C ABI: ``_launch`` with ``device`` current."""
+    with torch.cuda.device(device):
+        _launch(name, *args)
+
+
+@contextlib.contextmanager
+def scratch(device, tag, query, *dims, refuse=None):
+    """``with scratch(device, tag, "adain_x_workspace_bytes", *dims) as ws: _launch(...)`` - the calling stream's ``tag`` workspace
+    of ``device``, of the size ``lib().<query>(*dims)`` (or a callable's ``query(*dims)``) answers with ``device`` current; the body
+    runs with it current too, so a wrapper enters the device once for its query and its launch.  ``refuse``: the AdainHipError
+    text of a 0 answer, for the queries that refuse a size that way."""
+    with torch.cuda.device(device):
+        nbytes = getattr(lib(), query)(*dims) if isinstance(query, str) else query(*dims)
+        if nbytes == 0 and refuse is not None:
+            raise AdainHipError(refuse)
+        yield workspace(device, tag, nbytes)
+
+
 # --- weights ------------------------------------------------------------------------------------------------
 ENC_KEYS = [0, 2, 5, 9, 12, 16, 19, 22, 25, 29]
 DEC_KEYS = [1, 5, 8, 11, 14, 18, 21, 25, 28]
 
 
-def pack_encoder(state_dict, device):
-    """state_dict with reference keys ("0.weight", "2.weight", ... ) -> packed device buffer."""
-    ws = [_dev(state_dict[f"{k}.weight"].to(device=device, dtype=torch.float32), "weight") for k in ENC_KEYS]
-    bs = [_dev(state_dict[f"{k}.bias"].to(device=device, dtype=torch.float32), "bias") for k in ENC_KEYS]
-    packed = torch.empty(lib().adain_encoder_packed_floats(), dtype=torch.float32, device=device)
+def _pack(net, keys, state_dict, device):
+    ws = [device_tensor(state_dict[f"{k}.weight"].to(device=device, dtype=torch.float32), "weight") for k in keys]
+    bs = [device_tensor(state_dict[f"{k}.bias"].to(device=device, dtype=torch.float32), "bias") for k in keys]
+    packed = torch.empty(getattr(lib(), f"adain_{net}_packed_floats")(), dtype=torch.float32, device=device)
     wp, _k1 = _ptr_array(ws)
     bp, _k2 = _ptr_array(bs)
-    with torch.cuda.device(device):
-        _check(lib().adain_encoder_pack(wp, bp, packed.data_ptr(), _stream()), "adain_encoder_pack")
-        torch.cuda.current_stream().synchronize()   # the source tensors may be freed after return
+    call(f"adain_{net}_pack", packed.device, wp, bp, packed.data_ptr())
+    torch.cuda.current_stream(packed.device).synchronize()   # the source tensors may be freed after return
     return packed
+
+
+def pack_encoder(state_dict, device):
+    """state_dict with reference keys ("0.weight", "2.weight", ... ) -> packed device buffer."""
+    return _pack("encoder", ENC_KEYS, state_dict, device)
 
 
 def pack_decoder(state_dict, device):
-    ws = [_dev(state_dict[f"{k}.weight"].to(device=device, dtype=torch.float32), "weight") for k in DEC_KEYS]
-    bs = [_dev(state_dict[f"{k}.bias"].to(device=device, dtype=torch.float32), "bias") for k in DEC_KEYS]
-    packed = torch.empty(lib().adain_decoder_packed_floats(), dtype=torch.float32, device=device)
-    wp, _k1 = _ptr_array(ws)
-    bp, _k2 = _ptr_array(bs)
-    with torch.cuda.device(device):
-        _check(lib().adain_decoder_pack(wp, bp, packed.data_ptr(), _stream()), "adain_decoder_pack")
-        torch.cuda.current_stream().synchronize()
-    return packed
+    return _pack("decoder", DEC_KEYS, state_dict, device)
 
 
 # --- encoder / decoder -----------------------------------------------------------------------------------
@@ -271,58 +305,47 @@ def _event_array(events):
     return ctypes.cast(arr, _PP), arr
 
 
+def _encode(name, x, u8, packed, events):
+    x = device_tensor(x, "frames" if u8 else "image", torch.uint8 if u8 else torch.float32)
+    if x.dim() != 4 or x.shape[3 if u8 else 1] != 3:
+        raise AdainHipError(f"{name}: expected {'uint8 [n,h,w,3]' if u8 else '[n,3,h,w]'}, got {tuple(x.shape)}")
+    n, h, w = x.shape[:3] if u8 else (x.shape[0], x.shape[2], x.shape[3])
+    hc, wc = encoded_size(h, w)
+    feat = torch.empty((n, hc, wc, 512), dtype=torch.float32, device=x.device)
+    ev, _keep = _event_array(events)
+    with scratch(x.device, "conv", "adain_encode_workspace_bytes", n, h, w) as ws:
+        _launch(f"adain_{name}", x.data_ptr(), feat.data_ptr(), packed.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, ev)
+    return feat
+
+
 def encode(image, packed, events=None):
     """image NCHW [n,3,h,w] -> relu4_1 features NHWC [n,hc,wc,512]."""
-    image = _dev(image, "image")
-    if image.dim() != 4 or image.shape[1] != 3:
-        raise AdainHipError(f"encode: expected [n,3,h,w], got {tuple(image.shape)}")
-    n, _, h, w = image.shape
-    hc, wc = encoded_size(h, w)
-    feat = torch.empty((n, hc, wc, 512), dtype=torch.float32, device=image.device)
-    nbytes = lib().adain_encode_workspace_bytes(n, h, w)
-    ws = workspace(image.device, "conv", nbytes)
-    ev, _keep = _event_array(events)
-    with torch.cuda.device(image.device):
-        _check(lib().adain_encode(image.data_ptr(), feat.data_ptr(), packed.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, ev,
-                                  _stream()), "adain_encode")
-    return feat
+    return _encode("encode", image, False, packed, events)
 
 
 def encode_u8(frames_u8, packed, events=None):
     """Decoded frames HWC uint8 [n,h,w,3] -> relu4_1 features NHWC [n,hc,wc,512]; ToTensor (v / 255) happens inside the first
     layer's kernel: bit-identical to ``encode(u8_to_f32(frames_u8))``."""
-    x = _dev(frames_u8, "frames", torch.uint8)
-    if x.dim() != 4 or x.shape[3] != 3:
-        raise AdainHipError(f"encode_u8: expected uint8 [n,h,w,3], got {tuple(x.shape)}")
-    n, h, w, _ = x.shape
-    hc, wc = encoded_size(h, w)
-    feat = torch.empty((n, hc, wc, 512), dtype=torch.float32, device=x.device)
-    ws = workspace(x.device, "conv", lib().adain_encode_workspace_bytes(n, h, w))
-    ev, _keep = _event_array(events)
-    with torch.cuda.device(x.device):
-        _check(lib().adain_encode_u8(x.data_ptr(), feat.data_ptr(), packed.data_ptr(), ws.data_ptr(), ws.numel(), n, h, w, ev,
-                                     _stream()), "adain_encode_u8")
-    return feat
+    return _encode("encode_u8", frames_u8, True, packed, events)
 
 
 def encode_relu1_1(image, packed):
     """vgg[:4] (conv0 -> pad -> conv1_1 -> relu, net.py:39-42) as the one folded layer the encoder starts with: image NCHW float
     [n,3,h,w] or decoded uint8 frames [n,h,w,3] -> relu1_1 NHWC [n,h,w,64]."""
     u8 = isinstance(image, torch.Tensor) and image.dtype == torch.uint8
-    x = _dev(image, "image", torch.uint8 if u8 else torch.float32)
+    x = device_tensor(image, "image", torch.uint8 if u8 else torch.float32)
     if x.dim() != 4 or (x.shape[3] if u8 else x.shape[1]) != 3:
         raise AdainHipError(f"encode_relu1_1: expected float [n,3,h,w] or uint8 [n,h,w,3], got {tuple(x.shape)}")
     n, h, w = (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
     out = torch.empty((n, h, w, 64), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().adain_encode_relu1_1(x.data_ptr(), 1 if u8 else 0, out.data_ptr(), packed.data_ptr(), n, h, w, _stream()), "adain_encode_relu1_1")
+    call("adain_encode_relu1_1", x.device, x.data_ptr(), 1 if u8 else 0, out.data_ptr(), packed.data_ptr(), n, h, w)
     return out
 
 
 def encode_multi(images, packed, events=None):
     """Several image batches [n_i,3,h_i,w_i] of different sizes through the encoder in one pass (the content batch and the
     style image of one style_transfer call) -> list of relu4_1 features NHWC; bit-identical to ``encode`` per batch."""
-    images = [_dev(x, "image") for x in images]
+    images = [device_tensor(x, "image") for x in images]
     for x in images:
         if x.dim() != 4 or x.shape[1] != 3:
             raise AdainHipError(f"encode: expected [n,3,h,w], got {tuple(x.shape)}")
@@ -335,54 +358,31 @@ def encode_multi(images, packed, events=None):
     for x in images:
         hc, wc = encoded_size(x.shape[2], x.shape[3])
         feats.append(torch.empty((x.shape[0], hc, wc, 512), dtype=torch.float32, device=x.device))
-    nbytes = lib().adain_encode_multi_workspace_bytes(k, n, h, w)
-    if nbytes == 0:
-        raise AdainHipError(f"encode_multi: 1..4 image batches per call, got {k}")
-    ws = workspace(images[0].device, "conv", nbytes)
     ip, _k1 = _ptr_array(images)
     fp, _k2 = _ptr_array(feats)
     ev, _keep = _event_array(events)
-    with torch.cuda.device(images[0].device):
-        _check(lib().adain_encode_multi(k, ip, fp, n, h, w, packed.data_ptr(), ws.data_ptr(), ws.numel(), ev, _stream()), "adain_encode_multi")
+    with scratch(images[0].device, "conv", "adain_encode_multi_workspace_bytes", k, n, h, w,
+                 refuse=f"encode_multi: 1..4 image batches per call, got {k}") as ws:
+        _launch("adain_encode_multi", k, ip, fp, n, h, w, packed.data_ptr(), ws.data_ptr(), ws.numel(), ev)
     return feats
 
 
 def decode(feat, packed, events=None):
     """features NHWC [n,hc,wc,512] -> image NCHW [n,3,8hc,8wc]."""
-    feat = _dev(feat, "feat")
+    feat = device_tensor(feat, "feat")
     if feat.dim() != 4 or feat.shape[3] != 512:
         raise AdainHipError(f"decode: expected NHWC [n,hc,wc,512], got {tuple(feat.shape)}")
     n, hc, wc, _ = feat.shape
     img = torch.empty((n, 3, 8 * hc, 8 * wc), dtype=torch.float32, device=feat.device)
-    nbytes = lib().adain_decode_workspace_bytes(n, hc, wc)
-    ws = workspace(feat.device, "conv", nbytes)
     ev, _keep = _event_array(events)
-    with torch.cuda.device(feat.device):
-        _check(lib().adain_decode(feat.data_ptr(), img.data_ptr(), packed.data_ptr(), ws.data_ptr(), ws.numel(), n, hc, wc, ev,
-                                  _stream()), "adain_decode")
+    with scratch(feat.device, "conv", "adain_decode_workspace_bytes", n, hc, wc) as ws:
+        _launch("adain_decode", feat.data_ptr(), img.data_ptr(), packed.data_ptr(), ws.data_ptr(), ws.numel(), n, hc, wc, ev)
     return img
 
 
 # --- statistics and blend ------------------------------------------------------------------------------
-def mean_std(feat, nhwc, eps=1e-5):
-    """feat NHWC [n,h,w,c] (nhwc=True) or NCHW [n,c,h,w] -> (mean [n,c], std [n,c])."""
-    feat = _dev(feat, "feat")
-    assert feat.dim() == 4
-    if nhwc:
-        n, h, w, c = feat.shape
-    else:
-        n, c, h, w = feat.shape
-    mean = torch.empty((n, c), dtype=torch.float32, device=feat.device)
-    std = torch.empty_like(mean)
-    nbytes = lib().adain_mean_std_workspace_bytes(int(nhwc), n, c, h * w)
-    ws = workspace(feat.device, "stats", nbytes)
-    with torch.cuda.device(feat.device):
-        _check(lib().adain_mean_std(feat.data_ptr(), int(nhwc), n, c, h * w, eps, mean.data_ptr(), std.data_ptr(), ws.data_ptr(),
-                                    ws.numel(), _stream()), "adain_mean_std")
-    return mean, std
-
-
-def _blend_dims(x, nhwc):
+def _feat_dims(x, nhwc):
+    """(n, c, h * w) of a feature tensor NHWC [n,h,w,c] (nhwc) or NCHW [n,c,h,w]."""
     if nhwc:
         n, h, w, c = x.shape
     else:
@@ -390,92 +390,101 @@ def _blend_dims(x, nhwc):
     return n, c, h * w
 
 
+def mean_std(feat, nhwc, eps=1e-5):
+    """feat NHWC [n,h,w,c] (nhwc=True) or NCHW [n,c,h,w] -> (mean [n,c], std [n,c])."""
+    feat = device_tensor(feat, "feat")
+    assert feat.dim() == 4
+    n, c, hw = _feat_dims(feat, nhwc)
+    mean = torch.empty((n, c), dtype=torch.float32, device=feat.device)
+    std = torch.empty_like(mean)
+    with scratch(feat.device, "stats", "adain_mean_std_workspace_bytes", int(nhwc), n, c, hw) as ws:
+        _launch("adain_mean_std", feat.data_ptr(), int(nhwc), n, c, hw, eps, mean.data_ptr(), std.data_ptr(), ws.data_ptr(), ws.numel())
+    return mean, std
+
+
 def blend_alpha(x, nhwc, c_mean, c_std, s_mean, s_std, alpha):
     """AdaIN(x) * alpha + x * (1 - alpha);  alpha = 1 gives plain adaptive_instance_normalization."""
-    x = _dev(x, "content_feat")
-    n, c, hw = _blend_dims(x, nhwc)
+    x = device_tensor(x, "content_feat")
+    n, c, hw = _feat_dims(x, nhwc)
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _check(lib().adain_blend_alpha(x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(), s_mean.data_ptr(),
-                                       s_std.data_ptr(), s_mean.shape[0], float(alpha), float(1 - alpha), out.data_ptr(), _stream()),
-               "adain_blend_alpha")
+    call("adain_blend_alpha", x.device, x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(), s_mean.data_ptr(),
+         s_std.data_ptr(), s_mean.shape[0], float(alpha), float(1 - alpha), out.data_ptr())
     return out
 
 
 def blend_pmap(x, nhwc, c_mean, c_std, s_mean, s_std, pmap):
     """AdaIN(x) * (1 - P) + x * P with P [pn, hc, wc] (pn in {1, n})."""
-    x = _dev(x, "content_feat")
-    pmap = _dev(pmap, "pmap")
-    n, c, hw = _blend_dims(x, nhwc)
+    x = device_tensor(x, "content_feat")
+    pmap = device_tensor(pmap, "pmap")
+    n, c, hw = _feat_dims(x, nhwc)
     pn = pmap.numel() // hw
     if pn * hw != pmap.numel():
         raise AdainHipError("blend_pmap: strength map size does not match the feature map")
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _check(lib().adain_blend_pmap(x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(), s_mean.data_ptr(),
-                                      s_std.data_ptr(), s_mean.shape[0], pmap.data_ptr(), pn, out.data_ptr(), _stream()),
-               "adain_blend_pmap")
+    call("adain_blend_pmap", x.device, x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(), s_mean.data_ptr(),
+         s_std.data_ptr(), s_mean.shape[0], pmap.data_ptr(), pn, out.data_ptr())
     return out
 
 
 def strength_map(depth, hc, wc, offset, prominence):
     """depth [h0,w0] -> P [1,1,hc,wc]."""
-    depth = _dev(depth, "depth_map")
+    depth = device_tensor(depth, "depth_map")
     if depth.dim() != 2:
         raise AdainHipError(f"strength_map: expected a 2-D depth map, got {tuple(depth.shape)}")
     h0, w0 = depth.shape
     p = torch.empty((1, 1, hc, wc), dtype=torch.float32, device=depth.device)
-    ws = workspace(depth.device, "pmap", lib().adain_strength_map_workspace_bytes(hc, wc))
-    with torch.cuda.device(depth.device):
-        _check(lib().adain_strength_map(depth.data_ptr(), h0, w0, hc, wc, float(offset), float(prominence), p.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), _stream()), "adain_strength_map")
+    with scratch(depth.device, "pmap", "adain_strength_map_workspace_bytes", hc, wc) as ws:
+        _launch("adain_strength_map", depth.data_ptr(), h0, w0, hc, wc, float(offset), float(prominence), p.data_ptr(), ws.data_ptr(),
+                ws.numel())
     return p
 
 
 # --- pixel kernels -----------------------------------------------------------------------------------------
-def _resize(fn, name, x, size):
-    x = _dev(x, name)
-    assert x.dim() == 4
-    n, c, hi, wi = x.shape
-    ho, wo = size
-    out = torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(fn(x.data_ptr(), out.data_ptr(), n * c, hi, wi, ho, wo, _stream()), name)
+def _map(name, x, shape, *dims, dtype=torch.float32):
+    """A call that reads ``x`` and writes a new ``dtype`` tensor of ``shape``: ``lib().<name>(x, out, *dims, stream)``."""
+    out = torch.empty(shape, dtype=dtype, device=x.device)
+    call(name, x.device, x.data_ptr(), out.data_ptr(), *dims)
     return out
 
 
+def _resize(name, x, size):
+    x = device_tensor(x, name)
+    assert x.dim() == 4
+    n, c, hi, wi = x.shape
+    ho, wo = size
+    return _map(name, x, (n, c, ho, wo), n * c, hi, wi, ho, wo)
+
+
 def resize_bilinear(x, size):
-    return _resize(lib().adain_resize_bilinear, "adain_resize_bilinear", x, size)
+    return _resize("adain_resize_bilinear", x, size)
 
 
 def resize_nearest(x, size):
-    return _resize(lib().adain_resize_nearest, "adain_resize_nearest", x, size)
+    return _resize("adain_resize_nearest", x, size)
 
 
 def mask_composite(content, stylized, mask):
     """content, stylized NCHW [n,c,h,w]; mask [mn,mc,h,w] float -> content*(1-m) + stylized*m."""
-    content, stylized, mask = _dev(content, "content"), _dev(stylized, "stylized"), _dev(mask, "mask")
+    content, stylized, mask = device_tensor(content, "content"), device_tensor(stylized, "stylized"), device_tensor(mask, "mask")
     n, c, h, w = content.shape
     if stylized.shape != content.shape or mask.shape[-2:] != content.shape[-2:]:
         raise AdainHipError("mask_composite: shape mismatch")
     out = torch.empty_like(content)
-    with torch.cuda.device(content.device):
-        _check(lib().adain_mask_composite(content.data_ptr(), stylized.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[0],
-                                          out.data_ptr(), n, c, h * w, _stream()), "adain_mask_composite")
+    call("adain_mask_composite", content.device, content.data_ptr(), stylized.data_ptr(), mask.data_ptr(), mask.shape[1], mask.shape[0],
+         out.data_ptr(), n, c, h * w)
     return out
 
 
 def quantize_u8(img, out=None):
     """NCHW float [n,c,h,w] -> NHWC uint8 [n,h,w,c] (x*255 + 0.5, clamp, truncate); ``out``: a contiguous uint8 [n,h,w,c] GPU
     tensor to write into (a slice of a job's frame block)."""
-    img = _dev(img, "image")
+    img = device_tensor(img, "image")
     n, c, h, w = img.shape
     if out is None:
         out = torch.empty((n, h, w, c), dtype=torch.uint8, device=img.device)
     else:
-        _check_buffer(out, "quantize_u8: out", torch.uint8, img.device, shape=(n, h, w, c))
-    with torch.cuda.device(img.device):
-        _check(lib().adain_quantize_u8(img.data_ptr(), out.data_ptr(), n, c, h, w, _stream()), "adain_quantize_u8")
+        check_buffer(out, "quantize_u8: out", torch.uint8, img.device, shape=(n, h, w, c))
+    call("adain_quantize_u8", img.device, img.data_ptr(), out.data_ptr(), n, c, h, w)
     return out
 
 
@@ -485,12 +494,12 @@ def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, dept
     statistics, AdaIN blend - the alpha form, or the depth-aware form when ``depth_maps`` (one [h0,w0] float GPU tensor per frame)
     are given - decoder, mask composite, uint8 quantiser); the bytes the separate calls give.  frames_u8 uint8 [n,h,w,3]; s_mean /
     s_std [1,512]; mask [1|n, 1|3, hm, wm] uint8 / bool / float32 on the GPU.  Returns uint8 [n,oh,ow,3] (``out`` if given)."""
-    x = _dev(frames_u8, "frames", torch.uint8)
+    x = device_tensor(frames_u8, "frames", torch.uint8)
     if x.dim() != 4 or x.shape[3] != 3:
         raise AdainHipError(f"stylize_u8: expected uint8 [n,h,w,3], got {tuple(x.shape)}")
     n, h, w, _ = x.shape
     dev = x.device
-    s_mean, s_std = _dev(s_mean, "s_mean"), _dev(s_std, "s_std")
+    s_mean, s_std = device_tensor(s_mean, "s_mean"), device_tensor(s_std, "s_std")
     if s_mean.numel() != 512 or s_std.numel() != 512:
         raise AdainHipError("stylize_u8: the style statistics must be [1,512] each (one style per call)")
     mn = mc = mh = mw = 0
@@ -507,55 +516,48 @@ def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, dept
         m_ptr = mask.data_ptr()
     dp = dh = dw = None
     if depth_maps is not None:
-        depth_maps = [_dev(d, "depth_map") for d in depth_maps]
+        depth_maps = [device_tensor(d, "depth_map") for d in depth_maps]
         if len(depth_maps) != n or any(d.dim() != 2 for d in depth_maps):
             raise AdainHipError(f"stylize_u8: need {n} depth maps [h0,w0], one per frame")
         dp, _keep = _ptr_array(depth_maps)
         dh = (_c_int * n)(*[d.shape[0] for d in depth_maps])
         dw = (_c_int * n)(*[d.shape[1] for d in depth_maps])
     oh, ow = ctypes.c_int(), ctypes.c_int()
-    L = lib()
-    L.adain_stylize_u8_out_size(h, w, int(mask is not None), ctypes.byref(oh), ctypes.byref(ow))
+    lib().adain_stylize_u8_out_size(h, w, int(mask is not None), ctypes.byref(oh), ctypes.byref(ow))
     shape = (n, oh.value, ow.value, 3)
     if out is None:
         out = torch.empty(shape, dtype=torch.uint8, device=dev)
     else:
-        _check_buffer(out, "stylize_u8: out", torch.uint8, dev, shape=shape)
-    nbytes = L.adain_stylize_u8_workspace_bytes(n, h, w, int(depth_maps is not None), mn, mc, mh, mw, m_float)
-    ws = workspace(dev, "stylize", nbytes)
-    with torch.cuda.device(dev):
-        _check(L.adain_stylize_u8(x.data_ptr(), n, h, w, enc_packed.data_ptr(), dec_packed.data_ptr(), s_mean.data_ptr(), s_std.data_ptr(),
-                                  float(alpha), float(1 - alpha), dp, dh, dw, float(depth_offset), float(depth_prominence), m_ptr, m_float,
-                                  mn, mc, mh, mw, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "adain_stylize_u8")
+        check_buffer(out, "stylize_u8: out", torch.uint8, dev, shape=shape)
+    with scratch(dev, "stylize", "adain_stylize_u8_workspace_bytes", n, h, w, int(depth_maps is not None), mn, mc, mh, mw, m_float) as ws:
+        _launch("adain_stylize_u8", x.data_ptr(), n, h, w, enc_packed.data_ptr(), dec_packed.data_ptr(), s_mean.data_ptr(), s_std.data_ptr(),
+                float(alpha), float(1 - alpha), dp, dh, dw, float(depth_offset), float(depth_prominence), m_ptr, m_float, mn, mc, mh, mw,
+                out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
 
 
 def u8_to_f32(frames_u8):
     """torchvision ToTensor on the device: NHWC uint8 [n,h,w,c] -> NCHW float [n,c,h,w] = v / 255 (bit for bit the host's)."""
-    x = _dev(frames_u8, "frames", torch.uint8)
+    x = device_tensor(frames_u8, "frames", torch.uint8)
     if x.dim() != 4:
         raise AdainHipError(f"u8_to_f32: expected uint8 [n,h,w,c], got {tuple(x.shape)}")
     n, h, w, c = x.shape
-    out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().adain_u8_to_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, _stream()), "adain_u8_to_f32")
-    return out
+    return _map("adain_u8_to_f32", x, (n, c, h, w), n, c, h, w)
 
 
 def warp_blend_u8(cur, prev, flow, alpha, out=None):
     """Video post-pass: cur, prev uint8 [h,w,c]; flow float32 [2,h,w] -> blended uint8 [h,w,c] (written into ``out`` when given: a
     contiguous uint8 [h,w,c] GPU tensor that is neither ``cur`` nor ``prev`` - a row of the clip's result block)."""
-    cur, prev, flow = _dev(cur, "cur", torch.uint8), _dev(prev, "prev", torch.uint8), _dev(flow, "flow")
+    cur, prev, flow = device_tensor(cur, "cur", torch.uint8), device_tensor(prev, "prev", torch.uint8), device_tensor(flow, "flow")
     h, w, c = cur.shape
     if prev.shape != cur.shape or tuple(flow.shape) != (2, h, w):
         raise AdainHipError("warp_blend_u8: shape mismatch")
     if out is None:
         out = torch.empty_like(cur)
     else:
-        _check_buffer(out, "warp_blend_u8: out", torch.uint8, cur.device, shape=cur.shape, distinct=(cur, prev))
-    with torch.cuda.device(cur.device):
-        _check(lib().adain_warp_blend_u8(cur.data_ptr(), prev.data_ptr(), flow.data_ptr(), out.data_ptr(), h, w, c, float(alpha),
-                                         float(1 - alpha), _stream()), "adain_warp_blend_u8")
+        check_buffer(out, "warp_blend_u8: out", torch.uint8, cur.device, shape=cur.shape, distinct=(cur, prev))
+    call("adain_warp_blend_u8", cur.device, cur.data_ptr(), prev.data_ptr(), flow.data_ptr(), out.data_ptr(), h, w, c, float(alpha),
+         float(1 - alpha))
     return out
 
 
@@ -582,19 +584,15 @@ def colour_record(record):
     return dict(status=int(raw.status), fg=region(raw.fg), bg=region(raw.bg))
 
 
-def _colour_call(name, fn, images, out):
+def _colour_call(name, images, out):
     h, w, c = images[0].shape
     dev = images[0].device
     if out is None:
         out = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
     else:
-        _check_buffer(out, f"{name}: out", torch.uint8, dev, shape=(h, w, 3), distinct=images)
-    with torch.cuda.device(dev):
-        nbytes = lib().adain_colour_transfer_workspace_bytes(h, w)
-        if nbytes == 0:
-            raise AdainHipError(f"{name}: unsupported size {h} x {w}")
-        ws = workspace(dev, "colour", nbytes)
-        _check(fn(*[t.data_ptr() for t in images], out.data_ptr(), h, w, ws.data_ptr(), _stream()), f"adain_{name}")
+        check_buffer(out, f"{name}: out", torch.uint8, dev, shape=(h, w, 3), distinct=images)
+    with scratch(dev, "colour", "adain_colour_transfer_workspace_bytes", h, w, refuse=f"{name}: unsupported size {h} x {w}") as ws:
+        _launch(f"adain_{name}", *[t.data_ptr() for t in images], out.data_ptr(), h, w, ws.data_ptr())
         record = ws[:COLOUR_RECORD_BYTES].clone()        # the workspace is the stream's: the next call overwrites it
     return out, record
 
@@ -603,28 +601,29 @@ def colour_transfer_u8(fg, bg, out=None):
     """color_transfer_foreground (Style_3DGS/localized_style_transfer.py:128-168) on the device: fg, bg uint8 [h,w,3] -> (adjusted
     foreground uint8 [h,w,3], device record for ``colour_record``).  Nothing is copied to the host: an empty or one-pixel region leaves
     a copy of ``fg`` and a non-zero status in the record."""
-    fg, bg = _dev(fg, "fg", torch.uint8), _dev(bg, "bg", torch.uint8)
+    fg, bg = device_tensor(fg, "fg", torch.uint8), device_tensor(bg, "bg", torch.uint8)
     if fg.dim() != 3 or fg.shape[2] != 3 or bg.shape != fg.shape or bg.device != fg.device:
         raise AdainHipError(f"colour_transfer_u8: expected two uint8 [h,w,3] images of one size on one device, got {tuple(fg.shape)} and {tuple(bg.shape)}")
-    return _colour_call("colour_transfer_u8", lib().adain_colour_transfer_u8, (fg, bg), out)
+    return _colour_call("colour_transfer_u8", (fg, bg), out)
 
 
 def localized_combine_u8(content, stylised, mask, out=None):
     """The composite of run_localized_style_transfer (:232-238) with the colour transfer inside: content, stylised uint8 [h,w,3], mask
     uint8 [h,w] holding 0 and 1 only (1 = background; NOT checked here, that would wait for the device) -> (uint8 [h,w,3], record)."""
-    content, stylised, mask = _dev(content, "content", torch.uint8), _dev(stylised, "stylised", torch.uint8), _dev(mask, "mask", torch.uint8)
+    content, stylised, mask = (device_tensor(content, "content", torch.uint8), device_tensor(stylised, "stylised", torch.uint8),
+                               device_tensor(mask, "mask", torch.uint8))
     if (content.dim() != 3 or content.shape[2] != 3 or stylised.shape != content.shape or tuple(mask.shape) != tuple(content.shape[:2])
             or stylised.device != content.device or mask.device != content.device):
         raise AdainHipError(f"localized_combine_u8: expected uint8 [h,w,3], [h,w,3] and [h,w] on one device, got {tuple(content.shape)}, "
                             f"{tuple(stylised.shape)} and {tuple(mask.shape)}")
-    return _colour_call("localized_combine_u8", lib().adain_localized_combine_u8, (content, stylised, mask), out)
+    return _colour_call("localized_combine_u8", (content, stylised, mask), out)
 
 
 def resize_area_u8(frames, dsize):
     """cv2.resize(frame, dsize, interpolation=cv2.INTER_AREA) on uint8 HWC frames: [h,w,c] or a batch [n,h,w,c];
     ``dsize`` = (width, height) as in cv2 (reference video/utils.py:352-353): the true-area branch when both axes shrink
     or stay, OpenCV's fixed-point linear emulation when one is enlarged."""
-    frames = _dev(frames, "frames", torch.uint8)
+    frames = device_tensor(frames, "frames", torch.uint8)
     single = frames.dim() == 3
     if single:
         frames = frames.unsqueeze(0)
@@ -632,9 +631,7 @@ def resize_area_u8(frames, dsize):
         raise AdainHipError(f"resize_area_u8: expected [h,w,c] or [n,h,w,c] uint8, got {tuple(frames.shape)}")
     n, hi, wi, c = frames.shape
     wo, ho = int(dsize[0]), int(dsize[1])
-    out = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=frames.device)
-    with torch.cuda.device(frames.device):
-        _check(lib().adain_resize_area_u8(frames.data_ptr(), out.data_ptr(), n, hi, wi, c, ho, wo, _stream()), "adain_resize_area_u8")
+    out = _map("adain_resize_area_u8", frames, (n, ho, wo, c), n, hi, wi, c, ho, wo, dtype=torch.uint8)
     return out[0] if single else out
 
 
@@ -645,7 +642,7 @@ def resize_pil_bilinear_u8(frames, size, crop=None, out=None):
     """``PIL.Image.resize(size, BILINEAR)`` of uint8 images on the device, bit for bit (test.py:16-24's Resize on a PIL image).
     frames: uint8 [n,h,w,3] (packed RGB) or [n,h,w,4] (Pillow's RGBX storage); ``size`` = (width, height) as PIL takes it;
     ``crop`` = (top, left, height, width) window of the result (CenterCrop), default all of it.  Returns packed RGB uint8 [n,ch,cw,3]."""
-    x = _dev(frames, "frames", torch.uint8)
+    x = device_tensor(frames, "frames", torch.uint8)
     if x.dim() != 4 or x.shape[3] not in (3, 4):
         raise AdainHipError(f"resize_pil_bilinear_u8: expected uint8 [n,h,w,3|4], got {tuple(x.shape)}")
     n, hi, wi, pix = x.shape
@@ -654,13 +651,11 @@ def resize_pil_bilinear_u8(frames, size, crop=None, out=None):
     if out is None:
         out = torch.empty((n, max(ch, 0), max(cw, 0), 3), dtype=torch.uint8, device=x.device)
     else:
-        _check_buffer(out, "resize_pil_bilinear_u8: out", torch.uint8, x.device, shape=(n, ch, cw, 3))
+        check_buffer(out, "resize_pil_bilinear_u8: out", torch.uint8, x.device, shape=(n, ch, cw, 3))
     # the tap tables live in the stream's workspace between the call's two launches: calls from several threads (the job feeders'
     # fetch pool) on one stream must not interleave
-    with _pil_lock, torch.cuda.device(x.device):
-        ws = workspace(x.device, "pil", lib().adain_resize_pil_bilinear_u8_workspace_bytes(hi, wi, ho, wo))
-        _check(lib().adain_resize_pil_bilinear_u8(x.data_ptr(), pix, n, hi, wi, out.data_ptr(), ho, wo, y0, x0, ch, cw, ws.data_ptr(), ws.numel(),
-                                                  _stream()), "adain_resize_pil_bilinear_u8")
+    with _pil_lock, scratch(x.device, "pil", "adain_resize_pil_bilinear_u8_workspace_bytes", hi, wi, ho, wo) as ws:
+        _launch("adain_resize_pil_bilinear_u8", x.data_ptr(), pix, n, hi, wi, out.data_ptr(), ho, wo, y0, x0, ch, cw, ws.data_ptr(), ws.numel())
     return out
 
 
@@ -674,7 +669,7 @@ def jpeg_encode_sizes(n, h, w, c):
     stride, ws = _c_size_t(), _c_size_t()
     rc = lib().adain_jpeg_encode_u8_bytes(int(n), int(h), int(w), int(c), ctypes.byref(stride), ctypes.byref(ws))
     if rc != 0:
-        raise AdainHipError(f"adain_jpeg_encode_u8_bytes failed ({rc}): {lib().adain_last_error().decode()}")
+        raise _failure("adain_jpeg_encode_u8_bytes", rc)
     return stride.value, ws.value
 
 
@@ -684,7 +679,7 @@ def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY):
     format="JPEG", quality=quality)`` writes; the rest of the row is not written.  Nothing is copied to the host and nothing waits."""
     if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
         raise AdainHipError(f"jpeg_encode_u8: quality must be an int in 1..100, got {quality!r}")
-    x = _dev(u8, "frames", torch.uint8)
+    x = device_tensor(u8, "frames", torch.uint8)
     if x.dim() == 2:
         x = x[None, :, :, None]
     elif x.dim() == 3:
@@ -692,13 +687,17 @@ def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY):
     if x.dim() != 4 or x.shape[3] not in (1, 3) or x.shape[0] < 1:
         raise AdainHipError(f"jpeg_encode_u8: expected uint8 [n,h,w,3|1], [h,w,3|1] or [h,w], got {tuple(u8.shape)}")
     n, h, w, c = x.shape
-    stride, nbytes = jpeg_encode_sizes(n, h, w, c)
-    out = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
-    lengths = torch.empty((n,), dtype=torch.int32, device=x.device)
-    with torch.cuda.device(x.device):
-        ws = workspace(x.device, "jpeg", nbytes)
-        _check(lib().adain_jpeg_encode_u8(x.data_ptr(), n, h, w, c, quality, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          _stream()), "adain_jpeg_encode_u8")
+    stride = 0
+
+    def sizes():                # one query answers both: the file stride is kept for the output below
+        nonlocal stride
+        stride, nbytes = jpeg_encode_sizes(n, h, w, c)
+        return nbytes
+
+    with scratch(x.device, "jpeg", sizes) as ws:
+        out = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
+        lengths = torch.empty((n,), dtype=torch.int32, device=x.device)
+        _launch("adain_jpeg_encode_u8", x.data_ptr(), n, h, w, c, quality, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
     return out, lengths
 
 
@@ -710,90 +709,81 @@ def jpeg_files(out, lengths):
 
 
 def nhwc_to_nchw(x):
-    x = _dev(x, "x")
+    x = device_tensor(x, "x")
     n, h, w, c = x.shape
-    out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().adain_nhwc_to_nchw(x.data_ptr(), out.data_ptr(), n, c, h * w, _stream()), "adain_nhwc_to_nchw")
-    return out
+    return _map("adain_nhwc_to_nchw", x, (n, c, h, w), n, c, h * w)
 
 
 def nchw_to_nhwc(x):
-    x = _dev(x, "x")
+    x = device_tensor(x, "x")
     n, c, h, w = x.shape
-    out = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().adain_nchw_to_nhwc(x.data_ptr(), out.data_ptr(), n, c, h * w, _stream()), "adain_nchw_to_nhwc")
-    return out
+    return _map("adain_nchw_to_nhwc", x, (n, h, w, c), n, c, h * w)
 
 
 # --- single conv layer (tests / profiling) -------------------------------------------------------------------------------------
+def _pack_layer(which, w_oihw):
+    w = device_tensor(w_oihw, "weight")
+    cout, cin = w.shape[:2]
+    return _map(f"adain_conv3x3_{which}_pack", w, getattr(lib(), f"adain_conv3x3_{which}_packed_floats")(cin, cout), cin, cout)
+
+
 def conv3x3_wino_pack(w_oihw, form=5):
     """Packed transformed weights U = G4 g G2^T for conv3x3_wino / conv3x3_wino4_split (24 floats per (cin, cout) pair)."""
     if form != 5:
         raise AdainHipError(f"conv3x3_wino_pack: form {form} is retired; the library runs form 5, F(4,3) x F(2,3)")
-    w = _dev(w_oihw, "weight")
-    cout, cin = w.shape[:2]
-    packed = torch.empty(lib().adain_conv3x3_wino4_packed_floats(cin, cout), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _check(lib().adain_conv3x3_wino4_pack(w.data_ptr(), packed.data_ptr(), cin, cout, _stream()), "adain_conv3x3_wino4_pack")
-    return packed
-
-
-def conv3x3_wino(x_nhwc, packed_w, bias, cout, src_mode=SRC_DIRECT, relu=True, pool_out=False, m_tiles=5):
-    """One generic 3x3 layer, ReflectionPad2d(1) + Conv2d [+ ReLU] [+ fused ceil-mode pool] on NHWC, in the form the schedules run
-    (``m_tiles`` = the C ABI's `form`, 5 = F(4,3) x F(2,3); weights packed by conv3x3_wino_pack)."""
-    x = _dev(x_nhwc, "x")
-    n, hs, ws_, cin = x.shape
-    h, w = (2 * hs, 2 * ws_) if src_mode == SRC_UP2X else (hs, ws_)
-    oh, ow = ((h + 1) // 2, (w + 1) // 2) if pool_out else (h, w)
-    out = torch.empty((n, oh, ow, cout), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().adain_conv3x3_wino(x.data_ptr(), out.data_ptr(), packed_w.data_ptr(), bias.data_ptr(), n, h, w, hs, ws_, cin, cout,
-                                        src_mode, int(relu), int(pool_out), int(m_tiles), _stream()), "adain_conv3x3_wino")
-    return out
+    return _pack_layer("wino4", w_oihw)
 
 
 def conv3x3_up2x_poly_pack(w_oihw):
     """Packed weights of the polyphase up layer (adain_conv3x3_up2x_poly_pack): per output phase the folded 2 x 2 filter in
     Winograd F(5,2) x F(3,2), 96 floats per (cin, cout) pair."""
-    w = _dev(w_oihw, "weight")
-    cout, cin = w.shape[:2]
-    packed = torch.empty(lib().adain_conv3x3_up2x_poly_packed_floats(cin, cout), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _check(lib().adain_conv3x3_up2x_poly_pack(w.data_ptr(), packed.data_ptr(), cin, cout, _stream()), "adain_conv3x3_up2x_poly_pack")
-    return packed
+    return _pack_layer("up2x_poly", w_oihw)
+
+
+def _conv_layer(x, cout, src_mode, pool_out):
+    """A generic 3x3 layer over NHWC ``x``: ((n, h, w, hs, ws, cin), empty NHWC result) - h x w is the conv's own size, the source's
+    hs x ws doubled under SRC_UP2X; the result is that, halved (rounding up) under ``pool_out``."""
+    n, hs, ws_, cin = x.shape
+    h, w = (2 * hs, 2 * ws_) if src_mode == SRC_UP2X else (hs, ws_)
+    oh, ow = ((h + 1) // 2, (w + 1) // 2) if pool_out else (h, w)
+    return (n, h, w, hs, ws_, cin), torch.empty((n, oh, ow, cout), dtype=torch.float32, device=x.device)
+
+
+def conv3x3_wino(x_nhwc, packed_w, bias, cout, src_mode=SRC_DIRECT, relu=True, pool_out=False, m_tiles=5):
+    """One generic 3x3 layer, ReflectionPad2d(1) + Conv2d [+ ReLU] [+ fused ceil-mode pool] on NHWC, in the form the schedules run
+    (``m_tiles`` = the C ABI's `form`, 5 = F(4,3) x F(2,3); weights packed by conv3x3_wino_pack)."""
+    x = device_tensor(x_nhwc, "x")
+    dims, out = _conv_layer(x, cout, src_mode, pool_out)
+    call("adain_conv3x3_wino", x.device, x.data_ptr(), out.data_ptr(), packed_w.data_ptr(), bias.data_ptr(), *dims, cout, src_mode, int(relu),
+         int(pool_out), int(m_tiles))
+    return out
 
 
 def conv3x3_up2x_poly(x_nhwc, packed_w, bias, cout, relu=True):
     """The decoder's up layer as the schedules run it: nearest 2x upsample + ReflectionPad2d(1) + Conv2d [+ ReLU] on NHWC, as four
     phase convolutions of the source (weights packed by conv3x3_up2x_poly_pack)."""
-    x = _dev(x_nhwc, "x")
+    x = device_tensor(x_nhwc, "x")
     n, hs, ws_, cin = x.shape
     out = torch.empty((n, 2 * hs, 2 * ws_, cout), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().adain_conv3x3_up2x_poly(x.data_ptr(), out.data_ptr(), packed_w.data_ptr(), bias.data_ptr(), n, hs, ws_, cin, cout,
-                                             int(relu), _stream()), "adain_conv3x3_up2x_poly")
+    call("adain_conv3x3_up2x_poly", x.device, x.data_ptr(), out.data_ptr(), packed_w.data_ptr(), bias.data_ptr(), n, hs, ws_, cin, cout,
+         int(relu))
     return out
 
 
 def conv3x3_wino4_split_bytes(n, h, w, cin, cout):
-    """Bytes of partial-sum slabs a launch of this layer needs to be split along cin; 0: it would not be split."""
+    """Bytes of partial-sum slabs a launch of this layer needs to be split along cin; 0: it would not be split.  For the device
+    that is current on the calling thread (its compute units decide the split)."""
     return lib().adain_conv3x3_wino4_split_workspace_bytes(int(n), int(h), int(w), int(cin), int(cout))
 
 
 def conv3x3_wino4_split(x_nhwc, packed_w, bias, cout, src_mode=SRC_DIRECT, relu=True, pool_out=False):
     """The F(4,3) x F(2,3) layer as the latency schedule runs it: split along cin when the launch is smaller than the chip
     (adain_conv3x3_wino4_split; weights packed by conv3x3_wino_pack(form=5))."""
-    x = _dev(x_nhwc, "x")
-    n, hs, ws_, cin = x.shape
-    h, w = (2 * hs, 2 * ws_) if src_mode == SRC_UP2X else (hs, ws_)
-    oh, ow = ((h + 1) // 2, (w + 1) // 2) if pool_out else (h, w)
-    out = torch.empty((n, oh, ow, cout), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        nbytes = conv3x3_wino4_split_bytes(n, h, w, cin, cout)
-        ws = workspace(x.device, "conv_split", nbytes) if nbytes else None
-        _check(lib().adain_conv3x3_wino4_split(x.data_ptr(), out.data_ptr(), packed_w.data_ptr(), bias.data_ptr(), n, h, w, hs, ws_, cin, cout,
-                                               src_mode, int(relu), int(pool_out), ws.data_ptr() if ws is not None else None, nbytes, _stream()),
-               "adain_conv3x3_wino4_split")
+    x = device_tensor(x_nhwc, "x")
+    dims, out = _conv_layer(x, cout, src_mode, pool_out)
+    n, h, w, _hs, _ws, cin = dims
+    # a launch that would not be split (a 0 answer) ignores the slabs it is handed
+    with scratch(x.device, "conv_split", "adain_conv3x3_wino4_split_workspace_bytes", n, h, w, cin, cout) as ws:
+        _launch("adain_conv3x3_wino4_split", x.data_ptr(), out.data_ptr(), packed_w.data_ptr(), bias.data_ptr(), *dims, cout, src_mode,
+                int(relu), int(pool_out), ws.data_ptr(), ws.numel())
     return out

@@ -76,7 +76,7 @@ class TVL1:
 
     def prepare(self, gray, out=None):
         """uint8 gray [h,w] -> float32 [frame_floats]; [n,h,w] -> [n, frame_floats]."""
-        g = rt._dev(gray, "gray", torch.uint8)
+        g = rt.device_tensor(gray, "gray", torch.uint8)
         single = g.dim() == 2
         if single:
             g = g.unsqueeze(0)
@@ -86,10 +86,8 @@ class TVL1:
         if out is None:
             out = torch.empty((n, self.frame_floats), dtype=torch.float32, device=g.device)
         else:
-            rt._check_buffer(out, "tvl1: out", torch.float32, g.device, numel=n * self.frame_floats, align=256)
-        with torch.cuda.device(g.device):
-            rt._check(rt.lib().adain_tvl1_prepare(g.data_ptr(), n, self.h, self.w, ctypes.addressof(self.P), out.data_ptr(), rt._stream()),
-                      "adain_tvl1_prepare")
+            rt.check_buffer(out, "tvl1: out", torch.float32, g.device, numel=n * self.frame_floats, align=256)
+        rt.call("adain_tvl1_prepare", g.device, g.data_ptr(), n, self.h, self.w, ctypes.addressof(self.P), out.data_ptr())
         return out.view(self.frame_floats) if single else out.view(n, self.frame_floats)
 
     def prepared_views(self, prep):
@@ -112,21 +110,18 @@ class TVL1:
         dev = prev_list[0].device
         for t in list(prev_list) + list(next_list):
             # prepare() writes each frame 256-byte aligned; the kernels read it as float4 at 256-byte aligned scale offsets
-            rt._check_buffer(t, "tvl1: each of the prepared frames (made by prepare())", torch.float32, dev, min_numel=self.frame_floats,
-                             align=256)
+            rt.check_buffer(t, "tvl1: each of the prepared frames (made by prepare())", torch.float32, dev, min_numel=self.frame_floats,
+                            align=256)
         if out is None:
             out = torch.empty((n, 2, self.h, self.w), dtype=torch.float32, device=dev)
         else:
-            rt._check_buffer(out, "tvl1: out", torch.float32, dev, shape=(n, 2, self.h, self.w))
+            rt.check_buffer(out, "tvl1: out", torch.float32, dev, shape=(n, 2, self.h, self.w))
         if iters_out is not None:
-            rt._check_buffer(iters_out, "tvl1: iters_out", torch.int32, dev, shape=(n, len(self.scales), self.P.warps))
+            rt.check_buffer(iters_out, "tvl1: iters_out", torch.int32, dev, shape=(n, len(self.scales), self.P.warps))
         ptrs = torch.tensor([t.data_ptr() for t in prev_list] + [t.data_ptr() for t in next_list], dtype=torch.int64).to(dev)
-        nbytes = self.workspace_bytes(n)
-        ws = rt.workspace(dev, "tvl1", nbytes)
-        with torch.cuda.device(dev):
-            rt._check(rt.lib().adain_tvl1_flow(ptrs.data_ptr(), ptrs.data_ptr() + 8 * n, n, self.h, self.w, ctypes.addressof(self.P),
-                                               out.data_ptr(), iters_out.data_ptr() if iters_out is not None else None, ws.data_ptr(),
-                                               ws.numel(), rt._stream()), "adain_tvl1_flow")
+        ws = rt.workspace(dev, "tvl1", self.workspace_bytes(n))
+        rt.call("adain_tvl1_flow", dev, ptrs.data_ptr(), ptrs.data_ptr() + 8 * n, n, self.h, self.w, ctypes.addressof(self.P), out.data_ptr(),
+                iters_out.data_ptr() if iters_out is not None else None, ws.data_ptr(), ws.numel())
         return out
 
     def default_max_pairs(self, budget=512 << 20):
@@ -214,7 +209,7 @@ class TVL1Sequence:
         if out is None:
             out = torch.empty((n - 1, 2, h, w), dtype=torch.float32, device=grays[0].device)
         else:
-            rt._check_buffer(out, "TVL1Sequence.batch: out", torch.float32, grays[0].device, shape=(n - 1, 2, h, w))
+            rt.check_buffer(out, "TVL1Sequence.batch: out", torch.float32, grays[0].device, shape=(n - 1, 2, h, w))
         ring = torch.empty((m + 1, tv.frame_floats), dtype=torch.float32, device=grays[0].device)
 
         def prepare(a, b):                  # frames a..b-1 into their slots, in contiguous runs of the ring

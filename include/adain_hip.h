@@ -81,7 +81,9 @@ ADAIN_API int adain_decoder_pack(const float* const* w_host_array_of_dev_ptrs, c
 /* ---- encoder: vgg[:31](x), conv0 .. relu4_1 (net.py:38-69; test.py:57,63,76-77,185) -----------------
  * image NCHW [n][3][h][w] -> feat NHWC [n][hc][wc][512], hc = ceil(ceil(ceil(h/2)/2)/2) (same for w).
  * layer_events: optional host array of 11 hipEvent_t recorded before layer 0 and after each of the
- * 10 conv launches (profiling only; NULL in production). */
+ * 10 conv launches (profiling only; NULL in production).
+ * adain_encode_workspace_bytes answers for the device that is current on the calling thread (its compute-unit count sizes the
+ * cin-split slabs of ADAIN_SCHEDULE_LATENCY): ask it with the device current on which the call will run. */
 ADAIN_API void adain_encoded_size(int h, int w, int* hc, int* wc);
 ADAIN_API size_t adain_encode_workspace_bytes(int n, int h, int w);
 ADAIN_API int adain_encode(const float* image_nchw, float* feat_nhwc, const float* packed, void* workspace,
@@ -105,14 +107,16 @@ ADAIN_API int adain_encode_relu1_1(const void* image, int is_u8, float* relu1_1_
  * of a style_transfer call go through the same vgg (test.py:57,63 / :76-77).  Results are bit-identical to one adain_encode
  * per batch; every generic 3x3 layer is a single launch whose tile list covers all batches, so the small style-branch layers
  * ride in the content launches instead of under-filling the chip on their own.  images[i] NCHW [n[i]][3][h[i]][w[i]] ->
- * feats[i] NHWC.  The pointer arrays and n / h / w are HOST arrays.  layer_events as for adain_encode. */
+ * feats[i] NHWC.  The pointer arrays and n / h / w are HOST arrays.  layer_events as for adain_encode.
+ * adain_encode_multi_workspace_bytes, like adain_encode_workspace_bytes, answers for the device current on the calling thread. */
 ADAIN_API size_t adain_encode_multi_workspace_bytes(int count, const int* n, const int* h, const int* w);
 ADAIN_API int adain_encode_multi(int count, const float* const* images_nchw, float* const* feats_nhwc, const int* n, const int* h,
                        const int* w, const float* packed, void* workspace, size_t workspace_bytes,
                        void* const* layer_events, adain_stream_t stream);
 
 /* ---- decoder: net.decoder(feat) (net.py:6-36; test.py:71,81) ----------------------------------------
- * feat NHWC [n][hc][wc][512] -> image NCHW [n][3][8hc][8wc].  layer_events: 10 events (before + 9 convs). */
+ * feat NHWC [n][hc][wc][512] -> image NCHW [n][3][8hc][8wc].  layer_events: 10 events (before + 9 convs).
+ * adain_decode_workspace_bytes, like adain_encode_workspace_bytes, answers for the device current on the calling thread. */
 ADAIN_API size_t adain_decode_workspace_bytes(int n, int hc, int wc);
 ADAIN_API int adain_decode(const float* feat_nhwc, float* image_nchw, const float* packed, void* workspace,
                  size_t workspace_bytes, int n, int hc, int wc, void* const* layer_events, adain_stream_t stream);
@@ -329,7 +333,9 @@ ADAIN_API int adain_resize_pil_bilinear_u8(const uint8_t* in_u8, int pixel_bytes
  * image, once per style); depth_maps / depth_h / depth_w: HOST arrays of n device pointers / sizes; mask [mask_n][mask_c]
  * [mask_h][mask_w], mask_n in {1, n}, mask_c in {1, 3}, uint8 / bool bytes (mask_is_float == 0) or float; out_u8 HWC uint8
  * [n][oh][ow][3] with (oh, ow) = adain_stylize_u8_out_size: the frame's size with a mask, 8hc x 8wc without.  One workspace
- * (adain_stylize_u8_workspace_bytes) holds every intermediate.  21-27 kernel launches, no allocation, no synchronisation. */
+ * (adain_stylize_u8_workspace_bytes) holds every intermediate.  21-27 kernel launches, no allocation, no synchronisation.
+ * adain_stylize_u8_workspace_bytes contains the encoder's and the decoder's and, like them, answers for the device current on the
+ * calling thread. */
 ADAIN_API size_t adain_stylize_u8_workspace_bytes(int n, int h, int w, int use_depth, int mask_n, int mask_c, int mask_h, int mask_w,
                                         int mask_is_float);
 ADAIN_API void adain_stylize_u8_out_size(int h, int w, int has_mask, int* oh, int* ow);
@@ -386,8 +392,9 @@ ADAIN_API int adain_conv3x3_wino(const float* in_nhwc, float* out_nhwc, const fl
 
 /* The same layer (form 5) as ADAIN_SCHEDULE_LATENCY runs it, whatever the calling thread's schedule: split along cin when the launch
  * has fewer tiles than compute units.  *_workspace_bytes = the partial-sum slabs that launch needs (S x n x h x w x cout floats;
- * 0: it would not be split, and adain_conv3x3_wino4_split then is adain_conv3x3_wino).  For unit tests and the per-layer error
- * probe (tools/probes/wino_error_gpu.py). */
+ * 0: it would not be split, and adain_conv3x3_wino4_split then is adain_conv3x3_wino).  The query answers for the device current on
+ * the calling thread, whose compute units decide the split.  For unit tests and the per-layer error probe
+ * (tools/probes/wino_error_gpu.py). */
 ADAIN_API size_t adain_conv3x3_wino4_split_workspace_bytes(int n, int h, int w, int cin, int cout);
 ADAIN_API int adain_conv3x3_wino4_split(const float* in_nhwc, float* out_nhwc, const float* packed_w, const float* bias, int n, int h,
                               int w, int hs, int ws, int cin, int cout, int src_mode, int relu, int pool_out, void* workspace,
