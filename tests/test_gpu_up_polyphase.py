@@ -10,42 +10,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-# transforms of the kernel (input: B4^T, d B2 by columns j; output: A5^T, A3; filters: G5, G3)
-B4T = np.array([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0], [0, 4, 0, -5, 0, 1]], float)
-B2T = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], float)
-A5T = np.array([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 0], [0, 1, 1, 16, 16, 1]], float)
-A3T = np.array([[1, 1, 1, 0], [0, 1, -1, 0], [0, 1, 1, 1]], float)
-G5 = np.array([[1 / 4, 0], [-1 / 6, -1 / 6], [-1 / 6, 1 / 6], [1 / 24, 1 / 12], [1 / 24, -1 / 12], [0, 1]])
-G3 = np.array([[1, 0], [1 / 2, 1 / 2], [1 / 2, -1 / 2], [0, -1]])
-FOLD = [np.array([[1, 0, 0], [0, 1, 1]], float), np.array([[1, 1, 0], [0, 0, 1]], float)]      # even / odd phase
+# transforms of the kernel and its algebra in numpy: tests/conv_exact.py holds the one copy
+from conv_exact import A3T, A5T, B2T, B4T, FOLD, G3, G5, polyphase  # noqa: F401
 
 
 def reference(x, w):
     """x [cin][hs][ws], w [cout][cin][3][3] -> [cout][2 hs][2 ws], float64"""
     up = F.interpolate(torch.from_numpy(x)[None], scale_factor=2, mode="nearest")
     return F.conv2d(F.pad(up, (1, 1, 1, 1), mode="reflect"), torch.from_numpy(w))[0].numpy()
-
-
-def polyphase(x, w):
-    """The kernel's algebra in float64: per phase, tiles of 4 x 3 outputs (rows 0-3 of F(5,2)) of the clamp-padded source, 6 x 4
-    patches."""
-    cin, hs, ws = x.shape
-    cout = w.shape[0]
-    out = np.zeros((cout, 2 * hs, 2 * ws))
-    for py in range(2):
-        for px in range(2):
-            h = np.einsum("at,oits,bs->oiab", FOLD[py], w, FOLD[px])             # folded 2 x 2 filters
-            U = np.einsum("ra,oiab,jb->oirj", G5, h, G3)
-            for ty in range(0, hs, 4):
-                for tx in range(0, ws, 3):
-                    ys = np.clip(np.arange(ty - 1 + py, ty + 5 + py), 0, hs - 1)
-                    xs = np.clip(np.arange(tx - 1 + px, tx + 3 + px), 0, ws - 1)
-                    V = np.einsum("ra,iac,jc->irj", B4T, x[:, ys][:, :, xs], B2T)
-                    M = np.einsum("oirj,irj->orj", U, V)
-                    Y = np.einsum("ar,orj,bj->oab", A5T, M, A3T)
-                    ny, nx = min(4, hs - ty), min(3, ws - tx)
-                    out[:, 2 * ty + py:2 * (ty + ny):2, 2 * tx + px:2 * (tx + nx):2] = Y[:, :ny, :nx]
-    return out
 
 
 @pytest.mark.parametrize("cin,cout,hs,ws", [(3, 2, 7, 8), (2, 3, 1, 1), (4, 2, 2, 5), (2, 2, 11, 4)])
