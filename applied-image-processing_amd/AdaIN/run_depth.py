@@ -5,14 +5,15 @@ Style_3DGS/AdaIN/run_depth.py (:13-55), so existing invocations keep working:
 
 Extra flags make the depth-aware mode usable offline (the reference pulls MiDaS through torch.hub at run time):
 ``--depth_npy`` takes a precomputed proximity map, ``--vgg`` / ``--decoder`` the checkpoint paths; ``--jpeg_on_device`` encodes the
-result's JPEG file on the GPU (the same bytes).
+result's JPEG file on the GPU (the same bytes); ``--coral_on_device`` preserves the content's colours (``adain_inference``'s
+``preserve_color``, which the reference's CLI does not expose) with CORAL computed on the GPU.
 """
 import argparse
 
 import numpy as np
 import torch
 
-from .test import adain_inference, set_device_jpeg
+from .test import adain_inference, set_device_coral, set_device_jpeg
 
 # (flag, argparse keyword arguments) — names and defaults as in the reference CLI
 _REFERENCE_FLAGS = (
@@ -29,6 +30,7 @@ _EXTRA_FLAGS = (
     ("--vgg", dict(type=str, default="Style_3DGS/AdaIN/models/vgg_normalised.pth", help="encoder state_dict")),
     ("--decoder", dict(type=str, default="Style_3DGS/AdaIN/models/decoder.pth", help="decoder state_dict")),
     ("--jpeg_on_device", dict(action="store_true", help="encode the output JPEG on the GPU instead of in PIL (byte-identical file)")),
+    ("--coral_on_device", dict(action="store_true", help="preserve the content's colours (preserve_color) with CORAL computed on the GPU")),
 )
 
 
@@ -41,12 +43,14 @@ def main(argv=None):
     if ns.depth_npy:
         proximity = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
     prev = set_device_jpeg(ns.jpeg_on_device)
+    prev_coral = set_device_coral(ns.coral_on_device)
     try:
         return adain_inference(ns.content, ns.style, vgg_str=ns.vgg, decoder_str=ns.decoder, depth_offset=ns.depth_offset,
                                depth_prominence=ns.depth_prominence, output=ns.output, file_name=ns.file_name,
-                               use_depth=ns.use_depth, depth_map=proximity)
+                               use_depth=ns.use_depth, depth_map=proximity, preserve_color=ns.coral_on_device)
     finally:
         set_device_jpeg(prev)
+        set_device_coral(prev_coral)
 
 
 if __name__ == "__main__":

@@ -267,6 +267,21 @@ def set_device_jpeg(enabled):
     return prev
 
 
+_device_coral_on = False
+STYLE_PIXEL_UPLOADS = [0]             # style images whose pixels the device CORAL path brought to the device (tests count it)
+
+
+def set_device_coral(enabled):
+    """True: ``adain_inference(preserve_color=True)`` takes the cached one-call path too: the resized style's PIXELS are kept on the
+    device per style (``_style_key``), and every call runs ``coral(style, content)`` there (adain_coral), encodes the recoloured
+    style, takes its statistics and styles the frame with them in ``adain_stylize_u8`` - nothing of it on the host.  The file is
+    within one LSB of the default's (CORAL in float64 instead of float32).  Default False: CORAL runs on CPU tensors as in the
+    reference (test.py:201-202) through the call-by-call path.  Returns the previous setting."""
+    global _device_coral_on
+    prev, _device_coral_on = _device_coral_on, bool(enabled)
+    return prev
+
+
 def _is_jpeg_path(path):
     return str(path).lower().endswith((".jpg", ".jpeg"))
 
@@ -318,9 +333,9 @@ def _style_key(style_img, what, style_size, crop, enc, device):
     """Cache key of a style image: a file by (resolved path, mtime, size) - a rewritten file is another style -, an image object
     by identity (guarded by a weak reference: a dead object's id may be reused) AND a fingerprint of its pixels (an object edited
     in place is another style: the reference re-encodes every call, test.py:63 / :77), plus everything else the result depends on:
-    ``style_size``, ``crop``, the device and the encoder's parameter state (``load_state_dict`` / ``.to()`` / in-place edits
-    all change it).  None = not cacheable."""
-    params = (str(device),) + _param_state(enc)
+    ``style_size``, ``crop``, the device, the launch schedule (statistics computed under ADAIN_SCHEDULE_LATENCY differ in the last
+    bits) and the encoder's parameter state (``load_state_dict`` / ``.to()`` / in-place edits all change it).  None = not cacheable."""
+    params = (str(device), bool(_latency_schedule_on)) + _param_state(enc)
     if type(style_img) == str or isinstance(style_img, Path):
         try:
             p = Path(style_img).resolve()
@@ -499,7 +514,7 @@ def adain_inference(
 
     t0 = time.perf_counter()
     pil_content = Image.open(content_img) if type(content_img) == str else content_img
-    if _style_cache_on and not preserve_color and isinstance(enc, net.HipVGG) and isinstance(dec, net.HipDecoder):
+    if _style_cache_on and (not preserve_color or _device_coral_on) and isinstance(enc, net.HipVGG) and isinstance(dec, net.HipDecoder):
         # one style, many calls (video/utils.py:341-350, train.py:101): statistics from the cache, the frame in one C-ABI call
         pil_content.load()                                               # decode (a lazily opened file) - host work that stays
         T("open + decode content (PIL)", t0)
@@ -516,8 +531,14 @@ def adain_inference(
             if use_depth:
                 assert 0.0 <= depth_offset <= 1.0                        # test.py:56
             t0 = time.perf_counter()
-            stats = _style_stats(style_img, style_size, crop, enc, device, drop_alpha=use_depth)
-            T("style statistics (cached after the first call)", t0)
+            if preserve_color:
+                if not isinstance(frame, torch.Tensor):
+                    frame = torch.from_numpy(frame if frame.flags.writeable else frame.copy()).unsqueeze(0).to(device)
+                stats = _coral_style_stats(style_img, frame, style_size, crop, enc, device)
+                T("CORAL + style statistics (device, per call)", t0)
+            else:
+                stats = _style_stats(style_img, style_size, crop, enc, device, drop_alpha=use_depth)
+                T("style statistics (cached after the first call)", t0)
             if stats is not None:
                 _one_call(frame, stats, enc, dec, device, alpha, use_depth, depth_map, pil_content, depth_offset, depth_prominence, content_mask,
                           target, e0 if (T.on and isinstance(frame, torch.Tensor)) else None)
@@ -605,6 +626,28 @@ def _style_stats(style_img, style_size, crop, enc, device, drop_alpha):
 
     # an RGBA style gives other statistics on the depth path (alpha dropped) than on the alpha path (refused): part of the key
     return _cached_style(style_img, ("stats", bool(drop_alpha)), style_size, crop, enc, device, make)
+
+
+def _coral_style_stats(style_img, frame, style_size, crop, enc, device):
+    """(mean, std), each [1,512], of ``coral(style, content)``'s relu4_1 features (test.py:201-202, :77) for the resized frame uint8
+    [1,h,w,3] on the device.  The resized style's pixels are kept on the device per style (``_style_key``); CORAL, the encoder and
+    the statistics run per call, because the recoloured style depends on the frame.  None when the transformed style is not a
+    3-channel image (the call-by-call path reports it)."""
+    def make():
+        pil_style = Image.open(str(style_img)) if type(style_img) == str or isinstance(style_img, Path) else style_img
+        STYLE_PIXEL_UPLOADS[0] += 1
+        u8 = device_transform_u8(pil_style, style_size, crop, device)
+        if u8 is not None:
+            return u8
+        style = test_transform(style_size, crop)(pil_style)
+        return style.unsqueeze(0).to(device).contiguous() if style.shape[0] == 3 else None
+
+    pixels = _cached_style(style_img, "pixels", style_size, crop, enc, device, make)
+    if pixels is None:
+        return None
+    STYLE_ENCODES[0] += 1
+    recoloured, _record = rt.coral(pixels, frame)
+    return rt.mean_std(rt.encode(recoloured, enc.packed(device)), True)
 
 
 def _one_call(frame, stats, enc, dec, device, alpha, use_depth, depth_map, pil_content, depth_offset, depth_prominence, content_mask, target,

@@ -592,12 +592,26 @@ void adain_stylize_u8_out_size(int h, int w, int has_mask, int* oh, int* ow) {
     if (ow) *ow = has_mask ? w : 8 * wc;
 }
 
+size_t adain_stylize_u8_ex_workspace_bytes(int n, int h, int w, int use_depth, int mask_n, int mask_c, int mask_h, int mask_w, int mask_is_float) {
+    return adain_stylize_u8_workspace_bytes(n, h, w, use_depth, mask_n, mask_c, mask_h, mask_w, mask_is_float);
+}
+
 int adain_stylize_u8(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const float* s_mean,
                      const float* s_std, float alpha, float one_minus_alpha, const float* const* depth_maps, const int* depth_h, const int* depth_w,
                      float depth_offset, float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c, int mask_h,
                      int mask_w, uint8_t* out_u8, void* workspace, size_t ws_bytes, adain_stream_t stream) {
+    return adain_stylize_u8_ex(frames, n, h, w, enc_packed, dec_packed, s_mean, s_std, 1, alpha, one_minus_alpha, depth_maps, depth_h, depth_w,
+                               depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes, stream);
+}
+
+// s_mean / s_std [style_n][512], style_n 1 (adain_stylize_u8) or n: one style per frame
+int adain_stylize_u8_ex(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const float* s_mean,
+                        const float* s_std, int style_n, float alpha, float one_minus_alpha, const float* const* depth_maps, const int* depth_h,
+                        const int* depth_w, float depth_offset, float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c,
+                        int mask_h, int mask_w, uint8_t* out_u8, void* workspace, size_t ws_bytes, adain_stream_t stream) {
     if (!frames || !enc_packed || !dec_packed || !s_mean || !s_std || !out_u8 || !workspace) { set_error("stylize_u8: null pointer"); return ADAIN_EINVAL; }
     if (n < 1 || h < 9 || w < 9) { set_error("stylize_u8: frames %dx%d too small (needs h, w >= 9)", h, w); return ADAIN_EINVAL; }
+    if (style_n != 1 && style_n != n) { set_error("stylize_u8: %d styles for %d frames (1 or one per frame)", style_n, n); return ADAIN_EINVAL; }
     if (!depth_maps && !(alpha >= 0.f && alpha <= 1.f)) { set_error("stylize_u8: alpha %g outside [0, 1]", alpha); return ADAIN_EINVAL; }   // test.py:75
     if (depth_maps && (!depth_h || !depth_w)) { set_error("stylize_u8: depth maps without their sizes"); return ADAIN_EINVAL; }
     if (depth_maps && !(depth_offset >= 0.f && depth_offset <= 1.f)) { set_error("stylize_u8: offset %g outside [0, 1]", depth_offset); return ADAIN_EINVAL; }   // test.py:56
@@ -640,9 +654,9 @@ int adain_stylize_u8(const uint8_t* frames, int n, int h, int w, const float* en
             RET_IF(launch_strength_map(depth_maps[i], depth_h[i], depth_w[i], p.hc, p.wc, depth_offset, depth_prominence, pmap + (size_t)i * hw_c,
                                        pmap_ws, p.pmap_ws * sizeof(float), s));
         }
-        RET_IF(launch_adain_blend_ex(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, 1, 0.f, 0.f, pmap, n, g, s));
+        RET_IF(launch_adain_blend_ex(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, style_n, 0.f, 0.f, pmap, n, g, s));
     } else {                // AdaIN * alpha + content_f * (1 - alpha) (test.py:79-80)
-        RET_IF(launch_adain_blend_ex(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, 1, alpha, one_minus_alpha, nullptr, 1, g, s));
+        RET_IF(launch_adain_blend_ex(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, style_n, alpha, one_minus_alpha, nullptr, 1, g, s));
     }
     if (mask_n == 0 && ((uintptr_t)out_u8 & 3) == 0)        // decoder with save_image's quantiser inside its last layer (test.py:71 / :81, :243-244): the finished uint8 frames
         return decode_impl(g, nullptr, out_u8, dec_packed, conv, p.conv * sizeof(float), n, p.hc, p.wc, nullptr, stream);
@@ -670,6 +684,13 @@ int adain_stylize_u8(const uint8_t* frames, int n, int h, int w, const float* en
     }
     RET_IF(launch_mask_composite(content_f, sty, m, mask_c, mask_n, comp, n, 3, h * w, s));
     return launch_quantize_u8(comp, out_u8, n, 3, h, w, s);
+}
+
+size_t adain_coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc) { return coral_workspace_bytes(n, style_n, hs, ws, hc, wc); }
+
+int adain_coral(const void* style, int style_is_u8, int style_n, int hs, int ws, const void* content, int content_is_u8, int n, int hc, int wc,
+                float* out, void* workspace, size_t ws_bytes, adain_stream_t stream) {
+    return launch_coral(style, style_is_u8, style_n, hs, ws, content, content_is_u8, n, hc, wc, out, workspace, ws_bytes, (hipStream_t)stream);
 }
 
 size_t adain_conv3x3_wino4_packed_floats(int cin, int cout) { return (size_t)cin * cout * 24; }

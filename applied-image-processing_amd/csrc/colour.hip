@@ -36,6 +36,7 @@ inline char* adain_env_unset(const char*) { return nullptr; }
 
 #include "../../include/adain_hip.h"
 #include "common.h"
+#include "device_utils.h"
 
 namespace adain {
 
@@ -124,44 +125,6 @@ __global__ __launch_bounds__(CT_THREADS) void colour_moments_kernel(Images im, i
         double t = 0;
         for (int wv = 0; wv < CT_THREADS / 64; ++wv) t += sh[wv][threadIdx.x];
         partial[(size_t)blockIdx.x * 2 * CT_MOMENTS + threadIdx.x] = t;
-    }
-}
-
-// Eigenvalues (the diagonal of a on return) and eigenvectors (the columns of v) of a symmetric 3 x 3 matrix: cyclic Jacobi.
-__device__ void jacobi3(double a[3][3], double v[3][3]) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 32; ++sweep) {
-        if (fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]) == 0.0) break;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                const double apq = a[p][q];
-                if (apq == 0.0) continue;
-                const double g = 100.0 * fabs(apq);
-                if (fabs(a[p][p]) + g == fabs(a[p][p]) && fabs(a[q][q]) + g == fabs(a[q][q])) {   // below the diagonal's rounding
-                    a[p][q] = a[q][p] = 0.0;
-                    continue;
-                }
-                const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-                const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 3; ++k) {
-                    const double akp = a[k][p], akq = a[k][q];
-                    a[k][p] = c * akp - s * akq;
-                    a[k][q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double apk = a[p][k], aqk = a[q][k];
-                    a[p][k] = c * apk - s * aqk;
-                    a[q][k] = s * apk + c * aqk;
-                }
-                a[p][q] = a[q][p] = 0.0;
-                for (int k = 0; k < 3; ++k) {
-                    const double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = c * vkp - s * vkq;
-                    v[k][q] = s * vkp + c * vkq;
-                }
-            }
     }
 }
 

@@ -161,6 +161,11 @@ int jpeg_encode_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* wo
 int launch_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
                           hipStream_t s);
 
+// coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
+size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);
+int launch_coral(const void* style, int style_is_u8, int style_n, int hs, int ws, const void* content, int content_is_u8, int n, int hc, int wc,
+                 float* out, void* workspace, size_t ws_bytes, hipStream_t s);
+
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -20,6 +20,7 @@ class AdaINEngine:
         self.enc = rt.pack_encoder(vgg_state_dict, self.device)
         self.dec = rt.pack_decoder(decoder_state_dict, self.device)
         self.s_mean = self.s_std = None
+        self.style_px = None              # set_style_image: the style's pixels, for the colour-preserving path
 
     def synchronize(self):
         torch.cuda.synchronize(self.device)
@@ -58,6 +59,37 @@ class AdaINEngine:
         self.s_mean, self.s_std = rt.mean_std(f, True)
         return self
 
+    def set_style_image(self, style):
+        """``set_style`` that also keeps the (already resized) style's PIXELS on the device, for ``preserve_color=True``: there every
+        frame is styled with its own ``coral(style, frame)`` (function.py:26-67), so the pixels are needed, not only the statistics.
+        style: float [1,3,hs,ws] (or [1,4,...], alpha dropped) or uint8 [1,hs,ws,3]."""
+        style = style.to(self.device)
+        if style.dtype == torch.uint8:
+            style = style.contiguous()
+            self.s_mean, self.s_std = rt.mean_std(rt.encode_u8(style, self.enc), True)
+        else:
+            style = style[:, :3].to(torch.float32).contiguous()
+            self.set_style(style)
+        self.style_px = style
+        return self
+
+    def style_state(self):
+        """Statistics and resident pixels of the current style, for ``use_style_state`` (the job drivers keep one per style)."""
+        return self.s_mean, self.s_std, self.style_px
+
+    def use_style_state(self, state):
+        self.s_mean, self.s_std, self.style_px = state
+        return self
+
+    def _coral_stats(self, content):
+        """Per-frame style statistics of the colour-preserving path, each [n,512]: coral(style, frame_i) for every frame of the
+        sub-batch in one call, the n recoloured styles through the encoder, their channel statistics (test.py:201-202 then :77).
+        Each frame's row depends on that frame alone."""
+        if self.style_px is None:
+            raise rt.AdainHipError("preserve_color needs the style's pixels: set_style_image() first")
+        styles, _record = rt.coral(self.style_px, content)
+        return rt.mean_std(rt.encode(styles, self.enc), True)
+
     def features(self, images):
         return self._encode(images.to(self.device))
 
@@ -73,24 +105,31 @@ class AdaINEngine:
         """(h, w) of a content batch in either form (float NCHW / uint8 NHWC)."""
         return tuple(content.shape[1:3]) if content.dtype == torch.uint8 else tuple(content.shape[-2:])
 
-    def stylize(self, content, alpha=0.5, pmap=None):
+    def stylize(self, content, alpha=0.5, pmap=None, preserve_color=False):
         """content [n,3,h,w] float (or [n,h,w,3] uint8) on the GPU -> stylised [n,3,8*hc,8*wc].  ``pmap`` [1|n,1,hc,wc] switches
-        to the depth-aware blend (test.py:70); otherwise the alpha blend (test.py:80)."""
+        to the depth-aware blend (test.py:70); otherwise the alpha blend (test.py:80).  ``preserve_color``: every frame is styled
+        with ``coral(style, frame)`` (``set_style_image`` first) instead of the style itself."""
         assert 0.0 <= alpha <= 1.0
         if self.s_mean is None:
             raise rt.AdainHipError("set_style() first")
+        if preserve_color:
+            content = content.to(self.device)
+            content = content.contiguous() if content.dtype == torch.uint8 else content.to(torch.float32).contiguous()
+        s_mean, s_std = self._coral_stats(content) if preserve_color else (self.s_mean, self.s_std)
         f = self._encode(content)
         c_mean, c_std = rt.mean_std(f, True)
         if pmap is not None:
-            g = rt.blend_pmap(f, True, c_mean, c_std, self.s_mean, self.s_std, pmap)
+            g = rt.blend_pmap(f, True, c_mean, c_std, s_mean, s_std, pmap)
         else:
-            g = rt.blend_alpha(f, True, c_mean, c_std, self.s_mean, self.s_std, alpha)
+            g = rt.blend_alpha(f, True, c_mean, c_std, s_mean, s_std, alpha)
         return rt.decode(g, self.dec)
 
-    def stylize_u8(self, frames_u8, alpha=0.5, depth_maps=None, offset=0.15, prominence=20, masks=None, out=None):
+    def stylize_u8(self, frames_u8, alpha=0.5, depth_maps=None, offset=0.15, prominence=20, masks=None, out=None, preserve_color=False):
         """A sub-batch of decoded frames uint8 [n,h,w,3] -> finished uint8 frames [n,H,W,3] in ONE call of the C ABI
         (``adain_stylize_u8``): what ``stylize`` / ``stylize_depth`` -> ``composite`` -> ``to_u8`` give, byte for byte, with one
-        Python -> C transition per sub-batch instead of eight (the job drivers' launching thread is what eight ranks share)."""
+        Python -> C transition per sub-batch instead of eight (the job drivers' launching thread is what eight ranks share).
+        ``preserve_color``: coral -> encoder -> statistics of the n recoloured styles first (three more calls), then the same one
+        call with one style per frame (``adain_stylize_u8_ex``); a frame's bytes do not depend on the sub-batch it is in."""
         if self.s_mean is None:
             raise rt.AdainHipError("set_style() first")
         assert 0.0 <= alpha <= 1.0 and 0.0 <= offset <= 1.0
@@ -100,16 +139,21 @@ class AdaINEngine:
             masks = masks.to(self.device)
             if masks.dtype not in (torch.uint8, torch.bool, torch.float32):
                 masks = masks.float()
-        return rt.stylize_u8(frames_u8.to(self.device), self.enc, self.dec, self.s_mean, self.s_std, alpha, depth_maps, offset, prominence,
-                             masks, out)
+        frames_u8 = frames_u8.to(self.device)
+        if preserve_color:
+            frames_u8 = rt.device_tensor(frames_u8, "frames", torch.uint8)
+            s_mean, s_std = self._coral_stats(frames_u8)
+            return rt.stylize_u8(frames_u8, self.enc, self.dec, s_mean, s_std, alpha, depth_maps, offset, prominence, masks, out,
+                                 style_n=frames_u8.shape[0])
+        return rt.stylize_u8(frames_u8, self.enc, self.dec, self.s_mean, self.s_std, alpha, depth_maps, offset, prominence, masks, out)
 
-    def stylize_depth(self, content, depth_maps, offset=0.15, prominence=20):
+    def stylize_depth(self, content, depth_maps, offset=0.15, prominence=20, preserve_color=False):
         """Depth-aware path for a batch: ``depth_maps`` is a list of [h0,w0] GPU tensors, one per frame."""
         assert 0.0 <= offset <= 1.0
         h, w = self.frame_size(content)
         hc, wc = rt.encoded_size(h, w)
         p = torch.cat([rt.strength_map(d, hc, wc, offset, prominence) for d in depth_maps])
-        return self.stylize(content, pmap=p)
+        return self.stylize(content, pmap=p, preserve_color=preserve_color)
 
     def composite(self, content, stylized, masks):
         """masks [n|1, 1|3, hm, wm] float -> content*(1-m) + resize(stylized)*m (test.py:222-236)."""
@@ -156,13 +200,13 @@ class AdaINEngine:
 
 
 def precompute_guides(engine, views, names, output_dir, masks=None, content_size=512, crop=False, alpha=0.5,
-                      depth_maps=None, depth_offset=0.5, depth_prominence=20, save_ext=".jpg", sub_batch=8):
+                      depth_maps=None, depth_offset=0.5, depth_prominence=20, save_ext=".jpg", sub_batch=8, *, preserve_color=False):
     """Batched counterpart of the guide-image loop of the reference's Style_3DGS/train.py:86-115: every view
     is resized like ``adain_inference(content_size=...)`` does (test.py:190-200), stylised against the engine's
     current style, composited with its mask (``gt_image_np > 0``, train.py:97) and written to
     ``<output_dir>/<name><save_ext>`` — the same file naming, so the guide loss (train.py:208-221) reads it back
     unchanged.  ``views`` are PIL images (or paths); same-sized views are processed ``sub_batch`` at a time.
-    Returns {name: Path}."""
+    ``preserve_color``: every view is styled with ``coral(style, view)`` (``engine.set_style_image`` first).  Returns {name: Path}."""
     from pathlib import Path
 
     import numpy as np
@@ -188,9 +232,9 @@ def precompute_guides(engine, views, names, output_dir, masks=None, content_size
         content = torch.stack(tensors[i:j]).to(engine.device)
         if depth_maps is not None:
             out = engine.stylize_depth(content, [d.to(engine.device, torch.float32) for d in depth_maps[i:j]], depth_offset,
-                                       depth_prominence)
+                                       depth_prominence, preserve_color=preserve_color)
         else:
-            out = engine.stylize(content, alpha)
+            out = engine.stylize(content, alpha, preserve_color=preserve_color)
         for k in range(i, j):
             img = out[k - i:k - i + 1]
             if masks is not None and masks[k] is not None:

@@ -569,18 +569,20 @@ def _elapsed(engine, a, b):
     return f(a, b) if f is not None else b - a
 
 
-def _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence):
+def _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence, preserve_color=False):
     """One sub-batch of the feeder on the engine -> the finished uint8 frames [k,H,W,3]."""
     content, dev = batch.content, engine.device
+    coral = {"preserve_color": True} if preserve_color else {}      # only named when asked for: engines without the keyword keep working
     one_call = getattr(engine, "stylize_u8", None)
     if (one_call is not None and content.dtype == torch.uint8 and content.dim() == 4 and content.shape[-1] == 3
             and not isinstance(batch.mask, list)):
         # decoded RGB frames with (at most) one mask tensor for the sub-batch: the whole chain in one C-ABI call
-        return one_call(content, alpha=alpha, depth_maps=batch.depth, offset=depth_offset, prominence=depth_prominence, masks=batch.mask)
+        return one_call(content, alpha=alpha, depth_maps=batch.depth, offset=depth_offset, prominence=depth_prominence, masks=batch.mask,
+                        **coral)
     if batch.depth is not None:
-        out = engine.stylize_depth(content, [d.to(dev, torch.float32) for d in batch.depth], depth_offset, depth_prominence)
+        out = engine.stylize_depth(content, [d.to(dev, torch.float32) for d in batch.depth], depth_offset, depth_prominence, **coral)
     else:
-        out = engine.stylize(content, alpha)
+        out = engine.stylize(content, alpha, **coral)
     if isinstance(batch.mask, list):           # masks of different sizes inside one sub-batch: composite frame by frame
         out = torch.cat([engine.composite(content[k:k + 1], out[k:k + 1], m.to(dev).float().unsqueeze(0))
                          for k, m in enumerate(batch.mask)])
@@ -709,7 +711,7 @@ class _BlockGather:
 def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, depth_maps=None, depth_offset=0.15,
                            depth_prominence=20, masks=None, post=None, sub_batch=None, group=None, dst=0, gather=True,
                            require_transport=None, style_cache=None, out_hw=None, gather_chunks=1, sink=None,
-                           prefetch=4, host_out=None, fetch_workers=4):
+                           prefetch=4, host_out=None, fetch_workers=4, preserve_color=False):
     """Stylises ``frames`` (a sequence indexed lazily: a rank only ever touches its own block; an element is a decoded
     frame uint8 [h,w,3] / RGB PIL image, or a float tensor [3,h,w] in [0,1]) and returns ``(frames_u8, info)``: the uint8
     frames [n,H,W,3] in frame order on rank ``dst`` (None on the other ranks; with ``gather=False`` the local block — a
@@ -722,6 +724,10 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
     depth_maps      optional sequence of [h0,w0] proximity maps, one per frame -> depth-aware blend (test.py:52-71) with
                     ``depth_offset`` / ``depth_prominence``; otherwise the ``alpha`` blend (test.py:74-81).
     masks           optional sequence of [1|3,hm,wm] masks -> content-mask composite (test.py:222-236).
+    preserve_color  every frame is styled with ``coral(style, frame)`` instead of the style itself (adain_inference's
+                    ``preserve_color``, test.py:201-202), on the device: each style's PIXELS stay resident next to its statistics
+                    (``engine.set_style_image``; in ``style_cache`` under ``("pixels", index)``).  A frame's bytes do not depend on
+                    the sub-batch or the shard it is in.
     sub_batch       frames per sub-batch; None (default) = chosen from the frame size, about three megapixels per sub-batch
                     (``auto_sub_batch``: 26 frames of 256 x 456, 6 of 512 x 912; 4 of 1080p or 1200 x 1600 - inside the measured optima).
     post            optional ``f(u8_block) -> u8_block`` applied per sub-batch on the owning rank BEFORE the gather
@@ -786,10 +792,15 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
             i, j = batch.i, batch.j
             if style_of[i] != cur_style:
                 cur_style = style_of[i]
-                if cur_style not in stats:
-                    stats[cur_style] = engine.set_style(style_list[cur_style]).style_stats()
-                engine.use_style_stats(stats[cur_style])
-            u8 = _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence)
+                if preserve_color:
+                    if ("pixels", cur_style) not in stats:
+                        stats["pixels", cur_style] = engine.set_style_image(style_list[cur_style]).style_state()
+                    engine.use_style_state(stats["pixels", cur_style])
+                else:
+                    if cur_style not in stats:
+                        stats[cur_style] = engine.set_style(style_list[cur_style]).style_stats()
+                    engine.use_style_stats(stats[cur_style])
+            u8 = _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence, preserve_color)
             feeder.release(batch)
             if on_gpu:
                 queued.append(_event(dev))
@@ -850,7 +861,7 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
 
 def video_style_transfer_sharded(engine, frames, styles, *, flows=None, target_resolution=None, blend_alpha=0.7, depth_maps=None,
                                  offset=0.30, prominence=20, alpha=0.5, sub_batch=None, group=None, dst=0, require_transport=None,
-                                 gather_chunks=1):
+                                 gather_chunks=1, preserve_color=False):
     """The video caller (reference video/utils.py:297-369) over a frame list: per-frame AdaIN sharded over the ranks (styles
     switching through the clip as ``style_schedule`` says when several are given; depth-aware when ``depth_maps`` are
     given, which is how the reference runs it: ``use_depth=True``, offset 0.30, prominence 20), ``cv2.resize(...,
@@ -867,7 +878,7 @@ def video_style_transfer_sharded(engine, frames, styles, *, flows=None, target_r
     out, info = stylize_frames_sharded(engine, frames, style_list, style_of=style_schedule(n, len(style_list)), alpha=alpha,
                                        depth_maps=depth_maps, depth_offset=offset, depth_prominence=prominence, post=post,
                                        sub_batch=sub_batch, group=group, dst=dst, require_transport=require_transport,
-                                       out_hw=out_hw, gather_chunks=gather_chunks)
+                                       out_hw=out_hw, gather_chunks=gather_chunks, preserve_color=preserve_color)
     if out is not None and flows is not None and n > 1:
         t0 = time.perf_counter()
         out = engine.temporal_blend(out, flows.to(out.device, torch.float32), blend_alpha)
@@ -878,7 +889,7 @@ def video_style_transfer_sharded(engine, frames, styles, *, flows=None, target_r
 
 def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=None, content_size=512, crop=False, alpha=0.5,
                               depth_maps=None, depth_offset=0.5, depth_prominence=20, save_ext=".jpg", sub_batch=None, group=None,
-                              dst=0, write="dst", require_transport=None, writers=4, jpeg_on_device=False):
+                              dst=0, write="dst", require_transport=None, writers=4, jpeg_on_device=False, preserve_color=False):
     """The guide-image precompute of the reference's Style_3DGS/train.py:86-115 over all training views, sharded: every view
     is resized as ``adain_inference(content_size=...)`` resizes it (test.py:190-200), stylised, composited with its mask
     (``gt_image_np > 0``, train.py:97) and saved as ``<output_dir>/<name><save_ext>`` — the reference's naming, so the guide
@@ -887,7 +898,7 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
     finished — nothing is gathered and the views may have any mix of sizes.  The views are decoded / resized on a worker
     thread ahead of the kernels and travel to the device as uint8; the files are encoded and written by ``writers`` threads
     behind them.  ``jpeg_on_device``: .jpg / .jpeg guides are encoded on the device and only the files cross to the host (FileSink;
-    the same bytes).  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
+    the same bytes).  ``preserve_color``: every view is styled with ``coral(style, view)`` (``stylize_frames_sharded``).  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
     from PIL import Image
 
     from .AdaIN.test import device_transform_u8, test_transform_u8
@@ -925,11 +936,11 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
         if write == "local":
             _, info = stylize_frames_sharded(engine, _Views(), style, alpha=alpha, depth_maps=depth_maps, depth_offset=depth_offset,
                                              depth_prominence=depth_prominence, masks=masks, sub_batch=sub_batch, group=group, dst=dst,
-                                             gather=False, sink=lambda i, j, u8: sink.write(u8, [paths[names[k]] for k in range(i, j)]))
+                                             gather=False, preserve_color=preserve_color, sink=lambda i, j, u8: sink.write(u8, [paths[names[k]] for k in range(i, j)]))
         else:
             u8, info = stylize_frames_sharded(engine, _Views(), style, alpha=alpha, depth_maps=depth_maps, depth_offset=depth_offset,
                                               depth_prominence=depth_prominence, masks=masks, sub_batch=sub_batch, group=group, dst=dst,
-                                              gather=True, require_transport=require_transport)
+                                              gather=True, require_transport=require_transport, preserve_color=preserve_color)
             if rank == dst and len(names):
                 step = max(1, sub_batch or auto_sub_batch(*u8.shape[1:3]))
                 for a in range(0, len(names), step):

@@ -77,6 +77,9 @@ SIGNATURES = {
     "adain_colour_transfer_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
     "adain_colour_transfer_u8": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p]),
     "adain_localized_combine_u8": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "adain_coral_workspace_bytes": (_c_size_t, [_c_int] * 6),
+    "adain_coral": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t,
+                             _c_void_p]),
     "adain_resize_pil_bilinear_u8_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "adain_resize_pil_bilinear_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p]),
     "adain_stylize_u8_workspace_bytes": (_c_size_t, [_c_int] * 9),
@@ -84,6 +87,10 @@ SIGNATURES = {
     "adain_stylize_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_float, _c_float, _PP,
                                   ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), _c_float, _c_float, _c_void_p, _c_int, _c_int, _c_int, _c_int,
                                   _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_stylize_u8_ex_workspace_bytes": (_c_size_t, [_c_int] * 9),
+    "adain_stylize_u8_ex": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_float, _c_float, _PP,
+                                     ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), _c_float, _c_float, _c_void_p, _c_int, _c_int, _c_int, _c_int,
+                                     _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_nhwc_to_nchw": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
@@ -236,8 +243,8 @@ def free_workspaces():
 # --- the call path -----------------------------------------------------------------------------------------------
 # THE RULE: a library function whose answer depends on the device that is current on the calling thread is called only inside
 # call() or scratch(), which make the tensors' device current first.  Those functions are every launch (whatever takes a stream)
-# and the five size queries that count the device's compute units for the cin split: adain_encode_workspace_bytes,
-# adain_encode_multi_workspace_bytes, adain_decode_workspace_bytes, adain_stylize_u8_workspace_bytes and
+# and the size queries that count the device's compute units for the cin split: adain_encode_workspace_bytes,
+# adain_encode_multi_workspace_bytes, adain_decode_workspace_bytes, adain_stylize_u8_workspace_bytes (and its _ex twin) and
 # adain_conv3x3_wino4_split_workspace_bytes.  Asked elsewhere, such a query sizes the slabs for another device's compute units
 # (the launch then refuses them as too small, with the layers before it already queued) and opens a HIP context on a GPU the
 # caller never meant to touch.
@@ -489,19 +496,29 @@ def quantize_u8(img, out=None):
 
 
 def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, depth_maps=None, depth_offset=0.15, depth_prominence=20,
-               mask=None, out=None):
+               mask=None, out=None, style_n=None):
     """One sub-batch of decoded frames through the whole path in ONE call of the C ABI (``adain_stylize_u8``: ToTensor + encoder,
     statistics, AdaIN blend - the alpha form, or the depth-aware form when ``depth_maps`` (one [h0,w0] float GPU tensor per frame)
     are given - decoder, mask composite, uint8 quantiser); the bytes the separate calls give.  frames_u8 uint8 [n,h,w,3]; s_mean /
-    s_std [1,512]; mask [1|n, 1|3, hm, wm] uint8 / bool / float32 on the GPU.  Returns uint8 [n,oh,ow,3] (``out`` if given)."""
+    s_std [1,512]; mask [1|n, 1|3, hm, wm] uint8 / bool / float32 on the GPU.  Returns uint8 [n,oh,ow,3] (``out`` if given).
+    ``style_n`` (1 or n): the call goes through ``adain_stylize_u8_ex`` with s_mean / s_std [style_n,512], one style per frame when
+    it is n (the colour-preserving path: every frame has its own recoloured style)."""
     x = device_tensor(frames_u8, "frames", torch.uint8)
     if x.dim() != 4 or x.shape[3] != 3:
         raise AdainHipError(f"stylize_u8: expected uint8 [n,h,w,3], got {tuple(x.shape)}")
     n, h, w, _ = x.shape
     dev = x.device
     s_mean, s_std = device_tensor(s_mean, "s_mean"), device_tensor(s_std, "s_std")
-    if s_mean.numel() != 512 or s_std.numel() != 512:
-        raise AdainHipError("stylize_u8: the style statistics must be [1,512] each (one style per call)")
+    if style_n is None:
+        if s_mean.numel() != 512 or s_std.numel() != 512:
+            raise AdainHipError("stylize_u8: the style statistics must be [1,512] each (one style per call)")
+    else:
+        style_n = int(style_n)
+        if style_n not in (1, n) or s_mean.numel() != style_n * 512 or s_std.numel() != style_n * 512:
+            raise AdainHipError(f"stylize_u8: style_n must be 1 or {n} with statistics [style_n,512] each, got style_n {style_n} and "
+                                f"{tuple(s_mean.shape)}, {tuple(s_std.shape)}")
+        if s_mean.device != dev or s_std.device != dev:
+            raise AdainHipError("stylize_u8: the style statistics must be on the frames' device")
     mn = mc = mh = mw = 0
     m_float, m_ptr = 0, None
     if mask is not None:
@@ -529,8 +546,9 @@ def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, dept
         out = torch.empty(shape, dtype=torch.uint8, device=dev)
     else:
         check_buffer(out, "stylize_u8: out", torch.uint8, dev, shape=shape)
-    with scratch(dev, "stylize", "adain_stylize_u8_workspace_bytes", n, h, w, int(depth_maps is not None), mn, mc, mh, mw, m_float) as ws:
-        _launch("adain_stylize_u8", x.data_ptr(), n, h, w, enc_packed.data_ptr(), dec_packed.data_ptr(), s_mean.data_ptr(), s_std.data_ptr(),
+    name, styles = ("adain_stylize_u8", ()) if style_n is None else ("adain_stylize_u8_ex", (style_n,))
+    with scratch(dev, "stylize", f"{name}_workspace_bytes", n, h, w, int(depth_maps is not None), mn, mc, mh, mw, m_float) as ws:
+        _launch(name, x.data_ptr(), n, h, w, enc_packed.data_ptr(), dec_packed.data_ptr(), s_mean.data_ptr(), s_std.data_ptr(), *styles,
                 float(alpha), float(1 - alpha), dp, dh, dw, float(depth_offset), float(depth_prominence), m_ptr, m_float, mn, mc, mh, mw,
                 out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
@@ -617,6 +635,69 @@ def localized_combine_u8(content, stylised, mask, out=None):
         raise AdainHipError(f"localized_combine_u8: expected uint8 [h,w,3], [h,w,3] and [h,w] on one device, got {tuple(content.shape)}, "
                             f"{tuple(stylised.shape)} and {tuple(mask.shape)}")
     return _colour_call("localized_combine_u8", (content, stylised, mask), out)
+
+
+# --- colour preservation (adain_coral) ------------------------------------------------------------------------------------------
+CORAL_STYLE_FLAT, CORAL_CONTENT_FLAT, CORAL_STYLE_SINGLE, CORAL_CONTENT_SINGLE = 1, 2, 4, 8      # ADAIN_CORAL_*: adain_coral_record.status
+
+
+class _CoralSide(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int64), ("sum", ctypes.c_int64 * 3), ("sum2", ctypes.c_int64 * 6), ("mean", ctypes.c_double * 3),
+                ("std", ctypes.c_double * 3)]
+
+
+class _CoralRecord(ctypes.Structure):         # adain_coral_record of include/adain_hip.h
+    _fields_ = [("A", ctypes.c_double * 9), ("b", ctypes.c_double * 3), ("style", _CoralSide), ("content", _CoralSide),
+                ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+CORAL_RECORD_BYTES = ctypes.sizeof(_CoralRecord)
+
+
+def coral_record(record):
+    """The device records a ``coral`` call returned (uint8 [n, CORAL_RECORD_BYTES]) as a list of dicts, one per pair: ``status``,
+    ``A`` (3 x 3 nested lists), ``b`` and per side (``style``, ``content``) ``n``, ``sum``, ``sum2``, ``mean``, ``std``.  One copy to
+    the host, which waits for the call's stream."""
+    raw = record.cpu().numpy().tobytes()
+    side = lambda s: dict(n=int(s.n), sum=list(s.sum), sum2=list(s.sum2), mean=list(s.mean), std=list(s.std))
+    out = []
+    for i in range(len(raw) // CORAL_RECORD_BYTES):
+        r = _CoralRecord.from_buffer_copy(raw, i * CORAL_RECORD_BYTES)
+        out.append(dict(status=int(r.status), A=[list(r.A[3 * k:3 * k + 3]) for k in range(3)], b=list(r.b), style=side(r.style),
+                        content=side(r.content)))
+    return out
+
+
+def _coral_side(t, name):
+    """(contiguous tensor, is_u8, k, h, w) of one side of ``coral``: uint8 [k,h,w,3] or float32 [k,3,h,w] on a GPU."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.float32) or t.dim() != 4:
+        raise AdainHipError(f"coral: {name} must be a GPU tensor, uint8 [k,h,w,3] or float32 [k,3,h,w]")
+    u8 = t.dtype == torch.uint8
+    if t.shape[3 if u8 else 1] != 3:
+        raise AdainHipError(f"coral: {name} must be uint8 [k,h,w,3] or float32 [k,3,h,w], got {tuple(t.shape)}")
+    k, h, w = (t.shape[0], t.shape[1], t.shape[2]) if u8 else (t.shape[0], t.shape[2], t.shape[3])
+    return t.contiguous(), int(u8), k, h, w
+
+
+def coral(style, content, out=None):
+    """``coral(style_i, content_i)`` of the reference (function.py:26-67) for n contents and 1 or n styles on the device
+    (``adain_coral``): each side uint8 [k,h,w,3] or float32 [k,3,h,w], sizes independent -> (float32 [n,3,hs,ws], ready for ``encode``
+    and not clamped; device records uint8 [n, CORAL_RECORD_BYTES] for ``coral_record``).  Nothing is copied to the host: a degenerate
+    pair (a flat channel, a single pixel) gets a copy of its style and a non-zero status in its record."""
+    s, s_u8, sn, hs, ws_ = _coral_side(style, "style")
+    c, c_u8, n, hc, wc = _coral_side(content, "content")
+    if c.device != s.device or sn not in (1, n):
+        raise AdainHipError(f"coral: {sn} style image(s) for {n} content image(s) (1 or one per content, on one device)")
+    dev = c.device
+    if out is None:
+        out = torch.empty((n, 3, hs, ws_), dtype=torch.float32, device=dev)
+    else:
+        check_buffer(out, "coral: out", torch.float32, dev, shape=(n, 3, hs, ws_), distinct=(s, c))
+    with scratch(dev, "coral", "adain_coral_workspace_bytes", n, sn, hs, ws_, hc, wc,
+                 refuse=f"coral: unsupported shape ({sn} x {hs} x {ws_} style, {n} x {hc} x {wc} content)") as ws:
+        _launch("adain_coral", s.data_ptr(), s_u8, sn, hs, ws_, c.data_ptr(), c_u8, n, hc, wc, out.data_ptr(), ws.data_ptr(), ws.numel())
+        record = ws[:n * CORAL_RECORD_BYTES].clone().view(n, CORAL_RECORD_BYTES)      # the workspace is the stream's: the next call overwrites it
+    return out, record
 
 
 def resize_area_u8(frames, dsize):

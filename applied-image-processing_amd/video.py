@@ -152,7 +152,7 @@ def _jpeg_roundtrip(u8):
 
 
 def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device=False):
+         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device=False, preserve_color=False):
     from . import sharding as sh
     from .engine import AdaINEngine
 
@@ -216,7 +216,7 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
         depth_prominence=prominence,
         post=(lambda u8: engine.resize_area_u8(post(u8) if post else u8, target_resolution)) if target_resolution is not None else post,
         out_hw=(int(target_resolution[1]), int(target_resolution[0])) if target_resolution is not None else None,
-        group=group)
+        group=group, **({"preserve_color": True} if preserve_color else {}))
     err = None
     if rank == 0:
         # the frame-to-frame recurrence (video/utils.py:355-368) on the gathered frames; every frame is written by a worker
@@ -253,22 +253,24 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
 def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
                              cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                              vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth", decoder_str="Style_3DGS/AdaIN/models/decoder.pth",
-                             depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False):
+                             depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False, preserve_color=False):
     """One style for the whole clip (video/utils.py:244-295); keyword-only extras: a ready ``engine``, checkpoint paths,
     precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``jpeg_on_device`` (.jpg / .jpeg frames are
-    encoded on the device: the same files, jobs.FileSink)."""
+    encoded on the device: the same files, jobs.FileSink), ``preserve_color`` (every frame is styled with ``coral(style, frame)``,
+    adain_inference's colour preservation, on the device)."""
     return _run(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
-                engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device)
+                engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color)
 
 
 def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
                                    cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                                    vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth",
                                    decoder_str="Style_3DGS/AdaIN/models/decoder.pth", depth_maps=None, intermediate_jpeg=False,
-                                   group=None, jpeg_on_device=False):
-    """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372)."""
+                                   group=None, jpeg_on_device=False, preserve_color=False):
+    """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372).
+    ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics."""
     style_images = sorted(os.listdir(style_dir))
     if len(style_images) == 0:
         raise ValueError("No style images found in the style directory.")
     return _run(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
-                cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device)
+                cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color)

@@ -297,6 +297,49 @@ ADAIN_API int adain_colour_transfer_u8(const uint8_t* fg_u8, const uint8_t* bg_u
 ADAIN_API int adain_localized_combine_u8(const uint8_t* content_u8, const uint8_t* stylised_u8, const uint8_t* mask_u8, uint8_t* out_u8, int h,
                                          int w, void* workspace, adain_stream_t stream);
 
+/* ---- colour-preserving stylisation: coral(style, content) (Style_3DGS/AdaIN/function.py:26-67), which adain_inference applies to
+ * the transformed style image when preserve_color is set (test.py:201-202) and the reference computes on CPU tensors -------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * n content images and style_n (1: one style for all, or n: one per content) style images; pair i is (style i or 0, content i).  Each
+ * side is either uint8 HWC [k][h][w][3] (x_is_u8 != 0: what adain_resize_pil_bilinear_u8 writes) or float NCHW [k][3][h][w]; the
+ * two sides' sizes are independent.  out: float NCHW [n][3][hs][ws], the style images recoloured to their contents' channel
+ * statistics, ready for adain_encode; NOT clamped (the reference does not clamp).
+ * Per pair: the channel means, unbiased deviations and C = norm norm^T + I of both sides, the symmetric square roots of both C from a
+ * Jacobi eigen-solve in float64 (C = (HW - 1) x correlation matrix + I: every eigenvalue is >= 1, so the inverse square root is
+ * bounded by 1), folded into one affine map y = A x + b applied to every style pixel in float64 and rounded once to float.  uint8
+ * sides are summed as 64-bit integers of the byte values (exact); float sides in float64 over a partition fixed by the image size:
+ * the same inputs give the same bytes on every run, stream, batch position and device size.  A uint8 pixel is read as float(v) / 255
+ * correctly rounded, as adain_u8_to_f32 and adain_encode_u8 read it.
+ * The workspace (adain_coral_workspace_bytes; 0 for a refused shape; 8-byte aligned) starts with n adain_coral_record, one per pair,
+ * which the call fills on the device and which stay valid until the workspace is used again.
+ * DEGENERATE INPUT: a side with fewer than two pixels, or with a channel whose variance is zero, makes the reference divide by zero
+ * and return NaNs.  No NaNs are reproduced: the pair's record gets the matching ADAIN_CORAL_* status bit(s), A = I, b = 0, and the
+ * pair's output is a plain copy of its style image (as float); the other pairs of the call are not affected.
+ * Refused with ADAIN_EINVAL before anything is launched: style_n other than 1 and n, n outside 1..65535, an image of no pixels or of
+ * 2^30 or more, a workspace below the query's or not 8-byte aligned, float images / out not 4-byte aligned.  4 or 5 kernel launches,
+ * no allocation, no synchronisation. */
+#define ADAIN_CORAL_STYLE_FLAT 1     /* status bits: a channel of the style has zero variance */
+#define ADAIN_CORAL_CONTENT_FLAT 2
+#define ADAIN_CORAL_STYLE_SINGLE 4   /* the style has a single pixel: no deviation */
+#define ADAIN_CORAL_CONTENT_SINGLE 8
+typedef struct adain_coral_side {
+    int64_t n;       /* pixels */
+    int64_t sum[3];  /* uint8 side: the exact sums of the byte values per channel; float side: 0 */
+    int64_t sum2[6]; /* uint8 side: the exact sums of byte products rr, rg, rb, gg, gb, bb; float side: 0 */
+    double mean[3];  /* per channel, of v / 255 (uint8) or of the float values */
+    double std[3];   /* unbiased (HW - 1); 0 where the status says there is none */
+} adain_coral_side;
+typedef struct adain_coral_record {
+    double A[9]; /* row major: out[i] = sum_j A[3 i + j] style[j] + b[i] */
+    double b[3];
+    adain_coral_side style, content;
+    int32_t status; /* 0: the transfer ran; otherwise ADAIN_CORAL_* bits and the output is a copy of the style */
+    int32_t reserved;
+} adain_coral_record;
+ADAIN_API size_t adain_coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);
+ADAIN_API int adain_coral(const void* style, int style_is_u8, int style_n, int hs, int ws, const void* content, int content_is_u8, int n,
+                          int hc, int wc, float* out_nchw, void* workspace, size_t workspace_bytes, adain_stream_t stream);
+
 /* ---- test_transform's Resize [+ CenterCrop] on the device (test.py:16-24, applied at :190-204; video/utils.py:341-350) --------
  * PIL.Image.resize((wo, ho), BILINEAR) of uint8 RGB images, bit for bit (Pillow's ImagingResample: separable triangle filter whose
  * support grows with the shrink factor, double-precision taps converted to 22-bit fixed point, a horizontal pass into a uint8
@@ -345,6 +388,19 @@ ADAIN_API int adain_stylize_u8(const uint8_t* frames_nhwc_u8, int n, int h, int 
                      const int* depth_h_host, const int* depth_w_host, float depth_offset, float depth_prominence, const void* mask,
                      int mask_is_float, int mask_n, int mask_c, int mask_h, int mask_w, uint8_t* out_u8, void* workspace,
                      size_t workspace_bytes, adain_stream_t stream);
+
+/* adain_stylize_u8 with ONE STYLE PER FRAME: s_mean / s_std are [style_n][512], style_n = 1 (every frame takes row 0: exactly
+ * adain_stylize_u8, same bytes) or n (frame i takes row i: the statistics of n styles recoloured for their frames by adain_coral,
+ * adain_inference(preserve_color=True) for a sub-batch).  Everything else as adain_stylize_u8; the workspace is the same size.
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.) */
+ADAIN_API size_t adain_stylize_u8_ex_workspace_bytes(int n, int h, int w, int use_depth, int mask_n, int mask_c, int mask_h, int mask_w,
+                                           int mask_is_float);
+ADAIN_API int adain_stylize_u8_ex(const uint8_t* frames_nhwc_u8, int n, int h, int w, const float* enc_packed, const float* dec_packed,
+                        const float* s_mean, const float* s_std, int style_n, float alpha, float one_minus_alpha,
+                        const float* const* depth_maps_host_array_of_dev_ptrs,
+                        const int* depth_h_host, const int* depth_w_host, float depth_offset, float depth_prominence, const void* mask,
+                        int mask_is_float, int mask_n, int mask_c, int mask_h, int mask_w, uint8_t* out_u8, void* workspace,
+                        size_t workspace_bytes, adain_stream_t stream);
 
 /* ---- the callers' output files: PIL's Image.fromarray(frame).save(path) for a .jpg path (test.py:243-244 through torchvision's
  * save_image; video/utils.py:352-356 per frame), encoded on the device --------------------------------------------------------------

@@ -1,0 +1,241 @@
+"""GPU tests of the colour-preserving path above ``adain_coral``: ``adain_stylize_u8_ex`` (one style per frame), the engine's
+``preserve_color`` keyword, the job driver that passes it down, and ``adain_inference(preserve_color=True)`` under
+``set_device_coral``.  64 x 80 frames, the seeded weights and the small checkpoint files of the other GPU tests.  Run with ``-m gpu``."""
+import numpy as np
+import pytest
+import torch
+
+import applied_image_processing_amd.synth as synth
+from oracle import adain_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+H, W = 64, 80
+
+
+def T(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def u8frames(seed, n, h, w):
+    return T(np.stack([(synth.image(seed + i, 1, h, w)[0].transpose(1, 2, 0) * 255).astype(np.uint8) for i in range(n)]))
+
+
+@pytest.fixture(scope="module")
+def rt():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import applied_image_processing_amd.runtime as rt
+
+    rt.lib()
+    return rt
+
+
+@pytest.fixture(scope="module")
+def engine(weights):
+    from applied_image_processing_amd.engine import AdaINEngine
+
+    return AdaINEngine(weights[0], weights[1], "cuda:0")
+
+
+@pytest.fixture(scope="module")
+def frames():
+    return u8frames(3100, 3, H, W).cuda()
+
+
+@pytest.fixture(scope="module")
+def style_u8():
+    return u8frames(3200, 1, 48, 72)
+
+
+@pytest.fixture(scope="module")
+def three_styles(rt, engine):
+    """Statistics of three different styles, [3,512] each."""
+    f = rt.encode(T(synth.image(3300, 3, 40, 56)).cuda(), engine.enc)
+    return rt.mean_std(f, True)
+
+
+# ---- item 6: adain_stylize_u8_ex ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("path", ["alpha", "depth", "mask", "mask_resized"])
+def test_one_style_per_frame_equals_one_call_per_style(rt, engine, frames, three_styles, path):
+    s_mean, s_std = three_styles
+    kw = dict(alpha=0.6)
+    per_frame = [dict(kw) for _ in range(3)]
+    if path == "depth":
+        depth = [T(synth.smooth_depth(50 + i, 30 + i, 41)).cuda() for i in range(3)]
+        kw.update(depth_maps=depth, depth_offset=0.3, depth_prominence=15)
+        per_frame = [dict(kw, depth_maps=depth[i:i + 1]) for i in range(3)]
+    elif path in ("mask", "mask_resized"):
+        m = (frames > 70).permute(0, 3, 1, 2).contiguous() if path == "mask" else (T(synth.image(60, 3, 31, 45)) > 0.4).cuda()
+        kw.update(mask=m)
+        per_frame = [dict(kw, mask=m[i:i + 1].contiguous()) for i in range(3)]
+    got = rt.stylize_u8(frames, engine.enc, engine.dec, s_mean, s_std, style_n=3, **kw)
+    for i in range(3):
+        one = rt.stylize_u8(frames[i:i + 1].contiguous(), engine.enc, engine.dec, s_mean[i:i + 1].contiguous(), s_std[i:i + 1].contiguous(), **per_frame[i])
+        assert torch.equal(got[i:i + 1], one), (path, i)
+    assert not torch.equal(got[0], rt.stylize_u8(frames[:1].contiguous(), engine.enc, engine.dec, s_mean[1:2].contiguous(), s_std[1:2].contiguous(),
+                                                 **per_frame[0])[0])
+    # style_n = 1 through the new entry: the old entry's bytes
+    old = rt.stylize_u8(frames, engine.enc, engine.dec, s_mean[:1].contiguous(), s_std[:1].contiguous(), **kw)
+    assert torch.equal(rt.stylize_u8(frames, engine.enc, engine.dec, s_mean[:1].contiguous(), s_std[:1].contiguous(), style_n=1, **kw), old)
+
+
+def test_style_count_is_checked(rt, engine, frames, three_styles):
+    s_mean, s_std = three_styles
+    with pytest.raises(rt.AdainHipError):
+        rt.stylize_u8(frames, engine.enc, engine.dec, s_mean[:2].contiguous(), s_std[:2].contiguous(), style_n=2)
+    with pytest.raises(rt.AdainHipError):
+        rt.stylize_u8(frames, engine.enc, engine.dec, s_mean, s_std)                       # the old entry takes one style
+    ws = torch.empty(rt.lib().adain_stylize_u8_ex_workspace_bytes(3, H, W, 0, 0, 0, 0, 0, 0), dtype=torch.uint8, device="cuda")
+    out = torch.empty(3, H, W, 3, dtype=torch.uint8, device="cuda")
+    with pytest.raises(rt.AdainHipError, match="1 or one per frame"):       # the library's own check, before anything is launched
+        rt.call("adain_stylize_u8_ex", frames.device, frames.data_ptr(), 3, H, W, engine.enc.data_ptr(), engine.dec.data_ptr(), s_mean.data_ptr(),
+                s_std.data_ptr(), 2, 0.5, 0.5, None, None, None, 0.15, 20.0, None, 0, 0, 0, 0, 0, out.data_ptr(), ws.data_ptr(), ws.numel())
+
+
+# ---- item 7: the engine ---------------------------------------------------------------------------------------------------------
+def staged(rt, engine, style, content_u8, alpha):
+    """rt.coral -> encode -> mean_std -> blend -> decode -> quantize, call by call."""
+    styles, _ = rt.coral(style, content_u8)
+    s_mean, s_std = rt.mean_std(rt.encode(styles, engine.enc), True)
+    f = rt.encode_u8(content_u8, engine.enc)
+    c_mean, c_std = rt.mean_std(f, True)
+    return rt.quantize_u8(rt.decode(rt.blend_alpha(f, True, c_mean, c_std, s_mean, s_std, alpha), engine.dec))
+
+
+@pytest.mark.parametrize("style_form", ["u8", "f32"])
+def test_engine_preserve_color_equals_the_staged_calls_whatever_the_sub_batch(rt, engine, frames, style_u8, style_form):
+    style = style_u8.cuda() if style_form == "u8" else style_u8.permute(0, 3, 1, 2).float().div(255).cuda()
+    engine.set_style_image(style)
+    plain = engine.stylize_u8(frames, alpha=0.5)
+    got = engine.stylize_u8(frames, alpha=0.5, preserve_color=True)
+    assert got.shape == (3, H, W, 3) and not torch.equal(got, plain)
+    assert torch.equal(got, staged(rt, engine, engine.style_px, frames, 0.5))
+    for size in (1, 2):
+        parts = torch.cat([engine.stylize_u8(frames[i:i + size].contiguous(), alpha=0.5, preserve_color=True) for i in range(0, 3, size)])
+        assert torch.equal(parts, got), size
+    assert torch.equal(engine.to_u8(engine.stylize(frames, 0.5, preserve_color=True)), got)
+    assert torch.equal(engine.stylize_u8(frames, alpha=0.5), plain)                        # the keyword leaves the style's own statistics alone
+
+
+def test_engine_preserve_color_against_the_host_coral_and_the_oracle(engine, frames, style_u8, weights):
+    """style_transfer_simple(enc, dec, content, coral(style, content)) with the host's float32 coral and the CPU oracle: the project's
+    bar, relative L2 <= 1e-4 before the quantiser and <= 1 LSB after it."""
+    from applied_image_processing_amd.AdaIN.function import coral
+
+    engine.set_style_image(style_u8.cuda())
+    out = engine.stylize(frames, 0.5, preserve_color=True)
+    u8 = engine.stylize_u8(frames, alpha=0.5, preserve_color=True)
+    style = style_u8[0].permute(2, 0, 1).float().div(255)
+    for i in range(3):
+        c = frames[i].cpu().permute(2, 0, 1).float().div(255)
+        with torch.no_grad():
+            ref = O.style_transfer_simple(weights[0], weights[1], c[None], coral(style, c)[None], 0.5)
+        err = float((out[i].cpu() - ref[0]).norm() / ref[0].norm())
+        lsb = int((u8[i].cpu().int() - O.quantize_u8(ref)[0].int()).abs().max())
+        print(f"frame {i}: relative L2 {err:.2e}, {lsb} LSB")
+        assert err <= 1e-4 and lsb <= 1
+
+
+def test_preserve_color_needs_the_style_image(rt, weights, frames):
+    from applied_image_processing_amd.engine import AdaINEngine
+
+    eng = AdaINEngine(weights[0], weights[1], "cuda:0")
+    eng.set_style(T(synth.image(4, 1, 48, 64)).cuda())
+    with pytest.raises(rt.AdainHipError, match="set_style_image"):
+        eng.stylize_u8(frames, preserve_color=True)
+    with pytest.raises(rt.AdainHipError, match="set_style_image"):
+        eng.stylize(frames, preserve_color=True)
+
+
+def test_job_driver_passes_preserve_color_down(rt, engine, frames, style_u8):
+    """Two styles switching through five frames, sub-batches of 2: each frame's bytes are those of the engine on that frame alone."""
+    import applied_image_processing_amd.jobs as jobs
+
+    styles = [style_u8.permute(0, 3, 1, 2).float().div(255), T(synth.image(3400, 1, 40, 56))]
+    clip = [f.numpy() for f in u8frames(3500, 5, H, W)]
+    style_of = [0, 0, 0, 1, 1]
+    cache = {}
+    out, info = jobs.stylize_frames_sharded(engine, clip, styles, style_of=style_of, alpha=0.5, sub_batch=2, preserve_color=True, style_cache=cache)
+    assert sorted(cache, key=str) == [("pixels", 0), ("pixels", 1)] and all(len(v) == 3 and v[2] is not None for v in cache.values())
+    for k in range(5):
+        engine.set_style_image(styles[style_of[k]].cuda())
+        assert torch.equal(out[k:k + 1], engine.stylize_u8(T(clip[k])[None].cuda(), alpha=0.5, preserve_color=True)), k
+    plain, _ = jobs.stylize_frames_sharded(engine, clip, styles, style_of=style_of, alpha=0.5, sub_batch=2)
+    assert not torch.equal(plain, out)
+
+
+# ---- item 8: adain_inference ----------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def ckpt(tmp_path_factory):
+    d = tmp_path_factory.mktemp("ckpt")
+    torch.save(synth.to_torch(synth.vgg_state_dict(0, full=True)), d / "vgg.pth")
+    torch.save(synth.to_torch(synth.decoder_state_dict(0)), d / "dec.pth")
+    return dict(vgg_str=str(d / "vgg.pth"), decoder_str=str(d / "dec.pth"))
+
+
+@pytest.fixture
+def t():
+    from applied_image_processing_amd.AdaIN import test as t
+
+    t.clear_style_cache()
+    prev, prev_coral = t.set_style_cache(True), t.set_device_coral(False)
+    yield t
+    t.set_style_cache(prev)
+    t.set_device_coral(prev_coral)
+    t.set_device_jpeg(False)
+    t.clear_style_cache()
+
+
+def test_adain_inference_device_coral(t, ckpt, tmp_path):
+    from PIL import Image
+
+    def img(seed, h, w):
+        return Image.fromarray((synth.image(seed, 1, h, w)[0].transpose(1, 2, 0) * 255).astype(np.uint8))
+
+    contents, style = [img(3600 + k, 80, 100) for k in range(2)], img(3700, 90, 120)
+    kw = dict(content_size=64, style_size=48, save_ext=".png", preserve_color=True, **ckpt)
+    assert t.set_device_coral(False) is False                               # off by default
+    u0 = t.STYLE_PIXEL_UPLOADS[0]
+    off = [np.asarray(Image.open(t.adain_inference(c, style, output=str(tmp_path / "off"), file_name=f"f{k}", **kw))) for k, c in enumerate(contents)]
+    assert t.STYLE_PIXEL_UPLOADS[0] == u0                                   # the switch-off path is the call-by-call path, as before
+    assert t.set_device_coral(True) is False
+    e0, u0 = t.STYLE_ENCODES[0], t.STYLE_PIXEL_UPLOADS[0]
+    on = [np.asarray(Image.open(t.adain_inference(c, style, output=str(tmp_path / "on"), file_name=f"f{k}", **kw))) for k, c in enumerate(contents)]
+    assert t.STYLE_ENCODES[0] - e0 == 2                                     # the recoloured style is encoded per call ...
+    assert t.STYLE_PIXEL_UPLOADS[0] - u0 == 1                               # ... the style's pixels went up once
+    for a, b in zip(on, off):
+        assert a.shape == b.shape and np.abs(a.astype(int) - b.astype(int)).max() <= 1
+    assert not np.array_equal(on[0], np.asarray(Image.open(t.adain_inference(contents[0], style, output=str(tmp_path / "plain"), file_name="p",
+                                                                              **dict(kw, preserve_color=False)))))
+    # the depth path, a mask and the device JPEG writer ride on the same one call
+    depth = T(synth.smooth_depth(7, 80, 100))
+    m = np.asarray(contents[0]).transpose(2, 0, 1) > 60
+    more = dict(kw, use_depth=True, depth_map=depth, content_mask=m, depth_offset=0.3)
+    a = np.asarray(Image.open(t.adain_inference(contents[0], style, output=str(tmp_path / "on"), file_name="d", **more)))
+    t.set_device_coral(False)
+    b = np.asarray(Image.open(t.adain_inference(contents[0], style, output=str(tmp_path / "off"), file_name="d", **more)))
+    assert np.abs(a.astype(int) - b.astype(int)).max() <= 1
+    t.set_device_coral(True)
+    jpg = dict(kw, save_ext=".jpg")
+    pil = t.adain_inference(contents[1], style, output=str(tmp_path / "on"), file_name="j", **jpg).read_bytes()
+    t.set_device_jpeg(True)
+    assert t.adain_inference(contents[1], style, output=str(tmp_path / "onj"), file_name="j", **jpg).read_bytes() == pil
+
+
+def test_style_cache_key_holds_the_schedule(t, ckpt, tmp_path):
+    """Statistics computed under the latency schedule are not handed to a call under the batch schedule (and the other way round)."""
+    from PIL import Image
+
+    c = Image.fromarray((synth.image(3800, 1, 64, 80)[0].transpose(1, 2, 0) * 255).astype(np.uint8))
+    s = Image.fromarray((synth.image(3801, 1, 64, 80)[0].transpose(1, 2, 0) * 255).astype(np.uint8))
+    kw = dict(content_size=64, style_size=48, output=str(tmp_path / "o"), save_ext=".png", **ckpt)
+    e0 = t.STYLE_ENCODES[0]
+    t.adain_inference(c, s, file_name="a", **kw)
+    prev = t.set_latency_schedule(True)
+    try:
+        t.adain_inference(c, s, file_name="b", **kw)
+        t.adain_inference(c, s, file_name="c", **kw)
+    finally:
+        t.set_latency_schedule(prev)
+    t.adain_inference(c, s, file_name="d", **kw)
+    assert t.STYLE_ENCODES[0] - e0 == 2
