@@ -7,6 +7,10 @@ Extra flags make the depth-aware mode usable offline (the reference pulls MiDaS 
 ``--depth_npy`` takes a precomputed proximity map, ``--vgg`` / ``--decoder`` the checkpoint paths; ``--jpeg_on_device`` encodes the
 result's JPEG file on the GPU (the same bytes); ``--coral_on_device`` preserves the content's colours (``adain_inference``'s
 ``preserve_color``, which the reference's CLI does not expose) with CORAL computed on the GPU.
+
+Style interpolation (the upstream AdaIN CLI's flag, Style_3DGS/AdaIN/test_video.py:77-79): ``--style a.jpg,b.jpg
+--style_interpolation_weights 1,3`` styles the content with a mix of the styles.  The weights are divided by their sum (in double),
+as the upstream CLI does; this is the only place where they are normalised.
 """
 import argparse
 
@@ -18,7 +22,7 @@ from .test import adain_inference, set_device_coral, set_device_jpeg
 # (flag, argparse keyword arguments) — names and defaults as in the reference CLI
 _REFERENCE_FLAGS = (
     ("--content", dict(type=str, required=True, help="content image file")),
-    ("--style", dict(type=str, required=True, help="style image file")),
+    ("--style", dict(type=str, required=True, help="style image file (several, comma-separated, with --style_interpolation_weights)")),
     ("--output", dict(type=str, default="output", help="directory the result is written to")),
     ("--file_name", dict(type=str, default="stylized", help="result file name, extension excluded")),
     ("--depth_offset", dict(type=float, default=0.15, help="cap of the strength map is 1 - offset (depth-aware mode)")),
@@ -26,12 +30,24 @@ _REFERENCE_FLAGS = (
     ("--use_depth", dict(action="store_true", help="blend by the depth-proximity map instead of a global alpha")),
 )
 _EXTRA_FLAGS = (
+    ("--style_interpolation_weights", dict(type=str, default="", help="comma-separated weights, one per --style file; divided by their sum")),
     ("--depth_npy", dict(type=str, default=None, help=".npy proximity map [H0,W0]; replaces the MiDaS estimate")),
     ("--vgg", dict(type=str, default="Style_3DGS/AdaIN/models/vgg_normalised.pth", help="encoder state_dict")),
     ("--decoder", dict(type=str, default="Style_3DGS/AdaIN/models/decoder.pth", help="decoder state_dict")),
     ("--jpeg_on_device", dict(action="store_true", help="encode the output JPEG on the GPU instead of in PIL (byte-identical file)")),
     ("--coral_on_device", dict(action="store_true", help="preserve the content's colours (preserve_color) with CORAL computed on the GPU")),
 )
+
+
+def interpolation_weights(text, n_styles):
+    """``--style_interpolation_weights 1,3`` -> [0.25, 0.75]: divided by their sum in double (the upstream CLI's convention)."""
+    w = [float(v) for v in text.split(",")]
+    if len(w) != n_styles:
+        raise SystemExit(f"--style_interpolation_weights: {len(w)} weights for {n_styles} style files")
+    total = sum(w)
+    if not total > 0 or any(v < 0 for v in w):
+        raise SystemExit("--style_interpolation_weights: the weights must be non-negative with a positive sum")
+    return [v / total for v in w]
 
 
 def main(argv=None):
@@ -44,10 +60,16 @@ def main(argv=None):
         proximity = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
     prev = set_device_jpeg(ns.jpeg_on_device)
     prev_coral = set_device_coral(ns.coral_on_device)
+    style, mix = ns.style, {}
+    if ns.style_interpolation_weights:
+        style = ns.style.split(",")
+        mix = {"style_interpolation_weights": interpolation_weights(ns.style_interpolation_weights, len(style))}
+    elif "," in ns.style:
+        raise SystemExit("--style: several files need --style_interpolation_weights")
     try:
-        return adain_inference(ns.content, ns.style, vgg_str=ns.vgg, decoder_str=ns.decoder, depth_offset=ns.depth_offset,
+        return adain_inference(ns.content, style, vgg_str=ns.vgg, decoder_str=ns.decoder, depth_offset=ns.depth_offset,
                                depth_prominence=ns.depth_prominence, output=ns.output, file_name=ns.file_name,
-                               use_depth=ns.use_depth, depth_map=proximity, preserve_color=ns.coral_on_device)
+                               use_depth=ns.use_depth, depth_map=proximity, preserve_color=ns.coral_on_device, **mix)
     finally:
         set_device_jpeg(prev)
         set_device_coral(prev_coral)

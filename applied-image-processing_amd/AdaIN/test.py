@@ -412,6 +412,31 @@ def style_transfer_simple(vgg, decoder, content, style, alpha=0.5):
     return decoder(_adain_blend(content_f, style_f, alpha=alpha))
 
 
+def style_transfer_interpolated(vgg, decoder, content, styles, alpha=1.0, interpolation_weights=None):
+    """Style interpolation, the reference's ``style_transfer(vgg, decoder, content, style, alpha, interpolation_weights)``
+    (Style_3DGS/AdaIN/test_video.py:30-45): ``decoder(feat * alpha + content_f * (1 - alpha))`` with ``feat = sum_k w_k *
+    AdaIN(content_f, style_f[k])`` accumulated in style order, in one kernel (``rt.blend_mix``).  ``styles``: [K,3,hs,ws], or a list
+    of K tensors [3,h,w] / [1,3,h,w] of different sizes (the reference's batch needs one size).  ``interpolation_weights``: K Python
+    floats, used as given (the upstream CLI divides them by their sum before it calls; this function, like the reference's, does not)."""
+    from .function import _layout, _like
+
+    assert (0.0 <= alpha <= 1.0)
+    style_list = list(styles) if isinstance(styles, (list, tuple)) else [styles[i:i + 1] for i in range(styles.shape[0])]
+    style_list = [s.unsqueeze(0) if s.dim() == 3 else s for s in style_list]
+    if not interpolation_weights or len(interpolation_weights) != len(style_list):
+        raise ValueError(f"style_transfer_interpolated: {len(style_list)} styles need as many interpolation_weights, got {interpolation_weights!r}")
+    content_f = vgg(content)
+    N, C = content_f.size()[:2]
+    s_stats = [calc_mean_std(vgg(s)) for s in style_list]
+    s_mean = torch.cat([m.view(1, C) for m, _ in s_stats]).contiguous()
+    s_std = torch.cat([sd.view(1, C) for _, sd in s_stats]).contiguous()
+    c_mean, c_std = calc_mean_std(content_f)
+    view, nhwc = _layout(content_f)
+    weights = torch.tensor([float(w) for w in interpolation_weights], dtype=torch.float32, device=view.device)
+    feat = rt.blend_mix(view, nhwc, c_mean.view(N, C), c_std.view(N, C), s_mean, s_std, weights, alpha=alpha)
+    return decoder(_like(feat, nhwc))
+
+
 def _encode_both(vgg, content, style):
     """``vgg(content), vgg(style)`` (test.py:57,63 / :76-77).  The package's encoder takes both in one pass over its layers
     (``HipVGG.forward_many``: same results bit for bit, one launch per layer); any other module is simply called twice."""
@@ -501,16 +526,24 @@ def adain_inference(
     content_mask=None,
     use_depth=False,
     depth_map=None,
+    style_interpolation_weights=None,
 ):
     """Stylise one content image with one style image and save it; returns the output ``Path``
     (reference test.py:153-247; same parameters, defaults and return value).  ``depth_map`` (an addition, use it by
-    keyword) supplies a precomputed proximity map [H0,W0] for ``use_depth=True`` instead of the depth provider."""
+    keyword) supplies a precomputed proximity map [H0,W0] for ``use_depth=True`` instead of the depth provider.
+    Style interpolation (an addition; test_video.py:30-45): ``style_img`` a list of K style images with
+    ``style_interpolation_weights`` a list of K floats, used as given - the content is styled with that mix of the styles."""
     device = _device()
     out_dir = Path(output)
     out_dir.mkdir(exist_ok=True, parents=True)
     enc, dec = _singletons(device, vgg_str, decoder_str)
     target = out_dir / f"{file_name}{save_ext}"
     T = _stage_timer
+    if isinstance(style_img, (list, tuple)) or style_interpolation_weights is not None:
+        _mix_call(content_img, style_img, style_interpolation_weights, enc, dec, device, depth_offset, depth_prominence, content_size, style_size, alpha,
+                  crop, target, preserve_color, content_mask, use_depth, depth_map)
+        print(f"Image saved to {target}")
+        return target
 
     t0 = time.perf_counter()
     pil_content = Image.open(content_img) if type(content_img) == str else content_img
@@ -650,8 +683,39 @@ def _coral_style_stats(style_img, frame, style_size, crop, enc, device):
     return rt.mean_std(rt.encode(recoloured, enc.packed(device)), True)
 
 
+def _mix_call(content_img, style_imgs, weights, enc, dec, device, depth_offset, depth_prominence, content_size, style_size, alpha, crop, target,
+              preserve_color, content_mask, use_depth, depth_map):
+    """adain_inference with a list of styles: every style's statistics through the style cache, the frame in one C-ABI call
+    (``adain_stylize_u8_mix``) with the weights as given."""
+    if not isinstance(style_imgs, (list, tuple)) or weights is None or len(weights) != len(style_imgs) or not 1 <= len(style_imgs) <= rt.MIX_MAX_STYLES:
+        raise ValueError(f"style interpolation needs a list of 1 .. {rt.MIX_MAX_STYLES} style images and as many style_interpolation_weights")
+    if preserve_color:
+        raise ValueError("preserve_color with style_interpolation_weights is not supported (it would need coral of every style per frame)")
+    if not (isinstance(enc, net.HipVGG) and isinstance(dec, net.HipDecoder)):
+        raise rt.AdainHipError("style interpolation runs on the package's encoder and decoder")
+    if not _mask_fits(content_mask):
+        raise ValueError("content_mask must be [1|3,H,W] uint8, bool or float32")
+    assert 0.0 <= alpha <= 1.0
+    if use_depth:
+        assert 0.0 <= depth_offset <= 1.0
+    pil_content = Image.open(content_img) if type(content_img) == str else content_img
+    pil_content.load()
+    frame = device_transform_u8(pil_content, content_size, crop, device)
+    if frame is None:
+        frame = test_transform_u8(content_size, crop)(pil_content)
+    if not (isinstance(frame, torch.Tensor) and frame.dtype == torch.uint8 or isinstance(frame, np.ndarray) and frame.ndim == 3 and frame.shape[2] == 3):
+        raise ValueError("style interpolation needs an RGB content image")
+    stats = [_style_stats(s, style_size, crop, enc, device, drop_alpha=use_depth) for s in style_imgs]
+    if any(st is None for st in stats):
+        raise ValueError("style interpolation needs 3-channel style images")
+    mixed = (torch.cat([m.view(1, 512) for m, _ in stats]).contiguous(), torch.cat([sd.view(1, 512) for _, sd in stats]).contiguous())
+    w = torch.tensor([float(v) for v in weights], dtype=torch.float32, device=device)
+    _one_call(frame, mixed, enc, dec, device, alpha, use_depth, depth_map, pil_content, depth_offset, depth_prominence, content_mask, target,
+              style_weights=w)
+
+
 def _one_call(frame, stats, enc, dec, device, alpha, use_depth, depth_map, pil_content, depth_offset, depth_prominence, content_mask, target,
-              e0=None):
+              e0=None, style_weights=None):
     """A resized RGB frame (uint8: [1,h,w,3] on the device, or HWC on the host) -> the saved file: [upload,] ``adain_stylize_u8``,
     download, PIL save.  ``e0``: an event recorded before the device-side resize (stage timer: the kernels' time includes it)."""
     T = _stage_timer
@@ -680,7 +744,8 @@ def _one_call(frame, stats, enc, dec, device, alpha, use_depth, depth_map, pil_c
         if e0 is None:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
-    u8 = rt.stylize_u8(x, enc.packed(device), dec.packed(device), stats[0], stats[1], alpha, depth, depth_offset, depth_prominence, mask)
+    u8 = rt.stylize_u8(x, enc.packed(device), dec.packed(device), stats[0], stats[1], alpha, depth, depth_offset, depth_prominence, mask,
+                       style_weights=style_weights)
     if T.on:
         e1.record()
         T.events.append((e0, e1))

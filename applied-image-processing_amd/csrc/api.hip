@@ -434,6 +434,14 @@ int adain_blend_pmap(const float* x, int nhwc, int n, int c, int hw, const float
                                  (hipStream_t)stream);
 }
 
+int adain_blend_mix(const float* x, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const float* s_mean,
+                    const float* s_std, int k, const float* weights, int weights_n, int weights_hw, float alpha, float one_minus_alpha,
+                    const float* pmap, int pmap_n, float* out, adain_stream_t stream) {
+    if (!x || !c_mean || !c_std || !s_mean || !s_std || !weights || !out) { set_error("blend_mix: null pointer"); return ADAIN_EINVAL; }
+    return launch_adain_blend_mix(x, nhwc, n, c, hw, c_mean, c_std, s_mean, s_std, k, weights, weights_n, weights_hw, alpha, one_minus_alpha,
+                                  pmap, pmap_n, out, (hipStream_t)stream);
+}
+
 size_t adain_strength_map_workspace_bytes(int hc, int wc) { return strength_map_workspace_bytes(hc, wc); }
 
 int adain_strength_map(const float* depth, int h0, int w0, int hc, int wc, float offset, float prominence, float* pmap,
@@ -596,22 +604,23 @@ size_t adain_stylize_u8_ex_workspace_bytes(int n, int h, int w, int use_depth, i
     return adain_stylize_u8_workspace_bytes(n, h, w, use_depth, mask_n, mask_c, mask_h, mask_w, mask_is_float);
 }
 
-int adain_stylize_u8(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const float* s_mean,
-                     const float* s_std, float alpha, float one_minus_alpha, const float* const* depth_maps, const int* depth_h, const int* depth_w,
-                     float depth_offset, float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c, int mask_h,
-                     int mask_w, uint8_t* out_u8, void* workspace, size_t ws_bytes, adain_stream_t stream) {
-    return adain_stylize_u8_ex(frames, n, h, w, enc_packed, dec_packed, s_mean, s_std, 1, alpha, one_minus_alpha, depth_maps, depth_h, depth_w,
-                               depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes, stream);
-}
+static_assert(MIX_MAX_STYLES == ADAIN_MIX_MAX_STYLES, "csrc/common.h and include/adain_hip.h disagree");
 
-// s_mean / s_std [style_n][512], style_n 1 (adain_stylize_u8) or n: one style per frame
-int adain_stylize_u8_ex(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const float* s_mean,
-                        const float* s_std, int style_n, float alpha, float one_minus_alpha, const float* const* depth_maps, const int* depth_h,
-                        const int* depth_w, float depth_offset, float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c,
-                        int mask_h, int mask_w, uint8_t* out_u8, void* workspace, size_t ws_bytes, adain_stream_t stream) {
+// adain_stylize_u8 / _ex (weights == nullptr: s_mean / s_std [style_n][512], one style per frame when style_n == n) and
+// adain_stylize_u8_mix (weights != nullptr: s_mean / s_std [k][512] mixed per frame by weights [weights_n][k][weights_hw])
+static int stylize_impl(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const float* s_mean,
+                        const float* s_std, int style_n, int k, const float* weights, int weights_n, int weights_hw, float alpha,
+                        float one_minus_alpha, const float* const* depth_maps, const int* depth_h, const int* depth_w, float depth_offset,
+                        float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c, int mask_h, int mask_w, uint8_t* out_u8,
+                        void* workspace, size_t ws_bytes, adain_stream_t stream) {
     if (!frames || !enc_packed || !dec_packed || !s_mean || !s_std || !out_u8 || !workspace) { set_error("stylize_u8: null pointer"); return ADAIN_EINVAL; }
     if (n < 1 || h < 9 || w < 9) { set_error("stylize_u8: frames %dx%d too small (needs h, w >= 9)", h, w); return ADAIN_EINVAL; }
-    if (style_n != 1 && style_n != n) { set_error("stylize_u8: %d styles for %d frames (1 or one per frame)", style_n, n); return ADAIN_EINVAL; }
+    if (!weights && style_n != 1 && style_n != n) { set_error("stylize_u8: %d styles for %d frames (1 or one per frame)", style_n, n); return ADAIN_EINVAL; }
+    if (weights) {          // the mix's own rules, on the relu4_1 map's size
+        int hc, wc;
+        adain_encoded_size(h, w, &hc, &wc);
+        if (check_adain_blend_mix(1, n, 512, hc * wc, k, weights_n, weights_hw, 0, 1)) return ADAIN_EINVAL;
+    }
     if (!depth_maps && !(alpha >= 0.f && alpha <= 1.f)) { set_error("stylize_u8: alpha %g outside [0, 1]", alpha); return ADAIN_EINVAL; }   // test.py:75
     if (depth_maps && (!depth_h || !depth_w)) { set_error("stylize_u8: depth maps without their sizes"); return ADAIN_EINVAL; }
     if (depth_maps && !(depth_offset >= 0.f && depth_offset <= 1.f)) { set_error("stylize_u8: offset %g outside [0, 1]", depth_offset); return ADAIN_EINVAL; }   // test.py:56
@@ -654,7 +663,10 @@ int adain_stylize_u8_ex(const uint8_t* frames, int n, int h, int w, const float*
             RET_IF(launch_strength_map(depth_maps[i], depth_h[i], depth_w[i], p.hc, p.wc, depth_offset, depth_prominence, pmap + (size_t)i * hw_c,
                                        pmap_ws, p.pmap_ws * sizeof(float), s));
         }
-        RET_IF(launch_adain_blend_ex(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, style_n, 0.f, 0.f, pmap, n, g, s));
+        if (weights) RET_IF(launch_adain_blend_mix(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, k, weights, weights_n, weights_hw, 0.f, 0.f, pmap, n, g, s));
+        else RET_IF(launch_adain_blend_ex(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, style_n, 0.f, 0.f, pmap, n, g, s));
+    } else if (weights) {   // the same blend of the weighted mix of k styles (test_video.py:36-44)
+        RET_IF(launch_adain_blend_mix(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, k, weights, weights_n, weights_hw, alpha, one_minus_alpha, nullptr, 1, g, s));
     } else {                // AdaIN * alpha + content_f * (1 - alpha) (test.py:79-80)
         RET_IF(launch_adain_blend_ex(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, style_n, alpha, one_minus_alpha, nullptr, 1, g, s));
     }
@@ -684,6 +696,39 @@ int adain_stylize_u8_ex(const uint8_t* frames, int n, int h, int w, const float*
     }
     RET_IF(launch_mask_composite(content_f, sty, m, mask_c, mask_n, comp, n, 3, h * w, s));
     return launch_quantize_u8(comp, out_u8, n, 3, h, w, s);
+}
+
+int adain_stylize_u8(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const float* s_mean,
+                     const float* s_std, float alpha, float one_minus_alpha, const float* const* depth_maps, const int* depth_h, const int* depth_w,
+                     float depth_offset, float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c, int mask_h,
+                     int mask_w, uint8_t* out_u8, void* workspace, size_t ws_bytes, adain_stream_t stream) {
+    return stylize_impl(frames, n, h, w, enc_packed, dec_packed, s_mean, s_std, 1, 0, nullptr, 0, 0, alpha, one_minus_alpha, depth_maps, depth_h, depth_w,
+                        depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes, stream);
+}
+
+// s_mean / s_std [style_n][512], style_n 1 (adain_stylize_u8) or n: one style per frame
+int adain_stylize_u8_ex(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const float* s_mean,
+                        const float* s_std, int style_n, float alpha, float one_minus_alpha, const float* const* depth_maps, const int* depth_h,
+                        const int* depth_w, float depth_offset, float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c,
+                        int mask_h, int mask_w, uint8_t* out_u8, void* workspace, size_t ws_bytes, adain_stream_t stream) {
+    return stylize_impl(frames, n, h, w, enc_packed, dec_packed, s_mean, s_std, style_n, 0, nullptr, 0, 0, alpha, one_minus_alpha, depth_maps, depth_h,
+                        depth_w, depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes, stream);
+}
+
+size_t adain_stylize_u8_mix_workspace_bytes(int n, int h, int w, int use_depth, int mask_n, int mask_c, int mask_h, int mask_w, int mask_is_float) {
+    return adain_stylize_u8_workspace_bytes(n, h, w, use_depth, mask_n, mask_c, mask_h, mask_w, mask_is_float);
+}
+
+// s_mean / s_std [k][512] mixed by weights [weights_n][k][weights_hw] (adain_blend_mix in place of adain_blend_alpha / _pmap)
+int adain_stylize_u8_mix(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const float* s_mean,
+                         const float* s_std, int k, const float* weights, int weights_n, int weights_hw, float alpha, float one_minus_alpha,
+                         const float* const* depth_maps, const int* depth_h, const int* depth_w, float depth_offset, float depth_prominence,
+                         const void* mask, int mask_is_float, int mask_n, int mask_c, int mask_h, int mask_w, uint8_t* out_u8, void* workspace,
+                         size_t ws_bytes, adain_stream_t stream) {
+    if (!weights) { set_error("stylize_u8_mix: null pointer"); return ADAIN_EINVAL; }
+    return stylize_impl(frames, n, h, w, enc_packed, dec_packed, s_mean, s_std, 1, k, weights, weights_n, weights_hw, alpha, one_minus_alpha, depth_maps,
+                        depth_h, depth_w, depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes,
+                        stream);
 }
 
 size_t adain_coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc) { return coral_workspace_bytes(n, style_n, hs, ws, hc, wc); }

@@ -111,6 +111,12 @@ size_t mean_std_workspace_bytes(int nhwc, int n, int c, int hw);
 int launch_adain_blend_ex(const float* content, int nhwc, int n, int c, int hw, const float* c_mean,
                           const float* c_std, const float* s_mean, const float* s_std, int style_n, float alpha,
                           float one_minus_alpha, const float* pmap, int pmap_n, float* out, hipStream_t s);
+// the blend of a weighted mix of k styles (adain_blend_mix): s_mean / s_std [k][c], weights [weights_n][k][weights_hw] on the device
+constexpr int MIX_MAX_STYLES = 16;   // ADAIN_MIX_MAX_STYLES
+int check_adain_blend_mix(int nhwc, int n, int c, int hw, int k, int weights_n, int weights_hw, int has_pmap, int pmap_n);
+int launch_adain_blend_mix(const float* content, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const float* s_mean,
+                           const float* s_std, int k, const float* weights, int weights_n, int weights_hw, float alpha, float one_minus_alpha,
+                           const float* pmap, int pmap_n, float* out, hipStream_t s);
 
 // pixel.hip
 int launch_strength_map(const float* depth, int h0, int w0, int hc, int wc, float offset, float prominence,

@@ -254,4 +254,205 @@ int launch_adain_blend_ex(const float* content, int nhwc, int n, int c, int hw, 
     return check_launch("adain_blend");
 }
 
+// ---- AdaIN + blend of a weighted mix of K styles (style interpolation) ------------------------------------------------------------
+// The reference's style_transfer(..., interpolation_weights) (Style_3DGS/AdaIN/test_video.py:30-45) in its operation order, one
+// rounding per operation, no FMA contraction:
+//   nrm  = (x - mu_c) / sigma_c                                  function.py:21-22, the same for every style
+//   b_k  = nrm * sigma_s[k] + mu_s[k]                            function.py:23
+//   feat = w_0 * b_0 ; feat = feat + w_k * b_k, k = 1 .. K-1     test_video.py:37-40 (its leading 0 + w_0 * b_0 is w_0 * b_0)
+//   out  = feat * w1 + x * w2                                    test_video.py:44; w1, w2 as in adain_blend_kernel
+// w_k is a scalar (weights_hw == 1) or a per-pixel map W[k][pixel]; the weights are [weights_n][k][weights_hw] on the device and are
+// used as given.  With K = 1 and w_0 = 1 every operation above that adain_blend_kernel lacks is exact: the same bits.
+struct MixArgs {
+    const float* x;
+    const float *c_mean, *c_std, *s_mean, *s_std;   // [n][c], [n][c], [k][c], [k][c]
+    const float* weights;
+    const float* pmap;                              // nullptr: alpha form
+    float* out;
+    int c, hw, k, weights_n, weights_hw, pmap_n;
+    float alpha, one_minus_alpha;
+};
+
+// The product shape (NHWC, c = 512) and every other NHWC shape whose c / 4 channel quads divide the workgroup: a workgroup owns
+// whole pixels of ONE image, a thread one channel quad of them.  The thread keeps its quad of the content statistics and of the K
+// styles' (2 K + 2 b128 loads, once) in registers and then walks pixels with one b128 load and one b128 store each: 8 bytes per
+// element whatever K is.  KB bounds K at compile time so that the statistics are registers, not scratch: 4 (34 VGPRs of statistics)
+// or MIX_MAX_STYLES (130).  A pixel's weights and strength are the same for the lanes of its row (at c = 512 a row is two waves).
+template <int KB, bool MAPS>
+__global__ __launch_bounds__(256) void adain_mix_walk_kernel(const MixArgs a, int cols_log2, int bpi) {
+#pragma clang fp contract(off)
+    constexpr int UN = KB <= 4 ? 4 : 2;             // pixels in flight per thread
+    const unsigned c = (unsigned)a.c, hw = (unsigned)a.hw;
+    const unsigned tid = threadIdx.x, col = tid & ((1u << cols_log2) - 1u), row = tid >> cols_log2;
+    const unsigned rows = 256u >> cols_log2;
+    const unsigned img = blockIdx.x / (unsigned)bpi, b = blockIdx.x - img * (unsigned)bpi;
+    const unsigned ch = col * 4u;
+    const f32x4 mc = *(const f32x4*)(a.c_mean + (size_t)img * c + ch), sc = *(const f32x4*)(a.c_std + (size_t)img * c + ch);
+    const float* __restrict__ wrow = a.weights + (size_t)(a.weights_n == 1 ? 0u : img) * a.k * a.weights_hw;
+    f32x4 ms[KB], ss[KB];
+    float wk[KB];
+#pragma unroll
+    for (int j = 0; j < KB; ++j) {
+        ms[j] = ss[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        wk[j] = 0.f;
+        if (j < a.k) {
+            ms[j] = *(const f32x4*)(a.s_mean + (unsigned)j * c + ch);
+            ss[j] = *(const f32x4*)(a.s_std + (unsigned)j * c + ch);
+            if (!MAPS) wk[j] = wrow[j];
+        }
+    }
+    const float* __restrict__ xb = a.x + (size_t)img * hw * c + ch;
+    float* __restrict__ ob = a.out + (size_t)img * hw * c + ch;
+    const float* __restrict__ pb = a.pmap ? a.pmap + (size_t)(a.pmap_n == 1 ? 0u : img) * hw : nullptr;
+    auto one = [&](unsigned p, const f32x4 v) {
+#pragma clang fp contract(off)
+        float w1 = a.alpha, w2 = a.one_minus_alpha;
+        if (pb) {
+            const float pp = pb[p];
+            w1 = 1.0f - pp;
+            w2 = pp;
+        }
+        const f32x4 nrm = (v - mc) / sc;
+        f32x4 feat = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < KB; ++j) {
+            if (j < a.k) {
+                const float w = MAPS ? wrow[(size_t)j * hw + p] : wk[j];
+                const f32x4 t = nrm * ss[j] + ms[j];
+                const f32x4 wt = t * w;
+                feat = j ? feat + wt : wt;
+            }
+        }
+        const f32x4 l = feat * w1, r = v * w2;
+        *(f32x4*)(ob + p * c) = l + r;
+    };
+    if (row < rows) {
+        const unsigned step = (unsigned)bpi * rows;
+        unsigned p = b * rows + row;
+        for (; p + (UN - 1) * step < hw; p += UN * step) {
+            f32x4 v[UN];
+#pragma unroll
+            for (int u = 0; u < UN; ++u) v[u] = *(const f32x4*)(xb + (p + u * step) * c);
+#pragma unroll
+            for (int u = 0; u < UN; ++u) one(p + u * step, v[u]);
+        }
+        for (; p < hw; p += step) one(p, *(const f32x4*)(xb + p * c));
+    }
+}
+
+// Every other shape, with adain_blend_kernel's indexing: NHWC with any c % 4 == 0 (a quad is four channels of one pixel; the
+// statistics are b128 loads per style and quad) and NCHW (a quad may straddle images, so every element takes its own image).
+template <bool NHWC>
+__global__ __launch_bounds__(256) void adain_mix_flat_kernel(const MixArgs a, size_t total4) {
+#pragma clang fp contract(off)
+    const unsigned c = (unsigned)a.c, hw = (unsigned)a.hw, k = (unsigned)a.k, whw = (unsigned)a.weights_hw;
+    const unsigned per_img = c * hw;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)total4; i += gridDim.x * blockDim.x) {
+        const unsigned e = i * 4u;
+        const f32x4 v = *(const f32x4*)(a.x + e);
+        f32x4 r;
+        const unsigned img = e / per_img;
+        const unsigned rem = e - img * per_img;
+        if (NHWC) {
+            const unsigned pix = rem / c, ch = rem - pix * c;
+            const f32x4 mc = *(const f32x4*)(a.c_mean + img * c + ch), sc = *(const f32x4*)(a.c_std + img * c + ch);
+            float w1 = a.alpha, w2 = a.one_minus_alpha;
+            if (a.pmap) {
+                const float p = a.pmap[(size_t)(a.pmap_n == 1 ? 0u : img) * hw + pix];
+                w1 = 1.0f - p;
+                w2 = p;
+            }
+            const float* __restrict__ wp = a.weights + (size_t)(a.weights_n == 1 ? 0u : img) * k * whw + (whw == 1 ? 0u : pix);
+            const f32x4 nrm = (v - mc) / sc;
+            f32x4 feat = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (unsigned j = 0; j < k; ++j) {
+                const f32x4 ms = *(const f32x4*)(a.s_mean + j * c + ch), ss = *(const f32x4*)(a.s_std + j * c + ch);
+                const f32x4 t = nrm * ss + ms;
+                const f32x4 wt = t * wp[(size_t)j * whw];
+                feat = j ? feat + wt : wt;
+            }
+            const f32x4 l = feat * w1, rr = v * w2;
+            r = l + rr;
+        } else {
+            unsigned ik = img, rk = rem;
+#pragma unroll
+            for (int q = 0; q < 4; ++q, ++rk) {
+                if (rk >= per_img) {
+                    rk -= per_img;
+                    ++ik;
+                }
+                const unsigned ch = rk / hw, pix = rk - ch * hw;
+                const float mc = a.c_mean[ik * c + ch], sc = a.c_std[ik * c + ch];
+                float w1 = a.alpha, w2 = a.one_minus_alpha;
+                if (a.pmap) {
+                    const float p = a.pmap[(size_t)(a.pmap_n == 1 ? 0u : ik) * hw + pix];
+                    w1 = 1.0f - p;
+                    w2 = p;
+                }
+                const float* __restrict__ wp = a.weights + (size_t)(a.weights_n == 1 ? 0u : ik) * k * whw + (whw == 1 ? 0u : pix);
+                const float nrm = (v[q] - mc) / sc;
+                float feat = 0.f;
+                for (unsigned j = 0; j < k; ++j) {
+                    const float t = nrm * a.s_std[j * c + ch] + a.s_mean[j * c + ch];
+                    const float wt = t * wp[(size_t)j * whw];
+                    feat = j ? feat + wt : wt;
+                }
+                const float l = feat * w1, rr = v[q] * w2;
+                r[q] = l + rr;
+            }
+        }
+        *(f32x4*)(a.out + e) = r;
+    }
+}
+
+// host only, no HIP call: the argument rules of adain_blend_mix (and of the blend inside adain_stylize_u8_mix)
+int check_adain_blend_mix(int nhwc, int n, int c, int hw, int k, int weights_n, int weights_hw, int has_pmap, int pmap_n) {
+    if (n < 1 || c < 1 || hw < 1) { set_error("adain_blend_mix: bad shape n=%d c=%d hw=%d", n, c, hw); return -1; }
+    if (k < 1 || k > MIX_MAX_STYLES) { set_error("adain_blend_mix: %d styles (1..%d)", k, MIX_MAX_STYLES); return -1; }
+    if (weights_n != 1 && weights_n != n) { set_error("adain_blend_mix: weights batch %d must be 1 or %d", weights_n, n); return -1; }
+    if (weights_hw != 1 && weights_hw != hw) { set_error("adain_blend_mix: weights per style %d must be 1 or %d (hw)", weights_hw, hw); return -1; }
+    if (has_pmap && pmap_n != 1 && pmap_n != n) { set_error("adain_blend_mix: pmap batch %d must be 1 or %d", pmap_n, n); return -1; }
+    const size_t total = (size_t)n * c * hw;
+    if (nhwc ? (c & 3) : (total & 3)) { set_error("adain_blend_mix: element count / channels must be a multiple of 4"); return -1; }
+    if (total >= 0x7fffffffULL) { set_error("adain_blend_mix: more than 2^31 elements per call"); return -1; }
+    return 0;
+}
+
+// Launcher branches:
+//   NHWC, c / 4 a power of two <= 256 (c = 4 .. 1024; the product's 512): adain_mix_walk_kernel, KB = 4 for k <= 4 and MIX_MAX_STYLES
+//     above, scalar weights or maps; ceil(pixel rows / 8) workgroups per image, at most 2048 / n (at least 1): more pixels per thread
+//     on large maps, so that the statistics' loads stay a small share
+//   any other NHWC c, and NCHW: adain_mix_flat_kernel, at most 8192 workgroups, grid-stride
+int launch_adain_blend_mix(const float* content, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const float* s_mean,
+                           const float* s_std, int k, const float* weights, int weights_n, int weights_hw, float alpha, float one_minus_alpha,
+                           const float* pmap, int pmap_n, float* out, hipStream_t s) {
+    if (check_adain_blend_mix(nhwc, n, c, hw, k, weights_n, weights_hw, pmap != nullptr, pmap_n)) return -1;
+    const MixArgs a{content, c_mean, c_std, s_mean, s_std, weights, pmap, out, c, hw, k, weights_n, weights_hw, pmap_n, alpha, one_minus_alpha};
+    const int cols = c >> 2;
+    if (nhwc && cols <= 256 && (cols & (cols - 1)) == 0) {
+        int cols_log2 = 0;
+        while ((1 << cols_log2) < cols) ++cols_log2;
+        const int rows = 256 / cols;
+        const int groups = (hw + rows - 1) / rows;
+        int bpi = (groups + 7) / 8;
+        const int cap = n < 2048 ? 2048 / n : 1;
+        if (bpi > cap) bpi = cap;
+        const dim3 grid((unsigned)((size_t)n * bpi));
+        const bool maps = weights_hw != 1;
+        if (k <= 4) {
+            if (maps) hipLaunchKernelGGL((adain_mix_walk_kernel<4, true>), grid, dim3(256), 0, s, a, cols_log2, bpi);
+            else hipLaunchKernelGGL((adain_mix_walk_kernel<4, false>), grid, dim3(256), 0, s, a, cols_log2, bpi);
+        } else {
+            if (maps) hipLaunchKernelGGL((adain_mix_walk_kernel<MIX_MAX_STYLES, true>), grid, dim3(256), 0, s, a, cols_log2, bpi);
+            else hipLaunchKernelGGL((adain_mix_walk_kernel<MIX_MAX_STYLES, false>), grid, dim3(256), 0, s, a, cols_log2, bpi);
+        }
+        return check_launch("adain_blend_mix");
+    }
+    const size_t total4 = (size_t)n * c * hw / 4;
+    const unsigned blocks = (unsigned)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
+    if (nhwc) hipLaunchKernelGGL(adain_mix_flat_kernel<true>, dim3(blocks), dim3(256), 0, s, a, total4);
+    else hipLaunchKernelGGL(adain_mix_flat_kernel<false>, dim3(blocks), dim3(256), 0, s, a, total4);
+    return check_launch("adain_blend_mix");
+}
+
 }  // namespace adain

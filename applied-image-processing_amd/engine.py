@@ -59,6 +59,29 @@ class AdaINEngine:
         self.s_mean, self.s_std = rt.mean_std(f, True)
         return self
 
+    def set_styles(self, styles):
+        """A list of K style tensors (each as ``set_style`` takes it, sizes may differ) for style interpolation: every style is
+        encoded once and the engine holds their statistics as [K,512] rows, mixed per frame by the ``style_weights`` of
+        ``stylize`` / ``stylize_depth`` / ``stylize_u8``.  ``style_stats`` / ``style_state`` and their ``use_`` twins carry the rows."""
+        styles = list(styles)
+        if not 1 <= len(styles) <= rt.MIX_MAX_STYLES:
+            raise rt.AdainHipError(f"set_styles: 1 .. {rt.MIX_MAX_STYLES} styles, got {len(styles)}")
+        rows = [self.set_style(s).style_stats() for s in styles]
+        self.s_mean, self.s_std = torch.cat([m for m, _ in rows]).contiguous(), torch.cat([sd for _, sd in rows]).contiguous()
+        self.style_px = None
+        return self
+
+    def _mix(self, style_weights, preserve_color):
+        """The device tensor of a call's ``style_weights`` (None: a single-style call, which needs a single style)."""
+        if style_weights is None:
+            if self.s_mean.shape[0] != 1:
+                raise rt.AdainHipError(f"the engine holds {self.s_mean.shape[0]} styles (set_styles): pass style_weights to mix them")
+            return None
+        if preserve_color:
+            raise rt.AdainHipError("preserve_color with style_weights is not supported: it would need coral(style_k, frame) of every "
+                                   "style for every frame")
+        return torch.as_tensor(style_weights, dtype=torch.float32).to(self.device).contiguous()
+
     def set_style_image(self, style):
         """``set_style`` that also keeps the (already resized) style's PIXELS on the device, for ``preserve_color=True``: there every
         frame is styled with its own ``coral(style, frame)`` (function.py:26-67), so the pixels are needed, not only the statistics.
@@ -105,33 +128,41 @@ class AdaINEngine:
         """(h, w) of a content batch in either form (float NCHW / uint8 NHWC)."""
         return tuple(content.shape[1:3]) if content.dtype == torch.uint8 else tuple(content.shape[-2:])
 
-    def stylize(self, content, alpha=0.5, pmap=None, preserve_color=False):
+    def stylize(self, content, alpha=0.5, pmap=None, preserve_color=False, style_weights=None):
         """content [n,3,h,w] float (or [n,h,w,3] uint8) on the GPU -> stylised [n,3,8*hc,8*wc].  ``pmap`` [1|n,1,hc,wc] switches
         to the depth-aware blend (test.py:70); otherwise the alpha blend (test.py:80).  ``preserve_color``: every frame is styled
-        with ``coral(style, frame)`` (``set_style_image`` first) instead of the style itself."""
+        with ``coral(style, frame)`` (``set_style_image`` first) instead of the style itself.  ``style_weights`` ([K], [n,K],
+        [K,hc,wc] or [n,K,hc,wc], used as given): every frame is styled with that mix of the K styles of ``set_styles``
+        (style interpolation, ``rt.blend_mix``)."""
         assert 0.0 <= alpha <= 1.0
         if self.s_mean is None:
             raise rt.AdainHipError("set_style() first")
+        style_weights = self._mix(style_weights, preserve_color)
         if preserve_color:
             content = content.to(self.device)
             content = content.contiguous() if content.dtype == torch.uint8 else content.to(torch.float32).contiguous()
         s_mean, s_std = self._coral_stats(content) if preserve_color else (self.s_mean, self.s_std)
         f = self._encode(content)
         c_mean, c_std = rt.mean_std(f, True)
-        if pmap is not None:
+        if style_weights is not None:
+            g = rt.blend_mix(f, True, c_mean, c_std, s_mean, s_std, style_weights, alpha=alpha if pmap is None else None, pmap=pmap)
+        elif pmap is not None:
             g = rt.blend_pmap(f, True, c_mean, c_std, s_mean, s_std, pmap)
         else:
             g = rt.blend_alpha(f, True, c_mean, c_std, s_mean, s_std, alpha)
         return rt.decode(g, self.dec)
 
-    def stylize_u8(self, frames_u8, alpha=0.5, depth_maps=None, offset=0.15, prominence=20, masks=None, out=None, preserve_color=False):
+    def stylize_u8(self, frames_u8, alpha=0.5, depth_maps=None, offset=0.15, prominence=20, masks=None, out=None, preserve_color=False,
+                   style_weights=None):
         """A sub-batch of decoded frames uint8 [n,h,w,3] -> finished uint8 frames [n,H,W,3] in ONE call of the C ABI
         (``adain_stylize_u8``): what ``stylize`` / ``stylize_depth`` -> ``composite`` -> ``to_u8`` give, byte for byte, with one
         Python -> C transition per sub-batch instead of eight (the job drivers' launching thread is what eight ranks share).
         ``preserve_color``: coral -> encoder -> statistics of the n recoloured styles first (three more calls), then the same one
-        call with one style per frame (``adain_stylize_u8_ex``); a frame's bytes do not depend on the sub-batch it is in."""
+        call with one style per frame (``adain_stylize_u8_ex``); a frame's bytes do not depend on the sub-batch it is in.
+        ``style_weights``: the mix of ``set_styles``' K styles per frame, as for ``stylize`` (``adain_stylize_u8_mix``, still one call)."""
         if self.s_mean is None:
             raise rt.AdainHipError("set_style() first")
+        style_weights = self._mix(style_weights, preserve_color)
         assert 0.0 <= alpha <= 1.0 and 0.0 <= offset <= 1.0
         if depth_maps is not None:
             depth_maps = [d.to(self.device, torch.float32) for d in depth_maps]
@@ -145,15 +176,16 @@ class AdaINEngine:
             s_mean, s_std = self._coral_stats(frames_u8)
             return rt.stylize_u8(frames_u8, self.enc, self.dec, s_mean, s_std, alpha, depth_maps, offset, prominence, masks, out,
                                  style_n=frames_u8.shape[0])
-        return rt.stylize_u8(frames_u8, self.enc, self.dec, self.s_mean, self.s_std, alpha, depth_maps, offset, prominence, masks, out)
+        return rt.stylize_u8(frames_u8, self.enc, self.dec, self.s_mean, self.s_std, alpha, depth_maps, offset, prominence, masks, out,
+                             style_weights=style_weights)
 
-    def stylize_depth(self, content, depth_maps, offset=0.15, prominence=20, preserve_color=False):
+    def stylize_depth(self, content, depth_maps, offset=0.15, prominence=20, preserve_color=False, style_weights=None):
         """Depth-aware path for a batch: ``depth_maps`` is a list of [h0,w0] GPU tensors, one per frame."""
         assert 0.0 <= offset <= 1.0
         h, w = self.frame_size(content)
         hc, wc = rt.encoded_size(h, w)
         p = torch.cat([rt.strength_map(d, hc, wc, offset, prominence) for d in depth_maps])
-        return self.stylize(content, pmap=p, preserve_color=preserve_color)
+        return self.stylize(content, pmap=p, preserve_color=preserve_color, style_weights=style_weights)
 
     def composite(self, content, stylized, masks):
         """masks [n|1, 1|3, hm, wm] float -> content*(1-m) + resize(stylized)*m (test.py:222-236)."""

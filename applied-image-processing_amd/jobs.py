@@ -51,6 +51,34 @@ def style_schedule(n_frames, n_styles):
     return out
 
 
+def style_crossfade(n_frames, n_styles, fade):
+    """Style-mix weights per frame, float32 [n_frames][n_styles], for a clip that cross-fades where ``style_schedule`` cuts: at every
+    switch point s (the frame whose index advances from style a to a + 1) the ``fade`` frames s - fade // 2 .. s - fade // 2 + fade - 1
+    ramp linearly, frame f of them (j = f - (s - fade // 2)) taking (j + 1) / (fade + 1) of style a + 1 and the rest of style a.
+    The ramp is computed in double and rounded once; the two weights of a ramp frame are t and 1 - t rounded, every other frame is
+    one-hot: rows sum to 1 (within one rounding).  ``fade=0``: one-hot rows at ``style_schedule``'s indices.  Ramps of neighbouring
+    switch points must not overlap (``fade`` at most the frames per style), and a ramp is clipped at the ends of the clip."""
+    idx = style_schedule(n_frames, n_styles)
+    fade = int(fade)
+    if fade < 0:
+        raise ValueError("style_crossfade: fade must be >= 0")
+    if fade > max(1, n_frames // n_styles):
+        raise ValueError(f"style_crossfade: fade {fade} is longer than the {max(1, n_frames // n_styles)} frames a style is shown for")
+    rows = np.zeros((n_frames, n_styles), dtype=np.float64)
+    rows[np.arange(n_frames), idx] = 1.0
+    for s in range(1, n_frames):
+        if idx[s] == idx[s - 1]:
+            continue
+        a, first = idx[s - 1], s - fade // 2
+        for j in range(fade):
+            f = first + j
+            if 0 <= f < n_frames:
+                t = (j + 1) / (fade + 1)
+                rows[f] = 0.0
+                rows[f, a], rows[f, a + 1] = 1.0 - t, t
+    return rows.astype(np.float32)
+
+
 host_barrier = sh.host_barrier
 
 
@@ -569,10 +597,13 @@ def _elapsed(engine, a, b):
     return f(a, b) if f is not None else b - a
 
 
-def _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence, preserve_color=False):
-    """One sub-batch of the feeder on the engine -> the finished uint8 frames [k,H,W,3]."""
+def _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence, preserve_color=False, style_weights=None):
+    """One sub-batch of the feeder on the engine -> the finished uint8 frames [k,H,W,3].  ``style_weights``: the sub-batch's rows of
+    the job's style-mix weights, on the device."""
     content, dev = batch.content, engine.device
     coral = {"preserve_color": True} if preserve_color else {}      # only named when asked for: engines without the keyword keep working
+    if style_weights is not None:
+        coral["style_weights"] = style_weights
     one_call = getattr(engine, "stylize_u8", None)
     if (one_call is not None and content.dtype == torch.uint8 and content.dim() == 4 and content.shape[-1] == 3
             and not isinstance(batch.mask, list)):
@@ -711,7 +742,7 @@ class _BlockGather:
 def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, depth_maps=None, depth_offset=0.15,
                            depth_prominence=20, masks=None, post=None, sub_batch=None, group=None, dst=0, gather=True,
                            require_transport=None, style_cache=None, out_hw=None, gather_chunks=1, sink=None,
-                           prefetch=4, host_out=None, fetch_workers=4, preserve_color=False):
+                           prefetch=4, host_out=None, fetch_workers=4, preserve_color=False, style_weights=None):
     """Stylises ``frames`` (a sequence indexed lazily: a rank only ever touches its own block; an element is a decoded
     frame uint8 [h,w,3] / RGB PIL image, or a float tensor [3,h,w] in [0,1]) and returns ``(frames_u8, info)``: the uint8
     frames [n,H,W,3] in frame order on rank ``dst`` (None on the other ranks; with ``gather=False`` the local block — a
@@ -728,6 +759,11 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
                     ``preserve_color``, test.py:201-202), on the device: each style's PIXELS stay resident next to its statistics
                     (``engine.set_style_image``; in ``style_cache`` under ``("pixels", index)``).  A frame's bytes do not depend on
                     the sub-batch or the shard it is in.
+    style_weights   style interpolation: float32 rows [n][K] (``style_crossfade``), K = the number of ``styles``; frame i is styled with
+                    the mix ``style_weights[i]`` of ALL the styles (``engine.set_styles``, once per call; in ``style_cache`` under
+                    ``"mix"``) instead of the one style ``style_of[i]`` picks.  The rows go to the device once and every sub-batch takes
+                    its slice; they are used as given.  A frame's bytes do not depend on the sub-batch or the shard it is in.  Not
+                    with ``preserve_color`` or ``style_of``.
     sub_batch       frames per sub-batch; None (default) = chosen from the frame size, about three megapixels per sub-batch
                     (``auto_sub_batch``: 26 frames of 256 x 456, 6 of 512 x 912; 4 of 1080p or 1200 x 1600 - inside the measured optima).
     post            optional ``f(u8_block) -> u8_block`` applied per sub-batch on the owning rank BEFORE the gather
@@ -751,6 +787,12 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
     n = len(frames)
     lo, hi = sh.shard_range(n, world, rank)
     style_list = list(styles) if isinstance(styles, (list, tuple)) else [styles]
+    if style_weights is not None:
+        if style_of is not None or preserve_color:
+            raise ValueError("style_weights mixes every style into every frame: it goes with neither style_of nor preserve_color")
+        style_weights = np.ascontiguousarray(np.asarray(style_weights, dtype=np.float32))
+        if style_weights.shape != (n, len(style_list)):
+            raise ValueError(f"style_weights must be [{n}][{len(style_list)}] (one row per frame, one weight per style), got {style_weights.shape}")
     if style_of is None:
         style_of = [0] * n
     if len(style_of) != n:
@@ -786,11 +828,17 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
     try:
         cur_style = None
         stats = style_cache if style_cache is not None else {}
+        mix = None
+        if style_weights is not None and hi > lo:
+            if "mix" not in stats:
+                stats["mix"] = engine.set_styles(style_list).style_stats()
+            engine.use_style_stats(stats["mix"])
+            mix = torch.from_numpy(style_weights).to(dev)          # the whole clip's rows, resident for the call
         for batch in feeder:
             if on_gpu and len(queued) >= MAX_QUEUED_BATCHES:
                 sleep_wait(queued.pop(0))
             i, j = batch.i, batch.j
-            if style_of[i] != cur_style:
+            if mix is None and style_of[i] != cur_style:
                 cur_style = style_of[i]
                 if preserve_color:
                     if ("pixels", cur_style) not in stats:
@@ -800,7 +848,7 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
                     if cur_style not in stats:
                         stats[cur_style] = engine.set_style(style_list[cur_style]).style_stats()
                     engine.use_style_stats(stats[cur_style])
-            u8 = _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence, preserve_color)
+            u8 = _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence, preserve_color, None if mix is None else mix[i:j])
             feeder.release(batch)
             if on_gpu:
                 queued.append(_event(dev))

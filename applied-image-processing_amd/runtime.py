@@ -50,6 +50,8 @@ SIGNATURES = {
                                    _c_float, _c_float, _c_void_p, _c_void_p]),
     "adain_blend_pmap": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int,
                                   _c_void_p, _c_int, _c_void_p, _c_void_p]),
+    "adain_blend_mix": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int,
+                                 _c_int, _c_float, _c_float, _c_void_p, _c_int, _c_void_p, _c_void_p]),
     "adain_strength_map_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
     "adain_strength_map": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_resize_bilinear": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
@@ -91,6 +93,10 @@ SIGNATURES = {
     "adain_stylize_u8_ex": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_float, _c_float, _PP,
                                      ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), _c_float, _c_float, _c_void_p, _c_int, _c_int, _c_int, _c_int,
                                      _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_stylize_u8_mix_workspace_bytes": (_c_size_t, [_c_int] * 9),
+    "adain_stylize_u8_mix": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int,
+                                      _c_float, _c_float, _PP, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), _c_float, _c_float, _c_void_p, _c_int,
+                                      _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_nhwc_to_nchw": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
@@ -433,6 +439,53 @@ def blend_pmap(x, nhwc, c_mean, c_std, s_mean, s_std, pmap):
     return out
 
 
+MIX_MAX_STYLES = 16          # ADAIN_MIX_MAX_STYLES
+
+
+def mix_weights(weights, n, k, hc, wc, device, what):
+    """Style-mix weights as the C ABI takes them: ``weights`` float32 on ``device`` shaped [k], [n,k], [k,hc,wc] or [n,k,hc,wc]
+    (a row for all frames or one per frame; scalars or maps at feature resolution) -> (contiguous tensor, weights_n, weights_hw).
+    The values are handed over as they are: nothing normalises them."""
+    weights = device_tensor(weights, f"{what}: style weights")
+    shapes = {(k,): (1, 1), (n, k): (n, 1), (k, hc, wc): (1, hc * wc), (n, k, hc, wc): (n, hc * wc)}
+    if weights.device != device or tuple(weights.shape) not in shapes:
+        raise AdainHipError(f"{what}: style weights must be [{k}], [{n},{k}], [{k},{hc},{wc}] or [{n},{k},{hc},{wc}] on the features' device, "
+                            f"got {tuple(weights.shape)}")
+    return (weights,) + shapes[tuple(weights.shape)]
+
+
+def blend_mix(x, nhwc, c_mean, c_std, s_mean, s_std, weights, alpha=None, pmap=None):
+    """The blend of a weighted mix of K styles (``adain_blend_mix``; test_video.py:36-44): feat = sum_k w_k (nrm * s_std[k] +
+    s_mean[k]) accumulated in style order, then feat * alpha + x * (1 - alpha), or feat * (1 - P) + x * P when ``pmap`` [1|n,...] is
+    given.  s_mean / s_std [K,c]: one set of styles for the batch; ``weights`` [K], [n,K], [K,hc,wc] or [n,K,hc,wc] on the device,
+    used as given.  Exactly one of ``alpha`` and ``pmap``."""
+    if (alpha is None) == (pmap is None):
+        raise AdainHipError("blend_mix: exactly one of alpha and pmap")
+    x = device_tensor(x, "content_feat")
+    if x.dim() != 4:
+        raise AdainHipError(f"blend_mix: expected a 4-D feature tensor, got {tuple(x.shape)}")
+    n, c, hw = _feat_dims(x, nhwc)
+    hc, wc = (x.shape[1], x.shape[2]) if nhwc else (x.shape[2], x.shape[3])
+    s_mean, s_std = device_tensor(s_mean, "s_mean"), device_tensor(s_std, "s_std")
+    k = s_mean.numel() // c
+    if not 1 <= k <= MIX_MAX_STYLES or s_mean.numel() != k * c or s_std.numel() != k * c:
+        raise AdainHipError(f"blend_mix: style statistics must be [K,{c}] each with 1 <= K <= {MIX_MAX_STYLES}, got {tuple(s_mean.shape)}, "
+                            f"{tuple(s_std.shape)}")
+    weights, wn, whw = mix_weights(weights, n, k, hc, wc, x.device, "blend_mix")
+    p_ptr, pn = None, 1
+    if pmap is not None:
+        pmap = device_tensor(pmap, "pmap")
+        pn = pmap.numel() // hw
+        if pn * hw != pmap.numel():
+            raise AdainHipError("blend_mix: strength map size does not match the feature map")
+        p_ptr = pmap.data_ptr()
+    a = 0.0 if alpha is None else float(alpha)
+    out = torch.empty_like(x)
+    call("adain_blend_mix", x.device, x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(), s_mean.data_ptr(), s_std.data_ptr(),
+         k, weights.data_ptr(), wn, whw, a, float(1 - a), p_ptr, pn, out.data_ptr())
+    return out
+
+
 def strength_map(depth, hc, wc, offset, prominence):
     """depth [h0,w0] -> P [1,1,hc,wc]."""
     depth = device_tensor(depth, "depth_map")
@@ -496,20 +549,30 @@ def quantize_u8(img, out=None):
 
 
 def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, depth_maps=None, depth_offset=0.15, depth_prominence=20,
-               mask=None, out=None, style_n=None):
+               mask=None, out=None, style_n=None, style_weights=None):
     """One sub-batch of decoded frames through the whole path in ONE call of the C ABI (``adain_stylize_u8``: ToTensor + encoder,
     statistics, AdaIN blend - the alpha form, or the depth-aware form when ``depth_maps`` (one [h0,w0] float GPU tensor per frame)
     are given - decoder, mask composite, uint8 quantiser); the bytes the separate calls give.  frames_u8 uint8 [n,h,w,3]; s_mean /
     s_std [1,512]; mask [1|n, 1|3, hm, wm] uint8 / bool / float32 on the GPU.  Returns uint8 [n,oh,ow,3] (``out`` if given).
     ``style_n`` (1 or n): the call goes through ``adain_stylize_u8_ex`` with s_mean / s_std [style_n,512], one style per frame when
-    it is n (the colour-preserving path: every frame has its own recoloured style)."""
+    it is n (the colour-preserving path: every frame has its own recoloured style).
+    ``style_weights`` ([K], [n,K], [K,hc,wc] or [n,K,hc,wc] on the device, used as given): the call goes through
+    ``adain_stylize_u8_mix`` with s_mean / s_std [K,512], every frame styled with the weighted mix of the K styles (``blend_mix``)."""
     x = device_tensor(frames_u8, "frames", torch.uint8)
     if x.dim() != 4 or x.shape[3] != 3:
         raise AdainHipError(f"stylize_u8: expected uint8 [n,h,w,3], got {tuple(x.shape)}")
     n, h, w, _ = x.shape
     dev = x.device
     s_mean, s_std = device_tensor(s_mean, "s_mean"), device_tensor(s_std, "s_std")
-    if style_n is None:
+    if style_weights is not None:
+        if style_n is not None:
+            raise AdainHipError("stylize_u8: style_weights mixes one set of styles for the batch; style_n does not apply")
+        k = s_mean.numel() // 512
+        if not 1 <= k <= MIX_MAX_STYLES or s_mean.numel() != k * 512 or s_std.numel() != k * 512 or s_mean.device != dev or s_std.device != dev:
+            raise AdainHipError(f"stylize_u8: a style mix needs statistics [K,512] each on the frames' device, 1 <= K <= {MIX_MAX_STYLES}, got "
+                                f"{tuple(s_mean.shape)}, {tuple(s_std.shape)}")
+        style_weights, wn, whw = mix_weights(style_weights, n, k, *encoded_size(h, w), dev, "stylize_u8")
+    elif style_n is None:
         if s_mean.numel() != 512 or s_std.numel() != 512:
             raise AdainHipError("stylize_u8: the style statistics must be [1,512] each (one style per call)")
     else:
@@ -546,7 +609,10 @@ def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, dept
         out = torch.empty(shape, dtype=torch.uint8, device=dev)
     else:
         check_buffer(out, "stylize_u8: out", torch.uint8, dev, shape=shape)
-    name, styles = ("adain_stylize_u8", ()) if style_n is None else ("adain_stylize_u8_ex", (style_n,))
+    if style_weights is not None:
+        name, styles = "adain_stylize_u8_mix", (k, style_weights.data_ptr(), wn, whw)
+    else:
+        name, styles = ("adain_stylize_u8", ()) if style_n is None else ("adain_stylize_u8_ex", (style_n,))
     with scratch(dev, "stylize", f"{name}_workspace_bytes", n, h, w, int(depth_maps is not None), mn, mc, mh, mw, m_float) as ws:
         _launch(name, x.data_ptr(), n, h, w, enc_packed.data_ptr(), dec_packed.data_ptr(), s_mean.data_ptr(), s_std.data_ptr(), *styles,
                 float(alpha), float(1 - alpha), dp, dh, dw, float(depth_offset), float(depth_prominence), m_ptr, m_float, mn, mc, mh, mw,

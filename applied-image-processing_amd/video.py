@@ -152,7 +152,7 @@ def _jpeg_roundtrip(u8):
 
 
 def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device=False, preserve_color=False):
+         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device=False, preserve_color=False, crossfade_frames=0):
     from . import sharding as sh
     from .engine import AdaINEngine
 
@@ -211,8 +211,12 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
     post = None
     if intermediate_jpeg:
         post = lambda u8: torch.from_numpy(_jpeg_roundtrip(u8.cpu().numpy())).to(u8.device)
+    if crossfade_frames:        # the styles cross-fade in feature space where the schedule cuts: per-frame weights instead of an index
+        which = {"style_weights": jobs.style_crossfade(len(names), len(styles), crossfade_frames)}
+    else:
+        which = {"style_of": jobs.style_schedule(len(names), len(styles))}
     frames_u8, info = jobs.stylize_frames_sharded(
-        engine, Frames(), styles, style_of=jobs.style_schedule(len(names), len(styles)), depth_maps=Depths(), depth_offset=offset,
+        engine, Frames(), styles, **which, depth_maps=Depths(), depth_offset=offset,
         depth_prominence=prominence,
         post=(lambda u8: engine.resize_area_u8(post(u8) if post else u8, target_resolution)) if target_resolution is not None else post,
         out_hw=(int(target_resolution[1]), int(target_resolution[0])) if target_resolution is not None else None,
@@ -266,11 +270,17 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
                                    cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                                    vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth",
                                    decoder_str="Style_3DGS/AdaIN/models/decoder.pth", depth_maps=None, intermediate_jpeg=False,
-                                   group=None, jpeg_on_device=False, preserve_color=False):
+                                   group=None, jpeg_on_device=False, preserve_color=False, crossfade_frames=0):
     """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372).
-    ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics."""
+    ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics.
+    ``crossfade_frames`` (0, the default: the hard cuts of the reference): the styles cross-fade in feature space over that many
+    frames centred on each switch (``jobs.style_crossfade``, style interpolation on the device; at most 16 styles, and not with
+    ``preserve_color``)."""
     style_images = sorted(os.listdir(style_dir))
     if len(style_images) == 0:
         raise ValueError("No style images found in the style directory.")
+    if crossfade_frames and preserve_color:
+        raise ValueError("crossfade_frames mixes the styles of a frame; preserve_color is not supported with it")
     return _run(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
-                cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color)
+                cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color,
+                int(crossfade_frames))

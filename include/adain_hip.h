@@ -139,6 +139,27 @@ ADAIN_API int adain_blend_pmap(const float* content_feat, int nhwc, int n, int c
                      const float* c_std, const float* s_mean, const float* s_std, int style_n, const float* pmap,
                      int pmap_n, float* out, adain_stream_t stream);
 
+/* ---- style interpolation: the blend of a weighted mix of K styles (Style_3DGS/AdaIN/test_video.py:30-45, style_transfer(...,
+ * interpolation_weights); its CLI flag --style_interpolation_weights, :77-79) ---------------------------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * One rounding per operation, in the reference's order, no fused multiply-add:
+ *   nrm  = (x - c_mean) / c_std                                  function.py:21-22, the same for every style
+ *   b_k  = nrm * s_std[k] + s_mean[k]                            function.py:23
+ *   feat = w_0 * b_0 ; feat = feat + w_k * b_k, k = 1 .. K-1     test_video.py:37-40 (its 0 + w_0 * b_0 is w_0 * b_0)
+ *   alpha form: out = feat*alpha + x*one_minus_alpha             test_video.py:44
+ *   pmap  form: out = feat*(1 - P) + x*P, P [pmap_n][hw]         the substitution style_transfer makes for one style (test.py:70)
+ * s_mean / s_std [k][c]: ONE set of k styles for the batch, 1 <= k <= ADAIN_MIX_MAX_STYLES.  weights: a DEVICE array
+ * [weights_n][k][weights_hw]; weights_n = 1 (one row for every frame) or n (a row per frame: a cross-fade through a clip);
+ * weights_hw = 1 (a scalar per style) or hw (a map per style at feature resolution, W[k][pixel] standing where w_k stood).  The
+ * weights are used as given: nothing normalises them.  pmap NULL = alpha form; pmap_n 1 or n.  Layout and alignment rules are those
+ * of adain_blend_*: c % 4 == 0 for NHWC, n*c*hw % 4 == 0 for NCHW, fewer than 2^31 elements.  Everything else is refused with
+ * ADAIN_EINVAL before anything is launched.  With k = 1 and the scalar weight 1.0f the result is adain_blend_alpha's / _pmap's bit
+ * for bit (1 * b is exact).  8 bytes of HBM traffic per element whatever k is. */
+#define ADAIN_MIX_MAX_STYLES 16
+ADAIN_API int adain_blend_mix(const float* content_feat, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std,
+                    const float* s_mean, const float* s_std, int k, const float* weights, int weights_n, int weights_hw,
+                    float alpha, float one_minus_alpha, const float* pmap, int pmap_n, float* out, adain_stream_t stream);
+
 /* ---- compute_stylization_strength_map (test.py:119-150) ------------------------------------------------
  * depth [h0][w0] -> pmap [hc][wc]: bicubic resize, min-max normalise, minus mean, sigmoid(prominence*P),
  * clamp(max = 1 - offset); an exactly constant resized map gives zeros (test.py:141-143). */
@@ -401,6 +422,20 @@ ADAIN_API int adain_stylize_u8_ex(const uint8_t* frames_nhwc_u8, int n, int h, i
                         const int* depth_h_host, const int* depth_w_host, float depth_offset, float depth_prominence, const void* mask,
                         int mask_is_float, int mask_n, int mask_c, int mask_h, int mask_w, uint8_t* out_u8, void* workspace,
                         size_t workspace_bytes, adain_stream_t stream);
+
+/* adain_stylize_u8_ex with a weighted MIX OF K STYLES per frame in place of one style: (s_mean, s_std, k, weights, weights_n,
+ * weights_hw) as adain_blend_mix takes them (s_mean / s_std [k][512]; weights on the device, [weights_n][k][weights_hw] with
+ * weights_hw = 1 or hc * wc of adain_encoded_size) where _ex takes (s_mean, s_std, style_n).  `out_u8` holds the bytes that
+ * adain_encode_u8 -> adain_mean_std -> adain_blend_mix -> adain_decode -> composite -> adain_quantize_u8 give.  No new intermediate:
+ * the workspace is adain_stylize_u8_workspace_bytes'.  (Added without a version change: ADAIN_ABI_VERSION stays 4.) */
+ADAIN_API size_t adain_stylize_u8_mix_workspace_bytes(int n, int h, int w, int use_depth, int mask_n, int mask_c, int mask_h, int mask_w,
+                                            int mask_is_float);
+ADAIN_API int adain_stylize_u8_mix(const uint8_t* frames_nhwc_u8, int n, int h, int w, const float* enc_packed, const float* dec_packed,
+                         const float* s_mean, const float* s_std, int k, const float* weights, int weights_n, int weights_hw,
+                         float alpha, float one_minus_alpha, const float* const* depth_maps_host_array_of_dev_ptrs,
+                         const int* depth_h_host, const int* depth_w_host, float depth_offset, float depth_prominence, const void* mask,
+                         int mask_is_float, int mask_n, int mask_c, int mask_h, int mask_w, uint8_t* out_u8, void* workspace,
+                         size_t workspace_bytes, adain_stream_t stream);
 
 /* ---- the callers' output files: PIL's Image.fromarray(frame).save(path) for a .jpg path (test.py:243-244 through torchvision's
  * save_image; video/utils.py:352-356 per frame), encoded on the device --------------------------------------------------------------

@@ -1,0 +1,199 @@
+"""GPU tests of the style-interpolation blend (csrc/stats.hip: ``adain_blend_mix``) against tests/mix_ref.py.  Run with ``-m gpu``.
+
+The bar is the one tests/test_gpu_blend_stats.py holds for the single-style blend: equality of every element with the float32
+restatement (``got != want`` nowhere; never a norm).  The inputs are built as that file's ``blend_inputs`` builds them - statistics
+distinct per image, channel AND style; behind the K style rows one more row offset by 1000; behind the weights one more row of
+1000s, so that a read past ``k`` or past ``weights_n`` is not the value in front of it - with the weights in [0.05, 0.9], and the
+float32 form is first held within mix_ref.self_distance_bound of the float64 form: nothing cancels.
+
+Launcher branches (csrc/stats.hip, launch_adain_blend_mix) and the shapes that walk them:
+  * NHWC with c / 4 a power of two <= 256 -> the pixel-walk kernel: (3,4,5) (256 pixel rows, one quad column), (4,64,1), the product
+    shapes (2,512,9) and (1,512,1), (2,1024,3) (the widest: one pixel row);  other NHWC c -> the flat kernel: (3,12,5), (2,520,7),
+    (2,1028,3) (257 quads), (2,2048,3) (a power of two, but 512 quads);  NCHW -> the flat kernel, quads straddling images or not.
+  * K buckets of the walk kernel: k <= 4 keeps 4 styles' statistics in registers (4 pixels in flight), k > 4 sixteen (2 in flight):
+    K = 1, 2, 3, 4 | 5, 16 on every walk shape.  hw = 9 runs the unrolled loop once and the tail once (4 in flight), twice and once (2).
+  * scalar weights | weight maps: two instantiations of the walk kernel, one index switch in the flat kernel.
+  * workgroups per image = ceil(pixel rows / 8), capped at 2048 / n: (1,512,16) one | (1,512,17) two, (2,512,37) three,
+    (1025,256,33) two capped to one."""
+import numpy as np
+import pytest
+import torch
+
+import mix_ref as M
+from blend_ref import indices
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+F32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def rt():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import applied_image_processing_amd.runtime as rt
+
+    rt.lib()
+    torch.cuda.set_device(0)
+    return rt
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def host(t):
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+def mix_inputs(nhwc, n, c, hw, k, wn, maps, pmap_n, seed=0):
+    """x O(1); content mean 10 img + 16 ch / max(c, 16) + noise, stds in [0.5, 2]; style j's mean -(7 j + that level) + noise, its std
+    in [0.5, 2]; weights 0.05 + 0.85 * uniform; strength maps 0.05 + 0.2 img + noise (at most 0.85).  The style arrays have k + 1
+    rows, the last = row 0 + 1000; the weights wn + 1 rows, the last all 1000."""
+    rng = np.random.default_rng([seed, n, c, hw, int(nhwc), k])
+    x = rng.standard_normal((n, 1, hw, c) if nhwc else (n, c, 1, hw), dtype=F32)
+    chan = 16.0 * np.arange(c)[None, :] / max(c, 16)
+    cm = (10.0 * np.arange(n)[:, None] + chan + 0.25 * rng.random((n, c))).astype(F32)
+    cs = (0.5 + 1.5 * rng.random((n, c))).astype(F32)
+    sm = np.concatenate([-(7.0 * np.arange(k)[:, None] + chan + 0.25 * rng.random((k, c))), np.zeros((1, c))]).astype(F32)
+    ss = np.concatenate([0.5 + 1.5 * rng.random((k, c)), np.zeros((1, c))]).astype(F32)
+    sm[k], ss[k] = sm[0] + 1000, ss[0] + 1000
+    whw = hw if maps else 1
+    w = np.concatenate([0.05 + 0.85 * rng.random((wn, k, whw)), np.full((1, k, whw), 1000.0)]).astype(F32)
+    assert w[:wn].min() >= 0.05 and w[:wn].max() <= 0.9
+    p = None
+    if pmap_n:
+        p = (0.05 + 0.2 * (np.arange(pmap_n)[:, None] % 4) + 0.2 * rng.random((pmap_n, hw))).astype(F32)
+        assert p.max() <= 0.85 + 1e-6
+    return x, cm, cs, sm, ss, w, p
+
+
+def run_mix(rt, nhwc, x, cm, cs, sm_buf, ss_buf, k, w_buf, wn, maps, alpha=None, p=None):
+    """The wrapper call; statistics and weights are the leading rows of longer device arrays."""
+    n, hw = x.shape[0], x.shape[2] if nhwc else x.shape[3]
+    sm, ss = dev(sm_buf)[:k], dev(ss_buf)[:k]
+    w = dev(w_buf)[:wn]
+    if maps:
+        w = w.view(wn, k, 1, hw) if wn == n else w.view(k, 1, hw)
+    else:
+        w = w.view(wn, k) if wn == n else w.view(k)
+    if n == 1 and wn == 1:          # [1,k] and [k] are one shape class then; hand over the per-frame form
+        w = w.view((1, k, 1, hw) if maps else (1, k))
+    return host(rt.blend_mix(dev(x), nhwc, dev(cm), dev(cs), sm, ss, w, alpha=alpha, pmap=None if p is None else dev(p)))
+
+
+def assert_equal_elements(what, got, want, nhwc, n, c, hw):
+    bad = np.flatnonzero(got.reshape(-1) != want.reshape(-1))
+    img, ch, pix = indices(n, c, hw, nhwc)
+    where = [(int(img[i]), int(ch[i]), int(pix[i])) for i in bad[:8]]
+    print(f"{what}: {bad.size} of {got.size} elements differ from the float32 reference" + (f", first (img, ch, pix): {where}" if bad.size else ""))
+    assert got.shape == want.shape and got.dtype == want.dtype == F32
+    assert bad.size == 0, f"{what}: {bad.size} elements differ, first (img, ch, pix) {where}: got {got.reshape(-1)[bad[:8]]}, want {want.reshape(-1)[bad[:8]]}"
+
+
+def check_mix(rt, nhwc, n, c, hw, k, wn, maps, pmap, seed=0):
+    pmap_n = {"alpha": 0, "pmap1": 1, "pmapn": n}[pmap]
+    x, cm, cs, sm, ss, w, p = mix_inputs(nhwc, n, c, hw, k, wn, maps, pmap_n, seed)
+    what = f"{'NHWC' if nhwc else 'NCHW'} ({n}, {c}, {hw}) K {k} weights_n {wn} {'maps' if maps else 'scalars'} {pmap}"
+    kw = dict(alpha=0.7) if p is None else dict(pmap=p)
+    want = M.mix(x, nhwc, cm, cs, sm[:k], ss[:k], w[:wn], **kw)
+    want64, parts = M.mix(x, nhwc, cm, cs, sm[:k], ss[:k], w[:wn], dtype=np.float64, parts=True, **kw)
+    assert (np.abs(want.astype(np.float64) - want64).reshape(-1) <= M.self_distance_bound(parts)).all(), f"{what}: the inputs cancel"
+    got = run_mix(rt, nhwc, x, cm, cs, sm, ss, k, w, wn, maps, alpha=0.7 if p is None else None, p=p)
+    assert_equal_elements(what, got, want, nhwc, n, c, hw)
+
+
+NHWC_SHAPES = [(3, 4, 5), (3, 12, 5), (2, 520, 7), (4, 64, 1), (2, 512, 9), (1, 512, 1)]
+NCHW_SHAPES = [(2, 3, 2), (4, 1, 1), (4, 3, 5), (2, 64, 99)]
+SMALL = [(True,) + s for s in NHWC_SHAPES] + [(False,) + s for s in NCHW_SHAPES]
+# the launcher's other thresholds (module docstring)
+BRANCHES = [(True, 2, 1024, 3), (True, 2, 1028, 3), (True, 2, 2048, 3), (True, 1, 512, 16), (True, 1, 512, 17), (True, 2, 512, 37)]
+ids = lambda shapes: [f"{'nhwc' if s[0] else 'nchw'}-{s[1]}x{s[2]}x{s[3]}" for s in shapes]
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 5, 16])
+@pytest.mark.parametrize("nhwc,n,c,hw", SMALL, ids=ids(SMALL))
+def test_mix_matrix(rt, nhwc, n, c, hw, k):
+    """The full product weights_n {1, n} x weights_hw {1, hw} x {alpha, pmap1, pmapn} on every small shape and K."""
+    for wn in sorted({1, n}):
+        for maps in (False, True):
+            for pmap in ("alpha", "pmap1", "pmapn"):
+                check_mix(rt, nhwc, n, c, hw, k, wn, maps, pmap)
+
+
+@pytest.mark.parametrize("k", [1, 4, 5, 16])
+@pytest.mark.parametrize("nhwc,n,c,hw", BRANCHES, ids=ids(BRANCHES))
+def test_mix_launcher_thresholds(rt, nhwc, n, c, hw, k):
+    for wn, maps, pmap in ((1, False, "alpha"), (n, True, "pmapn"), (n, False, "pmap1"), (1, True, "alpha")):
+        check_mix(rt, nhwc, n, c, hw, k, wn, maps, pmap, seed=3)
+
+
+@pytest.mark.parametrize("k", [4, 8, 9])
+def test_mix_bucket_edges_on_the_product_shape(rt, k):
+    for maps in (False, True):
+        check_mix(rt, True, 2, 512, 9, k, 2, maps, "alpha", seed=4)
+        check_mix(rt, True, 2, 512, 9, k, 1, maps, "pmapn", seed=4)
+
+
+# each value of each axis at least once: weights_n 1 / n, scalars / maps, alpha / pmap1 / pmapn
+@pytest.mark.parametrize("wn,maps,pmap", [(1, False, "alpha"), (4, True, "pmap1"), (4, False, "pmapn")])
+def test_mix_grid_stride(rt, wn, maps, pmap):
+    """(4, 3, 700001) NCHW: 2100003 quads > 8192 x 256, every thread loops and the plane size is odd."""
+    check_mix(rt, False, 4, 3, 700001, 2, wn, maps, pmap)
+
+
+def test_mix_workgroup_cap(rt):
+    """1025 images of 33 pixels x 256 channels: two workgroups per image by the pixel count, capped to one by 2048 / n."""
+    check_mix(rt, True, 1025, 256, 33, 2, 1, False, "alpha")
+
+
+@pytest.mark.parametrize("nhwc,n,c,hw", [(True, 2, 512, 9), (True, 3, 12, 5), (False, 4, 3, 5), (False, 2, 64, 99)])
+def test_one_style_of_weight_one_is_the_single_style_blend(rt, nhwc, n, c, hw):
+    """K = 1, w = 1.0: 1 * b is exact, so the bytes are adain_blend_alpha's / adain_blend_pmap's - through the mix kernels, not the
+    old one (the launcher has no such route)."""
+    x, cm, cs, sm, ss, _, p = mix_inputs(nhwc, n, c, hw, 1, 1, False, n, seed=5)
+    X, CM, CS, SM, SS, P = dev(x), dev(cm), dev(cs), dev(sm)[:1], dev(ss)[:1], dev(p)
+    one = torch.ones(1, device=DEV)
+    bits = lambda t: host(t).view(np.int32)
+    for alpha in (0.7, 1.0, 0.0):
+        assert np.array_equal(bits(rt.blend_mix(X, nhwc, CM, CS, SM, SS, one, alpha=alpha)), bits(rt.blend_alpha(X, nhwc, CM, CS, SM, SS, alpha)))
+    assert np.array_equal(bits(rt.blend_mix(X, nhwc, CM, CS, SM, SS, one, pmap=P)), bits(rt.blend_pmap(X, nhwc, CM, CS, SM, SS, P)))
+    hw_shape = (1, hw)
+    ones_map = torch.ones((n, 1) + hw_shape, device=DEV)
+    assert np.array_equal(bits(rt.blend_mix(X, nhwc, CM, CS, SM, SS, ones_map, alpha=0.7)), bits(rt.blend_alpha(X, nhwc, CM, CS, SM, SS, 0.7)))
+
+
+@pytest.mark.parametrize("nhwc,n,c,hw", [(True, 2, 512, 9), (True, 2, 520, 7), (False, 4, 3, 5)])
+def test_a_zero_weight_leaves_the_other_styles_result(rt, nhwc, n, c, hw):
+    """w = (a, 0, b) over styles (0, 1, 2) equals w = (a, b) over styles (0, 2), and w = (a, b, 0) equals the K - 1 call w = (a, b)
+    over styles (0, 1): adding 0 * b_k (finite) changes no value."""
+    x, cm, cs, sm, ss, w, _ = mix_inputs(nhwc, n, c, hw, 3, 1, False, 0, seed=6)
+    X, CM, CS, SM, SS = dev(x), dev(cm), dev(cs), dev(sm), dev(ss)
+    a, b = float(w[0, 0, 0]), float(w[0, 2, 0])
+    W = lambda *v: torch.tensor(v, dtype=torch.float32, device=DEV)
+    mid = host(rt.blend_mix(X, nhwc, CM, CS, SM[:3], SS[:3], W(a, 0.0, b), alpha=0.7))
+    two = host(rt.blend_mix(X, nhwc, CM, CS, SM[[0, 2]].contiguous(), SS[[0, 2]].contiguous(), W(a, b), alpha=0.7))
+    assert np.array_equal(mid, two)
+    last = host(rt.blend_mix(X, nhwc, CM, CS, SM[:3], SS[:3], W(a, b, 0.0), alpha=0.7))
+    km1 = host(rt.blend_mix(X, nhwc, CM, CS, SM[:2], SS[:2], W(a, b), alpha=0.7))
+    assert np.array_equal(last, km1)
+    assert_equal_elements("zero last", last, M.mix(x, nhwc, cm, cs, sm[:3], ss[:3], np.array([[a, b, 0.0]], dtype=F32), alpha=0.7), nhwc, n, c, hw)
+
+
+FILL = 123.0
+
+
+@pytest.mark.parametrize("nhwc,n,c,hw,k,wn,whw,pn", [
+    (True, 2, 8, 5, 0, 1, 1, None), (True, 2, 8, 5, 17, 1, 1, None), (True, 4, 8, 5, 2, 2, 1, None), (True, 2, 8, 5, 2, 1, 4, None),
+    (True, 2, 6, 4, 2, 1, 1, None), (False, 3, 3, 5, 2, 1, 1, None), (True, 4, 8, 5, 2, 1, 1, 3), (False, 4, 3, 5, 2, 0, 1, None),
+], ids=lambda v: str(v))
+def test_mix_rejections_leave_the_output_alone(rt, nhwc, n, c, hw, k, wn, whw, pn):
+    L = rt.lib()
+    f = lambda *s: torch.ones(*s, device=DEV)
+    x, cm, cs, sm, ss, w, p = f(n * c * hw), f(n, c), f(n, c), f(17, c), f(17, c), f(n * 17 * hw), f(n, hw)
+    out = torch.full((n * c * hw,), FILL, device=DEV)
+    rc = L.adain_blend_mix(x.data_ptr(), int(nhwc), n, c, hw, cm.data_ptr(), cs.data_ptr(), sm.data_ptr(), ss.data_ptr(), k, w.data_ptr(), wn, whw,
+                           0.7, float(1 - 0.7), p.data_ptr() if pn is not None else None, pn or 1, out.data_ptr(), rt._stream())
+    assert rc == -1 and L.adain_last_error()
+    torch.cuda.synchronize()
+    assert (out == FILL).all()
