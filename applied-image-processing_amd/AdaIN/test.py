@@ -21,12 +21,14 @@ import time
 import weakref
 from collections import OrderedDict
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 from PIL import Image
 
 from .. import runtime as rt
+from ..engine import Style
 from . import net
 from .function import adaptive_instance_normalization, calc_mean_std, coral  # noqa: F401
 
@@ -427,9 +429,7 @@ def style_transfer_interpolated(vgg, decoder, content, styles, alpha=1.0, interp
         raise ValueError(f"style_transfer_interpolated: {len(style_list)} styles need as many interpolation_weights, got {interpolation_weights!r}")
     content_f = vgg(content)
     N, C = content_f.size()[:2]
-    s_stats = [calc_mean_std(vgg(s)) for s in style_list]
-    s_mean = torch.cat([m.view(1, C) for m, _ in s_stats]).contiguous()
-    s_std = torch.cat([sd.view(1, C) for _, sd in s_stats]).contiguous()
+    s_mean, s_std = Style.stack(Style(m.view(1, C), sd.view(1, C)) for m, sd in (calc_mean_std(vgg(s)) for s in style_list))
     c_mean, c_std = calc_mean_std(content_f)
     view, nhwc = _layout(content_f)
     weights = torch.tensor([float(w) for w in interpolation_weights], dtype=torch.float32, device=view.device)
@@ -539,59 +539,40 @@ def adain_inference(
     enc, dec = _singletons(device, vgg_str, decoder_str)
     target = out_dir / f"{file_name}{save_ext}"
     T = _stage_timer
+    call = SimpleNamespace(alpha=alpha, use_depth=use_depth, depth_map=depth_map, depth_offset=depth_offset, depth_prominence=depth_prominence,
+                           content_mask=content_mask, target=target)
     if isinstance(style_img, (list, tuple)) or style_interpolation_weights is not None:
-        _mix_call(content_img, style_img, style_interpolation_weights, enc, dec, device, depth_offset, depth_prominence, content_size, style_size, alpha,
-                  crop, target, preserve_color, content_mask, use_depth, depth_map)
+        _mix_call(content_img, style_img, style_interpolation_weights, enc, dec, device, content_size, style_size, crop, preserve_color, call)
         print(f"Image saved to {target}")
         return target
 
-    t0 = time.perf_counter()
-    pil_content = Image.open(content_img) if type(content_img) == str else content_img
     if _style_cache_on and (not preserve_color or _device_coral_on) and isinstance(enc, net.HipVGG) and isinstance(dec, net.HipDecoder):
         # one style, many calls (video/utils.py:341-350, train.py:101): statistics from the cache, the frame in one C-ABI call
-        pil_content.load()                                               # decode (a lazily opened file) - host work that stays
-        T("open + decode content (PIL)", t0)
-        t0 = time.perf_counter()
-        e0 = torch.cuda.Event(enable_timing=True) if T.on else None
-        frame = device_transform_u8(pil_content, content_size, crop, device, e0.record if T.on else None)     # upload + Resize [+ CenterCrop] on the device
-        if frame is None:
-            frame = test_transform_u8(content_size, crop)(pil_content)           # not RGB / padded crop: PIL on the host
-            T("resize content (PIL, host)", t0)
-        else:
-            T("upload + resize content (device; enqueue only)", t0)
-        if (isinstance(frame, np.ndarray) or isinstance(frame, torch.Tensor) and frame.dtype == torch.uint8) and _mask_fits(content_mask):
-            assert 0.0 <= alpha <= 1.0                                   # test.py:55 / :75
-            if use_depth:
-                assert 0.0 <= depth_offset <= 1.0                        # test.py:56
+        frame, e0 = _content_frame(content_img, content_size, crop, device, call)
+        if frame.dtype == torch.uint8 and _mask_fits(content_mask):
             t0 = time.perf_counter()
             if preserve_color:
-                if not isinstance(frame, torch.Tensor):
-                    frame = torch.from_numpy(frame if frame.flags.writeable else frame.copy()).unsqueeze(0).to(device)
                 stats = _coral_style_stats(style_img, frame, style_size, crop, enc, device)
                 T("CORAL + style statistics (device, per call)", t0)
             else:
                 stats = _style_stats(style_img, style_size, crop, enc, device, drop_alpha=use_depth)
                 T("style statistics (cached after the first call)", t0)
             if stats is not None:
-                _one_call(frame, stats, enc, dec, device, alpha, use_depth, depth_map, pil_content, depth_offset, depth_prominence, content_mask,
-                          target, e0 if (T.on and isinstance(frame, torch.Tensor)) else None)
+                _one_call(frame, stats, enc, dec, device, call, e0)
                 print(f"Image saved to {target}")
                 return target
-        if isinstance(frame, torch.Tensor) and frame.dtype == torch.uint8:
-            content = frame[0].cpu().permute(2, 0, 1).float().div(255)      # ToTensor of the resized frame (same bytes as PIL's)
-        else:
-            content = _to_tensor(Image.fromarray(frame)) if isinstance(frame, np.ndarray) else frame
+        content = frame[0].cpu().permute(2, 0, 1).float().div(255) if frame.dtype == torch.uint8 else frame      # ToTensor of the resized frame
     else:
-        content = test_transform(content_size, crop)(pil_content)
-    pil_style = Image.open(str(style_img)) if type(style_img) == str else style_img
+        call.pil_content = _open(content_img)
+        content = test_transform(content_size, crop)(call.pil_content)
     STYLE_ENCODES[0] += 1
-    style = test_transform(style_size, crop)(pil_style)
+    style = test_transform(style_size, crop)(_open(style_img))
     if preserve_color:                       # CORAL runs on the host tensors, as in the reference (test.py:201-202)
         style = coral(style, content)
     content, style = content.to(device).unsqueeze(0), style.to(device).unsqueeze(0)
 
     if use_depth:
-        proximity = depth_map if depth_map is not None else midas_depth_map_est(pil_content)
+        proximity = depth_map if depth_map is not None else midas_depth_map_est(call.pil_content)
         result = style_transfer(enc, dec, content, style, proximity, alpha, depth_offset, depth_prominence)
     else:
         result = style_transfer_simple(enc, dec, content, style, alpha)
@@ -638,53 +619,80 @@ def _mask_fits(content_mask):
     return dt in ("uint8", "bool", "float32")
 
 
+def _open(img):
+    return Image.open(str(img)) if type(img) == str or isinstance(img, Path) else img
+
+
+def _content_frame(content_img, content_size, crop, device, call):
+    """The content of the one-call path, opened and decoded (``call.pil_content``), after the range asserts of test.py:55-56 / :75 ->
+    (``test_transform_u8`` of it: uint8 [1,h,w,3] on the device, or a float tensor if not RGB; the stage timer's event before a device resize)."""
+    assert 0.0 <= call.alpha <= 1.0
+    if call.use_depth:
+        assert 0.0 <= call.depth_offset <= 1.0
+    T = _stage_timer
+    t0 = time.perf_counter()
+    pil_content = call.pil_content = _open(content_img)
+    pil_content.load()                                               # decode (a lazily opened file) - host work that stays
+    T("open + decode content (PIL)", t0)
+    t0 = time.perf_counter()
+    e0 = torch.cuda.Event(enable_timing=True) if T.on else None
+    frame = device_transform_u8(pil_content, content_size, crop, device, e0.record if T.on else None)     # upload + Resize [+ CenterCrop] on the device
+    if frame is None:
+        frame, e0 = test_transform_u8(content_size, crop)(pil_content), None      # not RGB / padded crop: PIL on the host
+        if isinstance(frame, np.ndarray):                                        # (np.asarray of a PIL image is read-only)
+            frame = torch.from_numpy(frame if frame.flags.writeable else frame.copy()).unsqueeze(0).to(device)
+        T("resize content (PIL, host)", t0)
+    else:
+        T("upload + resize content (device; enqueue only)", t0)
+    return frame, e0
+
+
+def _style_image(style_img, style_size, crop, device, drop_alpha=False):
+    """The transformed style on the device, as the encoder takes it: uint8 [1,h,w,3] for an RGB image (Resize [+ CenterCrop] there),
+    else ``test_transform``'s float [1,3,h,w] (``drop_alpha``: without an RGBA image's fourth plane); None for any other channel count."""
+    pil_style = _open(style_img)
+    u8 = device_transform_u8(pil_style, style_size, crop, device)
+    if u8 is not None:
+        return u8
+    style = test_transform(style_size, crop)(pil_style)
+    if style.shape[0] == 4 and drop_alpha:
+        style = style[:3]                                                 # test.py:60-61
+    return style.unsqueeze(0).to(device).contiguous() if style.shape[0] == 3 else None
+
+
 def _style_stats(style_img, style_size, crop, enc, device, drop_alpha):
-    """(mean, std), each [1,512], of the style image's relu4_1 features (test.py:63 + function.py:4-12 / :77), computed once per
-    style (``_style_key``).  None when the transformed style is not a 3-channel image the encoder can take (4 channels with the
-    alpha blend: the reference fails in its first convolution; the call-by-call path reports it)."""
+    """The ``Style`` (mean, std each [1,512]) of the style image's relu4_1 features (test.py:63 + function.py:4-12 / :77), computed
+    once per style (``_style_key``).  None when the transformed style is not a 3-channel image the encoder can take (4 channels with
+    the alpha blend: the reference fails in its first convolution; the call-by-call path reports it)."""
     def make():
-        pil_style = Image.open(str(style_img)) if type(style_img) == str or isinstance(style_img, Path) else style_img
-        u8 = device_transform_u8(pil_style, style_size, crop, device)
-        if u8 is not None:                                                # RGB: Resize on the device, ToTensor inside the first layer
-            STYLE_ENCODES[0] += 1
-            return rt.mean_std(rt.encode_u8(u8, enc.packed(device)), True)
-        style = test_transform(style_size, crop)(pil_style)
-        if style.shape[0] == 4 and drop_alpha:
-            style = style[:3]                                             # test.py:60-61
-        if style.shape[0] != 3:
+        style = _style_image(style_img, style_size, crop, device, drop_alpha)
+        if style is None:
             return None
         STYLE_ENCODES[0] += 1
-        f = rt.encode(style.unsqueeze(0).to(device).contiguous(), enc.packed(device))
-        return rt.mean_std(f, True)
+        return Style(*rt.mean_std((rt.encode_u8 if style.dtype == torch.uint8 else rt.encode)(style, enc.packed(device)), True))
 
     # an RGBA style gives other statistics on the depth path (alpha dropped) than on the alpha path (refused): part of the key
     return _cached_style(style_img, ("stats", bool(drop_alpha)), style_size, crop, enc, device, make)
 
 
 def _coral_style_stats(style_img, frame, style_size, crop, enc, device):
-    """(mean, std), each [1,512], of ``coral(style, content)``'s relu4_1 features (test.py:201-202, :77) for the resized frame uint8
-    [1,h,w,3] on the device.  The resized style's pixels are kept on the device per style (``_style_key``); CORAL, the encoder and
-    the statistics run per call, because the recoloured style depends on the frame.  None when the transformed style is not a
-    3-channel image (the call-by-call path reports it)."""
+    """The ``Style`` of ``coral(style, content)``'s relu4_1 features (test.py:201-202, :77) for the resized frame uint8 [1,h,w,3] on
+    the device.  The resized style's pixels are kept on the device per style (``_style_key``); CORAL, the encoder and the statistics
+    run per call, because the recoloured style depends on the frame.  None when the transformed style is not a 3-channel image (the
+    call-by-call path reports it)."""
     def make():
-        pil_style = Image.open(str(style_img)) if type(style_img) == str or isinstance(style_img, Path) else style_img
         STYLE_PIXEL_UPLOADS[0] += 1
-        u8 = device_transform_u8(pil_style, style_size, crop, device)
-        if u8 is not None:
-            return u8
-        style = test_transform(style_size, crop)(pil_style)
-        return style.unsqueeze(0).to(device).contiguous() if style.shape[0] == 3 else None
+        return _style_image(style_img, style_size, crop, device)
 
     pixels = _cached_style(style_img, "pixels", style_size, crop, enc, device, make)
     if pixels is None:
         return None
     STYLE_ENCODES[0] += 1
     recoloured, _record = rt.coral(pixels, frame)
-    return rt.mean_std(rt.encode(recoloured, enc.packed(device)), True)
+    return Style(*rt.mean_std(rt.encode(recoloured, enc.packed(device)), True))
 
 
-def _mix_call(content_img, style_imgs, weights, enc, dec, device, depth_offset, depth_prominence, content_size, style_size, alpha, crop, target,
-              preserve_color, content_mask, use_depth, depth_map):
+def _mix_call(content_img, style_imgs, weights, enc, dec, device, content_size, style_size, crop, preserve_color, call):
     """adain_inference with a list of styles: every style's statistics through the style cache, the frame in one C-ABI call
     (``adain_stylize_u8_mix``) with the weights as given."""
     if not isinstance(style_imgs, (list, tuple)) or weights is None or len(weights) != len(style_imgs) or not 1 <= len(style_imgs) <= rt.MIX_MAX_STYLES:
@@ -693,44 +701,31 @@ def _mix_call(content_img, style_imgs, weights, enc, dec, device, depth_offset, 
         raise ValueError("preserve_color with style_interpolation_weights is not supported (it would need coral of every style per frame)")
     if not (isinstance(enc, net.HipVGG) and isinstance(dec, net.HipDecoder)):
         raise rt.AdainHipError("style interpolation runs on the package's encoder and decoder")
-    if not _mask_fits(content_mask):
+    if not _mask_fits(call.content_mask):
         raise ValueError("content_mask must be [1|3,H,W] uint8, bool or float32")
-    assert 0.0 <= alpha <= 1.0
-    if use_depth:
-        assert 0.0 <= depth_offset <= 1.0
-    pil_content = Image.open(content_img) if type(content_img) == str else content_img
-    pil_content.load()
-    frame = device_transform_u8(pil_content, content_size, crop, device)
-    if frame is None:
-        frame = test_transform_u8(content_size, crop)(pil_content)
-    if not (isinstance(frame, torch.Tensor) and frame.dtype == torch.uint8 or isinstance(frame, np.ndarray) and frame.ndim == 3 and frame.shape[2] == 3):
+    frame, e0 = _content_frame(content_img, content_size, crop, device, call)
+    if frame.dtype != torch.uint8:
         raise ValueError("style interpolation needs an RGB content image")
-    stats = [_style_stats(s, style_size, crop, enc, device, drop_alpha=use_depth) for s in style_imgs]
+    stats = [_style_stats(s, style_size, crop, enc, device, drop_alpha=call.use_depth) for s in style_imgs]
     if any(st is None for st in stats):
         raise ValueError("style interpolation needs 3-channel style images")
-    mixed = (torch.cat([m.view(1, 512) for m, _ in stats]).contiguous(), torch.cat([sd.view(1, 512) for _, sd in stats]).contiguous())
     w = torch.tensor([float(v) for v in weights], dtype=torch.float32, device=device)
-    _one_call(frame, mixed, enc, dec, device, alpha, use_depth, depth_map, pil_content, depth_offset, depth_prominence, content_mask, target,
-              style_weights=w)
+    _one_call(frame, Style.stack(stats), enc, dec, device, call, e0, style_weights=w)
 
 
-def _one_call(frame, stats, enc, dec, device, alpha, use_depth, depth_map, pil_content, depth_offset, depth_prominence, content_mask, target,
-              e0=None, style_weights=None):
-    """A resized RGB frame (uint8: [1,h,w,3] on the device, or HWC on the host) -> the saved file: [upload,] ``adain_stylize_u8``,
-    download, PIL save.  ``e0``: an event recorded before the device-side resize (stage timer: the kernels' time includes it)."""
+def _one_call(x, style, enc, dec, device, call, e0=None, style_weights=None):
+    """A resized RGB frame (uint8 [1,h,w,3] on the device) -> the saved file: ``adain_stylize_u8``, download, PIL save.  ``call``: the
+    record of the call's options and its ``pil_content``.  ``e0``: an event recorded before the device-side resize (stage timer)."""
+    alpha, use_depth, depth_map, content_mask, target = call.alpha, call.use_depth, call.depth_map, call.content_mask, call.target
     T = _stage_timer
     depth = None
     if use_depth:
         t0 = time.perf_counter()
-        proximity = depth_map if depth_map is not None else midas_depth_map_est(pil_content)
+        proximity = depth_map if depth_map is not None else midas_depth_map_est(call.pil_content)
         if not isinstance(proximity, torch.Tensor):
             proximity = torch.as_tensor(np.asarray(proximity))
         T("depth provider", t0)
     t0 = time.perf_counter()
-    if isinstance(frame, torch.Tensor):
-        x = frame
-    else:
-        x = torch.from_numpy(frame if frame.flags.writeable else frame.copy()).unsqueeze(0).to(device)     # (np.asarray of a PIL image is read-only)
     if use_depth:
         depth = [proximity.to(device=device, dtype=torch.float32).contiguous()]
     mask = None
@@ -744,8 +739,8 @@ def _one_call(frame, stats, enc, dec, device, alpha, use_depth, depth_map, pil_c
         if e0 is None:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
-    u8 = rt.stylize_u8(x, enc.packed(device), dec.packed(device), stats[0], stats[1], alpha, depth, depth_offset, depth_prominence, mask,
-                       style_weights=style_weights)
+    u8 = rt.stylize_u8(x, enc.packed(device), dec.packed(device), style.mean, style.std, alpha, depth, call.depth_offset, call.depth_prominence,
+                       mask, style_weights=style_weights)
     if T.on:
         e1.record()
         T.events.append((e0, e1))

@@ -12,6 +12,31 @@ import torch
 from . import runtime as rt
 
 
+class Style:
+    """What a call is styled with: the channel statistics ``mean`` / ``std``, float32 [K,512] on the device (K > 1: the rows that a call's
+    ``style_weights`` mix), and ``pixels``: None, or the resized style's pixels (``set_style_image``).  Unpacks as ``mean, std = style``."""
+    __slots__ = ("mean", "std", "pixels")
+
+    def __init__(self, mean, std, pixels=None):
+        self.mean, self.std, self.pixels = mean, std, pixels
+
+    def __iter__(self):
+        return iter((self.mean, self.std))
+
+    k = property(lambda self: self.mean.shape[0])
+
+    @staticmethod
+    def check_count(k):
+        if not 1 <= k <= rt.MIX_MAX_STYLES:
+            raise rt.AdainHipError(f"set_styles: 1 .. {rt.MIX_MAX_STYLES} styles, got {k}")
+
+    @classmethod
+    def stack(cls, styles):                # the rows of single-row styles, in order, as one style to mix (no pixels)
+        styles = list(styles)
+        cls.check_count(len(styles))
+        return cls(torch.cat([s.mean for s in styles]).contiguous(), torch.cat([s.std for s in styles]).contiguous())
+
+
 class AdaINEngine:
     def __init__(self, vgg_state_dict, decoder_state_dict, device=None):
         if not torch.cuda.is_available():
@@ -19,8 +44,7 @@ class AdaINEngine:
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.enc = rt.pack_encoder(vgg_state_dict, self.device)
         self.dec = rt.pack_decoder(decoder_state_dict, self.device)
-        self.s_mean = self.s_std = None
-        self.style_px = None              # set_style_image: the style's pixels, for the colour-preserving path
+        self.style = None                 # the ``Style`` that calls are styled with: set_style / set_style_image / set_styles
 
     def synchronize(self):
         torch.cuda.synchronize(self.device)
@@ -42,76 +66,59 @@ class AdaINEngine:
         return a.elapsed_time(b) * 1e-3
 
     def style_stats(self):
-        """The current style's channel statistics (mean, std), each [1,512] on the GPU: what ``set_style`` computed."""
-        return self.s_mean, self.s_std
+        return self.style
 
     def use_style_stats(self, stats):
-        """Switches to statistics obtained earlier from ``style_stats`` (the job drivers move between a few styles through a
-        clip, video/utils.py:335-337: each style image is encoded once, its 2 x 512 statistics are kept by the job)."""
-        self.s_mean, self.s_std = stats
+        """Switches to a ``Style`` obtained earlier from ``style_stats`` or a plain (mean, std) pair (the job drivers keep one per style)."""
+        self.style = stats if isinstance(stats, Style) else Style(*stats)
         return self
 
     def set_style(self, style):
         """style [1,3,hs,ws] (or [1,4,...]: the alpha channel is dropped as in test.py:60-61)."""
         if style.shape[1] == 4:
             style = style[:, :3]
-        f = rt.encode(style.to(self.device, torch.float32).contiguous(), self.enc)
-        self.s_mean, self.s_std = rt.mean_std(f, True)
+        self.style = Style(*rt.mean_std(rt.encode(style.to(self.device, torch.float32).contiguous(), self.enc), True))
         return self
 
     def set_styles(self, styles):
         """A list of K style tensors (each as ``set_style`` takes it, sizes may differ) for style interpolation: every style is
         encoded once and the engine holds their statistics as [K,512] rows, mixed per frame by the ``style_weights`` of
-        ``stylize`` / ``stylize_depth`` / ``stylize_u8``.  ``style_stats`` / ``style_state`` and their ``use_`` twins carry the rows."""
+        ``stylize`` / ``stylize_depth`` / ``stylize_u8``."""
         styles = list(styles)
-        if not 1 <= len(styles) <= rt.MIX_MAX_STYLES:
-            raise rt.AdainHipError(f"set_styles: 1 .. {rt.MIX_MAX_STYLES} styles, got {len(styles)}")
-        rows = [self.set_style(s).style_stats() for s in styles]
-        self.s_mean, self.s_std = torch.cat([m for m, _ in rows]).contiguous(), torch.cat([sd for _, sd in rows]).contiguous()
-        self.style_px = None
+        Style.check_count(len(styles))
+        self.style = Style.stack([self.set_style(s).style for s in styles])
         return self
-
-    def _mix(self, style_weights, preserve_color):
-        """The device tensor of a call's ``style_weights`` (None: a single-style call, which needs a single style)."""
-        if style_weights is None:
-            if self.s_mean.shape[0] != 1:
-                raise rt.AdainHipError(f"the engine holds {self.s_mean.shape[0]} styles (set_styles): pass style_weights to mix them")
-            return None
-        if preserve_color:
-            raise rt.AdainHipError("preserve_color with style_weights is not supported: it would need coral(style_k, frame) of every "
-                                   "style for every frame")
-        return torch.as_tensor(style_weights, dtype=torch.float32).to(self.device).contiguous()
 
     def set_style_image(self, style):
         """``set_style`` that also keeps the (already resized) style's PIXELS on the device, for ``preserve_color=True``: there every
         frame is styled with its own ``coral(style, frame)`` (function.py:26-67), so the pixels are needed, not only the statistics.
         style: float [1,3,hs,ws] (or [1,4,...], alpha dropped) or uint8 [1,hs,ws,3]."""
         style = style.to(self.device)
-        if style.dtype == torch.uint8:
-            style = style.contiguous()
-            self.s_mean, self.s_std = rt.mean_std(rt.encode_u8(style, self.enc), True)
-        else:
-            style = style[:, :3].to(torch.float32).contiguous()
-            self.set_style(style)
-        self.style_px = style
+        style = style.contiguous() if style.dtype == torch.uint8 else style[:, :3].to(torch.float32).contiguous()
+        self.style = Style(*rt.mean_std(self._encode(style), True), style)
         return self
 
-    def style_state(self):
-        """Statistics and resident pixels of the current style, for ``use_style_state`` (the job drivers keep one per style)."""
-        return self.s_mean, self.s_std, self.style_px
-
-    def use_style_state(self, state):
-        self.s_mean, self.s_std, self.style_px = state
-        return self
-
-    def _coral_stats(self, content):
-        """Per-frame style statistics of the colour-preserving path, each [n,512]: coral(style, frame_i) for every frame of the
-        sub-batch in one call, the n recoloured styles through the encoder, their channel statistics (test.py:201-202 then :77).
-        Each frame's row depends on that frame alone."""
-        if self.style_px is None:
+    def _call_style(self, content, preserve_color, style_weights):
+        """THE place that decides what a call is styled with -> (mean, std, the keywords ``rt.stylize_u8`` takes with them): the engine's
+        one style ({}), its K styles mixed by ``style_weights`` (on the device), or - ``preserve_color`` - one recoloured style per frame
+        ({"style_n": n}): coral(style, frame_i) for every frame of the sub-batch ``content`` in one call, through the encoder, their channel
+        statistics (test.py:201-202 then :77; a frame's row depends on that frame alone).  Every refusal comes before any C-ABI call."""
+        style = self.style
+        if style is None:
+            raise rt.AdainHipError("set_style() first")
+        if style_weights is not None:
+            if preserve_color:
+                raise rt.AdainHipError("preserve_color with style_weights is not supported: it would need coral(style_k, frame) of every "
+                                       "style for every frame")
+            return style.mean, style.std, {"style_weights": torch.as_tensor(style_weights, dtype=torch.float32).to(self.device).contiguous()}
+        if style.k != 1:
+            raise rt.AdainHipError(f"the engine holds {style.k} styles (set_styles): pass style_weights to mix them")
+        if not preserve_color:
+            return style.mean, style.std, {}
+        if style.pixels is None:
             raise rt.AdainHipError("preserve_color needs the style's pixels: set_style_image() first")
-        styles, _record = rt.coral(self.style_px, content)
-        return rt.mean_std(rt.encode(styles, self.enc), True)
+        recoloured, _record = rt.coral(style.pixels, content)
+        return rt.mean_std(rt.encode(recoloured, self.enc), True) + ({"style_n": content.shape[0]},)
 
     def features(self, images):
         return self._encode(images.to(self.device))
@@ -135,17 +142,13 @@ class AdaINEngine:
         [K,hc,wc] or [n,K,hc,wc], used as given): every frame is styled with that mix of the K styles of ``set_styles``
         (style interpolation, ``rt.blend_mix``)."""
         assert 0.0 <= alpha <= 1.0
-        if self.s_mean is None:
-            raise rt.AdainHipError("set_style() first")
-        style_weights = self._mix(style_weights, preserve_color)
         if preserve_color:
-            content = content.to(self.device)
-            content = content.contiguous() if content.dtype == torch.uint8 else content.to(torch.float32).contiguous()
-        s_mean, s_std = self._coral_stats(content) if preserve_color else (self.s_mean, self.s_std)
+            content = content.to(self.device) if content.dtype == torch.uint8 else content.to(self.device, torch.float32)
+        s_mean, s_std, how = self._call_style(content, preserve_color, style_weights)
         f = self._encode(content)
         c_mean, c_std = rt.mean_std(f, True)
-        if style_weights is not None:
-            g = rt.blend_mix(f, True, c_mean, c_std, s_mean, s_std, style_weights, alpha=alpha if pmap is None else None, pmap=pmap)
+        if "style_weights" in how:
+            g = rt.blend_mix(f, True, c_mean, c_std, s_mean, s_std, how["style_weights"], alpha=alpha if pmap is None else None, pmap=pmap)
         elif pmap is not None:
             g = rt.blend_pmap(f, True, c_mean, c_std, s_mean, s_std, pmap)
         else:
@@ -160,9 +163,6 @@ class AdaINEngine:
         ``preserve_color``: coral -> encoder -> statistics of the n recoloured styles first (three more calls), then the same one
         call with one style per frame (``adain_stylize_u8_ex``); a frame's bytes do not depend on the sub-batch it is in.
         ``style_weights``: the mix of ``set_styles``' K styles per frame, as for ``stylize`` (``adain_stylize_u8_mix``, still one call)."""
-        if self.s_mean is None:
-            raise rt.AdainHipError("set_style() first")
-        style_weights = self._mix(style_weights, preserve_color)
         assert 0.0 <= alpha <= 1.0 and 0.0 <= offset <= 1.0
         if depth_maps is not None:
             depth_maps = [d.to(self.device, torch.float32) for d in depth_maps]
@@ -170,14 +170,9 @@ class AdaINEngine:
             masks = masks.to(self.device)
             if masks.dtype not in (torch.uint8, torch.bool, torch.float32):
                 masks = masks.float()
-        frames_u8 = frames_u8.to(self.device)
-        if preserve_color:
-            frames_u8 = rt.device_tensor(frames_u8, "frames", torch.uint8)
-            s_mean, s_std = self._coral_stats(frames_u8)
-            return rt.stylize_u8(frames_u8, self.enc, self.dec, s_mean, s_std, alpha, depth_maps, offset, prominence, masks, out,
-                                 style_n=frames_u8.shape[0])
-        return rt.stylize_u8(frames_u8, self.enc, self.dec, self.s_mean, self.s_std, alpha, depth_maps, offset, prominence, masks, out,
-                             style_weights=style_weights)
+        frames_u8 = rt.device_tensor(frames_u8.to(self.device), "frames", torch.uint8)
+        s_mean, s_std, how = self._call_style(frames_u8, preserve_color, style_weights)
+        return rt.stylize_u8(frames_u8, self.enc, self.dec, s_mean, s_std, alpha, depth_maps, offset, prominence, masks, out, **how)
 
     def stylize_depth(self, content, depth_maps, offset=0.15, prominence=20, preserve_color=False, style_weights=None):
         """Depth-aware path for a batch: ``depth_maps`` is a list of [h0,w0] GPU tensors, one per frame."""
@@ -314,7 +309,7 @@ class GraphedStylize:
 
     def __init__(self, engine, n, h, w, alpha=0.5, to_u8=False):
         self.engine = engine
-        self._keep = (engine.s_mean, engine.s_std, engine.enc, engine.dec)
+        self._keep = (engine.style, engine.enc, engine.dec)
         self.static_in = torch.zeros((n, 3, h, w), dtype=torch.float32, device=engine.device)
         side = torch.cuda.Stream(engine.device)
         side.wait_stream(torch.cuda.current_stream(engine.device))

@@ -601,25 +601,44 @@ def _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence, preserv
     """One sub-batch of the feeder on the engine -> the finished uint8 frames [k,H,W,3].  ``style_weights``: the sub-batch's rows of
     the job's style-mix weights, on the device."""
     content, dev = batch.content, engine.device
-    coral = {"preserve_color": True} if preserve_color else {}      # only named when asked for: engines without the keyword keep working
+    how = {"preserve_color": True} if preserve_color else {}        # only named when asked for: engines without the keyword keep working
     if style_weights is not None:
-        coral["style_weights"] = style_weights
+        how["style_weights"] = style_weights
     one_call = getattr(engine, "stylize_u8", None)
     if (one_call is not None and content.dtype == torch.uint8 and content.dim() == 4 and content.shape[-1] == 3
             and not isinstance(batch.mask, list)):
         # decoded RGB frames with (at most) one mask tensor for the sub-batch: the whole chain in one C-ABI call
         return one_call(content, alpha=alpha, depth_maps=batch.depth, offset=depth_offset, prominence=depth_prominence, masks=batch.mask,
-                        **coral)
+                        **how)
     if batch.depth is not None:
-        out = engine.stylize_depth(content, [d.to(dev, torch.float32) for d in batch.depth], depth_offset, depth_prominence, **coral)
+        out = engine.stylize_depth(content, [d.to(dev, torch.float32) for d in batch.depth], depth_offset, depth_prominence, **how)
     else:
-        out = engine.stylize(content, alpha, **coral)
+        out = engine.stylize(content, alpha, **how)
     if isinstance(batch.mask, list):           # masks of different sizes inside one sub-batch: composite frame by frame
         out = torch.cat([engine.composite(content[k:k + 1], out[k:k + 1], m.to(dev).float().unsqueeze(0))
                          for k, m in enumerate(batch.mask)])
     elif batch.mask is not None:
         out = engine.composite(content, out, batch.mask.to(dev).float())
     return engine.to_u8(out)
+
+
+class _StyleSwitch:
+    """``ready(s)`` makes the engine ready for a frame whose style index is ``s``, with one lookup ``key -> maker``: ``s`` -> ``set_style``,
+    ``("pixels", s)`` -> ``set_style_image`` (``preserve_color``), ``"mix"`` -> ``set_styles`` of the whole list (``mixing``).  A style is
+    made once and kept in ``cache`` (the caller's ``style_cache``, or the job's own) as whatever ``engine.style_stats()`` returns."""
+    def __init__(self, engine, style_list, cache, preserve_color=False, mixing=False):
+        self.engine, self.cache, self.cur = engine, cache if cache is not None else {}, None
+        self.key, self.make = ((lambda s: "mix", lambda s: engine.set_styles(style_list)) if mixing else
+                               (lambda s: ("pixels", s), lambda s: engine.set_style_image(style_list[s])) if preserve_color else
+                               (lambda s: s, lambda s: engine.set_style(style_list[s])))
+
+    def ready(self, s):
+        key = self.key(s)
+        if key != self.cur:
+            self.cur = key
+            if key not in self.cache:
+                self.cache[key] = self.make(s).style_stats()
+            self.engine.use_style_stats(self.cache[key])
 
 
 def _cat_blocks(blocks, geom, device):
@@ -826,28 +845,13 @@ def stylize_frames_sharded(engine, frames, styles, *, style_of=None, alpha=0.5, 
     queued = []
     err = None
     try:
-        cur_style = None
-        stats = style_cache if style_cache is not None else {}
-        mix = None
-        if style_weights is not None and hi > lo:
-            if "mix" not in stats:
-                stats["mix"] = engine.set_styles(style_list).style_stats()
-            engine.use_style_stats(stats["mix"])
-            mix = torch.from_numpy(style_weights).to(dev)          # the whole clip's rows, resident for the call
+        switch = _StyleSwitch(engine, style_list, style_cache, preserve_color, mixing=style_weights is not None)
+        mix = torch.from_numpy(style_weights).to(dev) if style_weights is not None and hi > lo else None      # the clip's rows, resident for the call
         for batch in feeder:
             if on_gpu and len(queued) >= MAX_QUEUED_BATCHES:
                 sleep_wait(queued.pop(0))
             i, j = batch.i, batch.j
-            if mix is None and style_of[i] != cur_style:
-                cur_style = style_of[i]
-                if preserve_color:
-                    if ("pixels", cur_style) not in stats:
-                        stats["pixels", cur_style] = engine.set_style_image(style_list[cur_style]).style_state()
-                    engine.use_style_state(stats["pixels", cur_style])
-                else:
-                    if cur_style not in stats:
-                        stats[cur_style] = engine.set_style(style_list[cur_style]).style_stats()
-                    engine.use_style_stats(stats[cur_style])
+            switch.ready(style_of[i])
             u8 = _stylize_batch(engine, batch, alpha, depth_offset, depth_prominence, preserve_color, None if mix is None else mix[i:j])
             feeder.release(batch)
             if on_gpu:

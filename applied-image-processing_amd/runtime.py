@@ -318,11 +318,17 @@ def _event_array(events):
     return ctypes.cast(arr, _PP), arr
 
 
+def _image_dims(x, refuse):
+    """(n, h, w) of an image batch, uint8 NHWC [n,h,w,3] or float NCHW [n,3,h,w]; AdainHipError("<refuse>, got <shape>") for any other."""
+    u8 = x.dtype == torch.uint8
+    if x.dim() != 4 or x.shape[3 if u8 else 1] != 3:
+        raise AdainHipError(f"{refuse}, got {tuple(x.shape)}")
+    return (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
+
+
 def _encode(name, x, u8, packed, events):
     x = device_tensor(x, "frames" if u8 else "image", torch.uint8 if u8 else torch.float32)
-    if x.dim() != 4 or x.shape[3 if u8 else 1] != 3:
-        raise AdainHipError(f"{name}: expected {'uint8 [n,h,w,3]' if u8 else '[n,3,h,w]'}, got {tuple(x.shape)}")
-    n, h, w = x.shape[:3] if u8 else (x.shape[0], x.shape[2], x.shape[3])
+    n, h, w = _image_dims(x, f"{name}: expected {'uint8 [n,h,w,3]' if u8 else '[n,3,h,w]'}")
     hc, wc = encoded_size(h, w)
     feat = torch.empty((n, hc, wc, 512), dtype=torch.float32, device=x.device)
     ev, _keep = _event_array(events)
@@ -347,9 +353,7 @@ def encode_relu1_1(image, packed):
     [n,3,h,w] or decoded uint8 frames [n,h,w,3] -> relu1_1 NHWC [n,h,w,64]."""
     u8 = isinstance(image, torch.Tensor) and image.dtype == torch.uint8
     x = device_tensor(image, "image", torch.uint8 if u8 else torch.float32)
-    if x.dim() != 4 or (x.shape[3] if u8 else x.shape[1]) != 3:
-        raise AdainHipError(f"encode_relu1_1: expected float [n,3,h,w] or uint8 [n,h,w,3], got {tuple(x.shape)}")
-    n, h, w = (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
+    n, h, w = _image_dims(x, "encode_relu1_1: expected float [n,3,h,w] or uint8 [n,h,w,3]")
     out = torch.empty((n, h, w, 64), dtype=torch.float32, device=x.device)
     call("adain_encode_relu1_1", x.device, x.data_ptr(), 1 if u8 else 0, out.data_ptr(), packed.data_ptr(), n, h, w)
     return out
@@ -425,14 +429,20 @@ def blend_alpha(x, nhwc, c_mean, c_std, s_mean, s_std, alpha):
     return out
 
 
+def _pmap(pmap, hw, what):
+    """(the strength maps P [pn,hc,wc] contiguous on the device, pn) for feature maps of ``hw`` pixels."""
+    pmap = device_tensor(pmap, "pmap")
+    pn = pmap.numel() // hw
+    if pn * hw != pmap.numel():
+        raise AdainHipError(f"{what}: strength map size does not match the feature map")
+    return pmap, pn
+
+
 def blend_pmap(x, nhwc, c_mean, c_std, s_mean, s_std, pmap):
     """AdaIN(x) * (1 - P) + x * P with P [pn, hc, wc] (pn in {1, n})."""
     x = device_tensor(x, "content_feat")
-    pmap = device_tensor(pmap, "pmap")
     n, c, hw = _feat_dims(x, nhwc)
-    pn = pmap.numel() // hw
-    if pn * hw != pmap.numel():
-        raise AdainHipError("blend_pmap: strength map size does not match the feature map")
+    pmap, pn = _pmap(pmap, hw, "blend_pmap")
     out = torch.empty_like(x)
     call("adain_blend_pmap", x.device, x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(), s_mean.data_ptr(),
          s_std.data_ptr(), s_mean.shape[0], pmap.data_ptr(), pn, out.data_ptr())
@@ -474,10 +484,7 @@ def blend_mix(x, nhwc, c_mean, c_std, s_mean, s_std, weights, alpha=None, pmap=N
     weights, wn, whw = mix_weights(weights, n, k, hc, wc, x.device, "blend_mix")
     p_ptr, pn = None, 1
     if pmap is not None:
-        pmap = device_tensor(pmap, "pmap")
-        pn = pmap.numel() // hw
-        if pn * hw != pmap.numel():
-            raise AdainHipError("blend_mix: strength map size does not match the feature map")
+        pmap, pn = _pmap(pmap, hw, "blend_mix")
         p_ptr = pmap.data_ptr()
     a = 0.0 if alpha is None else float(alpha)
     out = torch.empty_like(x)
@@ -548,6 +555,27 @@ def quantize_u8(img, out=None):
     return out
 
 
+def _stylize_u8_styles(x, s_mean, s_std, style_n, style_weights):
+    """(the entry point of a ``stylize_u8`` call of the frames ``x``, what it takes between ``s_std`` and ``alpha``): adain_stylize_u8 (),
+    _ex (style_n,) or _mix (K, weights, weights_n, weights_hw) - with the statistics checked for the rows that form takes."""
+    n, h, w, _ = x.shape
+    mixing = style_weights is not None
+    if mixing and style_n is not None:
+        raise AdainHipError("stylize_u8: style_weights mixes one set of styles for the batch; style_n does not apply")
+    rows = s_mean.numel() // 512 if mixing else 1 if style_n is None else int(style_n)
+    if mixing and not 1 <= rows <= MIX_MAX_STYLES:
+        raise AdainHipError(f"stylize_u8: a style mix needs statistics [K,512] each, 1 <= K <= {MIX_MAX_STYLES}, got {tuple(s_mean.shape)}")
+    if not mixing and rows not in (1, n):
+        raise AdainHipError(f"stylize_u8: style_n must be 1 or {n}, got {rows}")
+    if s_mean.numel() != rows * 512 or s_std.numel() != rows * 512 or s_mean.device != x.device or s_std.device != x.device:
+        raise AdainHipError(f"stylize_u8: the style statistics must be [{rows},512] each on the frames' device, got {tuple(s_mean.shape)}, "
+                            f"{tuple(s_std.shape)}")
+    if mixing:
+        weights, wn, whw = mix_weights(style_weights, n, rows, *encoded_size(h, w), x.device, "stylize_u8")
+        return "adain_stylize_u8_mix", (rows, weights.data_ptr(), wn, whw)
+    return ("adain_stylize_u8", ()) if style_n is None else ("adain_stylize_u8_ex", (rows,))
+
+
 def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, depth_maps=None, depth_offset=0.15, depth_prominence=20,
                mask=None, out=None, style_n=None, style_weights=None):
     """One sub-batch of decoded frames through the whole path in ONE call of the C ABI (``adain_stylize_u8``: ToTensor + encoder,
@@ -565,23 +593,8 @@ def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, dept
     dev = x.device
     s_mean, s_std = device_tensor(s_mean, "s_mean"), device_tensor(s_std, "s_std")
     if style_weights is not None:
-        if style_n is not None:
-            raise AdainHipError("stylize_u8: style_weights mixes one set of styles for the batch; style_n does not apply")
-        k = s_mean.numel() // 512
-        if not 1 <= k <= MIX_MAX_STYLES or s_mean.numel() != k * 512 or s_std.numel() != k * 512 or s_mean.device != dev or s_std.device != dev:
-            raise AdainHipError(f"stylize_u8: a style mix needs statistics [K,512] each on the frames' device, 1 <= K <= {MIX_MAX_STYLES}, got "
-                                f"{tuple(s_mean.shape)}, {tuple(s_std.shape)}")
-        style_weights, wn, whw = mix_weights(style_weights, n, k, *encoded_size(h, w), dev, "stylize_u8")
-    elif style_n is None:
-        if s_mean.numel() != 512 or s_std.numel() != 512:
-            raise AdainHipError("stylize_u8: the style statistics must be [1,512] each (one style per call)")
-    else:
-        style_n = int(style_n)
-        if style_n not in (1, n) or s_mean.numel() != style_n * 512 or s_std.numel() != style_n * 512:
-            raise AdainHipError(f"stylize_u8: style_n must be 1 or {n} with statistics [style_n,512] each, got style_n {style_n} and "
-                                f"{tuple(s_mean.shape)}, {tuple(s_std.shape)}")
-        if s_mean.device != dev or s_std.device != dev:
-            raise AdainHipError("stylize_u8: the style statistics must be on the frames' device")
+        style_weights = device_tensor(style_weights, "stylize_u8: style weights")      # held here until the launch
+    name, styles = _stylize_u8_styles(x, s_mean, s_std, style_n, style_weights)
     mn = mc = mh = mw = 0
     m_float, m_ptr = 0, None
     if mask is not None:
@@ -609,10 +622,6 @@ def stylize_u8(frames_u8, enc_packed, dec_packed, s_mean, s_std, alpha=0.5, dept
         out = torch.empty(shape, dtype=torch.uint8, device=dev)
     else:
         check_buffer(out, "stylize_u8: out", torch.uint8, dev, shape=shape)
-    if style_weights is not None:
-        name, styles = "adain_stylize_u8_mix", (k, style_weights.data_ptr(), wn, whw)
-    else:
-        name, styles = ("adain_stylize_u8", ()) if style_n is None else ("adain_stylize_u8_ex", (style_n,))
     with scratch(dev, "stylize", f"{name}_workspace_bytes", n, h, w, int(depth_maps is not None), mn, mc, mh, mw, m_float) as ws:
         _launch(name, x.data_ptr(), n, h, w, enc_packed.data_ptr(), dec_packed.data_ptr(), s_mean.data_ptr(), s_std.data_ptr(), *styles,
                 float(alpha), float(1 - alpha), dp, dh, dw, float(depth_offset), float(depth_prominence), m_ptr, m_float, mn, mc, mh, mw,
@@ -738,11 +747,7 @@ def _coral_side(t, name):
     """(contiguous tensor, is_u8, k, h, w) of one side of ``coral``: uint8 [k,h,w,3] or float32 [k,3,h,w] on a GPU."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.float32) or t.dim() != 4:
         raise AdainHipError(f"coral: {name} must be a GPU tensor, uint8 [k,h,w,3] or float32 [k,3,h,w]")
-    u8 = t.dtype == torch.uint8
-    if t.shape[3 if u8 else 1] != 3:
-        raise AdainHipError(f"coral: {name} must be uint8 [k,h,w,3] or float32 [k,3,h,w], got {tuple(t.shape)}")
-    k, h, w = (t.shape[0], t.shape[1], t.shape[2]) if u8 else (t.shape[0], t.shape[2], t.shape[3])
-    return t.contiguous(), int(u8), k, h, w
+    return (t.contiguous(), int(t.dtype == torch.uint8)) + _image_dims(t, f"coral: {name} must be uint8 [k,h,w,3] or float32 [k,3,h,w]")
 
 
 def coral(style, content, out=None):

@@ -220,7 +220,7 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
         depth_prominence=prominence,
         post=(lambda u8: engine.resize_area_u8(post(u8) if post else u8, target_resolution)) if target_resolution is not None else post,
         out_hw=(int(target_resolution[1]), int(target_resolution[0])) if target_resolution is not None else None,
-        group=group, **({"preserve_color": True} if preserve_color else {}))
+        group=group, preserve_color=preserve_color)
     err = None
     if rank == 0:
         # the frame-to-frame recurrence (video/utils.py:355-368) on the gathered frames; every frame is written by a worker

@@ -109,7 +109,7 @@ def test_engine_preserve_color_equals_the_staged_calls_whatever_the_sub_batch(rt
     plain = engine.stylize_u8(frames, alpha=0.5)
     got = engine.stylize_u8(frames, alpha=0.5, preserve_color=True)
     assert got.shape == (3, H, W, 3) and not torch.equal(got, plain)
-    assert torch.equal(got, staged(rt, engine, engine.style_px, frames, 0.5))
+    assert torch.equal(got, staged(rt, engine, engine.style.pixels, frames, 0.5))
     for size in (1, 2):
         parts = torch.cat([engine.stylize_u8(frames[i:i + size].contiguous(), alpha=0.5, preserve_color=True) for i in range(0, 3, size)])
         assert torch.equal(parts, got), size
@@ -156,7 +156,7 @@ def test_job_driver_passes_preserve_color_down(rt, engine, frames, style_u8):
     style_of = [0, 0, 0, 1, 1]
     cache = {}
     out, info = jobs.stylize_frames_sharded(engine, clip, styles, style_of=style_of, alpha=0.5, sub_batch=2, preserve_color=True, style_cache=cache)
-    assert sorted(cache, key=str) == [("pixels", 0), ("pixels", 1)] and all(len(v) == 3 and v[2] is not None for v in cache.values())
+    assert sorted(cache, key=str) == [("pixels", 0), ("pixels", 1)] and all(v.pixels is not None for v in cache.values())
     for k in range(5):
         engine.set_style_image(styles[style_of[k]].cuda())
         assert torch.equal(out[k:k + 1], engine.stylize_u8(T(clip[k])[None].cuda(), alpha=0.5, preserve_color=True)), k

@@ -101,11 +101,11 @@ def test_one_hot_rows_are_the_single_style_bytes(rt, engine, styles):
     one_hot = torch.eye(3, device="cuda")
     engine.set_styles(styles)
     mixed = engine.stylize_u8(frames, alpha=0.5, style_weights=one_hot)
-    state = engine.style_state()
+    state = engine.style_stats()
     for i in range(3):
         engine.set_style(styles[i].cuda())
         assert torch.equal(engine.stylize_u8(frames[i:i + 1].contiguous(), alpha=0.5), mixed[i:i + 1]), i
-    engine.use_style_state(state)
+    engine.use_style_stats(state)
     assert torch.equal(engine.stylize_u8(frames, alpha=0.5, style_weights=one_hot), mixed)
 
 
@@ -174,7 +174,7 @@ def test_job_driver_slices_the_rows(rt, engine, styles):
     w = jobs.style_crossfade(6, 2, 2)
     cache = {}
     out, info = jobs.stylize_frames_sharded(engine, clip, two, alpha=0.5, sub_batch=4, style_weights=w, style_cache=cache)
-    assert "mix" in cache and tuple(cache["mix"][0].shape) == (2, 512)
+    assert "mix" in cache and tuple(cache["mix"].mean.shape) == (2, 512)
     engine.set_styles(two)
     for k in range(6):
         assert torch.equal(out[k:k + 1], engine.stylize_u8(T(clip[k])[None].cuda(), alpha=0.5, style_weights=T(w[k]))), k

@@ -166,9 +166,9 @@ def test_batches_of_large_frames_two_phase_schedule_equals_frame_by_frame(rt, en
 def test_bad_arguments_raise(rt, engine):
     x = u8frames(790, 1, 32, 32).cuda()
     with pytest.raises(rt.AdainHipError):
-        rt.stylize_u8(x.cpu(), engine.enc, engine.dec, engine.s_mean, engine.s_std)      # no CPU fallback
+        rt.stylize_u8(x.cpu(), engine.enc, engine.dec, engine.style.mean, engine.style.std)      # no CPU fallback
     with pytest.raises(rt.AdainHipError):
-        rt.stylize_u8(x, engine.enc, engine.dec, engine.s_mean, engine.s_std, depth_maps=[])      # one map per frame
+        rt.stylize_u8(x, engine.enc, engine.dec, engine.style.mean, engine.style.std, depth_maps=[])      # one map per frame
     with pytest.raises(rt.AdainHipError):
         engine.stylize_u8(x, masks=torch.zeros(1, 2, 32, 32, device="cuda"))  # mask channels 1 or 3
     with pytest.raises(rt.AdainHipError):
