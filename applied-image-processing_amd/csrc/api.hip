@@ -542,6 +542,21 @@ int adain_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int qua
     return rc == -1 ? ADAIN_EINVAL : rc;
 }
 
+int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
+    return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, size_t workspace_bytes,
+                            adain_stream_t stream) {
+    if (!src || !dst || !workspace) { set_error("jpeg_roundtrip_u8: null pointer"); return ADAIN_EINVAL; }
+    size_t need_ws = 0;
+    if (jpeg_roundtrip_bytes(n, h, w, c, &need_ws)) return ADAIN_EINVAL;
+    if (workspace_bytes < need_ws) { set_error("jpeg_roundtrip_u8: workspace too small (%zu < %zu bytes)", workspace_bytes, need_ws); return ADAIN_EINVAL; }
+    const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst, bytes = (uintptr_t)n * h * w * c;
+    if (a < b + bytes && b < a + bytes) { set_error("jpeg_roundtrip_u8: dst overlaps src"); return ADAIN_EINVAL; }
+    const int rc = launch_jpeg_roundtrip_u8(src, n, h, w, c, quality, dst, workspace, (hipStream_t)stream);
+    return rc == -1 ? ADAIN_EINVAL : rc;
+}
+
 int adain_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, adain_stream_t stream) {
     if (!in || !out) { set_error("nhwc_to_nchw: null pointer"); return ADAIN_EINVAL; }
     return launch_nhwc_to_nchw(in, out, n, c, hw, (hipStream_t)stream);

@@ -166,6 +166,9 @@ int launch_tvl1_flow(const float* const* prev, const float* const* next, int npa
 int jpeg_encode_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes);
 int launch_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
                           hipStream_t s);
+// the pixels Pillow decodes from that file, without the file (the rules: top of jpeg.hip, tests/jpeg_decode_ref.py)
+int jpeg_roundtrip_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
+int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, hipStream_t s);
 
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);

@@ -34,6 +34,39 @@
 //              different lanes are disjoint, so atomicOr on 32-bit words is order-independent
 //   ffcount / scan / scatter   0xFF bytes per 1024-byte chunk, their scan, and the copy behind the header with a 0x00 after each 0xFF;
 //              the scatter also writes the header, FFD9 and lengths[i]
+//
+// The round trip (adain_jpeg_roundtrip_u8): the pixels Pillow decodes from that file, byte for byte, without the file.  Entropy coding is
+// lossless, so they are a function of the quantised coefficients the transform stage leaves in the workspace; what follows it is the
+// back half of libjpeg's decoder.  tests/jpeg_decode_ref.py restates it in NumPy, tests/test_jpeg_roundtrip_host.py holds that to Pillow.
+//
+// Its rules
+//   dequantise  coef * q, the q of `tables` above, natural order.
+//   IDCT        jidctint's jpeg_idct_islow: CONST_BITS 13, PASS1_BITS 2, COLUMNS then rows (the mirror of the encoder).  Per pass on d0..d7:
+//               z1 = (d2 + d6) * 4433, tmp2 = z1 - d6 * 15137, tmp3 = z1 + d2 * 6270; tmp0 = (d0 + d4) << 13, tmp1 = (d0 - d4) << 13;
+//               tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2; odd part from t0 = d7, t1 = d5, t2 = d3,
+//               t3 = d1: z1 = t0 + t3, z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3, z5 = (z3 + z4) * 9633; t0 *= 2446, t1 *= 16819, t2 *= 25172,
+//               t3 *= 12299; z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5; t0 += z1 + z3, t1 += z2 + z4,
+//               t2 += z2 + z3, t3 += z1 + z4.  Outputs 0..7: tmp10 + t3, tmp11 + t2, tmp12 + t1, tmp13 + t0, tmp13 - t0, tmp12 - t1,
+//               tmp11 - t2, tmp10 - t3, each descaled as (x + (1 << (n - 1))) >> n with n = 11 in the column pass and 18 in the row pass.
+//               The sample is range_limit[x & 0x3FF], libjpeg's table centred on 128: x + 128 clamped to 0..255 for x in -512..511,
+//               wrapping beyond as the 1024-entry table does.
+//   luma        the padded block grid cropped to h x w.  Greyscale: that plane is the output.
+//   chroma      the planes are cropped to ch = ceil(h/2) rows and cw = ceil(w/2) columns BEFORE upsampling: context beyond the first and
+//               last real row is that row replicated, the encoder's block padding is not used.  cw > 2: h2v2_fancy_upsample - for output
+//               row 2r + v, s[c] = 3 C[r][c] + C[r - 1 if v == 0 else r + 1][c] (row clamped to 0..ch-1), out[2c] = (3 s[c] + s[c-1] + 8)
+//               >> 4, out[2c+1] = (3 s[c] + s[c+1] + 7) >> 4, and at the ends out[0] = (4 s[0] + 8) >> 4, out[2cw-1] = (4 s[cw-1] + 7) >> 4
+//               (the column clamped to 0..cw-1 says the same).  cw <= 2 (w <= 4): libjpeg leaves the fancy filter out and every chroma
+//               sample is replicated 2 x 2.
+//   colour      with cb, cr minus 128: R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+//               B = Y + ((116130 cb + 32768) >> 16); arithmetic shifts; each channel clamped to 0..255.
+//
+// Its stages (3 launches per call, every one over all n frames)
+//   transform  the encoder's, unchanged
+//   idct       8 lanes per block: the zigzag int16 coefficients are dequantised into LDS in natural order, a lane per column, then a lane per
+//              row, and each lane stores its 8 samples as one 8-byte word into padded uint8 Y / Cb / Cr planes in the workspace
+//   merge      one workgroup per 512 pixels of an output row, a lane per chroma column (two pixels): upsampling and colour conversion into an
+//              LDS image of the row segment laid out at the destination's byte phase, which leaves as aligned dwords with byte stores at
+//              its two ends only - any destination address and any 3 w row stride
 #include "common.h"
 
 namespace adain {
@@ -555,6 +588,180 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(const uint32_t* __res
     }
 }
 
+// ---- the round trip: coefficients -> pixels ---------------------------------------------------------------------------------------------
+constexpr int IDCT_PER_WG = 32;         // blocks per workgroup of the IDCT, 8 lanes each
+constexpr int MERGE_PX = 512;           // pixels of one output row per workgroup of the merge, 2 per lane
+
+// Where the IDCT puts a frame's samples: uint8 planes of whole blocks, 64 bytes per block of the scan, Y [yh][yw] first, then (RGB)
+// Cb and Cr [8 mh][cw].  Every plane starts at a multiple of 64 bytes and every row stride is a multiple of 8.
+struct Planes {
+    int c, mw, bw, yw, cw;
+    size_t nblk, o_cb, o_cr, stride;
+};
+
+struct RoundtripPlan {
+    Planes g;
+    int mh, bh;
+    size_t o_coef, o_planes, total;     // workspace offsets (bytes) of the n-frame arrays
+};
+
+RoundtripPlan make_roundtrip_plan(int n, int h, int w, int c) {
+    RoundtripPlan p{};
+    Planes& g = p.g;
+    g.c = c;
+    g.bw = (w + 7) / 8, p.bh = (h + 7) / 8;
+    g.mw = (w + 15) / 16, p.mh = (h + 15) / 16;
+    g.nblk = c == 3 ? (size_t)g.mw * p.mh * 6 : (size_t)g.bw * p.bh;
+    g.yw = c == 3 ? 16 * g.mw : 8 * g.bw;
+    g.cw = c == 3 ? 8 * g.mw : 0;
+    g.o_cb = c == 3 ? (size_t)g.mw * p.mh * 256 : 0;
+    g.o_cr = c == 3 ? g.o_cb + (size_t)g.mw * p.mh * 64 : 0;
+    g.stride = g.nblk * 64;
+    p.o_coef = 0;
+    p.o_planes = align256((size_t)n * g.nblk * 64 * sizeof(int16_t));
+    p.total = p.o_planes + align256((size_t)n * g.stride);
+    return p;
+}
+
+// One pass of jidctint over 8 values p[0], p[S], ..., descaled by N bits.  int32 suffices for coefficients that come from 8-bit samples at
+// any quality: a dequantised coefficient is within q / 2 <= 127.5 of the forward DCT's, which is at most 1024, so |d| <= 1152, and in the
+// column pass even the sum of the absolute values of every term of the largest intermediate (an output: 169352 |d|) is 1.96e8 < 2^31.  For
+// the row pass that crude sum is too weak and Parseval does the work: the block's 64 coefficients are an orthonormal DCT of samples in
+// [-128, 127] (2-norm <= 8 * 128) plus a quantisation error (2-norm <= 8 * 127.5), the column pass is 4 sqrt(8) times an orthonormal
+// transform, so the 8 inputs of a row have a 2-norm of at most 4 sqrt(8) * 2044 + rounding < 23200; every intermediate of the pass is a
+// fixed linear form of them whose coefficient vector has a 2-norm below 30000 (the largest: z2, 20995 sqrt(2) = 29692; the outputs: 23200),
+// so by Cauchy-Schwarz it stays below 30000 * 23200 = 6.96e8 < 2^31.
+template <int S, int N>
+__device__ __forceinline__ void idct_pass(int* p) {
+    constexpr int R = 1 << (N - 1);
+    const int d0 = p[0], d1 = p[S], d2 = p[2 * S], d3 = p[3 * S], d4 = p[4 * S], d5 = p[5 * S], d6 = p[6 * S], d7 = p[7 * S];
+    int z1 = (d2 + d6) * 4433;
+    const int tmp2 = z1 - d6 * 15137, tmp3 = z1 + d2 * 6270;
+    const int tmp0 = (d0 + d4) * 8192, tmp1 = (d0 - d4) * 8192;
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    int t0 = d7, t1 = d5, t2 = d3, t3 = d1;
+    z1 = t0 + t3;
+    int z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
+    const int z5 = (z3 + z4) * 9633;
+    t0 *= 2446, t1 *= 16819, t2 *= 25172, t3 *= 12299;
+    z1 *= -7373, z2 *= -20995;
+    z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+    t0 += z1 + z3, t1 += z2 + z4, t2 += z2 + z3, t3 += z1 + z4;
+    p[0] = (tmp10 + t3 + R) >> N;
+    p[7 * S] = (tmp10 - t3 + R) >> N;
+    p[S] = (tmp11 + t2 + R) >> N;
+    p[6 * S] = (tmp11 - t2 + R) >> N;
+    p[2 * S] = (tmp12 + t1 + R) >> N;
+    p[5 * S] = (tmp12 - t1 + R) >> N;
+    p[3 * S] = (tmp13 + t0 + R) >> N;
+    p[4 * S] = (tmp13 - t0 + R) >> N;
+}
+
+__device__ __forceinline__ uint32_t range_limit(int x) {
+    const int i = x & 0x3ff;
+    return (uint32_t)(i < 512 ? min(i + 128, 255) : max(i - 896, 0));
+}
+
+__global__ __launch_bounds__(IDCT_PER_WG * 8) void jpeg_idct_kernel(const int16_t* __restrict__ coef, int quality, uint8_t* __restrict__ planes, Planes g) {
+    constexpr int NB = IDCT_PER_WG, THREADS = NB * 8;
+    __shared__ int samp[NB * 72];               // 8 rows of 9 ints per block, as in the forward transform
+    __shared__ int q[128];
+    const int t = threadIdx.x;
+    const size_t f = blockIdx.y, b0 = (size_t)blockIdx.x * NB;
+    const int count = (int)min((size_t)NB, g.nblk - b0);
+    if (t < 128) q[t] = quant_entry(t >> 6, t & 63, quality);
+    __syncthreads();
+    const uint32_t* s32 = (const uint32_t*)(coef + (f * g.nblk + b0) * 64);          // block starts are 128-byte aligned in the workspace
+    for (int i = t; i < count * 32; i += THREADS) {
+        const uint32_t v = s32[i];
+        const int blk = i >> 5, z = (i & 31) * 2;
+        const int* qt = q + (g.c == 3 && (b0 + blk) % 6 >= 4 ? 64 : 0);
+        const int n0 = T.zigzag[z], n1 = T.zigzag[z + 1];
+        samp[blk * 72 + (n0 >> 3) * 9 + (n0 & 7)] = (int)(int16_t)(v & 0xffff) * qt[n0];
+        samp[blk * 72 + (n1 >> 3) * 9 + (n1 & 7)] = (int)(int16_t)(v >> 16) * qt[n1];
+    }
+    __syncthreads();
+    const int blk = t >> 3, k = t & 7;
+    if (blk < count) idct_pass<9, 11>(samp + blk * 72 + k);
+    __syncthreads();
+    if (blk < count) {
+        int* p = samp + blk * 72 + k * 9;
+        idct_pass<1, 18>(p);
+        uint2 out;
+        out.x = range_limit(p[0]) | range_limit(p[1]) << 8 | range_limit(p[2]) << 16 | range_limit(p[3]) << 24;
+        out.y = range_limit(p[4]) | range_limit(p[5]) << 8 | range_limit(p[6]) << 16 | range_limit(p[7]) << 24;
+        const size_t b = b0 + blk;
+        size_t at;                              // of row k of the block in the frame's planes
+        if (g.c == 3) {
+            const size_t m = b / 6, my = m / g.mw, mx = m - my * g.mw;
+            const int j = (int)(b - m * 6);
+            if (j < 4) at = ((2 * my + (j >> 1)) * 8 + k) * g.yw + (2 * mx + (j & 1)) * 8;
+            else at = (j == 4 ? g.o_cb : g.o_cr) + (my * 8 + k) * g.cw + mx * 8;
+        } else {
+            const size_t by = b / g.bw, bx = b - by * g.bw;
+            at = (by * 8 + k) * g.yw + bx * 8;
+        }
+        *(uint2*)(planes + f * g.stride + at) = out;
+    }
+}
+
+__device__ __forceinline__ uint32_t clamp_u8(int v) { return (uint32_t)min(max(v, 0), 255); }
+
+// C = 3: the pixels (x, x + 1) of row y from their luma samples and chroma column x / 2; C = 1: the luma samples themselves.
+template <int C>
+__global__ __launch_bounds__(MERGE_PX / 2) void jpeg_merge_kernel(const uint8_t* __restrict__ planes, Planes g, int h, int w, uint8_t* __restrict__ dst) {
+    constexpr int THREADS = MERGE_PX / 2;
+    __shared__ __attribute__((aligned(4))) uint8_t seg[MERGE_PX * C + 8];           // the row segment, shifted by the destination's byte phase
+    const int t = threadIdx.x, y = blockIdx.y, x0 = blockIdx.x * MERGE_PX, x = x0 + 2 * t;
+    const uint8_t* fp = planes + (size_t)blockIdx.z * g.stride;
+    uint8_t* d = dst + (((size_t)blockIdx.z * h + y) * w + x0) * C;
+    const int sh = (int)((uintptr_t)d & 3), total = min(MERGE_PX, w - x0) * C;
+    if (x < w) {
+        const uint8_t* yp = fp + (size_t)y * g.yw + x;                              // x + 1 <= yw - 1: the plane has whole blocks
+        const int y0 = yp[0], y1 = yp[1];
+        uint8_t* o = seg + sh + 2 * t * C;
+        if (C == 1) {
+            o[0] = (uint8_t)y0, o[1] = (uint8_t)y1;
+        } else {
+            const int ch = (h + 1) >> 1, cw = (w + 1) >> 1, r = y >> 1, cc = x >> 1;
+            int cb[2], cr[2];
+            if (cw <= 2) {
+                cb[0] = cb[1] = fp[g.o_cb + (size_t)r * g.cw + cc];
+                cr[0] = cr[1] = fp[g.o_cr + (size_t)r * g.cw + cc];
+            } else {
+                const int rn = (y & 1) ? min(r + 1, ch - 1) : max(r - 1, 0), cl = max(cc - 1, 0), cn = min(cc + 1, cw - 1);
+                const uint8_t* a = fp + (size_t)r * g.cw;
+                const uint8_t* b = fp + (size_t)rn * g.cw;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const size_t o_k = k ? g.o_cr : g.o_cb;
+                    const int s = 3 * a[o_k + cc] + b[o_k + cc], sl = 3 * a[o_k + cl] + b[o_k + cl], sn = 3 * a[o_k + cn] + b[o_k + cn];
+                    (k ? cr : cb)[0] = (3 * s + sl + 8) >> 4;
+                    (k ? cr : cb)[1] = (3 * s + sn + 7) >> 4;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int yy = k ? y1 : y0, u = cb[k] - 128, v = cr[k] - 128;
+                o[3 * k] = (uint8_t)clamp_u8(yy + ((91881 * v + 32768) >> 16));
+                o[3 * k + 1] = (uint8_t)clamp_u8(yy + ((-22554 * u - 46802 * v + 32768) >> 16));
+                o[3 * k + 2] = (uint8_t)clamp_u8(yy + ((116130 * u + 32768) >> 16));
+            }
+        }
+    }
+    __syncthreads();
+    // seg[sh .. sh + total) goes to d[0 .. total): dword j of seg is the aligned dword j from d - sh on
+    uint8_t* base = d - sh;
+    for (int j = t; j < (sh + total + 3) >> 2; j += THREADS) {
+        const int lo = max(4 * j, sh), hi = min(4 * j + 4, sh + total);
+        if (hi - lo == 4) {
+            ((uint32_t*)base)[j] = ((const uint32_t*)seg)[j];
+        } else {
+            for (int i = lo; i < hi; ++i) base[i] = seg[i];
+        }
+    }
+}
+
 const char* check_shape(int n, int h, int w, int c, int quality) {
     if (n < 1) return "n < 1";
     if (c != 1 && c != 3) return "channels other than 1 (L) and 3 (RGB)";
@@ -608,6 +815,36 @@ int launch_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int qu
     jpeg_scan_kernel<uint32_t, uint32_t><<<n, SCAN_THREADS, 0, s>>>(ffcnt, ffoff, fftotal, p.chunks, 0, total);
     jpeg_scatter_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffoff, fftotal, p.chunks, h, w, c == 3, quality, out, out_stride, lengths);
     return check_launch("jpeg_encode_u8");
+}
+
+int jpeg_roundtrip_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
+    const char* bad = check_shape(n, h, w, c, 75);
+    if (bad) { set_error("jpeg_roundtrip_u8: %s (n %d, %d x %d x %d)", bad, n, h, w, c); return -1; }
+    if (workspace_bytes) *workspace_bytes = make_roundtrip_plan(n, h, w, c).total;
+    return 0;
+}
+
+int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, hipStream_t s) {
+    const char* bad = check_shape(n, h, w, c, quality);
+    if (bad) { set_error("jpeg_roundtrip_u8: %s (n %d, %d x %d x %d, quality %d)", bad, n, h, w, c, quality); return -1; }
+    if ((uintptr_t)workspace % 8) { set_error("jpeg_roundtrip_u8: the workspace must be 8-byte aligned"); return -1; }
+    const RoundtripPlan p = make_roundtrip_plan(n, h, w, c);
+    const Planes& g = p.g;
+    // gridDim.y and .z are limited to 65535: h <= 65535 keeps the rows below that; the frames ride in y (idct) and z (transform, merge)
+    if (n > 65535 || (g.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull) { set_error("jpeg_roundtrip_u8: batch of %d frames too large for one call", n); return -1; }
+    int16_t* coef = (int16_t*)((char*)workspace + p.o_coef);
+    uint8_t* planes = (uint8_t*)workspace + p.o_planes;
+    if (c == 3)
+        jpeg_transform_rgb_kernel<<<dim3((g.mw + MCUS_PER_WG - 1) / MCUS_PER_WG, p.mh, n), MCUS_PER_WG * 48, 0, s>>>(src, h, w, quality, coef, g.mw, g.bw, p.bh, g.nblk);
+    else
+        jpeg_transform_grey_kernel<<<dim3((g.bw + GREY_PER_WG - 1) / GREY_PER_WG, p.bh, n), GREY_PER_WG * 8, 0, s>>>(src, h, w, quality, coef, g.bw, g.nblk);
+    jpeg_idct_kernel<<<dim3((unsigned)((g.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG), n), IDCT_PER_WG * 8, 0, s>>>(coef, quality, planes, g);
+    const dim3 grid((w + MERGE_PX - 1) / MERGE_PX, h, n);
+    if (c == 3)
+        jpeg_merge_kernel<3><<<grid, MERGE_PX / 2, 0, s>>>(planes, g, h, w, dst);
+    else
+        jpeg_merge_kernel<1><<<grid, MERGE_PX / 2, 0, s>>>(planes, g, h, w, dst);
+    return check_launch("jpeg_roundtrip_u8");
 }
 
 }  // namespace adain

@@ -212,6 +212,11 @@ class AdaINEngine:
         device, encoded there (adain_jpeg_encode_u8) -> a list of n ``bytes``; only the files cross to the host."""
         return rt.jpeg_files(*rt.jpeg_encode_u8(frames_u8, quality))
 
+    def jpeg_roundtrip_u8(self, frames_u8, quality=rt.JPEG_DEFAULT_QUALITY):
+        """uint8 frames [n,h,w,3|1] on the device -> the frames Pillow decodes from the JPEG files it would save for them at ``quality``
+        (what ``video._jpeg_roundtrip`` computes on the host), byte for byte, on the device (adain_jpeg_roundtrip_u8)."""
+        return rt.jpeg_roundtrip_u8(frames_u8, quality)
+
     def colour_transfer_u8(self, fg, bg, out=None):
         """The localized pipeline's foreground colour transfer (localized_style_transfer.py:128-168) on uint8 HWC images -> (adjusted
         foreground, device record); see ``runtime.colour_transfer_u8``."""

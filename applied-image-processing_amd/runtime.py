@@ -99,6 +99,8 @@ SIGNATURES = {
                                       _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_jpeg_roundtrip_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t)]),
+    "adain_jpeg_roundtrip_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_nhwc_to_nchw": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_nchw_to_nhwc": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_conv3x3_wino4_packed_floats": (_c_size_t, [_c_int, _c_int]),
@@ -815,6 +817,20 @@ def resize_pil_bilinear_u8(frames, size, crop=None, out=None):
 JPEG_DEFAULT_QUALITY = 75          # Pillow's
 
 
+def _jpeg_frames(u8, what, quality):
+    """The checks and input forms the JPEG calls share: frames uint8 [n,h,w,3|1], one frame [h,w,3|1] or [h,w] -> contiguous [n,h,w,c]."""
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise AdainHipError(f"{what}: quality must be an int in 1..100, got {quality!r}")
+    x = device_tensor(u8, "frames", torch.uint8)
+    if x.dim() == 2:
+        x = x[None, :, :, None]
+    elif x.dim() == 3:
+        x = x[None]
+    if x.dim() != 4 or x.shape[3] not in (1, 3) or x.shape[0] < 1:
+        raise AdainHipError(f"{what}: expected uint8 [n,h,w,3|1], [h,w,3|1] or [h,w], got {tuple(u8.shape)}")
+    return x
+
+
 def jpeg_encode_sizes(n, h, w, c):
     """(out_stride, workspace_bytes) of adain_jpeg_encode_u8_bytes: the largest file a frame of this shape can have and the scratch
     of an n-frame call.  Host only.  AdainHipError for a refused shape."""
@@ -829,15 +845,7 @@ def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY):
     """Frames uint8 [n,h,w,c] (c = 3: RGB, 1: L; or one frame [h,w,c] / [h,w]) -> (files uint8 [n, stride], lengths int32 [n]), both on the
     device: row i starts with frame i's JPEG file, ``lengths[i]`` bytes, byte for byte what ``PIL.Image.fromarray(frame).save(f,
     format="JPEG", quality=quality)`` writes; the rest of the row is not written.  Nothing is copied to the host and nothing waits."""
-    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
-        raise AdainHipError(f"jpeg_encode_u8: quality must be an int in 1..100, got {quality!r}")
-    x = device_tensor(u8, "frames", torch.uint8)
-    if x.dim() == 2:
-        x = x[None, :, :, None]
-    elif x.dim() == 3:
-        x = x[None]
-    if x.dim() != 4 or x.shape[3] not in (1, 3) or x.shape[0] < 1:
-        raise AdainHipError(f"jpeg_encode_u8: expected uint8 [n,h,w,3|1], [h,w,3|1] or [h,w], got {tuple(u8.shape)}")
+    x = _jpeg_frames(u8, "jpeg_encode_u8", quality)
     n, h, w, c = x.shape
     stride = 0
 
@@ -858,6 +866,28 @@ def jpeg_files(out, lengths):
     the device)."""
     ln = lengths.cpu().tolist()
     return [out[i, :k].cpu().numpy().tobytes() for i, k in enumerate(ln)]
+
+
+def jpeg_roundtrip_sizes(n, h, w, c):
+    """workspace_bytes of adain_jpeg_roundtrip_u8_bytes: the scratch of an n-frame call.  Host only.  AdainHipError for a refused shape."""
+    ws = _c_size_t()
+    rc = lib().adain_jpeg_roundtrip_u8_bytes(int(n), int(h), int(w), int(c), ctypes.byref(ws))
+    if rc != 0:
+        raise _failure("adain_jpeg_roundtrip_u8_bytes", rc)
+    return ws.value
+
+
+def jpeg_roundtrip_u8(u8, quality=JPEG_DEFAULT_QUALITY):
+    """Frames uint8 [n,h,w,c] (c = 3: RGB, 1: L; or one frame [h,w,c] / [h,w]) -> a device tensor of the input's shape: per frame the
+    pixels ``Image.open`` decodes (mode RGB / L) from the file ``PIL.Image.fromarray(frame).save(f, format="JPEG", quality=quality)``
+    writes, byte for byte, computed on the device without the file (adain_jpeg_roundtrip_u8).  Nothing is copied to the host and
+    nothing waits."""
+    x = _jpeg_frames(u8, "jpeg_roundtrip_u8", quality)
+    n, h, w, c = x.shape
+    with scratch(x.device, "jpeg", jpeg_roundtrip_sizes, n, h, w, c) as ws:
+        out = torch.empty_like(x)
+        _launch("adain_jpeg_roundtrip_u8", x.data_ptr(), n, h, w, c, quality, out.data_ptr(), ws.data_ptr(), ws.numel())
+    return out.reshape(u8.shape)
 
 
 def nhwc_to_nchw(x):

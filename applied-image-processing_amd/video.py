@@ -25,7 +25,9 @@ What stays with the caller, because the reference gets it from libraries this pa
     (tvl1.TVL1Sequence.batch: each frame prepared once, many pairs per launch).  With either installed, a method it does not
     serve is refused before any frame is stylised.
 One deliberate difference: the reference writes every stylised frame as a JPEG into a temporary directory and reads it back
-(:261-273); here the uint8 frames stay in memory unless ``intermediate_jpeg=True`` re-creates that lossy round trip.
+(:261-273); here the uint8 frames stay in memory unless ``intermediate_jpeg=True`` re-creates that lossy round trip - through PIL on
+the host, or with ``jpeg_on_device=True`` on the GPU, where the whole batch becomes the pixels PIL would decode without a file being
+made (csrc/jpeg.hip, adain_jpeg_roundtrip_u8: the same bytes).
 """
 import io
 import os
@@ -209,7 +211,9 @@ def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolu
     styles = [stf(Image.open(p).convert("RGB")).unsqueeze(0) for p in style_paths]
     # stylise (sharded), resize to the target resolution on the owning rank, gather; the recurrence needs the flows: rank 0 only
     post = None
-    if intermediate_jpeg:
+    if intermediate_jpeg and jpeg_on_device and on_gpu:
+        post = engine.jpeg_roundtrip_u8                        # the same bytes, computed where the batch is (adain_jpeg_roundtrip_u8)
+    elif intermediate_jpeg:
         post = lambda u8: torch.from_numpy(_jpeg_roundtrip(u8.cpu().numpy())).to(u8.device)
     if crossfade_frames:        # the styles cross-fade in feature space where the schedule cuts: per-frame weights instead of an index
         which = {"style_weights": jobs.style_crossfade(len(names), len(styles), crossfade_frames)}
@@ -260,8 +264,9 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
                              depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False, preserve_color=False):
     """One style for the whole clip (video/utils.py:244-295); keyword-only extras: a ready ``engine``, checkpoint paths,
     precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``jpeg_on_device`` (.jpg / .jpeg frames are
-    encoded on the device: the same files, jobs.FileSink), ``preserve_color`` (every frame is styled with ``coral(style, frame)``,
-    adain_inference's colour preservation, on the device)."""
+    encoded on the device: the same files, jobs.FileSink; with ``intermediate_jpeg`` and the engine on a GPU the intermediate round trip
+    runs on the device too, ``AdaINEngine.jpeg_roundtrip_u8``: the same frames), ``preserve_color`` (every frame is styled with
+    ``coral(style, frame)``, adain_inference's colour preservation, on the device)."""
     return _run(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
                 engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color)
 
@@ -273,6 +278,7 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
                                    group=None, jpeg_on_device=False, preserve_color=False, crossfade_frames=0):
     """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372).
     ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics.
+    ``jpeg_on_device``: as in ``apply_style_transfer_ada``, the output files and, with ``intermediate_jpeg``, the intermediate round trip.
     ``crossfade_frames`` (0, the default: the hard cuts of the reference): the styles cross-fade in feature space over that many
     frames centred on each switch (``jobs.style_crossfade``, style interpolation on the device; at most 16 styles, and not with
     ``preserve_color``)."""

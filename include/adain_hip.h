@@ -463,6 +463,27 @@ ADAIN_API int adain_jpeg_encode_u8_bytes(int n, int h, int w, int c, size_t* out
 ADAIN_API int adain_jpeg_encode_u8(const uint8_t* src_u8, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride,
                                    int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
+/* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
+ * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * src, dst: n frames HWC uint8 [n][h][w][c], c = 3 (RGB) or 1 (L), at any byte address.  dst frame i holds the pixels Pillow decodes
+ * (Image.open(...), mode RGB for c = 3, mode L for c = 1) from the file its Image.fromarray(frame i).save(f, format="JPEG",
+ * quality=quality) writes, byte for byte (established against Pillow 12.2.0 built with libjpeg-turbo).  No file is made: entropy coding
+ * is lossless, so the decoded pixels are a function of the quantised coefficients adain_jpeg_encode_u8's transform stage computes.  Behind
+ * that stage run the coefficient times its quantisation-table entry, libjpeg's integer "islow" inverse DCT (columns, then rows) with its
+ * 1024-entry range-limit table, the crop of the luma block grid to h x w, for RGB libjpeg's h2v2 "fancy" chroma upsampling of the
+ * ceil(h/2) x ceil(w/2) real chroma samples (plain 2 x 2 replication when w <= 4, as libjpeg does) and its YCbCr -> RGB map.  The rules
+ * are listed at the top of csrc/jpeg.hip and restated in NumPy in tests/jpeg_decode_ref.py.  Integer arithmetic throughout: a frame's
+ * bytes do not depend on the batch, the stream or the device size.
+ * adain_jpeg_roundtrip_u8_bytes (host only): *workspace_bytes = the coefficients (2 bytes per sample of the padded block grid) and the
+ *   uint8 Y / Cb / Cr planes of n frames.  The output may be NULL.
+ * Refused with ADAIN_EINVAL before anything is launched: a null pointer, c other than 1 and 3, h or w outside 1..65535, n < 1, quality
+ * outside 1..100, n > 65535 (the frames ride in one grid dimension), a workspace_bytes below the query's, a workspace that is not
+ * 8-byte aligned, and a dst whose n h w c bytes overlap src's.  3 kernel launches per call, whatever n. */
+ADAIN_API int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
+ADAIN_API int adain_jpeg_roundtrip_u8(const uint8_t* src_u8, int n, int h, int w, int c, int quality, uint8_t* dst_u8, void* workspace,
+                                      size_t workspace_bytes, adain_stream_t stream);
+
 /* ---- layout changes at the boundary ([n][c][hw] <-> [n][hw][c]) ------------------------------------------ */
 ADAIN_API int adain_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, adain_stream_t stream);
 ADAIN_API int adain_nchw_to_nhwc(const float* in, float* out, int n, int c, int hw, adain_stream_t stream);

@@ -1,0 +1,111 @@
+"""Times the video path's intermediate JPEG round trip (``intermediate_jpeg=True``) on the device (csrc/jpeg.hip,
+adain_jpeg_roundtrip_u8) against the host route through Pillow on the same machine, at 256 x 456 and 1080 x 1920, on a stylised
+synthetic frame (seed-0 weights) and on uniform noise.  Per call on a batch of --batch frames, median and interquartile range over
+--reps calls (>= 200) after warm-up:
+  kernel_ms  adain_jpeg_roundtrip_u8 on device-resident frames, HIP events
+  device_ms  wall clock of the ``post`` hook with ``jpeg_on_device=True``: device tensor in, device tensor out, synchronised
+  host_ms    the ``post`` hook without it: download, ``video._jpeg_roundtrip`` (Pillow, one thread), upload, synchronised
+and whether the two give the same bytes.  ``device_is_faster``: device_ms sits below host_ms by more than the two interquartile ranges
+combined.  Prints one JSON line and, with --out, writes it to a file.
+Usage: python tools/jpeg_roundtrip_bench.py [--reps 200] [--batch 1] [--out profiles/jpeg_roundtrip_bench.json]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import PIL
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+import applied_image_processing_amd.runtime as rt  # noqa: E402
+import applied_image_processing_amd.synth as synth  # noqa: E402
+from applied_image_processing_amd import video  # noqa: E402
+from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
+from applied_image_processing_amd.telemetry import GpuTelemetry  # noqa: E402
+
+SIZES = [(256, 456), (1080, 1920)]
+
+
+def spread(times):
+    q = statistics.quantiles(times, n=4)
+    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
+
+
+def wall_ms(fn, reps, warmup):
+    """fn() ends with its result on the device; the clock stops after a synchronise."""
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t) * 1e3)
+    return spread(times)
+
+
+def event_ms(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return spread(times)
+
+
+def host_post(u8):
+    """The ``post`` hook of video._run without ``jpeg_on_device``."""
+    return torch.from_numpy(video._jpeg_roundtrip(u8.cpu().numpy())).to(u8.device)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--out", type=str, default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "jpeg_roundtrip_bench needs a GPU"
+    torch.cuda.set_device(0)
+    torch.set_num_threads(1)
+    reps, n = max(args.reps, 200), max(args.batch, 1)
+    dev = torch.device("cuda:0")
+    engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
+    engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
+    tel = GpuTelemetry(0).start()
+    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
+           "batch": n, "pillow": PIL.__version__, "sizes": {}}
+    for h, w in SIZES:
+        source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
+        frames = {"stylised": engine.stylize_u8(source, alpha=0.5).contiguous().expand(n, -1, -1, -1).contiguous(),
+                  "noise": torch.from_numpy(np.random.default_rng(0).integers(0, 256, (n, h, w, 3), dtype=np.uint8)).to(dev)}
+        for kind, x in frames.items():
+            t0 = time.perf_counter()
+            kernel = event_ms(lambda: rt.jpeg_roundtrip_u8(x), reps, 20)
+            tel.window(f"kernel_{kind}_{h}x{w}", t0, time.perf_counter())
+            device = wall_ms(lambda: engine.jpeg_roundtrip_u8(x), reps, 5)
+            host = wall_ms(lambda: host_post(x), reps, 3)
+            res["sizes"][f"{kind}_{h}x{w}"] = {"frame_bytes": int(x[0].numel()), "same_bytes_as_host": bool(torch.equal(engine.jpeg_roundtrip_u8(x), host_post(x))),
+                                               "kernel_ms": kernel, "device_ms": device, "host_ms": host,
+                                               "host_over_device": round(host["median"] / device["median"], 2),
+                                               "device_is_faster": device["median"] + device["iqr"] + host["iqr"] < host["median"]}
+    res["telemetry"] = tel.stop()          # shader clock and power over each kernel timing window (sysfs reads)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
