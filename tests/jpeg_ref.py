@@ -187,13 +187,10 @@ def _huff():
     return _TABLES
 
 
-def entropy_bits(z, tbl):
-    """Per coefficient of z [blocks, 64] (DC difference at 0) the bits it puts into the stream as (pattern uint64, right-aligned; length):
-    a non-zero AC coefficient carries the ZRLs of its run, its run/size code and its value bits; the DC always codes; the last coded
-    coefficient of a block that does not end at 63 carries the EOB as well.  Length 0: nothing."""
-    dcc, dcl, acc, acl = _huff()
+def run_sizes(z):
+    """Per coefficient of z [blocks, 64] (DC difference at 0): (coded bool - the DC and every non-zero AC; run - the zeros between it and
+    the coded coefficient before it, 0..62, 0 at the DC; size - bit_length(|v|); last - the last coded position at or before each)."""
     nb = len(z)
-    u = np.uint64
     pos = np.arange(64)
     nz = z != 0
     nz[:, 0] = True
@@ -202,6 +199,17 @@ def entropy_bits(z, tbl):
     run[:, 0] = 0
     a = np.abs(z)
     size = sum((a >> k) > 0 for k in range(12)).astype(np.int64)              # bit_length(|v|)
+    return nz, run, size, last
+
+
+def entropy_bits(z, tbl):
+    """Per coefficient of z [blocks, 64] (DC difference at 0) the bits it puts into the stream as (pattern uint64, right-aligned; length):
+    a non-zero AC coefficient carries the ZRLs of its run, its run/size code and its value bits; the DC always codes; the last coded
+    coefficient of a block that does not end at 63 carries the EOB as well.  Length 0: nothing."""
+    dcc, dcl, acc, acl = _huff()
+    u = np.uint64
+    pos = np.arange(64)
+    nz, run, size, last = run_sizes(z)
     val = (np.where(z < 0, z - 1, z) & ((1 << size) - 1)).astype(u)
     t = tbl[:, None]
     sym = np.where(nz, ((run & 15) << 4) | size, 0)
