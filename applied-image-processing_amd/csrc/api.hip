@@ -418,28 +418,33 @@ int adain_mean_std(const float* feat, int nhwc, int n, int c, int hw, float eps,
     return launch_mean_std(feat, nhwc, n, c, hw, eps, mean, std_out, workspace, ws_bytes, (hipStream_t)stream);
 }
 
+// s_mean / s_std [style_n][c] of the single-style entries: one row for every frame, or one row per frame
+static int blend_single(const float* x, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const float* s_mean,
+                        const float* s_std, int style_n, const BlendTerm& blend, float* out, adain_stream_t stream) {
+    if (style_n != 1 && style_n != n) { set_error("adain_blend: style batch %d must be 1 or %d", style_n, n); return -1; }
+    return launch_adain_blend(x, nhwc, n, c, hw, c_mean, c_std, StyleTerm{s_mean, s_std, 1, style_n == n, nullptr, 1, 1}, blend, out, (hipStream_t)stream);
+}
+
 int adain_blend_alpha(const float* x, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std,
                       const float* s_mean, const float* s_std, int style_n, float alpha, float one_minus_alpha, float* out,
                       adain_stream_t stream) {
     if (!x || !c_mean || !c_std || !s_mean || !s_std || !out) { set_error("blend_alpha: null pointer"); return ADAIN_EINVAL; }
-    return launch_adain_blend_ex(x, nhwc, n, c, hw, c_mean, c_std, s_mean, s_std, style_n, alpha, one_minus_alpha, nullptr, 1, out,
-                                 (hipStream_t)stream);
+    return blend_single(x, nhwc, n, c, hw, c_mean, c_std, s_mean, s_std, style_n, BlendTerm{alpha, one_minus_alpha, nullptr, 1}, out, stream);
 }
 
 int adain_blend_pmap(const float* x, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std,
                      const float* s_mean, const float* s_std, int style_n, const float* pmap, int pmap_n, float* out,
                      adain_stream_t stream) {
     if (!x || !c_mean || !c_std || !s_mean || !s_std || !out || !pmap) { set_error("blend_pmap: null pointer"); return ADAIN_EINVAL; }
-    return launch_adain_blend_ex(x, nhwc, n, c, hw, c_mean, c_std, s_mean, s_std, style_n, 0.f, 0.f, pmap, pmap_n, out,
-                                 (hipStream_t)stream);
+    return blend_single(x, nhwc, n, c, hw, c_mean, c_std, s_mean, s_std, style_n, BlendTerm{0.f, 0.f, pmap, pmap_n}, out, stream);
 }
 
 int adain_blend_mix(const float* x, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const float* s_mean,
                     const float* s_std, int k, const float* weights, int weights_n, int weights_hw, float alpha, float one_minus_alpha,
                     const float* pmap, int pmap_n, float* out, adain_stream_t stream) {
     if (!x || !c_mean || !c_std || !s_mean || !s_std || !weights || !out) { set_error("blend_mix: null pointer"); return ADAIN_EINVAL; }
-    return launch_adain_blend_mix(x, nhwc, n, c, hw, c_mean, c_std, s_mean, s_std, k, weights, weights_n, weights_hw, alpha, one_minus_alpha,
-                                  pmap, pmap_n, out, (hipStream_t)stream);
+    return launch_adain_blend(x, nhwc, n, c, hw, c_mean, c_std, StyleTerm{s_mean, s_std, k, 0, weights, weights_n, weights_hw},
+                              BlendTerm{alpha, one_minus_alpha, pmap, pmap_n}, out, (hipStream_t)stream);
 }
 
 size_t adain_strength_map_workspace_bytes(int hc, int wc) { return strength_map_workspace_bytes(hc, wc); }
@@ -621,21 +626,13 @@ size_t adain_stylize_u8_ex_workspace_bytes(int n, int h, int w, int use_depth, i
 
 static_assert(MIX_MAX_STYLES == ADAIN_MIX_MAX_STYLES, "csrc/common.h and include/adain_hip.h disagree");
 
-// adain_stylize_u8 / _ex (weights == nullptr: s_mean / s_std [style_n][512], one style per frame when style_n == n) and
-// adain_stylize_u8_mix (weights != nullptr: s_mean / s_std [k][512] mixed per frame by weights [weights_n][k][weights_hw])
-static int stylize_impl(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const float* s_mean,
-                        const float* s_std, int style_n, int k, const float* weights, int weights_n, int weights_hw, float alpha,
-                        float one_minus_alpha, const float* const* depth_maps, const int* depth_h, const int* depth_w, float depth_offset,
+// adain_stylize_u8 / _ex (one style, or one per frame) and adain_stylize_u8_mix (a weighted mix of k styles): style's rows are [512]
+static int stylize_impl(const uint8_t* frames, int n, int h, int w, const float* enc_packed, const float* dec_packed, const StyleTerm& style,
+                        float alpha, float one_minus_alpha, const float* const* depth_maps, const int* depth_h, const int* depth_w, float depth_offset,
                         float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c, int mask_h, int mask_w, uint8_t* out_u8,
                         void* workspace, size_t ws_bytes, adain_stream_t stream) {
-    if (!frames || !enc_packed || !dec_packed || !s_mean || !s_std || !out_u8 || !workspace) { set_error("stylize_u8: null pointer"); return ADAIN_EINVAL; }
+    if (!frames || !enc_packed || !dec_packed || !style.s_mean || !style.s_std || !out_u8 || !workspace) { set_error("stylize_u8: null pointer"); return ADAIN_EINVAL; }
     if (n < 1 || h < 9 || w < 9) { set_error("stylize_u8: frames %dx%d too small (needs h, w >= 9)", h, w); return ADAIN_EINVAL; }
-    if (!weights && style_n != 1 && style_n != n) { set_error("stylize_u8: %d styles for %d frames (1 or one per frame)", style_n, n); return ADAIN_EINVAL; }
-    if (weights) {          // the mix's own rules, on the relu4_1 map's size
-        int hc, wc;
-        adain_encoded_size(h, w, &hc, &wc);
-        if (check_adain_blend_mix(1, n, 512, hc * wc, k, weights_n, weights_hw, 0, 1)) return ADAIN_EINVAL;
-    }
     if (!depth_maps && !(alpha >= 0.f && alpha <= 1.f)) { set_error("stylize_u8: alpha %g outside [0, 1]", alpha); return ADAIN_EINVAL; }   // test.py:75
     if (depth_maps && (!depth_h || !depth_w)) { set_error("stylize_u8: depth maps without their sizes"); return ADAIN_EINVAL; }
     if (depth_maps && !(depth_offset >= 0.f && depth_offset <= 1.f)) { set_error("stylize_u8: offset %g outside [0, 1]", depth_offset); return ADAIN_EINVAL; }   // test.py:56
@@ -669,22 +666,20 @@ static int stylize_impl(const uint8_t* frames, int n, int h, int w, const float*
     float* sty_r = take(p.sty_r);
     float* comp = take(p.comp);
     const int hw_c = p.hc * p.wc;
+    const BlendTerm blend{alpha, one_minus_alpha, pmap, n};      // pmap: null without depth maps
+    if (check_adain_blend("stylize_u8", 1, n, 512, hw_c, style, blend)) return ADAIN_EINVAL;     // the blend's own rules, on the relu4_1 map's size
 
     // vgg(content) with ToTensor inside the first layer (test.py:203-204, :57 / :76), calc_mean_std(content_f) (function.py:4-12)
     RET_IF(adain_encode_u8(frames, f, enc_packed, conv, p.conv * sizeof(float), n, h, w, nullptr, stream));
     RET_IF(launch_mean_std(f, 1, n, 512, hw_c, 1e-5f, c_mean, c_std, stats_ws, p.stats_ws * sizeof(float), s));
-    if (depth_maps) {       // compute_stylization_strength_map per frame, then AdaIN * (1 - P) + content_f * P (test.py:66-70)
+    if (depth_maps)         // compute_stylization_strength_map per frame (test.py:66-69)
         for (int i = 0; i < n; ++i) {
             RET_IF(launch_strength_map(depth_maps[i], depth_h[i], depth_w[i], p.hc, p.wc, depth_offset, depth_prominence, pmap + (size_t)i * hw_c,
                                        pmap_ws, p.pmap_ws * sizeof(float), s));
         }
-        if (weights) RET_IF(launch_adain_blend_mix(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, k, weights, weights_n, weights_hw, 0.f, 0.f, pmap, n, g, s));
-        else RET_IF(launch_adain_blend_ex(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, style_n, 0.f, 0.f, pmap, n, g, s));
-    } else if (weights) {   // the same blend of the weighted mix of k styles (test_video.py:36-44)
-        RET_IF(launch_adain_blend_mix(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, k, weights, weights_n, weights_hw, alpha, one_minus_alpha, nullptr, 1, g, s));
-    } else {                // AdaIN * alpha + content_f * (1 - alpha) (test.py:79-80)
-        RET_IF(launch_adain_blend_ex(f, 1, n, 512, hw_c, c_mean, c_std, s_mean, s_std, style_n, alpha, one_minus_alpha, nullptr, 1, g, s));
-    }
+    // AdaIN * (1 - P) + content_f * P (test.py:70) or AdaIN * alpha + content_f * (1 - alpha) (test.py:79-80), AdaIN of the one style,
+    // the frame's own, or the weighted mix of k (test_video.py:36-44)
+    RET_IF(launch_adain_blend(f, 1, n, 512, hw_c, c_mean, c_std, style, blend, g, s));
     if (mask_n == 0 && ((uintptr_t)out_u8 & 3) == 0)        // decoder with save_image's quantiser inside its last layer (test.py:71 / :81, :243-244): the finished uint8 frames
         return decode_impl(g, nullptr, out_u8, dec_packed, conv, p.conv * sizeof(float), n, p.hc, p.wc, nullptr, stream);
     RET_IF(adain_decode(g, img, dec_packed, conv, p.conv * sizeof(float), n, p.hc, p.wc, nullptr, stream));     // test.py:71 / :81
@@ -717,8 +712,8 @@ int adain_stylize_u8(const uint8_t* frames, int n, int h, int w, const float* en
                      const float* s_std, float alpha, float one_minus_alpha, const float* const* depth_maps, const int* depth_h, const int* depth_w,
                      float depth_offset, float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c, int mask_h,
                      int mask_w, uint8_t* out_u8, void* workspace, size_t ws_bytes, adain_stream_t stream) {
-    return stylize_impl(frames, n, h, w, enc_packed, dec_packed, s_mean, s_std, 1, 0, nullptr, 0, 0, alpha, one_minus_alpha, depth_maps, depth_h, depth_w,
-                        depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes, stream);
+    return stylize_impl(frames, n, h, w, enc_packed, dec_packed, StyleTerm{s_mean, s_std, 1, 0, nullptr, 1, 1}, alpha, one_minus_alpha, depth_maps, depth_h,
+                        depth_w, depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes, stream);
 }
 
 // s_mean / s_std [style_n][512], style_n 1 (adain_stylize_u8) or n: one style per frame
@@ -726,8 +721,10 @@ int adain_stylize_u8_ex(const uint8_t* frames, int n, int h, int w, const float*
                         const float* s_std, int style_n, float alpha, float one_minus_alpha, const float* const* depth_maps, const int* depth_h,
                         const int* depth_w, float depth_offset, float depth_prominence, const void* mask, int mask_is_float, int mask_n, int mask_c,
                         int mask_h, int mask_w, uint8_t* out_u8, void* workspace, size_t ws_bytes, adain_stream_t stream) {
-    return stylize_impl(frames, n, h, w, enc_packed, dec_packed, s_mean, s_std, style_n, 0, nullptr, 0, 0, alpha, one_minus_alpha, depth_maps, depth_h,
-                        depth_w, depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes, stream);
+    if (style_n != 1 && style_n != n) { set_error("stylize_u8: %d styles for %d frames (1 or one per frame)", style_n, n); return ADAIN_EINVAL; }
+    return stylize_impl(frames, n, h, w, enc_packed, dec_packed, StyleTerm{s_mean, s_std, 1, style_n == n, nullptr, 1, 1}, alpha, one_minus_alpha, depth_maps,
+                        depth_h, depth_w, depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes,
+                        stream);
 }
 
 size_t adain_stylize_u8_mix_workspace_bytes(int n, int h, int w, int use_depth, int mask_n, int mask_c, int mask_h, int mask_w, int mask_is_float) {
@@ -741,9 +738,9 @@ int adain_stylize_u8_mix(const uint8_t* frames, int n, int h, int w, const float
                          const void* mask, int mask_is_float, int mask_n, int mask_c, int mask_h, int mask_w, uint8_t* out_u8, void* workspace,
                          size_t ws_bytes, adain_stream_t stream) {
     if (!weights) { set_error("stylize_u8_mix: null pointer"); return ADAIN_EINVAL; }
-    return stylize_impl(frames, n, h, w, enc_packed, dec_packed, s_mean, s_std, 1, k, weights, weights_n, weights_hw, alpha, one_minus_alpha, depth_maps,
-                        depth_h, depth_w, depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace, ws_bytes,
-                        stream);
+    return stylize_impl(frames, n, h, w, enc_packed, dec_packed, StyleTerm{s_mean, s_std, k, 0, weights, weights_n, weights_hw}, alpha, one_minus_alpha,
+                        depth_maps, depth_h, depth_w, depth_offset, depth_prominence, mask, mask_is_float, mask_n, mask_c, mask_h, mask_w, out_u8, workspace,
+                        ws_bytes, stream);
 }
 
 size_t adain_coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc) { return coral_workspace_bytes(n, style_n, hs, ws, hc, wc); }

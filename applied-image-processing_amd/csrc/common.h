@@ -108,15 +108,27 @@ int launch_conv_last(const float* in_nhwc, float* out_nchw, const float* packed,
 int launch_mean_std(const float* feat, int nhwc, int n, int c, int hw, float eps, float* mean, float* std_,
                     void* workspace, size_t ws_bytes, hipStream_t s);
 size_t mean_std_workspace_bytes(int nhwc, int n, int c, int hw);
-int launch_adain_blend_ex(const float* content, int nhwc, int n, int c, int hw, const float* c_mean,
-                          const float* c_std, const float* s_mean, const float* s_std, int style_n, float alpha,
-                          float one_minus_alpha, const float* pmap, int pmap_n, float* out, hipStream_t s);
-// the blend of a weighted mix of k styles (adain_blend_mix): s_mean / s_std [k][c], weights [weights_n][k][weights_hw] on the device
+// What a blend is styled with: s_mean / s_std hold k rows of c statistics.
+//   weights == nullptr: k = 1, the one style of every frame or (per_frame) frame i's row i
+//   weights != nullptr: the k rows are shared by all frames and mixed by weights [weights_n][k][weights_hw] on the device
+//                       (weights_n 1 | n, weights_hw 1 | hw: scalars or per-pixel maps); never with per_frame
 constexpr int MIX_MAX_STYLES = 16;   // ADAIN_MIX_MAX_STYLES
-int check_adain_blend_mix(int nhwc, int n, int c, int hw, int k, int weights_n, int weights_hw, int has_pmap, int pmap_n);
-int launch_adain_blend_mix(const float* content, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const float* s_mean,
-                           const float* s_std, int k, const float* weights, int weights_n, int weights_hw, float alpha, float one_minus_alpha,
-                           const float* pmap, int pmap_n, float* out, hipStream_t s);
+struct StyleTerm {
+    const float *s_mean, *s_std;
+    int k, per_frame;
+    const float* weights;
+    int weights_n, weights_hw;
+};
+// How strongly: out = styled * alpha + x * one_minus_alpha, or with pmap [pmap_n][hw] (pmap_n 1 | n) styled * (1 - P) + x * P
+struct BlendTerm {
+    float alpha, one_minus_alpha;
+    const float* pmap;
+    int pmap_n;
+};
+// host only, no HIP call: the argument rules of every blend; what: the entry's name for the error text
+int check_adain_blend(const char* what, int nhwc, int n, int c, int hw, const StyleTerm& style, const BlendTerm& blend);
+int launch_adain_blend(const float* content, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const StyleTerm& style,
+                       const BlendTerm& blend, float* out, hipStream_t s);
 
 // pixel.hip
 int launch_strength_map(const float* depth, int h0, int w0, int hc, int wc, float offset, float prominence,

@@ -166,110 +166,24 @@ int launch_mean_std(const float* feat, int nhwc, int n, int c, int hw, float eps
     return check_launch("mean_std");
 }
 
-// ---- AdaIN + blend ---------------------------------------------------------------------------------------
-// out = t * w1 + x * w2 with t = (x - mu_c) / sigma_c * sigma_s + mu_s, evaluated in the reference's
-// operation order without FMA contraction (function.py:21-23, test.py:70,80).
-//   alpha mode (pmap == nullptr): w1 = alpha, w2 = one_minus_alpha (computed on the host in double)
-//   pmap  mode                  : w1 = 1 - P[pixel], w2 = P[pixel]      (P broadcast over channels)
-template <bool NHWC>
-__global__ __launch_bounds__(256) void adain_blend_kernel(const float* __restrict__ x, int c, int hw,
-                                                          const float* __restrict__ c_mean, const float* __restrict__ c_std,
-                                                          const float* __restrict__ s_mean, const float* __restrict__ s_std,
-                                                          int style_n, float alpha, float one_minus_alpha,
-                                                          const float* __restrict__ pmap, int pmap_n,
-                                                          float* __restrict__ out, size_t total4) {
-#pragma clang fp contract(off)
-    // 32-bit index arithmetic (the launcher checks total < 2^31) and, for NHWC, one b128 load per statistic: the four
-    // elements of a quad are four consecutive channels of one pixel
-    const unsigned per_img = (unsigned)c * (unsigned)hw;
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)total4; i += gridDim.x * blockDim.x) {
-        const unsigned e = i * 4u;
-        const f32x4 v = *(const f32x4*)(x + e);
-        f32x4 r;
-        const unsigned img = e / per_img;
-        const unsigned rem = e - img * per_img;
-        const unsigned simg = style_n == 1 ? 0u : img;
-        if (NHWC) {
-            const unsigned pix = rem / (unsigned)c, ch = rem - pix * (unsigned)c;
-            const f32x4 mc = *(const f32x4*)(c_mean + img * c + ch), sc = *(const f32x4*)(c_std + img * c + ch);
-            const f32x4 ms = *(const f32x4*)(s_mean + simg * c + ch), ss = *(const f32x4*)(s_std + simg * c + ch);
-            float w1 = alpha, w2 = one_minus_alpha;
-            if (pmap) {
-                const float p = pmap[(pmap_n == 1 ? 0u : img) * (unsigned)hw + pix];
-                w1 = 1.0f - p;
-                w2 = p;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float nrm = (v[k] - mc[k]) / sc[k];
-                const float t = nrm * ss[k] + ms[k];
-                r[k] = t * w1 + v[k] * w2;
-            }
-        } else {
-            // the launcher asks n*c*hw % 4 == 0, not c*hw % 4 == 0: a quad may run over the end of its first element's image (over
-            // three of them when c*hw == 1), so every element takes its own image, and with it its own style and strength-map rows
-            unsigned ik = img, rk = rem;
-#pragma unroll
-            for (int k = 0; k < 4; ++k, ++rk) {
-                if (rk >= per_img) {
-                    rk -= per_img;
-                    ++ik;
-                }
-                const unsigned sk = style_n == 1 ? 0u : ik;
-                const unsigned ch = rk / (unsigned)hw, pix = rk - ch * (unsigned)hw;
-                const float mc = c_mean[ik * c + ch], sc = c_std[ik * c + ch];
-                const float ms = s_mean[sk * c + ch], ss = s_std[sk * c + ch];
-                const float nrm = (v[k] - mc) / sc;
-                const float t = nrm * ss + ms;
-                float w1 = alpha, w2 = one_minus_alpha;
-                if (pmap) {
-                    const float p = pmap[(pmap_n == 1 ? 0u : ik) * (unsigned)hw + pix];
-                    w1 = 1.0f - p;
-                    w2 = p;
-                }
-                r[k] = t * w1 + v[k] * w2;
-            }
-        }
-        *(f32x4*)(out + e) = r;
-    }
-}
-
-int launch_adain_blend_ex(const float* content, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std,
-                          const float* s_mean, const float* s_std, int style_n, float alpha, float one_minus_alpha,
-                          const float* pmap, int pmap_n, float* out, hipStream_t s) {
-    if (n < 1 || c < 1 || hw < 1) { set_error("adain_blend: bad shape"); return -1; }
-    if (style_n != 1 && style_n != n) { set_error("adain_blend: style batch %d must be 1 or %d", style_n, n); return -1; }
-    if (pmap && pmap_n != 1 && pmap_n != n) { set_error("adain_blend: pmap batch %d must be 1 or %d", pmap_n, n); return -1; }
-    const size_t total = (size_t)n * c * hw;
-    if (nhwc ? (c & 3) : (total & 3)) { set_error("adain_blend: element count / channels must be a multiple of 4"); return -1; }
-    if (total >= 0x7fffffffULL) { set_error("adain_blend: more than 2^31 elements per call"); return -1; }
-    const size_t total4 = total / 4;
-    const unsigned blocks = (unsigned)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
-    if (nhwc)
-        hipLaunchKernelGGL(adain_blend_kernel<true>, dim3(blocks), dim3(256), 0, s, content, c, hw, c_mean, c_std, s_mean, s_std,
-                           style_n, alpha, one_minus_alpha, pmap, pmap_n, out, total4);
-    else
-        hipLaunchKernelGGL(adain_blend_kernel<false>, dim3(blocks), dim3(256), 0, s, content, c, hw, c_mean, c_std, s_mean, s_std,
-                           style_n, alpha, one_minus_alpha, pmap, pmap_n, out, total4);
-    return check_launch("adain_blend");
-}
-
-// ---- AdaIN + blend of a weighted mix of K styles (style interpolation) ------------------------------------------------------------
-// The reference's style_transfer(..., interpolation_weights) (Style_3DGS/AdaIN/test_video.py:30-45) in its operation order, one
-// rounding per operation, no FMA contraction:
+// ---- AdaIN + blend, of one style or of a weighted mix of K styles (style interpolation) ------------------------------------------
+// The reference's style_transfer (Style_3DGS/AdaIN/test.py:70,80; with interpolation_weights test_video.py:30-45) in its operation
+// order, one rounding per operation, no FMA contraction:
 //   nrm  = (x - mu_c) / sigma_c                                  function.py:21-22, the same for every style
 //   b_k  = nrm * sigma_s[k] + mu_s[k]                            function.py:23
-//   feat = w_0 * b_0 ; feat = feat + w_k * b_k, k = 1 .. K-1     test_video.py:37-40 (its leading 0 + w_0 * b_0 is w_0 * b_0)
-//   out  = feat * w1 + x * w2                                    test_video.py:44; w1, w2 as in adain_blend_kernel
-// w_k is a scalar (weights_hw == 1) or a per-pixel map W[k][pixel]; the weights are [weights_n][k][weights_hw] on the device and are
-// used as given.  With K = 1 and w_0 = 1 every operation above that adain_blend_kernel lacks is exact: the same bits.
-struct MixArgs {
+//   feat = b_0                                                   one style (StyleTerm::weights == nullptr): nothing is multiplied
+//   feat = w_0 * b_0 ; feat = feat + w_k * b_k, k = 1 .. K-1     a mix, test_video.py:37-40 (its leading 0 + w_0 * b_0 is w_0 * b_0)
+//   out  = feat * w1 + x * w2                                    test.py:70,80, test_video.py:44
+//   alpha mode (pmap == nullptr): w1 = alpha, w2 = one_minus_alpha (computed on the host in double)
+//   pmap  mode                  : w1 = 1 - P[pixel], w2 = P[pixel]      (P broadcast over channels)
+// w_k is a scalar (weights_hw == 1) or a per-pixel map W[k][pixel]; the weights are used as given.
+struct BlendArgs {
     const float* x;
-    const float *c_mean, *c_std, *s_mean, *s_std;   // [n][c], [n][c], [k][c], [k][c]
-    const float* weights;
+    const float *c_mean, *c_std, *s_mean, *s_std;   // [n][c], [n][c], [k][c] or (per_frame) [n][k][c]
+    const float* weights;                           // nullptr: one style, k = 1
     const float* pmap;                              // nullptr: alpha form
     float* out;
-    int c, hw, k, weights_n, weights_hw, pmap_n;
+    int c, hw, k, per_frame, weights_n, weights_hw, pmap_n;
     float alpha, one_minus_alpha;
 };
 
@@ -278,8 +192,9 @@ struct MixArgs {
 // styles' (2 K + 2 b128 loads, once) in registers and then walks pixels with one b128 load and one b128 store each: 8 bytes per
 // element whatever K is.  KB bounds K at compile time so that the statistics are registers, not scratch: 4 (34 VGPRs of statistics)
 // or MIX_MAX_STYLES (130).  A pixel's weights and strength are the same for the lanes of its row (at c = 512 a row is two waves).
+// Mixes only: never launched without weights or with per_frame.
 template <int KB, bool MAPS>
-__global__ __launch_bounds__(256) void adain_mix_walk_kernel(const MixArgs a, int cols_log2, int bpi) {
+__global__ __launch_bounds__(256) void adain_mix_walk_kernel(const BlendArgs a, int cols_log2, int bpi) {
 #pragma clang fp contract(off)
     constexpr int UN = KB <= 4 ? 4 : 2;             // pixels in flight per thread
     const unsigned c = (unsigned)a.c, hw = (unsigned)a.hw;
@@ -340,96 +255,85 @@ __global__ __launch_bounds__(256) void adain_mix_walk_kernel(const MixArgs a, in
     }
 }
 
-// Every other shape, with adain_blend_kernel's indexing: NHWC with any c % 4 == 0 (a quad is four channels of one pixel; the
-// statistics are b128 loads per style and quad) and NCHW (a quad may straddle images, so every element takes its own image).
-template <bool NHWC>
-__global__ __launch_bounds__(256) void adain_mix_flat_kernel(const MixArgs a, size_t total4) {
+// T = f32x4: four consecutive channels from ch of NHWC pixel pix, one b128 load per statistic; T = float: one element.  Of image img.
+template <typename T>
+__device__ __forceinline__ T blend_one(const BlendArgs& a, T v, unsigned img, unsigned ch, unsigned pix) {
 #pragma clang fp contract(off)
     const unsigned c = (unsigned)a.c, hw = (unsigned)a.hw, k = (unsigned)a.k, whw = (unsigned)a.weights_hw;
-    const unsigned per_img = c * hw;
+    const T mc = *(const T*)(a.c_mean + img * c + ch), sc = *(const T*)(a.c_std + img * c + ch);
+    float w1 = a.alpha, w2 = a.one_minus_alpha;
+    if (a.pmap) {
+        const float p = a.pmap[(a.pmap_n == 1 ? 0u : img) * hw + pix];
+        w1 = 1.0f - p;
+        w2 = p;
+    }
+    const unsigned srow = ((a.per_frame ? img : 0u) * k) * c + ch;
+    const float* __restrict__ wp = a.weights ? a.weights + (size_t)(a.weights_n == 1 ? 0u : img) * k * whw + (whw == 1 ? 0u : pix) : nullptr;
+    const T nrm = (v - mc) / sc;
+    T feat{};
+    for (unsigned j = 0; j < k; ++j) {
+        T t = nrm * *(const T*)(a.s_std + srow + j * c) + *(const T*)(a.s_mean + srow + j * c);
+        if (wp) t = t * wp[(size_t)j * whw];
+        feat = j ? feat + t : t;
+    }
+    const T l = feat * w1, r = v * w2;
+    return l + r;
+}
+
+// Every other launch: quads of four elements, 32-bit index arithmetic (the launcher checks total < 2^31).  NHWC with any c % 4 == 0:
+// a quad is four channels of one pixel.  NCHW: the launcher asks n*c*hw % 4 == 0, not c*hw % 4 == 0, so a quad may run over the end
+// of its first element's image (over three of them when c*hw == 1): every element takes its own image, and with it its own style,
+// strength-map and weight rows.
+template <bool NHWC>
+__global__ __launch_bounds__(256) void adain_blend_kernel(const BlendArgs a, size_t total4) {
+    const unsigned c = (unsigned)a.c, hw = (unsigned)a.hw, per_img = c * hw;
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)total4; i += gridDim.x * blockDim.x) {
         const unsigned e = i * 4u;
         const f32x4 v = *(const f32x4*)(a.x + e);
         f32x4 r;
-        const unsigned img = e / per_img;
-        const unsigned rem = e - img * per_img;
+        unsigned img = e / per_img, rem = e - img * per_img;
         if (NHWC) {
-            const unsigned pix = rem / c, ch = rem - pix * c;
-            const f32x4 mc = *(const f32x4*)(a.c_mean + img * c + ch), sc = *(const f32x4*)(a.c_std + img * c + ch);
-            float w1 = a.alpha, w2 = a.one_minus_alpha;
-            if (a.pmap) {
-                const float p = a.pmap[(size_t)(a.pmap_n == 1 ? 0u : img) * hw + pix];
-                w1 = 1.0f - p;
-                w2 = p;
-            }
-            const float* __restrict__ wp = a.weights + (size_t)(a.weights_n == 1 ? 0u : img) * k * whw + (whw == 1 ? 0u : pix);
-            const f32x4 nrm = (v - mc) / sc;
-            f32x4 feat = f32x4{0.f, 0.f, 0.f, 0.f};
-            for (unsigned j = 0; j < k; ++j) {
-                const f32x4 ms = *(const f32x4*)(a.s_mean + j * c + ch), ss = *(const f32x4*)(a.s_std + j * c + ch);
-                const f32x4 t = nrm * ss + ms;
-                const f32x4 wt = t * wp[(size_t)j * whw];
-                feat = j ? feat + wt : wt;
-            }
-            const f32x4 l = feat * w1, rr = v * w2;
-            r = l + rr;
+            r = blend_one(a, v, img, rem % c, rem / c);
         } else {
-            unsigned ik = img, rk = rem;
 #pragma unroll
-            for (int q = 0; q < 4; ++q, ++rk) {
-                if (rk >= per_img) {
-                    rk -= per_img;
-                    ++ik;
+            for (int q = 0; q < 4; ++q, ++rem) {
+                if (rem >= per_img) {
+                    rem -= per_img;
+                    ++img;
                 }
-                const unsigned ch = rk / hw, pix = rk - ch * hw;
-                const float mc = a.c_mean[ik * c + ch], sc = a.c_std[ik * c + ch];
-                float w1 = a.alpha, w2 = a.one_minus_alpha;
-                if (a.pmap) {
-                    const float p = a.pmap[(size_t)(a.pmap_n == 1 ? 0u : ik) * hw + pix];
-                    w1 = 1.0f - p;
-                    w2 = p;
-                }
-                const float* __restrict__ wp = a.weights + (size_t)(a.weights_n == 1 ? 0u : ik) * k * whw + (whw == 1 ? 0u : pix);
-                const float nrm = (v[q] - mc) / sc;
-                float feat = 0.f;
-                for (unsigned j = 0; j < k; ++j) {
-                    const float t = nrm * a.s_std[j * c + ch] + a.s_mean[j * c + ch];
-                    const float wt = t * wp[(size_t)j * whw];
-                    feat = j ? feat + wt : wt;
-                }
-                const float l = feat * w1, rr = v[q] * w2;
-                r[q] = l + rr;
+                r[q] = blend_one(a, v[q], img, rem / hw, rem % hw);
             }
         }
         *(f32x4*)(a.out + e) = r;
     }
 }
 
-// host only, no HIP call: the argument rules of adain_blend_mix (and of the blend inside adain_stylize_u8_mix)
-int check_adain_blend_mix(int nhwc, int n, int c, int hw, int k, int weights_n, int weights_hw, int has_pmap, int pmap_n) {
-    if (n < 1 || c < 1 || hw < 1) { set_error("adain_blend_mix: bad shape n=%d c=%d hw=%d", n, c, hw); return -1; }
-    if (k < 1 || k > MIX_MAX_STYLES) { set_error("adain_blend_mix: %d styles (1..%d)", k, MIX_MAX_STYLES); return -1; }
-    if (weights_n != 1 && weights_n != n) { set_error("adain_blend_mix: weights batch %d must be 1 or %d", weights_n, n); return -1; }
-    if (weights_hw != 1 && weights_hw != hw) { set_error("adain_blend_mix: weights per style %d must be 1 or %d (hw)", weights_hw, hw); return -1; }
-    if (has_pmap && pmap_n != 1 && pmap_n != n) { set_error("adain_blend_mix: pmap batch %d must be 1 or %d", pmap_n, n); return -1; }
+int check_adain_blend(const char* what, int nhwc, int n, int c, int hw, const StyleTerm& st, const BlendTerm& b) {
+    if (n < 1 || c < 1 || hw < 1) { set_error("%s: bad shape n=%d c=%d hw=%d", what, n, c, hw); return -1; }
+    if (st.k < 1 || st.k > MIX_MAX_STYLES) { set_error("%s: %d styles (1..%d)", what, st.k, MIX_MAX_STYLES); return -1; }
+    if (st.weights ? st.per_frame : st.k != 1) { set_error("%s: a mix needs weights and one set of styles for all frames", what); return -1; }
+    if (st.weights && st.weights_n != 1 && st.weights_n != n) { set_error("%s: weights batch %d must be 1 or %d", what, st.weights_n, n); return -1; }
+    if (st.weights && st.weights_hw != 1 && st.weights_hw != hw) { set_error("%s: weights per style %d must be 1 or %d (hw)", what, st.weights_hw, hw); return -1; }
+    if (b.pmap && b.pmap_n != 1 && b.pmap_n != n) { set_error("%s: pmap batch %d must be 1 or %d", what, b.pmap_n, n); return -1; }
     const size_t total = (size_t)n * c * hw;
-    if (nhwc ? (c & 3) : (total & 3)) { set_error("adain_blend_mix: element count / channels must be a multiple of 4"); return -1; }
-    if (total >= 0x7fffffffULL) { set_error("adain_blend_mix: more than 2^31 elements per call"); return -1; }
+    if (nhwc ? (c & 3) : (total & 3)) { set_error("%s: element count / channels must be a multiple of 4", what); return -1; }
+    if (total >= 0x7fffffffULL) { set_error("%s: more than 2^31 elements per call", what); return -1; }
     return 0;
 }
 
 // Launcher branches:
-//   NHWC, c / 4 a power of two <= 256 (c = 4 .. 1024; the product's 512): adain_mix_walk_kernel, KB = 4 for k <= 4 and MIX_MAX_STYLES
-//     above, scalar weights or maps; ceil(pixel rows / 8) workgroups per image, at most 2048 / n (at least 1): more pixels per thread
-//     on large maps, so that the statistics' loads stay a small share
-//   any other NHWC c, and NCHW: adain_mix_flat_kernel, at most 8192 workgroups, grid-stride
-int launch_adain_blend_mix(const float* content, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const float* s_mean,
-                           const float* s_std, int k, const float* weights, int weights_n, int weights_hw, float alpha, float one_minus_alpha,
-                           const float* pmap, int pmap_n, float* out, hipStream_t s) {
-    if (check_adain_blend_mix(nhwc, n, c, hw, k, weights_n, weights_hw, pmap != nullptr, pmap_n)) return -1;
-    const MixArgs a{content, c_mean, c_std, s_mean, s_std, weights, pmap, out, c, hw, k, weights_n, weights_hw, pmap_n, alpha, one_minus_alpha};
+//   a mix, NHWC, c / 4 a power of two <= 256 (c = 4 .. 1024; the product's 512): adain_mix_walk_kernel, KB = 4 for k <= 4 and
+//     MIX_MAX_STYLES above, scalar weights or maps; ceil(pixel rows / 8) workgroups per image, at most 2048 / n (at least 1): more
+//     pixels per thread on large maps, so that the statistics' loads stay a small share
+//   one style, any other NHWC c, and NCHW: adain_blend_kernel, at most 8192 workgroups, grid-stride
+int launch_adain_blend(const float* content, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const StyleTerm& st,
+                       const BlendTerm& b, float* out, hipStream_t s) {
+    const char* what = st.weights ? "adain_blend_mix" : "adain_blend";
+    if (check_adain_blend(what, nhwc, n, c, hw, st, b)) return -1;
+    const BlendArgs a{content, c_mean, c_std, st.s_mean, st.s_std, st.weights, b.pmap, out, c, hw, st.k, st.per_frame, st.weights_n, st.weights_hw,
+                      b.pmap_n, b.alpha, b.one_minus_alpha};
     const int cols = c >> 2;
-    if (nhwc && cols <= 256 && (cols & (cols - 1)) == 0) {
+    if (st.weights && nhwc && cols <= 256 && (cols & (cols - 1)) == 0) {
         int cols_log2 = 0;
         while ((1 << cols_log2) < cols) ++cols_log2;
         const int rows = 256 / cols;
@@ -438,21 +342,21 @@ int launch_adain_blend_mix(const float* content, int nhwc, int n, int c, int hw,
         const int cap = n < 2048 ? 2048 / n : 1;
         if (bpi > cap) bpi = cap;
         const dim3 grid((unsigned)((size_t)n * bpi));
-        const bool maps = weights_hw != 1;
-        if (k <= 4) {
+        const bool maps = st.weights_hw != 1;
+        if (st.k <= 4) {
             if (maps) hipLaunchKernelGGL((adain_mix_walk_kernel<4, true>), grid, dim3(256), 0, s, a, cols_log2, bpi);
             else hipLaunchKernelGGL((adain_mix_walk_kernel<4, false>), grid, dim3(256), 0, s, a, cols_log2, bpi);
         } else {
             if (maps) hipLaunchKernelGGL((adain_mix_walk_kernel<MIX_MAX_STYLES, true>), grid, dim3(256), 0, s, a, cols_log2, bpi);
             else hipLaunchKernelGGL((adain_mix_walk_kernel<MIX_MAX_STYLES, false>), grid, dim3(256), 0, s, a, cols_log2, bpi);
         }
-        return check_launch("adain_blend_mix");
+        return check_launch(what);
     }
     const size_t total4 = (size_t)n * c * hw / 4;
     const unsigned blocks = (unsigned)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
-    if (nhwc) hipLaunchKernelGGL(adain_mix_flat_kernel<true>, dim3(blocks), dim3(256), 0, s, a, total4);
-    else hipLaunchKernelGGL(adain_mix_flat_kernel<false>, dim3(blocks), dim3(256), 0, s, a, total4);
-    return check_launch("adain_blend_mix");
+    if (nhwc) hipLaunchKernelGGL(adain_blend_kernel<true>, dim3(blocks), dim3(256), 0, s, a, total4);
+    else hipLaunchKernelGGL(adain_blend_kernel<false>, dim3(blocks), dim3(256), 0, s, a, total4);
+    return check_launch(what);
 }
 
 }  // namespace adain

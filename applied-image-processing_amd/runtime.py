@@ -421,14 +421,23 @@ def mean_std(feat, nhwc, eps=1e-5):
     return mean, std
 
 
+def _blend(name, x, nhwc, c_mean, c_std, term):
+    """The blends' common call: ``term(x, n, c, hw)`` checks and returns the arguments between ``c_std`` and ``out`` (tensors as they
+    are, so that they live until the call is made)."""
+    x = device_tensor(x, "content_feat")
+    if x.dim() != 4:
+        raise AdainHipError(f"{name}: expected a 4-D feature tensor, got {tuple(x.shape)}")
+    n, c, hw = _feat_dims(x, nhwc)
+    args = term(x, n, c, hw)
+    out = torch.empty_like(x)
+    call("adain_" + name, x.device, x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(),
+         *(a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args), out.data_ptr())
+    return out
+
+
 def blend_alpha(x, nhwc, c_mean, c_std, s_mean, s_std, alpha):
     """AdaIN(x) * alpha + x * (1 - alpha);  alpha = 1 gives plain adaptive_instance_normalization."""
-    x = device_tensor(x, "content_feat")
-    n, c, hw = _feat_dims(x, nhwc)
-    out = torch.empty_like(x)
-    call("adain_blend_alpha", x.device, x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(), s_mean.data_ptr(),
-         s_std.data_ptr(), s_mean.shape[0], float(alpha), float(1 - alpha), out.data_ptr())
-    return out
+    return _blend("blend_alpha", x, nhwc, c_mean, c_std, lambda x, n, c, hw: (s_mean, s_std, s_mean.shape[0], float(alpha), float(1 - alpha)))
 
 
 def _pmap(pmap, hw, what):
@@ -442,13 +451,7 @@ def _pmap(pmap, hw, what):
 
 def blend_pmap(x, nhwc, c_mean, c_std, s_mean, s_std, pmap):
     """AdaIN(x) * (1 - P) + x * P with P [pn, hc, wc] (pn in {1, n})."""
-    x = device_tensor(x, "content_feat")
-    n, c, hw = _feat_dims(x, nhwc)
-    pmap, pn = _pmap(pmap, hw, "blend_pmap")
-    out = torch.empty_like(x)
-    call("adain_blend_pmap", x.device, x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(), s_mean.data_ptr(),
-         s_std.data_ptr(), s_mean.shape[0], pmap.data_ptr(), pn, out.data_ptr())
-    return out
+    return _blend("blend_pmap", x, nhwc, c_mean, c_std, lambda x, n, c, hw: (s_mean, s_std, s_mean.shape[0]) + _pmap(pmap, hw, "blend_pmap"))
 
 
 MIX_MAX_STYLES = 16          # ADAIN_MIX_MAX_STYLES
@@ -473,26 +476,19 @@ def blend_mix(x, nhwc, c_mean, c_std, s_mean, s_std, weights, alpha=None, pmap=N
     used as given.  Exactly one of ``alpha`` and ``pmap``."""
     if (alpha is None) == (pmap is None):
         raise AdainHipError("blend_mix: exactly one of alpha and pmap")
-    x = device_tensor(x, "content_feat")
-    if x.dim() != 4:
-        raise AdainHipError(f"blend_mix: expected a 4-D feature tensor, got {tuple(x.shape)}")
-    n, c, hw = _feat_dims(x, nhwc)
-    hc, wc = (x.shape[1], x.shape[2]) if nhwc else (x.shape[2], x.shape[3])
-    s_mean, s_std = device_tensor(s_mean, "s_mean"), device_tensor(s_std, "s_std")
-    k = s_mean.numel() // c
-    if not 1 <= k <= MIX_MAX_STYLES or s_mean.numel() != k * c or s_std.numel() != k * c:
-        raise AdainHipError(f"blend_mix: style statistics must be [K,{c}] each with 1 <= K <= {MIX_MAX_STYLES}, got {tuple(s_mean.shape)}, "
-                            f"{tuple(s_std.shape)}")
-    weights, wn, whw = mix_weights(weights, n, k, hc, wc, x.device, "blend_mix")
-    p_ptr, pn = None, 1
-    if pmap is not None:
-        pmap, pn = _pmap(pmap, hw, "blend_mix")
-        p_ptr = pmap.data_ptr()
-    a = 0.0 if alpha is None else float(alpha)
-    out = torch.empty_like(x)
-    call("adain_blend_mix", x.device, x.data_ptr(), int(nhwc), n, c, hw, c_mean.data_ptr(), c_std.data_ptr(), s_mean.data_ptr(), s_std.data_ptr(),
-         k, weights.data_ptr(), wn, whw, a, float(1 - a), p_ptr, pn, out.data_ptr())
-    return out
+
+    def term(x, n, c, hw):
+        hc, wc = (x.shape[1], x.shape[2]) if nhwc else (x.shape[2], x.shape[3])
+        sm, sd = device_tensor(s_mean, "s_mean"), device_tensor(s_std, "s_std")
+        k = sm.numel() // c
+        if not 1 <= k <= MIX_MAX_STYLES or sm.numel() != k * c or sd.numel() != k * c:
+            raise AdainHipError(f"blend_mix: style statistics must be [K,{c}] each with 1 <= K <= {MIX_MAX_STYLES}, got {tuple(sm.shape)}, "
+                                f"{tuple(sd.shape)}")
+        a = 0.0 if alpha is None else float(alpha)
+        return (sm, sd, k) + mix_weights(weights, n, k, hc, wc, x.device, "blend_mix") + (a, float(1 - a)) + (
+            (None, 1) if pmap is None else _pmap(pmap, hw, "blend_mix"))
+
+    return _blend("blend_mix", x, nhwc, c_mean, c_std, term)
 
 
 def strength_map(depth, hc, wc, offset, prominence):

@@ -6,9 +6,9 @@ distinct per image, channel AND style; behind the K style rows one more row offs
 1000s, so that a read past ``k`` or past ``weights_n`` is not the value in front of it - with the weights in [0.05, 0.9], and the
 float32 form is first held within mix_ref.self_distance_bound of the float64 form: nothing cancels.
 
-Launcher branches (csrc/stats.hip, launch_adain_blend_mix) and the shapes that walk them:
+Launcher branches (csrc/stats.hip, launch_adain_blend with weights) and the shapes that walk them:
   * NHWC with c / 4 a power of two <= 256 -> the pixel-walk kernel: (3,4,5) (256 pixel rows, one quad column), (4,64,1), the product
-    shapes (2,512,9) and (1,512,1), (2,1024,3) (the widest: one pixel row);  other NHWC c -> the flat kernel: (3,12,5), (2,520,7),
+    shapes (2,512,9) and (1,512,1), (2,1024,3) (the widest: one pixel row);  other NHWC c -> the flat kernel (adain_blend_kernel, the single-style blend's): (3,12,5), (2,520,7),
     (2,1028,3) (257 quads), (2,2048,3) (a power of two, but 512 quads);  NCHW -> the flat kernel, quads straddling images or not.
   * K buckets of the walk kernel: k <= 4 keeps 4 styles' statistics in registers (4 pixels in flight), k > 4 sixteen (2 in flight):
     K = 1, 2, 3, 4 | 5, 16 on every walk shape.  hw = 9 runs the unrolled loop once and the tail once (4 in flight), twice and once (2).

@@ -39,7 +39,7 @@ for rep in range(3):
     cf, sf = rt.encode_multi([c, s], eng.enc)
     sm, ss = rt.mean_std(sf, True)                           # mean_std_nhwc_partial + mean_std_finalize
     cm, cs = rt.mean_std(cf, True)
-    g = rt.blend_alpha(cf, True, cm, cs, sm, ss, 0.5)        # adain_blend_kernel<nhwc>
+    g = rt.blend_alpha(cf, True, cm, cs, sm, ss, 0.5)        # adain_blend_kernel<nhwc> (one style: no weights)
     out = rt.decode(g, eng.dec)
     frames = u8(7, 2, 1200, 1600)
     f8 = rt.encode_u8(frames, eng.enc)                       # conv_first_kernel<true>; 300 x 400 / 150 x 200 maps: 16 x 16 tiles

@@ -8,9 +8,12 @@
 Expected from the bytes moved, not measured: (b) moves the 8 bytes per element of (a) whatever K is ((c) adds 4 K bytes per PIXEL,
 1/512 of that per element), (d) about (3 K + 2) / 2 times as many.
 HIP events around each call, medians and interquartile ranges of --reps calls after 20 warm-up calls; shader clock and power over each
-shape's window.  Prints one JSON line and, with --out, writes it to a file.
-Usage: python tools/mix_bench.py [--reps 200] [--out profiles/mix_bench.json]"""
+shape's window; each row also carries the sha256 of its last call's output bytes, so that two builds of the library (--lib PATH: that
+build in place of the package's own) can be held to the same bytes as well as the same time.  Prints one JSON line and, with --out,
+writes it to a file.
+Usage: python tools/mix_bench.py [--reps 200] [--lib PATH] [--out profiles/mix_bench.json]"""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -29,9 +32,10 @@ KS = [1, 2, 4, 16]
 C = 512
 
 
-def summary(times):
+def summary(times, out):
     q = statistics.quantiles(times, n=4)
-    return {"median_ms": round(statistics.median(times), 4), "iqr_ms": [round(q[0], 4), round(q[2], 4)]}
+    return {"median_ms": round(statistics.median(times), 4), "iqr_ms": [round(q[0], 4), round(q[2], 4)],
+            "sha256": hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()}
 
 
 def event_ms(fn, reps, warmup=20):
@@ -42,11 +46,11 @@ def event_ms(fn, reps, warmup=20):
     for _ in range(reps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        fn()
+        out = fn()
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b))
-    return summary(times)
+    return summary(times, out)
 
 
 def emulation(x, cm, cs, sm, ss, w, alpha):
@@ -65,14 +69,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--lib", type=str, default=None)
     args = ap.parse_args()
+    if args.lib:
+        rt.use_library(os.path.abspath(args.lib))
     assert torch.cuda.is_available(), "mix_bench needs a GPU"
     torch.cuda.set_device(0)
     reps = max(args.reps, 8)
     g = torch.Generator().manual_seed(0)
     rand = lambda *s: torch.rand(*s, generator=g).cuda()
     tel = GpuTelemetry(0).start()
-    res = {"device": torch.cuda.get_device_name(0), "reps": reps, "channels": C, "shapes": {}}
+    res = {"device": torch.cuda.get_device_name(0), "reps": reps, "lib": os.path.relpath(rt.LIB_PATH), "channels": C, "shapes": {}}
     for name, n, hc, wc in SHAPES:
         x = (rand(n, hc, wc, C) * 4 - 2).contiguous()
         cm, cs = rand(n, C), rand(n, C) + 0.5
