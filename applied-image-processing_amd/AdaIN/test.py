@@ -142,24 +142,63 @@ def _transform_window(w, h, size, crop):
     return (nw, nh), (int(round((nh - size) / 2.0)), int(round((nw - size) / 2.0)), size, size)
 
 
+def _device_plan(w, h, size, crop):
+    """((new width, new height), crop window | None) when the device runs ``test_transform_u8(size, crop)`` of a w x h RGB image, else None."""
+    plan = _transform_window(w, h, size, crop)
+    if plan is None:
+        return None
+    (nw, nh), _ = plan
+    if w > 256 * nw or h > 256 * nh:            # beyond the device resize's supported shrink factor: Pillow on the host
+        return None
+    return plan
+
+
+def _device_resize(x, w, h, plan):
+    """uint8 [1,h,w,3] on the device -> Resize [+ CenterCrop] of ``plan`` there."""
+    (nw, nh), win = plan
+    if (nw, nh) == (w, h):                      # Image.resize to the size it has is a copy
+        if win is None:
+            return x
+        return x[:, win[0]:win[0] + win[2], win[1]:win[1] + win[3]].contiguous()
+    return rt.resize_pil_bilinear_u8(x, (nw, nh), crop=win)
+
+
 def device_transform_u8(img, size, crop, device, mark=None):
     """``test_transform_u8(size, crop)(img)`` for an RGB PIL image, computed on the device: uint8 [1,h,w,3], byte for byte what PIL's
     resize + crop give (tests/test_gpu_resize_pil.py).  None for anything else (RGBA, L, ...: Pillow resizes those through other
     paths - premultiplied alpha for RGBA -, they keep the host transform)."""
     if getattr(img, "mode", None) != "RGB":
         return None
-    plan = _transform_window(img.size[0], img.size[1], size, crop)
+    plan = _device_plan(img.size[0], img.size[1], size, crop)
     if plan is None:
         return None
-    (nw, nh), win = plan
-    if img.size[0] > 256 * nw or img.size[1] > 256 * nh:      # beyond the device resize's supported shrink factor: Pillow on the host
+    return _device_resize(_upload_rgb(img, device, mark), img.size[0], img.size[1], plan)
+
+
+def device_decode_transform_u8(path, size, crop, device, mark=None):
+    """``device_transform_u8`` of the colour JPEG file at ``path`` without PIL: the file's bytes go up, the frame is decoded on the
+    device (adain_jpeg_decode_u8: Pillow's pixels) and resized there.  None when the file is not a three-component baseline JPEG the
+    decoder takes, or did not decode cleanly, or the transform is not the device's: the caller takes the PIL path."""
+    from .. import jpeg_file
+
+    with open(str(path), "rb") as f:
+        data = f.read()
+    try:
+        parsed = jpeg_file.parse(data)
+    except jpeg_file.UnsupportedJpeg:
         return None
-    x = _upload_rgb(img, device, mark)
-    if (nw, nh) == img.size:                    # Image.resize to the size it has is a copy
-        if win is None:
-            return x
-        return x[:, win[0]:win[0] + win[2], win[1]:win[1] + win[3]].contiguous()
-    return rt.resize_pil_bilinear_u8(x, (nw, nh), crop=win)
+    if parsed.c != 3:                           # PIL opens a grey file as mode L, which keeps the host transform
+        return None
+    plan = _device_plan(parsed.w, parsed.h, size, crop)
+    if plan is None:
+        return None
+    if mark is not None:
+        with torch.cuda.device(device):
+            mark()
+    out, record = rt.jpeg_decode_batch([parsed], [data], device)
+    if record[0, 0].item() != 0:
+        return None
+    return _device_resize(out, parsed.w, parsed.h, plan)
 
 
 def save_image(tensor, path):
@@ -266,6 +305,20 @@ def set_device_jpeg(enabled):
     extension is saved by PIL as before.  Default False.  Returns the previous setting."""
     global _device_jpeg_on
     prev, _device_jpeg_on = _device_jpeg_on, bool(enabled)
+    return prev
+
+
+_device_jpeg_decode_on = False
+
+
+def set_device_jpeg_decode(enabled):
+    """True: the cached per-call path of ``adain_inference`` reads the bytes of a content given as a ``.jpg`` / ``.jpeg`` path, decodes
+    them on the device (adain_jpeg_decode_u8: the pixels Pillow decodes) and resizes that frame there, instead of decoding with PIL and
+    uploading the pixels.  A file the decoder does not take (progressive, restart markers, grey, ...: jpeg_file.parse) or that does not
+    decode cleanly, a PIL image passed in by the caller and any other extension take the PIL path as before.  The output file does not
+    change.  Default False.  Returns the previous setting."""
+    global _device_jpeg_decode_on
+    prev, _device_jpeg_decode_on = _device_jpeg_decode_on, bool(enabled)
     return prev
 
 
@@ -632,6 +685,12 @@ def _content_frame(content_img, content_size, crop, device, call):
     T = _stage_timer
     t0 = time.perf_counter()
     pil_content = call.pil_content = _open(content_img)
+    if _device_jpeg_decode_on and (type(content_img) == str or isinstance(content_img, Path)) and _is_jpeg_path(content_img):
+        e0 = torch.cuda.Event(enable_timing=True) if T.on else None
+        frame = device_decode_transform_u8(content_img, content_size, crop, device, e0.record if T.on else None)
+        if frame is not None:                                        # (pil_content stays lazily opened: decoded only if a depth provider asks)
+            T("read + decode + resize content (device)", t0)
+            return frame, e0
     pil_content.load()                                               # decode (a lazily opened file) - host work that stays
     T("open + decode content (PIL)", t0)
     t0 = time.perf_counter()

@@ -67,6 +67,17 @@
 //   merge      one workgroup per 512 pixels of an output row, a lane per chroma column (two pixels): upsampling and colour conversion into an
 //              LDS image of the row segment laid out at the destination's byte phase, which leaves as aligned dwords with byte stores at
 //              its two ends only - any destination address and any 3 w row stride
+//
+// The file decoder (adain_jpeg_decode_u8): a baseline file's entropy-coded segment -> the pixels Pillow decodes from the file.  Its rule list
+// and its stages stand in front of its kernels below ("the file decoder"); in short
+//   taken     8-bit sequential Huffman files, one interleaved scan, grey or YCbCr with luma 1 x 1 / 2 x 1 / 2 x 2, no restart interval;
+//             the host (jpeg_file.py) walks the markers, refuses everything else and packs the file's tables into one blob
+//   entropy   the unstuffed stream is cut into subsequences; their exit states (bit position, block in the MCU, zigzag index) are iterated
+//             inside one workgroup per file until a round changes none - the fixed point is the sequential decoder's, whatever the data -
+//             then every subsequence writes its coefficients in parallel; garbage is decoded without leaving a buffer: a code in no table
+//             costs one bit, a run past 63 ends the block, the reader pads with 1-bits, every index is clamped
+//   status    per file: 0, or the stream did not hold exactly the expected blocks ending inside its last byte (the caller then uses PIL)
+//   back half the round trip's, with the file's own quantisation tables, three chroma layouts and a grey path
 #include "common.h"
 
 namespace adain {
@@ -762,6 +773,434 @@ __global__ __launch_bounds__(MERGE_PX / 2) void jpeg_merge_kernel(const uint8_t*
     }
 }
 
+// ---- the file decoder: a baseline file's entropy-coded segment -> pixels -----------------------------------------------------------------
+// adain_jpeg_decode_u8.  The host (jpeg_file.py) walks the markers and hands over the file's bytes, where its entropy-coded segment lies
+// and one blob of tables (FileTables); everything behind that runs here.  tests/jpeg_file_ref.py restates it in Python.
+//
+// Its rules
+//   files     no restart interval (the host refuses a DRI other than 0: RSTn markers are not removed here), one scan, 8-bit tables
+//   stream    the segment with the 00 behind every FF removed; bits big-endian; the reader returns 1-bits past its end
+//   symbol    libjpeg's look-up: the next 8 bits index look[] (length << 8 | symbol); a longer code is the first length l in 9..16 with
+//             code <= maxcode[l], its symbol val[(valoff[l] + code) & 255]; when no length matches ONE bit is consumed and nothing else
+//             changes (garbage is the normal case in round 0 of the decode, and a damaged file must not hang or leave its buffers)
+//   DC        zigzag index 0: symbol & 15 = size s, then s bits v; difference = v when v >= 2^(s-1), else v - 2^s + 1; the index becomes 1
+//   AC        symbol = run r << 4 | size s.  s = 0: r = 15 moves the index 16 on, any other r ends the block.  s > 0: the coefficient at
+//             index + r (past 63: not written), the index moves behind it.  An index of 64 or more ends the block
+//   blocks    per MCU the H x V luma blocks row-major, then Cb, Cr (grey: one block per MCU); a finished block moves on to the next
+//   status    0, or: a code that is in no table, a DC size above 11, an AC size above 10 or a coefficient past 63 in one of the expected
+//             blocks; a DC sum outside -2047..2047; fewer blocks than expected; a last block that does not end inside the last byte; a
+//             decode that did not settle.  Blocks beyond the expected count are decoded by nobody.
+//   DC        the differences are summed per component in scan order, kept as int16
+//   samples   coefficient times the FILE's table entry of its component, then the IDCT of the round trip above, unchanged
+//   chroma    cropped to the real samples first (ch x cw; 4:2:0: ceil(h/2) x ceil(w/2), 4:2:2: h x ceil(w/2), 4:4:4: h x w).
+//             4:2:0: h2v2_fancy_upsample as in the round trip.  4:2:2: h2v1_fancy_upsample - out[2c] = (3 C[c] + C[c-1] + 1) >> 2,
+//             out[2c+1] = (3 C[c] + C[c+1] + 2) >> 2, the column clamped to 0..cw-1 (which gives libjpeg's end cases out[0] = C[0] and
+//             out[2cw-1] = C[cw-1]).  Both: cw <= 2 (w <= 4) leaves the filter out and replicates every sample.  4:4:4: fullsize_upsample,
+//             the samples themselves.  Grey: the luma plane is the output.
+//
+// Its stages (one workgroup per file where a stage is sequential in the file, otherwise one launch over all files)
+//   table     the host's segment offsets and lengths reach the device as kernel arguments, 64 files per launch
+//   unstuff   per 4096-byte piece: count the stuffed zeros, scan, scatter; the tail of the stream is filled with FF
+//   settle    the stream is cut into subsequences of chunk_bits bits.  Round 0: every lane decodes its subsequence from the all-zero state
+//             at its first bit until its position passes the subsequence's end, and stores its exit state (position, block in the MCU,
+//             zigzag index).  Round r: lane s decodes subsequence s again from lane s - 1's exit state of round r - 1 (lane 0: from the
+//             true start) - or copies its own, when that input did not change.  The loop ends after the first round that changed no exit
+//             state, at most subsequences + 1 rounds.  The states then satisfy exit[s] = decode(s, exit[s-1]) for every s, a system with
+//             one solution: the sequential decoder's.  No luck is involved, a periodic stream only takes more rounds.  Two state arrays
+//             alternate, a workgroup barrier separates the rounds, nothing waits on another workgroup.  The blocks each subsequence
+//             begins are counted on the way and scanned at the end.
+//   write     fully parallel: every subsequence once more from its now known state and block index, the coefficients de-zigzagged as
+//             int16 into the zero-filled buffer, each by exactly one lane, DC terms as differences
+//   dc        per component the running sum in scan order; the record (status, rounds) is written here
+//   idct / pixels   as in the round trip, with the file's tables and the three layouts
+constexpr int DEC_THREADS = 1024;       // of the per-file workgroups (unstuff, settle, dc)
+constexpr int DEC_SEG_BATCH = 64;       // files per launch of the table kernel
+constexpr int DEC_DEFAULT_CHUNK_BITS = 1024;
+
+struct HuffTab {
+    uint16_t look[256];
+    int32_t maxcode[18];
+    int32_t valoff[18];
+    uint8_t val[256];
+};
+struct FileTables {             // the blob of jpeg_file.py
+    HuffTab huff[4];            // DC0, DC1, AC0, AC1
+    uint8_t q[3][64];           // per component, natural order
+    uint8_t sel[8];             // DC table of components 0..2, AC table of components 0..2
+};
+static_assert(sizeof(HuffTab) == 912 && sizeof(FileTables) == 3848, "the blob layout of jpeg_file.py");
+
+struct DecSeg { uint64_t off; uint32_t len, pad; };
+struct DecSegBatch { uint64_t off[DEC_SEG_BATCH]; uint32_t len[DEC_SEG_BATCH]; };
+struct DecMeta { uint32_t ulen, rounds, settled, err, endpos, pad[3]; };        // per file, in the workspace
+
+struct DecPlan {
+    int c, H, V, bpm, mw, mh, yw, yh, cw, chh;        // luma blocks per MCU H x V; plane sizes in samples (whole blocks)
+    size_t nblk, o_cb, o_cr, plane_stride;
+    uint32_t cap_words, nsub_max, chunk_bits;
+    size_t o_seg, o_meta, o_stream, o_state, o_count, o_coef, o_planes, total;
+};
+
+const char* check_decode_shape(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits) {
+    if (n < 1 || n > 65535) return "n outside 1..65535";
+    if (c != 1 && c != 3) return "components other than 1 (grey) and 3 (YCbCr)";
+    if (h < 1 || h > 65535 || w < 1 || w > 65535) return "height or width outside 1..65535";
+    if (sampling < 0 || sampling > 2 || (c == 1 && sampling != 0)) return "sampling other than 0 (4:4:4, grey), 1 (4:2:2) and 2 (4:2:0)";
+    if (max_segment_bytes >= ((size_t)1 << 28)) return "a segment of 2^28 bytes or more";
+    if (chunk_bits != 0 && (chunk_bits < 32 || chunk_bits % 32 != 0)) return "chunk_bits that is neither 0 nor a multiple of 32 from 32 up";
+    return nullptr;
+}
+
+DecPlan make_decode_plan(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits) {
+    DecPlan p{};
+    p.c = c;
+    p.H = sampling >= 1 ? 2 : 1, p.V = sampling == 2 ? 2 : 1;
+    p.bpm = c == 3 ? p.H * p.V + 2 : 1;
+    p.mw = (w + 8 * p.H - 1) / (8 * p.H), p.mh = (h + 8 * p.V - 1) / (8 * p.V);
+    p.nblk = (size_t)p.mw * p.mh * p.bpm;
+    p.yw = p.mw * p.H * 8, p.yh = p.mh * p.V * 8;
+    p.cw = c == 3 ? p.mw * 8 : 0, p.chh = c == 3 ? p.mh * 8 : 0;
+    p.o_cb = (size_t)p.yw * p.yh;
+    p.o_cr = p.o_cb + (size_t)p.cw * p.chh;
+    p.plane_stride = p.nblk * 64;
+    p.chunk_bits = chunk_bits ? (uint32_t)chunk_bits : (uint32_t)DEC_DEFAULT_CHUNK_BITS;
+    p.cap_words = (uint32_t)((max_segment_bytes + 3) / 4 + 3);
+    p.nsub_max = (uint32_t)((max_segment_bytes * 8 + p.chunk_bits - 1) / p.chunk_bits);
+    if (p.nsub_max == 0) p.nsub_max = 1;
+    size_t at = 0, N = (size_t)n;
+    auto take = [&](size_t bytes) { size_t o = at; at = align256(at + bytes); return o; };
+    p.o_seg = take(N * sizeof(DecSeg));
+    p.o_meta = take(N * sizeof(DecMeta));
+    p.o_stream = take(N * p.cap_words * sizeof(uint32_t));
+    p.o_state = take(3 * N * p.nsub_max * sizeof(uint2));
+    p.o_count = take(N * p.nsub_max * sizeof(uint32_t));
+    p.o_coef = take(N * p.nblk * 64 * sizeof(int16_t));
+    p.o_planes = take(N * p.plane_stride);
+    p.total = at;
+    return p;
+}
+
+__global__ void jpegd_table_kernel(DecSegBatch b, int first, int count, DecSeg* __restrict__ seg, DecMeta* __restrict__ meta) {
+    const int i = threadIdx.x;
+    if (i >= count) return;
+    seg[first + i] = DecSeg{b.off[i], b.len[i], 0u};
+    meta[first + i] = DecMeta{0u, 0u, 0u, 0u, 0xffffffffu, {0u, 0u, 0u}};
+}
+
+// inclusive sum over the DEC_THREADS threads of a workgroup; part: 16 uint32 of LDS
+__device__ __forceinline__ uint32_t decode_inclusive(uint32_t v, uint32_t* part) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(v, d);
+        if (lane >= d) v += up;
+    }
+    __syncthreads();                                   // the previous pass has read part
+    if (lane == 63) part[wv] = v;
+    __syncthreads();
+    for (int k = 0; k < wv; ++k) v += part[k];
+    return v;
+}
+
+// One workgroup per file: stream byte j = the j-th byte of the segment that is not a 00 behind an FF; then FF up to a whole word plus 8 bytes.
+__global__ __launch_bounds__(DEC_THREADS) void jpegd_unstuff_kernel(const uint8_t* __restrict__ files, const DecSeg* __restrict__ seg, DecMeta* __restrict__ meta,
+                                                                    uint8_t* __restrict__ stream, uint32_t cap_words) {
+    __shared__ uint32_t part[16];
+    const size_t f = blockIdx.x;
+    const uint8_t* src = files + seg[f].off;
+    const uint32_t len = seg[f].len;
+    uint8_t* out = stream + f * cap_words * 4;          // len + 12 <= 4 cap_words
+    uint32_t carry = 0;                                 // stream bytes written by the pieces before
+    for (uint32_t base = 0; base < len; base += DEC_THREADS * 4) {
+        const uint32_t i0 = base + threadIdx.x * 4;
+        uint8_t b[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const uint32_t i = i0 + k;                  // b[0] is the byte before the thread's four
+            b[k] = (i >= 1 && i - 1 < len) ? src[i - 1] : (uint8_t)0;
+        }
+        uint32_t keep = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) keep += (i0 + k < len && !(b[k + 1] == 0 && b[k] == 0xff && i0 + k >= 1)) ? 1u : 0u;
+        const uint32_t incl = decode_inclusive(keep, part);
+        uint32_t at = carry + incl - keep;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i0 + k < len && !(b[k + 1] == 0 && b[k] == 0xff && i0 + k >= 1)) out[at++] = b[k + 1];
+        __syncthreads();
+        if (threadIdx.x == DEC_THREADS - 1) part[15] = incl;          // wave 15's slot is read only by waves above it: none
+        __syncthreads();
+        carry += part[15];
+    }
+    const uint32_t end = ((carry + 3) & ~3u) + 8;
+    for (uint32_t i = carry + threadIdx.x; i < end; i += DEC_THREADS) out[i] = 0xff;
+    if (threadIdx.x == 0) meta[f].ulen = carry;
+}
+
+// 32 bits of the stream at bit position pos (big-endian); the stream holds FF bytes past its end, and the word index is clamped
+__device__ __forceinline__ uint32_t peek32(const uint32_t* __restrict__ s, uint32_t last_word, uint32_t pos) {
+    const uint32_t wi = min(pos >> 5, last_word - 1);
+    const uint64_t v = ((uint64_t)__builtin_bswap32(s[wi]) << 32) | __builtin_bswap32(s[wi + 1]);
+    return (uint32_t)((v << (pos & 31)) >> 32);
+}
+
+// (length << 8) | symbol of the code at the top of `bits`, 0 when none matches
+__device__ __forceinline__ uint32_t huff_symbol(const HuffTab& t, uint32_t bits) {
+    const uint32_t e = t.look[bits >> 24];
+    if (e) return e;
+    for (int l = 9; l <= 16; ++l) {
+        const int code = (int)(bits >> (32 - l));
+        if (code <= t.maxcode[l]) return ((uint32_t)l << 8) | t.val[(t.valoff[l] + code) & 255];
+    }
+    return 0;
+}
+
+struct DecShape { int H, V, bpm, c; size_t nblk; };
+
+// Decodes from state st = (position, block in MCU << 8 | zigzag index) while position < end; returns the exit state and counts the
+// blocks begun.  WRITE: b is the index of the block current at st; coefficients of blocks below nblk go to coef (natural order).
+template <bool WRITE>
+__device__ __forceinline__ uint2 decode_span(const uint32_t* __restrict__ s, uint32_t last_word, uint32_t end, uint2 st, const FileTables& T_, const DecShape& g,
+                                             uint32_t* begun, int16_t* __restrict__ coef, long long b, DecMeta* __restrict__ meta) {
+    uint32_t pos = st.x, blk = st.y >> 8, zz = st.y & 255, nb = 0;
+    blk = blk < (uint32_t)g.bpm ? blk : 0;
+    while (pos < end) {
+        const int comp = g.c == 3 && (int)blk >= g.H * g.V ? (int)blk - g.H * g.V + 1 : 0;
+        const uint32_t bits = peek32(s, last_word, pos);
+        const bool live = WRITE && b >= 0 && (size_t)b < g.nblk;
+        const uint32_t e = huff_symbol(T_.huff[zz == 0 ? (T_.sel[comp] & 1) : 2 + (T_.sel[3 + comp] & 1)], bits);
+        if (e == 0) {
+            pos += 1;
+            if (live) meta->err = 1;
+            continue;
+        }
+        const uint32_t len = e >> 8, sym = e & 255, sz = sym & 15;
+        // the value bits: len + sz <= 31
+        const uint32_t v = sz ? (bits << len) >> (32 - sz) : 0u;
+        const int value = (sz == 0 || v >= (1u << (sz - 1))) ? (int)v : (int)v - (1 << sz) + 1;
+        if (zz == 0) {
+            ++nb;
+            pos += len + sz;
+            if (live) {
+                coef[(size_t)b * 64] = (int16_t)value;
+                if (sym > 11) meta->err = 1;
+            }
+            zz = 1;
+        } else if (sz == 0) {
+            pos += len;
+            zz = (sym >> 4) == 15 ? zz + 16 : 64;
+        } else {
+            pos += len + sz;
+            const uint32_t k = zz + (sym >> 4);
+            if (live) {
+                if (k <= 63) coef[(size_t)b * 64 + T.zigzag[k]] = (int16_t)value;
+                if (k > 63 || sz > 10) meta->err = 1;
+            }
+            zz = k + 1;
+        }
+        if (zz >= 64) {
+            if (live && (size_t)b == g.nblk - 1) meta->endpos = pos;
+            zz = 0, blk = blk + 1 == (uint32_t)g.bpm ? 0 : blk + 1, ++b;
+        }
+    }
+    *begun = nb;
+    return make_uint2(pos, (blk << 8) | zz);
+}
+
+__device__ __forceinline__ void load_tables(FileTables* dst, const uint8_t* __restrict__ blob) {
+    for (int i = threadIdx.x; i < (int)sizeof(FileTables); i += blockDim.x) ((uint8_t*)dst)[i] = blob[i];
+    __syncthreads();
+}
+
+// One workgroup per file: the rounds, then the scan of the block counts (count[s] becomes the blocks begun before subsequence s).
+__global__ __launch_bounds__(DEC_THREADS) void jpegd_settle_kernel(const uint8_t* __restrict__ blobs, const uint32_t* __restrict__ stream, uint32_t cap_words,
+                                                                   DecMeta* __restrict__ meta, uint2* __restrict__ state, uint32_t* __restrict__ count,
+                                                                   uint32_t nsub_max, uint32_t chunk_bits, DecShape g) {
+    __shared__ FileTables ft;
+    __shared__ uint32_t part[16];
+    __shared__ int changed[2];
+    const size_t f = blockIdx.x;
+    const int t = threadIdx.x;
+    load_tables(&ft, blobs + f * sizeof(FileTables));
+    const uint32_t* s = stream + f * cap_words;
+    const uint32_t nbits = min(meta[f].ulen, (cap_words - 3) * 4) * 8;
+    const uint32_t nsub = (uint32_t)(((uint64_t)nbits + chunk_bits - 1) / chunk_bits);      // <= nsub_max
+    uint2* st[2] = {state + f * 3 * nsub_max, state + (f * 3 + 1) * nsub_max};
+    uint2* last_in = state + (f * 3 + 2) * nsub_max;    // the state each subsequence was last decoded from: read and written by its lane only
+    uint32_t* cnt = count + f * nsub_max;
+    uint32_t rounds = 0, settled = 0;
+    for (uint32_t r = 0; r <= nsub; ++r) {              // at most nsub + 1 rounds
+        if (t == 0) changed[r & 1] = 0;
+        __syncthreads();
+        uint2* cur = st[r & 1];                         // written in this round, by lane i at i only
+        const uint2* prev = st[(r & 1) ^ 1];            // the exit states of round r - 1: only read in this round
+        int any = 0;
+        for (uint32_t i = t; i < nsub; i += DEC_THREADS) {
+            const uint32_t begin = i * chunk_bits, end = min(begin + chunk_bits, nbits);
+            const uint2 in = (r == 0 || i == 0) ? make_uint2(begin, 0u) : prev[i - 1];
+            uint2 out;
+            if (r > 0 && last_in[i].x == in.x && last_in[i].y == in.y) {
+                out = prev[i];                          // the same input as last time: the same exit state
+            } else {
+                uint32_t nb = 0;
+                out = decode_span<false>(s, cap_words - 1, end, in, ft, g, &nb, nullptr, 0, nullptr);
+                cnt[i] = nb;
+                last_in[i] = in;
+                if (r > 0 && (out.x != prev[i].x || out.y != prev[i].y)) any = 1;
+            }
+            cur[i] = out;
+        }
+        if (any) changed[r & 1] = 1;
+        __syncthreads();
+        ++rounds;
+        if (r > 0 && !changed[r & 1]) { settled = 1; break; }
+    }
+    if (nsub == 0) settled = 1;
+    // exclusive scan of the counts
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nsub; base += DEC_THREADS) {
+        const uint32_t i = base + t;
+        const uint32_t v = i < nsub ? cnt[i] : 0u;
+        const uint32_t incl = decode_inclusive(v, part);
+        if (i < nsub) cnt[i] = carry + incl - v;
+        __syncthreads();
+        if (t == DEC_THREADS - 1) part[15] = incl;
+        __syncthreads();
+        carry += part[15];
+    }
+    if (t == 0) meta[f].rounds = rounds, meta[f].settled = settled;
+}
+
+__global__ __launch_bounds__(256) void jpegd_write_kernel(const uint8_t* __restrict__ blobs, const uint32_t* __restrict__ stream, uint32_t cap_words,
+                                                          DecMeta* __restrict__ meta, const uint2* __restrict__ state, const uint32_t* __restrict__ count,
+                                                          uint32_t nsub_max, uint32_t chunk_bits, DecShape g, int16_t* __restrict__ coef) {
+    __shared__ FileTables ft;
+    const size_t f = blockIdx.y;
+    load_tables(&ft, blobs + f * sizeof(FileTables));
+    const uint32_t nbits = min(meta[f].ulen, (cap_words - 3) * 4) * 8;
+    const uint32_t nsub = (uint32_t)(((uint64_t)nbits + chunk_bits - 1) / chunk_bits);
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nsub) return;
+    const uint2* exit_state = state + f * 3 * nsub_max;         // both arrays hold the settled states
+    const uint2 in = i == 0 ? make_uint2(0u, 0u) : exit_state[i - 1];
+    const long long b = (long long)count[f * nsub_max + i] - ((in.y & 255) ? 1 : 0);       // a block under way was begun further left
+    uint32_t nb;
+    decode_span<true>(stream + f * cap_words, cap_words - 1, min((i + 1) * chunk_bits, nbits), in, ft, g, &nb, coef + f * g.nblk * 64, b, meta + f);
+}
+
+// One workgroup per file: DC differences -> DC terms per component in scan order, then the file's record.
+__global__ __launch_bounds__(DEC_THREADS) void jpegd_dc_kernel(int16_t* __restrict__ coef, const DecMeta* __restrict__ meta, DecShape g, int32_t* __restrict__ record) {
+    __shared__ uint32_t part[16];
+    __shared__ int range_err;
+    const size_t f = blockIdx.x;
+    const int t = threadIdx.x, hv = g.H * g.V;
+    int16_t* fc = coef + f * g.nblk * 64;
+    const size_t nmcu = g.nblk / g.bpm;
+    if (t == 0) range_err = 0;
+    int bad = 0;
+    for (int comp = 0; comp < g.c; ++comp) {
+        const size_t cnt = comp == 0 ? nmcu * hv : nmcu;
+        const size_t per = (cnt + DEC_THREADS - 1) / DEC_THREADS;
+        const size_t a = min((size_t)t * per, cnt), e = min(a + per, cnt);
+        auto block_of = [&](size_t i) { return comp == 0 ? (i / hv) * g.bpm + i % hv : i * g.bpm + hv + comp - 1; };
+        int sum = 0;
+        for (size_t i = a; i < e; ++i) sum += fc[block_of(i) * 64];
+        int run = (int)decode_inclusive((uint32_t)sum, part) - sum;
+        for (size_t i = a; i < e; ++i) {
+            run += fc[block_of(i) * 64];
+            if (run > 2047 || run < -2047) bad = 1;
+            fc[block_of(i) * 64] = (int16_t)run;
+        }
+    }
+    __syncthreads();
+    if (bad) range_err = 1;
+    __syncthreads();
+    if (t == 0) {
+        const DecMeta m = meta[f];
+        const uint32_t nbits = m.ulen * 8;
+        const bool ok = m.settled && !m.err && !range_err && m.endpos != 0xffffffffu && m.endpos <= nbits && m.endpos + 8 > nbits;
+        record[2 * f] = ok ? 0 : 1;
+        record[2 * f + 1] = (int32_t)m.rounds;
+    }
+}
+
+struct DecPlanes { int c, H, V, bpm, mw, yw, cw; size_t nblk, o_cb, o_cr, stride; };
+
+// The round trip's IDCT stage on natural-order coefficients with the file's own tables; the planes are whole blocks, Y [8 V mh][8 H mw]
+// first, then (colour) Cb and Cr [8 mh][8 mw].
+__global__ __launch_bounds__(IDCT_PER_WG * 8) void jpegd_idct_kernel(const int16_t* __restrict__ coef, const uint8_t* __restrict__ blobs, uint8_t* __restrict__ planes,
+                                                                     DecPlanes g) {
+    constexpr int NB = IDCT_PER_WG, THREADS = NB * 8;
+    __shared__ int samp[NB * 72];
+    __shared__ int q[192];
+    const int t = threadIdx.x, hv = g.H * g.V;
+    const size_t f = blockIdx.y, b0 = (size_t)blockIdx.x * NB;
+    const int count = (int)min((size_t)NB, g.nblk - b0);
+    if (t < 192) q[t] = blobs[f * sizeof(FileTables) + offsetof(FileTables, q) + t];
+    __syncthreads();
+    const uint32_t* s32 = (const uint32_t*)(coef + (f * g.nblk + b0) * 64);
+    for (int i = t; i < count * 32; i += THREADS) {
+        const uint32_t v = s32[i];
+        const int blk = i >> 5, n0 = (i & 31) * 2;
+        const int j = (int)((b0 + blk) % g.bpm);
+        const int* qt = q + (j < hv ? 0 : j - hv + 1) * 64;
+        int* p = samp + blk * 72 + (n0 >> 3) * 9 + (n0 & 7);
+        p[0] = (int)(int16_t)(v & 0xffff) * qt[n0];
+        p[1] = (int)(int16_t)(v >> 16) * qt[n0 + 1];
+    }
+    __syncthreads();
+    const int blk = t >> 3, k = t & 7;
+    if (blk < count) idct_pass<9, 11>(samp + blk * 72 + k);
+    __syncthreads();
+    if (blk < count) {
+        int* p = samp + blk * 72 + k * 9;
+        idct_pass<1, 18>(p);
+        uint2 out;
+        out.x = range_limit(p[0]) | range_limit(p[1]) << 8 | range_limit(p[2]) << 16 | range_limit(p[3]) << 24;
+        out.y = range_limit(p[4]) | range_limit(p[5]) << 8 | range_limit(p[6]) << 16 | range_limit(p[7]) << 24;
+        const size_t b = b0 + blk, m = b / g.bpm, my = m / g.mw, mx = m - my * g.mw;
+        const int j = (int)(b - m * g.bpm);
+        size_t at;
+        if (j < hv) at = ((my * g.V + j / g.H) * 8 + k) * g.yw + (mx * g.H + j % g.H) * 8;
+        else at = (j == hv ? g.o_cb : g.o_cr) + (my * 8 + k) * g.cw + mx * 8;
+        *(uint2*)(planes + f * g.stride + at) = out;
+    }
+}
+
+// One lane per pixel.  C = 1: the luma sample; C = 3: upsampling by the file's layout (g.H, g.V) and libjpeg's YCbCr -> RGB.
+template <int C>
+__global__ __launch_bounds__(256) void jpegd_pixels_kernel(const uint8_t* __restrict__ planes, DecPlanes g, int h, int w, uint8_t* __restrict__ dst) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    const uint8_t* fp = planes + (size_t)blockIdx.z * g.stride;
+    uint8_t* d = dst + (((size_t)blockIdx.z * h + y) * w + x) * C;
+    const int yy = fp[(size_t)y * g.yw + x];
+    if (C == 1) { d[0] = (uint8_t)yy; return; }
+    const int ch = g.V == 2 ? (h + 1) >> 1 : h, cw = g.H == 2 ? (w + 1) >> 1 : w;
+    const int r = g.V == 2 ? y >> 1 : y, cc = g.H == 2 ? x >> 1 : x;
+    int uv[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint8_t* pl = fp + (k ? g.o_cr : g.o_cb);
+        const uint8_t* a = pl + (size_t)r * g.cw;
+        if (g.H == 1 || cw <= 2) {
+            uv[k] = a[cc];                              // fullsize_upsample, or the narrow case: replication
+        } else {
+            const int cn = (x & 1) ? min(cc + 1, cw - 1) : max(cc - 1, 0);
+            if (g.V == 2) {
+                const int rn = (y & 1) ? min(r + 1, ch - 1) : max(r - 1, 0);
+                const uint8_t* b = pl + (size_t)rn * g.cw;
+                uv[k] = (3 * (3 * a[cc] + b[cc]) + 3 * a[cn] + b[cn] + ((x & 1) ? 7 : 8)) >> 4;
+            } else {
+                uv[k] = (3 * a[cc] + a[cn] + ((x & 1) ? 2 : 1)) >> 2;
+            }
+        }
+    }
+    const int u = uv[0] - 128, v = uv[1] - 128;
+    d[0] = (uint8_t)clamp_u8(yy + ((91881 * v + 32768) >> 16));
+    d[1] = (uint8_t)clamp_u8(yy + ((-22554 * u - 46802 * v + 32768) >> 16));
+    d[2] = (uint8_t)clamp_u8(yy + ((116130 * u + 32768) >> 16));
+}
+
 const char* check_shape(int n, int h, int w, int c, int quality) {
     if (n < 1) return "n < 1";
     if (c != 1 && c != 3) return "channels other than 1 (L) and 3 (RGB)";
@@ -845,6 +1284,60 @@ int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int
     else
         jpeg_merge_kernel<1><<<grid, MERGE_PX / 2, 0, s>>>(planes, g, h, w, dst);
     return check_launch("jpeg_roundtrip_u8");
+}
+
+int jpeg_decode_bytes(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes) {
+    const char* bad = check_decode_shape(n, h, w, c, sampling, max_segment_bytes, chunk_bits);
+    if (bad) { set_error("jpeg_decode_u8: %s (n %d, %d x %d x %d, sampling %d, segment %zu, chunk_bits %d)", bad, n, h, w, c, sampling, max_segment_bytes, chunk_bits); return -1; }
+    if (workspace_bytes) *workspace_bytes = make_decode_plan(n, h, w, c, sampling, max_segment_bytes, chunk_bits).total;
+    return 0;
+}
+
+int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, const uint64_t* seg_offsets,
+                          const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace, size_t workspace_bytes, int chunk_bits, hipStream_t s) {
+    const char* bad = check_decode_shape(n, h, w, c, sampling, 0, chunk_bits);
+    if (bad) { set_error("jpeg_decode_u8: %s (n %d, %d x %d x %d, sampling %d, chunk_bits %d)", bad, n, h, w, c, sampling, chunk_bits); return -1; }
+    size_t longest = 0;
+    for (int i = 0; i < n; ++i) {
+        if (seg_offsets[i] > files_bytes || seg_lengths[i] > files_bytes - seg_offsets[i]) {
+            set_error("jpeg_decode_u8: segment %d (%llu + %u bytes) leaves the %zu bytes of files", i, (unsigned long long)seg_offsets[i], seg_lengths[i], files_bytes);
+            return -1;
+        }
+        longest = seg_lengths[i] > longest ? seg_lengths[i] : longest;
+    }
+    if ((bad = check_decode_shape(n, h, w, c, sampling, longest, chunk_bits))) { set_error("jpeg_decode_u8: %s", bad); return -1; }
+    if ((uintptr_t)workspace % 8 || (uintptr_t)record % 4) { set_error("jpeg_decode_u8: the workspace must be 8-byte and the record 4-byte aligned"); return -1; }
+    const DecPlan p = make_decode_plan(n, h, w, c, sampling, longest, chunk_bits);
+    if (workspace_bytes < p.total) { set_error("jpeg_decode_u8: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return -1; }
+    if ((p.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull) { set_error("jpeg_decode_u8: %d x %d: too many blocks for one launch", h, w); return -1; }
+    char* ws = (char*)workspace;
+    DecSeg* seg = (DecSeg*)(ws + p.o_seg);
+    DecMeta* meta = (DecMeta*)(ws + p.o_meta);
+    uint32_t* stream = (uint32_t*)(ws + p.o_stream);
+    uint2* state = (uint2*)(ws + p.o_state);
+    uint32_t* count = (uint32_t*)(ws + p.o_count);
+    int16_t* coef = (int16_t*)(ws + p.o_coef);
+    uint8_t* planes = (uint8_t*)(ws + p.o_planes);
+    const DecShape g{p.H, p.V, p.bpm, p.c, p.nblk};
+    const DecPlanes pg{p.c, p.H, p.V, p.bpm, p.mw, p.yw, p.cw, p.nblk, p.o_cb, p.o_cr, p.plane_stride};
+    for (int first = 0; first < n; first += DEC_SEG_BATCH) {
+        DecSegBatch b{};
+        const int count_ = n - first < DEC_SEG_BATCH ? n - first : DEC_SEG_BATCH;
+        for (int i = 0; i < count_; ++i) b.off[i] = seg_offsets[first + i], b.len[i] = seg_lengths[first + i];
+        jpegd_table_kernel<<<1, DEC_SEG_BATCH, 0, s>>>(b, first, count_, seg, meta);
+    }
+    jpegd_unstuff_kernel<<<n, DEC_THREADS, 0, s>>>(files, seg, meta, (uint8_t*)stream, p.cap_words);
+    if (hipMemsetAsync(coef, 0, (size_t)n * p.nblk * 64 * sizeof(int16_t), s) != hipSuccess) { set_error("jpeg_decode_u8: hipMemsetAsync failed"); return -1; }
+    jpegd_settle_kernel<<<n, DEC_THREADS, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g);
+    jpegd_write_kernel<<<dim3((p.nsub_max + 255) / 256, n), 256, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, coef);
+    jpegd_dc_kernel<<<n, DEC_THREADS, 0, s>>>(coef, meta, g, record);
+    jpegd_idct_kernel<<<dim3((unsigned)((p.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG), n), IDCT_PER_WG * 8, 0, s>>>(coef, blobs, planes, pg);
+    const dim3 grid((w + 255) / 256, h, n);
+    if (c == 3)
+        jpegd_pixels_kernel<3><<<grid, 256, 0, s>>>(planes, pg, h, w, dst);
+    else
+        jpegd_pixels_kernel<1><<<grid, 256, 0, s>>>(planes, pg, h, w, dst);
+    return check_launch("jpeg_decode_u8");
 }
 
 }  // namespace adain

@@ -101,6 +101,9 @@ SIGNATURES = {
     "adain_jpeg_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_roundtrip_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_roundtrip_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_jpeg_decode_u8_bytes": (_c_int, [_c_int] * 5 + [_c_size_t, _c_int, ctypes.POINTER(_c_size_t)]),
+    "adain_jpeg_decode_u8": (_c_int, [_c_void_p, _c_size_t, _c_void_p] + [_c_int] * 5 + [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                      _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p]),
     "adain_nhwc_to_nchw": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_nchw_to_nhwc": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_conv3x3_wino4_packed_floats": (_c_size_t, [_c_int, _c_int]),
@@ -884,6 +887,139 @@ def jpeg_roundtrip_u8(u8, quality=JPEG_DEFAULT_QUALITY):
         out = torch.empty_like(x)
         _launch("adain_jpeg_roundtrip_u8", x.data_ptr(), n, h, w, c, quality, out.data_ptr(), ws.data_ptr(), ws.numel())
     return out.reshape(u8.shape)
+
+
+# --- input files (adain_jpeg_decode_u8) -----------------------------------------------------------------------------------------------
+def jpeg_decode_sizes(n, h, w, c, sampling, max_segment_bytes, chunk_bits=0):
+    """workspace_bytes of adain_jpeg_decode_u8_bytes: the scratch of an n-file call whose longest entropy-coded segment has
+    ``max_segment_bytes``.  Host only.  AdainHipError for a refused shape."""
+    ws = _c_size_t()
+    rc = lib().adain_jpeg_decode_u8_bytes(int(n), int(h), int(w), int(c), int(sampling), int(max_segment_bytes), int(chunk_bits), ctypes.byref(ws))
+    if rc != 0:
+        raise _failure("adain_jpeg_decode_u8_bytes", rc)
+    return ws.value
+
+
+_jpeg_decode_lock = threading.Lock()
+
+
+def jpeg_decode_upload(parsed, datas, device, lead=0):
+    """The one upload of a ``jpeg_decode_batch`` call: the table blobs of n files of ONE geometry, ``lead`` spare bytes, then their
+    entropy-coded segments back to back -> (device uint8 tensor, segment offsets behind the blobs, segment lengths)."""
+    from . import jpeg_file
+
+    n = len(parsed)
+    if n < 1 or any(p.geometry != parsed[0].geometry for p in parsed) or len(datas) != n:
+        raise AdainHipError("jpeg_decode_batch: expected the files of one geometry")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise AdainHipError("jpeg_decode_u8: expected a GPU device (the device decoder has no CPU form)")
+    blobs = n * jpeg_file.BLOB_BYTES
+    lengths = [p.seg_length for p in parsed]
+    offsets = [lead + sum(lengths[:i]) for i in range(n)]
+    host = bytearray(blobs + lead + sum(lengths) + 1)           # one spare byte: the pointer behind the blobs stays inside the tensor
+    for i, (p, d) in enumerate(zip(parsed, datas)):
+        host[i * jpeg_file.BLOB_BYTES:(i + 1) * jpeg_file.BLOB_BYTES] = p.blob
+        host[blobs + offsets[i]:blobs + offsets[i] + lengths[i]] = d[p.seg_offset:p.seg_offset + p.seg_length]
+    return torch.frombuffer(host, dtype=torch.uint8).to(device), offsets, lengths
+
+
+def jpeg_decode_launch(up, offsets, lengths, geometry, chunk_bits=0):
+    """adain_jpeg_decode_u8 on an upload of ``jpeg_decode_upload`` -> (frames uint8 [n,h,w,c], record int32 [n,2]) on its device."""
+    from . import jpeg_file
+
+    n = len(lengths)
+    h, w, c, sampling = geometry
+    blobs = n * jpeg_file.BLOB_BYTES
+    off = (ctypes.c_uint64 * n)(*offsets)
+    ln = (ctypes.c_uint32 * n)(*lengths)
+    # the workspace is shared per stream: calls from several threads (the video path's fetch pool) on one stream must not interleave
+    with _jpeg_decode_lock, scratch(up.device, "jpeg_decode", jpeg_decode_sizes, n, h, w, c, sampling, max(lengths), chunk_bits) as ws:
+        out = torch.empty((n, h, w, c), dtype=torch.uint8, device=up.device)
+        record = torch.empty((n, 2), dtype=torch.int32, device=up.device)
+        _launch("adain_jpeg_decode_u8", up.data_ptr() + blobs, up.numel() - blobs, up.data_ptr(), n, h, w, c, sampling, off, ln, out.data_ptr(),
+                record.data_ptr(), ws.data_ptr(), ws.numel(), int(chunk_bits))
+    return out, record
+
+
+def jpeg_decode_batch(parsed, datas, device, chunk_bits=0, lead=0):
+    """``parsed``: jpeg_file.JpegFile of n files of ONE geometry, ``datas``: their bytes -> (frames uint8 [n,h,w,c], record int32 [n,2]:
+    status and rounds per file), both on ``device``.  One upload - the table blobs, ``lead`` spare bytes, then the entropy-coded
+    segments back to back at whatever byte offsets that gives - and one call of adain_jpeg_decode_u8; nothing comes back and nothing
+    waits.  A frame whose status is not 0 is unspecified."""
+    up, offsets, lengths = jpeg_decode_upload(parsed, datas, device, lead)
+    return jpeg_decode_launch(up, offsets, lengths, parsed[0].geometry, chunk_bits)
+
+
+def _pil_pixels(data, mode):
+    import io
+
+    import numpy as np
+    from PIL import Image
+
+    img = Image.open(io.BytesIO(data))
+    return np.asarray(img.convert(mode) if mode is not None else img)
+
+
+def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None):
+    """The bytes of image files (a list, or one ``bytes``) -> device uint8 tensors (a list, or one): per file the array
+    ``np.asarray(Image.open(io.BytesIO(data)))`` gives - [h,w,3] for a colour file, [h,w] for a grey one - or, with ``mode`` "RGB" / "L",
+    ``np.asarray(Image.open(...).convert(mode))`` (a grey file is replicated for "RGB"; "L" from a colour file goes to the host).  Baseline
+    JPEG files are decoded on the device (adain_jpeg_decode_u8; grouped by geometry, one call and one upload per group, the record
+    read once); whatever jpeg_file.parse refuses, and any file whose status comes back non-zero, is decoded by PIL on the host exactly
+    as before and uploaded - PIL's exceptions pass through.  ``report`` (a list): per file "device" or "host: <why>", and the rounds."""
+    from . import jpeg_file
+
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    datas = [bytes(files)] if single else [bytes(f) for f in files]
+    device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+    if mode not in (None, "RGB", "L"):
+        raise AdainHipError(f"jpeg_decode_u8: mode must be None, 'RGB' or 'L', got {mode!r}")
+    results, why, rounds, groups = [None] * len(datas), [None] * len(datas), [0] * len(datas), {}
+    for i, d in enumerate(datas):
+        try:
+            p = jpeg_file.parse(d)
+            if mode == "L" and p.c == 3:
+                raise jpeg_file.UnsupportedJpeg("a colour file where grey is wanted")
+            groups.setdefault(p.geometry, []).append((i, p))
+        except jpeg_file.UnsupportedJpeg as e:
+            why[i] = str(e)
+    launched = [(members, jpeg_decode_batch([p for _, p in members], [datas[i] for i, _ in members], device, chunk_bits)) for members in groups.values()]
+    for members, (out, record) in launched:
+        rec = record.cpu().tolist()                      # the one read of the record: waits for the call
+        for k, (i, p) in enumerate(members):
+            rounds[i] = rec[k][1]
+            if rec[k][0] != 0:
+                why[i] = "the entropy-coded data did not decode cleanly"
+                continue
+            frame = out[k]
+            results[i] = frame[..., 0] if p.c == 1 and mode != "RGB" else frame.expand(-1, -1, 3).contiguous() if p.c == 1 else frame
+    for i, d in enumerate(datas):
+        if results[i] is None:
+            results[i] = torch.from_numpy(_pil_pixels(d, mode).copy()).to(device)
+    if report is not None:
+        report[:] = [{"path": "device" if why[i] is None else "host: " + why[i], "rounds": rounds[i]} for i in range(len(datas))]
+    return results[0] if single else results
+
+
+def jpeg_decode_rgb_file(path, device):
+    """The frame ``np.asarray(Image.open(path).convert("RGB"))`` as a uint8 [h,w,3] tensor on ``device``, decoded there - or None when
+    the file is not one the device decoder takes (not a .jpg / .jpeg name, refused by jpeg_file.parse, a non-zero status): the caller
+    then decodes it with PIL as before.  Reads the record once (waits for the call)."""
+    from . import jpeg_file
+
+    if not str(path).lower().endswith((".jpg", ".jpeg")) or torch.device(device).type != "cuda":
+        return None
+    with open(str(path), "rb") as f:
+        data = f.read()
+    try:
+        parsed = jpeg_file.parse(data)
+    except jpeg_file.UnsupportedJpeg:
+        return None
+    out, record = jpeg_decode_batch([parsed], [data], device)
+    if record[0, 0].item() != 0:
+        return None
+    return out[0].expand(-1, -1, 3).contiguous() if parsed.c == 1 else out[0]
 
 
 def nhwc_to_nchw(x):

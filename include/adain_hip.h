@@ -484,6 +484,38 @@ ADAIN_API int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* 
 ADAIN_API int adain_jpeg_roundtrip_u8(const uint8_t* src_u8, int n, int h, int w, int c, int quality, uint8_t* dst_u8, void* workspace,
                                       size_t workspace_bytes, adain_stream_t stream);
 
+/* ---- the callers' input files: baseline JPEG files decoded on the device, pixel for pixel what Pillow's Image.open gives ----------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * n files of ONE geometry: height h, width w, c components (1: grey, 3: YCbCr) and luma sampling (0: 1 x 1 - 4:4:4 and grey, 1: 2 x 1 -
+ * 4:2:2, 2: 2 x 2 - 4:2:0; chroma 1 x 1), 8-bit baseline or extended-sequential Huffman, one interleaved scan, no restart interval.  The
+ * host walks the markers (jpeg_file.py does; a file it refuses stays with the host decoder) and hands over
+ *   files, files_bytes   device memory that holds the files' bytes, at any address
+ *   segment_offsets, segment_lengths   HOST arrays [n]: where file i's entropy-coded segment (behind SOS, in front of EOI, stuffed) lies in
+ *     `files` and how long it is; they are read before the call returns
+ *   blobs   device memory, n x 3848 bytes, any address: file i's tables - four Huffman tables DC0, DC1, AC0, AC1 of 912 bytes (look[256]
+ *     uint16: (code length << 8) | symbol for the next 8 bits of the stream, 0: none that short; maxcode[18] int32 by length, -1: none;
+ *     valoff[18] int32: index of the length's first symbol minus its first code; val[256] uint8: HUFFVAL), q[3][64] uint8: each
+ *     component's quantisation table in natural order, sel[8] uint8: the DC table of components 0..2, the AC table of components 0..2, 0, 0
+ *   dst   HWC uint8 [n][h][w][c], any address: frame i = np.asarray(Image.open(file i)) (established against Pillow 12.2.0 built with
+ *     libjpeg-turbo; the rules are listed in csrc/jpeg.hip and restated in tests/jpeg_file_ref.py)
+ *   record   device int32 [n][2]: file i's status and the rounds its entropy decode took.  Status 0: decoded.  Non-zero: the entropy data
+ *     did not decode to exactly the expected number of blocks ending inside the last byte, or held a code or value no 8-bit baseline
+ *     encoder writes; that frame's content is then unspecified (its writes stay inside dst) and the caller decodes the file on the host
+ *   chunk_bits   the bits of one subsequence of the parallel entropy decode: 0 for the default (1024), else a multiple of 32 from 32 up.
+ *     The pixels do not depend on it, nor on the batch, the stream or the device: integer arithmetic throughout.
+ * The entropy decode trusts no self-synchronisation: the exit states of the subsequences are iterated to their fixed point, which is the
+ * sequential decoder's, in at most (subsequences + 1) rounds inside one workgroup per file.  No copy to the host, no wait.
+ * adain_jpeg_decode_u8_bytes (host only): *workspace_bytes for n files whose longest segment is max_segment_bytes.  The output may be NULL.
+ * Refused with ADAIN_EINVAL before anything is launched: a null pointer, c other than 1 and 3, sampling outside 0..2 or not 0 for
+ * c = 1, h or w outside 1..65535, n outside 1..65535, a chunk_bits that is neither 0 nor a multiple of 32 from 32 up, a segment that
+ * leaves `files` or is 2^28 bytes or longer, a workspace_bytes below the query's for the longest segment, a workspace that is not
+ * 8-byte aligned or a record that is not 4-byte aligned.  7 kernel launches, one memset and one more launch per 64 files per call. */
+ADAIN_API int adain_jpeg_decode_u8_bytes(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits,
+                                         size_t* workspace_bytes);
+ADAIN_API int adain_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling,
+                                   const uint64_t* segment_offsets, const uint32_t* segment_lengths, uint8_t* dst_u8, int32_t* record,
+                                   void* workspace, size_t workspace_bytes, int chunk_bits, adain_stream_t stream);
+
 /* ---- layout changes at the boundary ([n][c][hw] <-> [n][hw][c]) ------------------------------------------ */
 ADAIN_API int adain_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, adain_stream_t stream);
 ADAIN_API int adain_nchw_to_nhwc(const float* in, float* out, int n, int c, int hw, adain_stream_t stream);

@@ -1,0 +1,449 @@
+"""The device JPEG file decoder (csrc/jpeg.hip, adain_jpeg_decode_u8) and its callers.  Everything here is element-for-element equality:
+the device's pixels against Pillow's ``np.asarray(Image.open(...))`` for the same bytes and, in tests of their own, against the Python
+restatement (tests/jpeg_file_ref.py) - a failure of the second kind says the kernel moved, of the first kind alone that the
+environment's Pillow / libjpeg did.  Then the chunk size of the parallel entropy decode, constant frames (periodic streams), batch
+independence and misaligned uploads, the memory contract through the guard-band arena (tests/abi_arena.py), damaged entropy data, and the
+callers: ``adain_inference`` with ``set_device_jpeg_decode`` and the video path with ``jpeg_decode_on_device``."""
+import ctypes
+import functools
+import glob
+import io
+import os
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import abi_arena as A
+import jpeg_file_ref as R
+import jpeg_ref as J
+from conftest import ROOT
+from test_jpeg_file_host import LAYOUTS, QUALITIES, SHAPES, pillow, save
+
+import applied_image_processing_amd.jpeg_file as F
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "jpeg", "*.jpg")))        # the only files read here
+_arena_passed = set()
+
+
+@pytest.fixture(scope="module")
+def rt():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import applied_image_processing_amd.runtime as rt
+
+    rt.lib()
+    torch.cuda.set_device(0)
+    return rt
+
+
+def first_difference(got, want):
+    """Names the first differing pixel (row, column) and channel of two frames [h,w,3] / [h,w]."""
+    assert got.shape == want.shape and got.dtype == want.dtype == np.uint8, f"{got.shape} {got.dtype} against {want.shape} {want.dtype}"
+    at = np.argwhere(got != want)
+    if len(at) == 0:
+        return None
+    i = tuple(int(v) for v in at[0])
+    return (f"{len(at)} of {got.size} elements differ; the first at pixel (row {i[0]}, column {i[1]}), channel {i[2] if len(i) > 2 else 0}: "
+            f"{got[i]} against {want[i]}")
+
+
+@functools.lru_cache(maxsize=None)
+def files_of(h, w):
+    """(name, bytes) of every host case of one shape: contents x layouts x (qualities + optimised tables)."""
+    out = []
+    for kind in J.CONTENTS:
+        for layout in LAYOUTS:
+            a = J.content(kind, h, w, 1 if layout == "L" else 3)
+            out += [(f"{kind} {h}x{w} layout {layout} q{q}", save(a, q, layout)) for q in QUALITIES]
+            out.append((f"{kind} {h}x{w} layout {layout} optimize", save(a, 75, layout, optimize=True)))
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def restatement(data):
+    """Computed once per file, shared by the tests and never written to."""
+    px, status, _ = R.decode(data)
+    assert status == 0
+    px.setflags(write=False)
+    return px
+
+
+def device_pixels(rt, datas, **kw):
+    """The frames of the files as numpy arrays, every one decoded ON THE DEVICE (a fallback to PIL fails the test), and the rounds."""
+    report = []
+    out = rt.jpeg_decode_u8(list(datas), DEV, report=report, **kw)
+    assert [r["path"] for r in report] == ["device"] * len(datas), report
+    assert all(o.is_cuda and o.dtype == torch.uint8 for o in out)
+    return [o.cpu().numpy() for o in out], [r["rounds"] for r in report]
+
+
+@pytest.mark.parametrize("h,w", SHAPES)
+def test_device_pixels_are_pillows(rt, h, w):
+    names, datas = zip(*files_of(h, w))
+    got, _ = device_pixels(rt, datas)
+    for name, data, g in zip(names, datas, got):
+        bad = first_difference(g, pillow(data))
+        assert bad is None, f"{name}: {bad}"
+
+
+@pytest.mark.parametrize("h,w", SHAPES)
+def test_device_pixels_are_the_restatements(rt, h, w):
+    names, datas = zip(*files_of(h, w))
+    got, _ = device_pixels(rt, datas)
+    for name, data, g in zip(names, datas, got):
+        bad = first_difference(g, restatement(data))
+        assert bad is None, f"{name}: {bad}"
+
+
+@pytest.mark.parametrize("path", GOLDEN, ids=os.path.basename)
+def test_other_encoders_files_against_pillow(rt, path):
+    data = open(path, "rb").read()
+    (got,), _ = device_pixels(rt, [data])
+    bad = first_difference(got, pillow(data))
+    assert bad is None, f"{os.path.basename(path)}: {bad}"
+
+
+@pytest.mark.parametrize("path", GOLDEN, ids=os.path.basename)
+def test_other_encoders_files_against_the_restatement(rt, path):
+    data = open(path, "rb").read()
+    (got,), _ = device_pixels(rt, [data])
+    bad = first_difference(got, restatement(data))
+    assert bad is None, f"{os.path.basename(path)}: {bad}"
+
+
+def test_restart_and_progressive_files_come_back_from_pil(rt):
+    """What the parser refuses takes the host path inside the wrapper, silently, and the report says so; ``mode`` converts as PIL does."""
+    a = J.content("smooth", 33, 17, 3)
+    buf = io.BytesIO()
+    Image.fromarray(a).save(buf, format="JPEG", progressive=True)
+    g = save(J.content("smooth", 17, 33, 1), 75, "L")
+    datas = [save(a, restart_marker_blocks=1), buf.getvalue(), save(a), g]
+    report = []
+    out = rt.jpeg_decode_u8(datas, DEV, report=report, mode="RGB")
+    assert [r["path"].split(":")[0] for r in report] == ["host", "host", "device", "device"], report
+    for data, o in zip(datas, out):
+        bad = first_difference(o.cpu().numpy(), np.asarray(Image.open(io.BytesIO(data)).convert("RGB")))
+        assert bad is None, bad
+    one = rt.jpeg_decode_u8(g, DEV)
+    assert tuple(one.shape) == (17, 33) and first_difference(one.cpu().numpy(), pillow(g)) is None
+
+
+# ---- the parallel entropy decode -----------------------------------------------------------------------------------------------------------
+CHUNK_FILES = {
+    "noise 48x64 q100 4:4:4": lambda: save(J.content("noise", 48, 64, 3), 100, 0),
+    "photograph-like 64x64": lambda: save(J.content("smooth", 64, 64, 3), 75, 2),
+    "noise 33x17 4:2:2 optimize": lambda: save(J.content("noise", 33, 17, 3), 95, 1, optimize=True),
+    "grey noise 40x72": lambda: save(J.content("noise", 40, 72, 1), 90, "L"),
+    "impronte_d_artista.jpg": lambda: open(os.path.join(ROOT, "tests", "golden", "jpeg", "impronte_d_artista.jpg"), "rb").read(),
+}
+
+
+@pytest.mark.parametrize("name", CHUNK_FILES)
+def test_pixels_do_not_depend_on_chunk_bits(rt, name):
+    data = CHUNK_FILES[name]()
+    want = pillow(data)
+    p = F.parse(data)
+    bits = 8 * (p.seg_length - data[p.seg_offset:p.seg_offset + p.seg_length].count(b"\xff\x00"))          # of the unstuffed stream
+    for chunk_bits in (32, 64, 256, 0):
+        assert bits > 2 * (chunk_bits or 1024), f"{name}: a stream of {bits} bits does not span three subsequences of {chunk_bits or 1024}"
+        (got,), (rounds,) = device_pixels(rt, [data], chunk_bits=chunk_bits)
+        bad = first_difference(got, want)
+        assert bad is None, f"{name} at chunk_bits {chunk_bits}: {bad}"
+        assert 2 <= rounds <= -(-bits // (chunk_bits or 1024)) + 1
+
+
+def test_rounds_are_the_simulations(rt):
+    """The device runs the scheme tests/jpeg_file_ref.py simulates: the same number of rounds."""
+    for name in ("photograph-like 64x64", "noise 33x17 4:2:2 optimize"):
+        data = CHUNK_FILES[name]()
+        for chunk_bits in (32, 256):
+            _, (rounds,) = device_pixels(rt, [data], chunk_bits=chunk_bits)
+            assert rounds == R.decode(data, chunk_bits)[2], (name, chunk_bits)
+
+
+@pytest.mark.parametrize("side", [64, 256])
+@pytest.mark.parametrize("value", [(255, 255, 255), (90, 160, 200)], ids=["white", "colour"])
+def test_constant_frames_at_32_bits(rt, side, value):
+    """A constant frame's stream is periodic: nothing synchronises by itself, the rounds carry the state along."""
+    data = save(np.full((side, side, 3), value, np.uint8), 75, 2)
+    (got,), (rounds,) = device_pixels(rt, [data], chunk_bits=32)
+    bad = first_difference(got, pillow(data))
+    assert bad is None, bad
+    print(f"constant {side}x{side} {value}: {rounds} rounds")
+    assert rounds > 2
+
+
+# ---- batches ------------------------------------------------------------------------------------------------------------------------------
+def batch_of_four():
+    h, w = 37, 53
+    return [save(J.content("noise", h, w, 3), 50), save(J.content("smooth", h, w, 3), 75, optimize=True), save(J.content("white", h, w, 3), 95),
+            save(J.content("binary", h, w, 3), 100, optimize=True)]
+
+
+@pytest.mark.parametrize("lead", [0, 1, 3])
+def test_a_batch_of_four_equals_four_single_calls(rt, lead):
+    """One geometry, four contents, four sets of tables (two of them optimised), the segments at whatever byte offsets they fall on
+    behind ``lead`` spare bytes; the third frame is constant, so anything it borrowed from a neighbour would show."""
+    datas = batch_of_four()
+    parsed = [F.parse(d) for d in datas]
+    assert len({p.geometry for p in parsed}) == 1 and len({p.blob for p in parsed}) == 4
+    assert len({(lead + sum(p.seg_length for p in parsed[:i])) % 4 for i in range(4)}) > 1, "the offsets should differ in alignment"
+    out, record = rt.jpeg_decode_batch(parsed, datas, DEV, lead=lead)
+    assert record[:, 0].cpu().tolist() == [0, 0, 0, 0]
+    batch = out.cpu().numpy()
+    for i, d in enumerate(datas):
+        single, rec = rt.jpeg_decode_batch(parsed[i:i + 1], [d], DEV)
+        assert rec[0, 0].item() == 0
+        bad = first_difference(batch[i], single[0].cpu().numpy())
+        assert bad is None, f"file {i}: {bad}"
+        bad = first_difference(batch[i], pillow(d))
+        assert bad is None, f"file {i}: {bad}"
+
+
+# ---- the memory contract, through the guard-band arena ----------------------------------------------------------------------------------
+def abi_case(rt, datas, parsed=None, chunk_bits=0):
+    """(specs, setup, call, geometry) of one direct call of the C ABI on the files ``datas`` (``parsed``: their descriptions, when the
+    bytes are damaged and must not be parsed again)."""
+    parsed = parsed or [F.parse(d) for d in datas]
+    n = len(datas)
+    h, w, c, sampling = parsed[0].geometry
+    segs = [d[p.seg_offset:p.seg_offset + p.seg_length] for d, p in zip(datas, parsed)]
+    lengths = [len(s) for s in segs]
+    offsets = [3 + sum(lengths[:i]) for i in range(n)]
+    files = b"\xa5\xa5\xa5" + b"".join(segs)
+    blobs = b"".join(p.blob for p in parsed)
+    nbytes = rt.jpeg_decode_sizes(n, h, w, c, sampling, max(lengths), chunk_bits)
+    specs = [("files", len(files), "in", 1), ("blobs", len(blobs), "in", 1), ("dst", n * h * w * c, "out", 1), ("record", 8 * n, "out", 4),
+             ("workspace", nbytes, "ws", 8)]
+    off, ln = (ctypes.c_uint64 * n)(*offsets), (ctypes.c_uint32 * n)(*lengths)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def setup(arena):
+        arena.put("files", torch.frombuffer(bytearray(files), dtype=torch.uint8))
+        arena.put("blobs", torch.frombuffer(bytearray(blobs), dtype=torch.uint8))
+
+    def call(arena):
+        rc = rt.lib().adain_jpeg_decode_u8(arena.ptr("files"), len(files), arena.ptr("blobs"), n, h, w, c, sampling, off, ln, arena.ptr("dst"),
+                                           arena.ptr("record"), arena.ptr("workspace"), arena.nbytes("workspace"), chunk_bits, stream)
+        assert rc == 0, rt.lib().adain_last_error().decode()
+
+    return specs, setup, call, (n, h, w, c)
+
+
+ARENA_CASES = {
+    "two 4:2:0 17x9": lambda: [save(J.content("noise", 17, 9, 3, seed=i), 90, 2) for i in range(2)],
+    "two 4:2:2 33x17, one optimised": lambda: [save(J.content("smooth", 33, 17, 3), 75, 1), save(J.content("noise", 33, 17, 3), 75, 1, optimize=True)],
+    "4:4:4 16x16": lambda: [save(J.content("binary", 16, 16, 3), 75, 0)],
+    "two grey 64x64": lambda: [save(J.content("binary", 64, 64, 1, seed=i), 75, "L") for i in range(2)],
+}
+
+
+@pytest.mark.parametrize("name", ARENA_CASES)
+def test_the_call_stays_in_its_buffers_and_ignores_stale_bytes(rt, name):
+    """dst, the record and the workspace start as 0xFF bytes and as a non-zero pattern: the pixels and the record are the same, no byte
+    outside the three regions changes; then a call on another file through the same workspace, and the call again: stale streams, states,
+    coefficients and planes."""
+    datas = ARENA_CASES[name]()
+    specs, setup, call, (n, h, w, c) = abi_case(rt, datas)
+    other = [save(J.content("noise", 8, 8, 3), 75, 2)]
+    ospecs, _, _, (on, oh, ow, oc) = abi_case(rt, other, chunk_bits=32)
+    assert ospecs[4][1] <= specs[4][1] and on * oh * ow * oc <= n * h * w * c
+    op = F.parse(other[0])
+    up = torch.frombuffer(bytearray(op.blob + other[0][op.seg_offset:op.seg_offset + op.seg_length]), dtype=torch.uint8).to(DEV)
+
+    def history(arena):
+        off, ln = (ctypes.c_uint64 * 1)(0), (ctypes.c_uint32 * 1)(op.seg_length)
+        rc = rt.lib().adain_jpeg_decode_u8(up.data_ptr() + F.BLOB_BYTES, op.seg_length, up.data_ptr(), 1, oh, ow, oc, op.sampling, off, ln, arena.ptr("dst"),
+                                           arena.ptr("record"), arena.ptr("workspace"), arena.nbytes("workspace"), 32, torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, rt.lib().adain_last_error().decode()
+
+    outs = A.run_case(specs, call, DEV, torch.cuda.synchronize, history=history, setup=setup)
+    record = outs["record"].cpu().numpy().view(np.int32).reshape(n, 2)
+    assert record[:, 0].tolist() == [0] * n and (record[:, 1] >= 2).all()
+    got = outs["dst"].cpu().numpy().reshape(n, h, w, c)
+    for i, d in enumerate(datas):
+        want = pillow(d)
+        bad = first_difference(got[i].reshape(want.shape), want)
+        assert bad is None, f"file {i}: {bad}"
+    _arena_passed.add(name)
+
+
+def test_refusals_come_before_any_launch(rt):
+    data = save(J.content("smooth", 16, 16, 3))
+    p = F.parse(data)
+    L = rt.lib()
+    up = torch.frombuffer(bytearray(p.blob + data), dtype=torch.uint8).to(DEV)
+    dst = torch.zeros(16 * 16 * 3, dtype=torch.uint8, device=DEV)
+    record = torch.full((2,), 77, dtype=torch.int32, device=DEV)
+    nbytes = rt.jpeg_decode_sizes(1, 16, 16, 3, 2, p.seg_length)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(n=1, h=16, w=16, c=3, sampling=2, offset=p.seg_offset, length=p.seg_length, files_bytes=len(data), nbytes=nbytes, chunk_bits=0, ws_ptr=ws.data_ptr()):
+        off, ln = (ctypes.c_uint64 * 1)(offset), (ctypes.c_uint32 * 1)(length)
+        return L.adain_jpeg_decode_u8(up.data_ptr() + F.BLOB_BYTES, files_bytes, up.data_ptr(), n, h, w, c, sampling, off, ln, dst.data_ptr(), record.data_ptr(),
+                                      ws_ptr, nbytes, chunk_bits, stream)
+
+    for kw in (dict(n=0), dict(c=2), dict(sampling=3), dict(c=1, sampling=2), dict(h=0), dict(w=65536), dict(chunk_bits=31), dict(chunk_bits=48), dict(chunk_bits=-32),
+               dict(offset=len(data)), dict(length=len(data)), dict(nbytes=nbytes - 1), dict(ws_ptr=ws.data_ptr() + 4)):
+        assert call(**kw) == -1 and L.adain_last_error().startswith(b"jpeg_decode_u8"), kw
+    torch.cuda.synchronize()
+    assert record.cpu().tolist() == [77, 77] and int(dst.sum()) == 0
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert record[0].item() == 0 and first_difference(dst.cpu().numpy().reshape(16, 16, 3), pillow(data)) is None
+    with pytest.raises(rt.AdainHipError):
+        rt.jpeg_decode_sizes(1, 16, 16, 3, 2, 1 << 28)
+
+
+# ---- damaged entropy data --------------------------------------------------------------------------------------------------------------------
+def damaged(kind):
+    data = save(J.content("noise", 16, 16, 3), 90, 2)
+    p = F.parse(data)
+    seg = bytearray(data[p.seg_offset:p.seg_offset + p.seg_length])
+    if kind == "cut":
+        seg = seg[:len(seg) // 2]
+    else:
+        rng = np.random.default_rng(0)
+        for at in rng.choice(len(seg), 8, replace=False):
+            seg[at] ^= int(rng.integers(1, 256))
+    bad = data[:p.seg_offset] + bytes(seg) + b"\xff\xd9"
+    q = F.JpegFile(**{**p.__dict__, "seg_length": len(seg)})
+    return bad, q
+
+
+def pil_outcome(data):
+    try:
+        with Image.open(io.BytesIO(data)) as img:
+            return np.asarray(img), None
+    except Exception as e:                       # whatever PIL raises for these bytes
+        return None, type(e)
+
+
+@pytest.mark.parametrize("kind", ["cut", "flipped"])
+def test_damaged_entropy_data(rt, kind):
+    """Half the segment gone, or 8 seeded bytes of it flipped: the status is non-zero or the pixels are Pillow's for those bytes, the
+    guard bands are intact either way, and the wrapper returns what PIL returns or raises what PIL raises."""
+    if _arena_passed != set(ARENA_CASES):
+        pytest.fail("runs only after the arena tests of valid files have passed")
+    bad, q = damaged(kind)
+    specs, setup, call, (n, h, w, c) = abi_case(rt, [bad], [q], chunk_bits=32)
+    outs = A.run_case(specs, call, DEV, torch.cuda.synchronize, setup=setup)
+    status = int(outs["record"].cpu().numpy().view(np.int32)[0])
+    want, error = pil_outcome(bad)
+    print(f"{kind}: status {status}, PIL {'raises ' + error.__name__ if error else 'decodes'}")
+    if status == 0:
+        assert error is None, f"status 0 for bytes PIL refuses with {error.__name__}"
+        got = outs["dst"].cpu().numpy().reshape(h, w, c)
+        diff = first_difference(got, want)
+        assert diff is None, f"status 0, but {diff}"
+    if error is not None:
+        with pytest.raises(error):
+            rt.jpeg_decode_u8(bad, DEV)
+    else:
+        report = []
+        got = rt.jpeg_decode_u8(bad, DEV, report=report).cpu().numpy()
+        assert first_difference(got, want) is None, report
+
+
+# ---- the callers ------------------------------------------------------------------------------------------------------------------------
+import applied_image_processing_amd.synth as synth
+
+
+def u8img(seed, h, w, c=3):
+    return (synth.image(seed, 1, h, w, c=c)[0].transpose(1, 2, 0) * 255).astype(np.uint8)
+
+
+@pytest.fixture(scope="module")
+def ckpt(tmp_path_factory):
+    d = tmp_path_factory.mktemp("ckpt")
+    torch.save(synth.to_torch(synth.vgg_state_dict(0, full=True)), d / "vgg.pth")
+    torch.save(synth.to_torch(synth.decoder_state_dict(0)), d / "dec.pth")
+    return dict(vgg_str=str(d / "vgg.pth"), decoder_str=str(d / "dec.pth"))
+
+
+@pytest.fixture(scope="module")
+def engine(rt, weights):
+    from applied_image_processing_amd.engine import AdaINEngine
+
+    return AdaINEngine(weights[0], weights[1], DEV)
+
+
+class Counter:
+    def __init__(self, fn):
+        self.fn, self.calls = fn, 0
+
+    def __call__(self, *args, **kwargs):
+        self.calls += 1
+        return self.fn(*args, **kwargs)
+
+
+@pytest.fixture
+def t():
+    from applied_image_processing_amd.AdaIN import test as t
+
+    t.clear_style_cache()
+    yield t
+    t.set_device_jpeg_decode(False)
+    t.clear_style_cache()
+
+
+@pytest.mark.parametrize("kind", ["baseline", "progressive"])
+def test_adain_inference_writes_the_same_file_with_the_device_decoder(rt, t, ckpt, tmp_path, monkeypatch, kind):
+    """A 48 x 64 JPEG content given as a path, a small style: byte-identical output with the switch off and on - decoded on the device
+    for the baseline file, through the fallback for the progressive one; a PIL image passed in is never touched."""
+    content = tmp_path / "content.jpg"
+    Image.fromarray(u8img(900, 48, 64)).save(content, quality=90, progressive=kind == "progressive")
+    style = Image.fromarray(u8img(950, 40, 56))
+    entry = Counter(rt.jpeg_decode_batch)
+    monkeypatch.setattr(rt, "jpeg_decode_batch", entry)
+    assert t.set_device_jpeg_decode(False) is False              # the default
+    files = {}
+    for on in (False, True):
+        t.set_device_jpeg_decode(on)
+        p = t.adain_inference(str(content), style, content_size=32, style_size=32, output=str(tmp_path / f"out_{int(on)}"), file_name="x", **ckpt)
+        files[on] = p.read_bytes()
+        assert entry.calls == (1 if on and kind == "baseline" else 0)
+    assert files[True] == files[False]
+    calls = entry.calls
+    p = t.adain_inference(Image.open(content), style, content_size=32, style_size=32, output=str(tmp_path / "out_pil"), file_name="x", **ckpt)
+    assert entry.calls == calls and p.read_bytes() == files[False]
+    assert t.set_device_jpeg_decode(False) is True
+
+
+def a_flow_provider(prev_frame_path, frame_path, target_resolution, method):
+    w, h = target_resolution
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+    return np.stack([1.5 * np.sin(yy / 7.0), 0.75 * np.cos(xx / 5.0)]).astype(np.float32)
+
+
+@pytest.mark.parametrize("provider", ["own", "callers"])
+def test_the_video_path_writes_the_same_frames_with_the_device_decoder(rt, engine, tmp_path, monkeypatch, provider):
+    """Three frames (one of them grey, one progressive), the flag off and on: identical files; with the package's own Farneback provider
+    the frames of the flow are decoded on the device as well."""
+    from applied_image_processing_amd import video
+
+    cdir = tmp_path / "frames"
+    cdir.mkdir()
+    Image.fromarray(u8img(700, 64, 96)).save(cdir / "frame_0000.jpg", quality=95)
+    Image.fromarray(u8img(701, 64, 96)[..., 0]).save(cdir / "frame_0001.jpg", quality=95)
+    Image.fromarray(u8img(702, 64, 96)).save(cdir / "frame_0002.jpg", quality=95, progressive=True)
+    Image.fromarray(u8img(750, 96, 96)).save(tmp_path / "style.png")
+    depth_maps = [synth.smooth_depth(480 + i, 64, 96) for i in range(3)]
+    entry = Counter(rt.jpeg_decode_batch)
+    monkeypatch.setattr(rt, "jpeg_decode_batch", entry)
+    out = {}
+    for on in (False, True):
+        video.set_flow_provider(video.device_flow_provider if provider == "own" else a_flow_provider)
+        try:
+            video.apply_style_transfer_ada(str(cdir), str(tmp_path / "style.png"), str(tmp_path / f"out_{int(on)}"), alpha=0.7, target_resolution=(96, 64),
+                                           engine=engine, depth_maps=depth_maps, jpeg_decode_on_device=on)
+        finally:
+            video.set_flow_provider(None)
+        out[on] = [(tmp_path / f"out_{int(on)}" / f"frame_{i:04d}.jpg").read_bytes() for i in range(3)]
+        assert entry.calls == (0 if not on else 2 + (2 if provider == "own" else 0))       # the progressive frame never reaches the device decoder
+    assert out[True] == out[False]
+    assert video._jpeg_decode_on_device is False
