@@ -184,7 +184,7 @@ def device_decode_transform_u8(path, size, crop, device, mark=None):
     with open(str(path), "rb") as f:
         data = f.read()
     try:
-        parsed = jpeg_file.parse(data)
+        parsed = jpeg_file.parse(data, restart=True)
     except jpeg_file.UnsupportedJpeg:
         return None
     if parsed.c != 3:                           # PIL opens a grey file as mode L, which keeps the host transform
@@ -314,9 +314,9 @@ _device_jpeg_decode_on = False
 def set_device_jpeg_decode(enabled):
     """True: the cached per-call path of ``adain_inference`` reads the bytes of a content given as a ``.jpg`` / ``.jpeg`` path, decodes
     them on the device (adain_jpeg_decode_u8: the pixels Pillow decodes) and resizes that frame there, instead of decoding with PIL and
-    uploading the pixels.  A file the decoder does not take (progressive, restart markers, grey, ...: jpeg_file.parse) or that does not
-    decode cleanly, a PIL image passed in by the caller and any other extension take the PIL path as before.  The output file does not
-    change.  Default False.  Returns the previous setting."""
+    uploading the pixels.  Files with restart intervals are decoded there too.  A file the decoder does not take (progressive, grey,
+    ...: jpeg_file.parse) or that does not decode cleanly, a PIL image passed in by the caller and any other extension take the PIL path
+    as before.  The output file does not change.  Default False.  Returns the previous setting."""
     global _device_jpeg_decode_on
     prev, _device_jpeg_decode_on = _device_jpeg_decode_on, bool(enabled)
     return prev

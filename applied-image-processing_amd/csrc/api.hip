@@ -562,16 +562,27 @@ int adain_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int 
     return rc == -1 ? ADAIN_EINVAL : rc;
 }
 
+int adain_jpeg_decode_restart_u8_bytes(int n, int h, int w, int c, int sampling, int restart_interval, size_t max_segment_bytes, int chunk_bits,
+                                       size_t* workspace_bytes) {
+    return jpeg_decode_bytes(n, h, w, c, sampling, restart_interval, max_segment_bytes, chunk_bits, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_jpeg_decode_restart_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, int restart_interval,
+                                 const uint64_t* segment_offsets, const uint32_t* segment_lengths, uint8_t* dst, int32_t* record, void* workspace,
+                                 size_t workspace_bytes, int chunk_bits, adain_stream_t stream) {
+    if (!files || !blobs || !segment_offsets || !segment_lengths || !dst || !record || !workspace) { set_error("jpeg_decode_u8: null pointer"); return ADAIN_EINVAL; }
+    const int rc = launch_jpeg_decode_u8(files, files_bytes, blobs, n, h, w, c, sampling, restart_interval, segment_offsets, segment_lengths, dst, record, workspace,
+                                         workspace_bytes, chunk_bits, (hipStream_t)stream);
+    return rc == -1 ? ADAIN_EINVAL : rc;
+}
+// the entries from before restart intervals: the ones above at 0
 int adain_jpeg_decode_u8_bytes(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes) {
-    return jpeg_decode_bytes(n, h, w, c, sampling, max_segment_bytes, chunk_bits, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+    return adain_jpeg_decode_restart_u8_bytes(n, h, w, c, sampling, 0, max_segment_bytes, chunk_bits, workspace_bytes);
 }
 int adain_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling,
                          const uint64_t* segment_offsets, const uint32_t* segment_lengths, uint8_t* dst, int32_t* record, void* workspace,
                          size_t workspace_bytes, int chunk_bits, adain_stream_t stream) {
-    if (!files || !blobs || !segment_offsets || !segment_lengths || !dst || !record || !workspace) { set_error("jpeg_decode_u8: null pointer"); return ADAIN_EINVAL; }
-    const int rc = launch_jpeg_decode_u8(files, files_bytes, blobs, n, h, w, c, sampling, segment_offsets, segment_lengths, dst, record, workspace, workspace_bytes,
-                                         chunk_bits, (hipStream_t)stream);
-    return rc == -1 ? ADAIN_EINVAL : rc;
+    return adain_jpeg_decode_restart_u8(files, files_bytes, blobs, n, h, w, c, sampling, 0, segment_offsets, segment_lengths, dst, record, workspace, workspace_bytes,
+                                        chunk_bits, stream);
 }
 
 int adain_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, adain_stream_t stream) {

@@ -182,9 +182,11 @@ int launch_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int qu
 int jpeg_roundtrip_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
 int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, hipStream_t s);
 // a baseline file's entropy-coded segment -> the pixels Pillow decodes from the file (the rules: jpeg.hip, tests/jpeg_file_ref.py)
-int jpeg_decode_bytes(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes);
-int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, const uint64_t* seg_offsets,
-                          const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace, size_t workspace_bytes, int chunk_bits, hipStream_t s);
+// restart_interval: MCUs per restart interval, 0 for a file without one (tests/jpeg_restart_ref.py)
+int jpeg_decode_bytes(int n, int h, int w, int c, int sampling, int restart_interval, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes);
+int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, int restart_interval,
+                          const uint64_t* seg_offsets, const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace, size_t workspace_bytes,
+                          int chunk_bits, hipStream_t s);
 
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);

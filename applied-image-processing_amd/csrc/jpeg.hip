@@ -68,15 +68,18 @@
 //              LDS image of the row segment laid out at the destination's byte phase, which leaves as aligned dwords with byte stores at
 //              its two ends only - any destination address and any 3 w row stride
 //
-// The file decoder (adain_jpeg_decode_u8): a baseline file's entropy-coded segment -> the pixels Pillow decodes from the file.  Its rule list
+// The file decoder (adain_jpeg_decode_u8, adain_jpeg_decode_restart_u8): a baseline file's entropy-coded segment -> the pixels Pillow decodes from the file.  Its rule list
 // and its stages stand in front of its kernels below ("the file decoder"); in short
-//   taken     8-bit sequential Huffman files, one interleaved scan, grey or YCbCr with luma 1 x 1 / 2 x 1 / 2 x 2, no restart interval;
-//             the host (jpeg_file.py) walks the markers, refuses everything else and packs the file's tables into one blob
+//   taken     8-bit sequential Huffman files, one interleaved scan, grey or YCbCr with luma 1 x 1 / 2 x 1 / 2 x 2, with or without a
+//             restart interval; the host (jpeg_file.py) walks the markers, refuses everything else and packs the file's tables into one blob
+//   restart   the RSTn markers are found and removed HERE, while unstuffing; every interval is decoded from its own byte-aligned all-zero
+//             state on a subsequence grid of its own, and the DC sums restart with it
 //   entropy   the unstuffed stream is cut into subsequences; their exit states (bit position, block in the MCU, zigzag index) are iterated
 //             inside one workgroup per file until a round changes none - the fixed point is the sequential decoder's, whatever the data -
 //             then every subsequence writes its coefficients in parallel; garbage is decoded without leaving a buffer: a code in no table
 //             costs one bit, a run past 63 ends the block, the reader pads with 1-bits, every index is clamped
-//   status    per file: 0, or the stream did not hold exactly the expected blocks ending inside its last byte (the caller then uses PIL)
+//   status    per file: 0, or the stream (every interval of it) did not hold exactly the expected blocks ending inside its last byte,
+//             or the restart markers are not the expected ones in order (the caller then uses PIL)
 //   back half the round trip's, with the file's own quantisation tables, three chroma layouts and a grey path
 #include "common.h"
 
@@ -774,12 +777,39 @@ __global__ __launch_bounds__(MERGE_PX / 2) void jpeg_merge_kernel(const uint8_t*
 }
 
 // ---- the file decoder: a baseline file's entropy-coded segment -> pixels -----------------------------------------------------------------
-// adain_jpeg_decode_u8.  The host (jpeg_file.py) walks the markers and hands over the file's bytes, where its entropy-coded segment lies
-// and one blob of tables (FileTables); everything behind that runs here.  tests/jpeg_file_ref.py restates it in Python.
+// adain_jpeg_decode_u8 and adain_jpeg_decode_restart_u8.  The host (jpeg_file.py) walks the markers and hands over the file's bytes, where
+// its entropy-coded segment lies, one blob of tables (FileTables) and the call's restart interval; everything behind that runs here.
+// tests/jpeg_file_ref.py restates it in Python, tests/jpeg_restart_ref.py the restart rules.
 //
 // Its rules
-//   files     no restart interval (the host refuses a DRI other than 0: RSTn markers are not removed here), one scan, 8-bit tables
+//   files     one scan, 8-bit tables, one restart interval Ri per call (0: none; the old entry is the new one at 0)
 //   stream    the segment with the 00 behind every FF removed; bits big-endian; the reader returns 1-bits past its end
+//   restart   Ri > 0 MCUs, nmcu = mw mh, nint = ceil(nmcu / Ri): interval k holds the MCUs k Ri .. min((k+1) Ri, nmcu) - 1 and expects
+//             bpm min(Ri, nmcu - k Ri) blocks.  Ri = 0: the whole stream is one interval of nmcu MCUs and nothing below changes today's scheme
+//     segment   from behind SOS to EOI as before; it now holds FF D0..D7 pairs, and as unstuffed entropy data cannot, each such pair
+//               is a marker.  Byte by byte, with Ri > 0 a byte is dropped when it is a 00 behind an FF, an FF in front of a D0..D7 that is
+//               still in the segment, or a D0..D7 behind an FF; every other byte is kept
+//     stream    the kept bytes.  Marker m (0-based, in file order) ends interval m; interval m + 1 begins at the stream byte behind it,
+//               interval 0 at byte 0.  THIS code finds the markers, in the unstuff stage, and records each interval's first stream byte in
+//               a per-file table in the workspace (a call still needs only its arguments and one upload).  A marker split over two
+//               threads' bytes or two 4096-byte pieces, and a stuffed FF 00 directly in front of a marker (the common case, as the pad
+//               bits are ones), are nothing special: every byte is judged by its two neighbours in the segment
+//     reader    inside interval k the bits at or beyond the interval's end read as 1; decoding never continues from one interval into
+//               the next; pad bits (at most 7 ones) complete no code, so they begin no block
+//     grid      interval k is cut into subsequences of chunk_bits bits from its own first bit, the last one shorter: no subsequence
+//               straddles an interval start.  In every round the first subsequence of an interval enters from (its first bit, block 0,
+//               index 0), every other one from its left neighbour's exit state of the round before; the loop ends after the first round
+//               that changed no exit state in any interval (which is the largest round count any interval needs on its own)
+//     blocks    a block's index is k Ri bpm plus the number of blocks begun before it in interval k: a segmented exclusive scan of the
+//               per-subsequence counts.  Blocks whose in-interval index is at or above the interval's expected count are written by
+//               nobody and are not damage
+//     DC        the running sum per component restarts at 0 at every interval's first MCU
+//     status    non-zero when, in some interval: damage inside an expected block, a DC sum outside -2047..2047, fewer blocks than
+//               expected, or the last expected block not ending inside the interval's last byte; when the markers found are not
+//               nint - 1, or marker m is not FF D(m mod 8); when the decode did not settle.  With a wrong marker count or order the
+//               entropy decode is skipped (no table entry is trusted) and the frame is that of all-zero coefficients.  Whatever the
+//               bytes, every write stays inside dst, record and the workspace and the kernels terminate: a marker beyond the expected
+//               count indexes nothing
 //   symbol    libjpeg's look-up: the next 8 bits index look[] (length << 8 | symbol); a longer code is the first length l in 9..16 with
 //             code <= maxcode[l], its symbol val[(valoff[l] + code) & 255]; when no length matches ONE bit is consumed and nothing else
 //             changes (garbage is the normal case in round 0 of the decode, and a damaged file must not hang or leave its buffers)
@@ -800,7 +830,8 @@ __global__ __launch_bounds__(MERGE_PX / 2) void jpeg_merge_kernel(const uint8_t*
 //
 // Its stages (one workgroup per file where a stage is sequential in the file, otherwise one launch over all files)
 //   table     the host's segment offsets and lengths reach the device as kernel arguments, 64 files per launch
-//   unstuff   per 4096-byte piece: count the stuffed zeros, scan, scatter; the tail of the stream is filled with FF
+//   unstuff   per 4096-byte piece: count the stuffed zeros (Ri > 0: and the marker bytes, and the markers), scan, scatter; the tail of
+//             the stream is filled with FF.  Ri > 0: marker m puts its stream position at entry m + 1 of the file's interval table
 //   settle    the stream is cut into subsequences of chunk_bits bits.  Round 0: every lane decodes its subsequence from the all-zero state
 //             at its first bit until its position passes the subsequence's end, and stores its exit state (position, block in the MCU,
 //             zigzag index).  Round r: lane s decodes subsequence s again from lane s - 1's exit state of round r - 1 (lane 0: from the
@@ -808,11 +839,15 @@ __global__ __launch_bounds__(MERGE_PX / 2) void jpeg_merge_kernel(const uint8_t*
 //             state, at most subsequences + 1 rounds.  The states then satisfy exit[s] = decode(s, exit[s-1]) for every s, a system with
 //             one solution: the sequential decoder's.  No luck is involved, a periodic stream only takes more rounds.  Two state arrays
 //             alternate, a workgroup barrier separates the rounds, nothing waits on another workgroup.  The blocks each subsequence
-//             begins are counted on the way and scanned at the end.
+//             begins are counted on the way and scanned at the end.  Ri > 0: a scan over the interval table first gives every interval
+//             its first subsequence (the table's second half); a subsequence finds its interval there by bisection, and every interval's
+//             first subsequence enters from the known state in every round
 //   write     fully parallel: every subsequence once more from its now known state and block index, the coefficients de-zigzagged as
 //             int16 into the zero-filled buffer, each by exactly one lane, DC terms as differences
-//   dc        per component the running sum in scan order; the record (status, rounds) is written here
+//   dc        per component the running sum in scan order, restarted at every interval's first MCU (a segmented sum over the
+//             workgroup); the record (status, rounds) is written here
 //   idct / pixels   as in the round trip, with the file's tables and the three layouts
+// Launches per call, whatever Ri: ceil(n / 64) table + unstuff + one memset + settle + write + dc + idct + pixels.
 constexpr int DEC_THREADS = 1024;       // of the per-file workgroups (unstuff, settle, dc)
 constexpr int DEC_SEG_BATCH = 64;       // files per launch of the table kernel
 constexpr int DEC_DEFAULT_CHUNK_BITS = 1024;
@@ -832,17 +867,21 @@ static_assert(sizeof(HuffTab) == 912 && sizeof(FileTables) == 3848, "the blob la
 
 struct DecSeg { uint64_t off; uint32_t len, pad; };
 struct DecSegBatch { uint64_t off[DEC_SEG_BATCH]; uint32_t len[DEC_SEG_BATCH]; };
-struct DecMeta { uint32_t ulen, rounds, settled, err, endpos, pad[3]; };        // per file, in the workspace
+struct DecMeta { uint32_t ulen, rounds, settled, err, done, nmark, merr, nsub; };        // per file, in the workspace
+// ulen: stream bytes; err: damage in an expected block or an interval's last block ending outside its last byte; done: intervals whose last
+// expected block ended; nmark: markers found; merr: a marker out of order; nsub: subsequences (0 when the marker structure is wrong)
 
 struct DecPlan {
     int c, H, V, bpm, mw, mh, yw, yh, cw, chh;        // luma blocks per MCU H x V; plane sizes in samples (whole blocks)
     size_t nblk, o_cb, o_cr, plane_stride;
     uint32_t cap_words, nsub_max, chunk_bits;
-    size_t o_seg, o_meta, o_stream, o_state, o_count, o_coef, o_planes, total;
+    uint32_t ri, nint;          // MCUs per interval (Ri, or all of them at Ri = 0) and intervals
+    size_t o_seg, o_meta, o_stream, o_state, o_count, o_coef, o_planes, o_itab, total;          // itab: per file nint + 1 first stream bytes, nint + 1 first subsequences; none at Ri = 0
 };
 
-const char* check_decode_shape(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits) {
+const char* check_decode_shape(int n, int h, int w, int c, int sampling, int restart_interval, size_t max_segment_bytes, int chunk_bits) {
     if (n < 1 || n > 65535) return "n outside 1..65535";
+    if (restart_interval < 0 || restart_interval > 65535) return "restart_interval outside 0..65535";
     if (c != 1 && c != 3) return "components other than 1 (grey) and 3 (YCbCr)";
     if (h < 1 || h > 65535 || w < 1 || w > 65535) return "height or width outside 1..65535";
     if (sampling < 0 || sampling > 2 || (c == 1 && sampling != 0)) return "sampling other than 0 (4:4:4, grey), 1 (4:2:2) and 2 (4:2:0)";
@@ -851,7 +890,7 @@ const char* check_decode_shape(int n, int h, int w, int c, int sampling, size_t 
     return nullptr;
 }
 
-DecPlan make_decode_plan(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits) {
+DecPlan make_decode_plan(int n, int h, int w, int c, int sampling, int restart_interval, size_t max_segment_bytes, int chunk_bits) {
     DecPlan p{};
     p.c = c;
     p.H = sampling >= 1 ? 2 : 1, p.V = sampling == 2 ? 2 : 1;
@@ -865,7 +904,11 @@ DecPlan make_decode_plan(int n, int h, int w, int c, int sampling, size_t max_se
     p.plane_stride = p.nblk * 64;
     p.chunk_bits = chunk_bits ? (uint32_t)chunk_bits : (uint32_t)DEC_DEFAULT_CHUNK_BITS;
     p.cap_words = (uint32_t)((max_segment_bytes + 3) / 4 + 3);
-    p.nsub_max = (uint32_t)((max_segment_bytes * 8 + p.chunk_bits - 1) / p.chunk_bits);
+    const uint32_t nmcu = (uint32_t)p.mw * (uint32_t)p.mh;
+    p.ri = restart_interval ? (uint32_t)restart_interval : nmcu;
+    p.nint = (nmcu + p.ri - 1) / p.ri;
+    // every interval rounds its last subsequence up: the sum of ceil(bits_k / chunk_bits) is below ceil(bits / chunk_bits) + nint
+    p.nsub_max = (uint32_t)((max_segment_bytes * 8 + p.chunk_bits - 1) / p.chunk_bits) + (restart_interval ? p.nint : 0u);
     if (p.nsub_max == 0) p.nsub_max = 1;
     size_t at = 0, N = (size_t)n;
     auto take = [&](size_t bytes) { size_t o = at; at = align256(at + bytes); return o; };
@@ -876,6 +919,7 @@ DecPlan make_decode_plan(int n, int h, int w, int c, int sampling, size_t max_se
     p.o_count = take(N * p.nsub_max * sizeof(uint32_t));
     p.o_coef = take(N * p.nblk * 64 * sizeof(int16_t));
     p.o_planes = take(N * p.plane_stride);
+    p.o_itab = take(restart_interval ? N * 2 * ((size_t)p.nint + 1) * sizeof(uint32_t) : 0);
     p.total = at;
     return p;
 }
@@ -884,7 +928,7 @@ __global__ void jpegd_table_kernel(DecSegBatch b, int first, int count, DecSeg* 
     const int i = threadIdx.x;
     if (i >= count) return;
     seg[first + i] = DecSeg{b.off[i], b.len[i], 0u};
-    meta[first + i] = DecMeta{0u, 0u, 0u, 0u, 0xffffffffu, {0u, 0u, 0u}};
+    meta[first + i] = DecMeta{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 }
 
 // inclusive sum over the DEC_THREADS threads of a workgroup; part: 16 uint32 of LDS
@@ -901,46 +945,73 @@ __device__ __forceinline__ uint32_t decode_inclusive(uint32_t v, uint32_t* part)
     return v;
 }
 
-// One workgroup per file: stream byte j = the j-th byte of the segment that is not a 00 behind an FF; then FF up to a whole word plus 8 bytes.
+// One workgroup per file: stream byte j = the j-th kept byte of the segment; then FF up to a whole word plus 8 bytes.  Dropped: a 00 behind
+// an FF and, with RESTART, both bytes of every FF D0..D7 pair; marker m (counted over the file) puts the stream position behind it at
+// itab[m + 1] when that is an interval's entry (m + 1 < nint) and is held to FF D(m mod 8).  itab[0] = 0 and itab[nint] = the stream's length.
+template <bool RESTART>
 __global__ __launch_bounds__(DEC_THREADS) void jpegd_unstuff_kernel(const uint8_t* __restrict__ files, const DecSeg* __restrict__ seg, DecMeta* __restrict__ meta,
-                                                                    uint8_t* __restrict__ stream, uint32_t cap_words) {
+                                                                    uint8_t* __restrict__ stream, uint32_t cap_words, uint32_t* __restrict__ itab, uint32_t nint) {
     __shared__ uint32_t part[16];
     const size_t f = blockIdx.x;
     const uint8_t* src = files + seg[f].off;
     const uint32_t len = seg[f].len;
     uint8_t* out = stream + f * cap_words * 4;          // len + 12 <= 4 cap_words
-    uint32_t carry = 0;                                 // stream bytes written by the pieces before
+    uint32_t* tab = RESTART ? itab + f * 2 * ((size_t)nint + 1) : nullptr;
+    uint32_t carry = 0, mcarry = 0;                     // stream bytes written, and markers met, by the pieces before
+    bool order = false;
     for (uint32_t base = 0; base < len; base += DEC_THREADS * 4) {
         const uint32_t i0 = base + threadIdx.x * 4;
-        uint8_t b[5];
+        uint8_t b[6];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const uint32_t i = i0 + k;                  // b[0] is the byte before the thread's four
+        for (int k = 0; k < 6; ++k) {
+            const uint32_t i = i0 + k;                  // b[0] is the byte before the thread's four, b[5] the one behind them
             b[k] = (i >= 1 && i - 1 < len) ? src[i - 1] : (uint8_t)0;
         }
-        uint32_t keep = 0;
+        bool kept[4], mark[4];
+        uint32_t keep = 0, marks = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) keep += (i0 + k < len && !(b[k + 1] == 0 && b[k] == 0xff && i0 + k >= 1)) ? 1u : 0u;
-        const uint32_t incl = decode_inclusive(keep, part);
-        uint32_t at = carry + incl - keep;
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t i = i0 + k;
+            const bool behind_ff = i >= 1 && b[k] == 0xff;
+            mark[k] = RESTART && i + 1 < len && b[k + 1] == 0xff && (b[k + 2] & 0xf8) == 0xd0;
+            kept[k] = i < len && !(behind_ff && b[k + 1] == 0) && !mark[k] && !(RESTART && behind_ff && (b[k + 1] & 0xf8) == 0xd0);
+            keep += kept[k] ? 1u : 0u, marks += mark[k] ? 1u : 0u;
+        }
+        // one scan for both counts: at most 4096 kept bytes and 2048 markers a piece
+        const uint32_t v = keep | (marks << 16);
+        const uint32_t incl = decode_inclusive(v, part);
+        uint32_t at = carry + ((incl - v) & 0xffffu), m = mcarry + ((incl - v) >> 16);
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (i0 + k < len && !(b[k + 1] == 0 && b[k] == 0xff && i0 + k >= 1)) out[at++] = b[k + 1];
+        for (int k = 0; k < 4; ++k) {
+            if (kept[k]) out[at++] = b[k + 1];
+            if (mark[k]) {
+                if (m + 1 < nint) tab[m + 1] = at;
+                if ((b[k + 2] & 7u) != (m & 7u)) order = true;
+                ++m;
+            }
+        }
         __syncthreads();
         if (threadIdx.x == DEC_THREADS - 1) part[15] = incl;          // wave 15's slot is read only by waves above it: none
         __syncthreads();
-        carry += part[15];
+        carry += part[15] & 0xffffu, mcarry += part[15] >> 16;
     }
     const uint32_t end = ((carry + 3) & ~3u) + 8;
     for (uint32_t i = carry + threadIdx.x; i < end; i += DEC_THREADS) out[i] = 0xff;
-    if (threadIdx.x == 0) meta[f].ulen = carry;
+    if (RESTART && order) meta[f].merr = 1;
+    if (threadIdx.x == 0) {
+        meta[f].ulen = carry, meta[f].nmark = mcarry;
+        if (RESTART) tab[0] = 0, tab[nint] = carry;
+    }
 }
 
-// 32 bits of the stream at bit position pos (big-endian); the stream holds FF bytes past its end, and the word index is clamped
-__device__ __forceinline__ uint32_t peek32(const uint32_t* __restrict__ s, uint32_t last_word, uint32_t pos) {
+// 32 bits of the stream at bit position pos (big-endian), the bits at or beyond `stop` (the interval's end) as ones; the stream holds FF
+// bytes past its own end, and the word index is clamped
+__device__ __forceinline__ uint32_t peek32(const uint32_t* __restrict__ s, uint32_t last_word, uint32_t pos, uint32_t stop) {
     const uint32_t wi = min(pos >> 5, last_word - 1);
     const uint64_t v = ((uint64_t)__builtin_bswap32(s[wi]) << 32) | __builtin_bswap32(s[wi + 1]);
-    return (uint32_t)((v << (pos & 31)) >> 32);
+    const uint32_t bits = (uint32_t)((v << (pos & 31)) >> 32);
+    if (pos + 32 <= stop) return bits;
+    return pos >= stop ? 0xffffffffu : bits | (0xffffffffu >> (stop - pos));
 }
 
 // (length << 8) | symbol of the code at the top of `bits`, 0 when none matches
@@ -954,19 +1025,35 @@ __device__ __forceinline__ uint32_t huff_symbol(const HuffTab& t, uint32_t bits)
     return 0;
 }
 
-struct DecShape { int H, V, bpm, c; size_t nblk; };
+struct DecShape { int H, V, bpm, c; size_t nblk; uint32_t ri, nint; };
 
-// Decodes from state st = (position, block in MCU << 8 | zigzag index) while position < end; returns the exit state and counts the
-// blocks begun.  WRITE: b is the index of the block current at st; coefficients of blocks below nblk go to coef (natural order).
+// The interval of subsequence i: its index, its first subsequence, its first bit and its end.  tab: the file's interval table (null at
+// Ri = 0: one interval, the stream); its second half is searched for the last interval that begins at or before i (empty ones begin nothing).
+struct DecInterval { uint32_t k, sub0, begin, stop; };
+__device__ __forceinline__ DecInterval interval_of(uint32_t i, const uint32_t* __restrict__ tab, uint32_t nint, uint32_t nbits) {
+    if (!tab) return DecInterval{0u, 0u, 0u, nbits};
+    const uint32_t* sub = tab + nint + 1;
+    uint32_t lo = 0, hi = nint;                         // sub[lo] <= i < sub[hi] = nsub
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (sub[mid] <= i) lo = mid; else hi = mid;
+    }
+    return DecInterval{lo, sub[lo], tab[lo] * 8, tab[lo + 1] * 8};
+}
+
+// Decodes from state st = (position, block in MCU << 8 | zigzag index) while position < end; the bits from `stop` on, the interval's end,
+// read as ones.  Returns the exit state and counts the blocks begun.  WRITE: b is the index of the block current at st; coefficients of the
+// interval's expected blocks b_lo <= b < b_end go to coef (natural order), and the last of them must end inside the interval's last byte.
 template <bool WRITE>
-__device__ __forceinline__ uint2 decode_span(const uint32_t* __restrict__ s, uint32_t last_word, uint32_t end, uint2 st, const FileTables& T_, const DecShape& g,
-                                             uint32_t* begun, int16_t* __restrict__ coef, long long b, DecMeta* __restrict__ meta) {
+__device__ __forceinline__ uint2 decode_span(const uint32_t* __restrict__ s, uint32_t last_word, uint32_t end, uint32_t stop, uint2 st, const FileTables& T_,
+                                             const DecShape& g, uint32_t* begun, int16_t* __restrict__ coef, long long b, long long b_lo, long long b_end,
+                                             DecMeta* __restrict__ meta) {
     uint32_t pos = st.x, blk = st.y >> 8, zz = st.y & 255, nb = 0;
     blk = blk < (uint32_t)g.bpm ? blk : 0;
     while (pos < end) {
         const int comp = g.c == 3 && (int)blk >= g.H * g.V ? (int)blk - g.H * g.V + 1 : 0;
-        const uint32_t bits = peek32(s, last_word, pos);
-        const bool live = WRITE && b >= 0 && (size_t)b < g.nblk;
+        const uint32_t bits = peek32(s, last_word, pos, stop);
+        const bool live = WRITE && b >= b_lo && b < b_end;
         const uint32_t e = huff_symbol(T_.huff[zz == 0 ? (T_.sel[comp] & 1) : 2 + (T_.sel[3 + comp] & 1)], bits);
         if (e == 0) {
             pos += 1;
@@ -998,7 +1085,9 @@ __device__ __forceinline__ uint2 decode_span(const uint32_t* __restrict__ s, uin
             zz = k + 1;
         }
         if (zz >= 64) {
-            if (live && (size_t)b == g.nblk - 1) meta->endpos = pos;
+            if (live && b == b_end - 1) {
+                if (pos <= stop && pos + 8 > stop) atomicAdd(&meta->done, 1u); else meta->err = 1;
+            }
             zz = 0, blk = blk + 1 == (uint32_t)g.bpm ? 0 : blk + 1, ++b;
         }
     }
@@ -1011,10 +1100,11 @@ __device__ __forceinline__ void load_tables(FileTables* dst, const uint8_t* __re
     __syncthreads();
 }
 
-// One workgroup per file: the rounds, then the scan of the block counts (count[s] becomes the blocks begun before subsequence s).
+// One workgroup per file: (Ri > 0) every interval's first subsequence, then the rounds, then the scan of the block counts (count[s] becomes
+// the blocks begun before subsequence s in the file; the write stage takes the interval's own first count off it).
 __global__ __launch_bounds__(DEC_THREADS) void jpegd_settle_kernel(const uint8_t* __restrict__ blobs, const uint32_t* __restrict__ stream, uint32_t cap_words,
                                                                    DecMeta* __restrict__ meta, uint2* __restrict__ state, uint32_t* __restrict__ count,
-                                                                   uint32_t nsub_max, uint32_t chunk_bits, DecShape g) {
+                                                                   uint32_t nsub_max, uint32_t chunk_bits, DecShape g, uint32_t* __restrict__ itab) {
     __shared__ FileTables ft;
     __shared__ uint32_t part[16];
     __shared__ int changed[2];
@@ -1023,7 +1113,26 @@ __global__ __launch_bounds__(DEC_THREADS) void jpegd_settle_kernel(const uint8_t
     load_tables(&ft, blobs + f * sizeof(FileTables));
     const uint32_t* s = stream + f * cap_words;
     const uint32_t nbits = min(meta[f].ulen, (cap_words - 3) * 4) * 8;
-    const uint32_t nsub = (uint32_t)(((uint64_t)nbits + chunk_bits - 1) / chunk_bits);      // <= nsub_max
+    uint32_t* tab = itab ? itab + f * 2 * ((size_t)g.nint + 1) : nullptr;
+    uint32_t nsub = (uint32_t)(((uint64_t)nbits + chunk_bits - 1) / chunk_bits);      // <= nsub_max
+    if (tab) {
+        // the table is whole only with nint - 1 markers in order: then its entries rise from 0 to the stream's length
+        const bool whole = meta[f].nmark == g.nint - 1 && !meta[f].merr;
+        uint32_t carry = 0;
+        for (uint32_t base = 0; base < g.nint && whole; base += DEC_THREADS) {
+            const uint32_t k = base + t;
+            const uint32_t v = k < g.nint ? (uint32_t)(((uint64_t)(tab[k + 1] - tab[k]) * 8 + chunk_bits - 1) / chunk_bits) : 0u;
+            const uint32_t incl = decode_inclusive(v, part);
+            if (k < g.nint) tab[g.nint + 1 + k] = carry + incl - v;
+            __syncthreads();
+            if (t == DEC_THREADS - 1) part[15] = incl;
+            __syncthreads();
+            carry += part[15];
+        }
+        nsub = whole && carry <= nsub_max ? carry : 0u;
+        if (t == 0) tab[2 * g.nint + 1] = nsub;
+        __syncthreads();
+    }
     uint2* st[2] = {state + f * 3 * nsub_max, state + (f * 3 + 1) * nsub_max};
     uint2* last_in = state + (f * 3 + 2) * nsub_max;    // the state each subsequence was last decoded from: read and written by its lane only
     uint32_t* cnt = count + f * nsub_max;
@@ -1035,14 +1144,15 @@ __global__ __launch_bounds__(DEC_THREADS) void jpegd_settle_kernel(const uint8_t
         const uint2* prev = st[(r & 1) ^ 1];            // the exit states of round r - 1: only read in this round
         int any = 0;
         for (uint32_t i = t; i < nsub; i += DEC_THREADS) {
-            const uint32_t begin = i * chunk_bits, end = min(begin + chunk_bits, nbits);
-            const uint2 in = (r == 0 || i == 0) ? make_uint2(begin, 0u) : prev[i - 1];
+            const DecInterval iv = interval_of(i, tab, g.nint, nbits);
+            const uint32_t begin = iv.begin + (i - iv.sub0) * chunk_bits, end = min(begin + chunk_bits, iv.stop);
+            const uint2 in = (r == 0 || i == iv.sub0) ? make_uint2(begin, 0u) : prev[i - 1];
             uint2 out;
             if (r > 0 && last_in[i].x == in.x && last_in[i].y == in.y) {
                 out = prev[i];                          // the same input as last time: the same exit state
             } else {
                 uint32_t nb = 0;
-                out = decode_span<false>(s, cap_words - 1, end, in, ft, g, &nb, nullptr, 0, nullptr);
+                out = decode_span<false>(s, cap_words - 1, end, iv.stop, in, ft, g, &nb, nullptr, 0, 0, 0, nullptr);
                 cnt[i] = nb;
                 last_in[i] = in;
                 if (r > 0 && (out.x != prev[i].x || out.y != prev[i].y)) any = 1;
@@ -1054,7 +1164,7 @@ __global__ __launch_bounds__(DEC_THREADS) void jpegd_settle_kernel(const uint8_t
         ++rounds;
         if (r > 0 && !changed[r & 1]) { settled = 1; break; }
     }
-    if (nsub == 0) settled = 1;
+    if (nsub == 0 && !(tab && nbits)) settled = 1;      // an empty stream is settled; a table that is not whole is not
     // exclusive scan of the counts
     uint32_t carry = 0;
     for (uint32_t base = 0; base < nsub; base += DEC_THREADS) {
@@ -1067,29 +1177,56 @@ __global__ __launch_bounds__(DEC_THREADS) void jpegd_settle_kernel(const uint8_t
         __syncthreads();
         carry += part[15];
     }
-    if (t == 0) meta[f].rounds = rounds, meta[f].settled = settled;
+    if (t == 0) meta[f].rounds = rounds, meta[f].settled = settled, meta[f].nsub = nsub;
 }
 
 __global__ __launch_bounds__(256) void jpegd_write_kernel(const uint8_t* __restrict__ blobs, const uint32_t* __restrict__ stream, uint32_t cap_words,
                                                           DecMeta* __restrict__ meta, const uint2* __restrict__ state, const uint32_t* __restrict__ count,
-                                                          uint32_t nsub_max, uint32_t chunk_bits, DecShape g, int16_t* __restrict__ coef) {
+                                                          uint32_t nsub_max, uint32_t chunk_bits, DecShape g, int16_t* __restrict__ coef,
+                                                          const uint32_t* __restrict__ itab) {
     __shared__ FileTables ft;
     const size_t f = blockIdx.y;
     load_tables(&ft, blobs + f * sizeof(FileTables));
     const uint32_t nbits = min(meta[f].ulen, (cap_words - 3) * 4) * 8;
-    const uint32_t nsub = (uint32_t)(((uint64_t)nbits + chunk_bits - 1) / chunk_bits);
+    const uint32_t nsub = meta[f].nsub;
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= nsub) return;
+    const DecInterval iv = interval_of(i, itab ? itab + f * 2 * ((size_t)g.nint + 1) : nullptr, g.nint, nbits);
     const uint2* exit_state = state + f * 3 * nsub_max;         // both arrays hold the settled states
-    const uint2 in = i == 0 ? make_uint2(0u, 0u) : exit_state[i - 1];
-    const long long b = (long long)count[f * nsub_max + i] - ((in.y & 255) ? 1 : 0);       // a block under way was begun further left
+    const uint32_t begin = iv.begin + (i - iv.sub0) * chunk_bits;
+    const uint2 in = i == iv.sub0 ? make_uint2(begin, 0u) : exit_state[i - 1];
+    const uint32_t* cnt = count + f * nsub_max;
+    const size_t mcu0 = (size_t)iv.k * g.ri, nmcu = g.nblk / g.bpm;
+    const long long b_lo = (long long)(mcu0 * g.bpm), b_end = b_lo + (long long)(min((size_t)g.ri, nmcu - mcu0) * g.bpm);
+    const long long b = b_lo + (long long)(cnt[i] - cnt[iv.sub0]) - ((in.y & 255) ? 1 : 0);       // a block under way was begun further left
     uint32_t nb;
-    decode_span<true>(stream + f * cap_words, cap_words - 1, min((i + 1) * chunk_bits, nbits), in, ft, g, &nb, coef + f * g.nblk * 64, b, meta + f);
+    decode_span<true>(stream + f * cap_words, cap_words - 1, min(begin + chunk_bits, iv.stop), iv.stop, in, ft, g, &nb, coef + f * g.nblk * 64, b, b_lo, b_end,
+                      meta + f);
 }
 
-// One workgroup per file: DC differences -> DC terms per component in scan order, then the file's record.
+// the segmented sum of the threads before this one, back to and with the nearest whose flag is set; part: 32 ints of LDS
+__device__ __forceinline__ int decode_exclusive_segmented(int v, int flag, int* part) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int uv = __shfl_up(v, d), uf = __shfl_up(flag, d);
+        if (lane >= d) {
+            if (!flag) v += uv;
+            flag |= uf;
+        }
+    }
+    __syncthreads();                                   // the previous pass has read part
+    if (lane == 63) part[wv] = v, part[16 + wv] = flag;
+    __syncthreads();
+    int before = 0;                                    // of the waves below
+    for (int k = 0; k < wv; ++k) before = part[16 + k] ? part[k] : before + part[k];
+    const int ev = __shfl_up(v, 1), ef = __shfl_up(flag, 1);
+    if (lane == 0) return before;
+    return ef ? ev : before + ev;
+}
+
+// One workgroup per file: DC differences -> DC terms per component in scan order, from 0 at every interval's first MCU; then the record.
 __global__ __launch_bounds__(DEC_THREADS) void jpegd_dc_kernel(int16_t* __restrict__ coef, const DecMeta* __restrict__ meta, DecShape g, int32_t* __restrict__ record) {
-    __shared__ uint32_t part[16];
+    __shared__ int part[32];
     __shared__ int range_err;
     const size_t f = blockIdx.x;
     const int t = threadIdx.x, hv = g.H * g.V;
@@ -1102,10 +1239,15 @@ __global__ __launch_bounds__(DEC_THREADS) void jpegd_dc_kernel(int16_t* __restri
         const size_t per = (cnt + DEC_THREADS - 1) / DEC_THREADS;
         const size_t a = min((size_t)t * per, cnt), e = min(a + per, cnt);
         auto block_of = [&](size_t i) { return comp == 0 ? (i / hv) * g.bpm + i % hv : i * g.bpm + hv + comp - 1; };
-        int sum = 0;
-        for (size_t i = a; i < e; ++i) sum += fc[block_of(i) * 64];
-        int run = (int)decode_inclusive((uint32_t)sum, part) - sum;
+        auto restarts = [&](size_t i) { return comp == 0 ? i % ((size_t)g.ri * hv) == 0 : i % g.ri == 0; };      // an interval's first block of the component
+        int sum = 0, flag = 0;
         for (size_t i = a; i < e; ++i) {
+            if (restarts(i)) sum = 0, flag = 1;
+            sum += fc[block_of(i) * 64];
+        }
+        int run = decode_exclusive_segmented(sum, flag, part);
+        for (size_t i = a; i < e; ++i) {
+            if (restarts(i)) run = 0;
             run += fc[block_of(i) * 64];
             if (run > 2047 || run < -2047) bad = 1;
             fc[block_of(i) * 64] = (int16_t)run;
@@ -1116,8 +1258,7 @@ __global__ __launch_bounds__(DEC_THREADS) void jpegd_dc_kernel(int16_t* __restri
     __syncthreads();
     if (t == 0) {
         const DecMeta m = meta[f];
-        const uint32_t nbits = m.ulen * 8;
-        const bool ok = m.settled && !m.err && !range_err && m.endpos != 0xffffffffu && m.endpos <= nbits && m.endpos + 8 > nbits;
+        const bool ok = m.settled && !m.err && !range_err && !m.merr && m.nmark + 1 == g.nint && m.done == g.nint;
         record[2 * f] = ok ? 0 : 1;
         record[2 * f + 1] = (int32_t)m.rounds;
     }
@@ -1286,17 +1427,25 @@ int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int
     return check_launch("jpeg_roundtrip_u8");
 }
 
-int jpeg_decode_bytes(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes) {
-    const char* bad = check_decode_shape(n, h, w, c, sampling, max_segment_bytes, chunk_bits);
-    if (bad) { set_error("jpeg_decode_u8: %s (n %d, %d x %d x %d, sampling %d, segment %zu, chunk_bits %d)", bad, n, h, w, c, sampling, max_segment_bytes, chunk_bits); return -1; }
-    if (workspace_bytes) *workspace_bytes = make_decode_plan(n, h, w, c, sampling, max_segment_bytes, chunk_bits).total;
+int jpeg_decode_bytes(int n, int h, int w, int c, int sampling, int restart_interval, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes) {
+    const char* bad = check_decode_shape(n, h, w, c, sampling, restart_interval, max_segment_bytes, chunk_bits);
+    if (bad) {
+        set_error("jpeg_decode_u8: %s (n %d, %d x %d x %d, sampling %d, restart_interval %d, segment %zu, chunk_bits %d)", bad, n, h, w, c, sampling, restart_interval,
+                  max_segment_bytes, chunk_bits);
+        return -1;
+    }
+    if (workspace_bytes) *workspace_bytes = make_decode_plan(n, h, w, c, sampling, restart_interval, max_segment_bytes, chunk_bits).total;
     return 0;
 }
 
-int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, const uint64_t* seg_offsets,
-                          const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace, size_t workspace_bytes, int chunk_bits, hipStream_t s) {
-    const char* bad = check_decode_shape(n, h, w, c, sampling, 0, chunk_bits);
-    if (bad) { set_error("jpeg_decode_u8: %s (n %d, %d x %d x %d, sampling %d, chunk_bits %d)", bad, n, h, w, c, sampling, chunk_bits); return -1; }
+int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, int restart_interval,
+                          const uint64_t* seg_offsets, const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace, size_t workspace_bytes,
+                          int chunk_bits, hipStream_t s) {
+    const char* bad = check_decode_shape(n, h, w, c, sampling, restart_interval, 0, chunk_bits);
+    if (bad) {
+        set_error("jpeg_decode_u8: %s (n %d, %d x %d x %d, sampling %d, restart_interval %d, chunk_bits %d)", bad, n, h, w, c, sampling, restart_interval, chunk_bits);
+        return -1;
+    }
     size_t longest = 0;
     for (int i = 0; i < n; ++i) {
         if (seg_offsets[i] > files_bytes || seg_lengths[i] > files_bytes - seg_offsets[i]) {
@@ -1305,9 +1454,9 @@ int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_
         }
         longest = seg_lengths[i] > longest ? seg_lengths[i] : longest;
     }
-    if ((bad = check_decode_shape(n, h, w, c, sampling, longest, chunk_bits))) { set_error("jpeg_decode_u8: %s", bad); return -1; }
+    if ((bad = check_decode_shape(n, h, w, c, sampling, restart_interval, longest, chunk_bits))) { set_error("jpeg_decode_u8: %s", bad); return -1; }
     if ((uintptr_t)workspace % 8 || (uintptr_t)record % 4) { set_error("jpeg_decode_u8: the workspace must be 8-byte and the record 4-byte aligned"); return -1; }
-    const DecPlan p = make_decode_plan(n, h, w, c, sampling, longest, chunk_bits);
+    const DecPlan p = make_decode_plan(n, h, w, c, sampling, restart_interval, longest, chunk_bits);
     if (workspace_bytes < p.total) { set_error("jpeg_decode_u8: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return -1; }
     if ((p.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull) { set_error("jpeg_decode_u8: %d x %d: too many blocks for one launch", h, w); return -1; }
     char* ws = (char*)workspace;
@@ -1318,7 +1467,8 @@ int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_
     uint32_t* count = (uint32_t*)(ws + p.o_count);
     int16_t* coef = (int16_t*)(ws + p.o_coef);
     uint8_t* planes = (uint8_t*)(ws + p.o_planes);
-    const DecShape g{p.H, p.V, p.bpm, p.c, p.nblk};
+    uint32_t* itab = restart_interval ? (uint32_t*)(ws + p.o_itab) : nullptr;
+    const DecShape g{p.H, p.V, p.bpm, p.c, p.nblk, p.ri, p.nint};
     const DecPlanes pg{p.c, p.H, p.V, p.bpm, p.mw, p.yw, p.cw, p.nblk, p.o_cb, p.o_cr, p.plane_stride};
     for (int first = 0; first < n; first += DEC_SEG_BATCH) {
         DecSegBatch b{};
@@ -1326,10 +1476,13 @@ int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_
         for (int i = 0; i < count_; ++i) b.off[i] = seg_offsets[first + i], b.len[i] = seg_lengths[first + i];
         jpegd_table_kernel<<<1, DEC_SEG_BATCH, 0, s>>>(b, first, count_, seg, meta);
     }
-    jpegd_unstuff_kernel<<<n, DEC_THREADS, 0, s>>>(files, seg, meta, (uint8_t*)stream, p.cap_words);
+    if (restart_interval)
+        jpegd_unstuff_kernel<true><<<n, DEC_THREADS, 0, s>>>(files, seg, meta, (uint8_t*)stream, p.cap_words, itab, p.nint);
+    else
+        jpegd_unstuff_kernel<false><<<n, DEC_THREADS, 0, s>>>(files, seg, meta, (uint8_t*)stream, p.cap_words, nullptr, p.nint);
     if (hipMemsetAsync(coef, 0, (size_t)n * p.nblk * 64 * sizeof(int16_t), s) != hipSuccess) { set_error("jpeg_decode_u8: hipMemsetAsync failed"); return -1; }
-    jpegd_settle_kernel<<<n, DEC_THREADS, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g);
-    jpegd_write_kernel<<<dim3((p.nsub_max + 255) / 256, n), 256, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, coef);
+    jpegd_settle_kernel<<<n, DEC_THREADS, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, itab);
+    jpegd_write_kernel<<<dim3((p.nsub_max + 255) / 256, n), 256, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, coef, itab);
     jpegd_dc_kernel<<<n, DEC_THREADS, 0, s>>>(coef, meta, g, record);
     jpegd_idct_kernel<<<dim3((unsigned)((p.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG), n), IDCT_PER_WG * 8, 0, s>>>(coef, blobs, planes, pg);
     const dim3 grid((w + 255) / 256, h, n);

@@ -1,13 +1,17 @@
-"""Reading a baseline JPEG file on the host for the device decoder (csrc/jpeg.hip, adain_jpeg_decode_u8): a walk over the file's markers
-that returns a description of the file and packs its tables into one small blob, or raises ``UnsupportedJpeg`` with the reason in words.
+"""Reading a baseline JPEG file on the host for the device decoder (csrc/jpeg.hip, adain_jpeg_decode_u8 / adain_jpeg_decode_restart_u8):
+a walk over the file's markers that returns a description of the file and packs its tables into one small blob, or raises
+``UnsupportedJpeg`` with the reason in words.
 
 Taken: 8-bit baseline (SOF0) and extended sequential Huffman (SOF1) files with ONE interleaved scan, one component (grey, sampled 1 x 1)
 or three with JFIF's ids 1, 2, 3, chroma sampled 1 x 1 and luma 1 x 1 (4:4:4), 2 x 1 (4:2:2) or 2 x 2 (4:2:0), 8-bit quantisation tables,
-Huffman tables 0 and 1 of either class, no restart interval, the entropy-coded segment followed by EOI.  Everything else is refused and
-stays with PIL: progressive, arithmetic, lossless and 12-bit files, several scans, non-interleaved scans, CMYK / YCCK or an Adobe APP14
-segment with transform 0, other component ids, any other sampling (4:4:0 and 4:1:1 included), DNL, a restart interval (DRI other than
-0: the device decoder does not remove RSTn markers yet), and truncated or inconsistent segments.  EXIF orientation is ignored, as PIL
-ignores it.  The parser never makes a caller fail: every caller catches ``UnsupportedJpeg`` and takes the PIL path.
+Huffman tables 0 and 1 of either class, the entropy-coded segment followed by EOI.  A restart interval (DRI other than 0) is taken with
+``parse(data, restart=True)``: the walk then passes the RSTn markers inside the scan, which stay in the segment - the device removes
+them - and must be ceil(MCUs / Ri) - 1 in number, numbered D0..D7 in turn, with no fill byte in front of any; ``restart_interval`` is
+the file's Ri.  By default such a file is refused as before.  Everything else is refused and stays with PIL: progressive, arithmetic,
+lossless and 12-bit files, several scans, non-interleaved scans, CMYK / YCCK or an Adobe APP14 segment with transform 0, other
+component ids, any other sampling (4:4:0 and 4:1:1 included), DNL, restart markers that are missing, surplus or out of order (no
+resynchronisation is tried), and truncated or inconsistent segments.  EXIF orientation is ignored, as PIL ignores it.  The parser never
+makes a caller fail: every caller catches ``UnsupportedJpeg`` and takes the PIL path.
 
 The blob (``BLOB_BYTES`` per file, the layout csrc/jpeg.hip's ``FileTables`` reads):
   4 Huffman tables in the order DC0, DC1, AC0, AC1, 912 bytes each - look[256] uint16: for the next 8 bits of the stream, (code length
@@ -43,9 +47,9 @@ class JpegFile:
     huffman: dict               # (class, id) -> (bits [16], huffval bytes), class 0 DC, 1 AC; the tables the scan uses
     dc_sel: tuple               # per component
     ac_sel: tuple
-    restart_interval: int       # always 0 for a file that is taken
+    restart_interval: int       # MCUs per restart interval; 0: none (always, unless parsed with restart=True)
     seg_offset: int             # of the entropy-coded segment in the file
-    seg_length: int
+    seg_length: int             # up to EOI, RSTn markers included
     blob: bytes                 # BLOB_BYTES
 
     @property
@@ -94,15 +98,15 @@ _SOF_REFUSED = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "diff
                 0xCD: "arithmetic coding (SOF13)", 0xCE: "arithmetic coding (SOF14)", 0xCF: "arithmetic coding (SOF15)"}
 
 
-def parse(data):
-    """bytes of a file -> JpegFile, or UnsupportedJpeg."""
+def parse(data, restart=False):
+    """bytes of a file -> JpegFile, or UnsupportedJpeg.  ``restart``: take files with a restart interval too."""
     data = bytes(data)
     n = len(data)
     if n < 4 or data[:2] != b"\xff\xd8":
         raise UnsupportedJpeg("not a JPEG file (no SOI)")
     qt, huff = {}, {}
     frame = None
-    restart = 0
+    restart_interval = 0
     adobe_transform = None
     at = 2
     while True:
@@ -188,7 +192,7 @@ def parse(data):
         elif m == 0xDD:
             if len(body) != 2:
                 raise UnsupportedJpeg("inconsistent: DRI length")
-            restart = (body[0] << 8) | body[1]
+            restart_interval = (body[0] << 8) | body[1]
         elif m == 0xEE:
             if body[:5] == b"Adobe" and len(body) >= 12:
                 adobe_transform = body[11]
@@ -207,8 +211,8 @@ def parse(data):
                 raise UnsupportedJpeg("scan components out of order")
             if tuple(body[-3:]) != (0, 63, 0):
                 raise UnsupportedJpeg("a scan that is not the whole spectrum at full precision")
-            if restart != 0:
-                raise UnsupportedJpeg(f"a restart interval ({restart} MCUs)")
+            if restart_interval != 0 and not restart:
+                raise UnsupportedJpeg(f"a restart interval ({restart_interval} MCUs)")
             for _, d, a in sel:
                 if d > 1 or a > 1:
                     raise UnsupportedJpeg("Huffman table ids above 1")
@@ -219,22 +223,36 @@ def parse(data):
                     raise UnsupportedJpeg("a missing quantisation table")
             seg = at + ln
             end = seg
-            while True:                  # the segment ends at the first marker that is neither a stuffed FF 00 nor a fill byte
+            markers = 0
+            while True:                  # the segment ends at the first marker that is neither a stuffed FF 00 nor (restart) the RSTn that is due
                 end = data.find(b"\xff", end)
                 if end < 0 or end + 1 >= n:
                     raise UnsupportedJpeg("truncated: no marker behind the entropy-coded segment")
                 if data[end + 1] == 0:
                     end += 2
                     continue
+                if restart_interval != 0 and 0xD0 <= data[end + 1] <= 0xD7:
+                    if data[end + 1] != 0xD0 + markers % 8:
+                        raise UnsupportedJpeg(f"restart marker {markers} is FF{data[end + 1]:02X}, not FF{0xD0 + markers % 8:02X}")
+                    markers += 1
+                    end += 2
+                    continue
+                if restart_interval != 0 and data[end + 1] == 0xFF:
+                    raise UnsupportedJpeg("a fill byte in front of a marker in a scan with restart intervals")
                 break
             if data[end + 1] != 0xD9:
                 raise UnsupportedJpeg(f"marker FF{data[end + 1]:02X} behind the scan (more than one scan, restart markers or damage)")
             if end - seg > MAX_SEGMENT_BYTES:
                 raise UnsupportedJpeg("an entropy-coded segment of 2^28 bytes or more")
+            if restart_interval != 0:
+                hh, vv = comps[0][1], comps[0][2]
+                nmcu = -(-w // (8 * hh)) * -(-h // (8 * vv))
+                if markers != -(-nmcu // restart_interval) - 1:
+                    raise UnsupportedJpeg(f"{markers} restart markers where {nmcu} MCUs in intervals of {restart_interval} have {-(-nmcu // restart_interval) - 1}")
             used = {(0, d) for _, d, _ in sel} | {(1, a) for _, _, a in sel}
             tables = {k: v for k, v in huff.items() if k in used}
             q = np.stack([qt[x[3]] for x in comps])
             dc_sel, ac_sel = tuple(s[1] for s in sel), tuple(s[2] for s in sel)
-            return JpegFile(h, w, nc, SAMPLINGS[(comps[0][1], comps[0][2])], q, tables, dc_sel, ac_sel, 0, seg, end - seg,
+            return JpegFile(h, w, nc, SAMPLINGS[(comps[0][1], comps[0][2])], q, tables, dc_sel, ac_sel, restart_interval, seg, end - seg,
                             _pack_blob(nc, q, tables, dc_sel, ac_sel))
         at += ln

@@ -104,6 +104,9 @@ SIGNATURES = {
     "adain_jpeg_decode_u8_bytes": (_c_int, [_c_int] * 5 + [_c_size_t, _c_int, ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_decode_u8": (_c_int, [_c_void_p, _c_size_t, _c_void_p] + [_c_int] * 5 + [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
                                       _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p]),
+    "adain_jpeg_decode_restart_u8_bytes": (_c_int, [_c_int] * 6 + [_c_size_t, _c_int, ctypes.POINTER(_c_size_t)]),
+    "adain_jpeg_decode_restart_u8": (_c_int, [_c_void_p, _c_size_t, _c_void_p] + [_c_int] * 6 + [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                              _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p]),
     "adain_nhwc_to_nchw": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_nchw_to_nhwc": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_conv3x3_wino4_packed_floats": (_c_size_t, [_c_int, _c_int]),
@@ -889,14 +892,16 @@ def jpeg_roundtrip_u8(u8, quality=JPEG_DEFAULT_QUALITY):
     return out.reshape(u8.shape)
 
 
-# --- input files (adain_jpeg_decode_u8) -----------------------------------------------------------------------------------------------
-def jpeg_decode_sizes(n, h, w, c, sampling, max_segment_bytes, chunk_bits=0):
-    """workspace_bytes of adain_jpeg_decode_u8_bytes: the scratch of an n-file call whose longest entropy-coded segment has
-    ``max_segment_bytes``.  Host only.  AdainHipError for a refused shape."""
+# --- input files (adain_jpeg_decode_restart_u8; at restart interval 0 that is adain_jpeg_decode_u8) ------------------------------------
+def jpeg_decode_sizes(n, h, w, c, sampling, max_segment_bytes, chunk_bits=0, restart_interval=0):
+    """workspace_bytes of adain_jpeg_decode_restart_u8_bytes: the scratch of an n-file call whose longest entropy-coded segment has
+    ``max_segment_bytes`` and whose files have ``restart_interval`` MCUs per restart interval (0: none).  Host only.  AdainHipError for
+    a refused shape."""
     ws = _c_size_t()
-    rc = lib().adain_jpeg_decode_u8_bytes(int(n), int(h), int(w), int(c), int(sampling), int(max_segment_bytes), int(chunk_bits), ctypes.byref(ws))
+    rc = lib().adain_jpeg_decode_restart_u8_bytes(int(n), int(h), int(w), int(c), int(sampling), int(restart_interval), int(max_segment_bytes), int(chunk_bits),
+                                                  ctypes.byref(ws))
     if rc != 0:
-        raise _failure("adain_jpeg_decode_u8_bytes", rc)
+        raise _failure("adain_jpeg_decode_restart_u8_bytes", rc)
     return ws.value
 
 
@@ -904,13 +909,16 @@ _jpeg_decode_lock = threading.Lock()
 
 
 def jpeg_decode_upload(parsed, datas, device, lead=0):
-    """The one upload of a ``jpeg_decode_batch`` call: the table blobs of n files of ONE geometry, ``lead`` spare bytes, then their
-    entropy-coded segments back to back -> (device uint8 tensor, segment offsets behind the blobs, segment lengths)."""
+    """The one upload of a ``jpeg_decode_batch`` call: the table blobs of n files of ONE geometry and ONE restart interval, ``lead``
+    spare bytes, then their entropy-coded segments (RSTn markers and all) back to back -> (device uint8 tensor, segment offsets behind
+    the blobs, segment lengths)."""
     from . import jpeg_file
 
     n = len(parsed)
     if n < 1 or any(p.geometry != parsed[0].geometry for p in parsed) or len(datas) != n:
         raise AdainHipError("jpeg_decode_batch: expected the files of one geometry")
+    if any(p.restart_interval != parsed[0].restart_interval for p in parsed):
+        raise AdainHipError("jpeg_decode_batch: expected the files of one restart interval")
     device = torch.device(device)
     if device.type != "cuda":
         raise AdainHipError("jpeg_decode_u8: expected a GPU device (the device decoder has no CPU form)")
@@ -924,8 +932,9 @@ def jpeg_decode_upload(parsed, datas, device, lead=0):
     return torch.frombuffer(host, dtype=torch.uint8).to(device), offsets, lengths
 
 
-def jpeg_decode_launch(up, offsets, lengths, geometry, chunk_bits=0):
-    """adain_jpeg_decode_u8 on an upload of ``jpeg_decode_upload`` -> (frames uint8 [n,h,w,c], record int32 [n,2]) on its device."""
+def jpeg_decode_launch(up, offsets, lengths, geometry, chunk_bits=0, restart_interval=0):
+    """adain_jpeg_decode_restart_u8 on an upload of ``jpeg_decode_upload`` whose files have ``restart_interval`` MCUs per restart
+    interval (0: none) -> (frames uint8 [n,h,w,c], record int32 [n,2]) on its device."""
     from . import jpeg_file
 
     n = len(lengths)
@@ -934,21 +943,22 @@ def jpeg_decode_launch(up, offsets, lengths, geometry, chunk_bits=0):
     off = (ctypes.c_uint64 * n)(*offsets)
     ln = (ctypes.c_uint32 * n)(*lengths)
     # the workspace is shared per stream: calls from several threads (the video path's fetch pool) on one stream must not interleave
-    with _jpeg_decode_lock, scratch(up.device, "jpeg_decode", jpeg_decode_sizes, n, h, w, c, sampling, max(lengths), chunk_bits) as ws:
+    with _jpeg_decode_lock, scratch(up.device, "jpeg_decode", jpeg_decode_sizes, n, h, w, c, sampling, max(lengths), chunk_bits,
+                                    restart_interval) as ws:
         out = torch.empty((n, h, w, c), dtype=torch.uint8, device=up.device)
         record = torch.empty((n, 2), dtype=torch.int32, device=up.device)
-        _launch("adain_jpeg_decode_u8", up.data_ptr() + blobs, up.numel() - blobs, up.data_ptr(), n, h, w, c, sampling, off, ln, out.data_ptr(),
-                record.data_ptr(), ws.data_ptr(), ws.numel(), int(chunk_bits))
+        _launch("adain_jpeg_decode_restart_u8", up.data_ptr() + blobs, up.numel() - blobs, up.data_ptr(), n, h, w, c, sampling, int(restart_interval), off, ln,
+                out.data_ptr(), record.data_ptr(), ws.data_ptr(), ws.numel(), int(chunk_bits))
     return out, record
 
 
 def jpeg_decode_batch(parsed, datas, device, chunk_bits=0, lead=0):
-    """``parsed``: jpeg_file.JpegFile of n files of ONE geometry, ``datas``: their bytes -> (frames uint8 [n,h,w,c], record int32 [n,2]:
-    status and rounds per file), both on ``device``.  One upload - the table blobs, ``lead`` spare bytes, then the entropy-coded
-    segments back to back at whatever byte offsets that gives - and one call of adain_jpeg_decode_u8; nothing comes back and nothing
-    waits.  A frame whose status is not 0 is unspecified."""
+    """``parsed``: jpeg_file.JpegFile of n files of ONE geometry and ONE restart interval (anything else is an error), ``datas``: their
+    bytes -> (frames uint8 [n,h,w,c], record int32 [n,2]: status and rounds per file), both on ``device``.  One upload - the table
+    blobs, ``lead`` spare bytes, then the entropy-coded segments back to back at whatever byte offsets that gives - and one call of
+    adain_jpeg_decode_restart_u8; nothing comes back and nothing waits.  A frame whose status is not 0 is unspecified."""
     up, offsets, lengths = jpeg_decode_upload(parsed, datas, device, lead)
-    return jpeg_decode_launch(up, offsets, lengths, parsed[0].geometry, chunk_bits)
+    return jpeg_decode_launch(up, offsets, lengths, parsed[0].geometry, chunk_bits, parsed[0].restart_interval)
 
 
 def _pil_pixels(data, mode):
@@ -961,13 +971,15 @@ def _pil_pixels(data, mode):
     return np.asarray(img.convert(mode) if mode is not None else img)
 
 
-def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None):
+def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None, restart=False):
     """The bytes of image files (a list, or one ``bytes``) -> device uint8 tensors (a list, or one): per file the array
     ``np.asarray(Image.open(io.BytesIO(data)))`` gives - [h,w,3] for a colour file, [h,w] for a grey one - or, with ``mode`` "RGB" / "L",
     ``np.asarray(Image.open(...).convert(mode))`` (a grey file is replicated for "RGB"; "L" from a colour file goes to the host).  Baseline
-    JPEG files are decoded on the device (adain_jpeg_decode_u8; grouped by geometry, one call and one upload per group, the record
-    read once); whatever jpeg_file.parse refuses, and any file whose status comes back non-zero, is decoded by PIL on the host exactly
-    as before and uploaded - PIL's exceptions pass through.  ``report`` (a list): per file "device" or "host: <why>", and the rounds."""
+    JPEG files are decoded on the device (adain_jpeg_decode_restart_u8; grouped by geometry and restart interval, one call and one
+    upload per group, the record read once); whatever jpeg_file.parse refuses, and any file whose status comes back non-zero, is decoded
+    by PIL on the host exactly as before and uploaded - PIL's exceptions pass through.  ``restart``: files with a restart interval (DRI,
+    RSTn markers) are decoded on the device as well; False, the default, leaves them to PIL as before.  ``report`` (a list): per file
+    "device" or "host: <why>", and the rounds."""
     from . import jpeg_file
 
     single = isinstance(files, (bytes, bytearray, memoryview))
@@ -978,10 +990,10 @@ def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None):
     results, why, rounds, groups = [None] * len(datas), [None] * len(datas), [0] * len(datas), {}
     for i, d in enumerate(datas):
         try:
-            p = jpeg_file.parse(d)
+            p = jpeg_file.parse(d, restart=restart)
             if mode == "L" and p.c == 3:
                 raise jpeg_file.UnsupportedJpeg("a colour file where grey is wanted")
-            groups.setdefault(p.geometry, []).append((i, p))
+            groups.setdefault((p.geometry, p.restart_interval), []).append((i, p))
         except jpeg_file.UnsupportedJpeg as e:
             why[i] = str(e)
     launched = [(members, jpeg_decode_batch([p for _, p in members], [datas[i] for i, _ in members], device, chunk_bits)) for members in groups.values()]
@@ -1005,7 +1017,7 @@ def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None):
 def jpeg_decode_rgb_file(path, device):
     """The frame ``np.asarray(Image.open(path).convert("RGB"))`` as a uint8 [h,w,3] tensor on ``device``, decoded there - or None when
     the file is not one the device decoder takes (not a .jpg / .jpeg name, refused by jpeg_file.parse, a non-zero status): the caller
-    then decodes it with PIL as before.  Reads the record once (waits for the call)."""
+    then decodes it with PIL as before.  Files with restart intervals are taken.  Reads the record once (waits for the call)."""
     from . import jpeg_file
 
     if not str(path).lower().endswith((".jpg", ".jpeg")) or torch.device(device).type != "cuda":
@@ -1013,7 +1025,7 @@ def jpeg_decode_rgb_file(path, device):
     with open(str(path), "rb") as f:
         data = f.read()
     try:
-        parsed = jpeg_file.parse(data)
+        parsed = jpeg_file.parse(data, restart=True)
     except jpeg_file.UnsupportedJpeg:
         return None
     out, record = jpeg_decode_batch([parsed], [data], device)

@@ -509,7 +509,24 @@ ADAIN_API int adain_jpeg_roundtrip_u8(const uint8_t* src_u8, int n, int h, int w
  * Refused with ADAIN_EINVAL before anything is launched: a null pointer, c other than 1 and 3, sampling outside 0..2 or not 0 for
  * c = 1, h or w outside 1..65535, n outside 1..65535, a chunk_bits that is neither 0 nor a multiple of 32 from 32 up, a segment that
  * leaves `files` or is 2^28 bytes or longer, a workspace_bytes below the query's for the longest segment, a workspace that is not
- * 8-byte aligned or a record that is not 4-byte aligned.  7 kernel launches, one memset and one more launch per 64 files per call. */
+ * 8-byte aligned or a record that is not 4-byte aligned.  7 kernel launches, one memset and one more launch per 64 files per call.
+ *
+ * adain_jpeg_decode_restart_u8 / _bytes (added without a version change): the same call for files that carry a restart interval,
+ * restart_interval = the DRI segment's Ri in MCUs, ONE value per call, 0..65535 (anything else: ADAIN_EINVAL before any launch).  0 means
+ * "no restart interval": that is adain_jpeg_decode_u8, which is this entry at 0 with an unchanged workspace query.  With Ri > 0 the
+ * segments still run from behind SOS to EOI and hold their FF D0..D7 markers; the device finds and removes them itself while it
+ * unstuffs, keeps each interval's first stream byte in the workspace, decodes every interval from its own byte-aligned all-zero state
+ * (subsequences are cut per interval, so the rounds are the largest count any interval needs) and restarts the DC sums at every
+ * interval's first MCU.  nint = ceil(MCUs / Ri); the status is also non-zero when the markers found are not nint - 1 or marker m is not
+ * FF D(m mod 8) - no resynchronisation is tried, such a file goes to the host - and when any interval has damage, too few blocks or a
+ * last block that does not end inside the interval's last byte.  Whatever the bytes, the writes stay inside dst, record and the
+ * workspace.  The rules: csrc/jpeg.hip, restated in tests/jpeg_restart_ref.py.  The same launches per call as above. */
+ADAIN_API int adain_jpeg_decode_restart_u8_bytes(int n, int h, int w, int c, int sampling, int restart_interval, size_t max_segment_bytes,
+                                                 int chunk_bits, size_t* workspace_bytes);
+ADAIN_API int adain_jpeg_decode_restart_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c,
+                                           int sampling, int restart_interval, const uint64_t* segment_offsets,
+                                           const uint32_t* segment_lengths, uint8_t* dst_u8, int32_t* record, void* workspace,
+                                           size_t workspace_bytes, int chunk_bits, adain_stream_t stream);
 ADAIN_API int adain_jpeg_decode_u8_bytes(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits,
                                          size_t* workspace_bytes);
 ADAIN_API int adain_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling,

@@ -1,7 +1,8 @@
 """Times the device JPEG file decoder (csrc/jpeg.hip, adain_jpeg_decode_u8) against the host route through Pillow on the same machine,
 one file per call: files at 256 x 456 and 1080 x 1920, saved by Pillow at its default settings (quality 75, 4:2:0) and at quality 95,
-of a stylised synthetic frame (seed-0 weights) and of uniform noise.  Median and interquartile range over --reps calls (>= 200) after
-warm-up:
+of a stylised synthetic frame (seed-0 weights) and of uniform noise, each also with one restart interval per MCU row (Pillow's
+``restart_marker_rows=1``, the ``_restart`` rows: adain_jpeg_decode_restart_u8).  Median and interquartile range over --reps calls (>= 200)
+after warm-up:
   kernel_ms  adain_jpeg_decode_u8 on bytes that are already on the device, HIP events
   device_ms  wall clock from ``bytes`` to a device frame with ``rt.jpeg_decode_u8``: marker walk, upload, decode, the record read
   host_ms    the route without it on one thread: ``Image.open`` + ``np.asarray`` + upload, synchronised
@@ -129,20 +130,21 @@ def main():
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         frames = {"stylised": engine.stylize_u8(source, alpha=0.5)[0].cpu().numpy(), "noise": np.random.default_rng(0).integers(0, 256, (h, w, 3), dtype=np.uint8)}
         for kind, frame in frames.items():
-            for label, kw in (("default", {}), ("q95", {"quality": 95})):
+            for label, kw in (("default", {}), ("q95", {"quality": 95}), ("default_restart", {"restart_marker_rows": 1}),
+                              ("q95_restart", {"quality": 95, "restart_marker_rows": 1})):
                 data = jpeg_bytes(frame, **kw)
-                parsed = jpeg_file.parse(data)
+                parsed = jpeg_file.parse(data, restart=True)
                 up, offsets, lengths = rt.jpeg_decode_upload([parsed], [data], dev)
-                launch = lambda chunk_bits=0: rt.jpeg_decode_launch(up, offsets, lengths, parsed.geometry, chunk_bits)
+                launch = lambda chunk_bits=0: rt.jpeg_decode_launch(up, offsets, lengths, parsed.geometry, chunk_bits, parsed.restart_interval)
                 name = f"{kind}_{label}_{h}x{w}"
                 t0 = time.perf_counter()
                 kernel = event_ms(launch, reps, 20)
                 tel.window(f"kernel_{name}", t0, time.perf_counter())
                 report = []
-                same = bool(torch.equal(rt.jpeg_decode_u8(data, dev, report=report), host_route(data, dev)))
-                device = wall_ms(lambda: rt.jpeg_decode_u8(data, dev), reps, 5)
+                same = bool(torch.equal(rt.jpeg_decode_u8(data, dev, report=report, restart=True), host_route(data, dev)))
+                device = wall_ms(lambda: rt.jpeg_decode_u8(data, dev, restart=True), reps, 5)
                 host = wall_ms(lambda: host_route(data, dev), reps, 3)
-                res["sizes"][name] = {"file_bytes": len(data), "path": report[0]["path"], "rounds": report[0]["rounds"], "same_pixels_as_host": same,
+                res["sizes"][name] = {"file_bytes": len(data), "restart_interval": parsed.restart_interval, "path": report[0]["path"], "rounds": report[0]["rounds"], "same_pixels_as_host": same,
                                       "kernel_ms": kernel, "device_ms": device, "host_ms": host, "host_over_device": round(host["median"] / device["median"], 2),
                                       "device_is_faster": device["median"] + device["iqr"] + host["iqr"] < host["median"]}
                 if h == 1080:
