@@ -6,7 +6,7 @@ Style_3DGS/AdaIN/run_depth.py (:13-55), so existing invocations keep working:
 Extra flags make the depth-aware mode usable offline (the reference pulls MiDaS through torch.hub at run time):
 ``--depth_npy`` takes a precomputed proximity map, ``--vgg`` / ``--decoder`` the checkpoint paths; ``--jpeg_on_device`` encodes the
 result's JPEG file on the GPU (the same bytes); ``--jpeg_decode_on_device`` decodes a baseline JPEG
-content there too (the same pixels); ``--coral_on_device`` preserves the content's colours (``adain_inference``'s
+content there too (the same pixels), ``--jpeg_decode_progressive`` (which implies it) a progressive one as well; ``--coral_on_device`` preserves the content's colours (``adain_inference``'s
 ``preserve_color``, which the reference's CLI does not expose) with CORAL computed on the GPU.
 
 Style interpolation (the upstream AdaIN CLI's flag, Style_3DGS/AdaIN/test_video.py:77-79): ``--style a.jpg,b.jpg
@@ -18,6 +18,7 @@ import argparse
 import numpy as np
 import torch
 
+from . import test as adain_test
 from .test import adain_inference, set_device_coral, set_device_jpeg, set_device_jpeg_decode
 
 # (flag, argparse keyword arguments) — names and defaults as in the reference CLI
@@ -38,6 +39,7 @@ _EXTRA_FLAGS = (
     ("--jpeg_on_device", dict(action="store_true", help="encode the output JPEG on the GPU instead of in PIL (byte-identical file)")),
     ("--coral_on_device", dict(action="store_true", help="preserve the content's colours (preserve_color) with CORAL computed on the GPU")),
     ("--jpeg_decode_on_device", dict(action="store_true", help="decode a baseline JPEG content on the GPU instead of in PIL (the same pixels)")),
+    ("--jpeg_decode_progressive", dict(action="store_true", help="decode a progressive JPEG content on the GPU too (implies --jpeg_decode_on_device)")),
 )
 
 
@@ -62,7 +64,8 @@ def main(argv=None):
         proximity = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
     prev = set_device_jpeg(ns.jpeg_on_device)
     prev_coral = set_device_coral(ns.coral_on_device)
-    prev_decode = set_device_jpeg_decode(ns.jpeg_decode_on_device)
+    prev_progressive = adain_test._device_jpeg_decode_progressive
+    prev_decode = set_device_jpeg_decode(ns.jpeg_decode_on_device or ns.jpeg_decode_progressive, progressive=ns.jpeg_decode_progressive)
     style, mix = ns.style, {}
     if ns.style_interpolation_weights:
         style = ns.style.split(",")
@@ -76,7 +79,7 @@ def main(argv=None):
     finally:
         set_device_jpeg(prev)
         set_device_coral(prev_coral)
-        set_device_jpeg_decode(prev_decode)
+        set_device_jpeg_decode(prev_decode, progressive=prev_progressive)
 
 
 if __name__ == "__main__":

@@ -178,13 +178,14 @@ def device_transform_u8(img, size, crop, device, mark=None):
 def device_decode_transform_u8(path, size, crop, device, mark=None):
     """``device_transform_u8`` of the colour JPEG file at ``path`` without PIL: the file's bytes go up, the frame is decoded on the
     device (adain_jpeg_decode_u8: Pillow's pixels) and resized there.  None when the file is not a three-component baseline JPEG the
-    decoder takes, or did not decode cleanly, or the transform is not the device's: the caller takes the PIL path."""
+    decoder takes (or, with ``set_device_jpeg_decode(True, progressive=True)``, a progressive one), or did not decode cleanly, or the
+    transform is not the device's: the caller takes the PIL path."""
     from .. import jpeg_file
 
     with open(str(path), "rb") as f:
         data = f.read()
     try:
-        parsed = jpeg_file.parse(data, restart=True)
+        parsed = jpeg_file.parse(data, restart=True, progressive=_device_jpeg_decode_progressive)
     except jpeg_file.UnsupportedJpeg:
         return None
     if parsed.c != 3:                           # PIL opens a grey file as mode L, which keeps the host transform
@@ -195,7 +196,10 @@ def device_decode_transform_u8(path, size, crop, device, mark=None):
     if mark is not None:
         with torch.cuda.device(device):
             mark()
-    out, record = rt.jpeg_decode_batch([parsed], [data], device)
+    if isinstance(parsed, jpeg_file.ProgressiveJpegFile):
+        out, record = rt.jpeg_decode_progressive_batch([parsed], [data], device)
+    else:
+        out, record = rt.jpeg_decode_batch([parsed], [data], device)
     if record[0, 0].item() != 0:
         return None
     return _device_resize(out, parsed.w, parsed.h, plan)
@@ -309,16 +313,19 @@ def set_device_jpeg(enabled):
 
 
 _device_jpeg_decode_on = False
+_device_jpeg_decode_progressive = False
 
 
-def set_device_jpeg_decode(enabled):
+def set_device_jpeg_decode(enabled, progressive=False):
     """True: the cached per-call path of ``adain_inference`` reads the bytes of a content given as a ``.jpg`` / ``.jpeg`` path, decodes
     them on the device (adain_jpeg_decode_u8: the pixels Pillow decodes) and resizes that frame there, instead of decoding with PIL and
     uploading the pixels.  Files with restart intervals are decoded there too.  A file the decoder does not take (progressive, grey,
     ...: jpeg_file.parse) or that does not decode cleanly, a PIL image passed in by the caller and any other extension take the PIL path
-    as before.  The output file does not change.  Default False.  Returns the previous setting."""
-    global _device_jpeg_decode_on
+    as before.  ``progressive`` (with ``enabled``): progressive files are decoded on the device too (adain_jpeg_decode_progressive_u8);
+    without it they take the PIL path as before.  The output file does not change.  Default False.  Returns the previous ``enabled``."""
+    global _device_jpeg_decode_on, _device_jpeg_decode_progressive
     prev, _device_jpeg_decode_on = _device_jpeg_decode_on, bool(enabled)
+    _device_jpeg_decode_progressive = bool(enabled and progressive)
     return prev
 
 

@@ -584,6 +584,21 @@ int adain_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t
     return adain_jpeg_decode_restart_u8(files, files_bytes, blobs, n, h, w, c, sampling, 0, segment_offsets, segment_lengths, dst, record, workspace, workspace_bytes,
                                         chunk_bits, stream);
 }
+// progressive (SOF2) files: one call per (geometry, scan script)
+int adain_jpeg_decode_progressive_u8_bytes(int n, int h, int w, int c, int sampling, int nscans, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes) {
+    return jpeg_decode_progressive_bytes(n, h, w, c, sampling, nscans, max_segment_bytes, chunk_bits, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, int nscans,
+                                     const int32_t* scans, const uint64_t* segment_offsets, const uint32_t* segment_lengths, uint8_t* dst, int32_t* record,
+                                     void* workspace, size_t workspace_bytes, int chunk_bits, adain_stream_t stream) {
+    if (!files || !blobs || !scans || !segment_offsets || !segment_lengths || !dst || !record || !workspace) {
+        set_error("jpeg_decode_progressive_u8: null pointer");
+        return ADAIN_EINVAL;
+    }
+    const int rc = launch_jpeg_decode_progressive_u8(files, files_bytes, blobs, n, h, w, c, sampling, nscans, scans, segment_offsets, segment_lengths, dst, record,
+                                                     workspace, workspace_bytes, chunk_bits, (hipStream_t)stream);
+    return rc == -1 ? ADAIN_EINVAL : rc;
+}
 
 int adain_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, adain_stream_t stream) {
     if (!in || !out) { set_error("nhwc_to_nchw: null pointer"); return ADAIN_EINVAL; }

@@ -187,6 +187,12 @@ int jpeg_decode_bytes(int n, int h, int w, int c, int sampling, int restart_inte
 int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, int restart_interval,
                           const uint64_t* seg_offsets, const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace, size_t workspace_bytes,
                           int chunk_bits, hipStream_t s);
+// the scans of a progressive (SOF2) file -> the same pixels (the rules: jpeg.hip, tests/jpeg_progressive_ref.py); scans: int32 [nscans][8] =
+// components, their frame indices (3), Ss, Se, Ah, Al; seg_offsets, seg_lengths and blobs are [n][nscans]
+int jpeg_decode_progressive_bytes(int n, int h, int w, int c, int sampling, int nscans, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes);
+int launch_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, int nscans,
+                                      const int32_t* scans, const uint64_t* seg_offsets, const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace,
+                                      size_t workspace_bytes, int chunk_bits, hipStream_t s);
 
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);

@@ -81,6 +81,12 @@
 //   status    per file: 0, or the stream (every interval of it) did not hold exactly the expected blocks ending inside its last byte,
 //             or the restart markers are not the expected ones in order (the caller then uses PIL)
 //   back half the round trip's, with the file's own quantisation tables, three chroma layouts and a grey path
+//
+// The progressive file decoder (adain_jpeg_decode_progressive_u8): the scans of an 8-bit progressive Huffman (SOF2) file with a complete
+// script -> the same coefficient buffer, then the file decoder's back half unchanged.  Its rules, stages and launches per call stand in
+// front of its kernels below ("the progressive file decoder"); in short: every scan's segment is unstuffed on its own, the scans apply in
+// file order, every Huffman-coded scan goes through the fixed-point scheme above with a state of its kind, a DC refinement is one lane
+// per block, and an AC refinement's state carries the block it is in because the bits a block takes depend on the coefficients before it
 #include "common.h"
 
 namespace adain {
@@ -1267,16 +1273,16 @@ __global__ __launch_bounds__(DEC_THREADS) void jpegd_dc_kernel(int16_t* __restri
 struct DecPlanes { int c, H, V, bpm, mw, yw, cw; size_t nblk, o_cb, o_cr, stride; };
 
 // The round trip's IDCT stage on natural-order coefficients with the file's own tables; the planes are whole blocks, Y [8 V mh][8 H mw]
-// first, then (colour) Cb and Cr [8 mh][8 mw].
-__global__ __launch_bounds__(IDCT_PER_WG * 8) void jpegd_idct_kernel(const int16_t* __restrict__ coef, const uint8_t* __restrict__ blobs, uint8_t* __restrict__ planes,
-                                                                     DecPlanes g) {
+// first, then (colour) Cb and Cr [8 mh][8 mw].  blob_stride: bytes from one file's tables to the next file's (a progressive file has a blob per scan).
+__global__ __launch_bounds__(IDCT_PER_WG * 8) void jpegd_idct_kernel(const int16_t* __restrict__ coef, const uint8_t* __restrict__ blobs, size_t blob_stride,
+                                                                     uint8_t* __restrict__ planes, DecPlanes g) {
     constexpr int NB = IDCT_PER_WG, THREADS = NB * 8;
     __shared__ int samp[NB * 72];
     __shared__ int q[192];
     const int t = threadIdx.x, hv = g.H * g.V;
     const size_t f = blockIdx.y, b0 = (size_t)blockIdx.x * NB;
     const int count = (int)min((size_t)NB, g.nblk - b0);
-    if (t < 192) q[t] = blobs[f * sizeof(FileTables) + offsetof(FileTables, q) + t];
+    if (t < 192) q[t] = blobs[f * blob_stride + offsetof(FileTables, q) + t];
     __syncthreads();
     const uint32_t* s32 = (const uint32_t*)(coef + (f * g.nblk + b0) * 64);
     for (int i = t; i < count * 32; i += THREADS) {
@@ -1340,6 +1346,437 @@ __global__ __launch_bounds__(256) void jpegd_pixels_kernel(const uint8_t* __rest
     d[0] = (uint8_t)clamp_u8(yy + ((91881 * v + 32768) >> 16));
     d[1] = (uint8_t)clamp_u8(yy + ((-22554 * u - 46802 * v + 32768) >> 16));
     d[2] = (uint8_t)clamp_u8(yy + ((116130 * u + 32768) >> 16));
+}
+
+// ---- the progressive file decoder: the scans of an SOF2 file -> the coefficient buffer of the file decoder above ---------------------------
+// adain_jpeg_decode_progressive_u8.  The host (jpeg_file.py, parse(progressive=True)) walks the markers, checks the scan script (every
+// coefficient's first scan has Ah = 0, every later one Ah = its current Al and Al = Ah - 1, and at EOI every coefficient stands at Al = 0)
+// and hands over, per file and scan, where the scan's entropy-coded segment lies and one FileTables blob with the Huffman tables in force
+// at that SOS; per call the scan descriptors (components, Ss, Se, Ah, Al).  A complete progressive file holds the quantised coefficients of
+// its sequential twin, so behind the scans the back half above runs unchanged.  tests/jpeg_progressive_ref.py restates the rules in Python.
+//
+// Its rules
+//   streams   every scan's segment is unstuffed on its own (the 00 behind every FF removed); bits big-endian; the reader returns 1-bits
+//             past the stream's end.  No restart intervals.
+//   blocks    an interleaved scan (all components, DC only) covers the MCU grid in the baseline order; a one-component scan covers the
+//             component's own raster, ceil(ceil(w Hi / Hmax) / 8) blocks a row and the same in h rows, row-major - for luma up to one
+//             column and one row less than the MCU grid - and block (by, bx) of it is block (by % V) H + bx % H of MCU (by / V) mw + bx / H
+//             in the coefficient buffer.  Blocks no scan codes stay zero.
+//   symbol    as above: a code in no table costs ONE bit and is damage
+//   DC first  (Ss = Se = 0, Ah = 0) symbol & 15 = size s, s bits v, the difference as above; the differences are summed per component
+//             in SCAN order and the DC term is the sum << Al.  State: position, block in the MCU.
+//   DC refine (Ah > 0) no Huffman code: bit i of the stream belongs to block i of the scan order; a set bit ORs 1 << Al into the DC term
+//   AC first  (1 <= Ss <= Se, Ah = 0, one component) symbol = r << 4 | s at zigzag index k (a block begins at Ss).  s > 0: k += r, the
+//             coefficient there is the value << Al, k += 1.  s = 0, r = 15: k += 16.  s = 0, r < 15: an end-of-band run of 2^r + the next
+//             r bits: this block ends and run - 1 further blocks are empty - the whole run is taken in the step that reads it, so the
+//             state is position and k alone and a step can begin tens of thousands of blocks.  k > Se ends the block.
+//   AC refine (Ah > 0) libjpeg's decode_mcu_AC_refine.  Outside an end-of-band run: symbol r << 4 | s; s = 1: one sign bit follows AT ONCE;
+//             s = 0, r < 15: run = 2^r + r bits, and the rest of this block is walked as a block inside the run; otherwise (s = 1, or
+//             ZRL with r = 15) walk from k: a coefficient with history (non-zero before this scan) reads one correction bit, one
+//             without counts r down and the walk stops at the first of them met with r = 0; s = 1 puts +-(1 << Al) there; k moves behind
+//             it.  Inside a run a block reads one correction bit per coefficient with history from k to Se and ends.  A correction bit
+//             that is set adds (1 << Al) away from zero where (coefficient & (1 << Al)) is 0.  The bits a block takes depend on which of
+//             its coefficients have history, so the state is (position, block of the scan, k, blocks of the run still to end), the
+//             history is a 64-bit mask per block taken BEFORE the scan's settle stage (which therefore reads no coefficient and writes
+//             none), and decoding stops at the scan's last block: steps inside a run may take no bit at all
+//   status    non-zero when in one of the blocks a scan covers: a code in no table, a DC size above 11, an AC size above 10 (first) or
+//             above 1 (refine), a coefficient index past Se, a value << Al that is no int16; when a scan's last block does not end inside
+//             its stream's last byte or is never reached (a DC refinement: the stream's last byte does not hold bit blocks - 1); when a
+//             scan did not settle; when a final DC term is outside -2047..2047.  Whatever the bytes, every index is clamped or checked.
+//
+// Its stages
+//   table, unstuff   the file decoder's kernels over n x scans streams, one launch of each (table: per 64 streams)
+//   per scan, in file order
+//     DC first    settle (the file decoder's scheme, one workgroup per file) + write (differences) + sum (per component in scan order)
+//     DC refine   one launch, a lane per block
+//     AC first    settle + write
+//     AC refine   mask + settle + write
+//   finish    the DC bound and the record: status, and the rounds summed over the Huffman-coded scans
+//   idct / pixels   the file decoder's kernels, unchanged
+// Launches per call: ceil(n scans / 64) table + unstuff + one memset + per scan 3 (DC first), 1 (DC refine), 2 (AC first) or 3 (AC refine)
+// + finish + idct + pixels.
+constexpr int PROG_MAX_SCANS = 32;
+
+struct ProgScan { int ncomp, comp, ss, se, ah, al; uint32_t bw, nblk; };       // comp: of a one-component scan; bw: its blocks per row; nblk: blocks the scan covers
+
+// block sb of the scan's order -> its index in the MCU-ordered coefficient buffer
+__device__ __forceinline__ size_t prog_block(const DecShape& g, const ProgScan& sc, int mw, uint32_t sb) {
+    if (sc.ncomp == g.c) return sb;
+    if (sc.comp > 0) return (size_t)sb * g.bpm + g.H * g.V + sc.comp - 1;
+    const uint32_t by = sb / sc.bw, bx = sb - by * sc.bw;
+    return ((size_t)(by / g.V) * mw + bx / g.H) * g.bpm + (by % g.V) * g.H + bx % g.H;
+}
+
+__device__ __forceinline__ uint32_t prog_bit(const uint32_t* __restrict__ s, uint32_t last_word, uint32_t pos, uint32_t stop) {
+    return peek32(s, last_word, pos, stop) >> 31;
+}
+
+// a scan's last block ended at pos
+__device__ __forceinline__ void prog_last_block(uint32_t pos, uint32_t stop, DecMeta* __restrict__ meta) {
+    if (pos <= stop && pos + 8 > stop) atomicAdd(&meta->done, 1u); else meta->err = 1;
+}
+
+// One correction bit of an AC refinement for the coefficient at p
+__device__ __forceinline__ void prog_correct(int16_t* p, int al) {
+    const int v = *p, p1 = 1 << al;
+    if ((v & p1) == 0) *p = (int16_t)(v >= 0 ? v + p1 : v - p1);
+}
+
+// Decodes a Huffman-coded scan from state st while position < end (and, KIND 2, block < sc.nblk); returns the exit state and counts the
+// blocks begun.  KIND 0, DC first: st = (position, block in MCU); 1, AC first: (position, k); 2, AC refine: (position, block, run, k).
+// WRITE: b is the scan-order index of the block current at st (KIND 2: st.y is); coefficients of the blocks below sc.nblk go to coef.
+template <int KIND, bool WRITE>
+__device__ __forceinline__ uint4 prog_span(const uint32_t* __restrict__ s, uint32_t last_word, uint32_t end, uint32_t stop, uint4 st, const FileTables& T_,
+                                           const DecShape& g, const ProgScan& sc, int mw, const uint64_t* __restrict__ mask, uint32_t* begun,
+                                           int16_t* __restrict__ coef, long long b, DecMeta* __restrict__ meta) {
+    uint32_t pos = st.x, nb = 0;
+    const int hv = g.H * g.V;
+    if (KIND == 0) {
+        const uint32_t bpm = sc.ncomp == g.c ? (uint32_t)g.bpm : 1u;
+        uint32_t blk = st.y < bpm ? st.y : 0u;
+        while (pos < end) {
+            const int comp = sc.ncomp == g.c ? (g.c == 3 && (int)blk >= hv ? (int)blk - hv + 1 : 0) : sc.comp;
+            const uint32_t bits = peek32(s, last_word, pos, stop);
+            const bool live = WRITE && b >= 0 && b < (long long)sc.nblk;
+            const uint32_t e = huff_symbol(T_.huff[T_.sel[comp] & 1], bits);
+            if (e == 0) {
+                pos += 1;
+                if (live) meta->err = 1;
+                continue;
+            }
+            const uint32_t len = e >> 8, sym = e & 255, sz = sym & 15;
+            const uint32_t v = sz ? (bits << len) >> (32 - sz) : 0u;
+            const int value = (sz == 0 || v >= (1u << (sz - 1))) ? (int)v : (int)v - (1 << sz) + 1;
+            ++nb;
+            pos += len + sz;
+            if (live) {
+                coef[prog_block(g, sc, mw, (uint32_t)b) * 64] = (int16_t)value;
+                if (sym > 11) meta->err = 1;
+                if (b == (long long)sc.nblk - 1) prog_last_block(pos, stop, meta);
+            }
+            blk = blk + 1 == bpm ? 0u : blk + 1;
+            ++b;
+        }
+        *begun = nb;
+        return make_uint4(pos, blk, 0u, 0u);
+    } else if (KIND == 1) {
+        const uint32_t ss = (uint32_t)sc.ss, se = (uint32_t)sc.se;
+        uint32_t k = st.y >= ss && st.y <= se ? st.y : ss;
+        const HuffTab& tab = T_.huff[2 + (T_.sel[3 + sc.comp] & 1)];
+        const long long last = (long long)sc.nblk - 1;
+        while (pos < end) {
+            const uint32_t bits = peek32(s, last_word, pos, stop);
+            const bool live = WRITE && b >= 0 && b <= last;
+            const uint32_t e = huff_symbol(tab, bits);
+            if (e == 0) {
+                pos += 1;
+                if (live) meta->err = 1;
+                continue;
+            }
+            if (k == ss) ++nb;
+            const uint32_t len = e >> 8, sym = e & 255, r = sym >> 4, sz = sym & 15;
+            if (sz == 0 && r < 15) {
+                const uint32_t run = (1u << r) + (r ? (bits << len) >> (32 - r) : 0u);      // len + r <= 30
+                pos += len + r;
+                nb += run - 1;
+                if (live && b + (long long)run - 1 >= last) prog_last_block(pos, stop, meta);
+                b += run, k = ss;
+                continue;
+            }
+            if (sz == 0) {
+                pos += len;
+                k += 16;
+                if (k > se && live) meta->err = 1;          // the index passed Se
+            } else {
+                const uint32_t v = (bits << len) >> (32 - sz);
+                const int value = v >= (1u << (sz - 1)) ? (int)v : (int)v - (1 << sz) + 1;
+                pos += len + sz;
+                k += r;
+                if (live) {
+                    const int val = value * (1 << sc.al);
+                    if (k <= se && val >= -32768 && val <= 32767) coef[prog_block(g, sc, mw, (uint32_t)b) * 64 + T.zigzag[k]] = (int16_t)val;
+                    if (k > se || sz > 10 || val < -32768 || val > 32767) meta->err = 1;
+                }
+                k += 1;
+            }
+            if (k > se) {
+                if (live && b == last) prog_last_block(pos, stop, meta);
+                k = ss, ++b;
+            }
+        }
+        *begun = nb;
+        return make_uint4(pos, k, 0u, 0u);
+    } else {
+        const uint32_t ss = (uint32_t)sc.ss, se = (uint32_t)sc.se;
+        uint32_t blk = min(st.y, sc.nblk), run = st.z & 0x7fffu, k = st.w >= ss && st.w <= se ? st.w : ss;
+        const HuffTab& tab = T_.huff[2 + (T_.sel[3 + sc.comp] & 1)];
+        while (blk < sc.nblk && (pos < end || (end == stop && run > 0 && pos <= stop))) {         // a run's blocks may take no bit: the stream's last subsequence ends them
+            const uint64_t m = mask[blk];
+            int16_t* bc = WRITE ? coef + prog_block(g, sc, mw, blk) * 64 : nullptr;
+            bool ends = run > 0;                // the block is inside a run: its rest is walked and it ends
+            if (!ends) {
+                const uint32_t bits = peek32(s, last_word, pos, stop);
+                const uint32_t e = huff_symbol(tab, bits);
+                if (e == 0) {
+                    pos += 1;
+                    if (WRITE) meta->err = 1;
+                    continue;
+                }
+                const uint32_t len = e >> 8, sym = e & 255, sz = sym & 15;
+                uint32_t r = sym >> 4;
+                if (sz == 0 && r < 15) {
+                    run = (1u << r) + (r ? (bits << len) >> (32 - r) : 0u);
+                    pos += len + r;
+                    ends = true;
+                } else {
+                    pos += len;
+                    int put = 0;
+                    if (sz) {
+                        if (WRITE && sz != 1) meta->err = 1;
+                        put = prog_bit(s, last_word, pos, stop) ? (1 << sc.al) : -(1 << sc.al);
+                        pos += 1;
+                    }
+                    while (k <= se) {
+                        if ((m >> k) & 1) {
+                            if (prog_bit(s, last_word, pos, stop) && WRITE) prog_correct(bc + T.zigzag[k], sc.al);
+                            pos += 1;
+                        } else {
+                            if (r == 0) break;
+                            --r;
+                        }
+                        ++k;
+                    }
+                    if (WRITE) {
+                        if (k > se) meta->err = 1;          // the run passed Se (a ZRL included)
+                        else if (put) bc[T.zigzag[k]] = (int16_t)put;
+                    }
+                    ++k;
+                    if (k > se) {
+                        ++blk, k = ss;
+                        if (WRITE && blk == sc.nblk) prog_last_block(pos, stop, meta);
+                    }
+                }
+            }
+            if (ends) {
+                for (; k <= se; ++k)
+                    if ((m >> k) & 1) {
+                        if (prog_bit(s, last_word, pos, stop) && WRITE) prog_correct(bc + T.zigzag[k], sc.al);
+                        pos += 1;
+                    }
+                --run, ++blk, k = ss;
+                if (WRITE && blk == sc.nblk) prog_last_block(pos, stop, meta);
+            }
+        }
+        *begun = 0;
+        return make_uint4(pos, blk, run, k);
+    }
+}
+
+__device__ __forceinline__ bool prog_same(uint4 a, uint4 b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
+
+// One workgroup per file, one scan: the file decoder's settle stage on the scan's own stream.  Every subsequence enters round 0 from
+// (its first bit, 0, 0, 0), which each kind reads as its start-of-block state.
+template <int KIND>
+__global__ __launch_bounds__(DEC_THREADS) void jpegp_settle_kernel(const uint8_t* __restrict__ blobs, const uint32_t* __restrict__ stream, uint32_t cap_words,
+                                                                   DecMeta* __restrict__ meta, uint4* __restrict__ state, uint32_t* __restrict__ count,
+                                                                   uint32_t nsub_max, uint32_t chunk_bits, DecShape g, ProgScan sc, int mw, int scan, int nscans,
+                                                                   const uint64_t* __restrict__ mask) {
+    __shared__ FileTables ft;
+    __shared__ uint32_t part[16];
+    __shared__ int changed[2];
+    const size_t f = blockIdx.x, fs = f * nscans + scan;
+    const int t = threadIdx.x;
+    load_tables(&ft, blobs + fs * sizeof(FileTables));
+    const uint32_t* s = stream + fs * cap_words;
+    const uint32_t nbits = min(meta[fs].ulen, (cap_words - 3) * 4) * 8;
+    const uint32_t nsub = min((uint32_t)(((uint64_t)nbits + chunk_bits - 1) / chunk_bits), nsub_max);
+    uint4* st[2] = {state + f * 3 * nsub_max, state + (f * 3 + 1) * nsub_max};
+    uint4* last_in = state + (f * 3 + 2) * nsub_max;
+    uint32_t* cnt = count + f * nsub_max;
+    const uint64_t* fm = mask + f * g.nblk;
+    uint32_t rounds = 0, settled = 0;
+    for (uint32_t r = 0; r <= nsub; ++r) {
+        if (t == 0) changed[r & 1] = 0;
+        __syncthreads();
+        uint4* cur = st[r & 1];
+        const uint4* prev = st[(r & 1) ^ 1];
+        int any = 0;
+        for (uint32_t i = t; i < nsub; i += DEC_THREADS) {
+            const uint32_t begin = i * chunk_bits, end = min(begin + chunk_bits, nbits);
+            const uint4 in = (r == 0 || i == 0) ? make_uint4(begin, 0u, 0u, 0u) : prev[i - 1];
+            uint4 out;
+            if (r > 0 && prog_same(last_in[i], in)) {
+                out = prev[i];
+            } else {
+                uint32_t nb = 0;
+                out = prog_span<KIND, false>(s, cap_words - 1, end, nbits, in, ft, g, sc, mw, fm, &nb, nullptr, 0, nullptr);
+                cnt[i] = nb;
+                last_in[i] = in;
+                if (r > 0 && !prog_same(out, prev[i])) any = 1;
+            }
+            cur[i] = out;
+        }
+        if (any) changed[r & 1] = 1;
+        __syncthreads();
+        ++rounds;
+        if (r > 0 && !changed[r & 1]) { settled = 1; break; }
+    }
+    if (nsub == 0) settled = 1;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nsub; base += DEC_THREADS) {
+        const uint32_t i = base + t;
+        const uint32_t v = i < nsub ? cnt[i] : 0u;
+        const uint32_t incl = decode_inclusive(v, part);
+        if (i < nsub) cnt[i] = carry + incl - v;
+        __syncthreads();
+        if (t == DEC_THREADS - 1) part[15] = incl;
+        __syncthreads();
+        carry += part[15];
+    }
+    if (t == 0) meta[fs].rounds = rounds, meta[fs].settled = settled, meta[fs].nsub = nsub;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void jpegp_write_kernel(const uint8_t* __restrict__ blobs, const uint32_t* __restrict__ stream, uint32_t cap_words,
+                                                          DecMeta* __restrict__ meta, const uint4* __restrict__ state, const uint32_t* __restrict__ count,
+                                                          uint32_t nsub_max, uint32_t chunk_bits, DecShape g, ProgScan sc, int mw, int scan, int nscans,
+                                                          const uint64_t* __restrict__ mask, int16_t* __restrict__ coef) {
+    __shared__ FileTables ft;
+    const size_t f = blockIdx.y, fs = f * nscans + scan;
+    load_tables(&ft, blobs + fs * sizeof(FileTables));
+    const uint32_t nbits = min(meta[fs].ulen, (cap_words - 3) * 4) * 8;
+    const uint32_t nsub = min(meta[fs].nsub, nsub_max);
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nsub) return;
+    const uint4* exit_state = state + f * 3 * nsub_max;
+    const uint32_t begin = i * chunk_bits;
+    const uint4 in = i == 0 ? make_uint4(0u, 0u, 0u, 0u) : exit_state[i - 1];
+    long long b = (long long)count[f * nsub_max + i];
+    if (KIND == 1 && in.y > (uint32_t)sc.ss && in.y <= (uint32_t)sc.se) b -= 1;          // a block under way was begun further left
+    uint32_t nb;
+    prog_span<KIND, true>(stream + fs * cap_words, cap_words - 1, min(begin + chunk_bits, nbits), nbits, in, ft, g, sc, mw, mask + f * g.nblk, &nb,
+                          coef + f * g.nblk * 64, b, meta + fs);
+}
+
+// One workgroup per file: the DC differences of a DC-first scan -> (sum per component in scan order) << Al
+__global__ __launch_bounds__(DEC_THREADS) void jpegp_dc_kernel(int16_t* __restrict__ coef, DecMeta* __restrict__ meta, DecShape g, ProgScan sc, int mw, int scan, int nscans) {
+    __shared__ uint32_t part[16];
+    const size_t f = blockIdx.x;
+    const int t = threadIdx.x, hv = g.H * g.V;
+    int16_t* fc = coef + f * g.nblk * 64;
+    const size_t nmcu = g.nblk / g.bpm;
+    const bool inter = sc.ncomp == g.c;
+    int bad = 0;
+    for (int ci = 0; ci < sc.ncomp; ++ci) {
+        const int comp = inter ? ci : sc.comp;
+        const size_t cnt = inter ? (comp == 0 ? nmcu * hv : nmcu) : (size_t)sc.nblk;
+        const size_t per = (cnt + DEC_THREADS - 1) / DEC_THREADS;
+        const size_t a = min((size_t)t * per, cnt), e = min(a + per, cnt);
+        auto block_of = [&](size_t i) { return inter ? (comp == 0 ? (i / hv) * g.bpm + i % hv : i * g.bpm + hv + comp - 1) : prog_block(g, sc, mw, (uint32_t)i); };
+        uint32_t sum = 0;
+        for (size_t i = a; i < e; ++i) sum += (uint32_t)(int)fc[block_of(i) * 64];
+        uint32_t run = decode_inclusive(sum, part) - sum;
+        for (size_t i = a; i < e; ++i) {
+            run += (uint32_t)(int)fc[block_of(i) * 64];
+            const long long v = (long long)(int)run * (1 << sc.al);
+            if (v < -32768 || v > 32767) bad = 1;
+            fc[block_of(i) * 64] = (int16_t)v;
+        }
+    }
+    if (bad) meta[f * nscans + scan].err = 1;
+}
+
+// A DC refinement: bit sb of the stream belongs to block sb of the scan
+__global__ __launch_bounds__(256) void jpegp_dcrefine_kernel(const uint32_t* __restrict__ stream, uint32_t cap_words, DecMeta* __restrict__ meta, DecShape g, ProgScan sc,
+                                                             int mw, int scan, int nscans, int16_t* __restrict__ coef) {
+    const size_t f = blockIdx.y, fs = f * nscans + scan;
+    const uint32_t nbits = min(meta[fs].ulen, (cap_words - 3) * 4) * 8;
+    const uint32_t sb = blockIdx.x * 256 + threadIdx.x;
+    if (sb == 0) {
+        meta[fs].settled = 1;
+        if (sc.nblk <= nbits && sc.nblk + 8 > nbits) meta[fs].done = 1; else meta[fs].err = 1;
+    }
+    if (sb >= sc.nblk || sb >= nbits) return;
+    if (prog_bit(stream + fs * cap_words, cap_words - 1, sb, nbits)) {
+        int16_t* p = coef + (f * g.nblk + prog_block(g, sc, mw, sb)) * 64;
+        *p = (int16_t)(*p | (1 << sc.al));
+    }
+}
+
+// The history of an AC refinement: bit k of mask[sb] is set when the coefficient at zigzag index k of the scan's block sb is not zero
+__global__ __launch_bounds__(256) void jpegp_mask_kernel(const int16_t* __restrict__ coef, DecShape g, ProgScan sc, int mw, uint64_t* __restrict__ mask) {
+    const size_t f = blockIdx.y;
+    const uint32_t sb = blockIdx.x * 256 + threadIdx.x;
+    if (sb >= sc.nblk) return;
+    const int16_t* bc = coef + (f * g.nblk + prog_block(g, sc, mw, sb)) * 64;
+    uint64_t m = 0;
+    for (int k = 0; k < 64; ++k) m |= (uint64_t)(bc[T.zigzag[k]] != 0) << k;
+    mask[f * g.nblk + sb] = m;
+}
+
+// One workgroup per file: the DC bound and the record
+__global__ __launch_bounds__(DEC_THREADS) void jpegp_finish_kernel(const int16_t* __restrict__ coef, const DecMeta* __restrict__ meta, DecShape g, int nscans,
+                                                                   int32_t* __restrict__ record) {
+    __shared__ int range_err;
+    const size_t f = blockIdx.x;
+    if (threadIdx.x == 0) range_err = 0;
+    __syncthreads();
+    int bad = 0;
+    for (size_t b = threadIdx.x; b < g.nblk; b += DEC_THREADS) {
+        const int dc = coef[(f * g.nblk + b) * 64];
+        if (dc > 2047 || dc < -2047) bad = 1;
+    }
+    if (bad) range_err = 1;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bool ok = !range_err;
+        uint32_t rounds = 0;
+        for (int k = 0; k < nscans; ++k) {
+            const DecMeta m = meta[f * nscans + k];
+            ok = ok && m.settled && !m.err && m.done == 1;
+            rounds += m.rounds;
+        }
+        record[2 * f] = ok ? 0 : 1;
+        record[2 * f + 1] = (int32_t)rounds;
+    }
+}
+
+struct ProgPlan {
+    DecPlan d;          // the geometry; of its offsets only the ones below are used
+    size_t o_seg, o_meta, o_stream, o_state, o_count, o_mask, o_coef, o_planes, total;
+};
+
+const char* check_progressive_scans(int c, int nscans, const int32_t* scans) {
+    if (nscans < 1 || nscans > PROG_MAX_SCANS) return "nscans outside 1..32";
+    for (int k = 0; k < nscans; ++k) {
+        const int32_t* d = scans + 8 * k;
+        const int ncomp = d[0], ss = d[4], se = d[5], ah = d[6], al = d[7];
+        if (ncomp != 1 && ncomp != c) return "a scan with neither one component nor all of them";
+        for (int i = 0; i < ncomp; ++i)
+            if (d[1 + i] < 0 || d[1 + i] >= c || (ncomp > 1 && d[1 + i] != i)) return "a scan component outside the frame, or an interleaved scan out of frame order";
+        if (ss < 0 || se < ss || se > 63) return "a band with Se < Ss or outside 0..63";
+        if (ss == 0 && se != 0) return "a scan that mixes the DC term with AC coefficients";
+        if (ss > 0 && ncomp != 1) return "an interleaved AC scan";
+        if (ah < 0 || ah > 13 || al < 0 || al > 13) return "Ah or Al outside 0..13";
+    }
+    return nullptr;
+}
+
+ProgPlan make_progressive_plan(int n, int h, int w, int c, int sampling, int nscans, size_t max_segment_bytes, int chunk_bits) {
+    ProgPlan p{};
+    p.d = make_decode_plan(n, h, w, c, sampling, 0, max_segment_bytes, chunk_bits);
+    size_t at = 0, N = (size_t)n, S = (size_t)nscans;
+    auto take = [&](size_t bytes) { size_t o = at; at = align256(at + bytes); return o; };
+    p.o_seg = take(N * S * sizeof(DecSeg));
+    p.o_meta = take(N * S * sizeof(DecMeta));
+    p.o_stream = take(N * S * p.d.cap_words * sizeof(uint32_t));
+    p.o_state = take(3 * N * p.d.nsub_max * sizeof(uint4));
+    p.o_count = take(N * p.d.nsub_max * sizeof(uint32_t));
+    p.o_mask = take(N * p.d.nblk * sizeof(uint64_t));
+    p.o_coef = take(N * p.d.nblk * 64 * sizeof(int16_t));
+    p.o_planes = take(N * p.d.plane_stride);
+    p.total = at;
+    return p;
 }
 
 const char* check_shape(int n, int h, int w, int c, int quality) {
@@ -1484,13 +1921,109 @@ int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_
     jpegd_settle_kernel<<<n, DEC_THREADS, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, itab);
     jpegd_write_kernel<<<dim3((p.nsub_max + 255) / 256, n), 256, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, coef, itab);
     jpegd_dc_kernel<<<n, DEC_THREADS, 0, s>>>(coef, meta, g, record);
-    jpegd_idct_kernel<<<dim3((unsigned)((p.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG), n), IDCT_PER_WG * 8, 0, s>>>(coef, blobs, planes, pg);
+    jpegd_idct_kernel<<<dim3((unsigned)((p.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG), n), IDCT_PER_WG * 8, 0, s>>>(coef, blobs, sizeof(FileTables), planes, pg);
     const dim3 grid((w + 255) / 256, h, n);
     if (c == 3)
         jpegd_pixels_kernel<3><<<grid, 256, 0, s>>>(planes, pg, h, w, dst);
     else
         jpegd_pixels_kernel<1><<<grid, 256, 0, s>>>(planes, pg, h, w, dst);
     return check_launch("jpeg_decode_u8");
+}
+
+int jpeg_decode_progressive_bytes(int n, int h, int w, int c, int sampling, int nscans, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes) {
+    const char* bad = check_decode_shape(n, h, w, c, sampling, 0, max_segment_bytes, chunk_bits);
+    if (!bad && (nscans < 1 || nscans > PROG_MAX_SCANS)) bad = "nscans outside 1..32";
+    if (bad) {
+        set_error("jpeg_decode_progressive_u8: %s (n %d, %d x %d x %d, sampling %d, %d scans, segment %zu, chunk_bits %d)", bad, n, h, w, c, sampling, nscans,
+                  max_segment_bytes, chunk_bits);
+        return -1;
+    }
+    if (workspace_bytes) *workspace_bytes = make_progressive_plan(n, h, w, c, sampling, nscans, max_segment_bytes, chunk_bits).total;
+    return 0;
+}
+
+int launch_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, int nscans,
+                                      const int32_t* scans, const uint64_t* seg_offsets, const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace,
+                                      size_t workspace_bytes, int chunk_bits, hipStream_t s) {
+    const char* bad = check_decode_shape(n, h, w, c, sampling, 0, 0, chunk_bits);
+    if (!bad) bad = check_progressive_scans(c, nscans, scans);
+    if (bad) {
+        set_error("jpeg_decode_progressive_u8: %s (n %d, %d x %d x %d, sampling %d, %d scans, chunk_bits %d)", bad, n, h, w, c, sampling, nscans, chunk_bits);
+        return -1;
+    }
+    const size_t streams = (size_t)n * nscans;
+    size_t longest = 0;
+    for (size_t i = 0; i < streams; ++i) {
+        if (seg_offsets[i] > files_bytes || seg_lengths[i] > files_bytes - seg_offsets[i]) {
+            set_error("jpeg_decode_progressive_u8: segment %zu (%llu + %u bytes) leaves the %zu bytes of files", i, (unsigned long long)seg_offsets[i], seg_lengths[i],
+                      files_bytes);
+            return -1;
+        }
+        longest = seg_lengths[i] > longest ? seg_lengths[i] : longest;
+    }
+    if ((bad = check_decode_shape(n, h, w, c, sampling, 0, longest, chunk_bits))) { set_error("jpeg_decode_progressive_u8: %s", bad); return -1; }
+    if ((uintptr_t)workspace % 8 || (uintptr_t)record % 4) { set_error("jpeg_decode_progressive_u8: the workspace must be 8-byte and the record 4-byte aligned"); return -1; }
+    const ProgPlan pp = make_progressive_plan(n, h, w, c, sampling, nscans, longest, chunk_bits);
+    const DecPlan& p = pp.d;
+    if (workspace_bytes < pp.total) { set_error("jpeg_decode_progressive_u8: workspace too small (%zu < %zu bytes)", workspace_bytes, pp.total); return -1; }
+    if ((p.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull || streams > 0x7fffffffull) {
+        set_error("jpeg_decode_progressive_u8: %d x %d, %d files: too many blocks or streams for one launch", h, w, n);
+        return -1;
+    }
+    char* ws = (char*)workspace;
+    DecSeg* seg = (DecSeg*)(ws + pp.o_seg);
+    DecMeta* meta = (DecMeta*)(ws + pp.o_meta);
+    uint32_t* stream = (uint32_t*)(ws + pp.o_stream);
+    uint4* state = (uint4*)(ws + pp.o_state);
+    uint32_t* count = (uint32_t*)(ws + pp.o_count);
+    uint64_t* mask = (uint64_t*)(ws + pp.o_mask);
+    int16_t* coef = (int16_t*)(ws + pp.o_coef);
+    uint8_t* planes = (uint8_t*)(ws + pp.o_planes);
+    const DecShape g{p.H, p.V, p.bpm, p.c, p.nblk, p.ri, p.nint};
+    const DecPlanes pg{p.c, p.H, p.V, p.bpm, p.mw, p.yw, p.cw, p.nblk, p.o_cb, p.o_cr, p.plane_stride};
+    for (size_t first = 0; first < streams; first += DEC_SEG_BATCH) {
+        DecSegBatch b{};
+        const int count_ = streams - first < (size_t)DEC_SEG_BATCH ? (int)(streams - first) : DEC_SEG_BATCH;
+        for (int i = 0; i < count_; ++i) b.off[i] = seg_offsets[first + i], b.len[i] = seg_lengths[first + i];
+        jpegd_table_kernel<<<1, DEC_SEG_BATCH, 0, s>>>(b, (int)first, count_, seg, meta);
+    }
+    jpegd_unstuff_kernel<false><<<(unsigned)streams, DEC_THREADS, 0, s>>>(files, seg, meta, (uint8_t*)stream, p.cap_words, nullptr, 1u);
+    if (hipMemsetAsync(coef, 0, (size_t)n * p.nblk * 64 * sizeof(int16_t), s) != hipSuccess) { set_error("jpeg_decode_progressive_u8: hipMemsetAsync failed"); return -1; }
+    const dim3 subs((p.nsub_max + 255) / 256, n);
+    for (int k = 0; k < nscans; ++k) {
+        const int32_t* d = scans + 8 * k;
+        ProgScan sc{d[0], d[0] == 1 ? d[1] : 0, d[4], d[5], d[6], d[7], 0u, 0u};
+        if (sc.ncomp == c) {
+            sc.bw = (uint32_t)p.mw * (c == 1 ? 1u : (uint32_t)p.H), sc.nblk = (uint32_t)p.nblk;
+        } else {
+            const uint32_t cw = sc.comp == 0 ? (uint32_t)w : (uint32_t)((w + p.H - 1) / p.H), chh = sc.comp == 0 ? (uint32_t)h : (uint32_t)((h + p.V - 1) / p.V);
+            sc.bw = (cw + 7) / 8, sc.nblk = sc.bw * ((chh + 7) / 8);
+        }
+        const dim3 blocks((sc.nblk + 255) / 256, n);
+#define JPEGP_SETTLE(KIND)                                                                                                                                     \
+    jpegp_settle_kernel<KIND><<<n, DEC_THREADS, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, sc, p.mw, k, nscans, mask); \
+    jpegp_write_kernel<KIND><<<subs, 256, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, sc, p.mw, k, nscans, mask, coef)
+        if (sc.ss == 0 && sc.ah == 0) {
+            JPEGP_SETTLE(0);
+            jpegp_dc_kernel<<<n, DEC_THREADS, 0, s>>>(coef, meta, g, sc, p.mw, k, nscans);
+        } else if (sc.ss == 0) {
+            jpegp_dcrefine_kernel<<<blocks, 256, 0, s>>>(stream, p.cap_words, meta, g, sc, p.mw, k, nscans, coef);
+        } else if (sc.ah == 0) {
+            JPEGP_SETTLE(1);
+        } else {
+            jpegp_mask_kernel<<<blocks, 256, 0, s>>>(coef, g, sc, p.mw, mask);
+            JPEGP_SETTLE(2);
+        }
+#undef JPEGP_SETTLE
+    }
+    jpegp_finish_kernel<<<n, DEC_THREADS, 0, s>>>(coef, meta, g, nscans, record);
+    jpegd_idct_kernel<<<dim3((unsigned)((p.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG), n), IDCT_PER_WG * 8, 0, s>>>(coef, blobs, (size_t)nscans * sizeof(FileTables), planes, pg);
+    const dim3 grid((w + 255) / 256, h, n);
+    if (c == 3)
+        jpegd_pixels_kernel<3><<<grid, 256, 0, s>>>(planes, pg, h, w, dst);
+    else
+        jpegd_pixels_kernel<1><<<grid, 256, 0, s>>>(planes, pg, h, w, dst);
+    return check_launch("jpeg_decode_progressive_u8");
 }
 
 }  // namespace adain

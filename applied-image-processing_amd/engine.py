@@ -212,11 +212,12 @@ class AdaINEngine:
         device, encoded there (adain_jpeg_encode_u8) -> a list of n ``bytes``; only the files cross to the host."""
         return rt.jpeg_files(*rt.jpeg_encode_u8(frames_u8, quality))
 
-    def jpeg_decode_u8(self, files, chunk_bits=0, mode=None, report=None, restart=False):
+    def jpeg_decode_u8(self, files, chunk_bits=0, mode=None, report=None, restart=False, progressive=False):
         """The bytes of image files (a list, or one ``bytes``) -> uint8 tensors on the engine's device, the pixels Pillow's ``Image.open``
         gives: baseline JPEG files are decoded on the device (adain_jpeg_decode_restart_u8; with ``restart=True`` those with restart intervals as
-        well), anything else by PIL as before (``rt.jpeg_decode_u8``)."""
-        return rt.jpeg_decode_u8(files, self.device, chunk_bits, mode, report, restart)
+        well, with ``progressive=True`` progressive files too: adain_jpeg_decode_progressive_u8), anything else by PIL as before
+        (``rt.jpeg_decode_u8``)."""
+        return rt.jpeg_decode_u8(files, self.device, chunk_bits, mode, report, restart, progressive)
 
     def jpeg_roundtrip_u8(self, frames_u8, quality=rt.JPEG_DEFAULT_QUALITY):
         """uint8 frames [n,h,w,3|1] on the device -> the frames Pillow decodes from the JPEG files it would save for them at ``quality``

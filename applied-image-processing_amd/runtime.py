@@ -107,6 +107,9 @@ SIGNATURES = {
     "adain_jpeg_decode_restart_u8_bytes": (_c_int, [_c_int] * 6 + [_c_size_t, _c_int, ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_decode_restart_u8": (_c_int, [_c_void_p, _c_size_t, _c_void_p] + [_c_int] * 6 + [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
                                               _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p]),
+    "adain_jpeg_decode_progressive_u8_bytes": (_c_int, [_c_int] * 6 + [_c_size_t, _c_int, ctypes.POINTER(_c_size_t)]),
+    "adain_jpeg_decode_progressive_u8": (_c_int, [_c_void_p, _c_size_t, _c_void_p] + [_c_int] * 6 + [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64),
+                                                  ctypes.POINTER(ctypes.c_uint32), _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p]),
     "adain_nhwc_to_nchw": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_nchw_to_nhwc": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p]),
     "adain_conv3x3_wino4_packed_floats": (_c_size_t, [_c_int, _c_int]),
@@ -961,6 +964,80 @@ def jpeg_decode_batch(parsed, datas, device, chunk_bits=0, lead=0):
     return jpeg_decode_launch(up, offsets, lengths, parsed[0].geometry, chunk_bits, parsed[0].restart_interval)
 
 
+# --- progressive input files (adain_jpeg_decode_progressive_u8) -----------------------------------------------------------------------
+def jpeg_decode_progressive_sizes(n, h, w, c, sampling, nscans, max_segment_bytes, chunk_bits=0):
+    """workspace_bytes of adain_jpeg_decode_progressive_u8_bytes: the scratch of an n-file call of ``nscans`` scans whose longest scan
+    segment has ``max_segment_bytes``.  Host only.  AdainHipError for a refused shape."""
+    ws = _c_size_t()
+    rc = lib().adain_jpeg_decode_progressive_u8_bytes(int(n), int(h), int(w), int(c), int(sampling), int(nscans), int(max_segment_bytes), int(chunk_bits),
+                                                      ctypes.byref(ws))
+    if rc != 0:
+        raise _failure("adain_jpeg_decode_progressive_u8_bytes", rc)
+    return ws.value
+
+
+def jpeg_decode_progressive_upload(parsed, datas, device, lead=0):
+    """The one upload of a ``jpeg_decode_progressive_batch`` call: the table blobs [n][scans] of n files of ONE geometry and ONE scan
+    script, ``lead`` spare bytes, then every file's scan segments back to back -> (device uint8 tensor, segment offsets behind the
+    blobs [n * scans], segment lengths [n * scans])."""
+    from . import jpeg_file
+
+    n = len(parsed)
+    if n < 1 or any(p.geometry != parsed[0].geometry for p in parsed) or len(datas) != n:
+        raise AdainHipError("jpeg_decode_progressive_batch: expected the files of one geometry")
+    if any(p.script != parsed[0].script for p in parsed):
+        raise AdainHipError("jpeg_decode_progressive_batch: expected the files of one scan script")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise AdainHipError("jpeg_decode_u8: expected a GPU device (the device decoder has no CPU form)")
+    scans = [(d, sc) for p, d in zip(parsed, datas) for sc in p.scans]
+    blobs = len(scans) * jpeg_file.BLOB_BYTES
+    lengths = [sc.seg_length for _, sc in scans]
+    offsets, at = [], lead
+    for ln in lengths:
+        offsets.append(at)
+        at += ln
+    host = bytearray(blobs + at + 1)            # one spare byte: the pointer behind the blobs stays inside the tensor
+    for i, (d, sc) in enumerate(scans):
+        host[i * jpeg_file.BLOB_BYTES:(i + 1) * jpeg_file.BLOB_BYTES] = sc.blob
+        host[blobs + offsets[i]:blobs + offsets[i] + lengths[i]] = d[sc.seg_offset:sc.seg_offset + sc.seg_length]
+    return torch.frombuffer(host, dtype=torch.uint8).to(device), offsets, lengths
+
+
+def jpeg_decode_progressive_launch(up, offsets, lengths, geometry, script, chunk_bits=0):
+    """adain_jpeg_decode_progressive_u8 on an upload of ``jpeg_decode_progressive_upload`` whose files have the scan ``script``
+    (ProgressiveJpegFile.script) -> (frames uint8 [n,h,w,c], record int32 [n,2]) on its device."""
+    from . import jpeg_file
+
+    nscans = len(script)
+    n = len(lengths) // max(nscans, 1)
+    h, w, c, sampling = geometry
+    blobs = n * nscans * jpeg_file.BLOB_BYTES
+    desc = []
+    for comps, ss, se, ah, al in script:
+        desc += [len(comps)] + list(comps) + [0] * (3 - len(comps)) + [ss, se, ah, al]
+    scans = (ctypes.c_int32 * max(len(desc), 1))(*desc)
+    off = (ctypes.c_uint64 * max(len(offsets), 1))(*offsets)
+    ln = (ctypes.c_uint32 * max(len(lengths), 1))(*lengths)
+    # the workspace is shared per stream, as the baseline decoder's is
+    with _jpeg_decode_lock, scratch(up.device, "jpeg_decode_progressive", jpeg_decode_progressive_sizes, n, h, w, c, sampling, nscans, max(lengths, default=0),
+                                    chunk_bits) as ws:
+        out = torch.empty((n, h, w, c), dtype=torch.uint8, device=up.device)
+        record = torch.empty((n, 2), dtype=torch.int32, device=up.device)
+        _launch("adain_jpeg_decode_progressive_u8", up.data_ptr() + blobs, up.numel() - blobs, up.data_ptr(), n, h, w, c, sampling, nscans, scans, off, ln,
+                out.data_ptr(), record.data_ptr(), ws.data_ptr(), ws.numel(), int(chunk_bits))
+    return out, record
+
+
+def jpeg_decode_progressive_batch(parsed, datas, device, chunk_bits=0, lead=0):
+    """``parsed``: jpeg_file.ProgressiveJpegFile of n files of ONE geometry and ONE scan script (anything else is an error), ``datas``:
+    their bytes -> (frames uint8 [n,h,w,c], record int32 [n,2]: status, and the rounds summed over the Huffman-coded scans), both on
+    ``device``.  One upload and one call of adain_jpeg_decode_progressive_u8; nothing comes back and nothing waits.  A frame whose
+    status is not 0 is unspecified."""
+    up, offsets, lengths = jpeg_decode_progressive_upload(parsed, datas, device, lead)
+    return jpeg_decode_progressive_launch(up, offsets, lengths, parsed[0].geometry, parsed[0].script, chunk_bits)
+
+
 def _pil_pixels(data, mode):
     import io
 
@@ -971,15 +1048,17 @@ def _pil_pixels(data, mode):
     return np.asarray(img.convert(mode) if mode is not None else img)
 
 
-def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None, restart=False):
+def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None, restart=False, progressive=False):
     """The bytes of image files (a list, or one ``bytes``) -> device uint8 tensors (a list, or one): per file the array
     ``np.asarray(Image.open(io.BytesIO(data)))`` gives - [h,w,3] for a colour file, [h,w] for a grey one - or, with ``mode`` "RGB" / "L",
     ``np.asarray(Image.open(...).convert(mode))`` (a grey file is replicated for "RGB"; "L" from a colour file goes to the host).  Baseline
     JPEG files are decoded on the device (adain_jpeg_decode_restart_u8; grouped by geometry and restart interval, one call and one
     upload per group, the record read once); whatever jpeg_file.parse refuses, and any file whose status comes back non-zero, is decoded
     by PIL on the host exactly as before and uploaded - PIL's exceptions pass through.  ``restart``: files with a restart interval (DRI,
-    RSTn markers) are decoded on the device as well; False, the default, leaves them to PIL as before.  ``report`` (a list): per file
-    "device" or "host: <why>", and the rounds."""
+    RSTn markers) are decoded on the device as well; False, the default, leaves them to PIL as before.  ``progressive``: 8-bit
+    progressive Huffman (SOF2) files with a complete scan script are decoded on the device as well (adain_jpeg_decode_progressive_u8;
+    grouped by geometry and scan script); False, the default, leaves them to PIL as before.  ``report`` (a list): per file "device" or
+    "host: <why>", and the rounds (a progressive file's: summed over its Huffman-coded scans)."""
     from . import jpeg_file
 
     single = isinstance(files, (bytes, bytearray, memoryview))
@@ -990,13 +1069,15 @@ def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None, res
     results, why, rounds, groups = [None] * len(datas), [None] * len(datas), [0] * len(datas), {}
     for i, d in enumerate(datas):
         try:
-            p = jpeg_file.parse(d, restart=restart)
+            p = jpeg_file.parse(d, restart=restart, progressive=progressive)
             if mode == "L" and p.c == 3:
                 raise jpeg_file.UnsupportedJpeg("a colour file where grey is wanted")
-            groups.setdefault((p.geometry, p.restart_interval), []).append((i, p))
+            key = ("progressive", p.script) if isinstance(p, jpeg_file.ProgressiveJpegFile) else ("sequential", p.restart_interval)
+            groups.setdefault((p.geometry, key), []).append((i, p))
         except jpeg_file.UnsupportedJpeg as e:
             why[i] = str(e)
-    launched = [(members, jpeg_decode_batch([p for _, p in members], [datas[i] for i, _ in members], device, chunk_bits)) for members in groups.values()]
+    launched = [(members, (jpeg_decode_progressive_batch if key[0] == "progressive" else jpeg_decode_batch)(
+        [p for _, p in members], [datas[i] for i, _ in members], device, chunk_bits)) for (_, key), members in groups.items()]
     for members, (out, record) in launched:
         rec = record.cpu().tolist()                      # the one read of the record: waits for the call
         for k, (i, p) in enumerate(members):
@@ -1014,10 +1095,11 @@ def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None, res
     return results[0] if single else results
 
 
-def jpeg_decode_rgb_file(path, device):
+def jpeg_decode_rgb_file(path, device, progressive=False):
     """The frame ``np.asarray(Image.open(path).convert("RGB"))`` as a uint8 [h,w,3] tensor on ``device``, decoded there - or None when
     the file is not one the device decoder takes (not a .jpg / .jpeg name, refused by jpeg_file.parse, a non-zero status): the caller
-    then decodes it with PIL as before.  Files with restart intervals are taken.  Reads the record once (waits for the call)."""
+    then decodes it with PIL as before.  Files with restart intervals are taken; progressive files only with ``progressive=True``.
+    Reads the record once (waits for the call)."""
     from . import jpeg_file
 
     if not str(path).lower().endswith((".jpg", ".jpeg")) or torch.device(device).type != "cuda":
@@ -1025,10 +1107,13 @@ def jpeg_decode_rgb_file(path, device):
     with open(str(path), "rb") as f:
         data = f.read()
     try:
-        parsed = jpeg_file.parse(data, restart=True)
+        parsed = jpeg_file.parse(data, restart=True, progressive=progressive)
     except jpeg_file.UnsupportedJpeg:
         return None
-    out, record = jpeg_decode_batch([parsed], [data], device)
+    if isinstance(parsed, jpeg_file.ProgressiveJpegFile):
+        out, record = jpeg_decode_progressive_batch([parsed], [data], device)
+    else:
+        out, record = jpeg_decode_batch([parsed], [data], device)
     if record[0, 0].item() != 0:
         return None
     return out[0].expand(-1, -1, 3).contiguous() if parsed.c == 1 else out[0]

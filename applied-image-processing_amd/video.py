@@ -43,6 +43,7 @@ from .AdaIN import test as adain_test
 
 _flow_provider = None
 _jpeg_decode_on_device = False          # set for the duration of a call with jpeg_decode_on_device=True (_run)
+_jpeg_decode_progressive = False        # with it: jpeg_decode_progressive=True, progressive frames are decoded on the device too
 _IMAGE_EXT = (".jpg", ".jpeg", ".png")
 
 
@@ -65,7 +66,7 @@ def _decode_gray(path, target_resolution, device):
     device (flow.frames_to_gray).  Decoded with PIL, which does not apply the EXIF orientation cv2.imread applies (unpinned)."""
     from . import flow as fl
 
-    rgb = rt.jpeg_decode_rgb_file(path, device) if _jpeg_decode_on_device else None        # the same pixels, decoded where they are used
+    rgb = rt.jpeg_decode_rgb_file(path, device, _jpeg_decode_progressive) if _jpeg_decode_on_device else None          # the same pixels, decoded where they are used
     if rgb is None:
         rgb = torch.from_numpy(np.array(Image.open(path).convert("RGB"))).to(device)
     return fl.frames_to_gray(rgb, target_resolution)
@@ -159,14 +160,15 @@ def _jpeg_roundtrip(u8):
 
 def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
          vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device=False, preserve_color=False, crossfade_frames=0,
-         jpeg_decode_on_device=False):
-    global _jpeg_decode_on_device
+         jpeg_decode_on_device=False, jpeg_decode_progressive=False):
+    global _jpeg_decode_on_device, _jpeg_decode_progressive
     prev, _jpeg_decode_on_device = _jpeg_decode_on_device, bool(jpeg_decode_on_device)
+    prev_progressive, _jpeg_decode_progressive = _jpeg_decode_progressive, bool(jpeg_decode_on_device and jpeg_decode_progressive)
     try:
         return _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
                          vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color, crossfade_frames)
     finally:
-        _jpeg_decode_on_device = prev
+        _jpeg_decode_on_device, _jpeg_decode_progressive = prev, prev_progressive
 
 
 def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
@@ -212,7 +214,7 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
         def __getitem__(self, k):
             if on_gpu and _jpeg_decode_on_device:             # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg.hip)
                 with torch.cuda.device(engine.device):
-                    rgb = rt.jpeg_decode_rgb_file(os.path.join(content_dir, names[k]), engine.device)
+                    rgb = rt.jpeg_decode_rgb_file(os.path.join(content_dir, names[k]), engine.device, _jpeg_decode_progressive)
                 plan = adain_test._device_plan(rgb.shape[1], rgb.shape[0], 256, False) if rgb is not None else None
                 if plan is not None:
                     return adain_test._device_resize(rgb[None], rgb.shape[1], rgb.shape[0], plan)[0]
@@ -284,30 +286,32 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
                              cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                              vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth", decoder_str="Style_3DGS/AdaIN/models/decoder.pth",
                              depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False, preserve_color=False,
-                             jpeg_decode_on_device=False):
+                             jpeg_decode_on_device=False, jpeg_decode_progressive=False):
     """One style for the whole clip (video/utils.py:244-295); keyword-only extras: a ready ``engine``, checkpoint paths,
     precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``jpeg_on_device`` (.jpg / .jpeg frames are
     encoded on the device: the same files, jobs.FileSink; with ``intermediate_jpeg`` and the engine on a GPU the intermediate round trip
     runs on the device too, ``AdaINEngine.jpeg_roundtrip_u8``: the same frames), ``preserve_color`` (every frame is styled with
     ``coral(style, frame)``, adain_inference's colour preservation, on the device), ``jpeg_decode_on_device`` (baseline .jpg / .jpeg
     frames are decoded on the device, for the stylisation and for the package's own flow providers: ``rt.jpeg_decode_rgb_file``, the
-    pixels PIL decodes; any other file, and the sharded feeder of jobs.py, keep PIL)."""
+    pixels PIL decodes; any other file, and the sharded feeder of jobs.py, keep PIL), ``jpeg_decode_progressive`` (acts with
+    ``jpeg_decode_on_device=True``: progressive frames are decoded on the device too; without it they keep PIL as before)."""
     return _run(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
                 engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color,
-                jpeg_decode_on_device=jpeg_decode_on_device)
+                jpeg_decode_on_device=jpeg_decode_on_device, jpeg_decode_progressive=jpeg_decode_progressive)
 
 
 def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
                                    cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                                    vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth",
                                    decoder_str="Style_3DGS/AdaIN/models/decoder.pth", depth_maps=None, intermediate_jpeg=False,
-                                   group=None, jpeg_on_device=False, preserve_color=False, crossfade_frames=0, jpeg_decode_on_device=False):
+                                   group=None, jpeg_on_device=False, preserve_color=False, crossfade_frames=0, jpeg_decode_on_device=False,
+                                   jpeg_decode_progressive=False):
     """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372).
     ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics.
     ``jpeg_on_device``: as in ``apply_style_transfer_ada``, the output files and, with ``intermediate_jpeg``, the intermediate round trip.
     ``crossfade_frames`` (0, the default: the hard cuts of the reference): the styles cross-fade in feature space over that many
     frames centred on each switch (``jobs.style_crossfade``, style interpolation on the device; at most 16 styles, and not with
-    ``preserve_color``).  ``jpeg_decode_on_device``: as in ``apply_style_transfer_ada``."""
+    ``preserve_color``).  ``jpeg_decode_on_device``, ``jpeg_decode_progressive``: as in ``apply_style_transfer_ada``."""
     style_images = sorted(os.listdir(style_dir))
     if len(style_images) == 0:
         raise ValueError("No style images found in the style directory.")
@@ -315,4 +319,4 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
         raise ValueError("crossfade_frames mixes the styles of a frame; preserve_color is not supported with it")
     return _run(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
                 cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color,
-                int(crossfade_frames), jpeg_decode_on_device=jpeg_decode_on_device)
+                int(crossfade_frames), jpeg_decode_on_device=jpeg_decode_on_device, jpeg_decode_progressive=jpeg_decode_progressive)

@@ -533,6 +533,39 @@ ADAIN_API int adain_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, con
                                    const uint64_t* segment_offsets, const uint32_t* segment_lengths, uint8_t* dst_u8, int32_t* record,
                                    void* workspace, size_t workspace_bytes, int chunk_bits, adain_stream_t stream);
 
+/* adain_jpeg_decode_progressive_u8 / _bytes (added without a version change): n 8-bit progressive Huffman (SOF2) files of ONE geometry
+ * and ONE scan script -> the same dst and record as above.  A complete progressive file holds the quantised coefficients of its
+ * sequential twin and Pillow's pixels are a function of those alone, so behind the scans the same back half runs.
+ *   nscans, scans   1..32 scans; scans is a HOST array int32 [nscans][8], read before the call returns: the scan's number of components,
+ *     their indices in the frame (three entries, unused ones ignored), Ss, Se, Ah, Al.  A DC scan has Ss = Se = 0 and either all components
+ *     of the frame in frame order (interleaved, in the MCU order above) or one; an AC scan has 1 <= Ss <= Se <= 63 and one component; a
+ *     one-component scan covers that component's own block raster, ceil(ceil(w Hi / Hmax) / 8) blocks a row.  Ah = 0 is a first scan,
+ *     Ah > 0 a refinement; Ah and Al are 0..13.  Anything else: ADAIN_EINVAL before any launch.  The order of the scans is the file's.  The
+ *     host checks the script (jpeg_file.py does: every coefficient begins with Ah = 0, is refined one bit at a time and ends at Al = 0;
+ *     no restart interval); a script that breaks those rules gives unspecified pixels, inside dst.
+ *   segment_offsets, segment_lengths   HOST arrays [n][nscans]: file i's scan k lies at segment_offsets[i nscans + k] of `files` (behind
+ *     its SOS, up to the next marker, stuffed)
+ *   blobs   device memory, [n][nscans] x 3848 bytes in the layout above: the Huffman tables in force at that scan's SOS, sel[] per frame
+ *     component (the entries of components the scan does not hold are ignored), and in every blob the frame's quantisation tables
+ *   record   status and the rounds SUMMED over the file's Huffman-coded scans (a DC refinement has no code and takes none)
+ * Every Huffman-coded scan is decoded by the scheme above - subsequences of chunk_bits bits, exit states iterated to the fixed point in
+ * at most (subsequences + 1) rounds, then a parallel write pass - one scan after the other in file order.  An AC refinement's state
+ * carries the block it is in, because the bits a block takes depend on which of its coefficients earlier scans made non-zero; that
+ * history is taken as one 64-bit mask per block before the scan is settled.  Status non-zero: a code in no table, a size that is illegal
+ * for the scan kind (DC above 11, AC above 10, a refinement's above 1), a coefficient index past Se, a value that is no int16, a final
+ * DC term outside -2047..2047, a scan with fewer blocks than it covers or whose last block does not end inside its segment's last
+ * byte, a scan that did not settle.  Whatever the bytes, the writes stay inside dst, record and the workspace and the kernels end.
+ * adain_jpeg_decode_progressive_u8_bytes (host only): *workspace_bytes for n files of nscans scans whose longest scan segment is
+ * max_segment_bytes.  Refused as above, and: nscans outside 1..32, a scan that breaks the rules of `scans`.  Launches per call:
+ * ceil(n nscans / 64) + 1 + one memset, per scan 3 (DC first), 1 (DC refinement), 2 (AC first) or 3 (AC refinement), and 3 more.  The
+ * rules: csrc/jpeg.hip, restated in tests/jpeg_progressive_ref.py. */
+ADAIN_API int adain_jpeg_decode_progressive_u8_bytes(int n, int h, int w, int c, int sampling, int nscans, size_t max_segment_bytes,
+                                                     int chunk_bits, size_t* workspace_bytes);
+ADAIN_API int adain_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c,
+                                               int sampling, int nscans, const int32_t* scans, const uint64_t* segment_offsets,
+                                               const uint32_t* segment_lengths, uint8_t* dst_u8, int32_t* record, void* workspace,
+                                               size_t workspace_bytes, int chunk_bits, adain_stream_t stream);
+
 /* ---- layout changes at the boundary ([n][c][hw] <-> [n][hw][c]) ------------------------------------------ */
 ADAIN_API int adain_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, adain_stream_t stream);
 ADAIN_API int adain_nchw_to_nhwc(const float* in, float* out, int n, int c, int hw, adain_stream_t stream);

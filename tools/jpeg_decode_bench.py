@@ -1,8 +1,9 @@
 """Times the device JPEG file decoder (csrc/jpeg.hip, adain_jpeg_decode_u8) against the host route through Pillow on the same machine,
 one file per call: files at 256 x 456 and 1080 x 1920, saved by Pillow at its default settings (quality 75, 4:2:0) and at quality 95,
 of a stylised synthetic frame (seed-0 weights) and of uniform noise, each also with one restart interval per MCU row (Pillow's
-``restart_marker_rows=1``, the ``_restart`` rows: adain_jpeg_decode_restart_u8).  Median and interquartile range over --reps calls (>= 200)
-after warm-up:
+``restart_marker_rows=1``, the ``_restart`` rows: adain_jpeg_decode_restart_u8) and as a progressive file (Pillow's ``progressive=True``:
+adain_jpeg_decode_progressive_u8; those rows stand under a key of their own, ``progressive``, with the same fields and no chunk sweep).
+Median and interquartile range over --reps calls (>= 200) after warm-up:
   kernel_ms  adain_jpeg_decode_u8 on bytes that are already on the device, HIP events
   device_ms  wall clock from ``bytes`` to a device frame with ``rt.jpeg_decode_u8``: marker walk, upload, decode, the record read
   host_ms    the route without it on one thread: ``Image.open`` + ``np.asarray`` + upload, synchronised
@@ -110,6 +111,20 @@ def per_call(reps, dev):
     return out
 
 
+def row(name, data, launch, restart_interval, kw, reps, dev, tel):
+    """One file's row: kernel_ms of ``launch`` (bytes already on the device), device_ms of ``rt.jpeg_decode_u8(data, **kw)``, host_ms."""
+    t0 = time.perf_counter()
+    kernel = event_ms(launch, reps, 20)
+    tel.window(f"kernel_{name}", t0, time.perf_counter())
+    report = []
+    same = bool(torch.equal(rt.jpeg_decode_u8(data, dev, report=report, **kw), host_route(data, dev)))
+    device = wall_ms(lambda: rt.jpeg_decode_u8(data, dev, **kw), reps, 5)
+    host = wall_ms(lambda: host_route(data, dev), reps, 3)
+    return {"file_bytes": len(data), "restart_interval": restart_interval, "path": report[0]["path"], "rounds": report[0]["rounds"], "same_pixels_as_host": same,
+            "kernel_ms": kernel, "device_ms": device, "host_ms": host, "host_over_device": round(host["median"] / device["median"], 2),
+            "device_is_faster": device["median"] + device["iqr"] + host["iqr"] < host["median"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -125,7 +140,7 @@ def main():
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     tel = GpuTelemetry(0).start()
     res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow": PIL.__version__, "sizes": {}, "chunk_bits": {}}
+           "pillow": PIL.__version__, "sizes": {}, "chunk_bits": {}, "progressive": {}}
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         frames = {"stylised": engine.stylize_u8(source, alpha=0.5)[0].cpu().numpy(), "noise": np.random.default_rng(0).integers(0, 256, (h, w, 3), dtype=np.uint8)}
@@ -137,22 +152,22 @@ def main():
                 up, offsets, lengths = rt.jpeg_decode_upload([parsed], [data], dev)
                 launch = lambda chunk_bits=0: rt.jpeg_decode_launch(up, offsets, lengths, parsed.geometry, chunk_bits, parsed.restart_interval)
                 name = f"{kind}_{label}_{h}x{w}"
-                t0 = time.perf_counter()
-                kernel = event_ms(launch, reps, 20)
-                tel.window(f"kernel_{name}", t0, time.perf_counter())
-                report = []
-                same = bool(torch.equal(rt.jpeg_decode_u8(data, dev, report=report, restart=True), host_route(data, dev)))
-                device = wall_ms(lambda: rt.jpeg_decode_u8(data, dev, restart=True), reps, 5)
-                host = wall_ms(lambda: host_route(data, dev), reps, 3)
-                res["sizes"][name] = {"file_bytes": len(data), "restart_interval": parsed.restart_interval, "path": report[0]["path"], "rounds": report[0]["rounds"], "same_pixels_as_host": same,
-                                      "kernel_ms": kernel, "device_ms": device, "host_ms": host, "host_over_device": round(host["median"] / device["median"], 2),
-                                      "device_is_faster": device["median"] + device["iqr"] + host["iqr"] < host["median"]}
+                res["sizes"][name] = row(name, data, launch, parsed.restart_interval, dict(restart=True), reps, dev, tel)
                 if h == 1080:
                     res["chunk_bits"][name] = {}
                     for cb in CHUNKS:
                         rounds = int(launch(cb)[1][0, 1].item())
                         res["chunk_bits"][name][str(cb)] = dict(event_ms(lambda: launch(cb), max(args.sweep_reps, 8), 3), rounds=rounds, reps=max(args.sweep_reps, 8))
                 print(f"{name}: {json.dumps(res['sizes'][name])} {json.dumps(res['chunk_bits'].get(name))}", file=sys.stderr, flush=True)
+            for label, kw in (("default_progressive", {"progressive": True}), ("q95_progressive", {"quality": 95, "progressive": True})):
+                data = jpeg_bytes(frame, **kw)
+                prog = jpeg_file.parse(data, progressive=True)
+                pup, poffsets, plengths = rt.jpeg_decode_progressive_upload([prog], [data], dev)
+                name = f"{kind}_{label}_{h}x{w}"
+                res["progressive"][name] = row(name, data, lambda: rt.jpeg_decode_progressive_launch(pup, poffsets, plengths, prog.geometry, prog.script), 0,
+                                               dict(progressive=True), reps, dev, tel)
+                res["progressive"][name]["scans"] = len(prog.scans)
+                print(f"{name}: {json.dumps(res['progressive'][name])}", file=sys.stderr, flush=True)
     res["per_call"] = per_call(reps, dev)
     res["telemetry"] = tel.stop()          # shader clock and power over each kernel timing window (sysfs reads)
     line = json.dumps(res)
