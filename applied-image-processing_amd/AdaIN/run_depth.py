@@ -5,7 +5,8 @@ Style_3DGS/AdaIN/run_depth.py (:13-55), so existing invocations keep working:
 
 Extra flags make the depth-aware mode usable offline (the reference pulls MiDaS through torch.hub at run time):
 ``--depth_npy`` takes a precomputed proximity map, ``--vgg`` / ``--decoder`` the checkpoint paths; ``--jpeg_on_device`` encodes the
-result's JPEG file on the GPU (the same bytes); ``--jpeg_decode_on_device`` decodes a baseline JPEG
+result's JPEG file on the GPU (the same bytes); ``--jpeg_quality``, ``--jpeg_subsampling`` (4:4:4, 4:2:2, 4:2:0) and ``--jpeg_optimize``
+are Pillow's save keywords for that file, on either route; ``--jpeg_decode_on_device`` decodes a baseline JPEG
 content there too (the same pixels), ``--jpeg_decode_progressive`` (which implies it) a progressive one as well; ``--coral_on_device`` preserves the content's colours (``adain_inference``'s
 ``preserve_color``, which the reference's CLI does not expose) with CORAL computed on the GPU.
 
@@ -19,7 +20,7 @@ import numpy as np
 import torch
 
 from . import test as adain_test
-from .test import adain_inference, set_device_coral, set_device_jpeg, set_device_jpeg_decode
+from .test import adain_inference, set_device_coral, set_device_jpeg, set_device_jpeg_decode, set_jpeg_save_options
 
 # (flag, argparse keyword arguments) — names and defaults as in the reference CLI
 _REFERENCE_FLAGS = (
@@ -37,6 +38,9 @@ _EXTRA_FLAGS = (
     ("--vgg", dict(type=str, default="Style_3DGS/AdaIN/models/vgg_normalised.pth", help="encoder state_dict")),
     ("--decoder", dict(type=str, default="Style_3DGS/AdaIN/models/decoder.pth", help="decoder state_dict")),
     ("--jpeg_on_device", dict(action="store_true", help="encode the output JPEG on the GPU instead of in PIL (byte-identical file)")),
+    ("--jpeg_quality", dict(type=int, default=75, help="Pillow's quality of the output JPEG, 1..100 (PIL or --jpeg_on_device: the same file)")),
+    ("--jpeg_subsampling", dict(type=str, default="4:2:0", choices=["4:4:4", "4:2:2", "4:2:0"], help="chroma subsampling of the output JPEG")),
+    ("--jpeg_optimize", dict(action="store_true", help="give the output JPEG its own optimal Huffman tables (Pillow's optimize=True)")),
     ("--coral_on_device", dict(action="store_true", help="preserve the content's colours (preserve_color) with CORAL computed on the GPU")),
     ("--jpeg_decode_on_device", dict(action="store_true", help="decode a baseline JPEG content on the GPU instead of in PIL (the same pixels)")),
     ("--jpeg_decode_progressive", dict(action="store_true", help="decode a progressive JPEG content on the GPU too (implies --jpeg_decode_on_device)")),
@@ -63,6 +67,7 @@ def main(argv=None):
     if ns.depth_npy:
         proximity = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
     prev = set_device_jpeg(ns.jpeg_on_device)
+    prev_options = set_jpeg_save_options(ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize)
     prev_coral = set_device_coral(ns.coral_on_device)
     prev_progressive = adain_test._device_jpeg_decode_progressive
     prev_decode = set_device_jpeg_decode(ns.jpeg_decode_on_device or ns.jpeg_decode_progressive, progressive=ns.jpeg_decode_progressive)
@@ -78,6 +83,7 @@ def main(argv=None):
                                use_depth=ns.use_depth, depth_map=proximity, preserve_color=ns.coral_on_device, **mix)
     finally:
         set_device_jpeg(prev)
+        set_jpeg_save_options(prev_options)
         set_device_coral(prev_coral)
         set_device_jpeg_decode(prev_decode, progressive=prev_progressive)
 

@@ -205,18 +205,20 @@ def device_decode_transform_u8(path, size, crop, device, mark=None):
     return _device_resize(out, parsed.w, parsed.h, plan)
 
 
-def save_image(tensor, path):
+def save_image(tensor, path, jpeg_options=None):
     """torchvision.utils.save_image for one image (test.py:243-244): x*255 + 0.5, clamp, uint8, PIL save.
-    The quantisation runs on the GPU (adain_quantize_u8)."""
+    The quantisation runs on the GPU (adain_quantize_u8).  ``jpeg_options`` (``runtime.JpegOptions``): how a .jpg / .jpeg file is
+    saved, by PIL or (``set_device_jpeg``) on the device; None: ``set_jpeg_save_options``' value."""
+    options = _jpeg_save_options if jpeg_options is None else rt.JpegOptions.of(jpeg_options)
     if tensor.dim() == 3:
         tensor = tensor.unsqueeze(0)
     if _device_jpeg_on and _is_jpeg_path(path) and tensor.shape[1] in (1, 3):
-        data, = rt.jpeg_files(*rt.jpeg_encode_u8(rt.quantize_u8(tensor.float()[:1])))
+        data, = rt.jpeg_files(*options.encode(rt.quantize_u8(tensor.float()[:1])))
         with open(str(path), "wb") as f:
             f.write(data)
         return
     u8 = rt.quantize_u8(tensor.float()[:1])[0].cpu().numpy()
-    Image.fromarray(u8[:, :, 0] if u8.shape[2] == 1 else u8).save(str(path))
+    options.save(Image.fromarray(u8[:, :, 0] if u8.shape[2] == 1 else u8), path)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -309,6 +311,20 @@ def set_device_jpeg(enabled):
     extension is saved by PIL as before.  Default False.  Returns the previous setting."""
     global _device_jpeg_on
     prev, _device_jpeg_on = _device_jpeg_on, bool(enabled)
+    return prev
+
+
+_jpeg_save_options = rt.JpegOptions()
+
+
+def set_jpeg_save_options(quality=rt.JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
+    """How ``adain_inference`` (the cached per-call path and ``save_image``) saves a ``.jpg`` / ``.jpeg`` output: Pillow's ``quality``,
+    ``subsampling`` (0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0") and ``optimize`` keywords, honoured by PIL and, with ``set_device_jpeg(True)``,
+    by the device encoder - the same file.  Any other extension never sees them.  A ``runtime.JpegOptions`` may be given in place of
+    ``quality``.  The defaults are Pillow's default save.  Returns the previous value (a ``JpegOptions``)."""
+    global _jpeg_save_options
+    new = rt.JpegOptions(quality, subsampling, optimize) if isinstance(quality, int) else rt.JpegOptions.of(quality)
+    prev, _jpeg_save_options = _jpeg_save_options, new
     return prev
 
 
@@ -811,7 +827,7 @@ def _one_call(x, style, enc, dec, device, call, e0=None, style_weights=None):
         e1.record()
         T.events.append((e0, e1))
     if _device_jpeg_on and _is_jpeg_path(target):
-        encoded = rt.jpeg_encode_u8(u8)
+        encoded = _jpeg_save_options.encode(u8)
         T("launch (one C-ABI call)", t0)
         t0 = time.perf_counter()
         data, = rt.jpeg_files(*encoded)
@@ -826,7 +842,7 @@ def _one_call(x, style, enc, dec, device, call, e0=None, style_weights=None):
     arr = u8[0].cpu().numpy()
     T("wait for the kernels + download", t0)
     t0 = time.perf_counter()
-    Image.fromarray(arr).save(str(target))
+    _jpeg_save_options.save(Image.fromarray(arr), target)
     T("encode + write the file", t0)
 
 

@@ -534,17 +534,29 @@ int adain_resize_pil_bilinear_u8(const uint8_t* in, int pixel_bytes, int n, int 
                                          (hipStream_t)stream);
 }
 
+int adain_jpeg_encode_opt_u8_bytes(int n, int h, int w, int c, int sampling, int optimize, size_t* out_stride, size_t* workspace_bytes) {
+    return jpeg_encode_bytes("jpeg_encode_opt_u8", n, h, w, c, sampling, optimize, out_stride, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+static int jpeg_encode(const char* who, const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out, size_t out_stride,
+                       int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream) {
+    if (!src || !out || !lengths || !workspace) { set_error("%s: null pointer", who); return ADAIN_EINVAL; }
+    size_t need_stride = 0, need_ws = 0;
+    if (jpeg_encode_bytes(who, n, h, w, c, sampling, optimize, &need_stride, &need_ws)) return ADAIN_EINVAL;
+    if (workspace_bytes < need_ws) { set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need_ws); return ADAIN_EINVAL; }
+    const int rc = launch_jpeg_encode_u8(who, src, n, h, w, c, quality, sampling, optimize, out, out_stride, lengths, workspace, (hipStream_t)stream);
+    return rc == -1 ? ADAIN_EINVAL : rc;
+}
+int adain_jpeg_encode_opt_u8(const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out, size_t out_stride,
+                             int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream) {
+    return jpeg_encode("jpeg_encode_opt_u8", src, n, h, w, c, quality, sampling, optimize, out, out_stride, lengths, workspace, workspace_bytes, stream);
+}
+// the entry from before the options: the one above at 4:2:0 with Annex K's tables
 int adain_jpeg_encode_u8_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes) {
-    return jpeg_encode_bytes(n, h, w, c, out_stride, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+    return jpeg_encode_bytes("jpeg_encode_u8", n, h, w, c, 2, 0, out_stride, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
 }
 int adain_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
                          size_t workspace_bytes, adain_stream_t stream) {
-    if (!src || !out || !lengths || !workspace) { set_error("jpeg_encode_u8: null pointer"); return ADAIN_EINVAL; }
-    size_t need_stride = 0, need_ws = 0;
-    if (jpeg_encode_bytes(n, h, w, c, &need_stride, &need_ws)) return ADAIN_EINVAL;
-    if (workspace_bytes < need_ws) { set_error("jpeg_encode_u8: workspace too small (%zu < %zu bytes)", workspace_bytes, need_ws); return ADAIN_EINVAL; }
-    const int rc = launch_jpeg_encode_u8(src, n, h, w, c, quality, out, out_stride, lengths, workspace, (hipStream_t)stream);
-    return rc == -1 ? ADAIN_EINVAL : rc;
+    return jpeg_encode("jpeg_encode_u8", src, n, h, w, c, quality, 2, 0, out, out_stride, lengths, workspace, workspace_bytes, stream);
 }
 
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {

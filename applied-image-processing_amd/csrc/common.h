@@ -175,9 +175,11 @@ int launch_tvl1_flow(const float* const* prev, const float* const* next, int npa
                      void* ws, size_t ws_bytes, hipStream_t s);
 
 // jpeg.hip: baseline JPEG files, byte for byte Pillow's default save (the rules: top of jpeg.hip, tests/jpeg_ref.py)
-int jpeg_encode_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes);
-int launch_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
-                          hipStream_t s);
+// sampling 0 / 1 / 2 (4:4:4, 4:2:2, 4:2:0), optimize 0 / 1 (a frame's own Huffman tables): Pillow's save with those keywords
+// (tests/jpeg_options_ref.py); (2, 0) is the default file.  who: the entry's name in front of its error messages
+int jpeg_encode_bytes(const char* who, int n, int h, int w, int c, int sampling, int optimize, size_t* out_stride, size_t* workspace_bytes);
+int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out,
+                          size_t out_stride, int32_t* lengths, void* workspace, hipStream_t s);
 // the pixels Pillow decodes from that file, without the file (the rules: top of jpeg.hip, tests/jpeg_decode_ref.py)
 int jpeg_roundtrip_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
 int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, hipStream_t s);

@@ -35,6 +35,17 @@
 //   ffcount / scan / scatter   0xFF bytes per 1024-byte chunk, their scan, and the copy behind the header with a 0x00 after each 0xFF;
 //              the scatter also writes the header, FFD9 and lengths[i]
 //
+// The options (adain_jpeg_encode_opt_u8): Pillow's save with subsampling = 0 / 1 / 2 and optimize = False / True; (2, False) is the file
+// above in the launches above.  tests/jpeg_options_ref.py restates the rules, tests/test_jpeg_options_host.py holds that to Pillow.
+//   4:4:4    8 x 8 MCUs, blocks Y Cb Cr, SOF0 luma sampling 0x11; the chroma planes are edge-replicated to whole blocks, not downsampled
+//   4:2:2    16 x 8 MCUs, blocks Y0 Y1 Cb Cr, 0x21; the full-resolution chroma columns are replicated to whole MCUs and downsampled as
+//            (a + b + bias) >> 1 with bias 0 on even output columns and 1 on odd ones, the rows replicated to whole blocks; a luma
+//            block beyond ceil(w/8) is a dummy as above
+//   grey     ignores the subsampling: the file is the one Pillow writes for an L image without the keyword
+//   optimize libjpeg's two-pass optimize_coding - the rule list stands in front of its kernels ("optimised tables"): the histogram and
+//            table stages run between transform and count (10 launches and a memset), count and emit read the frame's own tables
+//            from the workspace, and scatter writes a per-frame header with four (grey: two) DHT segments of only the symbols that occur
+//
 // The round trip (adain_jpeg_roundtrip_u8): the pixels Pillow decodes from that file, byte for byte, without the file.  Entropy coding is
 // lossless, so they are a function of the quantised coefficients the transform stage leaves in the workspace; what follows it is the
 // back half of libjpeg's decoder.  tests/jpeg_decode_ref.py restates it in NumPy, tests/test_jpeg_roundtrip_host.py holds that to Pillow.
@@ -111,6 +122,7 @@ struct Tables {
     Huff huff;
     uint8_t hdr[2][640];     // [0]: greyscale, [1]: RGB; the DQT entries and SOF0's size are left 0
     int hdr_len[2], dqt[2][2], sof_hw[2];       // offsets of the 64 DQT entries per table and of SOF0's height
+    int sof_luma[2], dht[2], sos[2];            // offsets of SOF0's luma sampling byte, of the first DHT and of SOS
     int max_block_bits;
 };
 
@@ -186,8 +198,11 @@ constexpr Tables make_tables() {
         t.sof_hw[rgb] = n;
         n += 4;
         put(rgb ? 3 : 1);
-        put(1); put(rgb ? 0x22 : 0x11); put(0);
+        put(1);
+        t.sof_luma[rgb] = n;
+        put(rgb ? 0x22 : 0x11); put(0);
         if (rgb) { put(2); put(0x11); put(1); put(3); put(0x11); put(1); }
+        t.dht[rgb] = n;
         for (int k = 0; k <= rgb; ++k) {
             seg(0xc4, 1 + 16 + 12);
             put(k);
@@ -198,6 +213,7 @@ constexpr Tables make_tables() {
             for (int i = 0; i < 16; ++i) put(AC_BITS[k][i]);
             for (int i = 0; i < 162; ++i) put(AC_VALS[k][i]);
         }
+        t.sos[rgb] = n;
         seg(0xda, rgb ? 10 : 6);
         put(rgb ? 3 : 1);
         put(1); put(0x00);
@@ -213,25 +229,41 @@ static_assert(HOST_T.hdr_len[1] == 623 && HOST_T.max_block_bits == 1660, "the he
 __constant__ const Tables T = make_tables();
 
 // ---- sizes -----------------------------------------------------------------------------------------------------------------------------
+// A frame's own Huffman code of one table slot (DC0, AC0, DC1, AC1), built on the device for optimize = 1: what count and emit read in
+// place of T.huff, and the slot's DHT payload for the header.
+struct HuffSlot {
+    uint16_t code[256];
+    uint8_t len[256];        // 0: the symbol does not occur
+    uint8_t bits[16];        // codes per length 1..16
+    uint8_t vals[256];       // the first nvals: the symbols by code length, then by value
+    uint32_t nvals;
+};
+constexpr int SLOTS = 4;                                    // per frame in the workspace, whatever c
+constexpr int OPT_BLOCK_BITS = (16 + 11) + 63 * (16 + 10);  // every code of an optimal table may be 16 bits long
+constexpr int HIST_GRID = 128;                              // workgroups per frame of the histogram stage
+
 struct Plan {
-    int c, mw, mh, bw, bh;
+    int c, hs, vs, mw, mh, bw, bh;      // hs x vs: luma blocks per MCU (RGB); mw x mh: MCUs
     size_t nblk;                  // blocks per frame in scan order, dummy blocks included
     size_t max_bytes;             // entropy-coded bytes of a frame before stuffing, at most
     size_t stream_words;          // words of one frame's bit stream
     size_t chunks;                // CHUNK-byte pieces of max_bytes
     size_t out_stride;
     size_t o_coef, o_bits, o_off, o_total, o_stream, o_ffcnt, o_ffoff, o_fftotal, total;      // workspace offsets (bytes) of the n-frame arrays
+    size_t o_hist, o_huff;              // optimize only: uint64 [n][SLOTS][256] symbol counts, HuffSlot [n][SLOTS]
 };
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-Plan make_plan(int n, int h, int w, int c) {
+// sampling: 0 (4:4:4), 1 (4:2:2), 2 (4:2:0); greyscale has no MCUs and is planned as 2: (2, false) is the default file's plan
+Plan make_plan(int n, int h, int w, int c, int sampling = 2, bool optimize = false) {
     Plan p{};
     p.c = c;
+    p.hs = c == 3 && sampling == 0 ? 1 : 2, p.vs = c == 3 && sampling != 2 ? 1 : 2;
     p.bw = (w + 7) / 8, p.bh = (h + 7) / 8;
-    p.mw = (w + 15) / 16, p.mh = (h + 15) / 16;
-    p.nblk = c == 3 ? (size_t)p.mw * p.mh * 6 : (size_t)p.bw * p.bh;
-    p.max_bytes = (p.nblk * HOST_T.max_block_bits + 7) / 8;
+    p.mw = (w + 8 * p.hs - 1) / (8 * p.hs), p.mh = (h + 8 * p.vs - 1) / (8 * p.vs);
+    p.nblk = c == 3 ? (size_t)p.mw * p.mh * (p.hs * p.vs + 2) : (size_t)p.bw * p.bh;
+    p.max_bytes = (p.nblk * (optimize ? OPT_BLOCK_BITS : HOST_T.max_block_bits) + 7) / 8;
     p.stream_words = (p.max_bytes + 3) / 4 + 4;
     p.chunks = (p.max_bytes + CHUNK - 1) / CHUNK;
     p.out_stride = HOST_T.hdr_len[c == 3] + 2 * p.max_bytes + 2;
@@ -245,6 +277,10 @@ Plan make_plan(int n, int h, int w, int c) {
     p.o_ffcnt = take(N * p.chunks * sizeof(uint32_t));
     p.o_ffoff = take(N * p.chunks * sizeof(uint32_t));
     p.o_fftotal = take(N * sizeof(uint32_t));
+    if (optimize) {
+        p.o_hist = take(N * SLOTS * 256 * sizeof(uint64_t));
+        p.o_huff = take(N * SLOTS * sizeof(HuffSlot));
+    }
     p.total = at;
     return p;
 }
@@ -354,6 +390,51 @@ __global__ __launch_bounds__(MCUS_PER_WG * 48) void jpeg_transform_rgb_kernel(co
                            [&](int j) { const int m = j / 6, k = j - m * 6; return k < 4 && !(2 * (mx0 + m) + (k & 1) < bw && 2 * my + (k >> 1) < bh); });
 }
 
+// 4:4:4 (HS = 1: 8 x 8 MCUs, blocks Y Cb Cr) and 4:2:2 (HS = 2: 16 x 8 MCUs, blocks Y0 Y1 Cb Cr): one workgroup per 128 x 8 pixel strip.
+// Chroma: the full-resolution planes are edge-replicated to whole MCUs; 4:2:2 then averages column pairs as (a + b + bias) >> 1 with bias
+// 0 on even output columns and 1 on odd ones.  The second luma block of a 4:2:2 MCU beyond ceil(w/8) is a dummy.
+template <int HS>
+__global__ __launch_bounds__((128 / (8 * HS)) * (HS + 2) * 8) void jpeg_transform_rgb_h_kernel(const uint8_t* __restrict__ src, int h, int w, int quality,
+                                                                                               int16_t* __restrict__ coef, int mw, int bw, size_t nblk) {
+    constexpr int PX = 128, BPM = HS + 2, MCUS = PX / (8 * HS), NB = MCUS * BPM, THREADS = NB * 8, CW = PX / HS;
+    __shared__ uint8_t raw[8 * PX * 3];
+    __shared__ int samp[NB * 72];
+    __shared__ int q8[128];
+    __shared__ __attribute__((aligned(16))) int16_t zq[NB * 64];
+    const int t = threadIdx.x, my = blockIdx.y, mx0 = blockIdx.x * MCUS;
+    const uint8_t* img = src + (size_t)blockIdx.z * h * w * 3;
+    if (t < 128) q8[t] = 8 * quant_entry(t >> 6, t & 63, quality);
+    for (int i = t; i < 8 * PX * 3; i += THREADS) {
+        const int r = i / (PX * 3), j = i - r * (PX * 3), px = j / 3, ch = j - px * 3;
+        const int gy = min(my * 8 + r, h - 1), gx = min(mx0 * 8 * HS + px, w - 1);
+        raw[i] = img[((size_t)gy * w + gx) * 3 + ch];
+    }
+    __syncthreads();
+    for (int i = t; i < 8 * PX + 2 * 8 * CW; i += THREADS) {
+        if (i < 8 * PX) {
+            const int r = i / PX, c = i - r * PX;
+            const uint8_t* p = raw + r * (PX * 3) + c * 3;
+            const int y = (19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 32768) >> 16;
+            samp[((c / (8 * HS)) * BPM + ((c >> 3) & (HS - 1))) * 72 + r * 9 + (c & 7)] = y - 128;
+        } else {
+            const int j = i - 8 * PX, comp = j / (8 * CW), jj = j - comp * (8 * CW), crow = jj / CW, cc = jj - crow * CW;
+            int sum = HS == 2 ? (cc & 1) : 0;
+#pragma unroll
+            for (int k = 0; k < HS; ++k) {
+                const uint8_t* p = raw + crow * (PX * 3) + (HS * cc + k) * 3;
+                sum += comp == 0 ? (-11059 * p[0] - 21709 * p[1] + 32768 * p[2] + (128 << 16) + 32767) >> 16
+                                 : (32768 * p[0] - 27439 * p[1] - 5329 * p[2] + (128 << 16) + 32767) >> 16;
+            }
+            samp[((cc >> 3) * BPM + HS + comp) * 72 + crow * 9 + (cc & 7)] = (sum >> (HS - 1)) - 128;
+        }
+    }
+    __syncthreads();
+    const int count = min(MCUS, mw - mx0) * BPM;
+    int16_t* dst = coef + ((size_t)blockIdx.z * nblk + ((size_t)my * mw + mx0) * BPM) * 64;
+    dct_quantise_store<NB>(samp, q8, zq, dst, count, [](int j) { return j % BPM >= HS ? 1 : 0; },
+                           [&](int j) { const int m = j / BPM, k = j - m * BPM; return k < HS && !(HS * (mx0 + m) + k < bw); });
+}
+
 __global__ __launch_bounds__(GREY_PER_WG * 8) void jpeg_transform_grey_kernel(const uint8_t* __restrict__ src, int h, int w, int quality, int16_t* __restrict__ coef,
                                                                               int bw, size_t nblk) {
     constexpr int NB = GREY_PER_WG, PX = NB * 8, THREADS = NB * 8;
@@ -374,109 +455,259 @@ __global__ __launch_bounds__(GREY_PER_WG * 8) void jpeg_transform_grey_kernel(co
 }
 
 // ---- entropy coding: one wave64 per block, one lane per coefficient ------------------------------------------------------------------------
+// The MCU layout is a template parameter of what follows: HS x VS luma blocks, then Cb and Cr (2 x 2: 4:2:0, 2 x 1: 4:2:2, 1 x 1: 4:4:4).
 struct Geometry {
     int c, mw, bw, bh;
     size_t nblk;
 };
 
-__device__ __forceinline__ bool luma_is_real(const Geometry& g, int mx, int my, int k) { return 2 * mx + (k & 1) < g.bw && 2 * my + (k >> 1) < g.bh; }
+template <int HS, int VS>
+__device__ __forceinline__ bool luma_is_real(const Geometry& g, int mx, int my, int k) { return HS * mx + (k % HS) < g.bw && VS * my + (k / HS) < g.bh; }
 
 // The DC difference of block b of a frame (wave-uniform).  The predictor of a real luma block is the last real block before it in the
 // scan: the dummy blocks in between carry that block's DC.
+template <int HS, int VS>
 __device__ int dc_difference(const int16_t* __restrict__ coef, size_t b, const Geometry& g, int* table) {
+    constexpr int NL = HS * VS, BPM = NL + 2;
     *table = 0;
     if (g.c != 3) return coef[b * 64] - (b ? coef[(b - 1) * 64] : 0);
-    size_t m = b / 6;
-    int k = (int)(b - m * 6);
-    if (k >= 4) {
+    size_t m = b / BPM;
+    int k = (int)(b - m * BPM);
+    if (k >= NL) {
         *table = 1;
-        return coef[b * 64] - (m ? coef[((m - 1) * 6 + k) * 64] : 0);
+        return coef[b * 64] - (m ? coef[((m - 1) * BPM + k) * 64] : 0);
     }
-    if (!luma_is_real(g, (int)(m % g.mw), (int)(m / g.mw), k)) return 0;
+    if (!luma_is_real<HS, VS>(g, (int)(m % g.mw), (int)(m / g.mw), k)) return 0;
     const int dc = coef[b * 64];
     if (k == 0) {
         if (m == 0) return dc;
-        --m, k = 3;
+        --m, k = NL - 1;
     } else {
         --k;
     }
     const int mx = (int)(m % g.mw), my = (int)(m / g.mw);
-    while (!luma_is_real(g, mx, my, k)) --k;      // block 0 of an MCU is always real
-    return dc - coef[(m * 6 + k) * 64];
+    while (!luma_is_real<HS, VS>(g, mx, my, k)) --k;      // block 0 of an MCU is always real
+    return dc - coef[(m * BPM + k) * 64];
 }
 
 // What this lane puts into the stream: the ZRLs of its run, its code and its value bits, and the EOB when it is the last coded
-// coefficient of a block that does not end at 63; right-aligned in *pattern.  Returns the number of bits (at most 63; 0: a zero).
-__device__ __forceinline__ int lane_bits(int lane, int v, int table, uint64_t* pattern) {
+// coefficient of a block that does not end at 63; right-aligned in *pattern.  Returns the number of bits (0: a zero).  Annex K's tables
+// (OPT false) keep all of it within 63 bits.  A frame's own tables (OPT: `huff`, its SLOTS HuffSlot) may give ZRL and EOB 16 bits, 90 in
+// all, so there the ZRLs go first into *zrl (at most 48 bits, *zrl_len) and the rest (at most 42) into *pattern.
+template <bool OPT>
+__device__ __forceinline__ int lane_bits(int lane, int v, int table, const HuffSlot* __restrict__ huff, uint64_t* pattern, uint64_t* zrl, int* zrl_len) {
     const uint64_t mask = __ballot(v != 0) | 1ull;        // the DC always codes
+    *zrl = 0, *zrl_len = 0;
     if (!((mask >> lane) & 1)) { *pattern = 0; return 0; }
     const int a = v < 0 ? -v : v;
     const int size = 32 - __clz(a);
     const uint32_t value = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << size) - 1);
+    const HuffSlot* dc = huff + 2 * table;
+    const HuffSlot* ac = dc + 1;
+    auto ac_code = [&](int sym) { return OPT ? (int)ac->code[sym] : (int)T.huff.ac_code[table][sym]; };
+    auto ac_len = [&](int sym) { return OPT ? (int)ac->len[sym] : (int)T.huff.ac_len[table][sym]; };
     uint64_t pat = 0;
     int len = 0;
     if (lane == 0) {
-        pat = T.huff.dc_code[table][size], len = T.huff.dc_len[table][size];
+        pat = OPT ? dc->code[size] : T.huff.dc_code[table][size], len = OPT ? dc->len[size] : T.huff.dc_len[table][size];
     } else {
         const int prev = 63 - __clzll((long long)(mask & ((1ull << lane) - 1)));
         const int run = lane - prev - 1;
-        const int zc = T.huff.ac_code[table][0xf0], zl = T.huff.ac_len[table][0xf0];
+        const int zc = ac_code(0xf0), zl = ac_len(0xf0);
         for (int k = 0; k < (run >> 4); ++k) pat = (pat << zl) | zc, len += zl;
+        if (OPT) *zrl = pat, *zrl_len = len, pat = 0, len = 0;
         const int sym = ((run & 15) << 4) | size;
-        const int cl = T.huff.ac_len[table][sym];
-        pat = (pat << cl) | T.huff.ac_code[table][sym], len += cl;
+        const int cl = ac_len(sym);
+        pat = (pat << cl) | ac_code(sym), len += cl;
     }
     pat = (pat << size) | value, len += size;
     if (lane < 63 && lane == 63 - __clzll((long long)mask)) {
-        const int el = T.huff.ac_len[table][0];
-        pat = (pat << el) | T.huff.ac_code[table][0], len += el;
+        const int el = ac_len(0);
+        pat = (pat << el) | ac_code(0), len += el;
     }
     *pattern = pat;
     return len;
 }
 
-__global__ __launch_bounds__(256) void jpeg_count_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ bits, Geometry g, size_t total_blocks) {
+template <int HS, int VS, bool OPT>
+__global__ __launch_bounds__(256) void jpeg_count_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ bits, Geometry g, size_t total_blocks,
+                                                         const HuffSlot* __restrict__ huff) {
     const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= total_blocks) return;
     const int lane = threadIdx.x & 63;
     const size_t f = gw / g.nblk, b = gw - f * g.nblk;
     const int16_t* fc = coef + f * g.nblk * 64;
     int table;
-    const int diff = dc_difference(fc, b, g, &table);
+    const int diff = dc_difference<HS, VS>(fc, b, g, &table);
     const int v = lane == 0 ? diff : fc[b * 64 + lane];
-    uint64_t pat;
-    int len = lane_bits(lane, v, table, &pat);
+    uint64_t pat, zrl;
+    int zrl_len;
+    int len = lane_bits<OPT>(lane, v, table, huff + f * SLOTS, &pat, &zrl, &zrl_len);
+    len += zrl_len;
     for (int d = 32; d >= 1; d >>= 1) len += __shfl_xor(len, d);
     if (lane == 0) bits[gw] = (uint32_t)len;
 }
 
+// ORs the `len` (1..64) right-aligned bits of pat into the big-endian bit stream at bit position pos.  A word is touched only where
+// there are bits for it: never beyond the frame's last coded bit.
+__device__ __forceinline__ void or_bits(uint32_t* __restrict__ stream, uint64_t pos, uint64_t pat, int len) {
+    uint32_t* word = stream + (size_t)(pos >> 5);
+    const int o = (int)(pos & 31);
+    const uint64_t hi = pat << (64 - len);                // left-aligned; the 96-bit window starting at the word is hi >> o
+    const uint32_t w0 = (uint32_t)((hi >> 32) >> o), w1 = (uint32_t)(hi >> o), w2 = o ? (uint32_t)hi << (32 - o) : 0u;
+    if (w0) atomicOr(word, w0);
+    if (w1) atomicOr(word + 1, w1);
+    if (w2) atomicOr(word + 2, w2);
+}
+
+template <int HS, int VS, bool OPT>
 __global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restrict__ coef, const uint64_t* __restrict__ off, uint32_t* __restrict__ stream,
-                                                        size_t stream_words, Geometry g, size_t total_blocks) {
+                                                        size_t stream_words, Geometry g, size_t total_blocks, const HuffSlot* __restrict__ huff) {
     const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= total_blocks) return;
     const int lane = threadIdx.x & 63;
     const size_t f = gw / g.nblk, b = gw - f * g.nblk;
     const int16_t* fc = coef + f * g.nblk * 64;
     int table;
-    const int diff = dc_difference(fc, b, g, &table);
+    const int diff = dc_difference<HS, VS>(fc, b, g, &table);
     const int v = lane == 0 ? diff : fc[b * 64 + lane];
-    uint64_t pat;
-    const int len = lane_bits(lane, v, table, &pat);
-    int incl = len;
+    uint64_t pat, zrl;
+    int zrl_len;
+    const int len = lane_bits<OPT>(lane, v, table, huff + f * SLOTS, &pat, &zrl, &zrl_len);
+    int incl = len + zrl_len;
     for (int d = 1; d < 64; d <<= 1) {
         const int up = __shfl_up(incl, d);
         if (lane >= d) incl += up;
     }
     if (len == 0) return;
-    const uint64_t pos = off[gw] + (uint64_t)(incl - len);
-    uint32_t* word = stream + f * stream_words + (size_t)(pos >> 5);
-    const int o = (int)(pos & 31);
-    const uint64_t hi = pat << (64 - len);                // left-aligned; the 96-bit window starting at the word is hi >> o
-    const uint32_t w0 = (uint32_t)((hi >> 32) >> o), w1 = (uint32_t)(hi >> o), w2 = o ? (uint32_t)hi << (32 - o) : 0u;
-    // a word is touched only where this lane has bits in it: never beyond the frame's last coded bit
-    if (w0) atomicOr(word, w0);
-    if (w1) atomicOr(word + 1, w1);
-    if (w2) atomicOr(word + 2, w2);
+    const uint64_t pos = off[gw] + (uint64_t)(incl - len - zrl_len);
+    if (OPT && zrl_len) or_bits(stream + f * stream_words, pos, zrl, zrl_len);
+    or_bits(stream + f * stream_words, pos + zrl_len, pat, len);
+}
+
+// ---- optimised tables: libjpeg's two-pass optimize_coding --------------------------------------------------------------------------------
+// histogram  the symbols emit will code, per frame and table slot: the DC category; per non-zero AC its run/size symbol and 0xF0 once per
+//            ZRL; 0x00 per EOB.  A workgroup counts its blocks in LDS (at most 64 symbols per block and table, far below 2^32 for
+//            the blocks one workgroup sees) and adds what it has to the frame's 64-bit counters: integer adds, any order, and no wrap
+// table      one workgroup per (frame, slot), one thread per symbol plus the pseudo-symbol 256 of frequency 1 (so that no code is all
+//            ones).  Merge until one tree is left: c1 = the smallest non-zero frequency, among equals the LARGEST symbol; c2 = the same
+//            without c1; c1 takes both frequencies, c2 becomes 0, every member of both trees gets one bit longer and c2's tree joins
+//            c1's.  Then the symbols are counted per length and limited to 16 as in Annex K.3 (from the longest down to 17: take two from
+//            length i, give one to i - 1; take one from the largest j <= i - 2 that has any, give two to j + 1), the pseudo-symbol leaves
+//            the longest length, and the symbols are listed by UNRESTRICTED length, then by value; codes count up per length.
+template <int HS, int VS>
+__global__ __launch_bounds__(256) void jpeg_histogram_kernel(const int16_t* __restrict__ coef, Geometry g, unsigned long long* __restrict__ hist) {
+    __shared__ uint32_t cnt[SLOTS][256];
+    const int lane = threadIdx.x & 63;
+    const size_t f = blockIdx.y;
+    for (int i = threadIdx.x; i < SLOTS * 256; i += 256) (&cnt[0][0])[i] = 0;
+    __syncthreads();
+    const int16_t* fc = coef + f * g.nblk * 64;
+    for (size_t b = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < g.nblk; b += (size_t)gridDim.x * 4) {
+        int table;
+        const int diff = dc_difference<HS, VS>(fc, b, g, &table);
+        const int v = lane == 0 ? diff : fc[b * 64 + lane];
+        const uint64_t mask = __ballot(v != 0) | 1ull;
+        if (!((mask >> lane) & 1)) continue;
+        const int size = 32 - __clz(v < 0 ? -v : v);
+        if (lane == 0) {
+            atomicAdd(&cnt[2 * table][size], 1u);
+        } else {
+            const int run = lane - (63 - __clzll((long long)(mask & ((1ull << lane) - 1)))) - 1;
+            if (run >> 4) atomicAdd(&cnt[2 * table + 1][0xf0], (uint32_t)(run >> 4));
+            atomicAdd(&cnt[2 * table + 1][((run & 15) << 4) | size], 1u);
+        }
+        if (lane < 63 && lane == 63 - __clzll((long long)mask)) atomicAdd(&cnt[2 * table + 1][0], 1u);
+    }
+    __syncthreads();
+    for (int k = 0; k < SLOTS; ++k) {
+        const uint32_t c = cnt[k][threadIdx.x];
+        if (c) atomicAdd(&hist[(f * SLOTS + k) * 256 + threadIdx.x], (unsigned long long)c);
+    }
+}
+
+constexpr int TABLE_THREADS = 320;      // 5 waves: a thread per symbol 0..256, the rest idle
+
+// The thread holding the smallest non-zero frequency (among equals the largest index) of those with `in`; -1: none.  Uniform over the
+// workgroup.  part: one of two LDS buffers that successive calls alternate, so that one barrier per call is enough: a wave can write a
+// buffer again only behind the barrier of the call in between, which every reader of the earlier contents has reached.
+struct Least {
+    unsigned long long f;
+    int at;
+};
+__device__ __forceinline__ Least better(Least a, Least b) { return (b.at >= 0 && (a.at < 0 || b.f < a.f || (b.f == a.f && b.at > a.at))) ? b : a; }
+__device__ __forceinline__ Least least_frequency(unsigned long long f, bool in, Least* part) {
+    Least m{f, in && f ? (int)threadIdx.x : -1};
+    for (int d = 32; d >= 1; d >>= 1) {
+        Least o;
+        o.f = ((unsigned long long)(uint32_t)__shfl_xor((int)(m.f >> 32), d) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)m.f, d);
+        o.at = __shfl_xor(m.at, d);
+        m = better(m, o);
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    m = part[0];
+    for (int k = 1; k < TABLE_THREADS / 64; ++k) m = better(m, part[k]);
+    return m;
+}
+
+__global__ __launch_bounds__(TABLE_THREADS) void jpeg_table_kernel(const unsigned long long* __restrict__ hist, HuffSlot* __restrict__ huff) {
+    __shared__ Least part[2][TABLE_THREADS / 64];
+    __shared__ int size_of[256];                // the unrestricted code length per symbol
+    __shared__ int bits[260];                   // symbols per code length; a chain of 257 symbols is at most 256 deep
+    __shared__ int first[18], upto[18];         // per length 1..16: its first code; the symbols of shorter-or-equal length
+    const int t = threadIdx.x;
+    const size_t slot = (size_t)blockIdx.y * SLOTS + blockIdx.x;
+    unsigned long long f = t < 256 ? hist[slot * 256 + t] : t == 256 ? 1ull : 0ull;
+    int tree = t, size = 0;
+    for (int i = t; i < 260; i += TABLE_THREADS) bits[i] = 0;
+    for (;;) {
+        const Least c1 = least_frequency(f, true, part[0]);
+        const Least c2 = least_frequency(f, t != c1.at, part[1]);
+        if (c2.at < 0) break;
+        if (t == c1.at) f += c2.f;
+        if (t == c2.at) f = 0;
+        if (tree == c1.at || tree == c2.at) ++size, tree = c1.at;
+    }
+    if (t < 256) size_of[t] = size;
+    __syncthreads();
+    if (t <= 256 && size) atomicAdd(&bits[size], 1);
+    __syncthreads();
+    if (t == 0) {
+        for (int i = 256; i > 16; --i)
+            while (bits[i] > 0) {
+                int j = i - 2;
+                while (j > 0 && bits[j] == 0) --j;
+                bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1;
+            }
+        int i = 16;
+        while (i > 1 && bits[i] == 0) --i;
+        bits[i] -= 1;
+        int code = 0, n = 0;
+        upto[0] = 0;
+        for (int len = 1; len <= 16; ++len) {
+            first[len] = code, n += bits[len], upto[len] = n;
+            code = (code + bits[len]) << 1;
+            huff[slot].bits[len - 1] = (uint8_t)bits[len];
+        }
+        huff[slot].nvals = (uint32_t)n;
+    }
+    __syncthreads();
+    if (t < 256) {
+        int len = 0, code = 0;
+        if (size) {
+            int rank = 0;
+            for (int s = 0; s < 256; ++s) {
+                const int other = size_of[s];
+                rank += (other && (other < size || (other == size && s < t))) ? 1 : 0;
+            }
+            len = 1;
+            while (len < 16 && upto[len] <= rank) ++len;
+            code = first[len] + rank - upto[len - 1];
+            huff[slot].vals[rank] = (uint8_t)t;
+        }
+        huff[slot].code[t] = (uint16_t)code, huff[slot].len[t] = (uint8_t)len;
+    }
 }
 
 // ---- scans: one workgroup per frame ------------------------------------------------------------------------------------------------------
@@ -570,24 +801,47 @@ __global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const uint32_t* __res
     }
 }
 
+// Byte i of a frame's header.  luma: SOF0's sampling byte of component 1.  OPT: the DHT segments hold the frame's own tables (`huff`, its
+// SLOTS HuffSlot; `slots` of them used), each with only the symbols that occur, so the header's length varies per frame: at[k] is
+// where segment k starts, at[slots] where SOS does.
+template <bool OPT>
+__device__ __forceinline__ int header_byte(int i, int rgb, int h, int w, int quality, int luma, const HuffSlot* __restrict__ huff, const int* at, int slots) {
+    if (OPT && i >= T.dht[rgb]) {
+        if (i >= at[slots]) return T.hdr[rgb][T.sos[rgb] + i - at[slots]];
+        int k = 0;
+        while (i >= at[k + 1]) ++k;
+        const int j = i - at[k], payload = 2 + 1 + 16 + (int)huff[k].nvals;
+        return j == 0 ? 0xff : j == 1 ? 0xc4 : j == 2 ? payload >> 8 : j == 3 ? payload & 255 : j == 4 ? ((k & 1) << 4) | (k >> 1)
+             : j < 21 ? huff[k].bits[j - 5] : huff[k].vals[j - 21];
+    }
+    int v = T.hdr[rgb][i];
+    for (int k = 0; k <= rgb; ++k)
+        if (i >= T.dqt[rgb][k] && i < T.dqt[rgb][k] + 64) v = quant_entry(k, T.zigzag[i - T.dqt[rgb][k]], quality);
+    const int j = i - T.sof_hw[rgb];
+    if (j >= 0 && j < 4) v = j == 0 ? h >> 8 : j == 1 ? h & 255 : j == 2 ? w >> 8 : w & 255;
+    return i == T.sof_luma[rgb] ? luma : v;
+}
+
+template <bool OPT>
 __global__ __launch_bounds__(256) void jpeg_scatter_kernel(const uint32_t* __restrict__ stream, size_t stream_words, const uint64_t* __restrict__ total_bits,
                                                            const uint32_t* __restrict__ ffoff, const uint32_t* __restrict__ fftotal, size_t chunks, int h, int w,
-                                                           int rgb, int quality, uint8_t* __restrict__ out, size_t out_stride, int32_t* __restrict__ lengths) {
+                                                           int rgb, int quality, int luma, const HuffSlot* __restrict__ huff, uint8_t* __restrict__ out,
+                                                           size_t out_stride, int32_t* __restrict__ lengths) {
     __shared__ int part[4];
     const size_t f = blockIdx.y;
     const uint64_t bits = total_bits[f];
     const uint32_t* s = stream + f * stream_words;
     uint8_t* file = out + f * out_stride;
-    const int hdr = T.hdr_len[rgb];
+    const int slots = rgb ? 4 : 2;
+    int at[SLOTS + 1] = {}, hdr = T.hdr_len[rgb];
+    if (OPT) {
+        huff += f * SLOTS;
+        at[0] = T.dht[rgb];
+        for (int k = 0; k < slots; ++k) at[k + 1] = at[k] + 4 + 1 + 16 + (int)huff[k].nvals;
+        hdr = at[slots] + T.hdr_len[rgb] - T.sos[rgb];
+    }
     if (blockIdx.x == 0) {
-        for (int i = threadIdx.x; i < hdr; i += 256) {
-            int v = T.hdr[rgb][i];
-            for (int k = 0; k <= rgb; ++k)
-                if (i >= T.dqt[rgb][k] && i < T.dqt[rgb][k] + 64) v = quant_entry(k, T.zigzag[i - T.dqt[rgb][k]], quality);
-            const int j = i - T.sof_hw[rgb];
-            if (j >= 0 && j < 4) v = j == 0 ? h >> 8 : j == 1 ? h & 255 : j == 2 ? w >> 8 : w & 255;
-            file[i] = (uint8_t)v;
-        }
+        for (int i = threadIdx.x; i < hdr; i += 256) file[i] = (uint8_t)header_byte<OPT>(i, rgb, h, w, quality, luma, huff, at, slots);
         if (threadIdx.x == 0) {
             const size_t end = hdr + stream_bytes(bits) + fftotal[f];
             file[end] = 0xff, file[end + 1] = 0xd9;
@@ -1787,26 +2041,56 @@ const char* check_shape(int n, int h, int w, int c, int quality) {
     return nullptr;
 }
 
+const char* check_options(int sampling, int optimize) {
+    if (sampling < 0 || sampling > 2) return "sampling outside 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)";
+    if (optimize < 0 || optimize > 1) return "optimize outside 0..1";
+    return nullptr;
+}
+
 }  // namespace
 
-int jpeg_encode_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes) {
+int jpeg_encode_bytes(const char* who, int n, int h, int w, int c, int sampling, int optimize, size_t* out_stride, size_t* workspace_bytes) {
     const char* bad = check_shape(n, h, w, c, 75);
-    if (!bad && make_plan(n, h, w, c).out_stride > (size_t)INT32_MAX) bad = "a worst-case file beyond 2^31 - 1 bytes (lengths are int32)";
-    if (bad) { set_error("jpeg_encode_u8: %s (n %d, %d x %d x %d)", bad, n, h, w, c); return -1; }
-    const Plan p = make_plan(n, h, w, c);
+    if (!bad) bad = check_options(sampling, optimize);
+    if (!bad && make_plan(n, h, w, c, sampling, optimize).out_stride > (size_t)INT32_MAX) bad = "a worst-case file beyond 2^31 - 1 bytes (lengths are int32)";
+    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, sampling %d, optimize %d)", who, bad, n, h, w, c, sampling, optimize); return -1; }
+    const Plan p = make_plan(n, h, w, c, sampling, optimize);
     if (out_stride) *out_stride = p.out_stride;
     if (workspace_bytes) *workspace_bytes = p.total;
     return 0;
 }
 
-int launch_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
-                          hipStream_t s) {
+namespace {
+
+// count, (optimize) histogram and emit of one MCU layout
+template <int HS, int VS>
+void launch_entropy_stage(int stage, bool optimize, unsigned grid, int n, const int16_t* coef, uint32_t* bits, const uint64_t* off, uint32_t* stream,
+                          size_t stream_words, const Geometry& g, size_t blocks, unsigned long long* hist, const HuffSlot* huff, hipStream_t s) {
+    if (stage == 0)
+        jpeg_histogram_kernel<HS, VS><<<dim3(HIST_GRID, n), 256, 0, s>>>(coef, g, hist);
+    else if (stage == 1 && optimize)
+        jpeg_count_kernel<HS, VS, true><<<grid, 256, 0, s>>>(coef, bits, g, blocks, huff);
+    else if (stage == 1)
+        jpeg_count_kernel<HS, VS, false><<<grid, 256, 0, s>>>(coef, bits, g, blocks, huff);
+    else if (optimize)
+        jpeg_emit_kernel<HS, VS, true><<<grid, 256, 0, s>>>(coef, off, stream, stream_words, g, blocks, huff);
+    else
+        jpeg_emit_kernel<HS, VS, false><<<grid, 256, 0, s>>>(coef, off, stream, stream_words, g, blocks, huff);
+}
+
+}  // namespace
+
+// sampling 2, optimize 0: the default file, in 8 launches.  Other samplings change the transform and the scan order only; optimize adds
+// the clearing of the counters (a memset), the histogram and the table stage in front of count: 10 launches, whatever n.
+int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out,
+                          size_t out_stride, int32_t* lengths, void* workspace, hipStream_t s) {
     const char* bad = check_shape(n, h, w, c, quality);
-    if (bad) { set_error("jpeg_encode_u8: %s (n %d, %d x %d x %d, quality %d)", bad, n, h, w, c, quality); return -1; }
-    const Plan p = make_plan(n, h, w, c);
-    if (p.out_stride > (size_t)INT32_MAX) { set_error("jpeg_encode_u8: %d x %d x %d: a worst-case file beyond 2^31 - 1 bytes", h, w, c); return -1; }
-    if (out_stride < p.out_stride) { set_error("jpeg_encode_u8: out_stride %zu below the %zu of adain_jpeg_encode_u8_bytes", out_stride, p.out_stride); return -1; }
-    if ((uintptr_t)workspace % 8 || (uintptr_t)lengths % 4) { set_error("jpeg_encode_u8: the workspace must be 8-byte and lengths 4-byte aligned"); return -1; }
+    if (!bad) bad = check_options(sampling, optimize);
+    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, quality %d, sampling %d, optimize %d)", who, bad, n, h, w, c, quality, sampling, optimize); return -1; }
+    const Plan p = make_plan(n, h, w, c, sampling, optimize);
+    if (p.out_stride > (size_t)INT32_MAX) { set_error("%s: %d x %d x %d: a worst-case file beyond 2^31 - 1 bytes", who, h, w, c); return -1; }
+    if (out_stride < p.out_stride) { set_error("%s: out_stride %zu below the %zu of the size query", who, out_stride, p.out_stride); return -1; }
+    if ((uintptr_t)workspace % 8 || (uintptr_t)lengths % 4) { set_error("%s: the workspace must be 8-byte and lengths 4-byte aligned", who); return -1; }
     char* ws = (char*)workspace;
     int16_t* coef = (int16_t*)(ws + p.o_coef);
     uint32_t* bits = (uint32_t*)(ws + p.o_bits);
@@ -1816,22 +2100,43 @@ int launch_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int qu
     uint32_t* ffcnt = (uint32_t*)(ws + p.o_ffcnt);
     uint32_t* ffoff = (uint32_t*)(ws + p.o_ffoff);
     uint32_t* fftotal = (uint32_t*)(ws + p.o_fftotal);
+    unsigned long long* hist = optimize ? (unsigned long long*)(ws + p.o_hist) : nullptr;
+    HuffSlot* huff = optimize ? (HuffSlot*)(ws + p.o_huff) : nullptr;
     const Geometry g{c, p.mw, p.bw, p.bh, p.nblk};
     const size_t blocks = (size_t)n * p.nblk;
     // gridDim.y and .z are limited to 65535: h, w <= 65535 keep the block rows below that; the frames ride in z
-    if (n > 65535 || (blocks + 3) / 4 > 0x7fffffffull) { set_error("jpeg_encode_u8: batch of %d frames too large for one call", n); return -1; }
-    if (c == 3)
-        jpeg_transform_rgb_kernel<<<dim3((p.mw + MCUS_PER_WG - 1) / MCUS_PER_WG, p.mh, n), MCUS_PER_WG * 48, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.bh, p.nblk);
-    else
+    if (n > 65535 || (blocks + 3) / 4 > 0x7fffffffull) { set_error("%s: batch of %d frames too large for one call", who, n); return -1; }
+    if (c != 3)
         jpeg_transform_grey_kernel<<<dim3((p.bw + GREY_PER_WG - 1) / GREY_PER_WG, p.bh, n), GREY_PER_WG * 8, 0, s>>>(src, h, w, quality, coef, p.bw, p.nblk);
-    jpeg_count_kernel<<<(unsigned)((blocks + 3) / 4), 256, 0, s>>>(coef, bits, g, blocks);
+    else if (p.vs == 2)
+        jpeg_transform_rgb_kernel<<<dim3((p.mw + MCUS_PER_WG - 1) / MCUS_PER_WG, p.mh, n), MCUS_PER_WG * 48, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.bh, p.nblk);
+    else if (p.hs == 2)
+        jpeg_transform_rgb_h_kernel<2><<<dim3((p.mw + 7) / 8, p.mh, n), 256, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.nblk);
+    else
+        jpeg_transform_rgb_h_kernel<1><<<dim3((p.mw + 15) / 16, p.mh, n), 384, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.nblk);
+    auto entropy = [&](int stage) {
+        const unsigned grid = (unsigned)((blocks + 3) / 4);
+        if (p.vs == 2) launch_entropy_stage<2, 2>(stage, optimize, grid, n, coef, bits, off, stream, p.stream_words, g, blocks, hist, huff, s);
+        else if (p.hs == 2) launch_entropy_stage<2, 1>(stage, optimize, grid, n, coef, bits, off, stream, p.stream_words, g, blocks, hist, huff, s);
+        else launch_entropy_stage<1, 1>(stage, optimize, grid, n, coef, bits, off, stream, p.stream_words, g, blocks, hist, huff, s);
+    };
+    if (optimize) {
+        if (hipMemsetAsync(hist, 0, (size_t)n * SLOTS * 256 * sizeof(uint64_t), s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return -1; }
+        entropy(0);
+        jpeg_table_kernel<<<dim3(c == 3 ? 4 : 2, n), TABLE_THREADS, 0, s>>>(hist, huff);
+    }
+    entropy(1);
     jpeg_scan_kernel<uint32_t, uint64_t><<<n, SCAN_THREADS, 0, s>>>(bits, off, total, p.nblk, p.nblk, nullptr);
     jpeg_zero_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total);
-    jpeg_emit_kernel<<<(unsigned)((blocks + 3) / 4), 256, 0, s>>>(coef, off, stream, p.stream_words, g, blocks);
+    entropy(2);
     jpeg_ffcount_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffcnt, p.chunks);
     jpeg_scan_kernel<uint32_t, uint32_t><<<n, SCAN_THREADS, 0, s>>>(ffcnt, ffoff, fftotal, p.chunks, 0, total);
-    jpeg_scatter_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffoff, fftotal, p.chunks, h, w, c == 3, quality, out, out_stride, lengths);
-    return check_launch("jpeg_encode_u8");
+    const int luma = c == 3 ? p.hs << 4 | p.vs : 0x11;
+    if (optimize)
+        jpeg_scatter_kernel<true><<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffoff, fftotal, p.chunks, h, w, c == 3, quality, luma, huff, out, out_stride, lengths);
+    else
+        jpeg_scatter_kernel<false><<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffoff, fftotal, p.chunks, h, w, c == 3, quality, luma, huff, out, out_stride, lengths);
+    return check_launch(who);
 }
 
 int jpeg_roundtrip_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {

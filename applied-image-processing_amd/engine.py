@@ -207,10 +207,11 @@ class AdaINEngine:
         """One step of the video recurrence: blend(cur, warp(prev, flow), alpha) on uint8 HWC frames (video/utils.py:89-105, :223-229)."""
         return rt.warp_blend_u8(cur, prev, flow, alpha)
 
-    def jpeg_encode_u8(self, frames_u8, quality=rt.JPEG_DEFAULT_QUALITY):
-        """The files ``PIL.Image.fromarray(frame).save(f, format="JPEG", quality=quality)`` writes for uint8 frames [n,h,w,3|1] on the
-        device, encoded there (adain_jpeg_encode_u8) -> a list of n ``bytes``; only the files cross to the host."""
-        return rt.jpeg_files(*rt.jpeg_encode_u8(frames_u8, quality))
+    def jpeg_encode_u8(self, frames_u8, quality=rt.JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
+        """The files ``PIL.Image.fromarray(frame).save(f, format="JPEG", quality=quality, subsampling=subsampling, optimize=optimize)``
+        writes for uint8 frames [n,h,w,3|1] on the device, encoded there (adain_jpeg_encode_u8 at the defaults, else
+        adain_jpeg_encode_opt_u8; ``runtime.jpeg_encode_u8``) -> a list of n ``bytes``; only the files cross to the host."""
+        return rt.jpeg_files(*rt.jpeg_encode_u8(frames_u8, quality, subsampling, optimize))
 
     def jpeg_decode_u8(self, files, chunk_bits=0, mode=None, report=None, restart=False, progressive=False):
         """The bytes of image files (a list, or one ``bytes``) -> uint8 tensors on the engine's device, the pixels Pillow's ``Image.open``
@@ -239,13 +240,15 @@ class AdaINEngine:
 
 
 def precompute_guides(engine, views, names, output_dir, masks=None, content_size=512, crop=False, alpha=0.5,
-                      depth_maps=None, depth_offset=0.5, depth_prominence=20, save_ext=".jpg", sub_batch=8, *, preserve_color=False):
+                      depth_maps=None, depth_offset=0.5, depth_prominence=20, save_ext=".jpg", sub_batch=8, *, preserve_color=False,
+                      jpeg_options=None):
     """Batched counterpart of the guide-image loop of the reference's Style_3DGS/train.py:86-115: every view
     is resized like ``adain_inference(content_size=...)`` does (test.py:190-200), stylised against the engine's
     current style, composited with its mask (``gt_image_np > 0``, train.py:97) and written to
     ``<output_dir>/<name><save_ext>`` — the same file naming, so the guide loss (train.py:208-221) reads it back
     unchanged.  ``views`` are PIL images (or paths); same-sized views are processed ``sub_batch`` at a time.
-    ``preserve_color``: every view is styled with ``coral(style, view)`` (``engine.set_style_image`` first).  Returns {name: Path}."""
+    ``preserve_color``: every view is styled with ``coral(style, view)`` (``engine.set_style_image`` first).  ``jpeg_options``
+    (``runtime.JpegOptions``): how .jpg / .jpeg guides are saved; default: ``AdaIN.test``'s setting.  Returns {name: Path}."""
     from pathlib import Path
 
     import numpy as np
@@ -281,7 +284,7 @@ def precompute_guides(engine, views, names, output_dir, masks=None, content_size
                 m = m if isinstance(m, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(m))
                 img = engine.composite(content[k - i:k - i + 1], img, m.float().unsqueeze(0))
             p = out_dir / f"{names[k]}{save_ext}"
-            save_image(img, str(p))
+            save_image(img, str(p), jpeg_options=jpeg_options)
             paths[names[k]] = p
         i = j
     return paths

@@ -34,6 +34,7 @@ import torch
 import torch.distributed as dist
 
 from . import sharding as sh
+from .runtime import JpegOptions
 
 
 def style_schedule(n_frames, n_styles):
@@ -455,15 +456,18 @@ class HostCopier:
 class FileSink:
     """Writes finished uint8 frames to image files off the compute path: the device -> host copy of a sub-batch runs on its own
     stream into a pinned buffer, a worker thread waits for it and encodes / saves the files (PIL), so the next sub-batch's
-    kernels are already running.  ``close()`` waits for every file and re-raises the first error.  ``jpeg_on_device`` (default off):
+    kernels are already running.  ``close()`` waits for every file and re-raises the first error.  ``jpeg_options`` (``JpegOptions``, a
+    (quality, subsampling, optimize) tuple or None for Pillow's defaults): how .jpg / .jpeg files are saved, on either route; files of
+    other extensions never see them.  ``jpeg_on_device`` (default off):
     a block whose paths all end in .jpg / .jpeg is encoded on the compute stream (adain_jpeg_encode_u8: the bytes PIL would write);
     the copy stream then brings over the lengths and, on a second stream of the sink's own, exactly that many bytes per frame, and the
     worker only writes them.  (The files do not ride on the lengths' stream: by the time a worker knows its lengths, the launching
     thread may have queued later blocks' length copies there, each waiting for later kernels.)"""
 
-    def __init__(self, device, workers=4, max_in_flight=None, jpeg_on_device=False):
+    def __init__(self, device, workers=4, max_in_flight=None, jpeg_on_device=False, jpeg_options=None):
         self.copier = HostCopier(device)
         self.jpeg_on_device = bool(jpeg_on_device)
+        self.jpeg_options = JpegOptions.of(jpeg_options)
         self.file_stream = torch.cuda.Stream(self.copier.device) if self.jpeg_on_device and self.copier.cuda else None
         self.file_bytes = 0                # bytes of encoded files the workers copied (under spare_lock)
         self.pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="adain-file-sink")
@@ -488,11 +492,10 @@ class FileSink:
                 return idle.pop()
         return torch.empty(shape, dtype=torch.uint8, pin_memory=True)
 
-    @staticmethod
-    def _save(arr, path):
+    def _save(self, arr, path):
         from PIL import Image
 
-        Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr).save(str(path))
+        self.jpeg_options.save(Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr), path)
 
     def _encodes(self, u8_block, paths):
         return (self.jpeg_on_device and self.copier.cuda and u8_block.is_cuda and u8_block.dtype == torch.uint8 and u8_block.dim() == 4
@@ -501,9 +504,7 @@ class FileSink:
     def _write_encoded(self, u8_block, paths):
         """The device-encode form of ``write``: the encode on the current stream, the lengths behind it on the copy stream; the worker
         waits for them, copies each frame's ``lengths[i]`` bytes into one pinned buffer on the copy stream and writes the files."""
-        from . import runtime as rt
-
-        files, lengths = rt.jpeg_encode_u8(u8_block)
+        files, lengths = self.jpeg_options.encode(u8_block)
         k = len(paths)
         lengths_host = torch.empty((k,), dtype=torch.int32, pin_memory=True)
         have_lengths = self.copier.copy(lengths_host, lengths)
@@ -941,7 +942,8 @@ def video_style_transfer_sharded(engine, frames, styles, *, flows=None, target_r
 
 def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=None, content_size=512, crop=False, alpha=0.5,
                               depth_maps=None, depth_offset=0.5, depth_prominence=20, save_ext=".jpg", sub_batch=None, group=None,
-                              dst=0, write="dst", require_transport=None, writers=4, jpeg_on_device=False, preserve_color=False):
+                              dst=0, write="dst", require_transport=None, writers=4, jpeg_on_device=False, preserve_color=False,
+                              jpeg_options=None):
     """The guide-image precompute of the reference's Style_3DGS/train.py:86-115 over all training views, sharded: every view
     is resized as ``adain_inference(content_size=...)`` resizes it (test.py:190-200), stylised, composited with its mask
     (``gt_image_np > 0``, train.py:97) and saved as ``<output_dir>/<name><save_ext>`` — the reference's naming, so the guide
@@ -950,7 +952,8 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
     finished — nothing is gathered and the views may have any mix of sizes.  The views are decoded / resized on a worker
     thread ahead of the kernels and travel to the device as uint8; the files are encoded and written by ``writers`` threads
     behind them.  ``jpeg_on_device``: .jpg / .jpeg guides are encoded on the device and only the files cross to the host (FileSink;
-    the same bytes).  ``preserve_color``: every view is styled with ``coral(style, view)`` (``stylize_frames_sharded``).  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
+    the same bytes).  ``jpeg_options`` (``JpegOptions``): quality, subsampling and optimize of .jpg / .jpeg guides, on either route;
+    default: Pillow's default save.  ``preserve_color``: every view is styled with ``coral(style, view)`` (``stylize_frames_sharded``).  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
     from PIL import Image
 
     from .AdaIN.test import device_transform_u8, test_transform_u8
@@ -981,7 +984,7 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
     on_gpu = torch.device(engine.device).type == "cuda"
     names = list(names)
     paths = {nm: out_dir / f"{nm}{save_ext}" for nm in names}
-    sink = FileSink(engine.device, workers=writers, jpeg_on_device=jpeg_on_device)
+    sink = FileSink(engine.device, workers=writers, jpeg_on_device=jpeg_on_device, jpeg_options=jpeg_options)
     err = None
     info = {}
     try:

@@ -246,12 +246,20 @@ def combine_localized_device(content_np, stylized_np, background_mask, device=No
 
 
 def run_localized_style_transfer(content_img_path, style_img_path, output_path="../output", file_name="test", use_depth=False,
-                                 depth_offset=0.5, depth_prominence=20, background_mask=None, *, colour_on_device=False, **adain_kwargs):
+                                 depth_offset=0.5, depth_prominence=20, background_mask=None, *, colour_on_device=False, jpeg_on_device=False,
+                                 jpeg_options=None, **adain_kwargs):
     """Same parameters and return value (the saved file's path, a str) as the reference (:191-245) plus ``background_mask``
     ([1,H,W] uint8) to bypass the mask provider; extra keyword arguments go to ``adain_inference`` (checkpoint paths,
     ``depth_map=`` ...).  ``colour_on_device`` (keyword only, default off): the colour transfer and the composite run on the device
-    (``combine_localized_device``) instead of in numpy; file names, the JPEG save and the return value do not change."""
+    (``combine_localized_device``) instead of in numpy; file names, the JPEG save and the return value do not change.
+    ``jpeg_options`` (``runtime.JpegOptions`` or a (quality, subsampling, optimize) tuple; default: Pillow's default save): how the final
+    composite's .jpg is saved.  ``jpeg_on_device`` (default off): that file comes from the device encoder - the same bytes; with
+    ``colour_on_device`` the composite never leaves the device before it is a file.  (The intermediate stylised file is
+    ``adain_inference``'s: ``AdaIN.test.set_device_jpeg`` / ``set_jpeg_save_options``.)"""
+    from . import runtime as rt
     from .AdaIN.test import adain_inference
+
+    options = rt.JpegOptions.of(jpeg_options)
 
     content_img = Image.open(content_img_path).convert("RGB")
     content_np = np.array(content_img)
@@ -262,8 +270,18 @@ def run_localized_style_transfer(content_img_path, style_img_path, output_path="
                                     output=output_path, file_name=file_name, use_depth=use_depth, depth_offset=depth_offset,
                                     depth_prominence=depth_prominence, alpha=1, **adain_kwargs)
     stylized_np = np.array(Image.open(stylized_path).convert("RGB"))
-    combined = (combine_localized_device if colour_on_device else combine_localized)(content_np, stylized_np, background_mask[0])
     Path(output_path).mkdir(exist_ok=True, parents=True)
     save_path = f"{output_path}/localized_style_transfer_result.jpg"
-    Image.fromarray(combined).save(save_path)
+    if jpeg_on_device:
+        dev = _device_of(None)
+        if colour_on_device:              # a device tensor in, a device tensor out
+            combined = combine_localized_device(_to_device(content_np, dev), stylized_np, background_mask[0], device=dev)
+        else:
+            combined = _to_device(combine_localized(content_np, stylized_np, background_mask[0]), dev)
+        data, = rt.jpeg_files(*options.encode(combined))
+        with open(save_path, "wb") as f:
+            f.write(data)
+        return save_path
+    combined = (combine_localized_device if colour_on_device else combine_localized)(content_np, stylized_np, background_mask[0])
+    options.save(Image.fromarray(combined), save_path)
     return save_path

@@ -8,7 +8,8 @@ It calls ``localized.run_localized_style_transfer`` (reference Style_3DGS/locali
 composite.  Extra flags make it usable offline (the reference downloads DeepLabV3 and MiDaS at run time): ``--mask_npy`` takes a
 precomputed background mask ([1,H,W] or [H,W], 1 = background), ``--depth_npy`` a proximity map, ``--vgg`` / ``--decoder`` the
 checkpoint paths, ``--colour_on_device`` moves the colour transfer and the composite to the GPU, ``--jpeg_on_device`` the JPEG encode of the intermediate
-stylised file (the same bytes; the final composite is still saved by PIL).  Without ``--mask_npy`` a provider must have been registered (``localized.set_mask_provider``).
+stylised file and of the final composite (the same bytes); ``--jpeg_quality``, ``--jpeg_subsampling``, ``--jpeg_optimize`` are Pillow's
+keywords for the final composite's file, on either route.  Without ``--mask_npy`` a provider must have been registered (``localized.set_mask_provider``).
 """
 import argparse
 
@@ -32,7 +33,10 @@ _EXTRA_FLAGS = (
     ("--vgg", dict(type=str, default="Style_3DGS/AdaIN/models/vgg_normalised.pth", help="encoder state_dict")),
     ("--decoder", dict(type=str, default="Style_3DGS/AdaIN/models/decoder.pth", help="decoder state_dict")),
     ("--colour_on_device", dict(action="store_true", help="run the foreground colour transfer and the composite on the GPU instead of in numpy")),
-    ("--jpeg_on_device", dict(action="store_true", help="encode the intermediate stylised JPEG on the GPU instead of in PIL (byte-identical file)")),
+    ("--jpeg_on_device", dict(action="store_true", help="encode the intermediate stylised JPEG and the final composite's on the GPU instead of in PIL (byte-identical files)")),
+    ("--jpeg_quality", dict(type=int, default=75, help="Pillow's quality of the final composite's JPEG, 1..100")),
+    ("--jpeg_subsampling", dict(type=str, default="4:2:0", choices=["4:4:4", "4:2:2", "4:2:0"], help="chroma subsampling of the final composite's JPEG")),
+    ("--jpeg_optimize", dict(action="store_true", help="give the final composite's JPEG its own optimal Huffman tables (Pillow's optimize=True)")),
 )
 
 
@@ -51,7 +55,9 @@ def main(argv=None):
     prev = set_device_jpeg(ns.jpeg_on_device)
     try:
         return run_localized_style_transfer(content_img_path=ns.content, style_img_path=ns.style, output_path=ns.output, file_name=ns.file_name,
-                                            use_depth=ns.use_depth, background_mask=mask, colour_on_device=ns.colour_on_device, **extra)
+                                            use_depth=ns.use_depth, background_mask=mask, colour_on_device=ns.colour_on_device,
+                                            jpeg_on_device=ns.jpeg_on_device, jpeg_options=(ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize),
+                                            **extra)
     finally:
         set_device_jpeg(prev)
 

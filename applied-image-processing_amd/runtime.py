@@ -99,6 +99,8 @@ SIGNATURES = {
                                       _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
+    "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_roundtrip_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_roundtrip_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_decode_u8_bytes": (_c_int, [_c_int] * 5 + [_c_size_t, _c_int, ctypes.POINTER(_c_size_t)]),
@@ -836,33 +838,138 @@ def _jpeg_frames(u8, what, quality):
     return x
 
 
-def jpeg_encode_sizes(n, h, w, c):
-    """(out_stride, workspace_bytes) of adain_jpeg_encode_u8_bytes: the largest file a frame of this shape can have and the scratch
-    of an n-frame call.  Host only.  AdainHipError for a refused shape."""
+JPEG_SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}          # Pillow's strings -> its numbers, which are the C ABI's `sampling`
+
+
+def jpeg_subsampling(subsampling, what="jpeg_encode_u8"):
+    """Pillow's ``subsampling`` keyword as the C ABI's number: 0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0".  Anything else (-1 and "keep"
+    included: they mean "whatever the source file had", and a frame has no source file) raises AdainHipError."""
+    if isinstance(subsampling, str) and subsampling in JPEG_SUBSAMPLING:
+        return JPEG_SUBSAMPLING[subsampling]
+    if isinstance(subsampling, bool) or not isinstance(subsampling, int) or not 0 <= subsampling <= 2:
+        raise AdainHipError(f"{what}: subsampling must be 0, 1, 2 or '4:4:4', '4:2:2', '4:2:0', got {subsampling!r}")
+    return subsampling
+
+
+def _jpeg_optimize(optimize, what):
+    if isinstance(optimize, int) and optimize in (0, 1):          # bool is an int
+        return int(optimize)
+    raise AdainHipError(f"{what}: optimize must be False or True, got {optimize!r}")
+
+
+def is_jpeg_path(path):
+    return str(path).lower().endswith((".jpg", ".jpeg"))
+
+
+class JpegOptions:
+    """How to save a JPEG: Pillow's ``quality`` (1..100, default 75), ``subsampling`` (0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0", default
+    4:2:0) and ``optimize`` (the file's own optimal Huffman tables, default off) - the keywords the device encoder covers.  The defaults
+    are Pillow's default save.  One value for both routes of a caller: ``encode`` is the device's (``jpeg_encode_u8``), ``save`` the
+    host's (``Image.save`` with the same keywords), and the files are the same.  An L image ignores ``subsampling`` on both routes: its
+    file is the one Pillow writes without the keyword.  What stays with Pillow alone: ``progressive=True``, ``qtables=``,
+    ``quality="keep"``, EXIF / ICC / comments / DPI, restart markers, CMYK.  AdainHipError for a value outside these."""
+    __slots__ = ("quality", "subsampling", "optimize")
+
+    def __init__(self, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
+        if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+            raise AdainHipError(f"JpegOptions: quality must be an int in 1..100, got {quality!r}")
+        object.__setattr__(self, "quality", quality)
+        object.__setattr__(self, "subsampling", jpeg_subsampling(subsampling, "JpegOptions"))
+        object.__setattr__(self, "optimize", bool(_jpeg_optimize(optimize, "JpegOptions")))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("JpegOptions is immutable")
+
+    @classmethod
+    def of(cls, value):
+        """None -> the defaults; a JpegOptions -> itself; a (quality, subsampling, optimize) tuple or a dict of keywords -> the value."""
+        if value is None:
+            return cls()
+        if isinstance(value, cls) or type(value).__name__ == cls.__name__:          # (a reloaded module's class is another object)
+            return value
+        if isinstance(value, dict):
+            return cls(**value)
+        if isinstance(value, (tuple, list)):
+            return cls(*value)
+        raise AdainHipError(f"jpeg_options: expected JpegOptions, a (quality, subsampling, optimize) tuple, a dict or None, got {value!r}")
+
+    def _key(self):
+        return (self.quality, self.subsampling, self.optimize)
+
+    def __eq__(self, other):
+        return type(other).__name__ == type(self).__name__ and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"JpegOptions(quality={self.quality}, subsampling={self.subsampling}, optimize={self.optimize})"
+
+    @property
+    def is_default(self):
+        return self._key() == (JPEG_DEFAULT_QUALITY, 2, False)
+
+    def save_kwargs(self, mode="RGB"):
+        """The keywords of ``Image.save`` for an image of ``mode``: none at the defaults (today's call), no ``subsampling`` for L."""
+        if self.is_default:
+            return {}
+        kw = {"quality": self.quality, "optimize": self.optimize}
+        if mode != "L":
+            kw["subsampling"] = self.subsampling
+        return kw
+
+    def save(self, img, path):
+        """The host route: ``img.save(path)``, with these keywords for a .jpg / .jpeg path only - other extensions never see them.
+        Pillow sizes its encoder buffer for ``optimize`` at width x height bytes and fails ("broken data stream") on a frame whose file
+        is larger, which a noisy 4:4:4 frame is: ImageFile.MAXBLOCK, Pillow's knob for it, is raised to the worst case first."""
+        kw = self.save_kwargs(img.mode) if is_jpeg_path(path) else {}
+        if kw.get("optimize"):
+            from PIL import ImageFile
+
+            ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 4 * img.size[0] * img.size[1] * len(img.getbands()) + 4096)
+        img.save(str(path), **kw)
+
+    def encode(self, u8):
+        """The device route: ``jpeg_encode_u8`` with these options -> (files, lengths) on the device."""
+        return jpeg_encode_u8(u8, self.quality, self.subsampling, self.optimize)
+
+
+def jpeg_encode_sizes(n, h, w, c, subsampling=2, optimize=False):
+    """(out_stride, workspace_bytes) of adain_jpeg_encode_opt_u8_bytes (at the defaults: adain_jpeg_encode_u8_bytes' values): the
+    largest file a frame of this shape can have and the scratch of an n-frame call.  Host only.  AdainHipError for a refused shape."""
     stride, ws = _c_size_t(), _c_size_t()
-    rc = lib().adain_jpeg_encode_u8_bytes(int(n), int(h), int(w), int(c), ctypes.byref(stride), ctypes.byref(ws))
+    rc = lib().adain_jpeg_encode_opt_u8_bytes(int(n), int(h), int(w), int(c), jpeg_subsampling(subsampling, "jpeg_encode_sizes"),
+                                              _jpeg_optimize(optimize, "jpeg_encode_sizes"), ctypes.byref(stride), ctypes.byref(ws))
     if rc != 0:
-        raise _failure("adain_jpeg_encode_u8_bytes", rc)
+        raise _failure("adain_jpeg_encode_opt_u8_bytes", rc)
     return stride.value, ws.value
 
 
-def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY):
+def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
     """Frames uint8 [n,h,w,c] (c = 3: RGB, 1: L; or one frame [h,w,c] / [h,w]) -> (files uint8 [n, stride], lengths int32 [n]), both on the
     device: row i starts with frame i's JPEG file, ``lengths[i]`` bytes, byte for byte what ``PIL.Image.fromarray(frame).save(f,
-    format="JPEG", quality=quality)`` writes; the rest of the row is not written.  Nothing is copied to the host and nothing waits."""
+    format="JPEG", quality=quality, subsampling=subsampling, optimize=optimize)`` writes; the rest of the row is not written.
+    ``subsampling``: 0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0" (the default, Pillow's own); L frames ignore it and get the file Pillow writes
+    without the keyword.  ``optimize``: the frame's own optimal Huffman tables.  The defaults give Pillow's default file
+    (adain_jpeg_encode_u8).  Nothing is copied to the host and nothing waits."""
+    sampling, optimize = jpeg_subsampling(subsampling), _jpeg_optimize(optimize, "jpeg_encode_u8")
     x = _jpeg_frames(u8, "jpeg_encode_u8", quality)
     n, h, w, c = x.shape
     stride = 0
 
     def sizes():                # one query answers both: the file stride is kept for the output below
         nonlocal stride
-        stride, nbytes = jpeg_encode_sizes(n, h, w, c)
+        stride, nbytes = jpeg_encode_sizes(n, h, w, c, sampling, optimize)
         return nbytes
 
     with scratch(x.device, "jpeg", sizes) as ws:
         out = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
         lengths = torch.empty((n,), dtype=torch.int32, device=x.device)
-        _launch("adain_jpeg_encode_u8", x.data_ptr(), n, h, w, c, quality, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
+        if (sampling, optimize) == (2, 0):
+            _launch("adain_jpeg_encode_u8", x.data_ptr(), n, h, w, c, quality, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
+        else:
+            _launch("adain_jpeg_encode_opt_u8", x.data_ptr(), n, h, w, c, quality, sampling, optimize, out.data_ptr(), stride, lengths.data_ptr(),
+                    ws.data_ptr(), ws.numel())
     return out, lengths
 
 

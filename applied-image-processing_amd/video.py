@@ -160,19 +160,20 @@ def _jpeg_roundtrip(u8):
 
 def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
          vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device=False, preserve_color=False, crossfade_frames=0,
-         jpeg_decode_on_device=False, jpeg_decode_progressive=False):
+         jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None):
     global _jpeg_decode_on_device, _jpeg_decode_progressive
     prev, _jpeg_decode_on_device = _jpeg_decode_on_device, bool(jpeg_decode_on_device)
     prev_progressive, _jpeg_decode_progressive = _jpeg_decode_progressive, bool(jpeg_decode_on_device and jpeg_decode_progressive)
     try:
         return _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-                         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color, crossfade_frames)
+                         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color, crossfade_frames,
+                         jobs.JpegOptions.of(jpeg_options))
     finally:
         _jpeg_decode_on_device, _jpeg_decode_progressive = prev, prev_progressive
 
 
 def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-              vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color, crossfade_frames):
+              vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color, crossfade_frames, jpeg_options):
     from . import sharding as sh
     from .engine import AdaINEngine
 
@@ -253,7 +254,7 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
     if rank == 0:
         # the frame-to-frame recurrence (video/utils.py:355-368) on the gathered frames; every frame is written by a worker
         # thread behind an asynchronous device -> host copy while the next frame's warp / blend is already running
-        sink = jobs.FileSink(engine.device, jpeg_on_device=jpeg_on_device)
+        sink = jobs.FileSink(engine.device, jpeg_on_device=jpeg_on_device, jpeg_options=jpeg_options)
         try:
             n, h, w, _ = frames_u8.shape
             prev = None
@@ -286,7 +287,7 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
                              cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                              vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth", decoder_str="Style_3DGS/AdaIN/models/decoder.pth",
                              depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False, preserve_color=False,
-                             jpeg_decode_on_device=False, jpeg_decode_progressive=False):
+                             jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None):
     """One style for the whole clip (video/utils.py:244-295); keyword-only extras: a ready ``engine``, checkpoint paths,
     precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``jpeg_on_device`` (.jpg / .jpeg frames are
     encoded on the device: the same files, jobs.FileSink; with ``intermediate_jpeg`` and the engine on a GPU the intermediate round trip
@@ -294,10 +295,13 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
     ``coral(style, frame)``, adain_inference's colour preservation, on the device), ``jpeg_decode_on_device`` (baseline .jpg / .jpeg
     frames are decoded on the device, for the stylisation and for the package's own flow providers: ``rt.jpeg_decode_rgb_file``, the
     pixels PIL decodes; any other file, and the sharded feeder of jobs.py, keep PIL), ``jpeg_decode_progressive`` (acts with
-    ``jpeg_decode_on_device=True``: progressive frames are decoded on the device too; without it they keep PIL as before)."""
+    ``jpeg_decode_on_device=True``: progressive frames are decoded on the device too; without it they keep PIL as before),
+    ``jpeg_options`` (``jobs.JpegOptions``, or a (quality, subsampling, optimize) tuple: how the .jpg / .jpeg OUTPUT frames are saved, by
+    PIL or with ``jpeg_on_device`` by the device encoder, the same files; default: Pillow's default save.  The ``intermediate_jpeg``
+    round trip stays the reference's default save, quality 75 and 4:2:0, whatever the options)."""
     return _run(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
                 engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color,
-                jpeg_decode_on_device=jpeg_decode_on_device, jpeg_decode_progressive=jpeg_decode_progressive)
+                jpeg_decode_on_device=jpeg_decode_on_device, jpeg_decode_progressive=jpeg_decode_progressive, jpeg_options=jpeg_options)
 
 
 def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
@@ -305,13 +309,14 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
                                    vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth",
                                    decoder_str="Style_3DGS/AdaIN/models/decoder.pth", depth_maps=None, intermediate_jpeg=False,
                                    group=None, jpeg_on_device=False, preserve_color=False, crossfade_frames=0, jpeg_decode_on_device=False,
-                                   jpeg_decode_progressive=False):
+                                   jpeg_decode_progressive=False, jpeg_options=None):
     """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372).
     ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics.
     ``jpeg_on_device``: as in ``apply_style_transfer_ada``, the output files and, with ``intermediate_jpeg``, the intermediate round trip.
     ``crossfade_frames`` (0, the default: the hard cuts of the reference): the styles cross-fade in feature space over that many
     frames centred on each switch (``jobs.style_crossfade``, style interpolation on the device; at most 16 styles, and not with
-    ``preserve_color``).  ``jpeg_decode_on_device``, ``jpeg_decode_progressive``: as in ``apply_style_transfer_ada``."""
+    ``preserve_color``).  ``jpeg_decode_on_device``, ``jpeg_decode_progressive``: as in ``apply_style_transfer_ada``.
+    ``jpeg_options``: as in ``apply_style_transfer_ada`` - the output files only, never the ``intermediate_jpeg`` round trip."""
     style_images = sorted(os.listdir(style_dir))
     if len(style_images) == 0:
         raise ValueError("No style images found in the style directory.")
@@ -319,4 +324,5 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
         raise ValueError("crossfade_frames mixes the styles of a frame; preserve_color is not supported with it")
     return _run(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
                 cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color,
-                int(crossfade_frames), jpeg_decode_on_device=jpeg_decode_on_device, jpeg_decode_progressive=jpeg_decode_progressive)
+                int(crossfade_frames), jpeg_decode_on_device=jpeg_decode_on_device, jpeg_decode_progressive=jpeg_decode_progressive,
+                jpeg_options=jpeg_options)

@@ -463,6 +463,37 @@ ADAIN_API int adain_jpeg_encode_u8_bytes(int n, int h, int w, int c, size_t* out
 ADAIN_API int adain_jpeg_encode_u8(const uint8_t* src_u8, int n, int h, int w, int c, int quality, uint8_t* out, size_t out_stride,
                                    int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
+/* adain_jpeg_encode_u8 with Pillow's `subsampling` and `optimize` keywords: frame i's file is byte for byte what
+ * Image.fromarray(frame).save(f, format="JPEG", quality=quality, subsampling=sampling, optimize=optimize) writes (established against
+ * Pillow 12.2.0 built with libjpeg-turbo; the rules are listed in csrc/jpeg.hip and restated in NumPy in tests/jpeg_options_ref.py).
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * sampling: the decoder's encoding - 0: 4:4:4 (8 x 8 MCUs, blocks Y Cb Cr), 1: 4:2:2 (16 x 8 MCUs, Y0 Y1 Cb Cr), 2: 4:2:0 (16 x 16
+ *   MCUs, Y00 Y01 Y10 Y11 Cb Cr); SOF0's luma sampling byte is 0x11 / 0x21 / 0x22.  For c = 1 any sampling in 0..2 is accepted and
+ *   ignored: the file is the one Pillow writes for an L image without the keyword (given the keyword, Pillow would put the factor into
+ *   the grey component's SOF0 byte and change nothing else).
+ * optimize: 0 - the Annex K Huffman tables; 1 - libjpeg's two-pass optimize_coding: per frame and table (DC0, AC0 and for RGB DC1, AC1)
+ *   the symbols of the scan are counted (64-bit counters), the optimal length-limited code is built on the device, and the file's DHT
+ *   segments hold that code with only the symbols that occur, so the header's length varies per frame.
+ * (sampling 2, optimize 0) is adain_jpeg_encode_u8: the same bytes, sizes and launches.
+ * adain_jpeg_encode_opt_u8_bytes (host only): as adain_jpeg_encode_u8_bytes, an overflow is impossible, not detected.  A block codes its
+ *   DC difference in at most L + 11 bits and each of its 63 AC coefficients in at most L + 10 bits, where L bounds a code's length (the
+ *   value bits are as derived above: |difference| < 2^11, |AC| < 2^10; a ZRL or the EOB costs at most L bits and stands for at least
+ *   one coefficient that is then not coded).  optimize 0: Annex K's tables, 1660 bits as above.  optimize 1: no code of a JPEG Huffman
+ *   table is longer than 16 bits, whatever the counts, so (16 + 11) + 63 * (16 + 10) = 1665 bits.  B blocks in the scan - 3 per 8 x 8
+ *   MCU for 4:4:4, 4 per 16 x 8 MCU for 4:2:2, 6 per 16 x 16 MCU for 4:2:0, dummy luma blocks included; ceil(h/8) * ceil(w/8) for L -
+ *   give E = ceil(bits B / 8) bytes, byte stuffing at most doubles them; an optimal table lists at most the symbols Annex K's does (12
+ *   DC categories; 160 run/size pairs, ZRL and EOB), so the header is at most the standard one (623 bytes RGB, 328 L):
+ *   out_stride = header + 2 E + 2.  *workspace_bytes = adain_jpeg_encode_u8_bytes' arrays for that B and, for optimize 1, the symbol
+ *   counts and code tables of n frames.  Either output may be NULL.
+ * Refused with ADAIN_EINVAL before anything is launched: everything adain_jpeg_encode_u8 refuses, sampling outside 0..2, optimize
+ * outside 0..1, and an out_stride or workspace_bytes below THIS query's.  Bytes of `out` behind a file are not written.  Nothing is
+ * copied to the host and nothing waits; 8 kernel launches per call for optimize 0 and 10 and one memset for optimize 1, whatever n. */
+ADAIN_API int adain_jpeg_encode_opt_u8_bytes(int n, int h, int w, int c, int sampling, int optimize, size_t* out_stride,
+                                             size_t* workspace_bytes);
+ADAIN_API int adain_jpeg_encode_opt_u8(const uint8_t* src_u8, int n, int h, int w, int c, int quality, int sampling, int optimize,
+                                       uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes,
+                                       adain_stream_t stream);
+
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
  * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)

@@ -5,7 +5,8 @@ after warm-up:
   device_ms  wall clock from the device uint8 frame to host ``bytes``: the call, the length read, the copy of exactly that many bytes
   pillow_ms  Image.fromarray(frame).save(BytesIO, format="JPEG") of the same frame on this machine's CPU, one thread
 and whether the two files are the same bytes.  ``passes_1080p``: device_ms sits below pillow_ms by more than the two interquartile
-ranges combined.  With --job, a 64-view 1200 x 1600 precompute_guides_sharded into a temporary directory with jpeg_on_device off and on:
+ranges combined.  ``options``: the same three figures at 1080 x 1920 per option set of OPTION_SETS (quality, subsampling, optimize), under a
+key of its own, Pillow given the same keywords; ``faster_than_pillow`` there by the same rule.  With --job, a 64-view 1200 x 1600 precompute_guides_sharded into a temporary directory with jpeg_on_device off and on:
 wall time, the sink's wait and the bytes that crossed to the host.  Prints one JSON line and, with --out, writes it to a file.
 Usage: python tools/jpeg_bench.py [--reps 200] [--job] [--out profiles/jpeg_bench.json]"""
 import argparse
@@ -20,7 +21,7 @@ import time
 import numpy as np
 import PIL
 import torch
-from PIL import Image
+from PIL import Image, ImageFile
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
@@ -31,6 +32,7 @@ from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
 from applied_image_processing_amd.telemetry import GpuTelemetry  # noqa: E402
 
 SIZES = [(256, 456), (1080, 1920), (1200, 1600)]
+OPTION_SETS = {"q95_444_optimize": (95, "4:4:4", True), "q75_420_optimize": (75, "4:2:0", True), "q75_422": (75, "4:2:2", False)}
 
 
 def spread(times):
@@ -66,10 +68,30 @@ def event_ms(fn, reps, warmup):
     return spread(times)
 
 
-def pillow_bytes(a):
+def pillow_bytes(a, options=None):
     f = io.BytesIO()
-    Image.fromarray(a).save(f, format="JPEG")
+    if options is None:
+        Image.fromarray(a).save(f, format="JPEG")
+    else:
+        ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 4 * a.size)          # Pillow's optimize buffer is w * h bytes: too small for noise
+        Image.fromarray(a).save(f, format="JPEG", **options.save_kwargs())
     return f.getvalue()
+
+
+def compare(x, options, reps, tel=None, label=None):
+    """kernel_ms, device_ms, pillow_ms of one device frame x [1,h,w,3] under ``options`` (None: the default entry, no keywords)."""
+    encode = (lambda: rt.jpeg_encode_u8(x)) if options is None else (lambda: options.encode(x))
+    host = x[0].cpu().numpy()
+    t0 = time.perf_counter()
+    kernel = event_ms(encode, reps, 20)
+    if tel is not None:
+        tel.window(label, t0, time.perf_counter())
+    device = wall_ms(lambda: rt.jpeg_files(*encode()), reps, 5, True)
+    pillow = wall_ms(lambda: pillow_bytes(host, options), reps, 3, False)
+    data, = rt.jpeg_files(*encode())
+    return {"frame_bytes": int(x.numel()), "file_bytes": len(data), "same_bytes_as_pillow": data == pillow_bytes(host, options),
+            "kernel_ms": kernel, "device_ms": device, "pillow_ms": pillow, "pillow_over_device": round(pillow["median"] / device["median"], 2),
+            "faster_than_pillow": device["median"] + device["iqr"] + pillow["iqr"] < pillow["median"]}
 
 
 def guide_job(engine, on, views, style, sub_batch):
@@ -100,22 +122,17 @@ def main():
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     tel = GpuTelemetry(0).start()
     res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow": PIL.__version__, "sizes": {}}
+           "pillow": PIL.__version__, "sizes": {}, "options": {}}
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         frames = {"stylised": engine.stylize_u8(source, alpha=0.5).contiguous(),
                   "noise": torch.from_numpy(np.random.default_rng(0).integers(0, 256, (1, h, w, 3), dtype=np.uint8)).to(dev)}
         for kind, x in frames.items():
-            host = x[0].cpu().numpy()
-            t0 = time.perf_counter()
-            kernel = event_ms(lambda: rt.jpeg_encode_u8(x), reps, 20)
-            tel.window(f"kernel_{kind}_{h}x{w}", t0, time.perf_counter())
-            device = wall_ms(lambda: rt.jpeg_files(*rt.jpeg_encode_u8(x)), reps, 5, True)
-            pillow = wall_ms(lambda: pillow_bytes(host), reps, 3, False)
-            data, = rt.jpeg_files(*rt.jpeg_encode_u8(x))
-            res["sizes"][f"{kind}_{h}x{w}"] = {"frame_bytes": int(x.numel()), "file_bytes": len(data), "same_bytes_as_pillow": data == pillow_bytes(host),
-                                               "kernel_ms": kernel, "device_ms": device, "pillow_ms": pillow,
-                                               "pillow_over_device": round(pillow["median"] / device["median"], 2)}
+            res["sizes"][f"{kind}_{h}x{w}"] = compare(x, None, reps, tel, f"kernel_{kind}_{h}x{w}")
+            if (h, w) == (1080, 1920):
+                for name, o in OPTION_SETS.items():
+                    res["options"].setdefault(name, {"quality": o[0], "subsampling": o[1], "optimize": o[2]})[f"{kind}_{h}x{w}"] = compare(
+                        x, rt.JpegOptions(*o), reps)
     res["passes_1080p"] = all(v["device_ms"]["median"] + v["device_ms"]["iqr"] + v["pillow_ms"]["iqr"] < v["pillow_ms"]["median"]
                               for k, v in res["sizes"].items() if k.endswith("1080x1920"))
     if args.job:
