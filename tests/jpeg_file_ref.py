@@ -126,7 +126,10 @@ def unstuff(seg):
 
 
 class Stream:
+    trace = None             # an object whose symbol(kind, table id, symbol, code length, position, size, value bits) takes the write pass's walk
+
     def __init__(self, info, data):
+        self.dc_id, self.ac_id = list(info["dc"]), list(info["ac"])
         off, ln = info["seg"]
         self.bytes = unstuff(data[off:off + ln])
         self.nbits = 8 * len(self.bytes)
@@ -168,6 +171,8 @@ def decode_span(st, state, end, sink=None, block=0):
             begun += 1
             s = sym & 15
             v = st.peek(pos + ln, s) if s else 0
+            if sink and st.trace and 0 <= b < sink.nblk:
+                st.trace.symbol("DC", st.dc_id[comp], sym, ln, pos, s, v)
             pos += ln + s
             if sink:
                 sink(b, 0, v if s == 0 or v >= 1 << (s - 1) else v - (1 << s) + 1)
@@ -182,6 +187,8 @@ def decode_span(st, state, end, sink=None, block=0):
                     sink(b, -1, 0)
                 continue
             r, s = sym >> 4, sym & 15
+            if sink and st.trace and 0 <= b < sink.nblk:
+                st.trace.symbol("AC", st.ac_id[comp], sym, ln, pos, s, st.peek(pos + ln, s) if s else 0, zz)
             if s == 0:
                 pos += ln
                 zz = zz + 16 if r == 15 else 64

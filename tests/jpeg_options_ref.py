@@ -131,18 +131,41 @@ def optimal_table(freq):
     return bits[1:17], vals
 
 
-def header(h, w, c, quality, subsampling, dht):
-    """jpeg_ref.header with the luma sampling factors of the layout and the four (two for L) given (bits, vals) tables."""
+def dht_segments(dht, ids=(0x00, 0x10, 0x01, 0x11), one_segment=False):
+    """The DHT segment(s) of the (bits, vals) tables ``dht`` under the class / id bytes ``ids``: one segment each, or all in one."""
+    parts = [bytes([tc_th]) + bytes(bits) + bytes(vals) for tc_th, (bits, vals) in zip(ids, dht)]
+    if one_segment:
+        return J._segment(0xC4, b"".join(parts)) if parts else b""
+    return b"".join(J._segment(0xC4, p) for p in parts)
+
+
+def sos_segment(sel, ss=0, se=63, ah=0, al=0):
+    """The SOS segment of a scan of the components ``sel``: (component id, DC table << 4 | AC table) each."""
+    return J._segment(0xDA, bytes([len(sel)]) + b"".join(bytes(x) for x in sel) + bytes([ss, se, ah << 4 | al]))
+
+
+def header(h, w, c, quality, subsampling, dht, *, qtables=None, qsel=None, dht_ids=(0x00, 0x10, 0x01, 0x11), one_dht=False, sel=None, sof=0xC0, ri=0,
+           fill=False, sos=True):
+    """jpeg_ref.header with the luma sampling factors of the layout and the four (two for L) given (bits, vals) tables.  The keywords
+    write the headers other encoders write: ``qtables`` [(id, natural-order table)] in place of the quality's two, ``qsel`` the table
+    id per component, ``dht_ids`` the class / id byte of each table of ``dht`` (any number, an id may come twice: the later definition
+    holds), ``one_dht`` all of them in one segment, ``sel`` DC << 4 | AC per component, ``sof`` the frame marker, ``ri`` a DRI segment,
+    ``fill`` an FF fill byte in front of the frame header's marker, ``sos`` False: no SOS segment (a progressive file writes its own)."""
     out = b"\xff\xd8" + J._segment(0xE0, b"JFIF\0" + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
-    for i, t in enumerate([J.Q_LUMA, J.Q_CHROMA][:2 if c == 3 else 1]):
-        out += J._segment(0xDB, bytes([i]) + bytes(J.quant_table(t, quality)[J.ZIGZAG].astype(np.uint8).tolist()))
+    if qtables is None:
+        qtables = list(enumerate(J.quant_table(t, quality) for t in [J.Q_LUMA, J.Q_CHROMA][:2 if c == 3 else 1]))
+    for i, t in qtables:
+        out += J._segment(0xDB, bytes([i]) + bytes(np.asarray(t)[J.ZIGZAG].astype(np.uint8).tolist()))
     hs, vs = SUBSAMPLING[subsampling]
-    comps = [(1, hs << 4 | vs, 0), (2, 0x11, 1), (3, 0x11, 1)] if c == 3 else [(1, 0x11, 0)]
-    out += J._segment(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([len(comps)]) + b"".join(bytes(x) for x in comps))
-    for tc_th, (bits, vals) in zip([0x00, 0x10, 0x01, 0x11], dht):
-        out += J._segment(0xC4, bytes([tc_th]) + bytes(bits) + bytes(vals))
-    sel = [(1, 0x00), (2, 0x11), (3, 0x11)] if c == 3 else [(1, 0x00)]
-    return out + J._segment(0xDA, bytes([len(sel)]) + b"".join(bytes(x) for x in sel) + bytes([0, 63, 0]))
+    qsel = qsel or (0, 1, 1)
+    comps = [(1, hs << 4 | vs, qsel[0]), (2, 0x11, qsel[1]), (3, 0x11, qsel[2])] if c == 3 else [(1, 0x11, qsel[0])]
+    out += b"\xff" * bool(fill)
+    out += J._segment(sof, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([len(comps)]) + b"".join(bytes(x) for x in comps))
+    if ri:
+        out += J._segment(0xDD, ri.to_bytes(2, "big"))
+    out += dht_segments(dht, dht_ids, one_dht)
+    sel = sel or (0x00, 0x11, 0x11)
+    return out + sos_segment([(i + 1, sel[i]) for i in range(c)]) if sos else out
 
 
 def entropy_data(z, tbl, dht):

@@ -142,8 +142,10 @@ def parse(data):
 # ---- one scan --------------------------------------------------------------------------------------------------------------------------------
 class Scan:
     """A scan's stream, tables and block geometry."""
+    trace = None             # an object that takes the write pass's walk: symbol(), end_of_band(), step(), correction(), put(), run_block()
 
     def __init__(self, info, sc, data):
+        self.dc_id, self.ac_id = list(sc["dc"]), list(sc["ac"])
         off, ln = sc["seg"]
         self.bytes = unstuff(data[off:off + ln])
         self.nbits = 8 * len(self.bytes)
@@ -236,6 +238,8 @@ def span(S, state, end, mask=None, out=None, b=0):
             s = sym & 15
             value = extend(S.peek(pos + ln, s), s)
             nb += 1
+            if live and S.trace:
+                S.trace.symbol("DC", S.dc_id[S.comp_of[blk]], sym, ln, pos, s, S.peek(pos + ln, s))
             pos += ln + s
             if live:
                 out.coef[S.block(b), 0] = value
@@ -258,8 +262,12 @@ def span(S, state, end, mask=None, out=None, b=0):
             if k == S.ss:
                 nb += 1
             r, s = sym >> 4, sym & 15
+            if live and S.trace:
+                S.trace.symbol("AC", S.ac_id[S.comp], sym, ln, pos, s, S.peek(pos + ln, s), k)
             if s == 0 and r < 15:
                 run = (1 << r) + S.peek(pos + ln, r)
+                if live and S.trace:
+                    S.trace.end_of_band(1, r, S.peek(pos + ln, r), pos + ln, b + run - 1 == last)
                 pos += ln + r
                 nb += run - 1
                 if live:
@@ -281,6 +289,8 @@ def span(S, state, end, mask=None, out=None, b=0):
                     val = value << S.al
                     if k <= S.se and fits(val):
                         out.coef[S.block(b), k] = val
+                        if S.trace:
+                            S.trace.put(S.block(b), k, S.al, False)
                     out.err |= k > S.se or s > 10 or not fits(val)
                 k += 1
             if k > S.se:
@@ -296,6 +306,9 @@ def span(S, state, end, mask=None, out=None, b=0):
         m = mask[blk]
         bc = S.block(blk)
         ends = run > 0
+        T = S.trace if out is not None else None
+        if T and ends:
+            T.run_block(bool((m >> k) & ((1 << (S.se + 1 - k)) - 1)), pos >= end)
         if not ends:
             sym, ln = S.symbol(table, pos)
             if sym is None:
@@ -304,8 +317,12 @@ def span(S, state, end, mask=None, out=None, b=0):
                     out.err = True
                 continue
             r, s = sym >> 4, sym & 15
+            if T:
+                T.symbol("AC", S.ac_id[S.comp], sym, ln, pos, s, S.peek(pos + ln, s), k)
             if s == 0 and r < 15:
                 run = (1 << r) + S.peek(pos + ln, r)
+                if T:
+                    T.end_of_band(2, r, S.peek(pos + ln, r), pos + ln, blk + run == S.nblk)
                 pos += ln + r
                 ends = True
                 if out is not None:
@@ -313,6 +330,7 @@ def span(S, state, end, mask=None, out=None, b=0):
             else:
                 pos += ln
                 put = 0
+                stepped = 0
                 if s:
                     if out is not None and s != 1:
                         out.err = True
@@ -320,19 +338,26 @@ def span(S, state, end, mask=None, out=None, b=0):
                     pos += 1
                 while k <= S.se:
                     if m >> k & 1:
+                        if T:
+                            T.correction(S.peek(pos, 1), int(out.coef[bc, k]), S.al, bc, k)
                         if S.peek(pos, 1) and out is not None:
                             correct(out, bc, k, S.al)
                         pos += 1
+                        stepped += 1
                     else:
                         if r == 0:
                             break
                         r -= 1
                     k += 1
+                if T:
+                    T.step("run" if s else "zrl", sym >> 4, stepped)
                 if out is not None:
                     if k > S.se:
                         out.err = True
                     elif put:
                         out.coef[bc, k] = put
+                        if T:
+                            T.put(bc, k, S.al, True)
                 k += 1
                 if k > S.se:
                     blk, k = blk + 1, S.ss
@@ -341,6 +366,8 @@ def span(S, state, end, mask=None, out=None, b=0):
         if ends:
             while k <= S.se:
                 if m >> k & 1:
+                    if T:
+                        T.correction(S.peek(pos, 1), int(out.coef[bc, k]), S.al, bc, k)
                     if S.peek(pos, 1) and out is not None:
                         correct(out, bc, k, S.al)
                     pos += 1
@@ -357,7 +384,8 @@ def start(S, pos):
 
 
 def history(S, coef):
-    return [sum(1 << k for k in range(64) if coef[S.block(sb), k] != 0) for sb in range(S.nblk)]
+    nz = (coef[[S.block(sb) for sb in range(S.nblk)]] != 0).astype(np.uint64)
+    return (nz << np.arange(64, dtype=np.uint64)).sum(axis=1, dtype=np.uint64).tolist()
 
 
 def dc_refine(S, out):
