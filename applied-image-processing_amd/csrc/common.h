@@ -183,13 +183,14 @@ int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int
 // the pixels Pillow decodes from that file, without the file (the rules: top of jpeg.hip, tests/jpeg_decode_ref.py)
 int jpeg_roundtrip_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
 int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, hipStream_t s);
-// a baseline file's entropy-coded segment -> the pixels Pillow decodes from the file (the rules: jpeg.hip, tests/jpeg_file_ref.py)
+// jpeg_decode.hip: a baseline file's entropy-coded segment -> the pixels Pillow decodes from the file (the rules: top of jpeg_decode.hip,
+// tests/jpeg_file_ref.py)
 // restart_interval: MCUs per restart interval, 0 for a file without one (tests/jpeg_restart_ref.py)
 int jpeg_decode_bytes(int n, int h, int w, int c, int sampling, int restart_interval, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes);
 int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, int restart_interval,
                           const uint64_t* seg_offsets, const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace, size_t workspace_bytes,
                           int chunk_bits, hipStream_t s);
-// the scans of a progressive (SOF2) file -> the same pixels (the rules: jpeg.hip, tests/jpeg_progressive_ref.py); scans: int32 [nscans][8] =
+// the scans of a progressive (SOF2) file -> the same pixels (the rules: jpeg_decode.hip, tests/jpeg_progressive_ref.py); scans: int32 [nscans][8] =
 // components, their frame indices (3), Ss, Se, Ah, Al; seg_offsets, seg_lengths and blobs are [n][nscans]
 int jpeg_decode_progressive_bytes(int n, int h, int w, int c, int sampling, int nscans, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes);
 int launch_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c, int sampling, int nscans,

@@ -1,4 +1,4 @@
-"""Reading a baseline JPEG file on the host for the device decoder (csrc/jpeg.hip, adain_jpeg_decode_u8 / adain_jpeg_decode_restart_u8):
+"""Reading a baseline JPEG file on the host for the device decoder (csrc/jpeg_decode.hip, adain_jpeg_decode_u8 / adain_jpeg_decode_restart_u8):
 a walk over the file's markers that returns a description of the file and packs its tables into one small blob, or raises
 ``UnsupportedJpeg`` with the reason in words.
 
@@ -22,7 +22,7 @@ component stands at Al = 0 (on an incomplete one libjpeg smooths between blocks 
 coefficients).  Every scan keeps its own segment (up to the next marker) and a blob with the Huffman tables in force at its SOS; files
 are batched by ``(geometry, script)``.  By default such a file is refused as before.
 
-The blob (``BLOB_BYTES`` per file, the layout csrc/jpeg.hip's ``FileTables`` reads):
+The blob (``BLOB_BYTES`` per file, the layout csrc/jpeg_decode.hip's ``FileTables`` reads):
   4 Huffman tables in the order DC0, DC1, AC0, AC1, 912 bytes each - look[256] uint16: for the next 8 bits of the stream, (code length
     << 8) | symbol of the code of at most 8 bits that starts there, 0 when none; maxcode[18] int32: the largest code of each length 1..16,
     -1 where the length has none (index 0 unused, index 17 = -1); valoff[18] int32: index into val of the first symbol of that length

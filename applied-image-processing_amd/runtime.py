@@ -1018,28 +1018,38 @@ def jpeg_decode_sizes(n, h, w, c, sampling, max_segment_bytes, chunk_bits=0, res
 _jpeg_decode_lock = threading.Lock()
 
 
+def _jpeg_upload(streams, device, lead):
+    """``streams``: per entropy-coded segment what describes it (``blob``, ``seg_offset``, ``seg_length``: a baseline file, or one scan of
+    a progressive one) and the bytes of its file -> (device uint8 tensor: the blobs, ``lead`` spare bytes, the segments back to back;
+    segment offsets behind the blobs; segment lengths)."""
+    from . import jpeg_file
+
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise AdainHipError("jpeg_decode_u8: expected a GPU device (the device decoder has no CPU form)")
+    blobs = len(streams) * jpeg_file.BLOB_BYTES
+    lengths = [s.seg_length for s, _ in streams]
+    offsets, at = [], lead
+    for ln in lengths:
+        offsets.append(at)
+        at += ln
+    host = bytearray(blobs + at + 1)            # one spare byte: the pointer behind the blobs stays inside the tensor
+    for i, (s, d) in enumerate(streams):
+        host[i * jpeg_file.BLOB_BYTES:(i + 1) * jpeg_file.BLOB_BYTES] = s.blob
+        host[blobs + offsets[i]:blobs + offsets[i] + lengths[i]] = d[s.seg_offset:s.seg_offset + s.seg_length]
+    return torch.frombuffer(host, dtype=torch.uint8).to(device), offsets, lengths
+
+
 def jpeg_decode_upload(parsed, datas, device, lead=0):
     """The one upload of a ``jpeg_decode_batch`` call: the table blobs of n files of ONE geometry and ONE restart interval, ``lead``
     spare bytes, then their entropy-coded segments (RSTn markers and all) back to back -> (device uint8 tensor, segment offsets behind
     the blobs, segment lengths)."""
-    from . import jpeg_file
-
     n = len(parsed)
     if n < 1 or any(p.geometry != parsed[0].geometry for p in parsed) or len(datas) != n:
         raise AdainHipError("jpeg_decode_batch: expected the files of one geometry")
     if any(p.restart_interval != parsed[0].restart_interval for p in parsed):
         raise AdainHipError("jpeg_decode_batch: expected the files of one restart interval")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise AdainHipError("jpeg_decode_u8: expected a GPU device (the device decoder has no CPU form)")
-    blobs = n * jpeg_file.BLOB_BYTES
-    lengths = [p.seg_length for p in parsed]
-    offsets = [lead + sum(lengths[:i]) for i in range(n)]
-    host = bytearray(blobs + lead + sum(lengths) + 1)           # one spare byte: the pointer behind the blobs stays inside the tensor
-    for i, (p, d) in enumerate(zip(parsed, datas)):
-        host[i * jpeg_file.BLOB_BYTES:(i + 1) * jpeg_file.BLOB_BYTES] = p.blob
-        host[blobs + offsets[i]:blobs + offsets[i] + lengths[i]] = d[p.seg_offset:p.seg_offset + p.seg_length]
-    return torch.frombuffer(host, dtype=torch.uint8).to(device), offsets, lengths
+    return _jpeg_upload(list(zip(parsed, datas)), device, lead)
 
 
 def jpeg_decode_launch(up, offsets, lengths, geometry, chunk_bits=0, restart_interval=0):
@@ -1087,28 +1097,12 @@ def jpeg_decode_progressive_upload(parsed, datas, device, lead=0):
     """The one upload of a ``jpeg_decode_progressive_batch`` call: the table blobs [n][scans] of n files of ONE geometry and ONE scan
     script, ``lead`` spare bytes, then every file's scan segments back to back -> (device uint8 tensor, segment offsets behind the
     blobs [n * scans], segment lengths [n * scans])."""
-    from . import jpeg_file
-
     n = len(parsed)
     if n < 1 or any(p.geometry != parsed[0].geometry for p in parsed) or len(datas) != n:
         raise AdainHipError("jpeg_decode_progressive_batch: expected the files of one geometry")
     if any(p.script != parsed[0].script for p in parsed):
         raise AdainHipError("jpeg_decode_progressive_batch: expected the files of one scan script")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise AdainHipError("jpeg_decode_u8: expected a GPU device (the device decoder has no CPU form)")
-    scans = [(d, sc) for p, d in zip(parsed, datas) for sc in p.scans]
-    blobs = len(scans) * jpeg_file.BLOB_BYTES
-    lengths = [sc.seg_length for _, sc in scans]
-    offsets, at = [], lead
-    for ln in lengths:
-        offsets.append(at)
-        at += ln
-    host = bytearray(blobs + at + 1)            # one spare byte: the pointer behind the blobs stays inside the tensor
-    for i, (d, sc) in enumerate(scans):
-        host[i * jpeg_file.BLOB_BYTES:(i + 1) * jpeg_file.BLOB_BYTES] = sc.blob
-        host[blobs + offsets[i]:blobs + offsets[i] + lengths[i]] = d[sc.seg_offset:sc.seg_offset + sc.seg_length]
-    return torch.frombuffer(host, dtype=torch.uint8).to(device), offsets, lengths
+    return _jpeg_upload([(sc, d) for p, d in zip(parsed, datas) for sc in p.scans], device, lead)
 
 
 def jpeg_decode_progressive_launch(up, offsets, lengths, geometry, script, chunk_bits=0):

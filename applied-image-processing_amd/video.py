@@ -213,7 +213,7 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
             return len(names)
 
         def __getitem__(self, k):
-            if on_gpu and _jpeg_decode_on_device:             # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg.hip)
+            if on_gpu and _jpeg_decode_on_device:             # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg_decode.hip)
                 with torch.cuda.device(engine.device):
                     rgb = rt.jpeg_decode_rgb_file(os.path.join(content_dir, names[k]), engine.device, _jpeg_decode_progressive)
                 plan = adain_test._device_plan(rgb.shape[1], rgb.shape[0], 256, False) if rgb is not None else None

@@ -528,7 +528,7 @@ ADAIN_API int adain_jpeg_roundtrip_u8(const uint8_t* src_u8, int n, int h, int w
  *     valoff[18] int32: index of the length's first symbol minus its first code; val[256] uint8: HUFFVAL), q[3][64] uint8: each
  *     component's quantisation table in natural order, sel[8] uint8: the DC table of components 0..2, the AC table of components 0..2, 0, 0
  *   dst   HWC uint8 [n][h][w][c], any address: frame i = np.asarray(Image.open(file i)) (established against Pillow 12.2.0 built with
- *     libjpeg-turbo; the rules are listed in csrc/jpeg.hip and restated in tests/jpeg_file_ref.py)
+ *     libjpeg-turbo; the rules are listed in csrc/jpeg_decode.hip and restated in tests/jpeg_file_ref.py)
  *   record   device int32 [n][2]: file i's status and the rounds its entropy decode took.  Status 0: decoded.  Non-zero: the entropy data
  *     did not decode to exactly the expected number of blocks ending inside the last byte, or held a code or value no 8-bit baseline
  *     encoder writes; that frame's content is then unspecified (its writes stay inside dst) and the caller decodes the file on the host
@@ -551,7 +551,7 @@ ADAIN_API int adain_jpeg_roundtrip_u8(const uint8_t* src_u8, int n, int h, int w
  * interval's first MCU.  nint = ceil(MCUs / Ri); the status is also non-zero when the markers found are not nint - 1 or marker m is not
  * FF D(m mod 8) - no resynchronisation is tried, such a file goes to the host - and when any interval has damage, too few blocks or a
  * last block that does not end inside the interval's last byte.  Whatever the bytes, the writes stay inside dst, record and the
- * workspace.  The rules: csrc/jpeg.hip, restated in tests/jpeg_restart_ref.py.  The same launches per call as above. */
+ * workspace.  The rules: csrc/jpeg_decode.hip, restated in tests/jpeg_restart_ref.py.  The same launches per call as above. */
 ADAIN_API int adain_jpeg_decode_restart_u8_bytes(int n, int h, int w, int c, int sampling, int restart_interval, size_t max_segment_bytes,
                                                  int chunk_bits, size_t* workspace_bytes);
 ADAIN_API int adain_jpeg_decode_restart_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c,
@@ -589,7 +589,7 @@ ADAIN_API int adain_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, con
  * adain_jpeg_decode_progressive_u8_bytes (host only): *workspace_bytes for n files of nscans scans whose longest scan segment is
  * max_segment_bytes.  Refused as above, and: nscans outside 1..32, a scan that breaks the rules of `scans`.  Launches per call:
  * ceil(n nscans / 64) + 1 + one memset, per scan 3 (DC first), 1 (DC refinement), 2 (AC first) or 3 (AC refinement), and 3 more.  The
- * rules: csrc/jpeg.hip, restated in tests/jpeg_progressive_ref.py. */
+ * rules: csrc/jpeg_decode.hip, restated in tests/jpeg_progressive_ref.py. */
 ADAIN_API int adain_jpeg_decode_progressive_u8_bytes(int n, int h, int w, int c, int sampling, int nscans, size_t max_segment_bytes,
                                                      int chunk_bits, size_t* workspace_bytes);
 ADAIN_API int adain_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, const uint8_t* blobs, int n, int h, int w, int c,

@@ -1,4 +1,4 @@
-"""JPEG files built from chosen coefficients, for the three device decoders (csrc/jpeg.hip: adain_jpeg_decode_u8, adain_jpeg_decode_restart_u8,
+"""JPEG files built from chosen coefficients, for the three device decoders (csrc/jpeg_decode.hip: adain_jpeg_decode_u8, adain_jpeg_decode_restart_u8,
 adain_jpeg_decode_progressive_u8).  Files an encoder derives from pixels reach only part of what a decoder must take; here the
 coefficients, the Huffman tables, the header fields and the scan script are chosen, and ``coverage`` counts from the restatements' own
 walk (tests/jpeg_file_ref.py, jpeg_restart_ref.py, jpeg_progressive_ref.py) what a file makes a decoder do.  NumPy only, deterministic,

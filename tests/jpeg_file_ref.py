@@ -1,4 +1,4 @@
-"""Plain NumPy / Python restatement of the device JPEG file decoder (csrc/jpeg.hip, adain_jpeg_decode_u8): the marker walk, a sequential
+"""Plain NumPy / Python restatement of the device JPEG file decoder (csrc/jpeg_decode.hip, adain_jpeg_decode_u8): the marker walk, a sequential
 Huffman decoder, the DC sums and the back half (dequantisation with the file's tables, libjpeg's islow IDCT, its three upsamplers, its
 YCbCr -> RGB map) - and the fixed-point scheme the device uses to decode a stream in parallel, simulated lane by lane.  The IDCT and
 the h2v2 upsampler are tests/jpeg_decode_ref.py's, imported.  tests/test_jpeg_file_host.py holds all of it to Pillow.

@@ -1,4 +1,4 @@
-"""Plain Python restatement of the device decoder for progressive JPEG files (csrc/jpeg.hip, adain_jpeg_decode_progressive_u8): a marker
+"""Plain Python restatement of the device decoder for progressive JPEG files (csrc/jpeg_decode.hip, adain_jpeg_decode_progressive_u8): a marker
 walk of its own (not the package's parser), a sequential decoder of the four scan kinds, and the device's scheme - every Huffman-coded
 scan cut into subsequences whose exit states are iterated to the fixed point - simulated lane by lane, which predicts the device's round
 count.  The back half (dequantisation, IDCT, upsampling, colour) is tests/jpeg_file_ref.py's.  Every index formed here is asserted to be

@@ -1,9 +1,9 @@
-"""Plain Python restatement of the device JPEG file decoder's restart-interval rules (csrc/jpeg.hip, adain_jpeg_decode_restart_u8), on top
+"""Plain Python restatement of the device JPEG file decoder's restart-interval rules (csrc/jpeg_decode.hip, adain_jpeg_decode_restart_u8), on top
 of tests/jpeg_file_ref.py: that file's entropy decoder, ``Sink``, ``decode_lanes`` and ``pixels`` are imported and run per interval; this
 one adds the marker walk, the per-interval streams, the sequential decoder per interval and the lane scheme per interval.
 tests/test_jpeg_restart_host.py holds all of it to Pillow.
 
-The rules (the ones csrc/jpeg.hip lists under "restart"; Ri > 0 MCUs, nmcu = mw mh, nint = ceil(nmcu / Ri), interval k holds the MCUs
+The rules (the ones csrc/jpeg_decode.hip lists under "restart"; Ri > 0 MCUs, nmcu = mw mh, nint = ceil(nmcu / Ri), interval k holds the MCUs
 k Ri .. min((k+1) Ri, nmcu) - 1 and expects bpm min(Ri, nmcu - k Ri) blocks)
   segment  from behind SOS to EOI; it holds FF D0..D7 pairs, and as unstuffed entropy data cannot, each such pair is a marker.  Byte by
            byte: dropped are a 00 behind an FF, an FF in front of a D0..D7 that is still in the segment, and a D0..D7 behind an FF

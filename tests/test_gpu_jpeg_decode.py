@@ -1,4 +1,4 @@
-"""The device JPEG file decoder (csrc/jpeg.hip, adain_jpeg_decode_u8) and its callers.  Everything here is element-for-element equality:
+"""The device JPEG file decoder (csrc/jpeg_decode.hip, adain_jpeg_decode_u8) and its callers.  Everything here is element-for-element equality:
 the device's pixels against Pillow's ``np.asarray(Image.open(...))`` for the same bytes and, in tests of their own, against the Python
 restatement (tests/jpeg_file_ref.py) - a failure of the second kind says the kernel moved, of the first kind alone that the
 environment's Pillow / libjpeg did.  Then the chunk size of the parallel entropy decode, constant frames (periodic streams), batch

@@ -1,4 +1,4 @@
-"""The three device JPEG decoders (csrc/jpeg.hip: adain_jpeg_decode_u8, adain_jpeg_decode_restart_u8, adain_jpeg_decode_progressive_u8) on
+"""The three device JPEG decoders (csrc/jpeg_decode.hip: adain_jpeg_decode_u8, adain_jpeg_decode_restart_u8, adain_jpeg_decode_progressive_u8) on
 the designed files of tests/jpeg_designed.py, which tests/test_jpeg_designed_host.py has settled against Pillow on the host.  Everything is
 element-for-element equality (``first_difference(...) is None``): the device's pixels against Pillow's and the restatement's, its rounds
 against the lane simulation's, at chunk_bits 32 and at the default; a batch of two designed files per decoder against the two single

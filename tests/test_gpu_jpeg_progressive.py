@@ -1,4 +1,4 @@
-"""The device decoder for progressive JPEG files (csrc/jpeg.hip, adain_jpeg_decode_progressive_u8) and its callers.  Everything here is
+"""The device decoder for progressive JPEG files (csrc/jpeg_decode.hip, adain_jpeg_decode_progressive_u8) and its callers.  Everything here is
 element-for-element equality: the device's pixels against Pillow's ``np.asarray(Image.open(...))`` and against the Python restatement
 (tests/jpeg_progressive_ref.py), whose lane simulation also predicts the rounds.  Then end-of-band runs at their longest, the chunk size
 of the parallel entropy decode, batches, the memory contract through the guard-band arena (tests/abi_arena.py) with stale workspaces

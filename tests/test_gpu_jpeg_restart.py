@@ -1,4 +1,4 @@
-"""Restart intervals in the device JPEG file decoder (csrc/jpeg.hip, adain_jpeg_decode_restart_u8) and its callers.  Element-for-element
+"""Restart intervals in the device JPEG file decoder (csrc/jpeg_decode.hip, adain_jpeg_decode_restart_u8) and its callers.  Element-for-element
 equality everywhere: the device's pixels against Pillow's for the same bytes and against the Python restatement
 (tests/jpeg_restart_ref.py), with no file allowed to fall back to the host.  Then markers on the unstuff stage's piece and thread
 boundaries, the chunk size and the rounds, batches, the memory contract through the guard-band arena (tests/abi_arena.py) with stale
@@ -19,7 +19,7 @@ import jpeg_ref as J
 import jpeg_restart_ref as RR
 from test_gpu_jpeg_decode import Counter, first_difference, pil_outcome, u8img
 from test_jpeg_file_host import LAYOUTS, SHAPES, pillow, save
-from test_jpeg_restart_host import GOLDEN_RESTART, LANE_FILES, restart_files
+from test_jpeg_restart_host import GOLDEN_RESTART, LANE_FILES, MANY_KINDS, many_intervals_file, markers_in, restart_files
 
 import applied_image_processing_amd.jpeg_file as F
 import applied_image_processing_amd.synth as synth
@@ -85,6 +85,24 @@ def test_without_the_keyword_a_restart_file_stays_on_the_host(rt):
     out = rt.jpeg_decode_u8(data, DEV, report=report)
     assert report[0]["path"].startswith("host: a restart interval"), report
     assert first_difference(out.cpu().numpy(), pillow(data)) is None
+
+
+@pytest.mark.parametrize("kind", MANY_KINDS)
+def test_more_intervals_than_threads(rt, kind):
+    """1089 intervals of one MCU: the settle stage's scans over the interval table and over the block counts run past one pass of the
+    workgroup's 1024 threads and carry into a second; the noise file is also longer than ten pieces of the unstuff stage."""
+    data = many_intervals_file(kind)
+    p = F.parse(data, restart=True)
+    assert p.restart_interval == 1 and markers_in(data) == 1088
+    assert kind != "noise" or p.seg_length > 10 * 4096
+    frames, record = rt.jpeg_decode_batch([p], [data], DEV)
+    assert record.cpu().tolist()[0][0] == 0, record
+    (got,), _ = device_pixels(rt, [data])                       # through the caller: not left to the host
+    assert np.array_equal(frames[0, :, :, 0].cpu().numpy(), got)
+    bad = first_difference(got, pillow(data))
+    assert bad is None, f"against Pillow: {bad}"
+    bad = first_difference(got, restatement(data))
+    assert bad is None, f"against the restatement: {bad}"
 
 
 # ---- markers on the unstuff stage's boundaries ---------------------------------------------------------------------------------------------

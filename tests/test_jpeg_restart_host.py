@@ -141,6 +141,30 @@ def test_the_lane_files_are_what_they_are_meant_to_be():
     assert len(bits["smooth 64x64 4:2:0 blocks 5"]) == 4 and len(bits["constant white 64x64 4:2:0 rows 2"]) == 2
 
 
+# ---- more intervals than a per-file workgroup has threads ------------------------------------------------------------------------------
+MANY_KINDS = ["smooth", "noise"]
+
+
+@functools.lru_cache(maxsize=None)
+def many_intervals_file(kind):
+    """A grey 264 x 264 frame, 33 x 33 = 1089 MCUs, one MCU per restart interval: more intervals than the 1024 threads of the device's
+    per-file workgroups, so its scans over the interval table and over the subsequences' block counts take a second pass and carry."""
+    return save(J.content(kind, 264, 264, 1), 75, "L", restart_marker_blocks=1)
+
+
+@pytest.mark.parametrize("kind", MANY_KINDS)
+def test_more_intervals_than_threads(kind):
+    """The restatement is Pillow, sequentially and by the device's scheme at chunks of 32 and 1024 bits."""
+    data = many_intervals_file(kind)
+    f = F.parse(data, restart=True)
+    assert f.restart_interval == 1 and f.geometry == (264, 264, 1, 0) and markers_in(data) == 1088
+    want = pillow(data)
+    for chunk_bits in (None, 32, 1024):
+        got, status, _ = RR.decode(data, chunk_bits)
+        assert status == 0, chunk_bits
+        assert_same(got, want, f"{kind}, chunks of {chunk_bits}")
+
+
 # ---- what the parser refuses with restart=True ----------------------------------------------------------------------------------------
 def _with_markers():
     data = save(J.content("noise", 33, 17, 3), 90, 0, restart_marker_blocks=2)

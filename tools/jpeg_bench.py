@@ -7,9 +7,11 @@ after warm-up:
 and whether the two files are the same bytes.  ``passes_1080p``: device_ms sits below pillow_ms by more than the two interquartile
 ranges combined.  ``options``: the same three figures at 1080 x 1920 per option set of OPTION_SETS (quality, subsampling, optimize), under a
 key of its own, Pillow given the same keywords; ``faster_than_pillow`` there by the same rule.  With --job, a 64-view 1200 x 1600 precompute_guides_sharded into a temporary directory with jpeg_on_device off and on:
-wall time, the sink's wait and the bytes that crossed to the host.  Prints one JSON line and, with --out, writes it to a file.
-Usage: python tools/jpeg_bench.py [--reps 200] [--job] [--out profiles/jpeg_bench.json]"""
+wall time, the sink's wait and the bytes that crossed to the host.  Every kernel_ms also carries the sha256 of its last call's output bytes, so that two builds of the library
+(--lib PATH: that build in place of the package's own) can be held to the same bytes as well as the same time.  Prints one JSON line and, with --out, writes it to a file.
+Usage: python tools/jpeg_bench.py [--reps 200] [--job] [--lib PATH] [--out profiles/jpeg_bench.json]"""
 import argparse
+import hashlib
 import io
 import json
 import os
@@ -40,6 +42,11 @@ def spread(times):
     return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
 
 
+def sha256(out):
+    """Of the files of an encode's (files, lengths)."""
+    return hashlib.sha256(b"".join(rt.jpeg_files(*out))).hexdigest()
+
+
 def wall_ms(fn, reps, warmup, sync):
     for _ in range(warmup):
         fn()
@@ -61,11 +68,11 @@ def event_ms(fn, reps, warmup):
     for _ in range(reps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        fn()
+        out = fn()
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b))
-    return spread(times)
+    return dict(spread(times), sha256=sha256(out))
 
 
 def pillow_bytes(a, options=None):
@@ -112,7 +119,10 @@ def main():
     ap.add_argument("--job", action="store_true")
     ap.add_argument("--views", type=int, default=64)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--lib", type=str, default=None)
     args = ap.parse_args()
+    if args.lib:
+        rt.use_library(os.path.abspath(args.lib))
     assert torch.cuda.is_available(), "jpeg_bench needs a GPU"
     torch.cuda.set_device(0)
     torch.set_num_threads(1)
@@ -122,7 +132,7 @@ def main():
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     tel = GpuTelemetry(0).start()
     res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow": PIL.__version__, "sizes": {}, "options": {}}
+           "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "sizes": {}, "options": {}}
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         frames = {"stylised": engine.stylize_u8(source, alpha=0.5).contiguous(),

@@ -1,4 +1,4 @@
-"""Times the device JPEG file decoder (csrc/jpeg.hip, adain_jpeg_decode_u8) against the host route through Pillow on the same machine,
+"""Times the device JPEG file decoder (csrc/jpeg_decode.hip, adain_jpeg_decode_u8) against the host route through Pillow on the same machine,
 one file per call: files at 256 x 456 and 1080 x 1920, saved by Pillow at its default settings (quality 75, 4:2:0) and at quality 95,
 of a stylised synthetic frame (seed-0 weights) and of uniform noise, each also with one restart interval per MCU row (Pillow's
 ``restart_marker_rows=1``, the ``_restart`` rows: adain_jpeg_decode_restart_u8) and as a progressive file (Pillow's ``progressive=True``:
@@ -11,9 +11,12 @@ with the rounds the entropy decode took, whether the two give the same pixels, a
 by more than the two interquartile ranges combined.  ``chunk_bits``: kernel_ms of the 1080p files at 256, 512, 1024 and 2048 bits per
 subsequence over --sweep-reps calls (the library's default is the best of them on the stylised frames; dense noise needs thousands of
 rounds at the small sizes, which is why the sweep makes fewer calls).  Progress goes to stderr.  ``per_call``: ``adain_inference`` on a 256 x 456 JPEG content (style cached,
-``bench.py --per-call video``'s call) with ``set_device_jpeg_decode`` off and on.  Prints one JSON line and, with --out, writes it.
-Usage: python tools/jpeg_decode_bench.py [--reps 200] [--out profiles/jpeg_decode_bench.json]"""
+``bench.py --per-call video``'s call) with ``set_device_jpeg_decode`` off and on.  Every kernel_ms also carries the sha256 of its last call's output bytes, so that two builds of the library
+(--lib PATH: that build in place of the package's own) can be held to the same bytes as well as the same time.  Prints one JSON line and, with --out,
+writes it.
+Usage: python tools/jpeg_decode_bench.py [--reps 200] [--lib PATH] [--out profiles/jpeg_decode_bench.json]"""
 import argparse
+import hashlib
 import io
 import json
 import os
@@ -45,6 +48,11 @@ def spread(times):
     return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
 
 
+def sha256(out):
+    """Of a launch's (frames, record)."""
+    return hashlib.sha256(b"".join(t.cpu().numpy().tobytes() for t in out)).hexdigest()
+
+
 def wall_ms(fn, reps, warmup):
     """fn() ends with its result on the device; the clock stops after a synchronise."""
     for _ in range(warmup):
@@ -67,11 +75,11 @@ def event_ms(fn, reps, warmup):
     for _ in range(reps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        fn()
+        out = fn()
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b))
-    return spread(times)
+    return dict(spread(times), sha256=sha256(out))
 
 
 def host_route(data, dev):
@@ -130,7 +138,10 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--sweep-reps", type=int, default=40)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--lib", type=str, default=None)
     args = ap.parse_args()
+    if args.lib:
+        rt.use_library(os.path.abspath(args.lib))
     assert torch.cuda.is_available(), "jpeg_decode_bench needs a GPU"
     torch.cuda.set_device(0)
     torch.set_num_threads(1)
@@ -140,7 +151,7 @@ def main():
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     tel = GpuTelemetry(0).start()
     res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow": PIL.__version__, "sizes": {}, "chunk_bits": {}, "progressive": {}}
+           "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "sizes": {}, "chunk_bits": {}, "progressive": {}}
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         frames = {"stylised": engine.stylize_u8(source, alpha=0.5)[0].cpu().numpy(), "noise": np.random.default_rng(0).integers(0, 256, (h, w, 3), dtype=np.uint8)}

@@ -6,9 +6,11 @@ synthetic frame (seed-0 weights) and on uniform noise.  Per call on a batch of -
   device_ms  wall clock of the ``post`` hook with ``jpeg_on_device=True``: device tensor in, device tensor out, synchronised
   host_ms    the ``post`` hook without it: download, ``video._jpeg_roundtrip`` (Pillow, one thread), upload, synchronised
 and whether the two give the same bytes.  ``device_is_faster``: device_ms sits below host_ms by more than the two interquartile ranges
-combined.  Prints one JSON line and, with --out, writes it to a file.
-Usage: python tools/jpeg_roundtrip_bench.py [--reps 200] [--batch 1] [--out profiles/jpeg_roundtrip_bench.json]"""
+combined.  Every kernel_ms also carries the sha256 of its last call's output bytes, so that two builds of the library
+(--lib PATH: that build in place of the package's own) can be held to the same bytes as well as the same time.  Prints one JSON line and, with --out, writes it to a file.
+Usage: python tools/jpeg_roundtrip_bench.py [--reps 200] [--batch 1] [--lib PATH] [--out profiles/jpeg_roundtrip_bench.json]"""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -35,6 +37,10 @@ def spread(times):
     return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
 
 
+def sha256(out):
+    return hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()
+
+
 def wall_ms(fn, reps, warmup):
     """fn() ends with its result on the device; the clock stops after a synchronise."""
     for _ in range(warmup):
@@ -57,11 +63,11 @@ def event_ms(fn, reps, warmup):
     for _ in range(reps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        fn()
+        out = fn()
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b))
-    return spread(times)
+    return dict(spread(times), sha256=sha256(out))
 
 
 def host_post(u8):
@@ -74,7 +80,10 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--lib", type=str, default=None)
     args = ap.parse_args()
+    if args.lib:
+        rt.use_library(os.path.abspath(args.lib))
     assert torch.cuda.is_available(), "jpeg_roundtrip_bench needs a GPU"
     torch.cuda.set_device(0)
     torch.set_num_threads(1)
@@ -84,7 +93,7 @@ def main():
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     tel = GpuTelemetry(0).start()
     res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "batch": n, "pillow": PIL.__version__, "sizes": {}}
+           "batch": n, "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "sizes": {}}
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         frames = {"stylised": engine.stylize_u8(source, alpha=0.5).contiguous().expand(n, -1, -1, -1).contiguous(),
