@@ -19,8 +19,8 @@ import argparse
 import numpy as np
 import torch
 
-from . import test as adain_test
-from .test import adain_inference, set_device_coral, set_device_jpeg, set_device_jpeg_decode, set_jpeg_save_options
+from .. import runtime as rt
+from .test import adain_inference, set_device_coral, set_jpeg_routes
 
 # (flag, argparse keyword arguments) — names and defaults as in the reference CLI
 _REFERENCE_FLAGS = (
@@ -66,11 +66,9 @@ def main(argv=None):
     proximity = None
     if ns.depth_npy:
         proximity = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
-    prev = set_device_jpeg(ns.jpeg_on_device)
-    prev_options = set_jpeg_save_options(ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize)
+    prev_jpeg = set_jpeg_routes(rt.JpegRoutes(ns.jpeg_on_device, ns.jpeg_decode_on_device or ns.jpeg_decode_progressive, ns.jpeg_decode_progressive,
+                                              (ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize)))
     prev_coral = set_device_coral(ns.coral_on_device)
-    prev_progressive = adain_test._device_jpeg_decode_progressive
-    prev_decode = set_device_jpeg_decode(ns.jpeg_decode_on_device or ns.jpeg_decode_progressive, progressive=ns.jpeg_decode_progressive)
     style, mix = ns.style, {}
     if ns.style_interpolation_weights:
         style = ns.style.split(",")
@@ -82,10 +80,8 @@ def main(argv=None):
                                depth_prominence=ns.depth_prominence, output=ns.output, file_name=ns.file_name,
                                use_depth=ns.use_depth, depth_map=proximity, preserve_color=ns.coral_on_device, **mix)
     finally:
-        set_device_jpeg(prev)
-        set_jpeg_save_options(prev_options)
+        set_jpeg_routes(prev_jpeg)
         set_device_coral(prev_coral)
-        set_device_jpeg_decode(prev_decode, progressive=prev_progressive)
 
 
 if __name__ == "__main__":

@@ -180,26 +180,17 @@ def device_decode_transform_u8(path, size, crop, device, mark=None):
     device (adain_jpeg_decode_u8: Pillow's pixels) and resized there.  None when the file is not a three-component baseline JPEG the
     decoder takes (or, with ``set_device_jpeg_decode(True, progressive=True)``, a progressive one), or did not decode cleanly, or the
     transform is not the device's: the caller takes the PIL path."""
-    from .. import jpeg_file
-
-    with open(str(path), "rb") as f:
-        data = f.read()
-    try:
-        parsed = jpeg_file.parse(data, restart=True, progressive=_device_jpeg_decode_progressive)
-    except jpeg_file.UnsupportedJpeg:
+    read = rt.jpeg_read_parsed(path, _jpeg.decode_progressive)
+    if read is None or read[0].c != 3:          # PIL opens a grey file as mode L, which keeps the host transform
         return None
-    if parsed.c != 3:                           # PIL opens a grey file as mode L, which keeps the host transform
-        return None
+    parsed, data = read
     plan = _device_plan(parsed.w, parsed.h, size, crop)
     if plan is None:
         return None
     if mark is not None:
         with torch.cuda.device(device):
             mark()
-    if isinstance(parsed, jpeg_file.ProgressiveJpegFile):
-        out, record = rt.jpeg_decode_progressive_batch([parsed], [data], device)
-    else:
-        out, record = rt.jpeg_decode_batch([parsed], [data], device)
+    out, record = rt.jpeg_decode_parsed([parsed], [data], device)
     if record[0, 0].item() != 0:
         return None
     return _device_resize(out, parsed.w, parsed.h, plan)
@@ -209,16 +200,10 @@ def save_image(tensor, path, jpeg_options=None):
     """torchvision.utils.save_image for one image (test.py:243-244): x*255 + 0.5, clamp, uint8, PIL save.
     The quantisation runs on the GPU (adain_quantize_u8).  ``jpeg_options`` (``runtime.JpegOptions``): how a .jpg / .jpeg file is
     saved, by PIL or (``set_device_jpeg``) on the device; None: ``set_jpeg_save_options``' value."""
-    options = _jpeg_save_options if jpeg_options is None else rt.JpegOptions.of(jpeg_options)
+    routes = _jpeg if jpeg_options is None else _jpeg.replace(options=jpeg_options)
     if tensor.dim() == 3:
         tensor = tensor.unsqueeze(0)
-    if _device_jpeg_on and _is_jpeg_path(path) and tensor.shape[1] in (1, 3):
-        data, = rt.jpeg_files(*options.encode(rt.quantize_u8(tensor.float()[:1])))
-        with open(str(path), "wb") as f:
-            f.write(data)
-        return
-    u8 = rt.quantize_u8(tensor.float()[:1])[0].cpu().numpy()
-    options.save(Image.fromarray(u8[:, :, 0] if u8.shape[2] == 1 else u8), path)
+    routes.write(rt.quantize_u8(tensor.float()[:1]), path)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -302,47 +287,41 @@ def set_latency_schedule(enabled):
     return prev
 
 
-_device_jpeg_on = False
+_jpeg = rt.JpegRoutes()               # the JPEG routes of ``adain_inference`` (the cached per-call path and ``save_image``): runtime.JpegRoutes
+
+
+def jpeg_routes():
+    return _jpeg
+
+
+def set_jpeg_routes(routes):
+    """All of ``adain_inference``'s JPEG routes at once: a ``runtime.JpegRoutes``, a dict of its keywords, or None for the defaults (PIL
+    everywhere, Pillow's default save).  The three setters below change fields of it.  Returns the previous value."""
+    global _jpeg
+    prev, _jpeg = _jpeg, rt.JpegRoutes.of(routes)
+    return prev
 
 
 def set_device_jpeg(enabled):
-    """True: ``adain_inference`` (the cached per-call path and ``save_image``) encodes a ``.jpg`` / ``.jpeg`` output on the device
-    (adain_jpeg_encode_u8: the bytes Pillow's default save writes) and brings over the file instead of the raw frame; any other
-    extension is saved by PIL as before.  Default False.  Returns the previous setting."""
-    global _device_jpeg_on
-    prev, _device_jpeg_on = _device_jpeg_on, bool(enabled)
-    return prev
-
-
-_jpeg_save_options = rt.JpegOptions()
+    """``encode_on_device``: ``adain_inference`` (the cached per-call path and ``save_image``) encodes a ``.jpg`` / ``.jpeg`` output on the
+    device (the bytes PIL writes) and brings over the file instead of the raw frame.  Default False.  Returns the previous setting."""
+    return set_jpeg_routes(_jpeg.replace(encode_on_device=enabled)).encode_on_device
 
 
 def set_jpeg_save_options(quality=rt.JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
-    """How ``adain_inference`` (the cached per-call path and ``save_image``) saves a ``.jpg`` / ``.jpeg`` output: Pillow's ``quality``,
-    ``subsampling`` (0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0") and ``optimize`` keywords, honoured by PIL and, with ``set_device_jpeg(True)``,
-    by the device encoder - the same file.  Any other extension never sees them.  A ``runtime.JpegOptions`` may be given in place of
-    ``quality``.  The defaults are Pillow's default save.  Returns the previous value (a ``JpegOptions``)."""
-    global _jpeg_save_options
-    new = rt.JpegOptions(quality, subsampling, optimize) if isinstance(quality, int) else rt.JpegOptions.of(quality)
-    prev, _jpeg_save_options = _jpeg_save_options, new
-    return prev
-
-
-_device_jpeg_decode_on = False
-_device_jpeg_decode_progressive = False
+    """``options``: how ``adain_inference`` saves a ``.jpg`` / ``.jpeg`` output - Pillow's ``quality``, ``subsampling`` and ``optimize``
+    (``runtime.JpegOptions``, which may be given in place of ``quality``), honoured by PIL and by the device encoder: the same file.
+    The defaults are Pillow's default save.  Returns the previous value (a ``JpegOptions``)."""
+    new = rt.JpegOptions(quality, subsampling, optimize) if isinstance(quality, int) else quality
+    return set_jpeg_routes(_jpeg.replace(options=new)).options
 
 
 def set_device_jpeg_decode(enabled, progressive=False):
-    """True: the cached per-call path of ``adain_inference`` reads the bytes of a content given as a ``.jpg`` / ``.jpeg`` path, decodes
-    them on the device (adain_jpeg_decode_u8: the pixels Pillow decodes) and resizes that frame there, instead of decoding with PIL and
-    uploading the pixels.  Files with restart intervals are decoded there too.  A file the decoder does not take (progressive, grey,
-    ...: jpeg_file.parse) or that does not decode cleanly, a PIL image passed in by the caller and any other extension take the PIL path
-    as before.  ``progressive`` (with ``enabled``): progressive files are decoded on the device too (adain_jpeg_decode_progressive_u8);
-    without it they take the PIL path as before.  The output file does not change.  Default False.  Returns the previous ``enabled``."""
-    global _device_jpeg_decode_on, _device_jpeg_decode_progressive
-    prev, _device_jpeg_decode_on = _device_jpeg_decode_on, bool(enabled)
-    _device_jpeg_decode_progressive = bool(enabled and progressive)
-    return prev
+    """``decode_on_device``: the cached per-call path of ``adain_inference`` decodes a content given as a ``.jpg`` / ``.jpeg`` path on the
+    device (the pixels PIL decodes; files with restart intervals too) and resizes it there.  A file the decoder does not take (grey, ...:
+    jpeg_file.parse) or that does not decode cleanly, a PIL image and any other extension take the PIL path as before.
+    ``decode_progressive`` (with ``enabled`` only): progressive files too.  Default False.  Returns the previous ``enabled``."""
+    return set_jpeg_routes(_jpeg.replace(decode_on_device=enabled, decode_progressive=progressive)).decode_on_device
 
 
 _device_coral_on = False
@@ -358,10 +337,6 @@ def set_device_coral(enabled):
     global _device_coral_on
     prev, _device_coral_on = _device_coral_on, bool(enabled)
     return prev
-
-
-def _is_jpeg_path(path):
-    return str(path).lower().endswith((".jpg", ".jpeg"))
 
 
 def _with_schedule(fn):
@@ -708,7 +683,7 @@ def _content_frame(content_img, content_size, crop, device, call):
     T = _stage_timer
     t0 = time.perf_counter()
     pil_content = call.pil_content = _open(content_img)
-    if _device_jpeg_decode_on and (type(content_img) == str or isinstance(content_img, Path)) and _is_jpeg_path(content_img):
+    if _jpeg.decode_on_device and (type(content_img) == str or isinstance(content_img, Path)) and rt.is_jpeg_path(content_img):
         e0 = torch.cuda.Event(enable_timing=True) if T.on else None
         frame = device_decode_transform_u8(content_img, content_size, crop, device, e0.record if T.on else None)
         if frame is not None:                                        # (pil_content stays lazily opened: decoded only if a depth provider asks)
@@ -826,24 +801,14 @@ def _one_call(x, style, enc, dec, device, call, e0=None, style_weights=None):
     if T.on:
         e1.record()
         T.events.append((e0, e1))
-    if _device_jpeg_on and _is_jpeg_path(target):
-        encoded = _jpeg_save_options.encode(u8)
-        T("launch (one C-ABI call)", t0)
+    stages = iter(("launch (one C-ABI call)", "wait for the kernels + download", "encode + write the file"))
+
+    def mark():
+        nonlocal t0
+        T(next(stages), t0)
         t0 = time.perf_counter()
-        data, = rt.jpeg_files(*encoded)
-        T("wait for the kernels + download", t0)
-        t0 = time.perf_counter()
-        with open(str(target), "wb") as f:
-            f.write(data)
-        T("encode + write the file", t0)
-        return
-    T("launch (one C-ABI call)", t0)
-    t0 = time.perf_counter()
-    arr = u8[0].cpu().numpy()
-    T("wait for the kernels + download", t0)
-    t0 = time.perf_counter()
-    _jpeg_save_options.save(Image.fromarray(arr), target)
-    T("encode + write the file", t0)
+
+    _jpeg.write(u8, target, mark)
 
 
 def composite_with_mask(content, output_img, content_mask):

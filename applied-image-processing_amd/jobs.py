@@ -34,7 +34,7 @@ import torch
 import torch.distributed as dist
 
 from . import sharding as sh
-from .runtime import JpegOptions
+from .runtime import JpegOptions, JpegRoutes
 
 
 def style_schedule(n_frames, n_styles):
@@ -458,17 +458,16 @@ class FileSink:
     stream into a pinned buffer, a worker thread waits for it and encodes / saves the files (PIL), so the next sub-batch's
     kernels are already running.  ``close()`` waits for every file and re-raises the first error.  ``jpeg_options`` (``JpegOptions``, a
     (quality, subsampling, optimize) tuple or None for Pillow's defaults): how .jpg / .jpeg files are saved, on either route; files of
-    other extensions never see them.  ``jpeg_on_device`` (default off):
+    other extensions never see them.  ``jpeg`` (a ``runtime.JpegRoutes``) gives both in place of the two keywords.  ``jpeg_on_device`` (default off):
     a block whose paths all end in .jpg / .jpeg is encoded on the compute stream (adain_jpeg_encode_u8: the bytes PIL would write);
     the copy stream then brings over the lengths and, on a second stream of the sink's own, exactly that many bytes per frame, and the
     worker only writes them.  (The files do not ride on the lengths' stream: by the time a worker knows its lengths, the launching
     thread may have queued later blocks' length copies there, each waiting for later kernels.)"""
 
-    def __init__(self, device, workers=4, max_in_flight=None, jpeg_on_device=False, jpeg_options=None):
+    def __init__(self, device, workers=4, max_in_flight=None, jpeg_on_device=False, jpeg_options=None, jpeg=None):
         self.copier = HostCopier(device)
-        self.jpeg_on_device = bool(jpeg_on_device)
-        self.jpeg_options = JpegOptions.of(jpeg_options)
-        self.file_stream = torch.cuda.Stream(self.copier.device) if self.jpeg_on_device and self.copier.cuda else None
+        self.jpeg = JpegRoutes.of(jpeg) if jpeg is not None else JpegRoutes(encode_on_device=jpeg_on_device, options=jpeg_options)
+        self.file_stream = torch.cuda.Stream(self.copier.device) if self.jpeg.encode_on_device and self.copier.cuda else None
         self.file_bytes = 0                # bytes of encoded files the workers copied (under spare_lock)
         self.pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="adain-file-sink")
         self.futures = []
@@ -495,16 +494,16 @@ class FileSink:
     def _save(self, arr, path):
         from PIL import Image
 
-        self.jpeg_options.save(Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr), path)
+        self.jpeg.options.save(Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr), path)
 
     def _encodes(self, u8_block, paths):
-        return (self.jpeg_on_device and self.copier.cuda and u8_block.is_cuda and u8_block.dtype == torch.uint8 and u8_block.dim() == 4
-                and u8_block.shape[3] in (1, 3) and len(paths) > 0 and all(str(p).lower().endswith((".jpg", ".jpeg")) for p in paths))
+        return (self.jpeg.encodes(list(paths)) and self.copier.cuda and u8_block.is_cuda and u8_block.dtype == torch.uint8 and u8_block.dim() == 4
+                and u8_block.shape[3] in (1, 3))
 
     def _write_encoded(self, u8_block, paths):
         """The device-encode form of ``write``: the encode on the current stream, the lengths behind it on the copy stream; the worker
         waits for them, copies each frame's ``lengths[i]`` bytes into one pinned buffer on the copy stream and writes the files."""
-        files, lengths = self.jpeg_options.encode(u8_block)
+        files, lengths = self.jpeg.options.encode(u8_block)
         k = len(paths)
         lengths_host = torch.empty((k,), dtype=torch.int32, pin_memory=True)
         have_lengths = self.copier.copy(lengths_host, lengths)

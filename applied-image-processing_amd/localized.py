@@ -252,14 +252,13 @@ def run_localized_style_transfer(content_img_path, style_img_path, output_path="
     ([1,H,W] uint8) to bypass the mask provider; extra keyword arguments go to ``adain_inference`` (checkpoint paths,
     ``depth_map=`` ...).  ``colour_on_device`` (keyword only, default off): the colour transfer and the composite run on the device
     (``combine_localized_device``) instead of in numpy; file names, the JPEG save and the return value do not change.
-    ``jpeg_options`` (``runtime.JpegOptions`` or a (quality, subsampling, optimize) tuple; default: Pillow's default save): how the final
-    composite's .jpg is saved.  ``jpeg_on_device`` (default off): that file comes from the device encoder - the same bytes; with
-    ``colour_on_device`` the composite never leaves the device before it is a file.  (The intermediate stylised file is
-    ``adain_inference``'s: ``AdaIN.test.set_device_jpeg`` / ``set_jpeg_save_options``.)"""
+    ``jpeg_on_device`` (default off) and ``jpeg_options`` (default: Pillow's default save) make the ``runtime.JpegRoutes`` of the final
+    composite's .jpg: encoded on the device - the same bytes; with ``colour_on_device`` the composite never leaves the device before it
+    is a file - and how it is saved.  (The intermediate stylised file is ``adain_inference``'s: ``AdaIN.test.set_jpeg_routes``.)"""
     from . import runtime as rt
     from .AdaIN.test import adain_inference
 
-    options = rt.JpegOptions.of(jpeg_options)
+    routes = rt.JpegRoutes(encode_on_device=jpeg_on_device, options=jpeg_options)
 
     content_img = Image.open(content_img_path).convert("RGB")
     content_np = np.array(content_img)
@@ -272,16 +271,13 @@ def run_localized_style_transfer(content_img_path, style_img_path, output_path="
     stylized_np = np.array(Image.open(stylized_path).convert("RGB"))
     Path(output_path).mkdir(exist_ok=True, parents=True)
     save_path = f"{output_path}/localized_style_transfer_result.jpg"
-    if jpeg_on_device:
+    if routes.encodes(save_path):
         dev = _device_of(None)
         if colour_on_device:              # a device tensor in, a device tensor out
             combined = combine_localized_device(_to_device(content_np, dev), stylized_np, background_mask[0], device=dev)
         else:
             combined = _to_device(combine_localized(content_np, stylized_np, background_mask[0]), dev)
-        data, = rt.jpeg_files(*options.encode(combined))
-        with open(save_path, "wb") as f:
-            f.write(data)
-        return save_path
-    combined = (combine_localized_device if colour_on_device else combine_localized)(content_np, stylized_np, background_mask[0])
-    options.save(Image.fromarray(combined), save_path)
+    else:
+        combined = (combine_localized_device if colour_on_device else combine_localized)(content_np, stylized_np, background_mask[0])
+    routes.write(combined, save_path)
     return save_path

@@ -824,6 +824,15 @@ def resize_pil_bilinear_u8(frames, size, crop=None, out=None):
 JPEG_DEFAULT_QUALITY = 75          # Pillow's
 
 
+def _jpeg_sizes(name, *dims, results=1):
+    """The size query ``name`` of the C ABI on the integers ``dims`` -> its size_t results.  Host only.  AdainHipError for a refused shape."""
+    out = [_c_size_t() for _ in range(results)]
+    rc = getattr(lib(), name)(*(int(d) for d in dims), *(ctypes.byref(o) for o in out))
+    if rc != 0:
+        raise _failure(name, rc)
+    return [o.value for o in out]
+
+
 def _jpeg_frames(u8, what, quality):
     """The checks and input forms the JPEG calls share: frames uint8 [n,h,w,3|1], one frame [h,w,3|1] or [h,w] -> contiguous [n,h,w,c]."""
     if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
@@ -861,7 +870,46 @@ def is_jpeg_path(path):
     return str(path).lower().endswith((".jpg", ".jpeg"))
 
 
-class JpegOptions:
+class _Value:
+    """What the immutable values below share: their fields are their ``__slots__``, set once in ``__init__`` (``_set``); equality, hash
+    and repr go by value; ``replace(**changes)`` gives a changed copy."""
+    __slots__ = ()
+
+    def _set(self, **fields):
+        for name, value in fields.items():
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"{type(self).__name__} is immutable")
+
+    def _key(self):
+        return tuple(getattr(self, name) for name in self.__slots__)
+
+    @classmethod
+    def of(cls, value):
+        """None -> the defaults; an instance -> itself; a dict of keywords -> the value."""
+        if value is None:
+            return cls()
+        if isinstance(value, cls) or type(value).__name__ == cls.__name__:          # (a reloaded module's class is another object)
+            return value
+        if isinstance(value, dict):
+            return cls(**value)
+        raise AdainHipError(f"expected {cls.__name__}, a dict or None, got {value!r}")
+
+    def replace(self, **changes):
+        return type(self)(**{**dict(zip(self.__slots__, self._key())), **changes})
+
+    def __eq__(self, other):
+        return type(other).__name__ == type(self).__name__ and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(f'{name}={value!r}' for name, value in zip(self.__slots__, self._key()))})"
+
+
+class JpegOptions(_Value):
     """How to save a JPEG: Pillow's ``quality`` (1..100, default 75), ``subsampling`` (0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0", default
     4:2:0) and ``optimize`` (the file's own optimal Huffman tables, default off) - the keywords the device encoder covers.  The defaults
     are Pillow's default save.  One value for both routes of a caller: ``encode`` is the device's (``jpeg_encode_u8``), ``save`` the
@@ -873,37 +921,16 @@ class JpegOptions:
     def __init__(self, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
         if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
             raise AdainHipError(f"JpegOptions: quality must be an int in 1..100, got {quality!r}")
-        object.__setattr__(self, "quality", quality)
-        object.__setattr__(self, "subsampling", jpeg_subsampling(subsampling, "JpegOptions"))
-        object.__setattr__(self, "optimize", bool(_jpeg_optimize(optimize, "JpegOptions")))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("JpegOptions is immutable")
+        self._set(quality=quality, subsampling=jpeg_subsampling(subsampling, "JpegOptions"), optimize=bool(_jpeg_optimize(optimize, "JpegOptions")))
 
     @classmethod
     def of(cls, value):
         """None -> the defaults; a JpegOptions -> itself; a (quality, subsampling, optimize) tuple or a dict of keywords -> the value."""
-        if value is None:
-            return cls()
-        if isinstance(value, cls) or type(value).__name__ == cls.__name__:          # (a reloaded module's class is another object)
-            return value
-        if isinstance(value, dict):
-            return cls(**value)
         if isinstance(value, (tuple, list)):
             return cls(*value)
+        if value is None or isinstance(value, dict) or type(value).__name__ == cls.__name__:
+            return super().of(value)
         raise AdainHipError(f"jpeg_options: expected JpegOptions, a (quality, subsampling, optimize) tuple, a dict or None, got {value!r}")
-
-    def _key(self):
-        return (self.quality, self.subsampling, self.optimize)
-
-    def __eq__(self, other):
-        return type(other).__name__ == type(self).__name__ and self._key() == other._key()
-
-    def __hash__(self):
-        return hash(self._key())
-
-    def __repr__(self):
-        return f"JpegOptions(quality={self.quality}, subsampling={self.subsampling}, optimize={self.optimize})"
 
     @property
     def is_default(self):
@@ -934,15 +961,56 @@ class JpegOptions:
         return jpeg_encode_u8(u8, self.quality, self.subsampling, self.optimize)
 
 
+class JpegRoutes(_Value):
+    """Which of a call's JPEG work the device does and how its files are saved - one value for every caller (``AdaIN.test``'s setters, the
+    video entry points, ``jobs.FileSink``, the localized pipeline).  ``encode_on_device``: .jpg / .jpeg outputs are encoded on the device
+    instead of by PIL, the same files; ``decode_on_device``: .jpg / .jpeg inputs are decoded there, the same pixels;
+    ``decode_progressive``: progressive inputs too - only with ``decode_on_device``, False without it (this is the one place that says
+    so); ``options``: a ``JpegOptions`` (or what ``JpegOptions.of`` takes), how an output is saved on either route.  The defaults:
+    everything off, Pillow's default save."""
+    __slots__ = ("encode_on_device", "decode_on_device", "decode_progressive", "options")
+
+    def __init__(self, encode_on_device=False, decode_on_device=False, decode_progressive=False, options=None):
+        self._set(encode_on_device=bool(encode_on_device), decode_on_device=bool(decode_on_device),
+                  decode_progressive=bool(decode_on_device and decode_progressive), options=JpegOptions.of(options))
+
+    def encodes(self, paths):
+        """Does the device encode the file(s) at ``paths`` (one, or a list)?  With ``encode_on_device``, when every path is .jpg / .jpeg."""
+        paths = paths if isinstance(paths, (list, tuple)) else [paths]
+        return self.encode_on_device and len(paths) > 0 and all(is_jpeg_path(p) for p in paths)
+
+    def write(self, u8, path, mark=None):
+        """One uint8 frame [1,h,w,c] or [h,w,c] on the device -> the file at ``path``: encoded there with ``options`` when ``encodes(path)``
+        and c is 1 or 3, only the file coming over; else downloaded (a numpy frame is taken as it is) and saved by ``options.save``.
+        ``mark()`` is called after each of the three steps: the launch, the wait for the device with the download, the write."""
+        from PIL import Image
+
+        mark = mark or (lambda: None)
+        if self.encodes(path) and u8.shape[-1] in (1, 3):
+            encoded = self.options.encode(u8)
+            mark()
+            data, = jpeg_files(*encoded)
+            mark()
+            with open(str(path), "wb") as f:
+                f.write(data)
+        else:
+            mark()
+            arr = u8.cpu().numpy() if isinstance(u8, torch.Tensor) else u8
+            arr = arr[0] if arr.ndim == 4 else arr
+            mark()
+            self.options.save(Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr), path)
+        mark()
+
+    def read_rgb(self, path, device):
+        """``jpeg_decode_rgb_file(path, device)`` with ``decode_on_device`` - the frame on the device, or None: the caller decodes with PIL."""
+        return jpeg_decode_rgb_file(path, device, self.decode_progressive) if self.decode_on_device else None
+
+
 def jpeg_encode_sizes(n, h, w, c, subsampling=2, optimize=False):
     """(out_stride, workspace_bytes) of adain_jpeg_encode_opt_u8_bytes (at the defaults: adain_jpeg_encode_u8_bytes' values): the
     largest file a frame of this shape can have and the scratch of an n-frame call.  Host only.  AdainHipError for a refused shape."""
-    stride, ws = _c_size_t(), _c_size_t()
-    rc = lib().adain_jpeg_encode_opt_u8_bytes(int(n), int(h), int(w), int(c), jpeg_subsampling(subsampling, "jpeg_encode_sizes"),
-                                              _jpeg_optimize(optimize, "jpeg_encode_sizes"), ctypes.byref(stride), ctypes.byref(ws))
-    if rc != 0:
-        raise _failure("adain_jpeg_encode_opt_u8_bytes", rc)
-    return stride.value, ws.value
+    return tuple(_jpeg_sizes("adain_jpeg_encode_opt_u8_bytes", n, h, w, c, jpeg_subsampling(subsampling, "jpeg_encode_sizes"),
+                             _jpeg_optimize(optimize, "jpeg_encode_sizes"), results=2))
 
 
 def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
@@ -982,11 +1050,7 @@ def jpeg_files(out, lengths):
 
 def jpeg_roundtrip_sizes(n, h, w, c):
     """workspace_bytes of adain_jpeg_roundtrip_u8_bytes: the scratch of an n-frame call.  Host only.  AdainHipError for a refused shape."""
-    ws = _c_size_t()
-    rc = lib().adain_jpeg_roundtrip_u8_bytes(int(n), int(h), int(w), int(c), ctypes.byref(ws))
-    if rc != 0:
-        raise _failure("adain_jpeg_roundtrip_u8_bytes", rc)
-    return ws.value
+    return _jpeg_sizes("adain_jpeg_roundtrip_u8_bytes", n, h, w, c)[0]
 
 
 def jpeg_roundtrip_u8(u8, quality=JPEG_DEFAULT_QUALITY):
@@ -1007,12 +1071,7 @@ def jpeg_decode_sizes(n, h, w, c, sampling, max_segment_bytes, chunk_bits=0, res
     """workspace_bytes of adain_jpeg_decode_restart_u8_bytes: the scratch of an n-file call whose longest entropy-coded segment has
     ``max_segment_bytes`` and whose files have ``restart_interval`` MCUs per restart interval (0: none).  Host only.  AdainHipError for
     a refused shape."""
-    ws = _c_size_t()
-    rc = lib().adain_jpeg_decode_restart_u8_bytes(int(n), int(h), int(w), int(c), int(sampling), int(restart_interval), int(max_segment_bytes), int(chunk_bits),
-                                                  ctypes.byref(ws))
-    if rc != 0:
-        raise _failure("adain_jpeg_decode_restart_u8_bytes", rc)
-    return ws.value
+    return _jpeg_sizes("adain_jpeg_decode_restart_u8_bytes", n, h, w, c, sampling, restart_interval, max_segment_bytes, chunk_bits)[0]
 
 
 _jpeg_decode_lock = threading.Lock()
@@ -1085,12 +1144,7 @@ def jpeg_decode_batch(parsed, datas, device, chunk_bits=0, lead=0):
 def jpeg_decode_progressive_sizes(n, h, w, c, sampling, nscans, max_segment_bytes, chunk_bits=0):
     """workspace_bytes of adain_jpeg_decode_progressive_u8_bytes: the scratch of an n-file call of ``nscans`` scans whose longest scan
     segment has ``max_segment_bytes``.  Host only.  AdainHipError for a refused shape."""
-    ws = _c_size_t()
-    rc = lib().adain_jpeg_decode_progressive_u8_bytes(int(n), int(h), int(w), int(c), int(sampling), int(nscans), int(max_segment_bytes), int(chunk_bits),
-                                                      ctypes.byref(ws))
-    if rc != 0:
-        raise _failure("adain_jpeg_decode_progressive_u8_bytes", rc)
-    return ws.value
+    return _jpeg_sizes("adain_jpeg_decode_progressive_u8_bytes", n, h, w, c, sampling, nscans, max_segment_bytes, chunk_bits)[0]
 
 
 def jpeg_decode_progressive_upload(parsed, datas, device, lead=0):
@@ -1139,6 +1193,28 @@ def jpeg_decode_progressive_batch(parsed, datas, device, chunk_bits=0, lead=0):
     return jpeg_decode_progressive_launch(up, offsets, lengths, parsed[0].geometry, parsed[0].script, chunk_bits)
 
 
+def jpeg_decode_parsed(parsed, datas, device, chunk_bits=0, lead=0):
+    """``jpeg_decode_progressive_batch`` or ``jpeg_decode_batch`` of files parsed alike, by what they were parsed as.  Every route to
+    the device decoders goes through here and through those two names (looked up when called: tests count the decodes there)."""
+    from . import jpeg_file
+
+    batch = jpeg_decode_progressive_batch if isinstance(parsed[0], jpeg_file.ProgressiveJpegFile) else jpeg_decode_batch
+    return batch(parsed, datas, device, chunk_bits, lead)
+
+
+def jpeg_read_parsed(path, progressive=False):
+    """The file at ``path``, read and parsed as the callers' file routes take it (restart intervals always, progressive files with
+    ``progressive``) -> (jpeg_file.JpegFile | ProgressiveJpegFile, its bytes), or None for a file jpeg_file.parse refuses."""
+    from . import jpeg_file
+
+    with open(str(path), "rb") as f:
+        data = f.read()
+    try:
+        return jpeg_file.parse(data, restart=True, progressive=progressive), data
+    except jpeg_file.UnsupportedJpeg:
+        return None
+
+
 def _pil_pixels(data, mode):
     import io
 
@@ -1173,12 +1249,11 @@ def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None, res
             p = jpeg_file.parse(d, restart=restart, progressive=progressive)
             if mode == "L" and p.c == 3:
                 raise jpeg_file.UnsupportedJpeg("a colour file where grey is wanted")
-            key = ("progressive", p.script) if isinstance(p, jpeg_file.ProgressiveJpegFile) else ("sequential", p.restart_interval)
-            groups.setdefault((p.geometry, key), []).append((i, p))
+            alike = p.script if hasattr(p, "script") else p.restart_interval          # what one batch call's files share beside the geometry
+            groups.setdefault((p.geometry, alike), []).append((i, p))
         except jpeg_file.UnsupportedJpeg as e:
             why[i] = str(e)
-    launched = [(members, (jpeg_decode_progressive_batch if key[0] == "progressive" else jpeg_decode_batch)(
-        [p for _, p in members], [datas[i] for i, _ in members], device, chunk_bits)) for (_, key), members in groups.items()]
+    launched = [(members, jpeg_decode_parsed([p for _, p in members], [datas[i] for i, _ in members], device, chunk_bits)) for members in groups.values()]
     for members, (out, record) in launched:
         rec = record.cpu().tolist()                      # the one read of the record: waits for the call
         for k, (i, p) in enumerate(members):
@@ -1201,20 +1276,11 @@ def jpeg_decode_rgb_file(path, device, progressive=False):
     the file is not one the device decoder takes (not a .jpg / .jpeg name, refused by jpeg_file.parse, a non-zero status): the caller
     then decodes it with PIL as before.  Files with restart intervals are taken; progressive files only with ``progressive=True``.
     Reads the record once (waits for the call)."""
-    from . import jpeg_file
-
-    if not str(path).lower().endswith((".jpg", ".jpeg")) or torch.device(device).type != "cuda":
+    read = jpeg_read_parsed(path, progressive) if is_jpeg_path(path) and torch.device(device).type == "cuda" else None
+    if read is None:
         return None
-    with open(str(path), "rb") as f:
-        data = f.read()
-    try:
-        parsed = jpeg_file.parse(data, restart=True, progressive=progressive)
-    except jpeg_file.UnsupportedJpeg:
-        return None
-    if isinstance(parsed, jpeg_file.ProgressiveJpegFile):
-        out, record = jpeg_decode_progressive_batch([parsed], [data], device)
-    else:
-        out, record = jpeg_decode_batch([parsed], [data], device)
+    parsed, data = read
+    out, record = jpeg_decode_parsed([parsed], [data], device)
     if record[0, 0].item() != 0:
         return None
     return out[0].expand(-1, -1, 3).contiguous() if parsed.c == 1 else out[0]

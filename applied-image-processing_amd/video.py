@@ -29,6 +29,8 @@ One deliberate difference: the reference writes every stylised frame as a JPEG i
 the host, or with ``jpeg_on_device=True`` on the GPU, where the whole batch becomes the pixels PIL would decode without a file being
 made (csrc/jpeg.hip, adain_jpeg_roundtrip_u8: the same bytes).
 """
+import contextlib
+import contextvars
 import io
 import os
 from pathlib import Path
@@ -42,8 +44,10 @@ from . import runtime as rt
 from .AdaIN import test as adain_test
 
 _flow_provider = None
-_jpeg_decode_on_device = False          # set for the duration of a call with jpeg_decode_on_device=True (_run)
-_jpeg_decode_progressive = False        # with it: jpeg_decode_progressive=True, progressive frames are decoded on the device too
+# The routes (rt.JpegRoutes) of the clip that is running on THIS thread; the default outside one.  Only the public flow providers read
+# it: they are called as fn(prev, cur, resolution, method), also from a caller's wrapper, and decode as their clip does.  Everything
+# else is handed the clip's value (the feeder's fetch threads inherit no context).
+_routes = contextvars.ContextVar("video_jpeg_routes", default=rt.JpegRoutes())
 _IMAGE_EXT = (".jpg", ".jpeg", ".png")
 
 
@@ -61,12 +65,21 @@ def estimate_optical_flow(prev_frame_path, frame_path, target_resolution, method
     return torch.as_tensor(np.asarray(f) if not isinstance(f, torch.Tensor) else f, dtype=torch.float32)
 
 
-def _decode_gray(path, target_resolution, device):
+@contextlib.contextmanager
+def _routes_scope(routes):
+    token = _routes.set(routes)
+    try:
+        yield
+    finally:
+        _routes.reset(token)
+
+
+def _decode_gray(path, target_resolution, device, routes):
     """cv2.imread + cv2.resize(target_resolution) + COLOR_RGB2GRAY of the reference (video/utils.py:75-77, :330-332), on the
     device (flow.frames_to_gray).  Decoded with PIL, which does not apply the EXIF orientation cv2.imread applies (unpinned)."""
     from . import flow as fl
 
-    rgb = rt.jpeg_decode_rgb_file(path, device, _jpeg_decode_progressive) if _jpeg_decode_on_device else None          # the same pixels, decoded where they are used
+    rgb = routes.read_rgb(path, device)          # the same pixels, decoded where they are used
     if rgb is None:
         rgb = torch.from_numpy(np.array(Image.open(path).convert("RGB"))).to(device)
     return fl.frames_to_gray(rgb, target_resolution)
@@ -82,7 +95,7 @@ def device_flow_provider(prev_frame_path, frame_path, target_resolution, method=
         raise ValueError(f"device_flow_provider: optical-flow method {method!r} is not built in (DualTV-L1 is not; use 'farneback' or "
                          "install a provider of your own)")
     dev = torch.device("cuda", torch.cuda.current_device())
-    prev, cur = _decode_gray(prev_frame_path, target_resolution, dev), _decode_gray(frame_path, target_resolution, dev)
+    prev, cur = (_decode_gray(p, target_resolution, dev, _routes.get()) for p in (prev_frame_path, frame_path))
     return fl.calc_optical_flow_farneback(prev, cur, None, 0.5, 5, 15, 3, 7, 1.5, 0).permute(2, 0, 1).contiguous()
 
 
@@ -98,7 +111,7 @@ def device_flow_provider_all(prev_frame_path, frame_path, target_resolution, met
     from . import tvl1
 
     dev = torch.device("cuda", torch.cuda.current_device())
-    prev, cur = _decode_gray(prev_frame_path, target_resolution, dev), _decode_gray(frame_path, target_resolution, dev)
+    prev, cur = (_decode_gray(p, target_resolution, dev, _routes.get()) for p in (prev_frame_path, frame_path))
     return tvl1.DualTVL1OpticalFlow_create().calc(prev, cur, None).permute(2, 0, 1).contiguous()
 
 
@@ -107,14 +120,14 @@ def device_flow_provider_all(prev_frame_path, frame_path, target_resolution, met
 _OWN_METHODS = {id(device_flow_provider): ("farneback",), id(device_flow_provider_all): ("farneback", "dualtvl1")}
 
 
-def _flow_source(content_dir, names, flow_method, size, device, cancel_flag):
+def _flow_source(content_dir, names, flow_method, size, device, cancel_flag, routes):
     """The recurrence's flows: ``f(i)`` is the [2,H,W] device flow frame i-1 -> frame i, called for i = 1, 2, ... in order.  The
     package's own estimators decode and prepare every frame once, with the same bits as their providers per pair; any other
     provider is called per pair."""
     path = lambda k: os.path.join(content_dir, names[k])
     if flow_method not in _OWN_METHODS.get(id(_flow_provider), ()):
         return lambda i: estimate_optical_flow(path(i - 1), path(i), size, flow_method).to(device)
-    gray = lambda k: _decode_gray(path(k), size, device)
+    gray = lambda k: _decode_gray(path(k), size, device, routes)
     with torch.cuda.device(device):
         if flow_method == "dualtvl1":
             # all n-1 flows before the recurrence, up to max_pairs pairs per call (chunks); None when cancelled
@@ -158,22 +171,8 @@ def _jpeg_roundtrip(u8):
     return out
 
 
-def _run(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device=False, preserve_color=False, crossfade_frames=0,
-         jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None):
-    global _jpeg_decode_on_device, _jpeg_decode_progressive
-    prev, _jpeg_decode_on_device = _jpeg_decode_on_device, bool(jpeg_decode_on_device)
-    prev_progressive, _jpeg_decode_progressive = _jpeg_decode_progressive, bool(jpeg_decode_on_device and jpeg_decode_progressive)
-    try:
-        return _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-                         vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color, crossfade_frames,
-                         jobs.JpegOptions.of(jpeg_options))
-    finally:
-        _jpeg_decode_on_device, _jpeg_decode_progressive = prev, prev_progressive
-
-
 def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-              vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color, crossfade_frames, jpeg_options):
+              vgg_str, decoder_str, depth_maps, group, preserve_color, crossfade_frames, intermediate_jpeg, routes):
     from . import sharding as sh
     from .engine import AdaINEngine
 
@@ -213,9 +212,9 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
             return len(names)
 
         def __getitem__(self, k):
-            if on_gpu and _jpeg_decode_on_device:             # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg_decode.hip)
+            if on_gpu and routes.decode_on_device:            # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg_decode.hip)
                 with torch.cuda.device(engine.device):
-                    rgb = rt.jpeg_decode_rgb_file(os.path.join(content_dir, names[k]), engine.device, _jpeg_decode_progressive)
+                    rgb = routes.read_rgb(os.path.join(content_dir, names[k]), engine.device)
                 plan = adain_test._device_plan(rgb.shape[1], rgb.shape[0], 256, False) if rgb is not None else None
                 if plan is not None:
                     return adain_test._device_resize(rgb[None], rgb.shape[1], rgb.shape[0], plan)[0]
@@ -236,7 +235,7 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
     styles = [stf(Image.open(p).convert("RGB")).unsqueeze(0) for p in style_paths]
     # stylise (sharded), resize to the target resolution on the owning rank, gather; the recurrence needs the flows: rank 0 only
     post = None
-    if intermediate_jpeg and jpeg_on_device and on_gpu:
+    if intermediate_jpeg and routes.encode_on_device and on_gpu:
         post = engine.jpeg_roundtrip_u8                        # the same bytes, computed where the batch is (adain_jpeg_roundtrip_u8)
     elif intermediate_jpeg:
         post = lambda u8: torch.from_numpy(_jpeg_roundtrip(u8.cpu().numpy())).to(u8.device)
@@ -254,11 +253,11 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
     if rank == 0:
         # the frame-to-frame recurrence (video/utils.py:355-368) on the gathered frames; every frame is written by a worker
         # thread behind an asynchronous device -> host copy while the next frame's warp / blend is already running
-        sink = jobs.FileSink(engine.device, jpeg_on_device=jpeg_on_device, jpeg_options=jpeg_options)
+        sink = jobs.FileSink(engine.device, jpeg=routes)
         try:
             n, h, w, _ = frames_u8.shape
             prev = None
-            flow_of = _flow_source(content_dir, names, flow_method, (w, h), frames_u8.device, cancel_flag) if n > 1 else None
+            flow_of = _flow_source(content_dir, names, flow_method, (w, h), frames_u8.device, cancel_flag, routes) if n > 1 else None
             for i, name in enumerate(names):
                 if cancel_flag is not None and cancel_flag.is_set():
                     print("Stopping style transfer...")
@@ -289,19 +288,18 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
                              depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False, preserve_color=False,
                              jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None):
     """One style for the whole clip (video/utils.py:244-295); keyword-only extras: a ready ``engine``, checkpoint paths,
-    precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``jpeg_on_device`` (.jpg / .jpeg frames are
-    encoded on the device: the same files, jobs.FileSink; with ``intermediate_jpeg`` and the engine on a GPU the intermediate round trip
-    runs on the device too, ``AdaINEngine.jpeg_roundtrip_u8``: the same frames), ``preserve_color`` (every frame is styled with
-    ``coral(style, frame)``, adain_inference's colour preservation, on the device), ``jpeg_decode_on_device`` (baseline .jpg / .jpeg
-    frames are decoded on the device, for the stylisation and for the package's own flow providers: ``rt.jpeg_decode_rgb_file``, the
-    pixels PIL decodes; any other file, and the sharded feeder of jobs.py, keep PIL), ``jpeg_decode_progressive`` (acts with
-    ``jpeg_decode_on_device=True``: progressive frames are decoded on the device too; without it they keep PIL as before),
-    ``jpeg_options`` (``jobs.JpegOptions``, or a (quality, subsampling, optimize) tuple: how the .jpg / .jpeg OUTPUT frames are saved, by
-    PIL or with ``jpeg_on_device`` by the device encoder, the same files; default: Pillow's default save.  The ``intermediate_jpeg``
-    round trip stays the reference's default save, quality 75 and 4:2:0, whatever the options)."""
-    return _run(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
-                engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color,
-                jpeg_decode_on_device=jpeg_decode_on_device, jpeg_decode_progressive=jpeg_decode_progressive, jpeg_options=jpeg_options)
+    precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``preserve_color`` (every frame is styled with
+    ``coral(style, frame)``, adain_inference's colour preservation, on the device) and the call's ``rt.JpegRoutes``, field by field:
+    ``jpeg_on_device`` (.jpg / .jpeg frames are encoded on the device: the same files, jobs.FileSink; with ``intermediate_jpeg`` and the
+    engine on a GPU that round trip runs on the device too, ``AdaINEngine.jpeg_roundtrip_u8``: the same frames), ``jpeg_decode_on_device``
+    (baseline .jpg / .jpeg frames are decoded on the device, for the stylisation and for the package's flow providers: the pixels PIL
+    decodes; any other file, and the sharded feeder of jobs.py, keep PIL), ``jpeg_decode_progressive`` (with it only: progressive frames
+    too), ``jpeg_options`` (``jobs.JpegOptions`` or a (quality, subsampling, optimize) tuple: how the .jpg / .jpeg OUTPUT frames are saved
+    on either route, default Pillow's default save; the ``intermediate_jpeg`` round trip stays quality 75 and 4:2:0 whatever they say)."""
+    routes = rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options)
+    with _routes_scope(routes):
+        return _run_clip(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
+                         engine, vgg_str, decoder_str, depth_maps, group, preserve_color, 0, intermediate_jpeg, routes)
 
 
 def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
@@ -312,17 +310,17 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
                                    jpeg_decode_progressive=False, jpeg_options=None):
     """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372).
     ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics.
-    ``jpeg_on_device``: as in ``apply_style_transfer_ada``, the output files and, with ``intermediate_jpeg``, the intermediate round trip.
     ``crossfade_frames`` (0, the default: the hard cuts of the reference): the styles cross-fade in feature space over that many
     frames centred on each switch (``jobs.style_crossfade``, style interpolation on the device; at most 16 styles, and not with
-    ``preserve_color``).  ``jpeg_decode_on_device``, ``jpeg_decode_progressive``: as in ``apply_style_transfer_ada``.
-    ``jpeg_options``: as in ``apply_style_transfer_ada`` - the output files only, never the ``intermediate_jpeg`` round trip."""
+    ``preserve_color``).  ``jpeg_on_device``, ``jpeg_decode_on_device``, ``jpeg_decode_progressive``, ``jpeg_options``: the call's
+    ``rt.JpegRoutes``, as in ``apply_style_transfer_ada`` (the options: the output files only, never the ``intermediate_jpeg`` round trip)."""
     style_images = sorted(os.listdir(style_dir))
     if len(style_images) == 0:
         raise ValueError("No style images found in the style directory.")
     if crossfade_frames and preserve_color:
         raise ValueError("crossfade_frames mixes the styles of a frame; preserve_color is not supported with it")
-    return _run(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
-                cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, intermediate_jpeg, group, jpeg_on_device, preserve_color,
-                int(crossfade_frames), jpeg_decode_on_device=jpeg_decode_on_device, jpeg_decode_progressive=jpeg_decode_progressive,
-                jpeg_options=jpeg_options)
+    routes = rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options)
+    with _routes_scope(routes):
+        return _run_clip(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
+                         cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, group, preserve_color, int(crossfade_frames),
+                         intermediate_jpeg, routes)

@@ -446,4 +446,33 @@ def test_the_video_path_writes_the_same_frames_with_the_device_decoder(rt, engin
         out[on] = [(tmp_path / f"out_{int(on)}" / f"frame_{i:04d}.jpg").read_bytes() for i in range(3)]
         assert entry.calls == (0 if not on else 2 + (2 if provider == "own" else 0))       # the progressive frame never reaches the device decoder
     assert out[True] == out[False]
-    assert video._jpeg_decode_on_device is False
+    assert video._routes.get() == rt.JpegRoutes()          # the clip's routes are call-scoped: the default again afterwards
+
+
+def test_a_wrapper_of_the_own_provider_decodes_on_the_device_during_the_clip(rt, engine, tmp_path, monkeypatch):
+    """Two colour baseline frames and a caller's wrapper around the package's Farneback provider - by identity not one of the package's
+    own, so it is called per pair: identical files with the flag off and on, and with it on the wrapper's two frames are decoded on the
+    device as well (the clip's setting reaches a provider that is called during the clip)."""
+    from applied_image_processing_amd import video
+
+    cdir = tmp_path / "frames"
+    cdir.mkdir()
+    for i in range(2):
+        Image.fromarray(u8img(710 + i, 64, 96)).save(cdir / f"frame_{i:04d}.jpg", quality=95)
+    Image.fromarray(u8img(750, 96, 96)).save(tmp_path / "style.png")
+    depth_maps = [synth.smooth_depth(480 + i, 64, 96) for i in range(2)]
+    entry = Counter(rt.jpeg_decode_batch)
+    monkeypatch.setattr(rt, "jpeg_decode_batch", entry)
+    out = {}
+    for on in (False, True):
+        video.set_flow_provider(lambda prev, cur, resolution, method: video.device_flow_provider(prev, cur, resolution, method))
+        try:
+            video.apply_style_transfer_ada(str(cdir), str(tmp_path / "style.png"), str(tmp_path / f"out_{int(on)}"), alpha=0.7, target_resolution=(96, 64),
+                                           engine=engine, depth_maps=depth_maps, jpeg_decode_on_device=on)
+        finally:
+            video.set_flow_provider(None)
+        out[on] = [(tmp_path / f"out_{int(on)}" / f"frame_{i:04d}.jpg").read_bytes() for i in range(2)]
+        print(f"jpeg_decode_on_device={on}: {entry.calls} device decodes")
+        assert entry.calls == (4 if on else 0)          # two frames in Frames, two in the provider's one pair
+    assert out[True] == out[False]
+    assert video._routes.get() == rt.JpegRoutes()

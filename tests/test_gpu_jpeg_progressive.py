@@ -406,7 +406,7 @@ def test_the_video_path_writes_the_same_frames(rt, engine, tmp_path, monkeypatch
         out[on] = [(tmp_path / f"out_{int(on)}" / f"frame_{i:04d}.jpg").read_bytes() for i in range(3)]
         assert (new.calls, old.calls) == ((1, 2) if on else (0, 0))
     assert out[True] == out[False]
-    assert video._jpeg_decode_on_device is False and video._jpeg_decode_progressive is False
+    assert video._routes.get() == rt.JpegRoutes()          # the clip's routes are call-scoped: the default again afterwards
 
 
 def test_jpeg_decode_rgb_file_takes_a_progressive_file_only_with_the_keyword(rt, tmp_path):
