@@ -3,7 +3,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "../../include/adain_hip.h"
 #include "common.h"
 
 namespace adain {
@@ -33,7 +32,6 @@ static const Layer ENC[8] = {{64, 64, 1, 0},   {64, 128, 0, 0},  {128, 128, 1, 0
 static const Layer DEC[8] = {{512, 256, 0, 0}, {256, 256, 0, 1}, {256, 256, 0, 0}, {256, 256, 0, 0},
                              {256, 128, 0, 0}, {128, 128, 0, 1}, {128, 64, 0, 0},  {64, 64, 0, 1}};
 
-static size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 constexpr size_t FIRST_W = 2 * 14 * 64, FIRST_B = 64, LAST_W = 8 * 64 * 4, LAST_B = 3;
 
 // The generic 3x3 layers run - and the library only contains - the Winograd F(4,3) x F(2,3) kernels (csrc/conv_wino4.hip).  The direct
@@ -43,35 +41,31 @@ static size_t form_floats(const Layer& l) { return (size_t)l.cin * l.cout * 24 *
 
 // packed layout: [first w][first b] (encoder) then per generic layer [w in the form the schedules launch][b], then [last w][last b]
 // (decoder), every block 256-B aligned: 75 MB for the two networks in the F(4,3) x F(2,3) form (only that form is packed and kept).
-struct Offsets { size_t w[8], b[8], first_b, last_w, last_b, total; };
+struct Offsets { size_t w[8], b[8], first_b, last_w, last_b, total; };      // floats
 static Offsets offsets(const Layer* L) {
     Offsets f{};
-    size_t o = 0;
+    Carve c;
+    auto floats = [&c](size_t n) { return c.take(n * sizeof(float)) / sizeof(float); };
     if (L == ENC) {
-        o += align64(FIRST_W);
-        f.first_b = o;
-        o += align64(FIRST_B);
+        floats(FIRST_W);            // at 0
+        f.first_b = floats(FIRST_B);
     }
     for (int i = 0; i < 8; ++i) {
-        f.w[i] = o;
-        o += align64(form_floats(L[i]));
-        f.b[i] = o;
-        o += align64(L[i].cout);
+        f.w[i] = floats(form_floats(L[i]));
+        f.b[i] = floats(L[i].cout);
     }
     if (L == DEC) {
-        f.last_w = o;
-        o += align64(LAST_W);
-        f.last_b = o;
-        o += align64(LAST_B);
+        f.last_w = floats(LAST_W);
+        f.last_b = floats(LAST_B);
     }
-    f.total = o;
+    f.total = c.at / sizeof(float);
     return f;
 }
 
 // a bias into its block of a packed network; the block's padding (the decoder's last bias: 3 floats of 64) is zeroed, so that a pack
 // writes every float the *_packed_floats query counts and the caller's buffer needs no preparation
 static int copy_bias(const float* src, float* dst, int n, hipStream_t s) {
-    const size_t pad = align64((size_t)n) - (size_t)n;
+    const size_t pad = align256((size_t)n * sizeof(float)) / sizeof(float) - (size_t)n;
     if (hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
         (pad && hipMemsetAsync(dst + n, 0, pad * sizeof(float), s) != hipSuccess)) {
         set_error("bias copy failed: %s", hipGetErrorString(hipGetLastError()));
@@ -154,7 +148,8 @@ struct NetPlan {
     size_t out_img[8];                                 // output floats per image
     int buf[8];
     int in_buf;                                        // where layer 0's input is
-    size_t buf_floats[2], slab_floats;                 // 64-float aligned
+    size_t o_buf[2], o_slab, total;                    // the workspace [A][B][slabs]: offsets and size in bytes
+    size_t slab_floats;                                // the slab block's floats, rounded up to its 256 bytes; 0: no layer would be split
     // the call's tensors (place()): the two buffers, the slab workspace, the caller's input / output tensor
     float* bufs[2];
     float* slab;
@@ -181,17 +176,19 @@ static NetPlan net_plan(const Layer* L, int n, int h, int w) {
         in_buf = p.buf[l];
         h = p.Ho[l]; w = p.Wo[l];
     }
-    p.buf_floats[BUF_A] = align64(mx[BUF_A]);
-    p.buf_floats[BUF_B] = align64(mx[BUF_B]);
-    p.slab_floats = align64(slab);
+    Carve c;
+    p.o_buf[BUF_A] = c.take(mx[BUF_A] * sizeof(float));
+    p.o_buf[BUF_B] = c.take(mx[BUF_B] * sizeof(float));
+    p.o_slab = c.take(slab * sizeof(float));      // the slabs themselves are the kernel's own layout (wino4_split_floats), left alone
+    p.total = c.at;
+    p.slab_floats = (p.total - p.o_slab) / sizeof(float);
     return p;
 }
-static size_t workspace_floats(const NetPlan& p) { return p.buf_floats[BUF_A] + p.buf_floats[BUF_B] + p.slab_floats; }
-// carves the plan's workspace from ws; in / out: the caller's tensors the network reads / writes in place of a buffer
-static void place(NetPlan& p, float* ws, const float* in, float* out) {
-    p.bufs[BUF_A] = ws;
-    p.bufs[BUF_B] = ws + p.buf_floats[BUF_A];
-    p.slab = p.bufs[BUF_B] + p.buf_floats[BUF_B];
+// the plan's workspace is at ws; in / out: the caller's tensors the network reads / writes in place of a buffer
+static void place(NetPlan& p, char* ws, const float* in, float* out) {
+    p.bufs[BUF_A] = (float*)(ws + p.o_buf[BUF_A]);
+    p.bufs[BUF_B] = (float*)(ws + p.o_buf[BUF_B]);
+    p.slab = (float*)(ws + p.o_slab);
     p.in = in;
     p.out = out;
 }
@@ -227,7 +224,7 @@ static int run_layers(const NetPlan& p, int l0, int l1, int i0, int k, const flo
 
 size_t adain_encode_workspace_bytes(int n, int h, int w) {
     if (n < 1 || h < 1 || w < 1) return 0;
-    return workspace_floats(net_plan(ENC, n, h, w)) * sizeof(float);
+    return net_plan(ENC, n, h, w).total;
 }
 
 size_t adain_encode_multi_workspace_bytes(int count, const int* n, const int* h, const int* w) {
@@ -239,7 +236,7 @@ size_t adain_encode_multi_workspace_bytes(int count, const int* n, const int* h,
 
 size_t adain_decode_workspace_bytes(int n, int hc, int wc) {
     if (n < 1 || hc < 1 || wc < 1) return 0;
-    return workspace_floats(net_plan(DEC, n, hc, wc)) * sizeof(float);
+    return net_plan(DEC, n, hc, wc).total;
 }
 
 // ---- batches of WIDE frames: which layers run frame by frame -----------------------------------------------------------------------
@@ -304,18 +301,18 @@ static int encode_impl(int count, const void* const* images, int u8, float* cons
             return ADAIN_EINVAL;
         }
     }
-    if (ws_bytes < adain_encode_multi_workspace_bytes(count, n, h, w)) { set_error("encode: workspace too small"); return ADAIN_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     const Offsets f = offsets(ENC);
     NetPlan p[MAX_CONV_SEGS];
     SplitWs split[MAX_CONV_SEGS];
-    float* base = (float*)workspace;
+    size_t need = 0;                // the batches' workspaces, one behind the other
     for (int i = 0; i < count; ++i) {
         p[i] = net_plan(ENC, n[i], h[i], w[i]);
-        place(p[i], base, nullptr, feats[i]);
-        base += workspace_floats(p[i]);
+        place(p[i], (char*)workspace + need, nullptr, feats[i]);
+        need += p[i].total;
         split[i] = split_ws(p[i]);
     }
+    RET_IF(check_workspace("encode", workspace, ws_bytes, need, 1));
     record(ev, 0, s);
     // a batch of large frames (one tensor pair, no per-layer events wanted): conv_first and its big layers frame by frame, see above,
     // leaving every image's tensors where the layer-major loop behind expects them
@@ -378,11 +375,11 @@ static int decode_impl(const float* feat, float* image, uint8_t* image_u8, const
                        int wc, void* const* ev, adain_stream_t stream) {
     if (!feat || (!image && !image_u8) || !packed || !workspace) { set_error("decode: null pointer"); return ADAIN_EINVAL; }
     if (n < 1 || hc < 2 || wc < 2) { set_error("decode: feature map %dx%d too small (needs >= 2x2)", hc, wc); return ADAIN_EINVAL; }
-    if (ws_bytes < adain_decode_workspace_bytes(n, hc, wc)) { set_error("decode: workspace too small"); return ADAIN_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     const Offsets f = offsets(DEC);
     NetPlan p = net_plan(DEC, n, hc, wc);
-    place(p, (float*)workspace, feat, nullptr);
+    RET_IF(check_workspace("decode", workspace, ws_bytes, p.total, 1));
+    place(p, (char*)workspace, feat, nullptr);
     record(ev, 0, s);
     // a batch of large frames: the leading small layers over the whole batch, then everything from the first big layer to the
     // image frame by frame, images last to first (see enc_frame_major_layers, frame_pass_is_safe)
@@ -421,7 +418,7 @@ int adain_mean_std(const float* feat, int nhwc, int n, int c, int hw, float eps,
 // s_mean / s_std [style_n][c] of the single-style entries: one row for every frame, or one row per frame
 static int blend_single(const float* x, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const float* s_mean,
                         const float* s_std, int style_n, const BlendTerm& blend, float* out, adain_stream_t stream) {
-    if (style_n != 1 && style_n != n) { set_error("adain_blend: style batch %d must be 1 or %d", style_n, n); return -1; }
+    if (style_n != 1 && style_n != n) { set_error("adain_blend: style batch %d must be 1 or %d", style_n, n); return ADAIN_EINVAL; }
     return launch_adain_blend(x, nhwc, n, c, hw, c_mean, c_std, StyleTerm{s_mean, s_std, 1, style_n == n, nullptr, 1, 1}, blend, out, (hipStream_t)stream);
 }
 
@@ -540,11 +537,8 @@ int adain_jpeg_encode_opt_u8_bytes(int n, int h, int w, int c, int sampling, int
 static int jpeg_encode(const char* who, const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out, size_t out_stride,
                        int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream) {
     if (!src || !out || !lengths || !workspace) { set_error("%s: null pointer", who); return ADAIN_EINVAL; }
-    size_t need_stride = 0, need_ws = 0;
-    if (jpeg_encode_bytes(who, n, h, w, c, sampling, optimize, &need_stride, &need_ws)) return ADAIN_EINVAL;
-    if (workspace_bytes < need_ws) { set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need_ws); return ADAIN_EINVAL; }
-    const int rc = launch_jpeg_encode_u8(who, src, n, h, w, c, quality, sampling, optimize, out, out_stride, lengths, workspace, (hipStream_t)stream);
-    return rc == -1 ? ADAIN_EINVAL : rc;
+    if (jpeg_encode_bytes(who, n, h, w, c, sampling, optimize, nullptr, nullptr)) return ADAIN_EINVAL;
+    return launch_jpeg_encode_u8(who, src, n, h, w, c, quality, sampling, optimize, out, out_stride, lengths, workspace, workspace_bytes, (hipStream_t)stream);
 }
 int adain_jpeg_encode_opt_u8(const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out, size_t out_stride,
                              int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream) {
@@ -565,13 +559,10 @@ int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_
 int adain_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, size_t workspace_bytes,
                             adain_stream_t stream) {
     if (!src || !dst || !workspace) { set_error("jpeg_roundtrip_u8: null pointer"); return ADAIN_EINVAL; }
-    size_t need_ws = 0;
-    if (jpeg_roundtrip_bytes(n, h, w, c, &need_ws)) return ADAIN_EINVAL;
-    if (workspace_bytes < need_ws) { set_error("jpeg_roundtrip_u8: workspace too small (%zu < %zu bytes)", workspace_bytes, need_ws); return ADAIN_EINVAL; }
+    if (jpeg_roundtrip_bytes(n, h, w, c, nullptr)) return ADAIN_EINVAL;       // the shape, before its product is used
     const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst, bytes = (uintptr_t)n * h * w * c;
     if (a < b + bytes && b < a + bytes) { set_error("jpeg_roundtrip_u8: dst overlaps src"); return ADAIN_EINVAL; }
-    const int rc = launch_jpeg_roundtrip_u8(src, n, h, w, c, quality, dst, workspace, (hipStream_t)stream);
-    return rc == -1 ? ADAIN_EINVAL : rc;
+    return launch_jpeg_roundtrip_u8(src, n, h, w, c, quality, dst, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int adain_jpeg_decode_restart_u8_bytes(int n, int h, int w, int c, int sampling, int restart_interval, size_t max_segment_bytes, int chunk_bits,
@@ -582,9 +573,8 @@ int adain_jpeg_decode_restart_u8(const uint8_t* files, size_t files_bytes, const
                                  const uint64_t* segment_offsets, const uint32_t* segment_lengths, uint8_t* dst, int32_t* record, void* workspace,
                                  size_t workspace_bytes, int chunk_bits, adain_stream_t stream) {
     if (!files || !blobs || !segment_offsets || !segment_lengths || !dst || !record || !workspace) { set_error("jpeg_decode_u8: null pointer"); return ADAIN_EINVAL; }
-    const int rc = launch_jpeg_decode_u8(files, files_bytes, blobs, n, h, w, c, sampling, restart_interval, segment_offsets, segment_lengths, dst, record, workspace,
-                                         workspace_bytes, chunk_bits, (hipStream_t)stream);
-    return rc == -1 ? ADAIN_EINVAL : rc;
+    return launch_jpeg_decode_u8(files, files_bytes, blobs, n, h, w, c, sampling, restart_interval, segment_offsets, segment_lengths, dst, record, workspace,
+                                 workspace_bytes, chunk_bits, (hipStream_t)stream);
 }
 // the entries from before restart intervals: the ones above at 0
 int adain_jpeg_decode_u8_bytes(int n, int h, int w, int c, int sampling, size_t max_segment_bytes, int chunk_bits, size_t* workspace_bytes) {
@@ -607,9 +597,8 @@ int adain_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, c
         set_error("jpeg_decode_progressive_u8: null pointer");
         return ADAIN_EINVAL;
     }
-    const int rc = launch_jpeg_decode_progressive_u8(files, files_bytes, blobs, n, h, w, c, sampling, nscans, scans, segment_offsets, segment_lengths, dst, record,
-                                                     workspace, workspace_bytes, chunk_bits, (hipStream_t)stream);
-    return rc == -1 ? ADAIN_EINVAL : rc;
+    return launch_jpeg_decode_progressive_u8(files, files_bytes, blobs, n, h, w, c, sampling, nscans, scans, segment_offsets, segment_lengths, dst, record,
+                                             workspace, workspace_bytes, chunk_bits, (hipStream_t)stream);
 }
 
 int adain_nhwc_to_nchw(const float* in, float* out, int n, int c, int hw, adain_stream_t stream) {
@@ -622,45 +611,53 @@ int adain_nchw_to_nhwc(const float* in, float* out, int n, int c, int hw, adain_
 }
 
 // ---- one sub-batch of the batch callers in one call ---------------------------------------------------------------------------
-// Workspace of adain_stylize_u8, carved in this order (every block 256-byte aligned):
+// Workspace of adain_stylize_u8: the blocks in the order they are taken, offsets in bytes.  A block the call does not use has no
+// bytes and the offset ABSENT, which block() turns into a null pointer - how the blend knows that there is no depth map.
+constexpr size_t ABSENT = ~(size_t)0;
+static size_t take(Carve& c, size_t bytes) { return bytes ? c.take(bytes) : ABSENT; }
 struct StylizePlan {
     int hc, wc, H8, W8;               // relu4_1 map; decoder output size (8hc x 8wc)
     int identity;                     // mask, decoder output and frame share one size: the fused composite + quantise tail
     int mask_only;                    // decoder output and frame share one size, the mask has another: the same tail sampling the mask
-    size_t conv, feat, stat, stats_ws, pmap, pmap_ws, img, content, mask_f, mask_r, sty_r, comp, total;   // floats (conv / *_ws: bytes / 4)
+    size_t conv_bytes, stats_ws_bytes, pmap_ws_bytes;      // the workspaces handed on to the encoder / decoder, mean_std and strength_map
+    size_t conv, f, g, c_mean, c_std, stats_ws, pmap, pmap_ws, img, content, mask_f, mask_r, sty_r, comp, total;
 };
 static StylizePlan stylize_plan(int n, int h, int w, int use_depth, int mask_n, int mask_c, int mask_h, int mask_w, int mask_is_float) {
     StylizePlan p{};
     adain_encoded_size(h, w, &p.hc, &p.wc);
     p.H8 = 8 * p.hc; p.W8 = 8 * p.wc;
-    const size_t enc = adain_encode_workspace_bytes(n, h, w), dec = adain_decode_workspace_bytes(n, p.hc, p.wc);
-    p.conv = align64(((enc > dec ? enc : dec) + 3) / 4);
-    p.feat = align64((size_t)n * p.hc * p.wc * 512);
-    p.stat = align64((size_t)n * 512);
-    p.stats_ws = align64((mean_std_workspace_bytes(1, n, 512, p.hc * p.wc) + 3) / 4);
-    if (use_depth) {
-        p.pmap = align64((size_t)n * p.hc * p.wc);
-        p.pmap_ws = align64((strength_map_workspace_bytes(p.hc, p.wc) + 3) / 4);
-    }
-    p.img = align64((size_t)n * 3 * p.H8 * p.W8);
     if (mask_n > 0) {
         p.identity = mask_h == h && mask_w == w && p.H8 == h && p.W8 == w;
         p.mask_only = !p.identity && p.H8 == h && p.W8 == w;
-        if (!p.identity && !p.mask_only) {
-            p.content = align64((size_t)n * 3 * h * w);
-            p.mask_f = mask_is_float ? 0 : align64((size_t)mask_n * mask_c * mask_h * mask_w);
-            p.mask_r = (mask_h == h && mask_w == w) ? 0 : align64((size_t)mask_n * mask_c * h * w);
-            p.sty_r = (p.H8 == h && p.W8 == w) ? 0 : align64((size_t)n * 3 * h * w);
-            p.comp = align64((size_t)n * 3 * h * w);
-        }
     }
-    p.total = p.conv + 2 * p.feat + 2 * p.stat + p.stats_ws + p.pmap + p.pmap_ws + p.img + p.content + p.mask_f + p.mask_r + p.sty_r + p.comp;
+    const bool general = mask_n > 0 && !p.identity && !p.mask_only;      // the composite on float images at the frame's size
+    const size_t enc = adain_encode_workspace_bytes(n, h, w), dec = adain_decode_workspace_bytes(n, p.hc, p.wc);
+    const size_t map = (size_t)n * p.hc * p.wc * sizeof(float), frame = (size_t)n * 3 * h * w * sizeof(float);
+    p.conv_bytes = enc > dec ? enc : dec;
+    p.stats_ws_bytes = mean_std_workspace_bytes(1, n, 512, p.hc * p.wc);
+    p.pmap_ws_bytes = use_depth ? strength_map_workspace_bytes(p.hc, p.wc) : 0;
+    Carve c;
+    p.conv = take(c, p.conv_bytes);
+    p.f = take(c, 512 * map);
+    p.g = take(c, 512 * map);
+    p.c_mean = take(c, (size_t)n * 512 * sizeof(float));
+    p.c_std = take(c, (size_t)n * 512 * sizeof(float));
+    p.stats_ws = take(c, p.stats_ws_bytes);
+    p.pmap = take(c, use_depth ? map : 0);
+    p.pmap_ws = take(c, p.pmap_ws_bytes);
+    p.img = take(c, (size_t)n * 3 * p.H8 * p.W8 * sizeof(float));
+    p.content = take(c, general ? frame : 0);
+    p.mask_f = take(c, general && !mask_is_float ? (size_t)mask_n * mask_c * mask_h * mask_w * sizeof(float) : 0);
+    p.mask_r = take(c, general && !(mask_h == h && mask_w == w) ? (size_t)mask_n * mask_c * h * w * sizeof(float) : 0);
+    p.sty_r = take(c, general && !(p.H8 == h && p.W8 == w) ? frame : 0);
+    p.comp = take(c, general ? frame : 0);
+    p.total = c.at;
     return p;
 }
 
 size_t adain_stylize_u8_workspace_bytes(int n, int h, int w, int use_depth, int mask_n, int mask_c, int mask_h, int mask_w, int mask_is_float) {
     if (n < 1 || h < 9 || w < 9) return 0;
-    return stylize_plan(n, h, w, use_depth, mask_n, mask_c, mask_h, mask_w, mask_is_float).total * sizeof(float);
+    return stylize_plan(n, h, w, use_depth, mask_n, mask_c, mask_h, mask_w, mask_is_float).total;
 }
 
 void adain_stylize_u8_out_size(int h, int w, int has_mask, int* oh, int* ow) {
@@ -697,42 +694,30 @@ static int stylize_impl(const uint8_t* frames, int n, int h, int w, const float*
         return ADAIN_EINVAL;
     }
     const StylizePlan p = stylize_plan(n, h, w, depth_maps != nullptr, mask_n, mask_c, mask_h, mask_w, mask_is_float);
-    if (ws_bytes < p.total * sizeof(float)) { set_error("stylize_u8: workspace too small (%zu < %zu bytes)", ws_bytes, p.total * sizeof(float)); return ADAIN_EINVAL; }
+    RET_IF(check_workspace("stylize_u8", workspace, ws_bytes, p.total, 1));
     hipStream_t s = (hipStream_t)stream;
-    float* at = (float*)workspace;
-    auto take = [&at](size_t floats) { float* r = at; at += floats; return floats ? r : (float*)nullptr; };
-    float* conv = take(p.conv);
-    float* f = take(p.feat);
-    float* g = take(p.feat);
-    float* c_mean = take(p.stat);
-    float* c_std = take(p.stat);
-    float* stats_ws = take(p.stats_ws);
-    float* pmap = take(p.pmap);
-    float* pmap_ws = take(p.pmap_ws);
-    float* img = take(p.img);
-    float* content_f = take(p.content);
-    float* mask_f = take(p.mask_f);
-    float* mask_r = take(p.mask_r);
-    float* sty_r = take(p.sty_r);
-    float* comp = take(p.comp);
+    auto block = [workspace](size_t offset) { return offset == ABSENT ? nullptr : (float*)((char*)workspace + offset); };
+    float *conv = block(p.conv), *f = block(p.f), *g = block(p.g), *c_mean = block(p.c_mean), *c_std = block(p.c_std), *stats_ws = block(p.stats_ws);
+    float *pmap = block(p.pmap), *pmap_ws = block(p.pmap_ws), *img = block(p.img);
+    float *content_f = block(p.content), *mask_f = block(p.mask_f), *mask_r = block(p.mask_r), *sty_r = block(p.sty_r), *comp = block(p.comp);
     const int hw_c = p.hc * p.wc;
     const BlendTerm blend{alpha, one_minus_alpha, pmap, n};      // pmap: null without depth maps
     if (check_adain_blend("stylize_u8", 1, n, 512, hw_c, style, blend)) return ADAIN_EINVAL;     // the blend's own rules, on the relu4_1 map's size
 
     // vgg(content) with ToTensor inside the first layer (test.py:203-204, :57 / :76), calc_mean_std(content_f) (function.py:4-12)
-    RET_IF(adain_encode_u8(frames, f, enc_packed, conv, p.conv * sizeof(float), n, h, w, nullptr, stream));
-    RET_IF(launch_mean_std(f, 1, n, 512, hw_c, 1e-5f, c_mean, c_std, stats_ws, p.stats_ws * sizeof(float), s));
+    RET_IF(adain_encode_u8(frames, f, enc_packed, conv, p.conv_bytes, n, h, w, nullptr, stream));
+    RET_IF(launch_mean_std(f, 1, n, 512, hw_c, 1e-5f, c_mean, c_std, stats_ws, p.stats_ws_bytes, s));
     if (depth_maps)         // compute_stylization_strength_map per frame (test.py:66-69)
         for (int i = 0; i < n; ++i) {
             RET_IF(launch_strength_map(depth_maps[i], depth_h[i], depth_w[i], p.hc, p.wc, depth_offset, depth_prominence, pmap + (size_t)i * hw_c,
-                                       pmap_ws, p.pmap_ws * sizeof(float), s));
+                                       pmap_ws, p.pmap_ws_bytes, s));
         }
     // AdaIN * (1 - P) + content_f * P (test.py:70) or AdaIN * alpha + content_f * (1 - alpha) (test.py:79-80), AdaIN of the one style,
     // the frame's own, or the weighted mix of k (test_video.py:36-44)
     RET_IF(launch_adain_blend(f, 1, n, 512, hw_c, c_mean, c_std, style, blend, g, s));
     if (mask_n == 0 && ((uintptr_t)out_u8 & 3) == 0)        // decoder with save_image's quantiser inside its last layer (test.py:71 / :81, :243-244): the finished uint8 frames
-        return decode_impl(g, nullptr, out_u8, dec_packed, conv, p.conv * sizeof(float), n, p.hc, p.wc, nullptr, stream);
-    RET_IF(adain_decode(g, img, dec_packed, conv, p.conv * sizeof(float), n, p.hc, p.wc, nullptr, stream));     // test.py:71 / :81
+        return decode_impl(g, nullptr, out_u8, dec_packed, conv, p.conv_bytes, n, p.hc, p.wc, nullptr, stream);
+    RET_IF(adain_decode(g, img, dec_packed, conv, p.conv_bytes, n, p.hc, p.wc, nullptr, stream));     // test.py:71 / :81
     if (mask_n == 0) return launch_quantize_u8(img, out_u8, n, 3, p.H8, p.W8, s);                                // test.py:243-244 (unaligned output)
     if (p.identity)         // both F.interpolate calls of test.py:227-234 are identities: composite + quantise in one pass
         return launch_composite_quantize_u8(frames, img, mask, mask_is_float, mask_c, mask_n, out_u8, n, h * w, s);

@@ -34,7 +34,6 @@ inline char* adain_env_unset(const char*) { return nullptr; }
 #include <rocprim/rocprim.hpp>
 #undef getenv
 
-#include "../../include/adain_hip.h"
 #include "common.h"
 #include "device_utils.h"
 
@@ -281,8 +280,6 @@ __global__ __launch_bounds__(CT_THREADS) void colour_match_kernel(Images im, int
     }
 }
 
-size_t a256(size_t b) { return (b + 255) / 256 * 256; }
-
 int moment_blocks(size_t hw) {
     const size_t per_block = (size_t)CT_THREADS * CT_PIX_PER_THREAD;
     const size_t b = (hw + per_block - 1) / per_block;
@@ -304,17 +301,16 @@ bool layout(int h, int w, Layout* l) {
     const size_t hw = (size_t)h * w;
     size_t tmp = 0;
     if (rocprim::radix_sort_keys(nullptr, tmp, (const double*)nullptr, (double*)nullptr, hw) != hipSuccess) return false;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += a256(bytes); return at; };
-    l->record = take(sizeof(adain_colour_record));
-    l->partial = take((size_t)moment_blocks(hw) * 2 * CT_MOMENTS * sizeof(double));
-    l->keys_fg = take(hw * sizeof(double));
-    l->keys_bg = take(hw * sizeof(double));
-    l->sorted_fg = take(hw * sizeof(double));
-    l->sorted_bg = take(hw * sizeof(double));
+    Carve c;
+    l->record = c.take(sizeof(adain_colour_record));
+    l->partial = c.take((size_t)moment_blocks(hw) * 2 * CT_MOMENTS * sizeof(double));
+    l->keys_fg = c.take(hw * sizeof(double));
+    l->keys_bg = c.take(hw * sizeof(double));
+    l->sorted_fg = c.take(hw * sizeof(double));
+    l->sorted_bg = c.take(hw * sizeof(double));
     l->sort_tmp_bytes = tmp;
-    l->sort_tmp = take(tmp);
-    l->total = o;
+    l->sort_tmp = c.take(tmp);
+    l->total = c.at;
     return true;
 }
 
@@ -322,7 +318,8 @@ int run(const Images& im, uint8_t* out, int h, int w, void* workspace, hipStream
     Layout l;
     if (!im.a || !im.b || !out || !workspace) { set_error("%s: null pointer", what); return ADAIN_EINVAL; }
     if (!layout(h, w, &l)) { set_error("%s: unsupported size %d x %d", what, h, w); return ADAIN_EINVAL; }
-    if ((uintptr_t)workspace % 8) { set_error("%s: the workspace must be 8-byte aligned", what); return ADAIN_EINVAL; }
+    // the entries carry no byte count: the caller's buffer is taken to have the layout's size, its pointer and alignment are checked
+    if (int rc = check_workspace(what, workspace, l.total, l.total, 8)) return rc;
     char* ws = (char*)workspace;
     auto* rec = (adain_colour_record*)(ws + l.record);
     double* partial = (double*)(ws + l.partial);

@@ -5,7 +5,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-struct adain_tvl1_params;   // include/adain_hip.h
+#include "../../include/adain_hip.h"
 
 namespace adain {
 
@@ -62,6 +62,25 @@ struct ConvSegs {
 
 // thread-local error text for adain_last_error()
 void set_error(const char* fmt, ...);
+
+// ---- scratch memory of a call ("Workspaces") ------------------------------------------------------------------------------
+// Every block of a workspace, a pyramid or a packed network starts on a multiple of 256 bytes.
+constexpr size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// Lays blocks out one behind the other: take() returns the block's offset and moves on to the next multiple of 256 bytes, so that
+// `at` is the size of everything taken so far.  A call's layout function is the one place that takes its blocks; its size query
+// returns the layout's total and its launcher reads the layout's offsets.
+struct Carve {
+    size_t at = 0;
+    size_t take(size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; }
+};
+// The one refusal of a launcher's workspace: null, shorter than its layout's total, or (align > 1) not aligned for the layout's types.
+inline int check_workspace(const char* who, const void* ptr, size_t have_bytes, size_t need_bytes, size_t align) {
+    if (!ptr) set_error("%s: the workspace is a null pointer", who);
+    else if (have_bytes < need_bytes) set_error("%s: workspace too small (%zu < %zu bytes)", who, have_bytes, need_bytes);
+    else if (align > 1 && (uintptr_t)ptr % align) set_error("%s: the workspace must be %zu-byte aligned", who, align);
+    else return 0;
+    return ADAIN_EINVAL;
+}
 
 // launchers (conv_edge.hip)
 int launch_pack_conv_first(const float* w0, const float* b0, const float* w1, const float* b1, float* packed,
@@ -179,10 +198,10 @@ int launch_tvl1_flow(const float* const* prev, const float* const* next, int npa
 // (tests/jpeg_options_ref.py); (2, 0) is the default file.  who: the entry's name in front of its error messages
 int jpeg_encode_bytes(const char* who, int n, int h, int w, int c, int sampling, int optimize, size_t* out_stride, size_t* workspace_bytes);
 int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out,
-                          size_t out_stride, int32_t* lengths, void* workspace, hipStream_t s);
+                          size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes, hipStream_t s);
 // the pixels Pillow decodes from that file, without the file (the rules: top of jpeg.hip, tests/jpeg_decode_ref.py)
 int jpeg_roundtrip_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
-int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, hipStream_t s);
+int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, size_t workspace_bytes, hipStream_t s);
 // jpeg_decode.hip: a baseline file's entropy-coded segment -> the pixels Pillow decodes from the file (the rules: top of jpeg_decode.hip,
 // tests/jpeg_file_ref.py)
 // restart_interval: MCUs per restart interval, 0 for a file without one (tests/jpeg_restart_ref.py)
@@ -206,7 +225,7 @@ inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("%s: %s", what, hipGetErrorString(e));
-        return -2;
+        return ADAIN_ELAUNCH;
     }
     return 0;
 }

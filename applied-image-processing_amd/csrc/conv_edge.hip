@@ -411,14 +411,14 @@ int launch_pack_conv_last(const float* w, float* p, hipStream_t s) {
 
 int launch_conv_first(const void* img, int u8, float* out, const float* packed, const float* bias, int n, int H, int W,
                       hipStream_t s) {
-    if (H < 2 || W < 2 || n < 1) { set_error("conv_first: H, W must be >= 2, got %dx%d", H, W); return -1; }
-    if ((size_t)W * 256 * 8 >= 0x7ffffff0ULL) { set_error("conv_first: eight 64-channel rows of width %d reach 2 GiB", W); return -1; }
-    if ((size_t)H * W * 12 >= 0x7ffffff0ULL) { set_error("conv_first: an image of %d x %d pixels reaches 2 GiB as three float planes", H, W); return -1; }
+    if (H < 2 || W < 2 || n < 1) { set_error("conv_first: H, W must be >= 2, got %dx%d", H, W); return ADAIN_EINVAL; }
+    if ((size_t)W * 256 * 8 >= 0x7ffffff0ULL) { set_error("conv_first: eight 64-channel rows of width %d reach 2 GiB", W); return ADAIN_EINVAL; }
+    if ((size_t)H * W * 12 >= 0x7ffffff0ULL) { set_error("conv_first: an image of %d x %d pixels reaches 2 GiB as three float planes", H, W); return ADAIN_EINVAL; }
     const int tx = (W + 31) / 32, ty = (H + 7) / 8;
     const long long ntiles = (long long)tx * ty * n;
-    if (ntiles > 0x7fffffffLL) { set_error("conv_first: bad grid"); return -1; }
+    if (ntiles > 0x7fffffffLL) { set_error("conv_first: bad grid"); return ADAIN_EINVAL; }
     const int cus = device_cu_count();
-    if (cus <= 0) { set_error("conv_first: device query failed"); return -1; }
+    if (cus <= 0) { set_error("conv_first: device query failed"); return ADAIN_EINVAL; }
     const long long per_cu = 3;                                            // 3 workgroups per CU walk the tiles (same box: 2: 85 us, 3: 80, 4: 90)
     const long long grid = ntiles < per_cu * cus ? ntiles : per_cu * cus;
     if (u8) hipLaunchKernelGGL(conv_first_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, img, out, packed, bias, H, W, tx, ty, (int)ntiles);
@@ -429,12 +429,12 @@ int launch_conv_first(const void* img, int u8, float* out, const float* packed, 
 int launch_conv_last(const float* in, float* out_f32, const float* packed, const float* bias, int n, int H, int W,
                      hipStream_t s, uint8_t* out_u8) {
     void* const out = out_u8 ? (void*)out_u8 : (void*)out_f32;
-    if (H < 2 || W < 2 || n < 1) { set_error("conv_last: H, W must be >= 2, got %dx%d", H, W); return -1; }
-    if ((size_t)W * 256 * 18 >= 0x7ffffff0ULL) { set_error("conv_last: eighteen 64-channel rows of width %d reach 2 GiB", W); return -1; }
+    if (H < 2 || W < 2 || n < 1) { set_error("conv_last: H, W must be >= 2, got %dx%d", H, W); return ADAIN_EINVAL; }
+    if ((size_t)W * 256 * 18 >= 0x7ffffff0ULL) { set_error("conv_last: eighteen 64-channel rows of width %d reach 2 GiB", W); return ADAIN_EINVAL; }
     const int tx = (W + TW - 1) / TW, ty = (H + CL_TH - 1) / CL_TH;
-    if ((long long)tx * ty * n > 0x7fffffffLL) { set_error("conv_last: bad grid"); return -1; }
+    if ((long long)tx * ty * n > 0x7fffffffLL) { set_error("conv_last: bad grid"); return ADAIN_EINVAL; }
     const dim3 grid((unsigned)(tx * ty * n));
-    if (out_u8 && ((W & 3) || ((uintptr_t)out_u8 & 3))) { set_error("conv_last: the uint8 form needs W %% 4 == 0 and a 4-byte aligned image"); return -1; }
+    if (out_u8 && ((W & 3) || ((uintptr_t)out_u8 & 3))) { set_error("conv_last: the uint8 form needs W %% 4 == 0 and a 4-byte aligned image"); return ADAIN_EINVAL; }
     if (out_u8) hipLaunchKernelGGL(conv_last_kernel<true>, grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
     else hipLaunchKernelGGL(conv_last_kernel<false>, grid, dim3(256), 0, s, in, out, packed, bias, H, W, tx, ty);
     return check_launch("conv_last");

@@ -822,7 +822,7 @@ __global__ __launch_bounds__(256) void splitk_combine_kernel(const float* __rest
 }
 
 int launch_pack_wino4(const float* w, float* p, int cin, int cout, hipStream_t s) {
-    if (cin % 8 || cout % 32) { set_error("pack_wino4: cin %% 8 or cout %% 32 != 0 (%d, %d)", cin, cout); return -1; }
+    if (cin % 8 || cout % 32) { set_error("pack_wino4: cin %% 8 or cout %% 32 != 0 (%d, %d)", cin, cout); return ADAIN_EINVAL; }
     const size_t total = (size_t)cin * cout * 24;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(pack_wino4_kernel, dim3(blocks), dim3(256), 0, s, w, p, cin, cout);
@@ -830,7 +830,7 @@ int launch_pack_wino4(const float* w, float* p, int cin, int cout, hipStream_t s
 }
 
 int launch_pack_up2x_poly(const float* w, float* p, int cin, int cout, hipStream_t s) {
-    if (cin % 8 || cout % 32 || cin < 8 || cout < 32) { set_error("pack_up2x_poly: cin %% 8 or cout %% 32 != 0 (%d, %d)", cin, cout); return -1; }
+    if (cin % 8 || cout % 32 || cin < 8 || cout < 32) { set_error("pack_up2x_poly: cin %% 8 or cout %% 32 != 0 (%d, %d)", cin, cout); return ADAIN_EINVAL; }
     const size_t total = (size_t)cin * cout * 96;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(pack_up2x_poly_kernel, dim3(blocks), dim3(256), 0, s, w, p, cin, cout);
@@ -843,24 +843,24 @@ static bool wino4_big(const ConvArgs& a) {
 }
 
 static int check_wino4_shape(const ConvArgs& a, int src_mode) {
-    if (a.cin % W4_KR || a.cin < W4_KR) { set_error("conv3x3_wino4: cin %d not a multiple of 16", a.cin); return -1; }
-    if (a.cout % 32) { set_error("conv3x3_wino4: cout %d not a multiple of 32", a.cout); return -1; }
-    if (a.H < 2 || a.W < 2 || a.n < 1) { set_error("conv3x3_wino4: H, W must be >= 2, got %dx%d", a.H, a.W); return -1; }
+    if (a.cin % W4_KR || a.cin < W4_KR) { set_error("conv3x3_wino4: cin %d not a multiple of 16", a.cin); return ADAIN_EINVAL; }
+    if (a.cout % 32) { set_error("conv3x3_wino4: cout %d not a multiple of 32", a.cout); return ADAIN_EINVAL; }
+    if (a.H < 2 || a.W < 2 || a.n < 1) { set_error("conv3x3_wino4: H, W must be >= 2, got %dx%d", a.H, a.W); return ADAIN_EINVAL; }
     // 32-bit offsets address a band of at most 18 source / 16 output rows (the taller tile geometry) from a per-tile descriptor: the
     // image itself may be of any size
     if ((size_t)a.Ws * a.cin * 4 * 18 >= 0x7ffffff0ULL || (size_t)a.W * a.cout * 4 * 16 >= 0x7ffffff0ULL) {
         set_error("conv3x3_wino4: a band of eighteen %d-channel source rows or sixteen %d-channel output rows of width %d reaches 2 GiB",
                   a.cin, a.cout, a.W);
-        return -1;
+        return ADAIN_EINVAL;
     }
-    if ((size_t)a.cin * a.cout * 96 >= 0xffffffffULL) { set_error("conv3x3_wino4: packed weights must stay below 4 GiB"); return -1; }
+    if ((size_t)a.cin * a.cout * 96 >= 0xffffffffULL) { set_error("conv3x3_wino4: packed weights must stay below 4 GiB"); return ADAIN_EINVAL; }
     if (src_mode == SRC_DIRECT) {
-        if (a.Hs != a.H || a.Ws != a.W) { set_error("conv3x3_wino4: direct mode needs Hs==H, Ws==W"); return -1; }
+        if (a.Hs != a.H || a.Ws != a.W) { set_error("conv3x3_wino4: direct mode needs Hs==H, Ws==W"); return ADAIN_EINVAL; }
     } else if (src_mode == SRC_UP2X) {
-        if (a.H != 2 * a.Hs || a.W != 2 * a.Ws) { set_error("conv3x3_wino4: up2x mode needs H==2Hs, W==2Ws"); return -1; }
+        if (a.H != 2 * a.Hs || a.W != 2 * a.Ws) { set_error("conv3x3_wino4: up2x mode needs H==2Hs, W==2Ws"); return ADAIN_EINVAL; }
     } else {
         set_error("conv3x3_wino4: unsupported src_mode %d", src_mode);
-        return -1;
+        return ADAIN_EINVAL;
     }
     return 0;
 }
@@ -942,6 +942,8 @@ static long long wino4_items(int n, int H, int W, int cout, int* geo_out) {
     if (geo_out) *geo_out = geo;
     return geo_tiles(geo, n, H, W) * (cout / 32);
 }
+// The slab workspace is S equal slabs of one output tensor each, nothing else: it has no layout value of its own, and its size is the
+// kernel's (not rounded to 256 bytes; the networks round the block they keep it in, api.hip's net_plan).
 size_t wino4_split_floats(int n, int H, int W, int cin, int cout) {
     if (n < 1 || H < 2 || W < 2 || cin % W4_KR || cout % 32) return 0;
     const int S = wino4_ksplit(wino4_items(n, H, W, cout, nullptr), cin);
@@ -970,7 +972,7 @@ static int w4_list(const ConvArgs& layer, const ConvSeg* segs, int count, int sr
     t.big = false;
     for (int i = 0; i < count; ++i) {
         set_seg(t.a, segs[i]);
-        if (check_wino4_shape(t.a, src_mode)) return -1;
+        if (check_wino4_shape(t.a, src_mode)) return ADAIN_EINVAL;
         t.big = t.big || wino4_big(t.a);
     }
     t.geo = t.big ? 0 : pick_geo(segs, count);
@@ -994,14 +996,14 @@ int launch_conv3x3_wino4(const ConvArgs& a0, int src_mode, hipStream_t s, SplitW
     layer.ksplit = 1; layer.cin_sub = layer.cin; layer.slab_stride = 0;
     const ConvSeg seg{layer.in, layer.out, layer.n, layer.H, layer.W, layer.Hs, layer.Ws, 0, 0, 0};
     W4List t;
-    if (w4_list(layer, &seg, 1, src_mode, t)) return -1;
+    if (w4_list(layer, &seg, 1, src_mode, t)) return ADAIN_EINVAL;
     const ConvArgs& a = t.a;
     const long long blocks = t.items;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) { set_error("conv3x3_wino4: bad grid %lld", blocks); return -1; }
+    if (blocks <= 0 || blocks > 0x7fffffffLL) { set_error("conv3x3_wino4: bad grid %lld", blocks); return ADAIN_EINVAL; }
     // persistent form whenever the launch has at least two tiles per resident workgroup (and cin is at most 2^20): +2-3 % on most
     // layer shapes, +1.1 % on the config-2 step
     const long long pgrid = persistent_grid();
-    if (pgrid <= 0) { set_error("conv3x3_wino4: device query failed"); return -1; }
+    if (pgrid <= 0) { set_error("conv3x3_wino4: device query failed"); return ADAIN_EINVAL; }
     const bool persist = a.cin <= (1 << 20) && a.cin >= 2 * W4_KR && pgrid >= 8 && blocks >= 2 * pgrid;
     const int items = (int)blocks;
     if (persist) {
@@ -1011,7 +1013,7 @@ int launch_conv3x3_wino4(const ConvArgs& a0, int src_mode, hipStream_t s, SplitW
     const int S = (split.slab && !t.big) ? wino4_ksplit(blocks, a.cin) : 1;
     if (S > 1) {
         const size_t slab = (size_t)a.n * a.H * a.W * a.cout;
-        if (split.floats < (size_t)S * slab) { set_error("conv3x3_wino4: split workspace too small (%zu < %zu floats)", split.floats, (size_t)S * slab); return -1; }
+        if (int rc = check_workspace("conv3x3_wino4 (cin split)", split.slab, split.floats * sizeof(float), (size_t)S * slab * sizeof(float), 1)) return rc;
         ConvArgs p = a;                  // first half: S workgroups per (tile, channel tile), partial sums into the slabs
         p.ksplit = S; p.cin_sub = a.cin / S; p.slab_stride = slab;
         p.out = split.slab; p.relu = 0; p.pool_out = 0;
@@ -1029,14 +1031,14 @@ int launch_conv3x3_wino4(const ConvArgs& a0, int src_mode, hipStream_t s, SplitW
 }
 
 int launch_conv3x3_wino4_multi(const ConvArgs& layer, const ConvSeg* segs, int count, int src_mode, hipStream_t s, const SplitWs* split) {
-    if (count < 1 || count > MAX_CONV_SEGS) { set_error("conv3x3_wino4_multi: 1..%d segments, got %d", MAX_CONV_SEGS, count); return -1; }
+    if (count < 1 || count > MAX_CONV_SEGS) { set_error("conv3x3_wino4_multi: 1..%d segments, got %d", MAX_CONV_SEGS, count); return ADAIN_EINVAL; }
     for (int i = 0; i < count; ++i)
-        if (!segs[i].in || !segs[i].out) { set_error("conv3x3_wino4_multi: null pointer in segment %d", i); return -1; }
+        if (!segs[i].in || !segs[i].out) { set_error("conv3x3_wino4_multi: null pointer in segment %d", i); return ADAIN_EINVAL; }
     W4List t;
-    if (w4_list(layer, segs, count, src_mode, t)) return -1;
-    if (t.items > 0x7fffffffLL) { set_error("conv3x3_wino4_multi: too many tiles"); return -1; }
+    if (w4_list(layer, segs, count, src_mode, t)) return ADAIN_EINVAL;
+    if (t.items > 0x7fffffffLL) { set_error("conv3x3_wino4_multi: too many tiles"); return ADAIN_EINVAL; }
     const long long pgrid = persistent_grid();
-    if (pgrid <= 0) { set_error("conv3x3_wino4: device query failed"); return -1; }
+    if (pgrid <= 0) { set_error("conv3x3_wino4: device query failed"); return ADAIN_EINVAL; }
     if (count == 1 || layer.cin < 2 * W4_KR || pgrid < 8 || t.items < 2 * pgrid) {
         // not enough work for a shared persistent list (or a single segment): one launch per segment
         ConvArgs a = layer;
@@ -1059,19 +1061,19 @@ namespace adain {
 int launch_conv3x3_up2x_poly(const ConvArgs& a0, hipStream_t s) {
     ConvArgs a = a0;
     a.ksplit = 1; a.cin_sub = a.cin; a.slab_stride = 0;
-    if (a.cin % W4_KR || a.cin < W4_KR) { set_error("conv3x3_up2x_poly: cin %d not a multiple of 16", a.cin); return -1; }
-    if (a.cout % 32 || a.cout < 32) { set_error("conv3x3_up2x_poly: cout %d not a multiple of 32", a.cout); return -1; }
+    if (a.cin % W4_KR || a.cin < W4_KR) { set_error("conv3x3_up2x_poly: cin %d not a multiple of 16", a.cin); return ADAIN_EINVAL; }
+    if (a.cout % 32 || a.cout < 32) { set_error("conv3x3_up2x_poly: cout %d not a multiple of 32", a.cout); return ADAIN_EINVAL; }
     if (a.n < 1 || a.Hs < 1 || a.Ws < 1 || a.H != 2 * a.Hs || a.W != 2 * a.Ws) {
         set_error("conv3x3_up2x_poly: needs n >= 1, a source of at least 1x1 and H == 2 Hs, W == 2 Ws (got %d: %dx%d -> %dx%d)", a.n, a.Hs, a.Ws, a.H, a.W);
-        return -1;
+        return ADAIN_EINVAL;
     }
-    if (a.pool_out) { set_error("conv3x3_up2x_poly: no fused output pool"); return -1; }
+    if (a.pool_out) { set_error("conv3x3_up2x_poly: no fused output pool"); return ADAIN_EINVAL; }
     // per-tile descriptors address a band of 19 source / 32 output rows with 32-bit offsets
     if ((size_t)a.Ws * a.cin * 4 * 19 >= 0x7ffffff0ULL || (size_t)a.W * a.cout * 4 * 32 >= 0x7ffffff0ULL) {
         set_error("conv3x3_up2x_poly: a band of 19 source or 32 output rows reaches 2 GiB");
-        return -1;
+        return ADAIN_EINVAL;
     }
-    if ((size_t)a.cin * a.cout * 384 >= 0xffffffffULL) { set_error("conv3x3_up2x_poly: packed weights must stay below 4 GiB"); return -1; }
+    if ((size_t)a.cin * a.cout * 384 >= 0xffffffffULL) { set_error("conv3x3_up2x_poly: packed weights must stay below 4 GiB"); return ADAIN_EINVAL; }
     const bool big = wino4_big(a);
     a.tiles_x = (a.Ws + W4P::TILE_W - 1) / W4P::TILE_W;
     a.tiles_y = (a.Hs + W4P::TILE_H - 1) / W4P::TILE_H;
@@ -1080,7 +1082,7 @@ int launch_conv3x3_up2x_poly(const ConvArgs& a0, hipStream_t s) {
     m.s[0] = ConvSeg{a.in, a.out, a.n, a.H, a.W, a.Hs, a.Ws, a.tiles_x, a.tiles_y, 0};
     m.ctg = walk_group(a.cin, 4 * a.cout);           // virtual channel tiles 4 ct + phase: the phases of a channel tile share halos
     const long long blocks = (long long)a.tiles_x * a.tiles_y * (4 * a.cout / 32) * a.n;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) { set_error("conv3x3_up2x_poly: bad grid %lld", blocks); return -1; }
+    if (blocks <= 0 || blocks > 0x7fffffffLL) { set_error("conv3x3_up2x_poly: bad grid %lld", blocks); return ADAIN_EINVAL; }
     // One tile per workgroup: the persistent form's loop-carried next-tile state does not fit beside nine staging items per thread
     // (the build spills; the one-tile form holds 246 registers and no scratch).
     const dim3 g((unsigned)blocks);

@@ -23,7 +23,6 @@
 // adain_u8_to_f32's value, what the encoder's first layer reads.  The output is NOT clamped (the reference does not clamp).
 // A side of fewer than two pixels or with a channel of zero variance (the reference divides by zero: NaNs) sets the record's status
 // and leaves the pair's output a plain copy of its style.
-#include "../../include/adain_hip.h"
 #include "common.h"
 #include "device_utils.h"
 
@@ -307,8 +306,6 @@ __global__ __launch_bounds__(CO_THREADS) void coral_apply_kernel(const void* __r
     }
 }
 
-size_t a256(size_t b) { return (b + 255) / 256 * 256; }
-
 struct Layout {
     int blocks_s, blocks_c;
     size_t records, partial_s, partial_c, total;
@@ -320,12 +317,11 @@ bool layout(int n, int style_n, int hs, int ws, int hc, int wc, Layout* l) {
     if ((size_t)hs * ws > 0x3fffffffULL || (size_t)hc * wc > 0x3fffffffULL) return false;
     l->blocks_s = moment_blocks((size_t)hs * ws);
     l->blocks_c = moment_blocks((size_t)hc * wc);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += a256(bytes); return at; };
-    l->records = take((size_t)n * sizeof(adain_coral_record));
-    l->partial_s = take((size_t)style_n * l->blocks_s * CO_SUMS * 8);
-    l->partial_c = take((size_t)n * l->blocks_c * CO_SUMS * 8);
-    l->total = o;
+    Carve c;
+    l->records = c.take((size_t)n * sizeof(adain_coral_record));
+    l->partial_s = c.take((size_t)style_n * l->blocks_s * CO_SUMS * 8);
+    l->partial_c = c.take((size_t)n * l->blocks_c * CO_SUMS * 8);
+    l->total = c.at;
     return true;
 }
 
@@ -352,8 +348,7 @@ int launch_coral(const void* style, int style_is_u8, int style_n, int hs, int ws
                   n, hc, wc, style_n, hs, ws);
         return ADAIN_EINVAL;
     }
-    if (ws_bytes < l.total) { set_error("coral: workspace too small (%zu < %zu bytes)", ws_bytes, l.total); return ADAIN_EINVAL; }
-    if ((uintptr_t)workspace % 8) { set_error("coral: the workspace must be 8-byte aligned"); return ADAIN_EINVAL; }
+    if (int rc = check_workspace("coral", workspace, ws_bytes, l.total, 8)) return rc;
     if ((!style_is_u8 && (uintptr_t)style % 4) || (!content_is_u8 && (uintptr_t)content % 4) || (uintptr_t)out % 4) {
         set_error("coral: float images must be 4-byte aligned");
         return ADAIN_EINVAL;

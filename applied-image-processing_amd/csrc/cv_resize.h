@@ -13,8 +13,6 @@
 
 namespace adain {
 
-inline size_t align64f(size_t floats) { return (floats + 63) & ~(size_t)63; }
-
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // cv::resize's choice for (ssize -> dsize) with the source-per-destination scales sx, sy

@@ -31,7 +31,6 @@
 // OpenCV's, one by one, and the flow equals the float32 mode of tests/farneback_ref.py bit for bit (fused multiply-adds are no less
 // accurate on average, but on narrow frames, where every pixel solves nearly the same ill-conditioned 2 x 2 system, they moved the
 // flow by up to 4.5e-5 px, more than twice the float32 restatement's own distance from float64 on some fixtures).
-#include "../../include/adain_hip.h"
 #include "common.h"
 #include "cv_resize.h"
 
@@ -47,17 +46,18 @@ struct FbPoly { float g[FB_MAX_POLY_N + 1], xg[FB_MAX_POLY_N + 1], xxg[FB_MAX_PO
 
 struct FbLevel { int w, h, ksize; double scale, sigma; size_t img_off, r_off; };   // offsets in floats into the pyramid
 
-// the level schedule; returns the effective `levels` (the coarsest k) or -1 when the parameters are refused
+// the level schedule; returns the effective `levels` (the coarsest k) or ADAIN_EINVAL (< 0) when the parameters are refused.  The
+// single source of a pyramid's layout: every level's image and its polynomial expansion start on a multiple of 256 bytes.
 static int fb_schedule(int h, int w, double pyr_scale, int levels, FbLevel* L, size_t* pyramid_floats) {
-    if (h < 1 || w < 1 || !(pyr_scale > 0.0 && pyr_scale < 1.0) || levels < 0) return -1;
+    if (h < 1 || w < 1 || !(pyr_scale > 0.0 && pyr_scale < 1.0) || levels < 0) return ADAIN_EINVAL;
     int k = 0;
     double scale = 1.0;
     for (k = 0; k < levels; ++k) {
         scale *= pyr_scale;
         if (w * scale < 32 || h * scale < 32) break;
     }
-    if (k + 1 > FB_MAX_LEVELS) return -1;
-    size_t off = 0;
+    if (k + 1 > FB_MAX_LEVELS) return ADAIN_EINVAL;
+    Carve c;
     for (int i = 0; i <= k; ++i) {
         double s = 1.0;
         for (int j = 0; j < i; ++j) s *= pyr_scale;
@@ -69,12 +69,10 @@ static int fb_schedule(int h, int w, double pyr_scale, int levels, FbLevel* L, s
         L[i].ksize = ks;
         L[i].w = (int)nearbyint(w * s);
         L[i].h = (int)nearbyint(h * s);
-        L[i].img_off = off;
-        off += align64f((size_t)L[i].w * L[i].h);
-        L[i].r_off = off;
-        off += align64f((size_t)L[i].w * L[i].h * 5);
+        L[i].img_off = c.take((size_t)L[i].w * L[i].h * sizeof(float)) / sizeof(float);
+        L[i].r_off = c.take((size_t)L[i].w * L[i].h * 5 * sizeof(float)) / sizeof(float);
     }
-    if (pyramid_floats) *pyramid_floats = off;
+    if (pyramid_floats) *pyramid_floats = c.at / sizeof(float);
     return k;
 }
 
@@ -414,26 +412,39 @@ size_t farneback_pyramid_bytes(int h, int w, double pyr_scale, int levels) {
     return fb_schedule(h, w, pyr_scale, levels, L, &floats) < 0 ? 0 : floats * sizeof(float);
 }
 
-size_t farneback_workspace_bytes(int h, int w) {
-    if (h < 1 || w < 1) return 0;
-    const size_t hw = align64f((size_t)h * w);
-    return (2 * 5 + 2 * 2) * hw * sizeof(float);    // flow: M ping-pong + two level flows; expand: the row pass (hw floats)
+// The one workspace of both calls (offsets in bytes), in planes of a full-size frame rounded up to 256 bytes.  The flow call: the
+// ping-pong matrices M (5 planes each) and the two level flows F (2 planes each).  The expand call: its row pass's buffer (1 plane),
+// which is the front of M[0].
+struct FbLayout { size_t o_M[2], o_F[2], o_rows, total; };
+static FbLayout fb_layout(int h, int w) {
+    const size_t plane = align256((size_t)h * w * sizeof(float));
+    FbLayout l{};
+    Carve c;
+    for (size_t& o : l.o_M) o = c.take(5 * plane);
+    for (size_t& o : l.o_F) o = c.take(2 * plane);
+    l.o_rows = l.o_M[0];
+    l.total = c.at;
+    return l;
 }
 
-static bool fb_common_checks(int h, int w, double pyr_scale, int levels, const void* ws, size_t ws_bytes, const char* what) {
+size_t farneback_workspace_bytes(int h, int w) {
+    if (h < 1 || w < 1) return 0;
+    return fb_layout(h, w).total;
+}
+
+// the checks both calls share; *layout: the workspace they passed
+static bool fb_common_checks(int h, int w, double pyr_scale, int levels, const void* ws, size_t ws_bytes, const char* what, FbLayout* layout) {
     if (!fb_check_frame(h, w, what)) return false;
     if (!(pyr_scale > 0.0 && pyr_scale < 1.0)) { set_error("%s: pyr_scale must be in (0, 1), got %g", what, pyr_scale); return false; }
     if (levels < 0) { set_error("%s: levels must be >= 0", what); return false; }
-    if (!ws || ws_bytes < farneback_workspace_bytes(h, w)) {
-        set_error("%s: workspace of %zu bytes, %zu needed", what, ws_bytes, farneback_workspace_bytes(h, w));
-        return false;
-    }
-    return true;
+    *layout = fb_layout(h, w);
+    return check_workspace(what, ws, ws_bytes, layout->total, 1) == 0;
 }
 
 int launch_farneback_expand(const uint8_t* gray, int h, int w, double pyr_scale, int levels, int poly_n, double poly_sigma,
                             float* pyramid, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (!fb_common_checks(h, w, pyr_scale, levels, ws, ws_bytes, "farneback_expand")) return ADAIN_EINVAL;
+    FbLayout lay;
+    if (!fb_common_checks(h, w, pyr_scale, levels, ws, ws_bytes, "farneback_expand", &lay)) return ADAIN_EINVAL;
     if (poly_n != 5 && poly_n != 7) { set_error("farneback_expand: poly_n must be 5 or 7, got %d", poly_n); return ADAIN_EINVAL; }
     FbLevel L[FB_MAX_LEVELS];
     const int k = fb_schedule(h, w, pyr_scale, levels, L, nullptr);
@@ -445,7 +456,7 @@ int launch_farneback_expand(const uint8_t* gray, int h, int w, double pyr_scale,
         }
     FbPoly P;
     fb_poly_coeffs(poly_n, poly_sigma, P);
-    float* tmp = (float*)ws;
+    float* tmp = (float*)((char*)ws + lay.o_rows);
     FbTaps T;                                 // 2 KB: passed by value into the launches below
     for (int i = 0; i <= k; ++i) {
         const FbLevel& l = L[i];
@@ -466,7 +477,8 @@ int launch_farneback_expand(const uint8_t* gray, int h, int w, double pyr_scale,
 
 int launch_farneback_flow(const float* pyr_prev, const float* pyr_next, int h, int w, double pyr_scale, int levels, int winsize,
                           int iterations, int flags, float* flow_out, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (!fb_common_checks(h, w, pyr_scale, levels, ws, ws_bytes, "farneback_flow")) return ADAIN_EINVAL;
+    FbLayout lay;
+    if (!fb_common_checks(h, w, pyr_scale, levels, ws, ws_bytes, "farneback_flow", &lay)) return ADAIN_EINVAL;
     if (flags != 0) {
         set_error("farneback_flow: only flags = 0 is supported (no OPTFLOW_USE_INITIAL_FLOW, no OPTFLOW_FARNEBACK_GAUSSIAN), got %d", flags);
         return ADAIN_EINVAL;
@@ -479,9 +491,9 @@ int launch_farneback_flow(const float* pyr_prev, const float* pyr_next, int h, i
     FbLevel L[FB_MAX_LEVELS];
     const int k = fb_schedule(h, w, pyr_scale, levels, L, nullptr);
     if (k < 0) { set_error("farneback_flow: more than %d pyramid levels", FB_MAX_LEVELS); return ADAIN_EINVAL; }
-    const size_t hw = align64f((size_t)h * w);
-    float* Mb[2] = {(float*)ws, (float*)ws + 5 * hw};
-    float* Fb[2] = {(float*)ws + 10 * hw, (float*)ws + 12 * hw};
+    char* base = (char*)ws;
+    float* Mb[2] = {(float*)(base + lay.o_M[0]), (float*)(base + lay.o_M[1])};
+    float* Fb[2] = {(float*)(base + lay.o_F[0]), (float*)(base + lay.o_F[1])};
     const int m = winsize / 2;
     const double bscale = 1. / ((double)winsize * winsize);
     const size_t lds = (size_t)IT_TY * (IT_TX + 2 * m) * 5 * sizeof(double);

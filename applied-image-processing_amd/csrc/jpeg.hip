@@ -129,21 +129,21 @@ Plan make_plan(int n, int h, int w, int c, int sampling = 2, bool optimize = fal
     p.stream_words = (p.max_bytes + 3) / 4 + 4;
     p.chunks = (p.max_bytes + CHUNK - 1) / CHUNK;
     p.out_stride = HOST_T.hdr_len[c == 3] + 2 * p.max_bytes + 2;
-    size_t at = 0, N = (size_t)n;
-    auto take = [&](size_t bytes) { size_t o = at; at = align256(at + bytes); return o; };
-    p.o_coef = take(N * p.nblk * 64 * sizeof(int16_t));
-    p.o_bits = take(N * p.nblk * sizeof(uint32_t));
-    p.o_off = take(N * p.nblk * sizeof(uint64_t));
-    p.o_total = take(N * sizeof(uint64_t));
-    p.o_stream = take(N * p.stream_words * sizeof(uint32_t));
-    p.o_ffcnt = take(N * p.chunks * sizeof(uint32_t));
-    p.o_ffoff = take(N * p.chunks * sizeof(uint32_t));
-    p.o_fftotal = take(N * sizeof(uint32_t));
+    const size_t N = (size_t)n;
+    Carve ws;
+    p.o_coef = ws.take(N * p.nblk * 64 * sizeof(int16_t));
+    p.o_bits = ws.take(N * p.nblk * sizeof(uint32_t));
+    p.o_off = ws.take(N * p.nblk * sizeof(uint64_t));
+    p.o_total = ws.take(N * sizeof(uint64_t));
+    p.o_stream = ws.take(N * p.stream_words * sizeof(uint32_t));
+    p.o_ffcnt = ws.take(N * p.chunks * sizeof(uint32_t));
+    p.o_ffoff = ws.take(N * p.chunks * sizeof(uint32_t));
+    p.o_fftotal = ws.take(N * sizeof(uint32_t));
     if (optimize) {
-        p.o_hist = take(N * SLOTS * 256 * sizeof(uint64_t));
-        p.o_huff = take(N * SLOTS * sizeof(HuffSlot));
+        p.o_hist = ws.take(N * SLOTS * 256 * sizeof(uint64_t));
+        p.o_huff = ws.take(N * SLOTS * sizeof(HuffSlot));
     }
-    p.total = at;
+    p.total = ws.at;
     return p;
 }
 
@@ -716,14 +716,16 @@ constexpr int MERGE_PX = 512;           // pixels of one output row per workgrou
 // The file's MCUs are 2 x 2 luma blocks (grey: one block); the n-frame arrays of the workspace are the coefficients, then the planes
 struct RoundtripPlan {
     DecPlanes g;
-    size_t o_planes, total;             // workspace offsets (bytes)
+    size_t o_coef, o_planes, total;     // workspace offsets (bytes)
 };
 
 RoundtripPlan make_roundtrip_plan(int n, int h, int w, int c) {
     RoundtripPlan p{};
     p.g = make_planes(h, w, c, c == 3 ? 2 : 1, c == 3 ? 2 : 1);
-    p.o_planes = align256((size_t)n * p.g.nblk * 64 * sizeof(int16_t));
-    p.total = p.o_planes + align256((size_t)n * p.g.stride);
+    Carve ws;
+    p.o_coef = ws.take((size_t)n * p.g.nblk * 64 * sizeof(int16_t));
+    p.o_planes = ws.take((size_t)n * p.g.stride);
+    p.total = ws.at;
     return p;
 }
 
@@ -811,7 +813,7 @@ int jpeg_encode_bytes(const char* who, int n, int h, int w, int c, int sampling,
     const char* bad = check_shape(n, h, w, c, 75);
     if (!bad) bad = check_options(sampling, optimize);
     if (!bad && make_plan(n, h, w, c, sampling, optimize).out_stride > (size_t)INT32_MAX) bad = "a worst-case file beyond 2^31 - 1 bytes (lengths are int32)";
-    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, sampling %d, optimize %d)", who, bad, n, h, w, c, sampling, optimize); return -1; }
+    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, sampling %d, optimize %d)", who, bad, n, h, w, c, sampling, optimize); return ADAIN_EINVAL; }
     const Plan p = make_plan(n, h, w, c, sampling, optimize);
     if (out_stride) *out_stride = p.out_stride;
     if (workspace_bytes) *workspace_bytes = p.total;
@@ -841,14 +843,15 @@ void launch_entropy_stage(int stage, bool optimize, unsigned grid, int n, const 
 // sampling 2, optimize 0: the default file, in 8 launches.  Other samplings change the transform and the scan order only; optimize adds
 // the clearing of the counters (a memset), the histogram and the table stage in front of count: 10 launches, whatever n.
 int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out,
-                          size_t out_stride, int32_t* lengths, void* workspace, hipStream_t s) {
+                          size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const char* bad = check_shape(n, h, w, c, quality);
     if (!bad) bad = check_options(sampling, optimize);
-    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, quality %d, sampling %d, optimize %d)", who, bad, n, h, w, c, quality, sampling, optimize); return -1; }
+    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, quality %d, sampling %d, optimize %d)", who, bad, n, h, w, c, quality, sampling, optimize); return ADAIN_EINVAL; }
     const Plan p = make_plan(n, h, w, c, sampling, optimize);
-    if (p.out_stride > (size_t)INT32_MAX) { set_error("%s: %d x %d x %d: a worst-case file beyond 2^31 - 1 bytes", who, h, w, c); return -1; }
-    if (out_stride < p.out_stride) { set_error("%s: out_stride %zu below the %zu of the size query", who, out_stride, p.out_stride); return -1; }
-    if ((uintptr_t)workspace % 8 || (uintptr_t)lengths % 4) { set_error("%s: the workspace must be 8-byte and lengths 4-byte aligned", who); return -1; }
+    if (p.out_stride > (size_t)INT32_MAX) { set_error("%s: %d x %d x %d: a worst-case file beyond 2^31 - 1 bytes", who, h, w, c); return ADAIN_EINVAL; }
+    if (out_stride < p.out_stride) { set_error("%s: out_stride %zu below the %zu of the size query", who, out_stride, p.out_stride); return ADAIN_EINVAL; }
+    if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, 8)) return rc;
+    if ((uintptr_t)lengths % 4) { set_error("%s: lengths must be 4-byte aligned", who); return ADAIN_EINVAL; }
     char* ws = (char*)workspace;
     int16_t* coef = (int16_t*)(ws + p.o_coef);
     uint32_t* bits = (uint32_t*)(ws + p.o_bits);
@@ -863,7 +866,7 @@ int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int
     const Geometry g{c, p.mw, p.bw, p.bh, p.nblk};
     const size_t blocks = (size_t)n * p.nblk;
     // gridDim.y and .z are limited to 65535: h, w <= 65535 keep the block rows below that; the frames ride in z
-    if (n > 65535 || (blocks + 3) / 4 > 0x7fffffffull) { set_error("%s: batch of %d frames too large for one call", who, n); return -1; }
+    if (n > 65535 || (blocks + 3) / 4 > 0x7fffffffull) { set_error("%s: batch of %d frames too large for one call", who, n); return ADAIN_EINVAL; }
     if (c != 3)
         jpeg_transform_grey_kernel<<<dim3((p.bw + GREY_PER_WG - 1) / GREY_PER_WG, p.bh, n), GREY_PER_WG * 8, 0, s>>>(src, h, w, quality, coef, p.bw, p.nblk);
     else if (p.vs == 2)
@@ -879,7 +882,7 @@ int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int
         else launch_entropy_stage<1, 1>(stage, optimize, grid, n, coef, bits, off, stream, p.stream_words, g, blocks, hist, huff, s);
     };
     if (optimize) {
-        if (hipMemsetAsync(hist, 0, (size_t)n * SLOTS * 256 * sizeof(uint64_t), s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return -1; }
+        if (hipMemsetAsync(hist, 0, (size_t)n * SLOTS * 256 * sizeof(uint64_t), s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return ADAIN_EINVAL; }
         entropy(0);
         jpeg_table_kernel<<<dim3(c == 3 ? 4 : 2, n), TABLE_THREADS, 0, s>>>(hist, huff);
     }
@@ -899,21 +902,21 @@ int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int
 
 int jpeg_roundtrip_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     const char* bad = check_shape(n, h, w, c, 75);
-    if (bad) { set_error("jpeg_roundtrip_u8: %s (n %d, %d x %d x %d)", bad, n, h, w, c); return -1; }
+    if (bad) { set_error("jpeg_roundtrip_u8: %s (n %d, %d x %d x %d)", bad, n, h, w, c); return ADAIN_EINVAL; }
     if (workspace_bytes) *workspace_bytes = make_roundtrip_plan(n, h, w, c).total;
     return 0;
 }
 
-int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, hipStream_t s) {
+int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const char* bad = check_shape(n, h, w, c, quality);
-    if (bad) { set_error("jpeg_roundtrip_u8: %s (n %d, %d x %d x %d, quality %d)", bad, n, h, w, c, quality); return -1; }
-    if ((uintptr_t)workspace % 8) { set_error("jpeg_roundtrip_u8: the workspace must be 8-byte aligned"); return -1; }
+    if (bad) { set_error("jpeg_roundtrip_u8: %s (n %d, %d x %d x %d, quality %d)", bad, n, h, w, c, quality); return ADAIN_EINVAL; }
     const RoundtripPlan p = make_roundtrip_plan(n, h, w, c);
+    if (int rc = check_workspace("jpeg_roundtrip_u8", workspace, workspace_bytes, p.total, 8)) return rc;
     const DecPlanes& g = p.g;
     const int bw = (w + 7) / 8, bh = (h + 7) / 8;
     // gridDim.y and .z are limited to 65535: h <= 65535 keeps the rows below that; the frames ride in y (idct) and z (transform, merge)
-    if (n > 65535 || (g.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull) { set_error("jpeg_roundtrip_u8: batch of %d frames too large for one call", n); return -1; }
-    int16_t* coef = (int16_t*)workspace;
+    if (n > 65535 || (g.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull) { set_error("jpeg_roundtrip_u8: batch of %d frames too large for one call", n); return ADAIN_EINVAL; }
+    int16_t* coef = (int16_t*)((char*)workspace + p.o_coef);
     uint8_t* planes = (uint8_t*)workspace + p.o_planes;
     if (c == 3)
         jpeg_transform_rgb_kernel<<<dim3((g.mw + MCUS_PER_WG - 1) / MCUS_PER_WG, g.mh, n), MCUS_PER_WG * 48, 0, s>>>(src, h, w, quality, coef, g.mw, bw, bh, g.nblk);

@@ -126,8 +126,6 @@ constexpr Tables HOST_T = make_tables();
 static_assert(HOST_T.hdr_len[1] == 623 && HOST_T.max_block_bits == 1660, "the header and the per-block bound of include/adain_hip.h");
 __constant__ const Tables T = make_tables();
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // One pass of jidctint over 8 values p[0], p[S], ..., descaled by N bits.  int32 suffices for coefficients that come from 8-bit samples at
 // any quality: a dequantised coefficient is within q / 2 <= 127.5 of the forward DCT's, which is at most 1024, so |d| <= 1152, and in the
 // column pass even the sum of the absolute values of every term of the largest intermediate (an output: 169352 |d|) is 1.96e8 < 2^31.  For

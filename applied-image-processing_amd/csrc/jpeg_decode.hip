@@ -200,18 +200,18 @@ DecPlan make_decode_plan(int n, int h, int w, int c, int sampling, int restart_i
     // every interval rounds its last subsequence up: the sum of ceil(bits_k / chunk_bits) is below ceil(bits / chunk_bits) + nint
     p.nsub_max = (uint32_t)((max_segment_bytes * 8 + p.chunk_bits - 1) / p.chunk_bits) + (restart_interval ? p.nint : 0u);
     if (p.nsub_max == 0) p.nsub_max = 1;
-    size_t at = 0, N = (size_t)n, S = (size_t)scans;
-    auto take = [&](size_t bytes) { size_t o = at; at = align256(at + bytes); return o; };
-    p.o_seg = take(N * S * sizeof(DecSeg));
-    p.o_meta = take(N * S * sizeof(DecMeta));
-    p.o_stream = take(N * S * p.cap_words * sizeof(uint32_t));
-    p.o_state = take(3 * N * p.nsub_max * state_bytes);
-    p.o_count = take(N * p.nsub_max * sizeof(uint32_t));
-    p.o_mask = take(mask ? N * p.g.nblk * sizeof(uint64_t) : 0);
-    p.o_coef = take(N * p.g.nblk * 64 * sizeof(int16_t));
-    p.o_planes = take(N * p.g.stride);
-    p.o_itab = take(restart_interval ? N * 2 * ((size_t)p.nint + 1) * sizeof(uint32_t) : 0);
-    p.total = at;
+    const size_t N = (size_t)n, S = (size_t)scans;
+    Carve ws;
+    p.o_seg = ws.take(N * S * sizeof(DecSeg));
+    p.o_meta = ws.take(N * S * sizeof(DecMeta));
+    p.o_stream = ws.take(N * S * p.cap_words * sizeof(uint32_t));
+    p.o_state = ws.take(3 * N * p.nsub_max * state_bytes);
+    p.o_count = ws.take(N * p.nsub_max * sizeof(uint32_t));
+    p.o_mask = ws.take(mask ? N * p.g.nblk * sizeof(uint64_t) : 0);
+    p.o_coef = ws.take(N * p.g.nblk * 64 * sizeof(int16_t));
+    p.o_planes = ws.take(N * p.g.stride);
+    p.o_itab = ws.take(restart_interval ? N * 2 * ((size_t)p.nint + 1) * sizeof(uint32_t) : 0);
+    p.total = ws.at;
     return p;
 }
 
@@ -948,16 +948,15 @@ int plan_decode(const char* who, size_t files_bytes, int n, int h, int w, int c,
     for (size_t i = 0; i < (size_t)n * scans; ++i) {
         if (seg_offsets[i] > files_bytes || seg_lengths[i] > files_bytes - seg_offsets[i]) {
             set_error("%s: segment %zu (%llu + %u bytes) leaves the %zu bytes of files", who, i, (unsigned long long)seg_offsets[i], seg_lengths[i], files_bytes);
-            return -1;
+            return ADAIN_EINVAL;
         }
         longest = seg_lengths[i] > longest ? seg_lengths[i] : longest;
     }
     const char* bad = check_decode_shape(n, h, w, c, sampling, restart_interval, longest, chunk_bits);
-    if (bad) { set_error("%s: %s", who, bad); return -1; }
-    if ((uintptr_t)workspace % 8 || (uintptr_t)record % 4) { set_error("%s: the workspace must be 8-byte and the record 4-byte aligned", who); return -1; }
+    if (bad) { set_error("%s: %s", who, bad); return ADAIN_EINVAL; }
+    if ((uintptr_t)record % 4) { set_error("%s: the record must be 4-byte aligned", who); return ADAIN_EINVAL; }
     *p = make_decode_plan(n, h, w, c, sampling, restart_interval, longest, chunk_bits, scans, state_bytes, mask);
-    if (workspace_bytes < p->total) { set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, p->total); return -1; }
-    return 0;
+    return check_workspace(who, workspace, workspace_bytes, p->total, 8);
 }
 
 // The front of both decoders: the segment table, the unstuffed streams (`streams` of them; an interval table only where the plan has
@@ -976,7 +975,7 @@ int launch_decode_front(const char* who, const DecPlan& p, char* ws, const uint8
         jpegd_unstuff_kernel<true><<<(unsigned)streams, DEC_THREADS, 0, s>>>(files, seg, meta, (uint8_t*)(ws + p.o_stream), p.cap_words, (uint32_t*)(ws + p.o_itab), p.nint);
     else
         jpegd_unstuff_kernel<false><<<(unsigned)streams, DEC_THREADS, 0, s>>>(files, seg, meta, (uint8_t*)(ws + p.o_stream), p.cap_words, nullptr, p.nint);
-    if (hipMemsetAsync(ws + p.o_coef, 0, (size_t)n * p.g.nblk * 64 * sizeof(int16_t), s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return -1; }
+    if (hipMemsetAsync(ws + p.o_coef, 0, (size_t)n * p.g.nblk * 64 * sizeof(int16_t), s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return ADAIN_EINVAL; }
     return 0;
 }
 
@@ -999,7 +998,7 @@ int jpeg_decode_bytes(int n, int h, int w, int c, int sampling, int restart_inte
     if (bad) {
         set_error("jpeg_decode_u8: %s (n %d, %d x %d x %d, sampling %d, restart_interval %d, segment %zu, chunk_bits %d)", bad, n, h, w, c, sampling, restart_interval,
                   max_segment_bytes, chunk_bits);
-        return -1;
+        return ADAIN_EINVAL;
     }
     if (workspace_bytes) *workspace_bytes = make_decode_plan(n, h, w, c, sampling, restart_interval, max_segment_bytes, chunk_bits, 1, sizeof(uint2), false).total;
     return 0;
@@ -1012,13 +1011,13 @@ int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_
     const char* bad = check_decode_shape(n, h, w, c, sampling, restart_interval, 0, chunk_bits);
     if (bad) {
         set_error("jpeg_decode_u8: %s (n %d, %d x %d x %d, sampling %d, restart_interval %d, chunk_bits %d)", bad, n, h, w, c, sampling, restart_interval, chunk_bits);
-        return -1;
+        return ADAIN_EINVAL;
     }
     DecPlan p{};
     if (plan_decode(who, files_bytes, n, h, w, c, sampling, restart_interval, chunk_bits, 1, sizeof(uint2), false, seg_offsets, seg_lengths, record, workspace,
                     workspace_bytes, &p))
-        return -1;
-    if ((p.g.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull) { set_error("jpeg_decode_u8: %d x %d: too many blocks for one launch", h, w); return -1; }
+        return ADAIN_EINVAL;
+    if ((p.g.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull) { set_error("jpeg_decode_u8: %d x %d: too many blocks for one launch", h, w); return ADAIN_EINVAL; }
     char* ws = (char*)workspace;
     DecMeta* meta = (DecMeta*)(ws + p.o_meta);
     const uint32_t* stream = (const uint32_t*)(ws + p.o_stream);
@@ -1027,7 +1026,7 @@ int launch_jpeg_decode_u8(const uint8_t* files, size_t files_bytes, const uint8_
     int16_t* coef = (int16_t*)(ws + p.o_coef);
     uint32_t* itab = restart_interval ? (uint32_t*)(ws + p.o_itab) : nullptr;
     const DecShape g{p.g.H, p.g.V, p.g.bpm, p.g.c, p.g.nblk, p.ri, p.nint};
-    if (launch_decode_front(who, p, ws, files, n, (size_t)n, seg_offsets, seg_lengths, restart_interval != 0, s)) return -1;
+    if (launch_decode_front(who, p, ws, files, n, (size_t)n, seg_offsets, seg_lengths, restart_interval != 0, s)) return ADAIN_EINVAL;
     jpegd_settle_kernel<<<n, DEC_THREADS, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, itab);
     jpegd_write_kernel<<<dim3((p.nsub_max + 255) / 256, n), 256, 0, s>>>(blobs, stream, p.cap_words, meta, state, count, p.nsub_max, p.chunk_bits, g, coef, itab);
     jpegd_dc_kernel<<<n, DEC_THREADS, 0, s>>>(coef, meta, g, record);
@@ -1040,7 +1039,7 @@ int jpeg_decode_progressive_bytes(int n, int h, int w, int c, int sampling, int 
     if (bad) {
         set_error("jpeg_decode_progressive_u8: %s (n %d, %d x %d x %d, sampling %d, %d scans, segment %zu, chunk_bits %d)", bad, n, h, w, c, sampling, nscans,
                   max_segment_bytes, chunk_bits);
-        return -1;
+        return ADAIN_EINVAL;
     }
     if (workspace_bytes) *workspace_bytes = make_decode_plan(n, h, w, c, sampling, 0, max_segment_bytes, chunk_bits, nscans, sizeof(uint4), true).total;
     return 0;
@@ -1054,16 +1053,16 @@ int launch_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, 
     if (!bad) bad = check_progressive_scans(c, nscans, scans);
     if (bad) {
         set_error("jpeg_decode_progressive_u8: %s (n %d, %d x %d x %d, sampling %d, %d scans, chunk_bits %d)", bad, n, h, w, c, sampling, nscans, chunk_bits);
-        return -1;
+        return ADAIN_EINVAL;
     }
     const size_t streams = (size_t)n * nscans;
     DecPlan p{};
     if (plan_decode(who, files_bytes, n, h, w, c, sampling, 0, chunk_bits, nscans, sizeof(uint4), true, seg_offsets, seg_lengths, record, workspace, workspace_bytes, &p))
-        return -1;
+        return ADAIN_EINVAL;
     const DecPlanes& pg = p.g;
     if ((pg.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull || streams > 0x7fffffffull) {
         set_error("jpeg_decode_progressive_u8: %d x %d, %d files: too many blocks or streams for one launch", h, w, n);
-        return -1;
+        return ADAIN_EINVAL;
     }
     char* ws = (char*)workspace;
     DecMeta* meta = (DecMeta*)(ws + p.o_meta);
@@ -1073,7 +1072,7 @@ int launch_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, 
     uint64_t* mask = (uint64_t*)(ws + p.o_mask);
     int16_t* coef = (int16_t*)(ws + p.o_coef);
     const DecShape g{pg.H, pg.V, pg.bpm, pg.c, pg.nblk, p.ri, p.nint};
-    if (launch_decode_front(who, p, ws, files, n, streams, seg_offsets, seg_lengths, false, s)) return -1;
+    if (launch_decode_front(who, p, ws, files, n, streams, seg_offsets, seg_lengths, false, s)) return ADAIN_EINVAL;
     const dim3 subs((p.nsub_max + 255) / 256, n);
     for (int k = 0; k < nscans; ++k) {
         const int32_t* d = scans + 8 * k;

@@ -135,18 +135,29 @@ __global__ __launch_bounds__(256) void strength_apply_kernel(float* __restrict__
 }
 
 constexpr int SM_BLOCKS = 64;
-size_t strength_map_workspace_bytes(int, int) { return SM_BLOCKS * 2 * sizeof(float) + SM_BLOCKS * sizeof(double); }
+// the workspace (offsets in bytes): K1's (min, max) pair and K2's partial sum per block
+struct StrengthLayout { size_t o_part, o_psum, total; };
+static StrengthLayout strength_layout() {
+    StrengthLayout l{};
+    Carve c;
+    l.o_part = c.take(SM_BLOCKS * 2 * sizeof(float));
+    l.o_psum = c.take(SM_BLOCKS * sizeof(double));
+    l.total = c.at;
+    return l;
+}
+size_t strength_map_workspace_bytes(int, int) { return strength_layout().total; }
 
 int launch_strength_map(const float* depth, int h0, int w0, int hc, int wc, float offset, float prominence, float* pmap,
                         void* workspace, size_t ws_bytes, hipStream_t s) {
-    if (h0 < 1 || w0 < 1 || hc < 1 || wc < 1) { set_error("strength_map: bad shape"); return -1; }
-    if ((size_t)hc * wc >= 0x7fffffffULL || (size_t)h0 * w0 >= 0x7fffffffULL) { set_error("strength_map: map too large"); return -1; }
-    if (!workspace || ws_bytes < strength_map_workspace_bytes(hc, wc)) { set_error("strength_map: workspace too small"); return -1; }
+    if (h0 < 1 || w0 < 1 || hc < 1 || wc < 1) { set_error("strength_map: bad shape"); return ADAIN_EINVAL; }
+    if ((size_t)hc * wc >= 0x7fffffffULL || (size_t)h0 * w0 >= 0x7fffffffULL) { set_error("strength_map: map too large"); return ADAIN_EINVAL; }
+    const StrengthLayout l = strength_layout();
+    if (int rc = check_workspace("strength_map", workspace, ws_bytes, l.total, 1)) return rc;
     const int total = hc * wc;
     int blocks = (total + 255) / 256;
     if (blocks > SM_BLOCKS) blocks = SM_BLOCKS;
-    float* part = (float*)workspace;
-    double* psum = (double*)(part + SM_BLOCKS * 2);
+    float* part = (float*)((char*)workspace + l.o_part);
+    double* psum = (double*)((char*)workspace + l.o_psum);
     hipLaunchKernelGGL(bicubic_minmax_kernel, dim3(blocks), dim3(256), 0, s, depth, h0, w0, hc, wc, pmap, part);
     hipLaunchKernelGGL(strength_sum_kernel, dim3(blocks), dim3(256), 0, s, pmap, total, part, blocks, psum);
     hipLaunchKernelGGL(strength_apply_kernel, dim3((total + 255) / 256), dim3(256), 0, s, pmap, total, part, blocks, psum, blocks, offset,
@@ -233,8 +244,8 @@ static unsigned grid_for(size_t total) {
 
 static int row_grid(const char* what, int planes, int ho, int wo, dim3* g) {
     const long long gx = ((long long)wo + 255) / 256, gy = ((long long)ho + 3) / 4;
-    if (gy > 65535 || planes > 65535) { set_error("%s: more than 262140 rows or 65535 planes per call", what); return -1; }
-    if ((size_t)ho * wo >= 0x7fffffffULL) { set_error("%s: a plane must stay below 2^31 pixels", what); return -1; }
+    if (gy > 65535 || planes > 65535) { set_error("%s: more than 262140 rows or 65535 planes per call", what); return ADAIN_EINVAL; }
+    if ((size_t)ho * wo >= 0x7fffffffULL) { set_error("%s: a plane must stay below 2^31 pixels", what); return ADAIN_EINVAL; }
     *g = dim3((unsigned)gx, (unsigned)gy, (unsigned)planes);
     return 0;
 }
@@ -242,10 +253,10 @@ static int row_grid(const char* what, int planes, int ho, int wo, dim3* g) {
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int launch_resize_bilinear(const float* in, float* out, int planes, int hi, int wi, int ho, int wo, hipStream_t s) {
-    if (planes < 1 || hi < 1 || wi < 1 || ho < 1 || wo < 1) { set_error("resize_bilinear: bad shape"); return -1; }
-    if ((size_t)hi * wi >= 0x7fffffffULL) { set_error("resize_bilinear: a plane must stay below 2^31 pixels"); return -1; }
+    if (planes < 1 || hi < 1 || wi < 1 || ho < 1 || wo < 1) { set_error("resize_bilinear: bad shape"); return ADAIN_EINVAL; }
+    if ((size_t)hi * wi >= 0x7fffffffULL) { set_error("resize_bilinear: a plane must stay below 2^31 pixels"); return ADAIN_EINVAL; }
     dim3 g;
-    if (row_grid("resize_bilinear", planes, ho, wo, &g)) return -1;
+    if (row_grid("resize_bilinear", planes, ho, wo, &g)) return ADAIN_EINVAL;
     const int vec = (int)(wo % 4 == 0 && aligned16(out));
     if (wi == wo && vec && aligned16(in)) hipLaunchKernelGGL(resize_bilinear_kernel<true>, g, dim3(64, 4), 0, s, in, out, hi, wi, ho, wo, vec);
     else hipLaunchKernelGGL(resize_bilinear_kernel<false>, g, dim3(64, 4), 0, s, in, out, hi, wi, ho, wo, vec);
@@ -253,10 +264,10 @@ int launch_resize_bilinear(const float* in, float* out, int planes, int hi, int 
 }
 
 int launch_resize_nearest(const float* in, float* out, int planes, int hi, int wi, int ho, int wo, hipStream_t s) {
-    if (planes < 1 || hi < 1 || wi < 1 || ho < 1 || wo < 1) { set_error("resize_nearest: bad shape"); return -1; }
-    if ((size_t)hi * wi >= 0x7fffffffULL) { set_error("resize_nearest: a plane must stay below 2^31 pixels"); return -1; }
+    if (planes < 1 || hi < 1 || wi < 1 || ho < 1 || wo < 1) { set_error("resize_nearest: bad shape"); return ADAIN_EINVAL; }
+    if ((size_t)hi * wi >= 0x7fffffffULL) { set_error("resize_nearest: a plane must stay below 2^31 pixels"); return ADAIN_EINVAL; }
     dim3 g;
-    if (row_grid("resize_nearest", planes, ho, wo, &g)) return -1;
+    if (row_grid("resize_nearest", planes, ho, wo, &g)) return ADAIN_EINVAL;
     hipLaunchKernelGGL(resize_nearest_kernel, g, dim3(64, 4), 0, s, in, out, hi, wi, ho, wo,
                        (int)(wo % 4 == 0 && aligned16(out) && aligned16(in)));
     return check_launch("resize_nearest");
@@ -287,10 +298,10 @@ __global__ __launch_bounds__(256) void mask_composite_kernel(const float* __rest
 
 int launch_mask_composite(const float* content, const float* stylized, const float* mask, int mask_c, int mask_n, float* out,
                           int n, int c, int hw, hipStream_t s) {
-    if (n < 1 || c < 1 || hw < 1) { set_error("mask_composite: bad shape"); return -1; }
-    if (mask_c != 1 && mask_c != c) { set_error("mask_composite: mask channels %d must be 1 or %d", mask_c, c); return -1; }
-    if (mask_n != 1 && mask_n != n) { set_error("mask_composite: mask batch %d must be 1 or %d", mask_n, n); return -1; }
-    if ((long long)n * c > 65535) { set_error("mask_composite: more than 65535 planes per call"); return -1; }
+    if (n < 1 || c < 1 || hw < 1) { set_error("mask_composite: bad shape"); return ADAIN_EINVAL; }
+    if (mask_c != 1 && mask_c != c) { set_error("mask_composite: mask channels %d must be 1 or %d", mask_c, c); return ADAIN_EINVAL; }
+    if (mask_n != 1 && mask_n != n) { set_error("mask_composite: mask batch %d must be 1 or %d", mask_n, n); return ADAIN_EINVAL; }
+    if ((long long)n * c > 65535) { set_error("mask_composite: more than 65535 planes per call"); return ADAIN_EINVAL; }
     const bool vec = hw % 4 == 0 && aligned16(content) && aligned16(stylized) && aligned16(mask) && aligned16(out);
     const unsigned gx = (unsigned)(((size_t)hw / (vec ? 4 : 1) + 255) / 256);
     if (vec)
@@ -333,8 +344,8 @@ __global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restric
 }
 
 int launch_quantize_u8(const float* in, uint8_t* out, int n, int c, int h, int w, hipStream_t s) {
-    if (n < 1 || c < 1 || h < 1 || w < 1) { set_error("quantize_u8: bad shape"); return -1; }
-    if ((size_t)h * w * c >= 0x7fffffffULL || n > 65535) { set_error("quantize_u8: image too large (2^31 elements) or batch > 65535"); return -1; }
+    if (n < 1 || c < 1 || h < 1 || w < 1) { set_error("quantize_u8: bad shape"); return ADAIN_EINVAL; }
+    if ((size_t)h * w * c >= 0x7fffffffULL || n > 65535) { set_error("quantize_u8: image too large (2^31 elements) or batch > 65535"); return ADAIN_EINVAL; }
     const int hw = h * w;
     if (c == 3 && hw % 4 == 0 && aligned16(in) && ((uintptr_t)out & 3) == 0)
         hipLaunchKernelGGL(quantize_u8_rgb4_kernel, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, s, in, out, hw);
@@ -370,8 +381,8 @@ __global__ __launch_bounds__(256) void u8_to_f32_kernel(const uint8_t* __restric
 }
 
 int launch_u8_to_f32(const uint8_t* in, float* out, int n, int c, int h, int w, hipStream_t s) {
-    if (n < 1 || c < 1 || h < 1 || w < 1) { set_error("u8_to_f32: bad shape"); return -1; }
-    if ((size_t)h * w * c >= 0x7fffffffULL || n > 65535) { set_error("u8_to_f32: image too large (2^31 elements) or batch > 65535"); return -1; }
+    if (n < 1 || c < 1 || h < 1 || w < 1) { set_error("u8_to_f32: bad shape"); return ADAIN_EINVAL; }
+    if ((size_t)h * w * c >= 0x7fffffffULL || n > 65535) { set_error("u8_to_f32: image too large (2^31 elements) or batch > 65535"); return ADAIN_EINVAL; }
     const int hw = h * w;
     if (c == 3 && hw % 4 == 0 && aligned16(out) && ((uintptr_t)in & 3) == 0)
         hipLaunchKernelGGL(u8_to_f32_rgb4_kernel, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, s, in, out, hw);
@@ -431,10 +442,10 @@ __global__ __launch_bounds__(256) void composite_quantize_u8_kernel(const uint8_
 
 int launch_composite_quantize_u8(const uint8_t* content, const float* stylized, const void* mask, int mask_is_float, int mask_c,
                                  int mask_n, uint8_t* out, int n, int hw, hipStream_t s) {
-    if (n < 1 || hw < 1) { set_error("composite_quantize_u8: bad shape"); return -1; }
-    if (mask_c != 1 && mask_c != 3) { set_error("composite_quantize_u8: mask channels %d must be 1 or 3", mask_c); return -1; }
-    if (mask_n != 1 && mask_n != n) { set_error("composite_quantize_u8: mask batch %d must be 1 or %d", mask_n, n); return -1; }
-    if ((size_t)hw * 3 >= 0x7fffffffULL || n > 65535) { set_error("composite_quantize_u8: frame too large or batch > 65535"); return -1; }
+    if (n < 1 || hw < 1) { set_error("composite_quantize_u8: bad shape"); return ADAIN_EINVAL; }
+    if (mask_c != 1 && mask_c != 3) { set_error("composite_quantize_u8: mask channels %d must be 1 or 3", mask_c); return ADAIN_EINVAL; }
+    if (mask_n != 1 && mask_n != n) { set_error("composite_quantize_u8: mask batch %d must be 1 or %d", mask_n, n); return ADAIN_EINVAL; }
+    if ((size_t)hw * 3 >= 0x7fffffffULL || n > 65535) { set_error("composite_quantize_u8: frame too large or batch > 65535"); return ADAIN_EINVAL; }
     const bool vec = hw % 4 == 0 && aligned16(stylized) && ((uintptr_t)content & 3) == 0 && ((uintptr_t)out & 3) == 0;
     const dim3 g((unsigned)(((size_t)hw / (vec ? 4 : 1) + 255) / 256), n);
     if (mask_is_float) {
@@ -502,12 +513,12 @@ __global__ __launch_bounds__(256) void composite_quantize_u8_nearest_kernel(cons
 
 int launch_composite_quantize_u8_nearest(const uint8_t* content, const float* stylized, const void* mask, int mask_is_float, int mask_c,
                                          int mask_n, int mh, int mw, uint8_t* out, int n, int h, int w, hipStream_t s) {
-    if (n < 1 || h < 1 || w < 1 || mh < 1 || mw < 1) { set_error("composite_quantize_u8_nearest: bad shape"); return -1; }
-    if (mask_c != 1 && mask_c != 3) { set_error("composite_quantize_u8_nearest: mask channels %d must be 1 or 3", mask_c); return -1; }
-    if (mask_n != 1 && mask_n != n) { set_error("composite_quantize_u8_nearest: mask batch %d must be 1 or %d", mask_n, n); return -1; }
-    if ((size_t)h * w * 3 >= 0x7fffffffULL || (size_t)mh * mw >= 0x7fffffffULL) { set_error("composite_quantize_u8_nearest: frame or mask too large"); return -1; }
+    if (n < 1 || h < 1 || w < 1 || mh < 1 || mw < 1) { set_error("composite_quantize_u8_nearest: bad shape"); return ADAIN_EINVAL; }
+    if (mask_c != 1 && mask_c != 3) { set_error("composite_quantize_u8_nearest: mask channels %d must be 1 or 3", mask_c); return ADAIN_EINVAL; }
+    if (mask_n != 1 && mask_n != n) { set_error("composite_quantize_u8_nearest: mask batch %d must be 1 or %d", mask_n, n); return ADAIN_EINVAL; }
+    if ((size_t)h * w * 3 >= 0x7fffffffULL || (size_t)mh * mw >= 0x7fffffffULL) { set_error("composite_quantize_u8_nearest: frame or mask too large"); return ADAIN_EINVAL; }
     dim3 g;
-    if (row_grid("composite_quantize_u8_nearest", n, h, w, &g)) return -1;
+    if (row_grid("composite_quantize_u8_nearest", n, h, w, &g)) return ADAIN_EINVAL;
     const int vec = (int)(w % 4 == 0 && aligned16(stylized) && ((uintptr_t)content & 3) == 0 && ((uintptr_t)out & 3) == 0);
     if (mask_is_float)
         hipLaunchKernelGGL(composite_quantize_u8_nearest_kernel<float>, g, dim3(64, 4), 0, s, content, stylized, (const float*)mask, mask_c, mask_n, mh, mw, out, h, w, vec);
@@ -523,7 +534,7 @@ __global__ __launch_bounds__(256) void mask_to_f32_kernel(const uint8_t* __restr
 }
 
 int launch_mask_to_f32(const uint8_t* in, float* out, size_t total, hipStream_t s) {
-    if (total < 1 || total >= ((size_t)1 << 39)) { set_error("mask_to_f32: bad size"); return -1; }
+    if (total < 1 || total >= ((size_t)1 << 39)) { set_error("mask_to_f32: bad size"); return ADAIN_EINVAL; }
     hipLaunchKernelGGL(mask_to_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, total);
     return check_launch("mask_to_f32");
 }
@@ -663,8 +674,8 @@ __global__ __launch_bounds__(256) void warp_blend_u8_kernel(const uint8_t* __res
 
 int launch_warp_blend_u8(const uint8_t* cur, const uint8_t* prev, const float* flow, uint8_t* out, int h, int w, int c, float alpha,
                          float one_minus_alpha, hipStream_t s) {
-    if (h < 1 || w < 1 || c < 1) { set_error("warp_blend_u8: bad shape"); return -1; }
-    if ((size_t)h * w * c >= 0x7fffffffULL) { set_error("warp_blend_u8: frame too large (2^31 bytes)"); return -1; }
+    if (h < 1 || w < 1 || c < 1) { set_error("warp_blend_u8: bad shape"); return ADAIN_EINVAL; }
+    if ((size_t)h * w * c >= 0x7fffffffULL) { set_error("warp_blend_u8: frame too large (2^31 bytes)"); return ADAIN_EINVAL; }
     const int total = h * w;
     if (c == 3 && total % 4 == 0 && aligned16(flow) && ((uintptr_t)cur & 3) == 0 && ((uintptr_t)out & 3) == 0)
         hipLaunchKernelGGL(warp_blend_u8_rgb4_kernel, dim3((total / 4 + 255) / 256), dim3(256), 0, s, cur, prev, flow, out, h, w, alpha,
@@ -891,12 +902,12 @@ __global__ __launch_bounds__(256) void resize_area_linear_u8_kernel(const uint8_
 }
 
 int launch_resize_area_u8(const uint8_t* in, uint8_t* out, int n, int hi, int wi, int c, int ho, int wo, hipStream_t s) {
-    if (n < 1 || hi < 1 || wi < 1 || c < 1 || ho < 1 || wo < 1) { set_error("resize_area_u8: bad shape"); return -1; }
-    if ((size_t)hi * wi * c >= 0x7fffffffULL || n > 65535 || (ho + 3) / 4 > 65535) { set_error("resize_area_u8: frame or batch too large"); return -1; }
+    if (n < 1 || hi < 1 || wi < 1 || c < 1 || ho < 1 || wo < 1) { set_error("resize_area_u8: bad shape"); return ADAIN_EINVAL; }
+    if ((size_t)hi * wi * c >= 0x7fffffffULL || n > 65535 || (ho + 3) / 4 > 65535) { set_error("resize_area_u8: frame or batch too large"); return ADAIN_EINVAL; }
     if (ho == hi && wo == wi) {
         if (hipMemcpyAsync(out, in, (size_t)n * hi * wi * c, hipMemcpyDeviceToDevice, s) != hipSuccess) {
             set_error("resize_area_u8: copy failed: %s", hipGetErrorString(hipGetLastError()));
-            return -2;
+            return ADAIN_ELAUNCH;
         }
         return 0;
     }
@@ -948,9 +959,9 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 }
 
 static int launch_transpose(const float* in, float* out, int n, int R, int C, hipStream_t s, const char* what) {
-    if (n < 1 || R < 1 || C < 1) { set_error("%s: bad shape", what); return -1; }
+    if (n < 1 || R < 1 || C < 1) { set_error("%s: bad shape", what); return ADAIN_EINVAL; }
     const size_t tiles = (size_t)((C + 31) / 32) * ((R + 31) / 32);
-    if (tiles > 0x7fffffffULL || n > 65535) { set_error("%s: grid too large", what); return -1; }
+    if (tiles > 0x7fffffffULL || n > 65535) { set_error("%s: grid too large", what); return ADAIN_EINVAL; }
     hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tiles, n), dim3(256), 0, s, in, out, R, C);
     return check_launch(what);
 }

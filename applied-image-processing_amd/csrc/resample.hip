@@ -116,42 +116,51 @@ __global__ __launch_bounds__(256) void pil_resize_kernel(const uint8_t* __restri
     o[2] = (uint8_t)clip8(a2);
 }
 
-static size_t align_ints(size_t n) { return (n + 63) & ~(size_t)63; }
+// the workspace (offsets in bytes): per axis, x then y, the tap bounds [out][2] and the taps [out][ksize], all int
+struct PilLayout { size_t o_bounds[2], o_kk[2], total; int ksize[2]; };
+static PilLayout pil_layout(int hi, int wi, int ho, int wo) {
+    const int in[2] = {wi, hi}, out[2] = {wo, ho};
+    PilLayout l{};
+    Carve c;
+    for (int a = 0; a < 2; ++a) {
+        l.ksize[a] = pil_ksize(in[a], out[a]);
+        l.o_bounds[a] = c.take((size_t)out[a] * 2 * sizeof(int));
+        l.o_kk[a] = c.take((size_t)out[a] * l.ksize[a] * sizeof(int));
+    }
+    l.total = c.at;
+    return l;
+}
 
 size_t resize_pil_workspace_bytes(int hi, int wi, int ho, int wo) {
     if (hi < 1 || wi < 1 || ho < 1 || wo < 1) return 0;
-    return (align_ints((size_t)wo * 2) + align_ints((size_t)wo * pil_ksize(wi, wo)) + align_ints((size_t)ho * 2) + align_ints((size_t)ho * pil_ksize(hi, ho))) * sizeof(int);
+    return pil_layout(hi, wi, ho, wo).total;
 }
 
 int launch_resize_pil_bilinear_u8(const uint8_t* in, int pixel_bytes, int n, int hi, int wi, uint8_t* out, int ho, int wo, int y0, int x0, int ch,
                                   int cw, void* workspace, size_t ws_bytes, hipStream_t s) {
-    if (pixel_bytes != 3 && pixel_bytes != 4) { set_error("resize_pil_bilinear_u8: source pixels of 3 (RGB) or 4 (RGBX) bytes, got %d", pixel_bytes); return -1; }
+    if (pixel_bytes != 3 && pixel_bytes != 4) { set_error("resize_pil_bilinear_u8: source pixels of 3 (RGB) or 4 (RGBX) bytes, got %d", pixel_bytes); return ADAIN_EINVAL; }
     // every side below 2^24 (Pillow's own limit on an image side is far below; keeps wo + ho, the tap-table sizes and the crop sums in int)
     if (n < 1 || hi < 1 || wi < 1 || ho < 1 || wo < 1 || hi >= (1 << 24) || wi >= (1 << 24) || ho >= (1 << 24) || wo >= (1 << 24)) {
         set_error("resize_pil_bilinear_u8: bad size %dx%d -> %dx%d (every side must be in [1, 2^24))", hi, wi, ho, wo);
-        return -1;
+        return ADAIN_EINVAL;
     }
     // a shrink factor beyond 256 (a tap window of more than ~770 source pixels per output pixel and axis, recomputed per output pixel by
     // this one-pass kernel) is not a resize any caller of the path makes (test.py:16-24: 512 / 256 from camera-sized images): refused
     // rather than run for seconds
     if ((long long)hi > 256LL * ho || (long long)wi > 256LL * wo) {
         set_error("resize_pil_bilinear_u8: shrink factor above 256 (%dx%d -> %dx%d) is not supported", hi, wi, ho, wo);
-        return -1;
+        return ADAIN_EINVAL;
     }
     if (y0 < 0 || x0 < 0 || ch < 1 || cw < 1 || (long long)y0 + ch > ho || (long long)x0 + cw > wo) {
         set_error("resize_pil_bilinear_u8: crop window (%d, %d, %d x %d) outside the %d x %d result", y0, x0, ch, cw, ho, wo);
-        return -1;
+        return ADAIN_EINVAL;
     }
-    if (!workspace || ws_bytes < resize_pil_workspace_bytes(hi, wi, ho, wo)) { set_error("resize_pil_bilinear_u8: workspace too small"); return -1; }
-    if ((size_t)n > 65535 || (size_t)(ch + 3) / 4 > 65535) { set_error("resize_pil_bilinear_u8: grid too large"); return -1; }
-    int* p = (int*)workspace;
-    PilAxis ax{wi, wo, pil_ksize(wi, wo), p, nullptr};
-    p += align_ints((size_t)wo * 2);
-    ax.kk = p;
-    p += align_ints((size_t)wo * ax.ksize);
-    PilAxis ay{hi, ho, pil_ksize(hi, ho), p, nullptr};
-    p += align_ints((size_t)ho * 2);
-    ay.kk = p;
+    const PilLayout l = pil_layout(hi, wi, ho, wo);
+    if (int rc = check_workspace("resize_pil_bilinear_u8", workspace, ws_bytes, l.total, 1)) return rc;
+    if ((size_t)n > 65535 || (size_t)(ch + 3) / 4 > 65535) { set_error("resize_pil_bilinear_u8: grid too large"); return ADAIN_EINVAL; }
+    char* base = (char*)workspace;
+    const PilAxis ax{wi, wo, l.ksize[0], (int*)(base + l.o_bounds[0]), (int*)(base + l.o_kk[0])};
+    const PilAxis ay{hi, ho, l.ksize[1], (int*)(base + l.o_bounds[1]), (int*)(base + l.o_kk[1])};
     hipLaunchKernelGGL(pil_coeffs_kernel, dim3((wo + ho + 255) / 256), dim3(256), 0, s, ax, ay);
     if (int r = check_launch("resize_pil_bilinear_u8 (tap tables)")) return r;
     const dim3 g((cw + 63) / 64, (ch + 3) / 4, n), b(64, 4);

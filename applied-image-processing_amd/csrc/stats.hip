@@ -145,6 +145,8 @@ static int nhwc_blocks(int c, int hw) {
     return nblk;
 }
 
+// The workspace is one block, the NHWC form's partial sums [n][nblk][c][2] double: nothing to lay out, and its size is not rounded up
+// to 256 bytes (a caller's buffer of exactly this size must stay enough).
 size_t mean_std_workspace_bytes(int nhwc, int n, int c, int hw) {
     if (!nhwc) return 0;
     if (c < 4 || (c & 3) || (c >> 2) > MS_THREADS) return 0;
@@ -153,11 +155,11 @@ size_t mean_std_workspace_bytes(int nhwc, int n, int c, int hw) {
 
 int launch_mean_std(const float* feat, int nhwc, int n, int c, int hw, float eps, float* mean, float* std_,
                     void* workspace, size_t ws_bytes, hipStream_t s) {
-    if (n < 1 || c < 1 || hw < 1) { set_error("mean_std: bad shape n=%d c=%d hw=%d", n, c, hw); return -1; }
+    if (n < 1 || c < 1 || hw < 1) { set_error("mean_std: bad shape n=%d c=%d hw=%d", n, c, hw); return ADAIN_EINVAL; }
     if (nhwc) {
-        if ((c & 3) || (c >> 2) > MS_THREADS) { set_error("mean_std(NHWC): c=%d must be a multiple of 4 and <= 1024", c); return -1; }
+        if ((c & 3) || (c >> 2) > MS_THREADS) { set_error("mean_std(NHWC): c=%d must be a multiple of 4 and <= 1024", c); return ADAIN_EINVAL; }
         const int nblk = nhwc_blocks(c, hw);
-        if (ws_bytes < mean_std_workspace_bytes(1, n, c, hw) || !workspace) { set_error("mean_std: workspace too small"); return -1; }
+        if (int rc = check_workspace("mean_std", workspace, ws_bytes, mean_std_workspace_bytes(1, n, c, hw), 1)) return rc;
         hipLaunchKernelGGL(mean_std_nhwc_partial, dim3(nblk, n), dim3(MS_THREADS), 0, s, feat, c, hw, nblk, (double*)workspace);
         hipLaunchKernelGGL(mean_std_finalize, dim3((c + 3) / 4, n), dim3(256), 0, s, (const double*)workspace, c, hw, nblk, eps, mean, std_);
     } else {
@@ -309,15 +311,15 @@ __global__ __launch_bounds__(256) void adain_blend_kernel(const BlendArgs a, siz
 }
 
 int check_adain_blend(const char* what, int nhwc, int n, int c, int hw, const StyleTerm& st, const BlendTerm& b) {
-    if (n < 1 || c < 1 || hw < 1) { set_error("%s: bad shape n=%d c=%d hw=%d", what, n, c, hw); return -1; }
-    if (st.k < 1 || st.k > MIX_MAX_STYLES) { set_error("%s: %d styles (1..%d)", what, st.k, MIX_MAX_STYLES); return -1; }
-    if (st.weights ? st.per_frame : st.k != 1) { set_error("%s: a mix needs weights and one set of styles for all frames", what); return -1; }
-    if (st.weights && st.weights_n != 1 && st.weights_n != n) { set_error("%s: weights batch %d must be 1 or %d", what, st.weights_n, n); return -1; }
-    if (st.weights && st.weights_hw != 1 && st.weights_hw != hw) { set_error("%s: weights per style %d must be 1 or %d (hw)", what, st.weights_hw, hw); return -1; }
-    if (b.pmap && b.pmap_n != 1 && b.pmap_n != n) { set_error("%s: pmap batch %d must be 1 or %d", what, b.pmap_n, n); return -1; }
+    if (n < 1 || c < 1 || hw < 1) { set_error("%s: bad shape n=%d c=%d hw=%d", what, n, c, hw); return ADAIN_EINVAL; }
+    if (st.k < 1 || st.k > MIX_MAX_STYLES) { set_error("%s: %d styles (1..%d)", what, st.k, MIX_MAX_STYLES); return ADAIN_EINVAL; }
+    if (st.weights ? st.per_frame : st.k != 1) { set_error("%s: a mix needs weights and one set of styles for all frames", what); return ADAIN_EINVAL; }
+    if (st.weights && st.weights_n != 1 && st.weights_n != n) { set_error("%s: weights batch %d must be 1 or %d", what, st.weights_n, n); return ADAIN_EINVAL; }
+    if (st.weights && st.weights_hw != 1 && st.weights_hw != hw) { set_error("%s: weights per style %d must be 1 or %d (hw)", what, st.weights_hw, hw); return ADAIN_EINVAL; }
+    if (b.pmap && b.pmap_n != 1 && b.pmap_n != n) { set_error("%s: pmap batch %d must be 1 or %d", what, b.pmap_n, n); return ADAIN_EINVAL; }
     const size_t total = (size_t)n * c * hw;
-    if (nhwc ? (c & 3) : (total & 3)) { set_error("%s: element count / channels must be a multiple of 4", what); return -1; }
-    if (total >= 0x7fffffffULL) { set_error("%s: more than 2^31 elements per call", what); return -1; }
+    if (nhwc ? (c & 3) : (total & 3)) { set_error("%s: element count / channels must be a multiple of 4", what); return ADAIN_EINVAL; }
+    if (total >= 0x7fffffffULL) { set_error("%s: more than 2^31 elements per call", what); return ADAIN_EINVAL; }
     return 0;
 }
 
@@ -329,7 +331,7 @@ int check_adain_blend(const char* what, int nhwc, int n, int c, int hw, const St
 int launch_adain_blend(const float* content, int nhwc, int n, int c, int hw, const float* c_mean, const float* c_std, const StyleTerm& st,
                        const BlendTerm& b, float* out, hipStream_t s) {
     const char* what = st.weights ? "adain_blend_mix" : "adain_blend";
-    if (check_adain_blend(what, nhwc, n, c, hw, st, b)) return -1;
+    if (check_adain_blend(what, nhwc, n, c, hw, st, b)) return ADAIN_EINVAL;
     const BlendArgs a{content, c_mean, c_std, st.s_mean, st.s_std, st.weights, b.pmap, out, c, hw, st.k, st.per_frame, st.weights_n, st.weights_hw,
                       b.pmap_n, b.alpha, b.one_minus_alpha};
     const int cols = c >> 2;

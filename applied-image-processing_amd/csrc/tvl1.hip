@@ -39,7 +39,6 @@
 // Each pair carries its own stop state (done flag, buffer parities, arrival counter): a step's last-arriving tile reduces the pair's
 // error partials, counts the step and sets the flag; later launches of that warp skip a flagged pair.  After each outer pass the host
 // reads how many pairs are done and skips the rest of the warp when all are.
-#include "../../include/adain_hip.h"
 #include "common.h"
 #include "cv_resize.h"
 
@@ -53,7 +52,8 @@ constexpr int TV_MIN_SIZE = 16;
 
 struct TvScale { int w, h; size_t off; };   // off: floats into a prepared frame, float4 (img, I_x, I_y, 0) per pixel
 
-// the scale list; returns the effective count or -1 (too many scales)
+// the scale list; returns the effective count or ADAIN_EINVAL (< 0: too many scales).  The single source of a prepared frame's layout: every scale's
+// block starts on a multiple of 256 bytes.
 static int tv_schedule(int h, int w, int nscales, double step, TvScale* S, size_t* frame_floats) {
     int n = 1;
     S[0].w = w;
@@ -61,17 +61,14 @@ static int tv_schedule(int h, int w, int nscales, double step, TvScale* S, size_
     for (int s = 1; s < nscales; ++s) {
         const int nw = (int)nearbyint(S[s - 1].w * step), nh = (int)nearbyint(S[s - 1].h * step);
         if (nw < TV_MIN_SIZE || nh < TV_MIN_SIZE) break;
-        if (n == TV_MAX_SCALES) return -1;
+        if (n == TV_MAX_SCALES) return ADAIN_EINVAL;
         S[s].w = nw;
         S[s].h = nh;
         n = s + 1;
     }
-    size_t off = 0;
-    for (int s = 0; s < n; ++s) {
-        S[s].off = off;
-        off += align64f((size_t)S[s].w * S[s].h * 4);
-    }
-    if (frame_floats) *frame_floats = off;
+    Carve c;
+    for (int s = 0; s < n; ++s) S[s].off = c.take((size_t)S[s].w * S[s].h * 4 * sizeof(float)) / sizeof(float);
+    if (frame_floats) *frame_floats = c.at / sizeof(float);
     return n;
 }
 
@@ -496,14 +493,32 @@ size_t tvl1_frame_bytes(int h, int w, const adain_tvl1_params* p) {
     return floats * sizeof(float);
 }
 
-static size_t tv_state_bytes(int npairs) { return ((size_t)(npairs + 1) * sizeof(TvState) + 255) & ~(size_t)255; }
 static int tv_nblk(int h, int w) { return ((w + ST_TX - 1) / ST_TX) * ((h + ST_TY - 1) / ST_TY); }
+
+// One call's workspace (offsets in bytes).  The stop counter and the pair states share the first block - the counter in a slot of a
+// state's size, the states behind it - and are cleared together at the start of a call; then every pair's error partials
+// [npairs][nblk] at the full size, then every pair's 16 pixel planes.
+struct TvLayout {
+    size_t o_ndone, o_state, clear_bytes, o_partials, o_pairs, total;
+    size_t plane, pair_floats;      // floats: one full-size pixel plane (a multiple of 256 bytes), a pair's buffers
+};
+static TvLayout tv_layout(int h, int w, int npairs) {
+    TvLayout l{};
+    Carve c;
+    l.o_ndone = c.take((size_t)(npairs + 1) * sizeof(TvState));
+    l.o_state = l.o_ndone + sizeof(TvState);
+    l.clear_bytes = c.at;
+    l.o_partials = c.take((size_t)npairs * tv_nblk(h, w) * sizeof(double));
+    l.plane = align256((size_t)h * w * sizeof(float)) / sizeof(float);
+    l.pair_floats = 16 * l.plane;
+    l.o_pairs = c.take((size_t)npairs * l.pair_floats * sizeof(float));
+    l.total = c.at;
+    return l;
+}
 
 size_t tvl1_workspace_bytes(int h, int w, int npairs, const adain_tvl1_params* p) {
     if (!tv_check(p, h, w, "tvl1_workspace_bytes") || npairs < 1 || npairs > 65535) return 0;
-    const size_t plane = align64f((size_t)h * w);
-    const size_t part = (((size_t)npairs * tv_nblk(h, w) * sizeof(double)) + 255) & ~(size_t)255;
-    return tv_state_bytes(npairs) + part + (size_t)npairs * 16 * plane * sizeof(float);
+    return tv_layout(h, w, npairs).total;
 }
 
 int launch_tvl1_prepare(const uint8_t* gray, int n, int h, int w, const adain_tvl1_params* p, float* prep, hipStream_t s) {
@@ -531,25 +546,22 @@ int launch_tvl1_flow(const float* const* prev, const float* const* next, int npa
                      void* ws, size_t ws_bytes, hipStream_t s) {
     if (!tv_check(p, h, w, "tvl1_flow")) return ADAIN_EINVAL;
     if (npairs < 1 || npairs > 65535) { set_error("tvl1_flow: bad pair count %d", npairs); return ADAIN_EINVAL; }
-    const size_t need = tvl1_workspace_bytes(h, w, npairs, p);
-    if (!ws || ws_bytes < need) { set_error("tvl1_flow: workspace of %zu bytes, %zu needed", ws_bytes, need); return ADAIN_EINVAL; }
+    const TvLayout l = tv_layout(h, w, npairs);
+    if (int rc = check_workspace("tvl1_flow", ws, ws_bytes, l.total, 1)) return rc;
     TvScale S[TV_MAX_SCALES];
     size_t ff = 0;
     const int ns = tv_schedule(h, w, p->nscales, p->scaleStep, S, &ff);
-    const size_t plane = align64f((size_t)h * w);
-    const size_t sb = tv_state_bytes(npairs);
-    const size_t part = (((size_t)npairs * tv_nblk(h, w) * sizeof(double)) + 255) & ~(size_t)255;
     char* base = (char*)ws;
     TvArgs a{};
     a.prev = prev;
     a.next = next;
     a.npairs = npairs;
-    a.ndone = (int*)base;
-    a.state = (TvState*)(base + sizeof(TvState));
-    a.partials = (double*)(base + sb);
-    a.ws_pairs = (float*)(base + sb + part);
-    a.pair_floats = 16 * plane;
-    a.plane = plane;
+    a.ndone = (int*)(base + l.o_ndone);
+    a.state = (TvState*)(base + l.o_state);
+    a.partials = (double*)(base + l.o_partials);
+    a.ws_pairs = (float*)(base + l.o_pairs);
+    a.pair_floats = l.pair_floats;
+    a.plane = l.plane;
     a.iters = iters;
     a.iters_stride = ns * p->warps;
     a.l_t = (float)(p->lambda * p->theta);
@@ -559,7 +571,7 @@ int launch_tvl1_flow(const float* const* prev, const float* const* next, int npa
     const size_t out_stride = 2 * (size_t)h * w;
     TvCubic tab;
     tv_cubic_table(tab);
-    if (hipMemsetAsync(ws, 0, sb, s) != hipSuccess) { set_error("tvl1_flow: hipMemsetAsync failed"); return ADAIN_ELAUNCH; }
+    if (hipMemsetAsync(base + l.o_ndone, 0, l.clear_bytes, s) != hipSuccess) { set_error("tvl1_flow: hipMemsetAsync failed"); return ADAIN_ELAUNCH; }
     const dim3 blk(64, 4);
     for (int k = ns - 1; k >= 0; --k) {
         const TvScale& c = S[k];
