@@ -5,7 +5,7 @@ Style_3DGS/AdaIN/run_depth.py (:13-55), so existing invocations keep working:
 
 Extra flags make the depth-aware mode usable offline (the reference pulls MiDaS through torch.hub at run time):
 ``--depth_npy`` takes a precomputed proximity map, ``--vgg`` / ``--decoder`` the checkpoint paths; ``--jpeg_on_device`` encodes the
-result's JPEG file on the GPU (the same bytes); ``--jpeg_quality``, ``--jpeg_subsampling`` (4:4:4, 4:2:2, 4:2:0) and ``--jpeg_optimize``
+result's JPEG file on the GPU (the same bytes); ``--jpeg_quality``, ``--jpeg_subsampling`` (4:4:4, 4:2:2, 4:2:0), ``--jpeg_optimize`` and ``--jpeg_progressive``
 are Pillow's save keywords for that file, on either route; ``--jpeg_decode_on_device`` decodes a baseline JPEG
 content there too (the same pixels), ``--jpeg_decode_progressive`` (which implies it) a progressive one as well; ``--coral_on_device`` preserves the content's colours (``adain_inference``'s
 ``preserve_color``, which the reference's CLI does not expose) with CORAL computed on the GPU.
@@ -41,6 +41,7 @@ _EXTRA_FLAGS = (
     ("--jpeg_quality", dict(type=int, default=75, help="Pillow's quality of the output JPEG, 1..100 (PIL or --jpeg_on_device: the same file)")),
     ("--jpeg_subsampling", dict(type=str, default="4:2:0", choices=["4:4:4", "4:2:2", "4:2:0"], help="chroma subsampling of the output JPEG")),
     ("--jpeg_optimize", dict(action="store_true", help="give the output JPEG its own optimal Huffman tables (Pillow's optimize=True)")),
+    ("--jpeg_progressive", dict(action="store_true", help="write the output JPEG as a progressive file (Pillow's progressive=True)")),
     ("--coral_on_device", dict(action="store_true", help="preserve the content's colours (preserve_color) with CORAL computed on the GPU")),
     ("--jpeg_decode_on_device", dict(action="store_true", help="decode a baseline JPEG content on the GPU instead of in PIL (the same pixels)")),
     ("--jpeg_decode_progressive", dict(action="store_true", help="decode a progressive JPEG content on the GPU too (implies --jpeg_decode_on_device)")),
@@ -67,7 +68,7 @@ def main(argv=None):
     if ns.depth_npy:
         proximity = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
     prev_jpeg = set_jpeg_routes(rt.JpegRoutes(ns.jpeg_on_device, ns.jpeg_decode_on_device or ns.jpeg_decode_progressive, ns.jpeg_decode_progressive,
-                                              (ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize)))
+                                              (ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize, ns.jpeg_progressive)))
     prev_coral = set_device_coral(ns.coral_on_device)
     style, mix = ns.style, {}
     if ns.style_interpolation_weights:

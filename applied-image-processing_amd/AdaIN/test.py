@@ -308,11 +308,11 @@ def set_device_jpeg(enabled):
     return set_jpeg_routes(_jpeg.replace(encode_on_device=enabled)).encode_on_device
 
 
-def set_jpeg_save_options(quality=rt.JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
-    """``options``: how ``adain_inference`` saves a ``.jpg`` / ``.jpeg`` output - Pillow's ``quality``, ``subsampling`` and ``optimize``
-    (``runtime.JpegOptions``, which may be given in place of ``quality``), honoured by PIL and by the device encoder: the same file.
+def set_jpeg_save_options(quality=rt.JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False, progressive=False):
+    """``options``: how ``adain_inference`` saves a ``.jpg`` / ``.jpeg`` output - Pillow's ``quality``, ``subsampling``, ``optimize`` and
+    ``progressive`` (``runtime.JpegOptions``, which may be given in place of ``quality``), honoured by PIL and by the device encoder: the same file.
     The defaults are Pillow's default save.  Returns the previous value (a ``JpegOptions``)."""
-    new = rt.JpegOptions(quality, subsampling, optimize) if isinstance(quality, int) else quality
+    new = rt.JpegOptions(quality, subsampling, optimize, progressive) if isinstance(quality, int) else quality
     return set_jpeg_routes(_jpeg.replace(options=new)).options
 
 

@@ -552,6 +552,16 @@ int adain_jpeg_encode_u8(const uint8_t* src, int n, int h, int w, int c, int qua
                          size_t workspace_bytes, adain_stream_t stream) {
     return jpeg_encode("jpeg_encode_u8", src, n, h, w, c, quality, 2, 0, out, out_stride, lengths, workspace, workspace_bytes, stream);
 }
+// Pillow's progressive=True: the same coefficients in libjpeg's simple progression, every scan under its own optimal table
+int adain_jpeg_encode_progressive_u8_bytes(int n, int h, int w, int c, int sampling, size_t* out_stride, size_t* workspace_bytes) {
+    return jpeg_encode_progressive_bytes(n, h, w, c, sampling, out_stride, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_jpeg_encode_progressive_u8(const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, uint8_t* out, size_t out_stride, int32_t* lengths,
+                                     void* workspace, size_t workspace_bytes, adain_stream_t stream) {
+    if (!src || !out || !lengths || !workspace) { set_error("jpeg_encode_progressive_u8: null pointer"); return ADAIN_EINVAL; }
+    if (jpeg_encode_progressive_bytes(n, h, w, c, sampling, nullptr, nullptr)) return ADAIN_EINVAL;
+    return launch_jpeg_encode_progressive_u8(src, n, h, w, c, quality, sampling, out, out_stride, lengths, workspace, workspace_bytes, (hipStream_t)stream);
+}
 
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;

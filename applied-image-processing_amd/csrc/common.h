@@ -199,6 +199,10 @@ int launch_tvl1_flow(const float* const* prev, const float* const* next, int npa
 int jpeg_encode_bytes(const char* who, int n, int h, int w, int c, int sampling, int optimize, size_t* out_stride, size_t* workspace_bytes);
 int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out,
                           size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes, hipStream_t s);
+// the progressive file Pillow's save(progressive=True) writes (the rules: jpeg.hip, "progressive files"; tests/jpeg_progressive_encode_ref.py)
+int jpeg_encode_progressive_bytes(int n, int h, int w, int c, int sampling, size_t* out_stride, size_t* workspace_bytes);
+int launch_jpeg_encode_progressive_u8(const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, uint8_t* out, size_t out_stride, int32_t* lengths,
+                                      void* workspace, size_t workspace_bytes, hipStream_t s);
 // the pixels Pillow decodes from that file, without the file (the rules: top of jpeg.hip, tests/jpeg_decode_ref.py)
 int jpeg_roundtrip_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
 int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int quality, uint8_t* dst, void* workspace, size_t workspace_bytes, hipStream_t s);

@@ -46,6 +46,9 @@
 //            table stages run between transform and count (10 launches and a memset), count and emit read the frame's own tables
 //            from the workspace, and scatter writes a per-frame header with four (grey: two) DHT segments of only the symbols that occur
 //
+// Progressive files (adain_jpeg_encode_progressive_u8): Pillow's save with progressive = True, the same coefficients in libjpeg's simple
+// progression; the rules and the stages stand in front of its kernels ("progressive files").
+//
 // The round trip (adain_jpeg_roundtrip_u8): the pixels Pillow decodes from that file, byte for byte, without the file.  Entropy coding is
 // lossless, so they are a function of the quantised coefficients the transform stage leaves in the workspace; what follows it is the
 // back half of libjpeg's decoder.  tests/jpeg_decode_ref.py restates it in NumPy, tests/test_jpeg_roundtrip_host.py holds that to Pillow.
@@ -513,13 +516,14 @@ __device__ __forceinline__ Least least_frequency(unsigned long long f, bool in, 
     return m;
 }
 
-__global__ __launch_bounds__(TABLE_THREADS) void jpeg_table_kernel(const unsigned long long* __restrict__ hist, HuffSlot* __restrict__ huff) {
+// slots: table slots per frame in hist and huff (blockIdx.y: the frame, blockIdx.x: its slot)
+__global__ __launch_bounds__(TABLE_THREADS) void jpeg_table_kernel(const unsigned long long* __restrict__ hist, HuffSlot* __restrict__ huff, int slots) {
     __shared__ Least part[2][TABLE_THREADS / 64];
     __shared__ int size_of[256];                // the unrestricted code length per symbol
     __shared__ int bits[260];                   // symbols per code length; a chain of 257 symbols is at most 256 deep
     __shared__ int first[18], upto[18];         // per length 1..16: its first code; the symbols of shorter-or-equal length
     const int t = threadIdx.x;
-    const size_t slot = (size_t)blockIdx.y * SLOTS + blockIdx.x;
+    const size_t slot = (size_t)blockIdx.y * slots + blockIdx.x;
     unsigned long long f = t < 256 ? hist[slot * 256 + t] : t == 256 ? 1ull : 0ull;
     int tree = t, size = 0;
     for (int i = t; i < 260; i += TABLE_THREADS) bits[i] = 0;
@@ -576,15 +580,11 @@ __global__ __launch_bounds__(TABLE_THREADS) void jpeg_table_kernel(const unsigne
 __device__ __forceinline__ size_t stream_bytes(uint64_t bits) { return (size_t)((bits + 7) >> 3); }
 __device__ __forceinline__ size_t stream_chunks(uint64_t bits) { return (stream_bytes(bits) + CHUNK - 1) / CHUNK; }
 
-// out[i] = in[0] + ... + in[i - 1] over a frame's `count` entries (count_bits != nullptr: the chunks of that many coded bits), the sum to total[frame]
+// out[i] = in[0] + ... + in[i - 1] over `count` entries by the SCAN_THREADS threads of a workgroup; part: one entry of LDS per thread.
+// Returns, in the last thread, the sum.
 template <class In, class Out>
-__global__ __launch_bounds__(SCAN_THREADS) void jpeg_scan_kernel(const In* __restrict__ in, Out* __restrict__ out, Out* __restrict__ total, size_t stride, size_t count,
-                                                                 const uint64_t* __restrict__ count_bits) {
-    __shared__ Out part[SCAN_THREADS];
+__device__ __forceinline__ Out exclusive_scan(const In* __restrict__ in, Out* __restrict__ out, size_t count, Out* part) {
     const int t = threadIdx.x;
-    const size_t f = blockIdx.x;
-    if (count_bits) count = stream_chunks(count_bits[f]);
-    in += f * stride, out += f * stride;
     const size_t per = (count + SCAN_THREADS - 1) / SCAN_THREADS;
     const size_t a = min((size_t)t * per, count), b = min(a + per, count);
     Out sum = 0;
@@ -603,7 +603,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void jpeg_scan_kernel(const In* __res
         out[i] = run;
         run += v;
     }
-    if (t == SCAN_THREADS - 1) total[f] = part[t];
+    return part[t];
+}
+
+// The scan over a frame's `count` entries (count_bits != nullptr: the chunks of that many coded bits), the sum to total[frame]
+template <class In, class Out>
+__global__ __launch_bounds__(SCAN_THREADS) void jpeg_scan_kernel(const In* __restrict__ in, Out* __restrict__ out, Out* __restrict__ total, size_t stride, size_t count,
+                                                                 const uint64_t* __restrict__ count_bits) {
+    __shared__ Out part[SCAN_THREADS];
+    const size_t f = blockIdx.x;
+    if (count_bits) count = stream_chunks(count_bits[f]);
+    const Out sum = exclusive_scan(in + f * stride, out + f * stride, count, part);
+    if (threadIdx.x == SCAN_THREADS - 1) total[f] = sum;
 }
 
 __global__ __launch_bounds__(256) void jpeg_zero_kernel(uint32_t* __restrict__ stream, size_t stream_words, const uint64_t* __restrict__ total_bits) {
@@ -706,6 +717,508 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(const uint32_t* __res
             const uint8_t byte = (uint8_t)(v >> (24 - 8 * k));
             *d++ = byte;
             if (byte == 255) *d++ = 0;
+        }
+    }
+}
+
+// ---- progressive files: libjpeg's jpeg_simple_progression ------------------------------------------------------------------------------
+// adain_jpeg_encode_progressive_u8: the file Pillow's save(progressive=True) writes.  The quantised coefficients are the baseline file's -
+// the transform stage is used unchanged - and only the entropy coding differs.  tests/jpeg_progressive_encode_ref.py restates the rules,
+// tests/test_jpeg_progressive_encode_host.py holds that to Pillow.
+//
+// The rules
+//   header   the baseline file's up to the frame header, which is SOF2 (FFC2); no DHT there: every scan brings its own
+//   scans    (Ss-Se, Ah, Al); colour, 10: DC of Y Cb Cr interleaved (0-0, 0, 1); Y (1-5, 0, 2); Cr (1-63, 0, 1); Cb (1-63, 0, 1); Y (6-63, 0, 2);
+//            Y (1-63, 2, 1); DC again (0-0, 1, 0); Cr (1-63, 1, 0); Cb (1-63, 1, 0); Y (1-63, 1, 0).  Grey, 6: DC (0-0, 0, 1); (1-5, 0, 2);
+//            (6-63, 0, 2); (1-63, 2, 1); DC (0-0, 1, 0); (1-63, 1, 0)
+//   tables   libjpeg forces optimize_coding: every scan that codes symbols is preceded by the DHT of the optimal table of its own symbol
+//            counts (the table stage above).  The first DC scan: class 0 id 0 (Y), then for colour class 0 id 1 (Cb and Cr counted
+//            together); an AC scan: class 1, id 0 for Y and 1 for chroma; the second DC scan has none.  SOS names only the table in use
+//   blocks   the DC scans are interleaved: MCU order, dummy luma blocks included, a dummy carrying the DC of the real block before it
+//            in its MCU.  An AC scan holds one component: its own grid row-major - Y ceil(h/8) x ceil(w/8) without the dummies, chroma
+//            the MCU grid.  No second copy of the coefficients: a scan's block index is mapped to the transform's block
+//   DC       first: v = DC >> Al (arithmetic), the difference to the component's previous v coded as baseline codes a DC.  Again: one raw
+//            bit per block, (DC >> Al) & 1
+//   AC first t = |coef| >> Al over the band; zeros extend the run r; a non-zero t writes the pending end-of-band run, a ZRL (0xF0) per 16
+//            of r, the symbol (r << 4) | bit_length(t) and t (a negative coefficient: ~t) in that many bits.  A block whose band ends in
+//            zeros adds 1 to EOBRUN, which is written as the symbol n << 4, n = floor(log2(EOBRUN)), and the low n bits of EOBRUN: before
+//            the next symbol, at the end of the scan, and at once when it reaches 0x7FFF
+//   AC again a = |coef| >> Al; EOB = the last a == 1 of the band.  a == 0 extends r; at every non-zero a, while r > 15 and k <= EOB: the
+//            pending run, a ZRL, then the correction bits buffered so far; a > 1 buffers its correction bit a & 1; a == 1 writes the pending
+//            run, (r << 4) | 1, a sign bit (0 negative, 1 positive) and the buffered bits.  A block with anything behind its EOB adds 1 to
+//            EOBRUN and its buffered bits to the run's; the run is written - symbol, count bits, then those bits - as above, and at once
+//            when it holds more than 937 bits (MAX_CORR_BITS - DCTSIZE2 + 1)
+//   data     every scan is padded to a byte with 1-bits and byte-stuffed on its own; FFD9 ends the file
+//
+// The stages (13 launches and a memset per call, every one over all n frames and all scans: a "unit" is one block of one scan)
+//   transform  the baseline encoder's, unchanged
+//   state      a wave per unit: does the block code a symbol, does it add to EOBRUN, how many correction bits does it leave to the run
+//   walk       a run is delimited by the blocks that code a symbol, and its 0x7FFF cuts lie at fixed offsets from its start, but the 937-bit
+//              cut is greedy in the bits gathered so far: no scan primitive places it.  So one wave per run walks its run from its first
+//              block, 64 blocks a step (a prefix sum over the lanes finds the next cut), and leaves per block the bits buffered before
+//              it and where its run is written, per written run its count and bits.  The walk is sequential in the steps: the worst
+//              case is one wave over a frame without detail, all blocks of a scan - 33 124 for a 1456 x 1456 frame, 518 steps; frames
+//              with detail have short runs and as many waves as runs
+//   histogram / table   the symbols per (frame, slot), the runs' n << 4 included, and their optimal codes: the stages of `optimize`
+//   count / scan / zero / emit   as the baseline stages, per (frame, scan); emit also places a lane's buffered bit behind the symbol of the
+//              lane that flushes it, or in its run's tail
+//   ffcount / scan / scatter   per (frame, scan); scatter adds up the scans' DHT, SOS and stuffed lengths and writes everything
+constexpr int PSCANS = 10;              // scans of a colour file; grey has 6
+constexpr int PSLOTS = 10;              // table slots per frame: 2 DC + 8 AC; grey uses 1 + 4
+constexpr int EOBRUN_CAP = 0x7fff;
+constexpr int CORR_CUT = 937;           // MAX_CORR_BITS - DCTSIZE2 + 1
+// The most bits a block can put into a scan when every code may be 16 bits long.  A coefficient counts in every scan that can spend bits on
+// it: a luma AC coefficient in three (first, and twice again), a chroma one in two.
+//   DC first   a code and an 11-bit difference; DC again: 1 bit
+//   run        the symbol and 14 count bits, at most once per block (the block that ends the run) and only when the band's last
+//              coefficient is not newly coded - that one is then zero (no bits) or costs its correction bit
+//   AC first   a code and 10 value bits per coefficient (a ZRL's 16 bits stand for 16 coefficients without any): m x 26, or (m - 1) x 26 + 30
+//   AC again   a code and a sign bit per new coefficient, one bit per old one: m x 17, or (m - 1) x 17 + 1 + 30
+constexpr int P_DC_FIRST_BITS = 16 + 11, P_RUN_BITS = 16 + 14;
+constexpr int prog_ac_bits(int m, bool again) { return again ? (m - 1) * 17 + 1 + P_RUN_BITS : (m - 1) * 26 + P_RUN_BITS; }
+constexpr int P_DHT_BYTES = 4 + 1 + 16 + 256;
+
+struct PScan {
+    int comp;                           // 0 Y, 1 Cb, 2 Cr; -1: every component, interleaved (the DC scans)
+    int ss, se, ah, al;
+    int slot;                           // the scan's table slot (first DC scan: Y's, the chroma one follows); -1: it codes no symbol
+    uint32_t nblk;                      // blocks in the scan
+    size_t unit0, word0, chunk0;        // its first unit, stream word and stuffing chunk among the frame's
+    size_t max_bytes;                   // entropy-coded bytes before stuffing, at most
+};
+struct PScript {
+    int c, hs, vs, mw, bw, bh, nscans, nslots;
+    size_t nblk, units, stream_words, chunks;          // per frame: coefficient blocks; units, stream words and chunks of all scans
+    PScan s[PSCANS];
+};
+struct ProgPlan {
+    Plan base;                          // the transform's geometry
+    PScript P;
+    size_t out_stride;
+    size_t o_coef, o_state, o_pre, o_run_n, o_run_be, o_run_end, o_body, o_bits, o_off, o_total, o_stream, o_ffcnt, o_ffoff, o_fftotal, o_hist, o_huff, total;
+};
+
+ProgPlan make_prog_plan(int n, int h, int w, int c, int sampling) {
+    static const int COLOUR[PSCANS][6] = {{-1, 0, 0, 0, 1, 0}, {0, 1, 5, 0, 2, 2}, {2, 1, 63, 0, 1, 3}, {1, 1, 63, 0, 1, 4}, {0, 6, 63, 0, 2, 5},
+                                          {0, 1, 63, 2, 1, 6}, {-1, 0, 0, 1, 0, -1}, {2, 1, 63, 1, 0, 7}, {1, 1, 63, 1, 0, 8}, {0, 1, 63, 1, 0, 9}};
+    static const int GREY[6][6] = {{-1, 0, 0, 0, 1, 0}, {0, 1, 5, 0, 2, 1}, {0, 6, 63, 0, 2, 2}, {0, 1, 63, 2, 1, 3}, {-1, 0, 0, 1, 0, -1}, {0, 1, 63, 1, 0, 4}};
+    ProgPlan p{};
+    p.base = make_plan(n, h, w, c, sampling, false);
+    PScript& P = p.P;
+    P.c = c, P.hs = p.base.hs, P.vs = p.base.vs, P.mw = p.base.mw, P.bw = p.base.bw, P.bh = p.base.bh;
+    P.nscans = c == 3 ? PSCANS : 6, P.nslots = c == 3 ? PSLOTS : 5;
+    P.nblk = p.base.nblk;
+    p.out_stride = HOST_T.dht[c == 3] + 2;
+    for (int i = 0; i < P.nscans; ++i) {
+        const int* d = c == 3 ? COLOUR[i] : GREY[i];
+        PScan& sc = P.s[i];
+        sc.comp = d[0], sc.ss = d[1], sc.se = d[2], sc.ah = d[3], sc.al = d[4], sc.slot = d[5];
+        const size_t nblk = sc.comp < 0 ? P.nblk : sc.comp == 0 ? (size_t)P.bw * P.bh : (size_t)P.mw * p.base.mh;
+        const int block_bits = sc.ss ? prog_ac_bits(sc.se - sc.ss + 1, sc.ah != 0) : sc.ah ? 1 : P_DC_FIRST_BITS;
+        sc.nblk = (uint32_t)nblk;
+        sc.max_bytes = (nblk * block_bits + 7) / 8;
+        sc.unit0 = P.units, sc.word0 = P.stream_words, sc.chunk0 = P.chunks;
+        P.units += nblk;
+        P.stream_words += (sc.max_bytes + 3) / 4 + 4;
+        P.chunks += (sc.max_bytes + CHUNK - 1) / CHUNK;
+        const int tables = sc.slot < 0 ? 0 : sc.ss == 0 && c == 3 ? 2 : 1, comps = sc.comp < 0 ? c : 1;
+        p.out_stride += tables * P_DHT_BYTES + 8 + 2 * comps + 2 * sc.max_bytes;
+    }
+    const size_t N = (size_t)n;
+    Carve ws;
+    p.o_coef = ws.take(N * P.nblk * 64 * sizeof(int16_t));
+    p.o_state = ws.take(N * P.units * sizeof(uint8_t));
+    p.o_pre = ws.take(N * P.units * sizeof(uint16_t));
+    p.o_run_n = ws.take(N * P.units * sizeof(uint16_t));
+    p.o_run_be = ws.take(N * P.units * sizeof(uint16_t));
+    p.o_run_end = ws.take(N * P.units * sizeof(uint32_t));
+    p.o_body = ws.take(N * P.units * sizeof(uint32_t));
+    p.o_bits = ws.take(N * P.units * sizeof(uint32_t));
+    p.o_off = ws.take(N * P.units * sizeof(uint64_t));
+    p.o_total = ws.take(N * PSCANS * sizeof(uint64_t));
+    p.o_stream = ws.take(N * P.stream_words * sizeof(uint32_t));
+    p.o_ffcnt = ws.take(N * P.chunks * sizeof(uint32_t));
+    p.o_ffoff = ws.take(N * P.chunks * sizeof(uint32_t));
+    p.o_fftotal = ws.take(N * PSCANS * sizeof(uint32_t));
+    p.o_hist = ws.take(N * PSLOTS * 256 * sizeof(uint64_t));
+    p.o_huff = ws.take(N * PSLOTS * sizeof(HuffSlot));
+    p.total = ws.at;
+    return p;
+}
+
+__device__ __forceinline__ uint64_t bits_upto(int p) { return p < 0 ? 0ull : p >= 63 ? ~0ull : (2ull << p) - 1; }          // bits 0..p
+__device__ __forceinline__ int top_bit(uint64_t m) { return m ? 63 - __clzll((long long)m) : -1; }
+
+__device__ __forceinline__ int prog_scan_of(const PScript& P, size_t unit) {
+    int s = 0;
+    while (s + 1 < P.nscans && unit >= P.s[s + 1].unit0) ++s;
+    return s;
+}
+
+// Block bi of a scan's own grid -> the block of the transform's array (MCU order: hs x vs luma blocks, Cb, Cr)
+__device__ __forceinline__ size_t prog_coef_block(const PScript& P, int comp, uint32_t bi) {
+    if (P.c != 3 || comp < 0) return bi;
+    const int nl = P.hs * P.vs, bpm = nl + 2;
+    if (comp > 0) return (size_t)bi * bpm + nl + comp - 1;
+    const uint32_t by = bi / (uint32_t)P.bw, bx = bi - by * (uint32_t)P.bw;
+    return ((size_t)(by / P.vs) * P.mw + bx / P.hs) * bpm + (by % P.vs) * P.hs + bx % P.hs;
+}
+
+// The DC of block b (MCU order): the transform leaves 0 in a dummy luma block, which carries the DC of the real block before it in its MCU
+__device__ int prog_dc(const int16_t* __restrict__ fc, const PScript& P, size_t b) {
+    if (P.c != 3) return fc[b * 64];
+    const int nl = P.hs * P.vs, bpm = nl + 2;
+    const size_t m = b / bpm;
+    int k = (int)(b - m * bpm);
+    if (k >= nl) return fc[b * 64];
+    const int mx = (int)(m % P.mw), my = (int)(m / P.mw);
+    while (!(P.hs * mx + k % P.hs < P.bw && P.vs * my + k / P.hs < P.bh)) --k;          // block 0 of an MCU is always real
+    return fc[(m * bpm + k) * 64];
+}
+
+// (DC >> al) minus the same of the component's block before b in the scan; *table: 0 luma, 1 chroma
+__device__ int prog_dc_difference(const int16_t* __restrict__ fc, const PScript& P, size_t b, int al, int* table) {
+    *table = 0;
+    if (P.c != 3) return (prog_dc(fc, P, b) >> al) - (b ? prog_dc(fc, P, b - 1) >> al : 0);
+    const int nl = P.hs * P.vs, bpm = nl + 2;
+    const size_t m = b / bpm;
+    const int k = (int)(b - m * bpm);
+    *table = k >= nl;
+    const bool none = k >= nl ? m == 0 : b == 0;
+    const size_t before = k >= nl ? b - bpm : k ? b - 1 : b - 3;          // luma block 0 follows the last luma block of the MCU before
+    return (prog_dc(fc, P, b) >> al) - (none ? 0 : prog_dc(fc, P, before) >> al);
+}
+
+// What lane k (coefficient k of a block) does in an AC scan.  "fresh": it codes a symbol - first scans: t != 0; later ones: a == 1.  "old":
+// later scans, a > 1: one correction bit, which waits for the next lane that flushes (a fresh one, or an old one in front of EOB with ZRLs
+// of its own) and follows that lane's first ZRL or, without one, its symbol and value bits; with no such lane it goes to the run's tail.
+struct PLane {
+    bool fresh, old;
+    int nzrl, sym, size, eob;           // ZRLs in front of it; its symbol; its value bits; the block's last fresh lane (-1: none)
+    uint32_t value, corr;
+    int waiting;                        // a lane that flushes: the old lanes' bits buffered for it
+    int flusher, rank;                  // an old lane: the lane that flushes its bit (-1: the run's tail) and its place among those bits
+    uint64_t old_mask;
+};
+
+__device__ __forceinline__ PLane prog_lane(int lane, int v, const PScan& sc) {
+    PLane L;
+    const bool in = lane >= sc.ss && lane <= sc.se;
+    const int a = in ? (v < 0 ? -v : v) >> sc.al : 0;
+    L.fresh = sc.ah ? a == 1 : a != 0;
+    L.old = sc.ah && a > 1;
+    const uint64_t fm = __ballot(L.fresh), zm = __ballot(in && a == 0), below = (1ull << lane) - 1;
+    L.old_mask = __ballot(L.old);
+    const int pn = max(top_bit(fm & below), sc.ss - 1);          // the fresh lane before this one, or the band's start
+    const uint64_t since = zm & ~bits_upto(pn);
+    const int zeros = __popcll(since & below);
+    const int pz = top_bit((fm | L.old_mask) & below);           // the non-zero lane before this one
+    const int given = pz > pn ? __popcll(since & bits_upto(pz)) >> 4 : 0;          // ZRLs written by then
+    L.eob = top_bit(fm);
+    L.nzrl = (L.fresh || L.old) && lane <= L.eob ? (zeros >> 4) - given : 0;
+    L.size = L.fresh ? 32 - __clz(a) : 0;
+    L.sym = ((zeros & 15) << 4) | L.size;
+    L.value = (uint32_t)(v < 0 ? ~a : a) & ((1u << L.size) - 1);
+    L.corr = (uint32_t)a & 1u;
+    const uint64_t flm = __ballot(L.fresh || L.nzrl > 0);
+    const uint64_t later = flm & ~bits_upto(lane);
+    L.flusher = later ? __ffsll((long long)later) - 1 : -1;
+    // an old lane that flushes buffers its own bit after that: the bits waiting at a lane are the old lanes from the last flush on
+    L.rank = __popcll(L.old_mask & below & ~bits_upto(top_bit(flm & bits_upto(lane)) - 1));
+    L.waiting = __popcll(L.old_mask & below & ~bits_upto(top_bit(flm & below) - 1));
+    return L;
+}
+
+// state: bit 0 - the block codes a symbol (which first writes the pending run); bit 1 - it adds to EOBRUN; bits 2..7 - the correction bits
+// it leaves to the run (old lanes behind its EOB)
+__global__ __launch_bounds__(256) void jpeg_prog_state_kernel(const int16_t* __restrict__ coef, PScript P, size_t total_units, uint8_t* __restrict__ state,
+                                                              uint16_t* __restrict__ run_n) {
+    const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= total_units) return;
+    const int lane = threadIdx.x & 63;
+    const size_t f = gw / P.units, u = gw - f * P.units;
+    const PScan& sc = P.s[prog_scan_of(P, u)];
+    int st = 0;
+    if (sc.ss) {
+        const int v = coef[(f * P.nblk + prog_coef_block(P, sc.comp, (uint32_t)(u - sc.unit0))) * 64 + lane];
+        const PLane L = prog_lane(lane, v, sc);
+        st = (L.eob >= 0 ? 1 : 0) | (L.eob != sc.se ? 2 : 0) | (__popcll(L.old_mask & ~bits_upto(L.eob)) << 2);
+    }
+    if (lane == 0) state[gw] = (uint8_t)st, run_n[gw] = 0;
+}
+
+// One wave per run, 64 blocks a step.  A run starts at a block that adds to EOBRUN and either codes a symbol (which wrote the run before
+// it), is the scan's first, or follows a block that added nothing; it goes on through the blocks that code no symbol.  Within a step the
+// bits gathered so far are a prefix sum over the lanes, and the next cut is the first lane at which they pass 937 or the count reaches
+// 0x7FFF; the walk goes on behind it with an empty run.  pre: the run's correction bits in front of the block's; at the block where a run
+// is written run_n, run_be: its count and correction bits; run_end: that block, for every block of the run.
+__global__ __launch_bounds__(256) void jpeg_prog_walk_kernel(PScript P, size_t total_units, const uint8_t* __restrict__ state, uint16_t* __restrict__ pre,
+                                                             uint16_t* __restrict__ run_n, uint16_t* __restrict__ run_be, uint32_t* __restrict__ run_end) {
+    const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= total_units) return;
+    const int lane = threadIdx.x & 63;
+    const size_t f = gw / P.units, u = gw - f * P.units;
+    const PScan& sc = P.s[prog_scan_of(P, u)];
+    if (sc.ss == 0) return;
+    const uint32_t bi = (uint32_t)(u - sc.unit0), s0 = state[gw];
+    if (!(s0 & 2) || (bi && !(s0 & 1) && (state[gw - 1] & 2))) return;
+    const size_t base = gw - bi;
+    uint32_t first = bi, count = 0, be = 0;          // the open run: its first block, its blocks and correction bits so far
+    auto write = [&](uint32_t e, uint32_t n, uint32_t bits) {
+        if (lane == 0) run_n[base + e] = (uint16_t)n, run_be[base + e] = (uint16_t)bits;
+        for (uint32_t i = first + lane; i <= e; i += 64) run_end[base + i] = e;
+    };
+    for (uint32_t j0 = bi;; j0 += 64) {
+        const uint32_t j = j0 + lane;
+        const uint32_t st = j < sc.nblk ? state[base + j] : 1u;          // the scan's end stops the run as a block that codes a symbol does
+        const uint64_t stops = __ballot((st & 1) && j != bi);
+        const int m = stops ? __ffsll((long long)stops) - 1 : 64;         // lanes 0..m-1 are blocks of the run
+        const uint32_t brt = lane < m ? st >> 2 : 0u;
+        uint32_t incl = brt;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        uint32_t before = 0;          // the bits of the lanes in front of `from`
+        for (int from = 0; from < m;) {
+            const uint32_t after = be + incl - before;
+            const uint64_t cuts = __ballot(lane >= from && lane < m && (after > CORR_CUT || count + lane - from + 1 == EOBRUN_CAP));
+            const int c = cuts ? __ffsll((long long)cuts) - 1 : m - 1;
+            if (lane >= from && lane <= c) pre[base + j] = (uint16_t)(after - brt);
+            const uint32_t bits = __shfl(after, c), n = count + c - from + 1;
+            if (cuts) {
+                write(j0 + c, n, bits);
+                first = j0 + c + 1, count = 0, be = 0;
+            } else {
+                count = n, be = bits;
+            }
+            before = __shfl(incl, c);
+            from = c + 1;
+        }
+        if (m < 64) {
+            if (count) write(j0 + m - 1, count, be);
+            return;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void jpeg_prog_histogram_kernel(const int16_t* __restrict__ coef, PScript P, const uint16_t* __restrict__ run_n,
+                                                                  unsigned long long* __restrict__ hist) {
+    __shared__ uint32_t cnt[PSLOTS][256];
+    const int lane = threadIdx.x & 63;
+    const size_t f = blockIdx.y;
+    for (int i = threadIdx.x; i < PSLOTS * 256; i += 256) (&cnt[0][0])[i] = 0;
+    __syncthreads();
+    const int16_t* fc = coef + f * P.nblk * 64;
+    for (size_t u = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < P.units; u += (size_t)gridDim.x * 4) {
+        const PScan& sc = P.s[prog_scan_of(P, u)];
+        if (sc.slot < 0) continue;
+        const uint32_t bi = (uint32_t)(u - sc.unit0);
+        if (sc.ss == 0) {
+            int table;
+            const int diff = prog_dc_difference(fc, P, bi, sc.al, &table);
+            if (lane == 0) atomicAdd(&cnt[sc.slot + table][32 - __clz(diff < 0 ? -diff : diff)], 1u);
+            continue;
+        }
+        const PLane L = prog_lane(lane, fc[prog_coef_block(P, sc.comp, bi) * 64 + lane], sc);
+        if (L.fresh) atomicAdd(&cnt[sc.slot][L.sym], 1u);
+        if (L.nzrl) atomicAdd(&cnt[sc.slot][0xf0], (uint32_t)L.nzrl);
+        const uint32_t rn = run_n[f * P.units + u];
+        if (lane == 0 && rn) atomicAdd(&cnt[sc.slot][(31 - __clz(rn)) << 4], 1u);
+    }
+    __syncthreads();
+    for (int k = 0; k < P.nslots; ++k) {
+        const uint32_t c = cnt[k][threadIdx.x];
+        if (c) atomicAdd(&hist[(f * PSLOTS + k) * 256 + threadIdx.x], (unsigned long long)c);
+    }
+}
+
+// count (EMIT false): body[unit] = the bits of the block's own symbols and of the correction bits among them; bits[unit] = that plus, where
+// a run is written, its symbol, count bits and correction bits.  emit: the same lanes OR their bits into the scan's stream.
+template <bool EMIT>
+__global__ __launch_bounds__(256) void jpeg_prog_code_kernel(const int16_t* __restrict__ coef, PScript P, size_t total_units, const HuffSlot* __restrict__ huff,
+                                                             const uint16_t* __restrict__ pre, const uint16_t* __restrict__ run_n, const uint16_t* __restrict__ run_be,
+                                                             const uint32_t* __restrict__ run_end, uint32_t* __restrict__ body, uint32_t* __restrict__ bits,
+                                                             const uint64_t* __restrict__ off, uint32_t* __restrict__ stream) {
+    const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= total_units) return;
+    const int lane = threadIdx.x & 63;
+    const size_t f = gw / P.units, u = gw - f * P.units;
+    const PScan& sc = P.s[prog_scan_of(P, u)];
+    const uint32_t bi = (uint32_t)(u - sc.unit0);
+    const int16_t* fc = coef + f * P.nblk * 64;
+    uint32_t* st = stream + f * P.stream_words + sc.word0;
+    const HuffSlot* tab = huff + f * PSLOTS + max(sc.slot, 0);
+    if (sc.ss == 0) {
+        uint64_t pat;
+        int len;
+        if (sc.ah) {
+            pat = (uint64_t)((prog_dc(fc, P, bi) >> sc.al) & 1), len = 1;
+        } else {
+            int table;
+            const int diff = prog_dc_difference(fc, P, bi, sc.al, &table);
+            const int size = 32 - __clz(diff < 0 ? -diff : diff);
+            tab += table;
+            pat = ((uint64_t)tab->code[size] << size) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << size) - 1));
+            len = tab->len[size] + size;
+        }
+        if (lane) return;
+        if (!EMIT) body[gw] = bits[gw] = (uint32_t)len;
+        else if (pat) or_bits(st, off[gw], pat, len);
+        return;
+    }
+    const PLane L = prog_lane(lane, fc[prog_coef_block(P, sc.comp, bi) * 64 + lane], sc);
+    const int zl = tab->len[0xf0], cl = L.fresh ? tab->len[L.sym] : 0;
+    const bool inside = L.old && L.flusher >= 0;          // its correction bit is among the block's symbols
+    const int len = L.nzrl * zl + cl + L.size + (inside ? 1 : 0);
+    int incl = len;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
+    }
+    const int total = __shfl(incl, 63);
+    const uint32_t rn = run_n[gw];
+    const int rk = rn ? 31 - __clz(rn) : 0, rl = rn ? tab->len[rk << 4] + rk : 0;
+    if (!EMIT) {
+        if (lane == 0) body[gw] = (uint32_t)total, bits[gw] = (uint32_t)(total + (rn ? rl + run_be[gw] : 0));
+        return;
+    }
+    const uint64_t at = off[gw];
+    // The lanes in front of a flushing lane that wait for it hold one bit each, so its group starts `waiting` bits before its own place.
+    // With ZRLs: the first ZRL, the waiting bits, then the rest; without: the symbol and value bits, then the waiting bits.
+    const int mine = incl - len, group = mine - L.waiting;
+    const int tail = group + (L.nzrl > 0 ? zl : cl + L.size);
+    const int tail_of = __shfl(tail, max(L.flusher, 0));
+    const uint64_t zc = tab->code[0xf0];
+    if (L.nzrl > 0) or_bits(st, at + group, zc, zl);
+    uint64_t pat = 0;
+    int plen = 0;
+    for (int k = 1; k < L.nzrl; ++k) pat = (pat << zl) | zc, plen += zl;
+    if (L.fresh) pat = (((pat << cl) | tab->code[L.sym]) << L.size) | L.value, plen += cl + L.size;
+    if (plen) or_bits(st, at + (L.nzrl > 0 ? mine + zl : group), pat, plen);
+    if (L.old && L.corr) {
+        uint64_t pos = at + tail_of + L.rank;
+        if (!inside) {          // the tail of the run the block is in: behind its symbol and count bits, in block order
+            const size_t e = gw - bi + run_end[gw];
+            const int ek = 31 - __clz((uint32_t)run_n[e]);
+            pos = off[e] + body[e] + tab->len[ek << 4] + ek + pre[gw] + L.rank;
+        }
+        or_bits(st, pos, 1, 1);
+    }
+    if (lane == 0 && rn) or_bits(st, at + total, ((uint64_t)tab->code[rk << 4] << rk) | (rn & ((1u << rk) - 1)), rl);
+}
+
+// out = the exclusive scan of a (frame, scan)'s entries - CHUNKS false: the units' bits; true: the 0xFF counts of the chunks its coded bits
+// fill - and the sum to total[frame][scan]
+template <class In, class Out, bool CHUNKS>
+__global__ __launch_bounds__(SCAN_THREADS) void jpeg_prog_scan_kernel(const In* __restrict__ in, Out* __restrict__ out, Out* __restrict__ total, PScript P,
+                                                                      const uint64_t* __restrict__ count_bits) {
+    __shared__ Out part[SCAN_THREADS];
+    const size_t f = blockIdx.y, slot = f * PSCANS + blockIdx.x;
+    const PScan& sc = P.s[blockIdx.x];
+    const size_t at = CHUNKS ? f * P.chunks + sc.chunk0 : f * P.units + sc.unit0;
+    const Out sum = exclusive_scan(in + at, out + at, CHUNKS ? stream_chunks(count_bits[slot]) : (size_t)sc.nblk, part);
+    if (threadIdx.x == SCAN_THREADS - 1) total[slot] = sum;
+}
+
+__global__ __launch_bounds__(256) void jpeg_prog_zero_kernel(uint32_t* __restrict__ stream, PScript P, const uint64_t* __restrict__ total_bits) {
+    const size_t f = blockIdx.y;
+    for (int k = 0; k < P.nscans; ++k) {
+        const size_t words = (size_t)((total_bits[f * PSCANS + k] + 31) >> 5) + 2;          // the plan keeps 4 beyond each scan's bound
+        uint32_t* s = stream + f * P.stream_words + P.s[k].word0;
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) s[i] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void jpeg_prog_ffcount_kernel(const uint32_t* __restrict__ stream, PScript P, const uint64_t* __restrict__ total_bits,
+                                                                uint32_t* __restrict__ ffcnt) {
+    __shared__ int part[4];
+    const size_t f = blockIdx.y;
+    for (int k = 0; k < P.nscans; ++k) {
+        const uint64_t bits = total_bits[f * PSCANS + k];
+        const uint32_t* s = stream + f * P.stream_words + P.s[k].word0;
+        for (size_t ck = blockIdx.x; ck < stream_chunks(bits); ck += gridDim.x) {
+            int valid;
+            const uint32_t v = stream_word(s, ck * (CHUNK / 4) + threadIdx.x, bits, &valid);
+            const int incl = workgroup_inclusive(count_ff(v, valid), part);
+            if (threadIdx.x == 255) ffcnt[f * P.chunks + P.s[k].chunk0 + ck] = (uint32_t)incl;
+        }
+    }
+}
+
+// What stands in front of a scan's data: the DHT segment of each of its tables (only the symbols that occur), then SOS
+__device__ __forceinline__ int prog_scan_tables(const PScript& P, const PScan& sc) { return sc.slot < 0 ? 0 : sc.ss == 0 && P.c == 3 ? 2 : 1; }
+__device__ __forceinline__ int prog_scan_components(const PScript& P, const PScan& sc) { return sc.comp < 0 ? P.c : 1; }
+__device__ int prog_scan_header_len(const PScript& P, const PScan& sc, const HuffSlot* __restrict__ huff) {
+    int len = 8 + 2 * prog_scan_components(P, sc);
+    for (int t = 0; t < prog_scan_tables(P, sc); ++t) len += 4 + 1 + 16 + (int)huff[sc.slot + t].nvals;
+    return len;
+}
+__device__ int prog_scan_header_byte(const PScript& P, const PScan& sc, const HuffSlot* __restrict__ huff, int j) {
+    for (int t = 0; t < prog_scan_tables(P, sc); ++t) {
+        const HuffSlot& k = huff[sc.slot + t];
+        const int payload = 2 + 1 + 16 + (int)k.nvals;
+        if (j < payload + 2)
+            return j == 0 ? 0xff : j == 1 ? 0xc4 : j == 2 ? payload >> 8 : j == 3 ? payload & 255 : j == 4 ? (sc.ss ? 0x10 | (sc.comp > 0) : t)
+                 : j < 21 ? k.bits[j - 5] : k.vals[j - 21];
+        j -= payload + 2;
+    }
+    const int comps = prog_scan_components(P, sc);
+    if (j < 5) return j == 0 ? 0xff : j == 1 ? 0xda : j == 2 ? 0 : j == 3 ? 6 + 2 * comps : comps;
+    j -= 5;
+    if (j < 2 * comps) {
+        const int i = j >> 1;
+        if (!(j & 1)) return sc.comp < 0 ? i + 1 : sc.comp + 1;
+        return sc.ss ? (sc.comp > 0 ? 0x01 : 0x00) : (sc.ah == 0 && i > 0 ? 0x10 : 0x00);
+    }
+    j -= 2 * comps;
+    return j == 0 ? sc.ss : j == 1 ? sc.se : (sc.ah << 4) | sc.al;
+}
+
+__global__ __launch_bounds__(256) void jpeg_prog_scatter_kernel(const uint32_t* __restrict__ stream, PScript P, const uint64_t* __restrict__ total_bits,
+                                                                const uint32_t* __restrict__ ffoff, const uint32_t* __restrict__ fftotal, int h, int w, int quality,
+                                                                int luma, const HuffSlot* __restrict__ huff, uint8_t* __restrict__ out, size_t out_stride,
+                                                                int32_t* __restrict__ lengths) {
+    __shared__ int part[4];
+    __shared__ size_t seg_at[PSCANS], data_at[PSCANS + 1];          // where each scan's DHT / SOS and its data start; [nscans]: FFD9
+    const size_t f = blockIdx.y;
+    const int rgb = P.c == 3;
+    huff += f * PSLOTS;
+    uint8_t* file = out + f * out_stride;
+    if (threadIdx.x == 0) {
+        size_t at = T.dht[rgb];
+        for (int k = 0; k < P.nscans; ++k) {
+            seg_at[k] = at, at += prog_scan_header_len(P, P.s[k], huff);
+            data_at[k] = at, at += stream_bytes(total_bits[f * PSCANS + k]) + fftotal[f * PSCANS + k];
+        }
+        data_at[P.nscans] = at;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < T.dht[rgb]; i += 256)
+            file[i] = i == T.sof_hw[rgb] - 4 ? 0xc2 : (uint8_t)header_byte<false>(i, rgb, h, w, quality, luma, nullptr, nullptr, 0);          // SOF2 for SOF0
+        for (int k = 0; k < P.nscans; ++k)
+            for (int j = threadIdx.x; j < (int)(data_at[k] - seg_at[k]); j += 256) file[seg_at[k] + j] = (uint8_t)prog_scan_header_byte(P, P.s[k], huff, j);
+        if (threadIdx.x == 0) {
+            const size_t end = data_at[P.nscans];
+            file[end] = 0xff, file[end + 1] = 0xd9;
+            lengths[f] = (int32_t)(end + 2);
+        }
+    }
+    for (int k = 0; k < P.nscans; ++k) {
+        const uint64_t bits = total_bits[f * PSCANS + k];
+        const uint32_t* s = stream + f * P.stream_words + P.s[k].word0;
+        for (size_t ck = blockIdx.x; ck < stream_chunks(bits); ck += gridDim.x) {
+            int valid;
+            const uint32_t v = stream_word(s, ck * (CHUNK / 4) + threadIdx.x, bits, &valid);
+            const int c = count_ff(v, valid);
+            const int before = workgroup_inclusive(c, part) - c;
+            uint8_t* d = file + data_at[k] + ck * CHUNK + ffoff[f * P.chunks + P.s[k].chunk0 + ck] + threadIdx.x * 4 + before;
+            for (int i = 0; i < valid; ++i) {
+                const uint8_t byte = (uint8_t)(v >> (24 - 8 * i));
+                *d++ = byte;
+                if (byte == 255) *d++ = 0;
+            }
         }
     }
 }
@@ -838,6 +1351,18 @@ void launch_entropy_stage(int stage, bool optimize, unsigned grid, int n, const 
         jpeg_emit_kernel<HS, VS, false><<<grid, 256, 0, s>>>(coef, off, stream, stream_words, g, blocks, huff);
 }
 
+// The transform stage of a plan's layout
+void launch_transform(const Plan& p, const uint8_t* src, int n, int h, int w, int c, int quality, int16_t* coef, hipStream_t s) {
+    if (c != 3)
+        jpeg_transform_grey_kernel<<<dim3((p.bw + GREY_PER_WG - 1) / GREY_PER_WG, p.bh, n), GREY_PER_WG * 8, 0, s>>>(src, h, w, quality, coef, p.bw, p.nblk);
+    else if (p.vs == 2)
+        jpeg_transform_rgb_kernel<<<dim3((p.mw + MCUS_PER_WG - 1) / MCUS_PER_WG, p.mh, n), MCUS_PER_WG * 48, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.bh, p.nblk);
+    else if (p.hs == 2)
+        jpeg_transform_rgb_h_kernel<2><<<dim3((p.mw + 7) / 8, p.mh, n), 256, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.nblk);
+    else
+        jpeg_transform_rgb_h_kernel<1><<<dim3((p.mw + 15) / 16, p.mh, n), 384, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.nblk);
+}
+
 }  // namespace
 
 // sampling 2, optimize 0: the default file, in 8 launches.  Other samplings change the transform and the scan order only; optimize adds
@@ -867,14 +1392,7 @@ int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int
     const size_t blocks = (size_t)n * p.nblk;
     // gridDim.y and .z are limited to 65535: h, w <= 65535 keep the block rows below that; the frames ride in z
     if (n > 65535 || (blocks + 3) / 4 > 0x7fffffffull) { set_error("%s: batch of %d frames too large for one call", who, n); return ADAIN_EINVAL; }
-    if (c != 3)
-        jpeg_transform_grey_kernel<<<dim3((p.bw + GREY_PER_WG - 1) / GREY_PER_WG, p.bh, n), GREY_PER_WG * 8, 0, s>>>(src, h, w, quality, coef, p.bw, p.nblk);
-    else if (p.vs == 2)
-        jpeg_transform_rgb_kernel<<<dim3((p.mw + MCUS_PER_WG - 1) / MCUS_PER_WG, p.mh, n), MCUS_PER_WG * 48, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.bh, p.nblk);
-    else if (p.hs == 2)
-        jpeg_transform_rgb_h_kernel<2><<<dim3((p.mw + 7) / 8, p.mh, n), 256, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.nblk);
-    else
-        jpeg_transform_rgb_h_kernel<1><<<dim3((p.mw + 15) / 16, p.mh, n), 384, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.nblk);
+    launch_transform(p, src, n, h, w, c, quality, coef, s);
     auto entropy = [&](int stage) {
         const unsigned grid = (unsigned)((blocks + 3) / 4);
         if (p.vs == 2) launch_entropy_stage<2, 2>(stage, optimize, grid, n, coef, bits, off, stream, p.stream_words, g, blocks, hist, huff, s);
@@ -884,7 +1402,7 @@ int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int
     if (optimize) {
         if (hipMemsetAsync(hist, 0, (size_t)n * SLOTS * 256 * sizeof(uint64_t), s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return ADAIN_EINVAL; }
         entropy(0);
-        jpeg_table_kernel<<<dim3(c == 3 ? 4 : 2, n), TABLE_THREADS, 0, s>>>(hist, huff);
+        jpeg_table_kernel<<<dim3(c == 3 ? 4 : 2, n), TABLE_THREADS, 0, s>>>(hist, huff, SLOTS);
     }
     entropy(1);
     jpeg_scan_kernel<uint32_t, uint64_t><<<n, SCAN_THREADS, 0, s>>>(bits, off, total, p.nblk, p.nblk, nullptr);
@@ -897,6 +1415,68 @@ int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int
         jpeg_scatter_kernel<true><<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffoff, fftotal, p.chunks, h, w, c == 3, quality, luma, huff, out, out_stride, lengths);
     else
         jpeg_scatter_kernel<false><<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffoff, fftotal, p.chunks, h, w, c == 3, quality, luma, huff, out, out_stride, lengths);
+    return check_launch(who);
+}
+
+int jpeg_encode_progressive_bytes(int n, int h, int w, int c, int sampling, size_t* out_stride, size_t* workspace_bytes) {
+    const char* who = "jpeg_encode_progressive_u8";
+    const char* bad = check_shape(n, h, w, c, 75);
+    if (!bad) bad = check_options(sampling, 0);
+    if (!bad && make_prog_plan(n, h, w, c, sampling).out_stride > (size_t)INT32_MAX) bad = "a worst-case file beyond 2^31 - 1 bytes (lengths are int32)";
+    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, sampling %d)", who, bad, n, h, w, c, sampling); return ADAIN_EINVAL; }
+    const ProgPlan p = make_prog_plan(n, h, w, c, sampling);
+    if (out_stride) *out_stride = p.out_stride;
+    if (workspace_bytes) *workspace_bytes = p.total;
+    return 0;
+}
+
+// 13 launches and a memset, whatever n: transform; state, walk; histogram, table; count, scan, zero, emit; ffcount, scan, scatter
+int launch_jpeg_encode_progressive_u8(const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, uint8_t* out, size_t out_stride, int32_t* lengths,
+                                      void* workspace, size_t workspace_bytes, hipStream_t s) {
+    const char* who = "jpeg_encode_progressive_u8";
+    const char* bad = check_shape(n, h, w, c, quality);
+    if (!bad) bad = check_options(sampling, 0);
+    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, quality %d, sampling %d)", who, bad, n, h, w, c, quality, sampling); return ADAIN_EINVAL; }
+    const ProgPlan p = make_prog_plan(n, h, w, c, sampling);
+    const PScript& P = p.P;
+    if (p.out_stride > (size_t)INT32_MAX) { set_error("%s: %d x %d x %d: a worst-case file beyond 2^31 - 1 bytes", who, h, w, c); return ADAIN_EINVAL; }
+    if (out_stride < p.out_stride) { set_error("%s: out_stride %zu below the %zu of the size query", who, out_stride, p.out_stride); return ADAIN_EINVAL; }
+    if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, 8)) return rc;
+    if ((uintptr_t)lengths % 4) { set_error("%s: lengths must be 4-byte aligned", who); return ADAIN_EINVAL; }
+    const size_t units = (size_t)n * P.units;
+    if (n > 65535 || (units + 3) / 4 > 0x7fffffffull) { set_error("%s: batch of %d frames too large for one call", who, n); return ADAIN_EINVAL; }
+    char* ws = (char*)workspace;
+    int16_t* coef = (int16_t*)(ws + p.o_coef);
+    uint8_t* state = (uint8_t*)(ws + p.o_state);
+    uint16_t* pre = (uint16_t*)(ws + p.o_pre);
+    uint16_t* run_n = (uint16_t*)(ws + p.o_run_n);
+    uint16_t* run_be = (uint16_t*)(ws + p.o_run_be);
+    uint32_t* run_end = (uint32_t*)(ws + p.o_run_end);
+    uint32_t* body = (uint32_t*)(ws + p.o_body);
+    uint32_t* bits = (uint32_t*)(ws + p.o_bits);
+    uint64_t* off = (uint64_t*)(ws + p.o_off);
+    uint64_t* total = (uint64_t*)(ws + p.o_total);
+    uint32_t* stream = (uint32_t*)(ws + p.o_stream);
+    uint32_t* ffcnt = (uint32_t*)(ws + p.o_ffcnt);
+    uint32_t* ffoff = (uint32_t*)(ws + p.o_ffoff);
+    uint32_t* fftotal = (uint32_t*)(ws + p.o_fftotal);
+    unsigned long long* hist = (unsigned long long*)(ws + p.o_hist);
+    HuffSlot* huff = (HuffSlot*)(ws + p.o_huff);
+    launch_transform(p.base, src, n, h, w, c, quality, coef, s);
+    if (hipMemsetAsync(hist, 0, (size_t)n * PSLOTS * 256 * sizeof(uint64_t), s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return ADAIN_EINVAL; }
+    const unsigned waves = (unsigned)((units + 3) / 4);
+    jpeg_prog_state_kernel<<<waves, 256, 0, s>>>(coef, P, units, state, run_n);
+    jpeg_prog_walk_kernel<<<waves, 256, 0, s>>>(P, units, state, pre, run_n, run_be, run_end);
+    jpeg_prog_histogram_kernel<<<dim3(HIST_GRID, n), 256, 0, s>>>(coef, P, run_n, hist);
+    jpeg_table_kernel<<<dim3(P.nslots, n), TABLE_THREADS, 0, s>>>(hist, huff, PSLOTS);
+    jpeg_prog_code_kernel<false><<<waves, 256, 0, s>>>(coef, P, units, huff, pre, run_n, run_be, run_end, body, bits, off, stream);
+    jpeg_prog_scan_kernel<uint32_t, uint64_t, false><<<dim3(P.nscans, n), SCAN_THREADS, 0, s>>>(bits, off, total, P, nullptr);
+    jpeg_prog_zero_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, P, total);
+    jpeg_prog_code_kernel<true><<<waves, 256, 0, s>>>(coef, P, units, huff, pre, run_n, run_be, run_end, body, bits, off, stream);
+    jpeg_prog_ffcount_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, P, total, ffcnt);
+    jpeg_prog_scan_kernel<uint32_t, uint32_t, true><<<dim3(P.nscans, n), SCAN_THREADS, 0, s>>>(ffcnt, ffoff, fftotal, P, total);
+    const int luma = c == 3 ? P.hs << 4 | P.vs : 0x11;
+    jpeg_prog_scatter_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, P, total, ffoff, fftotal, h, w, quality, luma, huff, out, out_stride, lengths);
     return check_launch(who);
 }
 

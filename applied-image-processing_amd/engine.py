@@ -207,11 +207,11 @@ class AdaINEngine:
         """One step of the video recurrence: blend(cur, warp(prev, flow), alpha) on uint8 HWC frames (video/utils.py:89-105, :223-229)."""
         return rt.warp_blend_u8(cur, prev, flow, alpha)
 
-    def jpeg_encode_u8(self, frames_u8, quality=rt.JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
+    def jpeg_encode_u8(self, frames_u8, quality=rt.JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False, progressive=False):
         """The files ``PIL.Image.fromarray(frame).save(f, format="JPEG", quality=quality, subsampling=subsampling, optimize=optimize)``
-        writes for uint8 frames [n,h,w,3|1] on the device, encoded there (adain_jpeg_encode_u8 at the defaults, else
-        adain_jpeg_encode_opt_u8; ``runtime.jpeg_encode_u8``) -> a list of n ``bytes``; only the files cross to the host."""
-        return rt.jpeg_files(*rt.jpeg_encode_u8(frames_u8, quality, subsampling, optimize))
+        writes (with ``progressive``: the same call with ``progressive=True``) for uint8 frames [n,h,w,3|1] on the device, encoded there
+        (adain_jpeg_encode_u8 at the defaults, else adain_jpeg_encode_opt_u8 or adain_jpeg_encode_progressive_u8; ``runtime.jpeg_encode_u8``) -> a list of n ``bytes``; only the files cross to the host."""
+        return rt.jpeg_files(*rt.jpeg_encode_u8(frames_u8, quality, subsampling, optimize, progressive))
 
     def jpeg_decode_u8(self, files, chunk_bits=0, mode=None, report=None, restart=False, progressive=False):
         """The bytes of image files (a list, or one ``bytes``) -> uint8 tensors on the engine's device, the pixels Pillow's ``Image.open``

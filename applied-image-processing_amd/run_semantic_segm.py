@@ -8,7 +8,7 @@ It calls ``localized.run_localized_style_transfer`` (reference Style_3DGS/locali
 composite.  Extra flags make it usable offline (the reference downloads DeepLabV3 and MiDaS at run time): ``--mask_npy`` takes a
 precomputed background mask ([1,H,W] or [H,W], 1 = background), ``--depth_npy`` a proximity map, ``--vgg`` / ``--decoder`` the
 checkpoint paths, ``--colour_on_device`` moves the colour transfer and the composite to the GPU, ``--jpeg_on_device`` the JPEG encode of the intermediate
-stylised file and of the final composite (the same bytes); ``--jpeg_quality``, ``--jpeg_subsampling``, ``--jpeg_optimize`` are Pillow's
+stylised file and of the final composite (the same bytes); ``--jpeg_quality``, ``--jpeg_subsampling``, ``--jpeg_optimize``, ``--jpeg_progressive`` are Pillow's
 keywords for the final composite's file, on either route.  Without ``--mask_npy`` a provider must have been registered (``localized.set_mask_provider``).
 """
 import argparse
@@ -37,6 +37,7 @@ _EXTRA_FLAGS = (
     ("--jpeg_quality", dict(type=int, default=75, help="Pillow's quality of the final composite's JPEG, 1..100")),
     ("--jpeg_subsampling", dict(type=str, default="4:2:0", choices=["4:4:4", "4:2:2", "4:2:0"], help="chroma subsampling of the final composite's JPEG")),
     ("--jpeg_optimize", dict(action="store_true", help="give the final composite's JPEG its own optimal Huffman tables (Pillow's optimize=True)")),
+    ("--jpeg_progressive", dict(action="store_true", help="write the final composite's JPEG as a progressive file (Pillow's progressive=True)")),
 )
 
 
@@ -56,7 +57,7 @@ def main(argv=None):
     try:
         return run_localized_style_transfer(content_img_path=ns.content, style_img_path=ns.style, output_path=ns.output, file_name=ns.file_name,
                                             use_depth=ns.use_depth, background_mask=mask, colour_on_device=ns.colour_on_device,
-                                            jpeg_on_device=ns.jpeg_on_device, jpeg_options=(ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize),
+                                            jpeg_on_device=ns.jpeg_on_device, jpeg_options=(ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize, ns.jpeg_progressive),
                                             **extra)
     finally:
         set_jpeg_routes(prev)

@@ -101,6 +101,8 @@ SIGNATURES = {
     "adain_jpeg_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_jpeg_encode_progressive_u8_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
+    "adain_jpeg_encode_progressive_u8": (_c_int, [_c_void_p] + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_roundtrip_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_roundtrip_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_decode_u8_bytes": (_c_int, [_c_int] * 5 + [_c_size_t, _c_int, ctypes.POINTER(_c_size_t)]),
@@ -860,10 +862,10 @@ def jpeg_subsampling(subsampling, what="jpeg_encode_u8"):
     return subsampling
 
 
-def _jpeg_optimize(optimize, what):
-    if isinstance(optimize, int) and optimize in (0, 1):          # bool is an int
-        return int(optimize)
-    raise AdainHipError(f"{what}: optimize must be False or True, got {optimize!r}")
+def _jpeg_flag(value, what, name):
+    if isinstance(value, int) and value in (0, 1):          # bool is an int
+        return int(value)
+    raise AdainHipError(f"{what}: {name} must be False or True, got {value!r}")
 
 
 def is_jpeg_path(path):
@@ -911,30 +913,38 @@ class _Value:
 
 class JpegOptions(_Value):
     """How to save a JPEG: Pillow's ``quality`` (1..100, default 75), ``subsampling`` (0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0", default
-    4:2:0) and ``optimize`` (the file's own optimal Huffman tables, default off) - the keywords the device encoder covers.  The defaults
-    are Pillow's default save.  One value for both routes of a caller: ``encode`` is the device's (``jpeg_encode_u8``), ``save`` the
+    4:2:0), ``optimize`` (the file's own optimal Huffman tables, default off) and ``progressive`` (libjpeg's simple progression, every
+    scan under its own optimal table, default off; ``optimize`` has no effect with it, as in Pillow) - the keywords the device encoder
+    covers.  The defaults are Pillow's default save.  One value for both routes of a caller: ``encode`` is the device's (``jpeg_encode_u8``), ``save`` the
     host's (``Image.save`` with the same keywords), and the files are the same.  An L image ignores ``subsampling`` on both routes: its
-    file is the one Pillow writes without the keyword.  What stays with Pillow alone: ``progressive=True``, ``qtables=``,
-    ``quality="keep"``, EXIF / ICC / comments / DPI, restart markers, CMYK.  AdainHipError for a value outside these."""
-    __slots__ = ("quality", "subsampling", "optimize")
+    file is the one Pillow writes without the keyword.  ``repr`` and ``save_kwargs`` name ``progressive`` only when it is set.  What
+    stays with Pillow alone: ``qtables=``, ``quality="keep"``, EXIF / ICC / comments / DPI, restart markers, CMYK, arithmetic coding,
+    scan scripts other than libjpeg's simple progression.  AdainHipError for a value outside these."""
+    __slots__ = ("quality", "subsampling", "optimize", "progressive")
 
-    def __init__(self, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
+    def __init__(self, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False, progressive=False):
         if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
             raise AdainHipError(f"JpegOptions: quality must be an int in 1..100, got {quality!r}")
-        self._set(quality=quality, subsampling=jpeg_subsampling(subsampling, "JpegOptions"), optimize=bool(_jpeg_optimize(optimize, "JpegOptions")))
+        self._set(quality=quality, subsampling=jpeg_subsampling(subsampling, "JpegOptions"), optimize=bool(_jpeg_flag(optimize, "JpegOptions", "optimize")),
+                  progressive=bool(_jpeg_flag(progressive, "JpegOptions", "progressive")))
 
     @classmethod
     def of(cls, value):
-        """None -> the defaults; a JpegOptions -> itself; a (quality, subsampling, optimize) tuple or a dict of keywords -> the value."""
+        """None -> the defaults; a JpegOptions -> itself; a (quality, subsampling, optimize[, progressive]) tuple or a dict of keywords -> the
+        value."""
         if isinstance(value, (tuple, list)):
             return cls(*value)
         if value is None or isinstance(value, dict) or type(value).__name__ == cls.__name__:
             return super().of(value)
-        raise AdainHipError(f"jpeg_options: expected JpegOptions, a (quality, subsampling, optimize) tuple, a dict or None, got {value!r}")
+        raise AdainHipError(f"jpeg_options: expected JpegOptions, a (quality, subsampling, optimize[, progressive]) tuple, a dict or None, got {value!r}")
 
     @property
     def is_default(self):
-        return self._key() == (JPEG_DEFAULT_QUALITY, 2, False)
+        return self._key() == (JPEG_DEFAULT_QUALITY, 2, False, False)
+
+    def __repr__(self):
+        fields = [(name, value) for name, value in zip(self.__slots__, self._key()) if name != "progressive" or value]
+        return f"JpegOptions({', '.join(f'{name}={value!r}' for name, value in fields)})"
 
     def save_kwargs(self, mode="RGB"):
         """The keywords of ``Image.save`` for an image of ``mode``: none at the defaults (today's call), no ``subsampling`` for L."""
@@ -943,14 +953,16 @@ class JpegOptions(_Value):
         kw = {"quality": self.quality, "optimize": self.optimize}
         if mode != "L":
             kw["subsampling"] = self.subsampling
+        if self.progressive:
+            kw["progressive"] = True
         return kw
 
     def save(self, img, path):
         """The host route: ``img.save(path)``, with these keywords for a .jpg / .jpeg path only - other extensions never see them.
-        Pillow sizes its encoder buffer for ``optimize`` at width x height bytes and fails ("broken data stream") on a frame whose file
+        Pillow sizes its encoder buffer for ``optimize`` or ``progressive`` at width x height bytes and fails ("broken data stream") on a frame whose file
         is larger, which a noisy 4:4:4 frame is: ImageFile.MAXBLOCK, Pillow's knob for it, is raised to the worst case first."""
         kw = self.save_kwargs(img.mode) if is_jpeg_path(path) else {}
-        if kw.get("optimize"):
+        if kw.get("optimize") or kw.get("progressive"):
             from PIL import ImageFile
 
             ImageFile.MAXBLOCK = max(ImageFile.MAXBLOCK, 4 * img.size[0] * img.size[1] * len(img.getbands()) + 4096)
@@ -958,7 +970,7 @@ class JpegOptions(_Value):
 
     def encode(self, u8):
         """The device route: ``jpeg_encode_u8`` with these options -> (files, lengths) on the device."""
-        return jpeg_encode_u8(u8, self.quality, self.subsampling, self.optimize)
+        return jpeg_encode_u8(u8, self.quality, self.subsampling, self.optimize, self.progressive)
 
 
 class JpegRoutes(_Value):
@@ -1006,34 +1018,42 @@ class JpegRoutes(_Value):
         return jpeg_decode_rgb_file(path, device, self.decode_progressive) if self.decode_on_device else None
 
 
-def jpeg_encode_sizes(n, h, w, c, subsampling=2, optimize=False):
-    """(out_stride, workspace_bytes) of adain_jpeg_encode_opt_u8_bytes (at the defaults: adain_jpeg_encode_u8_bytes' values): the
-    largest file a frame of this shape can have and the scratch of an n-frame call.  Host only.  AdainHipError for a refused shape."""
-    return tuple(_jpeg_sizes("adain_jpeg_encode_opt_u8_bytes", n, h, w, c, jpeg_subsampling(subsampling, "jpeg_encode_sizes"),
-                             _jpeg_optimize(optimize, "jpeg_encode_sizes"), results=2))
+def jpeg_encode_sizes(n, h, w, c, subsampling=2, optimize=False, progressive=False):
+    """(out_stride, workspace_bytes) of adain_jpeg_encode_opt_u8_bytes (at the defaults: adain_jpeg_encode_u8_bytes' values; with
+    ``progressive``: adain_jpeg_encode_progressive_u8_bytes', whatever ``optimize``): the largest file a frame of this shape can have
+    and the scratch of an n-frame call.  Host only.  AdainHipError for a refused shape."""
+    sampling, optimize = jpeg_subsampling(subsampling, "jpeg_encode_sizes"), _jpeg_flag(optimize, "jpeg_encode_sizes", "optimize")
+    if _jpeg_flag(progressive, "jpeg_encode_sizes", "progressive"):
+        return tuple(_jpeg_sizes("adain_jpeg_encode_progressive_u8_bytes", n, h, w, c, sampling, results=2))
+    return tuple(_jpeg_sizes("adain_jpeg_encode_opt_u8_bytes", n, h, w, c, sampling, optimize, results=2))
 
 
-def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False):
+def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False, progressive=False):
     """Frames uint8 [n,h,w,c] (c = 3: RGB, 1: L; or one frame [h,w,c] / [h,w]) -> (files uint8 [n, stride], lengths int32 [n]), both on the
     device: row i starts with frame i's JPEG file, ``lengths[i]`` bytes, byte for byte what ``PIL.Image.fromarray(frame).save(f,
     format="JPEG", quality=quality, subsampling=subsampling, optimize=optimize)`` writes; the rest of the row is not written.
     ``subsampling``: 0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0" (the default, Pillow's own); L frames ignore it and get the file Pillow writes
     without the keyword.  ``optimize``: the frame's own optimal Huffman tables.  The defaults give Pillow's default file
-    (adain_jpeg_encode_u8).  Nothing is copied to the host and nothing waits."""
-    sampling, optimize = jpeg_subsampling(subsampling), _jpeg_optimize(optimize, "jpeg_encode_u8")
+    (adain_jpeg_encode_u8).  ``progressive``: the file of ``save(..., progressive=True)`` (adain_jpeg_encode_progressive_u8), on which
+    ``optimize`` has no effect, as in Pillow.  Nothing is copied to the host and nothing waits."""
+    sampling, optimize = jpeg_subsampling(subsampling), _jpeg_flag(optimize, "jpeg_encode_u8", "optimize")
+    progressive = _jpeg_flag(progressive, "jpeg_encode_u8", "progressive")
     x = _jpeg_frames(u8, "jpeg_encode_u8", quality)
     n, h, w, c = x.shape
     stride = 0
 
     def sizes():                # one query answers both: the file stride is kept for the output below
         nonlocal stride
-        stride, nbytes = jpeg_encode_sizes(n, h, w, c, sampling, optimize)
+        stride, nbytes = jpeg_encode_sizes(n, h, w, c, sampling, optimize, progressive)
         return nbytes
 
     with scratch(x.device, "jpeg", sizes) as ws:
         out = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
         lengths = torch.empty((n,), dtype=torch.int32, device=x.device)
-        if (sampling, optimize) == (2, 0):
+        if progressive:
+            _launch("adain_jpeg_encode_progressive_u8", x.data_ptr(), n, h, w, c, quality, sampling, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(),
+                    ws.numel())
+        elif (sampling, optimize) == (2, 0):
             _launch("adain_jpeg_encode_u8", x.data_ptr(), n, h, w, c, quality, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
         else:
             _launch("adain_jpeg_encode_opt_u8", x.data_ptr(), n, h, w, c, quality, sampling, optimize, out.data_ptr(), stride, lengths.data_ptr(),

@@ -494,6 +494,33 @@ ADAIN_API int adain_jpeg_encode_opt_u8(const uint8_t* src_u8, int n, int h, int 
                                        uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes,
                                        adain_stream_t stream);
 
+/* adain_jpeg_encode_opt_u8 with Pillow's `progressive` keyword: frame i's file is byte for byte what Image.fromarray(frame).save(f,
+ * format="JPEG", quality=quality, subsampling=sampling, progressive=True) writes (established against Pillow 12.2.0 built with
+ * libjpeg-turbo; the rules are listed in csrc/jpeg.hip under "progressive files" and restated in tests/jpeg_progressive_encode_ref.py).
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * The quantised coefficients are adain_jpeg_encode_opt_u8's; the file is SOF2 with libjpeg's jpeg_simple_progression script - 10 scans
+ * for RGB (the Cr scans before the Cb scans), 6 for L - and, as libjpeg forces optimize_coding for progressive files, every scan that
+ * codes symbols is preceded by the DHT of the optimal table of its own symbol counts: there is no `optimize` argument, Pillow's
+ * progressive=True and progressive=True, optimize=True are the same file.  sampling: as above, ignored for c = 1.
+ * adain_jpeg_encode_progressive_u8_bytes (host only): an overflow is impossible, not detected.  Every code may be 16 bits long, and a
+ *   coefficient counts in every scan that can spend bits on it (a luma AC coefficient in three, a chroma one in two).  Per block of a
+ *   scan: the first DC scan 16 + 11 bits, the second 1; a first AC scan over m coefficients 26 (m - 1) + 30 (a code and 10 value bits
+ *   each; the 30 are an end-of-band run's code and 14 count bits, which a block writes at most once and only when its last coefficient
+ *   is not coded); a later AC scan 17 (m - 1) + 1 + 30 (a code and a sign bit per new coefficient, one correction bit per old one).
+ *   B_s blocks in scan s - the DC scans: the MCU order, dummy luma blocks included; a luma AC scan: ceil(h/8) * ceil(w/8); a chroma AC
+ *   scan: the MCUs - give E_s = ceil(bits_s B_s / 8) bytes, stuffing at most doubles them, and each scan adds at most 277 bytes per DHT
+ *   (two in the first DC scan of an RGB file) and its SOS: out_stride = the header up to SOF2 + sum over the scans + 2.
+ *   *workspace_bytes = the coefficients, per block and scan the run state, bit counts and offsets, the scans' unstuffed bit streams and
+ *   the symbol counts and code tables of n frames.  Either output may be NULL.
+ * Refused with ADAIN_EINVAL before anything is launched: everything adain_jpeg_encode_opt_u8 refuses.  Bytes of `out` behind a file
+ * are not written.  Nothing is copied to the host and nothing waits; 13 kernel launches and one memset per call, whatever n.  One of
+ * them walks each end-of-band run with one wave, 64 blocks a step (libjpeg cuts a run greedily once it holds more than 937 correction
+ * bits, which no parallel scan places): a frame without any detail is one run per scan and one wave walks all its blocks. */
+ADAIN_API int adain_jpeg_encode_progressive_u8_bytes(int n, int h, int w, int c, int sampling, size_t* out_stride, size_t* workspace_bytes);
+ADAIN_API int adain_jpeg_encode_progressive_u8(const uint8_t* src_u8, int n, int h, int w, int c, int quality, int sampling, uint8_t* out,
+                                               size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes,
+                                               adain_stream_t stream);
+
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
  * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)

@@ -1,0 +1,266 @@
+"""The byte-identity contract of the device JPEG encoder's progressive files, settled on the host: the restatement of its rules
+(tests/jpeg_progressive_encode_ref.py) writes the files Pillow's ``Image.save(f, format="JPEG", quality=q, subsampling=s,
+progressive=True)`` writes - no tolerance - so that the GPU tests can hold the kernels to Pillow directly.  Two designed frames reach the
+rules ordinary content never does: "stripes" the cut of an end-of-band run that holds more than 937 correction bits, a flat 1456 x 1456
+frame the cut at 0x7FFF blocks.  Then the C ABI's host side (symbols, refusals, the size bound) and the Python surface.
+
+An L frame ignores ``subsampling`` as everywhere else in the encoder: its file is held to Pillow's without the keyword."""
+import ctypes
+import io
+import os
+import re
+
+import numpy as np
+import pytest
+from PIL import Image, ImageFile
+
+import jpeg_progressive_encode_ref as R
+import jpeg_progressive_ref as D
+import jpeg_ref as J
+from conftest import ROOT
+
+MODES = [(3, 0), (3, 1), (3, 2), (1, 2)]
+MODE_IDS = ["RGB-0", "RGB-1", "RGB-2", "L"]
+AC_AGAIN = [(1, 63, 2, 1), (1, 63, 1, 0)]
+AC_SCANS = [(1, 5, 0, 2), (6, 63, 0, 2)] + AC_AGAIN
+
+
+def pillow_bytes(a, quality=75, subsampling=2, **more):
+    """Pillow's progressive file.  Its encoder buffer for progressive is w * h bytes, which a noise frame overruns: ImageFile.MAXBLOCK,
+    Pillow's documented knob, is raised for the call."""
+    kw = dict(quality=quality, progressive=True, **more)
+    if a.ndim == 3:
+        kw["subsampling"] = subsampling
+    f = io.BytesIO()
+    old, ImageFile.MAXBLOCK = ImageFile.MAXBLOCK, max(ImageFile.MAXBLOCK, 4 * a.size + 4096)
+    try:
+        Image.fromarray(a).save(f, format="JPEG", **kw)
+    finally:
+        ImageFile.MAXBLOCK = old
+    return f.getvalue()
+
+
+def cuts_of(report):
+    return {scan[1:]: cuts for scan, cuts in report if scan[1]}
+
+
+# every shape at the default quality; the other qualities on three shapes (as the option tests thin theirs)
+@pytest.mark.parametrize("c,s", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("h,w", J.SHAPES + [(17, 23)])
+def test_restatement_equals_pillow(h, w, c, s):
+    for kind in J.CONTENTS:
+        a = J.content(kind, h, w, c)
+        assert R.encode(a, 75, s) == pillow_bytes(a, 75, s), kind
+
+
+@pytest.mark.parametrize("quality", [30, 95, 100])
+@pytest.mark.parametrize("c,s", MODES, ids=MODE_IDS)
+def test_restatement_equals_pillow_at_other_qualities(c, s, quality):
+    for (h, w) in [(17, 9), (37, 53), (40, 72)]:
+        for kind in J.CONTENTS:
+            a = J.content(kind, h, w, c)
+            assert R.encode(a, quality, s) == pillow_bytes(a, quality, s), (h, w, kind)
+
+
+def test_optimize_changes_nothing():
+    for c, s in MODES:
+        a = J.content("smooth", 37, 53, c)
+        assert pillow_bytes(a, 75, s, optimize=True) == pillow_bytes(a, 75, s) == R.encode(a, 75, s)
+
+
+def test_the_file_is_one_the_progressive_decoder_takes():
+    for c, s in MODES:
+        for kind in ("noise", "smooth"):
+            a = J.content(kind, 37, 53, c)
+            data = R.encode(a, 75, s)
+            want = np.asarray(Image.open(io.BytesIO(data)).convert("RGB" if c == 3 else "L"))
+            got, status, _ = D.decode(data)
+            assert status == 0 and np.array_equal(np.asarray(got).reshape(want.shape), want), (c, s, kind)
+
+
+def test_the_header_and_the_scans():
+    data = R.encode(J.content("smooth", 17, 23, 3), 75, 2)
+    assert data.count(b"\xff\xc2") == 1 and b"\xff\xc0" not in data[:data.index(b"\xff\xda")]
+    assert data.index(b"\xff\xc4") > data.index(b"\xff\xc2")                     # no table in front of the frame header
+    sos = [m.start() for m in re.finditer(b"\xff\xda\x00", data)]
+    assert len(sos) == 10 and data[sos[0] + 4:sos[0] + 14] == bytes([3, 1, 0x00, 2, 0x10, 3, 0x10, 0, 0, 0x01])
+    assert [data[p + 4:p + 10] for p in sos[1:4]] == [bytes([1, 1, 0x00, 1, 5, 0x02]), bytes([1, 3, 0x01, 1, 63, 0x01]), bytes([1, 2, 0x01, 1, 63, 0x01])]
+    mcu, comp, grids = R.components(J.content("smooth", 17, 23, 3), 75, 2)
+    assert len(mcu) == 2 * 2 * 6 and grids[0].shape[:2] == (3, 3) and grids[1].shape[:2] == (2, 2)          # Y without the dummies
+
+
+# ---- the designed frames ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rgb", [False, True], ids=["L", "RGB"])
+def test_stripes_cut_a_run_by_its_correction_bits(rgb, monkeypatch):
+    a = R.stripes()
+    a = np.stack([a] * 3, axis=-1) if rgb else a
+    report = []
+    data = R.encode(a, 75, 2, report)
+    cuts = cuts_of(report)
+    # RGB repeats (1, 63, 1, 0) for the chroma scans: the dict keeps the last, Y's
+    assert all(cuts[scan]["corr"] >= 1 for scan in AC_AGAIN), cuts
+    assert data == pillow_bytes(a, 75, 2)
+    monkeypatch.setattr(R, "CORR_CUT", 1 << 30)
+    assert R.encode(a, 75, 2) != data                                             # without the rule the file differs
+
+
+def test_a_flat_frame_cuts_its_runs_at_the_cap():
+    a = R.flat()
+    assert (a.shape[0] // 8) ** 2 == 33124 > R.EOBRUN_CAP
+    report = []
+    data = R.encode(a, 75, 2, report)
+    cuts = cuts_of(report)
+    assert all(cuts[scan]["cap"] >= 1 for scan in AC_SCANS), cuts
+    assert data == pillow_bytes(a, 75, 2)
+
+
+# ---- the C ABI's host side -----------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def rt():
+    import applied_image_processing_amd.runtime as rt
+
+    rt.lib()
+    return rt
+
+
+def test_symbols_are_declared_bound_and_exported(rt):
+    header = open(os.path.join(ROOT, "include", "adain_hip.h")).read()
+    for name in ("adain_jpeg_encode_progressive_u8_bytes", "adain_jpeg_encode_progressive_u8"):
+        assert re.search(rf"ADAIN_API int {name}\(", header) and name in rt.SIGNATURES and hasattr(rt.lib(), name)
+    assert rt.lib().adain_abi_version() == 4 and "#define ADAIN_ABI_VERSION 4" in header
+
+
+def scan_block_bits(scan):
+    """The header's derivation of the most bits a block puts into a scan (every code 16 bits long)."""
+    comps, ss, se, ah, al = scan
+    m = se - ss + 1
+    if ss == 0:
+        return 1 if ah else 16 + 11
+    return 17 * (m - 1) + 1 + 30 if ah else 26 * (m - 1) + 30
+
+
+def stride_of(h, w, c, s):
+    hs, vs = R.O.SUBSAMPLING[s] if c == 3 else (1, 1)
+    mcus = -(-h // (8 * vs)) * -(-w // (8 * hs))
+    blocks = {None: mcus * (hs * vs + 2) if c == 3 else mcus, 0: -(-h // 8) * -(-w // 8), 1: mcus, 2: mcus}
+    total = len(R.O.header(h, w, c, 75, s if c == 3 else 0, [], sof=0xC2, sos=False)) + 2
+    for scan in R.script(c):
+        n = blocks[None if scan[1] == 0 else scan[0][0]]
+        tables = 0 if (scan[1] == 0 and scan[3]) else 2 if (scan[1] == 0 and c == 3) else 1
+        total += tables * 277 + 8 + 2 * len(scan[0]) + 2 * -(-n * scan_block_bits(scan) // 8)
+    return total
+
+
+def test_size_query_is_the_headers_derivation_and_covers_the_densest_files(rt):
+    for (h, w) in J.SHAPES + [(17, 23)]:
+        for c, s in MODES:
+            stride, nbytes = rt.jpeg_encode_sizes(1, h, w, c, s, progressive=True)
+            assert stride == stride_of(h, w, c, s)
+            assert nbytes > 0 and rt.jpeg_encode_sizes(3, h, w, c, s, progressive=True)[1] >= 3 * (nbytes - 20 * 256)
+            assert rt.jpeg_encode_sizes(1, h, w, c, s, True, True) == (stride, nbytes)          # optimize has no effect
+            if c == 1:
+                assert all(rt.jpeg_encode_sizes(1, h, w, 1, other, progressive=True) == (stride, nbytes) for other in (0, 1))
+        a = J.content("noise", h, w, 3)
+        assert len(R.encode(a, 100, 0)) <= rt.jpeg_encode_sizes(1, h, w, 3, 0, progressive=True)[0]
+        assert len(R.encode(a[..., 0], 100, 0)) <= rt.jpeg_encode_sizes(1, h, w, 1, 0, progressive=True)[0]
+    # the existing queries answer what they answered (tests/golden/workspace_sizes.json pins them): not through this keyword
+    assert rt.jpeg_encode_sizes(2, 37, 53, 3, 0, True) == rt.jpeg_encode_sizes(2, 37, 53, 3, 0, True, False)
+
+
+def test_refusals_are_the_option_entrys(rt):
+    L = rt.lib()
+    s, b = ctypes.c_size_t(), ctypes.c_size_t()
+    query = lambda n, h, w, c, sampling: L.adain_jpeg_encode_progressive_u8_bytes(n, h, w, c, sampling, ctypes.byref(s), ctypes.byref(b))
+    opt = lambda n, h, w, c, sampling: L.adain_jpeg_encode_opt_u8_bytes(n, h, w, c, sampling, 1, None, None)
+    accepted = [(1, 8, 8, 3, 0), (1, 65535, 1, 1, 1), (1, 1, 65535, 3, 1), (1, 8, 8, 1, 0), (1, 8, 8, 1, 1), (1, 8, 8, 1, 2), (7, 17, 23, 3, 2)]
+    refused = [(1, 8, 8, 3, 3), (1, 8, 8, 3, -1), (1, 8, 8, 1, 3), (1, 8, 8, 2, 0), (1, 0, 8, 3, 0), (1, 8, 65536, 3, 1), (0, 8, 8, 3, 0), (1, 65535, 65535, 3, 0)]
+    for args in accepted:
+        assert query(*args) == 0 == opt(*args), args
+    assert L.adain_jpeg_encode_progressive_u8_bytes(1, 8, 8, 3, 0, None, None) == 0
+    for bad in refused:
+        assert opt(*bad) == -1
+        assert query(*bad) == -1 and L.adain_last_error().startswith(b"jpeg_encode_progressive_u8"), bad
+        with pytest.raises(rt.AdainHipError):
+            rt.jpeg_encode_sizes(*bad, progressive=True)
+    # the launching call refuses before it touches a pointer (these are not device addresses)
+    buf = (ctypes.c_uint8 * 64)()
+    p = ctypes.addressof(buf)
+    call = lambda n, h, w, c, q, sampling, stride, ws: L.adain_jpeg_encode_progressive_u8(p, n, h, w, c, q, sampling, p, stride, p, p, ws, None)
+    assert query(1, 8, 8, 3, 0) == 0
+    for args in [(1, 8, 8, 3, 75, 3), (1, 8, 8, 3, 75, -1), (1, 8, 8, 1, 75, 3), (1, 8, 8, 2, 75, 0), (1, 8, 8, 3, 0, 0), (1, 8, 8, 3, 101, 0), (0, 8, 8, 3, 75, 0)]:
+        assert call(*args, s.value, b.value) == -1 and L.adain_last_error().startswith(b"jpeg_encode_progressive_u8"), args
+    assert call(1, 8, 8, 3, 75, 0, s.value - 1, b.value) == -1 and b"out_stride" in L.adain_last_error()
+    assert call(1, 8, 8, 3, 75, 0, s.value, b.value - 1) == -1 and b"workspace" in L.adain_last_error()
+    assert L.adain_jpeg_encode_progressive_u8(None, 1, 8, 8, 3, 75, 0, p, s.value, p, p, b.value, None) == -1 and b"null" in L.adain_last_error()
+    assert L.adain_jpeg_encode_progressive_u8(p, 1, 8, 8, 3, 75, 0, p, s.value, p + 1, p, b.value, None) == -1 and b"lengths" in L.adain_last_error()
+
+
+# ---- the Python surface -----------------------------------------------------------------------------------------------------------------------
+def test_jpeg_options_carries_progressive(rt):
+    d = rt.JpegOptions()
+    assert d.progressive is False and d.is_default
+    assert repr(rt.JpegRoutes()).endswith("options=JpegOptions(quality=75, subsampling=2, optimize=False))")          # pinned elsewhere too
+    o = rt.JpegOptions(progressive=True)
+    assert o.progressive is True and not o.is_default and o != d and hash(o) != hash(d)
+    assert repr(o) == "JpegOptions(quality=75, subsampling=2, optimize=False, progressive=True)"
+    assert o.save_kwargs("RGB") == dict(quality=75, optimize=False, subsampling=2, progressive=True)
+    assert o.save_kwargs("L") == dict(quality=75, optimize=False, progressive=True)
+    assert rt.JpegOptions(95, 0, True).save_kwargs("RGB") == dict(quality=95, subsampling=0, optimize=True)
+    assert rt.JpegOptions.of(o) is o and rt.JpegOptions.of((75, 2, False, True)) == o and rt.JpegOptions.of((75, 2, False)) == d
+    assert rt.JpegOptions.of(dict(progressive=True)) == o and rt.JpegOptions.of((75, "4:2:0", 0, 1)) == o and hash(rt.JpegOptions(75, 2, False, 1)) == hash(o)
+    assert d.replace(progressive=True) == o and o.replace(progressive=False) == d and o.replace(quality=50) == rt.JpegOptions(50, 2, False, True)
+    assert rt.JpegRoutes(options={"progressive": True}).options == o
+    for bad in (2, -1, "yes", None, 1.0):
+        with pytest.raises(rt.AdainHipError, match="progressive"):
+            rt.JpegOptions(progressive=bad)
+    with pytest.raises(AttributeError):
+        o.progressive = False
+
+
+def test_python_wrappers(rt):
+    import inspect
+
+    import torch
+
+    from applied_image_processing_amd.AdaIN import test as t
+    from applied_image_processing_amd.engine import AdaINEngine
+
+    for fn in (rt.jpeg_encode_u8, AdaINEngine.jpeg_encode_u8, rt.jpeg_encode_sizes, t.set_jpeg_save_options):
+        assert inspect.signature(fn).parameters["progressive"].default is False
+    x = torch.zeros((1, 8, 8, 3), dtype=torch.uint8)
+    with pytest.raises(rt.AdainHipError, match="GPU tensor"):
+        rt.jpeg_encode_u8(x, progressive=True)                       # no CPU fallback
+    for bad in (2, "yes", None):
+        with pytest.raises(rt.AdainHipError, match="progressive"):
+            rt.jpeg_encode_u8(x, progressive=bad)
+    prev = t.set_jpeg_save_options(progressive=True)
+    try:
+        assert prev == rt.JpegOptions() and t.set_jpeg_save_options() == rt.JpegOptions(progressive=True)
+    finally:
+        t.set_jpeg_save_options(prev)
+
+
+def test_the_clis_take_the_flag(rt):
+    from applied_image_processing_amd import run_semantic_segm
+    from applied_image_processing_amd.AdaIN import run_depth
+
+    for mod in (run_depth, run_semantic_segm):
+        assert dict(mod._EXTRA_FLAGS)["--jpeg_progressive"]["action"] == "store_true"
+
+
+def test_the_host_route_saves_pillows_progressive_file(rt, tmp_path):
+    import torch
+
+    from applied_image_processing_amd import jobs
+
+    frames = np.stack([J.content("noise", 40, 72, 3, seed=i) for i in range(2)])          # noise: larger than Pillow's own buffer
+    sink = jobs.FileSink(torch.device("cpu"), jpeg_on_device=True, jpeg_options={"quality": 95, "subsampling": 0, "progressive": True})
+    sink.write(torch.from_numpy(frames), [tmp_path / "a.jpg", tmp_path / "b.png"])
+    grey = J.content("smooth", 17, 9, 1)
+    sink.write(torch.from_numpy(grey[None, ..., None]), [tmp_path / "g.jpeg"])
+    sink.close()
+    assert (tmp_path / "a.jpg").read_bytes() == pillow_bytes(frames[0], 95, 0) == R.encode(frames[0], 95, 0)
+    assert (tmp_path / "g.jpeg").read_bytes() == pillow_bytes(grey, 95) == R.encode(grey, 95)
+    plain = io.BytesIO()
+    Image.fromarray(frames[1]).save(plain, format="PNG")
+    assert (tmp_path / "b.png").read_bytes() == plain.getvalue()

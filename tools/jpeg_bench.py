@@ -6,10 +6,14 @@ after warm-up:
   pillow_ms  Image.fromarray(frame).save(BytesIO, format="JPEG") of the same frame on this machine's CPU, one thread
 and whether the two files are the same bytes.  ``passes_1080p``: device_ms sits below pillow_ms by more than the two interquartile
 ranges combined.  ``options``: the same three figures at 1080 x 1920 per option set of OPTION_SETS (quality, subsampling, optimize), under a
-key of its own, Pillow given the same keywords; ``faster_than_pillow`` there by the same rule.  With --job, a 64-view 1200 x 1600 precompute_guides_sharded into a temporary directory with jpeg_on_device off and on:
+key of its own, Pillow given the same keywords; ``faster_than_pillow`` there by the same rule.  ``progressive``: the same three figures for
+``JpegOptions(progressive=True)`` at every size and kind, against Pillow's ``save(progressive=True)`` on one thread, and beside them this
+encoder's own ``optimize=True`` file of the same frame (``optimize_kernel_ms``, ``optimize_device_ms``); ``faster_than_pillow`` only where the
+device median is below Pillow's by more than both interquartile ranges.  --only KEY measures one of sizes / options / progressive and, with
+--out, replaces that key alone in an existing file.  With --job, a 64-view 1200 x 1600 precompute_guides_sharded into a temporary directory with jpeg_on_device off and on:
 wall time, the sink's wait and the bytes that crossed to the host.  Every kernel_ms also carries the sha256 of its last call's output bytes, so that two builds of the library
 (--lib PATH: that build in place of the package's own) can be held to the same bytes as well as the same time.  Prints one JSON line and, with --out, writes it to a file.
-Usage: python tools/jpeg_bench.py [--reps 200] [--job] [--lib PATH] [--out profiles/jpeg_bench.json]"""
+Usage: python tools/jpeg_bench.py [--reps 200] [--job] [--only KEY] [--lib PATH] [--out profiles/jpeg_bench.json]"""
 import argparse
 import hashlib
 import io
@@ -120,6 +124,7 @@ def main():
     ap.add_argument("--views", type=int, default=64)
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--lib", type=str, default=None)
+    ap.add_argument("--only", type=str, default=None, choices=["sizes", "options", "progressive"])
     args = ap.parse_args()
     if args.lib:
         rt.use_library(os.path.abspath(args.lib))
@@ -132,19 +137,27 @@ def main():
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     tel = GpuTelemetry(0).start()
     res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "sizes": {}, "options": {}}
+           "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "sizes": {}, "options": {}, "progressive": {}}
+    want = lambda key: args.only in (None, key)
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         frames = {"stylised": engine.stylize_u8(source, alpha=0.5).contiguous(),
                   "noise": torch.from_numpy(np.random.default_rng(0).integers(0, 256, (1, h, w, 3), dtype=np.uint8)).to(dev)}
         for kind, x in frames.items():
-            res["sizes"][f"{kind}_{h}x{w}"] = compare(x, None, reps, tel, f"kernel_{kind}_{h}x{w}")
-            if (h, w) == (1080, 1920):
+            if want("sizes"):
+                res["sizes"][f"{kind}_{h}x{w}"] = compare(x, None, reps, tel, f"kernel_{kind}_{h}x{w}")
+            if want("progressive"):
+                entry = compare(x, rt.JpegOptions(progressive=True), reps)
+                optimised = compare(x, rt.JpegOptions(optimize=True), reps)
+                entry.update(optimize_file_bytes=optimised["file_bytes"], optimize_kernel_ms=optimised["kernel_ms"], optimize_device_ms=optimised["device_ms"])
+                res["progressive"][f"{kind}_{h}x{w}"] = entry
+            if want("options") and (h, w) == (1080, 1920):
                 for name, o in OPTION_SETS.items():
                     res["options"].setdefault(name, {"quality": o[0], "subsampling": o[1], "optimize": o[2]})[f"{kind}_{h}x{w}"] = compare(
                         x, rt.JpegOptions(*o), reps)
-    res["passes_1080p"] = all(v["device_ms"]["median"] + v["device_ms"]["iqr"] + v["pillow_ms"]["iqr"] < v["pillow_ms"]["median"]
-                              for k, v in res["sizes"].items() if k.endswith("1080x1920"))
+    if want("sizes"):
+        res["passes_1080p"] = all(v["device_ms"]["median"] + v["device_ms"]["iqr"] + v["pillow_ms"]["iqr"] < v["pillow_ms"]["median"]
+                                  for k, v in res["sizes"].items() if k.endswith("1080x1920"))
     if args.job:
         base = [(synth.image(100 + k, 1, 1200, 1600)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8) for k in range(8)]
         views = [Image.fromarray(np.roll(base[k % 8], 16 * (k // 8), axis=1)) for k in range(args.views)]       # PIL views, as the 3DGS caller holds them
@@ -153,6 +166,10 @@ def main():
         guide_job(engine, True, views[:8], style, 4)
         res["guide_job_64x1200x1600"] = {"views": len(views), "off": guide_job(engine, False, views, style, 4), "on": guide_job(engine, True, views, style, 4)}
     res["telemetry"] = tel.stop()          # shader clock and power over each kernel timing window (sysfs reads)
+    if args.only:
+        res = {args.only: dict(res[args.only], reps=reps, pillow=res["pillow"], device=res["device"])}
+        if args.out and os.path.exists(args.out):
+            res = dict(json.load(open(args.out)), **res)
     line = json.dumps(res)
     print(line)
     if args.out:
