@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import runtime as rt
-from .test import adain_inference, set_device_coral, set_jpeg_routes
+from .test import adain_inference, set_device_coral, set_device_png, set_jpeg_routes
 
 # (flag, argparse keyword arguments) — names and defaults as in the reference CLI
 _REFERENCE_FLAGS = (
@@ -45,6 +45,8 @@ _EXTRA_FLAGS = (
     ("--coral_on_device", dict(action="store_true", help="preserve the content's colours (preserve_color) with CORAL computed on the GPU")),
     ("--jpeg_decode_on_device", dict(action="store_true", help="decode a baseline JPEG content on the GPU instead of in PIL (the same pixels)")),
     ("--jpeg_decode_progressive", dict(action="store_true", help="decode a progressive JPEG content on the GPU too (implies --jpeg_decode_on_device)")),
+    ("--save_ext", dict(type=str, default=".jpg", help="extension of the result file (adain_inference's save_ext)")),
+    ("--png_on_device", dict(action="store_true", help="encode a .png result on the GPU instead of in PIL (the same pixels, not Pillow's bytes)")),
 )
 
 
@@ -70,6 +72,7 @@ def main(argv=None):
     prev_jpeg = set_jpeg_routes(rt.JpegRoutes(ns.jpeg_on_device, ns.jpeg_decode_on_device or ns.jpeg_decode_progressive, ns.jpeg_decode_progressive,
                                               (ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize, ns.jpeg_progressive)))
     prev_coral = set_device_coral(ns.coral_on_device)
+    prev_png = set_device_png(ns.png_on_device)
     style, mix = ns.style, {}
     if ns.style_interpolation_weights:
         style = ns.style.split(",")
@@ -79,10 +82,11 @@ def main(argv=None):
     try:
         return adain_inference(ns.content, style, vgg_str=ns.vgg, decoder_str=ns.decoder, depth_offset=ns.depth_offset,
                                depth_prominence=ns.depth_prominence, output=ns.output, file_name=ns.file_name,
-                               use_depth=ns.use_depth, depth_map=proximity, preserve_color=ns.coral_on_device, **mix)
+                               use_depth=ns.use_depth, depth_map=proximity, preserve_color=ns.coral_on_device, save_ext=ns.save_ext, **mix)
     finally:
         set_jpeg_routes(prev_jpeg)
         set_device_coral(prev_coral)
+        set_device_png(prev_png)
 
 
 if __name__ == "__main__":

@@ -203,7 +203,9 @@ def save_image(tensor, path, jpeg_options=None):
     routes = _jpeg if jpeg_options is None else _jpeg.replace(options=jpeg_options)
     if tensor.dim() == 3:
         tensor = tensor.unsqueeze(0)
-    routes.write(rt.quantize_u8(tensor.float()[:1]), path)
+    u8 = rt.quantize_u8(tensor.float()[:1])
+    if not _png.write(u8, path):
+        routes.write(u8, path)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -300,6 +302,18 @@ def set_jpeg_routes(routes):
     global _jpeg
     prev, _jpeg = _jpeg, rt.JpegRoutes.of(routes)
     return prev
+
+
+_png = rt.PngRoute()                  # the .png route of ``adain_inference`` (the cached per-call path and ``save_image``): runtime.PngRoute
+
+
+def set_device_png(enabled):
+    """``adain_inference`` (the cached per-call path and ``save_image``) encodes a ``.png`` output (``save_ext=".png"``) on the device - a
+    file of the same pixels, not Pillow's bytes (``runtime.png_encode_u8``) - and brings over the file instead of the raw frame.  An RGBA
+    or host frame keeps PIL.  Default False.  Returns the previous setting."""
+    global _png
+    prev, _png = _png, _png.replace(encode_on_device=enabled)
+    return prev.encode_on_device
 
 
 def set_device_jpeg(enabled):
@@ -808,7 +822,8 @@ def _one_call(x, style, enc, dec, device, call, e0=None, style_weights=None):
         T(next(stages), t0)
         t0 = time.perf_counter()
 
-    _jpeg.write(u8, target, mark)
+    if not _png.write(u8, target, mark):        # a .png target under ``set_device_png``: encoded where the frame is
+        _jpeg.write(u8, target, mark)
 
 
 def composite_with_mask(content, output_img, content_mask):

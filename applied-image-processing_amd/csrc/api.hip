@@ -563,6 +563,15 @@ int adain_jpeg_encode_progressive_u8(const uint8_t* src, int n, int h, int w, in
     return launch_jpeg_encode_progressive_u8(src, n, h, w, c, quality, sampling, out, out_stride, lengths, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// .png outputs (test.py:243-244, video/utils.py:292-296, train.py:104-114): the launcher refuses everything itself
+int adain_png_encode_u8_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes) {
+    return png_encode_bytes(n, h, w, c, out_stride, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_png_encode_u8(const uint8_t* src, int n, int h, int w, int c, int filter, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
+                        size_t workspace_bytes, adain_stream_t stream) {
+    return launch_png_encode_u8(src, n, h, w, c, filter, out, out_stride, lengths, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
 }

@@ -220,6 +220,11 @@ int launch_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, 
                                       const int32_t* scans, const uint64_t* seg_offsets, const uint32_t* seg_lengths, uint8_t* dst, int32_t* record, void* workspace,
                                       size_t workspace_bytes, int chunk_bits, hipStream_t s);
 
+// png.hip: PNG files any reader decodes to the frame (the rules: top of png.hip, tests/png_ref.py); filter -1: adaptive, 0..4: forced
+int png_encode_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes);
+int launch_png_encode_u8(const uint8_t* src, int n, int h, int w, int c, int filter, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
+                         size_t workspace_bytes, hipStream_t s);
+
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);
 int launch_coral(const void* style, int style_is_u8, int style_n, int hs, int ws, const void* content, int content_is_u8, int n, int hc, int wc,

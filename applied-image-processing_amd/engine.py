@@ -213,6 +213,11 @@ class AdaINEngine:
         (adain_jpeg_encode_u8 at the defaults, else adain_jpeg_encode_opt_u8 or adain_jpeg_encode_progressive_u8; ``runtime.jpeg_encode_u8``) -> a list of n ``bytes``; only the files cross to the host."""
         return rt.jpeg_files(*rt.jpeg_encode_u8(frames_u8, quality, subsampling, optimize, progressive))
 
+    def png_encode_u8(self, frames_u8, filter=None):
+        """Finished uint8 frames [n,h,w,c] (c = 3: RGB, 1: L) on the device -> their PNG files (adain_png_encode_u8; ``runtime.png_encode_u8``:
+        files any reader decodes to the frames' pixels, not Pillow's bytes) -> a list of n ``bytes``; only the files cross to the host."""
+        return rt.png_files(*rt.png_encode_u8(frames_u8, filter))
+
     def jpeg_decode_u8(self, files, chunk_bits=0, mode=None, report=None, restart=False, progressive=False):
         """The bytes of image files (a list, or one ``bytes``) -> uint8 tensors on the engine's device, the pixels Pillow's ``Image.open``
         gives: baseline JPEG files are decoded on the device (adain_jpeg_decode_restart_u8; with ``restart=True`` those with restart intervals as

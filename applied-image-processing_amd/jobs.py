@@ -34,7 +34,7 @@ import torch
 import torch.distributed as dist
 
 from . import sharding as sh
-from .runtime import JpegOptions, JpegRoutes
+from .runtime import JpegOptions, JpegRoutes, PngRoute
 
 
 def style_schedule(n_frames, n_styles):
@@ -462,12 +462,15 @@ class FileSink:
     a block whose paths all end in .jpg / .jpeg is encoded on the compute stream (adain_jpeg_encode_u8: the bytes PIL would write);
     the copy stream then brings over the lengths and, on a second stream of the sink's own, exactly that many bytes per frame, and the
     worker only writes them.  (The files do not ride on the lengths' stream: by the time a worker knows its lengths, the launching
-    thread may have queued later blocks' length copies there, each waiting for later kernels.)"""
+    thread may have queued later blocks' length copies there, each waiting for later kernels.)  ``png_on_device`` (default off; or ``png``,
+    a ``runtime.PngRoute``): a block whose paths all end in .png goes the same way through adain_png_encode_u8 - files that decode to the
+    frames' pixels, not Pillow's bytes.  A block of mixed extensions, and every block with the switches off, is saved by PIL as before."""
 
-    def __init__(self, device, workers=4, max_in_flight=None, jpeg_on_device=False, jpeg_options=None, jpeg=None):
+    def __init__(self, device, workers=4, max_in_flight=None, jpeg_on_device=False, jpeg_options=None, jpeg=None, png_on_device=False, png=None):
         self.copier = HostCopier(device)
         self.jpeg = JpegRoutes.of(jpeg) if jpeg is not None else JpegRoutes(encode_on_device=jpeg_on_device, options=jpeg_options)
-        self.file_stream = torch.cuda.Stream(self.copier.device) if self.jpeg.encode_on_device and self.copier.cuda else None
+        self.png = PngRoute.of(png) if png is not None else PngRoute(encode_on_device=png_on_device)
+        self.file_stream = torch.cuda.Stream(self.copier.device) if (self.jpeg.encode_on_device or self.png.encode_on_device) and self.copier.cuda else None
         self.file_bytes = 0                # bytes of encoded files the workers copied (under spare_lock)
         self.pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="adain-file-sink")
         self.futures = []
@@ -496,14 +499,22 @@ class FileSink:
 
         self.jpeg.options.save(Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr), path)
 
-    def _encodes(self, u8_block, paths):
-        return (self.jpeg.encodes(list(paths)) and self.copier.cuda and u8_block.is_cuda and u8_block.dtype == torch.uint8 and u8_block.dim() == 4
-                and u8_block.shape[3] in (1, 3))
+    def _encoder(self, u8_block, paths):
+        """The device encoder of a block - ``self.jpeg.options.encode`` for .jpg / .jpeg paths, ``self.png.encode`` for .png paths - or None:
+        the block is downloaded and saved by PIL."""
+        if not (self.copier.cuda and u8_block.is_cuda and u8_block.dtype == torch.uint8 and u8_block.dim() == 4 and u8_block.shape[3] in (1, 3)):
+            return None
+        if self.jpeg.encodes(list(paths)):
+            return self.jpeg.options.encode
+        return self.png.encode if self.png.encodes(list(paths)) else None
 
-    def _write_encoded(self, u8_block, paths):
-        """The device-encode form of ``write``: the encode on the current stream, the lengths behind it on the copy stream; the worker
+    def _encodes(self, u8_block, paths):
+        return self._encoder(u8_block, paths) is not None
+
+    def _write_encoded(self, encode, u8_block, paths):
+        """The device-encode form of ``write``: ``encode`` on the current stream, the lengths behind it on the copy stream; the worker
         waits for them, copies each frame's ``lengths[i]`` bytes into one pinned buffer on the copy stream and writes the files."""
-        files, lengths = self.jpeg.options.encode(u8_block)
+        files, lengths = encode(u8_block)
         k = len(paths)
         lengths_host = torch.empty((k,), dtype=torch.int32, pin_memory=True)
         have_lengths = self.copier.copy(lengths_host, lengths)
@@ -545,9 +556,10 @@ class FileSink:
         t0 = time.perf_counter()
         self.slots.acquire()
         self.wait_s += time.perf_counter() - t0
-        if self._encodes(u8_block, paths):
+        encode = self._encoder(u8_block, paths)
+        if encode is not None:
             try:
-                return self._write_encoded(u8_block.contiguous(), paths)
+                return self._write_encoded(encode, u8_block.contiguous(), paths)
             except BaseException:
                 self.slots.release()
                 raise
@@ -942,7 +954,7 @@ def video_style_transfer_sharded(engine, frames, styles, *, flows=None, target_r
 def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=None, content_size=512, crop=False, alpha=0.5,
                               depth_maps=None, depth_offset=0.5, depth_prominence=20, save_ext=".jpg", sub_batch=None, group=None,
                               dst=0, write="dst", require_transport=None, writers=4, jpeg_on_device=False, preserve_color=False,
-                              jpeg_options=None):
+                              jpeg_options=None, png_on_device=False):
     """The guide-image precompute of the reference's Style_3DGS/train.py:86-115 over all training views, sharded: every view
     is resized as ``adain_inference(content_size=...)`` resizes it (test.py:190-200), stylised, composited with its mask
     (``gt_image_np > 0``, train.py:97) and saved as ``<output_dir>/<name><save_ext>`` — the reference's naming, so the guide
@@ -952,7 +964,8 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
     thread ahead of the kernels and travel to the device as uint8; the files are encoded and written by ``writers`` threads
     behind them.  ``jpeg_on_device``: .jpg / .jpeg guides are encoded on the device and only the files cross to the host (FileSink;
     the same bytes).  ``jpeg_options`` (``JpegOptions``): quality, subsampling and optimize of .jpg / .jpeg guides, on either route;
-    default: Pillow's default save.  ``preserve_color``: every view is styled with ``coral(style, view)`` (``stylize_frames_sharded``).  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
+    default: Pillow's default save.  ``png_on_device``: .png guides are encoded on the device (FileSink; the same pixels, not Pillow's
+    bytes).  ``preserve_color``: every view is styled with ``coral(style, view)`` (``stylize_frames_sharded``).  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
     from PIL import Image
 
     from .AdaIN.test import device_transform_u8, test_transform_u8
@@ -983,7 +996,7 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
     on_gpu = torch.device(engine.device).type == "cuda"
     names = list(names)
     paths = {nm: out_dir / f"{nm}{save_ext}" for nm in names}
-    sink = FileSink(engine.device, workers=writers, jpeg_on_device=jpeg_on_device, jpeg_options=jpeg_options)
+    sink = FileSink(engine.device, workers=writers, jpeg_on_device=jpeg_on_device, jpeg_options=jpeg_options, png_on_device=png_on_device)
     err = None
     info = {}
     try:

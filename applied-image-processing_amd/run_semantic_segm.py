@@ -9,14 +9,15 @@ composite.  Extra flags make it usable offline (the reference downloads DeepLabV
 precomputed background mask ([1,H,W] or [H,W], 1 = background), ``--depth_npy`` a proximity map, ``--vgg`` / ``--decoder`` the
 checkpoint paths, ``--colour_on_device`` moves the colour transfer and the composite to the GPU, ``--jpeg_on_device`` the JPEG encode of the intermediate
 stylised file and of the final composite (the same bytes); ``--jpeg_quality``, ``--jpeg_subsampling``, ``--jpeg_optimize``, ``--jpeg_progressive`` are Pillow's
-keywords for the final composite's file, on either route.  Without ``--mask_npy`` a provider must have been registered (``localized.set_mask_provider``).
+keywords for the final composite's file, on either route; ``--save_ext`` is the extension of the intermediate stylised file (the final composite
+stays .jpg) and, with ``--save_ext .png``, ``--png_on_device`` encodes that file on the GPU (the same pixels).  Without ``--mask_npy`` a provider must have been registered (``localized.set_mask_provider``).
 """
 import argparse
 
 import numpy as np
 import torch
 
-from .AdaIN.test import jpeg_routes, set_jpeg_routes
+from .AdaIN.test import jpeg_routes, set_device_png, set_jpeg_routes
 from .localized import run_localized_style_transfer
 
 # (flag, argparse keyword arguments) - names and defaults as in the reference CLI
@@ -38,6 +39,8 @@ _EXTRA_FLAGS = (
     ("--jpeg_subsampling", dict(type=str, default="4:2:0", choices=["4:4:4", "4:2:2", "4:2:0"], help="chroma subsampling of the final composite's JPEG")),
     ("--jpeg_optimize", dict(action="store_true", help="give the final composite's JPEG its own optimal Huffman tables (Pillow's optimize=True)")),
     ("--jpeg_progressive", dict(action="store_true", help="write the final composite's JPEG as a progressive file (Pillow's progressive=True)")),
+    ("--save_ext", dict(type=str, default=".jpg", help="extension of the intermediate stylised file (adain_inference's save_ext); the final composite stays .jpg")),
+    ("--png_on_device", dict(action="store_true", help="with --save_ext .png: encode the intermediate stylised file on the GPU instead of in PIL (the same pixels, not Pillow's bytes)")),
 )
 
 
@@ -50,10 +53,11 @@ def main(argv=None):
     if ns.mask_npy:
         mask = np.load(ns.mask_npy)
         mask = (mask[None] if mask.ndim == 2 else mask).astype(np.uint8)
-    extra = dict(vgg_str=ns.vgg, decoder_str=ns.decoder)
+    extra = dict(vgg_str=ns.vgg, decoder_str=ns.decoder, save_ext=ns.save_ext)
     if ns.depth_npy:
         extra["depth_map"] = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
     prev = set_jpeg_routes(jpeg_routes().replace(encode_on_device=ns.jpeg_on_device))
+    prev_png = set_device_png(ns.png_on_device)
     try:
         return run_localized_style_transfer(content_img_path=ns.content, style_img_path=ns.style, output_path=ns.output, file_name=ns.file_name,
                                             use_depth=ns.use_depth, background_mask=mask, colour_on_device=ns.colour_on_device,
@@ -61,6 +65,7 @@ def main(argv=None):
                                             **extra)
     finally:
         set_jpeg_routes(prev)
+        set_device_png(prev_png)
 
 
 if __name__ == "__main__":

@@ -99,6 +99,8 @@ SIGNATURES = {
                                       _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_png_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
+    "adain_png_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_progressive_u8_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
@@ -826,7 +828,7 @@ def resize_pil_bilinear_u8(frames, size, crop=None, out=None):
 JPEG_DEFAULT_QUALITY = 75          # Pillow's
 
 
-def _jpeg_sizes(name, *dims, results=1):
+def _size_query(name, *dims, results=1):
     """The size query ``name`` of the C ABI on the integers ``dims`` -> its size_t results.  Host only.  AdainHipError for a refused shape."""
     out = [_c_size_t() for _ in range(results)]
     rc = getattr(lib(), name)(*(int(d) for d in dims), *(ctypes.byref(o) for o in out))
@@ -835,10 +837,8 @@ def _jpeg_sizes(name, *dims, results=1):
     return [o.value for o in out]
 
 
-def _jpeg_frames(u8, what, quality):
-    """The checks and input forms the JPEG calls share: frames uint8 [n,h,w,3|1], one frame [h,w,3|1] or [h,w] -> contiguous [n,h,w,c]."""
-    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
-        raise AdainHipError(f"{what}: quality must be an int in 1..100, got {quality!r}")
+def _u8_frames(u8, what):
+    """The input forms the file encoders share: frames uint8 [n,h,w,3|1], one frame [h,w,3|1] or [h,w] -> contiguous [n,h,w,c]."""
     x = device_tensor(u8, "frames", torch.uint8)
     if x.dim() == 2:
         x = x[None, :, :, None]
@@ -847,6 +847,13 @@ def _jpeg_frames(u8, what, quality):
     if x.dim() != 4 or x.shape[3] not in (1, 3) or x.shape[0] < 1:
         raise AdainHipError(f"{what}: expected uint8 [n,h,w,3|1], [h,w,3|1] or [h,w], got {tuple(u8.shape)}")
     return x
+
+
+def _jpeg_frames(u8, what, quality):
+    """``_u8_frames`` behind the JPEG calls' check of ``quality``."""
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise AdainHipError(f"{what}: quality must be an int in 1..100, got {quality!r}")
+    return _u8_frames(u8, what)
 
 
 JPEG_SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}          # Pillow's strings -> its numbers, which are the C ABI's `sampling`
@@ -1024,8 +1031,8 @@ def jpeg_encode_sizes(n, h, w, c, subsampling=2, optimize=False, progressive=Fal
     and the scratch of an n-frame call.  Host only.  AdainHipError for a refused shape."""
     sampling, optimize = jpeg_subsampling(subsampling, "jpeg_encode_sizes"), _jpeg_flag(optimize, "jpeg_encode_sizes", "optimize")
     if _jpeg_flag(progressive, "jpeg_encode_sizes", "progressive"):
-        return tuple(_jpeg_sizes("adain_jpeg_encode_progressive_u8_bytes", n, h, w, c, sampling, results=2))
-    return tuple(_jpeg_sizes("adain_jpeg_encode_opt_u8_bytes", n, h, w, c, sampling, optimize, results=2))
+        return tuple(_size_query("adain_jpeg_encode_progressive_u8_bytes", n, h, w, c, sampling, results=2))
+    return tuple(_size_query("adain_jpeg_encode_opt_u8_bytes", n, h, w, c, sampling, optimize, results=2))
 
 
 def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False, progressive=False):
@@ -1068,9 +1075,97 @@ def jpeg_files(out, lengths):
     return [out[i, :k].cpu().numpy().tobytes() for i, k in enumerate(ln)]
 
 
+# --- .png output files (adain_png_encode_u8) ------------------------------------------------------------------------------------------
+def is_png_path(path):
+    return str(path).lower().endswith(".png")
+
+
+def _png_filter(filter, what):
+    """None (every row's filter by libpng's minimum sum of magnitudes) -> -1; 0..4 (None, Sub, Up, Average, Paeth on every row) -> itself."""
+    if filter is None:
+        return -1
+    if isinstance(filter, bool) or not isinstance(filter, int) or not 0 <= filter <= 4:
+        raise AdainHipError(f"{what}: filter must be None or an int in 0..4, got {filter!r}")
+    return filter
+
+
+def png_encode_sizes(n, h, w, c):
+    """(out_stride, workspace_bytes) of adain_png_encode_u8_bytes: the largest file a frame of this shape can have and the scratch of an
+    n-frame call.  Host only.  AdainHipError for a refused shape."""
+    return tuple(_size_query("adain_png_encode_u8_bytes", n, h, w, c, results=2))
+
+
+def png_encode_u8(u8, filter=None):
+    """Frames uint8 [n,h,w,c] (c = 3: RGB, 1: L; or one frame [h,w,c] / [h,w]) -> (files uint8 [n, stride], lengths int32 [n]), both on the
+    device: row i starts with frame i's PNG file, ``lengths[i]`` bytes - 8-bit, non-interlaced, IHDR / IDAT / IEND - which any reader
+    decodes to the frame's pixels; the rest of the row is not written.  The bytes are not Pillow's: they follow the rules of
+    csrc/png.hip (tests/png_ref.py) and depend on the frame and ``filter`` alone.  ``filter``: None chooses every row's filter as libpng
+    does, 0..4 forces one.  16-bit, palette, RGBA, interlace, ancillary chunks, ``compress_level`` and ``optimize`` stay with Pillow.
+    Nothing is copied to the host and nothing waits."""
+    filt = _png_filter(filter, "png_encode_u8")
+    x = _u8_frames(u8, "png_encode_u8")
+    n, h, w, c = x.shape
+    stride = 0
+
+    def sizes():                # one query answers both: the file stride is kept for the output below
+        nonlocal stride
+        stride, nbytes = png_encode_sizes(n, h, w, c)
+        return nbytes
+
+    with scratch(x.device, "png", sizes) as ws:
+        out = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
+        lengths = torch.empty((n,), dtype=torch.int32, device=x.device)
+        _launch("adain_png_encode_u8", x.data_ptr(), n, h, w, c, filt, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, lengths
+
+
+png_files = jpeg_files          # the files of a ``png_encode_u8`` result as a list of ``bytes`` (waits for the device)
+
+
+class PngRoute(_Value):
+    """Whether a call's .png outputs are encoded on the device - one value for every caller, beside ``JpegRoutes``.  ``encode_on_device``:
+    .png files of uint8 device frames with 1 or 3 channels are written by ``png_encode_u8`` (the same pixels, not Pillow's bytes) and
+    only the files cross to the host; ``filter``: its row filter, None for the adaptive choice.  The default: off, Pillow's save."""
+    __slots__ = ("encode_on_device", "filter")
+
+    def __init__(self, encode_on_device=False, filter=None):
+        _png_filter(filter, "PngRoute")
+        self._set(encode_on_device=bool(encode_on_device), filter=filter)
+
+    def encodes(self, paths):
+        """Does the device encode the file(s) at ``paths`` (one, or a list)?  With ``encode_on_device``, when every path is .png."""
+        paths = paths if isinstance(paths, (list, tuple)) else [paths]
+        return self.encode_on_device and len(paths) > 0 and all(is_png_path(p) for p in paths)
+
+    def takes(self, u8, paths):
+        """``encodes(paths)`` and ``u8`` is what the device route takes: a uint8 GPU tensor whose last dimension is 1 or 3."""
+        return self.encodes(paths) and isinstance(u8, torch.Tensor) and u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() in (3, 4) and u8.shape[-1] in (1, 3)
+
+    def encode(self, u8):
+        """The device route: ``png_encode_u8`` with this filter -> (files, lengths) on the device."""
+        return png_encode_u8(u8, self.filter)
+
+    def write(self, u8, path, mark=None):
+        """One uint8 frame [1,h,w,c] or [h,w,c] -> the file at ``path``: encoded on the device when ``takes(u8, path)``, only the file
+        coming over.  Returns False, having written nothing, for a frame or path this route does not take: the caller saves it as before.
+        ``mark()`` is called after each of the three steps, as ``JpegRoutes.write`` calls it: the launch, the wait for the device with the
+        download, the write."""
+        if not self.takes(u8, path):
+            return False
+        mark = mark or (lambda: None)
+        encoded = self.encode(u8)
+        mark()
+        data, = png_files(*encoded)
+        mark()
+        with open(str(path), "wb") as f:
+            f.write(data)
+        mark()
+        return True
+
+
 def jpeg_roundtrip_sizes(n, h, w, c):
     """workspace_bytes of adain_jpeg_roundtrip_u8_bytes: the scratch of an n-frame call.  Host only.  AdainHipError for a refused shape."""
-    return _jpeg_sizes("adain_jpeg_roundtrip_u8_bytes", n, h, w, c)[0]
+    return _size_query("adain_jpeg_roundtrip_u8_bytes", n, h, w, c)[0]
 
 
 def jpeg_roundtrip_u8(u8, quality=JPEG_DEFAULT_QUALITY):
@@ -1091,7 +1186,7 @@ def jpeg_decode_sizes(n, h, w, c, sampling, max_segment_bytes, chunk_bits=0, res
     """workspace_bytes of adain_jpeg_decode_restart_u8_bytes: the scratch of an n-file call whose longest entropy-coded segment has
     ``max_segment_bytes`` and whose files have ``restart_interval`` MCUs per restart interval (0: none).  Host only.  AdainHipError for
     a refused shape."""
-    return _jpeg_sizes("adain_jpeg_decode_restart_u8_bytes", n, h, w, c, sampling, restart_interval, max_segment_bytes, chunk_bits)[0]
+    return _size_query("adain_jpeg_decode_restart_u8_bytes", n, h, w, c, sampling, restart_interval, max_segment_bytes, chunk_bits)[0]
 
 
 _jpeg_decode_lock = threading.Lock()
@@ -1164,7 +1259,7 @@ def jpeg_decode_batch(parsed, datas, device, chunk_bits=0, lead=0):
 def jpeg_decode_progressive_sizes(n, h, w, c, sampling, nscans, max_segment_bytes, chunk_bits=0):
     """workspace_bytes of adain_jpeg_decode_progressive_u8_bytes: the scratch of an n-file call of ``nscans`` scans whose longest scan
     segment has ``max_segment_bytes``.  Host only.  AdainHipError for a refused shape."""
-    return _jpeg_sizes("adain_jpeg_decode_progressive_u8_bytes", n, h, w, c, sampling, nscans, max_segment_bytes, chunk_bits)[0]
+    return _size_query("adain_jpeg_decode_progressive_u8_bytes", n, h, w, c, sampling, nscans, max_segment_bytes, chunk_bits)[0]
 
 
 def jpeg_decode_progressive_upload(parsed, datas, device, lead=0):

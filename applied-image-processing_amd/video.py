@@ -172,7 +172,7 @@ def _jpeg_roundtrip(u8):
 
 
 def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-              vgg_str, decoder_str, depth_maps, group, preserve_color, crossfade_frames, intermediate_jpeg, routes):
+              vgg_str, decoder_str, depth_maps, group, preserve_color, crossfade_frames, intermediate_jpeg, routes, png=None):
     from . import sharding as sh
     from .engine import AdaINEngine
 
@@ -253,7 +253,7 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
     if rank == 0:
         # the frame-to-frame recurrence (video/utils.py:355-368) on the gathered frames; every frame is written by a worker
         # thread behind an asynchronous device -> host copy while the next frame's warp / blend is already running
-        sink = jobs.FileSink(engine.device, jpeg=routes)
+        sink = jobs.FileSink(engine.device, jpeg=routes, png=png)
         try:
             n, h, w, _ = frames_u8.shape
             prev = None
@@ -286,7 +286,7 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
                              cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                              vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth", decoder_str="Style_3DGS/AdaIN/models/decoder.pth",
                              depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False, preserve_color=False,
-                             jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None):
+                             jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False):
     """One style for the whole clip (video/utils.py:244-295); keyword-only extras: a ready ``engine``, checkpoint paths,
     precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``preserve_color`` (every frame is styled with
     ``coral(style, frame)``, adain_inference's colour preservation, on the device) and the call's ``rt.JpegRoutes``, field by field:
@@ -295,11 +295,13 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
     (baseline .jpg / .jpeg frames are decoded on the device, for the stylisation and for the package's flow providers: the pixels PIL
     decodes; any other file, and the sharded feeder of jobs.py, keep PIL), ``jpeg_decode_progressive`` (with it only: progressive frames
     too), ``jpeg_options`` (``jobs.JpegOptions`` or a (quality, subsampling, optimize) tuple: how the .jpg / .jpeg OUTPUT frames are saved
-    on either route, default Pillow's default save; the ``intermediate_jpeg`` round trip stays quality 75 and 4:2:0 whatever they say)."""
+    on either route, default Pillow's default save; the ``intermediate_jpeg`` round trip stays quality 75 and 4:2:0 whatever they say).
+    ``png_on_device`` (default off): .png frames are encoded on the device (``rt.PngRoute``, jobs.FileSink): files of the same pixels,
+    not Pillow's bytes."""
     routes = rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options)
     with _routes_scope(routes):
         return _run_clip(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
-                         engine, vgg_str, decoder_str, depth_maps, group, preserve_color, 0, intermediate_jpeg, routes)
+                         engine, vgg_str, decoder_str, depth_maps, group, preserve_color, 0, intermediate_jpeg, routes, rt.PngRoute(png_on_device))
 
 
 def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
@@ -307,13 +309,14 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
                                    vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth",
                                    decoder_str="Style_3DGS/AdaIN/models/decoder.pth", depth_maps=None, intermediate_jpeg=False,
                                    group=None, jpeg_on_device=False, preserve_color=False, crossfade_frames=0, jpeg_decode_on_device=False,
-                                   jpeg_decode_progressive=False, jpeg_options=None):
+                                   jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False):
     """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372).
     ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics.
     ``crossfade_frames`` (0, the default: the hard cuts of the reference): the styles cross-fade in feature space over that many
     frames centred on each switch (``jobs.style_crossfade``, style interpolation on the device; at most 16 styles, and not with
     ``preserve_color``).  ``jpeg_on_device``, ``jpeg_decode_on_device``, ``jpeg_decode_progressive``, ``jpeg_options``: the call's
-    ``rt.JpegRoutes``, as in ``apply_style_transfer_ada`` (the options: the output files only, never the ``intermediate_jpeg`` round trip)."""
+    ``rt.JpegRoutes``, as in ``apply_style_transfer_ada`` (the options: the output files only, never the ``intermediate_jpeg`` round trip);
+    ``png_on_device``: as there."""
     style_images = sorted(os.listdir(style_dir))
     if len(style_images) == 0:
         raise ValueError("No style images found in the style directory.")
@@ -323,4 +326,4 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
     with _routes_scope(routes):
         return _run_clip(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
                          cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, group, preserve_color, int(crossfade_frames),
-                         intermediate_jpeg, routes)
+                         intermediate_jpeg, routes, rt.PngRoute(png_on_device))

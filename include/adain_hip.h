@@ -521,6 +521,31 @@ ADAIN_API int adain_jpeg_encode_progressive_u8(const uint8_t* src_u8, int n, int
                                                size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes,
                                                adain_stream_t stream);
 
+/* ---- PNG output files: the reference's save of a .png path (test.py:243-244, video/utils.py:292-296, train.py:104-114) --------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * src: n frames HWC uint8 [n][h][w][c], c = 3 (colour type 2) or 1 (colour type 0), at any byte address.  Row i of `out`
+ * ([n][out_stride] bytes, at any byte address) starts with frame i's file and lengths[i] (int32, 4-byte aligned) is its size: an 8-bit
+ * non-interlaced PNG of signature, IHDR, one IDAT and IEND that any reader decodes to the frame's pixels.  The bytes are NOT Pillow's
+ * (that would be zlib's sequential matcher); they are a function of the frame and `filter` alone - not of n, the stream or the device
+ * - by the rules listed at the top of csrc/png.hip and restated in tests/png_ref.py.  filter: -1 chooses every row's filter by
+ * libpng's minimum sum of magnitudes, 0..4 forces None, Sub, Up, Average or Paeth on every row.
+ * adain_png_encode_u8_bytes (host only): *out_stride = the largest file a frame of this shape can have; an overflow is impossible, not
+ *   detected.  The filtered stream has S = h (w c + 1) bytes in B = ceil(S / 32768) deflate blocks.  Every block is written with the
+ *   cheaper of its own Huffman code and the fixed one, so it costs at most what the fixed code costs: 9 bits for a literal at most; a
+ *   match (4..258 bytes) at most 8 + 5 + 5 + 13 = 31 bits, less than the 32 its four or more literals would cost at least; 3 header bits
+ *   and the 7 of the end-of-block symbol per block.  With the zlib header (2), the Adler-32 (4) and the file's 57 bytes of signature,
+ *   IHDR, IDAT frame and IEND: out_stride = 63 + ceil((9 S + 10 B) / 8).  *workspace_bytes = the filtered stream, one 16-bit token per
+ *   filtered byte, per block the code tables, bit count and offset, and the zlib stream at its bound, of n frames.  Either output may be
+ *   NULL.
+ * Refused with ADAIN_EINVAL before anything is launched: null pointers, c outside {1, 3}, h or w outside 1..65535, n outside 1..65535,
+ * filter outside -1..4, a frame whose out_stride would pass 2^31 - 1, out_stride or workspace_bytes below the query's, a workspace
+ * that is not 8-byte aligned, lengths that is not 4-byte aligned.  Bytes of `out` behind a file are not written.  Nothing is copied
+ * to the host and nothing waits; 7 kernel launches and one memset per call, whatever n.
+ * What stays with Pillow: 16-bit, palette and RGBA images, interlace, ancillary chunks, compress_level, optimize. */
+ADAIN_API int adain_png_encode_u8_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes);
+ADAIN_API int adain_png_encode_u8(const uint8_t* src_u8, int n, int h, int w, int c, int filter /* -1: adaptive */, uint8_t* out,
+                                  size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream);
+
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
  * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)

@@ -1,0 +1,232 @@
+"""The PNG writer's restatement (tests/png_ref.py) held to zlib and Pillow on the cases of tests/png_cases.py, and the host side of
+adain_png_encode_u8: the size query, the refusals that need no GPU, the route value and the callers' keywords.  No GPU."""
+import ctypes
+import inspect
+import io
+import json
+import os
+import struct
+import zlib
+
+import numpy as np
+import pytest
+from PIL import Image
+
+import png_cases as C
+import png_ref as P
+
+SIZES = os.path.join(C.GOLDEN, "png_sizes.json")
+NAMES = [name for name, _, _ in C.cases()]
+
+
+def case(name):
+    return next((f, k) for n, f, k in C.cases() if n == name)
+
+
+def chunks(data):
+    """[(type, payload)] of a PNG file, every CRC verified with zlib.crc32."""
+    assert data[:8] == P.SIGNATURE
+    out, at = [], 8
+    while at < len(data):
+        n, = struct.unpack(">I", data[at:at + 4])
+        kind, payload = data[at + 4:at + 8], data[at + 8:at + 8 + n]
+        crc, = struct.unpack(">I", data[at + 8 + n:at + 12 + n])
+        assert zlib.crc32(kind + payload) == crc, f"CRC of {kind}"
+        out.append((kind, payload))
+        at += 12 + n
+    assert at == len(data)
+    return out
+
+
+def unfilter(stream, h, w, c):
+    """The pixels of a filtered stream: all five filter types, written out here.  None and Up rows are one NumPy operation, a Sub row is a
+    running sum per channel; Average and Paeth rows depend on their own left neighbour and go byte by byte over Python integers."""
+    rb = w * c
+    rows = np.frombuffer(stream, np.uint8).reshape(h, rb + 1)
+    out = np.zeros((h, rb), np.uint8)
+    up = [0] * rb
+    for y in range(h):
+        kind, line = int(rows[y, 0]), rows[y, 1:]
+        assert 0 <= kind <= 4
+        if kind == 0:
+            cur = line.tolist()
+        elif kind == 1:
+            cur = (np.cumsum(line.reshape(w, c).astype(np.int64), axis=0) & 255).reshape(-1).tolist()
+        elif kind == 2:
+            cur = ((line.astype(np.int64) + np.array(up, np.int64)) & 255).tolist()
+        else:
+            raw, cur = line.tolist(), [0] * rb
+            for x in range(rb):
+                a = cur[x - c] if x >= c else 0
+                b = up[x]
+                if kind == 3:
+                    pred = (a + b) // 2
+                else:
+                    cc = up[x - c] if x >= c else 0
+                    p = a + b - cc
+                    pa, pb, pc = abs(p - a), abs(p - b), abs(p - cc)
+                    pred = a if pa <= pb and pa <= pc else b if pb <= pc else cc
+                cur[x] = (raw[x] + pred) & 255
+        out[y] = cur
+        up = cur
+    return out.reshape(h, w, c)
+
+
+def check_file(data, frame, filt):
+    """Every assertion a valid file of ``frame`` must pass."""
+    h, w, c = frame.shape
+    parts = chunks(data)
+    kinds = [k for k, _ in parts]
+    assert kinds[0] == b"IHDR" and kinds[-1] == b"IEND" and len(kinds) >= 3 and set(kinds[1:-1]) == {b"IDAT"}
+    assert parts[0][1] == struct.pack(">IIBBBBB", w, h, 8, 2 if c == 3 else 0, 0, 0, 0) and parts[-1][1] == b""
+    z = b"".join(p for k, p in parts if k == b"IDAT")
+    assert z[0] & 15 == 8 and z[0] >> 4 == 7 and (z[0] * 256 + z[1]) % 31 == 0 and not z[1] & 32
+    stream, which = P.filter_rows(frame, filt)
+    assert zlib.decompress(z) == stream.tobytes()
+    assert np.array_equal(unfilter(stream.tobytes(), h, w, c), frame)
+    img = Image.open(io.BytesIO(data))
+    assert img.mode == ("RGB" if c == 3 else "L")
+    got = np.asarray(img)
+    assert np.array_equal(got if c == 3 else got[:, :, None], frame)
+    assert len(data) <= P.out_stride(h, w, c)
+
+
+@pytest.fixture(scope="module")
+def files():
+    return {name: P.encode(frame, filt) for name, frame, filt in C.cases()}
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_the_restatements_file_is_a_valid_png_of_the_frame(files, name):
+    frame, filt = case(name)
+    check_file(files[name], frame, filt)
+
+
+def test_the_cases_reach_the_rules():
+    """What the names of the cases promise, shown on the restatement's own report."""
+    P.STATS["halved"] = {15: 0, 7: 0}
+    reports = {}
+    for name, frame, filt in C.cases():
+        reports[name] = []
+        before = dict(P.STATS["halved"])
+        P.encode(frame, filt, reports[name])
+        reports[name].append({k: P.STATS["halved"][k] - before[k] for k in (15, 7)})
+    assert set(P.filter_rows(case("five_filters")[0])[1].tolist()) == {0, 1, 2, 3, 4}
+    # a zero row: every filter costs 0; a constant row on it: Sub and Paeth tie at the first pixel's bytes; constant on constant: Up and Paeth at 0
+    assert P.filter_rows(case("cost_ties")[0])[1].tolist() == [0, 1, 2, 2]
+    assert reports["fibonacci_15"][-1][15] >= 1, "no tree passed 15 bits"
+    assert any(r[-1][7] >= 1 for r in reports.values()), "no code-length tree passed 7 bits"
+    assert [len(r) - 1 for r in (reports["stream_32767"], reports["stream_32768"], reports["stream_32769"])] == [1, 1, 2]
+    assert sum(reports["source_in_previous_block"][1]["d_freq"]) > 0
+    assert sum(reports["no_match_dynamic"][0]["d_freq"]) == 0 and reports["no_match_dynamic"][0]["dynamic"]
+    assert reports["no_match_dynamic"][0]["d_len"][0] == 1 and sum(reports["no_match_dynamic"][0]["d_len"]) == 1
+    assert sum(1 for v in reports["one_literal"][0]["ll_freq"] if v) == 2 and not reports["one_literal"][0]["dynamic"]
+    lengths = set(i for i, v in enumerate(reports["length_symbols"][0]["ll_freq"]) if v and i > 256)
+    assert lengths == set(range(258, 286)), "every length symbol a 4..258 byte match can have"
+    # behind a run's first zero: 256, 257, 258 and 258 + 258 + 83 bytes at distance 1 - the 258 cap three times
+    assert reports["zero_runs"][0]["ll_freq"][285] == 3 and reports["zero_runs"][0]["d_freq"][0] == 6
+    d = reports["row_distances_1024"][0]["d_freq"]
+    assert d[19] and d[20], "row distances on both sides of the 1024 / 1025 code boundary"
+    assert sum(r["d_freq"][29] for r in reports["row_distance_32768"][:-1]) > 0
+    assert 32769 not in P.distances(32768, 1) and 32768 in P.distances(32768, 1)
+    tie = reports["dynamic_fixed_tie"][0]
+    assert tie["dynamic_bits"] == tie["fixed_bits"] and not tie["dynamic"], "a tie goes to the fixed code"
+    assert any(r["fixed_bits"] < r["dynamic_bits"] for rs in reports.values() for r in rs[:-1])
+    dynamic = [r["dynamic"] for rs in reports.values() for r in rs[:-1]]
+    assert any(dynamic) and not all(dynamic)
+    seen = set()
+    for rs in reports.values():
+        for r in rs[:-1]:
+            if r["dynamic"]:
+                hlit = max(i for i in range(286) if r["ll_len"][i]) + 1
+                hdist = max(i for i in range(30) if r["d_len"][i]) + 1
+                seen |= {(s, e) for s, e in P.run_length(list(r["ll_len"][:hlit]) + list(r["d_len"][:hdist])) if s >= 16}
+    for pair in ((16, 0), (16, 3), (17, 0), (17, 7), (18, 0), (18, 127)):
+        assert pair in seen, f"run-length symbol {pair[0]} with extra {pair[1]} never written"
+
+
+def test_sizes_are_the_recorded_ones_and_meet_the_bar(files):
+    sizes = {name: len(data) for name, data in files.items()}
+    with open(SIZES) as f:
+        assert json.load(f) == sizes, "the rules moved: tests/golden/png_sizes.json holds the sizes of every case"
+    for name in C.REALISTIC:                                       # no larger than Pillow's own fast setting
+        frame, _ = case(name)
+        f = io.BytesIO()
+        Image.fromarray(frame).save(f, format="PNG", compress_level=1)
+        print(name, sizes[name], "bytes against Pillow compress_level=1:", len(f.getvalue()))
+        assert sizes[name] <= len(f.getvalue()), name
+
+
+@pytest.mark.parametrize("fault,name", [("paeth_tie", "paeth_ties"), ("cross_block", "stream_32769"), ("msb_first", "five_filters"), ("hlit", "five_filters"),
+                                        ("adler", "five_filters")])
+def test_a_single_fault_breaks_a_check(fault, name):
+    frame, filt = case(name)
+    P.FAULTS.add(fault)
+    try:
+        data = P.encode(frame, filt)
+    finally:
+        P.FAULTS.discard(fault)
+    with pytest.raises((AssertionError, zlib.error, OSError, SyntaxError)):
+        check_file(data, frame, filt)
+
+
+# ---- the built library, without a GPU -------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def rt():
+    import applied_image_processing_amd.runtime as rt
+
+    rt.lib()
+    return rt
+
+
+def test_out_stride_is_the_derived_bound(rt, files):
+    for name, frame, _ in C.cases():
+        stride, nbytes = rt.png_encode_sizes(1, *frame.shape)
+        assert stride == P.out_stride(*frame.shape) and len(files[name]) <= stride and nbytes > 0, name
+    one, two = rt.png_encode_sizes(1, 64, 64, 3), rt.png_encode_sizes(2, 64, 64, 3)
+    assert one[0] == two[0] and one[1] < two[1]
+    assert rt.lib().adain_png_encode_u8_bytes(1, 8, 8, 3, None, None) == 0
+
+
+def test_refusals_that_need_no_gpu(rt):
+    L = rt.lib()
+    s, b = ctypes.c_size_t(), ctypes.c_size_t()
+    for dims in ((0, 8, 8, 3), (65536, 8, 8, 3), (1, 8, 8, 2), (1, 8, 8, 4), (1, 0, 8, 3), (1, 8, 0, 3), (1, 65536, 8, 3), (1, 8, 65536, 3), (1, 65535, 65535, 3)):
+        assert L.adain_png_encode_u8_bytes(*dims, ctypes.byref(s), ctypes.byref(b)) == -1 and b"png_encode_u8" in L.adain_last_error(), dims
+    assert L.adain_png_encode_u8_bytes(1, 8, 8, 3, ctypes.byref(s), ctypes.byref(b)) == 0
+    buf = ctypes.create_string_buffer(64)
+    p = (ctypes.addressof(buf) + 7) & ~7
+    call = lambda src=p, n=1, h=8, w=8, c=3, filt=-1, out=p, stride=s.value, lengths=p, ws=p, size=b.value: L.adain_png_encode_u8(
+        src, n, h, w, c, filt, out, stride, lengths, ws, size, None)
+    for kw in (dict(src=None), dict(out=None), dict(lengths=None), dict(ws=None), dict(c=2), dict(h=0), dict(w=65536), dict(n=0), dict(n=65536), dict(filt=-2),
+               dict(filt=5), dict(stride=s.value - 1), dict(size=b.value - 1), dict(ws=p + 4), dict(lengths=p + 2)):
+        assert call(**kw) == -1 and L.adain_last_error(), kw
+
+
+def test_the_route_value_and_the_callers_keywords(rt):
+    from applied_image_processing_amd import jobs, video
+    from applied_image_processing_amd.AdaIN import run_depth, test as t
+    from applied_image_processing_amd import run_semantic_segm
+    from applied_image_processing_amd.engine import AdaINEngine
+
+    r = rt.PngRoute()
+    assert (r.encode_on_device, r.filter) == (False, None) and repr(r) == "PngRoute(encode_on_device=False, filter=None)"
+    on = r.replace(encode_on_device=True)
+    assert on == rt.PngRoute(True) and on != r and rt.PngRoute.of(None) == r and rt.PngRoute.of({"encode_on_device": True, "filter": 2}).filter == 2
+    assert on.encodes("a.png") and on.encodes(["a.PNG", "b.png"]) and not on.encodes(["a.png", "b.jpg"]) and not on.encodes([]) and not r.encodes("a.png")
+    assert not on.takes(np.zeros((4, 4, 3), np.uint8), "a.png") and on.write(np.zeros((4, 4, 3), np.uint8), "a.png") is False
+    with pytest.raises(AttributeError):
+        on.filter = 1
+    with pytest.raises(rt.AdainHipError):
+        rt.PngRoute(filter=5)
+    assert rt.is_png_path("x/y.PNG") and not rt.is_png_path("x/y.jpg")
+    assert repr(rt.JpegRoutes()) == "JpegRoutes(encode_on_device=False, decode_on_device=False, decode_progressive=False, options=JpegOptions(quality=75, subsampling=2, optimize=False))"
+    assert callable(AdaINEngine.png_encode_u8)
+    for fn in (jobs.precompute_guides_sharded, video.apply_style_transfer_ada, video.apply_style_transfer_multi_ada):
+        par = inspect.signature(fn).parameters["png_on_device"]
+        assert par.default is False and par.kind is inspect.Parameter.KEYWORD_ONLY
+    assert inspect.signature(jobs.FileSink.__init__).parameters["png_on_device"].default is False
+    assert t.set_device_png(False) is False
+    assert t.set_device_png(True) is False and t.set_device_png(False) is True
+    for mod in (run_depth, run_semantic_segm):
+        assert dict(mod._EXTRA_FLAGS)["--png_on_device"]["action"] == "store_true" and dict(mod._EXTRA_FLAGS)["--save_ext"]["default"] == ".jpg"
