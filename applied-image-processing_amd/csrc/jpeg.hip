@@ -28,12 +28,12 @@
 //              and chroma downsample into per-block planes, the two DCT passes with one lane per row / column, quantisation, and the
 //              zigzag-ordered int16 coefficients leave as one contiguous store
 //   count      one wave64 per block, one lane per coefficient: __ballot gives the non-zero mask, the runs come from bit operations
-//   scan       exclusive scan of the blocks' bit counts per frame (64-bit offsets)
-//   zero       the words of the bit stream the frame will use
-//   emit       each lane ORs its ZRLs, code and value bits into the big-endian bit stream at block offset + in-block prefix; the bits of
-//              different lanes are disjoint, so atomicOr on 32-bit words is order-independent
-//   ffcount / scan / scatter   0xFF bytes per 1024-byte chunk, their scan, and the copy behind the header with a 0x00 after each 0xFF;
-//              the scatter also writes the header, FFD9 and lengths[i]
+//   emit       the same kernel behind the back half's scan and zero: each lane ORs its ZRLs, code and value bits into the big-endian bit
+//              stream at block offset + in-block prefix; the bits of different lanes are disjoint, so atomicOr on 32-bit words is
+//              order-independent
+//   the back half ("the back half of every file"): scan, zero, ffcount, scan and the scatter's stuffed copy - from the blocks' bit counts to
+//              the bytes behind the header - are written once for the one entropy-coded segment of this file and the scans of a
+//              progressive one; the scatter also writes the header, FFD9 and lengths[i]
 //
 // The options (adain_jpeg_encode_opt_u8): Pillow's save with subsampling = 0 / 1 / 2 and optimize = False / True; (2, False) is the file
 // above in the launches above.  tests/jpeg_options_ref.py restates the rules, tests/test_jpeg_options_host.py holds that to Pillow.
@@ -94,8 +94,29 @@ constexpr int GREY_PER_WG = 32;         // L: 32 blocks = 256 x 8 pixels, 256 th
 constexpr int CHUNK = 1024;             // bytes of entropy-coded data per workgroup pass of the stuffing kernels (one word per thread)
 constexpr int SCAN_THREADS = 1024;
 constexpr int STREAM_GRID = 64;         // workgroups per frame of the grid-stride kernels (zero, ffcount, scatter)
+constexpr int PSCANS = 10;              // scans of a colour progressive file; grey has 6
 
 // ---- sizes -----------------------------------------------------------------------------------------------------------------------------
+// A frame's entropy-coded segments, which the back half of every file walks: a baseline file has one, a progressive file one per scan.
+// A segment's "entries" are the blocks it codes; its bits are scanned per entry, its stream is stuffed per CHUNK.  Passed by value.
+struct Segment {
+    size_t entry0, word0, chunk0;       // its first entry, stream word and stuffing chunk among the frame's
+    uint32_t nentries;
+};
+struct Segments {
+    int count;
+    int totals;                                 // total_bits and fftotal hold this many per frame: [frame][totals]
+    size_t entries, stream_words, chunks;       // per frame, of all its segments
+    Segment s[PSCANS];
+    // appends a segment of nblk blocks and at most max_bytes entropy-coded bytes before stuffing
+    void add(size_t nblk, size_t max_bytes) {
+        s[count++] = Segment{entries, stream_words, chunks, (uint32_t)nblk};
+        entries += nblk;
+        stream_words += (max_bytes + 3) / 4 + 4;
+        chunks += (max_bytes + CHUNK - 1) / CHUNK;
+    }
+};
+
 // A frame's own Huffman code of one table slot (DC0, AC0, DC1, AC1), built on the device for optimize = 1: what count and emit read in
 // place of T.huff, and the slot's DHT payload for the header.
 struct HuffSlot {
@@ -113,8 +134,7 @@ struct Plan {
     int c, hs, vs, mw, mh, bw, bh;      // hs x vs: luma blocks per MCU (RGB); mw x mh: MCUs
     size_t nblk;                  // blocks per frame in scan order, dummy blocks included
     size_t max_bytes;             // entropy-coded bytes of a frame before stuffing, at most
-    size_t stream_words;          // words of one frame's bit stream
-    size_t chunks;                // CHUNK-byte pieces of max_bytes
+    Segments seg;                 // the one segment of the file
     size_t out_stride;
     size_t o_coef, o_bits, o_off, o_total, o_stream, o_ffcnt, o_ffoff, o_fftotal, total;      // workspace offsets (bytes) of the n-frame arrays
     size_t o_hist, o_huff;              // optimize only: uint64 [n][SLOTS][256] symbol counts, HuffSlot [n][SLOTS]
@@ -129,8 +149,8 @@ Plan make_plan(int n, int h, int w, int c, int sampling = 2, bool optimize = fal
     p.mw = (w + 8 * p.hs - 1) / (8 * p.hs), p.mh = (h + 8 * p.vs - 1) / (8 * p.vs);
     p.nblk = c == 3 ? (size_t)p.mw * p.mh * (p.hs * p.vs + 2) : (size_t)p.bw * p.bh;
     p.max_bytes = (p.nblk * (optimize ? OPT_BLOCK_BITS : HOST_T.max_block_bits) + 7) / 8;
-    p.stream_words = (p.max_bytes + 3) / 4 + 4;
-    p.chunks = (p.max_bytes + CHUNK - 1) / CHUNK;
+    p.seg.totals = 1;
+    p.seg.add(p.nblk, p.max_bytes);
     p.out_stride = HOST_T.hdr_len[c == 3] + 2 * p.max_bytes + 2;
     const size_t N = (size_t)n;
     Carve ws;
@@ -138,9 +158,9 @@ Plan make_plan(int n, int h, int w, int c, int sampling = 2, bool optimize = fal
     p.o_bits = ws.take(N * p.nblk * sizeof(uint32_t));
     p.o_off = ws.take(N * p.nblk * sizeof(uint64_t));
     p.o_total = ws.take(N * sizeof(uint64_t));
-    p.o_stream = ws.take(N * p.stream_words * sizeof(uint32_t));
-    p.o_ffcnt = ws.take(N * p.chunks * sizeof(uint32_t));
-    p.o_ffoff = ws.take(N * p.chunks * sizeof(uint32_t));
+    p.o_stream = ws.take(N * p.seg.stream_words * sizeof(uint32_t));
+    p.o_ffcnt = ws.take(N * p.seg.chunks * sizeof(uint32_t));
+    p.o_ffoff = ws.take(N * p.seg.chunks * sizeof(uint32_t));
     p.o_fftotal = ws.take(N * sizeof(uint32_t));
     if (optimize) {
         p.o_hist = ws.take(N * SLOTS * 256 * sizeof(uint64_t));
@@ -394,25 +414,6 @@ __device__ __forceinline__ int lane_bits(int lane, int v, int table, const HuffS
     return len;
 }
 
-template <int HS, int VS, bool OPT>
-__global__ __launch_bounds__(256) void jpeg_count_kernel(const int16_t* __restrict__ coef, uint32_t* __restrict__ bits, Geometry g, size_t total_blocks,
-                                                         const HuffSlot* __restrict__ huff) {
-    const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (gw >= total_blocks) return;
-    const int lane = threadIdx.x & 63;
-    const size_t f = gw / g.nblk, b = gw - f * g.nblk;
-    const int16_t* fc = coef + f * g.nblk * 64;
-    int table;
-    const int diff = dc_difference<HS, VS>(fc, b, g, &table);
-    const int v = lane == 0 ? diff : fc[b * 64 + lane];
-    uint64_t pat, zrl;
-    int zrl_len;
-    int len = lane_bits<OPT>(lane, v, table, huff + f * SLOTS, &pat, &zrl, &zrl_len);
-    len += zrl_len;
-    for (int d = 32; d >= 1; d >>= 1) len += __shfl_xor(len, d);
-    if (lane == 0) bits[gw] = (uint32_t)len;
-}
-
 // ORs the `len` (1..64) right-aligned bits of pat into the big-endian bit stream at bit position pos.  A word is touched only where
 // there are bits for it: never beyond the frame's last coded bit.
 __device__ __forceinline__ void or_bits(uint32_t* __restrict__ stream, uint64_t pos, uint64_t pat, int len) {
@@ -425,9 +426,12 @@ __device__ __forceinline__ void or_bits(uint32_t* __restrict__ stream, uint64_t 
     if (w2) atomicOr(word + 2, w2);
 }
 
-template <int HS, int VS, bool OPT>
-__global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restrict__ coef, const uint64_t* __restrict__ off, uint32_t* __restrict__ stream,
-                                                        size_t stream_words, Geometry g, size_t total_blocks, const HuffSlot* __restrict__ huff) {
+// count (EMIT false): bits[block] = the bits the block's lanes put into the stream.  emit: the lanes OR them into the frame's stream, from
+// the block's offset off[block] on, each behind the lanes before it.
+template <int HS, int VS, bool OPT, bool EMIT>
+__global__ __launch_bounds__(256) void jpeg_code_kernel(const int16_t* __restrict__ coef, Geometry g, size_t total_blocks, const HuffSlot* __restrict__ huff,
+                                                        uint32_t* __restrict__ bits, const uint64_t* __restrict__ off, uint32_t* __restrict__ stream,
+                                                        size_t stream_words) {
     const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= total_blocks) return;
     const int lane = threadIdx.x & 63;
@@ -439,6 +443,12 @@ __global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restric
     uint64_t pat, zrl;
     int zrl_len;
     const int len = lane_bits<OPT>(lane, v, table, huff + f * SLOTS, &pat, &zrl, &zrl_len);
+    if (!EMIT) {
+        int sum = len + zrl_len;
+        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+        if (lane == 0) bits[gw] = (uint32_t)sum;
+        return;
+    }
     int incl = len + zrl_len;
     for (int d = 1; d < 64; d <<= 1) {
         const int up = __shfl_up(incl, d);
@@ -576,7 +586,13 @@ __global__ __launch_bounds__(TABLE_THREADS) void jpeg_table_kernel(const unsigne
     }
 }
 
-// ---- scans: one workgroup per frame ------------------------------------------------------------------------------------------------------
+// ---- the back half of every file: from the entries' bit counts to the stuffed bytes, per (frame, segment) ----------------------------------
+//   scan       out = the exclusive scan of a segment's entries' bit counts (64-bit offsets), the sum to total_bits[frame][segment]
+//   zero       the words of the bit stream the segment will use; count or emit of the file's kind then fills them
+//   ffcount    the 0xFF bytes per CHUNK of the segment's stream, the 1-bit padding of its last byte applied
+//   scan       of those counts over the chunks the segment's bits fill, the sum to fftotal[frame][segment]
+//   stuffed copy   the scatter of the file's kind places each segment's bytes behind what it writes in front of them, a 0x00 after each 0xFF
+// One workgroup per (frame, segment) scans; STREAM_GRID workgroups per frame walk the segments one after the other, a chunk per pass.
 __device__ __forceinline__ size_t stream_bytes(uint64_t bits) { return (size_t)((bits + 7) >> 3); }
 __device__ __forceinline__ size_t stream_chunks(uint64_t bits) { return (stream_bytes(bits) + CHUNK - 1) / CHUNK; }
 
@@ -606,22 +622,27 @@ __device__ __forceinline__ Out exclusive_scan(const In* __restrict__ in, Out* __
     return part[t];
 }
 
-// The scan over a frame's `count` entries (count_bits != nullptr: the chunks of that many coded bits), the sum to total[frame]
-template <class In, class Out>
-__global__ __launch_bounds__(SCAN_THREADS) void jpeg_scan_kernel(const In* __restrict__ in, Out* __restrict__ out, Out* __restrict__ total, size_t stride, size_t count,
+// out = the exclusive scan of segment blockIdx.x of frame blockIdx.y - CHUNKS false: its entries; true: the chunks its count_bits coded bits
+// fill - and the sum to total[frame][segment]
+template <class In, class Out, bool CHUNKS>
+__global__ __launch_bounds__(SCAN_THREADS) void jpeg_scan_kernel(const In* __restrict__ in, Out* __restrict__ out, Out* __restrict__ total, Segments S,
                                                                  const uint64_t* __restrict__ count_bits) {
     __shared__ Out part[SCAN_THREADS];
-    const size_t f = blockIdx.x;
-    if (count_bits) count = stream_chunks(count_bits[f]);
-    const Out sum = exclusive_scan(in + f * stride, out + f * stride, count, part);
-    if (threadIdx.x == SCAN_THREADS - 1) total[f] = sum;
+    const size_t f = blockIdx.y, slot = f * S.totals + blockIdx.x;
+    const Segment& sg = S.s[blockIdx.x];
+    const size_t at = CHUNKS ? f * S.chunks + sg.chunk0 : f * S.entries + sg.entry0;
+    const Out sum = exclusive_scan(in + at, out + at, CHUNKS ? stream_chunks(count_bits[slot]) : (size_t)sg.nentries, part);
+    if (threadIdx.x == SCAN_THREADS - 1) total[slot] = sum;
 }
 
-__global__ __launch_bounds__(256) void jpeg_zero_kernel(uint32_t* __restrict__ stream, size_t stream_words, const uint64_t* __restrict__ total_bits) {
+__global__ __launch_bounds__(256) void jpeg_zero_kernel(uint32_t* __restrict__ stream, Segments S, const uint64_t* __restrict__ total_bits) {
     const size_t f = blockIdx.y;
-    const size_t words = (size_t)((total_bits[f] + 31) >> 5) + 2;           // <= stream_words: the plan keeps 4 beyond the bound
-    uint32_t* s = stream + f * stream_words;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) s[i] = 0;
+    int k = 0;
+    do {          // a file has a segment: the first one's loads do not wait for count, as a baseline file's never did
+        const size_t words = (size_t)((total_bits[f * S.totals + k] + 31) >> 5) + 2;          // the plan keeps 4 beyond each segment's bound
+        uint32_t* s = stream + f * S.stream_words + S.s[k].word0;
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) s[i] = 0;
+    } while (++k < S.count);
 }
 
 // ---- byte stuffing -------------------------------------------------------------------------------------------------------------------------
@@ -646,18 +667,44 @@ __device__ __forceinline__ int count_ff(uint32_t v, int valid) {
     return c;
 }
 
-__global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const uint32_t* __restrict__ stream, size_t stream_words, const uint64_t* __restrict__ total_bits,
-                                                           uint32_t* __restrict__ ffcnt, size_t chunks) {
+__global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const uint32_t* __restrict__ stream, Segments S, const uint64_t* __restrict__ total_bits,
+                                                           uint32_t* __restrict__ ffcnt) {
     __shared__ int part[4];
     const size_t f = blockIdx.y;
-    const uint64_t bits = total_bits[f];
-    const uint32_t* s = stream + f * stream_words;
+    int k = 0;
+    do {          // as in jpeg_zero_kernel
+        const uint64_t bits = total_bits[f * S.totals + k];
+        const uint32_t* s = stream + f * S.stream_words + S.s[k].word0;
+        for (size_t ck = blockIdx.x; ck < stream_chunks(bits); ck += gridDim.x) {
+            int valid;
+            const uint32_t v = stream_word(s, ck * (CHUNK / 4) + threadIdx.x, bits, &valid);
+            const int incl = workgroup_inclusive(count_ff(v, valid), part);
+            if (threadIdx.x == 255) ffcnt[f * S.chunks + S.s[k].chunk0 + ck] = (uint32_t)incl;
+        }
+    } while (++k < S.count);
+}
+
+// The stuffed copy of one segment by the frame's workgroups: the `bits` coded bits of its stream s go to dst with a 0x00 after each 0xFF;
+// ffoff: per chunk of the segment, the 0xFF bytes in front of it.  part: 4 ints of LDS.
+__device__ __forceinline__ void stuffed_copy(const uint32_t* __restrict__ s, uint64_t bits, const uint32_t* __restrict__ ffoff, uint8_t* __restrict__ dst, int* part) {
     for (size_t ck = blockIdx.x; ck < stream_chunks(bits); ck += gridDim.x) {
         int valid;
         const uint32_t v = stream_word(s, ck * (CHUNK / 4) + threadIdx.x, bits, &valid);
-        const int incl = workgroup_inclusive(count_ff(v, valid), part);
-        if (threadIdx.x == 255) ffcnt[f * chunks + ck] = (uint32_t)incl;
+        const int c = count_ff(v, valid);
+        const int before = workgroup_inclusive(c, part) - c;
+        uint8_t* d = dst + ck * CHUNK + ffoff[ck] + threadIdx.x * 4 + before;
+        for (int k = 0; k < valid; ++k) {
+            const uint8_t byte = (uint8_t)(v >> (24 - 8 * k));
+            *d++ = byte;
+            if (byte == 255) *d++ = 0;
+        }
     }
+}
+
+// FFD9 behind the last segment's bytes, which end at `end`, and the file's length
+__device__ __forceinline__ void end_file(uint8_t* __restrict__ file, size_t end, int32_t* __restrict__ length) {
+    file[end] = 0xff, file[end + 1] = 0xd9;
+    *length = (int32_t)(end + 2);
 }
 
 // Byte i of a frame's header.  luma: SOF0's sampling byte of component 1.  OPT: the DHT segments hold the frame's own tables (`huff`, its
@@ -681,6 +728,7 @@ __device__ __forceinline__ int header_byte(int i, int rgb, int h, int w, int qua
     return i == T.sof_luma[rgb] ? luma : v;
 }
 
+// The baseline file of frame blockIdx.y: the header, its one segment's stuffed bytes, FFD9
 template <bool OPT>
 __global__ __launch_bounds__(256) void jpeg_scatter_kernel(const uint32_t* __restrict__ stream, size_t stream_words, const uint64_t* __restrict__ total_bits,
                                                            const uint32_t* __restrict__ ffoff, const uint32_t* __restrict__ fftotal, size_t chunks, int h, int w,
@@ -689,7 +737,6 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(const uint32_t* __res
     __shared__ int part[4];
     const size_t f = blockIdx.y;
     const uint64_t bits = total_bits[f];
-    const uint32_t* s = stream + f * stream_words;
     uint8_t* file = out + f * out_stride;
     const int slots = rgb ? 4 : 2;
     int at[SLOTS + 1] = {}, hdr = T.hdr_len[rgb];
@@ -701,24 +748,9 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(const uint32_t* __res
     }
     if (blockIdx.x == 0) {
         for (int i = threadIdx.x; i < hdr; i += 256) file[i] = (uint8_t)header_byte<OPT>(i, rgb, h, w, quality, luma, huff, at, slots);
-        if (threadIdx.x == 0) {
-            const size_t end = hdr + stream_bytes(bits) + fftotal[f];
-            file[end] = 0xff, file[end + 1] = 0xd9;
-            lengths[f] = (int32_t)(end + 2);
-        }
+        if (threadIdx.x == 0) end_file(file, hdr + stream_bytes(bits) + fftotal[f], lengths + f);
     }
-    for (size_t ck = blockIdx.x; ck < stream_chunks(bits); ck += gridDim.x) {
-        int valid;
-        const uint32_t v = stream_word(s, ck * (CHUNK / 4) + threadIdx.x, bits, &valid);
-        const int c = count_ff(v, valid);
-        const int before = workgroup_inclusive(c, part) - c;
-        uint8_t* d = file + hdr + ck * CHUNK + ffoff[f * chunks + ck] + threadIdx.x * 4 + before;
-        for (int k = 0; k < valid; ++k) {
-            const uint8_t byte = (uint8_t)(v >> (24 - 8 * k));
-            *d++ = byte;
-            if (byte == 255) *d++ = 0;
-        }
-    }
+    stuffed_copy(stream + f * stream_words, bits, ffoff + f * chunks, file + hdr, part);
 }
 
 // ---- progressive files: libjpeg's jpeg_simple_progression ------------------------------------------------------------------------------
@@ -760,10 +792,10 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(const uint32_t* __res
 //              case is one wave over a frame without detail, all blocks of a scan - 33 124 for a 1456 x 1456 frame, 518 steps; frames
 //              with detail have short runs and as many waves as runs
 //   histogram / table   the symbols per (frame, slot), the runs' n << 4 included, and their optimal codes: the stages of `optimize`
-//   count / scan / zero / emit   as the baseline stages, per (frame, scan); emit also places a lane's buffered bit behind the symbol of the
-//              lane that flushes it, or in its run's tail
-//   ffcount / scan / scatter   per (frame, scan); scatter adds up the scans' DHT, SOS and stuffed lengths and writes everything
-constexpr int PSCANS = 10;              // scans of a colour file; grey has 6
+//   count / emit   one kernel, as the baseline file's: the bits of a unit, then - behind the back half's scan and zero - the bits themselves;
+//              emit also places a lane's buffered bit behind the symbol of the lane that flushes it, or in its run's tail
+//   the back half  the baseline file's kernels ("the back half of every file") with a segment per scan; the scatter adds up the scans'
+//              DHT, SOS and stuffed lengths, writes them and calls the stuffed copy per scan
 constexpr int PSLOTS = 10;              // table slots per frame: 2 DC + 8 AC; grey uses 1 + 4
 constexpr int EOBRUN_CAP = 0x7fff;
 constexpr int CORR_CUT = 937;           // MAX_CORR_BITS - DCTSIZE2 + 1
@@ -783,13 +815,12 @@ struct PScan {
     int ss, se, ah, al;
     int slot;                           // the scan's table slot (first DC scan: Y's, the chroma one follows); -1: it codes no symbol
     uint32_t nblk;                      // blocks in the scan
-    size_t unit0, word0, chunk0;        // its first unit, stream word and stuffing chunk among the frame's
-    size_t max_bytes;                   // entropy-coded bytes before stuffing, at most
 };
 struct PScript {
     int c, hs, vs, mw, bw, bh, nscans, nslots;
-    size_t nblk, units, stream_words, chunks;          // per frame: coefficient blocks; units, stream words and chunks of all scans
+    size_t nblk;                        // coefficient blocks per frame
     PScan s[PSCANS];
+    Segments seg;                       // scan i's units, stream and chunks: segment i; its entries are the frame's units
 };
 struct ProgPlan {
     Plan base;                          // the transform's geometry
@@ -808,6 +839,7 @@ ProgPlan make_prog_plan(int n, int h, int w, int c, int sampling) {
     P.c = c, P.hs = p.base.hs, P.vs = p.base.vs, P.mw = p.base.mw, P.bw = p.base.bw, P.bh = p.base.bh;
     P.nscans = c == 3 ? PSCANS : 6, P.nslots = c == 3 ? PSLOTS : 5;
     P.nblk = p.base.nblk;
+    P.seg.totals = PSCANS;
     p.out_stride = HOST_T.dht[c == 3] + 2;
     for (int i = 0; i < P.nscans; ++i) {
         const int* d = c == 3 ? COLOUR[i] : GREY[i];
@@ -815,30 +847,27 @@ ProgPlan make_prog_plan(int n, int h, int w, int c, int sampling) {
         sc.comp = d[0], sc.ss = d[1], sc.se = d[2], sc.ah = d[3], sc.al = d[4], sc.slot = d[5];
         const size_t nblk = sc.comp < 0 ? P.nblk : sc.comp == 0 ? (size_t)P.bw * P.bh : (size_t)P.mw * p.base.mh;
         const int block_bits = sc.ss ? prog_ac_bits(sc.se - sc.ss + 1, sc.ah != 0) : sc.ah ? 1 : P_DC_FIRST_BITS;
+        const size_t max_bytes = (nblk * block_bits + 7) / 8;          // entropy-coded bytes before stuffing, at most
         sc.nblk = (uint32_t)nblk;
-        sc.max_bytes = (nblk * block_bits + 7) / 8;
-        sc.unit0 = P.units, sc.word0 = P.stream_words, sc.chunk0 = P.chunks;
-        P.units += nblk;
-        P.stream_words += (sc.max_bytes + 3) / 4 + 4;
-        P.chunks += (sc.max_bytes + CHUNK - 1) / CHUNK;
+        P.seg.add(nblk, max_bytes);
         const int tables = sc.slot < 0 ? 0 : sc.ss == 0 && c == 3 ? 2 : 1, comps = sc.comp < 0 ? c : 1;
-        p.out_stride += tables * P_DHT_BYTES + 8 + 2 * comps + 2 * sc.max_bytes;
+        p.out_stride += tables * P_DHT_BYTES + 8 + 2 * comps + 2 * max_bytes;
     }
-    const size_t N = (size_t)n;
+    const size_t N = (size_t)n, units = P.seg.entries;
     Carve ws;
     p.o_coef = ws.take(N * P.nblk * 64 * sizeof(int16_t));
-    p.o_state = ws.take(N * P.units * sizeof(uint8_t));
-    p.o_pre = ws.take(N * P.units * sizeof(uint16_t));
-    p.o_run_n = ws.take(N * P.units * sizeof(uint16_t));
-    p.o_run_be = ws.take(N * P.units * sizeof(uint16_t));
-    p.o_run_end = ws.take(N * P.units * sizeof(uint32_t));
-    p.o_body = ws.take(N * P.units * sizeof(uint32_t));
-    p.o_bits = ws.take(N * P.units * sizeof(uint32_t));
-    p.o_off = ws.take(N * P.units * sizeof(uint64_t));
+    p.o_state = ws.take(N * units * sizeof(uint8_t));
+    p.o_pre = ws.take(N * units * sizeof(uint16_t));
+    p.o_run_n = ws.take(N * units * sizeof(uint16_t));
+    p.o_run_be = ws.take(N * units * sizeof(uint16_t));
+    p.o_run_end = ws.take(N * units * sizeof(uint32_t));
+    p.o_body = ws.take(N * units * sizeof(uint32_t));
+    p.o_bits = ws.take(N * units * sizeof(uint32_t));
+    p.o_off = ws.take(N * units * sizeof(uint64_t));
     p.o_total = ws.take(N * PSCANS * sizeof(uint64_t));
-    p.o_stream = ws.take(N * P.stream_words * sizeof(uint32_t));
-    p.o_ffcnt = ws.take(N * P.chunks * sizeof(uint32_t));
-    p.o_ffoff = ws.take(N * P.chunks * sizeof(uint32_t));
+    p.o_stream = ws.take(N * P.seg.stream_words * sizeof(uint32_t));
+    p.o_ffcnt = ws.take(N * P.seg.chunks * sizeof(uint32_t));
+    p.o_ffoff = ws.take(N * P.seg.chunks * sizeof(uint32_t));
     p.o_fftotal = ws.take(N * PSCANS * sizeof(uint32_t));
     p.o_hist = ws.take(N * PSLOTS * 256 * sizeof(uint64_t));
     p.o_huff = ws.take(N * PSLOTS * sizeof(HuffSlot));
@@ -849,9 +878,11 @@ ProgPlan make_prog_plan(int n, int h, int w, int c, int sampling) {
 __device__ __forceinline__ uint64_t bits_upto(int p) { return p < 0 ? 0ull : p >= 63 ? ~0ull : (2ull << p) - 1; }          // bits 0..p
 __device__ __forceinline__ int top_bit(uint64_t m) { return m ? 63 - __clzll((long long)m) : -1; }
 
-__device__ __forceinline__ int prog_scan_of(const PScript& P, size_t unit) {
+// The scan a frame's unit is in; *first: that scan's first unit
+__device__ __forceinline__ int prog_scan_of(const PScript& P, size_t unit, size_t* first) {
     int s = 0;
-    while (s + 1 < P.nscans && unit >= P.s[s + 1].unit0) ++s;
+    *first = 0;
+    while (s + 1 < P.nscans && unit >= P.seg.s[s + 1].entry0) *first = P.seg.s[++s].entry0;
     return s;
 }
 
@@ -936,11 +967,12 @@ __global__ __launch_bounds__(256) void jpeg_prog_state_kernel(const int16_t* __r
     const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= total_units) return;
     const int lane = threadIdx.x & 63;
-    const size_t f = gw / P.units, u = gw - f * P.units;
-    const PScan& sc = P.s[prog_scan_of(P, u)];
+    const size_t f = gw / P.seg.entries, u = gw - f * P.seg.entries;
+    size_t unit0;
+    const PScan& sc = P.s[prog_scan_of(P, u, &unit0)];
     int st = 0;
     if (sc.ss) {
-        const int v = coef[(f * P.nblk + prog_coef_block(P, sc.comp, (uint32_t)(u - sc.unit0))) * 64 + lane];
+        const int v = coef[(f * P.nblk + prog_coef_block(P, sc.comp, (uint32_t)(u - unit0))) * 64 + lane];
         const PLane L = prog_lane(lane, v, sc);
         st = (L.eob >= 0 ? 1 : 0) | (L.eob != sc.se ? 2 : 0) | (__popcll(L.old_mask & ~bits_upto(L.eob)) << 2);
     }
@@ -957,10 +989,11 @@ __global__ __launch_bounds__(256) void jpeg_prog_walk_kernel(PScript P, size_t t
     const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= total_units) return;
     const int lane = threadIdx.x & 63;
-    const size_t f = gw / P.units, u = gw - f * P.units;
-    const PScan& sc = P.s[prog_scan_of(P, u)];
+    const size_t f = gw / P.seg.entries, u = gw - f * P.seg.entries;
+    size_t unit0;
+    const PScan& sc = P.s[prog_scan_of(P, u, &unit0)];
     if (sc.ss == 0) return;
-    const uint32_t bi = (uint32_t)(u - sc.unit0), s0 = state[gw];
+    const uint32_t bi = (uint32_t)(u - unit0), s0 = state[gw];
     if (!(s0 & 2) || (bi && !(s0 & 1) && (state[gw - 1] & 2))) return;
     const size_t base = gw - bi;
     uint32_t first = bi, count = 0, be = 0;          // the open run: its first block, its blocks and correction bits so far
@@ -1010,10 +1043,11 @@ __global__ __launch_bounds__(256) void jpeg_prog_histogram_kernel(const int16_t*
     for (int i = threadIdx.x; i < PSLOTS * 256; i += 256) (&cnt[0][0])[i] = 0;
     __syncthreads();
     const int16_t* fc = coef + f * P.nblk * 64;
-    for (size_t u = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < P.units; u += (size_t)gridDim.x * 4) {
-        const PScan& sc = P.s[prog_scan_of(P, u)];
+    for (size_t u = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < P.seg.entries; u += (size_t)gridDim.x * 4) {
+        size_t unit0;
+        const PScan& sc = P.s[prog_scan_of(P, u, &unit0)];
         if (sc.slot < 0) continue;
-        const uint32_t bi = (uint32_t)(u - sc.unit0);
+        const uint32_t bi = (uint32_t)(u - unit0);
         if (sc.ss == 0) {
             int table;
             const int diff = prog_dc_difference(fc, P, bi, sc.al, &table);
@@ -1023,7 +1057,7 @@ __global__ __launch_bounds__(256) void jpeg_prog_histogram_kernel(const int16_t*
         const PLane L = prog_lane(lane, fc[prog_coef_block(P, sc.comp, bi) * 64 + lane], sc);
         if (L.fresh) atomicAdd(&cnt[sc.slot][L.sym], 1u);
         if (L.nzrl) atomicAdd(&cnt[sc.slot][0xf0], (uint32_t)L.nzrl);
-        const uint32_t rn = run_n[f * P.units + u];
+        const uint32_t rn = run_n[f * P.seg.entries + u];
         if (lane == 0 && rn) atomicAdd(&cnt[sc.slot][(31 - __clz(rn)) << 4], 1u);
     }
     __syncthreads();
@@ -1043,11 +1077,13 @@ __global__ __launch_bounds__(256) void jpeg_prog_code_kernel(const int16_t* __re
     const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= total_units) return;
     const int lane = threadIdx.x & 63;
-    const size_t f = gw / P.units, u = gw - f * P.units;
-    const PScan& sc = P.s[prog_scan_of(P, u)];
-    const uint32_t bi = (uint32_t)(u - sc.unit0);
+    const size_t f = gw / P.seg.entries, u = gw - f * P.seg.entries;
+    size_t unit0;
+    const int scan = prog_scan_of(P, u, &unit0);
+    const PScan& sc = P.s[scan];
+    const uint32_t bi = (uint32_t)(u - unit0);
     const int16_t* fc = coef + f * P.nblk * 64;
-    uint32_t* st = stream + f * P.stream_words + sc.word0;
+    uint32_t* st = stream + f * P.seg.stream_words + P.seg.s[scan].word0;
     const HuffSlot* tab = huff + f * PSLOTS + max(sc.slot, 0);
     if (sc.ss == 0) {
         uint64_t pat;
@@ -1108,44 +1144,6 @@ __global__ __launch_bounds__(256) void jpeg_prog_code_kernel(const int16_t* __re
     if (lane == 0 && rn) or_bits(st, at + total, ((uint64_t)tab->code[rk << 4] << rk) | (rn & ((1u << rk) - 1)), rl);
 }
 
-// out = the exclusive scan of a (frame, scan)'s entries - CHUNKS false: the units' bits; true: the 0xFF counts of the chunks its coded bits
-// fill - and the sum to total[frame][scan]
-template <class In, class Out, bool CHUNKS>
-__global__ __launch_bounds__(SCAN_THREADS) void jpeg_prog_scan_kernel(const In* __restrict__ in, Out* __restrict__ out, Out* __restrict__ total, PScript P,
-                                                                      const uint64_t* __restrict__ count_bits) {
-    __shared__ Out part[SCAN_THREADS];
-    const size_t f = blockIdx.y, slot = f * PSCANS + blockIdx.x;
-    const PScan& sc = P.s[blockIdx.x];
-    const size_t at = CHUNKS ? f * P.chunks + sc.chunk0 : f * P.units + sc.unit0;
-    const Out sum = exclusive_scan(in + at, out + at, CHUNKS ? stream_chunks(count_bits[slot]) : (size_t)sc.nblk, part);
-    if (threadIdx.x == SCAN_THREADS - 1) total[slot] = sum;
-}
-
-__global__ __launch_bounds__(256) void jpeg_prog_zero_kernel(uint32_t* __restrict__ stream, PScript P, const uint64_t* __restrict__ total_bits) {
-    const size_t f = blockIdx.y;
-    for (int k = 0; k < P.nscans; ++k) {
-        const size_t words = (size_t)((total_bits[f * PSCANS + k] + 31) >> 5) + 2;          // the plan keeps 4 beyond each scan's bound
-        uint32_t* s = stream + f * P.stream_words + P.s[k].word0;
-        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) s[i] = 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void jpeg_prog_ffcount_kernel(const uint32_t* __restrict__ stream, PScript P, const uint64_t* __restrict__ total_bits,
-                                                                uint32_t* __restrict__ ffcnt) {
-    __shared__ int part[4];
-    const size_t f = blockIdx.y;
-    for (int k = 0; k < P.nscans; ++k) {
-        const uint64_t bits = total_bits[f * PSCANS + k];
-        const uint32_t* s = stream + f * P.stream_words + P.s[k].word0;
-        for (size_t ck = blockIdx.x; ck < stream_chunks(bits); ck += gridDim.x) {
-            int valid;
-            const uint32_t v = stream_word(s, ck * (CHUNK / 4) + threadIdx.x, bits, &valid);
-            const int incl = workgroup_inclusive(count_ff(v, valid), part);
-            if (threadIdx.x == 255) ffcnt[f * P.chunks + P.s[k].chunk0 + ck] = (uint32_t)incl;
-        }
-    }
-}
-
 // What stands in front of a scan's data: the DHT segment of each of its tables (only the symbols that occur), then SOS
 __device__ __forceinline__ int prog_scan_tables(const PScript& P, const PScan& sc) { return sc.slot < 0 ? 0 : sc.ss == 0 && P.c == 3 ? 2 : 1; }
 __device__ __forceinline__ int prog_scan_components(const PScript& P, const PScan& sc) { return sc.comp < 0 ? P.c : 1; }
@@ -1199,28 +1197,11 @@ __global__ __launch_bounds__(256) void jpeg_prog_scatter_kernel(const uint32_t* 
             file[i] = i == T.sof_hw[rgb] - 4 ? 0xc2 : (uint8_t)header_byte<false>(i, rgb, h, w, quality, luma, nullptr, nullptr, 0);          // SOF2 for SOF0
         for (int k = 0; k < P.nscans; ++k)
             for (int j = threadIdx.x; j < (int)(data_at[k] - seg_at[k]); j += 256) file[seg_at[k] + j] = (uint8_t)prog_scan_header_byte(P, P.s[k], huff, j);
-        if (threadIdx.x == 0) {
-            const size_t end = data_at[P.nscans];
-            file[end] = 0xff, file[end + 1] = 0xd9;
-            lengths[f] = (int32_t)(end + 2);
-        }
+        if (threadIdx.x == 0) end_file(file, data_at[P.nscans], lengths + f);
     }
-    for (int k = 0; k < P.nscans; ++k) {
-        const uint64_t bits = total_bits[f * PSCANS + k];
-        const uint32_t* s = stream + f * P.stream_words + P.s[k].word0;
-        for (size_t ck = blockIdx.x; ck < stream_chunks(bits); ck += gridDim.x) {
-            int valid;
-            const uint32_t v = stream_word(s, ck * (CHUNK / 4) + threadIdx.x, bits, &valid);
-            const int c = count_ff(v, valid);
-            const int before = workgroup_inclusive(c, part) - c;
-            uint8_t* d = file + data_at[k] + ck * CHUNK + ffoff[f * P.chunks + P.s[k].chunk0 + ck] + threadIdx.x * 4 + before;
-            for (int i = 0; i < valid; ++i) {
-                const uint8_t byte = (uint8_t)(v >> (24 - 8 * i));
-                *d++ = byte;
-                if (byte == 255) *d++ = 0;
-            }
-        }
-    }
+    const Segments& S = P.seg;
+    for (int k = 0; k < P.nscans; ++k)
+        stuffed_copy(stream + f * S.stream_words + S.s[k].word0, total_bits[f * PSCANS + k], ffoff + f * S.chunks + S.s[k].chunk0, file + data_at[k], part);
 }
 
 // ---- the round trip: coefficients -> pixels ---------------------------------------------------------------------------------------------
@@ -1320,35 +1301,63 @@ const char* check_options(int sampling, int optimize) {
     return nullptr;
 }
 
-}  // namespace
+// The arguments of an encode call, or (quality nullptr) of its size query, as both kinds of file check and name them; the progressive
+// entry has no optimize (nullptr)
+struct EncodeArgs {
+    const char* who;
+    int n, h, w, c;
+    const int* quality;
+    int sampling;
+    const int* optimize;
+    const char* check() const {
+        const char* bad = check_shape(n, h, w, c, quality ? *quality : 75);
+        return bad ? bad : check_options(sampling, optimize ? *optimize : 0);
+    }
+    int refuse(const char* bad) const {
+        char q[32] = "", o[32] = "";
+        if (quality) snprintf(q, sizeof q, " quality %d,", *quality);
+        if (optimize) snprintf(o, sizeof o, ", optimize %d", *optimize);
+        set_error("%s: %s (n %d, %d x %d x %d,%s sampling %d%s)", who, bad, n, h, w, c, q, sampling, o);
+        return ADAIN_EINVAL;
+    }
+};
 
-int jpeg_encode_bytes(const char* who, int n, int h, int w, int c, int sampling, int optimize, size_t* out_stride, size_t* workspace_bytes) {
-    const char* bad = check_shape(n, h, w, c, 75);
-    if (!bad) bad = check_options(sampling, optimize);
-    if (!bad && make_plan(n, h, w, c, sampling, optimize).out_stride > (size_t)INT32_MAX) bad = "a worst-case file beyond 2^31 - 1 bytes (lengths are int32)";
-    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, sampling %d, optimize %d)", who, bad, n, h, w, c, sampling, optimize); return ADAIN_EINVAL; }
-    const Plan p = make_plan(n, h, w, c, sampling, optimize);
+// The size query of either kind of file; make_the_plan is called for checked arguments only
+template <class MakeThePlan>
+int encode_bytes(const EncodeArgs& a, MakeThePlan make_the_plan, size_t* out_stride, size_t* workspace_bytes) {
+    if (const char* bad = a.check()) return a.refuse(bad);
+    const auto p = make_the_plan();
+    if (p.out_stride > (size_t)INT32_MAX) return a.refuse("a worst-case file beyond 2^31 - 1 bytes (lengths are int32)");
     if (out_stride) *out_stride = p.out_stride;
     if (workspace_bytes) *workspace_bytes = p.total;
     return 0;
 }
 
-namespace {
+// What either launcher holds the buffers of a call with checked arguments to, in this order.  entries: the plan's blocks (progressive:
+// units) per frame, which count and emit give a wave each
+template <class AnyPlan>
+int check_encode_buffers(const EncodeArgs& a, const AnyPlan& p, size_t entries, size_t out_stride, const int32_t* lengths, const void* workspace,
+                         size_t workspace_bytes) {
+    if (p.out_stride > (size_t)INT32_MAX) { set_error("%s: %d x %d x %d: a worst-case file beyond 2^31 - 1 bytes", a.who, a.h, a.w, a.c); return ADAIN_EINVAL; }
+    if (out_stride < p.out_stride) { set_error("%s: out_stride %zu below the %zu of the size query", a.who, out_stride, p.out_stride); return ADAIN_EINVAL; }
+    if (int rc = check_workspace(a.who, workspace, workspace_bytes, p.total, 8)) return rc;
+    if ((uintptr_t)lengths % 4) { set_error("%s: lengths must be 4-byte aligned", a.who); return ADAIN_EINVAL; }
+    // gridDim.y and .z are limited to 65535: h, w <= 65535 keep the block rows below that; the frames ride in y or z
+    if (a.n > 65535 || ((size_t)a.n * entries + 3) / 4 > 0x7fffffffull) { set_error("%s: batch of %d frames too large for one call", a.who, a.n); return ADAIN_EINVAL; }
+    return 0;
+}
 
-// count, (optimize) histogram and emit of one MCU layout
+// histogram (stage 0, optimize only), count (1) and emit (2) of one MCU layout
 template <int HS, int VS>
 void launch_entropy_stage(int stage, bool optimize, unsigned grid, int n, const int16_t* coef, uint32_t* bits, const uint64_t* off, uint32_t* stream,
                           size_t stream_words, const Geometry& g, size_t blocks, unsigned long long* hist, const HuffSlot* huff, hipStream_t s) {
-    if (stage == 0)
+    if (stage == 0) {
         jpeg_histogram_kernel<HS, VS><<<dim3(HIST_GRID, n), 256, 0, s>>>(coef, g, hist);
-    else if (stage == 1 && optimize)
-        jpeg_count_kernel<HS, VS, true><<<grid, 256, 0, s>>>(coef, bits, g, blocks, huff);
-    else if (stage == 1)
-        jpeg_count_kernel<HS, VS, false><<<grid, 256, 0, s>>>(coef, bits, g, blocks, huff);
-    else if (optimize)
-        jpeg_emit_kernel<HS, VS, true><<<grid, 256, 0, s>>>(coef, off, stream, stream_words, g, blocks, huff);
-    else
-        jpeg_emit_kernel<HS, VS, false><<<grid, 256, 0, s>>>(coef, off, stream, stream_words, g, blocks, huff);
+        return;
+    }
+    const auto code = stage == 1 ? (optimize ? jpeg_code_kernel<HS, VS, true, false> : jpeg_code_kernel<HS, VS, false, false>)
+                                 : (optimize ? jpeg_code_kernel<HS, VS, true, true> : jpeg_code_kernel<HS, VS, false, true>);
+    code<<<grid, 256, 0, s>>>(coef, g, blocks, huff, bits, off, stream, stream_words);
 }
 
 // The transform stage of a plan's layout
@@ -1363,41 +1372,58 @@ void launch_transform(const Plan& p, const uint8_t* src, int n, int h, int w, in
         jpeg_transform_rgb_h_kernel<1><<<dim3((p.mw + 15) / 16, p.mh, n), 384, 0, s>>>(src, h, w, quality, coef, p.mw, p.bw, p.nblk);
 }
 
+// The back half's arrays in a call's workspace, at the offsets of its plan (of either kind), and its four launches: those that place the
+// entries in the stream, in front of emit, and those that place the chunks in the file, behind it
+struct BackHalf {
+    uint32_t* bits;
+    uint64_t *off, *total;
+    uint32_t *stream, *ffcnt, *ffoff, *fftotal;
+    template <class AnyPlan>
+    BackHalf(char* ws, const AnyPlan& p)
+        : bits((uint32_t*)(ws + p.o_bits)), off((uint64_t*)(ws + p.o_off)), total((uint64_t*)(ws + p.o_total)), stream((uint32_t*)(ws + p.o_stream)),
+          ffcnt((uint32_t*)(ws + p.o_ffcnt)), ffoff((uint32_t*)(ws + p.o_ffoff)), fftotal((uint32_t*)(ws + p.o_fftotal)) {}
+    void place_entries(const Segments& S, int n, hipStream_t s) const {
+        jpeg_scan_kernel<uint32_t, uint64_t, false><<<dim3(S.count, n), SCAN_THREADS, 0, s>>>(bits, off, total, S, nullptr);
+        jpeg_zero_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, S, total);
+    }
+    void place_chunks(const Segments& S, int n, hipStream_t s) const {
+        jpeg_ffcount_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, S, total, ffcnt);
+        jpeg_scan_kernel<uint32_t, uint32_t, true><<<dim3(S.count, n), SCAN_THREADS, 0, s>>>(ffcnt, ffoff, fftotal, S, total);
+    }
+};
+
 }  // namespace
+
+int jpeg_encode_bytes(const char* who, int n, int h, int w, int c, int sampling, int optimize, size_t* out_stride, size_t* workspace_bytes) {
+    return encode_bytes({who, n, h, w, c, nullptr, sampling, &optimize}, [&] { return make_plan(n, h, w, c, sampling, optimize); }, out_stride, workspace_bytes);
+}
+
+int jpeg_encode_progressive_bytes(int n, int h, int w, int c, int sampling, size_t* out_stride, size_t* workspace_bytes) {
+    return encode_bytes({"jpeg_encode_progressive_u8", n, h, w, c, nullptr, sampling, nullptr}, [&] { return make_prog_plan(n, h, w, c, sampling); }, out_stride,
+                        workspace_bytes);
+}
 
 // sampling 2, optimize 0: the default file, in 8 launches.  Other samplings change the transform and the scan order only; optimize adds
 // the clearing of the counters (a memset), the histogram and the table stage in front of count: 10 launches, whatever n.
 int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, int optimize, uint8_t* out,
                           size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    const char* bad = check_shape(n, h, w, c, quality);
-    if (!bad) bad = check_options(sampling, optimize);
-    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, quality %d, sampling %d, optimize %d)", who, bad, n, h, w, c, quality, sampling, optimize); return ADAIN_EINVAL; }
+    const EncodeArgs a{who, n, h, w, c, &quality, sampling, &optimize};
+    if (const char* bad = a.check()) return a.refuse(bad);
     const Plan p = make_plan(n, h, w, c, sampling, optimize);
-    if (p.out_stride > (size_t)INT32_MAX) { set_error("%s: %d x %d x %d: a worst-case file beyond 2^31 - 1 bytes", who, h, w, c); return ADAIN_EINVAL; }
-    if (out_stride < p.out_stride) { set_error("%s: out_stride %zu below the %zu of the size query", who, out_stride, p.out_stride); return ADAIN_EINVAL; }
-    if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, 8)) return rc;
-    if ((uintptr_t)lengths % 4) { set_error("%s: lengths must be 4-byte aligned", who); return ADAIN_EINVAL; }
+    if (int rc = check_encode_buffers(a, p, p.nblk, out_stride, lengths, workspace, workspace_bytes)) return rc;
     char* ws = (char*)workspace;
     int16_t* coef = (int16_t*)(ws + p.o_coef);
-    uint32_t* bits = (uint32_t*)(ws + p.o_bits);
-    uint64_t* off = (uint64_t*)(ws + p.o_off);
-    uint64_t* total = (uint64_t*)(ws + p.o_total);
-    uint32_t* stream = (uint32_t*)(ws + p.o_stream);
-    uint32_t* ffcnt = (uint32_t*)(ws + p.o_ffcnt);
-    uint32_t* ffoff = (uint32_t*)(ws + p.o_ffoff);
-    uint32_t* fftotal = (uint32_t*)(ws + p.o_fftotal);
+    const BackHalf b(ws, p);
     unsigned long long* hist = optimize ? (unsigned long long*)(ws + p.o_hist) : nullptr;
     HuffSlot* huff = optimize ? (HuffSlot*)(ws + p.o_huff) : nullptr;
     const Geometry g{c, p.mw, p.bw, p.bh, p.nblk};
     const size_t blocks = (size_t)n * p.nblk;
-    // gridDim.y and .z are limited to 65535: h, w <= 65535 keep the block rows below that; the frames ride in z
-    if (n > 65535 || (blocks + 3) / 4 > 0x7fffffffull) { set_error("%s: batch of %d frames too large for one call", who, n); return ADAIN_EINVAL; }
     launch_transform(p, src, n, h, w, c, quality, coef, s);
     auto entropy = [&](int stage) {
         const unsigned grid = (unsigned)((blocks + 3) / 4);
-        if (p.vs == 2) launch_entropy_stage<2, 2>(stage, optimize, grid, n, coef, bits, off, stream, p.stream_words, g, blocks, hist, huff, s);
-        else if (p.hs == 2) launch_entropy_stage<2, 1>(stage, optimize, grid, n, coef, bits, off, stream, p.stream_words, g, blocks, hist, huff, s);
-        else launch_entropy_stage<1, 1>(stage, optimize, grid, n, coef, bits, off, stream, p.stream_words, g, blocks, hist, huff, s);
+        if (p.vs == 2) launch_entropy_stage<2, 2>(stage, optimize, grid, n, coef, b.bits, b.off, b.stream, p.seg.stream_words, g, blocks, hist, huff, s);
+        else if (p.hs == 2) launch_entropy_stage<2, 1>(stage, optimize, grid, n, coef, b.bits, b.off, b.stream, p.seg.stream_words, g, blocks, hist, huff, s);
+        else launch_entropy_stage<1, 1>(stage, optimize, grid, n, coef, b.bits, b.off, b.stream, p.seg.stream_words, g, blocks, hist, huff, s);
     };
     if (optimize) {
         if (hipMemsetAsync(hist, 0, (size_t)n * SLOTS * 256 * sizeof(uint64_t), s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return ADAIN_EINVAL; }
@@ -1405,46 +1431,26 @@ int launch_jpeg_encode_u8(const char* who, const uint8_t* src, int n, int h, int
         jpeg_table_kernel<<<dim3(c == 3 ? 4 : 2, n), TABLE_THREADS, 0, s>>>(hist, huff, SLOTS);
     }
     entropy(1);
-    jpeg_scan_kernel<uint32_t, uint64_t><<<n, SCAN_THREADS, 0, s>>>(bits, off, total, p.nblk, p.nblk, nullptr);
-    jpeg_zero_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total);
+    b.place_entries(p.seg, n, s);
     entropy(2);
-    jpeg_ffcount_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffcnt, p.chunks);
-    jpeg_scan_kernel<uint32_t, uint32_t><<<n, SCAN_THREADS, 0, s>>>(ffcnt, ffoff, fftotal, p.chunks, 0, total);
+    b.place_chunks(p.seg, n, s);
     const int luma = c == 3 ? p.hs << 4 | p.vs : 0x11;
-    if (optimize)
-        jpeg_scatter_kernel<true><<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffoff, fftotal, p.chunks, h, w, c == 3, quality, luma, huff, out, out_stride, lengths);
-    else
-        jpeg_scatter_kernel<false><<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, p.stream_words, total, ffoff, fftotal, p.chunks, h, w, c == 3, quality, luma, huff, out, out_stride, lengths);
+    const auto scatter = optimize ? jpeg_scatter_kernel<true> : jpeg_scatter_kernel<false>;
+    scatter<<<dim3(STREAM_GRID, n), 256, 0, s>>>(b.stream, p.seg.stream_words, b.total, b.ffoff, b.fftotal, p.seg.chunks, h, w, c == 3, quality, luma, huff, out,
+                                                 out_stride, lengths);
     return check_launch(who);
-}
-
-int jpeg_encode_progressive_bytes(int n, int h, int w, int c, int sampling, size_t* out_stride, size_t* workspace_bytes) {
-    const char* who = "jpeg_encode_progressive_u8";
-    const char* bad = check_shape(n, h, w, c, 75);
-    if (!bad) bad = check_options(sampling, 0);
-    if (!bad && make_prog_plan(n, h, w, c, sampling).out_stride > (size_t)INT32_MAX) bad = "a worst-case file beyond 2^31 - 1 bytes (lengths are int32)";
-    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, sampling %d)", who, bad, n, h, w, c, sampling); return ADAIN_EINVAL; }
-    const ProgPlan p = make_prog_plan(n, h, w, c, sampling);
-    if (out_stride) *out_stride = p.out_stride;
-    if (workspace_bytes) *workspace_bytes = p.total;
-    return 0;
 }
 
 // 13 launches and a memset, whatever n: transform; state, walk; histogram, table; count, scan, zero, emit; ffcount, scan, scatter
 int launch_jpeg_encode_progressive_u8(const uint8_t* src, int n, int h, int w, int c, int quality, int sampling, uint8_t* out, size_t out_stride, int32_t* lengths,
                                       void* workspace, size_t workspace_bytes, hipStream_t s) {
     const char* who = "jpeg_encode_progressive_u8";
-    const char* bad = check_shape(n, h, w, c, quality);
-    if (!bad) bad = check_options(sampling, 0);
-    if (bad) { set_error("%s: %s (n %d, %d x %d x %d, quality %d, sampling %d)", who, bad, n, h, w, c, quality, sampling); return ADAIN_EINVAL; }
+    const EncodeArgs a{who, n, h, w, c, &quality, sampling, nullptr};
+    if (const char* bad = a.check()) return a.refuse(bad);
     const ProgPlan p = make_prog_plan(n, h, w, c, sampling);
     const PScript& P = p.P;
-    if (p.out_stride > (size_t)INT32_MAX) { set_error("%s: %d x %d x %d: a worst-case file beyond 2^31 - 1 bytes", who, h, w, c); return ADAIN_EINVAL; }
-    if (out_stride < p.out_stride) { set_error("%s: out_stride %zu below the %zu of the size query", who, out_stride, p.out_stride); return ADAIN_EINVAL; }
-    if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, 8)) return rc;
-    if ((uintptr_t)lengths % 4) { set_error("%s: lengths must be 4-byte aligned", who); return ADAIN_EINVAL; }
-    const size_t units = (size_t)n * P.units;
-    if (n > 65535 || (units + 3) / 4 > 0x7fffffffull) { set_error("%s: batch of %d frames too large for one call", who, n); return ADAIN_EINVAL; }
+    if (int rc = check_encode_buffers(a, p, P.seg.entries, out_stride, lengths, workspace, workspace_bytes)) return rc;
+    const size_t units = (size_t)n * P.seg.entries;
     char* ws = (char*)workspace;
     int16_t* coef = (int16_t*)(ws + p.o_coef);
     uint8_t* state = (uint8_t*)(ws + p.o_state);
@@ -1453,13 +1459,7 @@ int launch_jpeg_encode_progressive_u8(const uint8_t* src, int n, int h, int w, i
     uint16_t* run_be = (uint16_t*)(ws + p.o_run_be);
     uint32_t* run_end = (uint32_t*)(ws + p.o_run_end);
     uint32_t* body = (uint32_t*)(ws + p.o_body);
-    uint32_t* bits = (uint32_t*)(ws + p.o_bits);
-    uint64_t* off = (uint64_t*)(ws + p.o_off);
-    uint64_t* total = (uint64_t*)(ws + p.o_total);
-    uint32_t* stream = (uint32_t*)(ws + p.o_stream);
-    uint32_t* ffcnt = (uint32_t*)(ws + p.o_ffcnt);
-    uint32_t* ffoff = (uint32_t*)(ws + p.o_ffoff);
-    uint32_t* fftotal = (uint32_t*)(ws + p.o_fftotal);
+    const BackHalf b(ws, p);
     unsigned long long* hist = (unsigned long long*)(ws + p.o_hist);
     HuffSlot* huff = (HuffSlot*)(ws + p.o_huff);
     launch_transform(p.base, src, n, h, w, c, quality, coef, s);
@@ -1469,14 +1469,12 @@ int launch_jpeg_encode_progressive_u8(const uint8_t* src, int n, int h, int w, i
     jpeg_prog_walk_kernel<<<waves, 256, 0, s>>>(P, units, state, pre, run_n, run_be, run_end);
     jpeg_prog_histogram_kernel<<<dim3(HIST_GRID, n), 256, 0, s>>>(coef, P, run_n, hist);
     jpeg_table_kernel<<<dim3(P.nslots, n), TABLE_THREADS, 0, s>>>(hist, huff, PSLOTS);
-    jpeg_prog_code_kernel<false><<<waves, 256, 0, s>>>(coef, P, units, huff, pre, run_n, run_be, run_end, body, bits, off, stream);
-    jpeg_prog_scan_kernel<uint32_t, uint64_t, false><<<dim3(P.nscans, n), SCAN_THREADS, 0, s>>>(bits, off, total, P, nullptr);
-    jpeg_prog_zero_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, P, total);
-    jpeg_prog_code_kernel<true><<<waves, 256, 0, s>>>(coef, P, units, huff, pre, run_n, run_be, run_end, body, bits, off, stream);
-    jpeg_prog_ffcount_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, P, total, ffcnt);
-    jpeg_prog_scan_kernel<uint32_t, uint32_t, true><<<dim3(P.nscans, n), SCAN_THREADS, 0, s>>>(ffcnt, ffoff, fftotal, P, total);
+    jpeg_prog_code_kernel<false><<<waves, 256, 0, s>>>(coef, P, units, huff, pre, run_n, run_be, run_end, body, b.bits, b.off, b.stream);
+    b.place_entries(P.seg, n, s);
+    jpeg_prog_code_kernel<true><<<waves, 256, 0, s>>>(coef, P, units, huff, pre, run_n, run_be, run_end, body, b.bits, b.off, b.stream);
+    b.place_chunks(P.seg, n, s);
     const int luma = c == 3 ? P.hs << 4 | P.vs : 0x11;
-    jpeg_prog_scatter_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(stream, P, total, ffoff, fftotal, h, w, quality, luma, huff, out, out_stride, lengths);
+    jpeg_prog_scatter_kernel<<<dim3(STREAM_GRID, n), 256, 0, s>>>(b.stream, P, b.total, b.ffoff, b.fftotal, h, w, quality, luma, huff, out, out_stride, lengths);
     return check_launch(who);
 }
 
@@ -1493,15 +1491,11 @@ int launch_jpeg_roundtrip_u8(const uint8_t* src, int n, int h, int w, int c, int
     const RoundtripPlan p = make_roundtrip_plan(n, h, w, c);
     if (int rc = check_workspace("jpeg_roundtrip_u8", workspace, workspace_bytes, p.total, 8)) return rc;
     const DecPlanes& g = p.g;
-    const int bw = (w + 7) / 8, bh = (h + 7) / 8;
     // gridDim.y and .z are limited to 65535: h <= 65535 keeps the rows below that; the frames ride in y (idct) and z (transform, merge)
     if (n > 65535 || (g.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG > 0x7fffffffull) { set_error("jpeg_roundtrip_u8: batch of %d frames too large for one call", n); return ADAIN_EINVAL; }
     int16_t* coef = (int16_t*)((char*)workspace + p.o_coef);
     uint8_t* planes = (uint8_t*)workspace + p.o_planes;
-    if (c == 3)
-        jpeg_transform_rgb_kernel<<<dim3((g.mw + MCUS_PER_WG - 1) / MCUS_PER_WG, g.mh, n), MCUS_PER_WG * 48, 0, s>>>(src, h, w, quality, coef, g.mw, bw, bh, g.nblk);
-    else
-        jpeg_transform_grey_kernel<<<dim3((bw + GREY_PER_WG - 1) / GREY_PER_WG, bh, n), GREY_PER_WG * 8, 0, s>>>(src, h, w, quality, coef, bw, g.nblk);
+    launch_transform(make_plan(n, h, w, c), src, n, h, w, c, quality, coef, s);          // the default file's layout: g's blocks
     jpeg_idct_kernel<<<dim3((unsigned)((g.nblk + IDCT_PER_WG - 1) / IDCT_PER_WG), n), IDCT_PER_WG * 8, 0, s>>>(coef, quality, planes, g);
     const dim3 grid((w + MERGE_PX - 1) / MERGE_PX, h, n);
     if (c == 3)

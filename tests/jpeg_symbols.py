@@ -1,4 +1,4 @@
-"""Designed frames for the JPEG entropy coder (csrc/jpeg.hip: lane_bits, jpeg_count_kernel, jpeg_emit_kernel and the stuffing kernels), and
+"""Designed frames for the JPEG entropy coder (csrc/jpeg.hip: lane_bits, jpeg_code_kernel's count and emit forms and the stuffing kernels), and
 a report of what a set of frames makes the coder emit.  NumPy only; everything is deterministic from this code, nothing is read from a file.
 
 Random content reaches about two thirds of the luma and two fifths of the chroma run/size symbols, no chroma DC category 11 and lane

@@ -2,7 +2,8 @@
 progressive=True)`` directly: lengths and bytes, no tolerance (tests/test_jpeg_progressive_encode_host.py holds the restatement of the
 rules to the same files on the host).  Shapes from one block up, 17 x 23 among them - at 4:2:0 the smallest frame whose luma scans run
 over another grid (3 x 3 blocks) than the MCU order (4 x 4) - the two designed frames that reach the cuts of an end-of-band run, batches,
-a misaligned source, the memory contract, the device's own progressive decoder, and a caller.  An L frame ignores ``subsampling``."""
+a misaligned source, scans longer than the stuffing kernels' grid (through the baseline and optimize entries too, which share those
+kernels), the memory contract, the device's own progressive decoder, and a caller.  An L frame ignores ``subsampling``."""
 import io
 
 import numpy as np
@@ -31,9 +32,9 @@ def rt():
     return rt
 
 
-def pillow_bytes(a, quality=75, subsampling=2):
-    """Pillow's progressive file (ImageFile.MAXBLOCK raised for the call: its buffer is w * h bytes, which a noise frame overruns)."""
-    kw = dict(quality=quality, progressive=True)
+def pillow_file(a, quality, subsampling, **kw):
+    """Pillow's file under further keywords (ImageFile.MAXBLOCK raised for the call: its buffer is w * h bytes, which a noise frame overruns)."""
+    kw["quality"] = quality
     if a.ndim == 3:
         kw["subsampling"] = subsampling
     f = io.BytesIO()
@@ -43,6 +44,11 @@ def pillow_bytes(a, quality=75, subsampling=2):
     finally:
         ImageFile.MAXBLOCK = old
     return f.getvalue()
+
+
+def pillow_bytes(a, quality=75, subsampling=2):
+    """Pillow's progressive file."""
+    return pillow_file(a, quality, subsampling, progressive=True)
 
 
 def nhwc(a):
@@ -127,6 +133,66 @@ def test_a_source_at_an_odd_address(rt):
             assert got == pillow_bytes(a)
 
 
+# ---- scans longer than the stuffing kernels' grid ---------------------------------------------------------------------------------------
+# The back half walks a segment's stream in 1024-byte chunks, 64 workgroups per frame: a workgroup takes a second chunk only in a segment
+# beyond 64 x 1024 bytes.  Noise at quality 100 and 4:4:4 is the smallest convenient frame with such scans (128 x 200 stays at 21 KB);
+# its progressive file also has scans below one chunk, and its baseline files are one segment of several grids.
+LONG = dict(h=256, w=456, quality=100, subsampling=0)
+GRID_BYTES = 64 * 1024
+ENTRIES = {"baseline": {}, "optimize": {"optimize": True}, "progressive": {"progressive": True}}
+
+
+def long_frames(n):
+    return np.stack([J.content("noise", LONG["h"], LONG["w"], 3, seed=i) for i in range(n)])
+
+
+def scan_segment_bytes(data):
+    """The stuffed bytes of each entropy-coded segment of a JPEG file without restart markers."""
+    sizes, at = [], 2
+    while data[at + 1] != 0xD9:
+        assert data[at] == 0xFF
+        marker, at = data[at + 1], at + 2 + int.from_bytes(data[at + 2:at + 4], "big")
+        if marker == 0xDA:
+            end = at
+            while not (data[end] == 0xFF and data[end + 1] != 0x00):
+                end += 1
+            sizes.append(end - at)
+            at = end
+    return sizes
+
+
+@pytest.fixture(scope="module")
+def long_pillow():
+    """{entry: Pillow's files of long_frames(2)}: computed once."""
+    frames = long_frames(2)
+    return {name: [pillow_file(f, LONG["quality"], LONG["subsampling"], **kw) for f in frames] for name, kw in ENTRIES.items()}
+
+
+def test_scans_longer_than_the_stream_grid(rt, long_pillow):
+    want = long_pillow["progressive"][0]
+    sizes = scan_segment_bytes(want)
+    print("stuffed bytes per scan:", sizes)
+    assert len(sizes) == 10 and max(sizes) > GRID_BYTES and min(sizes) < 1024, sizes          # the case wraps the grid, and not in every scan
+    got, = device_files(rt, long_frames(1), LONG["quality"], LONG["subsampling"])
+    assert got == want, first_difference(got, want)
+
+
+@pytest.mark.parametrize("entry", list(ENTRIES))
+def test_a_batch_of_long_segments_through_every_entry(rt, long_pillow, entry):
+    """The second frame's chunks lie behind the first frame's in the workspace: more than one grid of them in every entry."""
+    frames = long_frames(2)
+    want = long_pillow[entry]
+    assert all(max(scan_segment_bytes(f)) > GRID_BYTES for f in want)
+
+    def files(x):
+        out, lengths = rt.jpeg_encode_u8(torch.from_numpy(x).to(DEV), LONG["quality"], LONG["subsampling"], **ENTRIES[entry])
+        return rt.jpeg_files(out, lengths)
+
+    batch = files(frames)
+    assert batch == [files(frames[i:i + 1])[0] for i in range(2)]
+    assert batch == want, [first_difference(g, w) for g, w in zip(batch, want)]
+
+
 # ---- the memory contract, through the guard-band arena ----------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,h,w,c,s,kind", [(1, 1, 1, 3, 2, "noise"), (3, 37, 53, 3, 2, "noise"), (2, 17, 23, 3, 0, "binary"), (2, 40, 72, 1, 2, "binary"),
                                             (1, 256, 256, 1, 2, "stripes")])
@@ -134,6 +200,15 @@ def test_the_call_stays_in_its_buffers_and_ignores_stale_bytes(rt, n, h, w, c, s
     """out, lengths and the workspace start as 0xFF bytes and as a non-zero pattern: the files and lengths are the same, no byte outside
     the three regions changes, none behind a file inside `out` either; a smaller call through the same workspace in between (stale
     coefficients, run states, symbol counts and code tables) changes nothing."""
+    memory_contract(rt, n, h, w, c, s, kind, 75)
+
+
+def test_the_call_stays_in_its_buffers_with_scans_longer_than_the_grid(rt):
+    """The same contract where the stuffing kernels' workgroups take more than one chunk of a scan, in both frames of a batch."""
+    memory_contract(rt, 2, LONG["h"], LONG["w"], 3, LONG["subsampling"], "noise", LONG["quality"])
+
+
+def memory_contract(rt, n, h, w, c, s, kind, quality):
     frames = (np.stack([R.stripes()] * n) if kind == "stripes" else np.stack([J.content(kind, h, w, c, seed=i) for i in range(n)])).reshape(n, h, w, c)
     stride, nbytes = rt.jpeg_encode_sizes(n, h, w, c, s, progressive=True)
     specs = [("src", frames.size, "in", 1), ("out", n * stride, "ws", 1), ("lengths", 4 * n, "out", 4), ("workspace", nbytes, "ws", 8)]
@@ -141,7 +216,7 @@ def test_the_call_stays_in_its_buffers_and_ignores_stale_bytes(rt, n, h, w, c, s
     stream = torch.cuda.current_stream().cuda_stream
 
     def call(arena, shape=(n, h, w, c)):
-        rc = rt.lib().adain_jpeg_encode_progressive_u8(arena.ptr("src"), *shape, 75, s, arena.ptr("out"), stride, arena.ptr("lengths"),
+        rc = rt.lib().adain_jpeg_encode_progressive_u8(arena.ptr("src"), *shape, quality, s, arena.ptr("out"), stride, arena.ptr("lengths"),
                                                        arena.ptr("workspace"), nbytes, stream)
         assert rc == 0, rt.lib().adain_last_error().decode()
 
@@ -160,7 +235,7 @@ def test_the_call_stays_in_its_buffers_and_ignores_stale_bytes(rt, n, h, w, c, s
 
     history = (lambda arena: call(arena, (1, h // 2, w // 2, c))) if h >= 16 else None
     outs = A.run_case(specs, call, DEV, torch.cuda.synchronize, history=history, setup=lambda arena: arena.put("src", src), extra=files)
-    want = [pillow_bytes(f if c == 3 else f[..., 0], 75, s) for f in frames]
+    want = [pillow_bytes(f if c == 3 else f[..., 0], quality, s) for f in frames]
     assert outs["files"].cpu().numpy().tobytes() == b"".join(want)
     assert outs["lengths"].view(torch.int32).tolist() == [len(b) for b in want]
 

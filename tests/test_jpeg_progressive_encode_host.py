@@ -7,6 +7,7 @@ frame the cut at 0x7FFF blocks.  Then the C ABI's host side (symbols, refusals, 
 An L frame ignores ``subsampling`` as everywhere else in the encoder: its file is held to Pillow's without the keyword."""
 import ctypes
 import io
+import json
 import os
 import re
 
@@ -17,7 +18,7 @@ from PIL import Image, ImageFile
 import jpeg_progressive_encode_ref as R
 import jpeg_progressive_ref as D
 import jpeg_ref as J
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
 MODES = [(3, 0), (3, 1), (3, 2), (1, 2)]
 MODE_IDS = ["RGB-0", "RGB-1", "RGB-2", "L"]
@@ -165,6 +166,21 @@ def test_size_query_is_the_headers_derivation_and_covers_the_densest_files(rt):
         assert len(R.encode(a[..., 0], 100, 0)) <= rt.jpeg_encode_sizes(1, h, w, 1, 0, progressive=True)[0]
     # the existing queries answer what they answered (tests/golden/workspace_sizes.json pins them): not through this keyword
     assert rt.jpeg_encode_sizes(2, 37, 53, 3, 0, True) == rt.jpeg_encode_sizes(2, 37, 53, 3, 0, True, False)
+
+
+def test_the_three_size_queries_answer_what_they_answered(rt):
+    """tests/golden/jpeg_encode_sizes.json holds (out_stride, workspace_bytes) of the default, the optimize and the progressive file as
+    the library answered them before the three shared one back half (its first key names that commit): the shapes are restated here, so
+    that a row cannot leave the file unnoticed."""
+    with open(os.path.join(GOLDEN, "jpeg_encode_sizes.json")) as f:
+        recorded = json.load(f)
+    assert next(iter(recorded)) == "recorded_at" and "commit 2082791" in recorded["recorded_at"]
+    shapes = [(1, 1), (8, 8), (17, 23), (40, 72), (256, 456), (1080, 1920)]
+    want = [[n, h, w, c, s, kind] for n in (1, 3) for h, w in shapes for c in (1, 3) for s in (0, 1, 2) for kind in ("default", "optimize", "progressive")]
+    assert [row[:6] for row in recorded["rows"]] == want
+    for n, h, w, c, s, kind, stride, nbytes in recorded["rows"]:
+        got = rt.jpeg_encode_sizes(n, h, w, c, s, optimize=kind == "optimize", progressive=kind == "progressive")
+        assert got == (stride, nbytes), (n, h, w, c, s, kind)
 
 
 def test_refusals_are_the_option_entrys(rt):
