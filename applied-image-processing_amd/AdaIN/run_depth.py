@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import runtime as rt
-from .test import adain_inference, set_device_coral, set_device_png, set_jpeg_routes
+from .test import adain_inference, output_routes, set_device_coral, set_output_routes
 
 # (flag, argparse keyword arguments) — names and defaults as in the reference CLI
 _REFERENCE_FLAGS = (
@@ -69,10 +69,10 @@ def main(argv=None):
     proximity = None
     if ns.depth_npy:
         proximity = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
-    prev_jpeg = set_jpeg_routes(rt.JpegRoutes(ns.jpeg_on_device, ns.jpeg_decode_on_device or ns.jpeg_decode_progressive, ns.jpeg_decode_progressive,
-                                              (ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize, ns.jpeg_progressive)))
+    jpeg = rt.JpegRoutes(ns.jpeg_on_device, ns.jpeg_decode_on_device or ns.jpeg_decode_progressive, ns.jpeg_decode_progressive,
+                         (ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize, ns.jpeg_progressive))
+    prev_routes = set_output_routes(rt.OutputRoutes(jpeg, output_routes().png.replace(encode_on_device=ns.png_on_device)))
     prev_coral = set_device_coral(ns.coral_on_device)
-    prev_png = set_device_png(ns.png_on_device)
     style, mix = ns.style, {}
     if ns.style_interpolation_weights:
         style = ns.style.split(",")
@@ -84,9 +84,8 @@ def main(argv=None):
                                depth_prominence=ns.depth_prominence, output=ns.output, file_name=ns.file_name,
                                use_depth=ns.use_depth, depth_map=proximity, preserve_color=ns.coral_on_device, save_ext=ns.save_ext, **mix)
     finally:
-        set_jpeg_routes(prev_jpeg)
+        set_output_routes(prev_routes)
         set_device_coral(prev_coral)
-        set_device_png(prev_png)
 
 
 if __name__ == "__main__":

@@ -180,7 +180,7 @@ def device_decode_transform_u8(path, size, crop, device, mark=None):
     device (adain_jpeg_decode_u8: Pillow's pixels) and resized there.  None when the file is not a three-component baseline JPEG the
     decoder takes (or, with ``set_device_jpeg_decode(True, progressive=True)``, a progressive one), or did not decode cleanly, or the
     transform is not the device's: the caller takes the PIL path."""
-    read = rt.jpeg_read_parsed(path, _jpeg.decode_progressive)
+    read = rt.jpeg_read_parsed(path, _routes.jpeg.decode_progressive)
     if read is None or read[0].c != 3:          # PIL opens a grey file as mode L, which keeps the host transform
         return None
     parsed, data = read
@@ -200,12 +200,10 @@ def save_image(tensor, path, jpeg_options=None):
     """torchvision.utils.save_image for one image (test.py:243-244): x*255 + 0.5, clamp, uint8, PIL save.
     The quantisation runs on the GPU (adain_quantize_u8).  ``jpeg_options`` (``runtime.JpegOptions``): how a .jpg / .jpeg file is
     saved, by PIL or (``set_device_jpeg``) on the device; None: ``set_jpeg_save_options``' value."""
-    routes = _jpeg if jpeg_options is None else _jpeg.replace(options=jpeg_options)
+    routes = _routes if jpeg_options is None else _routes.replace(jpeg=_routes.jpeg.replace(options=jpeg_options))
     if tensor.dim() == 3:
         tensor = tensor.unsqueeze(0)
-    u8 = rt.quantize_u8(tensor.float()[:1])
-    if not _png.write(u8, path):
-        routes.write(u8, path)
+    routes.write(rt.quantize_u8(tensor.float()[:1]), path)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -289,37 +287,41 @@ def set_latency_schedule(enabled):
     return prev
 
 
-_jpeg = rt.JpegRoutes()               # the JPEG routes of ``adain_inference`` (the cached per-call path and ``save_image``): runtime.JpegRoutes
+_routes = rt.OutputRoutes()           # who writes (and decodes) the files of ``adain_inference``, the cached per-call path and ``save_image``
 
 
-def jpeg_routes():
-    return _jpeg
+def output_routes():
+    return _routes
 
 
-def set_jpeg_routes(routes):
-    """All of ``adain_inference``'s JPEG routes at once: a ``runtime.JpegRoutes``, a dict of its keywords, or None for the defaults (PIL
-    everywhere, Pillow's default save).  The three setters below change fields of it.  Returns the previous value."""
-    global _jpeg
-    prev, _jpeg = _jpeg, rt.JpegRoutes.of(routes)
+def set_output_routes(routes):
+    """All of ``adain_inference``'s file routes at once: a ``runtime.OutputRoutes``, a dict of its keywords, or None for the defaults (PIL
+    everywhere, Pillow's default save).  Every setter below changes fields of it.  Returns the previous value."""
+    global _routes
+    prev, _routes = _routes, rt.OutputRoutes.of(routes)
     return prev
 
 
-_png = rt.PngRoute()                  # the .png route of ``adain_inference`` (the cached per-call path and ``save_image``): runtime.PngRoute
+def jpeg_routes():
+    return _routes.jpeg
+
+
+def set_jpeg_routes(routes):
+    """The JPEG routes alone: a ``runtime.JpegRoutes``, a dict of its keywords, or None for the defaults.  Returns the previous value."""
+    return set_output_routes(_routes.replace(jpeg=routes)).jpeg
 
 
 def set_device_png(enabled):
     """``adain_inference`` (the cached per-call path and ``save_image``) encodes a ``.png`` output (``save_ext=".png"``) on the device - a
     file of the same pixels, not Pillow's bytes (``runtime.png_encode_u8``) - and brings over the file instead of the raw frame.  An RGBA
     or host frame keeps PIL.  Default False.  Returns the previous setting."""
-    global _png
-    prev, _png = _png, _png.replace(encode_on_device=enabled)
-    return prev.encode_on_device
+    return set_output_routes(_routes.replace(png=_routes.png.replace(encode_on_device=enabled))).png.encode_on_device
 
 
 def set_device_jpeg(enabled):
     """``encode_on_device``: ``adain_inference`` (the cached per-call path and ``save_image``) encodes a ``.jpg`` / ``.jpeg`` output on the
     device (the bytes PIL writes) and brings over the file instead of the raw frame.  Default False.  Returns the previous setting."""
-    return set_jpeg_routes(_jpeg.replace(encode_on_device=enabled)).encode_on_device
+    return set_jpeg_routes(_routes.jpeg.replace(encode_on_device=enabled)).encode_on_device
 
 
 def set_jpeg_save_options(quality=rt.JPEG_DEFAULT_QUALITY, subsampling=2, optimize=False, progressive=False):
@@ -327,7 +329,7 @@ def set_jpeg_save_options(quality=rt.JPEG_DEFAULT_QUALITY, subsampling=2, optimi
     ``progressive`` (``runtime.JpegOptions``, which may be given in place of ``quality``), honoured by PIL and by the device encoder: the same file.
     The defaults are Pillow's default save.  Returns the previous value (a ``JpegOptions``)."""
     new = rt.JpegOptions(quality, subsampling, optimize, progressive) if isinstance(quality, int) else quality
-    return set_jpeg_routes(_jpeg.replace(options=new)).options
+    return set_jpeg_routes(_routes.jpeg.replace(options=new)).options
 
 
 def set_device_jpeg_decode(enabled, progressive=False):
@@ -335,7 +337,7 @@ def set_device_jpeg_decode(enabled, progressive=False):
     device (the pixels PIL decodes; files with restart intervals too) and resizes it there.  A file the decoder does not take (grey, ...:
     jpeg_file.parse) or that does not decode cleanly, a PIL image and any other extension take the PIL path as before.
     ``decode_progressive`` (with ``enabled`` only): progressive files too.  Default False.  Returns the previous ``enabled``."""
-    return set_jpeg_routes(_jpeg.replace(decode_on_device=enabled, decode_progressive=progressive)).decode_on_device
+    return set_jpeg_routes(_routes.jpeg.replace(decode_on_device=enabled, decode_progressive=progressive)).decode_on_device
 
 
 _device_coral_on = False
@@ -697,7 +699,7 @@ def _content_frame(content_img, content_size, crop, device, call):
     T = _stage_timer
     t0 = time.perf_counter()
     pil_content = call.pil_content = _open(content_img)
-    if _jpeg.decode_on_device and (type(content_img) == str or isinstance(content_img, Path)) and rt.is_jpeg_path(content_img):
+    if _routes.jpeg.decode_on_device and (type(content_img) == str or isinstance(content_img, Path)) and rt.is_jpeg_path(content_img):
         e0 = torch.cuda.Event(enable_timing=True) if T.on else None
         frame = device_decode_transform_u8(content_img, content_size, crop, device, e0.record if T.on else None)
         if frame is not None:                                        # (pil_content stays lazily opened: decoded only if a depth provider asks)
@@ -822,8 +824,7 @@ def _one_call(x, style, enc, dec, device, call, e0=None, style_weights=None):
         T(next(stages), t0)
         t0 = time.perf_counter()
 
-    if not _png.write(u8, target, mark):        # a .png target under ``set_device_png``: encoded where the frame is
-        _jpeg.write(u8, target, mark)
+    _routes.write(u8, target, mark)
 
 
 def composite_with_mask(content, output_img, content_mask):

@@ -34,7 +34,7 @@ import torch
 import torch.distributed as dist
 
 from . import sharding as sh
-from .runtime import JpegOptions, JpegRoutes, PngRoute
+from .runtime import JpegOptions, JpegRoutes, OutputRoutes, PngRoute
 
 
 def style_schedule(n_frames, n_styles):
@@ -458,19 +458,18 @@ class FileSink:
     stream into a pinned buffer, a worker thread waits for it and encodes / saves the files (PIL), so the next sub-batch's
     kernels are already running.  ``close()`` waits for every file and re-raises the first error.  ``jpeg_options`` (``JpegOptions``, a
     (quality, subsampling, optimize) tuple or None for Pillow's defaults): how .jpg / .jpeg files are saved, on either route; files of
-    other extensions never see them.  ``jpeg`` (a ``runtime.JpegRoutes``) gives both in place of the two keywords.  ``jpeg_on_device`` (default off):
-    a block whose paths all end in .jpg / .jpeg is encoded on the compute stream (adain_jpeg_encode_u8: the bytes PIL would write);
-    the copy stream then brings over the lengths and, on a second stream of the sink's own, exactly that many bytes per frame, and the
-    worker only writes them.  (The files do not ride on the lengths' stream: by the time a worker knows its lengths, the launching
-    thread may have queued later blocks' length copies there, each waiting for later kernels.)  ``png_on_device`` (default off; or ``png``,
-    a ``runtime.PngRoute``): a block whose paths all end in .png goes the same way through adain_png_encode_u8 - files that decode to the
-    frames' pixels, not Pillow's bytes.  A block of mixed extensions, and every block with the switches off, is saved by PIL as before."""
+    other extensions never see them.  ``jpeg_on_device`` (default off): a block whose paths all end in .jpg / .jpeg is encoded on the
+    compute stream (adain_jpeg_encode_u8: the bytes PIL would write); the copy stream then brings over the lengths and, on a second
+    stream of the sink's own, exactly that many bytes per frame, and the worker only writes them.  (The files do not ride on the
+    lengths' stream: by the time a worker knows its lengths, the launching thread may have queued later blocks' length copies there,
+    each waiting for later kernels.)  ``png_on_device`` (default off): a block whose paths all end in .png goes the same way through
+    adain_png_encode_u8 - files of the frames' pixels, not Pillow's bytes.  ``routes`` (a ``runtime.OutputRoutes``) gives all three.  A
+    block of mixed extensions, and every block with the switches off, is saved by PIL as before."""
 
-    def __init__(self, device, workers=4, max_in_flight=None, jpeg_on_device=False, jpeg_options=None, jpeg=None, png_on_device=False, png=None):
+    def __init__(self, device, workers=4, max_in_flight=None, jpeg_on_device=False, jpeg_options=None, png_on_device=False, routes=None):
         self.copier = HostCopier(device)
-        self.jpeg = JpegRoutes.of(jpeg) if jpeg is not None else JpegRoutes(encode_on_device=jpeg_on_device, options=jpeg_options)
-        self.png = PngRoute.of(png) if png is not None else PngRoute(encode_on_device=png_on_device)
-        self.file_stream = torch.cuda.Stream(self.copier.device) if (self.jpeg.encode_on_device or self.png.encode_on_device) and self.copier.cuda else None
+        self.routes = OutputRoutes.of(routes) if routes is not None else OutputRoutes(JpegRoutes(jpeg_on_device, options=jpeg_options), PngRoute(png_on_device))
+        self.file_stream = torch.cuda.Stream(self.copier.device) if (self.routes.jpeg.encode_on_device or self.routes.png.encode_on_device) and self.copier.cuda else None
         self.file_bytes = 0                # bytes of encoded files the workers copied (under spare_lock)
         self.pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="adain-file-sink")
         self.futures = []
@@ -494,19 +493,12 @@ class FileSink:
                 return idle.pop()
         return torch.empty(shape, dtype=torch.uint8, pin_memory=True)
 
-    def _save(self, arr, path):
-        from PIL import Image
-
-        self.jpeg.options.save(Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr), path)
+    def _save(self, arr, path):             # the host job's seam: tests slow it down
+        self.routes.save(arr, path)
 
     def _encoder(self, u8_block, paths):
-        """The device encoder of a block - ``self.jpeg.options.encode`` for .jpg / .jpeg paths, ``self.png.encode`` for .png paths - or None:
-        the block is downloaded and saved by PIL."""
-        if not (self.copier.cuda and u8_block.is_cuda and u8_block.dtype == torch.uint8 and u8_block.dim() == 4 and u8_block.shape[3] in (1, 3)):
-            return None
-        if self.jpeg.encodes(list(paths)):
-            return self.jpeg.options.encode
-        return self.png.encode if self.png.encodes(list(paths)) else None
+        """The device encoder of a block (``OutputRoutes.encoder``; a sink on a GPU and a 4-D block only), or None: downloaded and saved by PIL."""
+        return self.routes.encoder(u8_block, list(paths)) if self.copier.cuda and u8_block.dim() == 4 else None
 
     def _encodes(self, u8_block, paths):
         return self._encoder(u8_block, paths) is not None

@@ -17,7 +17,7 @@ import argparse
 import numpy as np
 import torch
 
-from .AdaIN.test import jpeg_routes, set_device_png, set_jpeg_routes
+from .AdaIN.test import output_routes, set_output_routes
 from .localized import run_localized_style_transfer
 
 # (flag, argparse keyword arguments) - names and defaults as in the reference CLI
@@ -56,16 +56,15 @@ def main(argv=None):
     extra = dict(vgg_str=ns.vgg, decoder_str=ns.decoder, save_ext=ns.save_ext)
     if ns.depth_npy:
         extra["depth_map"] = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
-    prev = set_jpeg_routes(jpeg_routes().replace(encode_on_device=ns.jpeg_on_device))
-    prev_png = set_device_png(ns.png_on_device)
+    now = output_routes()
+    prev = set_output_routes(now.replace(jpeg=now.jpeg.replace(encode_on_device=ns.jpeg_on_device), png=now.png.replace(encode_on_device=ns.png_on_device)))
     try:
         return run_localized_style_transfer(content_img_path=ns.content, style_img_path=ns.style, output_path=ns.output, file_name=ns.file_name,
                                             use_depth=ns.use_depth, background_mask=mask, colour_on_device=ns.colour_on_device,
                                             jpeg_on_device=ns.jpeg_on_device, jpeg_options=(ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize, ns.jpeg_progressive),
                                             **extra)
     finally:
-        set_jpeg_routes(prev)
-        set_device_png(prev_png)
+        set_output_routes(prev)
 
 
 if __name__ == "__main__":

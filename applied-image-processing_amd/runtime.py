@@ -999,30 +999,29 @@ class JpegRoutes(_Value):
         return self.encode_on_device and len(paths) > 0 and all(is_jpeg_path(p) for p in paths)
 
     def write(self, u8, path, mark=None):
-        """One uint8 frame [1,h,w,c] or [h,w,c] on the device -> the file at ``path``: encoded there with ``options`` when ``encodes(path)``
-        and c is 1 or 3, only the file coming over; else downloaded (a numpy frame is taken as it is) and saved by ``options.save``.
-        ``mark()`` is called after each of the three steps: the launch, the wait for the device with the download, the write."""
-        from PIL import Image
-
-        mark = mark or (lambda: None)
-        if self.encodes(path) and u8.shape[-1] in (1, 3):
-            encoded = self.options.encode(u8)
-            mark()
-            data, = jpeg_files(*encoded)
-            mark()
-            with open(str(path), "wb") as f:
-                f.write(data)
-        else:
-            mark()
-            arr = u8.cpu().numpy() if isinstance(u8, torch.Tensor) else u8
-            arr = arr[0] if arr.ndim == 4 else arr
-            mark()
-            self.options.save(Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr), path)
-        mark()
+        """``OutputRoutes.write`` with the .png route off: the device's file of a .jpg / .jpeg frame it holds, ``options.save`` for every other."""
+        OutputRoutes(jpeg=self).write(u8, path, mark)
 
     def read_rgb(self, path, device):
         """``jpeg_decode_rgb_file(path, device)`` with ``decode_on_device`` - the frame on the device, or None: the caller decodes with PIL."""
         return jpeg_decode_rgb_file(path, device, self.decode_progressive) if self.decode_on_device else None
+
+
+def _encode_files(x, tag, sizes, launch):
+    """What the file encoders share: frames [n,h,w,c] -> (files uint8 [n, stride], lengths int32 [n]) on their device.  ``sizes()`` answers
+    (out_stride, workspace_bytes), one query for both; ``launch(out, stride, lengths, ws)`` runs the encoder on the ``tag`` workspace."""
+    n, stride = x.shape[0], 0
+
+    def workspace_bytes():
+        nonlocal stride
+        stride, nbytes = sizes()
+        return nbytes
+
+    with scratch(x.device, tag, workspace_bytes) as ws:
+        out = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
+        lengths = torch.empty((n,), dtype=torch.int32, device=x.device)
+        launch(out, stride, lengths, ws)
+    return out, lengths
 
 
 def jpeg_encode_sizes(n, h, w, c, subsampling=2, optimize=False, progressive=False):
@@ -1047,25 +1046,17 @@ def jpeg_encode_u8(u8, quality=JPEG_DEFAULT_QUALITY, subsampling=2, optimize=Fal
     progressive = _jpeg_flag(progressive, "jpeg_encode_u8", "progressive")
     x = _jpeg_frames(u8, "jpeg_encode_u8", quality)
     n, h, w, c = x.shape
-    stride = 0
 
-    def sizes():                # one query answers both: the file stride is kept for the output below
-        nonlocal stride
-        stride, nbytes = jpeg_encode_sizes(n, h, w, c, sampling, optimize, progressive)
-        return nbytes
-
-    with scratch(x.device, "jpeg", sizes) as ws:
-        out = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
-        lengths = torch.empty((n,), dtype=torch.int32, device=x.device)
+    def launch(out, stride, lengths, ws):
+        tail = (out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
         if progressive:
-            _launch("adain_jpeg_encode_progressive_u8", x.data_ptr(), n, h, w, c, quality, sampling, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(),
-                    ws.numel())
+            _launch("adain_jpeg_encode_progressive_u8", x.data_ptr(), n, h, w, c, quality, sampling, *tail)
         elif (sampling, optimize) == (2, 0):
-            _launch("adain_jpeg_encode_u8", x.data_ptr(), n, h, w, c, quality, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
+            _launch("adain_jpeg_encode_u8", x.data_ptr(), n, h, w, c, quality, *tail)
         else:
-            _launch("adain_jpeg_encode_opt_u8", x.data_ptr(), n, h, w, c, quality, sampling, optimize, out.data_ptr(), stride, lengths.data_ptr(),
-                    ws.data_ptr(), ws.numel())
-    return out, lengths
+            _launch("adain_jpeg_encode_opt_u8", x.data_ptr(), n, h, w, c, quality, sampling, optimize, *tail)
+
+    return _encode_files(x, "jpeg", lambda: jpeg_encode_sizes(n, h, w, c, sampling, optimize, progressive), launch)
 
 
 def jpeg_files(out, lengths):
@@ -1105,27 +1096,20 @@ def png_encode_u8(u8, filter=None):
     filt = _png_filter(filter, "png_encode_u8")
     x = _u8_frames(u8, "png_encode_u8")
     n, h, w, c = x.shape
-    stride = 0
 
-    def sizes():                # one query answers both: the file stride is kept for the output below
-        nonlocal stride
-        stride, nbytes = png_encode_sizes(n, h, w, c)
-        return nbytes
-
-    with scratch(x.device, "png", sizes) as ws:
-        out = torch.empty((n, stride), dtype=torch.uint8, device=x.device)
-        lengths = torch.empty((n,), dtype=torch.int32, device=x.device)
+    def launch(out, stride, lengths, ws):
         _launch("adain_png_encode_u8", x.data_ptr(), n, h, w, c, filt, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
-    return out, lengths
+
+    return _encode_files(x, "png", lambda: png_encode_sizes(n, h, w, c), launch)
 
 
 png_files = jpeg_files          # the files of a ``png_encode_u8`` result as a list of ``bytes`` (waits for the device)
 
 
 class PngRoute(_Value):
-    """Whether a call's .png outputs are encoded on the device - one value for every caller, beside ``JpegRoutes``.  ``encode_on_device``:
-    .png files of uint8 device frames with 1 or 3 channels are written by ``png_encode_u8`` (the same pixels, not Pillow's bytes) and
-    only the files cross to the host; ``filter``: its row filter, None for the adaptive choice.  The default: off, Pillow's save."""
+    """Whether a call's .png outputs are encoded on the device - the ``png`` of its ``OutputRoutes``.  ``encode_on_device``: ``png_encode_u8``
+    writes them (the same pixels, not Pillow's bytes) and only the files cross to the host; ``filter``: its row filter, None for the
+    adaptive choice.  The default: off, Pillow's save."""
     __slots__ = ("encode_on_device", "filter")
 
     def __init__(self, encode_on_device=False, filter=None):
@@ -1137,30 +1121,54 @@ class PngRoute(_Value):
         paths = paths if isinstance(paths, (list, tuple)) else [paths]
         return self.encode_on_device and len(paths) > 0 and all(is_png_path(p) for p in paths)
 
-    def takes(self, u8, paths):
-        """``encodes(paths)`` and ``u8`` is what the device route takes: a uint8 GPU tensor whose last dimension is 1 or 3."""
-        return self.encodes(paths) and isinstance(u8, torch.Tensor) and u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() in (3, 4) and u8.shape[-1] in (1, 3)
-
     def encode(self, u8):
         """The device route: ``png_encode_u8`` with this filter -> (files, lengths) on the device."""
         return png_encode_u8(u8, self.filter)
 
+
+class OutputRoutes(_Value):
+    """Who writes a call's output files - one value for every caller: ``jpeg``, a ``JpegRoutes``, and ``png``, a ``PngRoute``, each given as
+    what its own ``of`` takes (None: everything off, Pillow's default save).  ``encoder`` alone decides between the device and Pillow."""
+    __slots__ = ("jpeg", "png")
+
+    def __init__(self, jpeg=None, png=None):
+        self._set(jpeg=JpegRoutes.of(jpeg), png=PngRoute.of(png))
+
+    def encoder(self, u8, paths):
+        """The device encoder of the frames ``u8`` for the file(s) at ``paths`` (one, or a list), a callable u8 -> (files, lengths), or None:
+        Pillow saves them.  The device takes a uint8 GPU tensor [n,h,w,c] or [h,w,c] with c = 1 or 3 whose paths are all .jpg / .jpeg with
+        ``jpeg.encode_on_device`` or all .png with ``png.encode_on_device``; no host frame, RGBA, float, mixed or empty list, other extension."""
+        if not (isinstance(u8, torch.Tensor) and u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() in (3, 4) and u8.shape[-1] in (1, 3)):
+            return None
+        if self.jpeg.encodes(paths):
+            return self.jpeg.options.encode
+        return self.png.encode if self.png.encodes(paths) else None
+
+    def save(self, arr, path):
+        """The host route: a numpy frame [h,w,c] (c = 1: mode L) -> the file ``jpeg.options.save`` writes (its keywords: .jpg / .jpeg only)."""
+        from PIL import Image
+
+        self.jpeg.options.save(Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr), path)
+
     def write(self, u8, path, mark=None):
-        """One uint8 frame [1,h,w,c] or [h,w,c] -> the file at ``path``: encoded on the device when ``takes(u8, path)``, only the file
-        coming over.  Returns False, having written nothing, for a frame or path this route does not take: the caller saves it as before.
-        ``mark()`` is called after each of the three steps, as ``JpegRoutes.write`` calls it: the launch, the wait for the device with the
-        download, the write."""
-        if not self.takes(u8, path):
-            return False
+        """One uint8 frame [1,h,w,c] or [h,w,c] -> the file at ``path``: encoded where it is by ``encoder(u8, path)``, only the file coming over;
+        without one downloaded (a numpy frame is taken as it is) and saved by ``save``.  ``mark()`` is called after each of the three steps:
+        the launch, the wait for the device with the download, the write."""
         mark = mark or (lambda: None)
-        encoded = self.encode(u8)
+        encode = self.encoder(u8, path)
+        if encode is not None:
+            encoded = encode(u8)
+            mark()
+            data, = jpeg_files(*encoded)
+            mark()
+            with open(str(path), "wb") as f:
+                f.write(data)
+        else:
+            mark()
+            arr = u8.cpu().numpy() if isinstance(u8, torch.Tensor) else u8
+            mark()
+            self.save(arr[0] if arr.ndim == 4 else arr, path)
         mark()
-        data, = png_files(*encoded)
-        mark()
-        with open(str(path), "wb") as f:
-            f.write(data)
-        mark()
-        return True
 
 
 def jpeg_roundtrip_sizes(n, h, w, c):

@@ -172,7 +172,7 @@ def _jpeg_roundtrip(u8):
 
 
 def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-              vgg_str, decoder_str, depth_maps, group, preserve_color, crossfade_frames, intermediate_jpeg, routes, png=None):
+              vgg_str, decoder_str, depth_maps, group, preserve_color, crossfade_frames, intermediate_jpeg, outputs):
     from . import sharding as sh
     from .engine import AdaINEngine
 
@@ -212,9 +212,9 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
             return len(names)
 
         def __getitem__(self, k):
-            if on_gpu and routes.decode_on_device:            # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg_decode.hip)
+            if on_gpu and outputs.jpeg.decode_on_device:      # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg_decode.hip)
                 with torch.cuda.device(engine.device):
-                    rgb = routes.read_rgb(os.path.join(content_dir, names[k]), engine.device)
+                    rgb = outputs.jpeg.read_rgb(os.path.join(content_dir, names[k]), engine.device)
                 plan = adain_test._device_plan(rgb.shape[1], rgb.shape[0], 256, False) if rgb is not None else None
                 if plan is not None:
                     return adain_test._device_resize(rgb[None], rgb.shape[1], rgb.shape[0], plan)[0]
@@ -235,7 +235,7 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
     styles = [stf(Image.open(p).convert("RGB")).unsqueeze(0) for p in style_paths]
     # stylise (sharded), resize to the target resolution on the owning rank, gather; the recurrence needs the flows: rank 0 only
     post = None
-    if intermediate_jpeg and routes.encode_on_device and on_gpu:
+    if intermediate_jpeg and outputs.jpeg.encode_on_device and on_gpu:
         post = engine.jpeg_roundtrip_u8                        # the same bytes, computed where the batch is (adain_jpeg_roundtrip_u8)
     elif intermediate_jpeg:
         post = lambda u8: torch.from_numpy(_jpeg_roundtrip(u8.cpu().numpy())).to(u8.device)
@@ -253,11 +253,11 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
     if rank == 0:
         # the frame-to-frame recurrence (video/utils.py:355-368) on the gathered frames; every frame is written by a worker
         # thread behind an asynchronous device -> host copy while the next frame's warp / blend is already running
-        sink = jobs.FileSink(engine.device, jpeg=routes, png=png)
+        sink = jobs.FileSink(engine.device, routes=outputs)
         try:
             n, h, w, _ = frames_u8.shape
             prev = None
-            flow_of = _flow_source(content_dir, names, flow_method, (w, h), frames_u8.device, cancel_flag, routes) if n > 1 else None
+            flow_of = _flow_source(content_dir, names, flow_method, (w, h), frames_u8.device, cancel_flag, outputs.jpeg) if n > 1 else None
             for i, name in enumerate(names):
                 if cancel_flag is not None and cancel_flag.is_set():
                     print("Stopping style transfer...")
@@ -296,12 +296,12 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
     decodes; any other file, and the sharded feeder of jobs.py, keep PIL), ``jpeg_decode_progressive`` (with it only: progressive frames
     too), ``jpeg_options`` (``jobs.JpegOptions`` or a (quality, subsampling, optimize) tuple: how the .jpg / .jpeg OUTPUT frames are saved
     on either route, default Pillow's default save; the ``intermediate_jpeg`` round trip stays quality 75 and 4:2:0 whatever they say).
-    ``png_on_device`` (default off): .png frames are encoded on the device (``rt.PngRoute``, jobs.FileSink): files of the same pixels,
-    not Pillow's bytes."""
-    routes = rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options)
-    with _routes_scope(routes):
+    ``png_on_device`` (default off): .png frames are encoded on the device (the clip's ``rt.OutputRoutes``, jobs.FileSink): files of the
+    same pixels, not Pillow's bytes."""
+    outputs = rt.OutputRoutes(rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options), rt.PngRoute(png_on_device))
+    with _routes_scope(outputs.jpeg):
         return _run_clip(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
-                         engine, vgg_str, decoder_str, depth_maps, group, preserve_color, 0, intermediate_jpeg, routes, rt.PngRoute(png_on_device))
+                         engine, vgg_str, decoder_str, depth_maps, group, preserve_color, 0, intermediate_jpeg, outputs)
 
 
 def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
@@ -322,8 +322,8 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
         raise ValueError("No style images found in the style directory.")
     if crossfade_frames and preserve_color:
         raise ValueError("crossfade_frames mixes the styles of a frame; preserve_color is not supported with it")
-    routes = rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options)
-    with _routes_scope(routes):
+    outputs = rt.OutputRoutes(rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options), rt.PngRoute(png_on_device))
+    with _routes_scope(outputs.jpeg):
         return _run_clip(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
                          cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, group, preserve_color, int(crossfade_frames),
-                         intermediate_jpeg, routes, rt.PngRoute(png_on_device))
+                         intermediate_jpeg, outputs)
