@@ -47,6 +47,7 @@ _EXTRA_FLAGS = (
     ("--jpeg_decode_progressive", dict(action="store_true", help="decode a progressive JPEG content on the GPU too (implies --jpeg_decode_on_device)")),
     ("--save_ext", dict(type=str, default=".jpg", help="extension of the result file (adain_inference's save_ext)")),
     ("--png_on_device", dict(action="store_true", help="encode a .png result on the GPU instead of in PIL (the same pixels, not Pillow's bytes)")),
+    ("--png_decode_on_device", dict(action="store_true", help="decode an 8-bit RGB .png content on the GPU instead of in PIL (the same pixels)")),
 )
 
 
@@ -71,7 +72,8 @@ def main(argv=None):
         proximity = torch.from_numpy(np.load(ns.depth_npy).astype(np.float32))
     jpeg = rt.JpegRoutes(ns.jpeg_on_device, ns.jpeg_decode_on_device or ns.jpeg_decode_progressive, ns.jpeg_decode_progressive,
                          (ns.jpeg_quality, ns.jpeg_subsampling, ns.jpeg_optimize, ns.jpeg_progressive))
-    prev_routes = set_output_routes(rt.OutputRoutes(jpeg, output_routes().png.replace(encode_on_device=ns.png_on_device)))
+    prev_routes = set_output_routes(rt.OutputRoutes(jpeg, output_routes().png.replace(encode_on_device=ns.png_on_device,
+                                                                                      decode_on_device=ns.png_decode_on_device)))
     prev_coral = set_device_coral(ns.coral_on_device)
     style, mix = ns.style, {}
     if ns.style_interpolation_weights:

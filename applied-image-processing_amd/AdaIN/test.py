@@ -196,6 +196,37 @@ def device_decode_transform_u8(path, size, crop, device, mark=None):
     return _device_resize(out, parsed.w, parsed.h, plan)
 
 
+def png_read_rgb(path):
+    """The file at ``path``, read and parsed -> (png_file.PngFile, its bytes) when it is a colour-type-2 (RGB) file the device decoder
+    takes, else None: PIL opens grey and RGBA files in modes that keep the host transform (Pillow resizes RGBA through premultiplied alpha)."""
+    from .. import png_file
+
+    with open(str(path), "rb") as f:
+        data = f.read()
+    try:
+        parsed = png_file.parse(data)
+    except png_file.UnsupportedPng:
+        return None
+    return (parsed, data) if parsed.c == 3 else None
+
+
+def device_png_decode_transform_u8(path, size, crop, device, mark=None):
+    """``device_decode_transform_u8`` for the .png file at ``path``: decoded on the device (adain_png_decode_u8: Pillow's pixels) and
+    resized there.  None when the file is not an RGB file the decoder takes, did not decode cleanly, or the transform is not the
+    device's: the caller takes the PIL path."""
+    read = png_read_rgb(path)
+    plan = _device_plan(read[0].w, read[0].h, size, crop) if read is not None else None
+    if plan is None:
+        return None
+    if mark is not None:
+        with torch.cuda.device(device):
+            mark()
+    out, record = rt.png_decode_batch([read[0]], [read[1]], device)
+    if record[0, 0].item() != 0:
+        return None
+    return _device_resize(out, read[0].w, read[0].h, plan)
+
+
 def save_image(tensor, path, jpeg_options=None):
     """torchvision.utils.save_image for one image (test.py:243-244): x*255 + 0.5, clamp, uint8, PIL save.
     The quantisation runs on the GPU (adain_quantize_u8).  ``jpeg_options`` (``runtime.JpegOptions``): how a .jpg / .jpeg file is
@@ -316,6 +347,13 @@ def set_device_png(enabled):
     file of the same pixels, not Pillow's bytes (``runtime.png_encode_u8``) - and brings over the file instead of the raw frame.  An RGBA
     or host frame keeps PIL.  Default False.  Returns the previous setting."""
     return set_output_routes(_routes.replace(png=_routes.png.replace(encode_on_device=enabled))).png.encode_on_device
+
+
+def set_device_png_decode(enabled):
+    """``decode_on_device`` of the .png route: the cached per-call path of ``adain_inference`` decodes a content given as a ``.png`` path on
+    the device (the pixels PIL decodes) and resizes it there.  A file the decoder does not take (png_file.parse), a grey or RGBA file, one
+    that does not decode cleanly and a PIL image take the PIL path as before.  Default False.  Returns the previous setting."""
+    return set_output_routes(_routes.replace(png=_routes.png.replace(decode_on_device=enabled))).png.decode_on_device
 
 
 def set_device_jpeg(enabled):
@@ -699,9 +737,15 @@ def _content_frame(content_img, content_size, crop, device, call):
     T = _stage_timer
     t0 = time.perf_counter()
     pil_content = call.pil_content = _open(content_img)
-    if _routes.jpeg.decode_on_device and (type(content_img) == str or isinstance(content_img, Path)) and rt.is_jpeg_path(content_img):
+    is_path = type(content_img) == str or isinstance(content_img, Path)
+    decode = None
+    if is_path and _routes.jpeg.decode_on_device and rt.is_jpeg_path(content_img):
+        decode = device_decode_transform_u8
+    elif is_path and _routes.png.decode_on_device and rt.is_png_path(content_img):
+        decode = device_png_decode_transform_u8
+    if decode is not None:
         e0 = torch.cuda.Event(enable_timing=True) if T.on else None
-        frame = device_decode_transform_u8(content_img, content_size, crop, device, e0.record if T.on else None)
+        frame = decode(content_img, content_size, crop, device, e0.record if T.on else None)
         if frame is not None:                                        # (pil_content stays lazily opened: decoded only if a depth provider asks)
             T("read + decode + resize content (device)", t0)
             return frame, e0

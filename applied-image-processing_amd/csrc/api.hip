@@ -572,6 +572,15 @@ int adain_png_encode_u8(const uint8_t* src, int n, int h, int w, int c, int filt
     return launch_png_encode_u8(src, n, h, w, c, filter, out, out_stride, lengths, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// .png inputs (train.py:86-115, test.py's content image, video/utils.py's frames): the launcher refuses everything itself
+int adain_png_decode_u8_bytes(int n, int h, int w, int c_file, size_t max_stream_bytes, size_t* workspace_bytes) {
+    return png_decode_bytes(n, h, w, c_file, max_stream_bytes, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_png_decode_u8(const uint8_t* streams, size_t streams_bytes, const uint64_t* offsets, int n, int h, int w, int c_file, int c_out, uint8_t* out,
+                        int32_t* record, void* workspace, size_t workspace_bytes, adain_stream_t stream) {
+    return launch_png_decode_u8(streams, streams_bytes, offsets, n, h, w, c_file, c_out, out, record, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
 }

@@ -224,6 +224,10 @@ int launch_jpeg_decode_progressive_u8(const uint8_t* files, size_t files_bytes, 
 int png_encode_bytes(int n, int h, int w, int c, size_t* out_stride, size_t* workspace_bytes);
 int launch_png_encode_u8(const uint8_t* src, int n, int h, int w, int c, int filter, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
                          size_t workspace_bytes, hipStream_t s);
+// png_decode.hip: PNG input files, pixel for pixel Pillow's (the rules: png_inflate.h, tests/png_decode_ref.py); offsets: HOST array [n + 1]
+int png_decode_bytes(int n, int h, int w, int c_file, size_t max_stream_bytes, size_t* workspace_bytes);
+int launch_png_decode_u8(const uint8_t* streams, size_t streams_bytes, const uint64_t* offsets, int n, int h, int w, int c_file, int c_out, uint8_t* out,
+                         int32_t* record, void* workspace, size_t workspace_bytes, hipStream_t s);
 
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);

@@ -225,6 +225,12 @@ class AdaINEngine:
         (``rt.jpeg_decode_u8``)."""
         return rt.jpeg_decode_u8(files, self.device, chunk_bits, mode, report, restart, progressive)
 
+    def png_decode_u8(self, files, mode=None, report=None):
+        """The bytes of PNG files (a list, or one ``bytes``) -> uint8 tensors on the engine's device, the pixels Pillow's ``Image.open``
+        gives: 8-bit non-interlaced grey, RGB and RGBA files are decoded on the device (adain_png_decode_u8), anything else by PIL as
+        before (``rt.png_decode_u8``)."""
+        return rt.png_decode_u8(files, self.device, mode, report)
+
     def jpeg_roundtrip_u8(self, frames_u8, quality=rt.JPEG_DEFAULT_QUALITY):
         """uint8 frames [n,h,w,3|1] on the device -> the frames Pillow decodes from the JPEG files it would save for them at ``quality``
         (what ``video._jpeg_roundtrip`` computes on the host), byte for byte, on the device (adain_jpeg_roundtrip_u8)."""

@@ -123,6 +123,7 @@ MAX_AUTO_SUB_BATCH = 32
 # from a batch (1280 x 1280: 335.5 / 337.5 at 2 / 4).  Larger frames have no layer left that a batch would help.
 LARGE_FRAME_PIXELS = (1.5e6, 3.0e6)
 LARGE_FRAME_SUB_BATCH = 4
+AUTO_FETCH_SUB_BATCH = 8           # the sub-batch the feeder's fetch window assumes while sub-batches are cut by frame size (sub_batch=None)
 MAX_QUEUED_BATCHES = 6             # sub-batches enqueued ahead of the device (stylize_frames_sharded)
 
 
@@ -196,7 +197,7 @@ class FrameFeeder:
             self.h2d_done = [None] * self.nslots
             self.consumed = [None] * self.nslots
         self.pool = ThreadPoolExecutor(max_workers=max(1, int(workers)), thread_name_prefix="adain-frame-fetch")
-        self.window = max(2 * (8 if self.auto else self.sub_batch), 2 * max(1, int(workers)))      # frames fetched ahead of the cutter
+        self.window = max(2 * (AUTO_FETCH_SUB_BATCH if self.auto else self.sub_batch), 2 * max(1, int(workers)))      # frames fetched ahead of the cutter
         self.thread = threading.Thread(target=self._run, name="adain-frame-feeder", daemon=True)
         self.thread.start()
 
@@ -946,7 +947,7 @@ def video_style_transfer_sharded(engine, frames, styles, *, flows=None, target_r
 def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=None, content_size=512, crop=False, alpha=0.5,
                               depth_maps=None, depth_offset=0.5, depth_prominence=20, save_ext=".jpg", sub_batch=None, group=None,
                               dst=0, write="dst", require_transport=None, writers=4, jpeg_on_device=False, preserve_color=False,
-                              jpeg_options=None, png_on_device=False):
+                              jpeg_options=None, png_on_device=False, png_decode_on_device=False):
     """The guide-image precompute of the reference's Style_3DGS/train.py:86-115 over all training views, sharded: every view
     is resized as ``adain_inference(content_size=...)`` resizes it (test.py:190-200), stylised, composited with its mask
     (``gt_image_np > 0``, train.py:97) and saved as ``<output_dir>/<name><save_ext>`` — the reference's naming, so the guide
@@ -957,9 +958,13 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
     behind them.  ``jpeg_on_device``: .jpg / .jpeg guides are encoded on the device and only the files cross to the host (FileSink;
     the same bytes).  ``jpeg_options`` (``JpegOptions``): quality, subsampling and optimize of .jpg / .jpeg guides, on either route;
     default: Pillow's default save.  ``png_on_device``: .png guides are encoded on the device (FileSink; the same pixels, not Pillow's
-    bytes).  ``preserve_color``: every view is styled with ``coral(style, view)`` (``stylize_frames_sharded``).  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
+    bytes).  ``png_decode_on_device``: 8-bit RGB views given as .png paths are decoded on the device (``rt.png_decode_batch``: the pixels
+    PIL decodes) and resized there, a rank's block in batches of the feeder's sub-batch - one call for the views of a batch that share a
+    size - on the fetch threads that run ahead of the kernels; grey and RGBA views, and whatever the decoder does not take, keep PIL and
+    the host transform.  ``preserve_color``: every view is styled with ``coral(style, view)`` (``stylize_frames_sharded``).  Every rank returns the full {name: Path} map once all files exist (an error on any rank raises on all)."""
     from PIL import Image
 
+    from . import runtime as rt
     from .AdaIN.test import device_transform_u8, test_transform_u8
 
     if write not in ("dst", "local"):
@@ -968,6 +973,39 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
     out_dir = Path(output_dir)
     out_dir.mkdir(exist_ok=True, parents=True)
     tf = test_transform_u8(content_size, crop)
+    lo, hi = sh.shard_range(len(views), world, rank)
+    png_step = max(1, int(sub_batch)) if sub_batch else AUTO_FETCH_SUB_BATCH          # the sub-batch the feeder's fetch window is sized by
+    png_lock, png_done, png_frames = threading.Lock(), set(), {}
+
+    def png_view(k):
+        """View k, a .png path of this rank's block, decoded and resized on the device - or None: the host opens it (a grey or RGBA file,
+        one that png_file.parse refuses or that did not decode cleanly, a transform that is not the device's).  The block's .png paths
+        are decoded in batches of the feeder's sub-batch - the RGB files of a batch that share a size in one ``rt.png_decode_batch`` call,
+        its record read once - on whichever fetch thread asks first; a frame stays cached until it is consumed."""
+        from .AdaIN.test import _device_plan, _device_resize, png_read_rgb
+
+        if not (lo <= k < hi):
+            return None
+        b = (k - lo) // png_step
+        with png_lock:
+            if b not in png_done:
+                png_done.add(b)
+                groups = {}
+                for q in range(lo + b * png_step, min(hi, lo + (b + 1) * png_step)):
+                    read = png_read_rgb(views[q]) if isinstance(views[q], (str, Path)) and rt.is_png_path(views[q]) else None
+                    if read is not None and _device_plan(read[0].w, read[0].h, content_size, crop) is not None:
+                        groups.setdefault(read[0].geometry, []).append((q, read[0]))
+                with torch.cuda.device(engine.device):
+                    launched = [(members, rt.png_decode_batch([p for _, p in members], None, engine.device)) for members in groups.values()]
+                    for members, (out, record) in launched:
+                        for (q, _), frame, status in zip(members, out, record[:, 0].tolist()):
+                            if status == 0:
+                                png_frames[q] = frame
+            frame = png_frames.pop(k, None)
+        if frame is None:
+            return None
+        with torch.cuda.device(engine.device):
+            return _device_resize(frame[None], frame.shape[1], frame.shape[0], _device_plan(frame.shape[1], frame.shape[0], content_size, crop))[0]
 
     class _Views:                         # lazy: a rank only opens and resizes the views of its own block
         def __len__(self):
@@ -975,6 +1013,10 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
 
         def __getitem__(self, k):
             v = views[k]
+            if png_decode_on_device and on_gpu and isinstance(v, (str, Path)) and rt.is_png_path(v):
+                d = png_view(k)
+                if d is not None:
+                    return d
             if isinstance(v, (str, Path)):
                 v = Image.open(str(v))
             if isinstance(v, (torch.Tensor, np.ndarray)):

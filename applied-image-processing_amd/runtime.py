@@ -101,6 +101,8 @@ SIGNATURES = {
     "adain_jpeg_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_png_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_png_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_png_decode_u8_bytes": (_c_int, [_c_int] * 4 + [_c_size_t, ctypes.POINTER(_c_size_t)]),
+    "adain_png_decode_u8": (_c_int, [_c_void_p, _c_size_t, ctypes.POINTER(ctypes.c_uint64)] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_progressive_u8_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
@@ -1106,15 +1108,122 @@ def png_encode_u8(u8, filter=None):
 png_files = jpeg_files          # the files of a ``png_encode_u8`` result as a list of ``bytes`` (waits for the device)
 
 
-class PngRoute(_Value):
-    """Whether a call's .png outputs are encoded on the device - the ``png`` of its ``OutputRoutes``.  ``encode_on_device``: ``png_encode_u8``
-    writes them (the same pixels, not Pillow's bytes) and only the files cross to the host; ``filter``: its row filter, None for the
-    adaptive choice.  The default: off, Pillow's save."""
-    __slots__ = ("encode_on_device", "filter")
+# --- .png input files (adain_png_decode_u8) -------------------------------------------------------------------------------------------
+def png_decode_sizes(n, h, w, c_file, max_stream_bytes):
+    """workspace_bytes of adain_png_decode_u8_bytes: the scratch of an n-file call whose longest zlib stream has ``max_stream_bytes``.
+    Host only.  AdainHipError for a refused shape."""
+    return _size_query("adain_png_decode_u8_bytes", n, h, w, c_file, max_stream_bytes)[0]
 
-    def __init__(self, encode_on_device=False, filter=None):
+
+_png_decode_lock = threading.Lock()
+
+
+def png_decode_batch(parsed, datas, device, c_out=None):
+    """``parsed``: png_file.PngFile of n files of ONE (h, w, colour type) (anything else is an error), ``datas``: their bytes, one per
+    file, or None (``jpeg_decode_batch``'s signature; a PngFile already holds its stream, so only their number is checked) -> (frames uint8 [n,h,w,c_out], record int32 [n,2]:
+    status and deflate blocks per file), both on ``device``.  ``c_out``: None for the file's channels, or 3 (grey replicated, alpha
+    dropped).  One upload - the zlib streams back to back - and one call of adain_png_decode_u8; nothing comes back and nothing waits.
+    A frame whose status is not 0 is unspecified.  The one door to the C call (looked up when called: tests count the decodes here)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise AdainHipError("png_decode_batch: expected a GPU device (the device decoder has no CPU form)")
+    n = len(parsed)
+    if n < 1 or any(p.geometry != parsed[0].geometry for p in parsed) or (datas is not None and len(datas) != n):
+        raise AdainHipError("png_decode_batch: expected the files of one height, width and colour type")
+    h, w, c = parsed[0].h, parsed[0].w, parsed[0].c
+    c_out = c if c_out is None else int(c_out)
+    offsets = [0]
+    for p in parsed:
+        offsets.append(offsets[-1] + len(p.stream))
+    up = torch.frombuffer(bytearray(b"".join(p.stream for p in parsed) + b"\0"), dtype=torch.uint8).to(device)
+    off = (ctypes.c_uint64 * (n + 1))(*offsets)
+    # Stream order is what keeps two calls off each other's workspace; the lock only keeps the size query, a growth of the stream's
+    # workspace and the launch of one thread's call together, so that a second thread on the same stream cannot re-make the workspace between them
+    with _png_decode_lock, scratch(device, "png_decode", png_decode_sizes, n, h, w, c, max(len(p.stream) for p in parsed)) as ws:
+        out = torch.empty((n, h, w, c_out), dtype=torch.uint8, device=device)
+        record = torch.empty((n, 2), dtype=torch.int32, device=device)
+        _launch("adain_png_decode_u8", up.data_ptr(), offsets[-1], off, n, h, w, c, c_out, out.data_ptr(), record.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, record
+
+
+def png_decode_u8(files, device=None, mode=None, report=None):
+    """The bytes of PNG files (a list, or one ``bytes``) -> device uint8 tensors (a list, or one): per file the array
+    ``np.asarray(Image.open(io.BytesIO(data)))`` gives - [h,w] for a grey file, [h,w,3] for RGB, [h,w,4] for RGBA - or, with ``mode``
+    "RGB" / "L", ``np.asarray(Image.open(...).convert(mode))`` (grey is replicated and alpha dropped for "RGB"; "L" from a colour file
+    goes to the host).  8-bit non-interlaced files of colour type 0, 2 or 6 are decoded on the device (adain_png_decode_u8; grouped by
+    height, width and colour type, one upload and one call per group, the record read once); whatever png_file.parse refuses, and any
+    file whose status comes back non-zero, is decoded by PIL on the host exactly as before and uploaded - PIL's exceptions pass through.
+    ``report`` (a list): per file "device" or "host: <why>", and the deflate blocks the device read."""
+    from . import png_file
+
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    datas = [bytes(files)] if single else [bytes(f) for f in files]
+    device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+    if mode not in (None, "RGB", "L"):
+        raise AdainHipError(f"png_decode_u8: mode must be None, 'RGB' or 'L', got {mode!r}")
+    results, why, blocks, groups = [None] * len(datas), [None] * len(datas), [0] * len(datas), {}
+    for i, d in enumerate(datas):
+        try:
+            p = png_file.parse(d)
+            if mode == "L" and p.c != 1:
+                raise png_file.UnsupportedPng("a colour file where grey is wanted")
+            groups.setdefault(p.geometry, []).append((i, p))
+        except png_file.UnsupportedPng as e:
+            why[i] = str(e)
+    launched = [(members, png_decode_batch([p for _, p in members], [datas[i] for i, _ in members], device, 3 if mode == "RGB" else None))
+                for members in groups.values()]
+    for members, (out, record) in launched:
+        rec = record.cpu().tolist()                      # the one read of the record: waits for the call
+        for k, (i, p) in enumerate(members):
+            blocks[i] = rec[k][1]
+            if rec[k][0] != 0:
+                why[i] = f"the zlib stream did not decode cleanly (status {rec[k][0]})"
+                continue
+            results[i] = out[k, :, :, 0] if out.shape[3] == 1 else out[k]
+    for i, d in enumerate(datas):
+        if results[i] is None:
+            results[i] = torch.from_numpy(_pil_pixels(d, mode).copy()).to(device)
+    if report is not None:
+        report[:] = [{"path": "device" if why[i] is None else "host: " + why[i], "blocks": blocks[i]} for i in range(len(datas))]
+    return results[0] if single else results
+
+
+def png_decode_rgb_file(path, device):
+    """The frame ``np.asarray(Image.open(path).convert("RGB"))`` as a uint8 [h,w,3] tensor on ``device``, decoded there - or None when
+    the file is not one the device decoder takes (not a .png name, refused by png_file.parse, a non-zero status): the caller then
+    decodes it with PIL as before.  Reads the record once (waits for the call)."""
+    from . import png_file
+
+    if not is_png_path(path) or torch.device(device).type != "cuda":
+        return None
+    with open(str(path), "rb") as f:
+        data = f.read()
+    try:
+        parsed = png_file.parse(data)
+    except png_file.UnsupportedPng:
+        return None
+    out, record = png_decode_batch([parsed], [data], device, 3)
+    return out[0] if record[0, 0].item() == 0 else None
+
+
+class PngRoute(_Value):
+    """Which of a call's .png work the device does - the ``png`` of its ``OutputRoutes``.  ``encode_on_device``: ``png_encode_u8`` writes
+    the .png outputs (the same pixels, not Pillow's bytes) and only the files cross to the host; ``filter``: its row filter, None for the
+    adaptive choice; ``decode_on_device``: .png inputs are decoded on the device (``png_decode_u8``), the same pixels.  The default:
+    everything off, Pillow's save and open.  ``repr`` names ``decode_on_device`` only when it is set."""
+    __slots__ = ("encode_on_device", "filter", "decode_on_device")
+
+    def __init__(self, encode_on_device=False, filter=None, decode_on_device=False):
         _png_filter(filter, "PngRoute")
-        self._set(encode_on_device=bool(encode_on_device), filter=filter)
+        self._set(encode_on_device=bool(encode_on_device), filter=filter, decode_on_device=bool(decode_on_device))
+
+    def __repr__(self):
+        shown = [name for name in self.__slots__ if name != "decode_on_device" or self.decode_on_device]
+        return f"PngRoute({', '.join(f'{name}={getattr(self, name)!r}' for name in shown)})"
+
+    def read_rgb(self, path, device):
+        """``png_decode_rgb_file(path, device)`` with ``decode_on_device`` - the frame on the device, or None: the caller decodes with PIL."""
+        return png_decode_rgb_file(path, device) if self.decode_on_device else None
 
     def encodes(self, paths):
         """Does the device encode the file(s) at ``paths`` (one, or a list)?  With ``encode_on_device``, when every path is .png."""
@@ -1143,6 +1252,11 @@ class OutputRoutes(_Value):
         if self.jpeg.encodes(paths):
             return self.jpeg.options.encode
         return self.png.encode if self.png.encodes(paths) else None
+
+    def read_rgb(self, path, device):
+        """The file at ``path`` as ``np.asarray(Image.open(path).convert("RGB"))`` on ``device``, decoded there by the route that owns its
+        extension (``png`` for .png, ``jpeg`` for everything else, which answers for .jpg / .jpeg) - or None: the caller decodes with PIL."""
+        return self.png.read_rgb(path, device) if is_png_path(path) else self.jpeg.read_rgb(path, device)
 
     def save(self, arr, path):
         """The host route: a numpy frame [h,w,c] (c = 1: mode L) -> the file ``jpeg.options.save`` writes (its keywords: .jpg / .jpeg only)."""

@@ -44,10 +44,12 @@ from . import runtime as rt
 from .AdaIN import test as adain_test
 
 _flow_provider = None
-# The routes (rt.JpegRoutes) of the clip that is running on THIS thread; the default outside one.  Only the public flow providers read
-# it: they are called as fn(prev, cur, resolution, method), also from a caller's wrapper, and decode as their clip does.  Everything
-# else is handed the clip's value (the feeder's fetch threads inherit no context).
-_routes = contextvars.ContextVar("video_jpeg_routes", default=rt.JpegRoutes())
+# The input routes of the clip that is running on THIS thread; the default outside one.  The value is whatever answers
+# ``read_rgb(path, device)``: the clip's rt.JpegRoutes - the default, and what a clip without ``png_decode_on_device`` sets, as before
+# that switch existed - or, with ``png_decode_on_device``, the clip's whole rt.OutputRoutes, which asks the route that owns the path's
+# extension.  Only the public flow providers read it: they are called as fn(prev, cur, resolution, method), also from a caller's
+# wrapper, and decode as their clip does.  Everything else is handed the clip's value (the feeder's fetch threads inherit no context).
+_routes = contextvars.ContextVar("video_input_routes", default=rt.JpegRoutes())
 _IMAGE_EXT = (".jpg", ".jpeg", ".png")
 
 
@@ -212,9 +214,10 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
             return len(names)
 
         def __getitem__(self, k):
-            if on_gpu and outputs.jpeg.decode_on_device:      # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg_decode.hip)
+            if on_gpu and (outputs.jpeg.decode_on_device or outputs.png.decode_on_device):
+                # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg_decode.hip, csrc/png_decode.hip)
                 with torch.cuda.device(engine.device):
-                    rgb = outputs.jpeg.read_rgb(os.path.join(content_dir, names[k]), engine.device)
+                    rgb = outputs.read_rgb(os.path.join(content_dir, names[k]), engine.device)
                 plan = adain_test._device_plan(rgb.shape[1], rgb.shape[0], 256, False) if rgb is not None else None
                 if plan is not None:
                     return adain_test._device_resize(rgb[None], rgb.shape[1], rgb.shape[0], plan)[0]
@@ -257,7 +260,7 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
         try:
             n, h, w, _ = frames_u8.shape
             prev = None
-            flow_of = _flow_source(content_dir, names, flow_method, (w, h), frames_u8.device, cancel_flag, outputs.jpeg) if n > 1 else None
+            flow_of = _flow_source(content_dir, names, flow_method, (w, h), frames_u8.device, cancel_flag, outputs) if n > 1 else None
             for i, name in enumerate(names):
                 if cancel_flag is not None and cancel_flag.is_set():
                     print("Stopping style transfer...")
@@ -286,7 +289,7 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
                              cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                              vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth", decoder_str="Style_3DGS/AdaIN/models/decoder.pth",
                              depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False, preserve_color=False,
-                             jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False):
+                             jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False, png_decode_on_device=False):
     """One style for the whole clip (video/utils.py:244-295); keyword-only extras: a ready ``engine``, checkpoint paths,
     precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``preserve_color`` (every frame is styled with
     ``coral(style, frame)``, adain_inference's colour preservation, on the device) and the call's ``rt.JpegRoutes``, field by field:
@@ -297,9 +300,11 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
     too), ``jpeg_options`` (``jobs.JpegOptions`` or a (quality, subsampling, optimize) tuple: how the .jpg / .jpeg OUTPUT frames are saved
     on either route, default Pillow's default save; the ``intermediate_jpeg`` round trip stays quality 75 and 4:2:0 whatever they say).
     ``png_on_device`` (default off): .png frames are encoded on the device (the clip's ``rt.OutputRoutes``, jobs.FileSink): files of the
-    same pixels, not Pillow's bytes."""
-    outputs = rt.OutputRoutes(rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options), rt.PngRoute(png_on_device))
-    with _routes_scope(outputs.jpeg):
+    same pixels, not Pillow's bytes.  ``png_decode_on_device`` (default off): 8-bit non-interlaced grey, RGB and RGBA .png frames are
+    decoded on the device (``rt.png_decode_rgb_file``), for the stylisation and for the package's flow providers: the pixels PIL decodes;
+    any other .png keeps PIL."""
+    outputs = rt.OutputRoutes(rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options), rt.PngRoute(png_on_device, None, png_decode_on_device))
+    with _routes_scope(outputs if outputs.png.decode_on_device else outputs.jpeg):
         return _run_clip(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
                          engine, vgg_str, decoder_str, depth_maps, group, preserve_color, 0, intermediate_jpeg, outputs)
 
@@ -309,21 +314,21 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
                                    vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth",
                                    decoder_str="Style_3DGS/AdaIN/models/decoder.pth", depth_maps=None, intermediate_jpeg=False,
                                    group=None, jpeg_on_device=False, preserve_color=False, crossfade_frames=0, jpeg_decode_on_device=False,
-                                   jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False):
+                                   jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False, png_decode_on_device=False):
     """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372).
     ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics.
     ``crossfade_frames`` (0, the default: the hard cuts of the reference): the styles cross-fade in feature space over that many
     frames centred on each switch (``jobs.style_crossfade``, style interpolation on the device; at most 16 styles, and not with
     ``preserve_color``).  ``jpeg_on_device``, ``jpeg_decode_on_device``, ``jpeg_decode_progressive``, ``jpeg_options``: the call's
     ``rt.JpegRoutes``, as in ``apply_style_transfer_ada`` (the options: the output files only, never the ``intermediate_jpeg`` round trip);
-    ``png_on_device``: as there."""
+    ``png_on_device``, ``png_decode_on_device``: as there."""
     style_images = sorted(os.listdir(style_dir))
     if len(style_images) == 0:
         raise ValueError("No style images found in the style directory.")
     if crossfade_frames and preserve_color:
         raise ValueError("crossfade_frames mixes the styles of a frame; preserve_color is not supported with it")
-    outputs = rt.OutputRoutes(rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options), rt.PngRoute(png_on_device))
-    with _routes_scope(outputs.jpeg):
+    outputs = rt.OutputRoutes(rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options), rt.PngRoute(png_on_device, None, png_decode_on_device))
+    with _routes_scope(outputs if outputs.png.decode_on_device else outputs.jpeg):
         return _run_clip(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
                          cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, group, preserve_color, int(crossfade_frames),
                          intermediate_jpeg, outputs)

@@ -546,6 +546,54 @@ ADAIN_API int adain_png_encode_u8_bytes(int n, int h, int w, int c, size_t* out_
 ADAIN_API int adain_png_encode_u8(const uint8_t* src_u8, int n, int h, int w, int c, int filter /* -1: adaptive */, uint8_t* out,
                                   size_t out_stride, int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
+/* ---- PNG input files decoded on the device, pixel for pixel what Pillow's Image.open gives (train.py:86-115, test.py's content image,
+ * video/utils.py's frames) ----------------------------------------------------------------------------------------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * n files of ONE shape: height h, width w, c_file channels (1: colour type 0, 3: colour type 2, 4: colour type 6), 8 bits deep,
+ * non-interlaced.  The host walks the chunks (png_file.py does; a file it refuses stays with the host decoder) and hands over
+ *   streams, streams_bytes   device memory, any address: per file its IDAT payloads joined - a zlib stream (RFC 1950) whose two header
+ *     bytes the host has checked - back to back
+ *   offsets   HOST array uint64 [n + 1], read before the call returns: file i's stream is streams[offsets[i] .. offsets[i + 1])
+ *   out   HWC uint8 [n][h][w][c_out], any address.  c_out is c_file, or 3: grey is replicated and alpha is dropped, the pixels of
+ *     Pillow's convert("RGB") (established against Pillow 12.2.0)
+ *   record   device int32 [n][2], 4-byte aligned: file i's status and the deflate blocks it read.  Status 0: decoded; anything else: the
+ *     frame's content is unspecified (its writes stay inside out) and the caller decodes the file on the host
+ * The rules are RFC 1950 / 1951 in full - stored, fixed and dynamic blocks, the whole 32 KiB window, matches that overlap their own
+ * output - and the PNG specification's five filters, restated in tests/png_decode_ref.py; the cores are csrc/png_inflate.h, which
+ * compiles for the host as well.  A wave per file inflates (one lane decodes up to 64 tokens, the wave writes them) into the filtered
+ * stream h (w c_file + 1) in the workspace and checks the Adler-32; a wave per file unfilters bands of 64 rows as a diagonal wavefront
+ * and writes the pixels.  Integer arithmetic throughout: a frame does not depend on the batch, the stream, the device or on what the
+ * workspace held.  3 kernel launches and one more per 64 files per call; no copy to the host, no wait.
+ * The decoder is total: whatever the bytes, every read stays inside the file's own [offsets[i], offsets[i + 1]), every write inside
+ * out, record and the workspace, every loop iteration consumes a bit of the stream or writes a byte, and a damaged file changes
+ * nothing about its neighbours in the call.  The statuses, in the order they are looked for: */
+#define ADAIN_PNGD_OK 0
+#define ADAIN_PNGD_TRUNCATED 1         /* the stream ends early: inside a header, a code, a stored block or the Adler-32 */
+#define ADAIN_PNGD_BLOCK_TYPE 2        /* block type 3 */
+#define ADAIN_PNGD_STORED_LEN 3        /* a stored block whose LEN is not ~NLEN */
+#define ADAIN_PNGD_OVERSUBSCRIBED 4    /* a set of code lengths with more codes than its lengths allow */
+#define ADAIN_PNGD_INCOMPLETE 5        /* an incomplete set other than the single one-bit code zlib accepts (a set without codes is accepted too) */
+#define ADAIN_PNGD_REPEAT 6            /* a repeat code with nothing to repeat, or one that runs past HLIT + HDIST */
+#define ADAIN_PNGD_NO_END_OF_BLOCK 7   /* a dynamic block whose symbol 256 has no code */
+#define ADAIN_PNGD_BAD_SYMBOL 8        /* length symbol 286 / 287 or distance symbol 30 / 31 */
+#define ADAIN_PNGD_FAR_DISTANCE 9      /* a distance that reaches before the stream's start */
+#define ADAIN_PNGD_TOO_MUCH 10         /* more output than h (w c_file + 1) */
+#define ADAIN_PNGD_TOO_LITTLE 11       /* less output than that */
+#define ADAIN_PNGD_TRAILING 12         /* bytes between the final block and the Adler-32, or behind it */
+#define ADAIN_PNGD_ADLER 13            /* the Adler-32 of the output is not the trailer's */
+#define ADAIN_PNGD_FILTER 14           /* a row whose filter byte is above 4 */
+#define ADAIN_PNGD_UNUSED_CODE 15      /* bits that are no code of an incomplete set that was accepted */
+#define ADAIN_PNGD_TOO_MANY_SYMBOLS 16 /* HLIT above 286 or HDIST above 30 */
+/* adain_png_decode_u8_bytes (host only): *workspace_bytes = the offsets, 8 bytes per file and the filtered streams of n files; it does
+ *   not depend on max_stream_bytes, the longest stream of the call, which is only checked.  The output may be NULL.
+ * Refused with ADAIN_EINVAL before anything is launched: a null pointer, c_file outside {1, 3, 4}, a c_out that is neither c_file nor 3,
+ * h or w below 1, n outside 1..65535, h (w c_file + 1) of 2^31 or more, offsets that run backwards or leave `streams`, a stream of 2^31
+ * bytes or more, a workspace_bytes below the query's, a workspace that is not 8-byte aligned, a record that is not 4-byte aligned.
+ * What stays with Pillow: palette, grey + alpha, 1 / 2 / 4 / 16-bit and interlaced files, tRNS, APNG. */
+ADAIN_API int adain_png_decode_u8_bytes(int n, int h, int w, int c_file, size_t max_stream_bytes, size_t* workspace_bytes);
+ADAIN_API int adain_png_decode_u8(const uint8_t* streams, size_t streams_bytes, const uint64_t* offsets, int n, int h, int w, int c_file,
+                                  int c_out, uint8_t* out, int32_t* record, void* workspace, size_t workspace_bytes, adain_stream_t stream);
+
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
  * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
