@@ -581,6 +581,22 @@ int adain_png_decode_u8(const uint8_t* streams, size_t streams_bytes, const uint
     return launch_png_decode_u8(streams, streams_bytes, offsets, n, h, w, c_file, c_out, out, record, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// the palette page (gui/second_page.py, _convert_image): the launchers refuse everything themselves
+int adain_palette_map_u8(const uint8_t* src, int n, int h, int w, const uint8_t* palette, int K, int metric, const uint8_t* lut, int grey, uint8_t* out,
+                         uint8_t* index, adain_stream_t stream) {
+    return launch_palette_map_u8(src, n, h, w, palette, K, metric, lut, grey, out, index, (hipStream_t)stream);
+}
+int adain_tone_u8(const uint8_t* src, int n, int h, int w, const uint8_t* lut, int grey, uint8_t* out, adain_stream_t stream) {
+    return launch_tone_u8(src, n, h, w, lut, grey, out, (hipStream_t)stream);
+}
+int adain_palette_dither_u8_bytes(int n, int h, int w, size_t* workspace_bytes) {
+    return palette_dither_bytes(n, h, w, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_palette_dither_u8(const uint8_t* src, int n, int h, int w, const uint8_t* palette, int K, const uint8_t* lut, int grey, uint8_t* out, uint8_t* index,
+                            void* workspace, size_t workspace_bytes, adain_stream_t stream) {
+    return launch_palette_dither_u8(src, n, h, w, palette, K, lut, grey, out, index, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
 }

@@ -229,6 +229,15 @@ int png_decode_bytes(int n, int h, int w, int c_file, size_t max_stream_bytes, s
 int launch_png_decode_u8(const uint8_t* streams, size_t streams_bytes, const uint64_t* offsets, int n, int h, int w, int c_file, int c_out, uint8_t* out,
                          int32_t* record, void* workspace, size_t workspace_bytes, hipStream_t s);
 
+// palette.hip: the palette page's recolouring, tone step and error diffusion (the rules: top of palette.hip, tests/palette_ref.py);
+// the launchers refuse everything themselves
+int launch_palette_map_u8(const uint8_t* src, int n, int h, int w, const uint8_t* palette, int K, int metric, const uint8_t* lut, int grey, uint8_t* out,
+                          uint8_t* index, hipStream_t s);
+int launch_tone_u8(const uint8_t* src, int n, int h, int w, const uint8_t* lut, int grey, uint8_t* out, hipStream_t s);
+int palette_dither_bytes(int n, int h, int w, size_t* workspace_bytes);
+int launch_palette_dither_u8(const uint8_t* src, int n, int h, int w, const uint8_t* palette, int K, const uint8_t* lut, int grey, uint8_t* out, uint8_t* index,
+                             void* workspace, size_t workspace_bytes, hipStream_t s);
+
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);
 int launch_coral(const void* style, int style_is_u8, int style_n, int hs, int ws, const void* content, int content_is_u8, int n, int hc, int wc,

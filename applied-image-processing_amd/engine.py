@@ -218,6 +218,13 @@ class AdaINEngine:
         files any reader decodes to the frames' pixels, not Pillow's bytes) -> a list of n ``bytes``; only the files cross to the host."""
         return rt.png_files(*rt.png_encode_u8(frames_u8, filter))
 
+    def pixelize_u8(self, frames_u8, colors, method="rgb", grayscale=False, brightness=0, contrast=0):
+        """Finished uint8 frames [n,h,w,3] (or [h,w,3]) on the device -> the palette page's grey / brightness / contrast / recolouring of
+        them (``pixelize.frames_post``: adain_palette_map_u8, or adain_palette_dither_u8 for "floyd-steinberg-diffused" with its error rows in
+        the stream's workspace), still on the device - ready for ``png_encode_u8``."""
+        from . import pixelize
+        return pixelize.frames_post(colors, method, grayscale, brightness, contrast)(rt.device_tensor(frames_u8, "pixelize_u8: frames", torch.uint8))
+
     def jpeg_decode_u8(self, files, chunk_bits=0, mode=None, report=None, restart=False, progressive=False):
         """The bytes of image files (a list, or one ``bytes``) -> uint8 tensors on the engine's device, the pixels Pillow's ``Image.open``
         gives: baseline JPEG files are decoded on the device (adain_jpeg_decode_restart_u8; with ``restart=True`` those with restart intervals as

@@ -103,6 +103,10 @@ SIGNATURES = {
     "adain_png_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_png_decode_u8_bytes": (_c_int, [_c_int] * 4 + [_c_size_t, ctypes.POINTER(_c_size_t)]),
     "adain_png_decode_u8": (_c_int, [_c_void_p, _c_size_t, ctypes.POINTER(ctypes.c_uint64)] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_palette_map_u8": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "adain_tone_u8": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_int, _c_void_p, _c_void_p]),
+    "adain_palette_dither_u8_bytes": (_c_int, [_c_int] * 3 + [ctypes.POINTER(_c_size_t)]),
+    "adain_palette_dither_u8": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_progressive_u8_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
@@ -1106,6 +1110,108 @@ def png_encode_u8(u8, filter=None):
 
 
 png_files = jpeg_files          # the files of a ``png_encode_u8`` result as a list of ``bytes`` (waits for the device)
+
+
+# --- palette control (adain_palette_map_u8, adain_tone_u8, adain_palette_dither_u8) --------------------------------------------------------
+PALETTE_DITHER_BAND = 1024          # ADAIN_PALETTE_DITHER_BAND: the rows one workgroup of adain_palette_dither_u8 holds at once
+PALETTE_METRICS = {"rgb": 0, "nearest": 1}          # ADAIN_PALETTE_METRIC_*
+
+
+def _rgb_frames(u8, what):
+    """uint8 [n,h,w,3] or one frame [h,w,3] on the device -> contiguous [n,h,w,3]."""
+    x = device_tensor(u8, what + ": frames", torch.uint8)
+    if x.dim() == 3:
+        x = x[None]
+    if x.dim() != 4 or x.shape[3] != 3 or x.numel() == 0:
+        raise AdainHipError(f"{what}: expected uint8 [n,h,w,3] or [h,w,3], got {tuple(u8.shape)}")
+    return x
+
+
+def palette_tensor(palette, device, what="palette"):
+    """A palette - a uint8 tensor [K,3] or a sequence of K RGB triples, 1 <= K <= 256 - as a contiguous uint8 [K,3] on ``device``."""
+    if isinstance(palette, torch.Tensor):
+        if palette.dtype != torch.uint8:
+            raise AdainHipError(f"{what}: a palette tensor must be uint8, got {palette.dtype}")
+        p = palette
+    else:
+        rows = [[int(v) for v in c] for c in palette]
+        if any(len(c) != 3 or min(c) < 0 or max(c) > 255 for c in rows):
+            raise AdainHipError(f"{what}: expected RGB triples of 0..255")
+        p = torch.tensor(rows, dtype=torch.uint8).reshape(-1, 3)
+    if p.dim() != 2 or p.shape[1] != 3 or not 1 <= p.shape[0] <= 256:
+        raise AdainHipError(f"{what}: expected [K,3] with 1 <= K <= 256, got {tuple(p.shape)}")
+    return p.to(device).contiguous()
+
+
+def _tone_args(lut, grey, device, what):
+    """(lut tensor or None, its pointer or None, grey as int).  ``lut``: None, or uint8 [256] (one table for the three channels) or [3,256]."""
+    if lut is None:
+        return None, None, int(bool(grey))
+    t = lut if isinstance(lut, torch.Tensor) else torch.as_tensor(lut)
+    if t.dtype != torch.uint8 or tuple(t.shape) not in ((256,), (3, 256)):
+        raise AdainHipError(f"{what}: lut must be uint8 [256] or [3,256], got {t.dtype} {tuple(t.shape)}")
+    t = t.expand(3, 256).to(device).contiguous()
+    return t, t.data_ptr(), int(bool(grey))
+
+
+def _index_plane(x, index):
+    return torch.empty(x.shape[:3], dtype=torch.uint8, device=x.device) if index else None
+
+
+def palette_map_u8(u8, palette, metric="nearest", lut=None, grey=False, index=False):
+    """Frames uint8 [n,h,w,3] (or [h,w,3]) on the device -> every pixel replaced by its palette entry (adain_palette_map_u8), in the
+    input's shape; with ``index`` a pair (frames, uint8 [n,h,w] or [h,w] of the chosen entries).  ``metric``: "rgb", the reference's
+    ``_recolor_image`` with its uint8 differences that wrap modulo 256, or "nearest", the true nearest colour (``_recolor_image_kd``);
+    the lowest index wins a tie.  ``grey`` / ``lut``: the tone step in front (``tone_u8``).  Nothing is copied to the host and nothing waits."""
+    what = "palette_map_u8"
+    if metric not in PALETTE_METRICS:
+        raise AdainHipError(f"{what}: metric must be one of {sorted(PALETTE_METRICS)}, got {metric!r}")
+    x = _rgb_frames(u8, what)
+    n, h, w, _ = x.shape
+    pal = palette_tensor(palette, x.device, what + ": palette")
+    keep, lut_ptr, grey = _tone_args(lut, grey, x.device, what)
+    out, idx = torch.empty_like(x), _index_plane(x, index)
+    call("adain_palette_map_u8", x.device, x.data_ptr(), n, h, w, pal.data_ptr(), pal.shape[0], PALETTE_METRICS[metric], lut_ptr, grey, out.data_ptr(),
+         idx.data_ptr() if index else None)
+    out = out.reshape(u8.shape)
+    return (out, idx.reshape(u8.shape[:-1])) if index else out
+
+
+def tone_u8(u8, lut=None, grey=False, out=None):
+    """Frames uint8 [n,h,w,3] (or [h,w,3]) -> the tone step alone (adain_tone_u8): ``grey``, Pillow's ``convert("L").convert("RGB")``,
+    then ``lut`` (uint8 [256] or [3,256]: channel c becomes lut[c][value]).  ``out``: the frames themselves for in place, or None."""
+    what = "tone_u8"
+    x = _rgb_frames(u8, what)
+    n, h, w, _ = x.shape
+    keep, lut_ptr, grey = _tone_args(lut, grey, x.device, what)
+    if out is None:
+        res = torch.empty_like(x)
+    else:
+        res = check_buffer(out, "tone_u8: out", torch.uint8, x.device, numel=x.numel())
+    call("adain_tone_u8", x.device, x.data_ptr(), n, h, w, lut_ptr, grey, res.data_ptr())
+    return res.reshape(u8.shape)
+
+
+def palette_dither_sizes(n, h, w):
+    """workspace_bytes of adain_palette_dither_u8_bytes.  Host only.  AdainHipError for a refused shape."""
+    return _size_query("adain_palette_dither_u8_bytes", n, h, w)[0]
+
+
+def palette_dither_u8(u8, palette, lut=None, grey=False, index=False):
+    """Frames uint8 [n,h,w,3] (or [h,w,3]) on the device -> Floyd-Steinberg error diffusion onto the palette (adain_palette_dither_u8): the
+    loop the reference's ``_recolor_image_floyd`` spells out, float32, bit for bit tests/palette_ref.py's sequential form.  Returns as
+    ``palette_map_u8`` does.  Nothing is copied to the host and nothing waits."""
+    what = "palette_dither_u8"
+    x = _rgb_frames(u8, what)
+    n, h, w, _ = x.shape
+    pal = palette_tensor(palette, x.device, what + ": palette")
+    keep, lut_ptr, grey = _tone_args(lut, grey, x.device, what)
+    out, idx = torch.empty_like(x), _index_plane(x, index)
+    with scratch(x.device, "palette", palette_dither_sizes, n, h, w) as ws:
+        _launch("adain_palette_dither_u8", x.data_ptr(), n, h, w, pal.data_ptr(), pal.shape[0], lut_ptr, grey, out.data_ptr(), idx.data_ptr() if index else None,
+                ws.data_ptr(), ws.numel())
+    out = out.reshape(u8.shape)
+    return (out, idx.reshape(u8.shape[:-1])) if index else out
 
 
 # --- .png input files (adain_png_decode_u8) -------------------------------------------------------------------------------------------

@@ -594,6 +594,46 @@ ADAIN_API int adain_png_decode_u8_bytes(int n, int h, int w, int c_file, size_t 
 ADAIN_API int adain_png_decode_u8(const uint8_t* streams, size_t streams_bytes, const uint64_t* offsets, int n, int h, int w, int c_file,
                                   int c_out, uint8_t* out, int32_t* record, void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
+/* ---- pixel-art palette control: the reference's palette page (gui/second_page.py, MainWindow._convert_image and its helpers) --------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * src, out: n frames HWC uint8 [n][h][w][3] at any byte address.  palette: K x 3 uint8 in device memory, 1 <= K <= 256; duplicate
+ * entries are legal.  index: NULL, or uint8 [n][h][w] that receives the chosen entry of every pixel.  The rules are listed at the top
+ * of csrc/palette.hip and restated in tests/palette_ref.py.
+ * The tone step runs in front of every call here, and alone as adain_tone_u8 (there src may be out):
+ *   grey != 0: Pillow's convert("L").convert("RGB"), L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 in all three channels
+ *     (established against Pillow 12.2.0), then
+ *   lut != NULL: uint8 [3][256] in device memory, channel c becomes lut[c][value].  _adjust_brightness_and_contrast is a function of the
+ *     channel value alone: the host evaluates the reference's float64 expression on 0..255 and uploads the table.
+ * adain_palette_map_u8: one thread per pixel, integer arithmetic, the lowest index among equal distances.
+ *   metric 0 ("rgb", _recolor_image's bytes): minimise sum_c ((p_c - P_kc) & 255)^2 - the reference subtracts uint8 from uint8, so
+ *     every channel difference wraps modulo 256 before the norm
+ *   metric 1 ("nearest", _recolor_image_kd; also what _recolor_image_floyd computes, whose error is read through a view of the pixel
+ *     it has just overwritten and is therefore zero): minimise sum_c (p_c - P_kc)^2
+ * adain_palette_dither_u8: Floyd-Steinberg error diffusion, the loop _recolor_image_floyd spells out with the error copied before the
+ *   pixel is overwritten.  float32, one operation at a time:
+ *     v = ((((p + e[y-1][x-1] * 1/16) + e[y-1][x] * 5/16) + e[y-1][x+1] * 3/16) + e[y][x-1] * 7/16), every product rounded before its
+ *       add, terms outside the frame left out; v is not clamped
+ *     t_k = sqrt((d0 d0 + d1 d1) + d2 d2) correctly rounded, d = P_k - v; the first k with the smallest t_k is chosen (the root, not the
+ *       sum, is compared: it merges neighbouring sums); e = v - P_k; the output pixel is P_k
+ *   One workgroup per frame; a thread per row of a band of ADAIN_PALETTE_DITHER_BAND rows, row y two columns behind row y - 1, one
+ *   barrier per step and w + 2 (rows - 1) steps per band for every thread; no spin-wait, flag or atomic.  A band's last error row
+ *   passes to the next band through the workspace.  A frame's bytes depend on the frame, the palette and the tone step alone - not on
+ *   n, the stream, the device or what the workspace held.
+ * adain_palette_dither_u8_bytes (host only): *workspace_bytes = per frame one error row, w x 3 float.  The output may be NULL.
+ * Refused with ADAIN_EINVAL before anything is launched, adain_last_error naming the argument: a null src, palette or out, K outside
+ * 1..256, a metric other than 0 and 1, h, w or n below 1, n above 65535, a frame beyond 2^31 - 1 bytes, a null workspace, a
+ * workspace_bytes below the query's, a workspace that is not 8-byte aligned.  out must not overlap src partially (map and dither:
+ * not at all).  Nothing is copied to the host and nothing waits; one kernel launch per call. */
+#define ADAIN_PALETTE_DITHER_BAND 1024
+#define ADAIN_PALETTE_METRIC_RGB 0
+#define ADAIN_PALETTE_METRIC_NEAREST 1
+ADAIN_API int adain_palette_map_u8(const uint8_t* src_u8, int n, int h, int w, const uint8_t* palette, int K, int metric, const uint8_t* lut_or_null,
+                                   int grey, uint8_t* out_u8, uint8_t* index_or_null, adain_stream_t stream);
+ADAIN_API int adain_tone_u8(const uint8_t* src_u8, int n, int h, int w, const uint8_t* lut_or_null, int grey, uint8_t* out_u8, adain_stream_t stream);
+ADAIN_API int adain_palette_dither_u8_bytes(int n, int h, int w, size_t* workspace_bytes);
+ADAIN_API int adain_palette_dither_u8(const uint8_t* src_u8, int n, int h, int w, const uint8_t* palette, int K, const uint8_t* lut_or_null, int grey,
+                                      uint8_t* out_u8, uint8_t* index_or_null, void* workspace, size_t workspace_bytes, adain_stream_t stream);
+
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
  * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
