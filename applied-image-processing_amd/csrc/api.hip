@@ -531,6 +531,24 @@ int adain_resize_pil_bilinear_u8(const uint8_t* in, int pixel_bytes, int n, int 
                                          (hipStream_t)stream);
 }
 
+// PIL.Image.resize for all six filters (resample_filters.hip): the table builder is host code, the launcher refuses everything itself
+int adain_pil_resize_taps_bytes(int filter, int in_size, int out_size, int* ksize, size_t* bytes) {
+    return pil_resize_taps_bytes(filter, in_size, out_size, ksize, bytes);
+}
+int adain_pil_resize_taps(int filter, int in_size, int out_size, int32_t* bounds_host, int32_t* taps_host) {
+    return pil_resize_taps(filter, in_size, out_size, bounds_host, taps_host);
+}
+int adain_resize_pil_u8_bytes(int n, int hi, int wi, int ho, int wo, int channels, int filter, int crop_y0, int crop_x0, int crop_h, int crop_w,
+                              size_t* workspace_bytes) {
+    return resize_pil_u8_bytes(n, hi, wi, ho, wo, channels, filter, crop_y0, crop_x0, crop_h, crop_w, workspace_bytes);
+}
+int adain_resize_pil_u8(const uint8_t* src, int pixel_bytes, int n, int hi, int wi, uint8_t* dst, int ho, int wo, int filter, const int32_t* x_bounds,
+                        const int32_t* x_taps, int x_ksize, const int32_t* y_bounds, const int32_t* y_taps, int y_ksize, int crop_y0, int crop_x0, int crop_h,
+                        int crop_w, void* workspace, size_t workspace_bytes, adain_stream_t stream) {
+    return launch_resize_pil_u8(src, pixel_bytes, n, hi, wi, dst, ho, wo, filter, x_bounds, x_taps, x_ksize, y_bounds, y_taps, y_ksize, crop_y0, crop_x0,
+                                crop_h, crop_w, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int adain_jpeg_encode_opt_u8_bytes(int n, int h, int w, int c, int sampling, int optimize, size_t* out_stride, size_t* workspace_bytes) {
     return jpeg_encode_bytes("jpeg_encode_opt_u8", n, h, w, c, sampling, optimize, out_stride, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
 }

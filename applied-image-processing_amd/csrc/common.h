@@ -175,6 +175,15 @@ size_t resize_pil_workspace_bytes(int hi, int wi, int ho, int wo);
 int launch_resize_pil_bilinear_u8(const uint8_t* in, int pixel_bytes, int n, int hi, int wi, uint8_t* out, int ho, int wo, int y0, int x0, int ch,
                                   int cw, void* workspace, size_t ws_bytes, hipStream_t s);
 
+// resample_filters.hip: PIL.Image.resize for all six filters on uint8 L / RGB, bit-exact: tap tables built on the host (pil_taps.h),
+// Pillow's two passes on the device; the launcher refuses everything itself
+int pil_resize_taps_bytes(int filter, int in_size, int out_size, int* ksize, size_t* bytes);
+int pil_resize_taps(int filter, int in_size, int out_size, int32_t* bounds, int32_t* taps);
+int resize_pil_u8_bytes(int n, int hi, int wi, int ho, int wo, int channels, int filter, int y0, int x0, int ch, int cw, size_t* workspace_bytes);
+int launch_resize_pil_u8(const uint8_t* src, int pixel_bytes, int n, int hi, int wi, uint8_t* dst, int ho, int wo, int filter, const int32_t* x_bounds,
+                         const int32_t* x_taps, int x_ksize, const int32_t* y_bounds, const int32_t* y_taps, int y_ksize, int y0, int x0, int ch, int cw,
+                         void* workspace, size_t workspace_bytes, hipStream_t s);
+
 // flow.hip: Farneback dense optical flow (OpenCV's calcOpticalFlowFarneback, flags 0) and the video callers' frame preparation
 int launch_flow_gray_u8(const uint8_t* rgb, int n, int hi, int wi, uint8_t* gray, int ho, int wo, hipStream_t s);
 int farneback_levels(int h, int w, double pyr_scale, int levels, int* out_levels, int* sizes_wh, int* ksizes, double* sigmas);

@@ -203,6 +203,11 @@ class AdaINEngine:
         """cv2.resize(frame, dsize, interpolation=cv2.INTER_AREA) per frame (video/utils.py:352-353); dsize = (width, height)."""
         return rt.resize_area_u8(frames_u8, dsize)
 
+    def resize_pil_u8(self, frames_u8, size, resample=rt.PIL_BILINEAR, crop=None, out=None):
+        """``PIL.Image.resize(size, resample)`` per uint8 frame for any of Pillow's six filters, bit for bit (``runtime.resize_pil_u8``:
+        tap tables from the host, two passes on the device); size = (width, height)."""
+        return rt.resize_pil_u8(frames_u8, size, resample, crop, out)
+
     def warp_blend_u8(self, cur, prev, flow, alpha=0.7):
         """One step of the video recurrence: blend(cur, warp(prev, flow), alpha) on uint8 HWC frames (video/utils.py:89-105, :223-229)."""
         return rt.warp_blend_u8(cur, prev, flow, alpha)

@@ -225,7 +225,8 @@ def color_transfer_foreground_device(foreground_img, background_img, device=None
 
 def combine_localized_device(content_np, stylized_np, background_mask, device=None, return_record=False):
     """``combine_localized`` on the device, the masked images never materialised: content uint8 [H,W,3], stylised uint8 (nearest-resized
-    to the mask on the host when sizes differ, :223-230), ``background_mask`` [H,W] holding 0 and 1 only."""
+    to the mask when sizes differ, :223-230: a GPU tensor on its device by ``runtime.resize_pil_u8``, anything else by Pillow on the host),
+    ``background_mask`` [H,W] holding 0 and 1 only."""
     import torch
 
     m = background_mask
@@ -234,11 +235,14 @@ def combine_localized_device(content_np, stylized_np, background_mask, device=No
         raise ValueError(f"background_mask must be an integer [H,W] array of 0 and 1, got {host_mask.dtype} {host_mask.shape}")
     _u8_image(content_np, "content_np", host_mask.shape + (3,))
     _u8_image(stylized_np, "stylized_np")
-    if tuple(stylized_np.shape[:2]) != host_mask.shape:
-        sty = stylized_np.cpu().numpy() if isinstance(stylized_np, torch.Tensor) else stylized_np
-        stylized_np = np.array(Image.fromarray(sty).resize((host_mask.shape[1], host_mask.shape[0]), Image.NEAREST))
     from . import runtime as rt
 
+    if tuple(stylized_np.shape[:2]) != host_mask.shape:
+        if isinstance(stylized_np, torch.Tensor) and stylized_np.is_cuda:
+            stylized_np = rt.resize_pil_u8(stylized_np.contiguous()[None], (host_mask.shape[1], host_mask.shape[0]), rt.PIL_NEAREST)[0]
+        else:
+            sty = stylized_np.cpu().numpy() if isinstance(stylized_np, torch.Tensor) else stylized_np
+            stylized_np = np.array(Image.fromarray(sty).resize((host_mask.shape[1], host_mask.shape[0]), Image.NEAREST))
     dev = _device_of(device, content_np, stylized_np)
     mask = m.to(dev, torch.uint8) if isinstance(m, torch.Tensor) else _to_device(host_mask.astype(np.uint8), dev)
     out, record = rt.localized_combine_u8(_to_device(content_np, dev), _to_device(stylized_np, dev), mask.contiguous())

@@ -26,6 +26,7 @@ import numpy as np
 METHODS = ("rgb", "kd-tree", "floyd-steinberg", "floyd-steinberg-diffused")
 _METRIC = {"rgb": "rgb", "kd-tree": "nearest", "floyd-steinberg": "nearest"}
 BILINEAR = 2          # PIL.Image.BILINEAR
+RESAMPLING = {"NEAREST": 0, "BOX": 4, "BILINEAR": 2, "HAMMING": 5, "BICUBIC": 3, "LANCZOS": 1}          # PIL.Image.Resampling, the page's cycle
 
 
 def _method(method):
@@ -239,9 +240,9 @@ def convert_image(image, downsampling_factor=1, resampling_mode=BILINEAR, graysc
     (Pillow's convert("L").convert("RGB")) when ``grayscale``; brightness / contrast when either is non-zero; recolour when ``colors``
     are given.  Grey, tone and recolouring are one kernel launch.
 
-    ``BILINEAR`` downsampling runs on the device through the Pillow-exact resize (``runtime.resize_pil_bilinear_u8``).  Every other
-    ``resampling_mode`` is resized by Pillow on the host and the result uploaded; so is everything on the host route.
-    Input kinds and ``device`` as in ``recolor``."""
+    Every ``resampling_mode`` of ``Image.Resampling`` (the page cycles through all six) is downsampled on the device through the
+    Pillow-exact resizes: ``BILINEAR`` by ``runtime.resize_pil_bilinear_u8``, the others by ``runtime.resize_pil_u8``; a factor beyond the
+    device calls' limit of 256 raises.  On the host route Pillow resizes.  Input kinds and ``device`` as in ``recolor``."""
     method = _method(method)
     pal = _palette(colors)
     kind, frames = _open(image)
@@ -251,11 +252,8 @@ def convert_image(image, downsampling_factor=1, resampling_mode=BILINEAR, graysc
     if f > 1:
         h, w = frames.shape[-3], frames.shape[-2]
         size = (w // f, h // f)
-        if dev is not None and int(resampling_mode) == BILINEAR:
-            from . import runtime as rt
-            x = _tensor(frames)
-            x = x.to(dev)
-            frames = rt.resize_pil_bilinear_u8(x.reshape((-1,) + tuple(x.shape[-3:])), size).reshape(tuple(x.shape[:-3]) + (size[1], size[0], 3))
+        if dev is not None:
+            frames = _downsample_device(frames, size, int(resampling_mode), dev)
         else:
             from PIL import Image
             a = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
@@ -264,15 +262,29 @@ def convert_image(image, downsampling_factor=1, resampling_mode=BILINEAR, graysc
     return _close(kind, _run(frames, pal, method, tone_lut(brightness, contrast), bool(grayscale), dev))
 
 
-def frames_post(colors, method="rgb", grayscale=False, brightness=0, contrast=0):
+def _downsample_device(frames, size, mode, dev):
+    """``_downsample_image`` on ``dev``: frames [..., h, w, 3] (NumPy or tensor) -> a tensor [..., size[1], size[0], 3] there."""
+    from . import runtime as rt
+    x = _tensor(frames)
+    x = x.to(dev)
+    flat = x.reshape((-1,) + tuple(x.shape[-3:]))
+    small = rt.resize_pil_bilinear_u8(flat, size) if mode == BILINEAR else rt.resize_pil_u8(flat, size, mode)
+    return small.reshape(tuple(x.shape[:-3]) + (size[1], size[0], 3))
+
+
+def frames_post(colors, method="rgb", grayscale=False, brightness=0, contrast=0, downsampling_factor=1, resampling_mode=BILINEAR):
     """An ``f(u8_block) -> u8_block`` for ``stylize_frames_sharded(post=...)``: every stylised sub-batch [n,h,w,3] leaves its rank already
-    grey / toned / recoloured, on the device, and can go straight to the device PNG or JPEG writer."""
+    downsampled (``downsampling_factor`` above 1: to (w // f, h // f) with ``resampling_mode``, as ``convert_image`` does; the default
+    keeps the frame's size) / grey / toned / recoloured, on the device, and can go straight to the device PNG or JPEG writer."""
     method = _method(method)
     pal = _palette(colors)
     lut = tone_lut(brightness, contrast)
     grey = bool(grayscale)
+    f, mode = int(downsampling_factor), int(resampling_mode)
 
     def post(u8):
+        if f > 1:
+            u8 = _downsample_device(u8, (u8.shape[-2] // f, u8.shape[-3] // f), mode, u8.device)
         return _run(u8, pal, method, lut, grey, u8.device)
 
     return post
@@ -290,6 +302,8 @@ def main(argv=None):
     ap.add_argument("--palettes", help="a JSON file in the lospec list's format")
     ap.add_argument("--method", default="rgb", choices=METHODS + ("LAB",))
     ap.add_argument("--factor", type=int, default=1)
+    ap.add_argument("--resampling", default="BILINEAR", type=str.upper, choices=tuple(RESAMPLING), metavar="NAME",
+                    help="the downsampling filter of --factor, a member of PIL.Image.Resampling: " + ", ".join(RESAMPLING) + " (default BILINEAR)")
     ap.add_argument("--grayscale", action="store_true")
     ap.add_argument("--brightness", type=float, default=0)
     ap.add_argument("--contrast", type=float, default=0)
@@ -303,7 +317,7 @@ def main(argv=None):
         if a.palette not in palettes:
             ap.error(f"no palette {a.palette!r} in {a.palettes}")
         colors = palettes[a.palette]
-    out = convert_image(Image.open(a.input).convert("RGB"), a.factor, BILINEAR, a.grayscale, a.brightness, a.contrast, colors, a.method)
+    out = convert_image(Image.open(a.input).convert("RGB"), a.factor, RESAMPLING[a.resampling], a.grayscale, a.brightness, a.contrast, colors, a.method)
     out.save(a.output)
     return 0
 

@@ -5,6 +5,7 @@ compute call below hands raw device pointers (``tensor.data_ptr()``) and the cur
 hand-written gfx950 kernel.  There is NO fallback: if the shared library is missing or the tensors
 are not on a GPU, these functions raise.
 """
+import collections
 import contextlib
 import ctypes
 import os
@@ -84,6 +85,11 @@ SIGNATURES = {
                              _c_void_p]),
     "adain_resize_pil_bilinear_u8_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "adain_resize_pil_bilinear_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p, _c_size_t, _c_void_p]),
+    "adain_pil_resize_taps_bytes": (_c_int, [_c_int] * 3 + [ctypes.POINTER(_c_int), ctypes.POINTER(_c_size_t)]),
+    "adain_pil_resize_taps": (_c_int, [_c_int] * 3 + [_c_void_p, _c_void_p]),
+    "adain_resize_pil_u8_bytes": (_c_int, [_c_int] * 11 + [ctypes.POINTER(_c_size_t)]),
+    "adain_resize_pil_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,
+                                     _c_void_p, _c_int] + [_c_int] * 4 + [_c_void_p, _c_size_t, _c_void_p]),
     "adain_stylize_u8_workspace_bytes": (_c_size_t, [_c_int] * 9),
     "adain_stylize_u8_out_size": (None, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
     "adain_stylize_u8": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_float, _c_float, _PP,
@@ -827,6 +833,106 @@ def resize_pil_bilinear_u8(frames, size, crop=None, out=None):
     # fetch pool) on one stream must not interleave
     with _pil_lock, scratch(x.device, "pil", "adain_resize_pil_bilinear_u8_workspace_bytes", hi, wi, ho, wo) as ws:
         _launch("adain_resize_pil_bilinear_u8", x.data_ptr(), pix, n, hi, wi, out.data_ptr(), ho, wo, y0, x0, ch, cw, ws.data_ptr(), ws.numel())
+    return out
+
+
+# --- PIL.Image.resize for all six filters (adain_resize_pil_u8) ---------------------------------------------------------------------------
+PIL_NEAREST, PIL_LANCZOS, PIL_BILINEAR, PIL_BICUBIC, PIL_BOX, PIL_HAMMING = 0, 1, 2, 3, 4, 5          # PIL.Image.Resampling
+PIL_FILTERS = {"NEAREST": PIL_NEAREST, "BOX": PIL_BOX, "BILINEAR": PIL_BILINEAR, "HAMMING": PIL_HAMMING, "BICUBIC": PIL_BICUBIC, "LANCZOS": PIL_LANCZOS}
+PIL_MAX_SHRINK = 256          # in / out per axis beyond which adain_resize_pil_u8 refuses
+PIL_TABLES_KEPT = 32          # axes whose device tables are kept, least recently used first out
+PIL_TABLE_STATS = {"hits": 0, "uploads": 0}          # per axis of a call: found in the cache / built on the host and uploaded
+_pil_tables = collections.OrderedDict()          # (device index, filter, in, out) -> (ksize, int32 device tensor: bounds, then taps, its stream)
+
+
+def pil_filter(resample):
+    """Pillow's integer code of ``resample``: an ``Image.Resampling`` member, its code, or its name."""
+    code = PIL_FILTERS.get(resample.upper()) if isinstance(resample, str) else int(resample)
+    if code not in PIL_FILTERS.values():
+        raise AdainHipError(f"resize_pil_u8: unknown resampling filter {resample!r} (one of {', '.join(PIL_FILTERS)})")
+    return code
+
+
+def _pil_taps_host(code, in_size, out_size):
+    """-> (ksize, one int32 array: bounds [out,2], then taps [out,ksize]) as adain_pil_resize_taps builds them.  Host only."""
+    import numpy as np
+
+    ksize, nbytes = _c_int(), _c_size_t()
+    rc = lib().adain_pil_resize_taps_bytes(code, int(in_size), int(out_size), ctypes.byref(ksize), ctypes.byref(nbytes))
+    if rc != 0:
+        raise _failure("adain_pil_resize_taps_bytes", rc)
+    table = np.empty(nbytes.value // 4, np.int32)
+    rc = lib().adain_pil_resize_taps(code, int(in_size), int(out_size), table.ctypes.data, table.ctypes.data + 8 * out_size if ksize.value else None)
+    if rc != 0:
+        raise _failure("adain_pil_resize_taps", rc)
+    return ksize.value, table
+
+
+def pil_resize_taps(resample, in_size, out_size):
+    """The tables of one axis as ``adain_pil_resize_taps`` builds them on the host (no device needed) ->
+    (ksize, bounds int32 [out,2], taps int32 [out,ksize]) as NumPy arrays."""
+    ksize, table = _pil_taps_host(pil_filter(resample), in_size, out_size)
+    return ksize, table[:2 * out_size].reshape(out_size, 2), table[2 * out_size:].reshape(out_size, ksize)
+
+
+def _pil_axis_tables(device, code, in_size, out_size, stream):
+    """(ksize, device table) of one axis from the cache, built and uploaded when it is not there.  Called under ``_pil_lock`` with
+    ``device`` current; ``stream``: the calling stream's handle."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), code, in_size, out_size)
+    hit = _pil_tables.get(key)
+    if hit is not None:
+        _pil_tables.move_to_end(key)
+        PIL_TABLE_STATS["hits"] += 1
+        if hit[2] != stream:          # it may leave the cache while this stream still reads it
+            hit[1].record_stream(torch.cuda.current_stream(device))
+        return hit[:2]
+    ksize, host = _pil_taps_host(code, in_size, out_size)
+    # a copy from pageable memory has arrived when .to() returns: any stream may read the table afterwards
+    table = torch.from_numpy(host).to(device)
+    PIL_TABLE_STATS["uploads"] += 1
+    _pil_tables[key] = (ksize, table, stream)
+    while len(_pil_tables) > PIL_TABLES_KEPT:
+        _pil_tables.popitem(last=False)
+    return ksize, table
+
+
+def free_pil_tables():
+    with _pil_lock:
+        _pil_tables.clear()
+
+
+def resize_pil_u8(frames, size, resample=PIL_BILINEAR, crop=None, out=None):
+    """``PIL.Image.resize(size, resample)`` of uint8 images on the device for Pillow's six filters (NEAREST, BOX, BILINEAR, HAMMING,
+    BICUBIC, LANCZOS: ``Image.Resampling`` members, their codes or names), bit for bit; no ``box=``, no ``reducing_gap``.
+    frames: uint8 [n,h,w,3] (packed RGB), [n,h,w,4] (Pillow's RGBX storage), [n,h,w,1] or [n,h,w] (L); ``size`` = (width, height) as PIL
+    takes it; ``crop`` = (top, left, height, width) window of the result, default all of it.  Returns packed RGB [n,ch,cw,3], or L in
+    the source's rank.  The tap tables come from the host (``pil_resize_taps``) and stay on the device in a small LRU cache per
+    (device, filter, in, out): a clip's second frame costs the two launches and no upload.  An unchanged size gives a copy."""
+    x = device_tensor(frames, "frames", torch.uint8)
+    flat = x.dim() == 3
+    if flat:
+        x = x.unsqueeze(3)
+    if x.dim() != 4 or x.shape[3] not in (1, 3, 4):
+        raise AdainHipError(f"resize_pil_u8: expected uint8 [n,h,w,3|4|1] or [n,h,w], got {tuple(frames.shape)}")
+    code = pil_filter(resample)
+    n, hi, wi, pix = x.shape
+    c = 1 if pix == 1 else 3
+    wo, ho = int(size[0]), int(size[1])
+    y0, x0, ch, cw = (0, 0, ho, wo) if crop is None else [int(v) for v in crop]
+    shape = (n, max(ch, 0), max(cw, 0)) + (() if flat else (c,))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    else:
+        check_buffer(out, "resize_pil_u8: out", torch.uint8, x.device, shape=shape, distinct=(x,))
+    # the intermediate lives in the stream's workspace between the call's two launches: calls from several threads on one stream
+    # must not interleave; the same lock guards the table cache
+    with _pil_lock, scratch(x.device, "pil_filters", lambda *d: _size_query("adain_resize_pil_u8_bytes", *d)[0], n, hi, wi, ho, wo, pix, code, y0, x0, ch,
+                            cw) as ws:
+        stream = _stream()
+        kx, tx = _pil_axis_tables(x.device, code, wi, wo, stream)
+        ky, ty = _pil_axis_tables(x.device, code, hi, ho, stream)
+        _launch("adain_resize_pil_u8", x.data_ptr(), pix, n, hi, wi, out.data_ptr(), ho, wo, code, tx.data_ptr(), tx.data_ptr() + 8 * wo, kx, ty.data_ptr(),
+                ty.data_ptr() + 8 * ho, ky, y0, x0, ch, cw, ws.data_ptr(), ws.numel())
     return out
 
 

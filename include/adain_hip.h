@@ -373,6 +373,51 @@ ADAIN_API int adain_resize_pil_bilinear_u8(const uint8_t* in_u8, int pixel_bytes
                                  int crop_y0, int crop_x0, int crop_h, int crop_w, void* workspace, size_t workspace_bytes,
                                  adain_stream_t stream);
 
+/* ---- PIL.Image.resize for all six filters (the palette page's _downsample_image, gui/second_page.py; the NEAREST resize of the
+ * localized composite; the LANCZOS / BICUBIC resizes of the loaders) -----------------------------------------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * PIL.Image.Image.resize((wo, ho), resample) of uint8 L and RGB images, bit for bit, without box= and without reducing_gap.
+ * `filter` is Pillow's integer code: 0 NEAREST, 1 LANCZOS, 2 BILINEAR, 3 BICUBIC, 4 BOX, 5 HAMMING.
+ *
+ * The five convolution filters (libImaging/Resample.c) share one tap rule, all in double:
+ *     BOX      support 0.5  f(x) = 1 for -0.5 < x <= 0.5, else 0
+ *     BILINEAR support 1    f(x) = 1 - |x| for |x| < 1, else 0
+ *     HAMMING  support 1    x = |x|; 1 at 0; 0 for x >= 1; else with x *= M_PI: sin(x) / x * (0.54f + 0.46f * cos(x)) - the two constants
+ *                           are floats widened to double, as Resample.c writes them
+ *     BICUBIC  support 2    a = -0.5, x = |x|; ((a + 2) x - (a + 3)) x x + 1 for x < 1; (((x - 5) x + 8) x - 4) a for x < 2; else 0
+ *     LANCZOS  support 3    sinc(x) sinc(x / 3) for -3 <= x < 3, else 0; sinc(0) = 1, else x *= M_PI, sin(x) / x
+ *   scale = in / out, filterscale = max(scale, 1), support = filter support * filterscale, ksize = (int)ceil(support) * 2 + 1; per
+ *   output index xx: center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0), count = min((int)(center + support +
+ *   0.5), in) - xmin, w[x] = f((x + xmin - center + 0.5) * (1 / filterscale)), summed in order and each divided by the sum when it is
+ *   not zero, then (int)(+-0.5 + w * 2^22) with the sign of w.  A horizontal pass writes a uint8 intermediate,
+ *   clip8((2^21 + sum in * k) >> 22), a vertical pass over it applies the same expression.  A pass whose axis keeps its size is not
+ *   run (Pillow skips it too), and only the intermediate rows and columns the crop window needs are computed.
+ * NEAREST is Geometry.c's ImagingScaleAffine: per axis s = in / out, o = s * 0.5, and for each output index in order the source index
+ *   is o < 0 ? -1 : (int)o, then o += s (a running sum); an index outside [0, in) leaves the pixel 0.
+ *
+ * The tables are built on the HOST - HAMMING and LANCZOS go through the C library's sin and cos, the functions Pillow calls - by
+ * adain_pil_resize_taps, which needs no device.  Per axis: bounds_host int32 [out_size][2] (first source index, tap count) and
+ * taps_host int32 [out_size][ksize] (zero behind the count); `bytes` is the size of both together.  NEAREST: ksize 0, bounds holds
+ * the source index and 1 (0 when the index is outside the source), taps_host may be NULL.
+ *
+ * adain_resize_pil_u8 takes both axes' tables as DEVICE pointers (x: wi -> wo, y: hi -> ho).  src: [n][hi][wi][pixel_bytes] with
+ * pixel_bytes 1 (L), 3 (packed RGB) or 4 (Pillow's RGBX storage, 4th byte ignored); dst: the window (crop_y0, crop_x0, crop_h,
+ * crop_w) of the ho x wo result, [n][crop_h][crop_w][1] for pixel_bytes 1 and packed RGB [n][crop_h][crop_w][3] otherwise.  The
+ * workspace holds the uint8 intermediate (0 bytes, and the pointer unused, when at most one pass runs); any alignment.  ho == hi and
+ * wo == wi copies the window.
+ * Refused (ADAIN_EINVAL, with a message, before any launch): an unknown filter; pixel_bytes / channels other than 1, 3, 4; n < 1; a
+ * side outside [1, 2^24); a shrink factor above 256 on either axis (in > 256 * out: bounds LANCZOS at 1537 taps per axis); a window
+ * outside the result; x_ksize / y_ksize other than the sizes' ksize; null pointers; a workspace too small; a result or workspace that
+ * overlaps the source, the tables or each other; more than 65535 images or 262140 rows. */
+ADAIN_API int adain_pil_resize_taps_bytes(int filter, int in_size, int out_size, int* ksize, size_t* bytes);
+ADAIN_API int adain_pil_resize_taps(int filter, int in_size, int out_size, int32_t* bounds_host, int32_t* taps_host);
+ADAIN_API int adain_resize_pil_u8_bytes(int n, int hi, int wi, int ho, int wo, int channels, int filter, int crop_y0, int crop_x0, int crop_h,
+                                        int crop_w, size_t* workspace_bytes);
+ADAIN_API int adain_resize_pil_u8(const uint8_t* src_u8, int pixel_bytes, int n, int hi, int wi, uint8_t* dst_u8, int ho, int wo, int filter,
+                                  const int32_t* x_bounds, const int32_t* x_taps, int x_ksize, const int32_t* y_bounds, const int32_t* y_taps,
+                                  int y_ksize, int crop_y0, int crop_x0, int crop_h, int crop_w, void* workspace, size_t workspace_bytes,
+                                  adain_stream_t stream);
+
 /* ---- one sub-batch of the reference's batch callers in ONE call ---------------------------------------------------------------
  * What adain_inference does between `Image.open` and `save_image` for n decoded frames of one size and one style whose
  * statistics are already known (test.py:203-244 per frame; the callers loop over frames with the same style,
