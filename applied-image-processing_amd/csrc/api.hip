@@ -615,6 +615,15 @@ int adain_palette_dither_u8(const uint8_t* src, int n, int h, int w, const uint8
     return launch_palette_dither_u8(src, n, h, w, palette, K, lut, grey, out, index, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// animated GIF clips (Style_3DGS/render.py:29-33; video/utils.py:374-392 writes a cv2 video instead): the launcher refuses everything itself
+int adain_gif_encode_u8_bytes(int n, int h, int w, int K, size_t* out_stride, size_t* workspace_bytes) {
+    return gif_encode_bytes(n, h, w, K, out_stride, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_gif_encode_u8(const uint8_t* index, int n, int h, int w, int K, int delay_cs, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
+                        size_t workspace_bytes, adain_stream_t stream) {
+    return launch_gif_encode_u8(index, n, h, w, K, delay_cs, out, out_stride, lengths, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
 }

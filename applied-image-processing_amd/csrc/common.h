@@ -247,6 +247,12 @@ int palette_dither_bytes(int n, int h, int w, size_t* workspace_bytes);
 int launch_palette_dither_u8(const uint8_t* src, int n, int h, int w, const uint8_t* palette, int K, const uint8_t* lut, int grey, uint8_t* out, uint8_t* index,
                              void* workspace, size_t workspace_bytes, hipStream_t s);
 
+// gif.hip: an animated GIF's frame records from palette index planes (the rules: top of gif.hip, tests/gif_ref.py); the launcher refuses
+// everything itself
+int gif_encode_bytes(int n, int h, int w, int K, size_t* out_stride, size_t* workspace_bytes);
+int launch_gif_encode_u8(const uint8_t* index, int n, int h, int w, int K, int delay_cs, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
+                         size_t workspace_bytes, hipStream_t s);
+
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);
 int launch_coral(const void* style, int style_is_u8, int style_n, int hs, int ws, const void* content, int content_is_u8, int n, int hc, int wc,

@@ -1,4 +1,5 @@
-// Device-side helpers shared by the convolution kernels (conv_edge.hip, conv_wino4.hip) and the colour kernels (colour.hip, coral.hip).
+// Device-side helpers shared by the convolution kernels (conv_edge.hip, conv_wino4.hip) and the colour kernels (colour.hip, coral.hip);
+// the workgroup scan and the bit writer of the file encoders (png.hip, gif.hip).
 #pragma once
 #include "common.h"
 
@@ -70,5 +71,46 @@ __device__ inline void jacobi3(double a[3][3], double v[3][3]) {
             }
     }
 }
+
+// exclusive prefix of v over the workgroup's THREADS threads; *total: the sum; part: THREADS / 64 entries of LDS (png.hip, gif.hip)
+template <int THREADS, class V>
+__device__ __forceinline__ V wg_exclusive(V v, V* part, V* total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    V inc = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const V up = __shfl_up(inc, d);
+        if (lane >= d) inc += up;
+    }
+    __syncthreads();
+    if (lane == 63) part[wv] = inc;
+    __syncthreads();
+    V before = 0, all = 0;
+    for (int k = 0; k < THREADS / 64; ++k) {
+        if (k < wv) before += part[k];
+        all += part[k];
+    }
+    *total = all;
+    return before + inc - v;
+}
+
+// LSB-first bits into a zeroed stream of 32-bit words, shared between writers by atomicOr (png.hip, gif.hip)
+struct BitWriter {
+    uint32_t* words;
+    size_t at;              // word being filled
+    uint64_t acc;
+    int have;               // bits of acc that belong to words[at] and the one behind it
+    __device__ BitWriter(uint32_t* stream, uint64_t bit) : words(stream), at((size_t)(bit >> 5)), acc(0), have((int)(bit & 31)) {}
+    __device__ void put(uint32_t value, int count) {          // count <= 32
+        acc |= (uint64_t)value << have;
+        have += count;
+        if (have >= 32) {
+            atomicOr(words + at, (uint32_t)acc);
+            acc >>= 32, have -= 32, ++at;
+        }
+    }
+    __device__ void flush() {
+        if (have > 0 && acc) atomicOr(words + at, (uint32_t)acc);
+    }
+};
 
 }  // namespace adain

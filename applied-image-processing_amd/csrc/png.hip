@@ -26,7 +26,7 @@
 //   emit    : a workgroup per block - header, tokens, end of block (and the Adler-32 behind the last) by atomicOr, LSB first
 //   scatter : the zlib stream behind the file's first 41 bytes, and the CRC-32 of 256-byte pieces shifted to the stream's end
 //   finish  : a thread per frame - signature, IHDR, IDAT's length, type and CRC, IEND, lengths[i]
-#include "common.h"
+#include "device_utils.h"
 
 namespace adain {
 namespace {
@@ -107,47 +107,6 @@ __device__ __forceinline__ V wg_sum(V v, V* part) {
     for (int k = 0; k < THREADS / 64; ++k) s += part[k];
     return s;
 }
-
-// exclusive prefix of v over the workgroup's threads; *total: the sum
-template <class V>
-__device__ __forceinline__ V wg_exclusive(V v, V* part, V* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    V inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const V up = __shfl_up(inc, d);
-        if (lane >= d) inc += up;
-    }
-    __syncthreads();
-    if (lane == 63) part[wv] = inc;
-    __syncthreads();
-    V before = 0, all = 0;
-    for (int k = 0; k < THREADS / 64; ++k) {
-        if (k < wv) before += part[k];
-        all += part[k];
-    }
-    *total = all;
-    return before + inc - v;
-}
-
-// LSB-first bits into a zeroed stream of 32-bit words
-struct BitWriter {
-    uint32_t* words;
-    size_t at;              // word being filled
-    uint64_t acc;
-    int have;               // bits of acc that belong to words[at] and the one behind it
-    __device__ BitWriter(uint32_t* stream, uint64_t bit) : words(stream), at((size_t)(bit >> 5)), acc(0), have((int)(bit & 31)) {}
-    __device__ void put(uint32_t value, int count) {          // count <= 32
-        acc |= (uint64_t)value << have;
-        have += count;
-        if (have >= 32) {
-            atomicOr(words + at, (uint32_t)acc);
-            acc >>= 32, have -= 32, ++at;
-        }
-    }
-    __device__ void flush() {
-        if (have > 0 && acc) atomicOr(words + at, (uint32_t)acc);
-    }
-};
 
 __device__ __forceinline__ int length_symbol(int len, int* extra_bits, int* extra) {         // len 3..258 -> symbol - 257
     if (len == MAX_MATCH) { *extra_bits = 0, *extra = 0; return 28; }
@@ -453,7 +412,7 @@ __global__ __launch_bounds__(THREADS) void png_scan_kernel(const uint32_t* __res
     const size_t f = blockIdx.x, per = (nblk + THREADS - 1) / THREADS, i0 = min(nblk, threadIdx.x * per), i1 = min(nblk, i0 + per);
     unsigned long long mine = 0, all;
     for (size_t i = i0; i < i1; ++i) mine += bbits[f * nblk + i];
-    unsigned long long at = 16 + wg_exclusive(mine, part, &all);
+    unsigned long long at = 16 + wg_exclusive<THREADS>(mine, part, &all);
     for (size_t i = i0; i < i1; ++i) boff[f * nblk + i] = at, at += bbits[f * nblk + i];
     if (threadIdx.x == 0) total[f] = 16 + all;
 }
@@ -497,7 +456,7 @@ __global__ __launch_bounds__(THREADS) void png_emit_kernel(const uint8_t* __rest
         bits += d_len[dist_symbol(dists.d[k >> 8], &eb, &ev)] + eb;
     }
     uint32_t all;
-    const uint32_t before = wg_exclusive(bits, part, &all);
+    const uint32_t before = wg_exclusive<THREADS>(bits, part, &all);
     const uint64_t base = boff[f * nblk + blk], body = base + tab.hdr_bits;
     {
         BitWriter out(s, body + before);

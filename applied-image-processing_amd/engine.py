@@ -223,6 +223,12 @@ class AdaINEngine:
         files any reader decodes to the frames' pixels, not Pillow's bytes) -> a list of n ``bytes``; only the files cross to the host."""
         return rt.png_files(*rt.png_encode_u8(frames_u8, filter))
 
+    def gif_encode_u8(self, index_u8, K, delay_cs):
+        """Palette index planes uint8 [n,h,w] on the device, every index below ``K`` -> the frames' GIF records (adain_gif_encode_u8;
+        ``runtime.gif_encode_u8``) as (records, lengths) on the device; ``gif_file.assemble`` makes the file of them and only the records
+        cross to the host."""
+        return rt.gif_encode_u8(index_u8, K, delay_cs)
+
     def pixelize_u8(self, frames_u8, colors, method="rgb", grayscale=False, brightness=0, contrast=0):
         """Finished uint8 frames [n,h,w,3] (or [h,w,3]) on the device -> the palette page's grey / brightness / contrast / recolouring of
         them (``pixelize.frames_post``: adain_palette_map_u8, or adain_palette_dither_u8 for "floyd-steinberg-diffused" with its error rows in

@@ -113,6 +113,8 @@ SIGNATURES = {
     "adain_tone_u8": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_int, _c_void_p, _c_void_p]),
     "adain_palette_dither_u8_bytes": (_c_int, [_c_int] * 3 + [ctypes.POINTER(_c_size_t)]),
     "adain_palette_dither_u8": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_gif_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
+    "adain_gif_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_progressive_u8_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
@@ -1318,6 +1320,39 @@ def palette_dither_u8(u8, palette, lut=None, grey=False, index=False):
                 ws.data_ptr(), ws.numel())
     out = out.reshape(u8.shape)
     return (out, idx.reshape(u8.shape[:-1])) if index else out
+
+
+# --- animated GIF frame records (adain_gif_encode_u8) -----------------------------------------------------------------------------------
+GIF_SEGMENT = 2048          # ADAIN_GIF_SEGMENT: the pixels coded from one CLEAR to the next
+
+
+def gif_encode_sizes(n, h, w, K):
+    """(out_stride, workspace_bytes) of adain_gif_encode_u8_bytes: the largest record a frame of this shape and palette size can have and
+    the scratch of an n-frame call.  Host only.  AdainHipError for a refused shape."""
+    return tuple(_size_query("adain_gif_encode_u8_bytes", n, h, w, K, results=2))
+
+
+def gif_encode_u8(index, K, delay_cs):
+    """Palette index planes uint8 [n,h,w] (or one, [h,w]) on the device, every index below ``K`` -> (records uint8 [n, stride], lengths
+    int32 [n]), both on the device: row i starts with frame i's GIF record - graphic control extension with ``delay_cs`` centiseconds,
+    image descriptor, LZW data - ``lengths[i]`` bytes; the rest of the row is not written.  ``gif_file.assemble`` makes the file.  The
+    bytes follow the rules of csrc/gif.hip (tests/gif_ref.py), not Pillow's, and depend on the indices, ``K`` and ``delay_cs`` alone.
+    A frame with an index >= K has length 0 (``gif_file.assemble`` raises).  Nothing is copied to the host and nothing waits."""
+    what = "gif_encode_u8"
+    for name, v, lo, hi in (("K", K, 1, 256), ("delay_cs", delay_cs, 0, 65535)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise AdainHipError(f"{what}: {name} must be an int in {lo}..{hi}, got {v!r}")
+    x = device_tensor(index, what + ": index", torch.uint8)
+    if x.dim() == 2:
+        x = x[None]
+    if x.dim() != 3 or x.numel() == 0:
+        raise AdainHipError(f"{what}: expected uint8 [n,h,w] or [h,w], got {tuple(index.shape)}")
+    n, h, w = x.shape
+
+    def launch(out, stride, lengths, ws):
+        _launch("adain_gif_encode_u8", x.data_ptr(), n, h, w, K, delay_cs, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
+
+    return _encode_files(x, "gif", lambda: gif_encode_sizes(n, h, w, K), launch)
 
 
 # --- .png input files (adain_png_decode_u8) -------------------------------------------------------------------------------------------

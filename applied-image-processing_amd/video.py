@@ -39,6 +39,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import gif_file
 from . import jobs
 from . import runtime as rt
 from .AdaIN import test as adain_test
@@ -173,8 +174,41 @@ def _jpeg_roundtrip(u8):
     return out
 
 
+def _gif_request(path, fps, palette, method):
+    """The GIF a clip also writes, settled before anything runs: None without a path."""
+    if path is None:
+        return None
+    palette = gif_file.WEB if palette is None else palette
+    gif_file.header((1, 1), palette)          # refuses a bad palette now
+    gif_file.delay_of(fps)
+    return {"path": str(path), "fps": fps, "palette": palette, "method": gif_file.default_method(palette) if method is None else method}
+
+
+def frames_to_gif(image_folder, output_gif, fps=20, palette=gif_file.WEB, method=None, routes=None):
+    """The frames of ``image_folder`` (sorted by name, one size) as one animated GIF: the counterpart of the reference's ``frames_to_video``
+    (video/utils.py:374-392, cv2's VideoWriter) in the container its results are shown in (Style_3DGS/render.py:29-33).  ``palette``,
+    ``method``: ``gif_file.write_gif``'s.  With a GPU the frames are read through ``routes`` (an ``rt.OutputRoutes``: decoded on the
+    device where it says so, PIL otherwise), recoloured and coded there; without one PIL reads and writes.  Returns ``output_gif``."""
+    names = _frame_files(image_folder)
+    if not names:
+        raise ValueError(f"frames_to_gif: no frames in {image_folder}")
+    routes = rt.OutputRoutes() if routes is None else routes
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    frames = []
+    for name in names:
+        path = os.path.join(image_folder, name)
+        rgb = routes.read_rgb(path, dev) if dev is not None else None
+        if rgb is None:
+            rgb = torch.from_numpy(np.array(Image.open(path).convert("RGB")))
+            rgb = rgb.to(dev) if dev is not None else rgb
+        if frames and rgb.shape != frames[0].shape:
+            raise ValueError(f"frames_to_gif: {name} is {tuple(rgb.shape[:2])}, the first frame {tuple(frames[0].shape[:2])}")
+        frames.append(rgb)
+    return gif_file.write_gif(torch.stack(frames), output_gif, palette, fps, method)
+
+
 def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence, engine,
-              vgg_str, decoder_str, depth_maps, group, preserve_color, crossfade_frames, intermediate_jpeg, outputs):
+              vgg_str, decoder_str, depth_maps, group, preserve_color, crossfade_frames, intermediate_jpeg, outputs, gif=None):
     from . import sharding as sh
     from .engine import AdaINEngine
 
@@ -257,6 +291,7 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
         # the frame-to-frame recurrence (video/utils.py:355-368) on the gathered frames; every frame is written by a worker
         # thread behind an asynchronous device -> host copy while the next frame's warp / blend is already running
         sink = jobs.FileSink(engine.device, routes=outputs)
+        finals = []
         try:
             n, h, w, _ = frames_u8.shape
             prev = None
@@ -271,6 +306,10 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
                 sink.write(cur.unsqueeze(0), [os.path.join(output_dir, name)])
                 print(f"Stylized and saved: {os.path.join(output_dir, name)}")
                 prev = cur
+                if gif is not None:
+                    finals.append(cur)
+            if finals:                                         # the clip's final frames, still on the device, as one animated GIF
+                gif_file.write_gif(torch.stack(finals), gif["path"], gif["palette"], gif["fps"], gif["method"])
         except Exception as e:
             err = e
         try:
@@ -289,7 +328,8 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
                              cancel_flag=None, offset=0.30, prominence=20, *, engine=None,
                              vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth", decoder_str="Style_3DGS/AdaIN/models/decoder.pth",
                              depth_maps=None, intermediate_jpeg=False, group=None, jpeg_on_device=False, preserve_color=False,
-                             jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False, png_decode_on_device=False):
+                             jpeg_decode_on_device=False, jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False, png_decode_on_device=False,
+                             gif_path=None, gif_fps=20, gif_palette=None, gif_method=None):
     """One style for the whole clip (video/utils.py:244-295); keyword-only extras: a ready ``engine``, checkpoint paths,
     precomputed ``depth_maps``, the reference's lossy intermediate JPEG, a process group, ``preserve_color`` (every frame is styled with
     ``coral(style, frame)``, adain_inference's colour preservation, on the device) and the call's ``rt.JpegRoutes``, field by field:
@@ -302,11 +342,15 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
     ``png_on_device`` (default off): .png frames are encoded on the device (the clip's ``rt.OutputRoutes``, jobs.FileSink): files of the
     same pixels, not Pillow's bytes.  ``png_decode_on_device`` (default off): 8-bit non-interlaced grey, RGB and RGBA .png frames are
     decoded on the device (``rt.png_decode_rgb_file``), for the stylisation and for the package's flow providers: the pixels PIL decodes;
-    any other .png keeps PIL."""
+    any other .png keeps PIL.
+    ``gif_path`` (default None: nothing changes): rank 0 also keeps the clip's final frames on the device and writes them there as one
+    animated GIF at the end (``gif_file.write_gif``: ``gif_fps``; ``gif_palette``, ``gif_file.header``'s forms, None for the 6x6x6 cube
+    ``"web"``; ``gif_method``, None for error diffusion onto the cube and the nearest colour onto any other palette)."""
     outputs = rt.OutputRoutes(rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options), rt.PngRoute(png_on_device, None, png_decode_on_device))
     with _routes_scope(outputs if outputs.png.decode_on_device else outputs.jpeg):
         return _run_clip(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,
-                         engine, vgg_str, decoder_str, depth_maps, group, preserve_color, 0, intermediate_jpeg, outputs)
+                         engine, vgg_str, decoder_str, depth_maps, group, preserve_color, 0, intermediate_jpeg, outputs,
+                         _gif_request(gif_path, gif_fps, gif_palette, gif_method))
 
 
 def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_method="farneback", alpha=0.7, target_resolution=None,
@@ -314,14 +358,15 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
                                    vgg_str="Style_3DGS/AdaIN/models/vgg_normalised.pth",
                                    decoder_str="Style_3DGS/AdaIN/models/decoder.pth", depth_maps=None, intermediate_jpeg=False,
                                    group=None, jpeg_on_device=False, preserve_color=False, crossfade_frames=0, jpeg_decode_on_device=False,
-                                   jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False, png_decode_on_device=False):
+                                   jpeg_decode_progressive=False, jpeg_options=None, png_on_device=False, png_decode_on_device=False,
+                                   gif_path=None, gif_fps=20, gif_palette=None, gif_method=None):
     """The styles of ``style_dir`` (sorted) switch through the clip every ``frames // styles`` frames (video/utils.py:297-372).
     ``preserve_color``: as in ``apply_style_transfer_ada``; each style's pixels stay on the device next to its statistics.
     ``crossfade_frames`` (0, the default: the hard cuts of the reference): the styles cross-fade in feature space over that many
     frames centred on each switch (``jobs.style_crossfade``, style interpolation on the device; at most 16 styles, and not with
     ``preserve_color``).  ``jpeg_on_device``, ``jpeg_decode_on_device``, ``jpeg_decode_progressive``, ``jpeg_options``: the call's
     ``rt.JpegRoutes``, as in ``apply_style_transfer_ada`` (the options: the output files only, never the ``intermediate_jpeg`` round trip);
-    ``png_on_device``, ``png_decode_on_device``: as there."""
+    ``png_on_device``, ``png_decode_on_device``, ``gif_path``, ``gif_fps``, ``gif_palette``, ``gif_method``: as there."""
     style_images = sorted(os.listdir(style_dir))
     if len(style_images) == 0:
         raise ValueError("No style images found in the style directory.")
@@ -331,4 +376,4 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
     with _routes_scope(outputs if outputs.png.decode_on_device else outputs.jpeg):
         return _run_clip(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
                          cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, group, preserve_color, int(crossfade_frames),
-                         intermediate_jpeg, outputs)
+                         intermediate_jpeg, outputs, _gif_request(gif_path, gif_fps, gif_palette, gif_method))

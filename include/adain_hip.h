@@ -679,6 +679,37 @@ ADAIN_API int adain_palette_dither_u8_bytes(int n, int h, int w, size_t* workspa
 ADAIN_API int adain_palette_dither_u8(const uint8_t* src_u8, int n, int h, int w, const uint8_t* palette, int K, const uint8_t* lut_or_null, int grey,
                                       uint8_t* out_u8, uint8_t* index_or_null, void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
+/* ---- animated GIF clips: the frame records of the file Pillow's save(save_all=True) writes in the reference (Style_3DGS/render.py:29-33
+ * create_gif; video/utils.py:374-392 frames_to_video writes a cv2 video instead) -------------------------------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * index: n palette index planes uint8 [n][h][w] at any byte address - what adain_palette_map_u8 / adain_palette_dither_u8 write - with
+ * every index below K.  Row i of `out` ([n][out_stride] bytes, at any byte address) starts with frame i's record and lengths[i] (int32,
+ * 4-byte aligned) is its size: graphic control extension (disposal 1, no transparency, delay_cs centiseconds), image descriptor (full
+ * frame, no local table, not interlaced), minimum code size m = max(2, ceil(log2 K)), the LZW data in sub-blocks of 255, terminator.
+ * The records of a clip back to back between a header with the global colour table and the trailer 3B are an animated GIF any reader
+ * plays (gif_file.py builds that file).  The bytes are NOT Pillow's: the indices are cut into segments of ADAIN_GIF_SEGMENT = 2048
+ * pixels that each start with CLEAR and an empty dictionary, so that segments are coded side by side; they are a function of the
+ * indices, K and delay_cs alone - not of n, the stream, the device or what the workspace held - by the rules listed at the top of
+ * csrc/gif.hip and restated in tests/gif_ref.py.
+ * adain_gif_encode_u8_bytes (host only): *out_stride = the largest record a frame of this shape can have; an overflow is impossible,
+ *   not detected.  The k-th code behind a CLEAR has w(k) bits, the smallest w >= m + 1 with 2^m + 1 + k <= 2^w; W(c) = w(1) + ... + w(c).
+ *   A segment of p pixels emits at most p codes (greedy LZW never emits more codes than pixels) and is closed by one more, the next CLEAR
+ *   or EOI: at most W(p + 1) bits.  With the first CLEAR's m + 1 bits, D = ceil(((m + 1) + sum over the segments of W(p_s + 1)) / 8)
+ *   data bytes at most, and out_stride = 20 + D + ceil(D / 255): 8 + 10 + 1 bytes in front, a length byte per sub-block, the terminator.
+ *   *workspace_bytes = 2048 16-bit codes, a count and a bit offset per segment, a bit total and a flag per frame, and the bit stream at
+ *   its bound, of n frames.  Either output may be NULL.
+ * A frame with an index >= K cannot be coded (the index would collide with CLEAR): lengths[i] = 0 and no byte of its row is written;
+ * the other frames of the call are not affected.  What the kernels use as an address is clamped first.
+ * Refused with ADAIN_EINVAL before anything is launched, adain_last_error naming the argument: null pointers, K outside 1..256, h or w
+ * outside 1..65535, n outside 1..65535, delay_cs outside 0..65535, a frame whose out_stride would pass 2^31 - 1, out_stride or
+ * workspace_bytes below the query's, a workspace that is not 8-byte aligned, lengths that is not 4-byte aligned.  Bytes of `out` behind
+ * a record are not written.  Nothing is copied to the host and nothing waits; 5 kernel launches and one memset per call, whatever n.
+ * Not built: frame differencing and transparency, local colour tables, interlace, choosing a palette from the clip, reading GIFs. */
+#define ADAIN_GIF_SEGMENT 2048
+ADAIN_API int adain_gif_encode_u8_bytes(int n, int h, int w, int K, size_t* out_stride, size_t* workspace_bytes);
+ADAIN_API int adain_gif_encode_u8(const uint8_t* index_u8, int n, int h, int w, int K, int delay_cs, uint8_t* out, size_t out_stride,
+                                  int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream);
+
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
  * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
