@@ -624,6 +624,15 @@ int adain_gif_encode_u8(const uint8_t* index, int n, int h, int w, int K, int de
     return launch_gif_encode_u8(index, n, h, w, K, delay_cs, out, out_stride, lengths, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// the palette of a full-colour clip, chosen from its frames (what Pillow's quantize does for create_gif): the launcher refuses everything itself
+int adain_quantize_palette_u8_bytes(int n, int h, int w, int mode, size_t* workspace_bytes) {
+    return quantize_palette_bytes(n, h, w, mode, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_quantize_palette_u8(const uint8_t* src, int n, int h, int w, int K, int mode, uint8_t* palettes, int32_t* used, void* workspace, size_t workspace_bytes,
+                              adain_stream_t stream) {
+    return launch_quantize_palette_u8(src, n, h, w, K, mode, palettes, used, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
 }

@@ -253,6 +253,12 @@ int gif_encode_bytes(int n, int h, int w, int K, size_t* out_stride, size_t* wor
 int launch_gif_encode_u8(const uint8_t* index, int n, int h, int w, int K, int delay_cs, uint8_t* out, size_t out_stride, int32_t* lengths, void* workspace,
                          size_t workspace_bytes, hipStream_t s);
 
+// quantize.hip: a palette of at most 256 colours chosen from the frames (the rules: top of quantize.hip, tests/quantize_ref.py); the
+// launcher refuses everything itself
+int quantize_palette_bytes(int n, int h, int w, int mode, size_t* workspace_bytes);
+int launch_quantize_palette_u8(const uint8_t* src, int n, int h, int w, int K, int mode, uint8_t* palettes, int32_t* used, void* workspace, size_t workspace_bytes,
+                               hipStream_t s);
+
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);
 int launch_coral(const void* style, int style_is_u8, int style_n, int hs, int ws, const void* content, int content_is_u8, int n, int hc, int wc,

@@ -2,7 +2,9 @@
 // Pillow save(save_all=True) of a clip (Style_3DGS/render.py:29-33 create_gif; video/utils.py:374-392 frames_to_video needs cv2's
 // VideoWriter).  The file around the records is the host's: gif_file.py.  The rules, byte for byte: tests/gif_ref.py.
 //
-// One record per frame; its bytes are a function of the frame's indices, K and the delay alone.
+// One record per frame; its bytes are a function of the frame's indices, K and the delay alone.  The palette of a full-colour clip is chosen
+// by csrc/quantize.hip; a frame's own colour table is spliced into its record by the host (gif_file.records_bytes), which these kernels
+// know nothing of.
 //   GCE        : 21 F9 04 04 dl dh 00 00 - disposal 1, no transparency, the delay in centiseconds, little endian.
 //   descriptor : 2C 00 00 00 00 wl wh hl hh 00 - the full frame, no local table, not interlaced.
 //   code size  : m = max(2, ceil(log2 K)); CLEAR = 2^m, EOI = CLEAR + 1, the first dictionary code is CLEAR + 2.

@@ -223,6 +223,11 @@ class AdaINEngine:
         files any reader decodes to the frames' pixels, not Pillow's bytes) -> a list of n ``bytes``; only the files cross to the host."""
         return rt.png_files(*rt.png_encode_u8(frames_u8, filter))
 
+    def quantize_palette_u8(self, frames_u8, K=256, per_frame=False):
+        """Frames uint8 [n,h,w,3] on the device -> (palettes uint8 [P,256,3], used int32 [P]) on the device: at most ``K`` colours chosen
+        from the frames themselves, for all of them or ``per_frame`` (adain_quantize_palette_u8; ``runtime.quantize_palette_u8``)."""
+        return rt.quantize_palette_u8(frames_u8, K, per_frame)
+
     def gif_encode_u8(self, index_u8, K, delay_cs):
         """Palette index planes uint8 [n,h,w] on the device, every index below ``K`` -> the frames' GIF records (adain_gif_encode_u8;
         ``runtime.gif_encode_u8``) as (records, lengths) on the device; ``gif_file.assemble`` makes the file of them and only the records

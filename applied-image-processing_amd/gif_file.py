@@ -10,8 +10,17 @@ A palette clip is at most 256 colours and already indexed on the device (csrc/pa
 
 The records are not Pillow's bytes: the indices are cut into segments of 2048 pixels that each start with a CLEAR code, so that the
 segments are coded side by side (the rules: top of csrc/gif.hip, tests/gif_ref.py); every reader decodes them to the same pixels.  Every
-frame is a full frame on the global table.  Not built: frame differencing and transparency, local colour tables, interlace, choosing a
-palette from the clip (Pillow's ``quantize``), reading GIFs.
+frame is a full frame.
+
+A full-colour clip brings no palette.  ``palette="adaptive"`` chooses one of 256 colours for the whole clip from its frames,
+``"adaptive-local"`` one per frame - what Pillow writes for the reference's ``create_gif``, which hands it RGB frames - and
+``adaptive(colors, local)`` names either with another count.  The colours are chosen on the device (csrc/quantize.hip,
+``runtime.quantize_palette_u8``: a median cut of its own, not Pillow's palette).  A frame's own table is spliced into its record on the
+host: the descriptor's flag byte (offset 17 of the record) becomes 0x80 | (g - 1) and 3 * 2^g table bytes follow it, the palette and then
+zeros, g = max(1, ceil(log2 colors)); the header then has no global table (flags 0x70).  Both go with the nearest colour: Pillow's
+``convert("P", palette=ADAPTIVE)`` does not dither.
+
+Not built: frame differencing and transparency, interlace, reading GIFs.
 
 Without a GPU the same indices go through Pillow's own ``save(save_all=True)``: other bytes, the same decoded pixels.
 """
@@ -22,6 +31,8 @@ import numpy as np
 from . import pixelize
 
 WEB = "web"          # the 6 x 6 x 6 colour cube, for clips that are not pixel art; it goes with "floyd-steinberg-diffused"
+ADAPTIVE = "adaptive"                   # one palette chosen from the whole clip, the global table
+ADAPTIVE_LOCAL = "adaptive-local"       # one palette chosen from every frame, a local table each
 
 
 def web_palette():
@@ -31,8 +42,50 @@ def web_palette():
 
 
 def default_method(palette):
-    """The method a caller that names none gets: error diffusion onto the cube, the nearest colour onto a pixel-art palette."""
+    """The method a caller that names none gets: error diffusion onto the cube, the nearest colour onto a pixel-art palette and onto the
+    adaptive ones (Pillow's ``convert("P", palette=ADAPTIVE)`` does not dither)."""
     return "floyd-steinberg-diffused" if isinstance(palette, str) and palette == WEB else "kd-tree"
+
+
+def adaptive(colors=256, local=False):
+    """The ``palette`` of a clip that brings none: ``"adaptive"`` / ``"adaptive-local"``, which stand for 256 colours, or with another
+    count ``"adaptive:N"`` / ``"adaptive-local:N"``."""
+    name = ADAPTIVE_LOCAL if local else ADAPTIVE
+    return name if _colors(colors) == 256 else f"{name}:{colors}"
+
+
+def parse_adaptive(palette):
+    """(local, colors) of ``adaptive``'s strings, None for any other palette; ValueError for a count outside 1..256."""
+    if not isinstance(palette, str):
+        return None
+    name, _, count = palette.partition(":")
+    if name not in (ADAPTIVE, ADAPTIVE_LOCAL) or (count and not count.isdigit()):
+        return None
+    return name == ADAPTIVE_LOCAL, _colors(int(count)) if count else 256
+
+
+def is_adaptive(palette):
+    return parse_adaptive(palette) is not None
+
+
+def check_palette(palette):
+    """ValueError for a palette ``write_gif`` would refuse."""
+    if not is_adaptive(palette):
+        header((1, 1), palette)
+
+
+def _colors(colors):
+    if isinstance(colors, bool) or not isinstance(colors, (int, np.integer)) or not 1 <= colors <= 256:
+        raise ValueError(f"gif: colors must be an int in 1..256, got {colors!r}")
+    return int(colors)
+
+
+def table_bits(colors):
+    """g: a colour table of 2^g entries holds ``colors`` of them, g = max(1, ceil(log2 colors))."""
+    g = 1
+    while (1 << g) < colors:
+        g += 1
+    return g
 
 
 def _palette(palette):
@@ -52,30 +105,44 @@ def _u16(v, what):
 
 def header(size, palette, loop=None):
     """Everything in front of the first record.  ``size``: (w, h); ``palette``: ``"web"`` or 1..256 colours (``pixelize.parse_palette``'s
-    forms or uint8 [K,3]); ``loop``: None for no NETSCAPE2.0 extension, or the loop count (0: for ever)."""
-    pal = _palette(palette)
+    forms or uint8 [K,3]), or None for a file without a global table (flags 0x70: every record brings its own, ``local_records``);
+    ``loop``: None for no NETSCAPE2.0 extension, or the loop count (0: for ever)."""
+    pal = None if palette is None else _palette(palette)
     w, h = (_u16(v, "a frame side") for v in size)
     if w < 1 or h < 1:
         raise ValueError(f"gif: an empty frame {size!r}")
-    g = 1
-    while (1 << g) < len(pal):
-        g += 1
-    out = b"GIF89a" + struct.pack("<HHBBB", w, h, 0x80 | 0x70 | (g - 1), 0, 0) + pal.tobytes() + bytes(3 * ((1 << g) - len(pal)))
+    if pal is None:
+        out = b"GIF89a" + struct.pack("<HHBBB", w, h, 0x70, 0, 0)
+    else:
+        g = table_bits(len(pal))
+        out = b"GIF89a" + struct.pack("<HHBBB", w, h, 0x80 | 0x70 | (g - 1), 0, 0) + pal.tobytes() + bytes(3 * ((1 << g) - len(pal)))
     if loop is not None:
         out += b"\x21\xff\x0bNETSCAPE2.0\x03\x01" + struct.pack("<H", _u16(loop, "loop")) + b"\x00"
     return out
 
 
-def records_bytes(records, lengths):
+FLAGS_AT = 17          # of a record: 8 bytes of graphic control extension, then 2C, left, top, width, height and the flag byte
+
+
+def records_bytes(records, lengths, tables=None, colors=None):
     """The records of a ``runtime.gif_encode_u8`` result back to back: the lengths first, then only the bytes that are records (waits for
-    the device).  ValueError for a frame the device refused (length 0: an index that is not below K)."""
+    the device).  ValueError for a frame the device refused (length 0: an index that is not below K).  ``tables``: per frame its own
+    colours uint8 [k,3], k <= ``colors``, spliced in as a local table of 2^g entries, g = ``table_bits(colors)``: the flag byte becomes
+    0x80 | (g - 1) and the table - the colours, then zeros - follows it."""
     ln = [int(v) for v in (lengths.cpu().tolist() if hasattr(lengths, "cpu") else np.asarray(lengths).tolist())]
     bad = [i for i, k in enumerate(ln) if k <= 0]
     if bad:
         raise ValueError(f"gif: frame(s) {bad} hold an index that is not below the palette's size")
     rows = records[:, :max(ln)]
     rows = rows.cpu().numpy() if hasattr(rows, "cpu") else np.asarray(rows)
-    return b"".join(rows[i, :k].tobytes() for i, k in enumerate(ln))
+    if tables is None:
+        return b"".join(rows[i, :k].tobytes() for i, k in enumerate(ln))
+    g = table_bits(colors)
+    parts = []
+    for i, k in enumerate(ln):
+        rec, pal = rows[i, :k].tobytes(), np.ascontiguousarray(tables[i], dtype=np.uint8)
+        parts += [rec[:FLAGS_AT], bytes([0x80 | (g - 1)]), pal.tobytes(), bytes(3 * ((1 << g) - len(pal))), rec[FLAGS_AT + 1:]]
+    return b"".join(parts)
 
 
 def assemble(header, records, lengths):
@@ -123,13 +190,55 @@ def index_planes(frames, palette, method="kd-tree"):
     return rt.palette_map_u8(x, pal, pixelize._METRIC[method], index=True)[1]
 
 
+def _write_adaptive(frames, path, local, colors, delay, method, loop, step):
+    """``write_gif`` for the two adaptive palettes: the colours come from the frames (``pixelize.quantize_palettes``: on the device when
+    there is one), a frame is indexed onto its palette's ``used`` colours and coded with K = ``colors``."""
+    n, h, w, _ = frames.shape
+    pals, used = pixelize.quantize_palettes(frames, colors, per_frame=local, device=None if _cuda(frames) is not None else "cpu")
+    tables = [pals[i, :u] for i, u in enumerate(used)]          # one, or one per frame
+    if _cuda(frames) is None:
+        from PIL import Image
+
+        images = []
+        for i in range(n):
+            pal = tables[i if local else 0]
+            im = Image.frombytes("P", (w, h), index_planes(frames[i:i + 1], pal, method)[0].tobytes())
+            im.putpalette(pal.tobytes())
+            images.append(im)
+        extra = {} if loop is None else {"loop": loop}
+        images[0].save(path, format="GIF", save_all=True, append_images=images[1:], duration=delay * 10, disposal=1, optimize=False, **extra)
+        return path
+    from . import runtime as rt
+    import torch
+
+    parts = [header((w, h), None if local else tables[0], loop)]
+    pending = None
+    for i in range(0, n, step):
+        block = frames[i:i + step]
+        if local:          # a palette each: a map per frame, one coding call for the block
+            idx = torch.stack([index_planes(block[j:j + 1], tables[i + j], method)[0] for j in range(len(block))])
+        else:
+            idx = index_planes(block, tables[0], method)
+        coded = rt.gif_encode_u8(idx, colors, delay) + ((tables[i:i + len(block)], colors) if local else ())
+        if pending is not None:
+            parts.append(records_bytes(*pending))
+        pending = coded
+    parts.append(records_bytes(*pending))
+    parts.append(b"\x3b")
+    with open(path, "wb") as f:
+        f.write(b"".join(parts))
+    return path
+
+
 def write_gif(frames, path, palette, fps=20, method="kd-tree", loop=0, sub_batch=None):
     """``frames`` - uint8 [N,h,w,3], a GPU tensor or a NumPy array - as an animated GIF at ``path``: mapped (``method`` "rgb", "kd-tree",
     "floyd-steinberg") or dithered ("floyd-steinberg-diffused"; None: ``default_method``) onto ``palette`` (``header``'s forms), ``round(100 / fps)`` centiseconds a
     frame, ``loop`` times (0: for ever; None: no loop extension for a single frame).  With a GPU the frames are indexed and coded there,
     ``sub_batch`` frames to a call (default: about 32 MiB of pixels), and only the records are downloaded; without one Pillow writes the
-    same indices.  Returns ``path``."""
-    pal = _palette(palette)
+    same indices.  ``palette="adaptive"``: at most 256 colours chosen from the whole clip, the global table; ``"adaptive-local"``: chosen
+    from every frame, a local table each (the module's text); ``adaptive(colors, local)`` names another count.  Returns ``path``."""
+    chosen = parse_adaptive(palette)
+    pal = None if chosen else _palette(palette)
     method = default_method(palette) if method is None else method
     delay = delay_of(fps)
     if getattr(frames, "ndim", 0) != 4 or frames.shape[3] != 3 or frames.shape[0] < 1 or str(frames.dtype).split(".")[-1] != "uint8":
@@ -140,6 +249,8 @@ def write_gif(frames, path, palette, fps=20, method="kd-tree", loop=0, sub_batch
     step = int(sub_batch) if sub_batch else max(1, min(n, (32 << 20) // (h * w)))
     if step < 1:
         raise ValueError(f"write_gif: sub_batch must be positive, got {sub_batch!r}")
+    if chosen:
+        return _write_adaptive(frames, path, chosen[0], chosen[1], delay, method, loop, step)
     if _cuda(frames) is None:
         from PIL import Image
 
@@ -171,12 +282,18 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m applied_image_processing_amd.gif_file", description="Write a directory of frames as an animated GIF on a palette.")
     ap.add_argument("frames_dir")
     ap.add_argument("output")
-    ap.add_argument("--palette", required=True, help="a name in --palettes, #hex,#hex,... or web (the 6x6x6 cube)")
+    ap.add_argument("--palette", required=True, help="a name in --palettes, #hex,#hex,..., web (the 6x6x6 cube), adaptive (--colors colours chosen from "
+                    "the clip) or adaptive-local (chosen from every frame, a local colour table each)")
+    ap.add_argument("--colors", type=int, default=256, help="the colours of --palette adaptive / adaptive-local, 1..256 (default 256)")
     ap.add_argument("--palettes", help="a JSON file in the lospec list's format")
     ap.add_argument("--method", default=None, choices=pixelize.METHODS, help="default: kd-tree; floyd-steinberg-diffused for web")
     ap.add_argument("--fps", type=float, default=20)
     a = ap.parse_args(argv)
-    if a.palette == WEB:
+    if a.palette in (ADAPTIVE, ADAPTIVE_LOCAL):
+        if not 1 <= a.colors <= 256:
+            ap.error("--colors must be in 1..256")
+        colors = adaptive(a.colors, a.palette == ADAPTIVE_LOCAL)
+    elif a.palette == WEB:
         colors = WEB
     elif a.palette.startswith("#"):
         colors = pixelize.parse_palette(a.palette.split(","))

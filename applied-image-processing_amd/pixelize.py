@@ -15,6 +15,10 @@ the reference's own outputs):
                                 error diffusion in float32.
 ``"LAB"``                       not available: it needs cv2's COLOR_RGB2LAB on uint8, which nothing here can be pinned to.
 
+``extract_palette`` chooses a palette from the image itself (the reference's gui/seven_page.py does it with sklearn's k-means in LAB; here
+a median cut in RGB by the rules at the top of csrc/quantize.hip): ``runtime.quantize_palette_u8`` on the device, the same rules in NumPy
+without one, the same palette either way.  ``--palette adaptive --colors N`` on the command line.
+
 With a GPU the work is done by csrc/palette.hip (``runtime.palette_map_u8`` / ``tone_u8`` / ``palette_dither_u8``).  Without one
 (``device="cpu"``, or ``device=None`` on a machine that has none) the same rules run in NumPy on the host: slow for the diffused
 method, a Python loop over every pixel, and meant for machines without a device, not as a substitute when a kernel fails.
@@ -140,6 +144,95 @@ def _run_host(a, pal, method, lut, grey):
     if method == "floyd-steinberg-diffused":
         return np.stack([_dither_host(f, pal) for f in a.reshape((-1,) + a.shape[-3:])]).reshape(a.shape)
     return _map_host(a, pal, _METRIC[method])
+
+
+# --- a palette chosen from the image (csrc/quantize.hip's rules on the host) -----------------------------------------------------------------
+ADAPTIVE = "adaptive"          # --palette adaptive: the image's own colours, ``extract_palette``
+
+
+def _quantize_host(pixels, K):
+    """The rules at the top of csrc/quantize.hip in NumPy, for machines without a GPU: ``pixels`` uint8 [N,3], all of one palette ->
+    (uint8 [256,3] with zeros behind the colours, used).  The same palette as ``runtime.quantize_palette_u8``'s."""
+    px = np.ascontiguousarray(pixels).reshape(-1, 3)
+    if len(px) < 1 or len(px) >= 1 << 32:
+        raise ValueError(f"extract_palette: a palette needs 1..2^32 - 1 pixels, got {len(px)}")
+    v = px.astype(np.int64)
+    cell = ((v[:, 0] >> 3) << 10) | ((v[:, 1] >> 3) << 5) | (v[:, 2] >> 3)
+    # five planes of integer moments; bincount sums in float64, exact below 2^53 (Q stays below 2^50)
+    planes = [np.bincount(cell, minlength=32768).astype(np.int64)]
+    planes += [np.bincount(cell, weights=v[:, c], minlength=32768).astype(np.int64) for c in range(3)]
+    planes.append(np.bincount(cell, weights=(v * v).sum(axis=1), minlength=32768).astype(np.int64))
+    planes = [p.reshape(32, 32, 32) for p in planes]
+
+    def settle(lo, hi):
+        """The tight box inside cells lo..hi (inclusive, per axis) as (lo, hi, [w, Sr, Sg, Sb, Q] as Python ints)."""
+        sub = planes[0][lo[0]:hi[0] + 1, lo[1]:hi[1] + 1, lo[2]:hi[2] + 1]
+        lo, hi = list(lo), list(hi)
+        for a in range(3):
+            at = np.flatnonzero(sub.sum(axis=tuple(i for i in range(3) if i != a)))
+            lo[a], hi[a] = lo[a] + int(at[0]), lo[a] + int(at[-1])
+        where = tuple(slice(lo[a], hi[a] + 1) for a in range(3))
+        return lo, hi, [int(p[where].sum()) for p in planes]
+
+    def numerator(m):
+        return m[0] * m[4] - (m[1] ** 2 + m[2] ** 2 + m[3] ** 2)          # w E, a Python int
+
+    boxes = [settle([0, 0, 0], [31, 31, 31])]
+    while len(boxes) < K:
+        best = None
+        for i, (lo, hi, m) in enumerate(boxes):
+            if lo == hi:
+                continue
+            # E_i > E_best, exactly
+            if best is None or numerator(m) * boxes[best][2][0] > numerator(boxes[best][2]) * m[0]:
+                best = i
+        if best is None:
+            break
+        lo, hi, m = boxes[best]
+        side = [hi[a] - lo[a] for a in range(3)]
+        axis = next(a for a in (1, 0, 2) if side[a] == max(side))
+        sub = planes[0][lo[0]:hi[0] + 1, lo[1]:hi[1] + 1, lo[2]:hi[2] + 1]
+        cum = np.cumsum(sub.sum(axis=tuple(i for i in range(3) if i != axis)))
+        k = min(lo[axis] + int(np.searchsorted(cum, (m[0] + 1) // 2)), hi[axis] - 1)
+        low_hi, high_lo = list(hi), list(lo)
+        low_hi[axis], high_lo[axis] = k, k + 1
+        boxes[best] = settle(lo, low_hi)
+        boxes.append(settle(high_lo, hi))
+    pal = np.zeros((256, 3), dtype=np.uint8)
+    for i, (_, _, m) in enumerate(boxes):
+        pal[i] = [(2 * m[1 + c] + m[0]) // (2 * m[0]) for c in range(3)]
+    return pal, len(boxes)
+
+
+def quantize_palettes(frames, K=256, per_frame=False, device=None):
+    """``frames`` uint8 [n,h,w,3], a NumPy array or a tensor -> (palettes uint8 [P,256,3], used: a list of P ints) as NumPy, chosen on the
+    device the frames are on (an array goes to the current GPU when there is one; ``device="cpu"``: never) by ``runtime.quantize_palette_u8``,
+    on the host by the same rules in NumPy.  Waits for the device."""
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= 256:
+        raise ValueError(f"a palette has 1..256 colours, got {K!r}")
+    torch = _torch()
+    dev = _device(device, frames, "tensor" if isinstance(frames, torch.Tensor) else "numpy")
+    if dev is None:
+        a = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+        parts = [_quantize_host(f, int(K)) for f in a] if per_frame else [_quantize_host(a, int(K))]
+        return np.stack([p for p, _ in parts]), [u for _, u in parts]
+    from . import runtime as rt
+    pals, used = rt.quantize_palette_u8(_tensor(frames).to(dev), int(K), per_frame)
+    return pals.cpu().numpy(), used.cpu().tolist()
+
+
+def extract_palette(image, K, per_frame=False, device=None):
+    """At most ``K`` colours chosen from ``image`` itself - a PIL image, a uint8 NumPy array or a uint8 tensor, [h,w,3] or [n,h,w,3] - as
+    uint8 [used,3] (the reference's gui/seven_page.py ``extract_palette`` takes ``num_colors`` by k-means in LAB; this is a median cut in
+    RGB, the rules at the top of csrc/quantize.hip).  One palette for all frames, or with ``per_frame`` a list of one per frame.  With a
+    GPU the palette is chosen there, without one (or ``device="cpu"``) by the same rules in NumPy: the same palette.  ``used`` is below
+    ``K`` when the image has fewer than ``K`` non-empty cells of 8 x 8 x 8 colours."""
+    _, frames = _open(image)
+    if frames.ndim == 3:
+        frames = frames[None]
+    pals, used = quantize_palettes(frames, K, per_frame, device)
+    out = [pals[i, :u].copy() for i, u in enumerate(used)]
+    return out if per_frame else out[0]
 
 
 # --- inputs: a PIL image, a NumPy array or a GPU tensor; the result comes back as the same kind -----------------------------------------
@@ -298,8 +391,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m applied_image_processing_amd.pixelize", description="Recolour an image onto a palette (the reference's palette page).")
     ap.add_argument("input")
     ap.add_argument("output")
-    ap.add_argument("--palette", required=True, help="a name in --palettes, or #hex,#hex,...")
+    ap.add_argument("--palette", required=True, help="a name in --palettes, #hex,#hex,... or adaptive (--colors colours chosen from the image)")
     ap.add_argument("--palettes", help="a JSON file in the lospec list's format")
+    ap.add_argument("--colors", type=int, default=256, help="the colours of --palette adaptive, 1..256 (default 256)")
     ap.add_argument("--method", default="rgb", choices=METHODS + ("LAB",))
     ap.add_argument("--factor", type=int, default=1)
     ap.add_argument("--resampling", default="BILINEAR", type=str.upper, choices=tuple(RESAMPLING), metavar="NAME",
@@ -308,7 +402,13 @@ def main(argv=None):
     ap.add_argument("--brightness", type=float, default=0)
     ap.add_argument("--contrast", type=float, default=0)
     a = ap.parse_args(argv)
-    if a.palette.startswith("#"):
+    image = Image.open(a.input).convert("RGB")
+    if a.palette == ADAPTIVE:
+        if not 1 <= a.colors <= 256:
+            ap.error("--colors must be in 1..256")
+        # of the image as the recolouring sees it: downsampled and toned, not yet recoloured
+        colors = extract_palette(convert_image(image, a.factor, RESAMPLING[a.resampling], a.grayscale, a.brightness, a.contrast), a.colors)
+    elif a.palette.startswith("#"):
         colors = parse_palette(a.palette.split(","))
     else:
         if not a.palettes:
@@ -317,7 +417,7 @@ def main(argv=None):
         if a.palette not in palettes:
             ap.error(f"no palette {a.palette!r} in {a.palettes}")
         colors = palettes[a.palette]
-    out = convert_image(Image.open(a.input).convert("RGB"), a.factor, RESAMPLING[a.resampling], a.grayscale, a.brightness, a.contrast, colors, a.method)
+    out = convert_image(image, a.factor, RESAMPLING[a.resampling], a.grayscale, a.brightness, a.contrast, colors, a.method)
     out.save(a.output)
     return 0
 

@@ -115,6 +115,8 @@ SIGNATURES = {
     "adain_palette_dither_u8": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_gif_encode_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_gif_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_quantize_palette_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t)]),
+    "adain_quantize_palette_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_progressive_u8_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
@@ -1353,6 +1355,36 @@ def gif_encode_u8(index, K, delay_cs):
         _launch("adain_gif_encode_u8", x.data_ptr(), n, h, w, K, delay_cs, out.data_ptr(), stride, lengths.data_ptr(), ws.data_ptr(), ws.numel())
 
     return _encode_files(x, "gif", lambda: gif_encode_sizes(n, h, w, K), launch)
+
+
+# --- a palette chosen from the frames (adain_quantize_palette_u8) -------------------------------------------------------------------------
+QUANTIZE_GLOBAL, QUANTIZE_PER_FRAME = 0, 1          # ADAIN_QUANTIZE_*
+
+
+def quantize_palette_sizes(n, h, w, per_frame=False):
+    """workspace_bytes of adain_quantize_palette_u8_bytes.  Host only.  AdainHipError for a refused shape."""
+    return _size_query("adain_quantize_palette_u8_bytes", n, h, w, QUANTIZE_PER_FRAME if per_frame else QUANTIZE_GLOBAL)[0]
+
+
+def quantize_palette_u8(frames, K=256, per_frame=False):
+    """Frames uint8 [n,h,w,3] (or [h,w,3]) on the device -> (palettes uint8 [P,256,3], used int32 [P]), both on the device: at most ``K``
+    colours chosen from the frames themselves, one palette for all of them (P = 1) or with ``per_frame`` one each (P = n).  Palette p's
+    colours are its first ``used[p]`` entries, the rest is zero.  A median cut over 32 x 32 x 32 cells by the rules of csrc/quantize.hip
+    (tests/quantize_ref.py), not Pillow's palette; a function of the pixels, ``K`` and ``per_frame`` alone.  ``palette_map_u8`` /
+    ``palette_dither_u8`` take ``palettes[p, :used[p]]``.  (``quantize_u8`` is the float -> uint8 quantiser of ``save_image``.)  Nothing is
+    copied to the host and nothing waits."""
+    what = "quantize_palette_u8"
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 256:
+        raise AdainHipError(f"{what}: K must be an int in 1..256, got {K!r}")
+    x = _rgb_frames(frames, what)
+    n, h, w, _ = x.shape
+    P = n if per_frame else 1
+    palettes = torch.empty((P, 256, 3), dtype=torch.uint8, device=x.device)
+    used = torch.empty((P,), dtype=torch.int32, device=x.device)
+    with scratch(x.device, "quantize", quantize_palette_sizes, n, h, w, bool(per_frame)) as ws:
+        _launch("adain_quantize_palette_u8", x.data_ptr(), n, h, w, K, QUANTIZE_PER_FRAME if per_frame else QUANTIZE_GLOBAL, palettes.data_ptr(), used.data_ptr(),
+                ws.data_ptr(), ws.numel())
+    return palettes, used
 
 
 # --- .png input files (adain_png_decode_u8) -------------------------------------------------------------------------------------------

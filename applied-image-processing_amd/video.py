@@ -179,7 +179,7 @@ def _gif_request(path, fps, palette, method):
     if path is None:
         return None
     palette = gif_file.WEB if palette is None else palette
-    gif_file.header((1, 1), palette)          # refuses a bad palette now
+    gif_file.check_palette(palette)          # refuses a bad palette now
     gif_file.delay_of(fps)
     return {"path": str(path), "fps": fps, "palette": palette, "method": gif_file.default_method(palette) if method is None else method}
 
@@ -187,7 +187,7 @@ def _gif_request(path, fps, palette, method):
 def frames_to_gif(image_folder, output_gif, fps=20, palette=gif_file.WEB, method=None, routes=None):
     """The frames of ``image_folder`` (sorted by name, one size) as one animated GIF: the counterpart of the reference's ``frames_to_video``
     (video/utils.py:374-392, cv2's VideoWriter) in the container its results are shown in (Style_3DGS/render.py:29-33).  ``palette``,
-    ``method``: ``gif_file.write_gif``'s.  With a GPU the frames are read through ``routes`` (an ``rt.OutputRoutes``: decoded on the
+    ``method``: ``gif_file.write_gif``'s (``"adaptive"`` / ``"adaptive-local"``: 256 colours chosen from the clip / from every frame; ``gif_file.adaptive``).  With a GPU the frames are read through ``routes`` (an ``rt.OutputRoutes``: decoded on the
     device where it says so, PIL otherwise), recoloured and coded there; without one PIL reads and writes.  Returns ``output_gif``."""
     names = _frame_files(image_folder)
     if not names:
@@ -344,8 +344,8 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
     decoded on the device (``rt.png_decode_rgb_file``), for the stylisation and for the package's flow providers: the pixels PIL decodes;
     any other .png keeps PIL.
     ``gif_path`` (default None: nothing changes): rank 0 also keeps the clip's final frames on the device and writes them there as one
-    animated GIF at the end (``gif_file.write_gif``: ``gif_fps``; ``gif_palette``, ``gif_file.header``'s forms, None for the 6x6x6 cube
-    ``"web"``; ``gif_method``, None for error diffusion onto the cube and the nearest colour onto any other palette)."""
+    animated GIF at the end (``gif_file.write_gif``: ``gif_fps``; ``gif_palette``, ``gif_file.header``'s forms, ``"adaptive"`` / ``"adaptive-local"`` for 256 colours
+    chosen from the clip / from every frame, None for the 6x6x6 cube ``"web"``; ``gif_method``, None for error diffusion onto the cube and the nearest colour onto any other palette)."""
     outputs = rt.OutputRoutes(rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options), rt.PngRoute(png_on_device, None, png_decode_on_device))
     with _routes_scope(outputs if outputs.png.decode_on_device else outputs.jpeg):
         return _run_clip(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,

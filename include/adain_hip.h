@@ -704,11 +704,36 @@ ADAIN_API int adain_palette_dither_u8(const uint8_t* src_u8, int n, int h, int w
  * outside 1..65535, n outside 1..65535, delay_cs outside 0..65535, a frame whose out_stride would pass 2^31 - 1, out_stride or
  * workspace_bytes below the query's, a workspace that is not 8-byte aligned, lengths that is not 4-byte aligned.  Bytes of `out` behind
  * a record are not written.  Nothing is copied to the host and nothing waits; 5 kernel launches and one memset per call, whatever n.
- * Not built: frame differencing and transparency, local colour tables, interlace, choosing a palette from the clip, reading GIFs. */
+ * A palette chosen from the clip: adain_quantize_palette_u8 below; local colour tables: gif_file.py splices them into these records on the
+ * host.  Not built: frame differencing and transparency, interlace, reading GIFs. */
 #define ADAIN_GIF_SEGMENT 2048
 ADAIN_API int adain_gif_encode_u8_bytes(int n, int h, int w, int K, size_t* out_stride, size_t* workspace_bytes);
 ADAIN_API int adain_gif_encode_u8(const uint8_t* index_u8, int n, int h, int w, int K, int delay_cs, uint8_t* out, size_t out_stride,
                                   int32_t* lengths, void* workspace, size_t workspace_bytes, adain_stream_t stream);
+
+/* ---- a palette chosen from the frames themselves: the stage in front of adain_palette_map_u8 / adain_palette_dither_u8 and
+ * adain_gif_encode_u8 for a full-colour clip (Style_3DGS/render.py:29-33 create_gif hands Pillow RGB frames, which Pillow quantises to an
+ * adaptive palette each; gui/seven_page.py extract_palette) ---------------------------------------------------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.  adain_quantize_u8 above is the float -> uint8
+ * quantiser of save_image and has nothing to do with this call.)
+ * src: n frames HWC uint8 [n][h][w][3] at any byte address.  mode ADAIN_QUANTIZE_GLOBAL: one palette for the n frames, P = 1;
+ * ADAIN_QUANTIZE_PER_FRAME: one per frame, P = n.  palettes: uint8 [P][256][3]; used: int32 [P], 4-byte aligned.  Palette p has used[p]
+ * <= K colours in its first entries, the entries behind them are zero.  NOT Pillow's palette: a median cut over a 32 x 32 x 32 grid of
+ * cells (value >> 3) with integer moments, the box with the largest squared error split at its pixel median along its longest side, every
+ * comparison exact; a function of the pixels, K and mode alone - not of the stream, the device or what the workspace held - by the rules
+ * listed at the top of csrc/quantize.hip and restated in tests/quantize_ref.py.  Two colours in one cell are merged: a frame with fewer
+ * than K non-empty cells gets used < K.
+ * adain_quantize_palette_u8_bytes (host only): *workspace_bytes = per palette the five planes of the grid, 32768 x (4 + 4 x 8) bytes.
+ * Refused with ADAIN_EINVAL before anything is launched, adain_last_error naming the argument: a null src, palettes or used, K outside
+ * 1..256, a mode other than the two, h, w or n below 1, n above 65535, 2^32 or more pixels for one palette (n h w for GLOBAL, h w for
+ * PER_FRAME), a null workspace, workspace_bytes below the query's, a workspace that is not 8-byte aligned, used that is not 4-byte
+ * aligned, palettes, used or the workspace overlapping src.  Nothing is copied to the host and nothing waits; 3 kernel launches and
+ * one memset per call, whatever n. */
+#define ADAIN_QUANTIZE_GLOBAL 0
+#define ADAIN_QUANTIZE_PER_FRAME 1
+ADAIN_API int adain_quantize_palette_u8_bytes(int n, int h, int w, int mode, size_t* workspace_bytes);
+ADAIN_API int adain_quantize_palette_u8(const uint8_t* src_u8, int n, int h, int w, int K, int mode, uint8_t* palettes_u8, int32_t* used_i32,
+                                        void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
