@@ -175,56 +175,33 @@ def device_transform_u8(img, size, crop, device, mark=None):
     return _device_resize(_upload_rgb(img, device, mark), img.size[0], img.size[1], plan)
 
 
+def device_frame_transform_u8(rgb, size, crop):
+    """``device_transform_u8`` of a frame that is on the device already, uint8 [h,w,3] (a file decoded there): uint8 [1,h',w',3], or
+    None when the transform is not the device's."""
+    h, w = rgb.shape[:2]
+    plan = _device_plan(w, h, size, crop)
+    return _device_resize(rgb[None], w, h, plan) if plan is not None else None
+
+
 def device_decode_transform_u8(path, size, crop, device, mark=None):
-    """``device_transform_u8`` of the colour JPEG file at ``path`` without PIL: the file's bytes go up, the frame is decoded on the
-    device (adain_jpeg_decode_u8: Pillow's pixels) and resized there.  None when the file is not a three-component baseline JPEG the
-    decoder takes (or, with ``set_device_jpeg_decode(True, progressive=True)``, a progressive one), or did not decode cleanly, or the
-    transform is not the device's: the caller takes the PIL path."""
-    read = rt.jpeg_read_parsed(path, _routes.jpeg.decode_progressive)
-    if read is None or read[0].c != 3:          # PIL opens a grey file as mode L, which keeps the host transform
+    """``device_transform_u8`` of the image file at ``path`` without PIL, when ``_routes`` decode its format on the device
+    (``set_device_jpeg_decode``, ``set_device_png_decode``): the file's bytes go up, the frame is decoded there (adain_jpeg_decode_u8,
+    adain_png_decode_u8: Pillow's pixels) and resized there.  None when the file is not a three-channel colour file the decoder takes
+    (a baseline JPEG, with ``set_device_jpeg_decode(True, progressive=True)`` a progressive one, an RGB PNG: PIL opens grey and RGBA
+    files in modes that keep the host transform), or did not decode cleanly, or the transform is not the device's: the caller takes the
+    PIL path."""
+    fmt, options = _routes.decoder(path) or (None, None)
+    read = rt.read_input(fmt, path, **options) if fmt is not None else None
+    if read is None or read[0].c != 3:
         return None
-    parsed, data = read
-    plan = _device_plan(parsed.w, parsed.h, size, crop)
+    plan = _device_plan(read[0].w, read[0].h, size, crop)          # before anything is uploaded
     if plan is None:
         return None
     if mark is not None:
         with torch.cuda.device(device):
             mark()
-    out, record = rt.jpeg_decode_parsed([parsed], [data], device)
-    if record[0, 0].item() != 0:
-        return None
-    return _device_resize(out, parsed.w, parsed.h, plan)
-
-
-def png_read_rgb(path):
-    """The file at ``path``, read and parsed -> (png_file.PngFile, its bytes) when it is a colour-type-2 (RGB) file the device decoder
-    takes, else None: PIL opens grey and RGBA files in modes that keep the host transform (Pillow resizes RGBA through premultiplied alpha)."""
-    from .. import png_file
-
-    with open(str(path), "rb") as f:
-        data = f.read()
-    try:
-        parsed = png_file.parse(data)
-    except png_file.UnsupportedPng:
-        return None
-    return (parsed, data) if parsed.c == 3 else None
-
-
-def device_png_decode_transform_u8(path, size, crop, device, mark=None):
-    """``device_decode_transform_u8`` for the .png file at ``path``: decoded on the device (adain_png_decode_u8: Pillow's pixels) and
-    resized there.  None when the file is not an RGB file the decoder takes, did not decode cleanly, or the transform is not the
-    device's: the caller takes the PIL path."""
-    read = png_read_rgb(path)
-    plan = _device_plan(read[0].w, read[0].h, size, crop) if read is not None else None
-    if plan is None:
-        return None
-    if mark is not None:
-        with torch.cuda.device(device):
-            mark()
-    out, record = rt.png_decode_batch([read[0]], [read[1]], device)
-    if record[0, 0].item() != 0:
-        return None
-    return _device_resize(out, read[0].w, read[0].h, plan)
+    (_, frame, _, _), = rt.settle_decodes(fmt, [(path, *read)], device)
+    return _device_resize(frame[None], read[0].w, read[0].h, plan) if frame is not None else None
 
 
 def save_image(tensor, path, jpeg_options=None):
@@ -737,15 +714,9 @@ def _content_frame(content_img, content_size, crop, device, call):
     T = _stage_timer
     t0 = time.perf_counter()
     pil_content = call.pil_content = _open(content_img)
-    is_path = type(content_img) == str or isinstance(content_img, Path)
-    decode = None
-    if is_path and _routes.jpeg.decode_on_device and rt.is_jpeg_path(content_img):
-        decode = device_decode_transform_u8
-    elif is_path and _routes.png.decode_on_device and rt.is_png_path(content_img):
-        decode = device_png_decode_transform_u8
-    if decode is not None:
+    if (type(content_img) == str or isinstance(content_img, Path)) and _routes.decoder(content_img) is not None:
         e0 = torch.cuda.Event(enable_timing=True) if T.on else None
-        frame = decode(content_img, content_size, crop, device, e0.record if T.on else None)
+        frame = device_decode_transform_u8(content_img, content_size, crop, device, e0.record if T.on else None)
         if frame is not None:                                        # (pil_content stays lazily opened: decoded only if a depth provider asks)
             T("read + decode + resize content (device)", t0)
             return frame, e0

@@ -982,7 +982,7 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
         one that png_file.parse refuses or that did not decode cleanly, a transform that is not the device's).  The block's .png paths
         are decoded in batches of the feeder's sub-batch - the RGB files of a batch that share a size in one ``rt.png_decode_batch`` call,
         its record read once - on whichever fetch thread asks first; a frame stays cached until it is consumed."""
-        from .AdaIN.test import _device_plan, _device_resize, png_read_rgb
+        from .AdaIN.test import _device_plan, device_frame_transform_u8
 
         if not (lo <= k < hi):
             return None
@@ -990,22 +990,18 @@ def precompute_guides_sharded(engine, views, names, output_dir, style, *, masks=
         with png_lock:
             if b not in png_done:
                 png_done.add(b)
-                groups = {}
+                items = []
                 for q in range(lo + b * png_step, min(hi, lo + (b + 1) * png_step)):
-                    read = png_read_rgb(views[q]) if isinstance(views[q], (str, Path)) and rt.is_png_path(views[q]) else None
-                    if read is not None and _device_plan(read[0].w, read[0].h, content_size, crop) is not None:
-                        groups.setdefault(read[0].geometry, []).append((q, read[0]))
+                    read = rt.read_input(rt.PNG_INPUT, views[q]) if isinstance(views[q], (str, Path)) and rt.is_png_path(views[q]) else None
+                    if read is not None and read[0].c == 3 and _device_plan(read[0].w, read[0].h, content_size, crop) is not None:
+                        items.append((q, *read))
                 with torch.cuda.device(engine.device):
-                    launched = [(members, rt.png_decode_batch([p for _, p in members], None, engine.device)) for members in groups.values()]
-                    for members, (out, record) in launched:
-                        for (q, _), frame, status in zip(members, out, record[:, 0].tolist()):
-                            if status == 0:
-                                png_frames[q] = frame
+                    png_frames.update((q, frame) for q, frame, status, _ in rt.settle_decodes(rt.PNG_INPUT, items, engine.device) if status == 0)
             frame = png_frames.pop(k, None)
         if frame is None:
             return None
         with torch.cuda.device(engine.device):
-            return _device_resize(frame[None], frame.shape[1], frame.shape[0], _device_plan(frame.shape[1], frame.shape[0], content_size, crop))[0]
+            return device_frame_transform_u8(frame, content_size, crop)[0]
 
     class _Views:                         # lazy: a rank only opens and resizes the views of its own block
         def __len__(self):

@@ -13,6 +13,8 @@ import threading
 
 import torch
 
+from . import jpeg_file, png_file
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # The product library.  Nothing in the environment can swap it: another build is loaded only by an explicit ``use_library(path)``
 # call (bench.py --lib: same-box A/B runs).
@@ -1387,104 +1389,6 @@ def quantize_palette_u8(frames, K=256, per_frame=False):
     return palettes, used
 
 
-# --- .png input files (adain_png_decode_u8) -------------------------------------------------------------------------------------------
-def png_decode_sizes(n, h, w, c_file, max_stream_bytes):
-    """workspace_bytes of adain_png_decode_u8_bytes: the scratch of an n-file call whose longest zlib stream has ``max_stream_bytes``.
-    Host only.  AdainHipError for a refused shape."""
-    return _size_query("adain_png_decode_u8_bytes", n, h, w, c_file, max_stream_bytes)[0]
-
-
-_png_decode_lock = threading.Lock()
-
-
-def png_decode_batch(parsed, datas, device, c_out=None):
-    """``parsed``: png_file.PngFile of n files of ONE (h, w, colour type) (anything else is an error), ``datas``: their bytes, one per
-    file, or None (``jpeg_decode_batch``'s signature; a PngFile already holds its stream, so only their number is checked) -> (frames uint8 [n,h,w,c_out], record int32 [n,2]:
-    status and deflate blocks per file), both on ``device``.  ``c_out``: None for the file's channels, or 3 (grey replicated, alpha
-    dropped).  One upload - the zlib streams back to back - and one call of adain_png_decode_u8; nothing comes back and nothing waits.
-    A frame whose status is not 0 is unspecified.  The one door to the C call (looked up when called: tests count the decodes here)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise AdainHipError("png_decode_batch: expected a GPU device (the device decoder has no CPU form)")
-    n = len(parsed)
-    if n < 1 or any(p.geometry != parsed[0].geometry for p in parsed) or (datas is not None and len(datas) != n):
-        raise AdainHipError("png_decode_batch: expected the files of one height, width and colour type")
-    h, w, c = parsed[0].h, parsed[0].w, parsed[0].c
-    c_out = c if c_out is None else int(c_out)
-    offsets = [0]
-    for p in parsed:
-        offsets.append(offsets[-1] + len(p.stream))
-    up = torch.frombuffer(bytearray(b"".join(p.stream for p in parsed) + b"\0"), dtype=torch.uint8).to(device)
-    off = (ctypes.c_uint64 * (n + 1))(*offsets)
-    # Stream order is what keeps two calls off each other's workspace; the lock only keeps the size query, a growth of the stream's
-    # workspace and the launch of one thread's call together, so that a second thread on the same stream cannot re-make the workspace between them
-    with _png_decode_lock, scratch(device, "png_decode", png_decode_sizes, n, h, w, c, max(len(p.stream) for p in parsed)) as ws:
-        out = torch.empty((n, h, w, c_out), dtype=torch.uint8, device=device)
-        record = torch.empty((n, 2), dtype=torch.int32, device=device)
-        _launch("adain_png_decode_u8", up.data_ptr(), offsets[-1], off, n, h, w, c, c_out, out.data_ptr(), record.data_ptr(), ws.data_ptr(), ws.numel())
-    return out, record
-
-
-def png_decode_u8(files, device=None, mode=None, report=None):
-    """The bytes of PNG files (a list, or one ``bytes``) -> device uint8 tensors (a list, or one): per file the array
-    ``np.asarray(Image.open(io.BytesIO(data)))`` gives - [h,w] for a grey file, [h,w,3] for RGB, [h,w,4] for RGBA - or, with ``mode``
-    "RGB" / "L", ``np.asarray(Image.open(...).convert(mode))`` (grey is replicated and alpha dropped for "RGB"; "L" from a colour file
-    goes to the host).  8-bit non-interlaced files of colour type 0, 2 or 6 are decoded on the device (adain_png_decode_u8; grouped by
-    height, width and colour type, one upload and one call per group, the record read once); whatever png_file.parse refuses, and any
-    file whose status comes back non-zero, is decoded by PIL on the host exactly as before and uploaded - PIL's exceptions pass through.
-    ``report`` (a list): per file "device" or "host: <why>", and the deflate blocks the device read."""
-    from . import png_file
-
-    single = isinstance(files, (bytes, bytearray, memoryview))
-    datas = [bytes(files)] if single else [bytes(f) for f in files]
-    device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-    if mode not in (None, "RGB", "L"):
-        raise AdainHipError(f"png_decode_u8: mode must be None, 'RGB' or 'L', got {mode!r}")
-    results, why, blocks, groups = [None] * len(datas), [None] * len(datas), [0] * len(datas), {}
-    for i, d in enumerate(datas):
-        try:
-            p = png_file.parse(d)
-            if mode == "L" and p.c != 1:
-                raise png_file.UnsupportedPng("a colour file where grey is wanted")
-            groups.setdefault(p.geometry, []).append((i, p))
-        except png_file.UnsupportedPng as e:
-            why[i] = str(e)
-    launched = [(members, png_decode_batch([p for _, p in members], [datas[i] for i, _ in members], device, 3 if mode == "RGB" else None))
-                for members in groups.values()]
-    for members, (out, record) in launched:
-        rec = record.cpu().tolist()                      # the one read of the record: waits for the call
-        for k, (i, p) in enumerate(members):
-            blocks[i] = rec[k][1]
-            if rec[k][0] != 0:
-                why[i] = f"the zlib stream did not decode cleanly (status {rec[k][0]})"
-                continue
-            results[i] = out[k, :, :, 0] if out.shape[3] == 1 else out[k]
-    for i, d in enumerate(datas):
-        if results[i] is None:
-            results[i] = torch.from_numpy(_pil_pixels(d, mode).copy()).to(device)
-    if report is not None:
-        report[:] = [{"path": "device" if why[i] is None else "host: " + why[i], "blocks": blocks[i]} for i in range(len(datas))]
-    return results[0] if single else results
-
-
-def png_decode_rgb_file(path, device):
-    """The frame ``np.asarray(Image.open(path).convert("RGB"))`` as a uint8 [h,w,3] tensor on ``device``, decoded there - or None when
-    the file is not one the device decoder takes (not a .png name, refused by png_file.parse, a non-zero status): the caller then
-    decodes it with PIL as before.  Reads the record once (waits for the call)."""
-    from . import png_file
-
-    if not is_png_path(path) or torch.device(device).type != "cuda":
-        return None
-    with open(str(path), "rb") as f:
-        data = f.read()
-    try:
-        parsed = png_file.parse(data)
-    except png_file.UnsupportedPng:
-        return None
-    out, record = png_decode_batch([parsed], [data], device, 3)
-    return out[0] if record[0, 0].item() == 0 else None
-
-
 class PngRoute(_Value):
     """Which of a call's .png work the device does - the ``png`` of its ``OutputRoutes``.  ``encode_on_device``: ``png_encode_u8`` writes
     the .png outputs (the same pixels, not Pillow's bytes) and only the files cross to the host; ``filter``: its row filter, None for the
@@ -1537,6 +1441,15 @@ class OutputRoutes(_Value):
         extension (``png`` for .png, ``jpeg`` for everything else, which answers for .jpg / .jpeg) - or None: the caller decodes with PIL."""
         return self.png.read_rgb(path, device) if is_png_path(path) else self.jpeg.read_rgb(path, device)
 
+    def decoder(self, path):
+        """(the ``InputFormat`` that owns the extension of ``path``, the options its file routes parse with) when that format's
+        ``decode_on_device`` is set - or None: PIL opens the file."""
+        if self.png.decode_on_device and is_png_path(path):
+            return PNG_INPUT, {}
+        if self.jpeg.decode_on_device and is_jpeg_path(path):
+            return JPEG_INPUT, {"restart": True, "progressive": self.jpeg.decode_progressive}
+        return None
+
     def save(self, arr, path):
         """The host route: a numpy frame [h,w,c] (c = 1: mode L) -> the file ``jpeg.options.save`` writes (its keywords: .jpg / .jpeg only)."""
         from PIL import Image
@@ -1582,7 +1495,8 @@ def jpeg_roundtrip_u8(u8, quality=JPEG_DEFAULT_QUALITY):
     return out.reshape(u8.shape)
 
 
-# --- input files (adain_jpeg_decode_restart_u8; at restart interval 0 that is adain_jpeg_decode_u8) ------------------------------------
+# --- input files: the doors to the C calls, the two formats, the one path over them, the public functions --------------------------------
+# baseline .jpg / .jpeg (adain_jpeg_decode_restart_u8; at restart interval 0 that is adain_jpeg_decode_u8)
 def jpeg_decode_sizes(n, h, w, c, sampling, max_segment_bytes, chunk_bits=0, restart_interval=0):
     """workspace_bytes of adain_jpeg_decode_restart_u8_bytes: the scratch of an n-file call whose longest entropy-coded segment has
     ``max_segment_bytes`` and whose files have ``restart_interval`` MCUs per restart interval (0: none).  Host only.  AdainHipError for
@@ -1597,8 +1511,6 @@ def _jpeg_upload(streams, device, lead):
     """``streams``: per entropy-coded segment what describes it (``blob``, ``seg_offset``, ``seg_length``: a baseline file, or one scan of
     a progressive one) and the bytes of its file -> (device uint8 tensor: the blobs, ``lead`` spare bytes, the segments back to back;
     segment offsets behind the blobs; segment lengths)."""
-    from . import jpeg_file
-
     device = torch.device(device)
     if device.type != "cuda":
         raise AdainHipError("jpeg_decode_u8: expected a GPU device (the device decoder has no CPU form)")
@@ -1630,8 +1542,6 @@ def jpeg_decode_upload(parsed, datas, device, lead=0):
 def jpeg_decode_launch(up, offsets, lengths, geometry, chunk_bits=0, restart_interval=0):
     """adain_jpeg_decode_restart_u8 on an upload of ``jpeg_decode_upload`` whose files have ``restart_interval`` MCUs per restart
     interval (0: none) -> (frames uint8 [n,h,w,c], record int32 [n,2]) on its device."""
-    from . import jpeg_file
-
     n = len(lengths)
     h, w, c, sampling = geometry
     blobs = n * jpeg_file.BLOB_BYTES
@@ -1656,7 +1566,7 @@ def jpeg_decode_batch(parsed, datas, device, chunk_bits=0, lead=0):
     return jpeg_decode_launch(up, offsets, lengths, parsed[0].geometry, chunk_bits, parsed[0].restart_interval)
 
 
-# --- progressive input files (adain_jpeg_decode_progressive_u8) -----------------------------------------------------------------------
+# progressive .jpg / .jpeg (adain_jpeg_decode_progressive_u8)
 def jpeg_decode_progressive_sizes(n, h, w, c, sampling, nscans, max_segment_bytes, chunk_bits=0):
     """workspace_bytes of adain_jpeg_decode_progressive_u8_bytes: the scratch of an n-file call of ``nscans`` scans whose longest scan
     segment has ``max_segment_bytes``.  Host only.  AdainHipError for a refused shape."""
@@ -1678,8 +1588,6 @@ def jpeg_decode_progressive_upload(parsed, datas, device, lead=0):
 def jpeg_decode_progressive_launch(up, offsets, lengths, geometry, script, chunk_bits=0):
     """adain_jpeg_decode_progressive_u8 on an upload of ``jpeg_decode_progressive_upload`` whose files have the scan ``script``
     (ProgressiveJpegFile.script) -> (frames uint8 [n,h,w,c], record int32 [n,2]) on its device."""
-    from . import jpeg_file
-
     nscans = len(script)
     n = len(lengths) // max(nscans, 1)
     h, w, c, sampling = geometry
@@ -1712,22 +1620,94 @@ def jpeg_decode_progressive_batch(parsed, datas, device, chunk_bits=0, lead=0):
 def jpeg_decode_parsed(parsed, datas, device, chunk_bits=0, lead=0):
     """``jpeg_decode_progressive_batch`` or ``jpeg_decode_batch`` of files parsed alike, by what they were parsed as.  Every route to
     the device decoders goes through here and through those two names (looked up when called: tests count the decodes there)."""
-    from . import jpeg_file
-
     batch = jpeg_decode_progressive_batch if isinstance(parsed[0], jpeg_file.ProgressiveJpegFile) else jpeg_decode_batch
     return batch(parsed, datas, device, chunk_bits, lead)
 
 
-def jpeg_read_parsed(path, progressive=False):
-    """The file at ``path``, read and parsed as the callers' file routes take it (restart intervals always, progressive files with
-    ``progressive``) -> (jpeg_file.JpegFile | ProgressiveJpegFile, its bytes), or None for a file jpeg_file.parse refuses."""
-    from . import jpeg_file
+# .png (adain_png_decode_u8)
+def png_decode_sizes(n, h, w, c_file, max_stream_bytes):
+    """workspace_bytes of adain_png_decode_u8_bytes: the scratch of an n-file call whose longest zlib stream has ``max_stream_bytes``.
+    Host only.  AdainHipError for a refused shape."""
+    return _size_query("adain_png_decode_u8_bytes", n, h, w, c_file, max_stream_bytes)[0]
 
+
+_png_decode_lock = threading.Lock()
+
+
+def png_decode_batch(parsed, datas, device, c_out=None):
+    """``parsed``: png_file.PngFile of n files of ONE (h, w, colour type) (anything else is an error), ``datas``: their bytes, one per
+    file, or None (``jpeg_decode_batch``'s signature; a PngFile already holds its stream, so only their number is checked) -> (frames uint8 [n,h,w,c_out], record int32 [n,2]:
+    status and deflate blocks per file), both on ``device``.  ``c_out``: None for the file's channels, or 3 (grey replicated, alpha
+    dropped).  One upload - the zlib streams back to back - and one call of adain_png_decode_u8; nothing comes back and nothing waits.
+    A frame whose status is not 0 is unspecified.  The one door to the C call (looked up when called: tests count the decodes here)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise AdainHipError("png_decode_batch: expected a GPU device (the device decoder has no CPU form)")
+    n = len(parsed)
+    if n < 1 or any(p.geometry != parsed[0].geometry for p in parsed) or (datas is not None and len(datas) != n):
+        raise AdainHipError("png_decode_batch: expected the files of one height, width and colour type")
+    h, w, c = parsed[0].h, parsed[0].w, parsed[0].c
+    c_out = c if c_out is None else int(c_out)
+    offsets = [0]
+    for p in parsed:
+        offsets.append(offsets[-1] + len(p.stream))
+    up = torch.frombuffer(bytearray(b"".join(p.stream for p in parsed) + b"\0"), dtype=torch.uint8).to(device)
+    off = (ctypes.c_uint64 * (n + 1))(*offsets)
+    # Stream order is what keeps two calls off each other's workspace; the lock only keeps the size query, a growth of the stream's
+    # workspace and the launch of one thread's call together, so that a second thread on the same stream cannot re-make the workspace between them
+    with _png_decode_lock, scratch(device, "png_decode", png_decode_sizes, n, h, w, c, max(len(p.stream) for p in parsed)) as ws:
+        out = torch.empty((n, h, w, c_out), dtype=torch.uint8, device=device)
+        record = torch.empty((n, 2), dtype=torch.int32, device=device)
+        _launch("adain_png_decode_u8", up.data_ptr(), offsets[-1], off, n, h, w, c, c_out, out.data_ptr(), record.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, record
+
+
+# What the two input formats do differently; everything below is written once over the two values.  ``owns(path)``: is the extension
+# the format's; ``parse(data, **options)``: the parsed file (the module's ``parse``, looked up when called: a test replaces it), or
+# ``refused`` raised with why not (the report's "host: <why>"); ``colour(p)``: is the parsed file one that mode "L" leaves to the host;
+# ``alike(p)``: what the files of one batch call share; ``launch(parsed, datas, device, mode, chunk_bits)``: one group's call ->
+# (out, record), through the doors above, looked up when called; ``shape(out, k, p, mode)``: row k of ``out`` as the caller's frame;
+# ``failure``: the host route's text for a non-zero ``status``; ``what``, ``count``: the public function's name in its errors and the
+# report's key for the record's second column.
+InputFormat = collections.namedtuple("InputFormat", "what owns parse refused colour alike launch shape failure count")
+JPEG_INPUT = InputFormat(
+    what="jpeg_decode_u8", owns=is_jpeg_path, count="rounds", failure="the entropy-coded data did not decode cleanly",
+    parse=lambda data, **options: jpeg_file.parse(data, **options), refused=jpeg_file.UnsupportedJpeg, colour=lambda p: p.c == 3,
+    alike=lambda p: (p.geometry, p.script if hasattr(p, "script") else p.restart_interval),
+    launch=lambda parsed, datas, device, mode, chunk_bits: jpeg_decode_parsed(parsed, datas, device, chunk_bits),
+    shape=lambda out, k, p, mode: out[k] if p.c == 3 else out[k, :, :, 0] if mode != "RGB" else out[k].expand(-1, -1, 3).contiguous())
+PNG_INPUT = InputFormat(
+    what="png_decode_u8", owns=is_png_path, count="blocks", failure="the zlib stream did not decode cleanly (status {status})",
+    parse=lambda data, **options: png_file.parse(data, **options), refused=png_file.UnsupportedPng, colour=lambda p: p.c != 1,
+    alike=lambda p: p.geometry,
+    launch=lambda parsed, datas, device, mode, chunk_bits: png_decode_batch(parsed, datas, device, 3 if mode == "RGB" else None),
+    shape=lambda out, k, p, mode: out[k, :, :, 0] if out.shape[3] == 1 else out[k])          # (the kernel replicated grey and dropped alpha)
+
+
+def settle_decodes(fmt, items, device, mode=None, chunk_bits=0):
+    """``items``: (key, parsed, data) per file that ``fmt.parse`` took -> yields (key, frame | None, status, count) per file, group by
+    group: the files are grouped by ``fmt.alike``, EVERY group is launched (one upload and one call each) before anything is read, then
+    each group's record is read once, in launch order (the read waits for the call).  ``frame``: ``fmt.shape``'s, on ``device``, or None
+    for a non-zero status.  ``mode``: None or "RGB" (a grey file replicated, a .png's alpha dropped).  A generator: nothing is launched
+    before the first result is asked for."""
+    groups = {}
+    for item in items:
+        groups.setdefault(fmt.alike(item[1]), []).append(item)
+    launched = [(members, fmt.launch([p for _, p, _ in members], [d for _, _, d in members], device, mode, chunk_bits)) for members in groups.values()]
+    for members, (out, record) in launched:
+        rec = record.cpu().tolist()                      # the one read of the record: waits for the call
+        for k, (key, p, _) in enumerate(members):
+            status, count = rec[k]
+            yield key, fmt.shape(out, k, p, mode) if status == 0 else None, status, count
+
+
+def read_input(fmt, path, **options):
+    """The file at ``path``, read and parsed -> (the parsed file, its bytes), or None for a file ``fmt.parse`` refuses."""
     with open(str(path), "rb") as f:
         data = f.read()
     try:
-        return jpeg_file.parse(data, restart=True, progressive=progressive), data
-    except jpeg_file.UnsupportedJpeg:
+        return fmt.parse(data, **options), data
+    except fmt.refused:
         return None
 
 
@@ -1741,6 +1721,45 @@ def _pil_pixels(data, mode):
     return np.asarray(img.convert(mode) if mode is not None else img)
 
 
+def _decode_files(fmt, files, device, mode, report, chunk_bits=0, **options):
+    """``jpeg_decode_u8`` / ``png_decode_u8``: parse every file, settle what the device takes, PIL for the rest, the report."""
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    datas = [bytes(files)] if single else [bytes(f) for f in files]
+    device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+    if mode not in (None, "RGB", "L"):
+        raise AdainHipError(f"{fmt.what}: mode must be None, 'RGB' or 'L', got {mode!r}")
+    results, why, counts, items = [None] * len(datas), [None] * len(datas), [0] * len(datas), []
+    for i, d in enumerate(datas):
+        try:
+            p = fmt.parse(d, **options)
+        except fmt.refused as e:
+            why[i] = str(e)
+            continue
+        if mode == "L" and fmt.colour(p):
+            why[i] = "a colour file where grey is wanted"
+        else:
+            items.append((i, p, d))
+    for i, frame, status, count in settle_decodes(fmt, items, device, mode, chunk_bits):
+        results[i], counts[i] = frame, count
+        if frame is None:
+            why[i] = fmt.failure.format(status=status)
+    for i, d in enumerate(datas):
+        if results[i] is None:
+            results[i] = torch.from_numpy(_pil_pixels(d, mode).copy()).to(device)
+    if report is not None:
+        report[:] = [{"path": "device" if w is None else "host: " + w, fmt.count: n} for w, n in zip(why, counts)]
+    return results[0] if single else results
+
+
+def _decode_rgb_file(fmt, path, device, **options):
+    """``jpeg_decode_rgb_file`` / ``png_decode_rgb_file``: a file of another extension is not opened."""
+    read = read_input(fmt, path, **options) if fmt.owns(path) and torch.device(device).type == "cuda" else None
+    if read is None:
+        return None
+    (_, frame, _, _), = settle_decodes(fmt, [(path, *read)], device, "RGB")
+    return frame
+
+
 def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None, restart=False, progressive=False):
     """The bytes of image files (a list, or one ``bytes``) -> device uint8 tensors (a list, or one): per file the array
     ``np.asarray(Image.open(io.BytesIO(data)))`` gives - [h,w,3] for a colour file, [h,w] for a grey one - or, with ``mode`` "RGB" / "L",
@@ -1752,39 +1771,18 @@ def jpeg_decode_u8(files, device=None, chunk_bits=0, mode=None, report=None, res
     progressive Huffman (SOF2) files with a complete scan script are decoded on the device as well (adain_jpeg_decode_progressive_u8;
     grouped by geometry and scan script); False, the default, leaves them to PIL as before.  ``report`` (a list): per file "device" or
     "host: <why>", and the rounds (a progressive file's: summed over its Huffman-coded scans)."""
-    from . import jpeg_file
+    return _decode_files(JPEG_INPUT, files, device, mode, report, chunk_bits, restart=restart, progressive=progressive)
 
-    single = isinstance(files, (bytes, bytearray, memoryview))
-    datas = [bytes(files)] if single else [bytes(f) for f in files]
-    device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-    if mode not in (None, "RGB", "L"):
-        raise AdainHipError(f"jpeg_decode_u8: mode must be None, 'RGB' or 'L', got {mode!r}")
-    results, why, rounds, groups = [None] * len(datas), [None] * len(datas), [0] * len(datas), {}
-    for i, d in enumerate(datas):
-        try:
-            p = jpeg_file.parse(d, restart=restart, progressive=progressive)
-            if mode == "L" and p.c == 3:
-                raise jpeg_file.UnsupportedJpeg("a colour file where grey is wanted")
-            alike = p.script if hasattr(p, "script") else p.restart_interval          # what one batch call's files share beside the geometry
-            groups.setdefault((p.geometry, alike), []).append((i, p))
-        except jpeg_file.UnsupportedJpeg as e:
-            why[i] = str(e)
-    launched = [(members, jpeg_decode_parsed([p for _, p in members], [datas[i] for i, _ in members], device, chunk_bits)) for members in groups.values()]
-    for members, (out, record) in launched:
-        rec = record.cpu().tolist()                      # the one read of the record: waits for the call
-        for k, (i, p) in enumerate(members):
-            rounds[i] = rec[k][1]
-            if rec[k][0] != 0:
-                why[i] = "the entropy-coded data did not decode cleanly"
-                continue
-            frame = out[k]
-            results[i] = frame[..., 0] if p.c == 1 and mode != "RGB" else frame.expand(-1, -1, 3).contiguous() if p.c == 1 else frame
-    for i, d in enumerate(datas):
-        if results[i] is None:
-            results[i] = torch.from_numpy(_pil_pixels(d, mode).copy()).to(device)
-    if report is not None:
-        report[:] = [{"path": "device" if why[i] is None else "host: " + why[i], "rounds": rounds[i]} for i in range(len(datas))]
-    return results[0] if single else results
+
+def png_decode_u8(files, device=None, mode=None, report=None):
+    """The bytes of PNG files (a list, or one ``bytes``) -> device uint8 tensors (a list, or one): per file the array
+    ``np.asarray(Image.open(io.BytesIO(data)))`` gives - [h,w] for a grey file, [h,w,3] for RGB, [h,w,4] for RGBA - or, with ``mode``
+    "RGB" / "L", ``np.asarray(Image.open(...).convert(mode))`` (grey is replicated and alpha dropped for "RGB"; "L" from a colour file
+    goes to the host).  8-bit non-interlaced files of colour type 0, 2 or 6 are decoded on the device (adain_png_decode_u8; grouped by
+    height, width and colour type, one upload and one call per group, the record read once); whatever png_file.parse refuses, and any
+    file whose status comes back non-zero, is decoded by PIL on the host exactly as before and uploaded - PIL's exceptions pass through.
+    ``report`` (a list): per file "device" or "host: <why>", and the deflate blocks the device read."""
+    return _decode_files(PNG_INPUT, files, device, mode, report)
 
 
 def jpeg_decode_rgb_file(path, device, progressive=False):
@@ -1792,14 +1790,14 @@ def jpeg_decode_rgb_file(path, device, progressive=False):
     the file is not one the device decoder takes (not a .jpg / .jpeg name, refused by jpeg_file.parse, a non-zero status): the caller
     then decodes it with PIL as before.  Files with restart intervals are taken; progressive files only with ``progressive=True``.
     Reads the record once (waits for the call)."""
-    read = jpeg_read_parsed(path, progressive) if is_jpeg_path(path) and torch.device(device).type == "cuda" else None
-    if read is None:
-        return None
-    parsed, data = read
-    out, record = jpeg_decode_parsed([parsed], [data], device)
-    if record[0, 0].item() != 0:
-        return None
-    return out[0].expand(-1, -1, 3).contiguous() if parsed.c == 1 else out[0]
+    return _decode_rgb_file(JPEG_INPUT, path, device, restart=True, progressive=progressive)
+
+
+def png_decode_rgb_file(path, device):
+    """The frame ``np.asarray(Image.open(path).convert("RGB"))`` as a uint8 [h,w,3] tensor on ``device``, decoded there - or None when
+    the file is not one the device decoder takes (not a .png name, refused by png_file.parse, a non-zero status): the caller then
+    decodes it with PIL as before.  Reads the record once (waits for the call)."""
+    return _decode_rgb_file(PNG_INPUT, path, device)
 
 
 def nhwc_to_nchw(x):

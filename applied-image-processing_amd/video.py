@@ -252,9 +252,9 @@ def _run_clip(content_dir, style_paths, output_dir, flow_method, alpha, target_r
                 # the file's bytes go up and are decoded there: Pillow's pixels (csrc/jpeg_decode.hip, csrc/png_decode.hip)
                 with torch.cuda.device(engine.device):
                     rgb = outputs.read_rgb(os.path.join(content_dir, names[k]), engine.device)
-                plan = adain_test._device_plan(rgb.shape[1], rgb.shape[0], 256, False) if rgb is not None else None
-                if plan is not None:
-                    return adain_test._device_resize(rgb[None], rgb.shape[1], rgb.shape[0], plan)[0]
+                frame = adain_test.device_frame_transform_u8(rgb, 256, False) if rgb is not None else None
+                if frame is not None:
+                    return frame[0]
             img = Image.open(os.path.join(content_dir, names[k])).convert("RGB")
             if on_gpu:                                        # Resize(256) on the device, PIL's bytes exactly (csrc/resample.hip)
                 return adain_test.device_transform_u8(img, 256, False, engine.device)[0]
