@@ -633,6 +633,27 @@ int adain_quantize_palette_u8(const uint8_t* src, int n, int h, int w, int K, in
     return launch_quantize_palette_u8(src, n, h, w, K, mode, palettes, used, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// the scores of Style_3DGS/metrics.py (utils/loss_utils.py ssim, utils/image_utils.py psnr) per frame: the launchers refuse everything themselves
+int adain_image_metrics_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
+    return image_metrics_u8_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_image_metrics_u8(const uint8_t* a, const uint8_t* b, int n, int h, int w, int c, double* out, float* ssim_map, void* workspace, size_t workspace_bytes,
+                           adain_stream_t stream) {
+    return launch_image_metrics_u8(a, b, n, h, w, c, out, ssim_map, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int adain_image_metrics_f32_bytes(int n, int c, int h, int w, size_t* workspace_bytes) {
+    return image_metrics_f32_bytes(n, c, h, w, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_image_metrics_f32(const float* a, const float* b, int n, int c, int h, int w, double* out, float* ssim_map, void* workspace, size_t workspace_bytes,
+                            adain_stream_t stream) {
+    return launch_image_metrics_f32(a, b, n, c, h, w, out, ssim_map, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int adain_ssim_window(float* out) {
+    if (!out) { set_error("ssim_window: out is a null pointer"); return ADAIN_EINVAL; }
+    ssim_window(out);
+    return ADAIN_OK;
+}
+
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
 }

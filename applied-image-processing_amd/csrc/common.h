@@ -259,6 +259,16 @@ int quantize_palette_bytes(int n, int h, int w, int mode, size_t* workspace_byte
 int launch_quantize_palette_u8(const uint8_t* src, int n, int h, int w, int K, int mode, uint8_t* palettes, int32_t* used, void* workspace, size_t workspace_bytes,
                                hipStream_t s);
 
+// metrics.hip: per-frame SSIM, MSE, L1 and PSNR of two clips (the rules: top of metrics.hip, tests/metrics_ref.py); the launchers refuse
+// everything themselves
+int image_metrics_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
+int image_metrics_f32_bytes(int n, int c, int h, int w, size_t* workspace_bytes);
+int launch_image_metrics_u8(const uint8_t* a, const uint8_t* b, int n, int h, int w, int c, double* out, float* ssim_map, void* workspace, size_t workspace_bytes,
+                            hipStream_t s);
+int launch_image_metrics_f32(const float* a, const float* b, int n, int c, int h, int w, double* out, float* ssim_map, void* workspace, size_t workspace_bytes,
+                             hipStream_t s);
+void ssim_window(float out[11]);
+
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);
 int launch_coral(const void* style, int style_is_u8, int style_n, int hs, int ws, const void* content, int content_is_u8, int n, int hc, int wc,

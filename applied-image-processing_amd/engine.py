@@ -228,6 +228,12 @@ class AdaINEngine:
         from the frames themselves, for all of them or ``per_frame`` (adain_quantize_palette_u8; ``runtime.quantize_palette_u8``)."""
         return rt.quantize_palette_u8(frames_u8, K, per_frame)
 
+    def image_metrics(self, a, b, ssim_map=False):
+        """Two clips on the device, uint8 [n,h,w,1|3] or float32 [n,1..4,h,w] -> their per-frame SSIM (window 11), MSE, L1 and PSNR as
+        float64 [n] device tensors, with ``ssim_map`` the map as well (adain_image_metrics_u8 / adain_image_metrics_f32;
+        ``runtime.image_metrics``)."""
+        return rt.image_metrics(a, b, ssim_map)
+
     def gif_encode_u8(self, index_u8, K, delay_cs):
         """Palette index planes uint8 [n,h,w] on the device, every index below ``K`` -> the frames' GIF records (adain_gif_encode_u8;
         ``runtime.gif_encode_u8``) as (records, lengths) on the device; ``gif_file.assemble`` makes the file of them and only the records

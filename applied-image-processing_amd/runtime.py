@@ -119,6 +119,11 @@ SIGNATURES = {
     "adain_gif_encode_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_quantize_palette_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t)]),
     "adain_quantize_palette_u8": (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_image_metrics_u8_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t)]),
+    "adain_image_metrics_u8": (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 4 + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_image_metrics_f32_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t)]),
+    "adain_image_metrics_f32": (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 4 + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_ssim_window": (_c_int, [ctypes.POINTER(_c_float)]),
     "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_progressive_u8_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
@@ -1387,6 +1392,67 @@ def quantize_palette_u8(frames, K=256, per_frame=False):
         _launch("adain_quantize_palette_u8", x.data_ptr(), n, h, w, K, QUANTIZE_PER_FRAME if per_frame else QUANTIZE_GLOBAL, palettes.data_ptr(), used.data_ptr(),
                 ws.data_ptr(), ws.numel())
     return palettes, used
+
+
+# --- image quality metrics (adain_image_metrics_u8 / adain_image_metrics_f32) ---------------------------------------------------------------
+METRICS_TILE = (16, 64)          # ADAIN_METRICS_TILE_Y, ADAIN_METRICS_TILE_X: rows x samples a workgroup takes
+
+
+class ImageMetrics:
+    """What ``image_metrics`` returns: ``ssim``, ``mse``, ``l1`` and ``psnr`` as float64 [n] device tensors (views of ``records``, the
+    call's float64 [n,4]) and ``ssim_map``, float32 of the inputs' shape, or None when it was not asked for."""
+    __slots__ = ("records", "ssim_map")
+
+    def __init__(self, records, ssim_map=None):
+        self.records, self.ssim_map = records, ssim_map
+
+    ssim = property(lambda self: self.records[:, 0])
+    mse = property(lambda self: self.records[:, 1])
+    l1 = property(lambda self: self.records[:, 2])
+    psnr = property(lambda self: self.records[:, 3])
+
+
+def image_metrics_sizes(n, h, w, c, u8=True):
+    """workspace_bytes of adain_image_metrics_u8_bytes (``u8``) or adain_image_metrics_f32_bytes.  Host only.  AdainHipError for a
+    refused shape."""
+    return _size_query("adain_image_metrics_u8_bytes", n, h, w, c)[0] if u8 else _size_query("adain_image_metrics_f32_bytes", n, c, h, w)[0]
+
+
+def image_metrics(a, b, ssim_map=False):
+    """Two clips on the device -> their per-frame scores, an ``ImageMetrics``: the reference's ``ssim`` (window 11), ``mse``, ``l1`` and
+    ``psnr`` (Style_3DGS utils/loss_utils.py, utils/image_utils.py) as float64 [n] device tensors, and with ``ssim_map`` the per-element
+    map.  uint8 [n,h,w,c] or [h,w,c] with c = 1 or 3 takes adain_image_metrics_u8 (scaled as ``to_tensor`` does, x / 255); float32
+    [n,c,h,w] or [c,h,w] with c in 1..4 takes adain_image_metrics_f32, values as given.  Equal frames score ssim 1, mse 0, l1 0 and
+    psnr +inf exactly; the uint8 mse and l1 are exact.  Nothing is copied to the host and nothing waits."""
+    what = "image_metrics"
+    if not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor) or a.dtype not in (torch.uint8, torch.float32):
+        raise AdainHipError(f"{what}: expected two uint8 or two float32 GPU tensors")
+    u8 = a.dtype == torch.uint8
+    x, y = device_tensor(a, what + ": a", a.dtype), device_tensor(b, what + ": b", a.dtype)
+    if x.shape != y.shape or x.device != y.device:
+        raise AdainHipError(f"{what}: a and b must have one shape and one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if x.dim() == 3:
+        x, y = x[None], y[None]
+    if x.dim() != 4 or x.numel() == 0 or (x.shape[3] not in (1, 3) if u8 else not 1 <= x.shape[1] <= 4):
+        raise AdainHipError(f"{what}: expected uint8 [n,h,w,1|3] / [h,w,1|3] or float32 [n,1..4,h,w] / [c,h,w], got {tuple(a.shape)}")
+    n = x.shape[0]
+    (h, w, c) = x.shape[1:] if u8 else (x.shape[2], x.shape[3], x.shape[1])
+    records = torch.empty((n, 4), dtype=torch.float64, device=x.device)
+    smap = torch.empty(x.shape, dtype=torch.float32, device=x.device) if ssim_map else None
+    with scratch(x.device, "metrics", image_metrics_sizes, n, h, w, c, u8) as ws:
+        dims = (n, h, w, c) if u8 else (n, c, h, w)
+        _launch("adain_image_metrics_u8" if u8 else "adain_image_metrics_f32", x.data_ptr(), y.data_ptr(), *dims, records.data_ptr(),
+                smap.data_ptr() if ssim_map else None, ws.data_ptr(), ws.numel())
+    return ImageMetrics(records, smap.reshape(a.shape) if ssim_map else None)
+
+
+def ssim_window():
+    """The eleven float32 weights of the SSIM kernel (adain_ssim_window): the reference's ``gaussian(11, 1.5)``.  Host only."""
+    out = (_c_float * 11)()
+    rc = lib().adain_ssim_window(out)
+    if rc != 0:
+        raise _failure("adain_ssim_window", rc)
+    return list(out)
 
 
 class PngRoute(_Value):

@@ -735,6 +735,44 @@ ADAIN_API int adain_quantize_palette_u8_bytes(int n, int h, int w, int mode, siz
 ADAIN_API int adain_quantize_palette_u8(const uint8_t* src_u8, int n, int h, int w, int K, int mode, uint8_t* palettes_u8, int32_t* used_i32,
                                         void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
+/* ---- image quality metrics of frames that are already on the device: the scores Style_3DGS/metrics.py computes per view with
+ * utils/loss_utils.py ssim (window 11, sigma 1.5) and utils/image_utils.py psnr, and the l1_loss / l2_loss beside them ------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * adain_image_metrics_u8: a, b are n frames HWC uint8 [n][h][w][c], c = 1 or 3, at any byte address, scaled as to_tensor does
+ *   (float(x) / 255.0f, a division).  adain_image_metrics_f32: a, b are contiguous NCHW float32 [n][c][h][w], c in 1..4, 4-byte aligned,
+ *   values as given (the reference does not clamp).  a may be b.
+ * out: double [n][4], 8-byte aligned; frame i's record is {ssim, mse, l1, psnr}:
+ *   ssim: the mean over the frame's h w c samples of the reference's map, ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)
+ *     (s1 + s2 + C2)) with C1 = 0.01^2, C2 = 0.03^2, under the float32 window gaussian(11, 1.5) (adain_ssim_window), zero padding of 5,
+ *     the window not renormalised at the border (a 1 x 1 frame is legal).  The map is float32, its sum float64.  The window is applied
+ *     as a row pass and a column pass, not as the reference's 121-tap product: the values differ from the reference's by less than the
+ *     reference's differ from float64 (tests/golden/metrics/noise.json).  Equal frames give exactly 1.
+ *   mse, l1: the means of (a - b)^2 and |a - b| in the scale of the scaled samples.  uint8: exact integer sums, then one float64
+ *     division by h w c 255^2 and by h w c 255.  float32: float64 sums of the float32 differences' squares and magnitudes.
+ *   psnr: 20 log10(1 / sqrt(mse)) in float64; +inf for equal frames.
+ * ssim_map: NULL, or float32 of the inputs' layout ([n][h][w][c], or [n][c][h][w]), 4-byte aligned, that receives the map; the records
+ *   are the same bits with it and without it.
+ * A frame's record and map are a function of its two frames alone - not of n, the stream, the device or what the workspace held: a
+ * workgroup takes ADAIN_METRICS_TILE_Y rows of ADAIN_METRICS_TILE_X samples (of the packed row of w c samples for uint8, of one plane
+ * for float32), reduces them in a fixed order and leaves one partial record in the workspace; a second kernel adds a frame's partial
+ * records in index order.  No float atomics.  The rules are listed at the top of csrc/metrics.hip and restated in tests/metrics_ref.py.
+ * adain_image_metrics_*_bytes (host only): *workspace_bytes = 24 bytes per tile of the n frames.  The output may be NULL.
+ * adain_ssim_window (host only, no device needed): the eleven float32 weights the kernel uses, bit for bit the reference's.
+ * Refused with ADAIN_EINVAL before anything is launched, adain_last_error naming the argument: a null a, b or out, c outside the above,
+ * n outside 1..65535, h or w below 1, a frame beyond 2^31 - 1 samples, a null workspace, workspace_bytes below the query's, a workspace
+ * or out that is not 8-byte aligned, a ssim_map (or float32 a, b) that is not 4-byte aligned, out, ssim_map or the workspace overlapping
+ * a or b.  Nothing is copied to the host and nothing waits; 2 kernel launches per call, whatever n.
+ * Not built: windows other than 11, a backward pass (the 3DGS training loss stays with torch), LPIPS. */
+#define ADAIN_METRICS_TILE_X 64
+#define ADAIN_METRICS_TILE_Y 16
+ADAIN_API int adain_image_metrics_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
+ADAIN_API int adain_image_metrics_u8(const uint8_t* a_u8, const uint8_t* b_u8, int n, int h, int w, int c, double* out, float* ssim_map_or_null,
+                                     void* workspace, size_t workspace_bytes, adain_stream_t stream);
+ADAIN_API int adain_image_metrics_f32_bytes(int n, int c, int h, int w, size_t* workspace_bytes);
+ADAIN_API int adain_image_metrics_f32(const float* a, const float* b, int n, int c, int h, int w, double* out, float* ssim_map_or_null,
+                                      void* workspace, size_t workspace_bytes, adain_stream_t stream);
+ADAIN_API int adain_ssim_window(float* out11);
+
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
  * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
