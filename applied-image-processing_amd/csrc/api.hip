@@ -794,6 +794,11 @@ static int stylize_impl(const uint8_t* frames, int n, int h, int w, const float*
         set_error("stylize_u8: mask [%d][%d][%d][%d] does not fit %d RGB frames", mask_n, mask_c, mask_h, mask_w, n);
         return ADAIN_EINVAL;
     }
+    // launch_mask_to_f32's limit (a thread per element), here with the other arguments: it runs behind the encoder, the blend and the decoder
+    if (mask && !mask_is_float && (size_t)mask_n * mask_c * mask_h * mask_w > 0xffffff00ULL) {
+        set_error("stylize_u8: a uint8 mask of more than 2^32 - 256 elements");
+        return ADAIN_EINVAL;
+    }
     const StylizePlan p = stylize_plan(n, h, w, depth_maps != nullptr, mask_n, mask_c, mask_h, mask_w, mask_is_float);
     RET_IF(check_workspace("stylize_u8", workspace, ws_bytes, p.total, 1));
     hipStream_t s = (hipStream_t)stream;

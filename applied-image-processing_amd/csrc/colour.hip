@@ -72,7 +72,10 @@ struct Rgb {
     __device__ bool in_region() const { return r + g + b > 0; }
 };
 
-__device__ __forceinline__ Rgb load_rgb(const uint8_t* p, int i) { return Rgb{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
+__device__ __forceinline__ Rgb load_rgb(const uint8_t* p, int i) {      // a byte offset: 3 i passes 2^31 - 1 from 715 827 883 pixels on (2^30 - 1 are admitted)
+    const size_t o = 3 * (size_t)i;
+    return Rgb{p[o], p[o + 1], p[o + 2]};
+}
 
 template <int REGION>   // 0: foreground, 1: background
 __device__ __forceinline__ Rgb region_pixel(const Images& im, int i) {
@@ -274,9 +277,9 @@ __global__ __launch_bounds__(CT_THREADS) void colour_match_kernel(Images im, int
                 o[c] = (unsigned)(fmin(fmax(v, 0.0), 1.0) * 255.0);
             }
         }
-        out[3 * i] = (uint8_t)o[0];
-        out[3 * i + 1] = (uint8_t)o[1];
-        out[3 * i + 2] = (uint8_t)o[2];
+        out[3 * (size_t)i] = (uint8_t)o[0];
+        out[3 * (size_t)i + 1] = (uint8_t)o[1];
+        out[3 * (size_t)i + 2] = (uint8_t)o[2];
     }
 }
 

@@ -59,7 +59,8 @@ __device__ __forceinline__ unsigned nearest(const int* spal, int K, int r, int g
     return kb;
 }
 
-// total pixels of all frames, 4 per thread (VEC4: total % 4 == 0, src / out / index 4-byte aligned) or one
+// total pixels of all frames, 4 per thread (VEC4: total % 4 == 0, src / out / index 4-byte aligned) or one.  A grid-stride walk: a launch
+// holds fewer than 2^32 threads (MAP_MAX_BLOCKS workgroups), a batch may hold more pixels than that.
 template <int METRIC, bool VEC4>
 __global__ __launch_bounds__(256) void palette_map_kernel(const uint8_t* __restrict__ src, size_t total, const uint8_t* __restrict__ pal, int K,
                                                           const uint8_t* __restrict__ lut, int grey, uint8_t* __restrict__ out,
@@ -70,33 +71,33 @@ __global__ __launch_bounds__(256) void palette_map_kernel(const uint8_t* __restr
     stage_lut(lut, slut, 256);
     __syncthreads();
     const uint8_t* l = lut ? slut : nullptr;
-    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (VEC4) {
-        if (q * 4 >= total) return;
-        using u32x3 = __attribute__((ext_vector_type(3))) unsigned;
-        const u32x3 in = *(const u32x3*)(src + q * 12);
-        unsigned by[12], idx = 0;
+    const size_t units = VEC4 ? total / 4 : total, stride = (size_t)gridDim.x * 256;
+    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < units; q += stride) {
+        if (VEC4) {
+            using u32x3 = __attribute__((ext_vector_type(3))) unsigned;
+            const u32x3 in = *(const u32x3*)(src + q * 12);
+            unsigned by[12], idx = 0;
 #pragma unroll
-        for (int e = 0; e < 12; ++e) by[e] = (in[e >> 2] >> (8 * (e & 3))) & 255u;
+            for (int e = 0; e < 12; ++e) by[e] = (in[e >> 2] >> (8 * (e & 3))) & 255u;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            tone_px(by[3 * p], by[3 * p + 1], by[3 * p + 2], l, grey);
-            const unsigned k = nearest<METRIC>(spal, K, (int)by[3 * p], (int)by[3 * p + 1], (int)by[3 * p + 2]);
-            by[3 * p] = (unsigned)spal[3 * k], by[3 * p + 1] = (unsigned)spal[3 * k + 1], by[3 * p + 2] = (unsigned)spal[3 * k + 2];
-            idx |= k << (8 * p);
+            for (int p = 0; p < 4; ++p) {
+                tone_px(by[3 * p], by[3 * p + 1], by[3 * p + 2], l, grey);
+                const unsigned k = nearest<METRIC>(spal, K, (int)by[3 * p], (int)by[3 * p + 1], (int)by[3 * p + 2]);
+                by[3 * p] = (unsigned)spal[3 * k], by[3 * p + 1] = (unsigned)spal[3 * k + 1], by[3 * p + 2] = (unsigned)spal[3 * k + 2];
+                idx |= k << (8 * p);
+            }
+            u32x3 o;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) o[d] = by[4 * d] | (by[4 * d + 1] << 8) | (by[4 * d + 2] << 16) | (by[4 * d + 3] << 24);
+            *(u32x3*)(out + q * 12) = o;
+            if (index) *(unsigned*)(index + q * 4) = idx;
+        } else {
+            unsigned r = src[q * 3], g = src[q * 3 + 1], b = src[q * 3 + 2];
+            tone_px(r, g, b, l, grey);
+            const unsigned k = nearest<METRIC>(spal, K, (int)r, (int)g, (int)b);
+            out[q * 3] = (uint8_t)spal[3 * k], out[q * 3 + 1] = (uint8_t)spal[3 * k + 1], out[q * 3 + 2] = (uint8_t)spal[3 * k + 2];
+            if (index) index[q] = (uint8_t)k;
         }
-        u32x3 o;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) o[d] = by[4 * d] | (by[4 * d + 1] << 8) | (by[4 * d + 2] << 16) | (by[4 * d + 3] << 24);
-        *(u32x3*)(out + q * 12) = o;
-        if (index) *(unsigned*)(index + q * 4) = idx;
-    } else {
-        if (q >= total) return;
-        unsigned r = src[q * 3], g = src[q * 3 + 1], b = src[q * 3 + 2];
-        tone_px(r, g, b, l, grey);
-        const unsigned k = nearest<METRIC>(spal, K, (int)r, (int)g, (int)b);
-        out[q * 3] = (uint8_t)spal[3 * k], out[q * 3 + 1] = (uint8_t)spal[3 * k + 1], out[q * 3 + 2] = (uint8_t)spal[3 * k + 2];
-        if (index) index[q] = (uint8_t)k;
     }
 }
 
@@ -105,11 +106,11 @@ __global__ __launch_bounds__(256) void tone_kernel(const uint8_t* src, size_t to
     __shared__ uint8_t slut[768];
     stage_lut(lut, slut, 256);
     __syncthreads();
-    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (q >= total) return;
-    unsigned r = src[q * 3], g = src[q * 3 + 1], b = src[q * 3 + 2];
-    tone_px(r, g, b, lut ? slut : nullptr, grey);
-    out[q * 3] = (uint8_t)r, out[q * 3 + 1] = (uint8_t)g, out[q * 3 + 2] = (uint8_t)b;
+    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (size_t)gridDim.x * 256) {          // as palette_map_kernel walks
+        unsigned r = src[q * 3], g = src[q * 3 + 1], b = src[q * 3 + 2];
+        tone_px(r, g, b, lut ? slut : nullptr, grey);
+        out[q * 3] = (uint8_t)r, out[q * 3 + 1] = (uint8_t)g, out[q * 3 + 2] = (uint8_t)b;
+    }
 }
 
 // the exchange of a step needs the LDS writes only: the frame's own loads and stores stay in flight across it
@@ -220,6 +221,10 @@ __global__ __launch_bounds__(BAND) void palette_dither_kernel(const uint8_t* __r
     }
 }
 
+// 2^32 - 256 threads: a launch's threads per dimension are a 32-bit count, and 2^32 or more of them are not refused by the runtime
+// but cut to their low 32 bits (a batch of 65535 frames of 257 x 259 pixels then left every frame from the 1010th on unwritten)
+constexpr size_t MAP_MAX_BLOCKS = 0xffffff;
+
 const char* check_palette_shape(int n, int h, int w, int K) {
     if (n < 1 || n > 65535) return "n outside 1..65535";
     if (h < 1 || w < 1) return "height or width below 1";
@@ -242,8 +247,7 @@ int launch_palette_map_u8(const uint8_t* src, int n, int h, int w, const uint8_t
     const size_t total = (size_t)n * h * w;
     const bool vec = total % 4 == 0 && (((uintptr_t)src | (uintptr_t)out | (uintptr_t)index) & 3) == 0;
     const size_t blocks = (total / (vec ? 4 : 1) + 255) / 256;
-    if (blocks > 0x7fffffffull) { set_error("%s: n h w = %zu pixels are more than one launch takes", who, total); return ADAIN_EINVAL; }
-    const dim3 g((unsigned)blocks);
+    const dim3 g((unsigned)(blocks < MAP_MAX_BLOCKS ? blocks : MAP_MAX_BLOCKS));
     grey = grey ? 1 : 0;
     if (metric == 0) {
         if (vec) palette_map_kernel<0, true><<<g, 256, 0, s>>>(src, total, palette, K, lut, grey, out, index);
@@ -261,8 +265,7 @@ int launch_tone_u8(const uint8_t* src, int n, int h, int w, const uint8_t* lut, 
     if (!out) { set_error("%s: out is a null pointer", who); return ADAIN_EINVAL; }
     if (const char* bad = check_palette_shape(n, h, w, 1)) { set_error("%s: %s (n %d, %d x %d)", who, bad, n, h, w); return ADAIN_EINVAL; }
     const size_t total = (size_t)n * h * w, blocks = (total + 255) / 256;
-    if (blocks > 0x7fffffffull) { set_error("%s: n h w = %zu pixels are more than one launch takes", who, total); return ADAIN_EINVAL; }
-    tone_kernel<<<dim3((unsigned)blocks), 256, 0, s>>>(src, total, lut, grey ? 1 : 0, out);
+    tone_kernel<<<dim3((unsigned)(blocks < MAP_MAX_BLOCKS ? blocks : MAP_MAX_BLOCKS)), 256, 0, s>>>(src, total, lut, grey ? 1 : 0, out);
     return check_launch(who);
 }
 

@@ -36,8 +36,9 @@ __global__ __launch_bounds__(256) void bicubic_minmax_kernel(const float* __rest
     const float sy = (float)h0 / (float)hc, sx = (float)w0 / (float)wc;
     const int total = hc * wc;
     float lo = INFINITY, hi = -INFINITY;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int oy = i / wc, ox = i - oy * wc;
+    // unsigned: total may lie within one stride of 2^31 - 1, where an int index would wrap before it fails the test
+    for (unsigned u = blockIdx.x * blockDim.x + threadIdx.x; u < (unsigned)total; u += gridDim.x * blockDim.x) {
+        const int i = (int)u, oy = i / wc, ox = i - oy * wc;
         const float ry = sy * ((float)oy + 0.5f) - 0.5f, rx = sx * ((float)ox + 0.5f) - 0.5f;
         const float fy = floorf(ry), fx = floorf(rx);
         const int iy = (int)fy, ix = (int)fx;
@@ -99,9 +100,10 @@ __global__ __launch_bounds__(256) void strength_sum_kernel(const float* __restri
     if (hi > lo) {
         const float range = hi - lo;
         // block b owns the contiguous slice [b * per, (b + 1) * per): the partition depends only on (total, gridDim)
-        const int per = (total + gridDim.x - 1) / gridDim.x;
-        const int i0 = blockIdx.x * per, i1 = min(i0 + per, total);
-        for (int i = i0 + threadIdx.x; i < i1; i += 256) s += (double)((p[i] - lo) / range);
+        // (unsigned: the last slice's end and a lane's last step may pass 2^31 - 1 before they are clipped to total)
+        const unsigned per = ((unsigned)total + gridDim.x - 1) / gridDim.x;
+        const unsigned i0 = blockIdx.x * per, i1 = min(i0 + per, (unsigned)total);
+        for (unsigned i = i0 + threadIdx.x; i < i1; i += 256) s += (double)((p[i] - lo) / range);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
@@ -122,8 +124,8 @@ __global__ __launch_bounds__(256) void strength_apply_kernel(float* __restrict__
     }
     __syncthreads();
     const float lo = shf[0], hi = shf[1], mean = shf[2];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;      // unsigned: the last block's idle lanes may pass 2^31 - 1
+    if (i >= (unsigned)total) return;
     if (!(hi > lo)) {   // constant map -> zeros (test.py:141-143)
         p[i] = 0.f;
         return;
@@ -154,13 +156,13 @@ int launch_strength_map(const float* depth, int h0, int w0, int hc, int wc, floa
     const StrengthLayout l = strength_layout();
     if (int rc = check_workspace("strength_map", workspace, ws_bytes, l.total, 1)) return rc;
     const int total = hc * wc;
-    int blocks = (total + 255) / 256;
-    if (blocks > SM_BLOCKS) blocks = SM_BLOCKS;
+    const unsigned all_blocks = (unsigned)(((size_t)total + 255) / 256);
+    const int blocks = all_blocks > (unsigned)SM_BLOCKS ? SM_BLOCKS : (int)all_blocks;
     float* part = (float*)((char*)workspace + l.o_part);
     double* psum = (double*)((char*)workspace + l.o_psum);
     hipLaunchKernelGGL(bicubic_minmax_kernel, dim3(blocks), dim3(256), 0, s, depth, h0, w0, hc, wc, pmap, part);
     hipLaunchKernelGGL(strength_sum_kernel, dim3(blocks), dim3(256), 0, s, pmap, total, part, blocks, psum);
-    hipLaunchKernelGGL(strength_apply_kernel, dim3((total + 255) / 256), dim3(256), 0, s, pmap, total, part, blocks, psum, blocks, offset,
+    hipLaunchKernelGGL(strength_apply_kernel, dim3(all_blocks), dim3(256), 0, s, pmap, total, part, blocks, psum, blocks, offset,
                        prominence);
     return check_launch("strength_map");
 }
@@ -185,8 +187,10 @@ __device__ __forceinline__ void store_quad(float* __restrict__ row, int x, int w
 template <bool SAMEW>
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, int hi,
                                                               int wi, int ho, int wo, int vec) {
-    const int x = (blockIdx.x * 64 + threadIdx.x) * 4, oy = blockIdx.y * 4 + threadIdx.y;
-    if (x >= wo || oy >= ho) return;
+    const unsigned ux = (blockIdx.x * 64 + threadIdx.x) * 4;      // unsigned: the last block's idle lanes may pass 2^31 - 1
+    const int oy = blockIdx.y * 4 + threadIdx.y;
+    if (ux >= (unsigned)wo || oy >= ho) return;
+    const int x = (int)ux;
     const float sy = (float)hi / (float)ho, sx = (float)wi / (float)wo;
     const float ry = fmaxf(sy * ((float)oy + 0.5f) - 0.5f, 0.f);
     const int y0 = min((int)ry, hi - 1), y1 = y0 + (y0 < hi - 1 ? 1 : 0);
@@ -222,8 +226,10 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
 
 __global__ __launch_bounds__(256) void resize_nearest_kernel(const float* __restrict__ in, float* __restrict__ out, int hi,
                                                              int wi, int ho, int wo, int vec) {
-    const int x = (blockIdx.x * 64 + threadIdx.x) * 4, oy = blockIdx.y * 4 + threadIdx.y;
-    if (x >= wo || oy >= ho) return;
+    const unsigned ux = (blockIdx.x * 64 + threadIdx.x) * 4;      // unsigned: the last block's idle lanes may pass 2^31 - 1
+    const int oy = blockIdx.y * 4 + threadIdx.y;
+    if (ux >= (unsigned)wo || oy >= ho) return;
+    const int x = (int)ux;
     const float sy = (float)hi / (float)ho, sx = (float)wi / (float)wo;
     const int y = min((int)floorf((float)oy * sy), hi - 1);
     const float* __restrict__ p = in + (size_t)blockIdx.z * hi * wi + (unsigned)(y * wi);
@@ -282,8 +288,8 @@ __global__ __launch_bounds__(256) void mask_composite_kernel(const float* __rest
     const unsigned plane = blockIdx.y, img = plane / (unsigned)c, ch = plane - img * (unsigned)c;
     const size_t base = (size_t)plane * hw;
     const float* __restrict__ mp = mask + ((size_t)(mask_n == 1 ? 0u : img) * mask_c + (mask_c == 1 ? 0u : ch)) * hw;
-    const int i = (blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
-    if (i >= hw) return;
+    const unsigned i = (blockIdx.x * 256 + threadIdx.x) * (VEC ? 4u : 1u);      // unsigned: idle lanes may pass 2^31 - 1
+    if (i >= (unsigned)hw) return;
     if (VEC) {
         const f32x4 m = *(const f32x4*)(mp + i), a = *(const f32x4*)(content + base + i), b = *(const f32x4*)(sty + base + i);
         f32x4 r;
@@ -336,8 +342,8 @@ __global__ __launch_bounds__(256) void quantize_u8_rgb4_kernel(const float* __re
 
 __global__ __launch_bounds__(256) void quantize_u8_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, int c, int hw) {
     // generic channel count: a thread owns one pixel of image blockIdx.y
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= hw) return;
+    const unsigned pix = blockIdx.x * 256 + threadIdx.x;      // unsigned: the last block's idle lanes may pass 2^31 - 1
+    if (pix >= (unsigned)hw) return;
     const float* __restrict__ p = in + (size_t)blockIdx.y * c * hw + pix;
     uint8_t* __restrict__ o = out + ((size_t)blockIdx.y * hw + pix) * c;
     for (int ch = 0; ch < c; ++ch) o[ch] = (uint8_t)quant1(p[(size_t)ch * hw]);
@@ -350,7 +356,7 @@ int launch_quantize_u8(const float* in, uint8_t* out, int n, int c, int h, int w
     if (c == 3 && hw % 4 == 0 && aligned16(in) && ((uintptr_t)out & 3) == 0)
         hipLaunchKernelGGL(quantize_u8_rgb4_kernel, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, s, in, out, hw);
     else
-        hipLaunchKernelGGL(quantize_u8_kernel, dim3((hw + 255) / 256, n), dim3(256), 0, s, in, out, c, hw);
+        hipLaunchKernelGGL(quantize_u8_kernel, dim3((unsigned)(((size_t)hw + 255) / 256), n), dim3(256), 0, s, in, out, c, hw);
     return check_launch("quantize_u8");
 }
 
@@ -373,8 +379,8 @@ __global__ __launch_bounds__(256) void u8_to_f32_rgb4_kernel(const uint8_t* __re
 }
 
 __global__ __launch_bounds__(256) void u8_to_f32_kernel(const uint8_t* __restrict__ in, float* __restrict__ out, int c, int hw) {
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= hw) return;
+    const unsigned pix = blockIdx.x * 256 + threadIdx.x;      // unsigned: the last block's idle lanes may pass 2^31 - 1
+    if (pix >= (unsigned)hw) return;
     const uint8_t* __restrict__ p = in + ((size_t)blockIdx.y * hw + pix) * c;
     float* __restrict__ o = out + (size_t)blockIdx.y * c * hw + pix;
     for (int ch = 0; ch < c; ++ch) o[(size_t)ch * hw] = __fdiv_rn((float)p[ch], 255.0f);
@@ -387,7 +393,7 @@ int launch_u8_to_f32(const uint8_t* in, float* out, int n, int c, int h, int w, 
     if (c == 3 && hw % 4 == 0 && aligned16(out) && ((uintptr_t)in & 3) == 0)
         hipLaunchKernelGGL(u8_to_f32_rgb4_kernel, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, s, in, out, hw);
     else
-        hipLaunchKernelGGL(u8_to_f32_kernel, dim3((hw + 255) / 256, n), dim3(256), 0, s, in, out, c, hw);
+        hipLaunchKernelGGL(u8_to_f32_kernel, dim3((unsigned)(((size_t)hw + 255) / 256), n), dim3(256), 0, s, in, out, c, hw);
     return check_launch("u8_to_f32");
 }
 
@@ -534,7 +540,8 @@ __global__ __launch_bounds__(256) void mask_to_f32_kernel(const uint8_t* __restr
 }
 
 int launch_mask_to_f32(const uint8_t* in, float* out, size_t total, hipStream_t s) {
-    if (total < 1 || total >= ((size_t)1 << 39)) { set_error("mask_to_f32: bad size"); return ADAIN_EINVAL; }
+    // a thread per element, and a launch's threads per dimension are a 32-bit count
+    if (total < 1 || total > 0xffffff00ULL) { set_error("mask_to_f32: bad size (1 .. 2^32 - 256 elements)"); return ADAIN_EINVAL; }
     hipLaunchKernelGGL(mask_to_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, total);
     return check_launch("mask_to_f32");
 }
@@ -664,10 +671,10 @@ __global__ __launch_bounds__(256) void warp_blend_u8_kernel(const uint8_t* __res
                                                             const float* __restrict__ flow, uint8_t* __restrict__ out, int h, int w,
                                                             int c, float alpha, float one_minus_alpha) {
     const int total = h * w;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int y = i / w, x = i - y * w;
-    const WarpTap t = warp_tap(x, y, flow[i], flow[total + i], h, w, c);
+    const unsigned u = blockIdx.x * 256 + threadIdx.x;      // unsigned: the last block's idle lanes may pass 2^31 - 1
+    if (u >= (unsigned)total) return;
+    const int i = (int)u, y = i / w, x = i - y * w;
+    const WarpTap t = warp_tap(x, y, flow[i], flow[(size_t)total + i], h, w, c);
     for (int ch = 0; ch < c; ++ch)
         out[(size_t)i * c + ch] = (uint8_t)warp_blend1(prev, t, ch, cur[(size_t)i * c + ch], alpha, one_minus_alpha);
 }
@@ -681,7 +688,7 @@ int launch_warp_blend_u8(const uint8_t* cur, const uint8_t* prev, const float* f
         hipLaunchKernelGGL(warp_blend_u8_rgb4_kernel, dim3((total / 4 + 255) / 256), dim3(256), 0, s, cur, prev, flow, out, h, w, alpha,
                            one_minus_alpha);
     else
-        hipLaunchKernelGGL(warp_blend_u8_kernel, dim3((total + 255) / 256), dim3(256), 0, s, cur, prev, flow, out, h, w, c, alpha,
+        hipLaunchKernelGGL(warp_blend_u8_kernel, dim3((unsigned)(((size_t)total + 255) / 256)), dim3(256), 0, s, cur, prev, flow, out, h, w, c, alpha,
                            one_minus_alpha);
     return check_launch("warp_blend_u8");
 }
@@ -728,8 +735,10 @@ __device__ __forceinline__ uint8_t sat_u8_rne(float v) {
 template <int MODE>
 __global__ __launch_bounds__(256) void resize_area_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int hi, int wi,
                                                              int c, int ho, int wo, double scale_x, double scale_y, int isx, int isy) {
-    const int dx = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
-    if (dx >= wo || dy >= ho) return;
+    const unsigned udx = blockIdx.x * 64 + threadIdx.x;      // unsigned: the last block's idle lanes may pass 2^31 - 1
+    const int dy = blockIdx.y * 4 + threadIdx.y;
+    if (udx >= (unsigned)wo || dy >= ho) return;
+    const int dx = (int)udx;
     const uint8_t* __restrict__ src = in + (size_t)blockIdx.z * hi * wi * c;
     uint8_t* __restrict__ dst = out + ((size_t)blockIdx.z * ho * wo + (size_t)dy * wo + dx) * c;
     if constexpr (MODE == 0) {
@@ -771,11 +780,12 @@ __global__ __launch_bounds__(256) void resize_area_tab_u8_kernel(const uint8_t* 
     using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
     __shared__ AreaTaps tx_s[64], ty_s[16];
     const int tid = threadIdx.y * 64 + threadIdx.x;
-    const int dx = blockIdx.x * 64 + threadIdx.x;
-    if (tid < 64) tx_s[tid] = area_taps(min(blockIdx.x * 64 + tid, wo - 1), wi, scale_x);
+    const unsigned udx = blockIdx.x * 64 + threadIdx.x;      // unsigned: the last block's idle lanes may pass 2^31 - 1
+    const int dx = (int)udx;                                 // used by live lanes only (udx < wo below)
+    if (tid < 64) tx_s[tid] = area_taps((int)min(blockIdx.x * 64 + (unsigned)tid, (unsigned)(wo - 1)), wi, scale_x);
     else if (tid < 80) ty_s[tid - 64] = area_taps(min(blockIdx.y * 16 + (tid - 64), ho - 1), hi, scale_y);
     __syncthreads();
-    if (dx >= wo) return;
+    if (udx >= (unsigned)wo) return;
     const AreaTaps tx = tx_s[threadIdx.x];
     const uint8_t* __restrict__ src = in + (size_t)blockIdx.z * hi * wi * c;
 #pragma unroll 1
@@ -888,8 +898,10 @@ __device__ __forceinline__ AreaLin area_linear(int d, int ssize, double inv_scal
 
 __global__ __launch_bounds__(256) void resize_area_linear_u8_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int hi,
                                                                     int wi, int c, int ho, int wo, double inv_x, double inv_y) {
-    const int dx = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
-    if (dx >= wo || dy >= ho) return;
+    const unsigned udx = blockIdx.x * 64 + threadIdx.x;      // unsigned: the last block's idle lanes may pass 2^31 - 1
+    const int dy = blockIdx.y * 4 + threadIdx.y;
+    if (udx >= (unsigned)wo || dy >= ho) return;
+    const int dx = (int)udx;
     const uint8_t* __restrict__ src = in + (size_t)blockIdx.z * hi * wi * c;
     uint8_t* __restrict__ dst = out + ((size_t)blockIdx.z * ho * wo + (size_t)dy * wo + dx) * c;
     const AreaLin ax = area_linear(dx, wi, inv_x, 1. / inv_x, true), ay = area_linear(dy, hi, inv_y, 1. / inv_y, false);
@@ -903,7 +915,11 @@ __global__ __launch_bounds__(256) void resize_area_linear_u8_kernel(const uint8_
 
 int launch_resize_area_u8(const uint8_t* in, uint8_t* out, int n, int hi, int wi, int c, int ho, int wo, hipStream_t s) {
     if (n < 1 || hi < 1 || wi < 1 || c < 1 || ho < 1 || wo < 1) { set_error("resize_area_u8: bad shape"); return ADAIN_EINVAL; }
-    if ((size_t)hi * wi * c >= 0x7fffffffULL || n > 65535 || (ho + 3) / 4 > 65535) { set_error("resize_area_u8: frame or batch too large"); return ADAIN_EINVAL; }
+    if ((size_t)hi * wi * c >= 0x7fffffffULL || n > 65535 || ho > 4 * 65535) {
+        set_error("resize_area_u8: frame (2^31 - 1 bytes), batch (65535) or output height (262140) too large");
+        return ADAIN_EINVAL;
+    }
+    const unsigned gx = (unsigned)(((size_t)wo + 63) / 64);
     if (ho == hi && wo == wi) {
         if (hipMemcpyAsync(out, in, (size_t)n * hi * wi * c, hipMemcpyDeviceToDevice, s) != hipSuccess) {
             set_error("resize_area_u8: copy failed: %s", hipGetErrorString(hipGetLastError()));
@@ -911,7 +927,7 @@ int launch_resize_area_u8(const uint8_t* in, uint8_t* out, int n, int hi, int wi
         }
         return 0;
     }
-    const dim3 g((wo + 63) / 64, (ho + 3) / 4, n), b(64, 4);
+    const dim3 g(gx, (ho + 3) / 4, n), b(64, 4);
     if (ho > hi || wo > wi) {       // an enlarged axis: the fixed-point linear path in area mode
         hipLaunchKernelGGL(resize_area_linear_u8_kernel, g, b, 0, s, in, out, hi, wi, c, ho, wo, (double)wo / wi, (double)ho / hi);
         return check_launch("resize_area_u8");
@@ -922,10 +938,10 @@ int launch_resize_area_u8(const uint8_t* in, uint8_t* out, int n, int hi, int wi
     const bool fast = fabs(scale_x - isx) < 2.220446049250313e-16 && fabs(scale_y - isy) < 2.220446049250313e-16;
     const size_t total_bytes = (size_t)n * hi * wi * c;
     if (!fast && (ho + 15) / 16 <= 65535 && c == 3 && scale_x < 3.0 && ((uintptr_t)in & 3) == 0)        // at most 4 taps across
-        hipLaunchKernelGGL(resize_area_tab_u8_kernel<true>, dim3((wo + 63) / 64, (ho + 15) / 16, n), b, 0, s, in, out, hi, wi, c, ho, wo, scale_x,
+        hipLaunchKernelGGL(resize_area_tab_u8_kernel<true>, dim3(gx, (ho + 15) / 16, n), b, 0, s, in, out, hi, wi, c, ho, wo, scale_x,
                            scale_y, total_bytes);
     else if (!fast && (ho + 15) / 16 <= 65535)
-        hipLaunchKernelGGL(resize_area_tab_u8_kernel<false>, dim3((wo + 63) / 64, (ho + 15) / 16, n), b, 0, s, in, out, hi, wi, c, ho, wo, scale_x,
+        hipLaunchKernelGGL(resize_area_tab_u8_kernel<false>, dim3(gx, (ho + 15) / 16, n), b, 0, s, in, out, hi, wi, c, ho, wo, scale_x,
                            scale_y, total_bytes);
     else if (!fast) hipLaunchKernelGGL(resize_area_u8_kernel<0>, g, b, 0, s, in, out, hi, wi, c, ho, wo, scale_x, scale_y, 0, 0);
     else if (isx == 2 && isy == 2 && c == 3 && wi % 8 == 0 && wo * 2 == wi && ((uintptr_t)in & 3) == 0 && ((uintptr_t)out & 3) == 0)
@@ -940,28 +956,30 @@ int launch_resize_area_u8(const uint8_t* in, uint8_t* out, int n, int hi, int wi
 __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int R, int C) {
     __shared__ float tile[32][33];
     const int img = blockIdx.y;
-    const int tiles_c = (C + 31) / 32;
-    const int c0 = (blockIdx.x % tiles_c) * 32, r0 = (blockIdx.x / tiles_c) * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    // unsigned: R or C may lie within a tile of 2^31 - 1, where an idle lane's row or column passes it
+    const unsigned tiles_c = ((unsigned)C + 31) / 32;
+    const unsigned c0 = (blockIdx.x % tiles_c) * 32, r0 = (blockIdx.x / tiles_c) * 32;
+    const unsigned tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const float* __restrict__ src = in + (size_t)img * R * C;
     float* __restrict__ dst = out + (size_t)img * R * C;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int r = r0 + ty + k * 8, cc = c0 + tx;
-        if (r < R && cc < C) tile[ty + k * 8][tx] = src[(size_t)r * C + cc];
+        const unsigned r = r0 + ty + k * 8, cc = c0 + tx;
+        if (r < (unsigned)R && cc < (unsigned)C) tile[ty + k * 8][tx] = src[(size_t)r * C + cc];
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int cc = c0 + ty + k * 8, r = r0 + tx;
-        if (r < R && cc < C) dst[(size_t)cc * R + r] = tile[tx][ty + k * 8];
+        const unsigned cc = c0 + ty + k * 8, r = r0 + tx;
+        if (r < (unsigned)R && cc < (unsigned)C) dst[(size_t)cc * R + r] = tile[tx][ty + k * 8];
     }
 }
 
 static int launch_transpose(const float* in, float* out, int n, int R, int C, hipStream_t s, const char* what) {
     if (n < 1 || R < 1 || C < 1) { set_error("%s: bad shape", what); return ADAIN_EINVAL; }
-    const size_t tiles = (size_t)((C + 31) / 32) * ((R + 31) / 32);
-    if (tiles > 0x7fffffffULL || n > 65535) { set_error("%s: grid too large", what); return ADAIN_EINVAL; }
+    const size_t tiles = (((size_t)C + 31) / 32) * (((size_t)R + 31) / 32);
+    // 256 threads a tile, and a launch's threads per dimension are a 32-bit count (more are cut to their low 32 bits, not refused)
+    if (tiles > 0xffffffULL || n > 65535) { set_error("%s: grid too large (more than 16777215 tiles of 32 x 32 per image, or 65535 images)", what); return ADAIN_EINVAL; }
     hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)tiles, n), dim3(256), 0, s, in, out, R, C);
     return check_launch(what);
 }

@@ -28,7 +28,7 @@ __global__ __launch_bounds__(MS_THREADS) void mean_std_nhwc_partial(const float*
     const float* __restrict__ base = feat + (size_t)img * hw * c;
     double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
     if (row < rows) {
-        const int step = nblk * rows;
+        const unsigned step = nblk * rows, uhw = (unsigned)hw;          // unsigned: p + 3 step may pass 2^31 - 1 before it fails the test
         auto add = [&](const f32x4 v) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -37,15 +37,15 @@ __global__ __launch_bounds__(MS_THREADS) void mean_std_nhwc_partial(const float*
                 q[k] += d * d;
             }
         };
-        auto at = [&](int p) { return *(const f32x4*)(base + (size_t)p * c + col * 4); };
-        int p = b * rows + row;
+        auto at = [&](unsigned p) { return *(const f32x4*)(base + (size_t)p * c + col * 4); };
+        unsigned p = b * rows + row;
         // four loads in flight per thread, summed in pixel order (the order of a plain loop: results unchanged bit for bit);
         // one dependent 16-byte load per iteration left the kernel latency-bound (1 workgroup per CU: 1.9 TB/s)
-        for (; p + 3 * step < hw; p += 4 * step) {
+        for (; p + 3 * step < uhw; p += 4 * step) {
             const f32x4 v0 = at(p), v1 = at(p + step), v2 = at(p + 2 * step), v3 = at(p + 3 * step);
             add(v0); add(v1); add(v2); add(v3);
         }
-        for (; p < hw; p += step) add(at(p));
+        for (; p < uhw; p += step) add(at(p));
     }
     // combine the row groups through LDS in a fixed order
     __shared__ double sh[MS_THREADS * 8];
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(MS_THREADS) void mean_std_nchw_kernel(const float* 
     const size_t plane = blockIdx.x;
     const float* __restrict__ p = feat + plane * hw;
     double s = 0, q = 0;
-    for (int i = threadIdx.x; i < hw; i += MS_THREADS) {
+    for (unsigned i = threadIdx.x; i < (unsigned)hw; i += MS_THREADS) {          // unsigned: the last step may pass 2^31 - 1
         const double d = (double)p[i];
         s += d;
         q += d * d;
@@ -138,11 +138,11 @@ __global__ __launch_bounds__(MS_THREADS) void mean_std_nchw_kernel(const float* 
 
 static int nhwc_blocks(int c, int hw) {
     const int rows = MS_THREADS / (c >> 2);
-    int nblk = (hw + rows * 16 - 1) / (rows * 16);   // >= 16 row groups of work per block
+    long long nblk = ((long long)hw + rows * 16 - 1) / (rows * 16);   // >= 16 row groups of work per block
     constexpr int cap = 256;
     if (nblk > cap) nblk = cap;
     if (nblk < 1) nblk = 1;
-    return nblk;
+    return (int)nblk;
 }
 
 // The workspace is one block, the NHWC form's partial sums [n][nblk][c][2] double: nothing to lay out, and its size is not rounded up
@@ -156,6 +156,12 @@ size_t mean_std_workspace_bytes(int nhwc, int n, int c, int hw) {
 int launch_mean_std(const float* feat, int nhwc, int n, int c, int hw, float eps, float* mean, float* std_,
                     void* workspace, size_t ws_bytes, hipStream_t s) {
     if (n < 1 || c < 1 || hw < 1) { set_error("mean_std: bad shape n=%d c=%d hw=%d", n, c, hw); return ADAIN_EINVAL; }
+    // the blends' limit; with it the NCHW form's n c planes of 256 threads stay below the 2^32 threads of a launch for hw >= 128
+    if ((size_t)n * c * hw >= 0x7fffffffULL) { set_error("mean_std: more than 2^31 elements per call"); return ADAIN_EINVAL; }
+    if (nhwc ? n > 65535 : (size_t)n * c > 0xffffffULL) {
+        set_error("mean_std: more than 65535 images (NHWC) or 16777215 planes (NCHW) per call");
+        return ADAIN_EINVAL;
+    }
     if (nhwc) {
         if ((c & 3) || (c >> 2) > MS_THREADS) { set_error("mean_std(NHWC): c=%d must be a multiple of 4 and <= 1024", c); return ADAIN_EINVAL; }
         const int nblk = nhwc_blocks(c, hw);

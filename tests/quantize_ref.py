@@ -17,16 +17,17 @@ import numpy as np
 AXIS_ORDER = (1, 0, 2)          # g, then r, then b
 
 
-def cells_of(pixels):
-    """pixels: an iterable of (r, g, b) -> {cell: [w, Sr, Sg, Sb, Q]}."""
-    cells = {}
+def cells_of(pixels, weight=1, cells=None):
+    """pixels: an iterable of (r, g, b), each counted ``weight`` times (a whole number: the moments are integers, so a pixel seen
+    ``weight`` times adds ``weight`` times its own) -> {cell: [w, Sr, Sg, Sb, Q]}, added into ``cells`` when given."""
+    cells = {} if cells is None else cells
     for r, g, b in pixels:
         m = cells.setdefault((r >> 3, g >> 3, b >> 3), [0, 0, 0, 0, 0])
-        m[0] += 1
-        m[1] += r
-        m[2] += g
-        m[3] += b
-        m[4] += r * r + g * g + b * b
+        m[0] += weight
+        m[1] += weight * r
+        m[2] += weight * g
+        m[3] += weight * b
+        m[4] += weight * (r * r + g * g + b * b)
     return cells
 
 
@@ -66,9 +67,9 @@ class Box:
         return [(2 * s + self.w) // (2 * self.w) for s in (self.sr, self.sg, self.sb)]
 
 
-def boxes_of(pixels, K):
-    """The boxes in index order."""
-    boxes = [Box(sorted(cells_of(pixels).items()))]
+def boxes_of(pixels, K, cells=None):
+    """The boxes in index order; ``cells``: the moments when the caller has them already (``pixels`` is then not read)."""
+    boxes = [Box(sorted((cells_of(pixels) if cells is None else cells).items()))]
     while len(boxes) < K:
         best = None
         for i, b in enumerate(boxes):
@@ -87,6 +88,20 @@ def palette(frames, K):
     """frames: uint8 [..., 3], all of it one palette's pixels -> (uint8 [256,3] with zeros from `used` on, used)."""
     px = np.asarray(frames).reshape(-1, 3).tolist()
     boxes = boxes_of(px, K)
+    out = np.zeros((256, 3), dtype=np.uint8)
+    for i, b in enumerate(boxes):
+        out[i] = b.entry()
+    return out, len(boxes)
+
+
+def palette_weighted(frames, weights, K):
+    """The palette of a clip in which frames[i] (uint8 [..., 3]) occurs weights[i] times, without building the clip: -> as ``palette``."""
+    cells = {}
+    for f, m in zip(frames, weights):
+        assert int(m) == m and m >= 0
+        if m:
+            cells_of(np.asarray(f).reshape(-1, 3).tolist(), int(m), cells)
+    boxes = boxes_of(None, K, cells)
     out = np.zeros((256, 3), dtype=np.uint8)
     for i, b in enumerate(boxes):
         out[i] = b.entry()

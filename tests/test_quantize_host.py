@@ -44,6 +44,23 @@ def test_split_axis_order():
     assert cells([(r, g, 0) for r in (0, 8, 16) for g in (0, 8)]).axis() == 0          # the longest side wins before the order
 
 
+@pytest.mark.parametrize("K", (2, 16, 256))
+def test_weights_are_repeated_frames(K):
+    """``palette_weighted``: a frame that occurs m times adds m times its integer moments - the palette of the clip that is built
+    out, in any order, and of weights (1, 1, 1) the plain one."""
+    frames = C.gradient(3, 19, 23, 5)
+    weights = (2, 3, 1)
+    clip = np.stack([frames[i] for i in (1, 0, 1, 2, 0, 1)])
+    want = Q.palette(clip, K)
+    got = Q.palette_weighted(frames, weights, K)
+    assert got[1] == want[1] and np.array_equal(got[0], want[0])
+    one = Q.palette_weighted(frames, (1, 1, 1), K)
+    assert one[1] == Q.palette(frames, K)[1] and np.array_equal(one[0], Q.palette(frames, K)[0])
+    assert not np.array_equal(got[0], one[0]) or K == 256          # the weights matter where the boxes are cut
+    zero = Q.palette_weighted(frames, (1, 0, 1), K)
+    assert np.array_equal(zero[0], Q.palette(frames[[0, 2]], K)[0])
+
+
 # ---- the package's host form is the restatement ----------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def generated():
