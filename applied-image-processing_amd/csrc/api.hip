@@ -653,6 +653,14 @@ int adain_ssim_window(float* out) {
     ssim_window(out);
     return ADAIN_OK;
 }
+// their gradient for train.py's loss (utils/loss_utils.py l1_loss, ssim under autograd): the launcher refuses everything itself
+int adain_image_metrics_grad_f32_bytes(int n, int c, int h, int w, int with_grad_b, size_t* workspace_bytes) {
+    return image_metrics_grad_f32_bytes(n, c, h, w, with_grad_b, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_image_metrics_grad_f32(const float* a, const float* b, int n, int c, int h, int w, const double* weights, float* grad_a, float* grad_b, void* workspace,
+                                 size_t workspace_bytes, adain_stream_t stream) {
+    return launch_image_metrics_grad_f32(a, b, n, c, h, w, weights, grad_a, grad_b, workspace, workspace_bytes, (hipStream_t)stream);
+}
 
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;

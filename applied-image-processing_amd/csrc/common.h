@@ -268,6 +268,10 @@ int launch_image_metrics_u8(const uint8_t* a, const uint8_t* b, int n, int h, in
 int launch_image_metrics_f32(const float* a, const float* b, int n, int c, int h, int w, double* out, float* ssim_map, void* workspace, size_t workspace_bytes,
                              hipStream_t s);
 void ssim_window(float out[11]);
+// the gradient of the float32 scores: weights [n][3] = upstream d/d{ssim, mse, l1} per frame; grad_b may be null
+int image_metrics_grad_f32_bytes(int n, int c, int h, int w, int with_grad_b, size_t* workspace_bytes);
+int launch_image_metrics_grad_f32(const float* a, const float* b, int n, int c, int h, int w, const double* weights, float* grad_a, float* grad_b,
+                                  void* workspace, size_t workspace_bytes, hipStream_t s);
 
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);

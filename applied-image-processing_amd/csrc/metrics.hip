@@ -27,6 +27,26 @@
 //            the waves in index order.  One partial record per tile goes into the workspace; every record is written by every call.
 //   finish : a wave per frame adds the frame's partial records in index order and writes the frame's double[4].
 // No float atomics, spin-waits or flags: a frame's record is a function of its pixels alone.
+//
+// The gradient (adain_image_metrics_grad_f32: what autograd hands back through train.py's (1 - lambda) l1_loss + lambda (1 - ssim)),
+// restated in float64 in tests/metrics_grad_ref.py.  With A = 2 mu1 mu2 + C1, B = 2 s12 + C2, D = mu1^2 + mu2^2 + C1, E = s1 + s2 + C2,
+// map = A B / (D E), the map's derivatives by the five window statistics are
+//      d_mu1 = 2 mu2 (B - A) / (D E) - map (2 mu1 / D - 2 mu1 / E),   d_e11 = d_e22 = -map / E,   d_e12 = 2 A / (D E)
+// (d_mu2: mu1 and mu2 swapped), and because the window is symmetric and the padding is zeros, the convolution is its own adjoint:
+//      d ssim / d x = (conv(d_mu1) + 2 x conv(d_e11) + y conv(d_e12)) / count,
+// to which mse adds 2 (x - y) / count and l1 sign(x - y) / count, sign(0) = 0.  The call recomputes the statistics from a and b.
+//   planes  : the tile pass above with another tail: in place of the records it writes the derivative planes of its samples into the
+//             workspace, float32 in the inputs' layout: d_mu1, d_e11, d_e12, and for the gradient of b d_mu2, d_e22 as well.  They are
+//             written as p = A / D, q = B / E, d_mu1 = 2 ((mu2 q - mu1 p q) / D - (mu2 p - mu1 p q) / E), d_e11 = -(p q) / E, d_e12 =
+//             2 p / E: A, B, D, E, p and q are the same numbers with the inputs swapped, and with x == y p = q = 1, so d_mu1 = 0 and
+//             d_e12 = -2 d_e11 exactly.
+//   combine : the same tile geometry; stages three planes with a halo of 5 (zeros outside the frame), row pass, column pass, then
+//             grad = ((c_mu + (2 x) c_11) + y c_12) (float)(w_ssim / count) + (x - y) (float)(2 w_mse / count) + sign (float)(w_l1 / count).
+//             The gradient of b is a second pass over d_mu2, d_e22, d_e12 with the inputs swapped.
+// Held: a frame's gradient bits are a function of its two frames and its three weights alone (not of n, the frame's index, the stream
+// or what the workspace held: every plane sample a combine pass reads was written by the same call's planes pass); a frame whose
+// weights are all zero gets zeros of either sign (a zero ssim weight skips both passes for the frame); grad_b(a, b) is bit for bit
+// grad_a(b, a), and grad_a is the same with and without grad_b; equal frames get exactly zero from the ssim term.
 #include "common.h"
 
 namespace adain {
@@ -67,7 +87,16 @@ struct TileArgs {
     Partial* partials;        // [n][tiles]
     int planes, H, Wp;        // of one frame
     int tiles_x, tiles_y;     // of one plane
+    // the planes tail only
+    const double* weights;    // [n][3]
+    float* dplanes;           // plane j of the derivatives starts dplane_pitch floats behind plane j - 1
+    size_t dplane_pitch;
 };
+
+// what the tile pass leaves: the partial records of the scores, or the derivative planes for the gradient of a, or of a and b
+constexpr int TAIL_RECORDS = 0, TAIL_PLANES_A = 3, TAIL_PLANES_AB = 5;
+// the planes' order in the workspace
+constexpr int P_MU1 = 0, P_E11 = 1, P_E12 = 2, P_MU2 = 3, P_E22 = 4;
 
 __device__ __forceinline__ float sample(const uint8_t* p, size_t i) { return (float)p[i] / 255.0f; }
 __device__ __forceinline__ float sample(const float* p, size_t i) { return p[i]; }
@@ -78,11 +107,37 @@ __device__ __forceinline__ V wave_sum(V v) {
     return v;
 }
 
-// grid (planes * tiles_y * tiles_x, n); CS: the plan's tap stride cs, a constant of the instantiation
-template <class T, int CS>
+// column pass of J quantities: rows r0 .. r0 + 3 of column c, from the row pass's results
+template <int J>
+__device__ __forceinline__ void column_pass(const float (*row)[STAGE_Y][TILE_X], int c, int r0, float (&q)[J][ROWS_PER_THREAD]) {
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+#pragma unroll
+        for (int o = 0; o < ROWS_PER_THREAD; ++o) q[j][o] = 0.0f;
+#pragma unroll
+    for (int r = 0; r < ROWS_PER_THREAD + WIN - 1; ++r)
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            const float v = row[j][r0 + r][c];
+#pragma unroll
+            for (int o = 0; o < ROWS_PER_THREAD; ++o)
+                if (r - o >= 0 && r - o < WIN) q[j][o] = fmaf(SSIM_WINDOW[r - o], v, q[j][o]);
+        }
+}
+
+// the map's derivative by one input's window mean: `mine` that input's mean, `other` the other's
+__device__ __forceinline__ float d_mean(float mine, float other, float p, float q, float pq, float D, float E) {
+    return 2.0f * ((other * q - mine * pq) / D - (other * p - mine * pq) / E);
+}
+
+// grid (planes * tiles_y * tiles_x, n); CS: the plan's tap stride cs, a constant of the instantiation; TAIL: what it leaves
+template <class T, int CS, int TAIL>
 __global__ __launch_bounds__(THREADS) void metrics_tile_kernel(TileArgs g) {
     __shared__ Shared sh;
     const int t = threadIdx.x;
+    if constexpr (TAIL != TAIL_RECORDS) {
+        if (g.weights[(size_t)blockIdx.y * 3] == 0.0) return;          // the frame's ssim weight: no combine pass reads its planes
+    }
     const int per_plane = g.tiles_x * g.tiles_y;
     const int plane = blockIdx.x / per_plane, tile = blockIdx.x % per_plane;
     const int x0 = (tile % g.tiles_x) * TILE_X, y0 = (tile / g.tiles_x) * TILE_Y;
@@ -122,19 +177,7 @@ __global__ __launch_bounds__(THREADS) void metrics_tile_kernel(TileArgs g) {
     // column pass: rows r0 .. r0 + 3 of column c
     const int c = t % TILE_X, r0 = (t / TILE_X) * ROWS_PER_THREAD;
     float q[5][ROWS_PER_THREAD];
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-#pragma unroll
-        for (int o = 0; o < ROWS_PER_THREAD; ++o) q[j][o] = 0.0f;
-#pragma unroll
-    for (int r = 0; r < ROWS_PER_THREAD + WIN - 1; ++r)
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const float v = sh.row[j][r0 + r][c];
-#pragma unroll
-            for (int o = 0; o < ROWS_PER_THREAD; ++o)
-                if (r - o >= 0 && r - o < WIN) q[j][o] = fmaf(SSIM_WINDOW[r - o], v, q[j][o]);
-        }
+    column_pass<5>(sh.row, c, r0, q);
 
     double ssim = 0.0;
     uint32_t se_i = 0, ae_i = 0;
@@ -147,7 +190,20 @@ __global__ __launch_bounds__(THREADS) void metrics_tile_kernel(TileArgs g) {
         const float mu1 = q[0][o], mu2 = q[1][o];
         const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
         const float s1 = q[2][o] - mu1_sq, s2 = q[3][o] - mu2_sq, s12 = q[4][o] - mu12;
-        const float value = ((2.0f * mu12 + C1) * (2.0f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
+        const float A = 2.0f * mu12 + C1, B = 2.0f * s12 + C2, D = mu1_sq + mu2_sq + C1, E = s1 + s2 + C2;
+        if constexpr (TAIL != TAIL_RECORDS) {
+            const float p = A / D, pe = B / E, pq = p * pe;
+            float* out = g.dplanes + plane_at + (size_t)y * g.Wp + x;
+            out[P_MU1 * g.dplane_pitch] = d_mean(mu1, mu2, p, pe, pq, D, E);
+            out[P_E11 * g.dplane_pitch] = -pq / E;
+            out[P_E12 * g.dplane_pitch] = (2.0f * p) / E;
+            if constexpr (TAIL == TAIL_PLANES_AB) {
+                out[P_MU2 * g.dplane_pitch] = d_mean(mu2, mu1, p, pe, pq, D, E);
+                out[P_E22 * g.dplane_pitch] = -pq / E;
+            }
+            continue;
+        }
+        const float value = (A * B) / (D * E);
         if (g.map) g.map[plane_at + (size_t)y * g.Wp + x] = value;
         ssim += (double)value;
         const float va = sh.in[0][r0 + o + HALO][c + halo_x], vb = sh.in[1][r0 + o + HALO][c + halo_x];
@@ -161,6 +217,7 @@ __global__ __launch_bounds__(THREADS) void metrics_tile_kernel(TileArgs g) {
         }
     }
 
+    if constexpr (TAIL != TAIL_RECORDS) return;
     // over the workgroup, in a fixed order
     ssim = wave_sum(ssim);
     ull se, ae;
@@ -220,6 +277,81 @@ __global__ __launch_bounds__(64) void metrics_finish_kernel(const Partial* __res
         const double l1 = U8 ? (double)ae_i / (count * 255.0) : ae_f / count;
         double* o = out + (size_t)blockIdx.x * 4;
         o[0] = ssim / count, o[1] = mse, o[2] = l1, o[3] = 20.0 * log10(1.0 / sqrt(mse));
+    }
+}
+
+// ---- the gradient's second pass -----------------------------------------------------------------------------------------------------------
+constexpr int GRAD_STAGE_W = TILE_X + 2 * HALO;             // 74: the tile's columns and the halo, tap stride 1
+
+struct CombineShared {
+    float in[3][STAGE_Y][GRAD_STAGE_W];                     // 23088 bytes: the derivative planes with their halo
+    float row[3][STAGE_Y][TILE_X];                          // 19968 bytes: after the row pass
+};
+static_assert(sizeof(CombineShared) <= sizeof(Shared), "the combine pass keeps within the tile pass's LDS");
+
+struct CombineArgs {
+    const float *x, *y;       // the input whose gradient this is, and the other one
+    const float *d_mu, *d_exx, *d_exy;          // the planes: by x's mean, by E[x^2], by E[xy]
+    const double* weights;    // [n][3]
+    float* grad;
+    int planes, H, Wp;        // of one frame
+    int tiles_x, tiles_y;     // of one plane
+};
+
+// grid (planes * tiles_y * tiles_x, n), as the tile pass
+__global__ __launch_bounds__(THREADS) void metrics_combine_kernel(CombineArgs g) {
+    __shared__ CombineShared sh;
+    const int t = threadIdx.x;
+    const int per_plane = g.tiles_x * g.tiles_y;
+    const int plane = blockIdx.x / per_plane, tile = blockIdx.x % per_plane;
+    const int x0 = (tile % g.tiles_x) * TILE_X, y0 = (tile / g.tiles_x) * TILE_Y;
+    const size_t plane_at = ((size_t)blockIdx.y * g.planes + plane) * (size_t)g.H * (size_t)g.Wp;          // samples in front of the plane
+    const double* w = g.weights + (size_t)blockIdx.y * 3;
+    const double count = (double)g.planes * (double)g.H * (double)g.Wp;
+    // the frame's three scalars, one rounding each
+    const float k_ssim = (float)(w[0] / count), k_mse = (float)(2.0 * w[1] / count), k_l1 = (float)(w[2] / count);
+    const bool with_ssim = w[0] != 0.0;          // the same in every thread of the workgroup
+
+    const int c = t % TILE_X, r0 = (t / TILE_X) * ROWS_PER_THREAD;
+    float q[3][ROWS_PER_THREAD];
+    if (with_ssim) {
+        // the planes' tile and its halo, zeros outside the plane
+        const float* src[3] = {g.d_mu + plane_at, g.d_exx + plane_at, g.d_exy + plane_at};
+        for (int i = t; i < STAGE_Y * GRAD_STAGE_W; i += THREADS) {
+            const int r = i / GRAD_STAGE_W, cc = i % GRAD_STAGE_W;
+            const int y = y0 - HALO + r, x = x0 - HALO + cc;
+            const bool inside = y >= 0 && y < g.H && x >= 0 && x < g.Wp;
+            const size_t at = (size_t)(inside ? y : 0) * g.Wp + (inside ? x : 0);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) sh.in[j][r][cc] = inside ? src[j][at] : 0.0f;
+        }
+        __syncthreads();
+        for (int i = t; i < STAGE_Y * TILE_X; i += THREADS) {
+            const int r = i / TILE_X, cc = i % TILE_X;
+            float acc[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int k = 0; k < WIN; ++k)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc[j] = fmaf(SSIM_WINDOW[k], sh.in[j][r][cc + k], acc[j]);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) sh.row[j][r][cc] = acc[j];
+        }
+        __syncthreads();
+        column_pass<3>(sh.row, c, r0, q);
+    }
+
+    const int x = x0 + c;
+#pragma unroll
+    for (int o = 0; o < ROWS_PER_THREAD; ++o) {
+        const int y = y0 + r0 + o;
+        if (x >= g.Wp || y >= g.H) continue;
+        const size_t at = plane_at + (size_t)y * g.Wp + x;
+        const float xv = g.x[at], yv = g.y[at];
+        const float d = xv - yv;
+        const float sign = xv > yv ? 1.0f : xv < yv ? -1.0f : d;          // d: zero, or the NaN of an input
+        float v = 0.0f;
+        if (with_ssim) v = k_ssim * ((q[0][o] + (2.0f * xv) * q[1][o]) + yv * q[2][o]);
+        g.grad[at] = (v + k_mse * d) + k_l1 * sign;
     }
 }
 
@@ -286,17 +418,77 @@ int launch_metrics(bool u8, const void* a, const void* b, int n, int h, int w, i
         if (overlaps(o.ptr, o.bytes, a, src_bytes)) { set_error("%s: %s overlaps a", who, o.name); return ADAIN_EINVAL; }
         if (overlaps(o.ptr, o.bytes, b, src_bytes)) { set_error("%s: %s overlaps b", who, o.name); return ADAIN_EINVAL; }
     }
-    TileArgs g;
+    TileArgs g{};
     g.a = a, g.b = b, g.map = map, g.partials = (Partial*)((char*)workspace + p.o_partials);
     g.planes = p.planes, g.H = p.H, g.Wp = p.Wp, g.tiles_x = p.tiles_x, g.tiles_y = p.tiles_y;
     const dim3 grid((unsigned)p.tiles, (unsigned)n);
     if (u8) {
-        if (p.cs == 1) metrics_tile_kernel<uint8_t, 1><<<grid, THREADS, 0, s>>>(g);
-        else metrics_tile_kernel<uint8_t, 3><<<grid, THREADS, 0, s>>>(g);
+        if (p.cs == 1) metrics_tile_kernel<uint8_t, 1, TAIL_RECORDS><<<grid, THREADS, 0, s>>>(g);
+        else metrics_tile_kernel<uint8_t, 3, TAIL_RECORDS><<<grid, THREADS, 0, s>>>(g);
         metrics_finish_kernel<true><<<(unsigned)n, 64, 0, s>>>(g.partials, (unsigned)p.tiles, (double)p.frame_samples, out);
     } else {
-        metrics_tile_kernel<float, 1><<<grid, THREADS, 0, s>>>(g);
+        metrics_tile_kernel<float, 1, TAIL_RECORDS><<<grid, THREADS, 0, s>>>(g);
         metrics_finish_kernel<false><<<(unsigned)n, 64, 0, s>>>(g.partials, (unsigned)p.tiles, (double)p.frame_samples, out);
+    }
+    return check_launch(who);
+}
+
+// The one layout of a gradient call: the derivative planes, each the clip's size
+struct GradPlan {
+    MetricsPlan m;
+    int nplanes;
+    size_t plane_bytes, pitch_bytes;          // of one plane; from one plane's start to the next
+    size_t total;
+};
+
+GradPlan make_grad_plan(int n, int h, int w, int c, bool with_grad_b) {
+    GradPlan p{};
+    p.m = make_metrics_plan(false, n, h, w, c);
+    p.nplanes = with_grad_b ? TAIL_PLANES_AB : TAIL_PLANES_A;
+    p.plane_bytes = (size_t)n * p.m.frame_samples * sizeof(float);
+    Carve ws;
+    for (int j = 0; j < p.nplanes; ++j) ws.take(p.plane_bytes);
+    p.pitch_bytes = align256(p.plane_bytes);
+    p.total = ws.at;
+    return p;
+}
+
+int launch_metrics_grad(const float* a, const float* b, int n, int h, int w, int c, const double* weights, float* grad_a, float* grad_b, void* workspace,
+                        size_t workspace_bytes, hipStream_t s) {
+    const char* who = "image_metrics_grad_f32";
+    if (!a) { set_error("%s: a is a null pointer", who); return ADAIN_EINVAL; }
+    if (!b) { set_error("%s: b is a null pointer", who); return ADAIN_EINVAL; }
+    if (!weights) { set_error("%s: weights is a null pointer", who); return ADAIN_EINVAL; }
+    if (!grad_a) { set_error("%s: grad_a is a null pointer", who); return ADAIN_EINVAL; }
+    if (const char* bad = check_metrics_shape(false, n, h, w, c)) { set_error("%s: %s (n %d, %d x %d, c %d)", who, bad, n, h, w, c); return ADAIN_EINVAL; }
+    const GradPlan p = make_grad_plan(n, h, w, c, grad_b != nullptr);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, p.total, 8)) return rc;
+    if ((uintptr_t)weights % 8) { set_error("%s: weights must be 8-byte aligned", who); return ADAIN_EINVAL; }
+    const struct { const char* name; const void* ptr; size_t bytes; } ins[3] = {{"a", a, p.plane_bytes}, {"b", b, p.plane_bytes}, {"weights", weights, (size_t)n * 3 * sizeof(double)}},
+      outs[3] = {{"grad_a", grad_a, p.plane_bytes}, {"grad_b", grad_b, p.plane_bytes}, {"the workspace", workspace, p.total}};
+    for (const auto* f : {&ins[0], &ins[1], &outs[0], &outs[1]})
+        if ((uintptr_t)f->ptr % 4) { set_error("%s: %s must be 4-byte aligned", who, f->name); return ADAIN_EINVAL; }
+    for (int i = 0; i < 3; ++i) {
+        if (!outs[i].ptr) continue;
+        for (const auto& in : ins)
+            if (overlaps(outs[i].ptr, outs[i].bytes, in.ptr, in.bytes)) { set_error("%s: %s overlaps %s", who, outs[i].name, in.name); return ADAIN_EINVAL; }
+        for (int k = 0; k < i; ++k)
+            if (outs[k].ptr && overlaps(outs[i].ptr, outs[i].bytes, outs[k].ptr, outs[k].bytes)) { set_error("%s: %s overlaps %s", who, outs[i].name, outs[k].name); return ADAIN_EINVAL; }
+    }
+    TileArgs g{};
+    g.a = a, g.b = b, g.planes = p.m.planes, g.H = p.m.H, g.Wp = p.m.Wp, g.tiles_x = p.m.tiles_x, g.tiles_y = p.m.tiles_y;
+    g.weights = weights, g.dplanes = (float*)workspace, g.dplane_pitch = p.pitch_bytes / sizeof(float);
+    const dim3 grid((unsigned)p.m.tiles, (unsigned)n);
+    if (grad_b) metrics_tile_kernel<float, 1, TAIL_PLANES_AB><<<grid, THREADS, 0, s>>>(g);
+    else metrics_tile_kernel<float, 1, TAIL_PLANES_A><<<grid, THREADS, 0, s>>>(g);
+    const auto plane = [&](int j) { return (const float*)g.dplanes + (size_t)j * g.dplane_pitch; };
+    CombineArgs k{};
+    k.weights = weights, k.planes = g.planes, k.H = g.H, k.Wp = g.Wp, k.tiles_x = g.tiles_x, k.tiles_y = g.tiles_y;
+    k.x = a, k.y = b, k.d_mu = plane(P_MU1), k.d_exx = plane(P_E11), k.d_exy = plane(P_E12), k.grad = grad_a;
+    metrics_combine_kernel<<<grid, THREADS, 0, s>>>(k);
+    if (grad_b) {
+        k.x = b, k.y = a, k.d_mu = plane(P_MU2), k.d_exx = plane(P_E22), k.grad = grad_b;
+        metrics_combine_kernel<<<grid, THREADS, 0, s>>>(k);
     }
     return check_launch(who);
 }
@@ -314,6 +506,17 @@ int launch_image_metrics_u8(const uint8_t* a, const uint8_t* b, int n, int h, in
 int launch_image_metrics_f32(const float* a, const float* b, int n, int c, int h, int w, double* out, float* ssim_map, void* workspace, size_t workspace_bytes,
                              hipStream_t s) {
     return launch_metrics(false, a, b, n, h, w, c, out, ssim_map, workspace, workspace_bytes, s);
+}
+
+int image_metrics_grad_f32_bytes(int n, int c, int h, int w, int with_grad_b, size_t* workspace_bytes) {
+    if (const char* bad = check_metrics_shape(false, n, h, w, c)) { set_error("image_metrics_grad_f32: %s (n %d, %d x %d, c %d)", bad, n, h, w, c); return ADAIN_EINVAL; }
+    if (workspace_bytes) *workspace_bytes = make_grad_plan(n, h, w, c, with_grad_b != 0).total;
+    return 0;
+}
+
+int launch_image_metrics_grad_f32(const float* a, const float* b, int n, int c, int h, int w, const double* weights, float* grad_a, float* grad_b, void* workspace,
+                                  size_t workspace_bytes, hipStream_t s) {
+    return launch_metrics_grad(a, b, n, h, w, c, weights, grad_a, grad_b, workspace, workspace_bytes, s);
 }
 
 void ssim_window(float out[11]) {

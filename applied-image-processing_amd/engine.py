@@ -234,6 +234,12 @@ class AdaINEngine:
         ``runtime.image_metrics``)."""
         return rt.image_metrics(a, b, ssim_map)
 
+    def image_metrics_grad(self, a, b, weights, grad_b=False):
+        """Two float32 clips [n,1..4,h,w] on the device and ``weights`` float64 [n,3], the upstream gradient of every frame's {ssim,
+        mse, l1} -> the float32 gradient by ``a``, with ``grad_b`` (grad_a, grad_b) (adain_image_metrics_grad_f32;
+        ``runtime.image_metrics_grad``)."""
+        return rt.image_metrics_grad(a, b, weights, grad_b)
+
     def gif_encode_u8(self, index_u8, K, delay_cs):
         """Palette index planes uint8 [n,h,w] on the device, every index below ``K`` -> the frames' GIF records (adain_gif_encode_u8;
         ``runtime.gif_encode_u8``) as (records, lengths) on the device; ``gif_file.assemble`` makes the file of them and only the records

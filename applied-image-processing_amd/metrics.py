@@ -5,8 +5,14 @@ ssim`` can be swapped for ``from applied_image_processing_amd.metrics import ssi
 Where the device scores: float32 GPU tensors [N,C,H,W] (``ssim`` also [C,H,W]) with C in 1..4 that need no gradient, at ``window_size``
 11, go through ``runtime.image_metrics`` (adain_image_metrics_f32: one fused pass, float64 sums); ``compare_dirs`` hands it the decoded
 uint8 frames (adain_image_metrics_u8).  Everything else - another window size, CPU tensors, other dtypes, tensors that need a gradient
-(there is no backward pass: the 3DGS training loss stays with torch) - runs the reference's expressions in torch, with the values they
-always had.  Without a GPU everything runs in torch on the CPU.
+- runs the reference's expressions in torch, with the values they always had.  Without a GPU everything runs in torch on the CPU.
+
+The training loss (Style_3DGS/train.py: ``(1 - lambda_dssim) * l1_loss(image, gt) + lambda_dssim * (1 - ssim(image, gt))``, then
+``loss.backward()``) has a device route as well, which is opt-in: after ``set_device_backward(True)`` the same float32 GPU tensors, when
+one of them needs a gradient, go through one ``torch.autograd.Function`` whose forward is ``runtime.image_metrics`` and whose backward is
+``runtime.image_metrics_grad`` (adain_image_metrics_grad_f32: the SSIM, MSE and L1 gradients in closed form, two kernels).  ``psnr``
+chains through its ``mse`` in torch.  ``dssim_loss`` is train.py's expression as one forward and one backward call.  The function is
+once differentiable; with the switch off (the default) a tensor that needs a gradient takes the torch route exactly as before.
 
 LPIPS comes by provider only: ``evaluate(paths, lpips_fn=...)`` with a callable (render, gt) -> value on [1,3,H,W] tensors in [0,1].  Its
 VGG weights are a network fetch, as those of the other networks are, and are not part of this package.
@@ -36,13 +42,76 @@ def _records(a, b):
     return rt.image_metrics(a, b)
 
 
+_device_backward = False
+
+
+def set_device_backward(enabled):
+    """Switches the device route of tensors that need a gradient on or off (off by default); returns the previous value."""
+    global _device_backward
+    previous, _device_backward = _device_backward, bool(enabled)
+    return previous
+
+
+def device_backward():
+    return _device_backward
+
+
+class _Scores(torch.autograd.Function):
+    """(a, b) float32 [N,C,H,W] on the device -> float64 [N,3], every frame's {ssim, mse, l1}; the backward hands the incoming [N,3]
+    to ``runtime.image_metrics_grad`` as the frames' weights."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        ctx.save_for_backward(a, b)
+        return _records(a, b).records[:, :3].contiguous()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        from . import runtime as rt
+
+        a, b = ctx.saved_tensors
+        weights = grad.to(torch.float64).contiguous()
+        need_a, need_b = ctx.needs_input_grad
+        if need_a and need_b:
+            return rt.image_metrics_grad(a, b, weights, grad_b=True)
+        if need_b:
+            return None, rt.image_metrics_grad(b, a, weights)          # grad_b(a, b) is grad_a(b, a), bit for bit
+        return rt.image_metrics_grad(a, b, weights), None
+
+
+def _grad_pair(a, b, dims=(4,)):
+    """Do ``a`` and ``b`` take the device call and its backward?  ``_device_pair``'s tensors, one of which needs a gradient, with the
+    switch on."""
+    return (_device_backward and isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)
+            and _device_pair(a.detach(), b.detach(), dims))
+
+
+def _scores(a, b):
+    """float64 [N,3] = {ssim, mse, l1} per frame of a ``_grad_pair``, differentiable once."""
+    return _Scores.apply(a, b) if a.dim() == 4 else _Scores.apply(a[None], b[None])
+
+
+def dssim_loss(image, gt, lambda_dssim=0.2):
+    """Style_3DGS/train.py's loss, ``(1 - lambda_dssim) * l1_loss(image, gt) + lambda_dssim * (1 - ssim(image, gt))``: on the device route
+    one forward and one backward call for both terms; otherwise that expression of this module's ``l1_loss`` and ``ssim``."""
+    if _grad_pair(image, gt, dims=(3, 4)):
+        s = _scores(image, gt)
+        return ((1.0 - lambda_dssim) * s[:, 2].mean() + lambda_dssim * (1.0 - s[:, 0].mean())).to(torch.float32)
+    return (1.0 - lambda_dssim) * l1_loss(image, gt) + lambda_dssim * (1.0 - ssim(image, gt))
+
+
 def l1_loss(network_output, gt):
+    if _grad_pair(network_output, gt):
+        return _scores(network_output, gt)[:, 2].mean().to(torch.float32)
     if _device_pair(network_output, gt):
         return _records(network_output, gt).l1.mean().to(torch.float32)          # frames of one size: the mean of their means
     return torch.abs((network_output - gt)).mean()
 
 
 def l2_loss(network_output, gt):
+    if _grad_pair(network_output, gt):
+        return _scores(network_output, gt)[:, 1].mean().to(torch.float32)
     if _device_pair(network_output, gt):
         return _records(network_output, gt).mse.mean().to(torch.float32)
     return ((network_output - gt) ** 2).mean()
@@ -69,6 +138,9 @@ def _ssim(img1, img2, window, window_size, channel, size_average=True):
 
 def ssim(img1, img2, window_size=11, size_average=True):
     """The reference's ``ssim``: a 0-d tensor, or with ``size_average=False`` one value per image, [N]."""
+    if window_size == 11 and _grad_pair(img1, img2, dims=(3, 4) if size_average else (4,)):
+        per_frame = _scores(img1, img2)[:, 0]
+        return (per_frame.mean() if size_average else per_frame).to(torch.float32)
     if window_size == 11 and _device_pair(img1, img2, dims=(3, 4) if size_average else (4,)):
         per_frame = _records(img1, img2).ssim
         return (per_frame.mean() if size_average else per_frame).to(torch.float32)
@@ -78,6 +150,8 @@ def ssim(img1, img2, window_size=11, size_average=True):
 
 
 def mse(img1, img2):
+    if _grad_pair(img1, img2):
+        return _scores(img1, img2)[:, 1].to(torch.float32)[:, None]
     if _device_pair(img1, img2):
         return _records(img1, img2).mse.to(torch.float32)[:, None]
     return (((img1 - img2)) ** 2).view(img1.shape[0], -1).mean(1, keepdim=True)
@@ -85,6 +159,8 @@ def mse(img1, img2):
 
 def psnr(img1, img2):
     """The reference's ``psnr``: [N,1]."""
+    if _grad_pair(img1, img2):
+        return (20 * torch.log10(1.0 / torch.sqrt(_scores(img1, img2)[:, 1]))).to(torch.float32)[:, None]          # autograd chains through mse
     if _device_pair(img1, img2):
         return _records(img1, img2).psnr.to(torch.float32)[:, None]
     return 20 * torch.log10(1.0 / torch.sqrt(mse(img1, img2)))

@@ -124,6 +124,8 @@ SIGNATURES = {
     "adain_image_metrics_f32_bytes": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_size_t)]),
     "adain_image_metrics_f32": (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 4 + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_ssim_window": (_c_int, [ctypes.POINTER(_c_float)]),
+    "adain_image_metrics_grad_f32_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t)]),
+    "adain_image_metrics_grad_f32": (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 4 + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_progressive_u8_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
@@ -1444,6 +1446,38 @@ def image_metrics(a, b, ssim_map=False):
         _launch("adain_image_metrics_u8" if u8 else "adain_image_metrics_f32", x.data_ptr(), y.data_ptr(), *dims, records.data_ptr(),
                 smap.data_ptr() if ssim_map else None, ws.data_ptr(), ws.numel())
     return ImageMetrics(records, smap.reshape(a.shape) if ssim_map else None)
+
+
+def image_metrics_grad_sizes(n, c, h, w, grad_b=False):
+    """workspace_bytes of adain_image_metrics_grad_f32_bytes: 3 planes of the clip's floats, 5 with ``grad_b``, each rounded up to 256
+    bytes.  Host only.  AdainHipError for a refused shape."""
+    return _size_query("adain_image_metrics_grad_f32_bytes", n, c, h, w, 1 if grad_b else 0)[0]
+
+
+def image_metrics_grad(a, b, weights, grad_b=False):
+    """The gradient of ``image_metrics``' float32 scores: ``a``, ``b`` float32 [n,c,h,w] or [c,h,w] with c in 1..4 on the device and
+    ``weights`` float64 [n,3] (or [3] for one frame) there, row i the upstream gradient of frame i's {ssim, mse, l1} -> ``grad_a``,
+    float32 of ``a``'s shape: weights[i,0] d ssim_i / d a + weights[i,1] 2 (a - b) / count + weights[i,2] sign(a - b) / count; with
+    ``grad_b`` (grad_a, grad_b) (adain_image_metrics_grad_f32).  The window statistics are recomputed from ``a`` and ``b``; a frame's
+    gradient is a function of its two frames and its three weights alone.  Nothing is copied to the host and nothing waits."""
+    what = "image_metrics_grad"
+    x, y = device_tensor(a, what + ": a"), device_tensor(b, what + ": b")
+    if x.shape != y.shape or x.device != y.device:
+        raise AdainHipError(f"{what}: a and b must have one shape and one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if x.dim() == 3:
+        x, y = x[None], y[None]
+    if x.dim() != 4 or x.numel() == 0 or not 1 <= x.shape[1] <= 4:
+        raise AdainHipError(f"{what}: expected float32 [n,1..4,h,w] / [c,h,w], got {tuple(a.shape)}")
+    n, c, h, w = x.shape
+    wts = device_tensor(weights, what + ": weights", torch.float64)
+    if wts.device != x.device or wts.numel() != 3 * n or tuple(wts.shape) not in ((n, 3), (3,)):
+        raise AdainHipError(f"{what}: weights must be float64 [{n},3] on {x.device}, got {tuple(weights.shape)} on {weights.device}")
+    ga = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    gb = torch.empty(x.shape, dtype=torch.float32, device=x.device) if grad_b else None
+    with scratch(x.device, "metrics_grad", image_metrics_grad_sizes, n, c, h, w, bool(grad_b)) as ws:
+        _launch("adain_image_metrics_grad_f32", x.data_ptr(), y.data_ptr(), n, c, h, w, wts.data_ptr(), ga.data_ptr(), gb.data_ptr() if grad_b else None,
+                ws.data_ptr(), ws.numel())
+    return (ga.reshape(a.shape), gb.reshape(a.shape)) if grad_b else ga.reshape(a.shape)
 
 
 def ssim_window():

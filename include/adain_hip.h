@@ -762,7 +762,7 @@ ADAIN_API int adain_quantize_palette_u8(const uint8_t* src_u8, int n, int h, int
  * n outside 1..65535, h or w below 1, a frame beyond 2^31 - 1 samples, a null workspace, workspace_bytes below the query's, a workspace
  * or out that is not 8-byte aligned, a ssim_map (or float32 a, b) that is not 4-byte aligned, out, ssim_map or the workspace overlapping
  * a or b.  Nothing is copied to the host and nothing waits; 2 kernel launches per call, whatever n.
- * Not built: windows other than 11, a backward pass (the 3DGS training loss stays with torch), LPIPS. */
+ * Not built: windows other than 11, LPIPS.  The backward pass is adain_image_metrics_grad_f32 below. */
 #define ADAIN_METRICS_TILE_X 64
 #define ADAIN_METRICS_TILE_Y 16
 ADAIN_API int adain_image_metrics_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes);
@@ -772,6 +772,39 @@ ADAIN_API int adain_image_metrics_f32_bytes(int n, int c, int h, int w, size_t* 
 ADAIN_API int adain_image_metrics_f32(const float* a, const float* b, int n, int c, int h, int w, double* out, float* ssim_map_or_null,
                                       void* workspace, size_t workspace_bytes, adain_stream_t stream);
 ADAIN_API int adain_ssim_window(float* out11);
+
+/* ---- the gradient of the float32 scores above: what autograd hands back through Style_3DGS/train.py's loss, (1 - lambda) l1_loss +
+ * lambda (1 - ssim), and its l1_loss against the stylised guide views -------------------------------------------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * a, b: contiguous NCHW float32 [n][c][h][w], c in 1..4, 4-byte aligned, as adain_image_metrics_f32 takes them.  a may be b.
+ * weights: device double [n][3], 8-byte aligned: row i is the upstream gradient of frame i's {ssim, mse, l1}.
+ * grad_a: float32 of the inputs' layout, 4-byte aligned: sample j of frame i receives
+ *     weights[i][0] d ssim_i / d a_j  +  weights[i][1] 2 (a_j - b_j) / count  +  weights[i][2] sign(a_j - b_j) / count,   count = c h w,
+ *   sign(0) = 0.  With the forward pass's mu1, mu2, e11 = E[a^2], e22 = E[b^2], e12 = E[ab] per sample and A = 2 mu1 mu2 + C1,
+ *   B = 2 (e12 - mu1 mu2) + C2, D = mu1^2 + mu2^2 + C1, E = (e11 - mu1^2) + (e22 - mu2^2) + C2, map = A B / (D E):
+ *     d_mu1 = 2 mu2 (B - A) / (D E) - map (2 mu1 / D - 2 mu1 / E),   d_e11 = -map / E,   d_e12 = 2 A / (D E)
+ *     d ssim_i / d a = ( conv(d_mu1) + 2 a conv(d_e11) + b conv(d_e12) ) / count
+ *   where conv is the forward pass's window (symmetric, zero padding of 5, not renormalised: its own adjoint), a row pass and a column
+ *   pass of 11 taps in float32.  The window statistics are recomputed from a and b; nothing of a forward call is taken.
+ * grad_b: NULL, or the same for b (d_mu2, d_e22 and the same d_e12; the mse and l1 terms change sign).
+ * Held, and stated at the top of csrc/metrics.hip:
+ *   - a frame's gradient bits are a function of its two frames and its three weights alone - not of n, the frame's index, the stream
+ *     or what the workspace held;
+ *   - a frame whose three weights are all zero receives zeros (of either sign);
+ *   - grad_b of (a, b) is bit for bit grad_a of (b, a) under the same weights, and grad_a is the same bits with and without grad_b;
+ *   - equal frames receive exactly zero from the ssim term.
+ * Kernels: the forward tile pass with another tail, which writes the derivative planes (3, or 5 with grad_b) into the workspace, and a
+ * combine pass of the same tile geometry over three of them per gradient: 2 launches, 3 with grad_b, whatever n.  No float atomics.
+ * adain_image_metrics_grad_f32_bytes (host only): *workspace_bytes = (with_grad_b ? 5 : 3) planes of n c h w floats, each rounded up
+ * to a multiple of 256 bytes.  The output may be NULL.
+ * Refused with ADAIN_EINVAL before anything is launched, adain_last_error naming the argument: a null a, b, weights or grad_a, c outside
+ * 1..4, n outside 1..65535, h or w below 1, a frame beyond 2^31 - 1 samples, a null workspace, workspace_bytes below the query's, a
+ * workspace or weights that is not 8-byte aligned, a, b, grad_a or grad_b that is not 4-byte aligned, grad_a, grad_b or the workspace
+ * overlapping a, b, the weights or each other.  Nothing is copied to the host and nothing waits.
+ * Not built: a gradient for uint8 input, other windows, a forward call that saves its planes for this one. */
+ADAIN_API int adain_image_metrics_grad_f32_bytes(int n, int c, int h, int w, int with_grad_b, size_t* workspace_bytes);
+ADAIN_API int adain_image_metrics_grad_f32(const float* a, const float* b, int n, int c, int h, int w, const double* weights, float* grad_a,
+                                           float* grad_b_or_null, void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
