@@ -7,11 +7,10 @@ frame and a 1080 x 1920 frame, each with a 512 x 512 style, on seeded synthetic 
 Medians and interquartile ranges of --reps calls after warm-up (20 calls of the kernel, so that the clock has ramped; 3 of the others);
 shader clock and power over each kernel window.  Seeded synthetic weights, JPEG output (PIL) to a temporary directory.  Prints one JSON line and,
 with --out, writes it to a file.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/coral_bench.py [--reps 200] [--out profiles/coral_bench.json]"""
-import argparse
 import contextlib
 import io
-import json
 import os
 import statistics
 import sys
@@ -28,6 +27,7 @@ import applied_image_processing_amd.synth as synth  # noqa: E402
 from applied_image_processing_amd.AdaIN import test as adain  # noqa: E402
 from applied_image_processing_amd.AdaIN.function import coral as host_coral  # noqa: E402
 from applied_image_processing_amd.telemetry import GpuTelemetry  # noqa: E402
+from benchkit import arguments, emit, event_times, wall_times  # noqa: E402
 
 SIZES = [(256, 456), (1080, 1920)]
 STYLE = (512, 512)
@@ -38,47 +38,17 @@ def u8(seed, h, w):
 
 
 def summary(times):
+    """This record's own shape: the quartiles themselves, not their distance."""
     q = statistics.quantiles(times, n=4)
     return {"median_ms": round(statistics.median(times), 4), "iqr_ms": [round(q[0], 4), round(q[2], 4)]}
-
-
-def wall_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t) * 1e3)
-    return summary(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return summary(times)
 
 
 def main():
     from PIL import Image
 
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--out", type=str, default=None)
-    args = ap.parse_args()
+    args = arguments(__doc__).parse_args()
     assert torch.cuda.is_available(), "coral_bench needs a GPU"
-    torch.cuda.set_device(0)
+    torch.cuda.set_device(0)          # its own setup and header: the calls run on the host's threads as they are, and the record names no library
     reps = max(args.reps, 8)
     tel = GpuTelemetry(0).start()
     res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(),
@@ -95,12 +65,12 @@ def main():
             d_frame = torch.from_numpy(frame)[None].cuda()
             out = torch.empty((1, 3) + STYLE, dtype=torch.float32, device="cuda")
             t0 = time.perf_counter()
-            kernel = event_ms(lambda: rt.coral(d_style, d_frame, out=out), reps, 20)
+            kernel = summary(event_times(lambda: rt.coral(d_style, d_frame, out=out), reps, 20)[0])
             tel.window(f"kernel_{h}x{w}", t0, time.perf_counter())
             c_host = torch.from_numpy(frame).permute(2, 0, 1).float().div(255)
             threads = torch.get_num_threads()
             torch.set_num_threads(1)
-            host = wall_ms(lambda: host_coral(s_host, c_host), reps, 3)
+            host = summary(wall_times(lambda: host_coral(s_host, c_host), reps, 3, "both")[0])
             torch.set_num_threads(threads)
             want = host_coral(s_host, c_host)
             err = float((out[0].cpu() - want).norm() / want.norm())
@@ -111,7 +81,7 @@ def main():
             for name, flag in (("call_off_ms", False), ("call_on_ms", True)):
                 prev = adain.set_device_coral(flag)
                 with contextlib.redirect_stdout(io.StringIO()):          # adain_inference prints the path it saved
-                    calls[name] = wall_ms(lambda: adain.adain_inference(pil_frame, pil_style, **kw), reps, 3)
+                    calls[name] = summary(wall_times(lambda: adain.adain_inference(pil_frame, pil_style, **kw), reps, 3, "both")[0])
                 adain.set_device_coral(prev)
             gap = calls["call_off_ms"]["median_ms"] - calls["call_on_ms"]["median_ms"]
             spread = max(b - a for a, b in (calls["call_off_ms"]["iqr_ms"], calls["call_on_ms"]["iqr_ms"]))
@@ -119,11 +89,7 @@ def main():
                                         "relative_l2_against_host": float(f"{err:.3e}"), **calls,
                                         "device_call_below_host_call_by_more_than_both_iqrs": bool(gap > spread)}
     res["telemetry"] = tel.stop()          # shader clock and power over each size's kernel timing (sysfs reads)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -8,14 +8,12 @@ K = 256 uniform noise.  Per clip, median and interquartile range over --reps cal
 with the two files' sizes beside the times, and whether the device's file plays as the frames.  Pillow's figure is the median of
 --pillow_reps calls (default: --reps; the number used is recorded).  ``faster_than_pillow`` / ``slower_than_pillow``: one median sits
 below the other by more than both interquartile ranges.  Prints one JSON line and, with --out, writes it to a file.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/gif_bench.py [--reps 200] [--pillow_reps N] [--out profiles/gif_bench.json]"""
-import argparse
 import io
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import PIL
@@ -28,43 +26,11 @@ import applied_image_processing_amd.runtime as rt  # noqa: E402
 import applied_image_processing_amd.synth as synth  # noqa: E402
 from applied_image_processing_amd import gif_file, pixelize  # noqa: E402
 from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
+from benchkit import arguments, below, emit, event_ms, gpu_setup, header, wall_ms  # noqa: E402
 
 CLIPS = [(1, 1080, 1920), (1, 256, 456), (64, 135, 240)]
 SLSO8 = ["#0d2b45", "#203c56", "#544e68", "#8d697a", "#d08159", "#ffaa5e", "#ffd4a3", "#ffecd6"]          # lospec's slso8
 DELAY = 5
-
-
-def spread(times):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
-
-
-def wall_ms(fn, reps, warmup, sync):
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        if sync:
-            torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t) * 1e3)
-    return spread(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return spread(times)
 
 
 def pillow_bytes(idx, pal):
@@ -95,33 +61,26 @@ def compare(idx, pal, reps, pillow_reps):
     encode = lambda: rt.gif_encode_u8(idx, K, DELAY)
     host = idx.cpu().numpy()
     kernel = event_ms(encode, reps, 20)
-    device = wall_ms(lambda: gif_file.assemble(head, *encode()), reps, 5, True)
-    pillow = wall_ms(lambda: pillow_bytes(host, pal), pillow_reps, 1, False)
+    device = wall_ms(lambda: gif_file.assemble(head, *encode()), reps, 5, "before")
+    pillow = wall_ms(lambda: pillow_bytes(host, pal), pillow_reps, 1, "none")
     data = gif_file.assemble(head, *encode())
-    below = lambda a, b: a["median"] + a["iqr"] + b["iqr"] < b["median"]
     return {"frames": n, "index_bytes": int(idx.numel()), "file_bytes": len(data), "pillow_file_bytes": len(pillow_bytes(host, pal)),
             "plays_as_the_frames": plays_as(data, pal[host]), "kernel_ms": kernel, "device_ms": device, "pillow_ms": pillow, "pillow_reps": pillow_reps,
             "faster_than_pillow": below(device, pillow), "slower_than_pillow": below(pillow, device)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__)
     ap.add_argument("--pillow_reps", type=int, default=None)
-    ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
-    assert torch.cuda.is_available(), "gif_bench needs a GPU"
-    torch.cuda.set_device(0)
-    torch.set_num_threads(1)
+    dev = gpu_setup("gif_bench")
     reps = max(args.reps, 200)
     pillow_reps = max(4, args.pillow_reps or reps)
-    dev = torch.device("cuda:0")
     engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     slso8 = pixelize.parse_palette(SLSO8)
     grey = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)
-    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "segment": rt.GIF_SEGMENT, "clips": {}}
+    res = header(reps=reps, pillow=PIL.__version__, segment=rt.GIF_SEGMENT, clips={})
     for n, h, w in CLIPS:
         planes = []
         for i in range(0, n, 16):
@@ -133,11 +92,7 @@ def main():
             key = f"{kind}_{n}x{h}x{w}"
             res["clips"][key] = compare(idx, pal, reps, pillow_reps)
             print(key, json.dumps(res["clips"][key]), file=sys.stderr, flush=True)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

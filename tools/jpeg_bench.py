@@ -13,13 +13,12 @@ device median is below Pillow's by more than both interquartile ranges.  --only 
 --out, replaces that key alone in an existing file.  With --job, a 64-view 1200 x 1600 precompute_guides_sharded into a temporary directory with jpeg_on_device off and on:
 wall time, the sink's wait and the bytes that crossed to the host.  Every kernel_ms also carries the sha256 of its last call's output bytes, so that two builds of the library
 (--lib PATH: that build in place of the package's own) can be held to the same bytes as well as the same time.  Prints one JSON line and, with --out, writes it to a file.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/jpeg_bench.py [--reps 200] [--job] [--only KEY] [--lib PATH] [--out profiles/jpeg_bench.json]"""
-import argparse
 import hashlib
 import io
 import json
 import os
-import statistics
 import sys
 import tempfile
 import time
@@ -36,14 +35,10 @@ import applied_image_processing_amd.synth as synth  # noqa: E402
 from applied_image_processing_amd import jobs  # noqa: E402
 from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
 from applied_image_processing_amd.telemetry import GpuTelemetry  # noqa: E402
+from benchkit import arguments, below, emit, event_times, gpu_setup, header, spread, wall_ms  # noqa: E402
 
 SIZES = [(256, 456), (1080, 1920), (1200, 1600)]
 OPTION_SETS = {"q95_444_optimize": (95, "4:4:4", True), "q75_420_optimize": (75, "4:2:0", True), "q75_422": (75, "4:2:2", False)}
-
-
-def spread(times):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
 
 
 def sha256(out):
@@ -51,31 +46,9 @@ def sha256(out):
     return hashlib.sha256(b"".join(rt.jpeg_files(*out))).hexdigest()
 
 
-def wall_ms(fn, reps, warmup, sync):
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        if sync:
-            torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t) * 1e3)
-    return spread(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
+def hashed_event_ms(fn, reps, warmup):
+    """The kit's event_ms with the sha256 of the last call's files beside it."""
+    times, out = event_times(fn, reps, warmup)
     return dict(spread(times), sha256=sha256(out))
 
 
@@ -94,15 +67,15 @@ def compare(x, options, reps, tel=None, label=None):
     encode = (lambda: rt.jpeg_encode_u8(x)) if options is None else (lambda: options.encode(x))
     host = x[0].cpu().numpy()
     t0 = time.perf_counter()
-    kernel = event_ms(encode, reps, 20)
+    kernel = hashed_event_ms(encode, reps, 20)
     if tel is not None:
         tel.window(label, t0, time.perf_counter())
-    device = wall_ms(lambda: rt.jpeg_files(*encode()), reps, 5, True)
-    pillow = wall_ms(lambda: pillow_bytes(host, options), reps, 3, False)
+    device = wall_ms(lambda: rt.jpeg_files(*encode()), reps, 5, "before")
+    pillow = wall_ms(lambda: pillow_bytes(host, options), reps, 3, "none")
     data, = rt.jpeg_files(*encode())
     return {"frame_bytes": int(x.numel()), "file_bytes": len(data), "same_bytes_as_pillow": data == pillow_bytes(host, options),
             "kernel_ms": kernel, "device_ms": device, "pillow_ms": pillow, "pillow_over_device": round(pillow["median"] / device["median"], 2),
-            "faster_than_pillow": device["median"] + device["iqr"] + pillow["iqr"] < pillow["median"]}
+            "faster_than_pillow": below(device, pillow)}
 
 
 def guide_job(engine, on, views, style, sub_batch):
@@ -118,26 +91,17 @@ def guide_job(engine, on, views, style, sub_batch):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__, lib=True)
     ap.add_argument("--job", action="store_true")
     ap.add_argument("--views", type=int, default=64)
-    ap.add_argument("--out", type=str, default=None)
-    ap.add_argument("--lib", type=str, default=None)
     ap.add_argument("--only", type=str, default=None, choices=["sizes", "options", "progressive"])
     args = ap.parse_args()
-    if args.lib:
-        rt.use_library(os.path.abspath(args.lib))
-    assert torch.cuda.is_available(), "jpeg_bench needs a GPU"
-    torch.cuda.set_device(0)
-    torch.set_num_threads(1)
+    dev = gpu_setup("jpeg_bench", args.lib)
     reps = max(args.reps, 200)
-    dev = torch.device("cuda:0")
     engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     tel = GpuTelemetry(0).start()
-    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "sizes": {}, "options": {}, "progressive": {}}
+    res = header(reps=reps, pillow=PIL.__version__, sizes={}, options={}, progressive={})
     want = lambda key: args.only in (None, key)
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
@@ -156,8 +120,7 @@ def main():
                     res["options"].setdefault(name, {"quality": o[0], "subsampling": o[1], "optimize": o[2]})[f"{kind}_{h}x{w}"] = compare(
                         x, rt.JpegOptions(*o), reps)
     if want("sizes"):
-        res["passes_1080p"] = all(v["device_ms"]["median"] + v["device_ms"]["iqr"] + v["pillow_ms"]["iqr"] < v["pillow_ms"]["median"]
-                                  for k, v in res["sizes"].items() if k.endswith("1080x1920"))
+        res["passes_1080p"] = all(below(v["device_ms"], v["pillow_ms"]) for k, v in res["sizes"].items() if k.endswith("1080x1920"))
     if args.job:
         base = [(synth.image(100 + k, 1, 1200, 1600)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8) for k in range(8)]
         views = [Image.fromarray(np.roll(base[k % 8], 16 * (k // 8), axis=1)) for k in range(args.views)]       # PIL views, as the 3DGS caller holds them
@@ -170,11 +133,7 @@ def main():
         res = {args.only: dict(res[args.only], reps=reps, pillow=res["pillow"], device=res["device"])}
         if args.out and os.path.exists(args.out):
             res = dict(json.load(open(args.out)), **res)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

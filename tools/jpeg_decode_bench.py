@@ -14,13 +14,12 @@ rounds at the small sizes, which is why the sweep makes fewer calls).  Progress 
 ``bench.py --per-call video``'s call) with ``set_device_jpeg_decode`` off and on.  Every kernel_ms also carries the sha256 of its last call's output bytes, so that two builds of the library
 (--lib PATH: that build in place of the package's own) can be held to the same bytes as well as the same time.  Prints one JSON line and, with --out,
 writes it.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/jpeg_decode_bench.py [--reps 200] [--lib PATH] [--out profiles/jpeg_decode_bench.json]"""
-import argparse
 import hashlib
 import io
 import json
 import os
-import statistics
 import sys
 import tempfile
 import time
@@ -38,14 +37,10 @@ import applied_image_processing_amd.synth as synth  # noqa: E402
 from applied_image_processing_amd.AdaIN import test as adain_test  # noqa: E402
 from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
 from applied_image_processing_amd.telemetry import GpuTelemetry  # noqa: E402
+from benchkit import arguments, below, emit, event_times, gpu_setup, header, spread, wall_ms  # noqa: E402
 
 SIZES = [(256, 456), (1080, 1920)]
 CHUNKS = [256, 512, 1024, 2048]
-
-
-def spread(times):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
 
 
 def sha256(out):
@@ -53,32 +48,9 @@ def sha256(out):
     return hashlib.sha256(b"".join(t.cpu().numpy().tobytes() for t in out)).hexdigest()
 
 
-def wall_ms(fn, reps, warmup):
-    """fn() ends with its result on the device; the clock stops after a synchronise."""
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t) * 1e3)
-    return spread(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
+def hashed_event_ms(fn, reps, warmup):
+    """The kit's event_ms with the sha256 of the last call's (frames, record) beside it."""
+    times, out = event_times(fn, reps, warmup)
     return dict(spread(times), sha256=sha256(out))
 
 
@@ -110,7 +82,7 @@ def per_call(reps, dev):
             try:
                 for on in (False, True):
                     adain_test.set_device_jpeg_decode(on)
-                    out["on" if on else "off"] = wall_ms(call, reps, 10)
+                    out["on" if on else "off"] = wall_ms(call, reps, 10, "both")
                     files[on] = open(os.path.join(d, "out", "x.jpg"), "rb").read()
             finally:
                 sys.stdout = stdout
@@ -122,36 +94,27 @@ def per_call(reps, dev):
 def row(name, data, launch, restart_interval, kw, reps, dev, tel):
     """One file's row: kernel_ms of ``launch`` (bytes already on the device), device_ms of ``rt.jpeg_decode_u8(data, **kw)``, host_ms."""
     t0 = time.perf_counter()
-    kernel = event_ms(launch, reps, 20)
+    kernel = hashed_event_ms(launch, reps, 20)
     tel.window(f"kernel_{name}", t0, time.perf_counter())
     report = []
     same = bool(torch.equal(rt.jpeg_decode_u8(data, dev, report=report, **kw), host_route(data, dev)))
-    device = wall_ms(lambda: rt.jpeg_decode_u8(data, dev, **kw), reps, 5)
-    host = wall_ms(lambda: host_route(data, dev), reps, 3)
+    device = wall_ms(lambda: rt.jpeg_decode_u8(data, dev, **kw), reps, 5, "both")          # both routes end on the device
+    host = wall_ms(lambda: host_route(data, dev), reps, 3, "both")
     return {"file_bytes": len(data), "restart_interval": restart_interval, "path": report[0]["path"], "rounds": report[0]["rounds"], "same_pixels_as_host": same,
             "kernel_ms": kernel, "device_ms": device, "host_ms": host, "host_over_device": round(host["median"] / device["median"], 2),
-            "device_is_faster": device["median"] + device["iqr"] + host["iqr"] < host["median"]}
+            "device_is_faster": below(device, host)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__, lib=True)
     ap.add_argument("--sweep-reps", type=int, default=40)
-    ap.add_argument("--out", type=str, default=None)
-    ap.add_argument("--lib", type=str, default=None)
     args = ap.parse_args()
-    if args.lib:
-        rt.use_library(os.path.abspath(args.lib))
-    assert torch.cuda.is_available(), "jpeg_decode_bench needs a GPU"
-    torch.cuda.set_device(0)
-    torch.set_num_threads(1)
+    dev = gpu_setup("jpeg_decode_bench", args.lib)
     reps = max(args.reps, 200)
-    dev = torch.device("cuda:0")
     engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     tel = GpuTelemetry(0).start()
-    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "sizes": {}, "chunk_bits": {}, "progressive": {}}
+    res = header(reps=reps, pillow=PIL.__version__, sizes={}, chunk_bits={}, progressive={})
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         frames = {"stylised": engine.stylize_u8(source, alpha=0.5)[0].cpu().numpy(), "noise": np.random.default_rng(0).integers(0, 256, (h, w, 3), dtype=np.uint8)}
@@ -168,7 +131,7 @@ def main():
                     res["chunk_bits"][name] = {}
                     for cb in CHUNKS:
                         rounds = int(launch(cb)[1][0, 1].item())
-                        res["chunk_bits"][name][str(cb)] = dict(event_ms(lambda: launch(cb), max(args.sweep_reps, 8), 3), rounds=rounds, reps=max(args.sweep_reps, 8))
+                        res["chunk_bits"][name][str(cb)] = dict(hashed_event_ms(lambda: launch(cb), max(args.sweep_reps, 8), 3), rounds=rounds, reps=max(args.sweep_reps, 8))
                 print(f"{name}: {json.dumps(res['sizes'][name])} {json.dumps(res['chunk_bits'].get(name))}", file=sys.stderr, flush=True)
             for label, kw in (("default_progressive", {"progressive": True}), ("q95_progressive", {"quality": 95, "progressive": True})):
                 data = jpeg_bytes(frame, **kw)
@@ -181,11 +144,7 @@ def main():
                 print(f"{name}: {json.dumps(res['progressive'][name])}", file=sys.stderr, flush=True)
     res["per_call"] = per_call(reps, dev)
     res["telemetry"] = tel.stop()          # shader clock and power over each kernel timing window (sysfs reads)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -8,12 +8,10 @@ synthetic frame (seed-0 weights) and on uniform noise.  Per call on a batch of -
 and whether the two give the same bytes.  ``device_is_faster``: device_ms sits below host_ms by more than the two interquartile ranges
 combined.  Every kernel_ms also carries the sha256 of its last call's output bytes, so that two builds of the library
 (--lib PATH: that build in place of the package's own) can be held to the same bytes as well as the same time.  Prints one JSON line and, with --out, writes it to a file.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/jpeg_roundtrip_bench.py [--reps 200] [--batch 1] [--lib PATH] [--out profiles/jpeg_roundtrip_bench.json]"""
-import argparse
 import hashlib
-import json
 import os
-import statistics
 import sys
 import time
 
@@ -28,45 +26,18 @@ import applied_image_processing_amd.synth as synth  # noqa: E402
 from applied_image_processing_amd import video  # noqa: E402
 from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
 from applied_image_processing_amd.telemetry import GpuTelemetry  # noqa: E402
+from benchkit import arguments, below, emit, event_times, gpu_setup, header, spread, wall_ms  # noqa: E402
 
 SIZES = [(256, 456), (1080, 1920)]
-
-
-def spread(times):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
 
 
 def sha256(out):
     return hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()
 
 
-def wall_ms(fn, reps, warmup):
-    """fn() ends with its result on the device; the clock stops after a synchronise."""
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t) * 1e3)
-    return spread(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
+def hashed_event_ms(fn, reps, warmup):
+    """The kit's event_ms with the sha256 of the last call's frames beside it."""
+    times, out = event_times(fn, reps, warmup)
     return dict(spread(times), sha256=sha256(out))
 
 
@@ -76,44 +47,31 @@ def host_post(u8):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__, lib=True)
     ap.add_argument("--batch", type=int, default=1)
-    ap.add_argument("--out", type=str, default=None)
-    ap.add_argument("--lib", type=str, default=None)
     args = ap.parse_args()
-    if args.lib:
-        rt.use_library(os.path.abspath(args.lib))
-    assert torch.cuda.is_available(), "jpeg_roundtrip_bench needs a GPU"
-    torch.cuda.set_device(0)
-    torch.set_num_threads(1)
+    dev = gpu_setup("jpeg_roundtrip_bench", args.lib)
     reps, n = max(args.reps, 200), max(args.batch, 1)
-    dev = torch.device("cuda:0")
     engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     tel = GpuTelemetry(0).start()
-    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "batch": n, "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "sizes": {}}
+    res = header(reps=reps, batch=n, pillow=PIL.__version__, sizes={})
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         frames = {"stylised": engine.stylize_u8(source, alpha=0.5).contiguous().expand(n, -1, -1, -1).contiguous(),
                   "noise": torch.from_numpy(np.random.default_rng(0).integers(0, 256, (n, h, w, 3), dtype=np.uint8)).to(dev)}
         for kind, x in frames.items():
             t0 = time.perf_counter()
-            kernel = event_ms(lambda: rt.jpeg_roundtrip_u8(x), reps, 20)
+            kernel = hashed_event_ms(lambda: rt.jpeg_roundtrip_u8(x), reps, 20)
             tel.window(f"kernel_{kind}_{h}x{w}", t0, time.perf_counter())
-            device = wall_ms(lambda: engine.jpeg_roundtrip_u8(x), reps, 5)
-            host = wall_ms(lambda: host_post(x), reps, 3)
+            device = wall_ms(lambda: engine.jpeg_roundtrip_u8(x), reps, 5, "both")          # both routes end on the device
+            host = wall_ms(lambda: host_post(x), reps, 3, "both")
             res["sizes"][f"{kind}_{h}x{w}"] = {"frame_bytes": int(x[0].numel()), "same_bytes_as_host": bool(torch.equal(engine.jpeg_roundtrip_u8(x), host_post(x))),
                                                "kernel_ms": kernel, "device_ms": device, "host_ms": host,
                                                "host_over_device": round(host["median"] / device["median"], 2),
-                                               "device_is_faster": device["median"] + device["iqr"] + host["iqr"] < host["median"]}
+                                               "device_is_faster": below(device, host)}
     res["telemetry"] = tel.stop()          # shader clock and power over each kernel timing window (sysfs reads)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -5,9 +5,8 @@ a disc foreground covering about a third of the frame, on seeded synthetic image
   host_ms    wall time of the host combine_localized (numpy, unchanged by the device path) on the same machine and inputs, median
 Warm-up calls are excluded (20 of the kernel, so that the clock has ramped); each median is over at least 20 calls.  Prints one JSON
 line and, with --out, writes it to a file.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/localized_bench.py [--reps 200] [--host_reps 5] [--out profiles/localized_bench.json]"""
-import argparse
-import json
 import os
 import statistics
 import sys
@@ -22,6 +21,7 @@ import applied_image_processing_amd.runtime as rt  # noqa: E402
 import applied_image_processing_amd.synth as synth  # noqa: E402
 from applied_image_processing_amd import localized as L  # noqa: E402
 from applied_image_processing_amd.telemetry import GpuTelemetry  # noqa: E402
+from benchkit import arguments, emit, event_times, wall_times  # noqa: E402
 
 SIZES = [(250, 333), (512, 512), (1080, 1920)]
 
@@ -35,42 +35,17 @@ def inputs(h, w, seed):
     return np.ascontiguousarray(content), np.ascontiguousarray(stylised), mask
 
 
-def wall_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t) * 1e3)
-    return statistics.median(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return statistics.median(times)
+def median(timed):
+    """This record's own shape: the bare median of a kit loop's (times, result)."""
+    return statistics.median(timed[0])
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__)
     ap.add_argument("--host_reps", type=int, default=5)
-    ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "localized_bench needs a GPU"
-    torch.cuda.set_device(0)
+    torch.cuda.set_device(0)          # its own setup and header: the host's threads are left as they are (omp_num_threads is recorded), and the record names no library
     tel = GpuTelemetry(0).start()
     res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(),
            "omp_num_threads": os.environ.get("OMP_NUM_THREADS"), "reps": args.reps, "host_reps": args.host_reps, "sizes": {}}
@@ -79,19 +54,15 @@ def main():
         dc, ds, dm = (torch.from_numpy(a).cuda() for a in (content, stylised, mask))
         out = torch.empty((h, w, 3), dtype=torch.uint8, device=dc.device)
         t0 = time.perf_counter()
-        kernel = event_ms(lambda: rt.localized_combine_u8(dc, ds, dm, out=out), max(args.reps, 20), 20)
+        kernel = median(event_times(lambda: rt.localized_combine_u8(dc, ds, dm, out=out), max(args.reps, 20), 20))
         tel.window(f"kernel_{h}x{w}", t0, time.perf_counter())
-        device = wall_ms(lambda: L.combine_localized_device(content, stylised, mask), max(args.reps, 20), 3)
-        host = wall_ms(lambda: L.combine_localized(content, stylised, mask), args.host_reps, 1)
+        device = median(wall_times(lambda: L.combine_localized_device(content, stylised, mask), max(args.reps, 20), 3, "both"))
+        host = median(wall_times(lambda: L.combine_localized(content, stylised, mask), args.host_reps, 1, "both"))
         same = int(np.abs(L.combine_localized_device(content, stylised, mask).astype(int) - L.combine_localized(content, stylised, mask).astype(int)).max())
         res["sizes"][f"{h}x{w}"] = {"foreground_pixels": int((mask == 0).sum()), "kernel_ms": round(kernel, 4), "device_ms": round(device, 3),
                                     "host_ms": round(host, 2), "host_over_device": round(host / device, 1), "max_level_difference": same}
     res["telemetry"] = tel.stop()          # shader clock and power over each size's kernel timing (sysfs reads)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -10,14 +10,12 @@ clip, median and interquartile range over --reps calls (>= 200) after warm-up, f
 Neither baseline is the code under test.  ``faster_than_torch_gpu`` / ``slower_than_torch_gpu`` (and ``..._torch_cpu``): device_f32_ms -
 the same input as the baseline's - has its median below (above) the other by more than both interquartile ranges.  Prints one JSON line
 and, with --out, writes it to a file.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/metrics_bench.py [--reps 200] [--cpu_reps 5] [--out profiles/metrics_bench.json]"""
-import argparse
 import json
 import math
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -26,39 +24,9 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 import applied_image_processing_amd.runtime as rt  # noqa: E402
+from benchkit import arguments, below, emit, event_ms, gpu_setup, header, wall_ms  # noqa: E402
 
 CLIPS = [(1, 256, 456), (1, 1080, 1920), (1, 1200, 1600), (64, 135, 240)]
-
-
-def spread(times):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
-
-
-def wall_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        t = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t) * 1e3)
-    return spread(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return spread(times)
 
 
 def window(channel, device):
@@ -81,19 +49,12 @@ def torch_scores(x, y, win):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__)
     ap.add_argument("--cpu_reps", type=int, default=5)
-    ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
-    assert torch.cuda.is_available(), "metrics_bench needs a GPU"
-    torch.cuda.set_device(0)
-    torch.set_num_threads(1)
+    dev = gpu_setup("metrics_bench")
     reps, cpu_reps = max(args.reps, 200), max(3, args.cpu_reps)
-    dev = torch.device("cuda:0")
-    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps, "cpu_reps": cpu_reps,
-           "torch": torch.__version__, "lib": os.path.relpath(rt.LIB_PATH), "tile": list(rt.METRICS_TILE), "clips": {}}
-    below = lambda a, b: a["median"] + a["iqr"] + b["iqr"] < b["median"]
+    res = header(reps=reps, cpu_reps=cpu_reps, torch=torch.__version__, tile=list(rt.METRICS_TILE), clips={})
     for n, h, w in CLIPS:
         rng = np.random.default_rng(n * h * w)
         a = rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
@@ -104,7 +65,7 @@ def main():
         row = {"frames": n, "samples": int(ua.numel()),
                "device_u8_ms": event_ms(lambda: rt.image_metrics(ua, ub), reps, 20), "device_u8_map_ms": event_ms(lambda: rt.image_metrics(ua, ub, True), reps, 20),
                "device_f32_ms": event_ms(lambda: rt.image_metrics(fa, fb), reps, 20), "device_f32_map_ms": event_ms(lambda: rt.image_metrics(fa, fb, True), reps, 20),
-               "torch_gpu_ms": event_ms(lambda: torch_scores(fa, fb, win_gpu), reps, 20), "torch_cpu_ms": wall_ms(lambda: torch_scores(ca, cb, win_cpu), cpu_reps, 1)}
+               "torch_gpu_ms": event_ms(lambda: torch_scores(fa, fb, win_gpu), reps, 20), "torch_cpu_ms": wall_ms(lambda: torch_scores(ca, cb, win_cpu), cpu_reps, 1, "none")}
         got, (want_s, want_p) = rt.image_metrics(fa, fb), torch_scores(fa, fb, win_gpu)
         row["ssim_distance_from_torch_gpu"] = float((got.ssim - want_s.double()).abs().max())
         row["psnr_distance_from_torch_gpu"] = float((got.psnr - want_p.double().reshape(-1)).abs().max())
@@ -113,11 +74,7 @@ def main():
         key = f"near_{n}x{h}x{w}"
         res["clips"][key] = row
         print(key, json.dumps(row), file=sys.stderr, flush=True)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

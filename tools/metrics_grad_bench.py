@@ -11,12 +11,11 @@ loss under PyTorch-ROCm on the same machine, on four float32 RGB clips of unifor
                         its own: no counters, nothing else timed meanwhile), microseconds
 The baseline is not the code under test.  ``device_faster`` / ``device_slower``: device_loss_ms has its median below (above)
 torch_loss_ms by more than both interquartile ranges.  Prints one JSON line and, with --out, writes it to a file.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/metrics_grad_bench.py [--reps 200] [--out profiles/metrics_grad_bench.json]"""
-import argparse
 import json
 import math
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -27,29 +26,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 import applied_image_processing_amd.metrics as M  # noqa: E402
 import applied_image_processing_amd.runtime as rt  # noqa: E402
+from benchkit import arguments, below, emit, event_ms, spread  # noqa: E402
 
 CLIPS = [(1, 256, 456), (1, 1080, 1920), (1, 1200, 1600), (64, 135, 240)]
 KERNELS = ("metrics_tile_kernel", "metrics_combine_kernel")
-
-
-def spread(times, digits=4):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), digits), "iqr": round(q[2] - q[0], digits)}
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return spread(times)
 
 
 def window(channel, device):
@@ -87,17 +67,13 @@ def kernel_records(fn, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--out", type=str, default=None)
-    args = ap.parse_args()
+    args = arguments(__doc__).parse_args()
     assert torch.cuda.is_available(), "metrics_grad_bench needs a GPU"
-    torch.cuda.set_device(0)
+    torch.cuda.set_device(0)          # its own setup and header: the record has no CPU counts, and the host's threads are left as they are
     reps = max(args.reps, 200)
     dev = torch.device("cuda:0")
     res = {"device": torch.cuda.get_device_name(0), "reps": reps, "torch": torch.__version__, "lib": os.path.relpath(rt.LIB_PATH), "tile": list(rt.METRICS_TILE),
            "clips": {}}
-    below = lambda a, b: a["median"] + a["iqr"] + b["iqr"] < b["median"]
     M.set_device_backward(True)
     for n, h, w in CLIPS:
         rng = np.random.default_rng(n * h * w)
@@ -132,11 +108,7 @@ def main():
         res["clips"][key] = row
         print(key, json.dumps(row), file=sys.stderr, flush=True)
     M.set_device_backward(False)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -11,10 +11,9 @@ HIP events around each call, medians and interquartile ranges of --reps calls af
 shape's window; each row also carries the sha256 of its last call's output bytes, so that two builds of the library (--lib PATH: that
 build in place of the package's own) can be held to the same bytes as well as the same time.  Prints one JSON line and, with --out,
 writes it to a file.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/mix_bench.py [--reps 200] [--lib PATH] [--out profiles/mix_bench.json]"""
-import argparse
 import hashlib
-import json
 import os
 import statistics
 import sys
@@ -26,6 +25,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 import applied_image_processing_amd.runtime as rt  # noqa: E402
 from applied_image_processing_amd.telemetry import GpuTelemetry  # noqa: E402
+from benchkit import arguments, emit, event_times  # noqa: E402
 
 SHAPES = [("256x456", 1, 32, 57), ("1080x1920", 1, 135, 240), ("8x1080x1920", 8, 135, 240)]
 KS = [1, 2, 4, 16]
@@ -33,24 +33,14 @@ C = 512
 
 
 def summary(times, out):
+    """This record's own shape: the quartiles themselves, and the sha256 of the last call's output."""
     q = statistics.quantiles(times, n=4)
     return {"median_ms": round(statistics.median(times), 4), "iqr_ms": [round(q[0], 4), round(q[2], 4)],
             "sha256": hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()}
 
 
-def event_ms(fn, reps, warmup=20):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return summary(times, out)
+def form_ms(fn, reps, warmup=20):
+    return summary(*event_times(fn, reps, warmup))
 
 
 def emulation(x, cm, cs, sm, ss, w, alpha):
@@ -66,15 +56,11 @@ def iqr(s):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--out", type=str, default=None)
-    ap.add_argument("--lib", type=str, default=None)
-    args = ap.parse_args()
+    args = arguments(__doc__, lib=True).parse_args()
     if args.lib:
         rt.use_library(os.path.abspath(args.lib))
     assert torch.cuda.is_available(), "mix_bench needs a GPU"
-    torch.cuda.set_device(0)
+    torch.cuda.set_device(0)          # its own setup and header: the record has no CPU counts, and the host's threads are left as they are
     reps = max(args.reps, 8)
     g = torch.Generator().manual_seed(0)
     rand = lambda *s: torch.rand(*s, generator=g).cuda()
@@ -85,15 +71,15 @@ def main():
         cm, cs = rand(n, C), rand(n, C) + 0.5
         sm, ss = rand(max(KS), C), rand(max(KS), C) + 0.5
         t0 = time.perf_counter()
-        row = {"elements": x.numel(), "blend_alpha": event_ms(lambda: rt.blend_alpha(x, True, cm, cs, sm[:1], ss[:1], 0.6), reps)}
+        row = {"elements": x.numel(), "blend_alpha": form_ms(lambda: rt.blend_alpha(x, True, cm, cs, sm[:1], ss[:1], 0.6), reps)}
         for k in KS:
             w = (rand(k) / k).contiguous()
             maps = (rand(n, k, hc, wc) / k).contiguous()
             smk, ssk = sm[:k].contiguous(), ss[:k].contiguous()
-            row[f"mix_scalar_{k}"] = event_ms(lambda: rt.blend_mix(x, True, cm, cs, smk, ssk, w, alpha=0.6), reps)
-            row[f"mix_maps_{k}"] = event_ms(lambda: rt.blend_mix(x, True, cm, cs, smk, ssk, maps, alpha=0.6), reps)
+            row[f"mix_scalar_{k}"] = form_ms(lambda: rt.blend_mix(x, True, cm, cs, smk, ssk, w, alpha=0.6), reps)
+            row[f"mix_maps_{k}"] = form_ms(lambda: rt.blend_mix(x, True, cm, cs, smk, ssk, maps, alpha=0.6), reps)
             wl = [float(v) for v in w.cpu()]
-            row[f"emulation_{k}"] = event_ms(lambda: emulation(x, cm, cs, smk, ssk, wl, 0.6), reps)
+            row[f"emulation_{k}"] = form_ms(lambda: emulation(x, cm, cs, smk, ssk, wl, 0.6), reps)
         tel.window(name, t0, time.perf_counter())
         a, b4 = row["blend_alpha"], row["mix_scalar_4"]
         row["mix_scalar_4_within_both_iqrs_of_blend_alpha"] = bool(abs(b4["median_ms"] - a["median_ms"]) <= iqr(a) + iqr(b4))
@@ -104,11 +90,7 @@ def main():
         row["blend_alpha_gb_per_s"] = round(8 * x.numel() / (a["median_ms"] * 1e-3) / 1e9, 1)
         res["shapes"][name] = row
     res["telemetry"] = tel.stop()
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -10,12 +10,11 @@ with the three files' sizes beside the times, and whether the device's file deco
 ``faster_than_pillow`` / ``faster_than_pillow_l1``: the device median sits below Pillow's by more than both interquartile ranges.
 With --job, a 64-view 1200 x 1600 precompute_guides_sharded(save_ext=".png") into a temporary directory with png_on_device off and on:
 wall time, the sink's wait and the bytes that crossed to the host.  Prints one JSON line and, with --out, writes it to a file.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/png_bench.py [--reps 200] [--pillow_reps N] [--job] [--out profiles/png_bench.json]"""
-import argparse
 import io
 import json
 import os
-import statistics
 import sys
 import tempfile
 import time
@@ -31,41 +30,9 @@ import applied_image_processing_amd.runtime as rt  # noqa: E402
 import applied_image_processing_amd.synth as synth  # noqa: E402
 from applied_image_processing_amd import jobs  # noqa: E402
 from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
+from benchkit import arguments, below, emit, event_ms, gpu_setup, header, wall_ms  # noqa: E402
 
 SIZES = [(256, 456), (1080, 1920), (1200, 1600)]
-
-
-def spread(times):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
-
-
-def wall_ms(fn, reps, warmup, sync):
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        if sync:
-            torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t) * 1e3)
-    return spread(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return spread(times)
 
 
 def pillow_bytes(a, **kw):
@@ -86,15 +53,14 @@ def compare(x, reps, pillow_reps):
     encode = lambda: rt.png_encode_u8(x)
     host = x[0].cpu().numpy()
     kernel = event_ms(encode, reps, 20)
-    device = wall_ms(lambda: rt.png_files(*encode()), reps, 5, True)
-    pillow = wall_ms(lambda: pillow_bytes(host), pillow_reps, 1, False)
-    fast = wall_ms(lambda: pillow_bytes(host, compress_level=1), pillow_reps, 1, False)
+    device = wall_ms(lambda: rt.png_files(*encode()), reps, 5, "before")
+    pillow = wall_ms(lambda: pillow_bytes(host), pillow_reps, 1, "none")
+    fast = wall_ms(lambda: pillow_bytes(host, compress_level=1), pillow_reps, 1, "none")
     data, = rt.png_files(*encode())
-    faster = lambda other: device["median"] + device["iqr"] + other["iqr"] < other["median"]
     return {"frame_bytes": int(x.numel()), "file_bytes": len(data), "pillow_file_bytes": len(pillow_bytes(host)),
             "pillow_l1_file_bytes": len(pillow_bytes(host, compress_level=1)), "decodes_to_the_frame": bool(np.array_equal(np.asarray(Image.open(io.BytesIO(data))), host)),
             "kernel_ms": kernel, "device_ms": device, "pillow_ms": pillow, "pillow_l1_ms": fast, "pillow_reps": pillow_reps,
-            "faster_than_pillow": faster(pillow), "faster_than_pillow_l1": faster(fast)}
+            "faster_than_pillow": below(device, pillow), "faster_than_pillow_l1": below(device, fast)}
 
 
 def guide_job(engine, on, views, style, sub_batch):
@@ -110,23 +76,17 @@ def guide_job(engine, on, views, style, sub_batch):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__)
     ap.add_argument("--pillow_reps", type=int, default=None)
     ap.add_argument("--job", action="store_true")
     ap.add_argument("--views", type=int, default=64)
-    ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
-    assert torch.cuda.is_available(), "png_bench needs a GPU"
-    torch.cuda.set_device(0)
-    torch.set_num_threads(1)
+    dev = gpu_setup("png_bench")
     reps = max(args.reps, 200)
     pillow_reps = max(4, args.pillow_reps or reps)
-    dev = torch.device("cuda:0")
     engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
-    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "sizes": {}}
+    res = header(reps=reps, pillow=PIL.__version__, sizes={})
     for h, w in SIZES:
         source = torch.from_numpy((synth.image(7, 1, h, w)[0].transpose(1, 2, 0) * np.float32(255)).astype(np.uint8)[None]).to(dev)
         gradient = noisy_gradient(h, w)
@@ -144,11 +104,7 @@ def main():
         guide_job(engine, False, views[:4], style, 4)                     # warm-up: workspaces, pinned buffers, clocks
         guide_job(engine, True, views[:4], style, 4)
         res["guide_job_64x1200x1600"] = {"views": len(views), "off": guide_job(engine, False, views, style, 4), "on": guide_job(engine, True, views, style, 4)}
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -11,14 +11,13 @@ with the deflate blocks the device read, whether the two give the same pixels, a
 more than the two interquartile ranges combined.  With --job, a 64-view ``precompute_guides_sharded`` from .png paths (copies of the
 fixture view) with ``png_decode_on_device`` off and on: wall, the time the compute loop waited for the feeder, and the bytes that went
 to the device (the feeder's uploads, and with the switch on the files).  Prints one JSON line and, with --out, writes it.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/png_decode_bench.py [--reps 200] [--batch-reps 200] [--job] [--out profiles/png_decode_bench.json]"""
-import argparse
 import ctypes
 import io
 import json
 import os
 import shutil
-import statistics
 import sys
 import tempfile
 import threading
@@ -38,42 +37,9 @@ import applied_image_processing_amd.synth as synth  # noqa: E402
 from applied_image_processing_amd import jobs  # noqa: E402
 from applied_image_processing_amd.AdaIN import test as adain_test  # noqa: E402
 from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
+from benchkit import arguments, below, emit, event_ms, gpu_setup, header, spread, wall_ms  # noqa: E402
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "png", "view_800.png")
-
-
-def spread(times):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
-
-
-def wall_ms(fn, reps, warmup):
-    """fn() ends with its result on the device; the clock stops after a synchronise."""
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t) * 1e3)
-    return spread(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return spread(times)
 
 
 def host_route(datas, dev):
@@ -139,12 +105,11 @@ def row(datas, reps, dev):
     launch = resident_call(parsed, dev)
     kernel = event_ms(launch, reps, 5)
     stages = stage_ms(launch, min(reps, 20))
-    device =wall_ms(lambda: rt.png_decode_u8(datas, dev, mode="RGB"), reps, 3)
-    host = wall_ms(lambda: host_route(datas, dev), reps, 2)
+    device = wall_ms(lambda: rt.png_decode_u8(datas, dev, mode="RGB"), reps, 3, "both")          # both routes end on the device
+    host = wall_ms(lambda: host_route(datas, dev), reps, 2, "both")
     return {"files": len(datas), "file_bytes": sum(len(d) for d in datas), "frame_bytes": sum(int(g.numel()) for g in got), "reps": reps,
             "path": report[0]["path"], "blocks": report[0]["blocks"], "same_pixels_as_host": same, "kernel_ms": kernel, "stage_ms": stages, "device_ms": device, "host_ms": host,
-            "host_over_device": round(host["median"] / device["median"], 2), "device_is_faster": device["median"] + device["iqr"] + host["iqr"] < host["median"],
-            "device_is_slower": host["median"] + device["iqr"] + host["iqr"] < device["median"]}
+            "host_over_device": round(host["median"] / device["median"], 2), "device_is_faster": below(device, host), "device_is_slower": below(host, device)}
 
 
 def guide_job(engine, on, views, style, sub_batch):
@@ -173,19 +138,14 @@ def guide_job(engine, on, views, style, sub_batch):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__)
     ap.add_argument("--batch-reps", type=int, default=200)
     ap.add_argument("--large-reps", type=int, default=200, help="calls of the 1080 x 1920 rows")
     ap.add_argument("--job", action="store_true")
     ap.add_argument("--views", type=int, default=64)
-    ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
-    assert torch.cuda.is_available(), "png_decode_bench needs a GPU"
-    torch.cuda.set_device(0)
-    torch.set_num_threads(1)
+    dev = gpu_setup("png_decode_bench")
     reps = max(args.reps, 200)
-    dev = torch.device("cuda:0")
     engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
     with open(FIXTURE, "rb") as f:
@@ -195,8 +155,7 @@ def main():
     by_pillow = io.BytesIO()
     Image.fromarray(stylised[0].cpu().numpy()).save(by_pillow, format="PNG")
     by_device, = rt.png_files(*rt.png_encode_u8(stylised))
-    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "pillow": PIL.__version__,
-           "lib": os.path.relpath(rt.LIB_PATH), "rows": {}}
+    res = header(pillow=PIL.__version__, rows={})
     for name, datas, n in (("view_800x800", [view], reps), ("view_800x800_x64", [view] * 64, max(args.batch_reps, 8)),
                            ("stylised_1080x1920_pillow", [by_pillow.getvalue()], max(args.large_reps, 8)),
                            ("stylised_1080x1920_device", [by_device], max(args.large_reps, 8))):
@@ -213,11 +172,7 @@ def main():
                 guide_job(engine, on, views[:8], style, 8)                   # warm-up: workspaces, pinned buffers, clocks
             res["job"] = {"views": args.views, "sub_batch": 8, "off": [guide_job(engine, False, views, style, 8) for _ in range(3)],
                           "on": [guide_job(engine, True, views, style, 8) for _ in range(3)]}
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -10,15 +10,13 @@ over --reps calls (>= 200) after warm-up; Pillow's over --pillow_reps (the numbe
   gif    : gif_file.write_gif(frames, path, "adaptive-local") from the device clip to the file (a temporary file, read back) against
            Pillow's save(save_all=True) of the same RGB frames to BytesIO - what the reference's create_gif does - with both files' sizes
 ``faster`` / ``slower``: one median sits below the other by more than both interquartile ranges.  Prints one JSON line; --out writes it.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/quantize_bench.py [--reps 200] [--pillow_reps 20] [--out profiles/quantize_bench.json]"""
-import argparse
 import io
 import json
 import os
-import statistics
 import sys
 import tempfile
-import time
 
 import numpy as np
 import PIL
@@ -31,46 +29,10 @@ import applied_image_processing_amd.runtime as rt  # noqa: E402
 import applied_image_processing_amd.synth as synth  # noqa: E402
 from applied_image_processing_amd import gif_file  # noqa: E402
 from applied_image_processing_amd.engine import AdaINEngine  # noqa: E402
+from benchkit import arguments, below, emit, event_ms, gpu_setup, header, spread, wall_ms  # noqa: E402
 
 KS = (16, 256)
 STAGES = {"hist": "quantize_hist_kernel", "sat": "quantize_sat_kernel", "cut": "quantize_cut_kernel"}
-
-
-def spread(times):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
-
-
-def below(a, b):
-    return a["median"] + a["iqr"] + b["iqr"] < b["median"]
-
-
-def wall_ms(fn, reps, warmup, sync):
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        if sync:
-            torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t) * 1e3)
-    return spread(times)
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return spread(times)
 
 
 def stage_ms(fn, reps):
@@ -98,7 +60,7 @@ def stage_ms(fn, reps):
 
 def pillow_ms(frames, K, method, reps):
     images = [Image.fromarray(f) for f in frames]
-    return wall_ms(lambda: [im.quantize(K, method=method, dither=Image.Dither.NONE) for im in images], reps, 1, False)
+    return wall_ms(lambda: [im.quantize(K, method=method, dither=Image.Dither.NONE) for im in images], reps, 1, "none")
 
 
 def chooser(x, host, per_frame, reps, pillow_reps):
@@ -131,7 +93,7 @@ def gif(x, host, reps, pillow_reps):
             images[0].save(f, format="GIF", save_all=True, append_images=images[1:], duration=50, loop=0)
             return f.getvalue()
 
-        a, b = wall_ms(ours, reps, 3, True), wall_ms(pillows, pillow_reps, 1, False)
+        a, b = wall_ms(ours, reps, 3, "before"), wall_ms(pillows, pillow_reps, 1, "none")
         data = ours()
         im = Image.open(io.BytesIO(data))
         return {"frames": len(host), "device_ms": a, "pillow_ms": b, "file_bytes": len(data), "pillow_file_bytes": len(pillows()), "frames_in_file": im.n_frames,
@@ -139,16 +101,11 @@ def gif(x, host, reps, pillow_reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__)
     ap.add_argument("--pillow_reps", type=int, default=20)
-    ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
-    assert torch.cuda.is_available(), "quantize_bench needs a GPU"
-    torch.cuda.set_device(0)
-    torch.set_num_threads(1)
+    dev = gpu_setup("quantize_bench")
     reps, pillow_reps = max(args.reps, 200), max(4, args.pillow_reps)
-    dev = torch.device("cuda:0")
     engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
 
@@ -160,8 +117,7 @@ def main():
             parts.append(engine.stylize_u8(source, alpha=0.5).contiguous())
         return torch.cat(parts).contiguous()
 
-    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "cpus_machine": os.cpu_count(), "reps": reps,
-           "pillow_reps": pillow_reps, "pillow": PIL.__version__, "lib": os.path.relpath(rt.LIB_PATH), "frames": {}, "clips": {}}
+    res = header(reps=reps, pillow_reps=pillow_reps, pillow=PIL.__version__, frames={}, clips={})
     h, w = 1080, 1920
     sources = {"stylised": stylised(1, h, w), "noise": torch.from_numpy(np.random.default_rng(5).integers(0, 256, (1, h, w, 3), dtype=np.uint8)).to(dev),
                "flat": torch.full((1, h, w, 3), 255, dtype=torch.uint8, device=dev)}
@@ -177,11 +133,7 @@ def main():
         res["clips"][mode] = chooser(clip, host, per_frame, reps, pillow_reps)
         print(mode, json.dumps(res["clips"][mode]), file=sys.stderr, flush=True)
     res["gif_adaptive_local"] = gif(clip, host, reps, pillow_reps)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

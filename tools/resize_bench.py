@@ -11,17 +11,15 @@ calls (>= 200):
 ``same_bytes``: the device frame is Pillow's.  ``device_faster`` / ``cold_device_faster``: the device median sits below the host's by more than
 both interquartile ranges; ``host_faster``: the other way round; ``two_pass_faster`` / ``one_pass_faster`` likewise between the two BILINEAR
 kernels.  Prints one JSON line and, with --out, writes it to a file after every cell.  --filters / --sizes narrow a run.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
 Usage: python tools/resize_bench.py [--reps 200] [--out profiles/resize_bench.json]"""
 import os
 
 for _v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):          # before NumPy loads: the host form runs on one thread
     os.environ[_v] = "1"
 
-import argparse  # noqa: E402
 import json  # noqa: E402
-import statistics  # noqa: E402
 import sys  # noqa: E402
-import time  # noqa: E402
 
 import numpy as np  # noqa: E402
 import PIL  # noqa: E402
@@ -34,62 +32,21 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import applied_image_processing_amd.runtime as rt  # noqa: E402
 import pil_resize_ref as R  # noqa: E402
+from benchkit import arguments, below, emit, event_ms, gpu_setup, header, wall_ms, write  # noqa: E402
 
 # name -> ((h, w) of the source, (width, height) asked for)
 SIZES = {"1080p_to_455x256": ((1080, 1920), (455, 256)), "1080p_to_960x540": ((1080, 1920), (960, 540)), "1080p_div8": ((1080, 1920), (240, 135)),
          "1080p_div99": ((1080, 1920), (19, 10)), "256x456_to_1080p": ((256, 456), (1920, 1080))}
 
 
-def spread(times):
-    q = statistics.quantiles(times, n=4)
-    return {"median": round(statistics.median(times), 4), "iqr": round(q[2] - q[0], 4)}
-
-
-def event_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return spread(times)
-
-
-def wall_ms(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(reps):
-        t = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t) * 1e3)
-    return spread(times)
-
-
-def below(a, b):
-    """a's median sits below b's by more than both interquartile ranges."""
-    return bool(a["median"] + a["iqr"] + b["iqr"] < b["median"])
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
+    ap = arguments(__doc__)
     ap.add_argument("--filters", default=",".join(R.FILTERS))
     ap.add_argument("--sizes", default=",".join(SIZES))
-    ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
-    assert torch.cuda.is_available(), "resize_bench needs a GPU"
-    torch.cuda.set_device(0)
-    torch.set_num_threads(1)
+    dev = gpu_setup("resize_bench")
     reps = max(args.reps, 200)
-    dev = torch.device("cuda:0")
-    res = {"device": torch.cuda.get_device_name(0), "cpus_usable": len(os.sched_getaffinity(0)), "pillow": PIL.__version__, "reps": reps,
-           "lib": os.path.relpath(rt.LIB_PATH), "cells": {}}
+    res = header(pillow=PIL.__version__, reps=reps, cells={})
     for size_name in args.sizes.split(","):
         hw, size = SIZES[size_name]
         frame = R.picture(1, *hw)
@@ -107,8 +64,8 @@ def main():
             want = np.asarray(image.resize(size, f))
             cell = {"same_bytes": bool(np.array_equal(rt.resize_pil_u8(x, size, f)[0].cpu().numpy(), want))}
             cell["kernels_ms"] = event_ms(lambda: rt.resize_pil_u8(x, size, f), reps, 5)
-            cell["cold_ms"] = wall_ms(cold, reps, 3)
-            cell["host_ms"] = wall_ms(lambda: image.resize(size, f), reps, 3)
+            cell["cold_ms"] = wall_ms(cold, reps, 3, "none")          # cold() ends with its own synchronise
+            cell["host_ms"] = wall_ms(lambda: image.resize(size, f), reps, 3, "none")
             cell["device_faster"], cell["host_faster"] = below(cell["kernels_ms"], cell["host_ms"]), below(cell["host_ms"], cell["kernels_ms"])
             cell["cold_device_faster"] = below(cell["cold_ms"], cell["host_ms"])
             if f == R.BILINEAR:
@@ -116,10 +73,8 @@ def main():
                 cell["two_pass_faster"], cell["one_pass_faster"] = below(cell["kernels_ms"], cell["one_pass_ms"]), below(cell["one_pass_ms"], cell["kernels_ms"])
             res["cells"][label] = cell
             print(label, json.dumps(cell), file=sys.stderr, flush=True)
-            if args.out:          # a run that is cut short keeps the cells it finished
-                with open(args.out, "w") as fh:
-                    fh.write(json.dumps(res) + "\n")
-    print(json.dumps(res))
+            write(json.dumps(res), args.out)          # a run that is cut short keeps the cells it finished
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

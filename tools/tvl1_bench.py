@@ -2,8 +2,9 @@
 1080p (preparation of both frames + the flow), a 256^2 clip through TVL1Sequence.batch (pairs/s), the inner steps each (scale, warp)
 executed for those inputs, the time per executed step, and the cost of the host's stop reads (two runs with the same launches,
 with and without the reads).  Prints one JSON line; the GPU's clock and power are read with amd-smi
-when it is there.  No cv2 baseline exists on any machine of this project.  Usage: python tools/tvl1_bench.py [--frames 64] [--reps 3]"""
-import argparse
+when it is there.  No cv2 baseline exists on any machine of this project.
+The timing loops, the statistic and the verdict's rule are tools/benchkit.py's.
+Usage: python tools/tvl1_bench.py [--frames 64] [--reps 3]"""
 import json
 import os
 import subprocess
@@ -14,20 +15,9 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import farneback_ref as F  # noqa: E402
+from benchkit import arguments, emit, event_mean_ms  # noqa: E402
 
 from applied_image_processing_amd import tvl1  # noqa: E402
-
-
-def timed(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def clock_power():
@@ -39,9 +29,9 @@ def clock_power():
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = arguments(__doc__)
     ap.add_argument("--frames", type=int, default=64)
-    ap.add_argument("--reps", type=int, default=3)
+    ap.set_defaults(reps=3)
     args = ap.parse_args()
     torch.cuda.set_device(0)
     res = {}
@@ -53,8 +43,8 @@ def main():
         it = torch.zeros((1, len(t.scales), t.P.warps), dtype=torch.int32, device="cuda")
         out = torch.empty(1, 2, h, w, device="cuda")
         calc = tvl1.DualTVL1OpticalFlow_create().calc
-        pair_ms = timed(lambda: calc(a, b), args.reps)
-        flow_ms = timed(lambda: t.flows([pa], [pb], out=out, iters_out=it), args.reps)
+        pair_ms = event_mean_ms(lambda: calc(a, b), args.reps)
+        flow_ms = event_mean_ms(lambda: t.flows([pa], [pb], out=out, iters_out=it), args.reps)
         steps = int(it.sum().item())
         res[f"{w}x{h}"] = {"pair_ms": round(pair_ms, 3), "flow_ms": round(flow_ms, 3), "inner_steps": steps,
                            "us_per_step": round(1000 * flow_ms / max(steps, 1), 2), "iters": it[0].cpu().tolist()}
@@ -62,7 +52,7 @@ def main():
     clip = [torch.from_numpy(F.texture(256, 256, (0.8 * i, 0.3 * i), seed=2)).cuda() for i in range(n)]
     out = torch.empty(n - 1, 2, 256, 256, device="cuda")
     seq = tvl1.TVL1Sequence()
-    ms = timed(lambda: seq.batch(clip, out=out), 1)
+    ms = event_mean_ms(lambda: seq.batch(clip, out=out), 1)
     t = tvl1.TVL1(256, 256)
     m = min(t.default_max_pairs(), n - 1)
     prep = t.prepare(torch.stack(clip[:m + 1]))
@@ -81,13 +71,13 @@ def main():
             tr = tvl1.TVL1(256, 256, epsilon=0.0, medianFiltering=1, outerIterations=outer, innerIterations=inner)
             pr = tr.prepare(torch.stack(clip[:npairs + 1]))
             o = torch.empty(npairs, 2, 256, 256, device="cuda")
-            ts[outer] = timed(lambda: tr.flows([pr[j] for j in range(npairs)], [pr[j + 1] for j in range(npairs)], out=o), args.reps)
+            ts[outer] = event_mean_ms(lambda: tr.flows([pr[j] for j in range(npairs)], [pr[j + 1] for j in range(npairs)], out=o), args.reps)
         nreads = len(tr.scales) * tr.P.warps * 9
         reads[f"pairs_{npairs}"] = {"ms_with_reads": round(ts[10], 3), "ms_without": round(ts[1], 3), "reads": nreads,
                                     "us_per_read": round(1000 * (ts[10] - ts[1]) / nreads, 2)}
     res["stop_reads_256"] = reads
     res["gpu"] = clock_power()
-    print(json.dumps(res))
+    emit(res, args.out)
 
 
 if __name__ == "__main__":
