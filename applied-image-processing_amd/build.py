@@ -12,7 +12,7 @@ CSRC = os.path.join(PKG, "csrc")
 INC = os.path.join(os.path.dirname(PKG), "include")
 LIB = os.path.join(PKG, "libadain_hip.so")
 # The direct implicit-GEMM and F(2x2,3x3) families of rounds 1-2 were retired in round 6 (git history).
-SOURCES = ["conv_edge.hip", "conv_wino4.hip", "stats.hip", "pixel.hip", "resample.hip", "resample_filters.hip", "flow.hip", "tvl1.hip", "colour.hip", "coral.hip", "jpeg.hip", "jpeg_decode.hip", "png.hip", "png_decode.hip", "palette.hip", "gif.hip", "quantize.hip", "metrics.hip", "api.hip"]
+SOURCES = ["conv_edge.hip", "conv_wino4.hip", "stats.hip", "pixel.hip", "resample.hip", "resample_filters.hip", "flow.hip", "tvl1.hip", "colour.hip", "coral.hip", "jpeg.hip", "jpeg_decode.hip", "png.hip", "png_decode.hip", "palette.hip", "gif.hip", "quantize.hip", "metrics.hip", "guide_loss.hip", "api.hip"]
 # -fvisibility=hidden: the shared library exports the C ABI of include/adain_hip.h (ADAIN_API) and nothing else
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # The MFMA kernels carry their fp32 vector-ALU work (input transform, epilogues) next to the matrix instructions, where
@@ -26,9 +26,10 @@ NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # palette.hip keeps numpy's float32 operations of the error diffusion apart (product, then add), as tests/palette_ref.py has them;
 # resample_filters.hip builds Pillow's tap tables on the host in double, one operation at a time (pil_taps.h has the pragma as well);
 # metrics.hip writes its fused operations out (fmaf in the two window passes) and keeps the SSIM map's products and sums apart, so that
-# both inputs run one instruction sequence and equal frames score exactly 1
+# both inputs run one instruction sequence and equal frames score exactly 1; guide_loss.hip keeps the bilinear taps' products and sums
+# apart, so that its resampled guide is adain_u8_to_f32 then adain_resize_bilinear bit for bit
 NO_CONTRACT = ["-ffp-contract=off"]
-EXTRA_FLAGS = {"conv_wino4.hip": NO_PACKED_F32, "flow.hip": NO_CONTRACT, "tvl1.hip": NO_CONTRACT, "colour.hip": NO_CONTRACT, "coral.hip": NO_CONTRACT, "palette.hip": NO_CONTRACT, "resample_filters.hip": NO_CONTRACT, "metrics.hip": NO_CONTRACT}
+EXTRA_FLAGS = {"conv_wino4.hip": NO_PACKED_F32, "flow.hip": NO_CONTRACT, "tvl1.hip": NO_CONTRACT, "colour.hip": NO_CONTRACT, "coral.hip": NO_CONTRACT, "palette.hip": NO_CONTRACT, "resample_filters.hip": NO_CONTRACT, "metrics.hip": NO_CONTRACT, "guide_loss.hip": NO_CONTRACT}
 
 
 def _hipcc():

@@ -662,6 +662,19 @@ int adain_image_metrics_grad_f32(const float* a, const float* b, int n, int c, i
     return launch_image_metrics_grad_f32(a, b, n, c, h, w, weights, grad_a, grad_b, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// train.py's guide-view loss (Style_3DGS/train.py:208-221) and its gradient: the launchers refuse everything themselves
+int adain_guide_l1_f32_bytes(int n, int h, int w, size_t* workspace_bytes) {
+    return guide_l1_f32_bytes(n, h, w, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
+}
+int adain_guide_l1_f32(const float* image, const uint8_t* guide, int n, int h, int w, int gh, int gw, double* out, float* resampled, void* workspace,
+                       size_t workspace_bytes, adain_stream_t stream) {
+    return launch_guide_l1_f32(image, guide, n, h, w, gh, gw, out, resampled, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int adain_guide_l1_grad_f32(const float* image, const uint8_t* guide, int n, int h, int w, int gh, int gw, const double* weights, float* grad,
+                            adain_stream_t stream) {
+    return launch_guide_l1_grad_f32(image, guide, n, h, w, gh, gw, weights, grad, (hipStream_t)stream);
+}
+
 int adain_jpeg_roundtrip_u8_bytes(int n, int h, int w, int c, size_t* workspace_bytes) {
     return jpeg_roundtrip_bytes(n, h, w, c, workspace_bytes) ? ADAIN_EINVAL : ADAIN_OK;
 }

@@ -273,6 +273,13 @@ int image_metrics_grad_f32_bytes(int n, int c, int h, int w, int with_grad_b, si
 int launch_image_metrics_grad_f32(const float* a, const float* b, int n, int c, int h, int w, const double* weights, float* grad_a, float* grad_b,
                                   void* workspace, size_t workspace_bytes, hipStream_t s);
 
+// guide_loss.hip: train.py's l1_loss of a render against its uint8 guide view, resampled on the fly, and its gradient (the rules: top of
+// guide_loss.hip, tests/guide_loss_ref.py); the launchers refuse everything themselves
+int guide_l1_f32_bytes(int n, int h, int w, size_t* workspace_bytes);
+int launch_guide_l1_f32(const float* image, const uint8_t* guide, int n, int h, int w, int gh, int gw, double* out, float* resampled, void* workspace,
+                        size_t workspace_bytes, hipStream_t s);
+int launch_guide_l1_grad_f32(const float* image, const uint8_t* guide, int n, int h, int w, int gh, int gw, const double* weights, float* grad, hipStream_t s);
+
 // coral.hip: coral(style, content) of the colour-preserving path (function.py:26-67)
 size_t coral_workspace_bytes(int n, int style_n, int hs, int ws, int hc, int wc);
 int launch_coral(const void* style, int style_is_u8, int style_n, int hs, int ws, const void* content, int content_is_u8, int n, int hc, int wc,

@@ -240,6 +240,17 @@ class AdaINEngine:
         ``runtime.image_metrics_grad``)."""
         return rt.image_metrics_grad(a, b, weights, grad_b)
 
+    def guide_l1(self, image, guide_u8, resampled=False):
+        """A render float32 [n,3,h,w] and its guide views uint8 [n,gh,gw,3] on the device -> train.py's ``l1_loss`` against the guide
+        bilinearly resized to the render, per frame as float64 [n], with ``resampled`` the resized guide as well (adain_guide_l1_f32;
+        ``runtime.guide_l1``)."""
+        return rt.guide_l1(image, guide_u8, resampled)
+
+    def guide_l1_grad(self, image, guide_u8, weights):
+        """The same inputs and ``weights`` float64 [n], the upstream gradient of every frame's l1 -> the float32 gradient by the render
+        (adain_guide_l1_grad_f32; ``runtime.guide_l1_grad``)."""
+        return rt.guide_l1_grad(image, guide_u8, weights)
+
     def gif_encode_u8(self, index_u8, K, delay_cs):
         """Palette index planes uint8 [n,h,w] on the device, every index below ``K`` -> the frames' GIF records (adain_gif_encode_u8;
         ``runtime.gif_encode_u8``) as (records, lengths) on the device; ``gif_file.assemble`` makes the file of them and only the records

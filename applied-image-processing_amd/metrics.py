@@ -14,6 +14,12 @@ one of them needs a gradient, go through one ``torch.autograd.Function`` whose f
 chains through its ``mse`` in torch.  ``dssim_loss`` is train.py's expression as one forward and one backward call.  The function is
 once differentiable; with the switch off (the default) a tensor that needs a gradient takes the torch route exactly as before.
 
+The second phase of train.py (lines 208-221: ``l1_loss`` of the render against the stylised guide view, read from its file and
+``F.interpolate``d to the render's size every iteration) is ``guide_l1_loss`` and ``GuideBank``: the guides stay uint8 on the device at
+their own size, and GPU tensors go through one ``torch.autograd.Function`` whose forward is ``runtime.guide_l1`` and whose backward is
+``runtime.guide_l1_grad`` (adain_guide_l1_f32 / adain_guide_l1_grad_f32: resample, difference, reduction and gradient fused).  It is a
+new function, so it needs no switch.
+
 LPIPS comes by provider only: ``evaluate(paths, lpips_fn=...)`` with a callable (render, gt) -> value on [1,3,H,W] tensors in [0,1].  Its
 VGG weights are a network fetch, as those of the other networks are, and are not part of this package.
 """
@@ -164,6 +170,114 @@ def psnr(img1, img2):
     if _device_pair(img1, img2):
         return _records(img1, img2).psnr.to(torch.float32)[:, None]
     return 20 * torch.log10(1.0 / torch.sqrt(mse(img1, img2)))
+
+
+# --- the guide-view loss of Style_3DGS/train.py:208-221 ---------------------------------------------------------------------------------------
+class _GuideL1(torch.autograd.Function):
+    """(image float32 [N,3,H,W] or [3,H,W], guide uint8 [N,gh,gw,3] or [gh,gw,3]) on the device -> train.py's ``Ll1``, 0-d float32: the
+    mean of the frames' float64 l1 (``runtime.guide_l1``), cast once.  The backward hands the incoming scalar / N to
+    ``runtime.guide_l1_grad`` as every frame's weight.  Only ``image`` gets a gradient.  The mean and the cast are inside the function,
+    so the graph of a training step holds this one node."""
+
+    @staticmethod
+    def forward(ctx, image, guide):
+        from . import runtime as rt
+
+        ctx.save_for_backward(image, guide)
+        l1 = rt.guide_l1(image, guide).l1
+        return (l1[0] if l1.shape[0] == 1 else l1.mean()).to(torch.float32)          # frames of one size: the mean of their means
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        from . import runtime as rt
+
+        image, guide = ctx.saved_tensors
+        n = image.shape[0] if image.dim() == 4 else 1
+        weights = grad.to(torch.float64).reshape(1)
+        return rt.guide_l1_grad(image, guide, weights if n == 1 else (weights / n).expand(n).contiguous()), None
+
+
+def _guide_pair(image, guide):
+    """Do ``image`` and ``guide`` take the device call?  A float32 GPU render [3,H,W] or [N,3,H,W] and uint8 guides [gh,gw,3] or [N,gh,gw,3] on
+    the same device, one guide per frame, not empty."""
+    if not (isinstance(image, torch.Tensor) and isinstance(guide, torch.Tensor) and image.is_cuda and guide.is_cuda and image.device == guide.device
+            and image.dtype == torch.float32 and guide.dtype == torch.uint8 and image.dim() in (3, 4) and guide.dim() in (3, 4)
+            and image.shape[-3] == 3 and guide.shape[-1] == 3 and image.numel() > 0 and guide.numel() > 0):
+        return False
+    return (image.shape[0] if image.dim() == 4 else 1) == (guide.shape[0] if guide.dim() == 4 else 1)
+
+
+def _guide_l1_torch(image, guide):
+    """train.py:214-220 after the file is open: ``to_tensor``, ``F.interpolate`` to the render's size, ``l1_loss``."""
+    frames = guide if guide.dim() == 4 else guide.unsqueeze(0)
+    image_guide_tensor = frames.permute(0, 3, 1, 2).contiguous().to(torch.float32).div(255).to(image.device)          # to_tensor
+    image_guide_resized = F.interpolate(image_guide_tensor, size=image.shape[-2:], mode="bilinear", align_corners=False)
+    if image.dim() == 3:
+        image_guide_resized = image_guide_resized.squeeze(0)
+    return torch.abs((image - image_guide_resized)).mean()
+
+
+def guide_l1_loss(image, guide):
+    """Style_3DGS/train.py's ``Ll1`` of its second phase, ``l1_loss(image, F.interpolate(to_tensor(guide)[None], size=image.shape[-2:],
+    mode="bilinear", align_corners=False))``, as a 0-d float32 tensor: ``image`` float32 [3,H,W] or [N,3,H,W], ``guide`` the picture as
+    uint8 [gh,gw,3] or [N,gh,gw,3] (what ``Image.convert("RGB")`` holds).  On GPU tensors one forward call (``runtime.guide_l1``) and, under
+    autograd, one backward call (``runtime.guide_l1_grad``) - no float guide is written; differentiable once, by ``image`` only.  Anything
+    else - CPU tensors, another channel count, another dtype - runs the reference's lines in torch."""
+    if _guide_pair(image, guide):
+        return _GuideL1.apply(image, guide)
+    return _guide_l1_torch(image, guide)
+
+
+class GuideBank:
+    """The stylised guide views of a scene by name, uint8 [gh,gw,3] each (sizes may differ), resident on one device: 0.75 MB for a 512 x 512
+    view against the 7.7 MB of an 800 x 800 float32 frame.  Without a GPU the tensors are on the CPU and ``loss`` takes the torch route."""
+
+    def __init__(self, frames):
+        self._frames = dict(frames)
+
+    @classmethod
+    def from_files(cls, paths, device=None, routes=None):
+        """``paths``: the {name: path} map ``precompute_guides_sharded`` returns.  Every file is read as train.py reads it back,
+        ``Image.open(path).convert("RGB")`` (the pixels after the JPEG) and uploaded once - or decoded on ``device`` where a decode route of
+        ``routes`` (an ``OutputRoutes``, or what its ``of`` takes) is switched on and takes the file: the same pixels."""
+        device = torch.device(device if device is not None else ("cuda:0" if torch.cuda.is_available() else "cpu"))
+        if routes is not None:
+            from . import runtime as rt
+
+            routes = rt.OutputRoutes.of(routes)
+        return cls((name, _read_rgb(str(path), device, routes).contiguous()) for name, path in paths.items())
+
+    @classmethod
+    def from_frames(cls, names, u8):
+        """Frames that are already there, one uint8 [gh,gw,3] per name (a tensor [N,gh,gw,3] or a sequence), used as given."""
+        names = list(names)
+        if len(names) != len(u8):
+            raise ValueError(f"GuideBank.from_frames: {len(names)} names for {len(u8)} frames")
+        for frame in u8:
+            if not (isinstance(frame, torch.Tensor) and frame.dtype == torch.uint8 and frame.dim() == 3):
+                raise ValueError("GuideBank.from_frames: every frame must be a uint8 tensor [gh,gw,3]")
+        return cls(zip(names, u8))
+
+    def __getitem__(self, name):
+        return self._frames[name]
+
+    def __contains__(self, name):
+        return name in self._frames
+
+    def __len__(self):
+        return len(self._frames)
+
+    def __iter__(self):
+        return iter(self._frames)
+
+    @property
+    def nbytes(self):
+        return sum(f.numel() * f.element_size() for f in self._frames.values())
+
+    def loss(self, image, name):
+        """``guide_l1_loss(image, bank[name])``: train.py:208-221 for the view ``name``."""
+        return guide_l1_loss(image, self._frames[name])
 
 
 # --- the evaluation of Style_3DGS/metrics.py -------------------------------------------------------------------------------------------------

@@ -126,6 +126,9 @@ SIGNATURES = {
     "adain_ssim_window": (_c_int, [ctypes.POINTER(_c_float)]),
     "adain_image_metrics_grad_f32_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t)]),
     "adain_image_metrics_grad_f32": (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 4 + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_guide_l1_f32_bytes": (_c_int, [_c_int] * 3 + [ctypes.POINTER(_c_size_t)]),
+    "adain_guide_l1_f32": (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "adain_guide_l1_grad_f32": (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 5 + [_c_void_p, _c_void_p, _c_void_p]),
     "adain_jpeg_encode_opt_u8_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
     "adain_jpeg_encode_opt_u8": (_c_int, [_c_void_p] + [_c_int] * 7 + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "adain_jpeg_encode_progressive_u8_bytes": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),
@@ -1487,6 +1490,67 @@ def ssim_window():
     if rc != 0:
         raise _failure("adain_ssim_window", rc)
     return list(out)
+
+
+# --- the guide-view loss (adain_guide_l1_f32 / adain_guide_l1_grad_f32) -----------------------------------------------------------------------
+class GuideL1:
+    """What ``guide_l1`` returns: ``l1``, float64 [n] on the device (train.py's ``Ll1`` per frame), and ``resampled``, the guide at the
+    render's size as float32 of the image's shape, or None when it was not asked for."""
+    __slots__ = ("l1", "resampled")
+
+    def __init__(self, l1, resampled=None):
+        self.l1, self.resampled = l1, resampled
+
+
+def guide_l1_sizes(n, h, w):
+    """workspace_bytes of adain_guide_l1_f32_bytes: a float64 per workgroup of the n frames.  Host only.  AdainHipError for a refused
+    shape."""
+    return _size_query("adain_guide_l1_f32_bytes", n, h, w)[0]
+
+
+def _guide_pair(image, guide, what):
+    """The input forms of the guide calls: ``image`` float32 [n,3,h,w] or [3,h,w], ``guide`` uint8 [n,gh,gw,3] or [gh,gw,3] on the same
+    device -> both contiguous with the batch dimension."""
+    x, g = device_tensor(image, what + ": image"), device_tensor(guide, what + ": guide", torch.uint8)
+    if x.dim() == 3:
+        x = x[None]
+    if g.dim() == 3:
+        g = g[None]
+    if x.dim() != 4 or g.dim() != 4 or x.shape[1] != 3 or g.shape[3] != 3 or x.numel() == 0 or g.numel() == 0 or x.shape[0] != g.shape[0] or x.device != g.device:
+        raise AdainHipError(f"{what}: expected float32 [n,3,h,w] / [3,h,w] and uint8 [n,gh,gw,3] / [gh,gw,3] on one device, got {tuple(image.shape)} "
+                            f"on {image.device} and {tuple(guide.shape)} on {guide.device}")
+    return x, g
+
+
+def guide_l1(image, guide, resampled=False):
+    """A render float32 [n,3,h,w] (or [3,h,w]) and its guide views uint8 [n,gh,gw,3] (or [gh,gw,3]) on the device -> a ``GuideL1``: per
+    frame ``l1_loss(image, F.interpolate(to_tensor(guide), size=(h, w), mode="bilinear", align_corners=False))`` of Style_3DGS/train.py as
+    float64 [n], and with ``resampled`` the interpolated guide (adain_guide_l1_f32).  No float guide is written otherwise.  Nothing is
+    copied to the host and nothing waits."""
+    x, g = _guide_pair(image, guide, "guide_l1")
+    n, _, h, w = x.shape
+    out = torch.empty((n,), dtype=torch.float64, device=x.device)
+    res = torch.empty(x.shape, dtype=torch.float32, device=x.device) if resampled else None
+    with scratch(x.device, "guide_l1", guide_l1_sizes, n, h, w) as ws:
+        _launch("adain_guide_l1_f32", x.data_ptr(), g.data_ptr(), n, h, w, g.shape[1], g.shape[2], out.data_ptr(), res.data_ptr() if resampled else None,
+                ws.data_ptr(), ws.numel())
+    return GuideL1(out, res.reshape(image.shape) if resampled else None)
+
+
+def guide_l1_grad(image, guide, weights):
+    """The gradient of ``guide_l1`` by the render: ``weights`` float64 [n] on the device, the upstream gradient of every frame's l1 ->
+    float32 of ``image``'s shape, weights[i] / (3 h w) * sign(image - guide at the render's size), sign(0) = 0
+    (adain_guide_l1_grad_f32).  The guide is resampled again; nothing of a forward call is taken.  Nothing is copied to the host and
+    nothing waits."""
+    what = "guide_l1_grad"
+    x, g = _guide_pair(image, guide, what)
+    n, _, h, w = x.shape
+    wts = device_tensor(weights, what + ": weights", torch.float64)
+    if wts.device != x.device or wts.numel() != n or wts.dim() > 1:
+        raise AdainHipError(f"{what}: weights must be float64 [{n}] on {x.device}, got {tuple(weights.shape)} on {weights.device}")
+    grad = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    call("adain_guide_l1_grad_f32", x.device, x.data_ptr(), g.data_ptr(), n, h, w, g.shape[1], g.shape[2], wts.data_ptr(), grad.data_ptr())
+    return grad.reshape(image.shape)
 
 
 class PngRoute(_Value):

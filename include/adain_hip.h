@@ -806,6 +806,46 @@ ADAIN_API int adain_image_metrics_grad_f32_bytes(int n, int c, int h, int w, int
 ADAIN_API int adain_image_metrics_grad_f32(const float* a, const float* b, int n, int c, int h, int w, const double* weights, float* grad_a,
                                            float* grad_b_or_null, void* workspace, size_t workspace_bytes, adain_stream_t stream);
 
+/* ---- the guide-view loss of Style_3DGS/train.py:208-221 and its gradient: l1_loss(image, F.interpolate(to_tensor(guide), size=image's,
+ * mode="bilinear", align_corners=False)) against uint8 guide views that stay on the device at their own size ------------------------------
+ * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
+ * image, grad, resampled: contiguous NCHW float32 [n][3][h][w], 4-byte aligned.  guide: contiguous HWC uint8 [n][gh][gw][3] at any byte
+ * address (what Image.convert("RGB") is).  Three channels only.
+ * The value of one sample; every line rounds once, in float32:
+ *   p = float(u8) / 255.0f, a true division (the rule of adain_u8_to_f32);
+ *   per axis ATen's rule: scale = f32(in) / f32(out); r = max(scale * (o + 0.5f) - 0.5f, 0); i0 = min(int(r), in - 1);
+ *     i1 = i0 + (i0 < in - 1); l1 = clamp(r - i0, 0, 1); l0 = 1 - l1;
+ *   top = lx0 * p[y0][x0] + lx1 * p[y0][x1], bot likewise on row y1, g = ly0 * top + ly1 * bot: the bits adain_u8_to_f32 followed by
+ *     adain_resize_bilinear produce; a tap of weight 0 still enters the sum;
+ *   d = x - g; term = |d|; sign = x > g ? 1 : x < g ? -1 : d (zero, or an input's NaN).
+ * adain_guide_l1_f32: out, device double [n], 8-byte aligned: out[i] = (the float64 sum of frame i's terms) / count, count = 3 h w, one
+ *   float64 division: train.py's Ll1 of the frame.  resampled: NULL, or receives g (for tests, and for a caller that wants the picture);
+ *   out is the same bits with it and without it.  Two launches whatever n: a tile pass in which a thread takes four outputs of a row in
+ *   all three planes and a workgroup of 256 threads leaves one float64 partial in the workspace, reduced in a fixed order (per thread,
+ *   across the wave by shuffles, across the waves through LDS), and a finish kernel that adds a frame's partials lane-parallel and then
+ *   in a fixed tree.
+ * adain_guide_l1_grad_f32: weights, device double [n], 8-byte aligned: the upstream gradient of out[i].  grad sample j of frame i
+ *   receives (float)(weights[i] / count) * sign_j, the scalar formed in float64 and rounded once.  One launch; g is recomputed and nothing
+ *   of a forward call is taken.  A frame whose weight is zero receives zeros and neither its image nor its guide is read.
+ * Both: the image is read (and the gradient written) 16 bytes at a time where w % 4 == 0 and the float buffers are 16-byte aligned, sample
+ * by sample otherwise; the guide is gathered from global memory.  No float atomics, spin-waits or flags: a frame's out and grad bits are a
+ * function of its image, its guide and its weight alone - not of n, the frame's index, the stream or what the workspace held.  The rules
+ * are listed at the top of csrc/guide_loss.hip and restated in tests/guide_loss_ref.py.
+ * adain_guide_l1_f32_bytes (host only): *workspace_bytes = 8 bytes per workgroup of the n frames (ceil(h ceil(w / 4) / 256) a frame),
+ * rounded up to a multiple of 256 bytes.  The output may be NULL.
+ * Refused with ADAIN_EINVAL before anything is launched, adain_last_error naming the argument: a null image, guide, out, weights, grad or
+ * workspace (a null resampled is legal), n outside 1..65535, h, w, gh or gw below 1, a frame or a guide beyond 2^31 - 1 samples,
+ * workspace_bytes below the query's, a workspace, out or weights that is not 8-byte aligned, image, resampled or grad that is not 4-byte
+ * aligned, out, resampled, grad or the workspace overlapping image, guide, weights or each other.  Nothing is copied to the host and
+ * nothing waits.
+ * Not built: a guide with alpha or one channel, antialias=True, align_corners=True, other interpolation modes, a mask, a gradient to the
+ * guide, a forward call that saves its signs for the backward, guides streamed from host memory for scenes that do not fit. */
+ADAIN_API int adain_guide_l1_f32_bytes(int n, int h, int w, size_t* workspace_bytes);
+ADAIN_API int adain_guide_l1_f32(const float* image, const uint8_t* guide_u8, int n, int h, int w, int gh, int gw, double* out,
+                                 float* resampled_or_null, void* workspace, size_t workspace_bytes, adain_stream_t stream);
+ADAIN_API int adain_guide_l1_grad_f32(const float* image, const uint8_t* guide_u8, int n, int h, int w, int gh, int gw, const double* weights,
+                                      float* grad, adain_stream_t stream);
+
 /* ---- the lossy JPEG round trip without the file: the reference's save and re-read of every stylised frame in front of the temporal
  * recurrence (video/utils.py:261-273) -------------------------------------------------------------------------------------------------
  * (Added without a version change: nothing existing moved, ADAIN_ABI_VERSION stays 4.)
