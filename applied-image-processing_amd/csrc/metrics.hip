@@ -150,10 +150,12 @@ __global__ __launch_bounds__(THREADS) void metrics_tile_kernel(TileArgs g) {
     // the tile and its halo, zeros outside the plane
     for (int i = t; i < STAGE_Y * stage_w; i += THREADS) {
         const int r = i / stage_w, c = i % stage_w;
-        const int y = y0 - HALO + r, x = x0 - halo_x + c;
+        // the staged sample lies dy rows and dx samples from the tile's corner.  y0 + dy and x0 + dx are formed for a sample of the plane
+        // only: at H or Wp = 2^31 - 1 the last tile's corner is within 64 of INT_MAX and its halo's own coordinates do not fit an int
+        const int dy = r - HALO, dx = c - halo_x;
         float va = 0.0f, vb = 0.0f;
-        if (y >= 0 && y < g.H && x >= 0 && x < g.Wp) {
-            const size_t at = (size_t)y * g.Wp + x;
+        if (dy >= -y0 && dy < g.H - y0 && dx >= -x0 && dx < g.Wp - x0) {
+            const size_t at = (size_t)(y0 + dy) * g.Wp + (x0 + dx);
             va = sample(a, at), vb = sample(b, at);
         }
         sh.in[0][r][c] = va, sh.in[1][r][c] = vb;
@@ -319,9 +321,9 @@ __global__ __launch_bounds__(THREADS) void metrics_combine_kernel(CombineArgs g)
         const float* src[3] = {g.d_mu + plane_at, g.d_exx + plane_at, g.d_exy + plane_at};
         for (int i = t; i < STAGE_Y * GRAD_STAGE_W; i += THREADS) {
             const int r = i / GRAD_STAGE_W, cc = i % GRAD_STAGE_W;
-            const int y = y0 - HALO + r, x = x0 - HALO + cc;
-            const bool inside = y >= 0 && y < g.H && x >= 0 && x < g.Wp;
-            const size_t at = (size_t)(inside ? y : 0) * g.Wp + (inside ? x : 0);
+            const int dy = r - HALO, dx = cc - HALO;          // from the tile's corner, as in the tile pass: no coordinate outside the plane is formed
+            const bool inside = dy >= -y0 && dy < g.H - y0 && dx >= -x0 && dx < g.Wp - x0;
+            const size_t at = inside ? (size_t)(y0 + dy) * g.Wp + (x0 + dx) : 0;
 #pragma unroll
             for (int j = 0; j < 3; ++j) sh.in[j][r][cc] = inside ? src[j][at] : 0.0f;
         }
@@ -378,7 +380,7 @@ const char* check_metrics_shape(bool u8, int n, int h, int w, int c) {
 MetricsPlan make_metrics_plan(bool u8, int n, int h, int w, int c) {
     MetricsPlan p{};
     p.planes = u8 ? 1 : c, p.H = h, p.Wp = u8 ? w * c : w, p.cs = u8 ? c : 1;
-    p.tiles_x = (p.Wp + TILE_X - 1) / TILE_X, p.tiles_y = (p.H + TILE_Y - 1) / TILE_Y;
+    p.tiles_x = (p.Wp - 1) / TILE_X + 1, p.tiles_y = (p.H - 1) / TILE_Y + 1;          // Wp + TILE_X - 1 does not fit an int at Wp = 2^31 - 1
     p.tiles = (size_t)p.planes * p.tiles_x * p.tiles_y;          // below 2^31: a tile holds a sample at least, 16 unless the plane is one tile high
     p.frame_samples = (size_t)h * w * c;
     Carve ws;

@@ -25,9 +25,13 @@ into one buffer of streams, from host tables.  Their rows put the P files' segme
 ``LEAD`` of more than 2^32 bytes, so that every offset lies past 2^32, and decode n = 65535 files, so that ``dst`` passes 2^32 in the
 same call; the offsets and lengths are computed arithmetically (``decode_tables``), no file is parsed more than once.
 
-Out of scope: the whole-network calls (adain_encode*, adain_decode, adain_stylize_u8*: workspaces of tens of GiB per case),
-adain_tvl1_flow and adain_farneback_* (a pair or a pyramid per call, no frame index), and the single-frame calls
-(adain_colour_transfer_u8, adain_strength_map, adain_localized_combine_u8, adain_warp_blend_u8)."""
+The gradient of the metrics (adain_image_metrics_grad_f32) runs without ``grad_b``: that form needs nine buffers of more than 2^32
+bytes each (a, b, two gradients, five derivative planes), 37 GiB at the smallest legal frame, which no case under the cap can hold.
+Its two extra planes lie 3 and 4 pitches behind the first and are reached by the ``size_t`` product ``j * dplane_pitch`` that plane 2
+uses, which the case here already puts past 8 GiB.
+
+Out of scope: the launches of include/adain_hip.h that are no ``call`` of a row are the keys of ``OUT_OF_SCOPE``, each with its
+reason; test_far_batch_host.py holds the two to the header, so that a new entry point has a row or a reason."""
 import functools
 import math
 
@@ -944,12 +948,133 @@ METRICS = [
     Case("conv3x3_up2x_poly", "metrics", "adain_conv3x3_up2x_poly", CONV_N, "float32 NHWC [27000,29,45,32] -> [27000,58,90,32], the polyphase up layer",
          _fixed(("x", "source", _CONV_F), ("out", "result", 4 * _CONV_F)), ("x", "out"), _conv("poly")),
 ]
+
+# ---- the 3DGS training loss: the metrics' gradient and the guide-view loss ----------------------------------------------------------------------------
+GRAD_C, GRAD_H, GRAD_W = 3, 43, 131          # three planes (the plane term of plane_at is live), 3 x 3 tiles, one-sample slivers each way
+# (how the pattern's gradient is held to the restatement, its upstream {ssim, mse, l1}): the first row of each of
+# metrics_grad_cases.WEIGHTS; a row of zeros, whose frames receive zeros though nothing of them is read; a zero ssim weight beside mse
+# and l1 weights of one sign (the planes pass returns early, the combine pass skips its staging); one more mixed row
+GRAD_ROWS = (("ssim", (1.0, 0.0, 0.0)), ("mse", (0.0, 1.0, 0.0)), ("l1", (0.0, 0.0, 1.0)), ("mixed", (-0.2, 0.7, 0.8)), ("zero", (0.0, 0.0, 0.0)),
+             ("no_ssim", (0.0, 0.7, 0.8)), ("mixed", (-1.5, -0.3, 0.4)))
+GUIDE_GH, GUIDE_GW = H, W                    # the guides are the table's default frame
+GUIDE_L1_HW = (73, 104)                      # w % 4 == 0: guide_l1_tile_kernel<true>
+GUIDE_GRAD_HW = (75, 101)                    # w % 4 != 0: guide_l1_grad_kernel<false>
+GUIDE_WEIGHTS = (1.0, -0.25, 0.75, 0.0, -2.0, 0.5, 3.0)          # pattern 3: +0 everywhere, neither its image nor its guide is read
+assert len(GRAD_ROWS) == P and len(GUIDE_WEIGHTS) == P
+
+
+def _metrics_grad(h, w, c):
+    def make():
+        """Expected: the float64 restatement's grad_a; the device test holds the P frames alone to it (bar_grad, or per element for
+        the rows without an ssim weight) and the batch to those P device results, bit for bit."""
+        import metrics_cases as C
+        import metrics_grad_ref as G
+
+        a, b = (C.to_nchw_f32(x) for x in C.pair("near", P, h, w, c, seed=8))
+        weights = np.array([row for _kind, row in GRAD_ROWS], dtype=np.float64)
+        return (a, b, weights), (G.grad(a, b, weights)[0],)
+    return make
+
+
+def guide_shape(hw):
+    """The guide_loss_cases shape of the P patterns of a guide case."""
+    return (P,) + tuple(hw) + (GUIDE_GH, GUIDE_GW)
+
+
+def _guide_l1(hw):
+    def make():
+        """guide_loss_cases' own guides and renders (g +- delta, no sample near a tie) -> the restatement's loss and resampled guide."""
+        import guide_loss_cases as K
+        import guide_loss_ref as R
+
+        shape = guide_shape(hw)
+        image, guide = K.image_delta(shape), K.guide(shape)
+        return (image, guide), (R.loss(image, guide), K.g_ref(shape))
+    return make
+
+
+def _guide_l1_grad(hw):
+    def make():
+        import guide_loss_cases as K
+        import guide_loss_ref as R
+
+        shape = guide_shape(hw)
+        image, guide, weights = K.image_delta(shape), K.guide(shape), np.array(GUIDE_WEIGHTS, dtype=np.float64)
+        return (image, guide, weights), (R.grad(image, guide, weights),)
+    return make
+
+
+_GRAD_F = GRAD_C * GRAD_H * GRAD_W * 4
+_GUIDE_F = 3 * GUIDE_GH * GUIDE_GW
+METRICS += [
+    Case("image_metrics_grad_f32", "metrics", "adain_image_metrics_grad_f32", N,
+         "float32 [n,3,43,131] pairs, weights float64 [n,3] of seven kinds, grad_a only (24.8 GiB; with grad_b: 37 GiB, past the cap)",
+         lambda n: [("a", "source", n * _GRAD_F), ("b", "source", n * _GRAD_F), ("weights", "source", n * 24), ("grad_a", "result", n * _GRAD_F),
+                    ("workspace", "workspace", _query("adain_image_metrics_grad_f32_bytes", n, GRAD_C, GRAD_H, GRAD_W, 0))],
+         ("a", "b", "grad_a", "workspace"), _metrics_grad(GRAD_H, GRAD_W, GRAD_C), below={"weights": "24 bytes per frame: 1.5 MB at n = 65535"}),
+    Case("guide_l1_f32", "metrics", "adain_guide_l1_f32", N, "float32 renders [n,3,73,104] (w % 4 == 0) against uint8 guides [n,128,176,3], with the resampled guide",
+         lambda n: [("image", "source", n * 12 * 73 * 104), ("guide", "source", n * _GUIDE_F), ("out", "result", n * 8), ("resampled", "result", n * 12 * 73 * 104),
+                    ("workspace", "workspace", _query("adain_guide_l1_f32_bytes", n, *GUIDE_L1_HW))],
+         ("image", "guide", "resampled"), _guide_l1(GUIDE_L1_HW),
+         below={"out": "8 bytes per frame", "workspace": "a float64 per 1024 pixels of a render, about 1/1500 of it: past 2^32 only with 6 TiB of renders"}),
+    Case("guide_l1_grad_f32", "metrics", "adain_guide_l1_grad_f32", N,
+         "float32 renders [n,3,75,101] (w % 4 != 0) against uint8 guides [n,128,176,3], weights float64 [n] of seven values, one of them 0",
+         lambda n: [("image", "source", n * 12 * 75 * 101), ("guide", "source", n * _GUIDE_F), ("weights", "source", n * 8), ("grad", "result", n * 12 * 75 * 101)],
+         ("image", "guide", "grad"), _guide_l1_grad(GUIDE_GRAD_HW), below={"weights": "8 bytes per frame"}),
+]
+
+# ---- the encoder's first layer alone ---------------------------------------------------------------------------------------------------------------------
+FIRST_H, FIRST_W = 9, 33          # tests/edge_exact.py's batch frame: 2 x 2 tiles of 8 x 32 with a seam, a partial row and a one-pixel column
+
+
+def first_layer_case():
+    """The far-batch first layer as a tests/edge_exact.py FirstCase of the P patterns (its head-room is checked on the host)."""
+    import edge_exact as E
+
+    return E.FirstCase("far-first", "batch", P, FIRST_H, FIRST_W, 4100)
+
+
+def _first_layer():
+    def make():
+        """Integer-valued images under edge_exact's integer weights: the float64 evaluation of the unfolded layer is what the kernel
+        gives, element for element."""
+        import edge_exact as E
+
+        x = E.first_image(first_layer_case())
+        return (x.numpy(),), (E.to_float32_exact(E.first_reference(x)).numpy(),)
+    return make
+
+
+METRICS += [
+    Case("encode_relu1_1", "metrics", "adain_encode_relu1_1", N, "float32 images [n,3,9,33] -> relu1_1 NHWC [n,9,33,64] (4.64 GiB), integer-exact operands",
+         _fixed(("image", "source", 12 * FIRST_H * FIRST_W), ("relu1_1", "result", 256 * FIRST_H * FIRST_W)), ("relu1_1",), _first_layer(),
+         below={"image": "12 bytes a pixel for 256 of relu1_1: images past 2^32 bytes need 91 GiB of output"}),
+]
 METRICS += [c for c in PIXEL if c.family == "metrics"]
 PIXEL = [c for c in PIXEL if c.family == "pixel"]
 
 CASES = PIXEL + RESIZE + ENCODE + DECODE + PALETTE + METRICS
 BY_ID = {c.id: c for c in CASES}
 assert len(BY_ID) == len(CASES)
+
+
+# ---- the launches without a row, and why ---------------------------------------------------------------------------------------------------------------
+_NETWORK = "a whole network per call: its ping-pong workspace is 28 x the float frames (335 MB per 1024 x 1024 image), more than 100 GiB before the frames pass 2^32"
+_NO_N = "one frame per call: no n, so no frame index"
+_PACK = "packs one set of weights: no n, no frame index"
+OUT_OF_SCOPE = {
+    "adain_encoder_pack": _PACK, "adain_decoder_pack": _PACK, "adain_conv3x3_wino4_pack": _PACK, "adain_conv3x3_up2x_poly_pack": _PACK,
+    "adain_encode": _NETWORK, "adain_encode_u8": _NETWORK, "adain_encode_multi": _NETWORK, "adain_decode": _NETWORK,
+    "adain_stylize_u8": _NETWORK, "adain_stylize_u8_ex": _NETWORK, "adain_stylize_u8_mix": _NETWORK,
+    "adain_tvl1_flow": "takes its frames by pointer, one pair at a time: no frame index into a caller's batch (its per-pair workspace slots are not "
+                       "taken past 2^32 here)",
+    "adain_farneback_expand": "one frame's pyramid per call: no n, so no frame index",
+    "adain_farneback_flow": "one pair of pyramids per call: no n, so no frame index",
+    "adain_colour_transfer_u8": _NO_N, "adain_strength_map": _NO_N, "adain_localized_combine_u8": _NO_N, "adain_warp_blend_u8": _NO_N,
+    "adain_conv3x3_wino4_split": "splits along cin only while tiles x channel tiles x 2 <= the device's compute units (wino4_ksplit): at most 128 tiles of "
+                                 "256 pixels on 256 units, an output of 4 MiB, and a source past 2^32 bytes only from 32768 input channels on; a larger "
+                                 "launch leaves no unit idle, is not split and is adain_conv3x3_wino's launch, which has a row",
+}
 
 
 def cases_of(family):

@@ -1,6 +1,7 @@
 """The arithmetic of every row of tests/far_batch.py, without a device: the buffers a row names pass 2^32 bytes (sized by the
 library's host-only ``*_bytes`` queries where the library sizes them), the frame size does not divide 2^32, P is coprime to
-floor(2^32 / F), the row fits the memory cap, and its P expected values exist and differ pairwise."""
+floor(2^32 / F), the row fits the memory cap, and its P expected values exist and differ pairwise.  And the table's completeness: every
+launch of include/adain_hip.h (tests/abi_launches.py) is the call of a row or a key of far_batch.OUT_OF_SCOPE."""
 import math
 
 import numpy as np
@@ -51,6 +52,41 @@ def test_every_buffer_of_every_call_passes_2_32_in_some_case():
             assert e["below"].get(name), f"{call}: no case takes {name} past 2^32 and none says why"
 
 
+def test_every_launch_of_the_header_has_a_row_or_a_reason():
+    """The table cannot fall behind the header: a declaration of include/adain_hip.h that ends in ``adain_stream_t stream`` is the
+    ``call`` of a row or a key of OUT_OF_SCOPE, never both, and OUT_OF_SCOPE names nothing the header does not declare."""
+    import abi_launches
+
+    assert len(abi_launches.launches()) >= 58
+    abi_launches.audit({c.call for c in B.CASES}, B.OUT_OF_SCOPE, "tests/far_batch.py")
+
+
+def test_the_header_parse_sees_a_new_launch_and_nothing_else():
+    """What the check above rests on: a launch added to the header's text is found, whatever its line breaks and comments; a host-only
+    query and a declaration that only mentions a stream in a comment are not."""
+    import abi_launches
+
+    with open(abi_launches.HEADER) as f:
+        text = f.read()
+    more = text + ("\nADAIN_API int adain_new_thing_u8(const uint8_t* src, int n, /* frames */ int h,\n        int w,   // width\n"
+                   "        adain_stream_t\n        stream);\n"
+                   "ADAIN_API int adain_new_thing_u8_bytes(int n, int h, int w, size_t* workspace_bytes);   /* adain_stream_t stream */\n")
+    assert abi_launches.launches(more) == abi_launches.launches(text) + ["adain_new_thing_u8"]
+    assert "adain_image_metrics_grad_f32" in abi_launches.launches() and "adain_image_metrics_grad_f32_bytes" not in abi_launches.launches()
+
+
+def test_the_gradient_rows_are_the_ones_the_gradients_own_tests_use():
+    import metrics_grad_cases as K
+
+    rows = [list(row) for _kind, row in B.GRAD_ROWS]
+    assert rows[:4] == [K.WEIGHTS[k][0] for k in ("ssim", "mse", "l1", "mixed")] and rows[6] == K.WEIGHTS["mixed"][1]
+    assert len({tuple(r) for r in rows}) == B.P and rows[4] == [0.0, 0.0, 0.0]
+    kind, (ssim, mse, l1) = B.GRAD_ROWS[5]
+    assert kind == "no_ssim" and ssim == 0.0 and mse > 0.0 and l1 > 0.0, "one sign: the two terms of a sample cannot cancel"
+    assert len(set(B.GUIDE_WEIGHTS)) == B.P and B.GUIDE_WEIGHTS.count(0.0) == 1
+    assert B.GUIDE_L1_HW[1] % 4 == 0 and B.GUIDE_GRAD_HW[1] % 4 != 0, "one case per kernel form"
+
+
 def test_ids_are_unique_and_families_known():
     assert len({c.id for c in B.CASES}) == len(B.CASES)
     assert {c.family for c in B.CASES} <= {"pixel", "resize", "encode", "decode", "palette", "metrics"}
@@ -65,6 +101,16 @@ def test_the_conv_layers_operands_are_integer_exact(entry):
     assert (c.cin, c.cout, c.hs, c.ws) == (B.CONV_C, B.CONV_C, B.CONV_H, B.CONV_W) and c.n == B.P
     for form, (a, b) in X.headroom(c).items():
         assert a < X.CAP and b < X.CAP, (entry, form, a, b)
+
+
+def test_the_first_layers_operands_are_integer_exact():
+    """The far-batch first layer is a tests/edge_exact.py case: the fold's and the layer's partial sums stay below 2^24."""
+    import edge_exact as E
+
+    c = B.first_layer_case()
+    assert (c.n, c.H, c.W) == (B.P, B.FIRST_H, B.FIRST_W) and len(E.first_tiles(c.H, c.W)) == 4
+    a, b = E.first_headroom(E.first_image(c))
+    assert a < E.CAP and b < E.CAP, (a, b)
 
 
 @pytest.mark.parametrize("kind", sorted(B.DECODERS))

@@ -7,7 +7,10 @@ refused values only, why every row was first run without a device, and why a new
 
 The largest admitted values themselves are launched nowhere: those frames are 2 GiB each and a wrong index there is out of
 bounds.  What stands for them is the audit behind the table (every index a live or an idle lane forms, every grid size and every
-grid-stride sum fits its type at the largest admitted value) and these refusals one step further."""
+grid-stride sum fits its type at the largest admitted value) and these refusals one step further.
+
+The table is held to the header: every launch of include/adain_hip.h (tests/abi_launches.py) is the call of a row here, or a key of
+``NO_ROW`` with the reason it has none."""
 import ctypes
 
 import pytest
@@ -31,6 +34,11 @@ PNG_OFF = ctypes.cast((ctypes.c_uint64 * 2)(0, 1 << 31), OFF64)
 SCANS = ctypes.cast((ctypes.c_int32 * 8)(3, 0, 1, 2, 0, 0, 0, 0), ctypes.POINTER(ctypes.c_int32))          # one scan: the DC terms of all three components
 TABLES = (C, D, 5, E, E + (1 << 30), 5)                 # resize_pil_u8's tap tables: x bounds, x taps, ksize, y bounds, y taps, ksize (BICUBIC at scale 1: 5 taps)
 WS = A + (1 << 39)
+# host tables of adain_encode_multi: one batch of one image of 9 x 2^20 pixels, its image and feature pointers made up like the rest
+PTRS = ctypes.POINTER(ctypes.c_void_p)
+INTS = ctypes.POINTER(ctypes.c_int)
+ONE_IMAGE, ONE_FEAT = ctypes.cast((ctypes.c_void_p * 1)(A), PTRS), ctypes.cast((ctypes.c_void_p * 1)(B), PTRS)
+ONE_N, NINE_ROWS, WIDE = (ctypes.cast((ctypes.c_int * 1)(v), INTS) for v in (1, 9, 1 << 20))
 
 
 def tv_params():
@@ -135,7 +143,53 @@ ROWS = [
     ("jpeg_encode_opt_u8: n", "adain_jpeg_encode_opt_u8", (A, 65536, 8, 8, 3, 75, 0, 1, B, BIG, C, D, BIG), "batch of 65536 frames too large"),
     ("jpeg_encode_progressive_u8: side", "adain_jpeg_encode_progressive_u8", (A, 1, 8, 65536, 3, 75, 2, B, BIG, C, D, BIG), "height or width outside 1..65535"),
     ("jpeg_encode_progressive_u8: n", "adain_jpeg_encode_progressive_u8", (A, 65536, 8, 8, 3, 75, 2, B, BIG, C, D, BIG), "batch of 65536 frames too large"),
+    # the 3DGS loss calls: a, b, n, c, h, w, weights, grad_a, grad_b, workspace / image, guide, n, h, w, gh, gw, ...
+    ("image_metrics_grad_f32: n", "adain_image_metrics_grad_f32", (A, B, 65536, 3, 4, 4, C, D, None, WS, BIG), "image_metrics_grad_f32: n outside 1..65535"),
+    ("image_metrics_grad_f32: frame", "adain_image_metrics_grad_f32", (A, B, 1, 1, 32768, 65536, C, D, None, WS, BIG), "a frame beyond 2^31 - 1 samples"),
+    ("image_metrics_grad_f32: frame, three planes", "adain_image_metrics_grad_f32", (A, B, 1, 3, 1, THIRD, C, D, None, WS, BIG), "a frame beyond 2^31 - 1 samples"),
+    ("image_metrics_grad_f32: frame, with grad_b", "adain_image_metrics_grad_f32", (A, B, 1, 3, THIRD, 1, C, D, E, WS, BIG), "a frame beyond 2^31 - 1 samples"),
+    ("guide_l1_f32: n", "adain_guide_l1_f32", (A, B, 65536, 4, 4, 4, 4, C, D, WS, BIG), "guide_l1_f32: n outside 1..65535"),
+    ("guide_l1_f32: render", "adain_guide_l1_f32", (A, B, 1, 1, THIRD, 4, 4, C, D, WS, BIG), "guide_l1_f32: a frame beyond 2^31 - 1 samples"),
+    ("guide_l1_f32: guide", "adain_guide_l1_f32", (A, B, 1, 4, 4, THIRD, 1, C, D, WS, BIG), "guide_l1_f32: a guide beyond 2^31 - 1 samples"),
+    ("guide_l1_grad_f32: n", "adain_guide_l1_grad_f32", (A, B, 65536, 4, 4, 4, 4, C, D), "guide_l1_grad_f32: n outside 1..65535"),
+    ("guide_l1_grad_f32: render", "adain_guide_l1_grad_f32", (A, B, 1, THIRD, 1, 4, 4, C, D), "guide_l1_grad_f32: a frame beyond 2^31 - 1 samples"),
+    ("guide_l1_grad_f32: guide", "adain_guide_l1_grad_f32", (A, B, 1, 4, 4, 1, THIRD, C, D), "guide_l1_grad_f32: a guide beyond 2^31 - 1 samples"),
+    # stylize_u8_ex's uint8-mask row for its two siblings (one launcher, stylize_impl)
+    ("stylize_u8: uint8 mask elements, one style", "adain_stylize_u8", (A, 1, 16, 16, B, C, D, E, 0.5, 0.5, None, None, None, 0.0, 0.0, A + (1 << 37), 0, 1, 1, 401, 10710641,
+                                                                         A + (1 << 38), WS, BIG), "stylize_u8: a uint8 mask of more than 2^32 - 256 elements"),
+    ("stylize_u8_mix: uint8 mask elements", "adain_stylize_u8_mix", (A, 1, 16, 16, B, C, D, E, 2, A + (1 << 36), 1, 1, 0.5, 0.5, None, None, None, 0.0, 0.0, A + (1 << 37), 0,
+                                                                     1, 1, 401, 10710641, A + (1 << 38), WS, BIG), "stylize_u8: a uint8 mask of more than 2^32 - 256 elements"),
+    # the networks' frame limits (Data layout in HBM): eight 64-channel rows and three float planes of an image below 2 GiB in the
+    # first layer, a band of eighteen source or sixteen output rows below 2 GiB in a 3 x 3 layer (32 output rows in the polyphase up layer)
+    ("encode_relu1_1: eight rows of relu1_1", "adain_encode_relu1_1", (A, 0, B, C, 1, 2, 1 << 20), "conv_first: eight 64-channel rows of width 1048576 reach 2 GiB"),
+    # 215 x 832 358 = 178 956 970 pixels, the first count with 12 h w >= 2^31 - 16
+    ("encode_relu1_1: three float planes", "adain_encode_relu1_1", (A, 0, B, C, 1, 215, 832358), "reaches 2 GiB as three float planes"),
+    ("encode: eight rows of relu1_1", "adain_encode", (A, B, C, WS, BIG, 1, 9, 1 << 20, None), "conv_first: eight 64-channel rows of width 1048576 reach 2 GiB"),
+    ("encode_u8: eight rows of relu1_1", "adain_encode_u8", (A, B, C, WS, BIG, 1, 9, 1 << 20, None), "conv_first: eight 64-channel rows of width 1048576 reach 2 GiB"),
+    ("encode_multi: eight rows of relu1_1", "adain_encode_multi", (1, ONE_IMAGE, ONE_FEAT, ONE_N, NINE_ROWS, WIDE, C, WS, BIG, None),
+     "conv_first: eight 64-channel rows of width 1048576 reach 2 GiB"),
+    # the decoder's first layer has 512 input channels: 18 x 2048 x 58 255 bytes is the first band of 2^31 - 16 bytes or more
+    ("decode: a band of source rows", "adain_decode", (A, B, C, WS, BIG, 1, 2, 58255, None), "conv3x3_wino4: a band of eighteen 512-channel source rows"),
+    ("conv3x3_wino: a band of output rows", "adain_conv3x3_wino", (A, B, C, D, 1, 2, 1 << 20, 2, 1 << 20, 16, 32, 0, 1, 0, 5), "of width 1048576 reaches 2 GiB"),
+    ("conv3x3_wino4_split: a band of output rows", "adain_conv3x3_wino4_split", (A, B, C, D, 1, 2, 1 << 20, 2, 1 << 20, 16, 32, 0, 1, 0, None, 0),
+     "of width 1048576 reaches 2 GiB"),
+    ("conv3x3_up2x_poly: a band of output rows", "adain_conv3x3_up2x_poly", (A, B, C, D, 1, 1, 1 << 18, 16, 32, 1), "a band of 19 source or 32 output rows reaches 2 GiB"),
+    # the flow estimators: h; 5 h w (Farneback); pairs, h, w and 4 h w (TV-L1, the limits of tvl1_prepare)
+    ("farneback_expand: rows", "adain_farneback_expand", (A, 65536, 1, 0.5, 3, 5, 1.1, B, WS, BIG), "farneback_expand: bad frame size 1 x 65536"),
+    ("farneback_expand: frame", "adain_farneback_expand", (A, 1, 429496730, 0.5, 3, 5, 1.1, B, WS, BIG), "farneback_expand: bad frame size 429496730 x 1"),
+    ("farneback_flow: rows", "adain_farneback_flow", (A, B, 65536, 1, 0.5, 3, 15, 3, 0, C, WS, BIG), "farneback_flow: bad frame size 1 x 65536"),
+    ("farneback_flow: frame", "adain_farneback_flow", (A, B, 1, 429496730, 0.5, 3, 15, 3, 0, C, WS, BIG), "farneback_flow: bad frame size 429496730 x 1"),
 ]
+
+# A launch of include/adain_hip.h without a row, a test of FILES or test_tvl1_prepare_caps_n_and_the_frame / test_tvl1_flow_caps_the_pairs_and_the_frame:
+# where its limit is enforced, or why it has none.  test_every_launch_of_the_header_has_a_row_or_a_reason holds this to the header.
+NO_ROW = {
+    "adain_encoder_pack": "no size argument: the ten layers of the one encoder, sizes fixed at compile time",
+    "adain_decoder_pack": "no size argument: the nine layers of the one decoder, sizes fixed at compile time",
+    "adain_conv3x3_wino4_pack": "refuses no size: a grid-stride walk of at most 4096 workgroups over cin cout 24 floats, counted in size_t; the layer that "
+                                "reads the weights refuses cin cout 96 >= 2^32 - 1 (adain_conv3x3_wino's launcher)",
+    "adain_conv3x3_up2x_poly_pack": "refuses no size: the same walk over cin cout 96 floats; adain_conv3x3_up2x_poly refuses cin cout 384 >= 2^32 - 1",
+}
 
 
 @pytest.fixture(scope="module")
@@ -160,6 +214,27 @@ def test_tvl1_prepare_caps_n_and_the_frame(lib):
                        ((A, 1, 23171, 23171, ctypes.addressof(P), B), "bad frame size 23171 x 23171")):
         assert lib.adain_tvl1_prepare(*args, None) == EINVAL
         assert text in lib.adain_last_error().decode()
+
+
+def test_tvl1_flow_caps_the_pairs_and_the_frame(lib):
+    """The frame limits are tvl1_prepare's (tv_check, in front of everything else); the pairs are capped like its n."""
+    P = tv_params()
+    for args, text in (((A, B, 65536, 36, 64, ctypes.addressof(P), C, None, WS, BIG), "tvl1_flow: bad pair count 65536"),
+                       ((A, B, 1, 65536, 64, ctypes.addressof(P), C, None, WS, BIG), "tvl1_flow: bad frame size"),
+                       ((A, B, 1, 64, 65536, ctypes.addressof(P), C, None, WS, BIG), "tvl1_flow: bad frame size"),
+                       ((A, B, 1, 23171, 23171, ctypes.addressof(P), C, None, WS, BIG), "tvl1_flow: bad frame size 23171 x 23171")):
+        assert lib.adain_tvl1_flow(*args, None) == EINVAL
+        assert text in lib.adain_last_error().decode()
+
+
+def test_every_launch_of_the_header_has_a_row_or_a_reason():
+    """The tables cannot fall behind the header: a declaration of include/adain_hip.h that ends in ``adain_stream_t stream`` is the call
+    of a row of ROWS or FILES or of one of the two TV-L1 tests, or a key of NO_ROW with its reason - never both."""
+    import abi_launches
+
+    tested = {r[1] for r in ROWS} | {f[0] for f in FILES} | {"adain_tvl1_prepare", "adain_tvl1_flow"}
+    abi_launches.audit(tested, NO_ROW, "tests/test_limits_host.py")
+    assert len({r[0] for r in ROWS}) == len(ROWS), "two rows have one id"
 
 
 # (call, its size query, arguments of the query after n, h, w; arguments of the call after src, n, h, w)
@@ -202,7 +277,12 @@ def test_the_size_queries_refuse_what_the_calls_refuse(lib):
                        ("adain_jpeg_decode_progressive_u8_bytes", (1, 8, 8, 3, 2, 1, 1 << 28, 0, ctypes.byref(size))),
                        ("adain_png_decode_u8_bytes", (1, 8, 8, 3, 1 << 31, ctypes.byref(size))), ("adain_png_decode_u8_bytes", (65536, 8, 8, 3, 64, ctypes.byref(size))),
                        ("adain_resize_pil_u8_bytes", (1, 257, 8, 1, 8, 3, 3, 0, 0, 1, 8, ctypes.byref(size))),
-                       ("adain_resize_pil_u8_bytes", (1, 8, S24, 8, S24, 3, 3, 0, 0, 8, 8, ctypes.byref(size)))):
+                       ("adain_resize_pil_u8_bytes", (1, 8, S24, 8, S24, 3, 3, 0, 0, 8, 8, ctypes.byref(size))),
+                       ("adain_image_metrics_f32_bytes", (65536, 3, 4, 4, ctypes.byref(size))), ("adain_image_metrics_f32_bytes", (1, 1, 32768, 65536, ctypes.byref(size))),
+                       ("adain_image_metrics_grad_f32_bytes", (65536, 3, 4, 4, 0, ctypes.byref(size))),
+                       ("adain_image_metrics_grad_f32_bytes", (1, 1, 32768, 65536, 0, ctypes.byref(size))),
+                       ("adain_image_metrics_grad_f32_bytes", (1, 3, 1, THIRD, 1, ctypes.byref(size))),
+                       ("adain_guide_l1_f32_bytes", (65536, 4, 4, ctypes.byref(size))), ("adain_guide_l1_f32_bytes", (1, 1, THIRD, ctypes.byref(size)))):
         assert getattr(lib, call)(*args) == EINVAL, (call, args)
         assert lib.adain_last_error()
     assert lib.adain_coral_workspace_bytes(65536, 1, 4, 4, 4, 4) == 0 and lib.adain_coral_workspace_bytes(1, 1, 1, M30, 4, 4) == 0
@@ -218,3 +298,16 @@ def test_the_largest_admitted_values_pass_the_size_queries(lib):
                        ("adain_png_decode_u8_bytes", (65535, 8, 8, 3, (1 << 31) - 1)), ("adain_resize_pil_u8_bytes", (65535, 256, 8, 1, 8, 3, 3, 0, 0, 1, 8))):
         assert getattr(lib, call)(*args, ctypes.byref(size)) == 0, (call, args, lib.adain_last_error())
     assert lib.adain_coral_workspace_bytes(65535, 1, 1, M30 - 1, 32767, 32768) > 0
+    # the 3DGS loss calls, and here the answer too: the tile counts of a plane of 2^31 - 1 samples are formed from sizes within 64 of
+    # INT_MAX (ceil(Wp / 64), ceil(H / 16)), the planes and partials of 65535 such frames in size_t
+    up256 = lambda v: -(-v // 256) * 256
+    for call, args, want in (("adain_image_metrics_f32_bytes", (1, 1, 1, M31), up256(24 << 25)), ("adain_image_metrics_f32_bytes", (1, 1, M31, 1), up256(24 << 27)),
+                             ("adain_image_metrics_u8_bytes", (1, 1, THIRD - 1, 3), up256(24 * -(-3 * (THIRD - 1) // 64))),
+                             ("adain_image_metrics_grad_f32_bytes", (1, 1, 1, M31, 0), 3 * up256(4 * M31)),
+                             ("adain_image_metrics_grad_f32_bytes", (1, 1, 1, M31, 1), 5 * up256(4 * M31)),
+                             ("adain_image_metrics_grad_f32_bytes", (1, 1, M31, 1, 1), 5 * up256(4 * M31)),
+                             ("adain_image_metrics_grad_f32_bytes", (65535, 3, 1, THIRD - 1, 0), 3 * up256(65535 * 3 * (THIRD - 1) * 4)),
+                             ("adain_guide_l1_f32_bytes", (65535, 1, THIRD - 1), up256(65535 * 8 * -(-(-(-(THIRD - 1) // 4)) // 256))),
+                             ("adain_guide_l1_f32_bytes", (1, THIRD - 1, 1), up256(8 * -(-(THIRD - 1) // 256)))):
+        assert getattr(lib, call)(*args, ctypes.byref(size)) == 0, (call, args, lib.adain_last_error())
+        assert size.value == want, (call, args, size.value, want)
