@@ -14,7 +14,8 @@
  *   - `stream` is a hipStream_t (NULL = the default stream); every call only enqueues work;
  *   - return value 0 = ok, negative = error (ADAIN_E*); adain_last_error() gives the text of the
  *     calling thread's last error.  No exceptions cross the ABI.  No call allocates, frees or
- *     synchronises, so every call may be captured into a hipGraph.
+ *     synchronises, so every call may be captured into a hipGraph.  (Tested launch by launch: tests/capture_cases.py holds a row
+ *     per launch declared here, tests/test_gpu_graph_capture.py captures and replays each; the one exception is adain_tvl1_flow.)
  */
 #ifndef ADAIN_HIP_H
 #define ADAIN_HIP_H

@@ -10,6 +10,10 @@ every byte that is not a declared output or workspace is compared with what was 
 ``run_case`` drives one case: fresh arenas with fills A and B, outputs bitwise equal between them, and (``history``) the same call
 again in arena B after another call has used the same workspace.  Works on a host arena with a Python stand-in for the call
 (tests/test_abi_arena_host.py) exactly as on the GPU (tests/test_gpu_abi_memory.py).
+
+``run_captured`` drives one row of tests/capture_cases.py: the call captured alone into a graph (``hip_graph``; a Python recorder on a
+host arena) and replayed on the captured data, on a second data set put into the same regions, and on the workspace that replay left,
+each time to the eager call's outputs bit for bit (tests/test_gpu_graph_capture.py).
 """
 import torch
 
@@ -216,3 +220,139 @@ def run_case(specs, call, device, sync, history=None, setup=None, extra=None):
         arena_b.check()
         compare_outputs(outputs(arena_b), outs["B"], "the rerun after a call of another shape", "fill B")
     return outs["A"]
+
+
+# ---- the same call captured into a graph and replayed ----------------------------------------------------------------------------------
+class CaptureFailed(AssertionError):
+    """The call returned an error while it was being captured, or the capture did not end clean.  Nothing was replayed."""
+
+
+def hip_graph(last_error=lambda: ""):
+    """``capture`` of ``run_captured`` on the GPU: ``capture(do)`` opens a side stream, captures the single call ``do()`` (which returns
+    the call's return value) into a ``torch.cuda.graph`` on that one stream - no second stream, no fork, no event: the graph is a chain
+    - and returns ``replay()``.  A non-zero return value or a capture that ends in an error raises CaptureFailed with
+    ``last_error()``, after making sure that no stream is left capturing; a graph whose capture did not end clean is never replayed."""
+    def capture(do):
+        torch.cuda.synchronize()
+        before = torch.cuda.current_stream()
+        side = torch.cuda.Stream()
+        graph = torch.cuda.CUDAGraph()
+        rc, err = None, None
+        try:
+            with torch.cuda.graph(graph, stream=side):
+                rc = do()                      # (no raise inside: the capture is ended first, whatever the call answered)
+        except Exception as e:                 # the runtime refused the capture: an error code, read below
+            err = e
+        text = last_error()
+        with torch.cuda.stream(side):
+            still = torch.cuda.is_current_stream_capturing()
+        still = still or torch.cuda.is_current_stream_capturing()
+        if still:                              # end it, so that the next test starts from a stream that is not capturing
+            try:
+                graph.capture_end()
+            except Exception:
+                pass
+            with torch.cuda.stream(side):
+                assert not torch.cuda.is_current_stream_capturing(), "the capture could not be ended"
+        # where the capture's end raised, torch did not leave its stream context: the side stream must not stay the current one
+        torch.cuda.set_stream(before)
+        if err is not None or still or (rc is not None and rc != 0):
+            del graph
+            raise CaptureFailed(f"the call could not be captured: rc {rc}, {text!r}" + (f", capture error: {err}" if err is not None else "")
+                                + (", the stream was still capturing" if still else ""))
+        torch.cuda.synchronize()
+
+        def replay():
+            graph.replay()
+        return replay
+    return capture
+
+
+def _overwrite(arena, how):
+    """Every byte of every output and workspace that the call may write (an output's declared padding stays, it is guarded) gets 0xFF
+    (``how`` "ff") or the arena's position-dependent pattern (``how`` "pattern")."""
+    for r in arena.regions:
+        if r.role == "in":
+            continue
+        at = 0
+        for a, b in list(r.holes) + [(r.nbytes, r.nbytes)]:
+            for c in range(at, a, _CHUNK):
+                d = min(a, c + _CHUNK)
+                arena.buf[r.offset + c:r.offset + d] = 0xFF if how == "ff" else pattern(r.offset + c, r.offset + d, arena.device)
+            at = b
+
+
+def _still_ff(arena):
+    """The name of the first output or workspace with a byte that is no longer the 0xFF of ``_overwrite``; None when all are."""
+    for r in arena.regions:
+        if r.role == "in":
+            continue
+        at = 0
+        for a, b in list(r.holes) + [(r.nbytes, r.nbytes)]:
+            if a > at and bool((arena.buf[r.offset + at:r.offset + a] != 0xFF).any()):
+                return r.name
+            at = b
+    return None
+
+
+def run_captured(specs, call, device, sync, sets, capture, differs=(), extra=None, last_error=lambda: ""):
+    """One call held to the promise that it may be captured into a graph.  ``sets``: {"A": setup_a, "B": setup_b}, each ``setup(arena)``
+    puts one data set of the same shapes; ``call(arena)`` makes the call with pointers into the arena and returns its return value (None
+    counts as 0); ``capture(do)`` records the single call ``do()`` without running it and returns ``replay()`` (``hip_graph`` on the GPU,
+    a Python stand-in on a host arena).  ``differs``: the outputs (names of ``arena.outputs()`` and of ``extra``) that must differ
+    between the eager results of the two sets, so that the replay on set B has something to show.  The steps:
+
+    1. eager: set A in a fresh arena (fill B), the call, ``arena.check()`` -> E_A; set B in another -> E_B (these are the warm-up too);
+    2. a fresh arena with set A, every output and workspace overwritten with 0xFF, the capture of the single call; afterwards they
+       still hold 0xFF and the arena checks: capturing wrote nothing.  A call or a capture that fails raises CaptureFailed, no replay;
+    3. first replay: the outputs are E_A bit for bit;
+    4. set B put into the same input regions, outputs and workspaces overwritten with the position-dependent pattern, second replay:
+       the outputs are E_B bit for bit;
+    5. third replay with nothing refilled - the workspace holds what the second left: E_B again.
+
+    Every comparison is an equality.  Returns (E_A, E_B)."""
+    def outputs(arena):
+        return dict(arena.outputs(), **(extra(arena) if extra is not None else {}))
+
+    def checked(arena, what):
+        rc = call(arena)
+        assert rc is None or rc == 0, f"{what}: rc {rc}: {last_error()}"
+
+    eager = {}
+    for name in ("A", "B"):
+        arena = Arena(specs, "B", device)
+        sets[name](arena)
+        checked(arena, f"the eager call on set {name}")
+        sync()
+        arena.check()
+        eager[name] = outputs(arena)
+    assert differs, "a row names what differs between its data sets"
+    for name in differs:
+        a, b = eager["A"][name], eager["B"][name]
+        assert a.numel() != b.numel() or not torch.equal(a, b), f"output {name} is the same for both data sets: the replay on set B could show nothing"
+    arena = Arena(specs, "B", device)
+    sets["A"](arena)
+    _overwrite(arena, "ff")
+    sync()
+    replay = capture(lambda: call(arena))
+    sync()
+    touched = _still_ff(arena)
+    if touched is not None:
+        raise ArenaViolation(f"{touched} was written while the call was captured, before any replay", touched)
+    arena.check()
+    replay()
+    sync()
+    arena.check()
+    compare_outputs(outputs(arena), eager["A"], "the first replay", "the eager call on set A")
+    sets["B"](arena)                                   # in place: the graph holds the addresses
+    _overwrite(arena, "pattern")
+    sync()
+    replay()
+    sync()
+    arena.check()
+    compare_outputs(outputs(arena), eager["B"], "the second replay (set B in place)", "the eager call on set B")
+    replay()
+    sync()
+    arena.check()
+    compare_outputs(outputs(arena), eager["B"], "the third replay (the workspace as the second left it)", "the eager call on set B")
+    return eager["A"], eager["B"]

@@ -140,3 +140,117 @@ def test_declared_padding_of_an_output_is_guarded_and_of_an_input_is_poisoned():
     with pytest.raises(A.ArenaViolation) as e:          # a read of the input's padding that reaches the output
         A.run_case(specs, lambda a: call(a, peek=True), "cpu", lambda: None, setup=setup)
     assert e.value.region == "out" and "fill A and fill B" in str(e.value)
+
+
+# ---- run_captured: the same harness around a call that is recorded once and replayed ---------------------------------------------------
+class Recorder:
+    """The stand-in for a graph capture: while ``capture`` runs, a stand-in call appends what it would enqueue to ``ops`` and runs
+    nothing; ``replay`` runs the recorded ops."""
+
+    def __init__(self):
+        self.ops, self.replays = None, 0
+
+    def enqueue(self, op):
+        if self.ops is None:
+            op()
+        else:
+            self.ops.append(op)
+
+    def capture(self, do):
+        self.ops = ops = []
+        try:
+            rc = do()
+        finally:
+            self.ops = None
+        if rc not in (None, 0):
+            raise A.CaptureFailed(f"rc {rc}")
+
+        def replay():
+            self.replays += 1
+            for op in ops:
+                op()
+        return replay
+
+
+def _sets():
+    def put(scale):
+        def setup(arena):
+            arena.put("x", scale * torch.arange(N, dtype=torch.float32))
+            arena.put("bias", torch.tensor([1.0, 2.0, 3.0]))
+        return setup
+    return {"A": put(1.0), "B": put(3.0)}
+
+
+def _captured(call, rec, **kw):
+    return A.run_captured(_specs(), call, "cpu", lambda: None, _sets(), rec.capture, differs=("out",), **kw)
+
+
+def test_a_well_behaved_call_is_captured_and_replayed_three_times():
+    rec = Recorder()
+    ea, eb = _captured(lambda arena: rec.enqueue(lambda: _good(arena)), rec)
+    assert rec.replays == 3
+    assert torch.equal(ea["out"].view(torch.float32), 2 * torch.arange(N, dtype=torch.float32) + 1)
+    assert torch.equal(eb["out"].view(torch.float32), 6 * torch.arange(N, dtype=torch.float32) + 1)
+
+
+def test_a_host_side_copy_of_the_input_taken_at_capture_is_caught_by_the_second_replay():
+    rec = Recorder()
+
+    def call(arena):
+        """Stages its input through host memory when it is called: the graph replays the copy, not the input."""
+        staged = arena.bytes("x").view(torch.float32).clone()
+
+        def op():
+            arena.bytes("ws").zero_()
+            arena.bytes("out").view(torch.float32).copy_(2 * staged + arena.bytes("bias").view(torch.float32)[0])
+        rec.enqueue(op)
+    with pytest.raises(A.ArenaViolation) as e:
+        _captured(call, rec)
+    assert e.value.region == "out" and "second replay" in str(e.value) and rec.replays == 2
+
+
+def test_work_done_at_capture_time_instead_of_enqueued_is_caught_before_any_replay():
+    rec = Recorder()
+
+    def call(arena):
+        arena.bytes("ws")[:16] = 0          # "clears a counter" right away, outside the stream
+        rec.enqueue(lambda: _good(arena))
+    with pytest.raises(A.ArenaViolation) as e:
+        _captured(call, rec)
+    assert e.value.region == "ws" and "captured" in str(e.value) and rec.replays == 0
+
+
+def test_a_result_that_depends_on_what_the_previous_replay_left_is_caught_by_the_third_replay():
+    rec = Recorder()
+
+    def op(arena):
+        ws = arena.bytes("ws")
+        again = bool(ws[0] == 0x5A) and bool(ws[1] == 0x5A)          # only its own earlier run leaves both
+        _good(arena)
+        arena.bytes("out").view(torch.float32)[3] += 1.0 if again else 0.0
+        ws[:2] = 0x5A
+    with pytest.raises(A.ArenaViolation) as e:
+        _captured(lambda arena: rec.enqueue(lambda: op(arena)), rec)
+    assert e.value.region == "out" and "third replay" in str(e.value) and rec.replays == 3
+
+
+def test_a_call_that_fails_while_it_is_captured_is_never_replayed():
+    rec = Recorder()
+
+    def call(arena):
+        if rec.ops is not None:
+            return -2
+        rec.enqueue(lambda: _good(arena))
+    with pytest.raises(A.CaptureFailed):
+        _captured(call, rec, last_error=lambda: "refused")
+    assert rec.replays == 0
+
+
+def test_data_sets_whose_outputs_do_not_differ_are_refused():
+    rec = Recorder()
+
+    def call(arena):          # ignores x: both sets give the same output
+        rec.enqueue(lambda: (arena.bytes("ws").zero_(), arena.bytes("out").zero_()))
+    with pytest.raises(AssertionError, match="could show nothing"):
+        _captured(call, rec)
+    assert rec.replays == 0
