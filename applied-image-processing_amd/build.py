@@ -12,7 +12,7 @@ CSRC = os.path.join(PKG, "csrc")
 INC = os.path.join(os.path.dirname(PKG), "include")
 LIB = os.path.join(PKG, "libadain_hip.so")
 # The direct implicit-GEMM and F(2x2,3x3) families of rounds 1-2 were retired in round 6 (git history).
-SOURCES = ["conv_edge.hip", "conv_wino4.hip", "stats.hip", "pixel.hip", "resample.hip", "resample_filters.hip", "flow.hip", "tvl1.hip", "colour.hip", "coral.hip", "jpeg.hip", "jpeg_decode.hip", "png.hip", "png_decode.hip", "palette.hip", "gif.hip", "quantize.hip", "metrics.hip", "guide_loss.hip", "api.hip"]
+SOURCES = ["conv_edge.hip", "conv_wino4.hip", "stats.hip", "pixel.hip", "resample.hip", "resample_filters.hip", "flow.hip", "tvl1.hip", "colour.hip", "coral.hip", "jpeg.hip", "jpeg_decode.hip", "png.hip", "png_decode.hip", "palette.hip", "gif.hip", "quantize.hip", "quantize_refine.hip", "metrics.hip", "guide_loss.hip", "api.hip"]
 # -fvisibility=hidden: the shared library exports the C ABI of include/adain_hip.h (ADAIN_API) and nothing else
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # The MFMA kernels carry their fp32 vector-ALU work (input transform, epilogues) next to the matrix instructions, where
@@ -50,7 +50,7 @@ def build(force=False, verbose=False):
     """Builds the library and returns its path."""
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "device_utils.h", "cv_resize.h", "jpeg_common.h", "png_inflate.h", "pil_taps.h", "gif_lzw.h", "quantize_cut.h")] + [os.path.join(INC, "adain_hip.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "device_utils.h", "cv_resize.h", "jpeg_common.h", "png_inflate.h", "pil_taps.h", "gif_lzw.h", "quantize_cut.h", "quantize_refine.h")] + [os.path.join(INC, "adain_hip.h")]
     hipcc = _hipcc()
     jobs = []
     objs = []

@@ -258,6 +258,10 @@ int launch_gif_encode_u8(const uint8_t* index, int n, int h, int w, int K, int d
 int quantize_palette_bytes(int n, int h, int w, int mode, size_t* workspace_bytes);
 int launch_quantize_palette_u8(const uint8_t* src, int n, int h, int w, int K, int mode, uint8_t* palettes, int32_t* used, void* workspace, size_t workspace_bytes,
                                hipStream_t s);
+// quantize_refine.hip: the rounds of k-means behind the cut (mode's ADAIN_QUANTIZE_REFINE bits), launched by launch_quantize_palette_u8
+unsigned quantize_refine_groups(size_t palettes, size_t pixels);
+void launch_quantize_refine(const uint8_t* src, size_t palettes_n, size_t pixels, unsigned groups, int K, int rounds, uint8_t* palettes, int32_t* used,
+                            void* accumulators, hipStream_t s);
 
 // metrics.hip: per-frame SSIM, MSE, L1 and PSNR of two clips (the rules: top of metrics.hip, tests/metrics_ref.py); the launchers refuse
 // everything themselves

@@ -17,7 +17,9 @@
 //      k = min(k, hi - 1).  [lo..k] keeps the box's index, [k + 1..hi] is appended; both are tightened.
 //   6. Entry i is (2 S_c + w) / (2 w), rounded down, per channel, for box i in index order; entries used..255 are zero; used is the number
 //      of boxes.
-// Known limit: two colours in one cell are merged, so a frame with fewer than K non-empty cells gets used < K however many colours it has.
+// Two colours in one cell are merged, so a frame with fewer than K non-empty cells gets used < K from these rules however many colours
+// it has; the rounds of k-means a call may ask for behind them (rules 7-11, csrc/quantize_refine.hip, mode's ADAIN_QUANTIZE_REFINE bits)
+// move the entries to their pixels' centres and fill the unused ones.
 //
 // Stages (a memset and 3 launches, whatever n; nothing allocates or waits):
 //   hist : the frames' bytes once.  A thread takes 16 pixels from three 16-byte loads (the pixels in front of the first 16-byte
@@ -32,7 +34,7 @@
 //          the boxes' keys in LDS, the marginal one slab count per thread, the two tightenings one slab count per thread (2 boxes x 3
 //          axes x 32 positions), the moments one plane per thread.  The rule functions are quantize_cut.h's, shared with the host.
 #include "common.h"
-#include "quantize_cut.h"
+#include "quantize_refine.h"
 
 namespace adain {
 namespace {
@@ -292,11 +294,19 @@ __global__ __launch_bounds__(CUT_THREADS) void quantize_cut_kernel(void* workspa
 struct QuantPlan {
     size_t palettes, pixels;          // pixels per palette
     unsigned hist_groups;             // workgroups per palette
-    size_t o_grids, total;
+    int rounds;                       // of refinement (csrc/quantize_refine.hip): mode >> 8
+    unsigned assign_groups;
+    size_t o_grids, o_refine, total;
+    size_t clear_bytes;               // from o_grids: the grids and, behind them, the refinement's accumulators
 };
 
+// mode = ADAIN_QUANTIZE_GLOBAL or _PER_FRAME in its low byte, or-ed with ADAIN_QUANTIZE_REFINE(rounds)
 const char* check_quantize_shape(int n, int h, int w, int mode) {
-    if (mode != ADAIN_QUANTIZE_GLOBAL && mode != ADAIN_QUANTIZE_PER_FRAME) return "mode other than ADAIN_QUANTIZE_GLOBAL (0) and ADAIN_QUANTIZE_PER_FRAME (1)";
+    static_assert(ADAIN_QUANTIZE_REFINE_MAX == 64, "the text below names the bound");
+    const int rounds = mode >> 8, which = mode & 0xff;
+    if (mode < 0 || rounds > ADAIN_QUANTIZE_REFINE_MAX || (which != ADAIN_QUANTIZE_GLOBAL && which != ADAIN_QUANTIZE_PER_FRAME))
+        return "mode other than ADAIN_QUANTIZE_GLOBAL (0) and ADAIN_QUANTIZE_PER_FRAME (1), or-ed with ADAIN_QUANTIZE_REFINE(0..64)";
+    mode = which;
     if (n < 1 || n > 65535) return "n outside 1..65535";
     if (h < 1 || w < 1) return "empty frames: height or width below 1";
     const uint64_t frame = (uint64_t)h * (uint64_t)w;          // below 2^62
@@ -307,6 +317,8 @@ const char* check_quantize_shape(int n, int h, int w, int mode) {
 // The one layout of a call
 QuantPlan make_quant_plan(int n, int h, int w, int mode) {
     QuantPlan p{};
+    p.rounds = mode >> 8;
+    mode &= 0xff;
     p.palettes = mode == ADAIN_QUANTIZE_GLOBAL ? 1 : (size_t)n;
     p.pixels = (size_t)h * w * (mode == ADAIN_QUANTIZE_GLOBAL ? (size_t)n : 1);
     // a workgroup clears and flushes a table of SLOTS: it takes two tiles at least where there are two
@@ -314,6 +326,12 @@ QuantPlan make_quant_plan(int n, int h, int w, int mode) {
     p.hist_groups = (unsigned)max((size_t)1, min((tiles + 1) / 2, share));
     Carve ws;
     p.o_grids = ws.take(p.palettes * quant::GRID_BYTES);
+    p.clear_bytes = p.palettes * quant::GRID_BYTES;
+    if (p.rounds) {          // without rounds the layout is the median cut's alone
+        p.assign_groups = quantize_refine_groups(p.palettes, p.pixels);
+        p.o_refine = ws.take(p.palettes * quant::REFINE_BYTES);
+        p.clear_bytes = p.o_refine + p.palettes * quant::REFINE_BYTES - p.o_grids;
+    }
     p.total = ws.at;
     return p;
 }
@@ -347,10 +365,11 @@ int launch_quantize_palette_u8(const uint8_t* src, int n, int h, int w, int K, i
     if (overlaps(used, used_bytes, src, src_bytes)) { set_error("%s: used overlaps src", who); return ADAIN_EINVAL; }
     if (overlaps(workspace, p.total, src, src_bytes)) { set_error("%s: the workspace overlaps src", who); return ADAIN_EINVAL; }
     char* grids = (char*)workspace + p.o_grids;
-    if (hipMemsetAsync(grids, 0, p.palettes * quant::GRID_BYTES, s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return ADAIN_ELAUNCH; }
+    if (hipMemsetAsync(grids, 0, p.clear_bytes, s) != hipSuccess) { set_error("%s: hipMemsetAsync failed", who); return ADAIN_ELAUNCH; }
     quantize_hist_kernel<<<dim3(p.hist_groups, (unsigned)p.palettes), HIST_THREADS, 0, s>>>(src, p.pixels, grids);
     quantize_sat_kernel<<<dim3(5, (unsigned)p.palettes), 1024, 0, s>>>(grids);
     quantize_cut_kernel<<<(unsigned)p.palettes, CUT_THREADS, 0, s>>>(grids, K, palettes, used);
+    if (p.rounds) launch_quantize_refine(src, p.palettes, p.pixels, p.assign_groups, K, p.rounds, palettes, used, (char*)workspace + p.o_refine, s);
     return check_launch(who);
 }
 

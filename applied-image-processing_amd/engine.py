@@ -223,10 +223,11 @@ class AdaINEngine:
         files any reader decodes to the frames' pixels, not Pillow's bytes) -> a list of n ``bytes``; only the files cross to the host."""
         return rt.png_files(*rt.png_encode_u8(frames_u8, filter))
 
-    def quantize_palette_u8(self, frames_u8, K=256, per_frame=False):
+    def quantize_palette_u8(self, frames_u8, K=256, per_frame=False, refine=0):
         """Frames uint8 [n,h,w,3] on the device -> (palettes uint8 [P,256,3], used int32 [P]) on the device: at most ``K`` colours chosen
-        from the frames themselves, for all of them or ``per_frame`` (adain_quantize_palette_u8; ``runtime.quantize_palette_u8``)."""
-        return rt.quantize_palette_u8(frames_u8, K, per_frame)
+        from the frames themselves, for all of them or ``per_frame``, with ``refine`` rounds of k-means behind the median cut
+        (adain_quantize_palette_u8; ``runtime.quantize_palette_u8``)."""
+        return rt.quantize_palette_u8(frames_u8, K, per_frame, refine)
 
     def image_metrics(self, a, b, ssim_map=False):
         """Two clips on the device, uint8 [n,h,w,1|3] or float32 [n,1..4,h,w] -> their per-frame SSIM (window 11), MSE, L1 and PSNR as

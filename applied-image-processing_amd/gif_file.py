@@ -14,8 +14,9 @@ frame is a full frame.
 
 A full-colour clip brings no palette.  ``palette="adaptive"`` chooses one of 256 colours for the whole clip from its frames,
 ``"adaptive-local"`` one per frame - what Pillow writes for the reference's ``create_gif``, which hands it RGB frames - and
-``adaptive(colors, local)`` names either with another count.  The colours are chosen on the device (csrc/quantize.hip,
-``runtime.quantize_palette_u8``: a median cut of its own, not Pillow's palette).  A frame's own table is spliced into its record on the
+``adaptive(colors, local, refine)`` names either with another count, and with ``refine`` = T rounds of k-means behind the cut
+(``"adaptive:N:rT"``; Pillow's ``quantize(kmeans=)`` is the like).  The colours are chosen on the device (csrc/quantize.hip,
+csrc/quantize_refine.hip, ``runtime.quantize_palette_u8``: a median cut of its own, not Pillow's palette).  A frame's own table is spliced into its record on the
 host: the descriptor's flag byte (offset 17 of the record) becomes 0x80 | (g - 1) and 3 * 2^g table bytes follow it, the palette and then
 zeros, g = max(1, ceil(log2 colors)); the header then has no global table (flags 0x70).  Both go with the nearest colour: Pillow's
 ``convert("P", palette=ADAPTIVE)`` does not dither.
@@ -47,21 +48,40 @@ def default_method(palette):
     return "floyd-steinberg-diffused" if isinstance(palette, str) and palette == WEB else "kd-tree"
 
 
-def adaptive(colors=256, local=False):
+def adaptive(colors=256, local=False, refine=0):
     """The ``palette`` of a clip that brings none: ``"adaptive"`` / ``"adaptive-local"``, which stand for 256 colours, or with another
-    count ``"adaptive:N"`` / ``"adaptive-local:N"``."""
+    count ``"adaptive:N"`` / ``"adaptive-local:N"``; with ``refine`` = T rounds of k-means behind the median cut (1..64,
+    ``runtime.quantize_palette_u8``'s) ``"adaptive:N:rT"`` / ``"adaptive-local:N:rT"``: the count rides in the string, as the colours do."""
     name = ADAPTIVE_LOCAL if local else ADAPTIVE
+    if pixelize._refine(refine):
+        return f"{name}:{_colors(colors)}:r{int(refine)}"
     return name if _colors(colors) == 256 else f"{name}:{colors}"
+
+
+def _parse(palette):
+    """(local, colors, refine) of ``adaptive``'s strings, None for any other palette; ValueError for a count outside 1..256 or rounds
+    outside 0..64."""
+    if not isinstance(palette, str):
+        return None
+    name, _, rest = palette.partition(":")
+    count, _, rounds = rest.partition(":")
+    if name not in (ADAPTIVE, ADAPTIVE_LOCAL) or (count and not count.isdigit()):
+        return None
+    if rounds and not (count and rounds[0] == "r" and rounds[1:].isdigit()):
+        return None
+    return name == ADAPTIVE_LOCAL, _colors(int(count)) if count else 256, pixelize._refine(int(rounds[1:])) if rounds else 0
 
 
 def parse_adaptive(palette):
     """(local, colors) of ``adaptive``'s strings, None for any other palette; ValueError for a count outside 1..256."""
-    if not isinstance(palette, str):
-        return None
-    name, _, count = palette.partition(":")
-    if name not in (ADAPTIVE, ADAPTIVE_LOCAL) or (count and not count.isdigit()):
-        return None
-    return name == ADAPTIVE_LOCAL, _colors(int(count)) if count else 256
+    chosen = _parse(palette)
+    return None if chosen is None else chosen[:2]
+
+
+def parse_refine(palette):
+    """The rounds T of ``adaptive``'s ``":rT"`` strings, 0 for the strings without and for any other palette."""
+    chosen = _parse(palette)
+    return 0 if chosen is None else chosen[2]
 
 
 def is_adaptive(palette):
@@ -190,11 +210,11 @@ def index_planes(frames, palette, method="kd-tree"):
     return rt.palette_map_u8(x, pal, pixelize._METRIC[method], index=True)[1]
 
 
-def _write_adaptive(frames, path, local, colors, delay, method, loop, step):
+def _write_adaptive(frames, path, local, colors, refine, delay, method, loop, step):
     """``write_gif`` for the two adaptive palettes: the colours come from the frames (``pixelize.quantize_palettes``: on the device when
-    there is one), a frame is indexed onto its palette's ``used`` colours and coded with K = ``colors``."""
+    there is one; ``refine`` rounds of k-means), a frame is indexed onto its palette's ``used`` colours and coded with K = ``colors``."""
     n, h, w, _ = frames.shape
-    pals, used = pixelize.quantize_palettes(frames, colors, per_frame=local, device=None if _cuda(frames) is not None else "cpu")
+    pals, used = pixelize.quantize_palettes(frames, colors, per_frame=local, device=None if _cuda(frames) is not None else "cpu", refine=refine)
     tables = [pals[i, :u] for i, u in enumerate(used)]          # one, or one per frame
     if _cuda(frames) is None:
         from PIL import Image
@@ -236,8 +256,9 @@ def write_gif(frames, path, palette, fps=20, method="kd-tree", loop=0, sub_batch
     frame, ``loop`` times (0: for ever; None: no loop extension for a single frame).  With a GPU the frames are indexed and coded there,
     ``sub_batch`` frames to a call (default: about 32 MiB of pixels), and only the records are downloaded; without one Pillow writes the
     same indices.  ``palette="adaptive"``: at most 256 colours chosen from the whole clip, the global table; ``"adaptive-local"``: chosen
-    from every frame, a local table each (the module's text); ``adaptive(colors, local)`` names another count.  Returns ``path``."""
-    chosen = parse_adaptive(palette)
+    from every frame, a local table each (the module's text); ``adaptive(colors, local, refine)`` names another count and rounds of
+    k-means behind the median cut.  Returns ``path``."""
+    chosen = _parse(palette)
     pal = None if chosen else _palette(palette)
     method = default_method(palette) if method is None else method
     delay = delay_of(fps)
@@ -250,7 +271,7 @@ def write_gif(frames, path, palette, fps=20, method="kd-tree", loop=0, sub_batch
     if step < 1:
         raise ValueError(f"write_gif: sub_batch must be positive, got {sub_batch!r}")
     if chosen:
-        return _write_adaptive(frames, path, chosen[0], chosen[1], delay, method, loop, step)
+        return _write_adaptive(frames, path, *chosen, delay, method, loop, step)
     if _cuda(frames) is None:
         from PIL import Image
 
@@ -285,6 +306,7 @@ def main(argv=None):
     ap.add_argument("--palette", required=True, help="a name in --palettes, #hex,#hex,..., web (the 6x6x6 cube), adaptive (--colors colours chosen from "
                     "the clip) or adaptive-local (chosen from every frame, a local colour table each)")
     ap.add_argument("--colors", type=int, default=256, help="the colours of --palette adaptive / adaptive-local, 1..256 (default 256)")
+    ap.add_argument("--refine", type=int, default=0, metavar="T", help="rounds of k-means behind the median cut of --palette adaptive / adaptive-local, 0..64 (default 0)")
     ap.add_argument("--palettes", help="a JSON file in the lospec list's format")
     ap.add_argument("--method", default=None, choices=pixelize.METHODS, help="default: kd-tree; floyd-steinberg-diffused for web")
     ap.add_argument("--fps", type=float, default=20)
@@ -292,7 +314,9 @@ def main(argv=None):
     if a.palette in (ADAPTIVE, ADAPTIVE_LOCAL):
         if not 1 <= a.colors <= 256:
             ap.error("--colors must be in 1..256")
-        colors = adaptive(a.colors, a.palette == ADAPTIVE_LOCAL)
+        if not 0 <= a.refine <= pixelize.REFINE_MAX:
+            ap.error(f"--refine must be in 0..{pixelize.REFINE_MAX}")
+        colors = adaptive(a.colors, a.palette == ADAPTIVE_LOCAL, a.refine)
     elif a.palette == WEB:
         colors = WEB
     elif a.palette.startswith("#"):

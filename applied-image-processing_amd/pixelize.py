@@ -17,7 +17,8 @@ the reference's own outputs):
 
 ``extract_palette`` chooses a palette from the image itself (the reference's gui/seven_page.py does it with sklearn's k-means in LAB; here
 a median cut in RGB by the rules at the top of csrc/quantize.hip): ``runtime.quantize_palette_u8`` on the device, the same rules in NumPy
-without one, the same palette either way.  ``--palette adaptive --colors N`` on the command line.
+without one, the same palette either way; ``refine=T`` adds T rounds of k-means in RGB behind the cut (csrc/quantize_refine.hip), which
+also fill the entries the cut left unused.  ``--palette adaptive --colors N --refine T`` on the command line.
 
 With a GPU the work is done by csrc/palette.hip (``runtime.palette_map_u8`` / ``tone_u8`` / ``palette_dither_u8``).  Without one
 (``device="cpu"``, or ``device=None`` on a machine that has none) the same rules run in NumPy on the host: slow for the diffused
@@ -150,9 +151,10 @@ def _run_host(a, pal, method, lut, grey):
 ADAPTIVE = "adaptive"          # --palette adaptive: the image's own colours, ``extract_palette``
 
 
-def _quantize_host(pixels, K):
+def _quantize_host(pixels, K, refine=0):
     """The rules at the top of csrc/quantize.hip in NumPy, for machines without a GPU: ``pixels`` uint8 [N,3], all of one palette ->
-    (uint8 [256,3] with zeros behind the colours, used).  The same palette as ``runtime.quantize_palette_u8``'s."""
+    (uint8 [256,3] with zeros behind the colours, used), then ``refine`` rounds of ``_refine_host``.  The same palette as
+    ``runtime.quantize_palette_u8``'s."""
     px = np.ascontiguousarray(pixels).reshape(-1, 3)
     if len(px) < 1 or len(px) >= 1 << 32:
         raise ValueError(f"extract_palette: a palette needs 1..2^32 - 1 pixels, got {len(px)}")
@@ -201,36 +203,85 @@ def _quantize_host(pixels, K):
     pal = np.zeros((256, 3), dtype=np.uint8)
     for i, (_, _, m) in enumerate(boxes):
         pal[i] = [(2 * m[1 + c] + m[0]) // (2 * m[0]) for c in range(3)]
+    if refine:
+        return _refine_host(v, pal, len(boxes), K, refine)
     return pal, len(boxes)
 
 
-def quantize_palettes(frames, K=256, per_frame=False, device=None):
+REFINE_MAX = 64          # ADAIN_QUANTIZE_REFINE_MAX
+
+
+def _refine(refine):
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= refine <= REFINE_MAX:
+        raise ValueError(f"refine must be an int in 0..{REFINE_MAX} (rounds of k-means behind the median cut), got {refine!r}")
+    return int(refine)
+
+
+def _refine_host(v, pal, used, K, rounds):
+    """Rules 7-11 (top of csrc/quantize_refine.hip) in NumPy: ``rounds`` rounds of k-means on the palette ``pal`` uint8 [256,3] with
+    ``used`` colours, over the pixels ``v`` int64 [N,3] -> (uint8 [256,3], used).  The rules see the multiset of the pixels only, so the
+    work is done on the distinct colours and their counts."""
+    code, weight = np.unique((v[:, 0] << 16) | (v[:, 1] << 8) | v[:, 2], return_counts=True)
+    col = np.stack([code >> 16, (code >> 8) & 255, code & 255], axis=1)
+    P, u = pal.astype(np.int64), int(used)
+    step = 8192          # colours at a time: a [step, 256] table of distances
+    for _ in range(rounds):
+        j, d = np.empty(len(col), dtype=np.int64), np.empty(len(col), dtype=np.int64)
+        for at in range(0, len(col), step):
+            c = col[at:at + step]
+            dist = sum((c[:, ch, None] - P[None, :u, ch]) ** 2 for ch in range(3))
+            near = dist.argmin(axis=1)          # the first of equal minima: the lowest index
+            j[at:at + step], d[at:at + step] = near, dist[np.arange(len(c)), near]
+        # bincount sums in float64, exact below 2^53 (255 x 2^32 is below 2^40)
+        n = np.bincount(j, weights=weight, minlength=256).astype(np.int64)
+        S = np.stack([np.bincount(j, weights=weight * col[:, ch], minlength=256).astype(np.int64) for ch in range(3)], axis=1)
+        F = np.zeros(256, dtype=np.int64)
+        np.maximum.at(F, j, (d << 24) | (0xFFFFFF - code))
+        live = n > 0
+        new = P.copy()
+        new[live] = (2 * S[live] + n[live, None]) // (2 * n[live, None])
+        free = np.flatnonzero(n[:K] == 0)
+        donors = np.flatnonzero(live & ((F >> 24) > 0))
+        donors = donors[np.lexsort((donors, -(F[donors] >> 24)))]          # the distance descending, then the index ascending
+        m = min(len(free), len(donors))
+        if m:
+            far = 0xFFFFFF - (F[donors[:m]] & 0xFFFFFF)
+            new[free[:m]] = np.stack([far >> 16, (far >> 8) & 255, far & 255], axis=1)
+            u = max(u, int(free[m - 1]) + 1)
+        P = new
+    return P.astype(np.uint8), u
+
+
+def quantize_palettes(frames, K=256, per_frame=False, device=None, refine=0):
     """``frames`` uint8 [n,h,w,3], a NumPy array or a tensor -> (palettes uint8 [P,256,3], used: a list of P ints) as NumPy, chosen on the
     device the frames are on (an array goes to the current GPU when there is one; ``device="cpu"``: never) by ``runtime.quantize_palette_u8``,
-    on the host by the same rules in NumPy.  Waits for the device."""
+    on the host by the same rules in NumPy.  ``refine``: rounds of k-means behind the median cut, 0..64.  Waits for the device."""
     if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= 256:
         raise ValueError(f"a palette has 1..256 colours, got {K!r}")
+    refine = _refine(refine)
     torch = _torch()
     dev = _device(device, frames, "tensor" if isinstance(frames, torch.Tensor) else "numpy")
     if dev is None:
         a = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
-        parts = [_quantize_host(f, int(K)) for f in a] if per_frame else [_quantize_host(a, int(K))]
+        parts = [_quantize_host(f, int(K), refine) for f in a] if per_frame else [_quantize_host(a, int(K), refine)]
         return np.stack([p for p, _ in parts]), [u for _, u in parts]
     from . import runtime as rt
-    pals, used = rt.quantize_palette_u8(_tensor(frames).to(dev), int(K), per_frame)
+    pals, used = rt.quantize_palette_u8(_tensor(frames).to(dev), int(K), per_frame, refine)
     return pals.cpu().numpy(), used.cpu().tolist()
 
 
-def extract_palette(image, K, per_frame=False, device=None):
+def extract_palette(image, K, per_frame=False, device=None, refine=0):
     """At most ``K`` colours chosen from ``image`` itself - a PIL image, a uint8 NumPy array or a uint8 tensor, [h,w,3] or [n,h,w,3] - as
     uint8 [used,3] (the reference's gui/seven_page.py ``extract_palette`` takes ``num_colors`` by k-means in LAB; this is a median cut in
-    RGB, the rules at the top of csrc/quantize.hip).  One palette for all frames, or with ``per_frame`` a list of one per frame.  With a
-    GPU the palette is chosen there, without one (or ``device="cpu"``) by the same rules in NumPy: the same palette.  ``used`` is below
-    ``K`` when the image has fewer than ``K`` non-empty cells of 8 x 8 x 8 colours."""
+    RGB, the rules at the top of csrc/quantize.hip, with ``refine`` rounds of k-means in RGB behind it, 0..64: csrc/quantize_refine.hip).
+    One palette for all frames, or with ``per_frame`` a list of one per frame.  With a
+    GPU the palette is chosen there, without one (or ``device="cpu"``) by the same rules in NumPy: the same palette.  Without ``refine``
+    ``used`` is below ``K`` when the image has fewer than ``K`` non-empty cells of 8 x 8 x 8 colours; the rounds fill the unused entries
+    with the image's farthest colours, up to twice as many a round."""
     _, frames = _open(image)
     if frames.ndim == 3:
         frames = frames[None]
-    pals, used = quantize_palettes(frames, K, per_frame, device)
+    pals, used = quantize_palettes(frames, K, per_frame, device, refine)
     out = [pals[i, :u].copy() for i, u in enumerate(used)]
     return out if per_frame else out[0]
 
@@ -394,6 +445,7 @@ def main(argv=None):
     ap.add_argument("--palette", required=True, help="a name in --palettes, #hex,#hex,... or adaptive (--colors colours chosen from the image)")
     ap.add_argument("--palettes", help="a JSON file in the lospec list's format")
     ap.add_argument("--colors", type=int, default=256, help="the colours of --palette adaptive, 1..256 (default 256)")
+    ap.add_argument("--refine", type=int, default=0, metavar="T", help="rounds of k-means behind --palette adaptive's median cut, 0..64 (default 0)")
     ap.add_argument("--method", default="rgb", choices=METHODS + ("LAB",))
     ap.add_argument("--factor", type=int, default=1)
     ap.add_argument("--resampling", default="BILINEAR", type=str.upper, choices=tuple(RESAMPLING), metavar="NAME",
@@ -406,8 +458,10 @@ def main(argv=None):
     if a.palette == ADAPTIVE:
         if not 1 <= a.colors <= 256:
             ap.error("--colors must be in 1..256")
+        if not 0 <= a.refine <= REFINE_MAX:
+            ap.error(f"--refine must be in 0..{REFINE_MAX}")
         # of the image as the recolouring sees it: downsampled and toned, not yet recoloured
-        colors = extract_palette(convert_image(image, a.factor, RESAMPLING[a.resampling], a.grayscale, a.brightness, a.contrast), a.colors)
+        colors = extract_palette(convert_image(image, a.factor, RESAMPLING[a.resampling], a.grayscale, a.brightness, a.contrast), a.colors, refine=a.refine)
     elif a.palette.startswith("#"):
         colors = parse_palette(a.palette.split(","))
     else:

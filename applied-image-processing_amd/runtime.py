@@ -1371,31 +1371,43 @@ def gif_encode_u8(index, K, delay_cs):
 
 # --- a palette chosen from the frames (adain_quantize_palette_u8) -------------------------------------------------------------------------
 QUANTIZE_GLOBAL, QUANTIZE_PER_FRAME = 0, 1          # ADAIN_QUANTIZE_*
+QUANTIZE_REFINE_MAX = 64                            # ADAIN_QUANTIZE_REFINE_MAX
 
 
-def quantize_palette_sizes(n, h, w, per_frame=False):
+def quantize_mode(per_frame=False, refine=0):
+    """The call's ``mode``: ADAIN_QUANTIZE_GLOBAL or _PER_FRAME, or-ed with ADAIN_QUANTIZE_REFINE(refine).  ValueError for a ``refine``
+    that is not an int in 0..64."""
+    if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= QUANTIZE_REFINE_MAX:
+        raise ValueError(f"quantize_palette_u8: refine must be an int in 0..{QUANTIZE_REFINE_MAX}, got {refine!r}")
+    return (QUANTIZE_PER_FRAME if per_frame else QUANTIZE_GLOBAL) | refine << 8
+
+
+def quantize_palette_sizes(n, h, w, per_frame=False, refine=0):
     """workspace_bytes of adain_quantize_palette_u8_bytes.  Host only.  AdainHipError for a refused shape."""
-    return _size_query("adain_quantize_palette_u8_bytes", n, h, w, QUANTIZE_PER_FRAME if per_frame else QUANTIZE_GLOBAL)[0]
+    return _size_query("adain_quantize_palette_u8_bytes", n, h, w, quantize_mode(per_frame, refine))[0]
 
 
-def quantize_palette_u8(frames, K=256, per_frame=False):
+def quantize_palette_u8(frames, K=256, per_frame=False, refine=0):
     """Frames uint8 [n,h,w,3] (or [h,w,3]) on the device -> (palettes uint8 [P,256,3], used int32 [P]), both on the device: at most ``K``
     colours chosen from the frames themselves, one palette for all of them (P = 1) or with ``per_frame`` one each (P = n).  Palette p's
     colours are its first ``used[p]`` entries, the rest is zero.  A median cut over 32 x 32 x 32 cells by the rules of csrc/quantize.hip
-    (tests/quantize_ref.py), not Pillow's palette; a function of the pixels, ``K`` and ``per_frame`` alone.  ``palette_map_u8`` /
+    (tests/quantize_ref.py), not Pillow's palette; a function of the pixels, ``K`` and ``per_frame`` alone.  ``refine`` = T in 1..64: T
+    rounds of k-means behind the cut, in integers (rules 7-11, csrc/quantize_refine.hip, tests/quantize_refine_ref.py): the entries move
+    to their pixels' centres and the unused ones take the farthest colours, so a frame with fewer than ``K`` non-empty cells still gets
+    ``K`` colours where it has them; ValueError outside 0..64.  ``palette_map_u8`` /
     ``palette_dither_u8`` take ``palettes[p, :used[p]]``.  (``quantize_u8`` is the float -> uint8 quantiser of ``save_image``.)  Nothing is
     copied to the host and nothing waits."""
     what = "quantize_palette_u8"
     if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 256:
         raise AdainHipError(f"{what}: K must be an int in 1..256, got {K!r}")
+    mode = quantize_mode(per_frame, refine)
     x = _rgb_frames(frames, what)
     n, h, w, _ = x.shape
     P = n if per_frame else 1
     palettes = torch.empty((P, 256, 3), dtype=torch.uint8, device=x.device)
     used = torch.empty((P,), dtype=torch.int32, device=x.device)
-    with scratch(x.device, "quantize", quantize_palette_sizes, n, h, w, bool(per_frame)) as ws:
-        _launch("adain_quantize_palette_u8", x.data_ptr(), n, h, w, K, QUANTIZE_PER_FRAME if per_frame else QUANTIZE_GLOBAL, palettes.data_ptr(), used.data_ptr(),
-                ws.data_ptr(), ws.numel())
+    with scratch(x.device, "quantize", quantize_palette_sizes, n, h, w, bool(per_frame), refine) as ws:
+        _launch("adain_quantize_palette_u8", x.data_ptr(), n, h, w, K, mode, palettes.data_ptr(), used.data_ptr(), ws.data_ptr(), ws.numel())
     return palettes, used
 
 

@@ -345,7 +345,7 @@ def apply_style_transfer_ada(content_dir, style_image_path, output_dir, flow_met
     any other .png keeps PIL.
     ``gif_path`` (default None: nothing changes): rank 0 also keeps the clip's final frames on the device and writes them there as one
     animated GIF at the end (``gif_file.write_gif``: ``gif_fps``; ``gif_palette``, ``gif_file.header``'s forms, ``"adaptive"`` / ``"adaptive-local"`` for 256 colours
-    chosen from the clip / from every frame, None for the 6x6x6 cube ``"web"``; ``gif_method``, None for error diffusion onto the cube and the nearest colour onto any other palette)."""
+    chosen from the clip / from every frame, ``gif_file.adaptive(colors, local, refine)``'s strings for another count and rounds of k-means, None for the 6x6x6 cube ``"web"``; ``gif_method``, None for error diffusion onto the cube and the nearest colour onto any other palette)."""
     outputs = rt.OutputRoutes(rt.JpegRoutes(jpeg_on_device, jpeg_decode_on_device, jpeg_decode_progressive, jpeg_options), rt.PngRoute(png_on_device, None, png_decode_on_device))
     with _routes_scope(outputs if outputs.png.decode_on_device else outputs.jpeg):
         return _run_clip(content_dir, [style_image_path], output_dir, flow_method, alpha, target_resolution, cancel_flag, offset, prominence,

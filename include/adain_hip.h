@@ -729,9 +729,28 @@ ADAIN_API int adain_gif_encode_u8(const uint8_t* index_u8, int n, int h, int w, 
  * 1..256, a mode other than the two, h, w or n below 1, n above 65535, 2^32 or more pixels for one palette (n h w for GLOBAL, h w for
  * PER_FRAME), a null workspace, workspace_bytes below the query's, a workspace that is not 8-byte aligned, used that is not 4-byte
  * aligned, palettes, used or the workspace overlapping src.  Nothing is copied to the host and nothing waits; 3 kernel launches and
- * one memset per call, whatever n. */
+ * one memset per call, whatever n.
+ * K-MEANS REFINEMENT (added without a version change: no declaration moved or was added).  mode & 0xff is ADAIN_QUANTIZE_GLOBAL or
+ * ADAIN_QUANTIZE_PER_FRAME; mode >> 8 is the number of rounds T, 0..ADAIN_QUANTIZE_REFINE_MAX, or-ed on with ADAIN_QUANTIZE_REFINE(T);
+ * every other mode is refused as above.  T = 0 is the call described above: the same launches, workspace, palette and used.  With
+ * T > 0 the cut's palette P and used = u are refined T times, in integers, by the rules at the top of csrc/quantize_refine.hip, restated
+ * in tests/quantize_refine_ref.py:
+ *   7.  every pixel goes to the entry i < u with the smallest squared Euclidean distance, the lowest i among equals;
+ *   8.  per entry: the count n, the sums S[c], and the far key F = max((d << 24) | (0xFFFFFF - (r << 16 | g << 8 | b))) over its pixels
+ *       at distance d: the farthest colour, among equally far ones the smallest r, g, b value;
+ *   9.  n > 0: the entry becomes (2 S[c] + n) / (2 n), rounded down; n == 0: it stays;
+ *   10. the free slots - i < K with n == 0, ascending: every i >= u and any live entry without a pixel - take, one each, the far colours
+ *       of the donors - entries with n > 0 and F >> 24 > 0, by that distance descending, then index ascending - as long as both lists
+ *       last; u' = max(u, 1 + the highest slot filled): a palette can at most double per round, so a frame with fewer than K non-empty
+ *       cells reaches K colours where it has them;
+ *   11. P, u <- P', u'; entries u..255 are zero at the end.
+ * The result is a function of the multiset of the pixels, K, T and the mode alone.  A round that changes nothing is a fixed point: T and
+ * T + 1 then agree.  The workspace gains per palette the accumulators of rule 8, 256 x 5 x 8 bytes, behind the grids; the call is
+ * 3 + 2 T kernel launches and one memset, a chain fixed by the arguments. */
 #define ADAIN_QUANTIZE_GLOBAL 0
 #define ADAIN_QUANTIZE_PER_FRAME 1
+#define ADAIN_QUANTIZE_REFINE_MAX 64
+#define ADAIN_QUANTIZE_REFINE(t) ((t) << 8)   /* or-ed onto ADAIN_QUANTIZE_GLOBAL / _PER_FRAME */
 ADAIN_API int adain_quantize_palette_u8_bytes(int n, int h, int w, int mode, size_t* workspace_bytes);
 ADAIN_API int adain_quantize_palette_u8(const uint8_t* src_u8, int n, int h, int w, int K, int mode, uint8_t* palettes_u8, int32_t* used_i32,
                                         void* workspace, size_t workspace_bytes, adain_stream_t stream);

@@ -35,8 +35,9 @@ KS = (16, 256)
 STAGES = {"hist": "quantize_hist_kernel", "sat": "quantize_sat_kernel", "cut": "quantize_cut_kernel"}
 
 
-def stage_ms(fn, reps):
-    """{stage: spread} from the profiler's kernel records of ``reps`` calls, or None."""
+def stage_ms(fn, reps, stages=STAGES):
+    """{stage: spread} from the profiler's kernel records of ``reps`` calls, or None.  ``stages``: {stage: its kernel's name}; a stage's
+    figure is per launch."""
     try:
         from torch.profiler import ProfilerActivity, profile
 
@@ -45,9 +46,9 @@ def stage_ms(fn, reps):
             for _ in range(reps):
                 fn()
             torch.cuda.synchronize()
-        times = {k: [] for k in STAGES}
+        times = {k: [] for k in stages}
         for e in prof.events():
-            for k, kernel in STAGES.items():
+            for k, kernel in stages.items():
                 if kernel in e.name:
                     times[k].append(getattr(e, "device_time", None) or getattr(e, "cuda_time", 0.0))
         if any(len(v) < reps for v in times.values()):
@@ -100,12 +101,9 @@ def gif(x, host, reps, pillow_reps):
                 "faster_than_pillow": below(a, b), "slower_than_pillow": below(b, a)}
 
 
-def main():
-    ap = arguments(__doc__)
-    ap.add_argument("--pillow_reps", type=int, default=20)
-    args = ap.parse_args()
-    dev = gpu_setup("quantize_bench")
-    reps, pillow_reps = max(args.reps, 200), max(4, args.pillow_reps)
+def inputs(dev):
+    """({kind: one 1080 x 1920 frame uint8 [1,h,w,3] on ``dev``}, the 64-frame 135 x 240 clip): what this tool and
+    tools/quantize_refine_timing.py time."""
     engine = AdaINEngine(synth.to_torch(synth.vgg_state_dict(0, full=False)), synth.to_torch(synth.decoder_state_dict(0)), dev)
     engine.set_style(torch.from_numpy(synth.image(4, 1, 512, 512)).to(dev))
 
@@ -117,17 +115,26 @@ def main():
             parts.append(engine.stylize_u8(source, alpha=0.5).contiguous())
         return torch.cat(parts).contiguous()
 
-    res = header(reps=reps, pillow_reps=pillow_reps, pillow=PIL.__version__, frames={}, clips={})
     h, w = 1080, 1920
     sources = {"stylised": stylised(1, h, w), "noise": torch.from_numpy(np.random.default_rng(5).integers(0, 256, (1, h, w, 3), dtype=np.uint8)).to(dev),
                "flat": torch.full((1, h, w, 3), 255, dtype=torch.uint8, device=dev)}
+    return sources, stylised(64, 135, 240)
+
+
+def main():
+    ap = arguments(__doc__)
+    ap.add_argument("--pillow_reps", type=int, default=20)
+    args = ap.parse_args()
+    dev = gpu_setup("quantize_bench")
+    reps, pillow_reps = max(args.reps, 200), max(4, args.pillow_reps)
+    sources, clip = inputs(dev)
+    res = header(reps=reps, pillow_reps=pillow_reps, pillow=PIL.__version__, frames={}, clips={})
     for kind, x in sources.items():
         res["frames"][kind] = chooser(x, x.cpu().numpy(), False, reps, pillow_reps)
         print(kind, json.dumps(res["frames"][kind]), file=sys.stderr, flush=True)
     hist = lambda kind: (res["frames"][kind]["K256"]["stage_ms"] or {}).get("hist")
     if hist("flat") and hist("noise"):
         res["hist_flat_over_noise"] = round(hist("flat")["median"] / hist("noise")["median"], 3)
-    clip = stylised(64, 135, 240)
     host = clip.cpu().numpy()
     for mode, per_frame in (("global", False), ("per_frame", True)):
         res["clips"][mode] = chooser(clip, host, per_frame, reps, pillow_reps)
