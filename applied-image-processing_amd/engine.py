@@ -278,6 +278,12 @@ class AdaINEngine:
         before (``rt.png_decode_u8``)."""
         return rt.png_decode_u8(files, self.device, mode, report)
 
+    def gif_decode_u8(self, data, report=None):
+        """The bytes of an animated GIF -> (frames uint8 [n,H,W,3] on the engine's device, ``gif_file.GifInfo``): the frames Pillow's
+        ``ImageSequence.Iterator`` + ``convert("RGB")`` gives, decoded and composed on the device (adain_gif_decode_u8), by Pillow
+        where the parser or a frame's status says so (``rt.gif_decode_u8``)."""
+        return rt.gif_decode_u8(data, self.device, report)
+
     def jpeg_roundtrip_u8(self, frames_u8, quality=rt.JPEG_DEFAULT_QUALITY):
         """uint8 frames [n,h,w,3|1] on the device -> the frames Pillow decodes from the JPEG files it would save for them at ``quality``
         (what ``video._jpeg_roundtrip`` computes on the host), byte for byte, on the device (adain_jpeg_roundtrip_u8)."""

@@ -21,11 +21,25 @@ host: the descriptor's flag byte (offset 17 of the record) becomes 0x80 | (g - 1
 zeros, g = max(1, ceil(log2 colors)); the header then has no global table (flags 0x70).  Both go with the nearest colour: Pillow's
 ``convert("P", palette=ADAPTIVE)`` does not dither.
 
-Not built: frame differencing and transparency, interlace, reading GIFs.
+Not built: frame differencing and transparency, interlace.
+
+Reading (``parse``, ``read_gif``): the host walks the file - header, screen, colour tables, extensions, descriptors, the data sub-blocks of
+every frame joined - and the device decodes and composes the clip (csrc/gif_decode.hip, ``runtime.gif_decode_u8``): the frames Pillow's
+``ImageSequence.Iterator`` + ``convert("RGB")`` gives, pixel for pixel.  Taken: ``GIF87a`` / ``GIF89a``; a screen of 1..65535 a side; a
+global table or none; per frame at most one graphic control extension (delay, disposal 0..3, transparent index) and a descriptor whose
+rectangle is not empty and lies inside the screen, a local table or none (some table there must be), the interlace flag, a minimum code
+size of 2..8, data sub-blocks of any lengths; the NETSCAPE2.0 loop count in front of the first frame; comment, plain-text and unknown
+application extensions, skipped; 1..65535 frames; the trailer.  Everything else is refused (``UnsupportedGif``, the reason in words) and
+stays with Pillow: a frame that leaves the screen (Pillow grows the screen), no table, code size 1 or above 8, disposal 4..7, a block that
+passes the end of the file, a missing trailer, junk between blocks, a second graphic control extension in front of one frame, and a colour
+table that is the grey ramp 0, 1, 2, ... (Pillow opens such a frame in mode "L").  The parser never makes a caller fail: every caller
+catches ``UnsupportedGif`` and takes Pillow.
 
 Without a GPU the same indices go through Pillow's own ``save(save_all=True)``: other bytes, the same decoded pixels.
 """
+import collections
 import struct
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -297,13 +311,210 @@ def write_gif(frames, path, palette, fps=20, method="kd-tree", loop=0, sub_batch
     return path
 
 
+# ---- reading -------------------------------------------------------------------------------------------------------------------------
+MAX_FRAMES = 65535
+DEFAULT_FPS = 20                       # ``write_gif``'s default, and ``clip_fps``'s answer for a clip of zero delays
+
+# durations: milliseconds per frame, as Pillow's ``info["duration"]`` (0 for a frame without a graphic control extension); loop: the
+# NETSCAPE2.0 count (0: for ever) or None for a file without one; size: (w, h) of the screen
+GifInfo = collections.namedtuple("GifInfo", "durations loop size")
+
+
+class UnsupportedGif(Exception):
+    """The file is not one the device decoder takes; str(e) says why.  Callers fall back to Pillow."""
+
+
+@dataclass
+class GifFrame:
+    left: int
+    top: int
+    w: int
+    h: int
+    interlace: bool
+    code_size: int              # the minimum code size, 2..8
+    disposal: int               # 0..3, as the file has it (0 inherits the method in force: csrc/gif_decode.hip, rule 3)
+    transparent: object         # the transparent index, or None
+    delay_cs: int               # centiseconds; 0 without a graphic control extension
+    table: bytes                # the frame's colour table, its own or the global one: 3 bytes an entry
+    local: bool                 # the table is the frame's own
+    data: bytes                 # the LZW data: the sub-blocks joined
+
+
+@dataclass
+class GifClip:
+    w: int
+    h: int
+    background: int             # the screen's background index; 0 in a file without a global table, as Pillow has it
+    loop: object                # the NETSCAPE2.0 count, or None
+    frames: list
+
+    @property
+    def durations(self):
+        return [10 * f.delay_cs for f in self.frames]
+
+    @property
+    def info(self):
+        return GifInfo(self.durations, self.loop, (self.w, self.h))
+
+
+def _grey_ramp(table):
+    return all(table[3 * i] == table[3 * i + 1] == table[3 * i + 2] == i for i in range(len(table) // 3))
+
+
+def _blocks(data, at, what):
+    """The sub-blocks from ``at`` on -> (their list, the offset behind the terminator)."""
+    out = []
+    while True:
+        if at >= len(data):
+            raise UnsupportedGif(f"{what}: a block that passes the end of the file")
+        size = data[at]
+        at += 1
+        if size == 0:
+            return out, at
+        if at + size > len(data):
+            raise UnsupportedGif(f"{what}: a block that passes the end of the file")
+        out.append(data[at:at + size])
+        at += size
+
+
+def parse(data):
+    """bytes of a file -> GifClip, or UnsupportedGif (the module's text lists what is taken)."""
+    data = bytes(data)
+    n = len(data)
+    if data[:6] not in (b"GIF87a", b"GIF89a"):
+        raise UnsupportedGif("not a GIF file (no signature)")
+    if n < 13:
+        raise UnsupportedGif("truncated inside the logical screen descriptor")
+    w, h, flags, background, _ = struct.unpack_from("<HHBBB", data, 6)
+    if w < 1 or h < 1:
+        raise UnsupportedGif(f"an empty screen ({w} x {h})")
+    at = 13
+    global_table = None
+    if flags & 0x80:
+        size = 3 << ((flags & 7) + 1)
+        if at + size > n:
+            raise UnsupportedGif("the global colour table passes the end of the file")
+        global_table = data[at:at + size]
+        at += size
+        if _grey_ramp(global_table):
+            raise UnsupportedGif("a global colour table that is the grey ramp (Pillow opens it in mode L)")
+    else:
+        background = 0
+    loop, frames, control = None, [], None
+    while True:
+        if at >= n:
+            raise UnsupportedGif("no trailer")
+        kind = data[at]
+        at += 1
+        if kind == 0x3B:
+            break
+        if kind == 0x21:
+            if at >= n:
+                raise UnsupportedGif("truncated inside an extension")
+            label = data[at]
+            blocks, at = _blocks(data, at + 1, f"extension {label:#04x}")
+            if label == 0xF9:
+                if control is not None:
+                    raise UnsupportedGif("two graphic control extensions in front of one frame")
+                if len(blocks) != 1 or len(blocks[0]) != 4:
+                    raise UnsupportedGif("a graphic control extension that is not one block of 4 bytes")
+                packed, delay, index = struct.unpack("<BHB", blocks[0])
+                disposal = packed >> 2 & 7
+                if disposal > 3:
+                    raise UnsupportedGif(f"disposal method {disposal}")
+                control = (disposal, index if packed & 1 else None, delay)
+            elif label == 0xFF and not frames and blocks and blocks[0].startswith(b"NETSCAPE2.0"):
+                if len(blocks) > 1 and len(blocks[1]) >= 3 and blocks[1][0] == 1:
+                    loop = blocks[1][1] | blocks[1][2] << 8
+            continue                    # comment, plain text, other applications: skipped
+        if kind != 0x2C:
+            raise UnsupportedGif(f"byte {kind:#04x} at {at - 1} where a block should start")
+        if at + 9 > n:
+            raise UnsupportedGif("truncated inside an image descriptor")
+        left, top, fw, fh, fl = struct.unpack_from("<HHHHB", data, at)
+        at += 9
+        k = len(frames)
+        if fw < 1 or fh < 1:
+            raise UnsupportedGif(f"frame {k}: an empty rectangle")
+        if left + fw > w or top + fh > h:
+            raise UnsupportedGif(f"frame {k}: the rectangle {fw} x {fh} at ({left}, {top}) leaves the {w} x {h} screen")
+        if fw * fh >= 1 << 31:
+            raise UnsupportedGif(f"frame {k}: 2^31 pixels or more")
+        table, local = global_table, False
+        if fl & 0x80:
+            size = 3 << ((fl & 7) + 1)
+            if at + size > n:
+                raise UnsupportedGif(f"frame {k}: the local colour table passes the end of the file")
+            table, local = data[at:at + size], True
+            at += size
+            if _grey_ramp(table):
+                raise UnsupportedGif(f"frame {k}: a local colour table that is the grey ramp (Pillow opens it in mode L)")
+        if table is None:
+            raise UnsupportedGif(f"frame {k}: no colour table, neither its own nor a global one")
+        if at >= n:
+            raise UnsupportedGif(f"frame {k}: truncated in front of the code size")
+        code_size = data[at]
+        if not 2 <= code_size <= 8:
+            raise UnsupportedGif(f"frame {k}: minimum code size {code_size}")
+        blocks, at = _blocks(data, at + 1, f"frame {k}")
+        if k >= MAX_FRAMES:
+            raise UnsupportedGif(f"more than {MAX_FRAMES} frames")
+        disposal, transparent, delay = control if control is not None else (0, None, 0)
+        control = None
+        frames.append(GifFrame(left, top, fw, fh, bool(fl & 0x40), code_size, disposal, transparent, delay, table, local, b"".join(blocks)))
+    if not frames:
+        raise UnsupportedGif("no frames")
+    return GifClip(w, h, background, loop, frames)
+
+
+def pil_clip(data):
+    """Pillow's clip: (uint8 [n,H,W,3] array, GifInfo); its exceptions pass through."""
+    import io
+
+    from PIL import Image, ImageSequence
+
+    im = Image.open(io.BytesIO(bytes(data)))
+    frames, durations = [], []
+    for f in ImageSequence.Iterator(im):
+        frames.append(np.asarray(f.convert("RGB")))
+        durations.append(f.info.get("duration", 0))
+    return np.stack(frames), GifInfo(durations, im.info.get("loop"), im.size)
+
+
+def read_gif(path_or_bytes, device=None):
+    """The counterpart of ``write_gif``: a file's path or its bytes -> (frames uint8 [n,H,W,3], GifInfo).  With a GPU the clip is decoded
+    there (``runtime.gif_decode_u8``; ``device``: default the current one) and the frames are a tensor on it; without one, or with
+    ``device="cpu"``, Pillow decodes and the same frames come as a NumPy array."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(str(path_or_bytes), "rb") as f:
+            data = f.read()
+    import torch
+
+    if str(device) == "cpu" or not torch.cuda.is_available():
+        return pil_clip(data)
+    from . import runtime as rt
+    return rt.gif_decode_u8(data, device)
+
+
+def clip_fps(info):
+    """The frames per second ``write_gif`` would give the clip's pace back with: 100 / round(mean delay in centiseconds);
+    ``DEFAULT_FPS`` for a clip of zero delays."""
+    durations = list(info.durations)
+    cs = int(round(sum(durations) / (10 * len(durations)))) if durations else 0
+    return 100 / cs if cs > 0 else float(DEFAULT_FPS)
+
+
 def main(argv=None):
     import argparse
 
     ap = argparse.ArgumentParser(prog="python -m applied_image_processing_amd.gif_file", description="Write a directory of frames as an animated GIF on a palette.")
-    ap.add_argument("frames_dir")
-    ap.add_argument("output")
-    ap.add_argument("--palette", required=True, help="a name in --palettes, #hex,#hex,..., web (the 6x6x6 cube), adaptive (--colors colours chosen from "
+    ap.add_argument("frames_dir", help="the directory of frames; with --extract the GIF to read")
+    ap.add_argument("output", help="the GIF to write; with --extract the directory the frames go to")
+    ap.add_argument("--extract", action="store_true", help="the other way round: write the frames of the GIF FRAMES_DIR into the directory OUTPUT "
+                    "as frame_0000.png, ... (video.gif_to_frames)")
+    ap.add_argument("--palette", help="a name in --palettes, #hex,#hex,..., web (the 6x6x6 cube), adaptive (--colors colours chosen from "
                     "the clip) or adaptive-local (chosen from every frame, a local colour table each)")
     ap.add_argument("--colors", type=int, default=256, help="the colours of --palette adaptive / adaptive-local, 1..256 (default 256)")
     ap.add_argument("--refine", type=int, default=0, metavar="T", help="rounds of k-means behind the median cut of --palette adaptive / adaptive-local, 0..64 (default 0)")
@@ -311,6 +522,14 @@ def main(argv=None):
     ap.add_argument("--method", default=None, choices=pixelize.METHODS, help="default: kd-tree; floyd-steinberg-diffused for web")
     ap.add_argument("--fps", type=float, default=20)
     a = ap.parse_args(argv)
+    if a.extract:
+        from . import video
+
+        info = video.gif_to_frames(a.frames_dir, a.output)
+        print(f"{len(info.durations)} frames of {info.size[0]} x {info.size[1]}, {clip_fps(info):g} fps")
+        return 0
+    if a.palette is None:
+        ap.error("the following arguments are required: --palette")
     if a.palette in (ADAPTIVE, ADAPTIVE_LOCAL):
         if not 1 <= a.colors <= 256:
             ap.error("--colors must be in 1..256")

@@ -156,7 +156,17 @@ SIGNATURES = {
     "adain_conv3x3_wino4_split": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p] + [_c_int] * 10 + [_c_void_p, _c_size_t, _c_void_p]),
 }
 
+# The GIF decoder's calls: include/adain_gif_decode.h, a header and a library of their own (the header says why).  name -> (restype,
+# argtypes), one to one as above; ``_entry`` finds a name's function in the library that has it, so ``call`` launches both alike.
+GIF_DECODE_LIB_PATH = os.path.join(_PKG, "libadain_gif_decode.so")
+GIF_DECODE_SIGNATURES = {
+    "adain_gif_decode_last_error": (ctypes.c_char_p, []),
+    "adain_gif_decode_u8_bytes": (_c_int, [_c_int] * 3 + [_c_size_t, ctypes.POINTER(_c_size_t)]),
+    "adain_gif_decode_u8": (_c_int, [_c_void_p, _c_size_t, _c_void_p] + [_c_int] * 3 + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+}
+
 _lib = None
+_gif_decode_lib = None
 _lock = threading.Lock()
 
 
@@ -186,6 +196,27 @@ def lib():
     return _lib
 
 
+def gif_decode_lib():
+    """Loads the GIF decoder's library once.  Raises if it has not been built: a missing kernel is an error, never a fall-back."""
+    global _gif_decode_lib
+    if _gif_decode_lib is None:
+        with _lock:
+            if _gif_decode_lib is None:
+                if not os.path.exists(GIF_DECODE_LIB_PATH):
+                    raise AdainHipError(f"{GIF_DECODE_LIB_PATH} is missing: build it with `python applied-image-processing_amd/build.py`")
+                l = ctypes.CDLL(GIF_DECODE_LIB_PATH)
+                for name, (res, args) in GIF_DECODE_SIGNATURES.items():
+                    f = getattr(l, name)
+                    f.restype, f.argtypes = res, args
+                _gif_decode_lib = l
+    return _gif_decode_lib
+
+
+def _entry(name):
+    """The C function ``name`` of whichever library declares it."""
+    return getattr(gif_decode_lib() if name in GIF_DECODE_SIGNATURES else lib(), name)
+
+
 def use_library(path):
     """Switches the process to another build of the library (bench.py --lib: a same-box A/B against another build of the
     product library).  The product path always runs ``LIB_PATH``."""
@@ -199,7 +230,8 @@ ABI_CALLS = [0]          # compute calls made through the C ABI by this process 
 
 
 def _failure(what, rc):
-    return AdainHipError(f"{what} failed ({rc}): {lib().adain_last_error().decode()}")
+    text = gif_decode_lib().adain_gif_decode_last_error() if what in GIF_DECODE_SIGNATURES else lib().adain_last_error()
+    return AdainHipError(f"{what} failed ({rc}): {text.decode()}")
 
 
 def _check(rc, what):
@@ -302,7 +334,7 @@ def free_workspaces():
 def _launch(name, *args):
     """``lib().<name>(*args, stream)`` on the device that is current, with its current stream: counted in ABI_CALLS,
     AdainHipError("<name> failed (<rc>): <last error>") on a non-zero return."""
-    _check(getattr(lib(), name)(*args, _stream()), name)
+    _check(_entry(name)(*args, _stream()), name)
 
 
 def call(name, device, *args):
@@ -959,7 +991,7 @@ JPEG_DEFAULT_QUALITY = 75          # Pillow's
 def _size_query(name, *dims, results=1):
     """The size query ``name`` of the C ABI on the integers ``dims`` -> its size_t results.  Host only.  AdainHipError for a refused shape."""
     out = [_c_size_t() for _ in range(results)]
-    rc = getattr(lib(), name)(*(int(d) for d in dims), *(ctypes.byref(o) for o in out))
+    rc = _entry(name)(*(int(d) for d in dims), *(ctypes.byref(o) for o in out))
     if rc != 0:
         raise _failure(name, rc)
     return [o.value for o in out]
@@ -1974,6 +2006,91 @@ def png_decode_rgb_file(path, device):
     the file is not one the device decoder takes (not a .png name, refused by png_file.parse, a non-zero status): the caller then
     decodes it with PIL as before.  Reads the record once (waits for the call)."""
     return _decode_rgb_file(PNG_INPUT, path, device)
+
+
+# .gif (adain_gif_decode_u8, include/adain_gif_decode.h)
+GIFD_ROW_WORDS = 8                      # ADAIN_GIFD_ROW_WORDS
+GIFD_STATUS = {0: "ok", 1: "the data ends before the rectangle is full", 2: "a code above the next free entry", 3: "a first code behind a CLEAR that is no root",
+               4: "the end code before the rectangle is full", 5: "a row of the frame table that leaves the screen, the blob or its plane"}
+
+
+def gif_decode_sizes(n, H, W, max_frame_pixels):
+    """workspace_bytes of adain_gif_decode_u8_bytes: the index planes of an n-frame clip on an H x W screen whose largest rectangle has
+    ``max_frame_pixels`` pixels.  Host only.  AdainHipError for a refused shape."""
+    return _size_query("adain_gif_decode_u8_bytes", n, H, W, max_frame_pixels)[0]
+
+
+def gif_decode_table(clip, lead=0):
+    """A ``gif_file.GifClip`` -> (the frame table as n x 8 Python ints, the blob ``bytes``): every colour table once, then every frame's
+    data; ``lead`` bytes of zeros in front of all of it (the far-batch test's).  The rows: include/adain_gif_decode.h."""
+    parts, at, tables, rows = [bytes(lead)] if lead else [], lead, {}, []
+    for f in clip.frames:
+        if f.table not in tables:
+            tables[f.table] = at
+            parts.append(f.table)
+            at += len(f.table)
+    for f in clip.frames:
+        flags = f.code_size | int(f.interlace) << 8 | f.disposal << 16 | ((0 if f.transparent is None else f.transparent + 1) << 32)
+        rows.append([at, len(f.data), f.left | f.top << 16 | f.w << 32 | f.h << 48, flags, tables[f.table], len(f.table) // 3, clip.background, 0])
+        parts.append(f.data)
+        at += len(f.data)
+    return rows, b"".join(parts)
+
+
+_gif_decode_lock = threading.Lock()
+
+
+def gif_decode_clip(clip, device):
+    """A ``gif_file.GifClip`` -> (frames uint8 [n,H,W,3], record int32 [n,2]: status and codes per frame), both on ``device``.  One upload
+    - the frame table and the blob in one buffer - and one call of adain_gif_decode_u8; nothing comes back and nothing waits.  With any
+    status not 0 the frames are unspecified.  The one door to the C call (looked up when called: tests count the decodes here)."""
+    import numpy as np
+
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise AdainHipError("gif_decode_clip: expected a GPU device (the device decoder has no CPU form)")
+    rows, blob = gif_decode_table(clip)
+    n = len(rows)
+    table = np.asarray(rows, dtype=np.uint64).tobytes()
+    up = torch.frombuffer(bytearray(table + blob + b"\0"), dtype=torch.uint8).to(device)
+    with _gif_decode_lock, scratch(device, "gif_decode", gif_decode_sizes, n, clip.h, clip.w, max(f.w * f.h for f in clip.frames)) as ws:
+        out = torch.empty((n, clip.h, clip.w, 3), dtype=torch.uint8, device=device)
+        record = torch.empty((n, 2), dtype=torch.int32, device=device)
+        _launch("adain_gif_decode_u8", up.data_ptr() + len(table), len(blob), up.data_ptr(), n, clip.h, clip.w, out.data_ptr(), record.data_ptr(), ws.data_ptr(),
+                ws.numel())
+    return out, record
+
+
+def gif_decode_u8(data, device=None, report=None):
+    """The bytes of an animated GIF -> (frames uint8 [n,H,W,3] on the device, ``gif_file.GifInfo(durations, loop, size)``): per frame the
+    array ``np.asarray(f.convert("RGB"))`` of Pillow's ``ImageSequence.Iterator``.  What gif_file.parse takes is decoded and composed on
+    the device (adain_gif_decode_u8: one upload, one call, the record read once); a file it refuses, and a clip with any frame whose
+    status comes back non-zero, is decoded whole by Pillow on the host and uploaded - Pillow's pixels, or Pillow's exception.  ``report``
+    (a list): one entry, "device" or "host: <why>", and the LZW codes the device read."""
+    from . import gif_file
+
+    data = bytes(data)
+    device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+    why, codes, frames, info = None, 0, None, None
+    try:
+        clip = gif_file.parse(data)
+    except gif_file.UnsupportedGif as e:
+        why = str(e)
+    else:
+        frames, record = gif_decode_clip(clip, device)
+        rec = record.cpu().tolist()                      # the one read of the record: waits for the call
+        codes = sum(c for _, c in rec)
+        bad = [(k, s) for k, (s, _) in enumerate(rec) if s != 0]
+        if bad:
+            why, frames = f"frame {bad[0][0]}: {GIFD_STATUS.get(bad[0][1], bad[0][1])} (status {bad[0][1]})", None
+        else:
+            info = clip.info
+    if frames is None:
+        pixels, info = gif_file.pil_clip(data)
+        frames = torch.from_numpy(pixels).to(device)
+    if report is not None:
+        report[:] = [{"path": "device" if why is None else "host: " + why, "codes": codes}]
+    return frames, info
 
 
 def nhwc_to_nchw(x):

@@ -377,3 +377,44 @@ def apply_style_transfer_multi_ada(content_dir, style_dir, output_dir, flow_meth
         return _run_clip(content_dir, [os.path.join(style_dir, s) for s in style_images], output_dir, flow_method, alpha, target_resolution,
                          cancel_flag, offset, prominence, engine, vgg_str, decoder_str, depth_maps, group, preserve_color, int(crossfade_frames),
                          intermediate_jpeg, outputs, _gif_request(gif_path, gif_fps, gif_palette, gif_method))
+
+
+def gif_to_frames(gif_path, output_dir, ext=".png", routes=None):
+    """The frames of the animated GIF ``gif_path`` as ``frame_0000<ext>``, ... in ``output_dir``: the counterpart of the reference's
+    ``video_to_frames`` (video/utils.py:24-42, cv2's VideoCapture) for the one clip container this package reads itself - the directory
+    ``apply_style_transfer_ada`` wants.  With a GPU the clip is decoded there (``gif_file.read_gif``) and the files are written through a
+    ``jobs.FileSink`` with ``routes`` (an ``rt.OutputRoutes``: ``png_on_device`` / ``jpeg_on_device`` files are encoded on the device);
+    without one Pillow reads and writes.  Returns the clip's ``gif_file.GifInfo``."""
+    from . import jobs
+
+    os.makedirs(output_dir, exist_ok=True)
+    frames, info = gif_file.read_gif(gif_path)
+    paths = [os.path.join(str(output_dir), f"frame_{i:04d}{ext}") for i in range(len(frames))]
+    if not isinstance(frames, torch.Tensor):
+        for frame, path in zip(frames, paths):
+            Image.fromarray(frame).save(path)
+        return info
+    sink = jobs.FileSink(frames.device, routes=rt.OutputRoutes() if routes is None else routes)
+    try:
+        step = max(1, (32 << 20) // (frames.shape[1] * frames.shape[2] * 3))
+        for i in range(0, len(paths), step):
+            sink.write(frames[i:i + step], paths[i:i + step])
+    finally:
+        sink.close()
+    return info
+
+
+def stylize_gif(gif_in, style, gif_out, **keywords):
+    """Stylise an animated GIF: its frames are extracted into a temporary directory (``gif_to_frames``), run through
+    ``apply_style_transfer_ada`` - ``apply_style_transfer_multi_ada`` when ``style`` is a directory - with ``gif_path=gif_out``, and the
+    stylised frames come back as one GIF at the clip's own pace (``gif_fps`` from ``gif_file.clip_fps`` unless one is given).  ``keywords``:
+    those of the function that runs, ``output_dir`` too (default: a second temporary directory).  Returns ``gif_out``."""
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as work:
+        frames_dir, output_dir = os.path.join(work, "frames"), keywords.pop("output_dir", os.path.join(work, "stylised"))
+        info = gif_to_frames(gif_in, frames_dir)
+        keywords.setdefault("gif_fps", gif_file.clip_fps(info))
+        run = apply_style_transfer_multi_ada if os.path.isdir(str(style)) else apply_style_transfer_ada
+        run(frames_dir, str(style), output_dir, gif_path=str(gif_out), **keywords)
+    return gif_out
